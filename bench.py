@@ -11,6 +11,12 @@ image tower forward (no backward is needed: CoOp has no visual prompts, SURVEY ย
 backward over all 100 class prompts, cosine logits, cross-entropy, prompt-gradient all-reduce, SGD update.
 Weak scaling: every rank processes its own 256 images; no data-path collective except the 32 KB gradient
 all-reduce.  Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the K steps and prints the line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+Everything else the line can carry -- CPU baselines, the trim-to-EOT rate, per-kernel / roofline figures, the serialized-tower
+pass, all-reduce timing, clock and power, the BASELINE configs[2..4] passes -- runs only with `--full`.
+`--dump-outputs DIR` writes what the last timed step handed its caller (loss, accuracy, every prompt parameter after the update
+and its gradient) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -227,6 +233,31 @@ def run_secondary_configs(dtype):
     return out, round(time.perf_counter() - t_all, 1)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, summary, prompt_learner):
+    """What one `MVLPT.forward_backward` hands its caller, from the last timed step: the loss summary, and the prompt
+    parameters the step updated with the gradients it computed (`.grad` views of the flat buffer).  fp32 / fp64 .npy files."""
+    import numpy as np
+
+    def host(x):
+        a = (x.detach().cpu() if torch.is_tensor(x) else torch.tensor(x)).numpy()
+        return a.astype(a.dtype if a.dtype == np.float64 else np.float32)
+
+    arrays = {k: host(v) for k, v in summary.items()}
+    for name, p in prompt_learner.named_parameters():
+        arrays["param." + name] = host(p)
+        if p.grad is not None:
+            arrays["grad." + name] = host(p.grad)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def _respawn_under_torchrun(n):
     """`python bench.py --gpus N` without a launcher: start N ranks ourselves (one process per GPU, RCCL), as the
     reference gets its replicas from one process (nn.DataParallel, trainers/mvlpt.py:877-880)."""
@@ -237,8 +268,9 @@ def _respawn_under_torchrun(n):
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    import subprocess
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def main():
@@ -272,7 +304,15 @@ def main():
     ap.add_argument("--no-secondary", action="store_true", help="skip the short passes of BASELINE configs[2..4] behind the headline run")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--all-kernel-timing", action="store_true", help="bracket every kernel class with marker events (slower)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: CPU baselines, trim-to-EOT pass, per-kernel timing / roofline, "
+                         "serialized-tower pass, all-reduce timing, clock sampling, BASELINE configs[2..4] (the --no-* flags above "
+                         "switch single legs off again); without it a run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (loss, accuracy, prompt parameters after the update, their gradients) "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
+    full = args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         _respawn_under_torchrun(args.gpus)
@@ -310,6 +350,7 @@ def main():
         n_vpt = 8 if args.method == "vpt" else 4
     cfg.TRAINER.MVLPT.COOP.N_CTX, cfg.TRAINER.MVLPT.VPT.N_CTX = n_ctx, n_vpt
     cfg.SEED = 1
+    torch.manual_seed(cfg.SEED)      # the prompt initialisation draws from the global generator (train.py: set_random_seed)
     sd = make_state_dict(arch, seed=1)
     # class prompts: the reference tokenizer's own ids for the BASELINE class lists (mvlpt_amd/data/class_prompts.npz)
     list_name = CP.BY_CLASS_COUNT.get(args.classes)
@@ -348,7 +389,7 @@ def main():
     # the hook below brackets steps W .. W+K-1 with barrier + synchronize on both sides.  Every timed step contains
     # exactly one image tower (the prefetch of the following batch), one text tower forward + backward, the head, the
     # gradient all-reduce and the SGD update; the loop is stopped before step W+K runs.
-    timing = not args.no_kernel_timing
+    timing = (full and not args.no_kernel_timing) or args.all_kernel_timing
     sample_every = 1 if args.all_kernel_timing else 4     # dispatch-timestamp timing costs ~2 us per launch: sample steps
     mark = {}
 
@@ -357,7 +398,7 @@ def main():
         D.barrier()
         torch.cuda.synchronize()
 
-    clk = _ClockSampler() if rank == 0 else None
+    clk = _ClockSampler() if (rank == 0 and full) else None
 
     def hook(i):
         if i == W:
@@ -383,11 +424,13 @@ def main():
     elapsed = mark["t1"] - mark["t0"]
     stats = eng.profile_end() if timing else {}
     elapsed = D.all_reduce_max(elapsed, dev)
+    if args.dump_outputs and rank == 0:      # before any extra pass below moves the prompts on
+        dump_outputs(args.dump_outputs, out, trainer.model.prompt_learner)
     # Reported beside the headline, never AS the headline: the same loop with the causal text tower evaluated only up to
     # max(EOT) (positions after EOT can reach neither a logit nor a gradient; exact, tests/test_hip_model.py::
     # test_trim_to_eot_is_exact).  `value` keeps all L positions, as the reference computes them.
     trim_line = None
-    if n_ctx and not args.trim_eot and not args.cut and not args.no_trim_extra and K >= 8:
+    if full and n_ctx and not args.trim_eot and not args.cut and not args.no_trim_extra and K >= 8:
         trainer.model.trim_text_to_eot = True
         W2, K2 = 4, min(K, 16)
         dm.train_loader_x = _CyclingLoader(dm.train_loader_x.batches, W2 + K2 + 1)
@@ -448,7 +491,7 @@ def main():
         ranks_info = [None] * world
         torch.distributed.all_gather_object(ranks_info, mine)
         flats = [f.flat for f in getattr(trainer, "_flat_grads", {}).values() if f.flat.numel()]
-        if flats and not shared_gpu_debug:
+        if full and flats and not shared_gpu_debug:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             scratch = flats[0].clone()
             for _ in range(3):
@@ -597,7 +640,7 @@ def main():
             line["step_mfma_fraction_executed"] = round((g["flops_executed"] / n_sampled + att) / (elapsed / K) / (MFMA_PEAK_TFLOPS * 1e12), 4)
         if trim_line is not None:
             line["text_trimmed_to_eot"] = trim_line
-        if world == 1 and not args.no_cpu_baseline and args.method == "coop" and pre is not None:
+        if full and world == 1 and not args.no_cpu_baseline and args.method == "coop" and pre is not None:
             line["cpu_baseline"] = cpu_baseline_images_per_sec(arch, sd, args.classes, L_text, n_ctx, pre)
             if is_headline:
                 # BASELINE.md ยง3(a): configs[0], the reference's own CPU-runnable case (ViT-B/32, B = 32, same class list)
@@ -605,7 +648,7 @@ def main():
                 a32 = _A["ViT-B/32"]
                 line["cpu_baseline_cfg1"] = cpu_baseline_images_per_sec(a32, _mk(a32, seed=cfg.SEED), args.classes, L_text, n_ctx, pre, B_cpu=32)
                 line["cpu_baseline_cfg1"]["config"] = "BASELINE configs[0]: CoOp ViT-B/32, 100 classes, n_ctx=16, L=77, full batch of 32"
-        if is_headline and world == 1 and not args.no_secondary and args.grad_precision == "split_grad":
+        if full and is_headline and world == 1 and not args.no_secondary and args.grad_precision == "split_grad":
             # this process is done with the GPU (everything above is synchronised): the children have it to themselves
             del trainer, dm
             torch.cuda.empty_cache()

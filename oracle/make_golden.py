@@ -6,6 +6,7 @@ Run in the build container only (needs /root/reference; see oracle/ref_shim.py):
     python oracle/make_golden.py tiny       # only the tiny-arch ones
     python oracle/make_golden.py vptopt     # VPT.PROJECT / VPT.DROPOUT cases (tiny arch)
     python oracle/make_golden.py ctxinit    # COOP.CTX_INIT (context initialised from words) cases (tiny arch)
+    python oracle/make_golden.py standalone # data the CPU tests would otherwise re-read from the reference tree
 
 The reference's `trainers.mvlpt.CustomCLIP` (trainers/mvlpt.py:517-583) is instantiated on a
 `clip.model.CLIP` (clip/model.py:239-322) whose weights come from OUR deterministic generator
@@ -448,6 +449,42 @@ def make_preprocess():
     print("[golden] preprocess:", len(specs), "cases,", os.path.getsize(os.path.join(OUT, "preprocess.npz")) // 1024, "KiB")
 
 
+def bpe_digest(tok):
+    """sha256 of the merge list (rank order) and of the vocabulary (id order) a BPETokenizer was built from."""
+    import hashlib
+    merges = sorted(tok.rank, key=tok.rank.get)
+    h = lambda lines: hashlib.sha256("\n".join(lines).encode("utf-8")).hexdigest()
+    return {"n_merges": len(merges), "n_vocab": len(tok.decoder), "merges_sha256": h(" ".join(m) for m in merges),
+            "vocab_sha256": h(tok.decoder)}
+
+
+def make_standalone(mv, cm):
+    """What the CPU tests used to re-read from the reference tree at run time, recorded as data: the digest of the tokenizer
+    CLIP's own vocabulary file yields, the class NAME tables behind mvlpt_amd/data/class_prompts.npz, and the parameter /
+    state_dict keys (with shapes) of the reference prompt learner a checkpoint of ours must load into."""
+    import json
+    from mvlpt_amd.tokenizer import BPETokenizer
+    from mvlpt_amd.weights import ARCHS, make_state_dict
+    from oracle.make_token_tables import class_lists
+    d = bpe_digest(BPETokenizer(os.path.join(ref_shim.REFERENCE_ROOT, "clip", "bpe_simple_vocab_16e6.txt.gz")))
+    d["source"] = "clip/bpe_simple_vocab_16e6.txt.gz of the reference, read by mvlpt_amd.tokenizer.BPETokenizer"
+    with open(os.path.join(OUT, "clip_bpe_digest.json"), "w") as f:
+        json.dump(d, f, indent=1)
+    with open(os.path.join(OUT, "class_lists.json"), "w") as f:
+        json.dump({k: [[t, list(cl)] for t, cl in v] for k, v in class_lists().items()}, f)
+    arch = ARCHS["tiny"]
+    ref_clip = cm.CLIP(*arch.ctor_args())
+    ref_clip.load_state_dict(make_state_dict(arch, 1, include_token_embedding=True))
+    cfg = ref_shim.make_cfg(input_size=32, coop_n_ctx=4, vpt_n_ctx=2, vpt_deep=True, project_dim=64)
+    pl = mv.CustomCLIP(cfg, ["dog", "grand piano", "sea horse", "airplane", "great white shark"], ref_clip.float(), dm=None).prompt_learner
+    rec = {"config": "tiny CLIP, COOP.N_CTX 4, VPT.N_CTX 2 deep, PROJECT_DIM 64, 5 classes (tests/test_train_step_fixture.py)",
+           "state_dict": {k: list(v.shape) for k, v in pl.state_dict().items()},
+           "parameters": [n for n, _ in pl.named_parameters()]}
+    with open(os.path.join(OUT, "ref_prompt_learner.json"), "w") as f:
+        json.dump(rec, f, indent=1)
+    print("[golden] standalone: clip_bpe_digest.json, class_lists.json, ref_prompt_learner.json")
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     if set(sys.argv[1:]) == {"preprocess"}:
@@ -475,6 +512,8 @@ def main():
         make_vpt_options(mv, cm)
     if "ctxinit" in which:
         make_ctx_init(mv, cm)
+    if "standalone" in which:
+        make_standalone(mv, cm)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 """bench.py prints ONE JSON line with the driver's contract fields (GPU box: the HIP path is the thing measured).
 
-Small K / W so that the test stays under a minute; the CPU baseline leg is exercised once on a tiny sample by the default
-`python bench.py` run, not here."""
+Small K / W so that the test stays under a minute; the CPU baseline leg is exercised once on a tiny sample by
+`python bench.py --full`, not here.  A plain run (no `--full`) carries the headline fields only."""
 import json
 import os
 import subprocess
@@ -14,8 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "4", "--no-cpu-baseline"],
-                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "4", "--no-cpu-baseline",
+                          "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -64,6 +64,34 @@ def test_bench_line_contract():
         assert 0.0 < k["frac"] < 1.0 and k["avg_us"] > 0
         if k["name"].startswith("image "):
             assert k["M"] == 256 * 197 and abs(k["launches_per_step"] - (11 if k["name"] != "image QKV" else 12)) <= 1
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """Without --full the line holds the headline only; --dump-outputs writes the last timed step's outputs as fp32 .npy, and a
+    second run with the same arguments (same seeded inputs) reproduces them."""
+    import numpy as np
+    for d in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                              "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["steps"] == 3 and j["warmup"] == 2 and j["ms_per_step"] > 0 and j["unit"] == "images/sec" and j["dtype"] == "fp16"
+    assert abs(j["value"] - 256 * 1e3 / j["ms_per_step"]) / j["value"] < 1e-3
+    for k in ("roofline", "cpu_baseline", "secondary_configs", "text_trimmed_to_eot", "clock"):
+        assert k not in j, k
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert {"loss.npy", "acc.npy", "param.ctx.npy", "grad.ctx.npy"} <= set(files), files
+    assert sorted(os.listdir(tmp_path / "a")) == files
+    arrays = {f: np.load(tmp_path / "b" / f) for f in files}
+    for f, a in arrays.items():
+        np.testing.assert_allclose(np.load(tmp_path / "a" / f), a, rtol=0, atol=1e-5 * max(float(np.abs(a).max()), 1e-30), err_msg=f)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["param.ctx.npy"].shape == (16, 512) and float(np.abs(arrays["grad.ctx.npy"]).max()) > 0
+    assert abs(float(arrays["loss.npy"]) - j["config"]["loss"]) < 1e-4
 
 
 @pytest.mark.gpu

@@ -5,7 +5,7 @@
 #   bash tools/r03_profile.sh      -> gpurun_out/r03/   (copy what is to be judged into profiles/)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r03; mkdir -p $O
-timeout 600 python bench.py --steps 30 --warmup 8 2>$O/bench.err | tail -1 > $O/bench_line.json
+timeout 600 python bench.py --full --steps 30 --warmup 8 2>$O/bench.err | tail -1 > $O/bench_line.json
 bash tools/r03_profile_headline.sh r03 > /dev/null 2>&1
 bash tools/r03_profile_cfgs.sh r03 > /dev/null 2>&1
 pmc() {   # name, bench args...

@@ -8,6 +8,6 @@ for rep in 1 2; do for k in 0 1; do
   MVLPT_ATTN32_PERSIST=$k timeout 300 python tools/attn_bench.py 2>&1 | grep -A5 "split-precision" >> $O/attn.txt
 done; done
 for k in 0 1; do
-  MVLPT_ATTN32_PERSIST=$k timeout 600 python bench.py --method vpt --classes 1000 --steps 10 --warmup 3 --no-cpu-baseline --no-trim-extra 2>>$O/bench.err | tail -1 | python -c "import json,sys; l=json.loads(sys.stdin.read()); print('cfg3 persist $k', l['value'], l['ms_per_step'], l['config']['loss'])" >> $O/bench.txt 2>&1
+  MVLPT_ATTN32_PERSIST=$k timeout 600 python bench.py --full --method vpt --classes 1000 --steps 10 --warmup 3 --no-cpu-baseline --no-trim-extra 2>>$O/bench.err | tail -1 | python -c "import json,sys; l=json.loads(sys.stdin.read()); print('cfg3 persist $k', l['value'], l['ms_per_step'], l['config']['loss'])" >> $O/bench.txt 2>&1
 done
 cat $O/pytest.txt $O/attn.txt $O/bench.txt; tail -3 $O/bench.err

@@ -9,6 +9,6 @@ for rep in 1 2; do for v in old new; do
   echo "== $v" >> $O/attn.txt
   MVLPT_HIP_LIB=$L timeout 300 python tools/attn_bench.py 2>&1 | grep -v amdgpu.ids >> $O/attn.txt
   MVLPT_HIP_LIB=$L timeout 300 python tools/image_bench.py 2>&1 | grep -v amdgpu.ids >> $O/attn.txt
-  MVLPT_HIP_LIB=$L timeout 300 python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-trim-extra 2>>$O/bench.err | tail -1 | python -c "import json,sys; l=json.loads(sys.stdin.read()); print('$v', l['value'], l['ms_per_step'], l['step_mfma_fraction'], l['config']['loss'])" >> $O/bench.txt 2>&1
+  MVLPT_HIP_LIB=$L timeout 300 python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-trim-extra 2>>$O/bench.err | tail -1 | python -c "import json,sys; l=json.loads(sys.stdin.read()); print('$v', l['value'], l['ms_per_step'], l['step_mfma_fraction'], l['config']['loss'])" >> $O/bench.txt 2>&1
 done; done
 cat $O/pytest.txt $O/attn.txt $O/bench.txt; tail -3 $O/bench.err

@@ -9,9 +9,9 @@ for rep in 1 2; do for k in 0 1; do
   MVLPT_GEMM_PCP=$k timeout 300 python tools/gemm_mixed_bench.py "7700,2048,512,5;7700,2048,512,6;7700,1536,512,7;50432,768,768,2" 2>&1 | grep -v amdgpu.ids >> $O/gemm.txt
   MVLPT_GEMM_PCP=$k timeout 300 python tools/text_bench.py 2>&1 | grep -v amdgpu.ids >> $O/gemm.txt
   MVLPT_GEMM_PCP=$k timeout 300 python tools/image_bench.py 2>&1 | grep -v amdgpu.ids >> $O/gemm.txt
-  MVLPT_GEMM_PCP=$k timeout 300 python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-trim-extra 2>>$O/bench.err | tail -1 | python -c "import json,sys; l=json.loads(sys.stdin.read()); print('pcp $k', l['value'], l['ms_per_step'], l['step_mfma_fraction'], l['config']['loss'])" >> $O/bench.txt 2>&1
+  MVLPT_GEMM_PCP=$k timeout 300 python bench.py --full --steps 40 --warmup 8 --no-cpu-baseline --no-trim-extra 2>>$O/bench.err | tail -1 | python -c "import json,sys; l=json.loads(sys.stdin.read()); print('pcp $k', l['value'], l['ms_per_step'], l['step_mfma_fraction'], l['config']['loss'])" >> $O/bench.txt 2>&1
 done; done
 for k in 0 1; do
-  MVLPT_GEMM_PCP=$k timeout 600 python bench.py --method vpt --classes 1000 --steps 10 --warmup 3 --no-cpu-baseline --no-trim-extra 2>>$O/bench.err | tail -1 | python -c "import json,sys; l=json.loads(sys.stdin.read()); print('cfg3 pcp $k', l['value'], l['ms_per_step'], l['config']['loss'])" >> $O/bench.txt 2>&1
+  MVLPT_GEMM_PCP=$k timeout 600 python bench.py --full --method vpt --classes 1000 --steps 10 --warmup 3 --no-cpu-baseline --no-trim-extra 2>>$O/bench.err | tail -1 | python -c "import json,sys; l=json.loads(sys.stdin.read()); print('cfg3 pcp $k', l['value'], l['ms_per_step'], l['config']['loss'])" >> $O/bench.txt 2>&1
 done
 cat $O/pytest.txt $O/gemm.txt $O/bench.txt; tail -3 $O/bench.err

@@ -4,7 +4,7 @@
 # counters), config sweep, parity reports.    bash tools/r04_profile.sh [tag]   -> gpurun_out/<tag>/   (copy what is judged into profiles/)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 TAG=${1:-r04}; O=gpurun_out/$TAG; mkdir -p $O
-timeout 900 python bench.py --steps 40 --warmup 8 2>$O/bench.err | tail -1 > $O/bench_line.json
+timeout 900 python bench.py --full --steps 40 --warmup 8 2>$O/bench.err | tail -1 > $O/bench_line.json
 bash tools/r03_profile_headline.sh $TAG > /dev/null 2>&1
 pmc() {   # name, bench args...
   local name=$1; shift

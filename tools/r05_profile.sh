@@ -5,7 +5,7 @@
 #   bash tools/r05_profile.sh [tag]   -> gpurun_out/<tag>/   (copy what is judged into profiles/)
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 TAG=${1:-r05}; O=gpurun_out/$TAG; mkdir -p $O
-timeout 900 python bench.py 2>$O/bench.err | tail -1 > $O/bench_line.json
+timeout 900 python bench.py --full 2>$O/bench.err | tail -1 > $O/bench_line.json
 bash tools/r03_profile_headline.sh $TAG > /dev/null 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats -d $O/trace_img -o t -- python tools/image_bench.py > /dev/null 2>&1
 python tools/rocpd_summary.py $(ls $O/trace_img/*.db | head -1) > $O/image_tower_kernels.md

@@ -15,8 +15,8 @@ run MVLPT_ATTN_PERSIST=1 python tools/image_bench.py
 run MVLPT_HIP_LIB=$V/libvar_nopk.so MVLPT_ATTN_PERSIST=1 python tools/image_bench.py
 done
 for i in 1 2; do
-run MVLPT_ATTN_PERSIST=0 python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-secondary --no-trim-extra
-run MVLPT_ATTN_PERSIST=1 python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-secondary --no-trim-extra
-run MVLPT_HIP_LIB=$V/libvar_nopk.so MVLPT_ATTN_PERSIST=1 python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-secondary --no-trim-extra
+run MVLPT_ATTN_PERSIST=0 python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-secondary --no-trim-extra
+run MVLPT_ATTN_PERSIST=1 python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-secondary --no-trim-extra
+run MVLPT_HIP_LIB=$V/libvar_nopk.so MVLPT_ATTN_PERSIST=1 python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-secondary --no-trim-extra
 done
 run MVLPT_HIP_LIB=$V/libvar_nopk.so MVLPT_RESID_PACKED=1 ITERS=6000 python tools/tower_stage_probe.py 256

@@ -11,10 +11,10 @@ echo "## pytest" >> $O
 timeout 1800 python -m pytest tests -m gpu -q 2>&1 | tail -12 >> $O
 run MVLPT_RESID_PACKED=1 ITERS=20000 python tools/tower_determinism_probe.py 256 -1 3
 for i in 1 2; do
-run MVLPT_RESID_PACKED=0 python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-secondary --no-trim-extra
-run MVLPT_RESID_PACKED=1 python bench.py --steps 30 --warmup 8 --no-cpu-baseline --no-secondary --no-trim-extra
+run MVLPT_RESID_PACKED=0 python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-secondary --no-trim-extra
+run MVLPT_RESID_PACKED=1 python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --no-secondary --no-trim-extra
 run MVLPT_RESID_PACKED=0 python tools/image_bench.py
 run MVLPT_RESID_PACKED=1 python tools/image_bench.py
-run MVLPT_LN_FOLD_MIN_ROWS=4096 python bench.py --arch ViT-B/32 --batch 32 --steps 40 --warmup 10 --no-cpu-baseline --no-secondary --no-trim-extra
-run MVLPT_LN_FOLD_MIN_ROWS=1024 python bench.py --arch ViT-B/32 --batch 32 --steps 40 --warmup 10 --no-cpu-baseline --no-secondary --no-trim-extra
+run MVLPT_LN_FOLD_MIN_ROWS=4096 python bench.py --full --arch ViT-B/32 --batch 32 --steps 40 --warmup 10 --no-cpu-baseline --no-secondary --no-trim-extra
+run MVLPT_LN_FOLD_MIN_ROWS=1024 python bench.py --full --arch ViT-B/32 --batch 32 --steps 40 --warmup 10 --no-cpu-baseline --no-secondary --no-trim-extra
 done

@@ -18,5 +18,6 @@ probe libvar_scl.so none 20
 probe libvar_scv.so none 20
 probe libmvlpt_hip.so text
 echo "## bench" >> $O
-python bench.py --steps 20 --warmup 5 --no-secondary > gpurun_out/r06_bench_start.json 2>> $O
-tail -c 1500 gpurun_out/r06_bench_start.json >> $O
+B=$(dirname $O)/r06_bench_start.json
+python bench.py --full --steps 20 --warmup 5 --no-secondary > $B 2>> $O
+tail -c 1500 $B >> $O

@@ -134,8 +134,18 @@ int mvlpt_image_bwd(void* handle, const float* dfeat, float* dvpt, float* dvpt_d
 int mvlpt_text_fwd(void* handle, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
                    const int32_t* layout, const int32_t* eot, int C, int L, float* feat_out, int save_for_bwd,
                    mvlpt_stream_t stream);
-/* dfeat [C,embed] fp32 -> dctx (same shape as ctx).  Must follow text_fwd(save_for_bwd=1). */
+/* CoCoOp: PromptLearner.forward + one TextEncoder call per image (trainers/cocoop.py:123-161, 48-59, 184-189) as ONE tower over
+ * G * C sequences.  Sequence s = g * C + c is class c's prefix / suffix / layout row / eot with context block g of ctx [G,n_ctx,dt] fp32
+ * (ctx + meta_net(image g), one block per image); prefix [C,1,dt], suffix [C,L-1-n_ctx,dt], layout int32 [C,L] and eot int32 [C] are
+ * the class tables of mvlpt_text_fwd, read G times (never copied).  feat_out [G*C,embed] fp32, row s = (image g, class c). */
+int mvlpt_text_fwd_grouped(void* handle, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                           const int32_t* eot, int G, int C, int L, float* feat_out, int save_for_bwd, mvlpt_stream_t stream);
+/* dfeat [C,embed] fp32 -> dctx (same shape as ctx).  Must follow text_fwd(save_for_bwd=1).  After text_fwd_grouped(save_for_bwd=1):
+ * dfeat [G*C,embed] -> dctx [G,n_ctx,dt], dctx[g] = sum over the C classes of image g (fixed order: deterministic). */
 int mvlpt_text_bwd(void* handle, const float* dfeat, float* dctx, mvlpt_stream_t stream);
+/* *out = bytes of text-tower workspace a text_fwd / text_fwd_grouped over C_total sequences of length L reserves (the ctx-position
+ * table counted for the largest n_ctx, L - 2); the workspace only grows, so a caller that chunks G keeps its peak under a budget. */
+int mvlpt_text_workspace_bytes(void* handle, int C_total, int L, int save_for_bwd, int64_t* out);
 
 /* Cosine logits (trainers/mvlpt.py:550-554) with the multiplicative per-task mask (:573-581):
  * logits[b,c] = exp(logit_scale) * <img_b/|img_b|, txt_c/|txt_c|> * [task_lo[b] <= c < task_hi[b]].
@@ -145,6 +155,12 @@ int mvlpt_logits_fwd(void* handle, const float* img_feat, const float* txt_feat,
 /* dlogits [B,C] -> dimg [B,embed], dtxt [C,embed] (either may be NULL).  Uses the features of the last
  * mvlpt_logits_fwd call on this handle. */
 int mvlpt_logits_bwd(void* handle, const float* dlogits, float* dimg, float* dtxt, mvlpt_stream_t stream);
+/* CoCoOp's head (trainers/cocoop.py:184-189): logits[g,c] = logit_scale_exp * <img_g/|img_g|, txt_{gC+c}/|txt_{gC+c}|>,
+ * img [G,embed], txt [G*C,embed] (rows of mvlpt_text_fwd_grouped), logits [G,C]; fp32 throughout.  The backward gives dtxt [G*C,embed]
+ * only (the image tower is frozen and carries no prompts there).  Uses the features of the last logits_grouped_fwd on this handle. */
+int mvlpt_logits_grouped_fwd(void* handle, const float* img, const float* txt, float logit_scale_exp, int G, int C, float* logits,
+                             mvlpt_stream_t stream);
+int mvlpt_logits_grouped_bwd(void* handle, const float* dlogits, float* dtxt, mvlpt_stream_t stream);
 
 /* F.cross_entropy(output, label) with mean reduction (trainers/mvlpt.py:931) and its gradient.
  * labels: int64 [B] (MVLPT_LABEL_INT64) or fp32 probabilities [B,C] (MVLPT_LABEL_PROB_F32, rows already
@@ -237,6 +253,12 @@ int mvlpt_op_attention_fwd(int dtype, const void* qkv, void* out, float* lse, in
 int mvlpt_op_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int N, int L, int H, int causal, mvlpt_stream_t stream);
 int mvlpt_op_cast(int dtype, const float* in, void* out, int64_t n, mvlpt_stream_t stream);
+/* the grouped (CoCoOp) glue of mvlpt_text_fwd_grouped / text_bwd: x [G*C, L, d] fp32 = assembled prompts + pos [L, d] (layout entries
+ * must address rows inside prefix / suffix / ctx); dctx [G, n_ctx, d] = sum over c of dx [G*C, L, d] at ctx_pos int32 [C, n_ctx] */
+int mvlpt_op_assemble_prompts_grouped(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                                      const float* pos, float* x, int G, int C, int L, int d, mvlpt_stream_t stream);
+int mvlpt_op_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, int G, int C, int L, int d, int n_ctx, float* dctx,
+                                     mvlpt_stream_t stream);
 
 /* ---- input pipeline ("next" row f3 of the scope table) -------------------------------------------------------
  * Replaces the per-image CPU transform the reference runs in DataLoader workers: Dassl `build_transform` with

@@ -70,6 +70,8 @@ def get_cfg_default() -> CfgNode:
         # the method has no visual prompts (TrainerX.run_epoch reads the loader one batch ahead)
         STEP_PIPELINING=True,
     )
+    # trainers/cocoop.py's own keys (train.py:125-128), read by mvlpt_amd.cocoop (--trainer CoCoOp)
+    cfg.TRAINER.COCOOP = CN(N_CTX=16, CTX_INIT="", PREC="fp16")
     cfg.DATASET = CN(NAME="synthetic", COOP=True, MULTITASK=False, MULTITASK_LABEL_PERTASK=False,
                      MULTITASK_EVALKEY="average", NUM_SHOTS=16)
     return cfg

@@ -182,12 +182,14 @@ struct Engine {
   void *uc16 = nullptr, *duc16 = nullptr, *dxc16 = nullptr, *dOc16 = nullptr;
   // text fwd extras
   int tC = 0, tL = 0, t_nctx = 0, t_per_class = 0; int32_t* eot_rows = nullptr; int32_t* ctx_pos = nullptr;
+  int t_groups = 0, t_gC = 0;   // grouped forward (mvlpt_text_fwd_grouped): tC = t_groups * t_gC sequences; 0 = not grouped
   // EOT-only last text block (compact [C,·] rows; the text-side twin of the CLS-only last image block)
   bool t_eot_last = false; float *txc32 = nullptr, *txm32 = nullptr, *txo32 = nullptr, *tdxc32 = nullptr, *tdhc32 = nullptr;
   void *tac16 = nullptr, *thc16 = nullptr, *tgc16 = nullptr, *tuc16 = nullptr, *tduc16 = nullptr, *tdxc16 = nullptr, *tdOc16 = nullptr;
   float* eot32 = nullptr; float* deot32 = nullptr;
   // head state
   int hB = 0, hC = 0; float h_scale = 0.f; const int32_t *h_lo = nullptr, *h_hi = nullptr;
+  bool h_grouped = false;        // the last head forward was mvlpt_logits_grouped_fwd (hB = G groups of hC classes)
   float *imn = nullptr, *txn = nullptr, *inorm = nullptr, *tnorm = nullptr;
   // profiling
   // mvlpt_debug_checksums: one 64-bit fingerprint per intermediate of the image tower (debug; off by default)
@@ -1091,13 +1093,22 @@ int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, 
 }
 
 // ------------------------------------------------------------------------------------------------ text tower
-int mvlpt_text_fwd(void* h, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
-                   const int32_t* layout, const int32_t* eot, int C, int L, float* feat_out, int save_for_bwd,
-                   mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !prefix || !suffix || !layout || !eot || !feat_out || C <= 0 || L <= 0)
-    return fail(E, MVLPT_ERR_ARG, "text_fwd: null/invalid argument");
-  if (int rc = mvlpt_frozen_ready(h)) return rc;
+// Bytes of txt_ws a text forward over C sequences of length L reserves (mvlpt_text_fwd, mvlpt_text_fwd_grouped,
+// mvlpt_text_workspace_bytes).  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of the ctx_pos table.
+static size_t text_ws_bytes(Engine* E, int C, int L, bool save, bool exact, size_t ctx_rows) {
+  const int dtw = E->arch.text_width;
+  const size_t X = exact ? 2 : 1;
+  return tower_bytes(E->txt, C, L, save, exact) + 7 * align256((size_t)C * dtw * 4) + 4 * align256((size_t)C * dtw * 2 * X) +
+         3 * align256((size_t)C * dtw * 8 * X) + align256((size_t)C * 4) + align256(ctx_rows * 4) + 4096;
+}
+static bool text_exact(const Engine* E) { return E->prec_mode == MVLPT_PREC_SPLIT_ALL || E->prec_mode == MVLPT_PREC_SPLIT_GRAD; }
+
+// The text tower over C sequences.  G == 0: mvlpt_text_fwd (prefix / suffix / layout / eot [C, ...], ctx [n_ctx, d] or CSC [C, n_ctx, d]);
+// G > 0: mvlpt_text_fwd_grouped, C = G * Cg sequences s = g * Cg + c from the [Cg, ...] class tables and ctx [G, n_ctx, d].
+static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
+                         const int32_t* layout, const int32_t* eot, int G, int Cg, int C, int L, float* feat_out, int save_for_bwd,
+                         mvlpt_stream_t stream) {
+  if (int rc = mvlpt_frozen_ready(E)) return rc;
   if ((n_ctx > 0) != (ctx != nullptr) || n_ctx < 0 || n_ctx > L - 2) return fail(E, MVLPT_ERR_ARG, "text_fwd: ctx pointer and n_ctx disagree");
   const MvlptArch& A = E->arch;
   if (L > A.context_length) return fail(E, MVLPT_ERR_ARG, "text_fwd: L exceeds context_length");
@@ -1110,10 +1121,9 @@ int mvlpt_text_fwd(void* h, const float* prefix, const float* suffix, const floa
   // image-side gradient through the logits; inference (model_inference, trainers/mvlpt.py:986-987): they are computed once
   // per parameter version, not per batch, so the extra matrix time does not recur — and single operands leave 5-9e-4 on the text
   // features, which put the inference logits of 5 of the 18 reference fixtures outside 1e-3 (profiles/r04_inference_parity.txt)
-  const bool exact = E->prec_mode == MVLPT_PREC_SPLIT_ALL || E->prec_mode == MVLPT_PREC_SPLIT_GRAD;
+  const bool exact = text_exact(E);
   const size_t X = exact ? 2 : 1;
-  size_t need = tower_bytes(E->txt, C, L, save, exact) + 7 * align256((size_t)C * dtw * 4) + 4 * align256((size_t)C * dtw * 2 * X) +
-                3 * align256((size_t)C * dtw * 8 * X) + align256((size_t)C * 4) + align256((size_t)C * (n_ctx > 0 ? n_ctx : 1) * 4) + 4096;
+  size_t need = text_ws_bytes(E, C, L, save, exact, (size_t)C * (n_ctx > 0 ? n_ctx : 1));
   E->ts.valid = false;
   HIPCHK(E, E->txt_ws.reserve(need));
   Bump bp; bp.base = (char*)E->txt_ws.p; bp.cap = E->txt_ws.cap;
@@ -1130,12 +1140,19 @@ int mvlpt_text_fwd(void* h, const float* prefix, const float* suffix, const floa
   carve_tower(bp, E->txt, E->ts, C, L, save, true, exact, split_kind(E));
   TowerState& st = E->ts;
   E->tC = C; E->tL = L; E->t_nctx = n_ctx; E->t_per_class = ctx_per_class;
+  E->t_groups = G; E->t_gC = G > 0 ? Cg : 0;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)C * L * dtw * 12.0);
-    HIPCHK(E, launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, E->tpos, st.x[0], C, L, dtw, s));
-    HIPCHK(E, launch_eot_rows(eot, E->eot_rows, C, L, s));
-    if (save && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, C, L, n_ctx, s)); }
+    if (G > 0) {
+      HIPCHK(E, launch_assemble_prompts_grouped(prefix, suffix, ctx, n_ctx, layout, E->tpos, st.x[0], G, Cg, L, dtw, s));
+      HIPCHK(E, launch_eot_rows_grouped(eot, E->eot_rows, G, Cg, L, s));
+      if (save) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
+    } else {
+      HIPCHK(E, launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, E->tpos, st.x[0], C, L, dtw, s));
+      HIPCHK(E, launch_eot_rows(eot, E->eot_rows, C, L, s));
+      if (save && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, C, L, n_ctx, s));
+    } }
   bool ln1_ready = false;
   for (int l = 0; l + 1 < E->txt.layers; ++l) {
     bool produced = false;
@@ -1175,6 +1192,34 @@ int mvlpt_text_fwd(void* h, const float* prefix, const float* suffix, const floa
   }
   { ProfScope ps(E, s, PC_HEAD, 2.0 * C * e * dtw, 4.0 * ((double)C * dtw + (double)e * dtw + (double)C * e));
     HIPCHK(E, launch_sgemm_bt(E->eot32, E->tproj_t, feat_out, C, e, dtw, nullptr, s)); }
+  return 0;
+}
+
+int mvlpt_text_fwd(void* h, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
+                   const int32_t* layout, const int32_t* eot, int C, int L, float* feat_out, int save_for_bwd,
+                   mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !prefix || !suffix || !layout || !eot || !feat_out || C <= 0 || L <= 0)
+    return fail(E, MVLPT_ERR_ARG, "text_fwd: null/invalid argument");
+  return text_fwd_impl(E, prefix, suffix, ctx, ctx_per_class, n_ctx, layout, eot, 0, C, C, L, feat_out, save_for_bwd, stream);
+}
+
+// PromptLearner.forward + the per-image TextEncoder calls of CoCoOp (trainers/cocoop.py:123-161, 48-59): one tower over G * C sequences
+int mvlpt_text_fwd_grouped(void* h, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                           const int32_t* eot, int G, int C, int L, float* feat_out, int save_for_bwd, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !prefix || !suffix || !ctx || !layout || !eot || !feat_out || G <= 0 || C <= 0 || L <= 0 || n_ctx <= 0)
+    return fail(E, MVLPT_ERR_ARG, "text_fwd_grouped: null/invalid argument");
+  if (G > 65535 || (int64_t)G * C > (int64_t)INT32_MAX / (L > 0 ? L : 1))
+    return fail(E, MVLPT_ERR_ARG, "text_fwd_grouped: too many sequences");
+  return text_fwd_impl(E, prefix, suffix, ctx, 0, n_ctx, layout, eot, G, C, G * C, L, feat_out, save_for_bwd, stream);
+}
+
+int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, int64_t* out) {
+  Engine* E = (Engine*)h;
+  if (!E || !out || C_total <= 0 || L <= 2) return fail(E, MVLPT_ERR_ARG, "text_workspace_bytes: null/invalid argument");
+  // the ctx_pos table is sized for the largest n_ctx a forward accepts (L - 2): at most C_total * L * 4 bytes over the exact figure
+  *out = (int64_t)text_ws_bytes(E, C_total, L, save_for_bwd != 0, text_exact(E), (size_t)C_total * (L - 2));
   return 0;
 }
 
@@ -1224,7 +1269,10 @@ int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stre
   for (int l = st.layers - 2; l >= 0; --l)
     if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)C * E->t_nctx * dtw * 4.0);
-    HIPCHK(E, launch_gather_ctx_grad(st.dx32, E->ctx_pos, C, L, dtw, E->t_nctx, E->t_per_class, dctx, st.scale_dev, s)); }
+    if (E->t_groups > 0)
+      HIPCHK(E, launch_gather_ctx_grad_grouped(st.dx32, E->ctx_pos, E->t_groups, E->t_gC, L, dtw, E->t_nctx, dctx, st.scale_dev, s));
+    else
+      HIPCHK(E, launch_gather_ctx_grad(st.dx32, E->ctx_pos, C, L, dtw, E->t_nctx, E->t_per_class, dctx, st.scale_dev, s)); }
   return 0;
 }
 
@@ -1247,7 +1295,7 @@ int mvlpt_logits_fwd(void* h, const float* img, const float* txt, float scale, c
     return fail(E, MVLPT_ERR_ARG, "logits_fwd: null/invalid argument");
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
-  E->hB = 0;
+  E->hB = 0; E->h_grouped = false;
   if (int rc = head_reserve(E, B, C)) return rc;
   ProfScope ps(E, s, PC_HEAD, 2.0 * B * C * e, 4.0 * ((double)B * e + (double)C * e + (double)B * C));
   HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, B, e, s));
@@ -1260,11 +1308,39 @@ int mvlpt_logits_fwd(void* h, const float* img, const float* txt, float scale, c
 int mvlpt_logits_bwd(void* h, const float* dlogits, float* dimg, float* dtxt, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !dlogits) return fail(E, MVLPT_ERR_ARG, "logits_bwd: null argument");
-  if (E->hB <= 0 || !E->imn) return fail(E, MVLPT_ERR_STATE, "logits_bwd: call logits_fwd first");
+  if (E->hB <= 0 || !E->imn || E->h_grouped) return fail(E, MVLPT_ERR_STATE, "logits_bwd: call logits_fwd first");
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
   ProfScope ps(E, s, PC_HEAD, 4.0 * E->hB * E->hC * e, 4.0 * ((double)E->hB * e + (double)E->hC * e + (double)E->hB * E->hC) * 2);
   HIPCHK(E, launch_logits_bwd(dlogits, E->imn, E->txn, E->inorm, E->tnorm, E->h_scale, E->h_lo, E->h_hi, dimg, dtxt, E->hB, E->hC, e, s));
+  return 0;
+}
+
+// CoCoOp's head (trainers/cocoop.py:184-189): image g against its own C text features txt[g*C .. g*C + C)
+int mvlpt_logits_grouped_fwd(void* h, const float* img, const float* txt, float scale, int G, int C, float* logits, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !img || !txt || !logits || G <= 0 || C <= 0 || G > 65535 || (int64_t)G * C > INT32_MAX)
+    return fail(E, MVLPT_ERR_ARG, "logits_grouped_fwd: null/invalid argument");
+  hipStream_t s = (hipStream_t)stream;
+  const int e = E->arch.embed_dim;
+  E->hB = 0; E->h_grouped = false;
+  if (int rc = head_reserve(E, G, G * C)) return rc;
+  ProfScope ps(E, s, PC_HEAD, 2.0 * G * C * e, 4.0 * ((double)G * e + (double)G * C * e + (double)G * C));
+  HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, G, e, s));
+  HIPCHK(E, launch_normalize_rows(txt, E->txn, E->tnorm, G * C, e, s));
+  HIPCHK(E, launch_logits_grouped(E->imn, E->txn, scale, logits, G, C, e, s));
+  E->hB = G; E->hC = C; E->h_scale = scale; E->h_lo = E->h_hi = nullptr; E->h_grouped = true;
+  return 0;
+}
+
+int mvlpt_logits_grouped_bwd(void* h, const float* dlogits, float* dtxt, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !dlogits || !dtxt) return fail(E, MVLPT_ERR_ARG, "logits_grouped_bwd: null argument");
+  if (E->hB <= 0 || !E->imn || !E->h_grouped) return fail(E, MVLPT_ERR_STATE, "logits_grouped_bwd: call logits_grouped_fwd first");
+  hipStream_t s = (hipStream_t)stream;
+  const int e = E->arch.embed_dim;
+  ProfScope ps(E, s, PC_HEAD, 4.0 * E->hB * E->hC * e, 4.0 * ((double)E->hB * e + 2.0 * E->hB * E->hC * e + (double)E->hB * E->hC));
+  HIPCHK(E, launch_logits_grouped_bwd(dlogits, E->imn, E->txn, E->tnorm, E->h_scale, dtxt, E->hB, E->hC, e, s));
   return 0;
 }
 
@@ -1517,6 +1593,20 @@ int mvlpt_op_attention_bwd(int dtype, const void* qkv, const void* out, const vo
 }
 int mvlpt_op_cast(int dtype, const float* in, void* out, int64_t n, mvlpt_stream_t stream) {
   OPCHK(launch_cast_f32_to16(dtype, in, out, (size_t)n, nullptr, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_assemble_prompts_grouped(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                                      const float* pos, float* x, int G, int C, int L, int d, mvlpt_stream_t stream) {
+  if (!prefix || !suffix || !ctx || !layout || !pos || !x || G <= 0 || C <= 0 || L <= n_ctx + 1 || n_ctx <= 0 || d <= 0) {
+    g_create_err = "op_assemble_prompts_grouped: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_assemble_prompts_grouped(prefix, suffix, ctx, n_ctx, layout, pos, x, G, C, L, d, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, int G, int C, int L, int d, int n_ctx, float* dctx,
+                                     mvlpt_stream_t stream) {
+  if (!dx || !ctx_pos || !dctx || G <= 0 || C <= 0 || L <= 0 || n_ctx <= 0 || d <= 0) {
+    g_create_err = "op_gather_ctx_grad_grouped: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_gather_ctx_grad_grouped(dx, ctx_pos, G, C, L, d, n_ctx, dctx, nullptr, (hipStream_t)stream));
   return 0;
 }
 

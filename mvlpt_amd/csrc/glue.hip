@@ -556,6 +556,47 @@ hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipS
   return hipGetLastError();
 }
 
+// ---- grouped (image-conditioned) prompts: sequence s = g * C + c pairs class c with context block g (trainers/cocoop.py:123-161)
+// x[s,i,:] = (layout[c,i] >= 0 ? fixed tokens of class c : ctx[g, row]) + pos[i]; prefix / suffix / layout stay [C, ...]
+__global__ void assemble_prompts_grouped_kernel(const float* __restrict__ prefix, const float* __restrict__ suffix,
+                                                const float* __restrict__ ctx, int n_ctx, const int32_t* __restrict__ layout,
+                                                const float* __restrict__ pos, float* __restrict__ x, int G, int C, int L, int d) {
+  const int d4 = d / 4;
+  const size_t total = (size_t)G * C * L * d4;
+  const int suf_len = L - 1 - n_ctx;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int c4 = (int)(i % d4);
+    const size_t tok = i / d4;
+    const int pos_i = (int)(tok % L);
+    const size_t seq = tok / L;
+    const int cls = (int)(seq % C), g = (int)(seq / C);
+    const int e = layout[(size_t)cls * L + pos_i];
+    const float* src;
+    if (e == 0) src = prefix + (size_t)cls * d;
+    else if (e > 0) src = suffix + ((size_t)cls * suf_len + (e - 1)) * d;
+    else src = ctx + ((size_t)g * n_ctx + (-e - 1)) * d;
+    *(f32x4*)(x + tok * d + c4 * 4) = *(const f32x4*)(src + c4 * 4) + *(const f32x4*)(pos + (size_t)pos_i * d + c4 * 4);
+  }
+}
+hipError_t launch_assemble_prompts_grouped(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                                           const float* pos, float* x, int G, int C, int L, int d, hipStream_t s) {
+  if (d % 4 || n_ctx <= 0) return hipErrorInvalidValue;
+  const size_t total = (size_t)G * C * L * (d / 4);
+  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  hipLaunchKernelGGL(assemble_prompts_grouped_kernel, dim3(grid), dim3(256), 0, s, prefix, suffix, ctx, n_ctx, layout, pos, x, G, C, L, d);
+  return hipGetLastError();
+}
+// rows[s] = s * L + eot[s % C] for the G * C sequences
+__global__ void eot_rows_grouped_kernel(const int32_t* __restrict__ eot, int32_t* __restrict__ rows, int N, int C, int L) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < N) rows[s] = s * L + eot[s % C];
+}
+hipError_t launch_eot_rows_grouped(const int32_t* eot, int32_t* rows, int G, int C, int L, hipStream_t s) {
+  const int N = G * C;
+  hipLaunchKernelGGL(eot_rows_grouped_kernel, dim3((N + 255) / 256), dim3(256), 0, s, eot, rows, N, C, L);
+  return hipGetLastError();
+}
+
 // generic ctx: dctx[j,:] = inv * sum_c dx[c, pos(c,j), :]  (ctx is expanded over classes: trainers/mvlpt.py:455-456)
 // class-specific (CSC): dctx[c,j,:] = inv * dx[c, pos(c,j), :]
 __global__ void gather_ctx_grad_csc_kernel(const float* __restrict__ dx, const int32_t* __restrict__ ctx_pos, int L, int d,
@@ -600,6 +641,41 @@ hipError_t launch_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C
     hipLaunchKernelGGL(gather_ctx_grad_csc_kernel, dim3((d + 255) / 256, n_ctx, C), dim3(256), 0, s, dx, ctx_pos, L, d, n_ctx, dctx, scale_dev);
   else
     hipLaunchKernelGGL(gather_ctx_grad_kernel, dim3((d + 255) / 256, n_ctx), dim3(1024), 0, s, dx, ctx_pos, C, L, d, n_ctx, dctx, scale_dev);
+  return hipGetLastError();
+}
+// grouped context (one block per image, expanded over the classes: trainers/cocoop.py:150-157):
+// dctx[g,j,:] = inv * sum_c dx[(g*C + c)*L + pos(c,j), :] — gather_ctx_grad_kernel with the group as blockIdx.z (same fixed order)
+__global__ __launch_bounds__(1024) void gather_ctx_grad_grouped_kernel(const float* __restrict__ dx, const int32_t* __restrict__ ctx_pos,
+                                                                       int C, int L, int d, int n_ctx, float* __restrict__ dctx,
+                                                                       const float* scale_dev) {
+  __shared__ f32x4 part[16][64];
+  const int j = blockIdx.y, g = blockIdx.z;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = (blockIdx.x * 64 + lane) * 4;
+  const bool ok = c < d;
+  const float* dxg = dx + (size_t)g * C * L * d;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (ok) {
+#pragma unroll 8
+    for (int cls = wave; cls < C; cls += 16)
+      acc += *(const f32x4*)(dxg + ((size_t)cls * L + ctx_pos[cls * n_ctx + j]) * d + c);
+  }
+  part[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && ok) {
+    f32x4 t = part[0][lane];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) t += part[w][lane];
+    const float inv = scale_dev ? scale_dev[1] : 1.0f;
+    *(f32x4*)(dctx + ((size_t)g * n_ctx + j) * d + c) = t * inv;
+  }
+}
+hipError_t launch_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, int G, int C, int L, int d, int n_ctx, float* dctx,
+                                          const float* scale_dev, hipStream_t s) {
+  if (n_ctx <= 0) return hipSuccess;
+  if (d % 4 || G <= 0 || G > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gather_ctx_grad_grouped_kernel, dim3((d + 255) / 256, n_ctx, G), dim3(1024), 0, s, dx, ctx_pos, C, L, d, n_ctx, dctx,
+                     scale_dev);
   return hipGetLastError();
 }
 
@@ -945,6 +1021,54 @@ hipError_t launch_logits_bwd(const float* dlogits, const float* imn, const float
   if (e > 1024 || e % 8) return hipErrorInvalidValue;
   if (dimg) hipLaunchKernelGGL(logits_bwd_kernel<true>, dim3(B), dim3(512), 0, s, dlogits, imn, txn, inorm, scale, lo, hi, dimg, B, C, e);
   if (dtxt) hipLaunchKernelGGL(logits_bwd_kernel<false>, dim3(C), dim3(512), 0, s, dlogits, imn, txn, tnorm, scale, lo, hi, dtxt, B, C, e);
+  return hipGetLastError();
+}
+
+// grouped head (every image has its own C text features, trainers/cocoop.py:184-189):
+// logits[g,c] = (scale * imn[g,:]) . txn[g*C + c, :]
+__global__ __launch_bounds__(256) void logits_grouped_kernel(const float* __restrict__ imn, const float* __restrict__ txn, float scale,
+                                                             float* __restrict__ logits, int G, int C, int e) {
+  extern __shared__ float simg[];
+  const int g = blockIdx.x;
+  for (int i = threadIdx.x; i < e; i += 256) simg[i] = scale * imn[(size_t)g * e + i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = blockIdx.y * 4 + wave; c < C; c += gridDim.y * 4) {
+    const float* t = txn + ((size_t)g * C + c) * e;
+    float s = 0.f;
+    for (int i = lane; i < e; i += 64) s += simg[i] * t[i];
+    s = wave_sum(s);
+    if (lane == 0) logits[(size_t)g * C + c] = s;
+  }
+}
+hipError_t launch_logits_grouped(const float* imn, const float* txn, float scale, float* logits, int G, int C, int e, hipStream_t s) {
+  if (G <= 0 || G > 65535) return hipErrorInvalidValue;
+  int gy = (C + 3) / 4; gy = gy > 64 ? 64 : gy;
+  hipLaunchKernelGGL(logits_grouped_kernel, dim3(G, gy), dim3(256), e * sizeof(float), s, imn, txn, scale, logits, G, C, e);
+  return hipGetLastError();
+}
+// d txn[s] for s = g*C + c: the only logit that reads text row s is logits[g,c], so with w = scale * dlogits[g,c]
+// d txt[s] = w * (imn[g] - txn[s] <imn[g], txn[s]>) / ||txt[s]||   (normalisation backward).  One wave per text row.
+__global__ __launch_bounds__(256) void logits_grouped_bwd_kernel(const float* __restrict__ dl, const float* __restrict__ imn,
+                                                                 const float* __restrict__ txn, const float* __restrict__ tnorm,
+                                                                 float scale, float* __restrict__ dtxt, int N, int C, int e) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= N) return;
+  const int g = row / C;
+  const float* im = imn + (size_t)g * e;
+  const float* t = txn + (size_t)row * e;
+  float dot = 0.f;
+  for (int i = lane; i < e; i += 64) dot += im[i] * t[i];
+  dot = wave_sum(dot);
+  const float w = scale * dl[row];                  // dlogits [G, C] is row-major: entry (g, c) sits at g*C + c = row
+  const float inv = 1.0f / tnorm[row];
+  for (int i = lane; i < e; i += 64) dtxt[(size_t)row * e + i] = w * (im[i] - t[i] * dot) * inv;
+}
+hipError_t launch_logits_grouped_bwd(const float* dlogits, const float* imn, const float* txn, const float* tnorm, float scale, float* dtxt,
+                                     int G, int C, int e, hipStream_t s) {
+  const int N = G * C;
+  hipLaunchKernelGGL(logits_grouped_bwd_kernel, dim3((N + 3) / 4), dim3(256), 0, s, dlogits, imn, txn, tnorm, scale, dtxt, N, C, e);
   return hipGetLastError();
 }
 

@@ -234,6 +234,11 @@ hipError_t launch_assemble_prompts(const float* prefix, const float* suffix, con
                                    const int32_t* layout, const float* pos, float* x, int C, int L, int d, hipStream_t s);
 hipError_t launch_build_ctx_pos(const int32_t* layout, int32_t* ctx_pos, int C, int L, int n_ctx, hipStream_t s);
 hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipStream_t s);
+// grouped prompts (trainers/cocoop.py:123-161): sequence s = g*C + c = class c's prefix / suffix / layout row + context block g of
+// ctx [G, n_ctx, d]; eot rows s*L + eot[s % C]
+hipError_t launch_assemble_prompts_grouped(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                                           const float* pos, float* x, int G, int C, int L, int d, hipStream_t s);
+hipError_t launch_eot_rows_grouped(const int32_t* eot, int32_t* rows, int G, int C, int L, hipStream_t s);
 // dst[r] = src[idx[r]] (scatter = 0) or dst[idx[r]] = src[r] (scatter = 1); row_bytes % 16 == 0
 hipError_t launch_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, hipStream_t s);
 // rows of row_bytes (multiple of 16) from src + r*src_pitch to dst + r*dst_pitch
@@ -244,6 +249,9 @@ hipError_t launch_reduce_prompt_rows(int dtype, float* dx32, void* dx16, int B, 
 // dctx (generic) [n,d] = inv_scale * sum_c dx[c, ctx_pos[c,j], :]  or (per class) [C,n,d]
 hipError_t launch_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C, int L, int d, int n_ctx, int per_class,
                                   float* dctx, const float* scale_dev, hipStream_t s);
+// dctx (grouped) [G,n,d] = inv_scale * sum_c dx[g*C + c, ctx_pos[c,j], :]  (ctx_pos per class, [C, n])
+hipError_t launch_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, int G, int C, int L, int d, int n_ctx, float* dctx,
+                                          const float* scale_dev, hipStream_t s);
 // scale_dev[0] = 2^k with amax(|v|)*2^k ~ target ; scale_dev[1] = 1/scale_dev[0]
 hipError_t launch_grad_scale(const float* v, size_t n, float target, float* scale_dev, hipStream_t s);
 hipError_t launch_zero(void* p, size_t bytes, hipStream_t s);
@@ -268,5 +276,9 @@ hipError_t launch_cross_entropy(const float* logits, const void* labels, int lab
 hipError_t launch_logits_bwd(const float* dlogits, const float* imn, const float* txn, const float* inorm, const float* tnorm,
                              float scale, const int32_t* lo, const int32_t* hi, float* dimg, float* dtxt,
                              int B, int C, int e, hipStream_t s);
+// grouped head: logits[g,c] = scale * imn[g] . txn[g*C + c];  backward: dtxt [G*C, e] only (the image side is frozen)
+hipError_t launch_logits_grouped(const float* imn, const float* txn, float scale, float* logits, int G, int C, int e, hipStream_t s);
+hipError_t launch_logits_grouped_bwd(const float* dlogits, const float* imn, const float* txn, const float* tnorm, float scale, float* dtxt,
+                                     int G, int C, int e, hipStream_t s);
 
 }  // namespace mvlpt

@@ -226,6 +226,33 @@ class Engine:
         return feat
 
     @_on_device
+    def text_fwd_grouped(self, prefix: torch.Tensor, suffix: torch.Tensor, ctx: torch.Tensor, layout: torch.Tensor,
+                         eot: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
+        """CoCoOp's text side (mvlpt_text_fwd_grouped): ctx [G, n_ctx, dt], one context block per image, against the
+        [C, ...] class tables -> features [G*C, e], row g*C + c = (image g, class c).  A following text_bwd returns [G, n_ctx, dt]."""
+        prefix = _req(prefix, torch.float32, "token_prefix")
+        suffix = _req(suffix, torch.float32, "token_suffix")
+        layout = _req(layout, torch.int32, "layout")
+        eot = _req(eot, torch.int32, "eot")
+        ctx = _req(ctx, torch.float32, "ctx")
+        if ctx.dim() != 3:
+            raise ValueError("grouped ctx must be [G, n_ctx, ctx_dim]")
+        Cn, L = layout.shape
+        G, n_ctx = ctx.shape[0], ctx.shape[1]
+        feat = torch.empty(G * Cn, self.arch.embed_dim, device=prefix.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_text_fwd_grouped(self.h, _ptr(prefix), _ptr(suffix), _ptr(ctx), n_ctx, _ptr(layout), _ptr(eot),
+                                              G, Cn, L, _ptr(feat), int(save_for_bwd), _stream()), self.h, "text_fwd_grouped")
+        self._txt_state = (tuple(ctx.shape), layout, eot) if save_for_bwd else None
+        return feat
+
+    def text_workspace_bytes(self, n_seq: int, L: int, save_for_bwd: bool) -> int:
+        """Text-tower workspace a forward over `n_seq` sequences of length L reserves (mvlpt_text_workspace_bytes)."""
+        out = C.c_int64()
+        _lib.check(lib.mvlpt_text_workspace_bytes(self.h, int(n_seq), int(L), int(save_for_bwd), C.byref(out)), self.h,
+                   "text_workspace_bytes")
+        return int(out.value)
+
+    @_on_device
     def text_bwd(self, dfeat: torch.Tensor) -> torch.Tensor:
         if self._txt_state is None or self._txt_state[0] is None:
             raise RuntimeError("text_bwd without text_fwd(save_for_bwd=True) with context tokens")
@@ -260,6 +287,32 @@ class Engine:
         dtxt = torch.empty(Cn, e, device=dlogits.device, dtype=torch.float32) if need_txt else None
         _lib.check(lib.mvlpt_logits_bwd(self.h, _ptr(dlogits), _ptr(dimg), _ptr(dtxt), _stream()), self.h, "logits_bwd")
         return dimg, dtxt
+
+    @_on_device
+    def logits_grouped_fwd(self, img_feat, txt_feat, logit_scale_exp: float) -> torch.Tensor:
+        """CoCoOp's head (mvlpt_logits_grouped_fwd): img [G, e] against its own rows of txt [G*C, e] -> logits [G, C]."""
+        img_feat = _req(img_feat, torch.float32, "img_feat")
+        txt_feat = _req(txt_feat, torch.float32, "txt_feat")
+        G = img_feat.shape[0]
+        if txt_feat.shape[0] % G:
+            raise ValueError(f"grouped head: {txt_feat.shape[0]} text rows are not a multiple of {G} images")
+        Cn = txt_feat.shape[0] // G
+        logits = torch.empty(G, Cn, device=img_feat.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_logits_grouped_fwd(self.h, _ptr(img_feat), _ptr(txt_feat), float(logit_scale_exp), G, Cn, _ptr(logits),
+                                                _stream()), self.h, "logits_grouped_fwd")
+        self._head_state = (None, None, G, Cn)
+        return logits
+
+    @_on_device
+    def logits_grouped_bwd(self, dlogits) -> torch.Tensor:
+        """d txt [G*C, e] of the last logits_grouped_fwd (the image side carries no gradient)."""
+        if self._head_state is None:
+            raise RuntimeError("logits_grouped_bwd without logits_grouped_fwd")
+        _, _, G, Cn = self._head_state
+        dlogits = _req(dlogits, torch.float32, "dlogits")
+        dtxt = torch.empty(G * Cn, self.arch.embed_dim, device=dlogits.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_logits_grouped_bwd(self.h, _ptr(dlogits), _ptr(dtxt), _stream()), self.h, "logits_grouped_bwd")
+        return dtxt
 
     @_on_device
     def cross_entropy(self, logits, label, need_grad: bool = True):
@@ -372,6 +425,28 @@ def join_mixed(p: torch.Tensor) -> torch.Tensor:
     d = p.shape[1] // 2
     lo8 = p[:, d:d + d // 2].contiguous().view(torch.uint8).view(torch.float8_e5m2).float()
     return p[:, :d].float() + lo8 * 2.0 ** -LO8_EXP[p.dtype]
+
+
+def op_assemble_prompts_grouped(prefix, suffix, ctx, layout, pos) -> torch.Tensor:
+    """Grouped prompt assembly (CoCoOp): [G*C, L, d] = class rows of prefix [C,1,d] / suffix [C,L-1-n,d] / layout [C,L] with context
+    block g of ctx [G,n,d], plus pos [L,d] (the first L rows are read)."""
+    C_, L = layout.shape
+    G, n, d = ctx.shape
+    x = torch.empty(G * C_, L, d, device=ctx.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_assemble_prompts_grouped(_ptr(prefix.contiguous()), _ptr(suffix.contiguous()), _ptr(ctx.contiguous()), n,
+                                                     _ptr(layout.to(torch.int32).contiguous()), _ptr(pos.contiguous()), _ptr(x),
+                                                     G, C_, L, d, _stream()), None, "op_assemble_prompts_grouped")
+    return x
+
+
+def op_gather_ctx_grad_grouped(dx, ctx_pos, G: int) -> torch.Tensor:
+    """dctx [G, n, d] = sum over the classes of dx [G*C, L, d] at the positions ctx_pos [C, n]."""
+    N, L, d = dx.shape
+    C_, n = ctx_pos.shape
+    dctx = torch.empty(G, n, d, device=dx.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_gather_ctx_grad_grouped(_ptr(dx.contiguous()), _ptr(ctx_pos.to(torch.int32).contiguous()), G, C_, L, d, n,
+                                                    _ptr(dctx), _stream()), None, "op_gather_ctx_grad_grouped")
+    return dctx
 
 
 def op_cast_mixed(x32: torch.Tensor, dtype) -> torch.Tensor:

@@ -9,7 +9,8 @@ as in the reference.  The towers do NOT run on PyTorch ops: `CustomCLIP.forward`
 tiny UPT projection (forward_mvlpt_proj, ≤52 tokens × width 128, trainable weights) stays on torch autograd.
 
 Deviations (documented in DESIGN.md): prompt parameters are kept in fp32 even when PREC == "fp16" (fp32 master
-copies; the reference keeps fp16 parameters and has no loss scaling); CoCoOp (COCOOP.N_CTX != 0) is out of scope.
+copies; the reference keeps fp16 parameters and has no loss scaling); CoCoOp inside MVLPT (MVLPT.COCOOP.N_CTX != 0) is out of
+scope — trainers/cocoop.py's own CoCoOp lives in mvlpt_amd/cocoop.py.
 """
 from __future__ import annotations
 

@@ -690,31 +690,18 @@ static int nkt_for(int L) {
   return t < 2 ? 2 : t;
 }
 
-// MVLPT_ATTN_STREAM: 0 = resident kernels only, 1 = streaming kernels always, unset = by sequence length
-static int stream_mode() {
-  static const int m = [] { const char* e = getenv("MVLPT_ATTN_STREAM"); return e ? atoi(e) : 2; }();
-  return m;
-}
-static bool use_stream(int L, bool bwd) {
-  const int m = stream_mode();
-  if (m == 0) return false;
-  if (m == 1) return true;
-  (void)bwd;
-  return L > 256;
-}
+// sequences longer than the resident kernels' key tiles take the streaming kernels (attention_stream.hip)
+static bool use_stream(int L) { return L > 256; }
 
 hipError_t launch_attn_fwd(int dtype, const AttnArgs& a_, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
   t_ev_a = ea; t_ev_b = eb;
   // bit 0: non-temporal K/V staging (one workgroup reads them once), bit 1: non-temporal output stores  (+0.5 % on the step)
-  static const int flags = [] { const char* e = getenv("MVLPT_ATTN_FLAGS"); return e ? atoi(e) : 3; }();
   AttnArgs a = a_;
-  a.flags = flags;
+  a.flags = 3;
   if (a.L <= 0 || a.L > attn_max_len() || a.N <= 0) return hipErrorInvalidValue;
-  if (use_stream(a.L, false)) return launch_attn_fwd_stream(dtype, a, s);
-  static const int odd_ok = [] { const char* e = getenv("MVLPT_ATTN_ODD"); return e ? atoi(e) : 1; }();
+  if (use_stream(a.L)) return launch_attn_fwd_stream(dtype, a, s);
   // persistent variant for the headline's shape: 13 key tiles, full sequences, at least two heads per compute unit of the stream
-  static const int persist = [] { const char* e = getenv("MVLPT_ATTN_PERSIST"); return e ? atoi(e) : 1; }();
-  if (persist && !a.causal && a.q_rows <= 0 && (a.L + 15) / 16 == PNT && (dtype == DT_F16 || dtype == DT_BF16)) {
+  if (!a.causal && a.q_rows <= 0 && (a.L + 15) / 16 == PNT && (dtype == DT_F16 || dtype == DT_BF16)) {
     const int total = a.N * a.H, cus = stream_cus(s);
     if (total >= 2 * cus) {
       static bool set = false;
@@ -728,15 +715,15 @@ hipError_t launch_attn_fwd(int dtype, const AttnArgs& a_, hipStream_t s, hipEven
       return hipGetLastError();
     }
   }
-  int nkt = nkt_for(a.L);
-  if (odd_ok && !a.causal && (a.L + 15) / 16 == 13) nkt = 13;
+  // (an odd tile count only for 13 tiles, fwd_n)
+  const int nkt = !a.causal && (a.L + 15) / 16 == 13 ? 13 : nkt_for(a.L);
   if (dtype == DT_F16) return a.causal ? fwd_n<f16, true>(nkt, a, s) : fwd_n<f16, false>(nkt, a, s);
   if (dtype == DT_BF16) return a.causal ? fwd_n<bf16, true>(nkt, a, s) : fwd_n<bf16, false>(nkt, a, s);
   return hipErrorInvalidValue;
 }
 hipError_t launch_attn_bwd(int dtype, const AttnBwdArgs& a, hipStream_t s) {
   if (a.L <= 0 || a.L > attn_max_len() || a.N <= 0) return hipErrorInvalidValue;
-  if (use_stream(a.L, true)) return launch_attn_bwd_stream(dtype, a, s);
+  if (use_stream(a.L)) return launch_attn_bwd_stream(dtype, a, s);
   const int nkt = nkt_for(a.L);
   if (dtype == DT_F16) return a.causal ? bwd_n<f16, true>(nkt, a, s) : bwd_n<f16, false>(nkt, a, s);
   if (dtype == DT_BF16) return a.causal ? bwd_n<bf16, true>(nkt, a, s) : bwd_n<bf16, false>(nkt, a, s);

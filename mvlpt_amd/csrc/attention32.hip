@@ -21,7 +21,6 @@
 // statistics are lane-local plus two shuffles, and those registers are directly the B operand of the second product
 // (P.V, dS.K, P^T.dO, dS^T.Q) — no LDS round trip.  Transposed operands come from the hardware transpose read (frag_vt).
 // Workgroups of one head run on the same XCD (its K/V stay in that L2).
-#include <cstdlib>
 #include "attn_common.h"
 
 namespace mvlpt {
@@ -828,10 +827,8 @@ __global__ __launch_bounds__(RNW * 64) void attn32r_fwd_kernel(Attn32Args a) {
   const int n = blockIdx.y, h = blockIdx.x, L = a.L, d = a.H * 64;
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d;
   const T* base = (const T*)a.qkv_split + (size_t)n * L * ld + h * 64;
-#if !defined(MVLPT_ABL) || MVLPT_ABL != 2      // ablation 2: no staging (compute on whatever LDS holds)
   stage_res<T>(Kh, Kl, base + d, lo, ld, L, wave, lane);
   stage_res<T>(Vh, Vl, base + 2 * d, lo, ld, L, wave, lane);
-#endif
   const int nt = (L + 15) >> 4;
   const int qlim = a.q_rows > 0 ? (a.q_rows < L ? a.q_rows : L) : L;
   v8 Qh[2][2], Ql[2][2];
@@ -854,11 +851,7 @@ __global__ __launch_bounds__(RNW * 64) void attn32r_fwd_kernel(Attn32Args a) {
 #pragma unroll
     for (int kt = 0; kt < RNT; ++kt) {
       S[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if defined(MVLPT_ABL) && MVLPT_ABL == 1       // ablation 1: no arithmetic (staging, own rows, stores only)
-      if (false) {
-#else
       if (kt < nt) {
-#endif
         S[kt] = tile_rows3<T>(Kh, Kl, kt, Qh[o], Ql[o], fr, fg);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -881,9 +874,7 @@ __global__ __launch_bounds__(RNW * 64) void attn32r_fwd_kernel(Attn32Args a) {
     f32x4 O[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) O[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#if !defined(MVLPT_ABL) || MVLPT_ABL != 1
     accum_res3<T>(O, Vh, Vl, S, 0, nt, fr, fg);
-#endif
     if (q < qlim) {
       const float inv = 1.f / sum;
       T* orow = (T*)a.out_split + ((size_t)n * L + q) * (2 * (size_t)d) + h * 64;
@@ -1238,16 +1229,10 @@ __global__ __launch_bounds__(RNW * 64) void attn32p_fwd_kernel(Attn32Args a, int
   }
 }
 
-static bool attn32_resident(int L, int causal) {
-  static const bool on = !(getenv("MVLPT_ATTN32_RESIDENT") && atoi(getenv("MVLPT_ATTN32_RESIDENT")) == 0);
-  return on && !causal && L <= RROWS;
-}
+static bool attn32_resident(int L, int causal) { return !causal && L <= RROWS; }
 
 // workgroup height: 8 waves (256 own rows) stream the other side fewer times; 4 waves (128 rows) pad less.
-// MVLPT_ATTN32_NW = 4 / 8 forces one (experiments)
 static int attn32_nw(int rows) {
-  static const int forced = getenv("MVLPT_ATTN32_NW") ? atoi(getenv("MVLPT_ATTN32_NW")) : 0;
-  if (forced == 4 || forced == 8) return forced;
   const int pad8 = (rows + 255) / 256 * 256, pad4 = (rows + 127) / 128 * 128;
   return pad8 * 8 <= pad4 * 9 ? 8 : 4;          // take 256-row workgroups unless they add more than 1/8 of padding
 }
@@ -1275,8 +1260,7 @@ static hipError_t bwd_x(const Attn32BwdArgs& a, hipStream_t s) {
     set_lds(attn32x_bwd_fused_kernel<T, CAUSAL, NW>, lds_kv); set = lds_kv;
   }
   const dim3 grid(stream_grid(a.N * a.H, nc)), block(NW * 64);
-  static const bool fuse = !(getenv("MVLPT_ATTN32_FUSED_BWD") && atoi(getenv("MVLPT_ATTN32_FUSED_BWD")) == 0);
-  if (nc == 1 && fuse) {
+  if (nc == 1) {      // one column chunk: dQ and dK/dV in one kernel
     hipLaunchKernelGGL((attn32x_bwd_fused_kernel<T, CAUSAL, NW>), grid, block, lds_kv, s, a, lpad);
     return hipGetLastError();
   }
@@ -1295,9 +1279,8 @@ static hipError_t fwd_t(const Attn32Args& a, hipStream_t s) {
   }
   if (attn32_resident(a.L, a.causal)) {
     // persistent variant (next head's K / V land under this head's arithmetic): full-sequence launches with more heads than CUs
-    static const bool persist = !(getenv("MVLPT_ATTN32_PERSIST") && atoi(getenv("MVLPT_ATTN32_PERSIST")) == 0);
     const int total = a.N * a.H, cus = stream_cus(s);
-    if (persist && a.q_rows <= 0 && total >= 2 * cus) {
+    if (a.q_rows <= 0 && total >= 2 * cus) {
       static bool setp = false;
       if (!setp) { set_lds(attn32p_fwd_kernel<T>, RLDS_P); setp = true; }
       hipLaunchKernelGGL((attn32p_fwd_kernel<T>), dim3(cus), dim3(RNW * 64), RLDS_P, s, a, total);

@@ -317,8 +317,7 @@ size_t tower_bytes(const TowerW& W, int N, int L, bool save, bool exact) {
 // row pitch (16-bit elements) of the pair tensors between the two MLP GEMMs ([T, 2 * 4d]: a16, du16; GemmArgs::lda / ldo): rows
 // whose dense pitch is a multiple of 4 KiB get 128 bytes more (every CLIP width: 16 d bytes)
 int wide_pitch(int cols) {
-  static const int on = getenv("MVLPT_WIDE_PITCH") ? atoi(getenv("MVLPT_WIDE_PITCH")) : 1;
-  return on && (4 * cols) % 4096 == 0 ? 2 * cols + 64 : 0;
+  return (4 * cols) % 4096 == 0 ? 2 * cols + 64 : 0;
 }
 void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool save, bool causal, bool exact, int xs) {
   const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1; const int nl = W.layers;

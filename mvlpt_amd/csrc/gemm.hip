@@ -21,9 +21,6 @@
 // Workgroups are remapped so that consecutive tiles (sharing an A panel) run on the same XCD/L2.
 #include <cstdlib>
 #include <hip/hip_ext.h>
-#ifdef MVLPT_GEMM_GLDS_ASM
-#define MVLPT_GLDS_ASM 1      // LDS-DMA of this file from inline asm (common.h)
-#endif
 #include "kernels.h"
 #include "gemm_epi.h"
 
@@ -36,15 +33,6 @@ constexpr int TR_MAX = 2048;
     g.trace[wave * TR_MAX + tr_n++] = ((long long)(p) << 56) | ((long long)__builtin_amdgcn_s_memtime() & 0xffffffffffffffLL); } while (0)
 #else
 #define MVLPT_TR(p) do { } while (0)
-#endif
-#ifndef MVLPT_NS2_MODE
-#define MVLPT_NS2_MODE 1
-#endif
-#ifndef MVLPT_FRAG_DEPTH
-#define MVLPT_FRAG_DEPTH 2
-#endif
-#ifndef MVLPT_NS2_POS
-#define MVLPT_NS2_POS (GROUPS / 2 - 2)   // after the 3rd of 8 MFMA groups; later positions expose the DMA latency (measured)
 #endif
 
 // BM_ x 128 tile, NW waves arranged (NW/2) x 2, NS-deep LDS ring.  Persistent: gridDim.x resident workgroups walk
@@ -216,8 +204,8 @@ __global__ __launch_bounds__(NW * 64, (NW == 2 || BM_ * BN_ / NW > 8192) ? 1 : 2
     // The 16-bit stages and the fp8 stages of a mixed pair run as TWO loops with one body each: with both bodies behind a
     // branch in one loop hipcc stops updating the accumulators in place (the MFMA destinations become fresh registers:
     // +64 VGPRs on a 64x64 wave tile, spills on 128x64).
-    const bool dma_first = (NW == 4) || (NS == 2 && MVLPT_NS2_MODE == 0) || (wave < NW / 2);
-    constexpr bool DMA_MID = NS == 2 && MVLPT_NS2_MODE == 1 && NW != 4;
+    const bool dma_first = (NW == 4) || (wave < NW / 2);
+    constexpr bool DMA_MID = NS == 2 && NW != 4;
     bool issued = false;
     auto stage_pre = [&]() {
       // K-stage f + NS - 1 goes to the slot freed by the last barrier.  An LDS-DMA instruction costs its wave
@@ -226,7 +214,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 2 || BM_ * BN_ / NW > 8192) ? 1 : 2
       // multiplies while its partner is busy with the memory pipe instead of both doing the same thing.
       // With a 2-deep ring the DMA issued in this stage is consumed right after the barrier that ends it, so nobody may
       // issue it at the END of the stage (its whole latency would be exposed): there the younger wave issues in the
-      // MIDDLE of its MFMA groups instead (MVLPT_NS2_MODE 1; 0 = every wave first).
+      // MIDDLE of its MFMA groups instead: after the 3rd of 8 groups (later positions expose the DMA latency, measured).
       issued = false;
       MVLPT_TR(1);
       if (dma_first) { issued = issue(); MVLPT_TR(2); }
@@ -254,10 +242,10 @@ __global__ __launch_bounds__(NW * 64, (NW == 2 || BM_ * BN_ / NW > 8192) ? 1 : 2
       const char* base = smem + slot * STAGE;
       // Register-buffered fragment pipeline: the ds_reads of MFMA group s+1 (two A fragments, plus the four B fragments
       // when the k-step changes) are issued BEFORE the 8 MFMAs of group s, so hipcc's counted lgkmcnt lets the LDS
-      // latency run under the matrix pipe instead of in front of every 8-MFMA burst.  (-DMVLPT_FRAG_DEPTH=3, two groups
-      // of lookahead, measured 5 % SLOWER on long-K shapes: 8192^3 1.23 vs 1.30 PF in the same run.)
+      // latency run under the matrix pipe instead of in front of every 8-MFMA burst.  (Two groups of lookahead were
+      // measured 5 % SLOWER on long-K shapes: 8192^3 1.23 vs 1.30 PF in the same run.)
       constexpr int PAIRS = WMF / 2, GROUPS = 2 * PAIRS;
-      constexpr int DEPTH = MVLPT_FRAG_DEPTH;          // 2 = double-buffered (one group ahead), 3 = two groups ahead
+      constexpr int DEPTH = 2;          // double-buffered: one group ahead
       v8 bfr[2][4], afr[DEPTH][2];
       auto load_b = [&](int ks, v8 (&bf)[4]) {
         const int c = ks ? c1 : c0;
@@ -298,7 +286,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 2 || BM_ * BN_ / NW > 8192) ? 1 : 2
             acc[ai >> 2][ai & 3][j] = mfma16<T>(bfr[ks & 1][j], afr[cur][i], acc[ai >> 2][ai & 3][j]);
           }
         __builtin_amdgcn_sched_barrier(0);
-        if (DMA_MID && sg == (MVLPT_NS2_POS) && !dma_first) { MVLPT_TR(3); issued = issue(); MVLPT_TR(2); }
+        if (DMA_MID && sg == GROUPS / 2 - 2 && !dma_first) { MVLPT_TR(3); issued = issue(); MVLPT_TR(2); }
       }
       stage_post();
     }
@@ -372,233 +360,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 2 || BM_ * BN_ / NW > 8192) ? 1 : 2
     stores_pending = (tm + 1) * BM_ <= M;
   }
 }
-
-#ifdef MVLPT_BREG
-// ---------------------------------------------------------------------------------------------- experiment (debug builds only)
-// "weight fragments straight from L2 into registers, the whole LDS ring for A".  256x256 tile, 8 waves of 128x64
-// as above, but only the A operand travels through LDS (ring of MVLPT_BREG_NS stages of 32 KiB, NS-1 stages ahead); every wave reads
-// the B fragments of ITS 64 columns with global_load_dwordx4 into registers, one K-stage ahead (two buffers of 32 VGPRs, the
-// K loop unrolled by two so that both are statically indexed).  vmcnt retires in order: the wait for B(f+1) at the end of stage f
-// may leave only the A pieces issued behind it in flight.  Dedicated epilogue scratch (a 32-KiB slot does not hold the 36 KiB).
-// tools/build_variant.sh breg -DMVLPT_BREG; MVLPT_GEMM_BREG=1 selects it for the single-operand 256x256 launches.
-#ifndef MVLPT_BREG_NS
-#define MVLPT_BREG_NS 3
-#endif
-#include <type_traits>
-template <typename T, int EPI>
-__global__ __launch_bounds__(512, 1) void gemm_breg_kernel(GemmArgs g) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  using v8 = typename Vec<T>::v8;
-  constexpr int BM_ = 256, BN = 256, NW = 8, NS = MVLPT_BREG_NS, WCN = 4, WMF = 8;
-  constexpr int STAGE = BM_ * BK * 2, A_IT = BM_ / 8 / NW;
-  constexpr bool CAN_FOLD = epi_folds(EPI);
-  char* const scr = smem + NS * STAGE;
-  [[maybe_unused]] char* const xlds = scr + NW * EPI_SCRATCH_PER_WAVE;
-  [[maybe_unused]] char* const xtab = xlds + xlds_tab(g.fold_ntp);
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int M = g.M, N = g.N, K = g.K;
-  const int lda = g.lda ? g.lda : K, ldb = g.ldb ? g.ldb : K;
-  const T* __restrict__ A = (const T*)g.A;
-  const T* __restrict__ Bt = (const T*)g.Bt;
-  const int G = gridDim.x, b = blockIdx.x;
-  const int tilesN = N / BN;
-  const int ntiles = ((M + BM_ - 1) / BM_) * tilesN;
-  const int gq = G >> 3, gr = G & 7, xcd = b & 7;
-  const int b_remap = (xcd < gr ? xcd * (gq + 1) : gr * (gq + 1) + (xcd - gr) * gq) + (b >> 3);
-  auto tile_mn = [&](int t, int& tm, int& tn) { tm = t / tilesN; tn = t - tm * tilesN; };
-  auto tile_of = [&](int round) -> int {
-    const int base = round * G;
-    return base + ((base + G <= ntiles) ? b_remap : b);
-  };
-  const int srow = lane >> 3, scol = ((lane & 7) ^ srow) * 8;
-  // (M % 256 == 0 in this experiment: no edge rows to clamp -> a wave-uniform base per tile + ONE 32-bit lane offset)
-  const char* ap_base;
-  const unsigned ap_voff = (unsigned)(srow * lda + scol) * 2u;
-  auto set_ptrs = [&](int t) {
-    int tm, tn;
-    tile_mn(t, tm, tn);
-    ap_base = (const char*)(A + (size_t)(tm * BM_ + wave * 8) * lda);
-  };
-  const int nk = K / BK;
-  int lround = 0, lt = tile_of(0), lkt = 0, lslot = 0;
-  if (lt >= ntiles) return;
-  set_ptrs(lt);
-  auto issue = [&]() -> bool {
-    if (lt >= ntiles) return false;
-    char* base = smem + lslot * STAGE;
-#pragma unroll
-    for (int i = 0; i < A_IT; ++i) glds16(ap_base + ((size_t)i * NW * 8 * lda + lkt * BK) * 2 + ap_voff, base + (i * NW + wave) * 1024);
-    if constexpr (CAN_FOLD) {
-      if (lkt == nk - 1) {
-        const int cpr = g.fold_ntp >> 1;
-        int ltm, ltn;
-        tile_mn(lt, ltm, ltn);
-        const long first = (long)ltm * BM_ * cpr, last = (long)M * cpr - 1;
-        for (int q0 = wave * 64; q0 < BM_ * cpr; q0 += NW * 64) {
-          long q = first + q0 + lane; q = q < last ? q : last;
-          glds16(g.fold_part + q * 4, xlds + q0 * 16);
-        }
-        const int n0 = ltn * BN + (lane < BN / 4 ? lane : BN / 4 - 1) * 4;
-        if (wave == NW - 1) glds16(g.fold_colsum + n0, xtab + XLDS_COLSUM);
-        if (wave == NW - 2) glds16(g.bias + n0, xtab + XLDS_BIAS);
-      }
-    }
-    lslot = lslot + 1 == NS ? 0 : lslot + 1;
-    if (++lkt == nk) {
-      lkt = 0;
-      lt = tile_of(++lround);
-      if (lt < ntiles) set_ptrs(lt);
-    }
-    return true;
-  };
-  const int wm = wave / WCN, wn = wave % WCN;
-  const int fr = lane & 15, fg = lane >> 4;
-  const int a_off = (wm * (WMF * 16) + fr) * 128;
-  const int c0 = ((0 + fg) ^ (fr & 7)) * 16, c1 = ((4 + fg) ^ (fr & 7)) * 16;
-  // the lane's B rows: fragment j = weight row n0 + wn*64 + j*16 + fr, k-step ks = elements ks*32 + fg*8 .. +7 of the stage
-  // (wave-uniform base in SGPRs + ONE 32-bit lane offset: the saddr form of global_load)
-  const char* bq_base;
-  const unsigned bq_voff = (unsigned)(fr * ldb + fg * 8) * 2u;
-  auto set_bptr = [&](int t) {
-    int tm, tn;
-    tile_mn(t, tm, tn);
-    bq_base = (const char*)(Bt + (size_t)(tn * BN + wn * 64) * ldb);
-  };
-  v8 bq[2][2][4];
-  auto load_bq = [&](v8 (&q)[2][4], int kt) {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        // from inline asm (hipcc's own loads take a 64-bit VGPR address per fragment and spill the fragments): the compiler does not
-        // know the result is pending — every use sits behind the explicit vmcnt wait + barrier that ends the stage
-        const char* bj = bq_base + ((size_t)j * 16 * ldb + kt * BK) * 2;
-        if (ks == 0) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(q[ks][j]) : "v"(bq_voff), "s"(bj) : "memory");
-        else asm volatile("global_load_dwordx4 %0, %1, %2 offset:64" : "=v"(q[ks][j]) : "v"(bq_voff), "s"(bj) : "memory");
-      }
-  };
-  int t = tile_of(0);
-  set_bptr(t);
-  load_bq(bq[0], 0);
-  __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-  for (int i = 0; i < NS - 1; ++i) issue();
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * A_IT) : "memory");
-  __builtin_amdgcn_s_barrier();
-
-  int slot = 0;
-  for (int round = 0; t < ntiles; t = tile_of(++round)) {
-    f32x4 acc[WMF / 4][4][4];
-#pragma unroll
-    for (int i = 0; i < WMF; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i >> 2][i & 3][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const bool dma_first = wave < NW / 2;
-    const char* bq_next;
-    {
-      const int nt = tile_of(round + 1);
-      int tm, tn;
-      tile_mn(nt < ntiles ? nt : t, tm, tn);
-      bq_next = (const char*)(Bt + (size_t)(tn * BN + wn * 64) * ldb);
-    }
-    auto stage = [&](auto curc, int kt) {
-      constexpr int CUR = decltype(curc)::value;
-      // B of the next stage first (so that the A pieces issued behind it may stay in flight across the wait below)
-      // (branch-free: behind the tile's last stage comes stage 0 of the next tile — of this one again when there is none)
-      __builtin_amdgcn_sched_barrier(0);
-      {
-        const bool last = kt + 1 >= nk;
-        bq_base = last ? bq_next : bq_base;
-        load_bq(bq[CUR ^ 1], last ? 0 : kt + 1);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      bool issued = false;
-      if (dma_first) issued = issue();
-      const char* base = smem + slot * STAGE;
-      constexpr int PAIRS = WMF / 2, GROUPS = 2 * PAIRS;
-      v8 afr[2][2];
-      auto load_a2 = [&](int ks, int pair, v8 (&af)[2]) {
-        const int c = ks ? c1 : c0;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) af[i] = *(const v8*)(base + a_off + (pair * 2 + i) * 2048 + c);
-      };
-      load_a2(0, 0, afr[0]);
-#pragma unroll
-      for (int sg = 0; sg < GROUPS; ++sg) {
-        const int ks = sg / PAIRS, pair = sg % PAIRS, cur = sg & 1;
-        __builtin_amdgcn_sched_barrier(0);
-        {
-          const int ai = pair * 2;
-          acc[ai >> 2][ai & 3][0] = mfma16<T>(bq[CUR][ks][0], afr[cur][0], acc[ai >> 2][ai & 3][0]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (sg + 1 < GROUPS) load_a2((sg + 1) / PAIRS, (sg + 1) % PAIRS, afr[(sg + 1) & 1]);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (i == 0 && j == 0) continue;
-            const int ai = pair * 2 + i;
-            acc[ai >> 2][ai & 3][j] = mfma16<T>(bq[CUR][ks][j], afr[cur][i], acc[ai >> 2][ai & 3][j]);
-          }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (!dma_first) issued = issue();
-      // A(f+1) (issued NS-2 stages ago) and B(f+1) (this stage) must have landed; only the A pieces issued behind B may stay
-      if (issued) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_IT) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      slot = slot + 1 == NS ? 0 : slot + 1;
-    };
-    for (int kt = 0; kt < nk; kt += 2) {
-      stage(std::integral_constant<int, 0>{}, kt);
-      stage(std::integral_constant<int, 1>{}, kt + 1);
-    }
-    int tm, tn;
-    tile_mn(t, tm, tn);
-    if constexpr (CAN_FOLD) {
-      if (tid < BM_) fold_build_coef(g, xlds, xtab, tid);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-    }
-#pragma unroll
-    for (int hh = 0; hh < WMF / 4; ++hh)
-      epilogue_store<T, EPI>(g, acc[hh], tm * BM_ + wm * (WMF * 16) + hh * 64, tn * BN + wn * 64, lane,
-                             LinearRows<144>{scr + wave * EPI_SCRATCH_PER_WAVE}, LinearRows<272>{scr + wave * EPI_SCRATCH_PER_WAVE},
-                             FoldCtx{xlds, xtab, wm * (WMF * 16) + hh * 64, wn, WCN, g.ln_split ? 1 : 0});
-    __builtin_amdgcn_s_barrier();
-    if constexpr (epi_ln_producer(EPI)) {
-      if (tid < BM_) {
-        const int row = tm * BM_ + tid;
-        if (row < M) {
-          const float2* p = (const float2*)(xlds + (size_t)tid * WCN * 8);
-#pragma unroll
-          for (int k = 0; k < WCN / 2; ++k)
-            *(float2*)(g.ln_part + ((size_t)row * g.ln_ntp + tn * (WCN / 2) + k) * 2) = float2{p[2 * k].x + p[2 * k + 1].x, p[2 * k].y + p[2 * k + 1].y};
-        }
-      }
-    }
-  }
-}
-template <typename T, int EPI>
-static hipError_t launch_breg(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
-  constexpr int LDS = MVLPT_BREG_NS * 256 * BK * 2 + 8 * EPI_SCRATCH_PER_WAVE;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_breg_kernel<T, EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-  const int lds = LDS + (epi_folds(EPI) ? xlds_bytes(g.fold_ntp) : (epi_ln_producer(EPI) ? XLDS_BYTES : 0));
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  const int cus = stream_cus(s);
-  const int tiles = ((g.M + 255) / 256) * (g.N / 256);
-  hipExtLaunchKernelGGL((gemm_breg_kernel<T, EPI>), dim3(tiles < cus ? tiles : cus), dim3(512), lds, s, ea, eb, 0, g);
-  return hipGetLastError();
-}
-#endif
 
 // ---------------------------------------------------------------------------------------------- phased variant
 // 256x128 tile, 8 waves, 3-deep ring, same data movement as above, but every K-stage is cut into FOUR barrier-
@@ -943,9 +704,8 @@ static hipError_t launch_pc_m(const GemmArgs& g, hipStream_t s, hipEvent_t ea, h
     attr_set = true;
   }
   const int tiles = ((g.M + 127) / 128) * (g.N / 128);
-  static const int xcd_order = getenv("MVLPT_PC_XCD_ORDER") ? atoi(getenv("MVLPT_PC_XCD_ORDER")) : 1;
   GemmArgs q = g;
-  q.xcd_order = xcd_order;
+  q.xcd_order = 1;
   hipExtLaunchKernelGGL((gemm_pc_kernel<T, EPI, MIXED>), dim3(tiles), dim3(512), LDS, s, ea, eb, 0, q);
   return hipGetLastError();
 }
@@ -1229,10 +989,7 @@ static hipError_t launch_geo_m(const GemmArgs& g, int wg_per_cu, hipStream_t s, 
   if (getenv("MVLPT_DBG_CUS")) cus = atoi(getenv("MVLPT_DBG_CUS"));      // CU-scaling measurement, debug builds only
 #endif
   const int tiles = ((g.M + BM_ - 1) / BM_) * ((g.N + BN_ - 1) / BN_);
-  int resident = cus * wg_per_cu;
-  // experiment: at most MVLPT_GEMM_MAXTILES tiles per workgroup (a CU is handed back to the dispatcher that often); 0 = persistent
-  static const int maxtiles = getenv("MVLPT_GEMM_MAXTILES") ? atoi(getenv("MVLPT_GEMM_MAXTILES")) : 0;
-  if (maxtiles > 0 && (tiles + maxtiles - 1) / maxtiles > resident) resident = (tiles + maxtiles - 1) / maxtiles;
+  const int resident = cus * wg_per_cu;      // persistent: at most one round of resident workgroups
   hipExtLaunchKernelGGL((gemm_bt_kernel<T, EPI, BM_, BN_, NW, NS, MIXED>), dim3(tiles < resident ? tiles : resident), dim3(NW * 64), lds, s,
                         ea, eb, 0, g);
   return hipGetLastError();
@@ -1247,24 +1004,6 @@ static hipError_t launch_geo(const GemmArgs& g, int wg_per_cu, hipStream_t s, hi
   return launch_geo_m<T, EPI, BM_, BN_, NW, NS, false>(g, wg_per_cu, s, ea, eb);
 }
 
-// rows [m_lo, m_lo + rows) of the problem as a GEMM of its own (all operands are row-major with leading dimension
-// K or N, so a row range is a contiguous sub-problem)
-template <int EPI>
-static GemmArgs row_slice(const GemmArgs& g, int m_lo, int rows) {
-  GemmArgs r = g;
-  const size_t ok = (size_t)m_lo * (g.lda ? (size_t)g.lda : (size_t)g.K * (g.a_split ? 2 : 1)), on = (size_t)m_lo * g.N;
-  constexpr int BE = epi_base(EPI);
-  constexpr size_t OB = (BE == EPI_RESID32 || BE == EPI_RESID32_LN || BE == EPI_STORE32 || BE == EPI_GELU_SPLIT || BE == EPI_GELUBWD_SPLIT || BE == EPI_STORE_SPLIT) ? 4 : 2;
-  r.A = (const char*)g.A + ok * 2;
-  r.M = rows;
-  r.out = (char*)g.out + on * OB;
-  if (g.out2) r.out2 = (char*)g.out2 + on * 2;
-  if (g.aux) r.aux = (const char*)g.aux + on * 2;
-  if (g.resid) r.resid = g.resid + on;
-  if (g.rp_hi_in) { r.rp_hi_in = (const char*)g.rp_hi_in + on * 2; r.rp_lo_in = g.rp_lo_in + on; r.rp_lo_out = g.rp_lo_out + on; }
-  return r;
-}
-
 template <typename T, int EPI>
 static hipError_t launch_one(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb, int* tile_m, int* tile_n) {
   // (256x256 with FOUR waves of 256x64 — 17 % less LDS-read traffic per FLOP, one wave per SIMD — was measured 17-36 % slower
@@ -1273,9 +1012,7 @@ static hipError_t launch_one(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hi
   // rounds of 256 resident workgroups to amortise its tail; 256x128 needs >= 1.5 rounds; otherwise 128x128.
   const long t128 = (long)((g.M + 255) / 256) * ((g.N + 127) / 128);
   const long t256 = (long)((g.M + 255) / 256) * (g.N / 256);
-  static const int geo = getenv("MVLPT_GEMM_GEO") ? atoi(getenv("MVLPT_GEMM_GEO")) : 2;   // experiment switch (0,1,2)
-  // phased 256x128 variant: measured +3..5 % on long-K GEMMs (MLP down-projection, K = 4d), -4..6 % on K = d
-  static const int phased = getenv("MVLPT_GEMM_PHASED") ? atoi(getenv("MVLPT_GEMM_PHASED")) : 2;   // 0 off, 1 all, 2 long K
+  // phased 256x128 variant: measured +3..5 % on long-K GEMMs (MLP down-projection, K = 4d), -4..6 % on K = d -> long K only
   // 256x256 needs >= 4 rounds of tiles, or >= 2 rounds when K is long (a ragged last round then costs less than the
   // smaller geometry's extra LDS traffic: N = 768, K = 3072: 315 -> 297 us with 2.3 rounds)
   const int Keff = g.a_split == 2 ? g.K + g.K / 2 : (g.a_split ? 2 * g.K : g.K);
@@ -1283,55 +1020,46 @@ static hipError_t launch_one(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hi
   const long cus = stream_cus(s);
   // ... or when the 256x256 tiles fill exactly one round (0.75 .. 1 tile per CU: the text tower's N = 2048 GEMMs at M = 7 700 are
   // 248 tiles): one tile time instead of two rounds of the 256x128 geometry
-  static const int one_round_on = getenv("MVLPT_GEMM_ONE_ROUND") ? atoi(getenv("MVLPT_GEMM_ONE_ROUND")) : 1;
-  static const int one_round_pct = getenv("MVLPT_GEMM_ONE_ROUND_PCT") ? atoi(getenv("MVLPT_GEMM_ONE_ROUND_PCT")) : 75;   // minimum fill of the round
-  const bool one_round = one_round_on && g.N % 256 == 0 && t256 <= cus && 100 * t256 >= one_round_pct * cus;
+  constexpr int ONE_ROUND_PCT = 75;      // minimum fill of the round
+  const bool one_round = g.N % 256 == 0 && t256 <= cus && 100 * t256 >= ONE_ROUND_PCT * cus;
   const bool big = g.N % 256 == 0 && (t256 >= 4 * cus || (t256 >= 2 * cus && Keff >= 2048) || one_round);
   const bool r15 = 2 * t128 >= 3 * cus;      // >= 1.5 rounds of 256x128 tiles
   // (the phased kernel has no fp8 stages: mixed pairs take the plain 256x128 geometry)
   // (nor the LayerNorm-folding fields: folded GEMMs take the plain geometries)
   constexpr bool folded = epi_folds(EPI) || epi_ln_producer(EPI);
-  if (g.a_split != 2 && !folded && r15 && (phased == 1 || (phased == 2 && Keff >= 2048 && !big))) {
+  if (g.a_split != 2 && !folded && r15 && Keff >= 2048 && !big) {
     *tile_m = 256; *tile_n = 128;
     if constexpr (!folded) return ea == (hipEvent_t)-1 ? hipSuccess : launch_phased<T, EPI>(g, s, ea, eb);
   }
-  if (geo >= 2 && big) {
+  if (big) {
     *tile_m = 256; *tile_n = 256;
-#ifdef MVLPT_BREG
-    static const int breg = getenv("MVLPT_GEMM_BREG") ? atoi(getenv("MVLPT_GEMM_BREG")) : 0;
-    if (breg && g.a_split == 0 && g.M % 256 == 0 && g.K % 128 == 0 && g.K / BK >= MVLPT_BREG_NS) return ea == (hipEvent_t)-1 ? hipSuccess : launch_breg<T, EPI>(g, s, ea, eb);
-#endif
     return ea == (hipEvent_t)-1 ? hipSuccess : launch_geo<T, EPI, 256, 256, 8, 2>(g, 1, s, ea, eb);
   }
   // (a folded consumer with 8-slot rows needs 20 KiB behind its ring: the 3-deep 256x128 ring has 16 left -> 256x256 or 128x128)
   const bool wide_fold = epi_folds(EPI) && g.fold_ntp > 6;
-  if (geo >= 2 && wide_fold && r15 && g.N % 256 == 0) {
+  if (wide_fold && r15 && g.N % 256 == 0) {
     *tile_m = 256; *tile_n = 256;
     return ea == (hipEvent_t)-1 ? hipSuccess : launch_geo<T, EPI, 256, 256, 8, 2>(g, 1, s, ea, eb);
   }
-  // 256x128 with data-movement waves (gemm_pcp_kernel): 1 on (default), 0 the self-serving 8-wave kernel
-  static const int pcp = getenv("MVLPT_GEMM_PCP") ? atoi(getenv("MVLPT_GEMM_PCP")) : 1;
-  if (geo >= 1 && r15 && !wide_fold && pcp && (!epi_folds(EPI) || (g.fold_ntp == 4 || g.fold_ntp == 6))) {
+  if (r15 && !wide_fold) {
     *tile_m = 256; *tile_n = 128;
-    return ea == (hipEvent_t)-1 ? hipSuccess : launch_pcp<T, EPI>(g, s, ea, eb);
-  }
-  if (geo >= 1 && r15 && !wide_fold) {
-    *tile_m = 256; *tile_n = 128;
+    // 256x128 with data-movement waves (gemm_pcp_kernel); its movers carry the row partials of 4- and 6-slot rows only, so a
+    // folded consumer with 2-slot rows (d <= 256) takes the self-serving 8-wave kernel
+    if (!epi_folds(EPI) || g.fold_ntp == 4 || g.fold_ntp == 6) return ea == (hipEvent_t)-1 ? hipSuccess : launch_pcp<T, EPI>(g, s, ea, eb);
     return ea == (hipEvent_t)-1 ? hipSuccess : launch_geo<T, EPI, 256, 128, 8, 3>(g, 1, s, ea, eb);
   }
-  // small problems (text tower: M = C*L ~ 7.7k rows) put at most one workgroup on a CU, so nothing hides the
-  // LDS-DMA latency of a 2-deep ring: use a 4-deep ring (128 KiB, three K-stages in flight) instead
-  static const int deep = getenv("MVLPT_GEMM_DEEP") ? atoi(getenv("MVLPT_GEMM_DEEP")) : 1;   // split operands only.  round 1 (single operands): text tower alone -7 %, overlapped step +1.4 %
-  // (its 128 KiB workgroups cannot share a CU with the image-tower kernels they overlap with) -> off.  Round 2 (split operands
-  // double every K of the text tower): tower alone 5.57 -> 5.10 ms, overlapped step 15.22 -> 15.00 ms -> on.
-  const long t_small = (long)((g.M + 127) / 128) * (g.N / 128);
-  // dedicated data-movement waves (gemm_pc_kernel above): split operands 1 (default), every operand kind 2, off 0
-  static const int pcw = getenv("MVLPT_GEMM_PC") ? atoi(getenv("MVLPT_GEMM_PC")) : 1;
-  if (pcw && (g.a_split || pcw >= 2) && pc_takes<EPI>(g, cus)) {
+  // split operands on problems with no more 128x128 tiles than compute units: dedicated data-movement waves (gemm_pc_kernel above)
+  if (g.a_split && pc_takes<EPI>(g, cus)) {
     *tile_m = 128; *tile_n = 128;
     return ea == (hipEvent_t)-1 ? hipSuccess : launch_pc<T, EPI>(g, s, ea, eb);
   }
-  if (deep && g.a_split && t_small <= cus) {
+  // small problems (text tower: M = C*L ~ 7.7k rows) put at most one workgroup on a CU, so nothing hides the
+  // LDS-DMA latency of a 2-deep ring: split operands use a 4-deep ring (128 KiB, three K-stages in flight) instead.
+  // Round 1 (single operands): text tower alone -7 %, overlapped step +1.4 % (its 128 KiB workgroups cannot share a CU with
+  // the image-tower kernels they overlap with).  Round 2 (split operands double every K of the text tower): tower alone
+  // 5.57 -> 5.10 ms, overlapped step 15.22 -> 15.00 ms.
+  const long t_small = (long)((g.M + 127) / 128) * (g.N / 128);
+  if (g.a_split && t_small <= cus) {
     *tile_m = 128; *tile_n = 128;
     return ea == (hipEvent_t)-1 ? hipSuccess : launch_geo<T, EPI, 128, 128, 4, 4>(g, 1, s, ea, eb);
   }
@@ -1341,32 +1069,8 @@ static hipError_t launch_one(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hi
 
 template <typename T, int EPI>
 static hipError_t launch_t(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
-  // Tail splitting (experiment, off by default).  The persistent grid runs rounds of `cus` big tiles; a ragged last round (e.g. 9.23 rounds for the
-  // MLP up-projection) leaves most CUs idle for a full tile time.  When the last round is less than ~70 % full, the
-  // rows of whole rounds go to the big geometry and the remaining rows are a second, small-tile launch (128x128,
-  // two workgroups per CU), which finishes in about half a big-tile time.
-  int bm = 0, bn = 0;
-  (void)launch_one<T, EPI>(g, s, (hipEvent_t)-1, nullptr, &bm, &bn);      // query the geometry only
-  static const int split = getenv("MVLPT_GEMM_TAILSPLIT") ? atoi(getenv("MVLPT_GEMM_TAILSPLIT")) : 0;   // measured: +2 % / -8 % by shape -> off
-  if (split && bm == 256) {
-    const int cus = stream_cus(s);
-    const long tn = g.N / bn, tm = (g.M + bm - 1) / bm, tiles = tm * tn;
-    const long full = tiles / cus;
-    const double frac = (double)(tiles - full * cus) / cus;
-    if (full >= 2 && frac > 0.02 && frac < 0.7) {
-      const long tm_main = full * cus / tn;                     // M tiles that fit the whole rounds
-      const int m_main = (int)(tm_main * bm);
-      if (m_main > 0 && m_main < g.M) {
-        const GemmArgs a = row_slice<EPI>(g, 0, m_main), b = row_slice<EPI>(g, m_main, g.M - m_main);
-        int x, y;
-        hipError_t e = launch_one<T, EPI>(a, s, ea, nullptr, &x, &y);
-        if (e != hipSuccess) return e;
-        return launch_geo<T, EPI, 128, 128, 4, 2>(b, 2, s, nullptr, eb);
-      }
-    }
-  }
-  int x, y;
-  return launch_one<T, EPI>(g, s, ea, eb, &x, &y);
+  int bm, bn;
+  return launch_one<T, EPI>(g, s, ea, eb, &bm, &bn);
 }
 
 template <typename T>
@@ -1429,8 +1133,6 @@ hipError_t launch_gemm(int dtype, int epi, const GemmArgs& g, hipStream_t s, hip
       return hipErrorInvalidValue;
   }
   if ((epi == EPI_GELUBWD || epi == EPI_GELUBWD_SPLIT) && !g.aux) return hipErrorInvalidValue;
-  static const int duo = getenv("MVLPT_GEMM_DUO") ? atoi(getenv("MVLPT_GEMM_DUO")) : 0;
-  if (duo && gemm_duo_takes(epi, g, s)) return launch_gemm_duo(dtype, epi, g, s, ea, eb);
   if (dtype == DT_F16) return launch_epi<f16>(g, epi, s, ea, eb);
   if (dtype == DT_BF16) return launch_epi<bf16>(g, epi, s, ea, eb);
   return hipErrorInvalidValue;

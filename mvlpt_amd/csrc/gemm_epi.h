@@ -1,4 +1,4 @@
-// Epilogues of the MFMA GEMMs (gemm.hip, gemm_duo.hip): bias / QuickGELU / fp32 residual / split-pair outputs and both sides of the
+// Epilogues of the MFMA GEMMs (gemm.hip): bias / QuickGELU / fp32 residual / split-pair outputs and both sides of the
 // LayerNorm folding, staged through a wave-private LDS scratch so that global memory sees full 128-256-byte row segments.
 #pragma once
 #include "kernels.h"
@@ -13,9 +13,6 @@ constexpr int BK = 64;
 // scratch (the ring slot that has just been released) and writes / reads global memory in full 128-256-byte
 // row segments (16 B per lane).  fp16 outputs are staged as 16-bit, 32 rows per pass; everything that is
 // combined with another global operand in fp32 (residual, GELU' * u) is staged as fp32, 16 rows per pass.
-#ifndef MVLPT_RESIDP_WIDE
-#define MVLPT_RESIDP_WIDE 1      // 0: the four-columns-per-lane walk of round 5 (A/B builds)
-#endif
 constexpr int EPI_SCRATCH_PER_WAVE = 4608;   // 32 rows x (128 + 16) B  >=  16 rows x (256 + 16) B
 
 // wave-private scratch rows: either one contiguous region, or (phased kernel) the wave's OWN six 1-KiB LDS-DMA slabs
@@ -52,8 +49,9 @@ struct FoldCtx {
   int mrel;      // first row of this wave's 64x64 block inside the tile
   int wn, wcn;   // column block of the wave / number of column blocks (producer)
   int xs;        // producer: format of the 16-bit copy (GemmArgs::ln_split; a compile-time 2 in the mixed-pair kernels)
-  // gemm_duo.hip: the bias of the workgroup's column panel in LDS (wn * 64 + column) instead of g.bias.  Typed as an LDS pointer:
-  // through a generic one hipcc emits flat loads, whose waits (vmcnt(0) lgkmcnt(0)) would drain the LDS-DMA queue
+  // the bias of the workgroup's column panel in LDS (wn * 64 + column) instead of g.bias.  No kernel sets it; the branch that reads
+  // it stays because without it hipcc schedules gemm_bt_phased_kernel<*, EPI_GELUBWD_SPLIT> differently (same instructions, other
+  // order).  Typed as an LDS pointer: through a generic one hipcc emits flat loads, whose waits would drain the LDS-DMA queue
   const __attribute__((address_space(3))) char* bias_lds = nullptr;
 };
 // {rstd, -rstd * mean} of tile row `row_rel`: the table fold_build_coef left behind the partials
@@ -152,8 +150,7 @@ __device__ __forceinline__ void store_a16(void* base, int split, size_t m, int N
   }
 }
 
-// H0, H1: the 32-row halves of the wave's 64x64 block this call stores (the K-split kernel gives each of its two wave groups one)
-template <typename T, int EPI_, typename Rows16, typename Rows32, int H0 = 0, int H1 = 2>
+template <typename T, int EPI_, typename Rows16, typename Rows32>
 __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&acc)[4][4], int mbase, int nbase, int lane,
                                                Rows16 rows16, Rows32 rows32, FoldCtx fc) {
   using v4 = typename Vec<T>::v4;
@@ -180,7 +177,7 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&
       T* outp = (T*)(which == 0 ? g.out : g.out2);
       if (which == 1 && !outp) break;
 #pragma unroll
-      for (int half = H0; half < H1; ++half) {
+      for (int half = 0; half < 2; ++half) {
         if constexpr (fold) {
           // the tile's colsum / bias slices sit in LDS (ds_read: no vmcnt, nothing to keep in registers across the stores).
           // All LDS reads of the half first (two rows' partials, four column-vector pairs), then the arithmetic: read-then-use
@@ -221,7 +218,7 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // All four row-segment reads of the pass in flight at once, then the stores.  (One read -> wait -> guarded store at a time
         // was four serialised LDS round trips plus four exec-mask branches per pass: ~1 700 cycles per 32 rows, the bulk of the
-        // 16-bit epilogue's time — tools/duo_trace.py.)  Whole passes inside the matrix (every tile but the last row of tiles)
+        // 16-bit epilogue's time.)  Whole passes inside the matrix (every tile but the last row of tiles)
         // store without per-lane guards.
         {
           const int c = lane & 7, r0 = lane >> 3;             // 8 lanes x 16 B = one 128-B row segment
@@ -241,9 +238,10 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // scratch is rewritten by the next pass
       }
     }
-  } else if constexpr (EPI == EPI_RESIDP_LN && MVLPT_RESIDP_WIDE && sizeof(T) == 2 && !__is_same(T, bf16)) {
+  } else if constexpr (EPI == EPI_RESIDP_LN) {
+    static_assert(__is_same(T, f16), "the packed residual stream is an fp16 format");
     // Packed residual stream, EIGHT columns per lane behind the transpose (8 lanes = the 64 columns of a row, 8 rows per pass): the
-    // 16-bit plane moves 16 B per lane and the byte plane 8 B — half the load / store instructions of the four-column walk below
+    // 16-bit plane moves 16 B per lane and the byte plane 8 B — half the load / store instructions of the four-column walk of round 5
     // (32 instead of 64 per 64x64 block; 1 KiB and 512 B per instruction instead of 512 and 256).  Under a saturated memory system an
     // epilogue is paced by its number of requests as much as by its bytes (NOTES round 6).
     int c = lane & 7, rq = lane >> 3;
@@ -252,7 +250,7 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&
     typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
     u32x2 lw[4][2];
 #pragma unroll
-    for (int i = 2 * H0; i < 2 * H1; ++i)
+    for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int it = 0; it < 2; ++it) {
         int m = mbase + i * 16 + it * 8 + rq;
@@ -264,7 +262,7 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&
     f32x4 cb0 = {0.f, 0.f, 0.f, 0.f}, cb1 = {0.f, 0.f, 0.f, 0.f};
     if (g.bias) { cb0 = *(const f32x4*)(g.bias + nbase + c * 8); cb1 = *(const f32x4*)(g.bias + nbase + c * 8 + 4); }
 #pragma unroll
-    for (int i = 2 * H0; i < 2 * H1; ++i) {
+    for (int i = 0; i < 4; ++i) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) *(f32x4*)(rows32(fr) + (j * 16 + fg * 4) * 4) = acc[i][j];
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -305,22 +303,9 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&
     // load while LDS-DMA is in flight, and that wait would also drain the stores issued before it.
     f32x4 rv[4][4];
     v4 uv[4][4];
-    [[maybe_unused]] uint32_t lw[4][4];      // packed stream: the hi plane arrives in uv, the byte plane here
-    if constexpr (EPI == EPI_RESIDP_LN) {
-#pragma unroll
-      for (int i = 2 * H0; i < 2 * H1; ++i)
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          int m = mbase + i * 16 + it * 4 + rq;
-          m = m < M ? m : M - 1;
-          const size_t o = (size_t)m * N + nbase + c * 4;
-          uv[i][it] = __builtin_nontemporal_load((const v4*)((const T*)g.rp_hi_in + o));
-          lw[i][it] = __builtin_nontemporal_load((const uint32_t*)(g.rp_lo_in + o));
-        }
-    }
     if constexpr (RESID || EPI == EPI_GELUBWD || EPI == EPI_GELUBWD_SPLIT) {
 #pragma unroll
-      for (int i = 2 * H0; i < 2 * H1; ++i)
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
           int m = mbase + i * 16 + it * 4 + rq;
@@ -335,14 +320,13 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&
       if (g.bias) colb = *(const f32x4*)(g.bias + nbase + c * 4);
       cols = *(const f32x4*)(g.ln_gamma + nbase + c * 4);
     }
-    if constexpr (EPI == EPI_RESIDP_LN) { if (g.bias) colb = *(const f32x4*)(g.bias + nbase + c * 4); }
     if constexpr (fold) {      // the bias is added behind the row scale: the raw accumulators are staged
       colb = *(const f32x4*)(fc.tab + XLDS_BIAS + (fc.wn * 64 + c * 4) * 4);
       cols = *(const f32x4*)(fc.tab + XLDS_COLSUM + (fc.wn * 64 + c * 4) * 4);
     }
     constexpr bool stage_raw = fold || epi_ln_producer(EPI);
 #pragma unroll
-    for (int i = 2 * H0; i < 2 * H1; ++i) {
+    for (int i = 0; i < 4; ++i) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) *(f32x4*)(rows32(fr) + (j * 16 + fg * 4) * 4) = stage_raw ? acc[i][j] : acc[i][j] + bv[j];
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -372,21 +356,6 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&
             store_a16<T>(g.ln_x16, fc.xs, (size_t)m, N, nbase + c * 4, v * cols);
           }
           __builtin_amdgcn_sched_barrier(0);     // one row segment at a time: interleaved passes cost registers this kernel does not have
-        } else if constexpr (EPI == EPI_RESIDP_LN) {
-          if constexpr (sizeof(T) == 2 && !__is_same(T, bf16)) {
-            v += respk_join4(uv[i][it], lw[i][it]) + colb;
-            float s1 = (v[0] + v[1]) + (v[2] + v[3]);
-            float s2 = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-            s1 = row16_sum(s1); s2 = row16_sum(s2);
-            if (c == 0) *(float2*)(fc.xl + ((size_t)(fc.mrel + i * 16 + r) * fc.wcn + fc.wn) * 8) = float2{s1, s2};
-            v4 hi;
-            const uint32_t lo = respk_split4(v, hi);
-            if (m < M) {
-              __builtin_nontemporal_store(hi, (v4*)((T*)g.out + o));
-              __builtin_nontemporal_store(lo, (uint32_t*)(g.rp_lo_out + o));
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
         } else if constexpr (EPI == EPI_GELUBWD) {
           v4 w;
 #pragma unroll

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void ln_fwd_stream_kernel(LnFwdArgs a) {
 template <typename TO>
 static void launch_ln_fwd_stream(const LnFwdArgs& a, hipStream_t s) {
   const int cus = stream_cus(s);
-  static const int per_cu = [] { const char* e = getenv("MVLPT_LN_BLOCKS_PER_CU"); return e ? atoi(e) : 8; }();
+  constexpr int per_cu = 8;      // resident workgroups per CU
   const int want = (a.rows + 3) / 4;
   dim3 grid(want < cus * per_cu ? want : cus * per_cu), block(256);
   const int nv = (a.d + 255) / 256;
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(256) void ln_bwd_stream_kernel(LnBwdArgs a) {
 template <typename TDY, typename T>
 static void launch_ln_bwd_stream(const LnBwdArgs& a, hipStream_t s) {
   const int cus = stream_cus(s);
-  static const int per_cu = [] { const char* e = getenv("MVLPT_LNB_BLOCKS_PER_CU"); return e ? atoi(e) : 8; }();
+  constexpr int per_cu = 8;      // resident workgroups per CU
   const int want = (a.rows + 3) / 4;
   dim3 grid(want < cus * per_cu ? want : cus * per_cu), block(256);
   const int nv = (a.d + 255) / 256;
@@ -293,8 +293,7 @@ static void launch_ln_bwd_stream(const LnBwdArgs& a, hipStream_t s) {
 hipError_t launch_ln_fwd(int out_dtype, const LnFwdArgs& a, hipStream_t s) {
   if (a.rows <= 0) return hipSuccess;
   if (a.d % 4 != 0 || a.d > LN_MAXV * 256) return hipErrorInvalidValue;
-  static const int stream_mode = [] { const char* e = getenv("MVLPT_LN_STREAM"); return e ? atoi(e) : 1; }();
-  if (stream_mode && a.rows >= 4096) {
+  if (a.rows >= 4096) {
     if (out_dtype == DT_F32) launch_ln_fwd_stream<float>(a, s);
     else if (out_dtype == DT_F16) launch_ln_fwd_stream<f16>(a, s);
     else if (out_dtype == DT_BF16) launch_ln_fwd_stream<bf16>(a, s);
@@ -314,8 +313,7 @@ hipError_t launch_ln_bwd(int dtype, const LnBwdArgs& a, hipStream_t s) {
   if (a.d % 4 != 0 || a.d > LN_MAXV * 256) return hipErrorInvalidValue;
   dim3 grid((a.rows + 3) / 4), block(256);
   const bool dy32 = a.dy_dtype == DT_F32;
-  static const int stream_mode = [] { const char* e = getenv("MVLPT_LNB_STREAM"); return e ? atoi(e) : 1; }();
-  if (stream_mode && a.rows >= 4096) {
+  if (a.rows >= 4096) {
     if (dtype == DT_F16) { if (dy32) launch_ln_bwd_stream<float, f16>(a, s); else launch_ln_bwd_stream<f16, f16>(a, s); }
     else if (dtype == DT_BF16) { if (dy32) launch_ln_bwd_stream<float, bf16>(a, s); else launch_ln_bwd_stream<bf16, bf16>(a, s); }
     else return hipErrorInvalidValue;

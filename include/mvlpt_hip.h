@@ -140,11 +140,23 @@ int mvlpt_text_fwd(void* handle, const float* prefix, const float* suffix, const
  * the class tables of mvlpt_text_fwd, read G times (never copied).  feat_out [G*C,embed] fp32, row s = (image g, class c). */
 int mvlpt_text_fwd_grouped(void* handle, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                            const int32_t* eot, int G, int C, int L, float* feat_out, int save_for_bwd, mvlpt_stream_t stream);
+/* The MVLPT trainer's CoCoOp branch under MULTITASK_LABEL_PERTASK (trainers/mvlpt.py:556-581): image g keeps only the logits of its own
+ * task's class range, so only those sequences run.  Group g owns classes [class_lo[g], class_hi[g]), 0 <= lo <= hi <= C (an empty range
+ * is legal, not all of them); its sequences are those classes in order, the groups follow one another: S = sum_g (hi - lo) sequences,
+ * feat_out [S,embed] fp32.  class_lo / class_hi are HOST int32 [G] arrays (the task of an image is known on the host before the step);
+ * they are checked and uploaded with the call, which stays enqueue-only.  The class tables are those of mvlpt_text_fwd_grouped, read
+ * through the ranges, never copied.  G <= 65535, S * L inside int32.  lo = 0, hi = C for every g computes what text_fwd_grouped does. */
+int mvlpt_text_fwd_ranged(void* handle, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                          const int32_t* eot, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L, float* feat_out,
+                          int save_for_bwd, mvlpt_stream_t stream);
 /* dfeat [C,embed] fp32 -> dctx (same shape as ctx).  Must follow text_fwd(save_for_bwd=1).  After text_fwd_grouped(save_for_bwd=1):
- * dfeat [G*C,embed] -> dctx [G,n_ctx,dt], dctx[g] = sum over the C classes of image g (fixed order: deterministic). */
+ * dfeat [G*C,embed] -> dctx [G,n_ctx,dt], dctx[g] = sum over the C classes of image g (fixed order: deterministic).  After
+ * text_fwd_ranged(save_for_bwd=1): dfeat [S,embed] -> dctx [G,n_ctx,dt], dctx[g] = sum over the sequences of group g's own range in the
+ * same fixed order (no atomics); all zeros for an empty range. */
 int mvlpt_text_bwd(void* handle, const float* dfeat, float* dctx, mvlpt_stream_t stream);
-/* *out = bytes of text-tower workspace a text_fwd / text_fwd_grouped over C_total sequences of length L reserves (the ctx-position
- * table counted for the largest n_ctx, L - 2); the workspace only grows, so a caller that chunks G keeps its peak under a budget. */
+/* *out = bytes of text-tower workspace a text_fwd / text_fwd_grouped / text_fwd_ranged over C_total sequences of length L reserves (the
+ * ctx-position table counted for the largest n_ctx, L - 2; a ranged tower adds its range tables and a per-class position table, a few
+ * bytes per class and sequence); the workspace only grows, so a caller that chunks G keeps its peak under a budget. */
 int mvlpt_text_workspace_bytes(void* handle, int C_total, int L, int save_for_bwd, int64_t* out);
 
 /* Cosine logits (trainers/mvlpt.py:550-554) with the multiplicative per-task mask (:573-581):
@@ -161,6 +173,14 @@ int mvlpt_logits_bwd(void* handle, const float* dlogits, float* dimg, float* dtx
 int mvlpt_logits_grouped_fwd(void* handle, const float* img, const float* txt, float logit_scale_exp, int G, int C, float* logits,
                              mvlpt_stream_t stream);
 int mvlpt_logits_grouped_bwd(void* handle, const float* dlogits, float* dtxt, mvlpt_stream_t stream);
+/* The ranged head: img [G,embed], txt [S,embed] (rows of mvlpt_text_fwd_ranged over the same HOST class_lo / class_hi), logits [G,C]:
+ * inside image g's range the cosine logit against its own text row, outside it exactly 0.0f (logits * select_index, :581).
+ * The backward reads dlogits [G,C] inside the ranges only and gives dtxt [S,embed] and / or dimg [G,embed] (either may be NULL): dimg is
+ * the gradient with respect to the UN-normalised image features (the image tower may carry visual prompts on this route).  Uses the
+ * features of the last logits_ranged_fwd on this handle. */
+int mvlpt_logits_ranged_fwd(void* handle, const float* img, const float* txt, float logit_scale_exp, const int32_t* class_lo,
+                            const int32_t* class_hi, int G, int C, float* logits, mvlpt_stream_t stream);
+int mvlpt_logits_ranged_bwd(void* handle, const float* dlogits, float* dtxt, float* dimg, mvlpt_stream_t stream);
 
 /* F.cross_entropy(output, label) with mean reduction (trainers/mvlpt.py:931) and its gradient.
  * labels: int64 [B] (MVLPT_LABEL_INT64) or fp32 probabilities [B,C] (MVLPT_LABEL_PROB_F32, rows already
@@ -259,6 +279,13 @@ int mvlpt_op_assemble_prompts_grouped(const float* prefix, const float* suffix, 
                                       const float* pos, float* x, int G, int C, int L, int d, mvlpt_stream_t stream);
 int mvlpt_op_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, int G, int C, int L, int d, int n_ctx, float* dctx,
                                      mvlpt_stream_t stream);
+/* the ranged glue of mvlpt_text_fwd_ranged / text_bwd: x [S, L, d] and dx [S, L, d] over the sequences of HOST class_lo / class_hi int32 [G]
+ * (see mvlpt_text_fwd_ranged), dctx [G, n_ctx, d], ctx_pos int32 [C, n_ctx].  These two calls wait for their kernel (test entry points). */
+int mvlpt_op_assemble_prompts_ranged(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                                     const float* pos, float* x, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L,
+                                     int d, mvlpt_stream_t stream);
+int mvlpt_op_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos, const int32_t* class_lo, const int32_t* class_hi, int G, int C,
+                                    int L, int d, int n_ctx, float* dctx, mvlpt_stream_t stream);
 
 /* ---- input pipeline ("next" row f3 of the scope table) -------------------------------------------------------
  * Replaces the per-image CPU transform the reference runs in DataLoader workers: Dassl `build_transform` with

@@ -63,11 +63,14 @@ SIGNATURES = {
     "mvlpt_text_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_bwd": (_i, [_vp, _vp, _vp, _vp]),
     "mvlpt_text_fwd_grouped": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "mvlpt_text_fwd_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_workspace_bytes": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int64)]),
     "mvlpt_logits_fwd": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp]),
     "mvlpt_logits_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mvlpt_logits_grouped_fwd": (_i, [_vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
     "mvlpt_logits_grouped_bwd": (_i, [_vp, _vp, _vp, _vp]),
+    "mvlpt_logits_ranged_fwd": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp]),
+    "mvlpt_logits_ranged_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mvlpt_cross_entropy": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mvlpt_op_gemm": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvlpt_op_gemm_split": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -97,6 +100,8 @@ SIGNATURES = {
     "mvlpt_op_cast": (_i, [_i, _vp, _vp, C.c_int64, _vp]),
     "mvlpt_op_assemble_prompts_grouped": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_gather_ctx_grad_grouped": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mvlpt_op_assemble_prompts_ranged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_gather_ctx_grad_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mvlpt_preprocess": (_i, [_vp, _vp, C.c_int64, C.POINTER(MvlptImageDesc), _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _i, _vp, _vp]),
     "mvlpt_profile_begin": (_i, [_vp, _i]),
     "mvlpt_profile_pause": (_i, [_vp, _i]),

@@ -183,6 +183,9 @@ struct Engine {
   // text fwd extras
   int tC = 0, tL = 0, t_nctx = 0, t_per_class = 0; int32_t* eot_rows = nullptr; int32_t* ctx_pos = nullptr;
   int t_groups = 0, t_gC = 0;   // grouped forward (mvlpt_text_fwd_grouped): tC = t_groups * t_gC sequences; 0 = not grouped
+  // ranged forward (mvlpt_text_fwd_ranged): t_groups groups over t_gC classes, tC = sum of the range widths; device tables in txt_ws
+  bool t_ranged = false; const int32_t *t_rlo = nullptr, *t_rstart = nullptr;
+  std::vector<int32_t> t_range_host, h_range_host;   // host images of the range tables (source of the asynchronous upload)
   // EOT-only last text block (compact [C,·] rows; the text-side twin of the CLS-only last image block)
   bool t_eot_last = false; float *txc32 = nullptr, *txm32 = nullptr, *txo32 = nullptr, *tdxc32 = nullptr, *tdhc32 = nullptr;
   void *tac16 = nullptr, *thc16 = nullptr, *tgc16 = nullptr, *tuc16 = nullptr, *tduc16 = nullptr, *tdxc16 = nullptr, *tdOc16 = nullptr;
@@ -190,6 +193,8 @@ struct Engine {
   // head state
   int hB = 0, hC = 0; float h_scale = 0.f; const int32_t *h_lo = nullptr, *h_hi = nullptr;
   bool h_grouped = false;        // the last head forward was mvlpt_logits_grouped_fwd (hB = G groups of hC classes)
+  // ... or mvlpt_logits_ranged_fwd: hB = G groups over hC classes, hS text rows; device tables in head_ws
+  bool h_ranged = false; int hS = 0; const int32_t *h_rlo = nullptr, *h_rstart = nullptr, *h_rgrp = nullptr;
   float *imn = nullptr, *txn = nullptr, *inorm = nullptr, *tnorm = nullptr;
   // profiling
   // mvlpt_debug_checksums: one 64-bit fingerprint per intermediate of the image tower (debug; off by default)
@@ -1091,6 +1096,27 @@ int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, 
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ class ranges
+// Host side of the ranged tower / head: class_lo / class_hi [G] (host arrays) -> t = [lo (G) | start (G + 1) | seq_cls (S) | seq_grp (S)],
+// checked here so that no kernel can index outside the class tables.  Returns S (the number of sequences), or -1 for a bad range.
+static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_hi, int G, int C, std::vector<int32_t>& t) {
+  int64_t S = 0;
+  for (int g = 0; g < G; ++g) {
+    if (class_lo[g] < 0 || class_lo[g] > class_hi[g] || class_hi[g] > C) return -1;
+    S += class_hi[g] - class_lo[g];
+  }
+  if (S > INT32_MAX) return -1;
+  t.resize((size_t)2 * G + 1 + 2 * (size_t)S);
+  int32_t *lo = t.data(), *start = lo + G, *cls = start + G + 1, *grp = cls + S;
+  int32_t s = 0;
+  for (int g = 0; g < G; ++g) {
+    lo[g] = class_lo[g]; start[g] = s;
+    for (int c = class_lo[g]; c < class_hi[g]; ++c, ++s) { cls[s] = c; grp[s] = g; }
+  }
+  start[G] = s;
+  return S;
+}
+
 // ------------------------------------------------------------------------------------------------ text tower
 // Bytes of txt_ws a text forward over C sequences of length L reserves (mvlpt_text_fwd, mvlpt_text_fwd_grouped,
 // mvlpt_text_workspace_bytes).  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of the ctx_pos table.
@@ -1104,9 +1130,10 @@ static bool text_exact(const Engine* E) { return E->prec_mode == MVLPT_PREC_SPLI
 
 // The text tower over C sequences.  G == 0: mvlpt_text_fwd (prefix / suffix / layout / eot [C, ...], ctx [n_ctx, d] or CSC [C, n_ctx, d]);
 // G > 0: mvlpt_text_fwd_grouped, C = G * Cg sequences s = g * Cg + c from the [Cg, ...] class tables and ctx [G, n_ctx, d].
+// ranged: mvlpt_text_fwd_ranged, G groups over the [Cg, ...] class tables, C = S sequences described by E->t_range_host.
 static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
                          const int32_t* layout, const int32_t* eot, int G, int Cg, int C, int L, float* feat_out, int save_for_bwd,
-                         mvlpt_stream_t stream) {
+                         mvlpt_stream_t stream, bool ranged = false) {
   if (int rc = mvlpt_frozen_ready(E)) return rc;
   if ((n_ctx > 0) != (ctx != nullptr) || n_ctx < 0 || n_ctx > L - 2) return fail(E, MVLPT_ERR_ARG, "text_fwd: ctx pointer and n_ctx disagree");
   const MvlptArch& A = E->arch;
@@ -1122,14 +1149,18 @@ static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, co
   // features, which put the inference logits of 5 of the 18 reference fixtures outside 1e-3 (profiles/r04_inference_parity.txt)
   const bool exact = text_exact(E);
   const size_t X = exact ? 2 : 1;
-  size_t need = text_ws_bytes(E, C, L, save, exact, (size_t)C * (n_ctx > 0 ? n_ctx : 1));
+  // ctx_pos is per class for the grouped / ranged towers; a ranged tower may run fewer sequences than there are classes
+  const size_t ctx_rows = (size_t)(ranged && Cg > C ? Cg : C) * (n_ctx > 0 ? n_ctx : 1);
+  const size_t range_ints = ranged ? E->t_range_host.size() : 0;
+  size_t need = text_ws_bytes(E, C, L, save, exact, ctx_rows) + align256(range_ints * 4);
   E->ts.valid = false;
   HIPCHK(E, E->txt_ws.reserve(need));
   Bump bp; bp.base = (char*)E->txt_ws.p; bp.cap = E->txt_ws.cap;
   E->eot32 = bp.take<float>((size_t)C * dtw);
   E->deot32 = bp.take<float>((size_t)C * dtw);
   E->eot_rows = bp.take<int32_t>(C);
-  E->ctx_pos = bp.take<int32_t>((size_t)C * (n_ctx > 0 ? n_ctx : 1));
+  E->ctx_pos = bp.take<int32_t>(ctx_rows);
+  int32_t* range_dev = ranged ? bp.take<int32_t>(range_ints) : nullptr;
   E->txc32 = bp.take<float>((size_t)C * dtw); E->txm32 = bp.take<float>((size_t)C * dtw); E->txo32 = bp.take<float>((size_t)C * dtw);
   E->tdxc32 = bp.take<float>((size_t)C * dtw); E->tdhc32 = bp.take<float>((size_t)C * dtw);
   E->tac16 = bp.take_bytes((size_t)C * dtw * 2 * X); E->thc16 = bp.take_bytes((size_t)C * dtw * 2 * X);
@@ -1140,10 +1171,17 @@ static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, co
   TowerState& st = E->ts;
   E->tC = C; E->tL = L; E->t_nctx = n_ctx; E->t_per_class = ctx_per_class;
   E->t_groups = G; E->t_gC = G > 0 ? Cg : 0;
+  E->t_ranged = ranged; E->t_rlo = range_dev; E->t_rstart = ranged ? range_dev + G : nullptr;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)C * L * dtw * 12.0);
-    if (G > 0) {
+    if (ranged) {
+      const int32_t *seq_cls = range_dev + 2 * G + 1, *seq_grp = seq_cls + C;
+      HIPCHK(E, hipMemcpyAsync(range_dev, E->t_range_host.data(), range_ints * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(E, launch_assemble_prompts_ranged(prefix, suffix, ctx, n_ctx, layout, E->tpos, st.x[0], seq_cls, seq_grp, C, L, dtw, s));
+      HIPCHK(E, launch_eot_rows_ranged(eot, E->eot_rows, seq_cls, C, L, s));
+      if (save) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
+    } else if (G > 0) {
       HIPCHK(E, launch_assemble_prompts_grouped(prefix, suffix, ctx, n_ctx, layout, E->tpos, st.x[0], G, Cg, L, dtw, s));
       HIPCHK(E, launch_eot_rows_grouped(eot, E->eot_rows, G, Cg, L, s));
       if (save) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
@@ -1214,6 +1252,21 @@ int mvlpt_text_fwd_grouped(void* h, const float* prefix, const float* suffix, co
   return text_fwd_impl(E, prefix, suffix, ctx, 0, n_ctx, layout, eot, G, C, G * C, L, feat_out, save_for_bwd, stream);
 }
 
+// The MVLPT trainer's CoCoOp branch under the per-task mask (trainers/mvlpt.py:556-581): image g runs only the classes of its own task
+int mvlpt_text_fwd_ranged(void* h, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                          const int32_t* eot, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L, float* feat_out,
+                          int save_for_bwd, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !prefix || !suffix || !ctx || !layout || !eot || !class_lo || !class_hi || !feat_out || G <= 0 || C <= 0 || L <= 0 || n_ctx <= 0)
+    return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: null/invalid argument");
+  if (G > 65535) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: too many groups");
+  const int64_t S = build_range_table(class_lo, class_hi, G, C, E->t_range_host);
+  if (S < 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: a class range is not inside [0, C] or the ranges hold too many sequences");
+  if (S == 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: every range is empty");
+  if (S > (int64_t)INT32_MAX / L) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: too many sequences");
+  return text_fwd_impl(E, prefix, suffix, ctx, 0, n_ctx, layout, eot, G, C, (int)S, L, feat_out, save_for_bwd, stream, true);
+}
+
 int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, int64_t* out) {
   Engine* E = (Engine*)h;
   if (!E || !out || C_total <= 0 || L <= 2) return fail(E, MVLPT_ERR_ARG, "text_workspace_bytes: null/invalid argument");
@@ -1268,7 +1321,9 @@ int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stre
   for (int l = st.layers - 2; l >= 0; --l)
     if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)C * E->t_nctx * dtw * 4.0);
-    if (E->t_groups > 0)
+    if (E->t_ranged)
+      HIPCHK(E, launch_gather_ctx_grad_ranged(st.dx32, E->ctx_pos, E->t_rlo, E->t_rstart, E->t_groups, L, dtw, E->t_nctx, dctx, st.scale_dev, s));
+    else if (E->t_groups > 0)
       HIPCHK(E, launch_gather_ctx_grad_grouped(st.dx32, E->ctx_pos, E->t_groups, E->t_gC, L, dtw, E->t_nctx, dctx, st.scale_dev, s));
     else
       HIPCHK(E, launch_gather_ctx_grad(st.dx32, E->ctx_pos, C, L, dtw, E->t_nctx, E->t_per_class, dctx, st.scale_dev, s)); }
@@ -1294,7 +1349,7 @@ int mvlpt_logits_fwd(void* h, const float* img, const float* txt, float scale, c
     return fail(E, MVLPT_ERR_ARG, "logits_fwd: null/invalid argument");
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
-  E->hB = 0; E->h_grouped = false;
+  E->hB = 0; E->h_grouped = false; E->h_ranged = false;
   if (int rc = head_reserve(E, B, C)) return rc;
   ProfScope ps(E, s, PC_HEAD, 2.0 * B * C * e, 4.0 * ((double)B * e + (double)C * e + (double)B * C));
   HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, B, e, s));
@@ -1307,7 +1362,7 @@ int mvlpt_logits_fwd(void* h, const float* img, const float* txt, float scale, c
 int mvlpt_logits_bwd(void* h, const float* dlogits, float* dimg, float* dtxt, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !dlogits) return fail(E, MVLPT_ERR_ARG, "logits_bwd: null argument");
-  if (E->hB <= 0 || !E->imn || E->h_grouped) return fail(E, MVLPT_ERR_STATE, "logits_bwd: call logits_fwd first");
+  if (E->hB <= 0 || !E->imn || E->h_grouped || E->h_ranged) return fail(E, MVLPT_ERR_STATE, "logits_bwd: call logits_fwd first");
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
   ProfScope ps(E, s, PC_HEAD, 4.0 * E->hB * E->hC * e, 4.0 * ((double)E->hB * e + (double)E->hC * e + (double)E->hB * E->hC) * 2);
@@ -1322,7 +1377,7 @@ int mvlpt_logits_grouped_fwd(void* h, const float* img, const float* txt, float 
     return fail(E, MVLPT_ERR_ARG, "logits_grouped_fwd: null/invalid argument");
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
-  E->hB = 0; E->h_grouped = false;
+  E->hB = 0; E->h_grouped = false; E->h_ranged = false;
   if (int rc = head_reserve(E, G, G * C)) return rc;
   ProfScope ps(E, s, PC_HEAD, 2.0 * G * C * e, 4.0 * ((double)G * e + (double)G * C * e + (double)G * C));
   HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, G, e, s));
@@ -1335,11 +1390,53 @@ int mvlpt_logits_grouped_fwd(void* h, const float* img, const float* txt, float 
 int mvlpt_logits_grouped_bwd(void* h, const float* dlogits, float* dtxt, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !dlogits || !dtxt) return fail(E, MVLPT_ERR_ARG, "logits_grouped_bwd: null argument");
-  if (E->hB <= 0 || !E->imn || !E->h_grouped) return fail(E, MVLPT_ERR_STATE, "logits_grouped_bwd: call logits_grouped_fwd first");
+  if (E->hB <= 0 || !E->imn || !E->h_grouped || E->h_ranged) return fail(E, MVLPT_ERR_STATE, "logits_grouped_bwd: call logits_grouped_fwd first");
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
   ProfScope ps(E, s, PC_HEAD, 4.0 * E->hB * E->hC * e, 4.0 * ((double)E->hB * e + 2.0 * E->hB * E->hC * e + (double)E->hB * E->hC));
   HIPCHK(E, launch_logits_grouped_bwd(dlogits, E->imn, E->txn, E->tnorm, E->h_scale, dtxt, E->hB, E->hC, e, s));
+  return 0;
+}
+
+// The ranged head (trainers/mvlpt.py:556-581): image g against the text rows of its own class range, 0 outside it
+int mvlpt_logits_ranged_fwd(void* h, const float* img, const float* txt, float scale, const int32_t* class_lo, const int32_t* class_hi,
+                            int G, int C, float* logits, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !img || !txt || !class_lo || !class_hi || !logits || G <= 0 || C <= 0 || G > 65535 || (int64_t)G * C > INT32_MAX)
+    return fail(E, MVLPT_ERR_ARG, "logits_ranged_fwd: null/invalid argument");
+  hipStream_t s = (hipStream_t)stream;
+  const int e = E->arch.embed_dim;
+  E->hB = 0; E->h_grouped = false; E->h_ranged = false;
+  const int64_t S64 = build_range_table(class_lo, class_hi, G, C, E->h_range_host);
+  if (S64 <= 0) return fail(E, MVLPT_ERR_ARG, "logits_ranged_fwd: a class range is not inside [0, C], or every range is empty");
+  const int S = (int)S64;
+  const size_t ints = E->h_range_host.size();
+  const size_t need = align256((size_t)G * e * 4) + align256((size_t)S * e * 4) + align256((size_t)G * 4) + align256((size_t)S * 4) +
+                      align256(ints * 4) + 4096;
+  HIPCHK(E, E->head_ws.reserve(need));
+  Bump bp; bp.base = (char*)E->head_ws.p;
+  E->imn = bp.take<float>((size_t)G * e); E->txn = bp.take<float>((size_t)S * e);
+  E->inorm = bp.take<float>(G); E->tnorm = bp.take<float>(S);
+  int32_t* tab = bp.take<int32_t>(ints);
+  ProfScope ps(E, s, PC_HEAD, 2.0 * S * e, 4.0 * ((double)G * e + (double)S * e + (double)G * C));
+  HIPCHK(E, hipMemcpyAsync(tab, E->h_range_host.data(), ints * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, G, e, s));
+  HIPCHK(E, launch_normalize_rows(txt, E->txn, E->tnorm, S, e, s));
+  HIPCHK(E, launch_logits_ranged(E->imn, E->txn, scale, tab, tab + G, logits, G, C, e, s));
+  E->hB = G; E->hC = C; E->hS = S; E->h_scale = scale; E->h_lo = E->h_hi = nullptr; E->h_ranged = true;
+  E->h_rlo = tab; E->h_rstart = tab + G; E->h_rgrp = tab + 2 * G + 1 + S;
+  return 0;
+}
+
+int mvlpt_logits_ranged_bwd(void* h, const float* dlogits, float* dtxt, float* dimg, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !dlogits || (!dtxt && !dimg)) return fail(E, MVLPT_ERR_ARG, "logits_ranged_bwd: null argument");
+  if (E->hB <= 0 || !E->imn || !E->h_ranged) return fail(E, MVLPT_ERR_STATE, "logits_ranged_bwd: call logits_ranged_fwd first");
+  hipStream_t s = (hipStream_t)stream;
+  const int e = E->arch.embed_dim;
+  ProfScope ps(E, s, PC_HEAD, 6.0 * E->hS * e, 4.0 * ((double)E->hB * e * 2 + 3.0 * E->hS * e + (double)E->hS));
+  HIPCHK(E, launch_logits_ranged_bwd(dlogits, E->imn, E->txn, E->inorm, E->tnorm, E->h_scale, E->h_rlo, E->h_rstart, E->h_rgrp, dimg, dtxt,
+                                     E->hB, E->hS, E->hC, e, s));
   return 0;
 }
 
@@ -1606,6 +1703,45 @@ int mvlpt_op_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, in
   if (!dx || !ctx_pos || !dctx || G <= 0 || C <= 0 || L <= 0 || n_ctx <= 0 || d <= 0) {
     g_create_err = "op_gather_ctx_grad_grouped: null/invalid argument"; return MVLPT_ERR_ARG; }
   OPCHK(launch_gather_ctx_grad_grouped(dx, ctx_pos, G, C, L, d, n_ctx, dctx, nullptr, (hipStream_t)stream));
+  return 0;
+}
+
+// The ranged glue without a tower (tests).  The range table is built and checked on the host, uploaded into a temporary buffer, and the
+// call waits for its kernel before the buffer is freed.
+static int op_range_table(const int32_t* class_lo, const int32_t* class_hi, int G, int C, std::vector<int32_t>& t, int32_t** dev, int* S) {
+  const int64_t S64 = build_range_table(class_lo, class_hi, G, C, t);
+  if (S64 <= 0) { g_create_err = "ranged op: a class range is not inside [0, C], or every range is empty"; return MVLPT_ERR_ARG; }
+  *S = (int)S64;
+  OPCHK(hipMalloc((void**)dev, t.size() * 4));
+  hipError_t e = hipMemcpy(*dev, t.data(), t.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { (void)hipFree(*dev); *dev = nullptr; OPCHK(e); }
+  return 0;
+}
+int mvlpt_op_assemble_prompts_ranged(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                                     const float* pos, float* x, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L,
+                                     int d, mvlpt_stream_t stream) {
+  if (!prefix || !suffix || !ctx || !layout || !pos || !x || !class_lo || !class_hi || G <= 0 || C <= 0 || L <= n_ctx + 1 || n_ctx <= 0 ||
+      d <= 0) {
+    g_create_err = "op_assemble_prompts_ranged: null/invalid argument"; return MVLPT_ERR_ARG; }
+  std::vector<int32_t> t; int32_t* dev = nullptr; int S = 0;
+  if (int rc = op_range_table(class_lo, class_hi, G, C, t, &dev, &S)) return rc;
+  hipError_t e = launch_assemble_prompts_ranged(prefix, suffix, ctx, n_ctx, layout, pos, x, dev + 2 * G + 1, dev + 2 * G + 1 + S, S, L, d,
+                                                (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(dev);
+  OPCHK(e);
+  return 0;
+}
+int mvlpt_op_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos, const int32_t* class_lo, const int32_t* class_hi, int G, int C,
+                                    int L, int d, int n_ctx, float* dctx, mvlpt_stream_t stream) {
+  if (!dx || !ctx_pos || !dctx || !class_lo || !class_hi || G <= 0 || C <= 0 || L <= 0 || n_ctx <= 0 || d <= 0) {
+    g_create_err = "op_gather_ctx_grad_ranged: null/invalid argument"; return MVLPT_ERR_ARG; }
+  std::vector<int32_t> t; int32_t* dev = nullptr; int S = 0;
+  if (int rc = op_range_table(class_lo, class_hi, G, C, t, &dev, &S)) return rc;
+  hipError_t e = launch_gather_ctx_grad_ranged(dx, ctx_pos, dev, dev + G, G, L, d, n_ctx, dctx, nullptr, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  (void)hipFree(dev);
+  OPCHK(e);
   return 0;
 }
 

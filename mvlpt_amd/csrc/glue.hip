@@ -679,6 +679,89 @@ hipError_t launch_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_po
   return hipGetLastError();
 }
 
+// ---- ranged (image-conditioned, per-task) prompts: group g runs only the classes of its own range (trainers/mvlpt.py:556-581: a logit
+// outside the image's task is multiplied by 0, so its sequence is never needed).  Sequence s belongs to group seq_grp[s] and class
+// seq_cls[s]; the class tables stay [C, ...] and are read through seq_cls.
+__global__ void assemble_prompts_ranged_kernel(const float* __restrict__ prefix, const float* __restrict__ suffix,
+                                               const float* __restrict__ ctx, int n_ctx, const int32_t* __restrict__ layout,
+                                               const float* __restrict__ pos, float* __restrict__ x,
+                                               const int32_t* __restrict__ seq_cls, const int32_t* __restrict__ seq_grp, int S, int L, int d) {
+  const int d4 = d / 4;
+  const size_t total = (size_t)S * L * d4;
+  const int suf_len = L - 1 - n_ctx;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int c4 = (int)(i % d4);
+    const size_t tok = i / d4;
+    const int pos_i = (int)(tok % L);
+    const size_t seq = tok / L;
+    const int cls = seq_cls[seq], g = seq_grp[seq];
+    const int e = layout[(size_t)cls * L + pos_i];
+    const float* src;
+    if (e == 0) src = prefix + (size_t)cls * d;
+    else if (e > 0) src = suffix + ((size_t)cls * suf_len + (e - 1)) * d;
+    else src = ctx + ((size_t)g * n_ctx + (-e - 1)) * d;
+    *(f32x4*)(x + tok * d + c4 * 4) = *(const f32x4*)(src + c4 * 4) + *(const f32x4*)(pos + (size_t)pos_i * d + c4 * 4);
+  }
+}
+hipError_t launch_assemble_prompts_ranged(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                                          const float* pos, float* x, const int32_t* seq_cls, const int32_t* seq_grp, int S, int L, int d,
+                                          hipStream_t s) {
+  if (d % 4 || n_ctx <= 0 || S <= 0) return hipErrorInvalidValue;
+  const size_t total = (size_t)S * L * (d / 4);
+  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  hipLaunchKernelGGL(assemble_prompts_ranged_kernel, dim3(grid), dim3(256), 0, s, prefix, suffix, ctx, n_ctx, layout, pos, x, seq_cls,
+                     seq_grp, S, L, d);
+  return hipGetLastError();
+}
+// rows[s] = s * L + eot[seq_cls[s]]
+__global__ void eot_rows_ranged_kernel(const int32_t* __restrict__ eot, int32_t* __restrict__ rows, const int32_t* __restrict__ seq_cls,
+                                       int S, int L) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < S) rows[s] = s * L + eot[seq_cls[s]];
+}
+hipError_t launch_eot_rows_ranged(const int32_t* eot, int32_t* rows, const int32_t* seq_cls, int S, int L, hipStream_t s) {
+  hipLaunchKernelGGL(eot_rows_ranged_kernel, dim3((S + 255) / 256), dim3(256), 0, s, eot, rows, seq_cls, S, L);
+  return hipGetLastError();
+}
+// dctx[g,j,:] = inv * sum_k dx[(start[g] + k)*L + pos(lo[g] + k, j), :], k over the group's own range: gather_ctx_grad_grouped_kernel with
+// a per-group width (2 or 211 classes alike: wave w takes k = w, w+16, ...; the same fixed order, so a full range gives the grouped bits)
+__global__ __launch_bounds__(1024) void gather_ctx_grad_ranged_kernel(const float* __restrict__ dx, const int32_t* __restrict__ ctx_pos,
+                                                                      const int32_t* __restrict__ lo, const int32_t* __restrict__ start,
+                                                                      int L, int d, int n_ctx, float* __restrict__ dctx,
+                                                                      const float* scale_dev) {
+  __shared__ f32x4 part[16][64];
+  const int j = blockIdx.y, g = blockIdx.z;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = (blockIdx.x * 64 + lane) * 4;
+  const bool ok = c < d;
+  const int s0 = start[g], n = start[g + 1] - s0;
+  const float* dxg = dx + (size_t)s0 * L * d;
+  const int32_t* cp = ctx_pos + (size_t)lo[g] * n_ctx + j;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (ok) {
+#pragma unroll 8
+    for (int k = wave; k < n; k += 16)
+      acc += *(const f32x4*)(dxg + ((size_t)k * L + cp[(size_t)k * n_ctx]) * d + c);
+  }
+  part[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && ok) {
+    f32x4 t = part[0][lane];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) t += part[w][lane];
+    const float inv = scale_dev ? scale_dev[1] : 1.0f;
+    *(f32x4*)(dctx + ((size_t)g * n_ctx + j) * d + c) = t * inv;
+  }
+}
+hipError_t launch_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos, const int32_t* lo, const int32_t* start, int G, int L,
+                                         int d, int n_ctx, float* dctx, const float* scale_dev, hipStream_t s) {
+  if (n_ctx <= 0) return hipSuccess;
+  if (d % 4 || G <= 0 || G > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gather_ctx_grad_ranged_kernel, dim3((d + 255) / 256, n_ctx, G), dim3(1024), 0, s, dx, ctx_pos, lo, start, L, d, n_ctx,
+                     dctx, scale_dev);
+  return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------ gradient scaling
 // The backward is linear in the incoming gradient, so it is run on  2^k * dfeat  to keep 16-bit activation
 // gradients in range (the reference's fp16 mode has no GradScaler, trainers/mvlpt.py:873,927-932, and simply
@@ -1069,6 +1152,121 @@ hipError_t launch_logits_grouped_bwd(const float* dlogits, const float* imn, con
                                      int G, int C, int e, hipStream_t s) {
   const int N = G * C;
   hipLaunchKernelGGL(logits_grouped_bwd_kernel, dim3((N + 3) / 4), dim3(256), 0, s, dlogits, imn, txn, tnorm, scale, dtxt, N, C, e);
+  return hipGetLastError();
+}
+
+// ranged head (trainers/mvlpt.py:556-581): image g has text rows start[g] .. start[g+1] - 1 for classes lo[g] ..; every logit outside
+// that range is 0.0f exactly (logits * select_index).  logits_grouped_kernel with the row looked up through the range.
+__global__ __launch_bounds__(256) void logits_ranged_kernel(const float* __restrict__ imn, const float* __restrict__ txn, float scale,
+                                                            const int32_t* __restrict__ lo, const int32_t* __restrict__ start,
+                                                            float* __restrict__ logits, int G, int C, int e) {
+  extern __shared__ float simg[];
+  const int g = blockIdx.x;
+  for (int i = threadIdx.x; i < e; i += 256) simg[i] = scale * imn[(size_t)g * e + i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int l0 = lo[g], s0 = start[g], n = start[g + 1] - s0;
+  for (int c = blockIdx.y * 4 + wave; c < C; c += gridDim.y * 4) {
+    const int k = c - l0;
+    float s = 0.f;
+    if (k >= 0 && k < n) {                              // uniform over the wave
+      const float* t = txn + (size_t)(s0 + k) * e;
+      for (int i = lane; i < e; i += 64) s += simg[i] * t[i];
+      s = wave_sum(s);
+    }
+    if (lane == 0) logits[(size_t)g * C + c] = s;
+  }
+}
+hipError_t launch_logits_ranged(const float* imn, const float* txn, float scale, const int32_t* lo, const int32_t* start, float* logits,
+                                int G, int C, int e, hipStream_t s) {
+  if (G <= 0 || G > 65535) return hipErrorInvalidValue;
+  int gy = (C + 3) / 4; gy = gy > 64 ? 64 : gy;
+  hipLaunchKernelGGL(logits_ranged_kernel, dim3(G, gy), dim3(256), e * sizeof(float), s, imn, txn, scale, lo, start, logits, G, C, e);
+  return hipGetLastError();
+}
+// d txt[s]: logits_grouped_bwd_kernel with (g, c) = (seq_grp[s], lo[g] + s - start[g]).  One wave per text row.
+__global__ __launch_bounds__(256) void logits_ranged_bwd_txt_kernel(const float* __restrict__ dl, const float* __restrict__ imn,
+                                                                    const float* __restrict__ txn, const float* __restrict__ tnorm,
+                                                                    float scale, const int32_t* __restrict__ lo,
+                                                                    const int32_t* __restrict__ start, const int32_t* __restrict__ seq_grp,
+                                                                    float* __restrict__ dtxt, int S, int C, int e) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= S) return;
+  const int g = seq_grp[row];
+  const int c = lo[g] + row - start[g];
+  const float* im = imn + (size_t)g * e;
+  const float* t = txn + (size_t)row * e;
+  float dot = 0.f;
+  for (int i = lane; i < e; i += 64) dot += im[i] * t[i];
+  dot = wave_sum(dot);
+  const float w = scale * dl[(size_t)g * C + c];
+  const float inv = 1.0f / tnorm[row];
+  for (int i = lane; i < e; i += 64) dtxt[(size_t)row * e + i] = w * (im[i] - t[i] * dot) * inv;
+}
+// d img[g] = normalisation backward of  scale * sum_k dlogits[g, lo[g] + k] * txn[start[g] + k]: logits_bwd_kernel<true> with the
+// reduction over the group's own rows (8 waves split the range, 8 columns per lane, partials combined through LDS in wave order);
+// an empty range gives zeros
+__global__ __launch_bounds__(512) void logits_ranged_bwd_img_kernel(const float* __restrict__ dl, const float* __restrict__ imn,
+                                                                    const float* __restrict__ txn, const float* __restrict__ inorm,
+                                                                    float scale, const int32_t* __restrict__ lo,
+                                                                    const int32_t* __restrict__ start, float* __restrict__ dimg,
+                                                                    int C, int e) {
+  __shared__ float part[8][1024];
+  __shared__ float red[8];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = blockIdx.x;
+  const int l0 = lo[g], s0 = start[g], n = start[g + 1] - s0;
+  const float* self = imn + (size_t)g * e;
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) { acc[k][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[k][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
+  for (int r = wave; r < n; r += 8) {
+    const float w = scale * dl[(size_t)g * C + l0 + r];
+    const float* o = txn + (size_t)(s0 + r) * e;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int i = (k * 64 + lane) * 8;
+      if (i < e) {
+        acc[k][0] += w * *(const f32x4*)(o + i);
+        acc[k][1] += w * *(const f32x4*)(o + i + 4);
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int i = (k * 64 + lane) * 8;
+    if (i < e) { *(f32x4*)&part[wave][i] = acc[k][0]; *(f32x4*)&part[wave][i + 4] = acc[k][1]; }
+  }
+  __syncthreads();
+  float gr[2], dot = 0.f;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int i = threadIdx.x + k * 512;
+    gr[k] = 0.f;
+    if (i < e) {
+      gr[k] = ((part[0][i] + part[1][i]) + (part[2][i] + part[3][i])) + ((part[4][i] + part[5][i]) + (part[6][i] + part[7][i]));
+      dot += gr[k] * self[i];
+    }
+  }
+  dot = wave_sum(dot);
+  if (lane == 0) red[wave] = dot;
+  __syncthreads();
+  dot = ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
+  const float inv = 1.0f / inorm[g];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int i = threadIdx.x + k * 512;
+    if (i < e) dimg[(size_t)g * e + i] = (gr[k] - self[i] * dot) * inv;
+  }
+}
+hipError_t launch_logits_ranged_bwd(const float* dlogits, const float* imn, const float* txn, const float* inorm, const float* tnorm,
+                                    float scale, const int32_t* lo, const int32_t* start, const int32_t* seq_grp, float* dimg, float* dtxt,
+                                    int G, int S, int C, int e, hipStream_t s) {
+  if (e > 1024 || e % 8 || G <= 0 || S <= 0) return hipErrorInvalidValue;
+  if (dtxt) hipLaunchKernelGGL(logits_ranged_bwd_txt_kernel, dim3((S + 3) / 4), dim3(256), 0, s, dlogits, imn, txn, tnorm, scale, lo, start,
+                               seq_grp, dtxt, S, C, e);
+  if (dimg) hipLaunchKernelGGL(logits_ranged_bwd_img_kernel, dim3(G), dim3(512), 0, s, dlogits, imn, txn, inorm, scale, lo, start, dimg, C, e);
   return hipGetLastError();
 }
 

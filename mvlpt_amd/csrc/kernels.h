@@ -247,6 +247,16 @@ hipError_t launch_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C
 // dctx (grouped) [G,n,d] = inv_scale * sum_c dx[g*C + c, ctx_pos[c,j], :]  (ctx_pos per class, [C, n])
 hipError_t launch_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, int G, int C, int L, int d, int n_ctx, float* dctx,
                                           const float* scale_dev, hipStream_t s);
+// ranged prompts (trainers/mvlpt.py:556-581 under the per-task mask): group g owns classes [lo[g], lo[g] + start[g+1] - start[g]); its
+// sequences start[g] .. start[g+1] - 1 are those classes in order.  seq_cls / seq_grp int32 [S]: class and group of every sequence;
+// lo int32 [G], start int32 [G + 1] (prefix sum, start[G] = S).  The tables are built and checked on the host (engine.hip).
+hipError_t launch_assemble_prompts_ranged(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
+                                          const float* pos, float* x, const int32_t* seq_cls, const int32_t* seq_grp, int S, int L, int d,
+                                          hipStream_t s);
+hipError_t launch_eot_rows_ranged(const int32_t* eot, int32_t* rows, const int32_t* seq_cls, int S, int L, hipStream_t s);
+// dctx (ranged) [G,n,d] = inv_scale * sum_k dx[start[g] + k, ctx_pos[lo[g] + k, j], :]  (ctx_pos per class, [C, n]); zeros for an empty range
+hipError_t launch_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos, const int32_t* lo, const int32_t* start, int G, int L,
+                                         int d, int n_ctx, float* dctx, const float* scale_dev, hipStream_t s);
 // scale_dev[0] = 2^k with amax(|v|)*2^k ~ target ; scale_dev[1] = 1/scale_dev[0]
 hipError_t launch_grad_scale(const float* v, size_t n, float target, float* scale_dev, hipStream_t s);
 hipError_t launch_zero(void* p, size_t bytes, hipStream_t s);
@@ -275,5 +285,12 @@ hipError_t launch_logits_bwd(const float* dlogits, const float* imn, const float
 hipError_t launch_logits_grouped(const float* imn, const float* txn, float scale, float* logits, int G, int C, int e, hipStream_t s);
 hipError_t launch_logits_grouped_bwd(const float* dlogits, const float* imn, const float* txn, const float* tnorm, float scale, float* dtxt,
                                      int G, int C, int e, hipStream_t s);
+// ranged head: logits[g,c] = scale * imn[g] . txn[start[g] + c - lo[g]] for lo[g] <= c < lo[g] + (start[g+1] - start[g]), 0 elsewhere;
+// backward: dtxt [S, e] and / or dimg [G, e] (through the image normalisation); dlogits outside the ranges is not read
+hipError_t launch_logits_ranged(const float* imn, const float* txn, float scale, const int32_t* lo, const int32_t* start, float* logits,
+                                int G, int C, int e, hipStream_t s);
+hipError_t launch_logits_ranged_bwd(const float* dlogits, const float* imn, const float* txn, const float* inorm, const float* tnorm,
+                                    float scale, const int32_t* lo, const int32_t* start, const int32_t* seq_grp, float* dimg, float* dtxt,
+                                    int G, int S, int C, int e, hipStream_t s);
 
 }  // namespace mvlpt

@@ -60,6 +60,22 @@ def device_cus(device: torch.device) -> int:
         return int(lib.mvlpt_stream_cus(None))
 
 
+def _host_ranges(class_lo, class_hi, G: int, n_cls: int):
+    """Host class ranges -> (int32 ctypes arrays lo, hi, S).  Checked here as well as in the library; never touches the device."""
+    if any(isinstance(t, torch.Tensor) and t.is_cuda for t in (class_lo, class_hi)):
+        raise ValueError("class ranges are host arrays (a device tensor would have to be read back)")
+    lo = [int(v) for v in (class_lo.tolist() if hasattr(class_lo, "tolist") else class_lo)]
+    hi = [int(v) for v in (class_hi.tolist() if hasattr(class_hi, "tolist") else class_hi)]
+    if len(lo) != G or len(hi) != G:
+        raise ValueError(f"class ranges must have one entry per group ({G}), got {len(lo)} / {len(hi)}")
+    if any(not (0 <= a <= b <= n_cls) for a, b in zip(lo, hi)):
+        raise ValueError(f"class ranges must satisfy 0 <= lo <= hi <= {n_cls}")
+    S = sum(b - a for a, b in zip(lo, hi))
+    if S == 0:
+        raise ValueError("every class range is empty")
+    return (C.c_int32 * G)(*lo), (C.c_int32 * G)(*hi), S
+
+
 def _req(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     if not t.is_cuda:
         raise RuntimeError(f"{name} must be a CUDA/HIP tensor: mvlpt_amd has no CPU path")
@@ -245,6 +261,28 @@ class Engine:
         self._txt_state = (tuple(ctx.shape), layout, eot) if save_for_bwd else None
         return feat
 
+    @_on_device
+    def text_fwd_ranged(self, prefix: torch.Tensor, suffix: torch.Tensor, ctx: torch.Tensor, layout: torch.Tensor, eot: torch.Tensor,
+                        class_lo, class_hi, save_for_bwd: bool = False) -> torch.Tensor:
+        """The ranged text side (mvlpt_text_fwd_ranged): ctx [G, n_ctx, dt]; image g runs classes [class_lo[g], class_hi[g]) only.
+        `class_lo` / `class_hi` are HOST integer sequences (lists, numpy or CPU tensors) of length G: nothing is read back from the
+        device.  Features [S, e], S = sum of the range widths, group after group.  A following text_bwd returns [G, n_ctx, dt]."""
+        prefix = _req(prefix, torch.float32, "token_prefix")
+        suffix = _req(suffix, torch.float32, "token_suffix")
+        layout = _req(layout, torch.int32, "layout")
+        eot = _req(eot, torch.int32, "eot")
+        ctx = _req(ctx, torch.float32, "ctx")
+        if ctx.dim() != 3:
+            raise ValueError("ranged ctx must be [G, n_ctx, ctx_dim]")
+        Cn, L = layout.shape
+        G, n_ctx = ctx.shape[0], ctx.shape[1]
+        lo, hi, S = _host_ranges(class_lo, class_hi, G, Cn)
+        feat = torch.empty(S, self.arch.embed_dim, device=prefix.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_text_fwd_ranged(self.h, _ptr(prefix), _ptr(suffix), _ptr(ctx), n_ctx, _ptr(layout), _ptr(eot), lo, hi,
+                                             G, Cn, L, _ptr(feat), int(save_for_bwd), _stream()), self.h, "text_fwd_ranged")
+        self._txt_state = (tuple(ctx.shape), layout, eot) if save_for_bwd else None
+        return feat
+
     def text_workspace_bytes(self, n_seq: int, L: int, save_for_bwd: bool) -> int:
         """Text-tower workspace a forward over `n_seq` sequences of length L reserves (mvlpt_text_workspace_bytes)."""
         out = C.c_int64()
@@ -313,6 +351,35 @@ class Engine:
         dtxt = torch.empty(G * Cn, self.arch.embed_dim, device=dlogits.device, dtype=torch.float32)
         _lib.check(lib.mvlpt_logits_grouped_bwd(self.h, _ptr(dlogits), _ptr(dtxt), _stream()), self.h, "logits_grouped_bwd")
         return dtxt
+
+    @_on_device
+    def logits_ranged_fwd(self, img_feat, txt_feat, logit_scale_exp: float, class_lo, class_hi, n_cls: int) -> torch.Tensor:
+        """The ranged head (mvlpt_logits_ranged_fwd): img [G, e] against txt [S, e] (rows of text_fwd_ranged over the same host ranges)
+        -> logits [G, n_cls], exactly 0 outside image g's range."""
+        img_feat = _req(img_feat, torch.float32, "img_feat")
+        txt_feat = _req(txt_feat, torch.float32, "txt_feat")
+        G = img_feat.shape[0]
+        lo, hi, S = _host_ranges(class_lo, class_hi, G, n_cls)
+        if txt_feat.shape[0] != S:
+            raise ValueError(f"ranged head: {txt_feat.shape[0]} text rows but the ranges hold {S} sequences")
+        logits = torch.empty(G, n_cls, device=img_feat.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_logits_ranged_fwd(self.h, _ptr(img_feat), _ptr(txt_feat), float(logit_scale_exp), lo, hi, G, n_cls,
+                                               _ptr(logits), _stream()), self.h, "logits_ranged_fwd")
+        self._head_state = (None, None, G, S)
+        return logits
+
+    @_on_device
+    def logits_ranged_bwd(self, dlogits, need_img: bool = False, need_txt: bool = True):
+        """(d img [G, e] w.r.t. the un-normalised image features or None, d txt [S, e] or None) of the last logits_ranged_fwd."""
+        if self._head_state is None:
+            raise RuntimeError("logits_ranged_bwd without logits_ranged_fwd")
+        _, _, G, S = self._head_state
+        dlogits = _req(dlogits, torch.float32, "dlogits")
+        e = self.arch.embed_dim
+        dimg = torch.empty(G, e, device=dlogits.device, dtype=torch.float32) if need_img else None
+        dtxt = torch.empty(S, e, device=dlogits.device, dtype=torch.float32) if need_txt else None
+        _lib.check(lib.mvlpt_logits_ranged_bwd(self.h, _ptr(dlogits), _ptr(dtxt), _ptr(dimg), _stream()), self.h, "logits_ranged_bwd")
+        return dimg, dtxt
 
     @_on_device
     def cross_entropy(self, logits, label, need_grad: bool = True):
@@ -446,6 +513,32 @@ def op_gather_ctx_grad_grouped(dx, ctx_pos, G: int) -> torch.Tensor:
     dctx = torch.empty(G, n, d, device=dx.device, dtype=torch.float32)
     _lib.check(lib.mvlpt_op_gather_ctx_grad_grouped(_ptr(dx.contiguous()), _ptr(ctx_pos.to(torch.int32).contiguous()), G, C_, L, d, n,
                                                     _ptr(dctx), _stream()), None, "op_gather_ctx_grad_grouped")
+    return dctx
+
+
+def op_assemble_prompts_ranged(prefix, suffix, ctx, layout, pos, class_lo, class_hi) -> torch.Tensor:
+    """x [S, L, d] of the ranged tower's entry (mvlpt_op_assemble_prompts_ranged); class_lo / class_hi: host sequences of length G."""
+    G, n, d = ctx.shape
+    C_, L = layout.shape
+    lo, hi, S = _host_ranges(class_lo, class_hi, G, C_)
+    x = torch.empty(S, L, d, device=ctx.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_assemble_prompts_ranged(_ptr(prefix.contiguous()), _ptr(suffix.contiguous()), _ptr(ctx.contiguous()), n,
+                                                    _ptr(layout.to(torch.int32).contiguous()), _ptr(pos.contiguous()), _ptr(x),
+                                                    lo, hi, G, C_, L, d, _stream()), None, "op_assemble_prompts_ranged")
+    return x
+
+
+def op_gather_ctx_grad_ranged(dx, ctx_pos, class_lo, class_hi) -> torch.Tensor:
+    """dctx [G, n_ctx, d] from dx [S, L, d] and ctx_pos [C, n_ctx] (mvlpt_op_gather_ctx_grad_ranged)."""
+    S_, L, d = dx.shape
+    C_, n = ctx_pos.shape
+    G = len(class_lo)
+    lo, hi, S = _host_ranges(class_lo, class_hi, G, C_)
+    if S != S_:
+        raise ValueError(f"dx has {S_} sequences but the ranges hold {S}")
+    dctx = torch.empty(G, n, d, device=dx.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_gather_ctx_grad_ranged(_ptr(dx.contiguous()), _ptr(ctx_pos.to(torch.int32).contiguous()), lo, hi, G, C_, L, d,
+                                                   n, _ptr(dctx), _stream()), None, "op_gather_ctx_grad_ranged")
     return dctx
 
 

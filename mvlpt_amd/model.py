@@ -196,7 +196,8 @@ class MultitaskVLPromptLearner(nn.Module):
         T = cfg.TRAINER.MVLPT
         coop_n_ctx, cocoop_n_ctx, vpt_n_ctx = T.COOP.N_CTX, T.COCOOP.N_CTX, T.VPT.N_CTX
         if cocoop_n_ctx != 0:
-            raise NotImplementedError("CoCoOp (COCOOP.N_CTX != 0) is outside the MI355X hot path (SURVEY §2.1 #5)")
+            raise NotImplementedError("COCOOP.N_CTX != 0 is not this class's route: image-conditioned prompts live in "
+                                      "mvlpt_amd.mvlpt_cocoop (MultitaskVLPromptLearner / CustomCLIP there; MVLPT.build_model picks them)")
         arch = clip_model.arch
         dtype = clip_model.dtype
         coop_ctx_dim, vpt_ctx_dim = arch.transformer_width, arch.vision_width

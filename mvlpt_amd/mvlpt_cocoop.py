@@ -1,0 +1,346 @@
+"""The MVLPT trainer's CoCoOp route (trainers/mvlpt.py with TRAINER.MVLPT.COCOOP.N_CTX != 0) on the HIP engine.
+
+`MVLPT.build_model` picks :class:`CustomCLIP` of this module iff ``cfg.TRAINER.MVLPT.COCOOP.N_CTX != 0``; every other configuration goes
+through `mvlpt_amd.model` exactly as before (whose classes keep refusing COCOOP.N_CTX != 0).  Class names, constructor arguments and
+``prompt_learner.state_dict()`` keys are the reference's (``cocoop_ctx``, ``meta_net.linear{1,2}.{weight,bias}``, ``token_prefix``,
+``token_suffix``, + ``vpt_embeddings[_deep]`` / ``vpt_proj.*`` with visual prompts), so checkpoints interoperate.
+
+What the route does (trainers/mvlpt.py:541-581): image tower (with visual prompts when VPT.N_CTX != 0) -> normalise -> ``meta_net`` ->
+``ctx_shifted = cocoop_ctx + bias`` (one context block per image) -> one text feature set PER IMAGE -> cosine logits -> per-task mask.
+The reference runs one text tower per image in a Python loop and multiplies every logit outside the image's task by 0.  Here
+
+* under ``DATASET.MULTITASK_LABEL_PERTASK`` image b runs ONLY the sequences of its own task's class range [lo_b, hi_b)
+  (mvlpt_text_fwd_ranged / mvlpt_logits_ranged_fwd): a masked logit is exactly 0 and carries no gradient, so its sequence is never
+  computed.  ``CustomCLIP.ranged_text = False`` selects the dense grouped tower (B x n_cls sequences) and a multiplicative mask
+  instead — the same logits, for comparison and as an escape hatch.  Without the per-task mask every range is [0, n_cls).
+* the batch is cut into chunks of consecutive images whose text tower fits ``max_text_workspace_bytes`` (sized over the chunk's OWN
+  sequence count, not B * n_cls).  ``forward`` returns logits, so the backward arrives later: with ONE chunk the forward saves its
+  activations and the backward uses them; with MORE than one chunk the forward runs without saving and the backward RE-RUNS every
+  chunk's text forward with saving right before that chunk's backward — one extra text forward per step, the price of keeping only
+  one chunk's activations alive.
+* ``meta_net``, the normalisation in front of it and ``ctx + bias`` stay on torch autograd (as in mvlpt_amd.cocoop); the text side is
+  one autograd node (image features, shifted contexts) -> logits whose backward hands out d ctx_shifted AND d image features (the
+  ranged head's dimg); the image tower with visual prompts is a second node whose incoming gradient is the sum autograd forms from the
+  head's dimg and the ``meta_net`` path.
+
+Deviations: parameters are fp32 masters for every COCOOP.PREC (the reference halves ``meta_net`` under fp16); COOP.N_CTX != 0
+together with COCOOP.N_CTX != 0 (a ``ctx`` the reference builds and never uses on this branch) is refused; step pipelining and class
+sharding do not apply to per-image text features.
+"""
+from __future__ import annotations
+
+import math
+from collections import OrderedDict
+from functools import reduce
+from operator import mul
+from typing import List, Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .cocoop import DEFAULT_MAX_TEXT_WORKSPACE_BYTES, MAX_SEQUENCES_PER_TOWER
+from .model import FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, build_prompt_layout
+from .model import MultitaskVLPromptLearner as _BasePromptLearner
+
+
+class MultitaskVLPromptLearner(_BasePromptLearner):
+    """trainers/mvlpt.py:138-325 for COCOOP.N_CTX != 0 (:260-289, :313-314).  The visual-prompt parameters and `forward_mvlpt_proj`
+    are the base class's; the text side is `cocoop_ctx` + `meta_net` with an "end" layout over `cocoop_n_ctx`."""
+
+    def __init__(self, cfg, classnames, clip_model: FrozenCLIP, pretokenized: Optional[PretokenizedPrompts] = None):
+        nn.Module.__init__(self)
+        n_cls = len(classnames)
+        T = cfg.TRAINER.MVLPT
+        cocoop_n_ctx, vpt_n_ctx = T.COCOOP.N_CTX, T.VPT.N_CTX
+        if cocoop_n_ctx == 0:
+            raise ValueError("mvlpt_amd.mvlpt_cocoop is the COCOOP.N_CTX != 0 route; use mvlpt_amd.model otherwise")
+        if T.COOP.N_CTX != 0:
+            raise NotImplementedError("COOP.N_CTX != 0 together with COCOOP.N_CTX != 0: the reference builds a `ctx` its logits never "
+                                      "depend on (trainers/mvlpt.py:556-571); set COOP.N_CTX 0")
+        arch = clip_model.arch
+        dtype = clip_model.dtype                                                        # fp32 masters (module docstring)
+        cocoop_ctx_dim, vpt_ctx_dim, vis_dim = arch.transformer_width, arch.vision_width, arch.embed_dim
+        clip_imsize, cfg_imsize = arch.image_resolution, cfg.INPUT.SIZE[0]
+        assert cfg_imsize == clip_imsize, f"cfg_imsize ({cfg_imsize}) must equal to clip_imsize ({clip_imsize})"
+
+        self.vpt_dropout = nn.Dropout(T.VPT.DROPOUT)                                    # :165
+        self.vpt_deep = T.VPT.DEEP
+        self.vpt_embeddings = None
+        self.vpt_embeddings_deep = None
+        if vpt_n_ctx != 0:                                                              # :167-201, as the base class
+            if T.VPT.PROJECT > -1:
+                vpt_dim = T.VPT.PROJECT
+                self.vpt_proj = nn.Linear(vpt_dim, vpt_ctx_dim, dtype=dtype)
+                nn.init.kaiming_normal_(self.vpt_proj.weight, a=0, mode="fan_out")
+            else:
+                vpt_dim = vpt_ctx_dim
+                self.vpt_proj = nn.Identity()
+            if T.VPT.CTX_INIT:
+                raise ValueError("CTX initiation scheme is not supported")            # :180-182
+            ps = arch.vision_patch_size
+            val = math.sqrt(6. / float(3 * reduce(mul, (ps, ps), 1) + vpt_dim))         # :186
+            self.vpt_embeddings = nn.Parameter(torch.zeros(1, vpt_n_ctx, vpt_dim, dtype=dtype))
+            nn.init.uniform_(self.vpt_embeddings.data, -val, val)
+            if self.vpt_deep:
+                self.vision_layers = arch.vision_layers
+                self.vpt_embeddings_deep = nn.Parameter(torch.zeros(arch.vision_layers - 1, vpt_n_ctx, vpt_dim, dtype=dtype))
+                nn.init.uniform_(self.vpt_embeddings_deep.data, -val, val)
+        self.ctx = None
+        self.mvlpt_proj = nn.Identity()                                                 # :235 (no COOP ctx: nothing to project)
+
+        ctx_init = T.COCOOP.CTX_INIT
+        if ctx_init:                                                                    # :262-270
+            ctx_init = ctx_init.replace("_", " ")
+            cocoop_n_ctx = len(ctx_init.split(" "))
+            ids = clip_model.tokenizer.tokenize(ctx_init)
+            with torch.no_grad():
+                ctx_vectors = clip_model.token_embedding(ids)[0, 1:1 + cocoop_n_ctx, :].to(dtype)
+            prompt_prefix = ctx_init
+        else:                                                                           # :271-275
+            ctx_vectors = torch.empty(cocoop_n_ctx, cocoop_ctx_dim, dtype=dtype)
+            nn.init.normal_(ctx_vectors, std=0.02)
+            prompt_prefix = " ".join(["X"] * cocoop_n_ctx)
+        self.cocoop_ctx = nn.Parameter(ctx_vectors)
+        self.meta_net = nn.Sequential(OrderedDict([                                     # :282-286
+            ("linear1", nn.Linear(vis_dim, vis_dim // 16)),
+            ("relu", nn.ReLU(inplace=True)),
+            ("linear2", nn.Linear(vis_dim // 16, cocoop_ctx_dim)),
+        ]))
+
+        if pretokenized is not None:
+            tokenized_prompts, name_lens = pretokenized.tokenized_prompts, pretokenized.name_lens
+        else:                                                                           # :292-305
+            tok = clip_model.tokenizer
+            names = [n.replace("_", " ") for n in classnames]
+            name_lens = [len(tok.encode(n)) for n in names]
+            prompts = [prompt_prefix + " " + n + "." for n in names]
+            if cfg.TRAINER.CUT_CONTEXTLEN:
+                max_length = min(clip_model.context_length, max(len(tok.encode(p)) + 2 for p in prompts))
+            else:
+                max_length = clip_model.context_length
+            tokenized_prompts = torch.cat([tok.tokenize(p, context_length=max_length) for p in prompts])
+        with torch.no_grad():
+            embedding = clip_model.token_embedding(tokenized_prompts).to(dtype)
+        self.register_buffer("token_prefix", embedding[:, :1, :].contiguous())                       # SOS
+        self.register_buffer("token_suffix", embedding[:, 1 + cocoop_n_ctx:, :].contiguous())       # CLS, EOS (:313-314)
+
+        self.n_cls, self.vpt_n_ctx, self.coop_n_ctx, self.cocoop_n_ctx = n_cls, vpt_n_ctx, 0, cocoop_n_ctx
+        self.tokenized_prompts = tokenized_prompts
+        self.name_lens = list(name_lens)
+        self.class_token_position = T.COOP.CLASS_TOKEN_POSITION
+        L = tokenized_prompts.shape[1]
+        # construct_prompts (:327-346) is cat([prefix, ctx, suffix]): the "end" layout of the HIP text tower
+        self.register_buffer("layout", build_prompt_layout(self.name_lens, cocoop_n_ctx, L, "end"), persistent=False)
+        self.register_buffer("eot", tokenized_prompts.argmax(dim=-1).to(torch.int32), persistent=False)
+        self.max_eot = int(self.eot.max())
+
+    def forward(self, im_features):
+        """forward_cocoop (:348-374) up to the shifted contexts [B, n_ctx, ctx_dim]; the prompts are assembled by the HIP tower."""
+        bias = self.meta_net(im_features).unsqueeze(1)       # (batch, 1, ctx_dim)
+        return self.cocoop_ctx.unsqueeze(0) + bias           # (batch, n_ctx, ctx_dim)
+
+
+def class_ranges(task, start, end, B: int, n_cls: int) -> Tuple[List[int], List[int]]:
+    """Host class range [lo_b, hi_b) of every image: its task's range (`start` / `end` indexed by task id, trainers/mvlpt.py:575-576)
+    or [0, n_cls) without the per-task mask (`start is None`).  `task` stays on the CPU: nothing is read back from the device."""
+    if start is None:
+        return [0] * B, [n_cls] * B
+    t = task.cpu().long() if torch.is_tensor(task) else torch.as_tensor(task).long()
+    if t.shape != (B,):
+        raise ValueError(f"task must hold one task id per image ({B}), got shape {tuple(t.shape)}")
+    return start[t].tolist(), end[t].tolist()
+
+
+def chunk_bounds(widths: List[int], fits) -> List[Tuple[int, int, int]]:
+    """Cut the images into chunks of consecutive images (g0, g1, S): greedily the longest run whose sequence count S = sum of the
+    range widths satisfies `fits(S)`; a single image that does not fit still makes a chunk of its own.  S may be 0 (empty ranges only)."""
+    out, g0, S = [], 0, 0
+    for g, w in enumerate(widths):
+        if g > g0 and S + w > 0 and not fits(S + w):
+            out.append((g0, g, S))
+            g0, S = g, 0
+        S += w
+    out.append((g0, len(widths), S))
+    return out
+
+
+def _text_inputs(model, pl):
+    """token_suffix / layout handed to the text tower; `trim_text_to_eot` as in mvlpt_amd.model._text_inputs."""
+    if not model.trim_text_to_eot:
+        return pl.token_suffix, pl.layout
+    L_eff = pl.max_eot + 1
+    return pl.token_suffix[:, :L_eff - 1 - pl.cocoop_n_ctx], pl.layout[:, :L_eff]
+
+
+class _ImageTowerFn(torch.autograd.Function):
+    """The image tower with visual prompts as an autograd node: mvlpt_image_fwd(save_for_bwd) / mvlpt_image_bwd."""
+
+    @staticmethod
+    def forward(fctx, model: "CustomCLIP", image, vpt_emb, vpt_deep_emb, grad_on=True):
+        need = grad_on and bool(fctx.needs_input_grad[2] or fctx.needs_input_grad[3])
+        img = model.engine.image_fwd(image, vpt_emb, vpt_deep_emb, save_for_bwd=need)
+        fctx.model, fctx.generation, fctx.vpt_shape = model, model._fwd_generation, vpt_emb.shape
+        return img
+
+    @staticmethod
+    def backward(fctx, dimg):
+        if fctx.generation != fctx.model._fwd_generation:
+            raise RuntimeError("backward of a stale forward: the engine holds the saved activations of the most recent "
+                               "CustomCLIP.forward only (call backward before the next forward)")
+        dvpt, ddeep = fctx.model.engine.image_bwd(dimg.contiguous())
+        return None, None, dvpt.view(fctx.vpt_shape), ddeep, None
+
+
+class _TextSideFn(torch.autograd.Function):
+    """(image features [B, e], shifted contexts [B, n_ctx, dt]) -> logits [B, n_cls]: per chunk the ranged (or dense grouped) text
+    tower and the ranged head.  See the module docstring for the one-chunk / recompute arrangement of the backward."""
+
+    @staticmethod
+    def _chunk_forward(model, img, ctx_shifted, lo, hi, g0, g1, save):
+        eng, pl = model.engine, model.prompt_learner
+        suffix, layout = _text_inputs(model, pl)
+        clo, chi = lo[g0:g1], hi[g0:g1]
+        if all(a == 0 and b == pl.n_cls for a, b in zip(clo, chi)):     # every range full: the grouped tower (same kernels, same bits)
+            txt = eng.text_fwd_grouped(pl.token_prefix, suffix, ctx_shifted[g0:g1], layout, pl.eot, save_for_bwd=save)
+        else:
+            txt = eng.text_fwd_ranged(pl.token_prefix, suffix, ctx_shifted[g0:g1], layout, pl.eot, clo, chi, save_for_bwd=save)
+        return eng.logits_ranged_fwd(img[g0:g1], txt, model.logit_scale_exp, clo, chi, pl.n_cls)
+
+    @staticmethod
+    def forward(fctx, model: "CustomCLIP", img, ctx_shifted, lo, hi, mask, grad_on=True):
+        pl = model.prompt_learner
+        need_img = grad_on and bool(fctx.needs_input_grad[1])
+        need_ctx = grad_on and bool(fctx.needs_input_grad[2])
+        need = need_img or need_ctx
+        L = _text_inputs(model, pl)[1].shape[1]
+        chunks = model.chunks(lo, hi, L, save_for_bwd=need)
+        save = need and len(chunks) == 1
+        B = ctx_shifted.shape[0]
+        logits = torch.empty(B, pl.n_cls, device=img.device, dtype=torch.float32)
+        for g0, g1, S in chunks:
+            if S == 0:
+                logits[g0:g1] = 0.0
+            else:
+                logits[g0:g1] = _TextSideFn._chunk_forward(model, img, ctx_shifted, lo, hi, g0, g1, save)
+        if mask is not None:
+            logits = logits * mask                           # the dense route's select_index (trainers/mvlpt.py:581)
+        model.last_chunks, model.last_sequences = len(chunks), sum(c[2] for c in chunks)
+        model.last_recompute = need and len(chunks) > 1
+        fctx.model, fctx.lo, fctx.hi, fctx.chunks, fctx.mask = model, lo, hi, chunks, mask
+        fctx.need_img, fctx.need_ctx, fctx.saved_in_engine = need_img, need_ctx, save
+        fctx.generation = model._fwd_generation
+        if need:
+            fctx.save_for_backward(img, ctx_shifted)
+        return logits
+
+    @staticmethod
+    def backward(fctx, dlogits):
+        model = fctx.model
+        eng = model.engine
+        if fctx.saved_in_engine and fctx.generation != model._fwd_generation:
+            raise RuntimeError("backward of a stale forward: the engine holds the saved activations of the most recent "
+                               "CustomCLIP.forward only (call backward before the next forward)")
+        img, ctx_shifted = fctx.saved_tensors
+        dl = dlogits.contiguous() if fctx.mask is None else (dlogits * fctx.mask).contiguous()
+        dimg = torch.zeros_like(img) if fctx.need_img else None
+        dctx = torch.zeros_like(ctx_shifted) if fctx.need_ctx else None
+        for g0, g1, S in fctx.chunks:
+            if S == 0:
+                continue                                     # empty ranges only: no logit depends on anything
+            if not fctx.saved_in_engine:                     # more than one chunk: this chunk's forward again, saved this time
+                _TextSideFn._chunk_forward(model, img, ctx_shifted, fctx.lo, fctx.hi, g0, g1, fctx.need_ctx)
+            di, dtxt = eng.logits_ranged_bwd(dl[g0:g1], need_img=fctx.need_img, need_txt=fctx.need_ctx)
+            if fctx.need_img:
+                dimg[g0:g1] = di
+            if fctx.need_ctx:
+                dctx[g0:g1] = eng.text_bwd(dtxt)
+        return None, dimg, dctx, None, None, None, None
+
+
+class CustomCLIP(nn.Module):
+    """trainers/mvlpt.py:517-583 for COCOOP.N_CTX != 0: `forward(image, task=None)` returns the logits [B, n_cls]."""
+
+    def __init__(self, cfg, classnames, clip_model: FrozenCLIP, dm=None, pretokenized: Optional[PretokenizedPrompts] = None):
+        super().__init__()
+        self.prompt_learner = MultitaskVLPromptLearner(cfg, classnames, clip_model, pretokenized)
+        self.tokenized_prompts = self.prompt_learner.tokenized_prompts
+        self.clip_model = clip_model
+        self.engine = clip_model.engine
+        self.logit_scale = clip_model.logit_scale
+        self.logit_scale_exp = float(clip_model.logit_scale.exp())
+        self.dtype = clip_model.dtype
+        self.trim_text_to_eot = False        # mvlpt_amd.model.CustomCLIP's switch, same default
+        self.ranged_text = True              # False: dense grouped tower (B x n_cls sequences) + multiplicative mask
+        self.max_text_workspace_bytes = DEFAULT_MAX_TEXT_WORKSPACE_BYTES
+        # Precision: the image features are meta_net's input and every text row carries a gradient; as
+        # mvlpt_amd.cocoop.CustomCLIP, raise the engine's default mode to split_all and leave an explicit "fast" alone
+        if self.engine.precision == _lib.PREC_SPLIT_GRAD:
+            self.engine.set_precision("split_all")
+        self.last_ncorrect = None
+        self.last_chunks = self.last_sequences = 0
+        self.last_recompute = False
+        self._fwd_generation = 0
+        self.multi_task_label_pertask = cfg.DATASET.MULTITASK_LABEL_PERTASK
+        self.class_index_pertask_start = self.class_index_pertask_end = None
+        if self.multi_task_label_pertask:
+            # indexed by task id; sized num_classes as in the reference (:529-537); kept on the CPU
+            start, end = torch.arange(dm._num_classes), torch.arange(dm._num_classes)
+            s = 0
+            for i, task in enumerate(dm._task_names):
+                start[i] = s
+                s += len(dm._labelmap[task])
+                end[i] = s
+            self.class_index_pertask_start, self.class_index_pertask_end = start, end
+
+    # ---- what does not apply to per-image text features
+    def enable_class_sharding(self, rank: int, world: int) -> None:
+        if world > 1:
+            raise NotImplementedError("class sharding does not apply to the COCOOP.N_CTX != 0 route: every image has its own text "
+                                      "features, there is no shared [n_cls, e] matrix to shard")
+
+    def prefetch_image_features(self, image) -> bool:
+        """Step pipelining is off on this route (the image features feed meta_net, and with visual prompts they are not constants)."""
+        return False
+
+    def drop_prefetch(self) -> None:
+        pass
+
+    # ---- chunking
+    def chunks(self, lo: List[int], hi: List[int], L: int, save_for_bwd: bool) -> List[Tuple[int, int, int]]:
+        """[(g0, g1, S)]: consecutive images whose text tower over S = sum(hi - lo) sequences fits `max_text_workspace_bytes`."""
+        eng, budget = self.engine, self.max_text_workspace_bytes
+        return chunk_bounds([b - a for a, b in zip(lo, hi)],
+                            lambda S: S <= MAX_SEQUENCES_PER_TOWER and eng.text_workspace_bytes(S, L, save_for_bwd) <= budget)
+
+    def vpt_dropout_masks(self, B):
+        from .model import CustomCLIP as _Base
+        return _Base.vpt_dropout_masks(self, B)
+
+    def forward(self, image, task=None):
+        pl = self.prompt_learner
+        B = image.shape[0]
+        self._fwd_generation += 1
+        _, vpt_emb, vpt_emb_deep = pl.forward_mvlpt_proj(self.dtype)             # :541 (no COOP ctx: the parameters themselves)
+        if vpt_emb is not None:
+            proj = pl.vpt_proj                                                   # :424, :77, as mvlpt_amd.model.CustomCLIP.forward
+            vpt_emb = proj(vpt_emb)
+            if vpt_emb_deep is not None:
+                vpt_emb_deep = proj(vpt_emb_deep)
+            self.engine.set_vpt_dropout(self.vpt_dropout_masks(B))
+            img = _ImageTowerFn.apply(self, image, vpt_emb, vpt_emb_deep, torch.is_grad_enabled())
+        else:
+            img = self.engine.image_fwd(image, None, None, save_for_bwd=False)   # frozen, prompt-free image tower
+        imf = img / img.norm(dim=-1, keepdim=True)                               # :561 (meta_net's input)
+        ctx_shifted = pl(imf)                                                    # :563, :361-364
+        lo, hi = class_ranges(task, self.class_index_pertask_start, self.class_index_pertask_end, B, pl.n_cls)
+        mask = None
+        if not self.ranged_text and self.multi_task_label_pertask:
+            idx = torch.arange(pl.n_cls).unsqueeze(0)
+            mask = ((idx >= torch.tensor(lo).unsqueeze(1)) & (idx < torch.tensor(hi).unsqueeze(1))).float().to(image.device)
+            lo, hi = [0] * B, [pl.n_cls] * B
+        return _TextSideFn.apply(self, img, ctx_shifted, lo, hi, mask, torch.is_grad_enabled())
+
+    def cross_entropy(self, logits, label):
+        """HIP replacement for ``F.cross_entropy(output, label)`` (trainers/mvlpt.py:931)."""
+        return _CrossEntropyFn.apply(self, logits, label)

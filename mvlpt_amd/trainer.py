@@ -401,6 +401,9 @@ class MVLPT(TrainerX):
                  fp16 mode; there is no GradScaler object, self.scaler stays None)
           fp32 : every tower in the split-operand mode, forward-only towers included (~22-bit products)."""
         assert cfg.TRAINER.MVLPT.PREC in ["fp16", "fp32", "amp"]        # :835-836
+        if cfg.TRAINER.MVLPT.COCOOP.N_CTX != 0:
+            # the image-conditioned route (mvlpt_amd.mvlpt_cocoop): all three run with split operands in every tower, see CustomCLIP there
+            assert cfg.TRAINER.MVLPT.COCOOP.PREC in ["fp16", "fp32", "amp"]
 
     def build_data_loader(self):
         self.multi_task = self.cfg.DATASET.MULTITASK
@@ -409,7 +412,9 @@ class MVLPT(TrainerX):
         if dm is None:
             raise ValueError("pass a data manager (e.g. SyntheticDataManager); dataset readers are out of scope")
         # the look-ahead lives in the loader (see LookAheadLoader): a plain `for batch in self.train_loader_x` pipelines
-        self.train_loader_x = LookAheadLoader(dm.train_loader_x, self) if self.cfg.TRAINER.MVLPT.STEP_PIPELINING else dm.train_loader_x
+        # (no look-ahead with COCOOP.N_CTX != 0: the image features feed meta_net and may depend on visual prompts)
+        pipelined = self.cfg.TRAINER.MVLPT.STEP_PIPELINING and self.cfg.TRAINER.MVLPT.COCOOP.N_CTX == 0
+        self.train_loader_x = LookAheadLoader(dm.train_loader_x, self) if pipelined else dm.train_loader_x
         self.train_loader_u = dm.train_loader_u
         self.val_loader, self.test_loader = dm.val_loader, dm.test_loader
         self.num_classes, self.num_source_domains, self.lab2cname = dm.num_classes, dm.num_source_domains, dm.lab2cname
@@ -427,8 +432,14 @@ class MVLPT(TrainerX):
         # PREC (see check_cfg): fp16 / amp -> split operands only where gradients flow; fp32 -> in every tower;
         # GRAD_PRECISION = "fast" (not in the reference) drops the split operands altogether (gradients within ~4e-3)
         prec = "split_all" if cfg.TRAINER.MVLPT.PREC == "fp32" else cfg.TRAINER.MVLPT.GRAD_PRECISION
+        model_cls = CustomCLIP
+        if cfg.TRAINER.MVLPT.COCOOP.N_CTX != 0:
+            # image-conditioned prompts: the ranged route of mvlpt_amd.mvlpt_cocoop (imported here: that module imports this one)
+            from .mvlpt_cocoop import CustomCLIP as model_cls
+            if cfg.TRAINER.MVLPT.COCOOP.PREC == "fp32":
+                prec = "split_all"
         clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec)
-        self.model = CustomCLIP(cfg, classnames, clip_model, dm=self.dm, pretokenized=pretok)
+        self.model = model_cls(cfg, classnames, clip_model, dm=self.dm, pretokenized=pretok)
         for name, param in self.model.named_parameters():               # :855-858 (the towers hold no nn.Parameters)
             if "prompt_learner" not in name:
                 param.requires_grad_(False)

@@ -287,6 +287,41 @@ int mvlpt_op_assemble_prompts_ranged(const float* prefix, const float* suffix, c
 int mvlpt_op_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos, const int32_t* class_lo, const int32_t* class_hi, int G, int C,
                                     int L, int d, int n_ctx, float* dctx, mvlpt_stream_t stream);
 
+/* ---- the dense head's neighbours and the fp32 glue of the towers at kernel level (tests/test_hip_head.py, test_hip_glue.py) ----
+ * sgemm_bt: C[M,N] = alpha * A[M,K] * Bt[N,K]^T in fp32 (the two projections next to the logits and their backward); alpha_dev is a
+ *   DEVICE float or NULL (1).  K % 16 == 0 and N % 4 == 0, anything else is refused.
+ * grad_scale: scale_dev (3 device floats) = {2^k, 2^-k, amax|v|} with k = exponent(target) - exponent(amax) clamped to [-60, 60]
+ *   (frexp exponents), 2^k = 1 when amax is 0, inf or NaN.  n <= 2^17 on a 16-byte aligned pointer runs as one workgroup, anything
+ *   else as amax + finish; both give the same three floats.
+ * reduce_prompt_rows: out [n,d] = scale_dev[1] (or 1 when NULL) * sum_b dx32[b, row0 + j, :] (* vmask [B,n,d] when given) over
+ *   dx32 [B,L,d]; zero_after != 0 clears those rows of dx32 and of its 16-bit copy dx16 (may be NULL; split16 0: [B*L, d], 1: hi|lo pair
+ *   [B*L, 2d], 2: mixed pair at the same pitch) afterwards.  d % 4 == 0.
+ * gather_ctx_grad: dctx [n_ctx,d] = scale_dev[1] * sum_c dx[c, ctx_pos[c,j], :] (per_class = 0) or dctx [C,n_ctx,d] without the sum
+ *   (per_class = 1); dx [C,L,d], ctx_pos int32 [C,n_ctx] with entries in [0, L).
+ * attention_bwd_cls: the attention backward when only query 0 of every sequence carries a gradient: qkv [N*L, 3*H*64] 16-bit,
+ *   o_cls / do_cls [N, H*64] (row 0 of every sequence), lse [N*H*L] -> dqkv [N*L, 3*H*64], every element written (dQ rows > 0 are 0).
+ * copy_rows: dst[r] = src[idx[r]] (scatter = 0) or dst[idx[r]] = src[r] (scatter = 1) for `rows` rows of row_bytes (% 16 == 0).
+ * overwrite_rows: x[b, 1 + j, :] = rows[j, :] (* vmask[b, j, :]) for j < n, x [B,L,d] fp32.
+ * assemble_tokens: the image tower's entry, x [B, 1 + n_vpt + G2, d]: row 0 = LN(cls + pos[0]), rows 1..n_vpt = vpt (* vmask [B,n_vpt,d]),
+ *   the rest LN(patch_emb[b, i] + pos[1 + i]); pos [1 + G2, d].
+ * assemble_prompts: the text tower's entry (arguments of mvlpt_text_fwd): x [C,L,d] = prompts + pos, eot_rows int32 [C] = c * L + eot[c],
+ *   and, when n_ctx > 0, ctx_pos int32 [C,n_ctx] = position of context row j in class c's sequence. */
+int mvlpt_op_sgemm_bt(const float* A, const float* Bt, float* C, int M, int N, int K, const float* alpha_dev, mvlpt_stream_t stream);
+int mvlpt_op_grad_scale(const float* v, int64_t n, float target, float* scale_dev, mvlpt_stream_t stream);
+int mvlpt_op_reduce_prompt_rows(int dtype, float* dx32, void* dx16, int B, int L, int d, int row0, int n, float* out,
+                                const float* scale_dev, int zero_after, int split16, const float* vmask, mvlpt_stream_t stream);
+int mvlpt_op_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C, int L, int d, int n_ctx, int per_class, float* dctx,
+                             const float* scale_dev, mvlpt_stream_t stream);
+int mvlpt_op_attention_bwd_cls(int dtype, const void* qkv, const void* o_cls, const void* do_cls, const float* lse, void* dqkv, int N,
+                               int L, int H, mvlpt_stream_t stream);
+int mvlpt_op_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, mvlpt_stream_t stream);
+int mvlpt_op_overwrite_rows(const float* rows, int n, float* x, int B, int L, int d, const float* vmask, mvlpt_stream_t stream);
+int mvlpt_op_assemble_tokens(const float* patch_emb, const float* cls, const float* pos, const float* ln_g, const float* ln_b,
+                             const float* vpt, int n_vpt, const float* vmask, float* x, int B, int G2, int d, mvlpt_stream_t stream);
+int mvlpt_op_assemble_prompts(const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
+                              const int32_t* layout, const float* pos, const int32_t* eot, float* x, int32_t* ctx_pos, int32_t* eot_rows,
+                              int C, int L, int d, mvlpt_stream_t stream);
+
 /* ---- input pipeline ("next" row f3 of the scope table) -------------------------------------------------------
  * Replaces the per-image CPU transform the reference runs in DataLoader workers: Dassl `build_transform` with
  * INPUT.TRANSFORMS = random_resized_crop / random_flip / normalize, INTERPOLATION bicubic, CLIP PIXEL_MEAN/STD

@@ -102,6 +102,15 @@ SIGNATURES = {
     "mvlpt_op_gather_ctx_grad_grouped": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mvlpt_op_assemble_prompts_ranged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_gather_ctx_grad_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mvlpt_op_sgemm_bt": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mvlpt_op_grad_scale": (_i, [_vp, C.c_int64, _f, _vp, _vp]),
+    "mvlpt_op_reduce_prompt_rows": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "mvlpt_op_gather_ctx_grad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mvlpt_op_attention_bwd_cls": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mvlpt_op_copy_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mvlpt_op_overwrite_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "mvlpt_op_assemble_tokens": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "mvlpt_op_assemble_prompts": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvlpt_preprocess": (_i, [_vp, _vp, C.c_int64, C.POINTER(MvlptImageDesc), _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _i, _vp, _vp]),
     "mvlpt_profile_begin": (_i, [_vp, _i]),
     "mvlpt_profile_pause": (_i, [_vp, _i]),

@@ -552,45 +552,52 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs a) {
 //   delta = dO.O,  p_j = exp(q.k_j / 8 - lse),  dp_j = dO.v_j,  ds_j = p_j (dp_j - delta) / 8,
 //   dV_j = p_j dO,  dK_j = ds_j q,  dQ_0 = sum_j ds_j k_j,  dQ_{i>0} = 0.
 // Four lanes share a key (16 of the 64 head dimensions each), a wave covers 16 keys, a block 64 keys per sweep.
+// delta = dO.O and dp_j = dO.v_j go through the SAME chain (cls_dot16: 16 fused multiply-adds per lane, then the two shuffles), so where
+// the softmax sits on a single key (O = v_j; a one-token sequence) dp_j - delta cancels to exactly 0, not to the last bits by which two
+// summation orders differ.
+template <typename T>
+__device__ __forceinline__ float cls_dot16(const float* g16, const typename Vec<T>::v8& a0, const typename Vec<T>::v8& a1) {
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { s = fmaf(g16[e], to_f32<T>(a0[e]), s); s = fmaf(g16[e + 8], to_f32<T>(a1[e]), s); }
+  s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64);
+  return s;
+}
 template <typename T>
 __global__ __launch_bounds__(256) void attn_bwd_cls_kernel(const T* __restrict__ qkv, const T* __restrict__ o_cls,
                                                            const T* __restrict__ do_cls, const float* __restrict__ lse,
                                                            T* __restrict__ dqkv, int N, int L, int H) {
   using v8 = typename Vec<T>::v8;
-  __shared__ float sq[64], sdo[64], red[4][64], sdelta;
+  __shared__ float sq[64], sdo[64], red[4][64];
   const int n = blockIdx.x / H, h = blockIdx.x % H, d = H * 64, tid = threadIdx.x;
   const size_t ld = (size_t)3 * d;
   const T* base = qkv + (size_t)n * L * ld + h * 64;
   T* gbase = dqkv + (size_t)n * L * ld + h * 64;
   if (tid < 64) {
     sq[tid] = to_f32<T>(base[tid]);
-    const float g = to_f32<T>(do_cls[(size_t)n * d + h * 64 + tid]);
-    sdo[tid] = g;
-    const float v = wave_sum(g * to_f32<T>(o_cls[(size_t)n * d + h * 64 + tid]));
-    if (tid == 0) sdelta = v;
+    sdo[tid] = to_f32<T>(do_cls[(size_t)n * d + h * 64 + tid]);
   }
   __syncthreads();
-  const float delta = sdelta, l0 = lse[((size_t)n * H + h) * L];
+  const float l0 = lse[((size_t)n * H + h) * L];
   const int lane = tid & 63, wave = tid >> 6, kg = lane >> 2, ch = lane & 3;
   float q16[16], g16[16], dqa[16];
 #pragma unroll
   for (int e = 0; e < 16; ++e) { q16[e] = sq[ch * 16 + e]; g16[e] = sdo[ch * 16 + e]; dqa[e] = 0.f; }
+  const T* op = o_cls + (size_t)n * d + h * 64 + ch * 16;
+  const float delta = cls_dot16<T>(g16, *(const v8*)op, *(const v8*)(op + 8));
   for (int j0 = wave * 16; j0 < L; j0 += 64) {
     const int j = j0 + kg;
     const int jc = j < L ? j : L - 1;
     const T* kp = base + (size_t)jc * ld + d + ch * 16;
     const v8 k0 = *(const v8*)kp, k1 = *(const v8*)(kp + 8);
     const v8 v0 = *(const v8*)(kp + d), v1 = *(const v8*)(kp + d + 8);
-    float k16[16], sdot = 0.f, dp = 0.f;
+    float k16[16], sdot = 0.f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      k16[e] = to_f32<T>(k0[e]); k16[e + 8] = to_f32<T>(k1[e]);
-      dp += g16[e] * to_f32<T>(v0[e]) + g16[e + 8] * to_f32<T>(v1[e]);
-    }
+    for (int e = 0; e < 8; ++e) { k16[e] = to_f32<T>(k0[e]); k16[e + 8] = to_f32<T>(k1[e]); }
+    const float dp = cls_dot16<T>(g16, v0, v1);
 #pragma unroll
     for (int e = 0; e < 16; ++e) sdot += q16[e] * k16[e];
     sdot += __shfl_xor(sdot, 1, 64); sdot += __shfl_xor(sdot, 2, 64);
-    dp += __shfl_xor(dp, 1, 64); dp += __shfl_xor(dp, 2, 64);
     const float pj = j < L ? __expf(sdot * 0.125f - l0) : 0.f;
     const float ds = pj * (dp - delta) * 0.125f;
     v8 wk[2], wv[2], wz[2];

@@ -1745,6 +1745,69 @@ int mvlpt_op_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos, con
   return 0;
 }
 
+// The dense head's neighbours and the fp32 glue without a tower (tests): the launchers the towers call, unchanged.
+int mvlpt_op_sgemm_bt(const float* A, const float* Bt, float* Cm, int M, int N, int K, const float* alpha_dev, mvlpt_stream_t stream) {
+  if (!A || !Bt || !Cm) { g_create_err = "op_sgemm_bt: null argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_sgemm_bt(A, Bt, Cm, M, N, K, alpha_dev, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_grad_scale(const float* v, int64_t n, float target, float* scale_dev, mvlpt_stream_t stream) {
+  if (!v || !scale_dev || n <= 0 || !(target > 0.f)) { g_create_err = "op_grad_scale: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_grad_scale(v, (size_t)n, target, scale_dev, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_reduce_prompt_rows(int dtype, float* dx32, void* dx16, int B, int L, int d, int row0, int n, float* out,
+                                const float* scale_dev, int zero_after, int split16, const float* vmask, mvlpt_stream_t stream) {
+  if (!dx32 || !out || B <= 0 || d <= 0 || n <= 0 || row0 < 0 || row0 + n > L || split16 < 0 || split16 > 2) {
+    g_create_err = "op_reduce_prompt_rows: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_reduce_prompt_rows(dtype, dx32, dx16, B, L, d, row0, n, out, scale_dev, zero_after, (hipStream_t)stream, split16, vmask));
+  return 0;
+}
+int mvlpt_op_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C, int L, int d, int n_ctx, int per_class, float* dctx,
+                             const float* scale_dev, mvlpt_stream_t stream) {
+  if (!dx || !ctx_pos || !dctx || C <= 0 || L <= 0 || n_ctx <= 0 || d <= 0) {
+    g_create_err = "op_gather_ctx_grad: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_gather_ctx_grad(dx, ctx_pos, C, L, d, n_ctx, per_class, dctx, scale_dev, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_attention_bwd_cls(int dtype, const void* qkv, const void* o_cls, const void* do_cls, const float* lse, void* dqkv, int N,
+                               int L, int H, mvlpt_stream_t stream) {
+  if (!qkv || !o_cls || !do_cls || !lse || !dqkv) { g_create_err = "op_attention_bwd_cls: null argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_attn_bwd_cls(dtype, qkv, o_cls, do_cls, lse, dqkv, N, L, H, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, mvlpt_stream_t stream) {
+  if (!src || !dst || !idx || rows <= 0 || row_bytes <= 0) { g_create_err = "op_copy_rows: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_copy_rows(src, dst, idx, rows, row_bytes, scatter, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_overwrite_rows(const float* rows, int n, float* x, int B, int L, int d, const float* vmask, mvlpt_stream_t stream) {
+  if (!rows || !x || n <= 0 || B <= 0 || 1 + n > L || d <= 0 || d % 4) {
+    g_create_err = "op_overwrite_rows: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_overwrite_rows(rows, n, x, B, L, d, (hipStream_t)stream, vmask));
+  return 0;
+}
+int mvlpt_op_assemble_tokens(const float* patch_emb, const float* cls, const float* pos, const float* ln_g, const float* ln_b,
+                             const float* vpt, int n_vpt, const float* vmask, float* x, int B, int G2, int d, mvlpt_stream_t stream) {
+  if (!patch_emb || !cls || !pos || !ln_g || !ln_b || !x || B <= 0 || G2 <= 0 || d <= 0 || n_vpt < 0 || (n_vpt > 0 && !vpt) ||
+      (vmask && n_vpt == 0)) {
+    g_create_err = "op_assemble_tokens: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_assemble_tokens(patch_emb, cls, pos, ln_g, ln_b, vpt, n_vpt, x, B, G2, d, (hipStream_t)stream, vmask));
+  return 0;
+}
+int mvlpt_op_assemble_prompts(const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
+                              const int32_t* layout, const float* pos, const int32_t* eot, float* x, int32_t* ctx_pos, int32_t* eot_rows,
+                              int C, int L, int d, mvlpt_stream_t stream) {
+  if (!prefix || !suffix || !layout || !pos || !eot || !x || !eot_rows || C <= 0 || n_ctx < 0 || L < n_ctx + 1 || d <= 0 ||
+      (n_ctx > 0 && (!ctx || !ctx_pos))) {
+    g_create_err = "op_assemble_prompts: null/invalid argument"; return MVLPT_ERR_ARG; }
+  hipStream_t s = (hipStream_t)stream;
+  OPCHK(launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, pos, x, C, L, d, s));
+  OPCHK(launch_eot_rows(eot, eot_rows, C, L, s));
+  OPCHK(launch_build_ctx_pos(layout, ctx_pos, C, L, n_ctx, s));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ input pipeline
 int mvlpt_preprocess(void* h, const uint8_t* src, int64_t src_bytes, const MvlptImageDesc* descs, int B, int out_h, int out_w,
                      const float* mean, const float* stdv, void* out, int out_dtype, uint8_t* out_u8, mvlpt_stream_t stream) {

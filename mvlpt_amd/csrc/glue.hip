@@ -768,11 +768,20 @@ hipError_t launch_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos
 // underflows); prompt gradients are multiplied by 2^-k when they are reduced.  Single block, deterministic.
 // stage 1: amax over many blocks (max is order-independent: atomicMax on the bit pattern of |v| is deterministic);
 // stage 2: one thread turns it into the power-of-two scale.  scale_dev = {scale, 1/scale, amax bits (scratch)}.
+// The maximum is taken over the BIT PATTERNS of |v| (for non-negative floats the same order, with inf and NaN on top): fmaxf returns
+// its other operand when one is a NaN, so a float maximum would lose a NaN and scale by the finite rest.
+__device__ __forceinline__ unsigned abs_bits(float x) { return __float_as_uint(fabsf(x)); }
+__device__ __forceinline__ unsigned umax(unsigned a, unsigned b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned wave_umax(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = umax(v, (unsigned)__shfl_xor((int)v, o, 64));
+  return v;
+}
 __global__ __launch_bounds__(256) void grad_amax_kernel(const float* __restrict__ v, size_t n, float* scale_dev) {
-  float m = 0.f;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = fmaxf(m, fabsf(v[i]));
-  m = wave_max(m);
-  if ((threadIdx.x & 63) == 0) atomicMax((unsigned*)(scale_dev + 2), __float_as_uint(m));   // m >= 0 (NaN/inf sort on top)
+  unsigned m = 0;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = umax(m, abs_bits(v[i]));
+  m = wave_umax(m);
+  if ((threadIdx.x & 63) == 0) atomicMax((unsigned*)(scale_dev + 2), m);
 }
 __global__ void grad_scale_finish_kernel(float target, float* scale_dev) {
   const float m = __uint_as_float(*(const unsigned*)(scale_dev + 2));
@@ -789,19 +798,19 @@ __global__ void grad_scale_finish_kernel(float target, float* scale_dev) {
 // the step's own call (dfeat of the text / image tower: C x e or B x e values, a few hundred KB) as ONE launch of one workgroup:
 // memset + 50-block amax + finish were three launches and ~25 us on the text tower's critical chain
 __global__ __launch_bounds__(1024) void grad_scale_small_kernel(const float* __restrict__ v, int n, float target, float* scale_dev) {
-  __shared__ float part[16];
-  float m = 0.f;
+  __shared__ unsigned part[16];
+  unsigned m = 0;
   for (int i = threadIdx.x * 4; i < n; i += 4096) {
-    if (i + 4 <= n) { const f32x4 q = *(const f32x4*)(v + i); m = fmaxf(fmaxf(m, fmaxf(fabsf(q[0]), fabsf(q[1]))), fmaxf(fabsf(q[2]), fabsf(q[3]))); }
-    else for (int k = i; k < n; ++k) m = fmaxf(m, fabsf(v[k]));
+    if (i + 4 <= n) { const f32x4 q = *(const f32x4*)(v + i); m = umax(umax(m, umax(abs_bits(q[0]), abs_bits(q[1]))), umax(abs_bits(q[2]), abs_bits(q[3]))); }
+    else for (int k = i; k < n; ++k) m = umax(m, abs_bits(v[k]));
   }
-  m = wave_max(m);
+  m = wave_umax(m);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
-    // NaN / inf must surface as in the two-stage version (atomicMax on the bit pattern): compare bit patterns of the non-negative values
+    // NaN / inf surface as in the two-stage version (atomicMax on the bit pattern)
     unsigned mb = 0;
-    for (int w = 0; w < 16; ++w) { const unsigned b = __float_as_uint(part[w]); mb = b > mb ? b : mb; }
+    for (int w = 0; w < 16; ++w) mb = umax(mb, part[w]);
     const float mm = __uint_as_float(mb);
     float sc = 1.0f;
     if (mm > 0.f && isfinite(mm)) {

@@ -542,6 +542,113 @@ def op_gather_ctx_grad_ranged(dx, ctx_pos, class_lo, class_hi) -> torch.Tensor:
     return dctx
 
 
+def op_sgemm_bt(A, Bt, alpha=None) -> torch.Tensor:
+    """fp32 C [M, N] = alpha * A [M, K] @ Bt [N, K]^T (mvlpt_op_sgemm_bt); alpha: a device float tensor or None."""
+    M, K = A.shape
+    N = Bt.shape[0]
+    out = torch.empty(M, N, device=A.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_sgemm_bt(_ptr(A.contiguous()), _ptr(Bt.contiguous()), _ptr(out), M, N, K, _ptr(alpha), _stream()), None,
+               "op_sgemm_bt")
+    return out
+
+
+def op_grad_scale(v: torch.Tensor, target: float) -> torch.Tensor:
+    """scale_dev = {2^k, 2^-k, amax|v|} (3 floats on the device) of the flat fp32 tensor `v`, which is read where it lies: a view that
+    starts 4 bytes into an allocation takes the two-stage path at any length."""
+    if v.dim() != 1 or v.stride(0) != 1 or v.dtype != torch.float32:
+        raise ValueError("op_grad_scale wants a flat fp32 tensor with unit stride")
+    sc = torch.full((3,), float("nan"), device=v.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_grad_scale(_ptr(v), v.numel(), float(target), _ptr(sc), _stream()), None, "op_grad_scale")
+    return sc
+
+
+def op_reduce_prompt_rows(dx32, dx16, row0: int, n: int, scale_dev=None, zero_after=False, split16=0, vmask=None) -> torch.Tensor:
+    """out [n, d] = scale_dev[1] * sum_b dx32[b, row0 + j] (* vmask[b, j]); dx32 [B, L, d] (and its 16-bit copy dx16 [B * L, d or 2d], or
+    None) are cleared IN PLACE at those rows when zero_after."""
+    B, L, d = dx32.shape
+    if not dx32.is_contiguous() or (dx16 is not None and not dx16.is_contiguous()):
+        raise ValueError("op_reduce_prompt_rows works in place: contiguous tensors only")
+    dt = _TORCH2DT[dx16.dtype] if dx16 is not None else DT_F16
+    out = torch.empty(n, d, device=dx32.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_reduce_prompt_rows(dt, _ptr(dx32), _ptr(dx16), B, L, d, row0, n, _ptr(out), _ptr(scale_dev), int(zero_after),
+                                               int(split16), _ptr(vmask), _stream()), None, "op_reduce_prompt_rows")
+    return out
+
+
+def op_gather_ctx_grad(dx, ctx_pos, per_class: bool, scale_dev=None) -> torch.Tensor:
+    """dctx [n, d] (generic: summed over the classes) or [C, n, d] (per class) from dx [C, L, d] at ctx_pos [C, n]."""
+    C_, L, d = dx.shape
+    n = ctx_pos.shape[1]
+    dctx = torch.empty((C_, n, d) if per_class else (n, d), device=dx.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_gather_ctx_grad(_ptr(dx.contiguous()), _ptr(ctx_pos.to(torch.int32).contiguous()), C_, L, d, n, int(per_class),
+                                            _ptr(dctx), _ptr(scale_dev), _stream()), None, "op_gather_ctx_grad")
+    return dctx
+
+
+def op_attention_bwd_cls(qkv, o_cls, do_cls, lse, N, L, H, fill=float("nan")) -> torch.Tensor:
+    """dqkv [N*L, 3*H*64] of the CLS-only attention backward; the output is pre-filled with `fill` (the kernel writes every element)."""
+    dqkv = torch.full_like(qkv, fill)
+    _lib.check(lib.mvlpt_op_attention_bwd_cls(_TORCH2DT[qkv.dtype], _ptr(qkv.contiguous()), _ptr(o_cls.contiguous()),
+                                              _ptr(do_cls.contiguous()), _ptr(lse.contiguous()), _ptr(dqkv), N, L, H, _stream()), None,
+               "op_attention_bwd_cls")
+    return dqkv
+
+
+def op_copy_rows(src, idx, dst=None) -> torch.Tensor:
+    """Gather (dst is None): returns src[idx].  Scatter: dst[idx[r]] = src[r] IN PLACE on the contiguous `dst`, which is returned."""
+    idx = idx.to(torch.int32).contiguous()
+    src = src.contiguous()
+    row_bytes = src[0].numel() * src.element_size()
+    scatter = dst is not None
+    if scatter and not dst.is_contiguous():
+        raise ValueError("op_copy_rows scatters in place: contiguous dst only")
+    if not scatter:
+        dst = torch.empty((idx.numel(),) + tuple(src.shape[1:]), device=src.device, dtype=src.dtype)
+    _lib.check(lib.mvlpt_op_copy_rows(_ptr(src), _ptr(dst), _ptr(idx), idx.numel(), row_bytes, int(scatter), _stream()), None, "op_copy_rows")
+    return dst
+
+
+def op_overwrite_rows(rows, x, vmask=None) -> torch.Tensor:
+    """x[b, 1 + j] = rows[j] (* vmask[b, j]) IN PLACE on the contiguous x [B, L, d], which is returned."""
+    B, L, d = x.shape
+    if not x.is_contiguous():
+        raise ValueError("op_overwrite_rows works in place: contiguous x only")
+    _lib.check(lib.mvlpt_op_overwrite_rows(_ptr(rows.contiguous()), rows.shape[0], _ptr(x), B, L, d, _ptr(vmask), _stream()), None,
+               "op_overwrite_rows")
+    return x
+
+
+def op_assemble_tokens(pe, cls, pos, g, b, batch: int, vpt=None, vmask=None, fill=float("nan")) -> torch.Tensor:
+    """x [batch, 1 + n_vpt + G2, d] of the image tower's entry from pe [batch * G2, d], cls [d], pos [1 + G2, d], ln_pre (g, b),
+    vpt [n_vpt, d] or None and its dropout mask [batch, n_vpt, d] or None; pre-filled with `fill`."""
+    d = pe.shape[1]
+    G2 = pe.shape[0] // batch
+    n_vpt = 0 if vpt is None else vpt.shape[0]
+    x = torch.full((batch, 1 + n_vpt + G2, d), fill, device=pe.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_assemble_tokens(_ptr(pe.contiguous()), _ptr(cls.contiguous()), _ptr(pos.contiguous()), _ptr(g.contiguous()),
+                                            _ptr(b.contiguous()), _ptr(None if vpt is None else vpt.contiguous()), n_vpt,
+                                            _ptr(None if vmask is None else vmask.contiguous()), _ptr(x), batch, G2, d, _stream()),
+               None, "op_assemble_tokens")
+    return x
+
+
+def op_assemble_prompts(prefix, suffix, ctx, layout, pos, eot):
+    """(x [C, L, d], ctx_pos int32 [C, n] or None, eot_rows int32 [C]) of the text tower's entry: ctx [n, d] (generic), [C, n, d] (per
+    class) or None (n = 0)."""
+    C_, L = layout.shape
+    d = prefix.shape[-1]
+    n = 0 if ctx is None else ctx.shape[-2]
+    x = torch.full((C_, L, d), float("nan"), device=prefix.device, dtype=torch.float32)
+    ctx_pos = torch.full((C_, n), -1, device=prefix.device, dtype=torch.int32) if n else None
+    rows = torch.full((C_,), -1, device=prefix.device, dtype=torch.int32)
+    _lib.check(lib.mvlpt_op_assemble_prompts(_ptr(prefix.contiguous()), _ptr(suffix.contiguous()),
+                                             _ptr(None if ctx is None else ctx.contiguous()), int(ctx is not None and ctx.dim() == 3), n,
+                                             _ptr(layout.to(torch.int32).contiguous()), _ptr(pos.contiguous()),
+                                             _ptr(eot.to(torch.int32).contiguous()), _ptr(x), _ptr(ctx_pos), _ptr(rows), C_, L, d,
+                                             _stream()), None, "op_assemble_prompts")
+    return x, ctx_pos, rows
+
+
 def op_cast_mixed(x32: torch.Tensor, dtype) -> torch.Tensor:
     rows, d = x32.shape
     out = torch.zeros(rows, 2 * d, device=x32.device, dtype=dtype)

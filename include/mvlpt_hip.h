@@ -194,6 +194,20 @@ int mvlpt_cross_entropy(void* handle, const float* logits, const void* labels, i
  * 2 fp32 out = acc+bias+resid32, 3 out16 = acc*QuickGELU'(aux16), 4 fp32 store).  K % 64 == 0, N % 128 == 0. */
 int mvlpt_op_gemm(int dtype, int epi, const void* A, const void* Bt, int M, int N, int K, const float* bias, const void* aux,
                   const float* resid, void* out, void* out2, mvlpt_stream_t stream);
+/* The same launch with every GEMM argument the towers set: a_split (0 single, 1 hi|lo pair, 2 mixed pair: A rows as described
+ * below), row pitches in 16-bit elements lda (A; 0 = dense: K, or 2K for a pair), ldo (`out` of the pair-producing epilogues 5 / 6 /
+ * 7; 0 = dense: 2N) and ldb (Bt; 0 = K), w8_exp (mixed pair: exponent of the weight's fp8 plane) and out_lo8 (epilogues 5 / 6: the
+ * output is a mixed pair instead of a hi|lo pair).  Pitches are multiples of 8 elements; an illegal combination returns an error. */
+int mvlpt_op_gemm_ex(int dtype, int epi, const void* A, const void* Bt, int M, int N, int K, const float* bias, const void* aux,
+                     const float* resid, void* out, void* out2, int a_split, int lda, int ldo, int ldb, int w8_exp, int out_lo8,
+                     mvlpt_stream_t stream);
+/* Which kernel a GEMM launch on `stream` would use, without launching (the choice depends on the tile counts against the stream's
+ * compute units; fold_ntp > 0: a folded consumer, mvlpt_op_gemm_folded, with that many slots per row).  Returns the kernel family
+ * (MVLPT_GEMM_*) and its tile / LDS-ring depth through the optional pointers, or a negative error. */
+enum { MVLPT_GEMM_BT_128x128_R2 = 1, MVLPT_GEMM_BT_128x128_R4 = 2, MVLPT_GEMM_BT_256x128_R3 = 3, MVLPT_GEMM_BT_256x256_R2 = 4,
+       MVLPT_GEMM_PHASED = 5, MVLPT_GEMM_PC = 6, MVLPT_GEMM_PCP = 7 };
+int mvlpt_op_gemm_route(int dtype, int epi, int a_split, int M, int N, int K, int fold_ntp, mvlpt_stream_t stream, int* tile_m,
+                        int* tile_n, int* ring);
 /* same with a split-precision A operand: A is [M, 2K] = [A_hi | A_lo] (16-bit pair), C = (A_hi + A_lo) * Bt^T; additional
  * epilogues 5 (out [M,2N] = hi|lo pair of QuickGELU(acc+bias), out2 = pre-activation) and 6 (pair of acc*QuickGELU'(aux)).
  * Note: the saved pre-activation `out2` is ONE 16-bit value per element in every mode (QuickGELU' is evaluated on it in the

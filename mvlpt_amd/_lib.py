@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("MVLPT_HIP_LIB") or os.path.join(_HERE, "libmvlpt_hip.
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 LABEL_INT64, LABEL_PROB_F32 = 0, 1
 EPI_STORE16, EPI_GELU, EPI_RESID32, EPI_GELUBWD, EPI_STORE32, EPI_GELU_SPLIT, EPI_GELUBWD_SPLIT, EPI_STORE_SPLIT = 0, 1, 2, 3, 4, 5, 6, 7
+# kernel families mvlpt_op_gemm_route reports (MVLPT_GEMM_* in the header)
+GEMM_BT_128x128_R2, GEMM_BT_128x128_R4, GEMM_BT_256x128_R3, GEMM_BT_256x256_R2, GEMM_PHASED, GEMM_PC, GEMM_PCP = 1, 2, 3, 4, 5, 6, 7
 PREC_FAST, PREC_SPLIT_GRAD, PREC_SPLIT_ALL = 0, 1, 2
 
 
@@ -73,6 +75,8 @@ SIGNATURES = {
     "mvlpt_logits_ranged_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mvlpt_cross_entropy": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mvlpt_op_gemm": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mvlpt_op_gemm_ex": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_gemm_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "mvlpt_op_gemm_split": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvlpt_op_layernorm_fwd_split": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "mvlpt_op_layernorm_bwd_split": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

@@ -1480,6 +1480,26 @@ int mvlpt_op_gemm(int dtype, int epi, const void* A, const void* Bt, int M, int 
 #endif
   return 0;
 }
+// every GemmArgs field the towers set, straight into launch_gemm (which checks them)
+int mvlpt_op_gemm_ex(int dtype, int epi, const void* A, const void* Bt, int M, int N, int K, const float* bias, const void* aux,
+                     const float* resid, void* out, void* out2, int a_split, int lda, int ldo, int ldb, int w8_exp, int out_lo8,
+                     mvlpt_stream_t stream) {
+  GemmArgs g{A, Bt, M, N, K, bias, aux, resid, out, out2};
+  g.a_split = a_split; g.lda = lda; g.ldo = ldo; g.ldb = ldb; g.w8_exp = w8_exp; g.out_lo8 = out_lo8;
+  OPCHK(launch_gemm(dtype, epi, g, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_gemm_route(int dtype, int epi, int a_split, int M, int N, int K, int fold_ntp, mvlpt_stream_t stream, int* tile_m,
+                        int* tile_n, int* ring) {
+  GemmArgs g{nullptr, nullptr, M, N, K, nullptr, nullptr, nullptr, nullptr, nullptr};
+  g.a_split = a_split; g.fold_ntp = fold_ntp;
+  GemmRoute r;
+  if (gemm_route(dtype, epi, g, fold_ntp > 0, (hipStream_t)stream, &r) != hipSuccess) { g_create_err = "gemm_route: no kernel for this problem"; return MVLPT_ERR_ARG; }
+  if (tile_m) *tile_m = r.tile_m;
+  if (tile_n) *tile_n = r.tile_n;
+  if (ring) *ring = r.ring;
+  return r.family;
+}
 int mvlpt_op_gemm_split(int dtype, int epi, const void* A, const void* Bt, int M, int N, int K, const float* bias, const void* aux,
                         const float* resid, void* out, void* out2, mvlpt_stream_t stream) {
   GemmArgs g{A, Bt, M, N, K, bias, aux, resid, out, out2};

@@ -515,6 +515,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_phased_kernel(GemmArgs g) {
 
 template <typename T, int EPI>
 static hipError_t launch_phased(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
+  if (ea == (hipEvent_t)-1) return hipSuccess;      // dry run (gemm_tile_n, gemm_route): this launcher takes the problem; nothing is launched
   constexpr int LDS = 3 * (256 + 128) * BK * 2;
   static bool attr_set = false;
   if (!attr_set) {
@@ -697,6 +698,7 @@ __global__ __launch_bounds__(512, 1) void gemm_pc_kernel(GemmArgs g) {
 
 template <typename T, int EPI, bool MIXED>
 static hipError_t launch_pc_m(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
+  if (ea == (hipEvent_t)-1) return hipSuccess;      // dry run (gemm_tile_n, gemm_route): this launcher takes the problem; nothing is launched
   constexpr int LDS = 4 * (128 + 128) * BK * 2 + XLDS_BYTES;
   static bool attr_set = false;
   if (!attr_set) {
@@ -951,6 +953,7 @@ __global__ __launch_bounds__(768, 1) void gemm_pcp_kernel(GemmArgs g) {
 
 template <typename T, int EPI, bool MIXED>
 static hipError_t launch_pcp_m(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
+  if (ea == (hipEvent_t)-1) return hipSuccess;      // dry run (gemm_tile_n, gemm_route): this launcher takes the problem; nothing is launched
   constexpr int LDS = 3 * (256 + 128) * BK * 2 + XLDS_BYTES;
   static bool attr_set = false;
   if (!attr_set) {
@@ -974,15 +977,16 @@ static hipError_t launch_pcp(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hi
 template <typename T, int EPI, int BM_, int BN_, int NW, int NS, bool MIXED>
 static hipError_t launch_geo_m(const GemmArgs& g, int wg_per_cu, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
   constexpr int LDS = NS * (BM_ + BN_) * BK * 2;
+  // LayerNorm folding: 16 KiB behind the ring (the consumer's row partials / the producer's per-tile column-block sums)
+  const int lds = LDS + (epi_folds(EPI) ? xlds_bytes(g.fold_ntp) : (epi_ln_producer(EPI) ? XLDS_BYTES : 0));
+  if (lds > 160 * 1024) return hipErrorInvalidValue;      // (launch_one keeps 8-slot consumers off the 3-deep 256x128 ring)
+  if (ea == (hipEvent_t)-1) return hipSuccess;      // dry run (gemm_tile_n, gemm_route): this launcher takes the problem; nothing is launched
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)gemm_bt_kernel<T, EPI, BM_, BN_, NW, NS, MIXED>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               LDS + (LDS + XLDS_BYTES_WIDE <= 160 * 1024 ? XLDS_BYTES_WIDE : XLDS_BYTES));
     attr_set = true;
   }
-  // LayerNorm folding: 16 KiB behind the ring (the consumer's row partials / the producer's per-tile column-block sums)
-  const int lds = LDS + (epi_folds(EPI) ? xlds_bytes(g.fold_ntp) : (epi_ln_producer(EPI) ? XLDS_BYTES : 0));
-  if (lds > 160 * 1024) return hipErrorInvalidValue;      // (launch_one keeps 8-slot consumers off the 3-deep 256x128 ring)
 
   int cus = stream_cus(s);
 #ifdef MVLPT_DEBUG_CUS
@@ -1005,7 +1009,7 @@ static hipError_t launch_geo(const GemmArgs& g, int wg_per_cu, hipStream_t s, hi
 }
 
 template <typename T, int EPI>
-static hipError_t launch_one(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb, int* tile_m, int* tile_n) {
+static hipError_t launch_one(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb, int* tile_m, int* tile_n, int* family) {
   // (256x256 with FOUR waves of 256x64 — 17 % less LDS-read traffic per FLOP, one wave per SIMD — was measured 17-36 % slower
   // than the eight-wave kernel: 8192^3 1.09 vs 1.31 PF; nothing hides a wave's own LDS-DMA issue and ds_read latency.)
   // geometry by tile count: 256x256 (128x64 wave tiles, least LDS-DMA / LDS-read traffic per FLOP) needs >= 4 full
@@ -1028,30 +1032,34 @@ static hipError_t launch_one(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hi
   // (nor the LayerNorm-folding fields: folded GEMMs take the plain geometries)
   constexpr bool folded = epi_folds(EPI) || epi_ln_producer(EPI);
   if (g.a_split != 2 && !folded && r15 && Keff >= 2048 && !big) {
-    *tile_m = 256; *tile_n = 128;
-    if constexpr (!folded) return ea == (hipEvent_t)-1 ? hipSuccess : launch_phased<T, EPI>(g, s, ea, eb);
+    *tile_m = 256; *tile_n = 128; *family = GEMM_FAM_PHASED;
+    if constexpr (!folded) return launch_phased<T, EPI>(g, s, ea, eb);
   }
   if (big) {
-    *tile_m = 256; *tile_n = 256;
-    return ea == (hipEvent_t)-1 ? hipSuccess : launch_geo<T, EPI, 256, 256, 8, 2>(g, 1, s, ea, eb);
+    *tile_m = 256; *tile_n = 256; *family = GEMM_FAM_BT_256x256_R2;
+    return launch_geo<T, EPI, 256, 256, 8, 2>(g, 1, s, ea, eb);
   }
   // (a folded consumer with 8-slot rows needs 20 KiB behind its ring: the 3-deep 256x128 ring has 16 left -> 256x256 or 128x128)
   const bool wide_fold = epi_folds(EPI) && g.fold_ntp > 6;
   if (wide_fold && r15 && g.N % 256 == 0) {
-    *tile_m = 256; *tile_n = 256;
-    return ea == (hipEvent_t)-1 ? hipSuccess : launch_geo<T, EPI, 256, 256, 8, 2>(g, 1, s, ea, eb);
+    *tile_m = 256; *tile_n = 256; *family = GEMM_FAM_BT_256x256_R2;
+    return launch_geo<T, EPI, 256, 256, 8, 2>(g, 1, s, ea, eb);
   }
   if (r15 && !wide_fold) {
     *tile_m = 256; *tile_n = 128;
     // 256x128 with data-movement waves (gemm_pcp_kernel); its movers carry the row partials of 4- and 6-slot rows only, so a
     // folded consumer with 2-slot rows (d <= 256) takes the self-serving 8-wave kernel
-    if (!epi_folds(EPI) || g.fold_ntp == 4 || g.fold_ntp == 6) return ea == (hipEvent_t)-1 ? hipSuccess : launch_pcp<T, EPI>(g, s, ea, eb);
-    return ea == (hipEvent_t)-1 ? hipSuccess : launch_geo<T, EPI, 256, 128, 8, 3>(g, 1, s, ea, eb);
+    if (!epi_folds(EPI) || g.fold_ntp == 4 || g.fold_ntp == 6) {
+      *family = GEMM_FAM_PCP;
+      return launch_pcp<T, EPI>(g, s, ea, eb);
+    }
+    *family = GEMM_FAM_BT_256x128_R3;
+    return launch_geo<T, EPI, 256, 128, 8, 3>(g, 1, s, ea, eb);
   }
   // split operands on problems with no more 128x128 tiles than compute units: dedicated data-movement waves (gemm_pc_kernel above)
   if (g.a_split && pc_takes<EPI>(g, cus)) {
-    *tile_m = 128; *tile_n = 128;
-    return ea == (hipEvent_t)-1 ? hipSuccess : launch_pc<T, EPI>(g, s, ea, eb);
+    *tile_m = 128; *tile_n = 128; *family = GEMM_FAM_PC;
+    return launch_pc<T, EPI>(g, s, ea, eb);
   }
   // small problems (text tower: M = C*L ~ 7.7k rows) put at most one workgroup on a CU, so nothing hides the
   // LDS-DMA latency of a 2-deep ring: split operands use a 4-deep ring (128 KiB, three K-stages in flight) instead.
@@ -1060,42 +1068,43 @@ static hipError_t launch_one(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hi
   // 5.57 -> 5.10 ms, overlapped step 15.22 -> 15.00 ms.
   const long t_small = (long)((g.M + 127) / 128) * (g.N / 128);
   if (g.a_split && t_small <= cus) {
-    *tile_m = 128; *tile_n = 128;
-    return ea == (hipEvent_t)-1 ? hipSuccess : launch_geo<T, EPI, 128, 128, 4, 4>(g, 1, s, ea, eb);
+    *tile_m = 128; *tile_n = 128; *family = GEMM_FAM_BT_128x128_R4;
+    return launch_geo<T, EPI, 128, 128, 4, 4>(g, 1, s, ea, eb);
   }
-  *tile_m = 128; *tile_n = 128;
-  return ea == (hipEvent_t)-1 ? hipSuccess : launch_geo<T, EPI, 128, 128, 4, 2>(g, 2, s, ea, eb);
+  *tile_m = 128; *tile_n = 128; *family = GEMM_FAM_BT_128x128_R2;
+  return launch_geo<T, EPI, 128, 128, 4, 2>(g, 2, s, ea, eb);
 }
 
 template <typename T, int EPI>
-static hipError_t launch_t(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
-  int bm, bn;
-  return launch_one<T, EPI>(g, s, ea, eb, &bm, &bn);
+static hipError_t launch_t(const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb, GemmRoute* r) {
+  GemmRoute q;
+  if (!r) r = &q;
+  return launch_one<T, EPI>(g, s, ea, eb, &r->tile_m, &r->tile_n, &r->family);
 }
 
 template <typename T>
-static hipError_t launch_epi(const GemmArgs& g, int epi, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
-  if (g.fold_part) {
+static hipError_t launch_epi(const GemmArgs& g, int epi, bool folded, hipStream_t s, hipEvent_t ea, hipEvent_t eb, GemmRoute* r = nullptr) {
+  if (folded) {
     switch (epi) {
-      case EPI_STORE16: return launch_t<T, EPI_STORE16_FOLD>(g, s, ea, eb);
-      case EPI_GELU: return launch_t<T, EPI_GELU_FOLD>(g, s, ea, eb);
-      case EPI_STORE_SPLIT: return launch_t<T, EPI_STORE_SPLIT_FOLD>(g, s, ea, eb);
-      case EPI_GELU_SPLIT: return launch_t<T, EPI_GELU_SPLIT_FOLD>(g, s, ea, eb);
+      case EPI_STORE16: return launch_t<T, EPI_STORE16_FOLD>(g, s, ea, eb, r);
+      case EPI_GELU: return launch_t<T, EPI_GELU_FOLD>(g, s, ea, eb, r);
+      case EPI_STORE_SPLIT: return launch_t<T, EPI_STORE_SPLIT_FOLD>(g, s, ea, eb, r);
+      case EPI_GELU_SPLIT: return launch_t<T, EPI_GELU_SPLIT_FOLD>(g, s, ea, eb, r);
     }
     return hipErrorInvalidValue;
   }
   switch (epi) {
-    case EPI_STORE16: return launch_t<T, EPI_STORE16>(g, s, ea, eb);
-    case EPI_GELU: return launch_t<T, EPI_GELU>(g, s, ea, eb);
-    case EPI_RESID32: return launch_t<T, EPI_RESID32>(g, s, ea, eb);
-    case EPI_GELUBWD: return launch_t<T, EPI_GELUBWD>(g, s, ea, eb);
-    case EPI_STORE32: return launch_t<T, EPI_STORE32>(g, s, ea, eb);
-    case EPI_GELU_SPLIT: return launch_t<T, EPI_GELU_SPLIT>(g, s, ea, eb);
-    case EPI_GELUBWD_SPLIT: return launch_t<T, EPI_GELUBWD_SPLIT>(g, s, ea, eb);
-    case EPI_STORE_SPLIT: return launch_t<T, EPI_STORE_SPLIT>(g, s, ea, eb);
-    case EPI_RESID32_LN: return launch_t<T, EPI_RESID32_LN>(g, s, ea, eb);
+    case EPI_STORE16: return launch_t<T, EPI_STORE16>(g, s, ea, eb, r);
+    case EPI_GELU: return launch_t<T, EPI_GELU>(g, s, ea, eb, r);
+    case EPI_RESID32: return launch_t<T, EPI_RESID32>(g, s, ea, eb, r);
+    case EPI_GELUBWD: return launch_t<T, EPI_GELUBWD>(g, s, ea, eb, r);
+    case EPI_STORE32: return launch_t<T, EPI_STORE32>(g, s, ea, eb, r);
+    case EPI_GELU_SPLIT: return launch_t<T, EPI_GELU_SPLIT>(g, s, ea, eb, r);
+    case EPI_GELUBWD_SPLIT: return launch_t<T, EPI_GELUBWD_SPLIT>(g, s, ea, eb, r);
+    case EPI_STORE_SPLIT: return launch_t<T, EPI_STORE_SPLIT>(g, s, ea, eb, r);
+    case EPI_RESID32_LN: return launch_t<T, EPI_RESID32_LN>(g, s, ea, eb, r);
     case EPI_RESIDP_LN:      // the packed stream is an fp16 format
-      if constexpr (__is_same(T, f16)) return launch_t<T, EPI_RESIDP_LN>(g, s, ea, eb);
+      if constexpr (__is_same(T, f16)) return launch_t<T, EPI_RESIDP_LN>(g, s, ea, eb, r);
       else return hipErrorInvalidValue;
   }
   return hipErrorInvalidValue;
@@ -1103,10 +1112,12 @@ static hipError_t launch_epi(const GemmArgs& g, int epi, hipStream_t s, hipEvent
 
 template <typename T>
 static int tile_n_epi(const GemmArgs& g, int epi, hipStream_t s) {
-  int bm = 0, bn = 0;
+  int bm = 0, bn = 0, fam = 0;
+  // dry run: launch_one writes the tile in front of the launcher it picks, and the launcher returns in front of its launch.  The
+  // launcher's verdict is dropped on purpose: the callers ask for the geometry of problems launch_gemm has yet to check
   switch (epi) {      // (the geometry does not depend on the epilogue except for the phased routing, which folded GEMMs skip)
-    case EPI_RESID32_LN: case EPI_RESIDP_LN: (void)launch_one<T, EPI_RESID32_LN>(g, s, (hipEvent_t)-1, nullptr, &bm, &bn); break;
-    default: (void)launch_one<T, EPI_RESID32>(g, s, (hipEvent_t)-1, nullptr, &bm, &bn); break;
+    case EPI_RESID32_LN: case EPI_RESIDP_LN: (void)launch_one<T, EPI_RESID32_LN>(g, s, (hipEvent_t)-1, nullptr, &bm, &bn, &fam); break;
+    default: (void)launch_one<T, EPI_RESID32>(g, s, (hipEvent_t)-1, nullptr, &bm, &bn, &fam); break;
   }
   return bn;
 }
@@ -1114,28 +1125,55 @@ int gemm_tile_n(int dtype, int epi, const GemmArgs& g, hipStream_t s) {
   return dtype == DT_BF16 ? tile_n_epi<bf16>(g, epi, s) : tile_n_epi<f16>(g, epi, s);
 }
 
+// What launch_gemm requires of a problem.  `dry`: the dry run of gemm_route, which knows the shape, the operand format and whether the
+// GEMM is a folded consumer, but has no operands: the checks of pointers, pitches and fold_nt are skipped.
 // K must be a multiple of 64 and N of 128 (every CLIP width is; conv K is zero-padded); M is arbitrary.
-hipError_t launch_gemm(int dtype, int epi, const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
-  if (g.M <= 0 || g.N <= 0 || g.K <= 0 || (g.K % BK) != 0 || (g.N % 128) != 0) return hipErrorInvalidValue;
-  if (g.a_split == 2 && ((g.K % 128) != 0 || g.ldb < g.K + g.K / 2)) return hipErrorInvalidValue;
-  if (g.ldb && (g.ldb < g.K || (g.ldb % 8) != 0)) return hipErrorInvalidValue;
-  if (g.lda && (g.lda < (g.a_split ? 2 : 1) * g.K || (g.lda % 8) != 0)) return hipErrorInvalidValue;
-  if (g.ldo && (g.ldo < 2 * g.N || (g.ldo % 8) != 0 || !(epi == EPI_GELU_SPLIT || epi == EPI_GELUBWD_SPLIT || epi == EPI_STORE_SPLIT))) return hipErrorInvalidValue;
-  if ((epi == EPI_RESID32 || epi == EPI_RESID32_LN) && !g.resid) return hipErrorInvalidValue;
-  if (epi == EPI_RESID32_LN && (!g.ln_gamma || !g.ln_x16 || !g.ln_part || g.ln_ntp <= 0 || (g.ln_ntp & 1))) return hipErrorInvalidValue;
-  if (epi == EPI_RESIDP_LN && (dtype != DT_F16 || g.a_split || !g.rp_hi_in || !g.rp_lo_in || !g.rp_lo_out || !g.ln_part || g.ln_ntp <= 0 || (g.ln_ntp & 1)))
-    return hipErrorInvalidValue;
-  if (g.fold_part) {
+static bool gemm_args_ok(int dtype, int epi, const GemmArgs& g, bool folded, bool dry) {
+  if (dtype != DT_F16 && dtype != DT_BF16) return false;
+  if (g.M <= 0 || g.N <= 0 || g.K <= 0 || (g.K % BK) != 0 || (g.N % 128) != 0 || g.a_split < 0 || g.a_split > 2) return false;
+  if (g.a_split == 2 && (g.K % 128) != 0) return false;
+  if (epi == EPI_RESIDP_LN && (dtype != DT_F16 || g.a_split)) return false;
+  if (folded) {
     const bool can = epi == EPI_STORE16 || epi == EPI_GELU || epi == EPI_STORE_SPLIT || epi == EPI_GELU_SPLIT;
     const int nk = g.a_split == 2 ? g.K / BK + g.K / 128 : (g.a_split ? 2 : 1) * (g.K / BK);
     // the row partials ride with the LAST K-stage of a tile: it must be issued inside the tile's own K loop (ring depth <= 4)
-    if (!can || !g.fold_colsum || !g.bias || g.fold_nt <= 0 || g.fold_nt > g.fold_ntp || g.fold_ntp > FOLD_MAX_NTP || (g.fold_ntp & 1) || nk < 4)
-      return hipErrorInvalidValue;
+    if (!can || g.fold_ntp <= 0 || g.fold_ntp > FOLD_MAX_NTP || (g.fold_ntp & 1) || nk < 4) return false;
   }
-  if ((epi == EPI_GELUBWD || epi == EPI_GELUBWD_SPLIT) && !g.aux) return hipErrorInvalidValue;
-  if (dtype == DT_F16) return launch_epi<f16>(g, epi, s, ea, eb);
-  if (dtype == DT_BF16) return launch_epi<bf16>(g, epi, s, ea, eb);
-  return hipErrorInvalidValue;
+  if (dry) return true;
+  if (g.a_split == 2 && g.ldb < g.K + g.K / 2) return false;
+  if (g.ldb && (g.ldb < g.K || (g.ldb % 8) != 0)) return false;
+  if (g.lda && (g.lda < (g.a_split ? 2 : 1) * g.K || (g.lda % 8) != 0)) return false;
+  if (g.ldo && (g.ldo < 2 * g.N || (g.ldo % 8) != 0 || !(epi == EPI_GELU_SPLIT || epi == EPI_GELUBWD_SPLIT || epi == EPI_STORE_SPLIT))) return false;
+  if ((epi == EPI_RESID32 || epi == EPI_RESID32_LN) && !g.resid) return false;
+  if (epi == EPI_RESID32_LN && (!g.ln_gamma || !g.ln_x16 || !g.ln_part || g.ln_ntp <= 0 || (g.ln_ntp & 1))) return false;
+  if (epi == EPI_RESIDP_LN && (!g.rp_hi_in || !g.rp_lo_in || !g.rp_lo_out || !g.ln_part || g.ln_ntp <= 0 || (g.ln_ntp & 1))) return false;
+  if (folded && (!g.fold_colsum || !g.bias || g.fold_nt <= 0 || g.fold_nt > g.fold_ntp)) return false;
+  if ((epi == EPI_GELUBWD || epi == EPI_GELUBWD_SPLIT) && !g.aux) return false;
+  return true;
+}
+
+// The kernel launch_gemm would pick: the same checks and the same walk through launch_one and the launchers behind it, which return in
+// front of the launch itself when the start event is (hipEvent_t)-1.  Reads M, N, K, a_split and fold_ntp of `g` only.
+hipError_t gemm_route(int dtype, int epi, const GemmArgs& g, bool folded, hipStream_t s, GemmRoute* r) {
+  if (!r || !gemm_args_ok(dtype, epi, g, folded, true)) return hipErrorInvalidValue;
+  *r = GemmRoute{};
+  const hipError_t e = dtype == DT_F16 ? launch_epi<f16>(g, epi, folded, s, (hipEvent_t)-1, nullptr, r)
+                                       : launch_epi<bf16>(g, epi, folded, s, (hipEvent_t)-1, nullptr, r);
+  if (e != hipSuccess) return e;
+  switch (r->family) {
+    case GEMM_FAM_BT_128x128_R2: case GEMM_FAM_BT_256x256_R2: r->ring = 2; break;
+    case GEMM_FAM_BT_256x128_R3: case GEMM_FAM_PHASED: case GEMM_FAM_PCP: r->ring = 3; break;
+    case GEMM_FAM_BT_128x128_R4: case GEMM_FAM_PC: r->ring = 4; break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipSuccess;
+}
+
+hipError_t launch_gemm(int dtype, int epi, const GemmArgs& g, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
+  const bool folded = g.fold_part != nullptr;
+  if (!gemm_args_ok(dtype, epi, g, folded, false)) return hipErrorInvalidValue;
+  if (dtype == DT_F16) return launch_epi<f16>(g, epi, folded, s, ea, eb);
+  return launch_epi<bf16>(g, epi, folded, s, ea, eb);
 }
 
 // ---------------------------------------------------------------------------------------------- fp32 GEMM

@@ -99,6 +99,20 @@ struct GemmArgs {
 };
 // N-tile width the launcher picks for this problem on this stream
 int gemm_tile_n(int dtype, int epi, const GemmArgs& g, hipStream_t s);
+// Which of the seven GEMM kernels the launcher picks for a problem on a stream (gemm.hip launch_one; kernel-level tests assert it,
+// so that a moved routing threshold cannot silently move their coverage).  Values are part of the C ABI (mvlpt_op_gemm_route).
+enum GemmFamily {
+  GEMM_FAM_BT_128x128_R2 = 1,  // gemm_bt_kernel 128x128, 2-deep ring, two workgroups per compute unit
+  GEMM_FAM_BT_128x128_R4 = 2,  // gemm_bt_kernel 128x128, 4-deep ring
+  GEMM_FAM_BT_256x128_R3 = 3,  // gemm_bt_kernel 256x128, 3-deep ring
+  GEMM_FAM_BT_256x256_R2 = 4,  // gemm_bt_kernel 256x256, 2-deep ring
+  GEMM_FAM_PHASED = 5,         // gemm_bt_phased_kernel (256x128, 3-deep ring)
+  GEMM_FAM_PC = 6,             // gemm_pc_kernel (128x128, 4-deep ring, one tile per workgroup)
+  GEMM_FAM_PCP = 7,            // gemm_pcp_kernel (256x128, 3-deep ring, persistent with movers)
+};
+struct GemmRoute { int family = 0, tile_m = 0, tile_n = 0, ring = 0; };
+// (reads M, N, K, a_split and fold_ntp of `g`; `folded`: a folded consumer, i.e. a launch with fold_part set)
+hipError_t gemm_route(int dtype, int epi, const GemmArgs& g, bool folded, hipStream_t s, GemmRoute* r);
 // ev_start/ev_stop (optional): recorded by the dispatch itself (hipExtLaunchKernelGGL): kernel-exact timing with no
 // extra marker packets on the stream.
 hipError_t launch_gemm(int dtype, int epi, const GemmArgs& g, hipStream_t s, hipEvent_t ev_start = nullptr,

@@ -454,6 +454,22 @@ def op_gemm(A, Bt, epi=_lib.EPI_STORE16, bias=None, aux=None, resid=None, out2=F
     return (out, o2) if out2 else out
 
 
+def op_gemm_ex(A, Bt, epi, M, N, K, out, bias=None, aux=None, resid=None, out2=None, a_split=0, lda=0, ldo=0, ldb=0, w8_exp=0, out_lo8=0):
+    """mvlpt_op_gemm_ex on caller-owned tensors (nothing is copied or made contiguous: pitches and aliasing are the caller's)."""
+    _lib.check(lib.mvlpt_op_gemm_ex(_TORCH2DT[A.dtype], epi, _ptr(A), _ptr(Bt), M, N, K, _ptr(bias), _ptr(aux), _ptr(resid), _ptr(out),
+                                    _ptr(out2), a_split, lda, ldo, ldb, w8_exp, out_lo8, _stream()), None, "op_gemm_ex")
+    return out
+
+
+def op_gemm_route(dtype, epi, a_split, M, N, K, fold_ntp=0):
+    """(family, tile_m, tile_n, ring depth) of the kernel a GEMM on the current stream would use (_lib.GEMM_*)."""
+    tm, tn, ring = C.c_int(0), C.c_int(0), C.c_int(0)
+    fam = lib.mvlpt_op_gemm_route(_TORCH2DT[dtype], epi, a_split, M, N, K, fold_ntp, _stream(), C.byref(tm), C.byref(tn), C.byref(ring))
+    if fam <= 0:
+        raise RuntimeError(f"libmvlpt_hip op_gemm_route failed (code {fam}): {_lib.last_error(None)}")
+    return fam, tm.value, tn.value, ring.value
+
+
 def split_pair(x: torch.Tensor, dtype) -> torch.Tensor:
     """fp32 [M,K] -> 16-bit hi|lo pair [M,2K] (the layout of GemmArgs::a_split; host-side helper for tests)."""
     hi = x.to(dtype)

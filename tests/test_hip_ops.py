@@ -56,7 +56,7 @@ def test_gemm_epilogues(dtype):
     resid = torch.randn(M, N, generator=g)
     outr = E.op_gemm(A.cuda(), Bt.cuda(), E._lib.EPI_RESID32, bias=bias.cuda(), resid=resid.cuda())
     assert relerr(outr, acc + bias + resid) < 2e-5
-    # in-place residual (out aliases resid) is what the towers use
+    # in-place residual (out aliases resid) is what the towers use: tests/test_hip_gemm_matrix.py runs it on every route (_run_case)
     # QuickGELU + saved pre-activation
     a16, u16 = E.op_gemm(A.cuda(), Bt.cuda(), E._lib.EPI_GELU, bias=bias.cuda(), out2=True)
     assert relerr(u16, acc + bias) < TOL[dtype]
@@ -141,7 +141,8 @@ def test_attention_is_not_transposed():
     assert relerr(out, o.reshape(L, 64)) < 3e-3
 
 
-@pytest.mark.parametrize("M,N,K,epi", [(16640, 768, 3072, 2),     # phased 256x128 kernel (two wave groups one phase apart)
+@pytest.mark.parametrize("M,N,K,epi", [(16640, 768, 3072, 2),     # chosen for the phased 256x128 kernel; 195 tiles of 256x256 now fill one round, so it runs there
+                                       #   (tests/test_hip_gemm_matrix.py asserts its routes and covers the phased kernel)
                                        (30000, 2304, 768, 0),     # 256x256 geometry, ragged last M tile
                                        (25600, 768, 768, 2),      # 256x128 3-stage ring
                                        (7700, 512, 2048, 2)])     # 128x128, ragged M

@@ -113,7 +113,9 @@ int mvlpt_stream_cus(mvlpt_stream_t stream);
  * `dev_ptr` is a contiguous device tensor of `dtype` (fp32/fp16/bf16).  Unknown names return MVLPT_ERR_ARG. */
 int mvlpt_load_frozen(void* handle, const char* name, const void* dev_ptr, int dtype, const int64_t* shape, int ndim,
                       mvlpt_stream_t stream);
-/* 0 when every tensor the towers need has been loaded; otherwise <0 and last_error names the first missing. */
+/* "token_embedding.weight" [vocab, text_width] is optional: when passed, an fp32 copy is kept for mvlpt_text_encode_tokens (vocab *
+ * text_width * 4 bytes: 101 MB for ViT-B/16); callers that feed prefix / suffix embeddings skip the key and pay nothing.
+ * 0 when every tensor the towers need has been loaded; otherwise <0 and last_error names the first missing. */
 int mvlpt_frozen_ready(void* handle);
 
 /* ImageEncoder.forward (trainers/mvlpt.py:52-93).  image [B,3,R,R] of `image_dtype`; vpt [n_vpt,dv] fp32 or
@@ -158,6 +160,30 @@ int mvlpt_text_bwd(void* handle, const float* dfeat, float* dctx, mvlpt_stream_t
  * ctx-position table counted for the largest n_ctx, L - 2; a ranged tower adds its range tables and a per-class position table, a few
  * bytes per class and sequence); the workspace only grows, so a caller that chunks G keeps its peak under a budget. */
 int mvlpt_text_workspace_bytes(void* handle, int C_total, int L, int save_for_bwd, int64_t* out);
+
+/* CLIP.encode_text (clip/model.py:343-356: token_embedding(text) + positional_embedding -> transformer -> ln_final ->
+ * x[arange, text.argmax(-1)] @ text_projection) for S sequences of token ids: what the zero-shot trainers feed (trainers/zsclip.py:45-49,
+ * 91-92).  Needs "token_embedding.weight" [vocab, text_width], which mvlpt_load_frozen keeps as an fp32 copy when (and only when) the
+ * caller passes it; mvlpt_frozen_ready does not ask for it.
+ * ids is a HOST int32 [S, ld] array, ld >= L; the device reads columns 0 .. L-1 only (the tower is causal: positions behind the EOT
+ * token cannot reach the EOT row, so trimming a sequence to L > eot is exact, not an approximation).  The table is checked on the host
+ * and uploaded with the call, which stays enqueue-only; nothing is launched when the check fails:
+ *   - any id in columns 0 .. L-1 outside [0, vocab): MVLPT_ERR_ARG (it would be an out-of-bounds read of the table);
+ *   - a row whose EOT position — first occurrence of the maximum of the WHOLE row of ld ids, as text.argmax(dim=-1) — is >= L;
+ *   - L > context_length, or L < MVLPT_TEXT_MIN_L: the attention and GEMM launchers take any L >= 1 (any M >= 1), the tower needs
+ *     L >= n_ctx + 2 = 2, and mvlpt_text_workspace_bytes, which sizes it, refuses L <= 2 — so 3 is the smallest L every entry accepts;
+ *   - S > 65535 (the attention launches put the sequence index on grid.y; callers chunk, as they do for the workspace);
+ *   - no token embedding loaded: MVLPT_ERR_STATE.
+ * feat_out [S, embed] fp32, un-normalised.  Workspace: mvlpt_text_workspace_bytes(S, L, 0) plus the id table,
+ * ((S * L + S) * 4 rounded up to 256) bytes (the trimmed ids and one EOT row index per sequence).  Everything behind the assembly is
+ * the tower of mvlpt_text_fwd with n_ctx = 0, save_for_bwd = 0: the same bits for the same embeddings.  No gradient on this route. */
+enum { MVLPT_TEXT_MIN_L = 3 };
+int mvlpt_text_encode_tokens(void* handle, const int32_t* ids, int ld, int S, int L, float* feat_out, mvlpt_stream_t stream);
+/* Prompt ensembling (trainers/zsclip.py:88-96) as one kernel: feats fp32 [T, C, e], template-major as the reference loops;
+ * out[c] = normalize((1/T) * sum_t feats[t,c] / |feats[t,c]|), fp32, summed over t in the fixed order 0 .. T-1 (reruns are
+ * bit-identical).  T = 1 gives x / |x| with the bits of the head's row normalisation (the mean of one unit vector is that vector; the
+ * second normalisation is skipped).  e <= 1024.  Handle-free: errors go to mvlpt_last_error(NULL). */
+int mvlpt_text_ensemble(const float* feats, int T, int C, int e, float* out, mvlpt_stream_t stream);
 
 /* Cosine logits (trainers/mvlpt.py:550-554) with the multiplicative per-task mask (:573-581):
  * logits[b,c] = exp(logit_scale) * <img_b/|img_b|, txt_c/|txt_c|> * [task_lo[b] <= c < task_hi[b]].
@@ -320,6 +346,14 @@ int mvlpt_op_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos, con
  *   the rest LN(patch_emb[b, i] + pos[1 + i]); pos [1 + G2, d].
  * assemble_prompts: the text tower's entry (arguments of mvlpt_text_fwd): x [C,L,d] = prompts + pos, eot_rows int32 [C] = c * L + eot[c],
  *   and, when n_ctx > 0, ctx_pos int32 [C,n_ctx] = position of context row j in class c's sequence. */
+/* ---- the zero-shot glue at kernel level (tests/test_hip_zsclip_ops.py) ----
+ * embed_tokens: x [S, L, d] = emb[ids[s, t]] + pos[t] with ids a DEVICE int32 [S, ld] table, ld >= L, columns 0 .. L-1 read; the caller
+ *   guarantees those ids are rows of emb.  d % 4 == 0.
+ * ensemble_features: the kernel of mvlpt_text_ensemble.  normalize_rows: xn = x / |x|, norm = |x| per row (the head's normalisation). */
+int mvlpt_op_embed_tokens(const float* emb, const float* pos, const int32_t* ids, int ld, float* x, int S, int L, int d,
+                          mvlpt_stream_t stream);
+int mvlpt_op_ensemble_features(const float* feats, float* out, int T, int C, int e, mvlpt_stream_t stream);
+int mvlpt_op_normalize_rows(const float* x, float* xn, float* norm, int rows, int d, mvlpt_stream_t stream);
 int mvlpt_op_sgemm_bt(const float* A, const float* Bt, float* C, int M, int N, int K, const float* alpha_dev, mvlpt_stream_t stream);
 int mvlpt_op_grad_scale(const float* v, int64_t n, float target, float* scale_dev, mvlpt_stream_t stream);
 int mvlpt_op_reduce_prompt_rows(int dtype, float* dx32, void* dx16, int B, int L, int d, int row0, int n, float* out,

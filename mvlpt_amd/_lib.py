@@ -22,6 +22,7 @@ EPI_STORE16, EPI_GELU, EPI_RESID32, EPI_GELUBWD, EPI_STORE32, EPI_GELU_SPLIT, EP
 # kernel families mvlpt_op_gemm_route reports (MVLPT_GEMM_* in the header)
 GEMM_BT_128x128_R2, GEMM_BT_128x128_R4, GEMM_BT_256x128_R3, GEMM_BT_256x256_R2, GEMM_PHASED, GEMM_PC, GEMM_PCP = 1, 2, 3, 4, 5, 6, 7
 PREC_FAST, PREC_SPLIT_GRAD, PREC_SPLIT_ALL = 0, 1, 2
+TEXT_MIN_L = 3      # MVLPT_TEXT_MIN_L: the smallest sequence length mvlpt_text_encode_tokens accepts
 
 
 class MvlptArch(C.Structure):
@@ -67,6 +68,8 @@ SIGNATURES = {
     "mvlpt_text_fwd_grouped": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_fwd_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_workspace_bytes": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int64)]),
+    "mvlpt_text_encode_tokens": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "mvlpt_text_ensemble": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mvlpt_logits_fwd": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp]),
     "mvlpt_logits_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mvlpt_logits_grouped_fwd": (_i, [_vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
@@ -106,6 +109,9 @@ SIGNATURES = {
     "mvlpt_op_gather_ctx_grad_grouped": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mvlpt_op_assemble_prompts_ranged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_gather_ctx_grad_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "mvlpt_op_embed_tokens": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "mvlpt_op_ensemble_features": (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    "mvlpt_op_normalize_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "mvlpt_op_sgemm_bt": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "mvlpt_op_grad_scale": (_i, [_vp, C.c_int64, _f, _vp, _vp]),
     "mvlpt_op_reduce_prompt_rows": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),

@@ -34,6 +34,9 @@ class CfgNode(dict):
             if isinstance(val, str) and not isinstance(old, str):
                 if isinstance(old, bool):
                     val = val.lower() in ("1", "true", "yes")
+                elif isinstance(old, list) and old and isinstance(old[0], str):
+                    import json
+                    val = [str(x) for x in json.loads(val)]      # a list of strings (TRAINER.ZSCLIP.TEMPLATES) comes as JSON
                 elif isinstance(old, (list, tuple)):
                     val = type(old)(int(x) for x in val.strip("()[]").split(","))
                 else:
@@ -72,6 +75,9 @@ def get_cfg_default() -> CfgNode:
     )
     # trainers/cocoop.py's own keys (train.py:125-128), read by mvlpt_amd.cocoop (--trainer CoCoOp)
     cfg.TRAINER.COCOOP = CN(N_CTX=16, CTX_INIT="", PREC="fp16")
+    # mvlpt_amd.zsclip (--trainer ZeroshotCLIP / ZeroshotCLIP2).  Not a reference key: the reference picks its templates from tables in
+    # its own source by DATASET.NAME; here they are configuration.  ZeroshotCLIP takes exactly one, ZeroshotCLIP2 any number >= 1.
+    cfg.TRAINER.ZSCLIP = CN(TEMPLATES=["a photo of a {}."])
     cfg.DATASET = CN(NAME="synthetic", COOP=True, MULTITASK=False, MULTITASK_LABEL_PERTASK=False,
                      MULTITASK_EVALKEY="average", NUM_SHOTS=16)
     return cfg

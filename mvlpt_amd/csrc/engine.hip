@@ -171,6 +171,8 @@ struct Engine {
   float *vproj = nullptr, *vproj_t = nullptr;  // [dv,e] and [e,dv] fp32 (the projections next to the logits stay fp32)
   // text extras
   float* tpos = nullptr; LNp ln_final; float *tproj = nullptr, *tproj_t = nullptr;
+  // token embedding [vocab, text_width] fp32: kept only when the caller loads it (mvlpt_text_encode_tokens reads it)
+  float* tok_emb = nullptr; int vocab = 0;
   std::vector<void*> owned;               // every weight allocation (freed in destroy)
   DevBuf vis_ws, txt_ws, head_ws, ce_ws, tmp, pp_ws;
   TowerState vs, ts;
@@ -186,6 +188,7 @@ struct Engine {
   // ranged forward (mvlpt_text_fwd_ranged): t_groups groups over t_gC classes, tC = sum of the range widths; device tables in txt_ws
   bool t_ranged = false; const int32_t *t_rlo = nullptr, *t_rstart = nullptr;
   std::vector<int32_t> t_range_host, h_range_host;   // host images of the range tables (source of the asynchronous upload)
+  std::vector<int32_t> t_ids_host;   // mvlpt_text_encode_tokens: [ids (S * L, trimmed rows) | eot rows (S)], checked on the host
   // EOT-only last text block (compact [C,·] rows; the text-side twin of the CLS-only last image block)
   bool t_eot_last = false; float *txc32 = nullptr, *txm32 = nullptr, *txo32 = nullptr, *tdxc32 = nullptr, *tdhc32 = nullptr;
   void *tac16 = nullptr, *thc16 = nullptr, *tgc16 = nullptr, *tuc16 = nullptr, *tduc16 = nullptr, *tdxc16 = nullptr, *tdOc16 = nullptr;
@@ -807,8 +810,9 @@ int mvlpt_load_frozen(void* h, const char* name, const void* dev_ptr, int dtype,
   size_t n = 1;
   for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
   std::string nm(name);
-  if (nm == "logit_scale" || nm == "token_embedding.weight") return 0;  // not used by the towers
-  E->fold_ready = false;      // W gamma / b + W beta of the LayerNorm folding are rebuilt from the new tensors (prepare_fold)
+  if (nm == "logit_scale") return 0;  // not used by the towers
+  const bool is_tok = nm == "token_embedding.weight";   // read by mvlpt_text_encode_tokens only: the towers' packed state is untouched
+  if (!is_tok) E->fold_ready = false;      // W gamma / b + W beta of the LayerNorm folding are rebuilt from the new tensors (prepare_fold)
   // stage as fp32
   const float* p32 = (const float*)dev_ptr;
   if (dtype != MVLPT_DT_F32) {
@@ -854,6 +858,11 @@ int mvlpt_load_frozen(void* h, const char* name, const void* dev_ptr, int dtype,
   } else if (nm == "positional_embedding") { if (!is2(A.context_length, dtw)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->tpos, s);
   } else if (nm == "ln_final.weight") { if (!is1(dtw)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->ln_final.g, s);
   } else if (nm == "ln_final.bias") { if (!is1(dtw)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->ln_final.b, s);
+  } else if (is_tok) {
+    if (!(ndim == 2 && shape[0] > 0 && shape[0] <= INT32_MAX && shape[1] == dtw)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
+    E->vocab = 0;
+    rc = upload_f32(E, p32, n, &E->tok_emb, s);
+    if (!rc) E->vocab = (int)shape[0];
   } else if (nm == "text_projection") {
     if (!is2(dtw, e)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
     void *w = nullptr, *wt = nullptr;
@@ -1131,9 +1140,10 @@ static bool text_exact(const Engine* E) { return E->prec_mode == MVLPT_PREC_SPLI
 // The text tower over C sequences.  G == 0: mvlpt_text_fwd (prefix / suffix / layout / eot [C, ...], ctx [n_ctx, d] or CSC [C, n_ctx, d]);
 // G > 0: mvlpt_text_fwd_grouped, C = G * Cg sequences s = g * Cg + c from the [Cg, ...] class tables and ctx [G, n_ctx, d].
 // ranged: mvlpt_text_fwd_ranged, G groups over the [Cg, ...] class tables, C = S sequences described by E->t_range_host.
+// ids: mvlpt_text_encode_tokens, C sequences of token ids (E->t_ids_host); no prefix / suffix / ctx / layout / eot tables.
 static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
                          const int32_t* layout, const int32_t* eot, int G, int Cg, int C, int L, float* feat_out, int save_for_bwd,
-                         mvlpt_stream_t stream, bool ranged = false) {
+                         mvlpt_stream_t stream, bool ranged = false, bool ids = false) {
   if (int rc = mvlpt_frozen_ready(E)) return rc;
   if ((n_ctx > 0) != (ctx != nullptr) || n_ctx < 0 || n_ctx > L - 2) return fail(E, MVLPT_ERR_ARG, "text_fwd: ctx pointer and n_ctx disagree");
   const MvlptArch& A = E->arch;
@@ -1152,7 +1162,8 @@ static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, co
   // ctx_pos is per class for the grouped / ranged towers; a ranged tower may run fewer sequences than there are classes
   const size_t ctx_rows = (size_t)(ranged && Cg > C ? Cg : C) * (n_ctx > 0 ? n_ctx : 1);
   const size_t range_ints = ranged ? E->t_range_host.size() : 0;
-  size_t need = text_ws_bytes(E, C, L, save, exact, ctx_rows) + align256(range_ints * 4);
+  const size_t ids_ints = ids ? E->t_ids_host.size() : 0;
+  size_t need = text_ws_bytes(E, C, L, save, exact, ctx_rows) + align256(range_ints * 4) + align256(ids_ints * 4);
   E->ts.valid = false;
   HIPCHK(E, E->txt_ws.reserve(need));
   Bump bp; bp.base = (char*)E->txt_ws.p; bp.cap = E->txt_ws.cap;
@@ -1161,6 +1172,7 @@ static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, co
   E->eot_rows = bp.take<int32_t>(C);
   E->ctx_pos = bp.take<int32_t>(ctx_rows);
   int32_t* range_dev = ranged ? bp.take<int32_t>(range_ints) : nullptr;
+  int32_t* ids_dev = ids ? bp.take<int32_t>(ids_ints) : nullptr;
   E->txc32 = bp.take<float>((size_t)C * dtw); E->txm32 = bp.take<float>((size_t)C * dtw); E->txo32 = bp.take<float>((size_t)C * dtw);
   E->tdxc32 = bp.take<float>((size_t)C * dtw); E->tdhc32 = bp.take<float>((size_t)C * dtw);
   E->tac16 = bp.take_bytes((size_t)C * dtw * 2 * X); E->thc16 = bp.take_bytes((size_t)C * dtw * 2 * X);
@@ -1174,6 +1186,12 @@ static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, co
   E->t_ranged = ranged; E->t_rlo = range_dev; E->t_rstart = ranged ? range_dev + G : nullptr;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
+  if (ids) {
+    ProfScope ps(E, s, PC_GLUE, 0, (double)C * L * dtw * 12.0);
+    HIPCHK(E, hipMemcpyAsync(ids_dev, E->t_ids_host.data(), ids_ints * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(E, hipMemcpyAsync(E->eot_rows, ids_dev + (size_t)C * L, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(E, launch_embed_tokens(E->tok_emb, E->tpos, ids_dev, L, st.x[0], C, L, dtw, s));
+  } else
   { ProfScope ps(E, s, PC_GLUE, 0, (double)C * L * dtw * 12.0);
     if (ranged) {
       const int32_t *seq_cls = range_dev + 2 * G + 1, *seq_grp = seq_cls + C;
@@ -1265,6 +1283,42 @@ int mvlpt_text_fwd_ranged(void* h, const float* prefix, const float* suffix, con
   if (S == 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: every range is empty");
   if (S > (int64_t)INT32_MAX / L) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: too many sequences");
   return text_fwd_impl(E, prefix, suffix, ctx, 0, n_ctx, layout, eot, G, C, (int)S, L, feat_out, save_for_bwd, stream, true);
+}
+
+// CLIP.encode_text (clip/model.py:343-356) over S sequences of token ids, trimmed to their first L positions
+int mvlpt_text_encode_tokens(void* h, const int32_t* ids, int ld, int S, int L, float* feat_out, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !ids || !feat_out || S <= 0 || L <= 0 || ld < L) return fail(E, MVLPT_ERR_ARG, "text_encode_tokens: null/invalid argument");
+  if (!E->tok_emb || E->vocab <= 0)
+    return fail(E, MVLPT_ERR_STATE, "text_encode_tokens: token_embedding.weight is not loaded (mvlpt_load_frozen)");
+  if (L < MVLPT_TEXT_MIN_L) return fail(E, MVLPT_ERR_ARG, "text_encode_tokens: L is below MVLPT_TEXT_MIN_L");
+  if (L > E->arch.context_length) return fail(E, MVLPT_ERR_ARG, "text_encode_tokens: L exceeds context_length");
+  if (S > 65535) return fail(E, MVLPT_ERR_ARG, "text_encode_tokens: more than 65535 sequences (the attention launches put the sequence on grid.y)");
+  // every id the kernel will read is checked here, and the EOT row (first occurrence of the row maximum over all ld columns, as
+  // text.argmax(dim=-1)) must lie inside the trimmed sequence; nothing is launched for a bad table
+  std::vector<int32_t>& t = E->t_ids_host;
+  t.resize((size_t)S * L + S);
+  int32_t* rows = t.data() + (size_t)S * L;
+  for (int q = 0; q < S; ++q) {
+    const int32_t* r = ids + (size_t)q * ld;
+    int arg = 0;
+    for (int i = 1; i < ld; ++i) if (r[i] > r[arg]) arg = i;
+    if (arg >= L) return fail(E, MVLPT_ERR_ARG, "text_encode_tokens: the EOT position of sequence " + std::to_string(q) + " is not below L");
+    for (int i = 0; i < L; ++i) {
+      if (r[i] < 0 || r[i] >= E->vocab)
+        return fail(E, MVLPT_ERR_ARG, "text_encode_tokens: token id outside [0, vocab) in sequence " + std::to_string(q));
+      t[(size_t)q * L + i] = r[i];
+    }
+    rows[q] = q * L + arg;
+  }
+  return text_fwd_impl(E, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, S, S, L, feat_out, 0, stream, false, true);
+}
+
+int mvlpt_text_ensemble(const float* feats, int T, int C, int e, float* out, mvlpt_stream_t stream) {
+  if (!feats || !out || T <= 0 || C <= 0 || e <= 0) { g_create_err = "text_ensemble: null/invalid argument"; return MVLPT_ERR_ARG; }
+  const hipError_t rc = launch_ensemble_features(feats, out, T, C, e, (hipStream_t)stream);
+  if (rc != hipSuccess) { g_create_err = std::string("text_ensemble: ") + hipGetErrorString(rc); return MVLPT_ERR_HIP; }
+  return 0;
 }
 
 int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, int64_t* out) {
@@ -1825,6 +1879,26 @@ int mvlpt_op_assemble_prompts(const float* prefix, const float* suffix, const fl
   OPCHK(launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, pos, x, C, L, d, s));
   OPCHK(launch_eot_rows(eot, eot_rows, C, L, s));
   OPCHK(launch_build_ctx_pos(layout, ctx_pos, C, L, n_ctx, s));
+  return 0;
+}
+
+// The zero-shot glue without a tower (tests): ids is a DEVICE int32 [S, ld] table here, and every id in columns 0 .. L-1 must be inside
+// [0, vocab) — the caller's responsibility at this level (mvlpt_text_encode_tokens checks its host table).
+int mvlpt_op_embed_tokens(const float* emb, const float* pos, const int32_t* ids, int ld, float* x, int S, int L, int d,
+                          mvlpt_stream_t stream) {
+  if (!emb || !pos || !ids || !x || S <= 0 || L <= 0 || ld < L || d <= 0 || d % 4) {
+    g_create_err = "op_embed_tokens: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_embed_tokens(emb, pos, ids, ld, x, S, L, d, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_ensemble_features(const float* feats, float* out, int T, int C, int e, mvlpt_stream_t stream) {
+  if (!feats || !out || T <= 0 || C <= 0 || e <= 0) { g_create_err = "op_ensemble_features: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_ensemble_features(feats, out, T, C, e, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_normalize_rows(const float* x, float* xn, float* norm, int rows, int d, mvlpt_stream_t stream) {
+  if (!x || !xn || !norm || rows <= 0 || d <= 0) { g_create_err = "op_normalize_rows: null/invalid argument"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_normalize_rows(x, xn, norm, rows, d, (hipStream_t)stream));
   return 0;
 }
 

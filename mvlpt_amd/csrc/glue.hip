@@ -556,6 +556,30 @@ hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipS
   return hipGetLastError();
 }
 
+// ---- token ids: x[s,t,:] = emb[ids[s,t], :] + pos[t, :]   (clip/model.py encode_text: token_embedding(text) + positional_embedding)
+// ids [S, ld] with ld >= L, only columns 0 .. L-1 are read; every id read must be inside the table (the callers check on the host)
+__global__ void embed_tokens_kernel(const float* __restrict__ emb, const float* __restrict__ pos, const int32_t* __restrict__ ids,
+                                    int ld, float* __restrict__ x, int S, int L, int d) {
+  const int d4 = d / 4;
+  const size_t total = (size_t)S * L * d4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int c4 = (int)(i % d4);
+    const size_t tok = i / d4;
+    const int pos_i = (int)(tok % L);
+    const size_t seq = tok / L;
+    const float* src = emb + (size_t)ids[seq * ld + pos_i] * d;
+    *(f32x4*)(x + tok * d + c4 * 4) = *(const f32x4*)(src + c4 * 4) + *(const f32x4*)(pos + (size_t)pos_i * d + c4 * 4);
+  }
+}
+hipError_t launch_embed_tokens(const float* emb, const float* pos, const int32_t* ids, int ld, float* x, int S, int L, int d,
+                               hipStream_t s) {
+  if (S <= 0 || L <= 0 || ld < L || d <= 0 || d % 4) return hipErrorInvalidValue;
+  const size_t total = (size_t)S * L * (d / 4);
+  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  hipLaunchKernelGGL(embed_tokens_kernel, dim3(grid), dim3(256), 0, s, emb, pos, ids, ld, x, S, L, d);
+  return hipGetLastError();
+}
+
 // ---- grouped (image-conditioned) prompts: sequence s = g * C + c pairs class c with context block g (trainers/cocoop.py:123-161)
 // x[s,i,:] = (layout[c,i] >= 0 ? fixed tokens of class c : ctx[g, row]) + pos[i]; prefix / suffix / layout stay [C, ...]
 __global__ void assemble_prompts_grouped_kernel(const float* __restrict__ prefix, const float* __restrict__ suffix,
@@ -949,6 +973,56 @@ __global__ __launch_bounds__(256) void normalize_rows_kernel(const float* __rest
 }
 hipError_t launch_normalize_rows(const float* x, float* xn, float* norm, int rows, int d, hipStream_t s) {
   hipLaunchKernelGGL(normalize_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, xn, norm, rows, d);
+  return hipGetLastError();
+}
+
+// Prompt ensembling (trainers/zsclip.py:88-96): out[c] = normalize((1/T) sum_t feats[t,c] / |feats[t,c]|), feats [T, C, e] template-major.
+// One wave per class; lane l owns columns l, l + 64, ... (the column map and the arithmetic of normalize_rows_kernel, so that T == 1 —
+// where the mean of one unit vector is that vector and the second normalisation is skipped — gives its bits); the templates are summed
+// in the order t = 0 .. T-1 in per-lane fp32 accumulators: no atomics, reruns are bit-identical.  e <= 64 * ENS_COLS.
+constexpr int ENS_COLS = 16;
+__global__ __launch_bounds__(256) void ensemble_features_kernel(const float* __restrict__ feats, float* __restrict__ out, int T, int C,
+                                                                int e) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= C) return;
+  float acc[ENS_COLS];
+#pragma unroll
+  for (int j = 0; j < ENS_COLS; ++j) acc[j] = 0.f;
+  for (int t = 0; t < T; ++t) {
+    const float* p = feats + ((size_t)t * C + row) * e;
+    float v[ENS_COLS];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < ENS_COLS; ++j) {
+      const int c = lane + 64 * j;
+      v[j] = c < e ? p[c] : 0.f;
+      if (c < e) s += v[j] * v[j];
+    }
+    const float nm = sqrtf(wave_sum(s));
+#pragma unroll
+    for (int j = 0; j < ENS_COLS; ++j) acc[j] += v[j] / nm;
+  }
+  float nm = 1.f;
+  if (T > 1) {
+    const float fT = (float)T;
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < ENS_COLS; ++j) {
+      acc[j] = acc[j] / fT;
+      if (lane + 64 * j < e) s += acc[j] * acc[j];
+    }
+    nm = sqrtf(wave_sum(s));
+  }
+#pragma unroll
+  for (int j = 0; j < ENS_COLS; ++j) {
+    const int c = lane + 64 * j;
+    if (c < e) out[(size_t)row * e + c] = T > 1 ? acc[j] / nm : acc[j];
+  }
+}
+hipError_t launch_ensemble_features(const float* feats, float* out, int T, int C, int e, hipStream_t s) {
+  if (T <= 0 || C <= 0 || e <= 0 || e > 64 * ENS_COLS) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ensemble_features_kernel, dim3((C + 3) / 4), dim3(256), 0, s, feats, out, T, C, e);
   return hipGetLastError();
 }
 

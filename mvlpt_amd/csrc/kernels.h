@@ -243,6 +243,9 @@ hipError_t launch_assemble_prompts(const float* prefix, const float* suffix, con
                                    const int32_t* layout, const float* pos, float* x, int C, int L, int d, hipStream_t s);
 hipError_t launch_build_ctx_pos(const int32_t* layout, int32_t* ctx_pos, int C, int L, int n_ctx, hipStream_t s);
 hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipStream_t s);
+// token ids (clip/model.py encode_text): x [S, L, d] = emb[ids[s, t]] + pos[t]; ids int32 [S, ld], ld >= L, columns 0 .. L-1 read, every one
+// of them inside the table (checked on the host by the callers); d % 4 == 0
+hipError_t launch_embed_tokens(const float* emb, const float* pos, const int32_t* ids, int ld, float* x, int S, int L, int d, hipStream_t s);
 // grouped prompts (trainers/cocoop.py:123-161): sequence s = g*C + c = class c's prefix / suffix / layout row + context block g of
 // ctx [G, n_ctx, d]; eot rows s*L + eot[s % C]
 hipError_t launch_assemble_prompts_grouped(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
@@ -288,6 +291,9 @@ hipError_t launch_respk_unpack_rows(const void* hi, const uint8_t* lo, int row_m
 
 // ---------------------------------------------------------------- head: cosine logits + cross-entropy (fp32)
 hipError_t launch_normalize_rows(const float* x, float* xn, float* norm, int rows, int d, hipStream_t s);
+// prompt ensembling (trainers/zsclip.py:88-96): out [C, e] = normalize(mean_t normalize(feats[t, c])), feats [T, C, e]; fixed summation
+// order over t; T == 1 gives the bits of launch_normalize_rows; e <= 1024
+hipError_t launch_ensemble_features(const float* feats, float* out, int T, int C, int e, hipStream_t s);
 hipError_t launch_logits(const float* imn, const float* txn, float scale, const int32_t* lo, const int32_t* hi,
                          float* logits, int B, int C, int e, hipStream_t s);
 hipError_t launch_cross_entropy(const float* logits, const void* labels, int label_kind, int B, int C, float* row_loss,

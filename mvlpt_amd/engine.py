@@ -283,6 +283,54 @@ class Engine:
         self._txt_state = (tuple(ctx.shape), layout, eot) if save_for_bwd else None
         return feat
 
+    def load_token_embedding(self, weight: torch.Tensor) -> None:
+        """Opt-in: keep an fp32 copy of `token_embedding.weight` [vocab, text_width] on the device for text_encode_tokens
+        (load_frozen skips the key, so the prompt-tuning routes never pay for it)."""
+        with torch.cuda.device(self.device):
+            tg = weight.detach().float().to(self.device).contiguous()
+            if tg.dim() != 2 or tg.shape[1] != self.arch.transformer_width:
+                raise ValueError(f"token_embedding.weight must be [vocab, {self.arch.transformer_width}], got {tuple(tg.shape)}")
+            shape = (C.c_int64 * 2)(*tg.shape)
+            _lib.check(lib.mvlpt_load_frozen(self.h, b"token_embedding.weight", _ptr(tg), DT_F32, shape, 2, _stream()), self.h,
+                       "load_frozen(token_embedding.weight)")
+            torch.cuda.current_stream().synchronize()   # tg may be freed right after
+        self.vocab_size = int(tg.shape[0])
+
+    @_on_device
+    def text_encode_tokens(self, ids, L: Optional[int] = None) -> torch.Tensor:
+        """CLIP.encode_text over token ids (mvlpt_text_encode_tokens): `ids` is a HOST integer array [S, ld] (CPU tensor or numpy);
+        the tower runs the first L columns (default: all of them).  Un-normalised features [S, embed] fp32 on the device."""
+        if isinstance(ids, torch.Tensor):
+            if ids.is_cuda:
+                raise ValueError("token ids are a host array (they are checked on the host and uploaded with the call)")
+            ids = ids.numpy()
+        import numpy as np
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        if ids.ndim != 2:
+            raise ValueError("token ids must be [S, ld]")
+        S, ld = ids.shape
+        L = ld if L is None else int(L)
+        feat = torch.empty(S, self.arch.embed_dim, device=self.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_text_encode_tokens(self.h, C.c_void_p(ids.ctypes.data), ld, S, L, _ptr(feat), _stream()), self.h,
+                   "text_encode_tokens")
+        self._txt_state = None
+        return feat
+
+    def text_encode_workspace_bytes(self, n_seq: int, L: int) -> int:
+        """Workspace text_encode_tokens reserves for `n_seq` sequences of length L: the tower's plus the id table (include/mvlpt_hip.h)."""
+        return self.text_workspace_bytes(n_seq, L, False) + ((4 * (n_seq * L + n_seq) + 255) & ~255)
+
+    def text_ensemble(self, feats: torch.Tensor) -> torch.Tensor:
+        """Prompt ensembling (mvlpt_text_ensemble): feats [T, C, e] fp32, template-major -> [C, e] unit rows."""
+        feats = _req(feats, torch.float32, "feats")
+        if feats.dim() != 3:
+            raise ValueError("feats must be [T, C, embed]")
+        T, Cn, e = feats.shape
+        out = torch.empty(Cn, e, device=feats.device, dtype=torch.float32)
+        with torch.cuda.device(feats.device):
+            _lib.check(lib.mvlpt_text_ensemble(_ptr(feats), T, Cn, e, _ptr(out), _stream()), None, "text_ensemble")
+        return out
+
     def text_workspace_bytes(self, n_seq: int, L: int, save_for_bwd: bool) -> int:
         """Text-tower workspace a forward over `n_seq` sequences of length L reserves (mvlpt_text_workspace_bytes)."""
         out = C.c_int64()
@@ -556,6 +604,34 @@ def op_gather_ctx_grad_ranged(dx, ctx_pos, class_lo, class_hi) -> torch.Tensor:
     _lib.check(lib.mvlpt_op_gather_ctx_grad_ranged(_ptr(dx.contiguous()), _ptr(ctx_pos.to(torch.int32).contiguous()), lo, hi, G, C_, L, d,
                                                    n, _ptr(dctx), _stream()), None, "op_gather_ctx_grad_ranged")
     return dctx
+
+
+def op_embed_tokens(emb, pos, ids, L: int, out=None) -> torch.Tensor:
+    """x [S, L, d] = emb[ids[:, :L]] + pos[:L] (the entry of mvlpt_text_encode_tokens); ids int32 [S, ld] on the DEVICE, only columns
+    0 .. L-1 are read and must be rows of emb.  `out`: a preallocated buffer whose first S * L * d floats are written."""
+    emb, pos, ids = _req(emb, torch.float32, "emb"), _req(pos, torch.float32, "pos"), _req(ids, torch.int32, "ids")
+    S, ld = ids.shape
+    d = emb.shape[1]
+    x = out if out is not None else torch.empty(S, L, d, device=emb.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_embed_tokens(_ptr(emb), _ptr(pos), _ptr(ids), ld, _ptr(x), S, int(L), d, _stream()), None, "op_embed_tokens")
+    return x
+
+
+def op_ensemble_features(feats) -> torch.Tensor:
+    feats = _req(feats, torch.float32, "feats")
+    T, Cn, e = feats.shape
+    out = torch.empty(Cn, e, device=feats.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_ensemble_features(_ptr(feats), _ptr(out), T, Cn, e, _stream()), None, "op_ensemble_features")
+    return out
+
+
+def op_normalize_rows(x):
+    """(x / |x|, |x|) per row: the head's normalisation kernel."""
+    x = _req(x, torch.float32, "x")
+    rows, d = x.shape
+    xn, norm = torch.empty_like(x), torch.empty(rows, device=x.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_normalize_rows(_ptr(x), _ptr(xn), _ptr(norm), rows, d, _stream()), None, "op_normalize_rows")
+    return xn, norm
 
 
 def op_sgemm_bt(A, Bt, alpha=None) -> torch.Tensor:

@@ -24,6 +24,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 import torch
 import torch.nn as nn
 
+from ._lib import TEXT_MIN_L
 from .engine import Engine
 from .weights import ClipArch, _randn, arch_from_state_dict
 
@@ -130,14 +131,101 @@ class FrozenCLIP:
         self.tokenizer = tokenizer or default_tokenizer()
         self._token_embedding = state_dict.get("token_embedding.weight")
         self._token_seed = token_seed
+        self._token_embedding_loaded = False      # the device copy encode_text needs (Engine.load_token_embedding), made on first use
+        self.max_text_workspace_bytes = DEFAULT_MAX_TEXT_WORKSPACE_BYTES
+        self.min_sequences_per_chunk = MIN_SEQUENCES_PER_CHUNK
         self.dtype = torch.float32   # dtype of the prompt parameters (see module docstring)
 
     def token_embedding(self, ids: torch.Tensor) -> torch.Tensor:
         """clip_model.token_embedding(tokenized_prompts) (trainers/mvlpt.py:306-307); init-time only, CPU."""
+        return self._token_table().float().cpu()[ids.cpu()]
+
+    def _token_table(self) -> torch.Tensor:
         if self._token_embedding is None:
             self._token_embedding = _randn("token_embedding.weight", self._token_seed,
                                            (self.arch.vocab_size, self.arch.transformer_width), 0.02)
-        return self._token_embedding.float().cpu()[ids.cpu()]
+        return self._token_embedding
+
+    # ------------------------------------------------------------------ clip_model.encode_text / encode_image
+    def text_chunks(self, eot: Sequence[int], trim: bool = True):
+        """The chunks encode_text runs for sequences with these EOT positions (plan_text_chunks on this engine's workspace sizes)."""
+        return plan_text_chunks(eot, self.engine.text_encode_workspace_bytes, self.max_text_workspace_bytes,
+                                min_chunk=self.min_sequences_per_chunk, force_len=None if trim else self.context_length)
+
+    @torch.no_grad()
+    def encode_text(self, tokenized, trim: bool = True) -> torch.Tensor:
+        """clip_model.encode_text(tokenized) (clip/model.py:343-356): token ids [n, context_length] (a HOST tensor, as clip.tokenize
+        returns) -> un-normalised features [n, embed] fp32 on the device, rows in input order.  The sequences are sorted by EOT
+        position and run in chunks of their own length L = max eot + 1 (exact: the tower is causal, nothing behind the EOT token
+        reaches the EOT row) whose workspace stays under `max_text_workspace_bytes`; trim = False runs every chunk at the full
+        context length instead.  The first call uploads the token embedding (Engine.load_token_embedding)."""
+        ids = torch.as_tensor(tokenized).cpu()
+        if ids.dim() != 2 or ids.shape[0] == 0:
+            raise ValueError("tokenized must be [n, context_length]")
+        if not self._token_embedding_loaded:
+            self.engine.load_token_embedding(self._token_table())
+            self._token_embedding_loaded = True
+        ids = ids.to(torch.int32).contiguous()
+        chunks = self.text_chunks(ids.argmax(dim=-1).tolist(), trim)
+        out = torch.empty(ids.shape[0], self.arch.embed_dim, device=self.device, dtype=torch.float32)
+        for L, members in chunks:
+            idx = torch.tensor(members, dtype=torch.long)
+            feats = self.engine.text_encode_tokens(ids[idx], L)
+            out.index_copy_(0, idx.to(self.device), feats)
+        self.last_text_chunks = [(L, len(m)) for L, m in chunks]
+        return out
+
+    @torch.no_grad()
+    def encode_image(self, image: torch.Tensor) -> torch.Tensor:
+        """clip_model.encode_image(image) (clip/model.py:340-341): un-normalised features [B, embed] fp32."""
+        return self.engine.image_fwd(image.to(self.device), None, None, save_for_bwd=False)
+
+
+# Workspace budget of one encode_text chunk (not a reference key), the figure CoCoOp's grouped tower uses
+DEFAULT_MAX_TEXT_WORKSPACE_BYTES = 16 << 30
+# sequences per tower: the attention launches put the sequence index on grid.y
+MAX_SEQUENCES_PER_TOWER = 32768
+# a bucket of equal-length sequences smaller than this takes the next lengths in as well (a tower over a handful of rows leaves the
+# device idle; the positions it adds are bounded by min_chunk * (L_chunk - L_own))
+MIN_SEQUENCES_PER_CHUNK = 512
+
+
+def plan_text_chunks(eot: Sequence[int], workspace_bytes: Callable[[int, int], int], budget: int, min_len: int = TEXT_MIN_L,
+                     max_seq: int = MAX_SEQUENCES_PER_TOWER, min_chunk: int = MIN_SEQUENCES_PER_CHUNK,
+                     force_len: Optional[int] = None):
+    """Cut sequences with EOT positions `eot` into towers: [(L, [indices into eot])].  Pure host arithmetic.
+    The sequences are sorted by EOT position (ties by index).  A chunk starts at the shortest sequence not yet placed, takes every
+    sequence of that length, and goes on into longer ones only while it holds fewer than `min_chunk`; it never holds more than
+    `max_seq` sequences and `workspace_bytes(count, L)` never exceeds `budget`, with L = the longest member's eot + 1, raised to
+    `min_len` (force_len: that length for every chunk).  Chunks are returned largest workspace first, so that a grow-only workspace
+    is sized once.  Raises ValueError when a single sequence does not fit the budget."""
+    eot = [int(v) for v in eot]
+    if any(v < 0 for v in eot):
+        raise ValueError("EOT positions must be >= 0")
+    order = sorted(range(len(eot)), key=lambda i: (eot[i], i))
+
+    def length(i):
+        return force_len if force_len is not None else max(eot[i] + 1, min_len)
+
+    if force_len is not None and order and eot[order[-1]] >= force_len:
+        raise ValueError(f"an EOT position lies outside the forced length {force_len}")
+    chunks, a, n = [], 0, len(order)
+    while a < n:
+        if workspace_bytes(1, length(order[a])) > budget:
+            raise ValueError(f"one sequence of length {length(order[a])} needs {workspace_bytes(1, length(order[a]))} bytes of text "
+                             f"workspace, over the budget of {budget}")
+        b = a + 1
+        while b < n and b - a < max_seq:
+            same = length(order[b]) == length(order[b - 1])
+            if not same and b - a >= min_chunk:
+                break
+            if workspace_bytes(b - a + 1, length(order[b])) > budget:
+                break
+            b += 1
+        chunks.append((length(order[b - 1]), order[a:b]))
+        a = b
+    chunks.sort(key=lambda c: -workspace_bytes(len(c[1]), c[0]))
+    return chunks
 
 
 # ------------------------------------------------------------------------------------------------ UPT projection

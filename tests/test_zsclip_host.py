@@ -1,0 +1,207 @@
+"""Zero-shot CLIP without a GPU: the C ABI's new symbols, the float64 references of tests/zs_ref.py, the tokenizer against the fixtures'
+clip.tokenize ids, the encode_text chunk planner and the template handling of mvlpt_amd.zsclip."""
+import json
+import os
+import random
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+from tests import zs_ref
+from tests.golden_util import GOLDEN, load_npz, t
+
+FIXTURES = ["tiny_zsclip", "tiny_zsclip_ensemble", "full_vitb16_zsclip"]
+
+
+def templates_fixture():
+    with open(os.path.join(GOLDEN, "zsclip_templates.json")) as f:
+        return json.load(f)
+
+
+# ------------------------------------------------------------------------------------------------ ABI
+def test_abi_exports_the_zero_shot_symbols():
+    from mvlpt_amd import _lib
+    for name in ("mvlpt_text_encode_tokens", "mvlpt_text_ensemble", "mvlpt_op_embed_tokens", "mvlpt_op_ensemble_features",
+                 "mvlpt_op_normalize_rows"):
+        assert name in _lib.SIGNATURES, name
+        assert hasattr(_lib.lib, name), f"{name} is not exported by libmvlpt_hip.so"
+    header = open(os.path.join(os.path.dirname(GOLDEN), "..", "include", "mvlpt_hip.h")).read()
+    assert f"MVLPT_TEXT_MIN_L = {_lib.TEXT_MIN_L}" in header
+
+
+# ------------------------------------------------------------------------------------------------ references
+def test_embed_reference_is_the_exactly_rounded_fp32_sum():
+    g = torch.Generator().manual_seed(1)
+    emb, pos = torch.randn(50, 24, generator=g), torch.randn(9, 24, generator=g)
+    ids = torch.randint(0, 50, (4, 9), generator=g)
+    ids[:, 6:] = 10 ** 6                                         # columns behind L are never read
+    ref = zs_ref.embed_ref64(emb, pos, ids, 6)
+    assert ref.dtype == torch.float64 and ref.shape == (4, 6, 24)
+    assert torch.equal(ref.float(), emb[ids[:, :6]] + pos[:6])
+
+
+@pytest.mark.parametrize("T,C,e", [(1, 3, 128), (8, 5, 512), (81, 2, 768)])
+def test_ensemble_reference_and_bound(T, C, e):
+    f = zs_ref.ensemble_inputs(T, C, e)
+    ref, bound = zs_ref.ensemble_ref64(f), zs_ref.ensemble_bound(f)
+    assert torch.allclose(ref.norm(dim=-1), torch.ones(C, dtype=torch.float64), atol=1e-14)
+    # the reference's own fp32 loop (trainers/zsclip.py:88-96) is one legal evaluation order: it must sit inside the bound
+    mean = 0
+    for k in range(T):
+        mean = mean + f[k] / f[k].norm(dim=-1, keepdim=True)
+    mean = mean / T
+    got = mean / mean.norm(dim=-1, keepdim=True)
+    assert bool(((got.double() - ref).abs() <= bound).all())
+    assert float(bound.max()) < 1e-3 * float(ref.abs().max())      # the bound is tight enough to mean something
+    if T == 1:
+        x = f[0].double()
+        assert torch.allclose(ref, x / x.norm(dim=-1, keepdim=True), atol=1e-15)
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+def test_fixture_text_features_follow_from_their_per_template_features(name):
+    case = load_npz(name)
+    per = t(case["text_features_per_template"])
+    T, C = per.shape[:2]
+    assert T == len(case["templates"]) and C == len(case["classnames"])
+    ref = zs_ref.ensemble_ref64(per)
+    got = t(case["text_features"]).double()
+    assert bool(((got - ref).abs() <= zs_ref.ensemble_bound(per)).all())
+
+
+# ------------------------------------------------------------------------------------------------ tokens
+@pytest.mark.parametrize("name", FIXTURES)
+def test_bpe_tokenizer_reproduces_the_fixture_token_ids(name):
+    from mvlpt_amd.model import default_tokenizer
+    from mvlpt_amd.zsclip import build_prompts
+    case = load_npz(name)
+    prompts = build_prompts([str(s) for s in case["templates"]], [str(c) for c in case["classnames"]])
+    ids = default_tokenizer().tokenize(prompts, 77)
+    assert torch.equal(ids, t(case["tokenized_prompts"]))
+
+
+def test_fixture_templates_are_the_ones_the_template_file_lists():
+    tf = templates_fixture()
+    assert len(tf["imagenet"]) == 80 and len(tf["imagenet_select"]) == 7 and all("{}" in s for s in tf["imagenet"])
+    one, ens = load_npz("tiny_zsclip"), load_npz("tiny_zsclip_ensemble")
+    own = tf["per_dataset"][str(one["dataset_name"])]
+    assert [str(s) for s in one["templates"]] == [own]
+    assert [str(s) for s in ens["templates"]] == tf["imagenet_select"] + [own]
+
+
+# ------------------------------------------------------------------------------------------------ chunk planner
+def _bytes(count, L):
+    return 1000 + 64 * count * L + 4 * count
+
+
+def _check_plan(eot, budget, **kw):
+    from mvlpt_amd.model import plan_text_chunks
+    chunks = plan_text_chunks(eot, _bytes, budget, **kw)
+    seen = sorted(i for _, members in chunks for i in members)
+    assert seen == list(range(len(eot))), "every sequence lands in exactly one chunk"
+    for L, members in chunks:
+        assert members and all(L >= eot[i] + 1 for i in members)
+        assert L >= kw.get("min_len", 3)
+        assert _bytes(len(members), L) <= budget
+        assert len(members) <= kw.get("max_seq", 32768)
+    return chunks
+
+
+def test_chunk_planner_on_random_eot_vectors():
+    rng = random.Random(0)
+    for trial in range(40):
+        n = rng.randint(1, 400)
+        eot = [rng.randint(1, 76) for _ in range(n)]
+        budget = rng.choice([_bytes(1, 77), _bytes(7, 77), _bytes(50, 40), 10 ** 9])
+        _check_plan(eot, budget, min_chunk=rng.choice([1, 16, 512]), max_seq=rng.choice([5, 64, 32768]))
+    chunks = _check_plan([9] * 300, 10 ** 9)                        # all equal: one chunk of that length
+    assert [(L, len(m)) for L, m in chunks] == [(10, 300)]
+    chunks = _check_plan([5] * 600 + [76], 10 ** 9)                 # one very long sequence does not drag the short ones to 77
+    assert sorted((L, len(m)) for L, m in chunks) == [(6, 600), (77, 1)]
+    chunks = _check_plan([1, 0, 1], 10 ** 9)                        # raised to the tower's minimum length
+    assert all(L == 3 for L, _ in chunks)
+    chunks = _check_plan([4, 9, 30], 10 ** 9, force_len=77)         # the untrimmed plan
+    assert [(L, len(m)) for L, m in chunks] == [(77, 3)]
+    tight = _check_plan([8] * 100, _bytes(30, 9))                   # a budget of 30 sequences: 4 chunks
+    assert len(tight) == 4
+
+
+def test_chunk_planner_refuses_a_budget_below_one_sequence():
+    from mvlpt_amd.model import plan_text_chunks
+    with pytest.raises(ValueError):
+        plan_text_chunks([5, 40, 6], _bytes, _bytes(1, 41) - 1)
+    with pytest.raises(ValueError):
+        plan_text_chunks([5, 80], _bytes, 10 ** 9, force_len=77)
+
+
+def test_chunk_planner_is_deterministic_and_sorted_by_eot():
+    from mvlpt_amd.model import plan_text_chunks
+    eot = [7, 3, 7, 12, 3, 9]
+    a = plan_text_chunks(eot, _bytes, 10 ** 9, min_chunk=1)
+    assert a == plan_text_chunks(eot, _bytes, 10 ** 9, min_chunk=1)
+    assert sorted(a) == [(4, [1, 4]), (8, [0, 2]), (10, [5]), (13, [3])]
+    assert a[0][0] == 8 or a[0][0] == 13                             # largest workspace first
+    assert _bytes(len(a[0][1]), a[0][0]) == max(_bytes(len(m), L) for L, m in a)
+
+
+# ------------------------------------------------------------------------------------------------ templates
+def test_prompts_replace_underscores_and_run_template_major():
+    from mvlpt_amd.zsclip import build_prompts
+    assert build_prompts(["a photo of a {}.", "{} texture."], ["sea_horse", "great_white_shark"]) == [
+        "a photo of a sea horse.", "a photo of a great white shark.", "sea horse texture.", "great white shark texture."]
+
+
+def _cfg(templates):
+    from mvlpt_amd.config import get_cfg_default
+    cfg = get_cfg_default()
+    cfg.MODEL.BACKBONE.NAME = "tiny"
+    cfg.INPUT.SIZE = (32, 32)
+    cfg.TRAINER.ZSCLIP.TEMPLATES = templates
+    return cfg
+
+
+def test_template_configuration():
+    from mvlpt_amd.config import get_cfg_default
+    from mvlpt_amd.zsclip import ZeroshotCLIP, ZeroshotCLIP2, read_templates
+    assert get_cfg_default().TRAINER.ZSCLIP.TEMPLATES == ["a photo of a {}."]
+    two = _cfg(["a photo of a {}.", "a drawing of a {}."])
+    with pytest.raises(ValueError):
+        ZeroshotCLIP.check_cfg(SimpleNamespace(single_template=True), two)
+    ZeroshotCLIP2.check_cfg(SimpleNamespace(single_template=False), two)
+    assert read_templates(two, single=False) == two.TRAINER.ZSCLIP.TEMPLATES
+    for bad in ([], ["no placeholder"], "a photo of a {}."):
+        with pytest.raises(ValueError):
+            read_templates(_cfg(bad), single=False)
+    cfg = get_cfg_default()
+    cfg.merge_from_list(["TRAINER.ZSCLIP.TEMPLATES", '["a {}.", "the {}."]'])
+    assert cfg.TRAINER.ZSCLIP.TEMPLATES == ["a {}.", "the {}."]
+
+
+def test_two_builds_in_a_row_keep_the_template_count(monkeypatch):
+    """The reference's `self.templates += [...]` grows a class attribute on every build_model; here the list comes from the config."""
+    from mvlpt_amd import zsclip
+    from mvlpt_amd.model import default_tokenizer
+    seen = []
+
+    class _Clip:
+        def __init__(self, *a, **k):
+            self.tokenizer, self.context_length = default_tokenizer(), 77
+            self.logit_scale = torch.tensor(1.0)
+            self.engine = SimpleNamespace(text_ensemble=lambda f: f.mean(0))
+
+        def encode_text(self, tokenized):
+            seen.append(tokenized.shape[0])
+            return torch.zeros(tokenized.shape[0], 8)
+
+    monkeypatch.setattr(zsclip, "FrozenCLIP", _Clip)
+    templates = ["a photo of a {}.", "a drawing of a {}.", "{} texture."]
+    cfg = _cfg(templates)
+    tr = object.__new__(zsclip.ZeroshotCLIP2)
+    tr.cfg, tr._sd_arg, tr.device = cfg, {}, torch.device("cpu")
+    tr.dm = SimpleNamespace(dataset=SimpleNamespace(classnames=["dog", "sea_horse"]))
+    tr.build_model()
+    tr.build_model()
+    assert seen == [6, 6] and tr.templates == templates and cfg.TRAINER.ZSCLIP.TEMPLATES == templates
+    assert not hasattr(zsclip.ZeroshotCLIP2, "templates")
+    assert tr.text_features.shape == (2, 8)

@@ -139,7 +139,8 @@ int mvlpt_text_fwd(void* handle, const float* prefix, const float* suffix, const
 /* CoCoOp: PromptLearner.forward + one TextEncoder call per image (trainers/cocoop.py:123-161, 48-59, 184-189) as ONE tower over
  * G * C sequences.  Sequence s = g * C + c is class c's prefix / suffix / layout row / eot with context block g of ctx [G,n_ctx,dt] fp32
  * (ctx + meta_net(image g), one block per image); prefix [C,1,dt], suffix [C,L-1-n_ctx,dt], layout int32 [C,L] and eot int32 [C] are
- * the class tables of mvlpt_text_fwd, read G times (never copied).  feat_out [G*C,embed] fp32, row s = (image g, class c). */
+ * the class tables of mvlpt_text_fwd, read G times (never copied).  feat_out [G*C,embed] fp32, row s = (image g, class c).
+ * Runs as mvlpt_text_fwd_ranged with every range full. */
 int mvlpt_text_fwd_grouped(void* handle, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                            const int32_t* eot, int G, int C, int L, float* feat_out, int save_for_bwd, mvlpt_stream_t stream);
 /* The MVLPT trainer's CoCoOp branch under MULTITASK_LABEL_PERTASK (trainers/mvlpt.py:556-581): image g keeps only the logits of its own
@@ -147,7 +148,7 @@ int mvlpt_text_fwd_grouped(void* handle, const float* prefix, const float* suffi
  * is legal, not all of them); its sequences are those classes in order, the groups follow one another: S = sum_g (hi - lo) sequences,
  * feat_out [S,embed] fp32.  class_lo / class_hi are HOST int32 [G] arrays (the task of an image is known on the host before the step);
  * they are checked and uploaded with the call, which stays enqueue-only.  The class tables are those of mvlpt_text_fwd_grouped, read
- * through the ranges, never copied.  G <= 65535, S * L inside int32.  lo = 0, hi = C for every g computes what text_fwd_grouped does. */
+ * through the ranges, never copied.  G <= 65535, S * L inside int32.  lo = 0, hi = C for every g is text_fwd_grouped. */
 int mvlpt_text_fwd_ranged(void* handle, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                           const int32_t* eot, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L, float* feat_out,
                           int save_for_bwd, mvlpt_stream_t stream);
@@ -157,8 +158,9 @@ int mvlpt_text_fwd_ranged(void* handle, const float* prefix, const float* suffix
  * same fixed order (no atomics); all zeros for an empty range. */
 int mvlpt_text_bwd(void* handle, const float* dfeat, float* dctx, mvlpt_stream_t stream);
 /* *out = bytes of text-tower workspace a text_fwd / text_fwd_grouped / text_fwd_ranged over C_total sequences of length L reserves (the
- * ctx-position table counted for the largest n_ctx, L - 2; a ranged tower adds its range tables and a per-class position table, a few
- * bytes per class and sequence); the workspace only grows, so a caller that chunks G keeps its peak under a budget. */
+ * ctx-position table counted for the largest n_ctx, L - 2; a grouped or ranged tower adds its range tables, and a ranged one a per-class
+ * position table, a few bytes per class and sequence, which the figure covers unless n_ctx is within a few tokens of L - 2); the
+ * workspace only grows, so a caller that chunks G keeps its peak under a budget. */
 int mvlpt_text_workspace_bytes(void* handle, int C_total, int L, int save_for_bwd, int64_t* out);
 
 /* CLIP.encode_text (clip/model.py:343-356: token_embedding(text) + positional_embedding -> transformer -> ln_final ->
@@ -195,7 +197,8 @@ int mvlpt_logits_fwd(void* handle, const float* img_feat, const float* txt_feat,
 int mvlpt_logits_bwd(void* handle, const float* dlogits, float* dimg, float* dtxt, mvlpt_stream_t stream);
 /* CoCoOp's head (trainers/cocoop.py:184-189): logits[g,c] = logit_scale_exp * <img_g/|img_g|, txt_{gC+c}/|txt_{gC+c}|>,
  * img [G,embed], txt [G*C,embed] (rows of mvlpt_text_fwd_grouped), logits [G,C]; fp32 throughout.  The backward gives dtxt [G*C,embed]
- * only (the image tower is frozen and carries no prompts there).  Uses the features of the last logits_grouped_fwd on this handle. */
+ * only (the image tower is frozen and carries no prompts there).  Uses the features of the last logits_grouped_fwd on this handle.
+ * Runs as the ranged head with every range full; each backward still follows only the forward of its own name (MVLPT_ERR_STATE). */
 int mvlpt_logits_grouped_fwd(void* handle, const float* img, const float* txt, float logit_scale_exp, int G, int C, float* logits,
                              mvlpt_stream_t stream);
 int mvlpt_logits_grouped_bwd(void* handle, const float* dlogits, float* dtxt, mvlpt_stream_t stream);
@@ -313,14 +316,10 @@ int mvlpt_op_attention_fwd(int dtype, const void* qkv, void* out, float* lse, in
 int mvlpt_op_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int N, int L, int H, int causal, mvlpt_stream_t stream);
 int mvlpt_op_cast(int dtype, const float* in, void* out, int64_t n, mvlpt_stream_t stream);
-/* the grouped (CoCoOp) glue of mvlpt_text_fwd_grouped / text_bwd: x [G*C, L, d] fp32 = assembled prompts + pos [L, d] (layout entries
- * must address rows inside prefix / suffix / ctx); dctx [G, n_ctx, d] = sum over c of dx [G*C, L, d] at ctx_pos int32 [C, n_ctx] */
-int mvlpt_op_assemble_prompts_grouped(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
-                                      const float* pos, float* x, int G, int C, int L, int d, mvlpt_stream_t stream);
-int mvlpt_op_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, int G, int C, int L, int d, int n_ctx, float* dctx,
-                                     mvlpt_stream_t stream);
-/* the ranged glue of mvlpt_text_fwd_ranged / text_bwd: x [S, L, d] and dx [S, L, d] over the sequences of HOST class_lo / class_hi int32 [G]
- * (see mvlpt_text_fwd_ranged), dctx [G, n_ctx, d], ctx_pos int32 [C, n_ctx].  These two calls wait for their kernel (test entry points). */
+/* the glue of mvlpt_text_fwd_ranged / _grouped / text_bwd: x [S, L, d] fp32 = assembled prompts + pos [L, d] (layout entries must address
+ * rows inside prefix / suffix / ctx) and dx [S, L, d] over the sequences of HOST class_lo / class_hi int32 [G] (see mvlpt_text_fwd_ranged;
+ * lo = 0, hi = C for every g is the grouped tower, S = G * C), dctx [G, n_ctx, d] = sum over group g's sequences of dx at ctx_pos
+ * int32 [C, n_ctx].  These two calls wait for their kernel (test entry points). */
 int mvlpt_op_assemble_prompts_ranged(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                                      const float* pos, float* x, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L,
                                      int d, mvlpt_stream_t stream);

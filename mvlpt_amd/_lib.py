@@ -105,8 +105,6 @@ SIGNATURES = {
     "mvlpt_op_attention_fwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_attention_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_cast": (_i, [_i, _vp, _vp, C.c_int64, _vp]),
-    "mvlpt_op_assemble_prompts_grouped": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "mvlpt_op_gather_ctx_grad_grouped": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mvlpt_op_assemble_prompts_ranged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_gather_ctx_grad_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mvlpt_op_embed_tokens": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),

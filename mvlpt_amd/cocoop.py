@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import distributed as dist_utils
-from .model import FrozenCLIP, PretokenizedPrompts, build_prompt_layout
+from .model import FrozenCLIP, PretokenizedPrompts, _text_inputs, build_prompt_layout
 from .trainer import MVLPT, TrainerX, build_lr_scheduler, build_optimizer, load_pretrained_weights
 from .weights import ARCHS, make_state_dict
 
@@ -97,14 +97,6 @@ class PromptLearner(nn.Module):
         return self.ctx.unsqueeze(0) + bias                  # (batch, n_ctx, ctx_dim)
 
 
-def _text_inputs(model, pl):
-    """token_suffix / layout handed to the text tower; `trim_text_to_eot` as in mvlpt_amd.model._text_inputs."""
-    if not model.trim_text_to_eot:
-        return pl.token_suffix, pl.layout
-    L_eff = pl.max_eot + 1
-    return pl.token_suffix[:, :L_eff - 1 - pl.n_ctx], pl.layout[:, :L_eff]
-
-
 class _CoCoOpLossFn(torch.autograd.Function):
     """Text side + head + cross-entropy of one CoCoOp training step as ONE autograd node.  Each chunk of images runs grouped
     text forward (saved) -> grouped logits -> cross-entropy -> grouped logits backward -> text backward straight away, so only
@@ -113,7 +105,7 @@ class _CoCoOpLossFn(torch.autograd.Function):
     @staticmethod
     def forward(fctx, model: "CustomCLIP", img, ctx_shifted, label):
         eng, pl = model.engine, model.prompt_learner
-        suffix, layout = _text_inputs(model, pl)
+        suffix, layout = _text_inputs(model, pl, pl.n_ctx)
         B = ctx_shifted.shape[0]
         step = model.images_per_chunk(B, layout.shape[1], save_for_bwd=True)
         dctx = torch.empty_like(ctx_shifted)
@@ -180,7 +172,7 @@ class CustomCLIP(nn.Module):
     @torch.no_grad()
     def _eval_logits(self, img, ctx_shifted):
         eng, pl = self.engine, self.prompt_learner
-        suffix, layout = _text_inputs(self, pl)
+        suffix, layout = _text_inputs(self, pl, pl.n_ctx)
         B = ctx_shifted.shape[0]
         step = self.images_per_chunk(B, layout.shape[1], save_for_bwd=False)
         out = torch.empty(B, pl.n_cls, device=img.device, dtype=torch.float32)

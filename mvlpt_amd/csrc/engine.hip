@@ -145,6 +145,12 @@ static const char* kProfNames[PC_COUNT] = {"gemm_bt", "attention_fwd", "attentio
                                            "glue", "head_logits_ce", "attention_fwd_image"};
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes, flops_exec; int M = 0, N = 0, K = 0, epi = -1, split = 0, fold = 0; };
 
+// How the sequences of a text forward are put together: prompts of C classes (mvlpt_text_fwd), prompts of per-group class ranges
+// (mvlpt_text_fwd_ranged; mvlpt_text_fwd_grouped is every range full), token ids (mvlpt_text_encode_tokens)
+enum class TextKind { Plain, Ranged, Ids };
+// The entry that ran the last head forward.  Grouped is computed as Ranged with every range full.
+enum class HeadKind { Plain, Grouped, Ranged };
+
 struct Engine {
   MvlptArch arch{};
   int dt = DT_F16;
@@ -184,9 +190,9 @@ struct Engine {
   void *uc16 = nullptr, *duc16 = nullptr, *dxc16 = nullptr, *dOc16 = nullptr;
   // text fwd extras
   int tC = 0, tL = 0, t_nctx = 0, t_per_class = 0; int32_t* eot_rows = nullptr; int32_t* ctx_pos = nullptr;
-  int t_groups = 0, t_gC = 0;   // grouped forward (mvlpt_text_fwd_grouped): tC = t_groups * t_gC sequences; 0 = not grouped
-  // ranged forward (mvlpt_text_fwd_ranged): t_groups groups over t_gC classes, tC = sum of the range widths; device tables in txt_ws
-  bool t_ranged = false; const int32_t *t_rlo = nullptr, *t_rstart = nullptr;
+  TextKind t_kind = TextKind::Plain;   // the last text forward
+  // TextKind::Ranged (mvlpt_text_fwd_ranged, mvlpt_text_fwd_grouped): t_groups groups, tC = sum of the range widths; device tables in txt_ws
+  int t_groups = 0; const int32_t *t_rlo = nullptr, *t_rstart = nullptr;
   std::vector<int32_t> t_range_host, h_range_host;   // host images of the range tables (source of the asynchronous upload)
   std::vector<int32_t> t_ids_host;   // mvlpt_text_encode_tokens: [ids (S * L, trimmed rows) | eot rows (S)], checked on the host
   // EOT-only last text block (compact [C,·] rows; the text-side twin of the CLS-only last image block)
@@ -195,9 +201,9 @@ struct Engine {
   float* eot32 = nullptr; float* deot32 = nullptr;
   // head state
   int hB = 0, hC = 0; float h_scale = 0.f; const int32_t *h_lo = nullptr, *h_hi = nullptr;
-  bool h_grouped = false;        // the last head forward was mvlpt_logits_grouped_fwd (hB = G groups of hC classes)
-  // ... or mvlpt_logits_ranged_fwd: hB = G groups over hC classes, hS text rows; device tables in head_ws
-  bool h_ranged = false; int hS = 0; const int32_t *h_rlo = nullptr, *h_rstart = nullptr, *h_rgrp = nullptr;
+  HeadKind h_kind = HeadKind::Plain;   // the last head forward; a backward runs only after the forward of its own name
+  // HeadKind::Grouped / Ranged: hB = G groups over hC classes, hS text rows; device tables in head_ws
+  int hS = 0; const int32_t *h_rlo = nullptr, *h_rstart = nullptr, *h_rgrp = nullptr;
   float *imn = nullptr, *txn = nullptr, *inorm = nullptr, *tnorm = nullptr;
   // profiling
   // mvlpt_debug_checksums: one 64-bit fingerprint per intermediate of the image tower (debug; off by default)
@@ -1127,8 +1133,16 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 }
 
 // ------------------------------------------------------------------------------------------------ text tower
-// Bytes of txt_ws a text forward over C sequences of length L reserves (mvlpt_text_fwd, mvlpt_text_fwd_grouped,
-// mvlpt_text_workspace_bytes).  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of the ctx_pos table.
+// Bytes of txt_ws a text forward over C sequences of length L reserves, without the range table of a ranged / grouped forward and the
+// id table of mvlpt_text_encode_tokens (text_fwd_impl adds those).  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of
+// the ctx_pos table.
+// mvlpt_text_workspace_bytes publishes this figure with ctx_rows = C * (L - 2), the largest n_ctx a forward accepts.  A ranged or
+// grouped forward over S sequences in G <= S groups of a class table no longer than S also reserves its range table, 2 G + 1 + 2 S
+// <= 4 S + 1 ints, and uses S * n_ctx of the ctx_pos rows, so the published figure still bounds the reservation whenever
+// S * (L - 2 - n_ctx) >= 4 S + 1 + 128 ints (the 128 cover the two roundings to 256 bytes): n_ctx <= L - 7 from S = 129 sequences on,
+// n_ctx <= L - 8 from S = 65, the trainers' n_ctx = 4 or 16 at L = 77 from S = 3.  It does not when n_ctx is close to L - 2 (or for
+// a ranged forward over fewer sequences than classes); the reservation then exceeds it by at most 16 S + 514 bytes, and txt_ws
+// grows on demand.
 static size_t text_ws_bytes(Engine* E, int C, int L, bool save, bool exact, size_t ctx_rows) {
   const int dtw = E->arch.text_width;
   const size_t X = exact ? 2 : 1;
@@ -1137,13 +1151,14 @@ static size_t text_ws_bytes(Engine* E, int C, int L, bool save, bool exact, size
 }
 static bool text_exact(const Engine* E) { return E->prec_mode == MVLPT_PREC_SPLIT_ALL || E->prec_mode == MVLPT_PREC_SPLIT_GRAD; }
 
-// The text tower over C sequences.  G == 0: mvlpt_text_fwd (prefix / suffix / layout / eot [C, ...], ctx [n_ctx, d] or CSC [C, n_ctx, d]);
-// G > 0: mvlpt_text_fwd_grouped, C = G * Cg sequences s = g * Cg + c from the [Cg, ...] class tables and ctx [G, n_ctx, d].
-// ranged: mvlpt_text_fwd_ranged, G groups over the [Cg, ...] class tables, C = S sequences described by E->t_range_host.
-// ids: mvlpt_text_encode_tokens, C sequences of token ids (E->t_ids_host); no prefix / suffix / ctx / layout / eot tables.
-static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
+// The text tower over C sequences.  Plain: mvlpt_text_fwd (prefix / suffix / layout / eot [C, ...], ctx [n_ctx, d] or CSC [C, n_ctx, d];
+// G = 0, Cg = C).  Ranged: mvlpt_text_fwd_ranged / _grouped, G groups over the [Cg, ...] class tables and ctx [G, n_ctx, d], C = S
+// sequences described by E->t_range_host.  Ids: mvlpt_text_encode_tokens, C sequences of token ids (E->t_ids_host); no prefix /
+// suffix / ctx / layout / eot tables.
+static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
                          const int32_t* layout, const int32_t* eot, int G, int Cg, int C, int L, float* feat_out, int save_for_bwd,
-                         mvlpt_stream_t stream, bool ranged = false, bool ids = false) {
+                         mvlpt_stream_t stream) {
+  const bool ranged = kind == TextKind::Ranged, ids = kind == TextKind::Ids;
   if (int rc = mvlpt_frozen_ready(E)) return rc;
   if ((n_ctx > 0) != (ctx != nullptr) || n_ctx < 0 || n_ctx > L - 2) return fail(E, MVLPT_ERR_ARG, "text_fwd: ctx pointer and n_ctx disagree");
   const MvlptArch& A = E->arch;
@@ -1159,7 +1174,7 @@ static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, co
   // features, which put the inference logits of 5 of the 18 reference fixtures outside 1e-3 (profiles/r04_inference_parity.txt)
   const bool exact = text_exact(E);
   const size_t X = exact ? 2 : 1;
-  // ctx_pos is per class for the grouped / ranged towers; a ranged tower may run fewer sequences than there are classes
+  // ctx_pos is per class for the ranged tower, which may run fewer sequences than there are classes
   const size_t ctx_rows = (size_t)(ranged && Cg > C ? Cg : C) * (n_ctx > 0 ? n_ctx : 1);
   const size_t range_ints = ranged ? E->t_range_host.size() : 0;
   const size_t ids_ints = ids ? E->t_ids_host.size() : 0;
@@ -1182,8 +1197,7 @@ static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, co
   carve_tower(bp, E->txt, E->ts, C, L, save, true, exact, split_kind(E));
   TowerState& st = E->ts;
   E->tC = C; E->tL = L; E->t_nctx = n_ctx; E->t_per_class = ctx_per_class;
-  E->t_groups = G; E->t_gC = G > 0 ? Cg : 0;
-  E->t_ranged = ranged; E->t_rlo = range_dev; E->t_rstart = ranged ? range_dev + G : nullptr;
+  E->t_kind = kind; E->t_groups = G; E->t_rlo = range_dev; E->t_rstart = ranged ? range_dev + G : nullptr;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
   if (ids) {
@@ -1198,10 +1212,6 @@ static int text_fwd_impl(Engine* E, const float* prefix, const float* suffix, co
       HIPCHK(E, hipMemcpyAsync(range_dev, E->t_range_host.data(), range_ints * 4, hipMemcpyHostToDevice, s));
       HIPCHK(E, launch_assemble_prompts_ranged(prefix, suffix, ctx, n_ctx, layout, E->tpos, st.x[0], seq_cls, seq_grp, C, L, dtw, s));
       HIPCHK(E, launch_eot_rows_ranged(eot, E->eot_rows, seq_cls, C, L, s));
-      if (save) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
-    } else if (G > 0) {
-      HIPCHK(E, launch_assemble_prompts_grouped(prefix, suffix, ctx, n_ctx, layout, E->tpos, st.x[0], G, Cg, L, dtw, s));
-      HIPCHK(E, launch_eot_rows_grouped(eot, E->eot_rows, G, Cg, L, s));
       if (save) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
     } else {
       HIPCHK(E, launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, E->tpos, st.x[0], C, L, dtw, s));
@@ -1256,10 +1266,11 @@ int mvlpt_text_fwd(void* h, const float* prefix, const float* suffix, const floa
   Engine* E = (Engine*)h;
   if (!E || !prefix || !suffix || !layout || !eot || !feat_out || C <= 0 || L <= 0)
     return fail(E, MVLPT_ERR_ARG, "text_fwd: null/invalid argument");
-  return text_fwd_impl(E, prefix, suffix, ctx, ctx_per_class, n_ctx, layout, eot, 0, C, C, L, feat_out, save_for_bwd, stream);
+  return text_fwd_impl(E, TextKind::Plain, prefix, suffix, ctx, ctx_per_class, n_ctx, layout, eot, 0, C, C, L, feat_out, save_for_bwd, stream);
 }
 
-// PromptLearner.forward + the per-image TextEncoder calls of CoCoOp (trainers/cocoop.py:123-161, 48-59): one tower over G * C sequences
+// PromptLearner.forward + the per-image TextEncoder calls of CoCoOp (trainers/cocoop.py:123-161, 48-59): one tower over G * C sequences,
+// the ranged tower with every range full
 int mvlpt_text_fwd_grouped(void* h, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                            const int32_t* eot, int G, int C, int L, float* feat_out, int save_for_bwd, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
@@ -1267,7 +1278,9 @@ int mvlpt_text_fwd_grouped(void* h, const float* prefix, const float* suffix, co
     return fail(E, MVLPT_ERR_ARG, "text_fwd_grouped: null/invalid argument");
   if (G > 65535 || (int64_t)G * C > (int64_t)INT32_MAX / (L > 0 ? L : 1))
     return fail(E, MVLPT_ERR_ARG, "text_fwd_grouped: too many sequences");
-  return text_fwd_impl(E, prefix, suffix, ctx, 0, n_ctx, layout, eot, G, C, G * C, L, feat_out, save_for_bwd, stream);
+  const std::vector<int32_t> lo((size_t)G, 0), hi((size_t)G, C);
+  const int64_t S = build_range_table(lo.data(), hi.data(), G, C, E->t_range_host);
+  return text_fwd_impl(E, TextKind::Ranged, prefix, suffix, ctx, 0, n_ctx, layout, eot, G, C, (int)S, L, feat_out, save_for_bwd, stream);
 }
 
 // The MVLPT trainer's CoCoOp branch under the per-task mask (trainers/mvlpt.py:556-581): image g runs only the classes of its own task
@@ -1282,7 +1295,7 @@ int mvlpt_text_fwd_ranged(void* h, const float* prefix, const float* suffix, con
   if (S < 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: a class range is not inside [0, C] or the ranges hold too many sequences");
   if (S == 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: every range is empty");
   if (S > (int64_t)INT32_MAX / L) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: too many sequences");
-  return text_fwd_impl(E, prefix, suffix, ctx, 0, n_ctx, layout, eot, G, C, (int)S, L, feat_out, save_for_bwd, stream, true);
+  return text_fwd_impl(E, TextKind::Ranged, prefix, suffix, ctx, 0, n_ctx, layout, eot, G, C, (int)S, L, feat_out, save_for_bwd, stream);
 }
 
 // CLIP.encode_text (clip/model.py:343-356) over S sequences of token ids, trimmed to their first L positions
@@ -1311,7 +1324,7 @@ int mvlpt_text_encode_tokens(void* h, const int32_t* ids, int ld, int S, int L, 
     }
     rows[q] = q * L + arg;
   }
-  return text_fwd_impl(E, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, S, S, L, feat_out, 0, stream, false, true);
+  return text_fwd_impl(E, TextKind::Ids, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, S, S, L, feat_out, 0, stream);
 }
 
 int mvlpt_text_ensemble(const float* feats, int T, int C, int e, float* out, mvlpt_stream_t stream) {
@@ -1375,10 +1388,8 @@ int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stre
   for (int l = st.layers - 2; l >= 0; --l)
     if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)C * E->t_nctx * dtw * 4.0);
-    if (E->t_ranged)
+    if (E->t_kind == TextKind::Ranged)
       HIPCHK(E, launch_gather_ctx_grad_ranged(st.dx32, E->ctx_pos, E->t_rlo, E->t_rstart, E->t_groups, L, dtw, E->t_nctx, dctx, st.scale_dev, s));
-    else if (E->t_groups > 0)
-      HIPCHK(E, launch_gather_ctx_grad_grouped(st.dx32, E->ctx_pos, E->t_groups, E->t_gC, L, dtw, E->t_nctx, dctx, st.scale_dev, s));
     else
       HIPCHK(E, launch_gather_ctx_grad(st.dx32, E->ctx_pos, C, L, dtw, E->t_nctx, E->t_per_class, dctx, st.scale_dev, s)); }
   return 0;
@@ -1403,20 +1414,20 @@ int mvlpt_logits_fwd(void* h, const float* img, const float* txt, float scale, c
     return fail(E, MVLPT_ERR_ARG, "logits_fwd: null/invalid argument");
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
-  E->hB = 0; E->h_grouped = false; E->h_ranged = false;
+  E->hB = 0;
   if (int rc = head_reserve(E, B, C)) return rc;
   ProfScope ps(E, s, PC_HEAD, 2.0 * B * C * e, 4.0 * ((double)B * e + (double)C * e + (double)B * C));
   HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, B, e, s));
   HIPCHK(E, launch_normalize_rows(txt, E->txn, E->tnorm, C, e, s));
   HIPCHK(E, launch_logits(E->imn, E->txn, scale, lo, hi, logits, B, C, e, s));
-  E->hB = B; E->hC = C; E->h_scale = scale; E->h_lo = lo; E->h_hi = hi;
+  E->hB = B; E->hC = C; E->h_scale = scale; E->h_lo = lo; E->h_hi = hi; E->h_kind = HeadKind::Plain;
   return 0;
 }
 
 int mvlpt_logits_bwd(void* h, const float* dlogits, float* dimg, float* dtxt, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !dlogits) return fail(E, MVLPT_ERR_ARG, "logits_bwd: null argument");
-  if (E->hB <= 0 || !E->imn || E->h_grouped || E->h_ranged) return fail(E, MVLPT_ERR_STATE, "logits_bwd: call logits_fwd first");
+  if (E->hB <= 0 || !E->imn || E->h_kind != HeadKind::Plain) return fail(E, MVLPT_ERR_STATE, "logits_bwd: call logits_fwd first");
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
   ProfScope ps(E, s, PC_HEAD, 4.0 * E->hB * E->hC * e, 4.0 * ((double)E->hB * e + (double)E->hC * e + (double)E->hB * E->hC) * 2);
@@ -1424,46 +1435,10 @@ int mvlpt_logits_bwd(void* h, const float* dlogits, float* dimg, float* dtxt, mv
   return 0;
 }
 
-// CoCoOp's head (trainers/cocoop.py:184-189): image g against its own C text features txt[g*C .. g*C + C)
-int mvlpt_logits_grouped_fwd(void* h, const float* img, const float* txt, float scale, int G, int C, float* logits, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !img || !txt || !logits || G <= 0 || C <= 0 || G > 65535 || (int64_t)G * C > INT32_MAX)
-    return fail(E, MVLPT_ERR_ARG, "logits_grouped_fwd: null/invalid argument");
-  hipStream_t s = (hipStream_t)stream;
+// The ranged head over the table in E->h_range_host (G groups, S text rows): image g against the text rows of its own class range
+static int head_ranged_fwd(Engine* E, HeadKind kind, const float* img, const float* txt, float scale, int G, int C, int S, float* logits,
+                           hipStream_t s) {
   const int e = E->arch.embed_dim;
-  E->hB = 0; E->h_grouped = false; E->h_ranged = false;
-  if (int rc = head_reserve(E, G, G * C)) return rc;
-  ProfScope ps(E, s, PC_HEAD, 2.0 * G * C * e, 4.0 * ((double)G * e + (double)G * C * e + (double)G * C));
-  HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, G, e, s));
-  HIPCHK(E, launch_normalize_rows(txt, E->txn, E->tnorm, G * C, e, s));
-  HIPCHK(E, launch_logits_grouped(E->imn, E->txn, scale, logits, G, C, e, s));
-  E->hB = G; E->hC = C; E->h_scale = scale; E->h_lo = E->h_hi = nullptr; E->h_grouped = true;
-  return 0;
-}
-
-int mvlpt_logits_grouped_bwd(void* h, const float* dlogits, float* dtxt, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !dlogits || !dtxt) return fail(E, MVLPT_ERR_ARG, "logits_grouped_bwd: null argument");
-  if (E->hB <= 0 || !E->imn || !E->h_grouped || E->h_ranged) return fail(E, MVLPT_ERR_STATE, "logits_grouped_bwd: call logits_grouped_fwd first");
-  hipStream_t s = (hipStream_t)stream;
-  const int e = E->arch.embed_dim;
-  ProfScope ps(E, s, PC_HEAD, 4.0 * E->hB * E->hC * e, 4.0 * ((double)E->hB * e + 2.0 * E->hB * E->hC * e + (double)E->hB * E->hC));
-  HIPCHK(E, launch_logits_grouped_bwd(dlogits, E->imn, E->txn, E->tnorm, E->h_scale, dtxt, E->hB, E->hC, e, s));
-  return 0;
-}
-
-// The ranged head (trainers/mvlpt.py:556-581): image g against the text rows of its own class range, 0 outside it
-int mvlpt_logits_ranged_fwd(void* h, const float* img, const float* txt, float scale, const int32_t* class_lo, const int32_t* class_hi,
-                            int G, int C, float* logits, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !img || !txt || !class_lo || !class_hi || !logits || G <= 0 || C <= 0 || G > 65535 || (int64_t)G * C > INT32_MAX)
-    return fail(E, MVLPT_ERR_ARG, "logits_ranged_fwd: null/invalid argument");
-  hipStream_t s = (hipStream_t)stream;
-  const int e = E->arch.embed_dim;
-  E->hB = 0; E->h_grouped = false; E->h_ranged = false;
-  const int64_t S64 = build_range_table(class_lo, class_hi, G, C, E->h_range_host);
-  if (S64 <= 0) return fail(E, MVLPT_ERR_ARG, "logits_ranged_fwd: a class range is not inside [0, C], or every range is empty");
-  const int S = (int)S64;
   const size_t ints = E->h_range_host.size();
   const size_t need = align256((size_t)G * e * 4) + align256((size_t)S * e * 4) + align256((size_t)G * 4) + align256((size_t)S * 4) +
                       align256(ints * 4) + 4096;
@@ -1477,21 +1452,55 @@ int mvlpt_logits_ranged_fwd(void* h, const float* img, const float* txt, float s
   HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, G, e, s));
   HIPCHK(E, launch_normalize_rows(txt, E->txn, E->tnorm, S, e, s));
   HIPCHK(E, launch_logits_ranged(E->imn, E->txn, scale, tab, tab + G, logits, G, C, e, s));
-  E->hB = G; E->hC = C; E->hS = S; E->h_scale = scale; E->h_lo = E->h_hi = nullptr; E->h_ranged = true;
+  E->hB = G; E->hC = C; E->hS = S; E->h_scale = scale; E->h_lo = E->h_hi = nullptr; E->h_kind = kind;
   E->h_rlo = tab; E->h_rstart = tab + G; E->h_rgrp = tab + 2 * G + 1 + S;
   return 0;
 }
-
-int mvlpt_logits_ranged_bwd(void* h, const float* dlogits, float* dtxt, float* dimg, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !dlogits || (!dtxt && !dimg)) return fail(E, MVLPT_ERR_ARG, "logits_ranged_bwd: null argument");
-  if (E->hB <= 0 || !E->imn || !E->h_ranged) return fail(E, MVLPT_ERR_STATE, "logits_ranged_bwd: call logits_ranged_fwd first");
-  hipStream_t s = (hipStream_t)stream;
+// dtxt [S, e] and / or dimg [G, e] of the last head_ranged_fwd (a null output's kernel is not launched)
+static int head_ranged_bwd(Engine* E, const float* dlogits, float* dtxt, float* dimg, hipStream_t s) {
   const int e = E->arch.embed_dim;
   ProfScope ps(E, s, PC_HEAD, 6.0 * E->hS * e, 4.0 * ((double)E->hB * e * 2 + 3.0 * E->hS * e + (double)E->hS));
   HIPCHK(E, launch_logits_ranged_bwd(dlogits, E->imn, E->txn, E->inorm, E->tnorm, E->h_scale, E->h_rlo, E->h_rstart, E->h_rgrp, dimg, dtxt,
                                      E->hB, E->hS, E->hC, e, s));
   return 0;
+}
+
+// CoCoOp's head (trainers/cocoop.py:184-189): image g against its own C text features txt[g*C .. g*C + C), the ranged head with every
+// range full
+int mvlpt_logits_grouped_fwd(void* h, const float* img, const float* txt, float scale, int G, int C, float* logits, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !img || !txt || !logits || G <= 0 || C <= 0 || G > 65535 || (int64_t)G * C > INT32_MAX)
+    return fail(E, MVLPT_ERR_ARG, "logits_grouped_fwd: null/invalid argument");
+  E->hB = 0;
+  const std::vector<int32_t> lo((size_t)G, 0), hi((size_t)G, C);
+  const int64_t S = build_range_table(lo.data(), hi.data(), G, C, E->h_range_host);
+  return head_ranged_fwd(E, HeadKind::Grouped, img, txt, scale, G, C, (int)S, logits, (hipStream_t)stream);
+}
+
+int mvlpt_logits_grouped_bwd(void* h, const float* dlogits, float* dtxt, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !dlogits || !dtxt) return fail(E, MVLPT_ERR_ARG, "logits_grouped_bwd: null argument");
+  if (E->hB <= 0 || !E->imn || E->h_kind != HeadKind::Grouped) return fail(E, MVLPT_ERR_STATE, "logits_grouped_bwd: call logits_grouped_fwd first");
+  return head_ranged_bwd(E, dlogits, dtxt, nullptr, (hipStream_t)stream);      // the image side is frozen and carries no prompts there
+}
+
+// The ranged head (trainers/mvlpt.py:556-581): image g against the text rows of its own class range, 0 outside it
+int mvlpt_logits_ranged_fwd(void* h, const float* img, const float* txt, float scale, const int32_t* class_lo, const int32_t* class_hi,
+                            int G, int C, float* logits, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !img || !txt || !class_lo || !class_hi || !logits || G <= 0 || C <= 0 || G > 65535 || (int64_t)G * C > INT32_MAX)
+    return fail(E, MVLPT_ERR_ARG, "logits_ranged_fwd: null/invalid argument");
+  E->hB = 0;
+  const int64_t S = build_range_table(class_lo, class_hi, G, C, E->h_range_host);
+  if (S <= 0) return fail(E, MVLPT_ERR_ARG, "logits_ranged_fwd: a class range is not inside [0, C], or every range is empty");
+  return head_ranged_fwd(E, HeadKind::Ranged, img, txt, scale, G, C, (int)S, logits, (hipStream_t)stream);
+}
+
+int mvlpt_logits_ranged_bwd(void* h, const float* dlogits, float* dtxt, float* dimg, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !dlogits || (!dtxt && !dimg)) return fail(E, MVLPT_ERR_ARG, "logits_ranged_bwd: null argument");
+  if (E->hB <= 0 || !E->imn || E->h_kind != HeadKind::Ranged) return fail(E, MVLPT_ERR_STATE, "logits_ranged_bwd: call logits_ranged_fwd first");
+  return head_ranged_bwd(E, dlogits, dtxt, dimg, (hipStream_t)stream);
 }
 
 int mvlpt_cross_entropy(void* h, const float* logits, const void* labels, int kind, int B, int C, float* loss, float* dlogits,
@@ -1765,21 +1774,6 @@ int mvlpt_op_cast(int dtype, const float* in, void* out, int64_t n, mvlpt_stream
   OPCHK(launch_cast_f32_to16(dtype, in, out, (size_t)n, nullptr, (hipStream_t)stream));
   return 0;
 }
-int mvlpt_op_assemble_prompts_grouped(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
-                                      const float* pos, float* x, int G, int C, int L, int d, mvlpt_stream_t stream) {
-  if (!prefix || !suffix || !ctx || !layout || !pos || !x || G <= 0 || C <= 0 || L <= n_ctx + 1 || n_ctx <= 0 || d <= 0) {
-    g_create_err = "op_assemble_prompts_grouped: null/invalid argument"; return MVLPT_ERR_ARG; }
-  OPCHK(launch_assemble_prompts_grouped(prefix, suffix, ctx, n_ctx, layout, pos, x, G, C, L, d, (hipStream_t)stream));
-  return 0;
-}
-int mvlpt_op_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, int G, int C, int L, int d, int n_ctx, float* dctx,
-                                     mvlpt_stream_t stream) {
-  if (!dx || !ctx_pos || !dctx || G <= 0 || C <= 0 || L <= 0 || n_ctx <= 0 || d <= 0) {
-    g_create_err = "op_gather_ctx_grad_grouped: null/invalid argument"; return MVLPT_ERR_ARG; }
-  OPCHK(launch_gather_ctx_grad_grouped(dx, ctx_pos, G, C, L, d, n_ctx, dctx, nullptr, (hipStream_t)stream));
-  return 0;
-}
-
 // The ranged glue without a tower (tests).  The range table is built and checked on the host, uploaded into a temporary buffer, and the
 // call waits for its kernel before the buffer is freed.
 static int op_range_table(const int32_t* class_lo, const int32_t* class_hi, int G, int C, std::vector<int32_t>& t, int32_t** dev, int* S) {

@@ -485,25 +485,39 @@ hipError_t launch_reduce_prompt_rows(int dtype, float* dx32, void* dx16, int B, 
 }
 
 // ------------------------------------------------------------------------------------------------ text side
+// The token write loop of every text tower: x[seq,t,:] = src_row(seq, t)[:] + pos[t,:] over S sequences of L tokens, one f32x4 per
+// thread and step.  The kernels differ only in where a token's source row comes from.
+template <typename SrcRow>
+__device__ __forceinline__ void write_tokens(const float* pos, float* x, size_t S, int L, int d, SrcRow src_row) {
+  const int d4 = d / 4;
+  const size_t total = S * L * d4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int c4 = (int)(i % d4);
+    const size_t tok = i / d4;
+    const int pos_i = (int)(tok % L);
+    const size_t seq = tok / L;
+    const float* src = src_row(seq, pos_i);
+    *(f32x4*)(x + tok * d + c4 * 4) = *(const f32x4*)(src + c4 * 4) + *(const f32x4*)(pos + (size_t)pos_i * d + c4 * 4);
+  }
+}
+// layout entry e of class cls: 0 = its prefix row, e > 0 = row e - 1 of its suffix, e < 0 = row -e - 1 of the context block ctx_blk
+__device__ __forceinline__ const float* prompt_row(const float* prefix, const float* suffix, const float* ctx_blk, int suf_len, int e,
+                                                   int cls, int d) {
+  if (e == 0) return prefix + (size_t)cls * d;
+  if (e > 0) return suffix + ((size_t)cls * suf_len + (e - 1)) * d;
+  return ctx_blk + (size_t)(-e - 1) * d;
+}
+
 // x[c,i,:] = (layout[c,i] >= 0 ? fixed tokens : ctx row) + pos[i]      (trainers/mvlpt.py:439-515 + :107/:112)
 __global__ void assemble_prompts_kernel(const float* __restrict__ prefix, const float* __restrict__ suffix,
                                         const float* __restrict__ ctx, int ctx_per_class, int n_ctx,
                                         const int32_t* __restrict__ layout, const float* __restrict__ pos,
                                         float* __restrict__ x, int C, int L, int d) {
-  const int d4 = d / 4;
-  const size_t total = (size_t)C * L * d4;
   const int suf_len = L - 1 - n_ctx;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int c4 = (int)(i % d4);
-    const size_t tok = i / d4;
-    const int pos_i = (int)(tok % L), cls = (int)(tok / L);
-    const int e = layout[tok];
-    const float* src;
-    if (e == 0) src = prefix + (size_t)cls * d;
-    else if (e > 0) src = suffix + ((size_t)cls * suf_len + (e - 1)) * d;
-    else src = ctx + ((size_t)(ctx_per_class ? cls * n_ctx : 0) + (-e - 1)) * d;
-    *(f32x4*)(x + tok * d + c4 * 4) = *(const f32x4*)(src + c4 * 4) + *(const f32x4*)(pos + (size_t)pos_i * d + c4 * 4);
-  }
+  write_tokens(pos, x, (size_t)C, L, d, [&](size_t seq, int pos_i) {
+    const int cls = (int)seq;
+    return prompt_row(prefix, suffix, ctx + (size_t)(ctx_per_class ? cls * n_ctx : 0) * d, suf_len, layout[seq * L + pos_i], cls, d);
+  });
 }
 hipError_t launch_assemble_prompts(const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
                                    const int32_t* layout, const float* pos, float* x, int C, int L, int d, hipStream_t s) {
@@ -560,16 +574,7 @@ hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipS
 // ids [S, ld] with ld >= L, only columns 0 .. L-1 are read; every id read must be inside the table (the callers check on the host)
 __global__ void embed_tokens_kernel(const float* __restrict__ emb, const float* __restrict__ pos, const int32_t* __restrict__ ids,
                                     int ld, float* __restrict__ x, int S, int L, int d) {
-  const int d4 = d / 4;
-  const size_t total = (size_t)S * L * d4;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int c4 = (int)(i % d4);
-    const size_t tok = i / d4;
-    const int pos_i = (int)(tok % L);
-    const size_t seq = tok / L;
-    const float* src = emb + (size_t)ids[seq * ld + pos_i] * d;
-    *(f32x4*)(x + tok * d + c4 * 4) = *(const f32x4*)(src + c4 * 4) + *(const f32x4*)(pos + (size_t)pos_i * d + c4 * 4);
-  }
+  write_tokens(pos, x, (size_t)S, L, d, [&](size_t seq, int pos_i) { return emb + (size_t)ids[seq * ld + pos_i] * d; });
 }
 hipError_t launch_embed_tokens(const float* emb, const float* pos, const int32_t* ids, int ld, float* x, int S, int L, int d,
                                hipStream_t s) {
@@ -577,47 +582,6 @@ hipError_t launch_embed_tokens(const float* emb, const float* pos, const int32_t
   const size_t total = (size_t)S * L * (d / 4);
   const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipLaunchKernelGGL(embed_tokens_kernel, dim3(grid), dim3(256), 0, s, emb, pos, ids, ld, x, S, L, d);
-  return hipGetLastError();
-}
-
-// ---- grouped (image-conditioned) prompts: sequence s = g * C + c pairs class c with context block g (trainers/cocoop.py:123-161)
-// x[s,i,:] = (layout[c,i] >= 0 ? fixed tokens of class c : ctx[g, row]) + pos[i]; prefix / suffix / layout stay [C, ...]
-__global__ void assemble_prompts_grouped_kernel(const float* __restrict__ prefix, const float* __restrict__ suffix,
-                                                const float* __restrict__ ctx, int n_ctx, const int32_t* __restrict__ layout,
-                                                const float* __restrict__ pos, float* __restrict__ x, int G, int C, int L, int d) {
-  const int d4 = d / 4;
-  const size_t total = (size_t)G * C * L * d4;
-  const int suf_len = L - 1 - n_ctx;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int c4 = (int)(i % d4);
-    const size_t tok = i / d4;
-    const int pos_i = (int)(tok % L);
-    const size_t seq = tok / L;
-    const int cls = (int)(seq % C), g = (int)(seq / C);
-    const int e = layout[(size_t)cls * L + pos_i];
-    const float* src;
-    if (e == 0) src = prefix + (size_t)cls * d;
-    else if (e > 0) src = suffix + ((size_t)cls * suf_len + (e - 1)) * d;
-    else src = ctx + ((size_t)g * n_ctx + (-e - 1)) * d;
-    *(f32x4*)(x + tok * d + c4 * 4) = *(const f32x4*)(src + c4 * 4) + *(const f32x4*)(pos + (size_t)pos_i * d + c4 * 4);
-  }
-}
-hipError_t launch_assemble_prompts_grouped(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
-                                           const float* pos, float* x, int G, int C, int L, int d, hipStream_t s) {
-  if (d % 4 || n_ctx <= 0) return hipErrorInvalidValue;
-  const size_t total = (size_t)G * C * L * (d / 4);
-  const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  hipLaunchKernelGGL(assemble_prompts_grouped_kernel, dim3(grid), dim3(256), 0, s, prefix, suffix, ctx, n_ctx, layout, pos, x, G, C, L, d);
-  return hipGetLastError();
-}
-// rows[s] = s * L + eot[s % C] for the G * C sequences
-__global__ void eot_rows_grouped_kernel(const int32_t* __restrict__ eot, int32_t* __restrict__ rows, int N, int C, int L) {
-  const int s = blockIdx.x * blockDim.x + threadIdx.x;
-  if (s < N) rows[s] = s * L + eot[s % C];
-}
-hipError_t launch_eot_rows_grouped(const int32_t* eot, int32_t* rows, int G, int C, int L, hipStream_t s) {
-  const int N = G * C;
-  hipLaunchKernelGGL(eot_rows_grouped_kernel, dim3((N + 255) / 256), dim3(256), 0, s, eot, rows, N, C, L);
   return hipGetLastError();
 }
 
@@ -631,21 +595,20 @@ __global__ void gather_ctx_grad_csc_kernel(const float* __restrict__ dx, const i
   const float inv = scale_dev ? scale_dev[1] : 1.0f;
   dctx[((size_t)cls * n_ctx + j) * d + c0] = inv * dx[((size_t)cls * L + ctx_pos[cls * n_ctx + j]) * d + c0];
 }
-// generic context: 16 waves per block, wave w sums classes w, w+16, ... (independent loads), lane = float4 column;
-// partials are added in a fixed order through LDS (deterministic)
-__global__ __launch_bounds__(1024) void gather_ctx_grad_kernel(const float* __restrict__ dx, const int32_t* __restrict__ ctx_pos,
-                                                               int C, int L, int d, int n_ctx, float* __restrict__ dctx,
-                                                               const float* scale_dev) {
-  __shared__ f32x4 part[16][64];
-  const int j = blockIdx.y;
+// The context-gradient reduction: dctx[row,:] = inv * sum_k dxg[k, cp[k * n_ctx + j], :] over n sequences of L tokens.  16 waves per
+// block, wave w sums k = w, w+16, ... (independent loads), lane = float4 column; the partials are added in a fixed order through LDS
+// (deterministic, and the same bits whichever kernel calls it).  cp / j and dctx / row stay apart (no pointer is advanced by the
+// caller): with these index expressions gather_ctx_grad_kernel compiles to the registers it had before the body was shared.
+__device__ __forceinline__ void gather_ctx_row(f32x4 (&part)[16][64], const float* dxg, const int32_t* cp, int j, int n, int L, int d,
+                                               int n_ctx, float* dctx, size_t row, const float* scale_dev) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = (blockIdx.x * 64 + lane) * 4;
   const bool ok = c < d;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   if (ok) {
 #pragma unroll 8
-    for (int cls = wave; cls < C; cls += 16)
-      acc += *(const f32x4*)(dx + ((size_t)cls * L + ctx_pos[cls * n_ctx + j]) * d + c);
+    for (int k = wave; k < n; k += 16)
+      acc += *(const f32x4*)(dxg + ((size_t)k * L + cp[k * n_ctx + j]) * d + c);
   }
   part[wave][lane] = acc;
   __syncthreads();
@@ -654,8 +617,16 @@ __global__ __launch_bounds__(1024) void gather_ctx_grad_kernel(const float* __re
 #pragma unroll
     for (int w = 1; w < 16; ++w) t += part[w][lane];
     const float inv = scale_dev ? scale_dev[1] : 1.0f;
-    *(f32x4*)(dctx + (size_t)j * d + c) = t * inv;
+    *(f32x4*)(dctx + row * d + c) = t * inv;
   }
+}
+// generic context: row j of dctx from all C classes
+__global__ __launch_bounds__(1024) void gather_ctx_grad_kernel(const float* __restrict__ dx, const int32_t* __restrict__ ctx_pos,
+                                                               int C, int L, int d, int n_ctx, float* __restrict__ dctx,
+                                                               const float* scale_dev) {
+  __shared__ f32x4 part[16][64];
+  const int j = blockIdx.y;
+  gather_ctx_row(part, dx, ctx_pos, j, C, L, d, n_ctx, dctx, (size_t)j, scale_dev);
 }
 hipError_t launch_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C, int L, int d, int n_ctx, int per_class,
                                   float* dctx, const float* scale_dev, hipStream_t s) {
@@ -667,65 +638,20 @@ hipError_t launch_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C
     hipLaunchKernelGGL(gather_ctx_grad_kernel, dim3((d + 255) / 256, n_ctx), dim3(1024), 0, s, dx, ctx_pos, C, L, d, n_ctx, dctx, scale_dev);
   return hipGetLastError();
 }
-// grouped context (one block per image, expanded over the classes: trainers/cocoop.py:150-157):
-// dctx[g,j,:] = inv * sum_c dx[(g*C + c)*L + pos(c,j), :] — gather_ctx_grad_kernel with the group as blockIdx.z (same fixed order)
-__global__ __launch_bounds__(1024) void gather_ctx_grad_grouped_kernel(const float* __restrict__ dx, const int32_t* __restrict__ ctx_pos,
-                                                                       int C, int L, int d, int n_ctx, float* __restrict__ dctx,
-                                                                       const float* scale_dev) {
-  __shared__ f32x4 part[16][64];
-  const int j = blockIdx.y, g = blockIdx.z;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = (blockIdx.x * 64 + lane) * 4;
-  const bool ok = c < d;
-  const float* dxg = dx + (size_t)g * C * L * d;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (ok) {
-#pragma unroll 8
-    for (int cls = wave; cls < C; cls += 16)
-      acc += *(const f32x4*)(dxg + ((size_t)cls * L + ctx_pos[cls * n_ctx + j]) * d + c);
-  }
-  part[wave][lane] = acc;
-  __syncthreads();
-  if (wave == 0 && ok) {
-    f32x4 t = part[0][lane];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) t += part[w][lane];
-    const float inv = scale_dev ? scale_dev[1] : 1.0f;
-    *(f32x4*)(dctx + ((size_t)g * n_ctx + j) * d + c) = t * inv;
-  }
-}
-hipError_t launch_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, int G, int C, int L, int d, int n_ctx, float* dctx,
-                                          const float* scale_dev, hipStream_t s) {
-  if (n_ctx <= 0) return hipSuccess;
-  if (d % 4 || G <= 0 || G > 65535) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gather_ctx_grad_grouped_kernel, dim3((d + 255) / 256, n_ctx, G), dim3(1024), 0, s, dx, ctx_pos, C, L, d, n_ctx, dctx,
-                     scale_dev);
-  return hipGetLastError();
-}
 
-// ---- ranged (image-conditioned, per-task) prompts: group g runs only the classes of its own range (trainers/mvlpt.py:556-581: a logit
-// outside the image's task is multiplied by 0, so its sequence is never needed).  Sequence s belongs to group seq_grp[s] and class
-// seq_cls[s]; the class tables stay [C, ...] and are read through seq_cls.
+// ---- ranged (image-conditioned) prompts: one context block per image (trainers/cocoop.py:123-161), and group g runs only the classes
+// of its own range (trainers/mvlpt.py:556-581: a logit outside the image's task is multiplied by 0, so its sequence is never needed).
+// Sequence s belongs to group seq_grp[s] and class seq_cls[s]; the class tables stay [C, ...] and are read through seq_cls.  CoCoOp's
+// grouped tower is the case of every range full: s = g * C + c.
 __global__ void assemble_prompts_ranged_kernel(const float* __restrict__ prefix, const float* __restrict__ suffix,
                                                const float* __restrict__ ctx, int n_ctx, const int32_t* __restrict__ layout,
                                                const float* __restrict__ pos, float* __restrict__ x,
                                                const int32_t* __restrict__ seq_cls, const int32_t* __restrict__ seq_grp, int S, int L, int d) {
-  const int d4 = d / 4;
-  const size_t total = (size_t)S * L * d4;
   const int suf_len = L - 1 - n_ctx;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    const int c4 = (int)(i % d4);
-    const size_t tok = i / d4;
-    const int pos_i = (int)(tok % L);
-    const size_t seq = tok / L;
+  write_tokens(pos, x, (size_t)S, L, d, [&](size_t seq, int pos_i) {
     const int cls = seq_cls[seq], g = seq_grp[seq];
-    const int e = layout[(size_t)cls * L + pos_i];
-    const float* src;
-    if (e == 0) src = prefix + (size_t)cls * d;
-    else if (e > 0) src = suffix + ((size_t)cls * suf_len + (e - 1)) * d;
-    else src = ctx + ((size_t)g * n_ctx + (-e - 1)) * d;
-    *(f32x4*)(x + tok * d + c4 * 4) = *(const f32x4*)(src + c4 * 4) + *(const f32x4*)(pos + (size_t)pos_i * d + c4 * 4);
-  }
+    return prompt_row(prefix, suffix, ctx + (size_t)g * n_ctx * d, suf_len, layout[(size_t)cls * L + pos_i], cls, d);
+  });
 }
 hipError_t launch_assemble_prompts_ranged(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                                           const float* pos, float* x, const int32_t* seq_cls, const int32_t* seq_grp, int S, int L, int d,
@@ -747,35 +673,16 @@ hipError_t launch_eot_rows_ranged(const int32_t* eot, int32_t* rows, const int32
   hipLaunchKernelGGL(eot_rows_ranged_kernel, dim3((S + 255) / 256), dim3(256), 0, s, eot, rows, seq_cls, S, L);
   return hipGetLastError();
 }
-// dctx[g,j,:] = inv * sum_k dx[(start[g] + k)*L + pos(lo[g] + k, j), :], k over the group's own range: gather_ctx_grad_grouped_kernel with
-// a per-group width (2 or 211 classes alike: wave w takes k = w, w+16, ...; the same fixed order, so a full range gives the grouped bits)
+// dctx[g,j,:] = inv * sum_k dx[(start[g] + k)*L + pos(lo[g] + k, j), :], k over the group's own range (2 or 211 classes alike);
+// ctx_pos is per class, [C, n_ctx]
 __global__ __launch_bounds__(1024) void gather_ctx_grad_ranged_kernel(const float* __restrict__ dx, const int32_t* __restrict__ ctx_pos,
                                                                       const int32_t* __restrict__ lo, const int32_t* __restrict__ start,
                                                                       int L, int d, int n_ctx, float* __restrict__ dctx,
                                                                       const float* scale_dev) {
   __shared__ f32x4 part[16][64];
   const int j = blockIdx.y, g = blockIdx.z;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = (blockIdx.x * 64 + lane) * 4;
-  const bool ok = c < d;
   const int s0 = start[g], n = start[g + 1] - s0;
-  const float* dxg = dx + (size_t)s0 * L * d;
-  const int32_t* cp = ctx_pos + (size_t)lo[g] * n_ctx + j;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (ok) {
-#pragma unroll 8
-    for (int k = wave; k < n; k += 16)
-      acc += *(const f32x4*)(dxg + ((size_t)k * L + cp[(size_t)k * n_ctx]) * d + c);
-  }
-  part[wave][lane] = acc;
-  __syncthreads();
-  if (wave == 0 && ok) {
-    f32x4 t = part[0][lane];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) t += part[w][lane];
-    const float inv = scale_dev ? scale_dev[1] : 1.0f;
-    *(f32x4*)(dctx + ((size_t)g * n_ctx + j) * d + c) = t * inv;
-  }
+  gather_ctx_row(part, dx + (size_t)s0 * L * d, ctx_pos + (size_t)lo[g] * n_ctx, j, n, L, d, n_ctx, dctx, (size_t)g * n_ctx + j, scale_dev);
 }
 hipError_t launch_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos, const int32_t* lo, const int32_t* start, int G, int L,
                                          int d, int n_ctx, float* dctx, const float* scale_dev, hipStream_t s) {
@@ -1120,31 +1027,25 @@ hipError_t launch_cross_entropy(const float* logits, const void* labels, int lab
   return hipGetLastError();
 }
 
-// d imn = scale * (dlogits*mask) txn ; d txn = scale * (dlogits*mask)^T imn ; then through x/||x||.
-// One workgroup per output row (image b / class c); its 8 waves split the reduction axis (classes / images: 32 dependent row loads
-// per wave at B = 256 instead of 64 with four waves — the kernel is a latency chain, 36 -> ~20 us stand-alone), every
+// The accumulation and tail of a normalisation backward: dout[row,:] = (g - self <g, self>) / norm[row], g[:] = sum_r w_r * o_r[:] over
+// r = 0 .. nred-1, where term(r) gives the weight and the row of r, or keep = false for a term that is left out.  The workgroup's
+// 8 waves split r (32 dependent row loads per wave at 256 terms instead of 64 with four waves: the kernel is a latency chain), every
 // lane owns 8 consecutive feature columns (e <= 1024 = 2 x 64 lanes x 8), partial rows are combined through LDS in wave order.
-template <bool IMG>
-__global__ __launch_bounds__(512) void logits_bwd_kernel(const float* __restrict__ dl, const float* __restrict__ imn,
-                                                         const float* __restrict__ txn, const float* __restrict__ norm,
-                                                         float scale, const int32_t* __restrict__ lo,
-                                                         const int32_t* __restrict__ hi, float* __restrict__ dout,
-                                                         int B, int C, int e) {
-  __shared__ float part[8][1024];
-  __shared__ float red[8];
+// The term comes back by value and norm / dout are indexed by row here: with out-parameters or advanced pointers logits_bwd_kernel
+// needs 6 more VGPRs than before the body was shared.
+struct NormBwdTerm { bool keep; float w; const float* o; };
+template <typename Term>
+__device__ __forceinline__ void norm_bwd_row(float (&part)[8][1024], float (&red)[8], int nred, Term term, const float* self, const float* norm,
+                                             float* dout, int row, int e) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int row = blockIdx.x;                       // b (IMG) or c
-  const float* other = IMG ? txn : imn;             // rows of the other side, indexed by the reduction index
-  const float* self = (IMG ? imn : txn) + (size_t)row * e;
-  const int nred = IMG ? C : B;
   f32x4 acc[2][2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) { acc[k][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[k][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
   for (int r = wave; r < nred; r += 8) {
-    const int b = IMG ? row : r, c = IMG ? r : row;
-    if (lo && !(c >= lo[b] && c < hi[b])) continue;     // multiplicative 0/1 task mask
-    const float w = scale * dl[(size_t)b * C + c];
-    const float* o = other + (size_t)r * e;
+    const NormBwdTerm t = term(r);
+    if (!t.keep) continue;
+    const float w = t.w;
+    const float* o = t.o;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int i = (k * 64 + lane) * 8;
@@ -1181,6 +1082,26 @@ __global__ __launch_bounds__(512) void logits_bwd_kernel(const float* __restrict
     if (i < e) dout[(size_t)row * e + i] = (g[k] - self[i] * dot) * inv;
   }
 }
+
+// d imn = scale * (dlogits*mask) txn ; d txn = scale * (dlogits*mask)^T imn ; then through x/||x||.
+// One workgroup per output row (image b / class c), reducing over the classes / images.
+template <bool IMG>
+__global__ __launch_bounds__(512) void logits_bwd_kernel(const float* __restrict__ dl, const float* __restrict__ imn,
+                                                         const float* __restrict__ txn, const float* __restrict__ norm,
+                                                         float scale, const int32_t* __restrict__ lo,
+                                                         const int32_t* __restrict__ hi, float* __restrict__ dout,
+                                                         int B, int C, int e) {
+  __shared__ float part[8][1024];
+  __shared__ float red[8];
+  const int row = blockIdx.x;                       // b (IMG) or c
+  const float* other = IMG ? txn : imn;             // rows of the other side, indexed by the reduction index
+  const float* self = (IMG ? imn : txn) + (size_t)row * e;
+  norm_bwd_row(part, red, IMG ? C : B, [&](int r) {
+    const int b = IMG ? row : r, c = IMG ? r : row;
+    if (lo && !(c >= lo[b] && c < hi[b])) return NormBwdTerm{false, 0.f, nullptr};     // multiplicative 0/1 task mask
+    return NormBwdTerm{true, scale * dl[(size_t)b * C + c], other + (size_t)r * e};
+  }, self, norm, dout, row, e);
+}
 hipError_t launch_logits_bwd(const float* dlogits, const float* imn, const float* txn, const float* inorm, const float* tnorm,
                              float scale, const int32_t* lo, const int32_t* hi, float* dimg, float* dtxt, int B, int C, int e,
                              hipStream_t s) {
@@ -1190,56 +1111,9 @@ hipError_t launch_logits_bwd(const float* dlogits, const float* imn, const float
   return hipGetLastError();
 }
 
-// grouped head (every image has its own C text features, trainers/cocoop.py:184-189):
-// logits[g,c] = (scale * imn[g,:]) . txn[g*C + c, :]
-__global__ __launch_bounds__(256) void logits_grouped_kernel(const float* __restrict__ imn, const float* __restrict__ txn, float scale,
-                                                             float* __restrict__ logits, int G, int C, int e) {
-  extern __shared__ float simg[];
-  const int g = blockIdx.x;
-  for (int i = threadIdx.x; i < e; i += 256) simg[i] = scale * imn[(size_t)g * e + i];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int c = blockIdx.y * 4 + wave; c < C; c += gridDim.y * 4) {
-    const float* t = txn + ((size_t)g * C + c) * e;
-    float s = 0.f;
-    for (int i = lane; i < e; i += 64) s += simg[i] * t[i];
-    s = wave_sum(s);
-    if (lane == 0) logits[(size_t)g * C + c] = s;
-  }
-}
-hipError_t launch_logits_grouped(const float* imn, const float* txn, float scale, float* logits, int G, int C, int e, hipStream_t s) {
-  if (G <= 0 || G > 65535) return hipErrorInvalidValue;
-  int gy = (C + 3) / 4; gy = gy > 64 ? 64 : gy;
-  hipLaunchKernelGGL(logits_grouped_kernel, dim3(G, gy), dim3(256), e * sizeof(float), s, imn, txn, scale, logits, G, C, e);
-  return hipGetLastError();
-}
-// d txn[s] for s = g*C + c: the only logit that reads text row s is logits[g,c], so with w = scale * dlogits[g,c]
-// d txt[s] = w * (imn[g] - txn[s] <imn[g], txn[s]>) / ||txt[s]||   (normalisation backward).  One wave per text row.
-__global__ __launch_bounds__(256) void logits_grouped_bwd_kernel(const float* __restrict__ dl, const float* __restrict__ imn,
-                                                                 const float* __restrict__ txn, const float* __restrict__ tnorm,
-                                                                 float scale, float* __restrict__ dtxt, int N, int C, int e) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= N) return;
-  const int g = row / C;
-  const float* im = imn + (size_t)g * e;
-  const float* t = txn + (size_t)row * e;
-  float dot = 0.f;
-  for (int i = lane; i < e; i += 64) dot += im[i] * t[i];
-  dot = wave_sum(dot);
-  const float w = scale * dl[row];                  // dlogits [G, C] is row-major: entry (g, c) sits at g*C + c = row
-  const float inv = 1.0f / tnorm[row];
-  for (int i = lane; i < e; i += 64) dtxt[(size_t)row * e + i] = w * (im[i] - t[i] * dot) * inv;
-}
-hipError_t launch_logits_grouped_bwd(const float* dlogits, const float* imn, const float* txn, const float* tnorm, float scale, float* dtxt,
-                                     int G, int C, int e, hipStream_t s) {
-  const int N = G * C;
-  hipLaunchKernelGGL(logits_grouped_bwd_kernel, dim3((N + 3) / 4), dim3(256), 0, s, dlogits, imn, txn, tnorm, scale, dtxt, N, C, e);
-  return hipGetLastError();
-}
-
-// ranged head (trainers/mvlpt.py:556-581): image g has text rows start[g] .. start[g+1] - 1 for classes lo[g] ..; every logit outside
-// that range is 0.0f exactly (logits * select_index).  logits_grouped_kernel with the row looked up through the range.
+// ranged head: image g has text rows start[g] .. start[g+1] - 1 for classes lo[g] ..; every logit outside that range is 0.0f exactly
+// (logits * select_index, trainers/mvlpt.py:556-581).  CoCoOp's grouped head (every image against its own C text features,
+// trainers/cocoop.py:184-189) is the case of every range full: logits[g,c] = (scale * imn[g,:]) . txn[g*C + c, :]
 __global__ __launch_bounds__(256) void logits_ranged_kernel(const float* __restrict__ imn, const float* __restrict__ txn, float scale,
                                                             const int32_t* __restrict__ lo, const int32_t* __restrict__ start,
                                                             float* __restrict__ logits, int G, int C, int e) {
@@ -1267,7 +1141,8 @@ hipError_t launch_logits_ranged(const float* imn, const float* txn, float scale,
   hipLaunchKernelGGL(logits_ranged_kernel, dim3(G, gy), dim3(256), e * sizeof(float), s, imn, txn, scale, lo, start, logits, G, C, e);
   return hipGetLastError();
 }
-// d txt[s]: logits_grouped_bwd_kernel with (g, c) = (seq_grp[s], lo[g] + s - start[g]).  One wave per text row.
+// d txt[s] for (g, c) = (seq_grp[s], lo[g] + s - start[g]): the only logit that reads text row s is logits[g,c], so with
+// w = scale * dlogits[g,c],  d txt[s] = w * (imn[g] - txn[s] <imn[g], txn[s]>) / ||txt[s]||  (normalisation backward).  One wave per text row.
 __global__ __launch_bounds__(256) void logits_ranged_bwd_txt_kernel(const float* __restrict__ dl, const float* __restrict__ imn,
                                                                     const float* __restrict__ txn, const float* __restrict__ tnorm,
                                                                     float scale, const int32_t* __restrict__ lo,
@@ -1288,8 +1163,7 @@ __global__ __launch_bounds__(256) void logits_ranged_bwd_txt_kernel(const float*
   for (int i = lane; i < e; i += 64) dtxt[(size_t)row * e + i] = w * (im[i] - t[i] * dot) * inv;
 }
 // d img[g] = normalisation backward of  scale * sum_k dlogits[g, lo[g] + k] * txn[start[g] + k]: logits_bwd_kernel<true> with the
-// reduction over the group's own rows (8 waves split the range, 8 columns per lane, partials combined through LDS in wave order);
-// an empty range gives zeros
+// reduction over the group's own rows; an empty range gives zeros
 __global__ __launch_bounds__(512) void logits_ranged_bwd_img_kernel(const float* __restrict__ dl, const float* __restrict__ imn,
                                                                     const float* __restrict__ txn, const float* __restrict__ inorm,
                                                                     float scale, const int32_t* __restrict__ lo,
@@ -1297,56 +1171,16 @@ __global__ __launch_bounds__(512) void logits_ranged_bwd_img_kernel(const float*
                                                                     int C, int e) {
   __shared__ float part[8][1024];
   __shared__ float red[8];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = blockIdx.x;
   const int l0 = lo[g], s0 = start[g], n = start[g + 1] - s0;
-  const float* self = imn + (size_t)g * e;
-  f32x4 acc[2][2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) { acc[k][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[k][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-  for (int r = wave; r < n; r += 8) {
-    const float w = scale * dl[(size_t)g * C + l0 + r];
-    const float* o = txn + (size_t)(s0 + r) * e;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int i = (k * 64 + lane) * 8;
-      if (i < e) {
-        acc[k][0] += w * *(const f32x4*)(o + i);
-        acc[k][1] += w * *(const f32x4*)(o + i + 4);
-      }
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int i = (k * 64 + lane) * 8;
-    if (i < e) { *(f32x4*)&part[wave][i] = acc[k][0]; *(f32x4*)&part[wave][i + 4] = acc[k][1]; }
-  }
-  __syncthreads();
-  float gr[2], dot = 0.f;
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int i = threadIdx.x + k * 512;
-    gr[k] = 0.f;
-    if (i < e) {
-      gr[k] = ((part[0][i] + part[1][i]) + (part[2][i] + part[3][i])) + ((part[4][i] + part[5][i]) + (part[6][i] + part[7][i]));
-      dot += gr[k] * self[i];
-    }
-  }
-  dot = wave_sum(dot);
-  if (lane == 0) red[wave] = dot;
-  __syncthreads();
-  dot = ((red[0] + red[1]) + (red[2] + red[3])) + ((red[4] + red[5]) + (red[6] + red[7]));
-  const float inv = 1.0f / inorm[g];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {
-    const int i = threadIdx.x + k * 512;
-    if (i < e) dimg[(size_t)g * e + i] = (gr[k] - self[i] * dot) * inv;
-  }
+  norm_bwd_row(part, red, n, [&](int r) {
+    return NormBwdTerm{true, scale * dl[(size_t)g * C + l0 + r], txn + (size_t)(s0 + r) * e};
+  }, imn + (size_t)g * e, inorm, dimg, g, e);
 }
 hipError_t launch_logits_ranged_bwd(const float* dlogits, const float* imn, const float* txn, const float* inorm, const float* tnorm,
                                     float scale, const int32_t* lo, const int32_t* start, const int32_t* seq_grp, float* dimg, float* dtxt,
                                     int G, int S, int C, int e, hipStream_t s) {
-  if (e > 1024 || e % 8 || G <= 0 || S <= 0) return hipErrorInvalidValue;
+  if (G <= 0 || S <= 0 || (dimg && (e > 1024 || e % 8))) return hipErrorInvalidValue;      // only the image kernel limits e
   if (dtxt) hipLaunchKernelGGL(logits_ranged_bwd_txt_kernel, dim3((S + 3) / 4), dim3(256), 0, s, dlogits, imn, txn, tnorm, scale, lo, start,
                                seq_grp, dtxt, S, C, e);
   if (dimg) hipLaunchKernelGGL(logits_ranged_bwd_img_kernel, dim3(G), dim3(512), 0, s, dlogits, imn, txn, inorm, scale, lo, start, dimg, C, e);

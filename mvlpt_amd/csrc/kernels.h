@@ -246,11 +246,6 @@ hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipS
 // token ids (clip/model.py encode_text): x [S, L, d] = emb[ids[s, t]] + pos[t]; ids int32 [S, ld], ld >= L, columns 0 .. L-1 read, every one
 // of them inside the table (checked on the host by the callers); d % 4 == 0
 hipError_t launch_embed_tokens(const float* emb, const float* pos, const int32_t* ids, int ld, float* x, int S, int L, int d, hipStream_t s);
-// grouped prompts (trainers/cocoop.py:123-161): sequence s = g*C + c = class c's prefix / suffix / layout row + context block g of
-// ctx [G, n_ctx, d]; eot rows s*L + eot[s % C]
-hipError_t launch_assemble_prompts_grouped(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
-                                           const float* pos, float* x, int G, int C, int L, int d, hipStream_t s);
-hipError_t launch_eot_rows_grouped(const int32_t* eot, int32_t* rows, int G, int C, int L, hipStream_t s);
 // dst[r] = src[idx[r]] (scatter = 0) or dst[idx[r]] = src[r] (scatter = 1); row_bytes % 16 == 0
 hipError_t launch_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, hipStream_t s);
 // rows of row_bytes (multiple of 16) from src + r*src_pitch to dst + r*dst_pitch
@@ -261,12 +256,11 @@ hipError_t launch_reduce_prompt_rows(int dtype, float* dx32, void* dx16, int B, 
 // dctx (generic) [n,d] = inv_scale * sum_c dx[c, ctx_pos[c,j], :]  or (per class) [C,n,d]
 hipError_t launch_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C, int L, int d, int n_ctx, int per_class,
                                   float* dctx, const float* scale_dev, hipStream_t s);
-// dctx (grouped) [G,n,d] = inv_scale * sum_c dx[g*C + c, ctx_pos[c,j], :]  (ctx_pos per class, [C, n])
-hipError_t launch_gather_ctx_grad_grouped(const float* dx, const int32_t* ctx_pos, int G, int C, int L, int d, int n_ctx, float* dctx,
-                                          const float* scale_dev, hipStream_t s);
-// ranged prompts (trainers/mvlpt.py:556-581 under the per-task mask): group g owns classes [lo[g], lo[g] + start[g+1] - start[g]); its
+// ranged prompts (one context block of ctx [G, n_ctx, d] per image, trainers/cocoop.py:123-161; under the per-task mask of
+// trainers/mvlpt.py:556-581 only the image's own classes): group g owns classes [lo[g], lo[g] + start[g+1] - start[g]); its
 // sequences start[g] .. start[g+1] - 1 are those classes in order.  seq_cls / seq_grp int32 [S]: class and group of every sequence;
 // lo int32 [G], start int32 [G + 1] (prefix sum, start[G] = S).  The tables are built and checked on the host (engine.hip).
+// CoCoOp's grouped tower and head are the case of every range full (s = g*C + c).
 hipError_t launch_assemble_prompts_ranged(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                                           const float* pos, float* x, const int32_t* seq_cls, const int32_t* seq_grp, int S, int L, int d,
                                           hipStream_t s);
@@ -301,10 +295,6 @@ hipError_t launch_cross_entropy(const float* logits, const void* labels, int lab
 hipError_t launch_logits_bwd(const float* dlogits, const float* imn, const float* txn, const float* inorm, const float* tnorm,
                              float scale, const int32_t* lo, const int32_t* hi, float* dimg, float* dtxt,
                              int B, int C, int e, hipStream_t s);
-// grouped head: logits[g,c] = scale * imn[g] . txn[g*C + c];  backward: dtxt [G*C, e] only (the image side is frozen)
-hipError_t launch_logits_grouped(const float* imn, const float* txn, float scale, float* logits, int G, int C, int e, hipStream_t s);
-hipError_t launch_logits_grouped_bwd(const float* dlogits, const float* imn, const float* txn, const float* tnorm, float scale, float* dtxt,
-                                     int G, int C, int e, hipStream_t s);
 // ranged head: logits[g,c] = scale * imn[g] . txn[start[g] + c - lo[g]] for lo[g] <= c < lo[g] + (start[g+1] - start[g]), 0 elsewhere;
 // backward: dtxt [S, e] and / or dimg [G, e] (through the image normalisation); dlogits outside the ranges is not read
 hipError_t launch_logits_ranged(const float* imn, const float* txn, float scale, const int32_t* lo, const int32_t* start, float* logits,

@@ -558,30 +558,10 @@ def join_mixed(p: torch.Tensor) -> torch.Tensor:
     return p[:, :d].float() + lo8 * 2.0 ** -LO8_EXP[p.dtype]
 
 
-def op_assemble_prompts_grouped(prefix, suffix, ctx, layout, pos) -> torch.Tensor:
-    """Grouped prompt assembly (CoCoOp): [G*C, L, d] = class rows of prefix [C,1,d] / suffix [C,L-1-n,d] / layout [C,L] with context
-    block g of ctx [G,n,d], plus pos [L,d] (the first L rows are read)."""
-    C_, L = layout.shape
-    G, n, d = ctx.shape
-    x = torch.empty(G * C_, L, d, device=ctx.device, dtype=torch.float32)
-    _lib.check(lib.mvlpt_op_assemble_prompts_grouped(_ptr(prefix.contiguous()), _ptr(suffix.contiguous()), _ptr(ctx.contiguous()), n,
-                                                     _ptr(layout.to(torch.int32).contiguous()), _ptr(pos.contiguous()), _ptr(x),
-                                                     G, C_, L, d, _stream()), None, "op_assemble_prompts_grouped")
-    return x
-
-
-def op_gather_ctx_grad_grouped(dx, ctx_pos, G: int) -> torch.Tensor:
-    """dctx [G, n, d] = sum over the classes of dx [G*C, L, d] at the positions ctx_pos [C, n]."""
-    N, L, d = dx.shape
-    C_, n = ctx_pos.shape
-    dctx = torch.empty(G, n, d, device=dx.device, dtype=torch.float32)
-    _lib.check(lib.mvlpt_op_gather_ctx_grad_grouped(_ptr(dx.contiguous()), _ptr(ctx_pos.to(torch.int32).contiguous()), G, C_, L, d, n,
-                                                    _ptr(dctx), _stream()), None, "op_gather_ctx_grad_grouped")
-    return dctx
-
-
 def op_assemble_prompts_ranged(prefix, suffix, ctx, layout, pos, class_lo, class_hi) -> torch.Tensor:
-    """x [S, L, d] of the ranged tower's entry (mvlpt_op_assemble_prompts_ranged); class_lo / class_hi: host sequences of length G."""
+    """x [S, L, d] of the ranged tower's entry (mvlpt_op_assemble_prompts_ranged): class rows of prefix [C,1,d] / suffix [C,L-1-n,d] /
+    layout [C,L] with context block g of ctx [G,n,d], plus pos [L,d] (the first L rows are read).  class_lo / class_hi: host sequences
+    of length G; [0]*G, [C]*G is the grouped (CoCoOp) tower, S = G*C."""
     G, n, d = ctx.shape
     C_, L = layout.shape
     lo, hi, S = _host_ranges(class_lo, class_hi, G, C_)

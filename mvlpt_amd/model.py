@@ -472,15 +472,15 @@ class ClassShard:
 
 
 # ------------------------------------------------------------------------------------------------ autograd bridge
-def _text_inputs(model, pl):
-    """token_suffix / layout handed to the text tower.  With `trim_text_to_eot` (off by default) only the first
-    max(eot)+1 positions are evaluated: the text transformer is causal (clip/model.py:324-330) and the feature is read
+def _text_inputs(model, pl, n_ctx):
+    """token_suffix / layout handed to the text tower, for a prompt learner `pl` with `n_ctx` context tokens.
+    With `trim_text_to_eot` (off by default) only the first max(eot)+1 positions are evaluated: the text transformer is causal (clip/model.py:324-330) and the feature is read
     at the EOT position (trainers/mvlpt.py:128), so later (padding) positions can influence neither the logits nor
     any gradient — the same observation the reference's CUT_CONTEXTLEN option is built on (trainers/mvlpt.py:297-305)."""
     if not model.trim_text_to_eot:
         return pl.token_suffix, pl.layout
     L_eff = pl.max_eot + 1
-    return pl.token_suffix[:, :L_eff - 1 - pl.coop_n_ctx], pl.layout[:, :L_eff]
+    return pl.token_suffix[:, :L_eff - 1 - n_ctx], pl.layout[:, :L_eff]
 
 
 class _PromptedClipFn(torch.autograd.Function):
@@ -506,7 +506,7 @@ class _PromptedClipFn(torch.autograd.Function):
         else:
             cached_eval = False
         run_text = not ((coop_emb is None or cached_eval) and model._const_text_features is not None)
-        suffix, layout = _text_inputs(model, pl)
+        suffix, layout = _text_inputs(model, pl, pl.coop_n_ctx)
         # features computed ahead of time (prefetch_image_features), keyed by the tensor they belong to
         pre = model._prefetched.pop((image.data_ptr(), tuple(image.shape), image._version), None) if vpt_emb is None else None
         if pre is not None:

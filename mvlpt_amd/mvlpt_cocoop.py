@@ -11,7 +11,7 @@ The reference runs one text tower per image in a Python loop and multiplies ever
 
 * under ``DATASET.MULTITASK_LABEL_PERTASK`` image b runs ONLY the sequences of its own task's class range [lo_b, hi_b)
   (mvlpt_text_fwd_ranged / mvlpt_logits_ranged_fwd): a masked logit is exactly 0 and carries no gradient, so its sequence is never
-  computed.  ``CustomCLIP.ranged_text = False`` selects the dense grouped tower (B x n_cls sequences) and a multiplicative mask
+  computed.  ``CustomCLIP.ranged_text = False`` runs every range full (B x n_cls sequences, CoCoOp's tower) and a multiplicative mask
   instead — the same logits, for comparison and as an escape hatch.  Without the per-task mask every range is [0, n_cls).
 * the batch is cut into chunks of consecutive images whose text tower fits ``max_text_workspace_bytes`` (sized over the chunk's OWN
   sequence count, not B * n_cls).  ``forward`` returns logits, so the backward arrives later: with ONE chunk the forward saves its
@@ -40,7 +40,7 @@ import torch.nn as nn
 
 from . import _lib
 from .cocoop import DEFAULT_MAX_TEXT_WORKSPACE_BYTES, MAX_SEQUENCES_PER_TOWER
-from .model import FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, build_prompt_layout
+from .model import FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, _text_inputs, build_prompt_layout
 from .model import MultitaskVLPromptLearner as _BasePromptLearner
 
 
@@ -165,14 +165,6 @@ def chunk_bounds(widths: List[int], fits) -> List[Tuple[int, int, int]]:
     return out
 
 
-def _text_inputs(model, pl):
-    """token_suffix / layout handed to the text tower; `trim_text_to_eot` as in mvlpt_amd.model._text_inputs."""
-    if not model.trim_text_to_eot:
-        return pl.token_suffix, pl.layout
-    L_eff = pl.max_eot + 1
-    return pl.token_suffix[:, :L_eff - 1 - pl.cocoop_n_ctx], pl.layout[:, :L_eff]
-
-
 class _ImageTowerFn(torch.autograd.Function):
     """The image tower with visual prompts as an autograd node: mvlpt_image_fwd(save_for_bwd) / mvlpt_image_bwd."""
 
@@ -193,18 +185,15 @@ class _ImageTowerFn(torch.autograd.Function):
 
 
 class _TextSideFn(torch.autograd.Function):
-    """(image features [B, e], shifted contexts [B, n_ctx, dt]) -> logits [B, n_cls]: per chunk the ranged (or dense grouped) text
-    tower and the ranged head.  See the module docstring for the one-chunk / recompute arrangement of the backward."""
+    """(image features [B, e], shifted contexts [B, n_ctx, dt]) -> logits [B, n_cls]: per chunk the ranged text tower (every range
+    full on the dense route) and the ranged head.  See the module docstring for the one-chunk / recompute arrangement of the backward."""
 
     @staticmethod
     def _chunk_forward(model, img, ctx_shifted, lo, hi, g0, g1, save):
         eng, pl = model.engine, model.prompt_learner
-        suffix, layout = _text_inputs(model, pl)
+        suffix, layout = _text_inputs(model, pl, pl.cocoop_n_ctx)
         clo, chi = lo[g0:g1], hi[g0:g1]
-        if all(a == 0 and b == pl.n_cls for a, b in zip(clo, chi)):     # every range full: the grouped tower (same kernels, same bits)
-            txt = eng.text_fwd_grouped(pl.token_prefix, suffix, ctx_shifted[g0:g1], layout, pl.eot, save_for_bwd=save)
-        else:
-            txt = eng.text_fwd_ranged(pl.token_prefix, suffix, ctx_shifted[g0:g1], layout, pl.eot, clo, chi, save_for_bwd=save)
+        txt = eng.text_fwd_ranged(pl.token_prefix, suffix, ctx_shifted[g0:g1], layout, pl.eot, clo, chi, save_for_bwd=save)
         return eng.logits_ranged_fwd(img[g0:g1], txt, model.logit_scale_exp, clo, chi, pl.n_cls)
 
     @staticmethod
@@ -213,7 +202,7 @@ class _TextSideFn(torch.autograd.Function):
         need_img = grad_on and bool(fctx.needs_input_grad[1])
         need_ctx = grad_on and bool(fctx.needs_input_grad[2])
         need = need_img or need_ctx
-        L = _text_inputs(model, pl)[1].shape[1]
+        L = _text_inputs(model, pl, pl.cocoop_n_ctx)[1].shape[1]
         chunks = model.chunks(lo, hi, L, save_for_bwd=need)
         save = need and len(chunks) == 1
         B = ctx_shifted.shape[0]
@@ -271,7 +260,7 @@ class CustomCLIP(nn.Module):
         self.logit_scale_exp = float(clip_model.logit_scale.exp())
         self.dtype = clip_model.dtype
         self.trim_text_to_eot = False        # mvlpt_amd.model.CustomCLIP's switch, same default
-        self.ranged_text = True              # False: dense grouped tower (B x n_cls sequences) + multiplicative mask
+        self.ranged_text = True              # False: every range full (B x n_cls sequences) + multiplicative mask
         self.max_text_workspace_bytes = DEFAULT_MAX_TEXT_WORKSPACE_BYTES
         # Precision: the image features are meta_net's input and every text row carries a gradient; as
         # mvlpt_amd.cocoop.CustomCLIP, raise the engine's default mode to split_all and leave an explicit "fast" alone

@@ -21,16 +21,14 @@ def _rel(a, b):
 
 
 # ------------------------------------------------------------------------------------------------ kernels
-@pytest.mark.parametrize("position", ["end", "middle"])
-def test_grouped_assembly_bit_exact(position):
-    from mvlpt_amd.engine import op_assemble_prompts_grouped
+def _grouped_assembly_bit_exact(G, C, L, n, d, name_lens, position):
+    from mvlpt_amd.engine import op_assemble_prompts_ranged
     from mvlpt_amd.model import build_prompt_layout
     g = torch.Generator().manual_seed(5)
-    G, C, L, n, d = 3, 7, 40, 5, 192
-    layout = build_prompt_layout([1, 2, 3, 1, 4, 2, 1], n, L, position)
+    layout = build_prompt_layout(name_lens, n, L, position)
     prefix, suffix = torch.randn(C, 1, d, generator=g), torch.randn(C, L - 1 - n, d, generator=g)
     ctx, pos = torch.randn(G, n, d, generator=g), torch.randn(L + 3, d, generator=g)
-    got = op_assemble_prompts_grouped(prefix.to(DEV), suffix.to(DEV), ctx.to(DEV), layout.to(DEV), pos.to(DEV)).cpu()
+    got = op_assemble_prompts_ranged(prefix.to(DEV), suffix.to(DEV), ctx.to(DEV), layout.to(DEV), pos.to(DEV), [0] * G, [C] * G).cpu()
     fixed = torch.cat([prefix, suffix], dim=1)                                              # [C, L - n, d]
     table = torch.cat([fixed.unsqueeze(0).expand(G, -1, -1, -1), ctx.unsqueeze(1).expand(-1, C, -1, -1)], dim=2)   # [G, C, L, d]
     idx = torch.where(layout >= 0, layout, (L - n) + (-layout - 1)).long()                  # row of `table` per position
@@ -38,8 +36,21 @@ def test_grouped_assembly_bit_exact(position):
     assert torch.equal(got, want.reshape(G * C, L, d))
 
 
+@pytest.mark.parametrize("position", ["end", "middle"])
+def test_grouped_assembly_bit_exact(position):
+    _grouped_assembly_bit_exact(3, 7, 40, 5, 192, [1, 2, 3, 1, 4, 2, 1], position)
+
+
+def test_grouped_assembly_bit_exact_capped_grid():
+    """(300, 77, 512), the capped-grid shape of tests/test_hip_glue.py::test_assemble_prompts_bit_exact, with two groups: 5.9 M float4
+    items against the 8192 x 256 threads of the capped grid, so every thread takes a second and a third stride (CoCoOp's real shapes
+    always do), and the later strides belong to the second group."""
+    C = 300
+    _grouped_assembly_bit_exact(2, C, 77, 5, 512, [1 + c % 4 for c in range(C)], "middle")
+
+
 def test_grouped_ctx_grad_gather_deterministic_and_exact():
-    from mvlpt_amd.engine import op_gather_ctx_grad_grouped
+    from mvlpt_amd.engine import op_gather_ctx_grad_ranged
     from mvlpt_amd.model import build_prompt_layout
     g = torch.Generator().manual_seed(6)
     G, C, L, n, d = 4, 37, 30, 6, 256
@@ -50,8 +61,8 @@ def test_grouped_ctx_grad_gather_deterministic_and_exact():
             if layout[c, i] < 0:
                 ctx_pos[c, -int(layout[c, i]) - 1] = i
     dx = torch.randn(G * C, L, d, generator=g)
-    a = op_gather_ctx_grad_grouped(dx.to(DEV), ctx_pos.to(DEV), G).cpu()
-    b = op_gather_ctx_grad_grouped(dx.to(DEV), ctx_pos.to(DEV), G).cpu()
+    a = op_gather_ctx_grad_ranged(dx.to(DEV), ctx_pos.to(DEV), [0] * G, [C] * G).cpu()
+    b = op_gather_ctx_grad_ranged(dx.to(DEV), ctx_pos.to(DEV), [0] * G, [C] * G).cpu()
     assert torch.equal(a, b)
     rows = dx.double().view(G, C, L, d)[:, torch.arange(C).view(C, 1), ctx_pos.long()]      # [G, C, n, d]
     want = rows.sum(1)
@@ -85,28 +96,63 @@ def test_grouped_head_fwd_bwd_against_float64(tiny_clip):
 
 # ------------------------------------------------------------------------------------------------ engine
 def test_grouped_text_tower_equals_csc_tower(tiny_clip):
+    """The grouped entry against the plain kernels.  (1, 17): a single group with more classes than the gather has waves; (2, 16):
+    exactly one class per wave."""
     from mvlpt_amd.model import build_prompt_layout
     eng, arch = tiny_clip.engine, tiny_clip.arch
     g = torch.Generator().manual_seed(8)
-    G, C, L, n, dt = 3, 5, 77, 4, arch.transformer_width
-    layout = build_prompt_layout([1, 2, 2, 1, 3], n, L, "end").to(DEV)
-    eot = torch.tensor([8, 9, 9, 8, 10], dtype=torch.int32, device=DEV)
-    prefix = (torch.randn(C, 1, dt, generator=g) * 0.02).to(DEV)
-    suffix = (torch.randn(C, L - 1 - n, dt, generator=g) * 0.02).to(DEV)
-    ctx = (torch.randn(G, n, dt, generator=g) * 0.1).to(DEV)
-    dfeat = torch.randn(G * C, arch.embed_dim, generator=g).to(DEV)
-    fg = eng.text_fwd_grouped(prefix, suffix, ctx, layout, eot, save_for_bwd=True)
-    dg = eng.text_bwd(dfeat)
-    assert dg.shape == (G, n, dt)
-    fc = eng.text_fwd(prefix.repeat(G, 1, 1), suffix.repeat(G, 1, 1), ctx.repeat_interleave(C, 0), layout.repeat(G, 1),
-                      eot.repeat(G), save_for_bwd=True)
-    dc = eng.text_bwd(dfeat)
+    L, n, dt = 77, 4, arch.transformer_width
+    for G, C in ((3, 5), (1, 17), (2, 16)):
+        name_lens = ([1, 2, 2, 1, 3] * 4)[:C]
+        layout = build_prompt_layout(name_lens, n, L, "end").to(DEV)
+        eot = torch.tensor([7 + k for k in name_lens], dtype=torch.int32, device=DEV)
+        prefix = (torch.randn(C, 1, dt, generator=g) * 0.02).to(DEV)
+        suffix = (torch.randn(C, L - 1 - n, dt, generator=g) * 0.02).to(DEV)
+        ctx = (torch.randn(G, n, dt, generator=g) * 0.1).to(DEV)
+        dfeat = torch.randn(G * C, arch.embed_dim, generator=g).to(DEV)
+        fg = eng.text_fwd_grouped(prefix, suffix, ctx, layout, eot, save_for_bwd=True)
+        dg = eng.text_bwd(dfeat)
+        assert dg.shape == (G, n, dt)
+        fc = eng.text_fwd(prefix.repeat(G, 1, 1), suffix.repeat(G, 1, 1), ctx.repeat_interleave(C, 0), layout.repeat(G, 1),
+                          eot.repeat(G), save_for_bwd=True)
+        dc = eng.text_bwd(dfeat)
+        torch.cuda.synchronize()
+        assert torch.equal(fg, fc), f"G={G} C={C}: grouped features must be bit-identical to the materialised CSC tower"
+        want = dc.view(G, C, n, dt).double().sum(1)
+        assert float((dg.double() - want).abs().max()) <= 1e-6 * float(want.abs().max()), f"G={G} C={C}"
+        per_image = eng.text_workspace_bytes(C, L, True)
+        assert per_image > 0 and (G == 1 or eng.text_workspace_bytes(G * C, L, True) > per_image)
+
+
+def test_head_backward_follows_only_its_own_forward(tiny_clip):
+    """logits_bwd, logits_grouped_bwd and logits_ranged_bwd each run after the forward of their own name and raise after either of
+    the other two, although the grouped head is computed by the ranged kernels."""
+    eng = tiny_clip.engine
+    e = tiny_clip.arch.embed_dim
+    g = torch.Generator().manual_seed(11)
+    G, C = 2, 3
+    img, txt_c = torch.randn(G, e, generator=g).to(DEV), torch.randn(C, e, generator=g).to(DEV)
+    txt_gc = torch.randn(G * C, e, generator=g).to(DEV)
+    dl = torch.randn(G, C, generator=g).to(DEV)
+    forwards = {
+        "plain": lambda: eng.logits_fwd(img, txt_c, 10.0),
+        "grouped": lambda: eng.logits_grouped_fwd(img, txt_gc, 10.0),
+        "ranged": lambda: eng.logits_ranged_fwd(img, txt_gc, 10.0, [0] * G, [C] * G, C),
+    }
+    backwards = {
+        "plain": lambda: eng.logits_bwd(dl),
+        "grouped": lambda: eng.logits_grouped_bwd(dl),
+        "ranged": lambda: eng.logits_ranged_bwd(dl),
+    }
+    for f, fwd in forwards.items():
+        for b, bwd in backwards.items():
+            assert fwd().shape == (G, C)
+            if b == f:
+                bwd()
+            else:
+                with pytest.raises(RuntimeError, match=r"call logits\w*_fwd first"):
+                    bwd()
     torch.cuda.synchronize()
-    assert torch.equal(fg, fc), "grouped features must be bit-identical to the materialised CSC tower"
-    want = dc.view(G, C, n, dt).double().sum(1)
-    assert float((dg.double() - want).abs().max()) <= 1e-6 * float(want.abs().max())
-    nb = eng.text_workspace_bytes(G * C, L, True)
-    assert nb > eng.text_workspace_bytes(C, L, True) > 0
 
 
 # ------------------------------------------------------------------------------------------------ model vs reference

@@ -62,7 +62,7 @@ def _ctx_pos(layout, n):
 
 
 def test_ranged_ctx_grad_gather_deterministic_and_exact():
-    from mvlpt_amd.engine import op_gather_ctx_grad_grouped, op_gather_ctx_grad_ranged
+    from mvlpt_amd.engine import op_gather_ctx_grad, op_gather_ctx_grad_ranged
     from mvlpt_amd.model import build_prompt_layout
     g = torch.Generator().manual_seed(6)
     C, L, n, d = 37, 30, 6, 256
@@ -80,11 +80,12 @@ def test_ranged_ctx_grad_gather_deterministic_and_exact():
         want[gi] += dx[s].double()[ctx_pos[c].long()]
     assert float((a.double() - want).abs().max()) <= 1e-6 * float(want.abs().max())
     assert torch.equal(a[3], torch.zeros(n, d)), "an empty range must give exact zeros"
-    # every range full: the grouped kernel's bits
+    # every range full (the grouped tower): group by group the bits of the generic-context gather over the group's C sequences
     G2 = 3
     dx2 = torch.randn(G2 * C, L, d, generator=g)
     full = op_gather_ctx_grad_ranged(dx2.to(DEV), ctx_pos.to(DEV), [0] * G2, [C] * G2).cpu()
-    assert torch.equal(full, op_gather_ctx_grad_grouped(dx2.to(DEV), ctx_pos.to(DEV), G2).cpu())
+    per_group = [op_gather_ctx_grad(dx2[k * C:(k + 1) * C].to(DEV), ctx_pos.to(DEV), False, None).cpu() for k in range(G2)]
+    assert torch.equal(full, torch.stack(per_group))
 
 
 @pytest.fixture(scope="module")

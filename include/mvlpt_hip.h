@@ -369,6 +369,37 @@ int mvlpt_op_assemble_prompts(const float* prefix, const float* suffix, const fl
                               const int32_t* layout, const float* pos, const int32_t* eot, float* x, int32_t* ctx_pos, int32_t* eot_rows,
                               int C, int L, int d, mvlpt_stream_t stream);
 
+/* ---- fused optimizer step over the flat prompt buffers (row f2 of the scope table; tests/test_hip_optim.py) ----
+ * ONE launch updates param, state1 and state2 in place over [0, n) with torch.optim's single-tensor formulas in fp32:
+ *   SGD   (kind 0): d = g + wd p;  buf = d on a segment's first step, else m buf + (1 - damp) d;  p -= lr (nesterov ? d + m buf : buf);
+ *                   momentum == 0: no buffer (state1 may be NULL), p -= lr d.
+ *   Adam  (kind 1): g' = g + wd p;                      AdamW (kind 2): p *= 1 - lr wd, g' = g;   then, with t the segment's step count,
+ *                   m += (1 - b1)(g' - m);  v = b2 v + (1 - b2) g'^2;  p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps).
+ * The buffers are the parameter tensors back to back, 16-byte aligned; segs_dev (DEVICE, n_segs <= MVLPT_OPTIM_MAX_SEGS entries sorted by
+ * `begin`, not overlapping, boundaries arbitrary) names them.  A segment with active == 0 (a parameter without a gradient), and any
+ * element no segment covers, is not touched, bit for bit.  A segment's step count is t = launch - missed: the caller adds to `missed`
+ * the launches a segment sat out when it comes back, so a table whose active set does not change is never uploaded again.
+ * `hyper` is HOST memory, read at call time.  loss_dev (DEVICE float, or NULL): when *loss_dev is NaN or +-inf the launch writes
+ * nothing to param / state1 / state2 and adds 1 to *skipped_dev (DEVICE int32, or NULL), once per launch.  Enqueue-only on `stream`. */
+enum { MVLPT_OPTIM_SGD = 0, MVLPT_OPTIM_ADAM = 1, MVLPT_OPTIM_ADAMW = 2 };
+enum { MVLPT_OPTIM_MAX_SEGS = 1024 };
+typedef struct MvlptOptimSeg {
+  int64_t begin, end;             /* elements [begin, end) of the flat buffers */
+  int32_t active;                 /* 0: the parameter has no gradient this step */
+  int32_t missed;                 /* launches this segment did not take part in */
+} MvlptOptimSeg;
+typedef struct MvlptOptimHyper {
+  int32_t kind;                   /* MVLPT_OPTIM_* */
+  int32_t nesterov;
+  /* doubles, as torch.optim holds them: the kernel's fp32 constants (1 - beta, 1 - dampening, 1 - lr wd, the bias corrections) are
+   * formed in double and rounded once — 1 - beta2^t from a beta2 already rounded to fp32 would be off by 1e-5 of its value */
+  double lr, weight_decay, momentum, dampening;
+  double beta1, beta2, eps;
+  int64_t launch;                 /* 1-based count of step calls */
+} MvlptOptimHyper;
+int mvlpt_op_optim_step(const MvlptOptimHyper* hyper, float* param, const float* grad, float* state1, float* state2, int64_t n,
+                        const MvlptOptimSeg* segs_dev, int n_segs, const float* loss_dev, int32_t* skipped_dev, mvlpt_stream_t stream);
+
 /* ---- input pipeline ("next" row f3 of the scope table) -------------------------------------------------------
  * Replaces the per-image CPU transform the reference runs in DataLoader workers: Dassl `build_transform` with
  * INPUT.TRANSFORMS = random_resized_crop / random_flip / normalize, INTERPOLATION bicubic, CLIP PIXEL_MEAN/STD

@@ -42,6 +42,19 @@ class MvlptImageDesc(C.Structure):
         "out_top", "out_left", "flip", "reserved")]
 
 
+OPTIM_SGD, OPTIM_ADAM, OPTIM_ADAMW = 0, 1, 2
+OPTIM_MAX_SEGS = 1024   # MVLPT_OPTIM_MAX_SEGS
+
+
+class MvlptOptimSeg(C.Structure):
+    _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("active", C.c_int32), ("missed", C.c_int32)]
+
+
+class MvlptOptimHyper(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("nesterov", C.c_int32), ("lr", C.c_double), ("weight_decay", C.c_double), ("momentum", C.c_double),
+                ("dampening", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("launch", C.c_int64)]
+
+
 _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 
 # name -> (restype, argtypes): every symbol include/mvlpt_hip.h declares
@@ -112,6 +125,7 @@ SIGNATURES = {
     "mvlpt_op_normalize_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "mvlpt_op_sgemm_bt": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "mvlpt_op_grad_scale": (_i, [_vp, C.c_int64, _f, _vp, _vp]),
+    "mvlpt_op_optim_step": (_i, [C.POINTER(MvlptOptimHyper), _vp, _vp, _vp, _vp, C.c_int64, _vp, _i, _vp, _vp, _vp]),
     "mvlpt_op_reduce_prompt_rows": (_i, [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "mvlpt_op_gather_ctx_grad": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mvlpt_op_attention_bwd_cls": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

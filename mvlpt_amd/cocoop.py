@@ -228,10 +228,7 @@ class CoCoOp(MVLPT):
         self.model.to(self.device)
         if self.world_size > 1:
             dist_utils.broadcast_parameters(self.model.prompt_learner)
-        self.optim = build_optimizer(self.model.prompt_learner, cfg.OPTIM)              # :238-241
-        self.sched = build_lr_scheduler(self.optim, cfg.OPTIM)
-        self.register_model("prompt_learner", self.model.prompt_learner, self.optim, self.sched)
-        self.flatten_gradients("prompt_learner")
+        self.optim, self.sched = self.build_optim("prompt_learner", self.model.prompt_learner)   # :238-241
         self.scaler = None    # amp: the HIP backward scales its 16-bit activation gradients internally (MVLPT.check_cfg)
 
     def forward_backward(self, batch):

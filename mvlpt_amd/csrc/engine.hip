@@ -1824,6 +1824,21 @@ int mvlpt_op_grad_scale(const float* v, int64_t n, float target, float* scale_de
   OPCHK(launch_grad_scale(v, (size_t)n, target, scale_dev, (hipStream_t)stream));
   return 0;
 }
+int mvlpt_op_optim_step(const MvlptOptimHyper* hyper, float* param, const float* grad, float* state1, float* state2, int64_t n,
+                        const MvlptOptimSeg* segs_dev, int n_segs, const float* loss_dev, int32_t* skipped_dev, mvlpt_stream_t stream) {
+  if (!hyper || !param || !grad || !segs_dev || n <= 0 || n_segs <= 0) { g_create_err = "op_optim_step: null/invalid argument"; return MVLPT_ERR_ARG; }
+  const MvlptOptimHyper& h = *hyper;
+  if (h.kind < MVLPT_OPTIM_SGD || h.kind > MVLPT_OPTIM_ADAMW || h.launch < 1) { g_create_err = "op_optim_step: unknown kind, or launch < 1"; return MVLPT_ERR_ARG; }
+  if (n_segs > MVLPT_OPTIM_MAX_SEGS) { g_create_err = "op_optim_step: more than MVLPT_OPTIM_MAX_SEGS segments"; return MVLPT_ERR_UNSUPPORTED; }
+  if ((h.kind == MVLPT_OPTIM_SGD && h.momentum != 0.0 && !state1) || (h.kind != MVLPT_OPTIM_SGD && (!state1 || !state2))) {
+    g_create_err = "op_optim_step: this optimizer kind needs its state buffer(s)"; return MVLPT_ERR_ARG; }
+  if (h.kind == MVLPT_OPTIM_SGD && h.nesterov && (h.momentum <= 0.0 || h.dampening != 0.0)) {
+    g_create_err = "op_optim_step: nesterov needs a momentum and zero dampening"; return MVLPT_ERR_ARG; }
+  if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)state1 | (uintptr_t)state2) & 15) != 0) {
+    g_create_err = "op_optim_step: the flat buffers must be 16-byte aligned"; return MVLPT_ERR_ARG; }
+  OPCHK(launch_optim_step(h, param, grad, state1, state2, n, segs_dev, n_segs, loss_dev, skipped_dev, (hipStream_t)stream));
+  return 0;
+}
 int mvlpt_op_reduce_prompt_rows(int dtype, float* dx32, void* dx16, int B, int L, int d, int row0, int n, float* out,
                                 const float* scale_dev, int zero_after, int split16, const float* vmask, mvlpt_stream_t stream) {
   if (!dx32 || !out || B <= 0 || d <= 0 || n <= 0 || row0 < 0 || row0 + n > L || split16 < 0 || split16 > 2) {

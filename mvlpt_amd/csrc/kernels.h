@@ -3,6 +3,9 @@
 #pragma once
 #include "common.h"
 
+struct MvlptOptimHyper;      // include/mvlpt_hip.h
+struct MvlptOptimSeg;
+
 namespace mvlpt {
 
 // ---------------------------------------------------------------- streams with a compute-unit partition (engine.hip)
@@ -270,6 +273,10 @@ hipError_t launch_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos
                                          int d, int n_ctx, float* dctx, const float* scale_dev, hipStream_t s);
 // scale_dev[0] = 2^k with amax(|v|)*2^k ~ target ; scale_dev[1] = 1/scale_dev[0]
 hipError_t launch_grad_scale(const float* v, size_t n, float target, float* scale_dev, hipStream_t s);
+// fused optimizer step over the flat prompt buffers (optim.hip; semantics in include/mvlpt_hip.h, mvlpt_op_optim_step); the
+// arguments are checked by the caller (engine.hip)
+hipError_t launch_optim_step(const MvlptOptimHyper& h, float* param, const float* grad, float* state1, float* state2, int64_t n,
+                             const MvlptOptimSeg* segs_dev, int n_segs, const float* loss_dev, int32_t* skipped_dev, hipStream_t s);
 hipError_t launch_zero(void* p, size_t bytes, hipStream_t s);
 hipError_t launch_checksum(const void* p, size_t bytes, unsigned long long* out, hipStream_t s);      // debug (mvlpt_debug_checksums)
 // LayerNorm folding: colsum[n] = sum_k W16[n,k] gamma[k], bias2[n] = b[n] + sum_k W16[n,k] beta[k]  (W16 [N, ld] packed weight)

@@ -115,6 +115,43 @@ class FlatGradients:
             dist.all_reduce(self.flat, op=dist.ReduceOp.AVG)
 
 
+class FlatParameters:
+    """The twin of `FlatGradients` for the values: ONE fp32 buffer that the trainable parameters' `.data` are views of, in the same
+    order and at the same offsets as their gradients in `FlatGradients.flat`, so that one kernel launch can step all of them
+    (mvlpt_amd.optim).  The parameters stay leaf nn.Parameters with their state_dict() keys; `load_state_dict` and everything else
+    that copies in place (`param.copy_`, `param.data.copy_`) keeps the views.  Create it AFTER `model.to(device)`: moving the
+    module afterwards gives the parameters storage of their own again (`intact()` is False then and `attach()` adopts them)."""
+
+    def __init__(self, params: Iterable[torch.nn.Parameter]):
+        self.params = [p for p in params if p.requires_grad]
+        n = sum(p.numel() for p in self.params)
+        dev = self.params[0].device if self.params else torch.device("cpu")
+        self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.views: List[torch.Tensor] = []
+        self.offsets: List[int] = []
+        off = 0
+        for p in self.params:
+            if p.dtype != torch.float32:
+                raise TypeError("FlatParameters: fp32 master parameters expected")
+            if p.device != dev:
+                raise ValueError("FlatParameters: every parameter must already be on the same device (create it after model.to(device))")
+            self.views.append(self.flat[off:off + p.numel()].view(p.shape))
+            self.offsets.append(off)
+            off += p.numel()
+        self.attach()
+
+    def attach(self) -> None:
+        """Adopt every parameter whose `.data` is not (or no longer) its view: copy the values into the slot, point `.data` at it."""
+        with torch.no_grad():
+            for p, v in zip(self.params, self.views):
+                if p.data_ptr() != v.data_ptr():
+                    v.copy_(p.data)
+                    p.data = v
+
+    def intact(self) -> bool:
+        return all(p.data_ptr() == v.data_ptr() and p.device == v.device for p, v in zip(self.params, self.views))
+
+
 def all_reduce_gradients(params: Iterable[torch.nn.Parameter], world_size: int) -> None:
     """grad <- mean over ranks, through one flat buffer (each rank's loss is the mean over its own slice, all
     slices have the same size, so the mean of rank gradients is the gradient of the global-batch mean loss)."""

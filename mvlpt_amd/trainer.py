@@ -29,15 +29,31 @@ from .weights import ARCHS, make_state_dict
 
 
 # ------------------------------------------------------------------------------------------------ Dassl stand-ins
-def build_optimizer(model: torch.nn.Module, optim_cfg) -> torch.optim.Optimizer:
-    """Dassl build_optimizer("sgd") defaults: over model.parameters()."""
+def build_optimizer(model: torch.nn.Module, optim_cfg, flat=None) -> torch.optim.Optimizer:
+    """Dassl build_optimizer("sgd" | "adam" | "adamw") defaults: over model.parameters().
+    OPTIM.FUSED (not in the reference, opt-in): the same optimizer as ONE HIP launch per step (mvlpt_amd.optim) over
+    `flat` = (distributed.FlatParameters, distributed.FlatGradients) of those parameters."""
     params = [p for p in model.parameters() if p.requires_grad]
     name = optim_cfg.NAME.lower()
+    if optim_cfg.get("FUSED", False):
+        from .optim import FUSED
+        if name not in FUSED:
+            raise ValueError(f"unsupported optimizer {optim_cfg.NAME} on the fused route (sgd | adam | adamw)")
+        if optim_cfg.get("AMSGRAD", False) or optim_cfg.get("STAGED_LR", False):
+            raise ValueError("OPTIM.FUSED supports neither amsgrad nor staged learning rates (one param group)")
+        if flat is None:
+            raise ValueError("OPTIM.FUSED: build_optimizer needs flat=(FlatParameters, FlatGradients) of the model's parameters")
+        if name == "sgd":
+            return FUSED[name](flat[0], flat[1], lr=optim_cfg.LR, momentum=optim_cfg.MOMENTUM, weight_decay=optim_cfg.WEIGHT_DECAY,
+                               dampening=optim_cfg.SGD_DAMPNING, nesterov=optim_cfg.SGD_NESTEROV)
+        return FUSED[name](flat[0], flat[1], lr=optim_cfg.LR, weight_decay=optim_cfg.WEIGHT_DECAY)
     if name == "sgd":
         return torch.optim.SGD(params, lr=optim_cfg.LR, momentum=optim_cfg.MOMENTUM, weight_decay=optim_cfg.WEIGHT_DECAY,
                                dampening=optim_cfg.SGD_DAMPNING, nesterov=optim_cfg.SGD_NESTEROV)
     if name == "adam":
         return torch.optim.Adam(params, lr=optim_cfg.LR, weight_decay=optim_cfg.WEIGHT_DECAY)
+    if name == "adamw":
+        return torch.optim.AdamW(params, lr=optim_cfg.LR, weight_decay=optim_cfg.WEIGHT_DECAY)
     raise ValueError(f"unsupported optimizer {optim_cfg.NAME}")
 
 
@@ -122,7 +138,7 @@ class TrainerX:
 
     def __init__(self, cfg: CfgNode):
         self._models, self._optims, self._scheds = OrderedDict(), OrderedDict(), OrderedDict()
-        self._flat_grads = {}
+        self._flat_grads, self._flat_params, self._skipped_seen = {}, {}, {}
         self.cfg = cfg
         self.rank, self.world_size, self.local_rank = dist_utils.rank_info()
         self.device = torch.device(f"cuda:{self.local_rank}") if torch.cuda.is_available() else torch.device("cpu")
@@ -165,18 +181,24 @@ class TrainerX:
     def model_backward(self, loss):
         loss.backward()
 
-    def model_update(self, names=None):
+    def model_update(self, names=None, loss=None):
+        """`loss` (the step's loss on the device) reaches a fused optimizer as its guard: a non-finite loss leaves the
+        parameters and the optimizer state as they are (mvlpt_amd.optim)."""
         for n in self.get_model_names(names):
             if self._optims[n] is not None:
-                self._optims[n].step()
+                if loss is not None and n in getattr(self, "_flat_params", {}):
+                    self._optims[n].step(loss_dev=loss.detach())
+                else:
+                    self._optims[n].step()
 
     def model_backward_and_update(self, loss, names=None):
         """Dassl order: zero_grad -> backward -> step.  The finite-loss check of Dassl's `detect_anomaly` is done
-        once per PRINT_FREQ on the host copy of the loss instead of forcing a device sync every step."""
+        once per PRINT_FREQ on the host copy of the loss instead of forcing a device sync every step; a fused optimizer
+        (OPTIM.FUSED) also gets the loss as a device pointer and skips the update of a step whose loss is not finite."""
         self.model_zero_grad(names)
         self.model_backward(loss)
         self.sync_gradients(names)
-        self.model_update(names)
+        self.model_update(names, loss=loss)
 
     def sync_gradients(self, names=None):
         """The one exchange of the data-parallel step (replaces nn.DataParallel's gather, trainers/mvlpt.py:877-880): a single
@@ -193,6 +215,32 @@ class TrainerX:
         """Give the registered model's parameters one persistent flat gradient buffer (distributed.FlatGradients)."""
         self._flat_grads[name] = dist_utils.FlatGradients(self._models[name].parameters())
         return self._flat_grads[name]
+
+    def build_optim(self, name, module):
+        """Optimizer, scheduler, registry entry and flat gradient buffer of the trainable `module`.  OPTIM.FUSED: its values become
+        views of one flat buffer too (distributed.FlatParameters; the module is on its device by now) and the optimizer steps both
+        buffers in one launch."""
+        flat = None
+        if self.cfg.OPTIM.get("FUSED", False):
+            flat = (dist_utils.FlatParameters(module.parameters()), dist_utils.FlatGradients(module.parameters()))
+        optim = build_optimizer(module, self.cfg.OPTIM, flat)
+        sched = build_lr_scheduler(optim, self.cfg.OPTIM)
+        self.register_model(name, module, optim, sched)
+        if flat is None:
+            self.flatten_gradients(name)      # zero_grad = 1 launch; N > 1: one in-place all-reduce, nothing else
+        else:
+            self._flat_params[name], self._flat_grads[name] = flat
+        return optim, sched
+
+    def check_skipped_steps(self, names=None):
+        """Fused route, called where the loop syncs anyway: a step whose loss was not finite was NOT applied (the prompts and the
+        optimizer state are the last good ones) — the same error Dassl's anomaly check raises."""
+        for n in self.get_model_names(names):
+            if n in getattr(self, "_flat_params", {}):
+                k = self._optims[n].skipped()
+                if k != self._skipped_seen.get(n, 0):
+                    self._skipped_seen[n] = k
+                    raise FloatingPointError("Loss is infinite or NaN!")
 
     # -- checkpoints (Dassl format: state_dict, epoch, optimizer, scheduler, val_result)
     def save_model(self, epoch, directory, is_best=False, val_result=None, model_name=""):
@@ -239,6 +287,7 @@ class TrainerX:
                     vals = {k: (float(v) if torch.is_tensor(v) else v) for k, v in summary.items()}
                     if not math.isfinite(vals["loss"]):
                         raise FloatingPointError("Loss is infinite or NaN!")
+                    self.check_skipped_steps()
                     print(f"epoch [{self.epoch + 1}/{self.max_epoch}] batch [{self.batch_idx + 1}/{self.num_batches}] "
                           f"time {time.time() - t0:.2f}s " + " ".join(f"{k} {v:.4f}" for k, v in vals.items()))
         finally:
@@ -448,10 +497,7 @@ class MVLPT(TrainerX):
         self.model.to(self.device)
         if self.world_size > 1:
             dist_utils.broadcast_parameters(self.model.prompt_learner)   # identical prompts on every rank
-        self.optim = build_optimizer(self.model.prompt_learner, cfg.OPTIM)   # NOTE: only the prompt learner (:869)
-        self.sched = build_lr_scheduler(self.optim, cfg.OPTIM)
-        self.register_model("prompt_learner", self.model.prompt_learner, self.optim, self.sched)
-        self.flatten_gradients("prompt_learner")      # zero_grad = 1 launch; N > 1: one in-place all-reduce, nothing else
+        self.optim, self.sched = self.build_optim("prompt_learner", self.model.prompt_learner)   # NOTE: only the prompt learner (:869)
         self.scaler = None    # the HIP backward scales its 16-bit activation gradients internally
 
     def forward_backward(self, batch):

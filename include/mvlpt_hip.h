@@ -105,6 +105,15 @@ const char* mvlpt_version(void);
 int mvlpt_stream_create_cus(int cu_first, int cu_count, mvlpt_stream_t* stream);
 int mvlpt_stream_destroy(mvlpt_stream_t stream);
 int mvlpt_stream_cus(mvlpt_stream_t stream);
+/* Grid cap of ANY stream (no CU mask, no new stream): while it is set, mvlpt_stream_cus(stream) is min(partition size or device
+ * count, n rounded DOWN to a multiple of 8 — workgroup b runs on XCD b % 8 and the tile remap of the persistent kernels assumes the
+ * same share of every XCD), so the persistent / grid-stride launches enqueued on `stream` occupy at most that many compute units and
+ * leave the rest to the kernels of other streams.  n <= 0 clears it; 1 .. 7 is MVLPT_ERR_ARG.  Results do not depend on the cap: the
+ * GEMM geometries agree bit for bit, and where two kernels do not (the persistent attention forward against one workgroup per head)
+ * the choice is made by the uncapped count.  Read on the host at enqueue time: setting and
+ * clearing it between two enqueues needs no device synchronisation and does not touch launches already enqueued.  The NULL stream
+ * cannot be capped (MVLPT_ERR_ARG). */
+int mvlpt_stream_set_cu_cap(mvlpt_stream_t stream, int n);
 
 /* Frozen weights (replaces `self.model.to(self.device)` for the CLIP towers, trainers/mvlpt.py:867, with a
  * one-time pack: 16-bit copy for the forward GEMM and a pre-transposed copy for the dX GEMM — legal because
@@ -123,6 +132,17 @@ int mvlpt_frozen_ready(void* handle);
  * layers 1..n_deep, :73-83).  feat_out [B,embed] fp32.  save_for_bwd != 0 keeps activations for image_bwd. */
 int mvlpt_image_fwd(void* handle, const void* image, int image_dtype, const float* vpt, const float* vpt_deep, int n_vpt,
                     int n_deep, int B, float* feat_out, int save_for_bwd, mvlpt_stream_t stream);
+/* The same forward in two enqueues (mvlpt_image_fwd is begin(stop_block = layers) + resume): begin carves the workspace and runs the
+ * tower entry and blocks [0, stop_block) (clamped to [0, layers]; the CLS-only last block always belongs to resume); resume runs
+ * blocks [stop_block, layers), ln_post and the projection into feat_out [B,embed], on a stream of the caller's choice — ordering the
+ * two streams is the caller's job.  The launches, their order and (on equally sized grids) their results are those of
+ * mvlpt_image_fwd.  The engine holds ONE pending forward: resume without begin, a second begin before resume and mvlpt_image_bwd in
+ * between return MVLPT_ERR_STATE without touching the device.  vpt / vpt_deep and the dropout masks must stay valid until resume has
+ * been enqueued.  mvlpt_image_fwd_abandon forgets a pending begin (its workspace is reused by the next begin; host state only). */
+int mvlpt_image_fwd_begin(void* handle, const void* image, int image_dtype, const float* vpt, const float* vpt_deep, int n_vpt,
+                          int n_deep, int B, int save_for_bwd, int stop_block, mvlpt_stream_t stream);
+int mvlpt_image_fwd_resume(void* handle, float* feat_out, mvlpt_stream_t stream);
+int mvlpt_image_fwd_abandon(void* handle);
 /* dX-only backward of the image tower: dfeat [B,embed] fp32 -> dvpt [n_vpt,dv], dvpt_deep [n_deep,n_vpt,dv]
  * (sum over the batch: prompts are `expand`ed, :75,:424).  Must follow image_fwd(save_for_bwd=1), same B. */
 int mvlpt_image_bwd(void* handle, const float* dfeat, float* dvpt, float* dvpt_deep, mvlpt_stream_t stream);

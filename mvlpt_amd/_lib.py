@@ -22,6 +22,7 @@ EPI_STORE16, EPI_GELU, EPI_RESID32, EPI_GELUBWD, EPI_STORE32, EPI_GELU_SPLIT, EP
 # kernel families mvlpt_op_gemm_route reports (MVLPT_GEMM_* in the header)
 GEMM_BT_128x128_R2, GEMM_BT_128x128_R4, GEMM_BT_256x128_R3, GEMM_BT_256x256_R2, GEMM_PHASED, GEMM_PC, GEMM_PCP = 1, 2, 3, 4, 5, 6, 7
 PREC_FAST, PREC_SPLIT_GRAD, PREC_SPLIT_ALL = 0, 1, 2
+ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4      # MVLPT_ERR_*
 TEXT_MIN_L = 3      # MVLPT_TEXT_MIN_L: the smallest sequence length mvlpt_text_encode_tokens accepts
 
 
@@ -72,9 +73,13 @@ SIGNATURES = {
     "mvlpt_stream_create_cus": (_i, [_i, _i, C.POINTER(_vp)]),
     "mvlpt_stream_destroy": (_i, [_vp]),
     "mvlpt_stream_cus": (_i, [_vp]),
+    "mvlpt_stream_set_cu_cap": (_i, [_vp, _i]),
     "mvlpt_load_frozen": (_i, [_vp, C.c_char_p, _vp, _i, C.POINTER(C.c_int64), _i, _vp]),
     "mvlpt_frozen_ready": (_i, [_vp]),
     "mvlpt_image_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "mvlpt_image_fwd_begin": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "mvlpt_image_fwd_resume": (_i, [_vp, _vp, _vp]),
+    "mvlpt_image_fwd_abandon": (_i, [_vp]),
     "mvlpt_image_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mvlpt_text_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_bwd": (_i, [_vp, _vp, _vp, _vp]),

@@ -74,6 +74,16 @@ def get_cfg_default() -> CfgNode:
         # not in the reference: compute the NEXT batch's image features underneath the current text-tower backward when
         # the method has no visual prompts (TrainerX.run_epoch reads the loader one batch ahead)
         STEP_PIPELINING=True,
+        # not in the reference: (stop_block, cu_cap).  With step pipelining, the entry and blocks [0, stop_block) of the NEXT batch's image
+        # tower are enqueued before this step's forward, on grids capped at cu_cap compute units (0: uncapped), beside the text forward;
+        # the rest of the tower follows behind the cross-entropy as before.  (0, 0): the tower in one piece behind the cross-entropy.
+        # Inert (one piece) with visual prompts, CoCoOp, a class-sharded text tower, a CU partition, the towers on one stream, and on
+        # towers with fewer than stop_block + 1 blocks.  (6, 192): the headline step -1.2 % .. -2.7 % depending on the box (profiles/r07_prefetch_split_sweep.txt);
+        # results are bit-identical either way.  MVLPT_PREFETCH_SPLIT=k:c overrides it (tools).
+        PREFETCH_SPLIT=(6, 192),
+        # the backbones (MODEL.BACKBONE.NAME) PREFETCH_SPLIT applies to; every other tower runs in one piece.  Measured: ViT-B/16 -2.1 % at
+        # B = 256 and at B = 128, but ViT-B/32 (B = 256) +2.1 % and ViT-L/14 (B = 128) +1.0 % with the same setting.  (): every backbone.
+        PREFETCH_SPLIT_TOWERS=("ViT-B/16",),
     )
     # trainers/cocoop.py's own keys (train.py:125-128), read by mvlpt_amd.cocoop (--trainer CoCoOp)
     cfg.TRAINER.COCOOP = CN(N_CTX=16, CTX_INIT="", PREC="fp16")

@@ -709,8 +709,9 @@ hipError_t launch_attn_fwd(int dtype, const AttnArgs& a_, hipStream_t s, hipEven
   if (use_stream(a.L)) return launch_attn_fwd_stream(dtype, a, s);
   // persistent variant for the headline's shape: 13 key tiles, full sequences, at least two heads per compute unit of the stream
   if (!a.causal && a.q_rows <= 0 && (a.L + 15) / 16 == PNT && (dtype == DT_F16 || dtype == DT_BF16)) {
+    // (which kernel: by the stream's compute units without a grid cap — the two differ in the last bit; how many workgroups: with it)
     const int total = a.N * a.H, cus = stream_cus(s);
-    if (total >= 2 * cus) {
+    if (total >= 2 * stream_cus_nocap(s)) {
       static bool set = false;
       if (!set) {
         hipFuncSetAttribute((const void*)attn_fwdp_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, PLDS);

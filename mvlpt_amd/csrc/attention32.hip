@@ -1279,8 +1279,8 @@ static hipError_t fwd_t(const Attn32Args& a, hipStream_t s) {
   }
   if (attn32_resident(a.L, a.causal)) {
     // persistent variant (next head's K / V land under this head's arithmetic): full-sequence launches with more heads than CUs
-    const int total = a.N * a.H, cus = stream_cus(s);
-    if (a.q_rows <= 0 && total >= 2 * cus) {
+    const int total = a.N * a.H, cus = stream_cus(s);      // (kernel by the uncapped count, grid by the capped one: see attention.hip)
+    if (a.q_rows <= 0 && total >= 2 * stream_cus_nocap(s)) {
       static bool setp = false;
       if (!setp) { set_lds(attn32p_fwd_kernel<T>, RLDS_P); setp = true; }
       hipLaunchKernelGGL((attn32p_fwd_kernel<T>), dim3(cus), dim3(RNW * 64), RLDS_P, s, a, total);

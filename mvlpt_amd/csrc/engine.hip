@@ -32,12 +32,15 @@ using namespace mvlpt;
 // ------------------------------------------------------------------------------------------------ CU-partitioned streams
 // A stream made by mvlpt_stream_create_cus only ever gets the compute units of its mask; everything that sizes a grid by
 // "resident workgroups" (persistent GEMM, grid-stride LayerNorm) asks stream_cus() instead of the device.  A handful of
-// streams per process: a linear scan under a mutex costs nothing next to a launch.
+// streams per process: a linear scan under a mutex costs nothing next to a launch.  mvlpt_stream_set_cu_cap lowers the figure for ANY
+// stream without a mask: the launches then simply use fewer workgroups and leave the other compute units to other streams.
 
 namespace {
 struct StreamPart { hipStream_t s; int cus; };
 std::mutex g_part_mu;
 std::vector<StreamPart> g_parts;
+// mvlpt_stream_set_cu_cap: a grid cap on any stream (a multiple of 8; no entry: no cap).  Host state read at enqueue time.
+std::vector<StreamPart> g_caps;
 int device_cus() {
   static int cus = 0;
   if (!cus) {
@@ -49,13 +52,18 @@ int device_cus() {
 }
 }  // namespace
 namespace mvlpt {
-int stream_cus(hipStream_t s) {
+static int stream_cus_impl(hipStream_t s, bool capped) {
+  int cus = 0, cap = 0;
   if (s) {
     std::lock_guard<std::mutex> lk(g_part_mu);
-    for (const StreamPart& p : g_parts) if (p.s == s) return p.cus;
+    for (const StreamPart& p : g_parts) if (p.s == s) { cus = p.cus; break; }
+    if (capped) for (const StreamPart& p : g_caps) if (p.s == s) { cap = p.cus; break; }
   }
-  return device_cus();
+  if (!cus) cus = device_cus();
+  return cap > 0 && cap < cus ? cap : cus;
 }
+int stream_cus(hipStream_t s) { return stream_cus_impl(s, true); }
+int stream_cus_nocap(hipStream_t s) { return stream_cus_impl(s, false); }
 }  // namespace mvlpt
 
 namespace {
@@ -186,6 +194,8 @@ struct Engine {
   int vB = 0, v_nvpt = 0, v_ndeep = 0; float* cls32 = nullptr; float* dcls32 = nullptr;
   float* xc32 = nullptr; void *ac16 = nullptr, *hc16 = nullptr, *gc16 = nullptr;   // CLS-only last layer (compact [B,·])
   // ... and what its backward needs (VPT / UPT): saved LN inputs, pre-GELU, and the compact gradient buffers
+  // mvlpt_image_fwd_begin .. mvlpt_image_fwd_resume: what crosses the cut (the rest is in vs / the v_* fields above)
+  struct ImgPending { bool active = false, packed = false, ln1_ready = false, save = false; int next = 0; const float* vpt_deep = nullptr; } ip;
   bool v_cls_last = false; float *xcm32 = nullptr, *xco32 = nullptr, *dxc32 = nullptr, *dhc32 = nullptr;
   void *uc16 = nullptr, *duc16 = nullptr, *dxc16 = nullptr, *dOc16 = nullptr;
   // text fwd extras
@@ -737,6 +747,7 @@ int mvlpt_stream_destroy(mvlpt_stream_t stream) {
   {
     std::lock_guard<std::mutex> lk(g_part_mu);
     for (size_t i = 0; i < g_parts.size(); ++i) if (g_parts[i].s == s) { g_parts.erase(g_parts.begin() + i); break; }
+    for (size_t i = 0; i < g_caps.size(); ++i) if (g_caps[i].s == s) { g_caps.erase(g_caps.begin() + i); break; }
   }
   hipError_t e = hipStreamDestroy(s);
   if (e != hipSuccess) return hipfail(nullptr, e, "hipStreamDestroy");
@@ -744,6 +755,21 @@ int mvlpt_stream_destroy(mvlpt_stream_t stream) {
 }
 
 int mvlpt_stream_cus(mvlpt_stream_t stream) { return stream_cus((hipStream_t)stream); }
+
+int mvlpt_stream_set_cu_cap(mvlpt_stream_t stream, int n) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!s) return fail(nullptr, MVLPT_ERR_ARG, "stream_set_cu_cap: the NULL stream cannot be capped");
+  if (n > 0 && n < 8) return fail(nullptr, MVLPT_ERR_ARG, "stream_set_cu_cap: a cap is at least 8 compute units (one per XCD)");
+  const int cap = n > 0 ? n / 8 * 8 : 0;      // workgroup b runs on XCD b % 8: the same share of every XCD
+  std::lock_guard<std::mutex> lk(g_part_mu);
+  for (size_t i = 0; i < g_caps.size(); ++i)
+    if (g_caps[i].s == s) {
+      if (cap > 0) g_caps[i].cus = cap; else g_caps.erase(g_caps.begin() + i);
+      return 0;
+    }
+  if (cap > 0) g_caps.push_back(StreamPart{s, cap});
+  return 0;
+}
 
 int mvlpt_set_resid_packed(void* h, int on) {
   Engine* E = (Engine*)h;
@@ -894,16 +920,56 @@ int mvlpt_frozen_ready(void* h) {
 }
 
 // ------------------------------------------------------------------------------------------------ image tower
-int mvlpt_image_fwd(void* h, const void* image, int image_dtype, const float* vpt, const float* vpt_deep, int n_vpt, int n_deep,
-                    int B, float* feat_out, int save_for_bwd, mvlpt_stream_t stream) {
+// Blocks [from, to) of the image tower at full width, each behind its deep-prompt overwrite (or skipped, see below).  Returns 1 when
+// it reaches the last block, which is CLS-only and run by mvlpt_image_fwd_resume.  `ln1_ready` is carried from block to block, and
+// across the begin / resume cut.
+static int image_blocks(Engine* E, int from, int to, bool packed, bool* ln1_ready, const float* vpt_deep, hipStream_t s) {
+  TowerState& st = E->vs;
+  const int B = E->vB, n_vpt = E->v_nvpt, n_deep = E->v_ndeep, dv = E->arch.vision_width, Lv = st.L;
+  const float* const masks = E->v_mask;
+  auto vmask = [&](int l) -> const float* { return masks ? masks + (size_t)l * B * n_vpt * dv : nullptr; };
+  // ln_1 of block l can be folded when nothing touches the residual stream between FC2 of block l-1 and it: not behind a
+  // deep-prompt overwrite, not behind a skipped block
+  auto next_foldable = [&](int l) -> const LNp* {
+    const int n = l + 1;
+    if (!st.fold || n >= E->vis.layers) return nullptr;
+    if (n_deep > 0) return nullptr;                       // rows 1..n_vpt are overwritten (or the block is skipped) in front of every later ln_1
+    return &E->vis.blocks[n].ln1;
+  };
+  for (int l = from; l < to; ++l) {
+    if (l > 0 && n_deep > 0) {
+      if (l <= n_deep) {
+        ProfScope ps(E, s, PC_GLUE, 0, (double)B * n_vpt * dv * 4.0);
+        HIPCHK(E, launch_overwrite_rows(vpt_deep + (size_t)(l - 1) * n_vpt * dv, n_vpt, st.x[2 * l], B, Lv, dv, s, vmask(l)));
+      } else {
+        // reference quirk (trainers/mvlpt.py:71-83 has no `else`): the layer is skipped entirely
+        st.skip[l] = 1;
+        if (st.saved) {
+          HIPCHK(E, hipMemcpyAsync(st.x[2 * l + 2], st.x[2 * l], (size_t)B * Lv * dv * 4, hipMemcpyDeviceToDevice, s));
+        }
+        continue;
+      }
+    }
+    if (l == E->vis.layers - 1) return 1;      // the caller runs it on the CLS rows only
+    if (packed) { if (int rc = block_fwd_packed(E, E->vis, st, l, s)) return rc; continue; }
+    bool produced = false;
+    if (int rc = block_fwd(E, E->vis, st, l, s, *ln1_ready, next_foldable(l), &produced)) return rc;
+    *ln1_ready = produced;
+  }
+  return 0;
+}
+
+int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const float* vpt, const float* vpt_deep, int n_vpt, int n_deep,
+                          int B, int save_for_bwd, int stop_block, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
-  if (!E || !image || !feat_out || B <= 0) return fail(E, MVLPT_ERR_ARG, "image_fwd: null/invalid argument");
+  if (!E || !image || B <= 0) return fail(E, MVLPT_ERR_ARG, "image_fwd: null/invalid argument");
+  if (E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_fwd_begin: a forward is pending (call image_fwd_resume or image_fwd_abandon first)");
   if (int rc = mvlpt_frozen_ready(h)) return rc;
   if ((n_vpt > 0) != (vpt != nullptr)) return fail(E, MVLPT_ERR_ARG, "image_fwd: vpt pointer and n_vpt disagree");
   if ((n_deep > 0) != (vpt_deep != nullptr) || (n_deep > 0 && n_vpt <= 0)) return fail(E, MVLPT_ERR_ARG, "image_fwd: deep prompts need vpt");
   hipStream_t s = (hipStream_t)stream;
   const MvlptArch& A = E->arch;
-  const int G = A.image_resolution / A.patch_size, G2 = G * G, dv = A.vision_width, e = A.embed_dim;
+  const int G = A.image_resolution / A.patch_size, G2 = G * G, dv = A.vision_width;
   const int Lv = 1 + n_vpt + G2;
   if (Lv > attn_max_len()) return fail(E, MVLPT_ERR_UNSUPPORTED, "image_fwd: sequence length > 256 not supported yet");
   const bool save = save_for_bwd != 0;
@@ -941,7 +1007,7 @@ int mvlpt_image_fwd(void* h, const void* image, int image_dtype, const float* vp
   if (masks && (n_vpt <= 0 || mask_layers < 1 + n_deep || mask_B != B || mask_n != n_vpt))
     return fail(E, MVLPT_ERR_ARG, "image_fwd: the prompt dropout masks do not match this forward (layers >= 1 + n_deep, batch, n_vpt)");
   E->v_mask = masks;
-  auto vmask = [&](int l) -> const float* { return masks ? masks + (size_t)l * B * n_vpt * dv : nullptr; };
+  const float* const vmask0 = masks;      // layer 0: the shallow prompts
   { ProfScope ps(E, s, PC_GLUE, 0, (double)npatch * E->Kp * 6.0);
     HIPCHK(E, launch_patchify(E->dt, image, image_dtype, patches, B, A.image_resolution, A.patch_size, E->Kp, s)); }
   if (E->dbg_ck_on) { E->dbg_ck_n = 0; if (E->dbg_ck) (void)hipMemsetAsync(E->dbg_ck, 0, DBG_CK_MAX * sizeof(unsigned long long), s); }
@@ -962,38 +1028,40 @@ int mvlpt_image_fwd(void* h, const void* image, int image_dtype, const float* vp
     dbg_ck(E, xhi, (size_t)B * Lv * dv * 3, s); dbg_ck(E, st.part[0], (size_t)B * Lv * ntp_d * 8, s);
   } else {
     ProfScope ps(E, s, PC_GLUE, 0, (double)B * Lv * dv * 8.0);
-    HIPCHK(E, launch_assemble_tokens(pe, E->cls_emb, E->vpos, E->ln_pre.g, E->ln_pre.b, vpt, n_vpt, st.x[0], B, G2, dv, s, vmask(0)));
+    HIPCHK(E, launch_assemble_tokens(pe, E->cls_emb, E->vpos, E->ln_pre.g, E->ln_pre.b, vpt, n_vpt, st.x[0], B, G2, dv, s, vmask0));
   }
-  bool cls_only_last = false;
+  // blocks [0, stop_block); the last block (CLS rows only) always belongs to resume
+  const int stop = std::min(std::max(stop_block, 0), E->vis.layers - 1);
   bool ln1_ready = packed;      // LayerNorm folding: the previous block's FC2 left this block's ln_1 input in folded form
-  // ln_1 of block l can be folded when nothing touches the residual stream between FC2 of block l-1 and it: not behind a
-  // deep-prompt overwrite, not behind a skipped block
-  auto next_foldable = [&](int l) -> const LNp* {
-    const int n = l + 1;
-    if (!st.fold || n >= E->vis.layers) return nullptr;
-    if (n_deep > 0) return nullptr;                       // rows 1..n_vpt are overwritten (or the block is skipped) in front of every later ln_1
-    return &E->vis.blocks[n].ln1;
-  };
-  for (int l = 0; l < E->vis.layers; ++l) {
-    if (l > 0 && n_deep > 0) {
-      if (l <= n_deep) {
-        ProfScope ps(E, s, PC_GLUE, 0, (double)B * n_vpt * dv * 4.0);
-        HIPCHK(E, launch_overwrite_rows(vpt_deep + (size_t)(l - 1) * n_vpt * dv, n_vpt, st.x[2 * l], B, Lv, dv, s, vmask(l)));
-      } else {
-        // reference quirk (trainers/mvlpt.py:71-83 has no `else`): the layer is skipped entirely
-        st.skip[l] = 1;
-        if (st.saved) {
-          HIPCHK(E, hipMemcpyAsync(st.x[2 * l + 2], st.x[2 * l], (size_t)B * Lv * dv * 4, hipMemcpyDeviceToDevice, s));
-        }
-        continue;
-      }
-    }
-    if (l == E->vis.layers - 1) { cls_only_last = true; break; }
-    if (packed) { if (int rc = block_fwd_packed(E, E->vis, st, l, s)) return rc; continue; }
-    bool produced = false;
-    if (int rc = block_fwd(E, E->vis, st, l, s, ln1_ready, next_foldable(l), &produced)) return rc;
-    ln1_ready = produced;
-  }
+  if (int rc = image_blocks(E, 0, stop, packed, &ln1_ready, vpt_deep, s)) return rc;
+  E->ip.active = true; E->ip.packed = packed; E->ip.ln1_ready = ln1_ready; E->ip.save = save; E->ip.next = stop; E->ip.vpt_deep = vpt_deep;
+  return 0;
+}
+
+int mvlpt_image_fwd_abandon(void* h) {
+  Engine* E = (Engine*)h;
+  if (!E) return MVLPT_ERR_ARG;
+  if (E->ip.active) { E->ip.active = false; E->vs.valid = false; }
+  return 0;
+}
+
+int mvlpt_image_fwd_resume(void* h, float* feat_out, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !feat_out) return fail(E, MVLPT_ERR_ARG, "image_fwd_resume: null argument");
+  if (!E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_fwd_resume: call image_fwd_begin first");
+  E->ip.active = false;
+  hipStream_t s = (hipStream_t)stream;
+  TowerState& st = E->vs;
+  const MvlptArch& A = E->arch;
+  const int B = E->vB, dv = A.vision_width, e = A.embed_dim, Lv = st.L;
+  const bool save = E->ip.save, packed = E->ip.packed;
+  const size_t X = st.exact ? 2 : 1;
+  void* const xhi = st.x[0];
+  uint8_t* const xlo = (uint8_t*)st.x[0] + (size_t)B * Lv * dv * 2;
+  bool ln1_ready = E->ip.ln1_ready;
+  const int rest = image_blocks(E, E->ip.next, E->vis.layers, packed, &ln1_ready, E->ip.vpt_deep, s);
+  if (rest < 0) { st.valid = false; return rest; }
+  const bool cls_only_last = rest == 1;
   if (cls_only_last) {
     // Only x[:, 0, :] of the last block is consumed (trainers/mvlpt.py:88): keys/values are still needed for every
     // token, but queries, out-proj, ln_2 and the MLP are evaluated for the CLS row only (B rows instead of B*Lv: ~20/24
@@ -1042,10 +1110,19 @@ int mvlpt_image_fwd(void* h, const void* image, int image_dtype, const float* vp
   return 0;
 }
 
+int mvlpt_image_fwd(void* h, const void* image, int image_dtype, const float* vpt, const float* vpt_deep, int n_vpt, int n_deep,
+                    int B, float* feat_out, int save_for_bwd, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !image || !feat_out || B <= 0) return fail(E, MVLPT_ERR_ARG, "image_fwd: null/invalid argument");
+  if (int rc = mvlpt_image_fwd_begin(h, image, image_dtype, vpt, vpt_deep, n_vpt, n_deep, B, save_for_bwd, E->vis.layers, stream)) return rc;
+  return mvlpt_image_fwd_resume(h, feat_out, stream);
+}
+
 int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !dfeat) return fail(E, MVLPT_ERR_ARG, "image_bwd: null argument");
   TowerState& st = E->vs;
+  if (E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_bwd: a forward is pending between image_fwd_begin and image_fwd_resume");
   if (!st.valid || !st.saved) return fail(E, MVLPT_ERR_STATE, "image_bwd: call image_fwd(save_for_bwd=1) first");
   if ((E->v_nvpt > 0 && !dvpt) || (E->v_ndeep > 0 && !dvpt_deep)) return fail(E, MVLPT_ERR_ARG, "image_bwd: missing gradient output");
   hipStream_t s = (hipStream_t)stream;

@@ -12,6 +12,10 @@ namespace mvlpt {
 // Compute units the kernels of `s` can run on: the partition size for a stream made by mvlpt_stream_create_cus, the whole
 // device otherwise.  Persistent / grid-stride launchers size their grids from it.
 int stream_cus(hipStream_t s);
+// The same without the grid cap of mvlpt_stream_set_cu_cap.  A launcher that chooses between two kernels whose results differ in the
+// last bit (the persistent attention forward against one workgroup per head) chooses by THIS count and sizes the grid by stream_cus:
+// a cap then changes how many workgroups run, never which arithmetic.
+int stream_cus_nocap(hipStream_t s);
 
 // ---------------------------------------------------------------- GEMM  C = A * Bt^T (+ epilogue)
 enum GemmEpi {

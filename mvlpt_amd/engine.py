@@ -60,6 +60,17 @@ def device_cus(device: torch.device) -> int:
         return int(lib.mvlpt_stream_cus(None))
 
 
+def set_stream_cu_cap(stream: "torch.cuda.Stream", n: int) -> None:
+    """Grid cap of `stream` (mvlpt_stream_set_cu_cap): persistent / grid-stride launches enqueued on it from now on occupy at most
+    n (rounded down to a multiple of 8) compute units; n <= 0 clears it.  Host state: no synchronisation."""
+    _lib.check(lib.mvlpt_stream_set_cu_cap(C.c_void_p(stream.cuda_stream), int(n)), None, "stream_set_cu_cap")
+
+
+def stream_cus(stream: Optional["torch.cuda.Stream"] = None) -> int:
+    """Compute units the launchers size the grids of `stream` (default: the current one) by (mvlpt_stream_cus)."""
+    return int(lib.mvlpt_stream_cus(C.c_void_p(stream.cuda_stream) if stream is not None else _stream()))
+
+
 def _host_ranges(class_lo, class_hi, G: int, n_cls: int):
     """Host class ranges -> (int32 ctypes arrays lo, hi, S).  Checked here as well as in the library; never touches the device."""
     if any(isinstance(t, torch.Tensor) and t.is_cuda for t in (class_lo, class_hi)):
@@ -106,6 +117,7 @@ class Engine:
         self.precision = _lib.PREC_SPLIT_GRAD
         self._keep: List[torch.Tensor] = []     # tensors the library reads asynchronously / later
         self._img_state = None
+        self._img_pending = None      # image_fwd_begin .. image_fwd_resume: (image, vpt, vpt_deep, masks, state for image_bwd)
         self._txt_state = None
         self._head_state = None
 
@@ -183,9 +195,7 @@ class Engine:
             _lib.check(lib.mvlpt_frozen_ready(self.h), self.h, "frozen_ready")
 
     # ------------------------------------------------------------------ towers
-    @_on_device
-    def image_fwd(self, image: torch.Tensor, vpt: Optional[torch.Tensor] = None, vpt_deep: Optional[torch.Tensor] = None,
-                  save_for_bwd: bool = False) -> torch.Tensor:
+    def _image_args(self, image, vpt, vpt_deep):
         if image.dtype not in _TORCH2DT:
             image = image.float()
         image = image.contiguous()
@@ -202,6 +212,12 @@ class Engine:
         if vpt_deep is not None:
             vpt_deep = _req(vpt_deep, torch.float32, "vpt_deep")
             n_deep = vpt_deep.shape[0]
+        return image, vpt, vpt_deep, n_vpt, n_deep, B, m
+
+    @_on_device
+    def image_fwd(self, image: torch.Tensor, vpt: Optional[torch.Tensor] = None, vpt_deep: Optional[torch.Tensor] = None,
+                  save_for_bwd: bool = False) -> torch.Tensor:
+        image, vpt, vpt_deep, n_vpt, n_deep, B, m = self._image_args(image, vpt, vpt_deep)
         feat = torch.empty(B, self.arch.embed_dim, device=image.device, dtype=torch.float32)
         _lib.check(lib.mvlpt_image_fwd(self.h, _ptr(image), _TORCH2DT[image.dtype], _ptr(vpt), _ptr(vpt_deep), n_vpt, n_deep, B,
                                        _ptr(feat), int(save_for_bwd), _stream()), self.h, "image_fwd")
@@ -209,6 +225,44 @@ class Engine:
         # the setting was one-shot: this forward consumed it; its backward reads the buffer, so the tensor stays alive until then
         self._vpt_masks_saved, self._vpt_masks = (m if save_for_bwd else None), None
         return feat
+
+    @_on_device
+    def image_fwd_begin(self, image: torch.Tensor, vpt: Optional[torch.Tensor] = None, vpt_deep: Optional[torch.Tensor] = None,
+                        save_for_bwd: bool = False, stop_block: Optional[int] = None) -> None:
+        """First part of image_fwd on the current stream (mvlpt_image_fwd_begin): the tower entry and blocks [0, stop_block);
+        None: everything ahead of the last block.  image_fwd_resume finishes the forward; the engine holds one pending forward."""
+        image, vpt, vpt_deep, n_vpt, n_deep, B, m = self._image_args(image, vpt, vpt_deep)
+        stop = self.arch.vision_layers if stop_block is None else int(stop_block)
+        _lib.check(lib.mvlpt_image_fwd_begin(self.h, _ptr(image), _TORCH2DT[image.dtype], _ptr(vpt), _ptr(vpt_deep), n_vpt, n_deep, B,
+                                             int(save_for_bwd), stop, _stream()), self.h, "image_fwd_begin")
+        self._img_state = None
+        # resume still reads the image-side inputs (deep prompts, masks): they stay alive until then
+        self._img_pending = (image, vpt, vpt_deep, m, (n_vpt, n_deep, B) if save_for_bwd else None)
+        self._vpt_masks = None
+
+    @_on_device
+    def image_fwd_resume(self) -> torch.Tensor:
+        """Second part of the pending forward on the current stream (mvlpt_image_fwd_resume) -> features [B, embed] fp32.  The caller
+        orders this stream behind the one image_fwd_begin ran on."""
+        pend = self._img_pending
+        if pend is None:
+            raise RuntimeError("image_fwd_resume without image_fwd_begin")
+        image, _vpt, _deep, m, state = pend
+        feat = torch.empty(image.shape[0], self.arch.embed_dim, device=image.device, dtype=torch.float32)
+        self._img_pending = None
+        _lib.check(lib.mvlpt_image_fwd_resume(self.h, _ptr(feat), _stream()), self.h, "image_fwd_resume")
+        self._img_state = state
+        self._vpt_masks_saved = m if state is not None else None
+        return feat
+
+    def image_fwd_pending(self) -> bool:
+        return self._img_pending is not None
+
+    def image_fwd_abandon(self) -> None:
+        """Forget a pending image_fwd_begin (mvlpt_image_fwd_abandon): host state only; the next begin reuses the workspace, so
+        the caller orders it behind whatever the abandoned part enqueued."""
+        _lib.check(lib.mvlpt_image_fwd_abandon(self.h), self.h, "image_fwd_abandon")
+        self._img_pending = None
 
     @_on_device
     def image_bwd(self, dfeat: torch.Tensor) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:

@@ -508,7 +508,12 @@ class _PromptedClipFn(torch.autograd.Function):
         run_text = not ((coop_emb is None or cached_eval) and model._const_text_features is not None)
         suffix, layout = _text_inputs(model, pl, pl.coop_n_ctx)
         # features computed ahead of time (prefetch_image_features), keyed by the tensor they belong to
-        pre = model._prefetched.pop((image.data_ptr(), tuple(image.shape), image._version), None) if vpt_emb is None else None
+        key = (image.data_ptr(), tuple(image.shape), image._version)
+        if model._pending is not None and (vpt_emb is not None or key not in model._prefetched):
+            # a tower begun under the prefetch split that nobody resumed (the loop left the loader early), or begun for THIS tensor:
+            # it is finished before this forward uses the engine's one image-tower state
+            model._resume_pending()
+        pre = model._prefetched.pop(key, None) if vpt_emb is None else None
         if pre is not None:
             def image_fwd(*_a, **_k):
                 torch.cuda.current_stream().wait_event(pre[1])
@@ -656,6 +661,8 @@ class CustomCLIP(nn.Module):
         self._prefetch_stream = None
         self._prefetched = {}                     # (data_ptr, shape, version) of an image tensor -> (features, event, the tensor:
                                                   # holding it pins its storage, so the pointer cannot be handed to another batch)
+        self._pending = None                      # prefetch split: (key, image, event behind the first part) of the tower begun
+        self.prefetch_split = (0, 0)              # (stop_block, cu_cap) of TRAINER.MVLPT.PREFETCH_SPLIT; (0, 0): one piece
         self._fwd_generation = 0
         # MVLPT_TEXT_PRIORITY=1 (experiment): the text tower's stream above, the image prefetch stream below the default priority
         self._prio = os.environ.get("MVLPT_TEXT_PRIORITY", "0") != "0"
@@ -709,13 +716,42 @@ class CustomCLIP(nn.Module):
         self._prefetch_stream = partition_stream(dev, text_cus, total - text_cus)
         self.text_cus = text_cus
 
-    def prefetch_image_features(self, image) -> bool:
+    def split_active(self) -> bool:
+        """The prefetch split applies: a split is set and nothing makes today's schedule the only one (the towers on one stream,
+        visual prompts, a class-sharded text tower, a CU partition, a tower with fewer blocks than the split point)."""
+        layers = getattr(getattr(self.engine, "arch", None), "vision_layers", 0)
+        # (a split point past the last full-width block is not a split of THIS tower: a default found on twelve blocks leaves a
+        # two-block test tower in one piece; stop_block = layers - 1 is the old early-prefetch schedule, kept as the control)
+        return (0 < self.prefetch_split[0] <= layers - 1 and self.overlap_towers and self._side_stream is not None
+                and self._class_shard is None and self.text_cus == 0 and self.prompt_learner.vpt_embeddings is None)
+
+    def has_prefetched(self, image) -> bool:
+        return (image.data_ptr(), tuple(image.shape), image._version) in self._prefetched
+
+    def _resume_pending(self) -> None:
+        """Second part of the tower begun by prefetch_image_features(stop_block=...): uncapped, on the prefetch stream."""
+        key, image, _ = self._pending
+        self._pending = None
+        st = self._prefetch_stream
+        with torch.cuda.stream(st):
+            feat = self.engine.image_fwd_resume()
+            ev = torch.cuda.Event()
+            ev.record(st)
+        if len(self._prefetched) >= 4:
+            self._prefetched.pop(next(iter(self._prefetched)))
+        self._prefetched[key] = (feat, ev, image)
+
+    def prefetch_image_features(self, image, stop_block=None, cu_cap=None) -> bool:
         """Software pipelining across steps: with no visual prompts the image tower is a pure function of the image
         (frozen weights, trainers/mvlpt.py:855-858), so the features of the NEXT batch are computed on a third HIP stream
         beside the current step's text tower (forward, backward: small launches that cannot fill the chip), head and
         optimizer.  `forward(image)` picks the result up when it is called with the same tensor.  Successive prefetches
         queue up on that one stream (they share the tower workspace), so the trainer can issue the one for batch i+1 BEFORE
-        step i's own forward: the image stream then never waits for a step's logits."""
+        step i's own forward: the image stream then never waits for a step's logits.
+
+        Prefetch split: with `stop_block` > 0 only the tower entry and blocks [0, stop_block) are enqueued, with their grids capped
+        at `cu_cap` compute units (0 / None: uncapped) so that they leave the rest of the chip to the text forward they run beside;
+        a second call for the same tensor enqueues the rest, uncapped, behind whatever the main stream holds at that point."""
         pl = self.prompt_learner
         if pl.vpt_embeddings is not None or self._side_stream is None:
             return False
@@ -731,6 +767,25 @@ class CustomCLIP(nn.Module):
         ready = torch.cuda.Event()
         ready.record(main)
         st.wait_event(ready)
+        if self._pending is not None:
+            # the second call for the tensor whose tower was begun — or a tower begun for a tensor nobody came back for
+            mine = self._pending[0] == key
+            self._resume_pending()
+            if mine:
+                return True
+        if stop_block and self.split_active():
+            from .engine import set_stream_cu_cap
+            with torch.cuda.stream(st):
+                set_stream_cu_cap(st, int(cu_cap or 0))
+                try:
+                    self.engine.image_fwd_begin(image, None, None, save_for_bwd=False, stop_block=int(stop_block))
+                finally:
+                    set_stream_cu_cap(st, 0)
+                ev = torch.cuda.Event()
+                ev.record(st)
+            image.record_stream(st)
+            self._pending = (key, image, ev)
+            return True
         with torch.cuda.stream(st):
             feat = self.engine.image_fwd(image, None, None, save_for_bwd=False)
             ev = torch.cuda.Event()
@@ -743,7 +798,12 @@ class CustomCLIP(nn.Module):
 
     def drop_prefetch(self) -> None:
         """Forget prefetched image forwards that nobody will pick up (the loop left the loader early): the main stream
-        waits for the side stream so that the image-tower workspace is quiescent for whatever runs next."""
+        waits for the side stream so that the image-tower workspace is quiescent for whatever runs next.  A tower that was
+        begun and not resumed is given up: the next forward carves the workspace anew, behind the first part."""
+        if self._pending is not None:
+            self.engine.image_fwd_abandon()
+            torch.cuda.current_stream().wait_event(self._pending[2])
+            self._pending = None
         pre, self._prefetched = self._prefetched, {}
         for entry in pre.values():
             torch.cuda.current_stream().wait_event(entry[1])

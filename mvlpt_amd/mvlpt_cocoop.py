@@ -288,8 +288,11 @@ class CustomCLIP(nn.Module):
             raise NotImplementedError("class sharding does not apply to the COCOOP.N_CTX != 0 route: every image has its own text "
                                       "features, there is no shared [n_cls, e] matrix to shard")
 
-    def prefetch_image_features(self, image) -> bool:
+    def prefetch_image_features(self, image, stop_block=None, cu_cap=None) -> bool:
         """Step pipelining is off on this route (the image features feed meta_net, and with visual prompts they are not constants)."""
+        return False
+
+    def split_active(self) -> bool:
         return False
 
     def drop_prefetch(self) -> None:

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import math
 import os
+import re
 import os.path as osp
 import time
 from collections import OrderedDict
@@ -131,6 +132,23 @@ def build_lr_scheduler(optim, optim_cfg):
 # Measured (NOTES_experiments.md, round 4): enqueued early the image stream never waits for a step's logits, but the step gets no
 # shorter — 14.18-14.21 vs 14.11-14.12 ms in the same run: what bounds the step is the work of the two towers, not that bubble.
 _PREFETCH_EARLY = os.environ.get("MVLPT_PREFETCH_EARLY", "0") != "0"
+
+
+def prefetch_split(cfg) -> tuple:
+    """(stop_block, cu_cap) of the prefetch split: MVLPT_PREFETCH_SPLIT=k:c when set (any backbone), else TRAINER.MVLPT.PREFETCH_SPLIT
+    on the backbones of TRAINER.MVLPT.PREFETCH_SPLIT_TOWERS and (0, 0) on every other."""
+    env = os.environ.get("MVLPT_PREFETCH_SPLIT", "")
+    if env:
+        m = re.fullmatch(r"\s*(\d+)\s*:\s*(\d+)\s*", env)
+        if m is None:
+            raise ValueError(f"MVLPT_PREFETCH_SPLIT={env!r}: expected k:c, two non-negative integers (stop_block:cu_cap, e.g. 6:192; "
+                             "0:0 keeps the image tower in one piece)")
+        return int(m.group(1)), int(m.group(2))
+    towers = tuple(cfg.TRAINER.MVLPT.PREFETCH_SPLIT_TOWERS)
+    if towers and cfg.MODEL.BACKBONE.NAME not in towers:      # measured to pay on the listed backbones only
+        return 0, 0
+    k, c = cfg.TRAINER.MVLPT.PREFETCH_SPLIT
+    return max(int(k), 0), max(int(c), 0)
 
 
 class TrainerX:
@@ -489,6 +507,7 @@ class MVLPT(TrainerX):
                 prec = "split_all"
         clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec)
         self.model = model_cls(cfg, classnames, clip_model, dm=self.dm, pretokenized=pretok)
+        self.model.prefetch_split = prefetch_split(cfg)
         for name, param in self.model.named_parameters():               # :855-858 (the towers hold no nn.Parameters)
             if "prompt_learner" not in name:
                 param.requires_grad_(False)
@@ -515,18 +534,28 @@ class MVLPT(TrainerX):
             label = label.float()
             label = label / label.sum(dim=-1, keepdim=True)
         early = next_batch is not None and _PREFETCH_EARLY
-        if early:
+        # prefetch split (TRAINER.MVLPT.PREFETCH_SPLIT): only the first blocks of batch i+1's tower go in front of this step's forward,
+        # on capped grids beside the text forward; the rest follows behind the cross-entropy.  Only when this step's own features
+        # are there already (from the second step on): a forward that has to run its tower first gains nothing from it.
+        stop_block, cu_cap = getattr(self.model, "prefetch_split", (0, 0))
+        split = (next_batch is not None and not early and stop_block > 0 and self.model.split_active()
+                 and self.model.has_prefetched(image))
+        if early or split:
             # batch i+1: its H2D copy and its image tower are enqueued BEFORE step i's own forward, so the image stream
             # goes from one batch straight into the next while this step's text tower, head and optimizer run beside it
             parsed = self.parse_batch_train(next_batch)
             self._parsed_ahead = (next_batch, parsed)
-            self.model.prefetch_image_features(parsed[0])
+            if split:
+                self.model.prefetch_image_features(parsed[0], stop_block=stop_block, cu_cap=cu_cap)
+            else:
+                self.model.prefetch_image_features(parsed[0])
         output = self.model(image, task=tasks_)
         loss = self.model.cross_entropy(output, label)                  # F.cross_entropy (:931) as a HIP kernel
         if next_batch is not None and not early:                        # the H2D copy of batch i+1 and its image tower overlap this step's backward
-            parsed = self.parse_batch_train(next_batch)
-            self._parsed_ahead = (next_batch, parsed)
-            self.model.prefetch_image_features(parsed[0])
+            if not split:
+                parsed = self.parse_batch_train(next_batch)
+                self._parsed_ahead = (next_batch, parsed)
+            self.model.prefetch_image_features(parsed[0])               # (prefetch split: the rest of the tower begun above)
         self.model_backward_and_update(loss)
         # device tensors: no .item() sync inside the step (the reference syncs twice per step, :941-942)
         loss_summary = {"loss": loss.detach(), "acc": self.model.last_ncorrect[0] * (100.0 / output.shape[0])}

@@ -34,7 +34,8 @@ def wrap(obj, name, label=None):
         return r
     setattr(obj, name, g)
 
-for n in ("text_fwd", "image_fwd", "logits_fwd", "cross_entropy", "logits_bwd", "text_bwd"):
+# (prefetch split, MVLPT_PREFETCH_SPLIT=k:c: the tower of the next batch shows as image_fwd_begin + image_fwd_resume)
+for n in ("text_fwd", "image_fwd", "image_fwd_begin", "image_fwd_resume", "logits_fwd", "cross_entropy", "logits_bwd", "text_bwd"):
     wrap(eng, n)
 wrap(tr, "model_zero_grad", "zero_grad")
 wrap(tr, "model_update", "optimizer")

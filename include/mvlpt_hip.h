@@ -420,6 +420,37 @@ typedef struct MvlptOptimHyper {
 int mvlpt_op_optim_step(const MvlptOptimHyper* hyper, float* param, const float* grad, float* state1, float* state2, int64_t n,
                         const MvlptOptimSeg* segs_dev, int n_segs, const float* loss_dev, int32_t* skipped_dev, mvlpt_stream_t stream);
 
+/* ---- prompt interpretation: the nearest vocabulary tokens of context vectors (row i of the scope table; tests/test_hip_nearest.py) ----
+ * Replaces `torch.cdist(ctx, token_embedding)` + `torch.argsort(distance, dim=1)[:, :topk]` (scripts/interpret_prompt.py:49-59) with a
+ * fused distance + top-k: for every row of q [R, d] fp32 the k rows of table [V, d] fp32 (row-major) with the smallest Euclidean
+ * distance, ascending, into idx int32 [R, k] and dist fp32 [R, k].  No [R, V] array exists at any point; the scratch memory is partial
+ * lists of k (distance, index) pairs per row, mvlpt_nearest_workspace_bytes of them.
+ *   Distance: s = sum_i (q_i - e_i)^2 in the difference form (never |q|^2 + |e|^2 - 2 q.e, which cancels), fp32, the d terms of a
+ *     (row, token) pair added in the order i = 0 .. d-1 whatever the pair's place in the table, the row tile, the vocabulary slice or
+ *     the grid; dist = sqrtf(s), correctly rounded.  So |dist - exact| <= (d / 2 + 3) * 2^-24 * exact, a query that is a copy of a
+ *     table row is at distance exactly 0.0, bitwise copies of a table row tie exactly, and the results do not depend on the stream's
+ *     compute units (mvlpt_stream_create_cus, mvlpt_stream_set_cu_cap) or on a rerun.
+ *   Order: the key is (s, token index): smaller s first, equal s by smaller index (torch.argsort leaves ties open).  A NaN s orders
+ *     behind every number, +inf included, as torch.sort places it; NaNs among themselves by index.  A query row of NaN or of +-inf
+ *     therefore returns tokens 0 .. k-1 with NaN / +inf distances, and a table row that holds a NaN is returned only when fewer than
+ *     k other rows exist.  The selection is exact on this order: nothing is sampled or approximated.
+ *   Limits: R >= 1, V >= 1, 1 <= k <= min(V, MVLPT_NEAREST_MAX_K), d % 4 == 0, 4 <= d <= 1024, R <= MVLPT_NEAREST_MAX_ROWS (the row
+ *     tile rides on grid.y; callers chunk R), q / table 16-byte aligned.  Every violation, a NULL pointer and a workspace below
+ *     mvlpt_nearest_workspace_bytes return MVLPT_ERR_ARG (k > MVLPT_NEAREST_MAX_K: MVLPT_ERR_UNSUPPORTED) before anything is launched;
+ *     the outputs are not touched.
+ * mvlpt_nearest_workspace_bytes: *out = bytes mvlpt_op_nearest_rows needs for these sizes on `stream` (the number of vocabulary
+ *   slices follows mvlpt_stream_cus(stream) so that R = 16 still fills the device: ask again after the stream's cap has changed).
+ * mvlpt_op_nearest_rows: the kernel-level entry, handle-free (errors: mvlpt_last_error(NULL)); the caller owns `workspace`;
+ *   enqueue-only on `stream`.
+ * mvlpt_nearest_tokens: the same against the engine's resident "token_embedding.weight" (d = text_width, V = vocab), scratch from the
+ *   engine's grow-only workspace; MVLPT_ERR_STATE when the table has not been passed to mvlpt_load_frozen. */
+enum { MVLPT_NEAREST_MAX_K = 64 };
+enum { MVLPT_NEAREST_MAX_ROWS = 65535 * 8 };
+int mvlpt_nearest_workspace_bytes(int R, int V, int d, int k, mvlpt_stream_t stream, int64_t* out);
+int mvlpt_op_nearest_rows(const float* q, const float* table, int R, int V, int d, int k, int32_t* idx, float* dist, void* workspace,
+                          int64_t workspace_bytes, mvlpt_stream_t stream);
+int mvlpt_nearest_tokens(void* handle, const float* q, int R, int k, int32_t* idx, float* dist, mvlpt_stream_t stream);
+
 /* ---- input pipeline ("next" row f3 of the scope table) -------------------------------------------------------
  * Replaces the per-image CPU transform the reference runs in DataLoader workers: Dassl `build_transform` with
  * INPUT.TRANSFORMS = random_resized_crop / random_flip / normalize, INTERPOLATION bicubic, CLIP PIXEL_MEAN/STD

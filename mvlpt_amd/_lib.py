@@ -23,6 +23,7 @@ EPI_STORE16, EPI_GELU, EPI_RESID32, EPI_GELUBWD, EPI_STORE32, EPI_GELU_SPLIT, EP
 GEMM_BT_128x128_R2, GEMM_BT_128x128_R4, GEMM_BT_256x128_R3, GEMM_BT_256x256_R2, GEMM_PHASED, GEMM_PC, GEMM_PCP = 1, 2, 3, 4, 5, 6, 7
 PREC_FAST, PREC_SPLIT_GRAD, PREC_SPLIT_ALL = 0, 1, 2
 ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4      # MVLPT_ERR_*
+NEAREST_MAX_K, NEAREST_MAX_ROWS = 64, 65535 * 8      # MVLPT_NEAREST_MAX_K, MVLPT_NEAREST_MAX_ROWS
 TEXT_MIN_L = 3      # MVLPT_TEXT_MIN_L: the smallest sequence length mvlpt_text_encode_tokens accepts
 
 
@@ -138,6 +139,9 @@ SIGNATURES = {
     "mvlpt_op_overwrite_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
     "mvlpt_op_assemble_tokens": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "mvlpt_op_assemble_prompts": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mvlpt_nearest_workspace_bytes": (_i, [_i, _i, _i, _i, _vp, C.POINTER(C.c_int64)]),
+    "mvlpt_op_nearest_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_int64, _vp]),
+    "mvlpt_nearest_tokens": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "mvlpt_preprocess": (_i, [_vp, _vp, C.c_int64, C.POINTER(MvlptImageDesc), _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _i, _vp, _vp]),
     "mvlpt_profile_begin": (_i, [_vp, _i]),
     "mvlpt_profile_pause": (_i, [_vp, _i]),

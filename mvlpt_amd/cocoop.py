@@ -183,6 +183,19 @@ class CustomCLIP(nn.Module):
         self.last_chunks = -(-B // step)
         return out
 
+    @torch.no_grad()
+    def image_contexts(self, image) -> torch.Tensor:
+        """ctx + meta_net(image features) [B, n_ctx, ctx_dim]: the contexts the text tower sees for these images (:178, :147-161).
+        The prompt-free image tower keeps nothing for a backward on this route, so the call disturbs no pending backward."""
+        img = self.engine.image_fwd(image.to(self.clip_model.device), None, None, save_for_bwd=False)
+        return self.prompt_learner(img / img.norm(dim=-1, keepdim=True))
+
+    def interpret_images(self, images, topk: int = 5):
+        """Nearest vocabulary words of every image's own contexts: [B][n_ctx] lists of (word, distance), B * n_ctx rows in ONE
+        nearest-token call (mvlpt_amd.interpret)."""
+        from .interpret import nearest_words
+        return nearest_words(self.clip_model, self.image_contexts(images), topk)
+
     def forward(self, image, label=None):
         """CE loss when `prompt_learner.training` (trainers/cocoop.py:191-192), the [B, n_cls] logits otherwise."""
         img = self.engine.image_fwd(image, None, None, save_for_bwd=False)          # frozen, prompt-free image tower
@@ -255,6 +268,10 @@ class CoCoOp(MVLPT):
     @torch.no_grad()
     def model_inference(self, input, task=None):
         return self.model(input)
+
+    def interpret_images(self, images, topk: int = 5):
+        """Nearest vocabulary words of ctx + meta_net(image features) per image (CustomCLIP.interpret_images); never called by the loop."""
+        return self.model.interpret_images(images, topk)
 
     def load_model(self, directory, epoch=None):
         """:286-315 (token_prefix / token_suffix are dropped: they come from the current class names)."""

@@ -188,7 +188,7 @@ struct Engine {
   // token embedding [vocab, text_width] fp32: kept only when the caller loads it (mvlpt_text_encode_tokens reads it)
   float* tok_emb = nullptr; int vocab = 0;
   std::vector<void*> owned;               // every weight allocation (freed in destroy)
-  DevBuf vis_ws, txt_ws, head_ws, ce_ws, tmp, pp_ws;
+  DevBuf vis_ws, txt_ws, head_ws, ce_ws, tmp, pp_ws, near_ws;
   TowerState vs, ts;
   // vision fwd extras (carved from vis_ws)
   int vB = 0, v_nvpt = 0, v_ndeep = 0; float* cls32 = nullptr; float* dcls32 = nullptr;
@@ -820,7 +820,7 @@ int mvlpt_trim(void* h) {
   Engine* E = (Engine*)h;
   if (!E) return MVLPT_ERR_ARG;
   HIPCHK(E, hipDeviceSynchronize());       // epoch boundary: a host-side pause is acceptable here, never inside a step
-  for (DevBuf* b : {&E->vis_ws, &E->txt_ws, &E->head_ws, &E->ce_ws, &E->tmp, &E->pp_ws}) (void)b->trim();
+  for (DevBuf* b : {&E->vis_ws, &E->txt_ws, &E->head_ws, &E->ce_ws, &E->tmp, &E->pp_ws, &E->near_ws}) (void)b->trim();
   return 0;
 }
 
@@ -1986,6 +1986,55 @@ int mvlpt_op_normalize_rows(const float* x, float* xn, float* norm, int rows, in
   if (!x || !xn || !norm || rows <= 0 || d <= 0) { g_create_err = "op_normalize_rows: null/invalid argument"; return MVLPT_ERR_ARG; }
   OPCHK(launch_normalize_rows(x, xn, norm, rows, d, (hipStream_t)stream));
   return 0;
+}
+
+// ------------------------------------------------------------------------------------------------ prompt interpretation
+// Every limit of include/mvlpt_hip.h is checked here, before a launch: the kernels (nearest.hip) trust their arguments.
+static int nearest_check(const char* who, int R, int V, int d, int k, std::string* msg) {
+  auto bad = [&](int code, const char* what) { *msg = std::string(who) + ": " + what; return code; };
+  if (R < 1 || V < 1) return bad(MVLPT_ERR_ARG, "R and V must be at least 1");
+  if (k > MVLPT_NEAREST_MAX_K) return bad(MVLPT_ERR_UNSUPPORTED, "k exceeds MVLPT_NEAREST_MAX_K");
+  if (k < 1 || k > V) return bad(MVLPT_ERR_ARG, "k must lie in [1, min(V, MVLPT_NEAREST_MAX_K)]");
+  if (d < 4 || d % 4 || d > 1024) return bad(MVLPT_ERR_ARG, "d must be a multiple of 4 in [4, 1024]");
+  if (R > MVLPT_NEAREST_MAX_ROWS) return bad(MVLPT_ERR_ARG, "R exceeds MVLPT_NEAREST_MAX_ROWS (chunk the rows)");
+  return 0;
+}
+static int nearest_run(const char* who, const float* q, const float* table, int R, int V, int d, int k, int32_t* idx, float* dist,
+                       void* ws, const NearestPlan& p, hipStream_t s, std::string* msg) {
+  if ((((uintptr_t)q | (uintptr_t)table) & 15) != 0) { *msg = std::string(who) + ": q and table must be 16-byte aligned"; return MVLPT_ERR_ARG; }
+  const hipError_t e = launch_nearest_rows(q, table, R, V, d, k, idx, dist, ws, p, s);
+  if (e != hipSuccess) { *msg = std::string(who) + ": " + hipGetErrorString(e); return MVLPT_ERR_HIP; }
+  return 0;
+}
+int mvlpt_nearest_workspace_bytes(int R, int V, int d, int k, mvlpt_stream_t stream, int64_t* out) {
+  if (!out) { g_create_err = "nearest_workspace_bytes: null argument"; return MVLPT_ERR_ARG; }
+  if (int rc = nearest_check("nearest_workspace_bytes", R, V, d, k, &g_create_err)) return rc;
+  *out = (int64_t)nearest_plan(R, V, k, stream_cus((hipStream_t)stream)).ws_bytes;
+  return 0;
+}
+int mvlpt_op_nearest_rows(const float* q, const float* table, int R, int V, int d, int k, int32_t* idx, float* dist, void* workspace,
+                          int64_t workspace_bytes, mvlpt_stream_t stream) {
+  if (!q || !table || !idx || !dist || !workspace) { g_create_err = "op_nearest_rows: null argument"; return MVLPT_ERR_ARG; }
+  if (int rc = nearest_check("op_nearest_rows", R, V, d, k, &g_create_err)) return rc;
+  const NearestPlan p = nearest_plan(R, V, k, stream_cus((hipStream_t)stream));
+  if (workspace_bytes < 0 || (uint64_t)workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 7) != 0) {
+    g_create_err = "op_nearest_rows: the workspace is smaller than mvlpt_nearest_workspace_bytes (" + std::to_string(p.ws_bytes) +
+                   " bytes), or not 8-byte aligned";
+    return MVLPT_ERR_ARG;
+  }
+  return nearest_run("op_nearest_rows", q, table, R, V, d, k, idx, dist, workspace, p, (hipStream_t)stream, &g_create_err);
+}
+int mvlpt_nearest_tokens(void* h, const float* q, int R, int k, int32_t* idx, float* dist, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E) return MVLPT_ERR_ARG;
+  if (!q || !idx || !dist) return fail(E, MVLPT_ERR_ARG, "nearest_tokens: null argument");
+  if (!E->tok_emb || E->vocab <= 0)
+    return fail(E, MVLPT_ERR_STATE, "nearest_tokens: token_embedding.weight is not loaded (mvlpt_load_frozen)");
+  if (int rc = nearest_check("nearest_tokens", R, E->vocab, E->arch.text_width, k, &E->err)) return rc;
+  const NearestPlan p = nearest_plan(R, E->vocab, k, stream_cus((hipStream_t)stream));
+  HIPCHK(E, E->near_ws.reserve(p.ws_bytes));
+  return nearest_run("nearest_tokens", q, E->tok_emb, R, E->vocab, E->arch.text_width, k, idx, dist, E->near_ws.p, p, (hipStream_t)stream,
+                     &E->err);
 }
 
 // ------------------------------------------------------------------------------------------------ input pipeline

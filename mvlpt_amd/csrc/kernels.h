@@ -314,4 +314,14 @@ hipError_t launch_logits_ranged_bwd(const float* dlogits, const float* imn, cons
                                     float scale, const int32_t* lo, const int32_t* start, const int32_t* seq_grp, float* dimg, float* dtxt,
                                     int G, int S, int C, int e, hipStream_t s);
 
+// ---------------------------------------------------------------- nearest table rows (nearest.hip; semantics in include/mvlpt_hip.h)
+// Geometry of one call: row tiles of NR_ROWS query rows (grid.y) x vocabulary slices (grid.x), NR_WAVES partial lists of k keys per
+// row and slice.  The slice count follows the stream's compute units; the results do not depend on it.  The arguments are checked by
+// the caller (engine.hip): 1 <= k <= min(V, 64), d % 4 == 0, row_tiles <= 65535, ws of ws_bytes.
+constexpr int NR_ROWS = 8, NR_WAVES = 4;
+struct NearestPlan { int row_tiles = 0, slices = 0, tiles_per_slice = 0, parts = 0; size_t ws_bytes = 0; };
+NearestPlan nearest_plan(int R, int V, int k, int cus);
+hipError_t launch_nearest_rows(const float* q, const float* table, int R, int V, int d, int k, int32_t* idx, float* dist, void* ws,
+                               const NearestPlan& p, hipStream_t s);
+
 }  // namespace mvlpt

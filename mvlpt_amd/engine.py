@@ -120,6 +120,7 @@ class Engine:
         self._img_pending = None      # image_fwd_begin .. image_fwd_resume: (image, vpt, vpt_deep, masks, state for image_bwd)
         self._txt_state = None
         self._head_state = None
+        self.token_table_loader = None   # weakref.WeakMethod of FrozenCLIP's "upload the token table once" (nearest_tokens: first use)
 
     # ------------------------------------------------------------------ lifecycle
     def close(self):
@@ -369,6 +370,32 @@ class Engine:
                    "text_encode_tokens")
         self._txt_state = None
         return feat
+
+    @_on_device
+    def nearest_tokens(self, q: torch.Tensor, k: int, max_rows: int = _lib.NEAREST_MAX_ROWS) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The k nearest rows of the resident token table for every row of q [R, text_width] (mvlpt_nearest_tokens): token ids int64
+        [R, k] and Euclidean distances fp32 [R, k], ascending by (distance, id), on the device.  No [R, vocab] matrix is built.  The
+        table is uploaded on first use (FrozenCLIP's loader, the one encode_text uses).  R above `max_rows` (the grid's limit,
+        MVLPT_NEAREST_MAX_ROWS) runs in chunks of that many rows; the rows are independent, so chunking changes no result."""
+        q = _req(q, torch.float32, "q")
+        if q.dim() != 2 or q.shape[0] == 0 or q.shape[1] != self.arch.transformer_width:
+            raise ValueError(f"q must be [R >= 1, {self.arch.transformer_width}], got {tuple(q.shape)}")
+        k = int(k)
+        if not 1 <= k <= _lib.NEAREST_MAX_K:
+            raise ValueError(f"topk must lie in [1, {_lib.NEAREST_MAX_K}] (MVLPT_NEAREST_MAX_K), got {k}")
+        if not 1 <= max_rows <= _lib.NEAREST_MAX_ROWS:
+            raise ValueError(f"max_rows must lie in [1, {_lib.NEAREST_MAX_ROWS}]")
+        load = self.token_table_loader() if self.token_table_loader is not None else None
+        if load is not None:
+            load()
+        R = q.shape[0]
+        idx = torch.empty(R, k, device=q.device, dtype=torch.int32)
+        dist = torch.empty(R, k, device=q.device, dtype=torch.float32)
+        for r0 in range(0, R, max_rows):
+            r1 = min(R, r0 + max_rows)
+            _lib.check(lib.mvlpt_nearest_tokens(self.h, _ptr(q[r0:r1]), r1 - r0, k, _ptr(idx[r0:r1]), _ptr(dist[r0:r1]), _stream()),
+                       self.h, "nearest_tokens")
+        return idx.long(), dist
 
     def text_encode_workspace_bytes(self, n_seq: int, L: int) -> int:
         """Workspace text_encode_tokens reserves for `n_seq` sequences of length L: the tower's plus the id table (include/mvlpt_hip.h)."""
@@ -649,6 +676,30 @@ def op_embed_tokens(emb, pos, ids, L: int, out=None) -> torch.Tensor:
     x = out if out is not None else torch.empty(S, L, d, device=emb.device, dtype=torch.float32)
     _lib.check(lib.mvlpt_op_embed_tokens(_ptr(emb), _ptr(pos), _ptr(ids), ld, _ptr(x), S, int(L), d, _stream()), None, "op_embed_tokens")
     return x
+
+
+def nearest_workspace_bytes(R: int, V: int, d: int, k: int) -> int:
+    """Scratch bytes op_nearest_rows needs for these sizes on the current stream (mvlpt_nearest_workspace_bytes)."""
+    out = C.c_int64()
+    _lib.check(lib.mvlpt_nearest_workspace_bytes(int(R), int(V), int(d), int(k), _stream(), C.byref(out)), None, "nearest_workspace_bytes")
+    return int(out.value)
+
+
+def op_nearest_rows(q, table, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(idx int32 [R, k], dist fp32 [R, k]): the k nearest rows of table [V, d] for every row of q [R, d], fp32 on the device
+    (mvlpt_op_nearest_rows; order, NaN rule and limits in include/mvlpt_hip.h)."""
+    q, table = _req(q, torch.float32, "q"), _req(table, torch.float32, "table")
+    (R, d), V = q.shape, table.shape[0]
+    if table.shape[1] != d:
+        raise ValueError("q and table must have the same width")
+    with torch.cuda.device(q.device):
+        nb = nearest_workspace_bytes(R, V, d, k)
+        ws = torch.empty(max(nb, 8) // 8, device=q.device, dtype=torch.int64)
+        idx = torch.empty(R, k, device=q.device, dtype=torch.int32)
+        dist = torch.empty(R, k, device=q.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_op_nearest_rows(_ptr(q), _ptr(table), R, V, d, int(k), _ptr(idx), _ptr(dist), _ptr(ws), nb, _stream()), None,
+                   "op_nearest_rows")
+    return idx, dist
 
 
 def op_ensemble_features(feats) -> torch.Tensor:

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import math
 import os
+import weakref
 from collections import OrderedDict
 from functools import reduce
 from operator import mul
@@ -135,6 +136,13 @@ class FrozenCLIP:
         self.max_text_workspace_bytes = DEFAULT_MAX_TEXT_WORKSPACE_BYTES
         self.min_sequences_per_chunk = MIN_SEQUENCES_PER_CHUNK
         self.dtype = torch.float32   # dtype of the prompt parameters (see module docstring)
+        # Engine.nearest_tokens: the same upload, on its first use (weak: the engine must not keep its owner alive in a cycle)
+        self.engine.token_table_loader = weakref.WeakMethod(self._ensure_token_embedding)
+
+    def _ensure_token_embedding(self) -> None:
+        if not self._token_embedding_loaded:
+            self.engine.load_token_embedding(self._token_table())
+            self._token_embedding_loaded = True
 
     def token_embedding(self, ids: torch.Tensor) -> torch.Tensor:
         """clip_model.token_embedding(tokenized_prompts) (trainers/mvlpt.py:306-307); init-time only, CPU."""
@@ -162,9 +170,7 @@ class FrozenCLIP:
         ids = torch.as_tensor(tokenized).cpu()
         if ids.dim() != 2 or ids.shape[0] == 0:
             raise ValueError("tokenized must be [n, context_length]")
-        if not self._token_embedding_loaded:
-            self.engine.load_token_embedding(self._token_table())
-            self._token_embedding_loaded = True
+        self._ensure_token_embedding()
         ids = ids.to(torch.int32).contiguous()
         chunks = self.text_chunks(ids.argmax(dim=-1).tolist(), trim)
         out = torch.empty(ids.shape[0], self.arch.embed_dim, device=self.device, dtype=torch.float32)

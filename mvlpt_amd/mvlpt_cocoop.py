@@ -309,22 +309,47 @@ class CustomCLIP(nn.Module):
         from .model import CustomCLIP as _Base
         return _Base.vpt_dropout_masks(self, B)
 
-    def forward(self, image, task=None):
+    def _image_side(self, image):
+        """(image features [B, e], shifted contexts [B, n_ctx, ctx_dim]): the image tower with its visual prompts, then :561-563."""
         pl = self.prompt_learner
-        B = image.shape[0]
-        self._fwd_generation += 1
         _, vpt_emb, vpt_emb_deep = pl.forward_mvlpt_proj(self.dtype)             # :541 (no COOP ctx: the parameters themselves)
         if vpt_emb is not None:
             proj = pl.vpt_proj                                                   # :424, :77, as mvlpt_amd.model.CustomCLIP.forward
             vpt_emb = proj(vpt_emb)
             if vpt_emb_deep is not None:
                 vpt_emb_deep = proj(vpt_emb_deep)
-            self.engine.set_vpt_dropout(self.vpt_dropout_masks(B))
+            self.engine.set_vpt_dropout(self.vpt_dropout_masks(image.shape[0]))
             img = _ImageTowerFn.apply(self, image, vpt_emb, vpt_emb_deep, torch.is_grad_enabled())
         else:
             img = self.engine.image_fwd(image, None, None, save_for_bwd=False)   # frozen, prompt-free image tower
         imf = img / img.norm(dim=-1, keepdim=True)                               # :561 (meta_net's input)
-        ctx_shifted = pl(imf)                                                    # :563, :361-364
+        return img, pl(imf)                                                      # :563, :361-364
+
+    @torch.no_grad()
+    def image_contexts(self, image) -> torch.Tensor:
+        """cocoop_ctx + meta_net(image features) [B, n_ctx, ctx_dim], as an evaluation forward computes them: the prompt learner is put
+        in eval mode for the call (no VPT dropout, nothing drawn from the RNG) and restored.  It counts as a forward: the image tower
+        runs and replaces the activations the engine keeps, so the backward of an earlier forward raises the stale-forward error."""
+        pl = self.prompt_learner
+        was_training = pl.training
+        pl.eval()
+        self._fwd_generation += 1
+        try:
+            return self._image_side(image.to(self.clip_model.device))[1]
+        finally:
+            pl.train(was_training)
+
+    def interpret_images(self, images, topk: int = 5):
+        """Nearest vocabulary words of every image's own contexts: [B][n_ctx] lists of (word, distance), B * n_ctx rows in ONE
+        nearest-token call (mvlpt_amd.interpret)."""
+        from .interpret import nearest_words
+        return nearest_words(self.clip_model, self.image_contexts(images), topk)
+
+    def forward(self, image, task=None):
+        pl = self.prompt_learner
+        B = image.shape[0]
+        self._fwd_generation += 1
+        img, ctx_shifted = self._image_side(image)
         lo, hi = class_ranges(task, self.class_index_pertask_start, self.class_index_pertask_end, B, pl.n_cls)
         mask = None
         if not self.ranged_text and self.multi_task_label_pertask:

@@ -660,6 +660,20 @@ class MVLPT(TrainerX):
         self.last_results = results
         return list(results.values())[0]
 
+    def interpret_prompt(self, topk: int = 5):
+        """Nearest vocabulary words of the live model's context vectors (mvlpt_amd.interpret.interpret_model): "ctx" (per class under
+        CSC), "cocoop_ctx", and under UPT "ctx (projected)", the contexts that enter the text tower.  Never called by the loop."""
+        from .interpret import interpret_model
+        cfg = self.cfg
+        classnames = self.dm.dataset.classnames if cfg.DATASET.COOP else list(self.dm.lab2cname.values())
+        return interpret_model(self.model, topk, classnames)
+
+    def interpret_images(self, images, topk: int = 5):
+        """Nearest vocabulary words of cocoop_ctx + meta_net(image features) per image (the COCOOP.N_CTX != 0 route)."""
+        if not hasattr(self.model, "interpret_images"):
+            raise RuntimeError("interpret_images needs image-conditioned prompts (TRAINER.MVLPT.COCOOP.N_CTX != 0, or the CoCoOp trainer)")
+        return self.model.interpret_images(images, topk)
+
     def _task_ranges(self):
         """[(class_start, class_end)] per task id (trainers/mvlpt.py:785-790), or None for single-task data."""
         idx = getattr(self.dm, "_task_class_idx", None)

@@ -19,6 +19,7 @@
  */
 #ifndef MVLPT_HIP_H
 #define MVLPT_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -450,6 +451,29 @@ int mvlpt_nearest_workspace_bytes(int R, int V, int d, int k, mvlpt_stream_t str
 int mvlpt_op_nearest_rows(const float* q, const float* table, int R, int V, int d, int k, int32_t* idx, float* dist, void* workspace,
                           int64_t workspace_bytes, mvlpt_stream_t stream);
 int mvlpt_nearest_tokens(void* handle, const float* q, int R, int k, int32_t* idx, float* dist, mvlpt_stream_t stream);
+
+/* ---- linear-probe CLIP baseline: L2-regularised multinomial logistic regression (row j of the scope table; tests/test_hip_softmax_reg.py) ----
+ * Replaces sklearn's LogisticRegression(solver="lbfgs", penalty="l2", C=C) of lpclip/linear_probe.py with full-batch evaluations on
+ * the device.  The objective is the one sklearn 1.7 minimises,
+ *     F(W, b) = (1/N) sum_i [logsumexp(z_i) - z_i[y_i]] + (l2/2) |W|_F^2,   z_i = W x_i + b,   l2 = 1 / (C N),   b unpenalised.
+ * theta = [W row-major [K, D] | b [K]] fp32; grad has the same layout; X [N, D] fp32 row-major; y int32 [N] on the DEVICE, every
+ * label in [0, K) (the caller's responsibility at this level: a label outside matches no class, nothing is read out of bounds).
+ *   mvlpt_op_softmax_reg_eval: grad = dF/dtheta and stats = {F, max|grad|, grad . dir (0 when dir is NULL), |grad|^2}, four doubles on
+ *     the device.  The logits are an fp32 product on the fp32-input matrix instruction; max, log-sum-exp, loss and the probabilities
+ *     are formed in double from them; R = (p - onehot) / N is rounded once to fp32; grad_W = R^T X over row slices whose count depends
+ *     on (N, D, K) alone, the slices added in double in slice order with l2 W and rounded once; grad_b = the column sums of R in
+ *     double; the statistics in double.  No floating-point atomics: the bits of every output depend on the inputs and the shape alone.
+ *   mvlpt_op_softmax_reg_predict: pred[i] = arg max_k z_i[k], the lowest class index among equal logits (numpy's rule), and, when
+ *     margin is not NULL, margin[i] = largest - second largest logit (0 for a tie).  Callers chunk the rows to bound the workspace.
+ *   mvlpt_softmax_reg_workspace_bytes: the bytes either entry needs for these sizes (predict uses the first N * roundup(K, 4) floats).
+ *   Limits: N >= 1, K >= 2, D >= 4, D % 4 == 0, K * (D + 1) < 2^31; X, theta and the workspace 16-byte aligned.  Every violation, a
+ *     NULL pointer and a workspace that is too small return MVLPT_ERR_ARG with a message (mvlpt_last_error(NULL)) before anything is
+ *     launched.  Handle-free and enqueue-only on `stream`; offsets are 64-bit. */
+int mvlpt_softmax_reg_workspace_bytes(int N, int D, int K, size_t* bytes);
+int mvlpt_op_softmax_reg_eval(const float* X, const int32_t* y, const float* theta, const float* dir, int N, int D, int K, double l2,
+                              float* grad, double* stats, void* ws, size_t ws_bytes, mvlpt_stream_t stream);
+int mvlpt_op_softmax_reg_predict(const float* X, const float* theta, int N, int D, int K, int32_t* pred, float* margin, void* ws,
+                                 size_t ws_bytes, mvlpt_stream_t stream);
 
 /* ---- input pipeline ("next" row f3 of the scope table) -------------------------------------------------------
  * Replaces the per-image CPU transform the reference runs in DataLoader workers: Dassl `build_transform` with

@@ -142,6 +142,9 @@ SIGNATURES = {
     "mvlpt_nearest_workspace_bytes": (_i, [_i, _i, _i, _i, _vp, C.POINTER(C.c_int64)]),
     "mvlpt_op_nearest_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_int64, _vp]),
     "mvlpt_nearest_tokens": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "mvlpt_softmax_reg_workspace_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
+    "mvlpt_op_softmax_reg_eval": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "mvlpt_op_softmax_reg_predict": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mvlpt_preprocess": (_i, [_vp, _vp, C.c_int64, C.POINTER(MvlptImageDesc), _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _i, _vp, _vp]),
     "mvlpt_profile_begin": (_i, [_vp, _i]),
     "mvlpt_profile_pause": (_i, [_vp, _i]),

@@ -2037,6 +2037,53 @@ int mvlpt_nearest_tokens(void* h, const float* q, int R, int k, int32_t* idx, fl
                      &E->err);
 }
 
+// ------------------------------------------------------------------------------------------------ softmax regression (linear probe)
+// Every limit of include/mvlpt_hip.h is checked here, before a launch: the kernels (softmax_reg.hip) trust their arguments.
+static int softmax_reg_check(const char* who, int N, int D, int K) {
+  auto bad = [&](const char* what) { g_create_err = std::string(who) + ": " + what; return MVLPT_ERR_ARG; };
+  if (N < 1) return bad("N must be at least 1");
+  if (K < 2) return bad("K must be at least 2");
+  if (D < 4 || D % 4) return bad("D must be a multiple of 4, at least 4");
+  if ((int64_t)K * ((int64_t)D + 1) >= ((int64_t)1 << 31)) return bad("K * (D + 1) must stay below 2^31");
+  return 0;
+}
+static int softmax_reg_ws_check(const char* who, const void* ws, size_t have, size_t need) {
+  if (have < need || ((uintptr_t)ws & 15) != 0) {
+    g_create_err = std::string(who) + ": the workspace is smaller than needed (" + std::to_string(need) + " bytes), or not 16-byte aligned";
+    return MVLPT_ERR_ARG;
+  }
+  return 0;
+}
+int mvlpt_softmax_reg_workspace_bytes(int N, int D, int K, size_t* bytes) {
+  if (!bytes) { g_create_err = "softmax_reg_workspace_bytes: null argument"; return MVLPT_ERR_ARG; }
+  if (int rc = softmax_reg_check("softmax_reg_workspace_bytes", N, D, K)) return rc;
+  *bytes = softmax_reg_plan(N, D, K).ws_bytes;
+  return 0;
+}
+int mvlpt_op_softmax_reg_eval(const float* X, const int32_t* y, const float* theta, const float* dir, int N, int D, int K, double l2,
+                              float* grad, double* stats, void* ws, size_t ws_bytes, mvlpt_stream_t stream) {
+  if (!X || !y || !theta || !grad || !stats || !ws) { g_create_err = "op_softmax_reg_eval: null argument"; return MVLPT_ERR_ARG; }
+  if (int rc = softmax_reg_check("op_softmax_reg_eval", N, D, K)) return rc;
+  if (!(l2 >= 0.0)) { g_create_err = "op_softmax_reg_eval: l2 must be a number >= 0"; return MVLPT_ERR_ARG; }
+  if ((((uintptr_t)X | (uintptr_t)theta) & 15) != 0 || ((uintptr_t)stats & 7) != 0) {
+    g_create_err = "op_softmax_reg_eval: X and theta must be 16-byte aligned, stats 8-byte aligned"; return MVLPT_ERR_ARG; }
+  const SoftmaxRegPlan p = softmax_reg_plan(N, D, K);
+  if (int rc = softmax_reg_ws_check("op_softmax_reg_eval", ws, ws_bytes, p.ws_bytes)) return rc;
+  OPCHK(launch_softmax_reg_eval(X, y, theta, dir, N, D, K, l2, grad, stats, ws, p, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_softmax_reg_predict(const float* X, const float* theta, int N, int D, int K, int32_t* pred, float* margin, void* ws,
+                                 size_t ws_bytes, mvlpt_stream_t stream) {
+  if (!X || !theta || !pred || !ws) { g_create_err = "op_softmax_reg_predict: null argument"; return MVLPT_ERR_ARG; }
+  if (int rc = softmax_reg_check("op_softmax_reg_predict", N, D, K)) return rc;
+  if ((((uintptr_t)X | (uintptr_t)theta) & 15) != 0) {
+    g_create_err = "op_softmax_reg_predict: X and theta must be 16-byte aligned"; return MVLPT_ERR_ARG; }
+  const SoftmaxRegPlan p = softmax_reg_plan(N, D, K);
+  if (int rc = softmax_reg_ws_check("op_softmax_reg_predict", ws, ws_bytes, p.predict_bytes)) return rc;
+  OPCHK(launch_softmax_reg_predict(X, theta, N, D, K, pred, margin, ws, p, (hipStream_t)stream));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ input pipeline
 int mvlpt_preprocess(void* h, const uint8_t* src, int64_t src_bytes, const MvlptImageDesc* descs, int B, int out_h, int out_w,
                      const float* mean, const float* stdv, void* out, int out_dtype, uint8_t* out_u8, mvlpt_stream_t stream) {

@@ -324,4 +324,19 @@ NearestPlan nearest_plan(int R, int V, int k, int cus);
 hipError_t launch_nearest_rows(const float* q, const float* table, int R, int V, int d, int k, int32_t* idx, float* dist, void* ws,
                                const NearestPlan& p, hipStream_t s);
 
+// ---------------------------------------------------------------- softmax regression (softmax_reg.hip; semantics in include/mvlpt_hip.h)
+// Geometry and workspace layout of one call, a function of (N, D, K) alone: the logits / residuals Z [N, ldz] first (all that predict
+// needs: predict_bytes), then `slices` partial [K, D] gradients, their column sums, the loss partials of the row blocks and the
+// partial statistics of the final reduce.  The arguments are checked by the caller (engine.hip).
+constexpr int SR_TILE = 128;
+struct SoftmaxRegPlan {
+  int ldz = 0, slices = 0, rows_per_slice = 0, row_blocks = 0, fin_blocks = 0;
+  size_t off_part = 0, off_colsum = 0, off_lossp = 0, off_bstats = 0, ws_bytes = 0, predict_bytes = 0;
+};
+SoftmaxRegPlan softmax_reg_plan(int N, int D, int K);
+hipError_t launch_softmax_reg_eval(const float* X, const int32_t* y, const float* theta, const float* dir, int N, int D, int K, double l2,
+                                   float* grad, double* stats, void* ws, const SoftmaxRegPlan& p, hipStream_t s);
+hipError_t launch_softmax_reg_predict(const float* X, const float* theta, int N, int D, int K, int32_t* pred, float* margin, void* ws,
+                                      const SoftmaxRegPlan& p, hipStream_t s);
+
 }  // namespace mvlpt

@@ -702,6 +702,62 @@ def op_nearest_rows(q, table, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     return idx, dist
 
 
+def softmax_reg_workspace_bytes(N: int, D: int, K: int) -> int:
+    """Scratch bytes op_softmax_reg_eval / op_softmax_reg_predict need for these sizes (mvlpt_softmax_reg_workspace_bytes)."""
+    out = C.c_size_t()
+    _lib.check(lib.mvlpt_softmax_reg_workspace_bytes(int(N), int(D), int(K), C.byref(out)), None, "softmax_reg_workspace_bytes")
+    return int(out.value)
+
+
+def softmax_reg_workspace(N: int, D: int, K: int, device) -> torch.Tensor:
+    """A workspace of softmax_reg_workspace_bytes for these sizes (int64 elements: 8-byte units of an aligned allocation)."""
+    return torch.empty((softmax_reg_workspace_bytes(N, D, K) + 7) // 8, device=device, dtype=torch.int64)
+
+
+def op_softmax_reg_eval(X, y, theta, l2: float, dir=None, grad=None, stats=None, ws=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(grad fp32 [K*D + K], stats float64 [4] = F, max|grad|, grad . dir, |grad|^2) of the softmax-regression objective at
+    theta = [W [K, D] | b [K]] for X fp32 [N, D] and labels y int32 [N] in [0, K), all on the device (mvlpt_op_softmax_reg_eval;
+    arithmetic and limits in include/mvlpt_hip.h).  Enqueue-only: nothing is read back.  grad / stats / ws may be passed to reuse
+    buffers over the evaluations of a fit."""
+    X, y, theta = _req(X, torch.float32, "X"), _req(y, torch.int32, "y"), _req(theta, torch.float32, "theta")
+    N, D = X.shape
+    if y.shape != (N,):
+        raise ValueError("y must hold one label per row of X")
+    if theta.dim() != 1 or theta.numel() % (D + 1):
+        raise ValueError("theta must be flat with K * D + K elements")
+    K = theta.numel() // (D + 1)
+    if dir is not None:
+        dir = _req(dir, torch.float32, "dir")
+        if dir.shape != theta.shape:
+            raise ValueError("dir must have theta's shape")
+    with torch.cuda.device(X.device):
+        ws = softmax_reg_workspace(N, D, K, X.device) if ws is None else ws
+        grad = torch.empty_like(theta) if grad is None else _req(grad, torch.float32, "grad")
+        stats = torch.empty(4, device=X.device, dtype=torch.float64) if stats is None else _req(stats, torch.float64, "stats")
+        if grad.numel() < theta.numel() or stats.numel() < 4:
+            raise ValueError("grad / stats are too small")
+        _lib.check(lib.mvlpt_op_softmax_reg_eval(_ptr(X), _ptr(y), _ptr(theta), _ptr(dir), N, D, K, float(l2), _ptr(grad), _ptr(stats),
+                                                 _ptr(ws), ws.numel() * ws.element_size(), _stream()), None, "op_softmax_reg_eval")
+    return grad, stats
+
+
+def op_softmax_reg_predict(X, theta, margin: bool = False, ws=None):
+    """pred int32 [N] (and margin fp32 [N] = largest - second largest logit when asked) of theta = [W [K, D] | b [K]] on X fp32 [N, D]
+    (mvlpt_op_softmax_reg_predict: equal logits go to the lowest class index)."""
+    X, theta = _req(X, torch.float32, "X"), _req(theta, torch.float32, "theta")
+    N, D = X.shape
+    if theta.dim() != 1 or theta.numel() % (D + 1):
+        raise ValueError("theta must be flat with K * D + K elements")
+    K = theta.numel() // (D + 1)
+    with torch.cuda.device(X.device):
+        ws = softmax_reg_workspace(N, D, K, X.device) if ws is None else ws
+        pred = torch.empty(N, device=X.device, dtype=torch.int32)
+        mg = torch.empty(N, device=X.device, dtype=torch.float32) if margin else None
+        _lib.check(lib.mvlpt_op_softmax_reg_predict(_ptr(X), _ptr(theta), N, D, K, _ptr(pred), _ptr(mg), _ptr(ws),
+                                                    ws.numel() * ws.element_size(), _stream()), None, "op_softmax_reg_predict")
+    return (pred, mg) if margin else pred
+
+
 def op_ensemble_features(feats) -> torch.Tensor:
     feats = _req(feats, torch.float32, "feats")
     T, Cn, e = feats.shape

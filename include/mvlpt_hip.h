@@ -55,6 +55,28 @@ typedef struct MvlptArch {
 enum { MVLPT_PREC_FAST = 0, MVLPT_PREC_SPLIT_GRAD = 1, MVLPT_PREC_SPLIT_ALL = 2 };
 
 int mvlpt_create(const MvlptArch* arch, void** handle);
+/* A handle whose image tower is CLIP's ModifiedResNet (clip/model.py:94-150: RN50, RN101; three-conv stem, four stages of Bottleneck
+ * blocks of `layers[i]` blocks and width * {1,2,4,8} planes, AttentionPool2d with `heads` heads of 64 over 32 * width channels).
+ * `arch` carries the text tower, embed_dim and compute_dtype; its ViT vision fields (image_resolution, patch_size, vision_width,
+ * vision_layers, vision_heads) must be 0.  image_resolution % 32 == 0, width % 4 == 0, heads * 64 == 32 * width,
+ * output_dim == embed_dim (MVLPT_ERR_ARG otherwise); compute_dtype must be MVLPT_DT_F16 (bf16: MVLPT_ERR_UNSUPPORTED).
+ * The tower is frozen and forward-only, as every route of the reference that reaches it (trainers/coop.py:220, cocoop.py:169,
+ * zsclip.py:56, lpclip/feat_extractor.py:155; trainers/mvlpt.py:48 cannot prompt a ResNet): NHWC fp16 activations, implicit-GEMM
+ * convolutions on the fp16 MFMA with fp32 accumulation, BatchNorm (running statistics) as an fp32 scale / shift in the epilogue.
+ * On such a handle
+ *   - mvlpt_load_frozen takes the reference's keys visual.conv{1,2,3}.weight, visual.bn{1,2,3}.*, visual.layer{1..4}.{i}.conv{1,2,3}.weight,
+ *     .bn{1,2,3}.*, .downsample.0.weight, .downsample.1.*, visual.attnpool.positional_embedding, visual.attnpool.{q,k,v,c}_proj.*;
+ *   - mvlpt_image_fwd(handle, image, dtype, NULL, NULL, 0, 0, B, feat_out, 0, stream) runs the tower, enqueue-only;
+ *   - visual prompts, save_for_bwd != 0, mvlpt_image_bwd, mvlpt_image_fwd_begin / _resume and mvlpt_set_vpt_dropout return
+ *     MVLPT_ERR_UNSUPPORTED with a message, without touching the device;
+ *   - mvlpt_set_precision accepts all three modes; the ResNet tower runs single fp16 operands in each of them (it carries no
+ *     gradient); the text tower, the heads, the cross-entropy, nearest-token and preprocess entries work as on any handle. */
+typedef struct MvlptResNetArch {
+  int image_resolution, width;
+  int layers[4];
+  int heads, output_dim;
+} MvlptResNetArch;
+int mvlpt_create_resnet(const MvlptArch* arch, const MvlptResNetArch* rn, void** handle);
 /* switch the precision mode (takes effect at the next tower forward) */
 int mvlpt_set_precision(void* handle, int mode);
 /* LayerNorm folding (no counterpart in the reference, which calls nn.LayerNorm as its own op, clip/model.py:186-187): inside a
@@ -389,6 +411,29 @@ int mvlpt_op_assemble_tokens(const float* patch_emb, const float* cls, const flo
 int mvlpt_op_assemble_prompts(const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
                               const int32_t* layout, const float* pos, const int32_t* eot, float* x, int32_t* ctx_pos, int32_t* eot_rows,
                               int C, int L, int d, mvlpt_stream_t stream);
+
+/* ---- the convolutional tower at kernel level (tests/test_hip_conv.py).  fp16 NHWC activations; handle-free, enqueue-only; every
+ * argument error (a NULL pointer, an extent <= 0, a shape outside the limits) returns MVLPT_ERR_ARG or MVLPT_ERR_UNSUPPORTED with a
+ * message in mvlpt_last_error(NULL) before anything is launched.
+ * pack_conv_weight: w32 [Cout, Cin, k, k] fp32 -> out fp16 [Cout, Kp], column (ky * k + kx) * cin_pad + ci (tap-major: a tap's channel
+ *   run is contiguous, as in the NHWC input), zero for ci >= Cin and for the tail; Kp = k * k * cin_pad rounded up to 32 is returned
+ *   through *kp (out may be NULL to ask for it).  cin_pad >= Cin, cin_pad % 8 == 0.
+ * conv2d: y [B, Ho, Wo, Cout] = act(conv(x [B, H, W, Cin], w) * scale[c] + shift[c] (+ resid [B, Ho, Wo, Cout])), act = ReLU when
+ *   relu != 0; fp32 accumulation and epilogue, ONE rounding to fp16.  k in {1, 3}, pad k / 2, stride 1, or 2 with k = 3;
+ *   Ho = (H + 2 pad - k) / stride + 1; Cin (= the weight's cin_pad) % 8 == 0, Cout % 8 == 0 (MVLPT_ERR_UNSUPPORTED otherwise);
+ *   scale / shift fp32 [Cout].  Out-of-image taps are zero; pointers 16-byte aligned.
+ * avgpool2x2: AvgPool2d(2), y [B, H/2, W/2, C], fp32 sum of four and one rounding; C % 8 == 0.
+ * nchw_to_nhwc8: image [B, 3, R, R] of image_dtype (MVLPT_DT_*) -> [B, R, R, 8] fp16, channels 3..7 zero.
+ * attnpool_tokens: tok [B, 1 + HW, E] fp16 = [mean over HW ; x [B, HW, E]] + pos [1 + HW, E] fp32 (mean and sum in fp32, one rounding).
+ * attnpool_query: out [B, E] fp16: per image and head of 64 channels softmax(q . K / 8) V with q [B, E], kv [B, T, 2E] = [K | V];
+ *   scores and softmax in fp32; 1 <= T <= 145, E % 64 == 0. */
+int mvlpt_op_pack_conv_weight(const float* w32, int Cout, int Cin, int k, int cin_pad, void* out, int* kp, mvlpt_stream_t stream);
+int mvlpt_op_conv2d(const void* x, const void* w, const float* scale, const float* shift, const void* resid, void* y, int B, int H,
+                    int W, int Cin, int Cout, int k, int stride, int relu, mvlpt_stream_t stream);
+int mvlpt_op_avgpool2x2(const void* x, void* y, int B, int H, int W, int C, mvlpt_stream_t stream);
+int mvlpt_op_nchw_to_nhwc8(const void* image, int image_dtype, void* out, int B, int R, mvlpt_stream_t stream);
+int mvlpt_op_attnpool_tokens(const void* x, const float* pos, void* tok, int B, int HW, int E, mvlpt_stream_t stream);
+int mvlpt_op_attnpool_query(const void* q, const void* kv, void* out, int B, int T, int E, mvlpt_stream_t stream);
 
 /* ---- fused optimizer step over the flat prompt buffers (row f2 of the scope table; tests/test_hip_optim.py) ----
  * ONE launch updates param, state1 and state2 in place over [0, n) with torch.optim's single-tensor formulas in fp32:

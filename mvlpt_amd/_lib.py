@@ -33,6 +33,10 @@ class MvlptArch(C.Structure):
         "context_length", "text_width", "text_layers", "text_heads", "embed_dim", "compute_dtype")]
 
 
+class MvlptResNetArch(C.Structure):
+    _fields_ = [("image_resolution", C.c_int), ("width", C.c_int), ("layers", C.c_int * 4), ("heads", C.c_int), ("output_dim", C.c_int)]
+
+
 class MvlptKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double), ("busy_ms", C.c_double), ("flops_executed", C.c_double)]
@@ -62,6 +66,7 @@ _vp, _i, _f = C.c_void_p, C.c_int, C.c_float
 # name -> (restype, argtypes): every symbol include/mvlpt_hip.h declares
 SIGNATURES = {
     "mvlpt_create": (_i, [C.POINTER(MvlptArch), C.POINTER(_vp)]),
+    "mvlpt_create_resnet": (_i, [C.POINTER(MvlptArch), C.POINTER(MvlptResNetArch), C.POINTER(_vp)]),
     "mvlpt_destroy": (_i, [_vp]),
     "mvlpt_set_precision": (_i, [_vp, _i]),
     "mvlpt_trim": (_i, [_vp]),
@@ -124,6 +129,12 @@ SIGNATURES = {
     "mvlpt_op_attention_fwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_attention_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_cast": (_i, [_i, _vp, _vp, C.c_int64, _vp]),
+    "mvlpt_op_pack_conv_weight": (_i, [_vp, _i, _i, _i, _i, _vp, C.POINTER(C.c_int), _vp]),
+    "mvlpt_op_conv2d": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_avgpool2x2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_nchw_to_nhwc8": (_i, [_vp, _i, _vp, _i, _i, _vp]),
+    "mvlpt_op_attnpool_tokens": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mvlpt_op_attnpool_query": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvlpt_op_assemble_prompts_ranged": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_gather_ctx_grad_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "mvlpt_op_embed_tokens": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _vp]),

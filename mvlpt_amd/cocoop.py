@@ -26,7 +26,7 @@ from . import _lib
 from . import distributed as dist_utils
 from .model import FrozenCLIP, PretokenizedPrompts, _text_inputs, build_prompt_layout
 from .trainer import MVLPT, TrainerX, build_lr_scheduler, build_optimizer, load_pretrained_weights
-from .weights import ARCHS, make_state_dict
+from .weights import get_arch, make_state_dict
 
 # Workspace budget of the CoCoOp text tower (not a reference key).  A chunk is the largest number of images whose grouped
 # text tower fits it (mvlpt_text_workspace_bytes).  ViT-B/16 with 100 classes needs 1.67 GiB per image for a training step.
@@ -228,7 +228,7 @@ class CoCoOp(MVLPT):
         pretok = getattr(self.dm, "pretokenized", None)
         sd = self._sd_arg
         if sd is None:
-            sd = make_state_dict(ARCHS[cfg.MODEL.BACKBONE.NAME], seed=cfg.SEED)
+            sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED)
         # fp16 / amp / fp32 all end in split_all (CustomCLIP raises the default mode); GRAD_PRECISION = "fast" keeps single operands
         prec = "split_all" if cfg.TRAINER.COCOOP.PREC == "fp32" else cfg.TRAINER.MVLPT.GRAD_PRECISION
         clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec)

@@ -127,6 +127,21 @@ struct LNp { float* g = nullptr; float* b = nullptr; };
 struct Block { LNp ln1, ln2; Linear qkv, o, fc, pr; };
 struct TowerW { int width = 0, layers = 0, heads = 0; std::vector<Block> blocks; };
 
+// Frozen ModifiedResNet (mvlpt_create_resnet): packed fp16 conv weights [Cout, Kp] (conv.hip) and BatchNorm as the four tensors the
+// state dict holds plus the fp32 scale / shift the conv epilogue applies (built once behind a load, prepare_resnet)
+struct BNp { float *g = nullptr, *b = nullptr, *m = nullptr, *v = nullptr, *scale = nullptr, *shift = nullptr; };
+struct ConvW { void* w = nullptr; int cin = 0, cin_pad = 0, cout = 0, k = 0; BNp bn; };
+struct RNBlock { ConvW c1, c2, c3, ds; bool has_ds = false; int stride = 1; };
+struct ResNetW {
+  bool on = false, ready = false;
+  MvlptResNetArch a{};
+  ConvW stem[3];
+  std::vector<RNBlock> stage[4];
+  // AttentionPool2d: positional embedding [T, E] fp32; dense fp16 weights q [E, E], k|v [2E, E], c [out, E] and their fp32 biases
+  float* pos = nullptr; void *qw = nullptr, *kvw = nullptr, *cw = nullptr; float *qb = nullptr, *kvb = nullptr, *cb = nullptr;
+  bool have[8] = {false, false, false, false, false, false, false, false};      // q, k, v, c weights; q, k, v, c biases
+};
+
 struct TowerState {
   bool valid = false, saved = false, causal = false;
   bool exact = false;                    // split-precision operands + pair-product attention (see DESIGN.md "Precision modes")
@@ -180,6 +195,7 @@ struct Engine {
   bool lo8 = true;      // split towers of MVLPT_PREC_SPLIT_GRAD use the mixed pair (hi + e5m2 residual byte; MVLPT_SPLIT_LO8=0: 16-bit pairs)
   std::string err;
   TowerW vis, txt;
+  ResNetW rn;           // rn.on: the image tower is a ModifiedResNet (vis stays empty)
   // vision extras
   void* conv_w = nullptr; int Kp = 0; float* cls_emb = nullptr; float* vpos = nullptr; LNp ln_pre, ln_post;
   float *vproj = nullptr, *vproj_t = nullptr;  // [dv,e] and [e,dv] fp32 (the projections next to the logits stay fp32)
@@ -609,9 +625,30 @@ const char* first_missing(Engine* E) {
   static thread_local std::string m;
   auto chk = [&](const void* p, const std::string& n) { if (!p && m.empty()) m = n; };
   m.clear();
+  if (E->rn.on) {
+    auto conv = [&](const ConvW& c, const std::string& cn, const std::string& bn) {
+      chk(c.w, cn + ".weight"); chk(c.bn.g, bn + ".weight"); chk(c.bn.b, bn + ".bias");
+      chk(c.bn.m, bn + ".running_mean"); chk(c.bn.v, bn + ".running_var");
+    };
+    for (int i = 0; i < 3; ++i) conv(E->rn.stem[i], "visual.conv" + std::to_string(i + 1), "visual.bn" + std::to_string(i + 1));
+    for (int st = 0; st < 4; ++st)
+      for (size_t i = 0; i < E->rn.stage[st].size(); ++i) {
+        const RNBlock& B = E->rn.stage[st][i];
+        const std::string q = "visual.layer" + std::to_string(st + 1) + "." + std::to_string(i) + ".";
+        conv(B.c1, q + "conv1", q + "bn1"); conv(B.c2, q + "conv2", q + "bn2"); conv(B.c3, q + "conv3", q + "bn3");
+        if (B.has_ds) conv(B.ds, q + "downsample.0", q + "downsample.1");
+      }
+    chk(E->rn.pos, "visual.attnpool.positional_embedding");
+    static const char* const pn[4] = {"q", "k", "v", "c"};
+    for (int i = 0; i < 4; ++i) {
+      if (!E->rn.have[i] && m.empty()) m = std::string("visual.attnpool.") + pn[i] + "_proj.weight";
+      if (!E->rn.have[4 + i] && m.empty()) m = std::string("visual.attnpool.") + pn[i] + "_proj.bias";
+    }
+  } else {
   chk(E->conv_w, "visual.conv1.weight"); chk(E->cls_emb, "visual.class_embedding"); chk(E->vpos, "visual.positional_embedding");
   chk(E->ln_pre.g, "visual.ln_pre.weight"); chk(E->ln_pre.b, "visual.ln_pre.bias");
   chk(E->ln_post.g, "visual.ln_post.weight"); chk(E->ln_post.b, "visual.ln_post.bias"); chk(E->vproj, "visual.proj");
+  }
   chk(E->tpos, "positional_embedding"); chk(E->ln_final.g, "ln_final.weight"); chk(E->ln_final.b, "ln_final.bias");
   chk(E->tproj, "text_projection");
   for (int t = 0; t < 2; ++t) {
@@ -668,6 +705,186 @@ int prepare_fold(Engine* E, hipStream_t s) {
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ ModifiedResNet image tower
+const char* kRefuseRN = "the ResNet image tower is frozen and forward-only in one piece (trainers/mvlpt.py:48 cannot prompt a ResNet): ";
+
+int rn_load_conv(Engine* E, ConvW& c, const float* p, const int64_t* shape, int ndim, const std::string& nm, hipStream_t s) {
+  if (!(ndim == 4 && shape[0] == c.cout && shape[1] == c.cin && shape[2] == c.k && shape[3] == c.k))
+    return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
+  if (!c.w) {
+    void* w = nullptr;
+    HIPCHK(E, hipMalloc(&w, (size_t)c.cout * conv_kp(c.k, c.cin_pad) * 2)); E->owned.push_back(w);
+    c.w = w;
+  }
+  HIPCHK(E, launch_pack_conv_weight(p, c.w, c.cout, c.cin, c.k, c.cin_pad, s));
+  return 0;
+}
+int rn_load_bn(Engine* E, ConvW& c, const std::string& field, const float* p, const int64_t* shape, int ndim, const std::string& nm,
+               hipStream_t s) {
+  if (!(ndim == 1 && shape[0] == c.cout)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
+  float** dst = field == "weight" ? &c.bn.g : field == "bias" ? &c.bn.b : field == "running_mean" ? &c.bn.m
+                : field == "running_var" ? &c.bn.v : nullptr;
+  if (!dst) return fail(E, MVLPT_ERR_ARG, "unknown frozen tensor name: " + nm);
+  return upload_f32(E, p, (size_t)c.cout, dst, s);
+}
+// "<conv>.weight" / "<bn>.<field>" of one conv + BatchNorm pair; `t` is the name behind the pair's prefix
+int rn_load_pair(Engine* E, ConvW& c, const std::string& t, const std::string& conv, const std::string& bn, const float* p,
+                 const int64_t* shape, int ndim, const std::string& nm, hipStream_t s) {
+  if (t == conv + ".weight") return rn_load_conv(E, c, p, shape, ndim, nm, s);
+  if (t.rfind(bn + ".", 0) == 0) return rn_load_bn(E, c, t.substr(bn.size() + 1), p, shape, ndim, nm, s);
+  return 1;      // not this pair
+}
+
+int rn_load(Engine* E, const std::string& nm, const float* p, const int64_t* shape, int ndim, hipStream_t s) {
+  ResNetW& R = E->rn;
+  R.ready = false;
+  const std::string t = nm.substr(7);      // behind "visual."
+  const int Ech = 32 * R.a.width, T = (R.a.image_resolution / 32) * (R.a.image_resolution / 32) + 1;
+  for (int i = 0; i < 3; ++i) {
+    const int rc = rn_load_pair(E, R.stem[i], t, "conv" + std::to_string(i + 1), "bn" + std::to_string(i + 1), p, shape, ndim, nm, s);
+    if (rc <= 0) return rc;
+  }
+  if (t.rfind("layer", 0) == 0 && t.size() > 7 && t[5] >= '1' && t[5] <= '4' && t[6] == '.') {
+    const int st = t[5] - '1';
+    char* endp = nullptr;
+    const long bi = strtol(t.c_str() + 7, &endp, 10);
+    if (endp == t.c_str() + 7 || *endp != '.' || bi < 0 || bi >= (long)R.stage[st].size())
+      return fail(E, MVLPT_ERR_ARG, "block index out of range: " + nm);
+    RNBlock& B = R.stage[st][bi];
+    const std::string u(endp + 1);
+    int rc = rn_load_pair(E, B.c1, u, "conv1", "bn1", p, shape, ndim, nm, s); if (rc <= 0) return rc;
+    rc = rn_load_pair(E, B.c2, u, "conv2", "bn2", p, shape, ndim, nm, s); if (rc <= 0) return rc;
+    rc = rn_load_pair(E, B.c3, u, "conv3", "bn3", p, shape, ndim, nm, s); if (rc <= 0) return rc;
+    if (B.has_ds) { rc = rn_load_pair(E, B.ds, u, "downsample.0", "downsample.1", p, shape, ndim, nm, s); if (rc <= 0) return rc; }
+    return fail(E, MVLPT_ERR_ARG, "unknown frozen tensor name: " + nm);
+  }
+  if (t == "attnpool.positional_embedding") {
+    if (!(ndim == 2 && shape[0] == T && shape[1] == Ech)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
+    return upload_f32(E, p, (size_t)T * Ech, &R.pos, s);
+  }
+  static const char* const pn[4] = {"q", "k", "v", "c"};
+  for (int i = 0; i < 4; ++i) {
+    const std::string base = std::string("attnpool.") + pn[i] + "_proj.";
+    const int out = i == 3 ? R.a.output_dim : Ech;
+    if (t == base + "weight") {
+      if (!(ndim == 2 && shape[0] == out && shape[1] == Ech)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
+      void** w = i == 0 ? &R.qw : i == 3 ? &R.cw : &R.kvw;
+      if (!*w) {
+        void* q = nullptr;
+        HIPCHK(E, hipMalloc(&q, (size_t)(i == 1 || i == 2 ? 2 : 1) * out * Ech * 2)); E->owned.push_back(q);
+        *w = q;
+      }
+      HIPCHK(E, launch_pack_weight(DT_F16, p, (char*)*w + (i == 2 ? (size_t)Ech * Ech * 2 : 0), out, Ech, Ech, s));
+      R.have[i] = true;
+      return 0;
+    }
+    if (t == base + "bias") {
+      if (!(ndim == 1 && shape[0] == out)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
+      float** b = i == 0 ? &R.qb : i == 3 ? &R.cb : &R.kvb;
+      if (!*b) {
+        void* q = nullptr;
+        HIPCHK(E, hipMalloc(&q, (size_t)(i == 1 || i == 2 ? 2 : 1) * out * 4)); E->owned.push_back(q);
+        *b = (float*)q;
+      }
+      HIPCHK(E, hipMemcpyAsync(*b + (i == 2 ? Ech : 0), p, (size_t)out * 4, hipMemcpyDeviceToDevice, s));
+      R.have[4 + i] = true;
+      return 0;
+    }
+  }
+  return fail(E, MVLPT_ERR_ARG, "unknown frozen tensor name: " + nm);
+}
+
+// BatchNorm scale / shift of every conv, once behind a (re)load of the frozen tensors
+int prepare_resnet(Engine* E, hipStream_t s) {
+  ResNetW& R = E->rn;
+  if (R.ready) return 0;
+  int rc = 0;
+  auto one = [&](ConvW& c) {
+    if (rc) return;
+    if (!c.bn.scale) {
+      void* p = nullptr;
+      hipError_t e = hipMalloc(&p, (size_t)c.cout * 2 * sizeof(float));
+      if (e != hipSuccess) { rc = hipfail(E, e, "hipMalloc"); return; }
+      E->owned.push_back(p);
+      c.bn.scale = (float*)p; c.bn.shift = (float*)p + c.cout;
+    }
+    hipError_t e = launch_bn_affine(c.bn.g, c.bn.b, c.bn.m, c.bn.v, 1e-5f, c.bn.scale, c.bn.shift, c.cout, s);
+    if (e != hipSuccess) rc = hipfail(E, e, "launch_bn_affine");
+  };
+  if (R.stem[0].bn.scale) HIPCHK(E, hipDeviceSynchronize());      // a rebuild: another stream may still read the old vectors
+  for (ConvW& c : R.stem) one(c);
+  for (auto& st : R.stage) for (RNBlock& B : st) { one(B.c1); one(B.c2); one(B.c3); if (B.has_ds) one(B.ds); }
+  if (rc) return rc;
+  HIPCHK(E, hipStreamSynchronize(s));      // (the next forward may run on another stream)
+  R.ready = true;
+  return 0;
+}
+
+hipError_t rn_conv(const ConvW& c, const void* x, const void* resid, void* y, int B, int H, int W, int stride, int relu, hipStream_t s) {
+  ConvArgs a{x, c.w, c.bn.scale, c.bn.shift, resid, y, B, H, W, c.cin_pad, c.cout, c.k, stride, relu};
+  return launch_conv2d(a, s);
+}
+
+int resnet_fwd(Engine* E, const void* image, int image_dtype, int B, float* feat_out, hipStream_t s) {
+  ResNetW& R = E->rn;
+  if (int rc = prepare_resnet(E, s)) return rc;
+  const int res = R.a.image_resolution, w = R.a.width, g = res / 32, HW = g * g, T = HW + 1, Ech = 32 * w, e = R.a.output_dim;
+  if ((size_t)B * res * res / 4 * w > (size_t)1 << 40 || B > 65535) return fail(E, MVLPT_ERR_ARG, "image_fwd: batch too large");
+  // the largest map: the stem's last conv and the first stage's output, B * (res/2)^2 * w elements; five maps live at once
+  const size_t mapn = (size_t)B * (res / 2) * (res / 2) * w;
+  const size_t need = align256((size_t)B * res * res * 8 * 2) + 5 * align256(mapn * 2) + align256((size_t)B * T * Ech * 2) +
+                      align256((size_t)B * T * 2 * Ech * 2) + 2 * align256((size_t)B * Ech * 2) + 4096;
+  E->vs.valid = false;
+  HIPCHK(E, E->vis_ws.reserve(need));
+  Bump bp; bp.base = (char*)E->vis_ws.p; bp.cap = E->vis_ws.cap;
+  void* img8 = bp.take_bytes((size_t)B * res * res * 8 * 2);
+  void* buf[5];
+  for (void*& b : buf) b = bp.take_bytes(mapn * 2);
+  void* tok = bp.take_bytes((size_t)B * T * Ech * 2);
+  void* kv = bp.take_bytes((size_t)B * T * 2 * Ech * 2);
+  void* q16 = bp.take_bytes((size_t)B * Ech * 2);
+  void* o16 = bp.take_bytes((size_t)B * Ech * 2);
+  void *x = buf[0], *a = buf[1], *b = buf[2], *c = buf[3], *d = buf[4];
+
+  { ProfScope ps(E, s, PC_GLUE, 0, (double)B * res * res * (3.0 * 4.0 + 16.0));
+    HIPCHK(E, launch_nchw_to_nhwc8(image, image_dtype, img8, B, res, s)); }
+  int H = res / 2;      // the stem: conv3x3 stride 2, conv3x3, conv3x3 (each + BN + ReLU), AvgPool2d(2)
+  HIPCHK(E, rn_conv(R.stem[0], img8, nullptr, a, B, res, res, 2, 1, s));
+  HIPCHK(E, rn_conv(R.stem[1], a, nullptr, b, B, H, H, 1, 1, s));
+  HIPCHK(E, rn_conv(R.stem[2], b, nullptr, a, B, H, H, 1, 1, s));
+  HIPCHK(E, launch_avgpool2x2(a, x, B, H, H, w, s));
+  H /= 2;
+  for (int st = 0; st < 4; ++st)
+    for (const RNBlock& K : R.stage[st]) {
+      // Bottleneck (clip/model.py:10-55): every strided convolution is an average pool in front of a stride-1 convolution
+      const int Ho = H / K.stride;
+      HIPCHK(E, rn_conv(K.c1, x, nullptr, a, B, H, H, 1, 1, s));
+      HIPCHK(E, rn_conv(K.c2, a, nullptr, b, B, H, H, 1, 1, s));
+      const void* main_in = b;
+      if (K.stride > 1) { HIPCHK(E, launch_avgpool2x2(b, a, B, H, H, K.c2.cout, s)); main_in = a; }
+      const void* identity = x;
+      if (K.has_ds) {
+        const void* ds_in = x;
+        if (K.stride > 1) { HIPCHK(E, launch_avgpool2x2(x, c, B, H, H, K.ds.cin, s)); ds_in = c; }
+        HIPCHK(E, rn_conv(K.ds, ds_in, nullptr, d, B, Ho, Ho, 1, 0, s));
+        identity = d;
+      }
+      HIPCHK(E, rn_conv(K.c3, main_in, identity, b == main_in ? a : b, B, Ho, Ho, 1, 1, s));
+      void* out = b == main_in ? a : b;
+      if (out == a) { a = x; x = out; } else { b = x; x = out; }
+      H = Ho;
+    }
+  // AttentionPool2d (clip/model.py:58-91): only token 0's output is returned, so only its query is projected
+  { ProfScope ps(E, s, PC_GLUE, 0, (double)B * T * Ech * 4.0);
+    HIPCHK(E, launch_attnpool_tokens(x, R.pos, tok, B, HW, Ech, s)); }
+  HIPCHK(E, gemm(E, EPI_STORE16, tok, WRef{R.qw, Ech, 0}, B, Ech, Ech, R.qb, nullptr, nullptr, q16, nullptr, s, DT_F16, 0, nullptr, T * Ech));
+  HIPCHK(E, gemm(E, EPI_STORE16, tok, WRef{R.kvw, Ech, 0}, B * T, 2 * Ech, Ech, R.kvb, nullptr, nullptr, kv, nullptr, s, DT_F16));
+  { ProfScope ps(E, s, PC_ATTN_FWD, 4.0 * T * 64.0 * B * (Ech / 64), (double)B * T * 2 * Ech * 2.0);
+    HIPCHK(E, launch_attnpool_query(q16, kv, o16, B, T, Ech, s)); }
+  HIPCHK(E, gemm(E, EPI_STORE32, o16, WRef{R.cw, Ech, 0}, B, e, Ech, R.cb, nullptr, nullptr, feat_out, nullptr, s, DT_F16));
+  return 0;
+}
+
 }  // namespace
 
 // ================================================================================================ C ABI
@@ -711,6 +928,56 @@ int mvlpt_create(const MvlptArch* a, void** handle) {
   E->txt.blocks.resize(a->text_layers);
   const int K = 3 * a->patch_size * a->patch_size;
   E->Kp = (K + 63) / 64 * 64;
+  *handle = E;
+  return 0;
+}
+
+int mvlpt_create_resnet(const MvlptArch* a, const MvlptResNetArch* rn, void** handle) {
+  if (!a || !rn || !handle) return fail(nullptr, MVLPT_ERR_ARG, "null argument");
+  if (a->image_resolution || a->patch_size || a->vision_width || a->vision_layers || a->vision_heads)
+    return fail(nullptr, MVLPT_ERR_ARG, "create_resnet: the ViT vision fields of MvlptArch must be 0");
+  if (a->compute_dtype == MVLPT_DT_BF16) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "create_resnet: the ResNet tower computes in fp16 only");
+  if (a->compute_dtype != MVLPT_DT_F16) return fail(nullptr, MVLPT_ERR_ARG, "compute_dtype must be MVLPT_DT_F16");
+  if (a->text_width != a->text_heads * 64) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "head_dim must be 64");
+  if (a->text_width % 128 || a->embed_dim % 64) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "widths must be multiples of 128 and embed_dim of 64");
+  if (a->text_layers <= 0 || a->context_length <= 0) return fail(nullptr, MVLPT_ERR_ARG, "bad layer count / context length");
+  if (rn->image_resolution <= 0 || rn->image_resolution % 32) return fail(nullptr, MVLPT_ERR_ARG, "create_resnet: image_resolution must be a positive multiple of 32");
+  if (rn->width <= 0 || rn->width % 4) return fail(nullptr, MVLPT_ERR_ARG, "create_resnet: width must be a positive multiple of 4");
+  for (int i = 0; i < 4; ++i) if (rn->layers[i] <= 0) return fail(nullptr, MVLPT_ERR_ARG, "create_resnet: every stage needs at least one block");
+  if (rn->heads * 64 != 32 * rn->width) return fail(nullptr, MVLPT_ERR_ARG, "create_resnet: heads * 64 must equal 32 * width");
+  if (rn->output_dim != a->embed_dim) return fail(nullptr, MVLPT_ERR_ARG, "create_resnet: output_dim must equal embed_dim");
+  if (rn->width % 16 || rn->output_dim % 128)      // stem channels width / 2 in runs of 8; the projections run on the 128-column GEMM tiles
+    return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "create_resnet: width must be a multiple of 16 and output_dim of 128");
+  const int g = rn->image_resolution / 32;
+  if (g * g + 1 > attnpool_max_tokens()) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "create_resnet: more than 145 attention-pool tokens");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    return fail(nullptr, MVLPT_ERR_HIP, "no HIP device visible: libmvlpt_hip needs an AMD GPU (there is no CPU fallback)");
+  Engine* E = new Engine();
+  E->arch = *a; E->dt = a->compute_dtype;
+  if (const char* v = getenv("MVLPT_SPLIT_LO8")) E->lo8 = atoi(v) != 0;
+  if (const char* v = getenv("MVLPT_LN_FOLD")) E->fold_mode = atoi(v);
+  if (const char* v = getenv("MVLPT_LN_FOLD_MIN_ROWS")) E->fold_min_rows = atoi(v) > 0 ? atoi(v) : 1;
+  E->txt.width = a->text_width; E->txt.layers = a->text_layers; E->txt.heads = a->text_heads;
+  E->txt.blocks.resize(a->text_layers);
+  ResNetW& R = E->rn;
+  R.on = true; R.a = *rn;
+  const int w = rn->width;
+  auto conv = [](ConvW& c, int cin, int cout, int k) { c.cin = cin; c.cin_pad = (cin + 7) / 8 * 8; c.cout = cout; c.k = k; };
+  conv(R.stem[0], 3, w / 2, 3); conv(R.stem[1], w / 2, w / 2, 3); conv(R.stem[2], w / 2, w, 3);
+  int inplanes = w;
+  for (int st = 0; st < 4; ++st) {
+    const int planes = w << st;
+    R.stage[st].resize(rn->layers[st]);
+    for (int i = 0; i < rn->layers[st]; ++i) {
+      RNBlock& B = R.stage[st][i];
+      B.stride = (i == 0 && st > 0) ? 2 : 1;
+      B.has_ds = B.stride > 1 || inplanes != planes * 4;
+      conv(B.c1, inplanes, planes, 1); conv(B.c2, planes, planes, 3); conv(B.c3, planes, planes * 4, 1);
+      if (B.has_ds) conv(B.ds, inplanes, planes * 4, 1);
+      inplanes = planes * 4;
+    }
+  }
   *handle = E;
   return 0;
 }
@@ -789,6 +1056,7 @@ int mvlpt_set_ln_fold(void* h, int mode, int min_rows) {
 int mvlpt_set_vpt_dropout(void* h, const float* masks, int n_layers, int batch, int n_vpt, int width) {
   Engine* E = (Engine*)h;
   if (!E) return MVLPT_ERR_ARG;
+  if (E->rn.on) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "set_vpt_dropout");
   if (masks && (n_layers <= 0 || batch <= 0 || n_vpt <= 0 || width != E->arch.vision_width))
     return fail(E, MVLPT_ERR_ARG, "set_vpt_dropout: masks are [n_layers, batch, n_vpt, vision_width], every extent positive");
   E->vpt_mask = masks;
@@ -854,13 +1122,15 @@ int mvlpt_load_frozen(void* h, const char* name, const void* dev_ptr, int dtype,
   }
   const MvlptArch& A = E->arch;
   const int dv = A.vision_width, dtw = A.text_width, e = A.embed_dim;
-  const int G2 = (A.image_resolution / A.patch_size) * (A.image_resolution / A.patch_size);
+  const int G = A.patch_size > 0 ? A.image_resolution / A.patch_size : 0, G2 = G * G;      // (a ResNet handle has no patches)
   auto is1 = [&](int r) { return ndim == 1 && shape[0] == r; };
   auto is2 = [&](int r, int c) { return ndim == 2 && shape[0] == r && shape[1] == c; };
   int rc = 0;
   const char* vb = "visual.transformer.resblocks.";
   const char* tb = "transformer.resblocks.";
-  if (nm.rfind(vb, 0) == 0 || nm.rfind(tb, 0) == 0) {
+  if (E->rn.on && nm.rfind("visual.", 0) == 0) {
+    rc = rn_load(E, nm, p32, shape, ndim, s);
+  } else if (nm.rfind(vb, 0) == 0 || nm.rfind(tb, 0) == 0) {
     const bool isv = nm.rfind(vb, 0) == 0;
     int layer; const char* tail;
     if (!parse_block_name(name + strlen(isv ? vb : tb), &layer, &tail)) return fail(E, MVLPT_ERR_ARG, "malformed block name: " + nm);
@@ -963,6 +1233,7 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
                           int B, int save_for_bwd, int stop_block, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !image || B <= 0) return fail(E, MVLPT_ERR_ARG, "image_fwd: null/invalid argument");
+  if (E->rn.on) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "image_fwd_begin");
   if (E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_fwd_begin: a forward is pending (call image_fwd_resume or image_fwd_abandon first)");
   if (int rc = mvlpt_frozen_ready(h)) return rc;
   if ((n_vpt > 0) != (vpt != nullptr)) return fail(E, MVLPT_ERR_ARG, "image_fwd: vpt pointer and n_vpt disagree");
@@ -1048,6 +1319,7 @@ int mvlpt_image_fwd_abandon(void* h) {
 int mvlpt_image_fwd_resume(void* h, float* feat_out, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !feat_out) return fail(E, MVLPT_ERR_ARG, "image_fwd_resume: null argument");
+  if (E->rn.on) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "image_fwd_resume");
   if (!E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_fwd_resume: call image_fwd_begin first");
   E->ip.active = false;
   hipStream_t s = (hipStream_t)stream;
@@ -1114,6 +1386,12 @@ int mvlpt_image_fwd(void* h, const void* image, int image_dtype, const float* vp
                     int B, float* feat_out, int save_for_bwd, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !image || !feat_out || B <= 0) return fail(E, MVLPT_ERR_ARG, "image_fwd: null/invalid argument");
+  if (E->rn.on) {
+    if (vpt || vpt_deep || n_vpt || n_deep) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "visual prompts");
+    if (save_for_bwd) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "save_for_bwd");
+    if (int rc = mvlpt_frozen_ready(h)) return rc;
+    return resnet_fwd(E, image, image_dtype, B, feat_out, (hipStream_t)stream);
+  }
   if (int rc = mvlpt_image_fwd_begin(h, image, image_dtype, vpt, vpt_deep, n_vpt, n_deep, B, save_for_bwd, E->vis.layers, stream)) return rc;
   return mvlpt_image_fwd_resume(h, feat_out, stream);
 }
@@ -1121,6 +1399,7 @@ int mvlpt_image_fwd(void* h, const void* image, int image_dtype, const float* vp
 int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !dfeat) return fail(E, MVLPT_ERR_ARG, "image_bwd: null argument");
+  if (E->rn.on) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "image_bwd");
   TowerState& st = E->vs;
   if (E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_bwd: a forward is pending between image_fwd_begin and image_fwd_resume");
   if (!st.valid || !st.saved) return fail(E, MVLPT_ERR_STATE, "image_bwd: call image_fwd(save_for_bwd=1) first");
@@ -1847,6 +2126,50 @@ int mvlpt_op_attention_bwd(int dtype, const void* qkv, const void* out, const vo
   OPCHK(launch_attn_bwd(dtype, a, (hipStream_t)stream));
   return 0;
 }
+// ---- the convolutional tower at kernel level
+int mvlpt_op_pack_conv_weight(const float* w32, int Cout, int Cin, int k, int cin_pad, void* out, int* kp, mvlpt_stream_t stream) {
+  if (Cout <= 0 || Cin <= 0 || cin_pad < Cin || cin_pad % 8) return fail(nullptr, MVLPT_ERR_ARG, "op_pack_conv_weight: Cout, Cin > 0, cin_pad >= Cin, cin_pad % 8 == 0");
+  if (k != 1 && k != 3) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "op_pack_conv_weight: kernel size must be 1 or 3");
+  if (kp) *kp = conv_kp(k, cin_pad);
+  if (!out) return kp ? 0 : fail(nullptr, MVLPT_ERR_ARG, "op_pack_conv_weight: null pointer");
+  if (!w32) return fail(nullptr, MVLPT_ERR_ARG, "op_pack_conv_weight: null pointer");
+  OPCHK(launch_pack_conv_weight(w32, out, Cout, Cin, k, cin_pad, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_conv2d(const void* x, const void* w, const float* scale, const float* shift, const void* resid, void* y, int B, int H,
+                    int W, int Cin, int Cout, int k, int stride, int relu, mvlpt_stream_t stream) {
+  ConvArgs a{x, w, scale, shift, resid, y, B, H, W, Cin, Cout, k, stride, relu};
+  if (const char* why = conv2d_check(a)) {
+    const bool arg = !x || !w || !scale || !shift || !y || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0;
+    return fail(nullptr, arg ? MVLPT_ERR_ARG : MVLPT_ERR_UNSUPPORTED, std::string("op_conv2d: ") + why);
+  }
+  OPCHK(launch_conv2d(a, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_avgpool2x2(const void* x, void* y, int B, int H, int W, int C, mvlpt_stream_t stream) {
+  if (!x || !y || B <= 0 || H < 2 || W < 2 || C <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_avgpool2x2: null pointer or empty map");
+  if (C % 8) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "op_avgpool2x2: C must be a multiple of 8");
+  OPCHK(launch_avgpool2x2(x, y, B, H, W, C, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_nchw_to_nhwc8(const void* image, int image_dtype, void* out, int B, int R, mvlpt_stream_t stream) {
+  if (!image || !out || B <= 0 || R <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_nchw_to_nhwc8: null pointer or empty image");
+  if (image_dtype != MVLPT_DT_F32 && image_dtype != MVLPT_DT_F16 && image_dtype != MVLPT_DT_BF16) return fail(nullptr, MVLPT_ERR_ARG, "op_nchw_to_nhwc8: unknown image dtype");
+  OPCHK(launch_nchw_to_nhwc8(image, image_dtype, out, B, R, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_attnpool_tokens(const void* x, const float* pos, void* tok, int B, int HW, int E, mvlpt_stream_t stream) {
+  if (!x || !pos || !tok || B <= 0 || B > 65535 || HW <= 0 || E <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_attnpool_tokens: null pointer or extent out of range");
+  OPCHK(launch_attnpool_tokens(x, pos, tok, B, HW, E, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_attnpool_query(const void* q, const void* kv, void* out, int B, int T, int E, mvlpt_stream_t stream) {
+  if (!q || !kv || !out || B <= 0 || B > 65535 || T <= 0 || E <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_attnpool_query: null pointer or extent out of range");
+  if (T > attnpool_max_tokens() || E % 64) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "op_attnpool_query: T <= 145 and E % 64 == 0");
+  OPCHK(launch_attnpool_query(q, kv, out, B, T, E, (hipStream_t)stream));
+  return 0;
+}
+
 int mvlpt_op_cast(int dtype, const float* in, void* out, int64_t n, mvlpt_stream_t stream) {
   OPCHK(launch_cast_f32_to16(dtype, in, out, (size_t)n, nullptr, (hipStream_t)stream));
   return 0;

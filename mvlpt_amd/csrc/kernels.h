@@ -314,6 +314,32 @@ hipError_t launch_logits_ranged_bwd(const float* dlogits, const float* imn, cons
                                     float scale, const int32_t* lo, const int32_t* start, const int32_t* seq_grp, float* dimg, float* dtxt,
                                     int G, int S, int C, int e, hipStream_t s);
 
+// ---------------------------------------------------------------- convolutional tower (conv.hip; fp16 only, forward only)
+// y [B,Ho,Wo,Cout] = act(conv(x [B,H,W,Cin], w) * scale[c] + shift[c] (+ resid [B,Ho,Wo,Cout])), NHWC fp16, one rounding.
+// k in {1, 3}, pad k/2, stride 1 (2 with k = 3 only), Cin % 8 == 0, Cout % 8 == 0; w is the packed [Cout, conv_kp(k, Cin)] weight of
+// launch_pack_conv_weight; scale / shift fp32 [Cout], 16-byte aligned.
+struct ConvArgs {
+  const void* x; const void* w; const float* scale; const float* shift; const void* resid; void* y;
+  int B, H, W, Cin, Cout, k, stride, relu;
+};
+int conv_kp(int k, int cin_pad);                     // packed row length: k*k*cin_pad rounded up to the K-step
+const char* conv2d_check(const ConvArgs& a);         // null when the launch is legal, else what is wrong with it
+hipError_t launch_conv2d(const ConvArgs& a, hipStream_t s);
+// w32 [Cout,Cin,k,k] fp32 -> out [Cout, conv_kp(k, cin_pad)] fp16, tap-major (ky, kx, ci), channels Cin .. cin_pad-1 and the tail zero
+hipError_t launch_pack_conv_weight(const float* w32, void* out, int Cout, int Cin, int k, int cin_pad, hipStream_t s);
+// BatchNorm with running statistics as an affine map: scale = g / sqrt(var + eps), shift = b - mean * scale
+hipError_t launch_bn_affine(const float* g, const float* b, const float* mean, const float* var, float eps, float* scale, float* shift,
+                            int C, hipStream_t s);
+// AvgPool2d(2) on NHWC fp16 (fp32 sum, one rounding); C % 8 == 0, odd H / W drop their last row / column as torch does
+hipError_t launch_avgpool2x2(const void* x, void* y, int B, int H, int W, int C, hipStream_t s);
+// image [B,3,R,R] (fp32 / fp16 / bf16) -> [B,R,R,8] fp16, channels 3..7 zero
+hipError_t launch_nchw_to_nhwc8(const void* image, int image_dtype, void* out, int B, int R, hipStream_t s);
+// AttentionPool2d: tok [B, 1+HW, E] fp16 = [mean over HW (fp32) ; x] + pos [1+HW, E] fp32;  out [B,E] = single-query attention of
+// q [B,E] over kv [B,T,2E] = [K | V], heads of 64, fp32 scores and softmax, T <= attnpool_max_tokens()
+int attnpool_max_tokens();
+hipError_t launch_attnpool_tokens(const void* x, const float* pos, void* tok, int B, int HW, int E, hipStream_t s);
+hipError_t launch_attnpool_query(const void* q, const void* kv, void* out, int B, int T, int E, hipStream_t s);
+
 // ---------------------------------------------------------------- nearest table rows (nearest.hip; semantics in include/mvlpt_hip.h)
 // Geometry of one call: row tiles of NR_ROWS query rows (grid.y) x vocabulary slices (grid.x), NR_WAVES partial lists of k keys per
 // row and slice.  The slice count follows the stream's compute units; the results do not depend on it.  The arguments are checked by

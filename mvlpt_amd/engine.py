@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import DT_BF16, DT_F16, DT_F32, lib
-from .weights import ClipArch, arch_from_state_dict
+from .weights import ClipArch, arch_from_state_dict, is_resnet
 
 _TORCH2DT = {torch.float32: DT_F32, torch.float16: DT_F16, torch.bfloat16: DT_BF16}
 _DT2TORCH = {DT_F16: torch.float16, DT_BF16: torch.bfloat16, DT_F32: torch.float32}
@@ -107,12 +107,24 @@ class Engine:
         self.arch = arch
         self.dt = {"fp16": DT_F16, "bf16": DT_BF16}[compute_dtype]
         self.torch_dtype = _DT2TORCH[self.dt]
-        a = _lib.MvlptArch(arch.image_resolution, arch.vision_patch_size, arch.vision_width, arch.vision_layers,
-                           arch.vision_heads, arch.context_length, arch.transformer_width, arch.transformer_layers,
-                           arch.transformer_heads, arch.embed_dim, self.dt)
+        self.resnet = is_resnet(arch)
         h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(lib.mvlpt_create(C.byref(a), C.byref(h)), None, "mvlpt_create")
+        if self.resnet:
+            # the image tower is CLIP's ModifiedResNet: frozen, forward-only, fp16 (include/mvlpt_hip.h: mvlpt_create_resnet)
+            if compute_dtype != "fp16":
+                raise ValueError("a ResNet backbone computes in fp16 only (compute_dtype='bf16' is not supported)")
+            a = _lib.MvlptArch(0, 0, 0, 0, 0, arch.context_length, arch.transformer_width, arch.transformer_layers,
+                               arch.transformer_heads, arch.embed_dim, self.dt)
+            rn = _lib.MvlptResNetArch(arch.image_resolution, arch.vision_width, (C.c_int * 4)(*arch.vision_layers),
+                                      arch.vision_heads, arch.embed_dim)
+            with torch.cuda.device(self.device):
+                _lib.check(lib.mvlpt_create_resnet(C.byref(a), C.byref(rn), C.byref(h)), None, "mvlpt_create_resnet")
+        else:
+            a = _lib.MvlptArch(arch.image_resolution, arch.vision_patch_size, arch.vision_width, arch.vision_layers,
+                               arch.vision_heads, arch.context_length, arch.transformer_width, arch.transformer_layers,
+                               arch.transformer_heads, arch.embed_dim, self.dt)
+            with torch.cuda.device(self.device):
+                _lib.check(lib.mvlpt_create(C.byref(a), C.byref(h)), None, "mvlpt_create")
         self.h = h
         self.precision = _lib.PREC_SPLIT_GRAD
         self._keep: List[torch.Tensor] = []     # tensors the library reads asynchronously / later
@@ -144,6 +156,9 @@ class Engine:
         """Per-image dropout masks of the visual prompt rows for the next image_fwd / image_bwd pair (include/mvlpt_hip.h:
         mvlpt_set_vpt_dropout): fp32 [n_layers, B, n_vpt, width], or None to clear.  One-shot: the next image_fwd consumes the setting
         (and keeps the tensor alive for its backward); a forward without a new call runs without dropout."""
+        if self.resnet and masks is None:
+            return      # nothing to clear: the tower takes no prompts
+        self._refuse_on_resnet("visual prompt dropout")
         if masks is not None:
             masks = _req(masks, torch.float32, "vpt dropout masks")
             if masks.dim() != 4 or masks.shape[-1] != self.arch.vision_width:
@@ -151,6 +166,13 @@ class Engine:
         self._vpt_masks = masks
         sh = (0, 0, 0, 0) if masks is None else tuple(int(v) for v in masks.shape)
         _lib.check(lib.mvlpt_set_vpt_dropout(self.h, _ptr(masks), *sh), self.h, "set_vpt_dropout")
+
+    def _refuse_on_resnet(self, what: str) -> None:
+        """The ResNet tower is frozen and runs forward-only in one piece; the reference cannot prompt it either
+        (trainers/mvlpt.py:48 "HACK: Assume all is vision transformer")."""
+        if self.resnet:
+            raise ValueError(f"{what} is not available on a ResNet backbone ({self.arch.name}): the tower is frozen and forward-only "
+                             "(the reference's trainers/mvlpt.py:48 assumes a vision transformer for visual prompts)")
 
     def debug_checksums(self, enable: bool = True):
         """mvlpt_debug_checksums: the stage fingerprints of the last image_fwd (list of ints) and the new on / off state."""
@@ -186,6 +208,8 @@ class Engine:
             for name, t in sd.items():
                 if name in ("logit_scale", "token_embedding.weight", "input_resolution", "context_length", "vocab_size"):
                     continue
+                if name.endswith(".num_batches_tracked"):      # BatchNorm's step counter: not a weight
+                    continue
                 if t.dtype not in _TORCH2DT:
                     t = t.float()
                 tg = t.to(self.device).contiguous()
@@ -218,6 +242,10 @@ class Engine:
     @_on_device
     def image_fwd(self, image: torch.Tensor, vpt: Optional[torch.Tensor] = None, vpt_deep: Optional[torch.Tensor] = None,
                   save_for_bwd: bool = False) -> torch.Tensor:
+        if vpt is not None or vpt_deep is not None:
+            self._refuse_on_resnet("visual prompts")
+        if save_for_bwd:
+            self._refuse_on_resnet("an image tower backward (save_for_bwd)")
         image, vpt, vpt_deep, n_vpt, n_deep, B, m = self._image_args(image, vpt, vpt_deep)
         feat = torch.empty(B, self.arch.embed_dim, device=image.device, dtype=torch.float32)
         _lib.check(lib.mvlpt_image_fwd(self.h, _ptr(image), _TORCH2DT[image.dtype], _ptr(vpt), _ptr(vpt_deep), n_vpt, n_deep, B,
@@ -232,6 +260,7 @@ class Engine:
                         save_for_bwd: bool = False, stop_block: Optional[int] = None) -> None:
         """First part of image_fwd on the current stream (mvlpt_image_fwd_begin): the tower entry and blocks [0, stop_block);
         None: everything ahead of the last block.  image_fwd_resume finishes the forward; the engine holds one pending forward."""
+        self._refuse_on_resnet("image_fwd_begin / image_fwd_resume")
         image, vpt, vpt_deep, n_vpt, n_deep, B, m = self._image_args(image, vpt, vpt_deep)
         stop = self.arch.vision_layers if stop_block is None else int(stop_block)
         _lib.check(lib.mvlpt_image_fwd_begin(self.h, _ptr(image), _TORCH2DT[image.dtype], _ptr(vpt), _ptr(vpt_deep), n_vpt, n_deep, B,
@@ -245,6 +274,7 @@ class Engine:
     def image_fwd_resume(self) -> torch.Tensor:
         """Second part of the pending forward on the current stream (mvlpt_image_fwd_resume) -> features [B, embed] fp32.  The caller
         orders this stream behind the one image_fwd_begin ran on."""
+        self._refuse_on_resnet("image_fwd_begin / image_fwd_resume")
         pend = self._img_pending
         if pend is None:
             raise RuntimeError("image_fwd_resume without image_fwd_begin")
@@ -267,6 +297,7 @@ class Engine:
 
     @_on_device
     def image_bwd(self, dfeat: torch.Tensor) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+        self._refuse_on_resnet("an image tower backward")
         if self._img_state is None:
             raise RuntimeError("image_bwd without image_fwd(save_for_bwd=True)")
         n_vpt, n_deep, B = self._img_state
@@ -1122,3 +1153,74 @@ def op_gemm_folded(x16, Bt, colsum, bias2, part, nt, epi=_lib.EPI_STORE16, a_spl
     _lib.check(lib.mvlpt_op_gemm_folded(_TORCH2DT[dtype], epi, _ptr(x16), a_split, _ptr(Bt), ldb, w8_exp, M, N, K, _ptr(colsum), _ptr(bias2),
                                         _ptr(part), part.shape[1], nt, _ptr(out), _ptr(o2), _stream()), None, "op_gemm_folded")
     return (out, o2) if out2 else out
+
+
+# ------------------------------------------------------------------------------------------------ convolutional tower at kernel level
+def conv_out_size(n: int, k: int, stride: int) -> int:
+    return (n + 2 * (k // 2) - k) // stride + 1
+
+
+def op_pack_conv_weight(w32: torch.Tensor, cin_pad: Optional[int] = None) -> torch.Tensor:
+    """w32 [Cout, Cin, k, k] fp32 -> the packed fp16 [Cout, Kp] weight of mvlpt_op_conv2d (tap-major, zero padded)."""
+    w32 = _req(w32, torch.float32, "w32")
+    cout, cin, k, _ = w32.shape
+    cin_pad = cin_pad or (cin + 7) // 8 * 8
+    kp = C.c_int(0)
+    _lib.check(lib.mvlpt_op_pack_conv_weight(None, cout, cin, k, cin_pad, None, C.byref(kp), _stream()), None, "op_pack_conv_weight")
+    out = torch.empty(cout, kp.value, device=w32.device, dtype=torch.float16)
+    _lib.check(lib.mvlpt_op_pack_conv_weight(_ptr(w32), cout, cin, k, cin_pad, _ptr(out), None, _stream()), None, "op_pack_conv_weight")
+    return out
+
+
+def op_conv2d_raw(x, w, scale, shift, resid, y, B, H, W, Cin, Cout, k, stride, relu) -> int:
+    """mvlpt_op_conv2d with nothing checked on this side: returns the library's code."""
+    return lib.mvlpt_op_conv2d(_ptr(x), _ptr(w), _ptr(scale), _ptr(shift), _ptr(resid), _ptr(y), B, H, W, Cin, Cout, k, stride,
+                               int(relu), _stream())
+
+
+def op_conv2d(x: torch.Tensor, w_packed: torch.Tensor, scale, shift, k: int, stride: int = 1, relu: bool = False, resid=None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [B, H, W, Cin] fp16 NHWC -> [B, Ho, Wo, Cout] fp16 (include/mvlpt_hip.h: mvlpt_op_conv2d)."""
+    B, H, W, cin = x.shape
+    cout = w_packed.shape[0]
+    ho, wo = conv_out_size(H, k, stride), conv_out_size(W, k, stride)
+    if out is None:
+        out = torch.empty(B, ho, wo, cout, device=x.device, dtype=torch.float16)
+    _lib.check(op_conv2d_raw(_req(x, torch.float16, "x"), w_packed, _req(scale, torch.float32, "scale"), _req(shift, torch.float32, "shift"),
+                             resid, out, B, H, W, cin, cout, k, stride, relu), None, "op_conv2d")
+    return out
+
+
+def op_avgpool2x2(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    B, H, W, c = x.shape
+    if out is None:
+        out = torch.empty(B, H // 2, W // 2, c, device=x.device, dtype=torch.float16)
+    _lib.check(lib.mvlpt_op_avgpool2x2(_ptr(_req(x, torch.float16, "x")), _ptr(out), B, H, W, c, _stream()), None, "op_avgpool2x2")
+    return out
+
+
+def op_nchw_to_nhwc8(image: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    image = image.contiguous()
+    B, _, R, _ = image.shape
+    if out is None:
+        out = torch.empty(B, R, R, 8, device=image.device, dtype=torch.float16)
+    _lib.check(lib.mvlpt_op_nchw_to_nhwc8(_ptr(image), _TORCH2DT[image.dtype], _ptr(out), B, R, _stream()), None, "op_nchw_to_nhwc8")
+    return out
+
+
+def op_attnpool_tokens(x: torch.Tensor, pos: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    B, HW, E = x.shape
+    if out is None:
+        out = torch.empty(B, HW + 1, E, device=x.device, dtype=torch.float16)
+    _lib.check(lib.mvlpt_op_attnpool_tokens(_ptr(_req(x, torch.float16, "x")), _ptr(_req(pos, torch.float32, "pos")), _ptr(out), B, HW, E,
+                                            _stream()), None, "op_attnpool_tokens")
+    return out
+
+
+def op_attnpool_query(q: torch.Tensor, kv: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    B, T, E2 = kv.shape
+    if out is None:
+        out = torch.empty(B, E2 // 2, device=q.device, dtype=torch.float16)
+    _lib.check(lib.mvlpt_op_attnpool_query(_ptr(_req(q, torch.float16, "q")), _ptr(_req(kv, torch.float16, "kv")), _ptr(out), B, T, E2 // 2,
+                                           _stream()), None, "op_attnpool_query")
+    return out

@@ -295,8 +295,9 @@ def linear_probe(train, val, test, num_step: int = 8, num_run: int = 10, shots: 
 # ------------------------------------------------------------------------------------------------ features and their files
 def extract_features(clip, batches: Iterable) -> Tuple[np.ndarray, np.ndarray]:
     """(features [n, embed] fp32, labels [n] int64) of an iterable of (images, labels): FrozenCLIP.encode_image per batch, un-normalised
-    as the reference's clip_model.visual(data) is (lpclip/feat_extractor.py:155), rows in input order.  The tower is whatever ViT the
-    FrozenCLIP holds; the reference hard-codes RN50, which this engine does not have."""
+    as the reference's clip_model.visual(data) is (lpclip/feat_extractor.py:155), rows in input order.  The tower is whatever the
+    FrozenCLIP holds: the reference hard-codes RN50 (mvlpt_amd.weights.RESNET_ARCHS["RN50"], the convolutional tower of
+    mvlpt_create_resnet); any ViT of ARCHS works the same way."""
     feats, labels = [], []
     for images, lab in batches:
         feats.append(clip.encode_image(images).float().cpu().numpy())

@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from ._lib import TEXT_MIN_L
 from .engine import Engine
-from .weights import ClipArch, _randn, arch_from_state_dict
+from .weights import ClipArch, _randn, arch_from_state_dict, is_resnet
 
 # compute units of the text tower's partition in the two-tower pipeline (CustomCLIP.set_cu_partition); 0 = no partition.
 # Overridden by the environment variable MVLPT_TEXT_CUS.
@@ -294,6 +294,9 @@ class MultitaskVLPromptLearner(nn.Module):
                                       "mvlpt_amd.mvlpt_cocoop (MultitaskVLPromptLearner / CustomCLIP there; MVLPT.build_model picks them)")
         arch = clip_model.arch
         dtype = clip_model.dtype
+        if is_resnet(arch) and vpt_n_ctx != 0:
+            raise ValueError("visual prompts (VPT.N_CTX != 0, UPT) need a ViT backbone: a ResNet tower is frozen and forward-only here, and the "
+                             "reference cannot prompt it either (trainers/mvlpt.py:48 \"HACK: Assume all is vision transformer\")")
         coop_ctx_dim, vpt_ctx_dim = arch.transformer_width, arch.vision_width
         clip_imsize, cfg_imsize = arch.image_resolution, cfg.INPUT.SIZE[0]
         assert cfg_imsize == clip_imsize, f"cfg_imsize ({cfg_imsize}) must equal to clip_imsize ({clip_imsize})"
@@ -725,6 +728,8 @@ class CustomCLIP(nn.Module):
     def split_active(self) -> bool:
         """The prefetch split applies: a split is set and nothing makes today's schedule the only one (the towers on one stream,
         visual prompts, a class-sharded text tower, a CU partition, a tower with fewer blocks than the split point)."""
+        if getattr(self.engine, "resnet", False):
+            return False      # a ResNet tower runs in one piece (no mvlpt_image_fwd_begin / _resume): the whole-tower prefetch stays
         layers = getattr(getattr(self.engine, "arch", None), "vision_layers", 0)
         # (a split point past the last full-width block is not a split of THIS tower: a default found on twelve blocks leaves a
         # two-block test tower in one piece; stop_block = layers - 1 is the old early-prefetch schedule, kept as the control)

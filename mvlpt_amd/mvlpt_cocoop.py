@@ -42,6 +42,7 @@ from . import _lib
 from .cocoop import DEFAULT_MAX_TEXT_WORKSPACE_BYTES, MAX_SEQUENCES_PER_TOWER
 from .model import FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, _text_inputs, build_prompt_layout
 from .model import MultitaskVLPromptLearner as _BasePromptLearner
+from .weights import is_resnet
 
 
 class MultitaskVLPromptLearner(_BasePromptLearner):
@@ -60,6 +61,9 @@ class MultitaskVLPromptLearner(_BasePromptLearner):
                                       "depend on (trainers/mvlpt.py:556-571); set COOP.N_CTX 0")
         arch = clip_model.arch
         dtype = clip_model.dtype                                                        # fp32 masters (module docstring)
+        if is_resnet(arch) and vpt_n_ctx != 0:
+            raise ValueError("visual prompts (VPT.N_CTX != 0, UPT) need a ViT backbone: a ResNet tower is frozen and forward-only here, and the "
+                             "reference cannot prompt it either (trainers/mvlpt.py:48 \"HACK: Assume all is vision transformer\")")
         cocoop_ctx_dim, vpt_ctx_dim, vis_dim = arch.transformer_width, arch.vision_width, arch.embed_dim
         clip_imsize, cfg_imsize = arch.image_resolution, cfg.INPUT.SIZE[0]
         assert cfg_imsize == clip_imsize, f"cfg_imsize ({cfg_imsize}) must equal to clip_imsize ({clip_imsize})"

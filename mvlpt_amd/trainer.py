@@ -26,7 +26,7 @@ import torch
 from . import distributed as dist_utils
 from .config import CfgNode
 from .model import CustomCLIP, FrozenCLIP
-from .weights import ARCHS, make_state_dict
+from .weights import RESNET_ARCHS, get_arch, make_state_dict
 
 
 # ------------------------------------------------------------------------------------------------ Dassl stand-ins
@@ -468,6 +468,10 @@ class MVLPT(TrainerX):
                  fp16 mode; there is no GradScaler object, self.scaler stays None)
           fp32 : every tower in the split-operand mode, forward-only towers included (~22-bit products)."""
         assert cfg.TRAINER.MVLPT.PREC in ["fp16", "fp32", "amp"]        # :835-836
+        if cfg.MODEL.BACKBONE.NAME in RESNET_ARCHS and cfg.TRAINER.MVLPT.VPT.N_CTX != 0:
+            # (a state dict passed to the trainer is checked again where the prompt learner is built)
+            raise ValueError("visual prompts (VPT.N_CTX != 0, UPT) need a ViT backbone: a ResNet tower is frozen and forward-only here, and the "
+                             "reference cannot prompt it either (trainers/mvlpt.py:48 \"HACK: Assume all is vision transformer\")")
         if cfg.TRAINER.MVLPT.COCOOP.N_CTX != 0:
             # the image-conditioned route (mvlpt_amd.mvlpt_cocoop): all three run with split operands in every tower, see CustomCLIP there
             assert cfg.TRAINER.MVLPT.COCOOP.PREC in ["fp16", "fp32", "amp"]
@@ -495,7 +499,7 @@ class MVLPT(TrainerX):
         sd = self._sd_arg
         if sd is None:
             # no network: synthetic frozen weights of the named architecture (clip/clip.py:57 would download)
-            sd = make_state_dict(ARCHS[cfg.MODEL.BACKBONE.NAME], seed=cfg.SEED)
+            sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED)
         # PREC (see check_cfg): fp16 / amp -> split operands only where gradients flow; fp32 -> in every tower;
         # GRAD_PRECISION = "fast" (not in the reference) drops the split operands altogether (gradients within ~4e-3)
         prec = "split_all" if cfg.TRAINER.MVLPT.PREC == "fp32" else cfg.TRAINER.MVLPT.GRAD_PRECISION

@@ -21,7 +21,7 @@ import torch
 
 from .model import FrozenCLIP
 from .trainer import MVLPT, TrainerX
-from .weights import ARCHS, make_state_dict
+from .weights import get_arch, make_state_dict
 
 
 def build_prompts(templates: Sequence[str], classnames: Sequence[str]) -> List[str]:
@@ -56,7 +56,7 @@ class ZeroshotCLIP(MVLPT):
         self.templates = read_templates(cfg, self.single_template)      # an instance attribute, rebuilt from the config every time
         sd = self._sd_arg
         if sd is None:
-            sd = make_state_dict(ARCHS[cfg.MODEL.BACKBONE.NAME], seed=cfg.SEED, include_token_embedding=True)
+            sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED, include_token_embedding=True)
         clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device,
                                 precision=cfg.TRAINER.MVLPT.GRAD_PRECISION)   # text tower: split operands unless "fast"
         prompts = build_prompts(self.templates, classnames)

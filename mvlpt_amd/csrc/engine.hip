@@ -163,6 +163,17 @@ struct TowerState {
 };
 constexpr int FOLD_NTP = 8;              // slots per row the buffers are sized for (gemm.hip: FOLD_MAX_NTP)
 
+// The R rows of a tower's last block whose output is read (image: the CLS row of every image; text: the EOT row of every sequence),
+// gathered into compact [R, ·] buffers: out-projection, ln_2, the MLP and the closing LayerNorm run on these rows only
+// (last_block_fwd / last_block_bwd).  The 16-bit buffers hold hi|lo pairs in a split tower.
+struct Compact {
+  bool kept = false;                     // the forward kept what last_block_bwd reads
+  float *x32 = nullptr, *xm32 = nullptr, *xo32 = nullptr;      // block input, ln_2 input, closing LayerNorm input
+  float *out32 = nullptr, *dout32 = nullptr;                   // closing LayerNorm output (the projection's input) and its gradient
+  void *a16 = nullptr, *h16 = nullptr, *g16 = nullptr, *u16 = nullptr;      // attention output, ln_2 output, GELU output, pre-GELU
+  float *dx32 = nullptr, *dh32 = nullptr; void *dx16 = nullptr, *dO16 = nullptr, *du16 = nullptr;
+};
+
 enum ProfClass { PC_GEMM = 0, PC_ATTN_FWD, PC_ATTN_BWD, PC_LN_FWD, PC_LN_BWD, PC_GLUE, PC_HEAD, PC_ATTN_FWD_IMG, PC_COUNT };
 static const char* kProfNames[PC_COUNT] = {"gemm_bt", "attention_fwd", "attention_bwd", "layernorm_fwd", "layernorm_bwd",
                                            "glue", "head_logits_ce", "attention_fwd_image"};
@@ -207,13 +218,10 @@ struct Engine {
   DevBuf vis_ws, txt_ws, head_ws, ce_ws, tmp, pp_ws, near_ws;
   TowerState vs, ts;
   // vision fwd extras (carved from vis_ws)
-  int vB = 0, v_nvpt = 0, v_ndeep = 0; float* cls32 = nullptr; float* dcls32 = nullptr;
-  float* xc32 = nullptr; void *ac16 = nullptr, *hc16 = nullptr, *gc16 = nullptr;   // CLS-only last layer (compact [B,·])
-  // ... and what its backward needs (VPT / UPT): saved LN inputs, pre-GELU, and the compact gradient buffers
+  int vB = 0, v_nvpt = 0, v_ndeep = 0;
+  Compact vc;                            // CLS-only last image block (compact [B,·] rows)
   // mvlpt_image_fwd_begin .. mvlpt_image_fwd_resume: what crosses the cut (the rest is in vs / the v_* fields above)
   struct ImgPending { bool active = false, packed = false, ln1_ready = false, save = false; int next = 0; const float* vpt_deep = nullptr; } ip;
-  bool v_cls_last = false; float *xcm32 = nullptr, *xco32 = nullptr, *dxc32 = nullptr, *dhc32 = nullptr;
-  void *uc16 = nullptr, *duc16 = nullptr, *dxc16 = nullptr, *dOc16 = nullptr;
   // text fwd extras
   int tC = 0, tL = 0, t_nctx = 0, t_per_class = 0; int32_t* eot_rows = nullptr; int32_t* ctx_pos = nullptr;
   TextKind t_kind = TextKind::Plain;   // the last text forward
@@ -221,10 +229,7 @@ struct Engine {
   int t_groups = 0; const int32_t *t_rlo = nullptr, *t_rstart = nullptr;
   std::vector<int32_t> t_range_host, h_range_host;   // host images of the range tables (source of the asynchronous upload)
   std::vector<int32_t> t_ids_host;   // mvlpt_text_encode_tokens: [ids (S * L, trimmed rows) | eot rows (S)], checked on the host
-  // EOT-only last text block (compact [C,·] rows; the text-side twin of the CLS-only last image block)
-  bool t_eot_last = false; float *txc32 = nullptr, *txm32 = nullptr, *txo32 = nullptr, *tdxc32 = nullptr, *tdhc32 = nullptr;
-  void *tac16 = nullptr, *thc16 = nullptr, *tgc16 = nullptr, *tuc16 = nullptr, *tduc16 = nullptr, *tdxc16 = nullptr, *tdOc16 = nullptr;
-  float* eot32 = nullptr; float* deot32 = nullptr;
+  Compact tc;                            // EOT-only last text block (compact [C,·] rows)
   // head state
   int hB = 0, hC = 0; float h_scale = 0.f; const int32_t *h_lo = nullptr, *h_hi = nullptr;
   HeadKind h_kind = HeadKind::Plain;   // the last head forward; a backward runs only after the forward of its own name
@@ -245,15 +250,21 @@ int hipfail(Engine* E, hipError_t e, const char* what) {
 }
 #define HIPCHK(E, call) do { hipError_t _e = (call); if (_e != hipSuccess) return hipfail((E), _e, #call); } while (0)
 
+// Two events of the profiling pool, which grows by 512 up to 65 536 events; false: none left (the launch then goes unrecorded)
+bool take_events(Engine* E, hipEvent_t* a, hipEvent_t* b) {
+  if (E->ev_used + 2 > E->ev_pool.size() && E->ev_pool.size() < 65536)
+    for (int i = 0; i < 512; ++i) { hipEvent_t ev; if (hipEventCreate(&ev) != hipSuccess) break; E->ev_pool.push_back(ev); }
+  if (E->ev_used + 2 > E->ev_pool.size()) return false;
+  *a = E->ev_pool[E->ev_used++]; *b = E->ev_pool[E->ev_used++];
+  return true;
+}
+
 struct ProfScope {
   Engine* E; hipStream_t s; bool on = false; hipEvent_t b{};
   ProfScope(Engine* E_, hipStream_t s_, int cls, double flops, double bytes) : E(E_), s(s_) {
     if (!E || !E->prof_on || !E->prof_all) return;   // marker events cost ~1.5 us each: only in the full-breakdown mode
-    if (E->ev_used + 2 > E->ev_pool.size()) {
-      if (E->ev_pool.size() >= 65536) return;
-      for (int i = 0; i < 512; ++i) { hipEvent_t ev; if (hipEventCreate(&ev) != hipSuccess) return; E->ev_pool.push_back(ev); }
-    }
-    hipEvent_t a = E->ev_pool[E->ev_used++]; b = E->ev_pool[E->ev_used++];
+    hipEvent_t a{};
+    if (!take_events(E, &a, &b)) return;
     (void)hipEventRecord(a, s);
     E->prof.push_back(ProfRec{cls, a, b, flops, bytes, flops});
     on = true;
@@ -271,14 +282,8 @@ static void dbg_ck(Engine* E, const void* p, size_t bytes, hipStream_t s) {
 // profiling is on (class "attention_fwd_image": bench.py's roofline.image_attention_fwd)
 static hipError_t attn_fwd_timed(Engine* E, const AttnArgs& a, double flops, double bytes, hipStream_t s) {
   hipEvent_t ea = nullptr, eb = nullptr;
-  if (E && E->prof_on && !E->prof_all) {
-    if (E->ev_used + 2 > E->ev_pool.size() && E->ev_pool.size() < 65536)
-      for (int i = 0; i < 512; ++i) { hipEvent_t ev; if (hipEventCreate(&ev) != hipSuccess) break; E->ev_pool.push_back(ev); }
-    if (E->ev_used + 2 <= E->ev_pool.size()) {
-      ea = E->ev_pool[E->ev_used++]; eb = E->ev_pool[E->ev_used++];
-      E->prof.push_back(ProfRec{PC_ATTN_FWD_IMG, ea, eb, flops, bytes, flops});
-    }
-  }
+  if (E && E->prof_on && !E->prof_all && take_events(E, &ea, &eb))
+    E->prof.push_back(ProfRec{PC_ATTN_FWD_IMG, ea, eb, flops, bytes, flops});
   return launch_attn_fwd(E->dt, a, s, ea, eb);
 }
 
@@ -305,18 +310,13 @@ hipError_t gemm(Engine* E, int epi, const void* A, WRef Bt, int M, int N, int K,
                     (epi == EPI_GELUBWD_SPLIT ? 6.0 : 2.0)));
   // the dominant kernel is timed by its own dispatch (start/stop timestamps of the AQL packet): no marker packets
   hipEvent_t ea = nullptr, eb = nullptr;
-  if (E && E->prof_on) {
-    if (E->ev_used + 2 > E->ev_pool.size() && E->ev_pool.size() < 65536)
-      for (int i = 0; i < 512; ++i) { hipEvent_t ev; if (hipEventCreate(&ev) != hipSuccess) break; E->ev_pool.push_back(ev); }
-    if (E->ev_used + 2 <= E->ev_pool.size()) {
-      ea = E->ev_pool[E->ev_used++]; eb = E->ev_pool[E->ev_used++];
-      // flops = ALGORITHMIC (what the reference's fp32 GEMM does: 2MNK); the split-precision modes execute twice that
-      // (16-bit pair) or 1.5x in 16-bit-MFMA time (mixed pair: the residual term runs on the fp8 MFMA at twice the rate)
-      const double xa = a_split == 2 ? 1.5 : (a_split ? 2.0 : 1.0);
-      E->prof.push_back(ProfRec{PC_GEMM, ea, eb, 2.0 * M * N * K,
-                                2.0 * ((double)M * K * xa + (double)N * K * (a_split == 2 ? 1.5 : 1.0)) + ob * M * N + (out2 ? 2.0 * M * N : 0),
-                                2.0 * M * N * K * xa, M, N, K, epi, a_split, (f && f->fold_part) ? 1 : 0});
-    }
+  if (E && E->prof_on && take_events(E, &ea, &eb)) {
+    // flops = ALGORITHMIC (what the reference's fp32 GEMM does: 2MNK); the split-precision modes execute twice that
+    // (16-bit pair) or 1.5x in 16-bit-MFMA time (mixed pair: the residual term runs on the fp8 MFMA at twice the rate)
+    const double xa = a_split == 2 ? 1.5 : (a_split ? 2.0 : 1.0);
+    E->prof.push_back(ProfRec{PC_GEMM, ea, eb, 2.0 * M * N * K,
+                              2.0 * ((double)M * K * xa + (double)N * K * (a_split == 2 ? 1.5 : 1.0)) + ob * M * N + (out2 ? 2.0 * M * N : 0),
+                              2.0 * M * N * K * xa, M, N, K, epi, a_split, (f && f->fold_part) ? 1 : 0});
   }
   return launch_gemm(dt, epi, g, s, ea, eb);
 }
@@ -392,20 +392,46 @@ void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool s
 // MVLPT_PREC_SPLIT_ALL (PREC = "fp32": as exact as this engine gets) keeps 16-bit pairs everywhere
 int split_kind(const Engine* E) { return (E->prec_mode == MVLPT_PREC_SPLIT_ALL || !E->lo8) ? 1 : 2; }
 
-// attention core of the split-precision mode: qkv pair [T,6d] -> O as a hi|lo pair [T,2d]
-int attn32_fwd(Engine* E, TowerState& st, int l, int q_rows, hipStream_t s) {
-  Attn32Args a{st.qkv[l], st.attn[l], st.saved ? st.lse[l] : nullptr, st.N, st.L, st.H, st.causal ? 1 : 0, q_rows};
-  a.out_lo8 = st.xs == 2 ? 1 : 0;
-  const double rows = q_rows > 0 ? (double)q_rows : (double)st.L;
-  ProfScope ps(E, s, PC_ATTN_FWD, 4.0 * rows * st.L * 64.0 * st.N * st.H * (st.causal ? 0.5 : 1.0), (double)st.N * st.L * st.d * 16.0);
-  HIPCHK(E, launch_attn32_fwd(E->dt, a, s));
+// Attention core of layer l, all rows or (q_rows > 0) only queries 0..q_rows-1 of every sequence; lse is kept when the tower saves its
+// activations.  Split towers (st.xs): qkv pair [T,6d] -> O as a hi|lo pair [T,2d].  Single operands: `timed` (the full-width blocks)
+// adds the dispatch-timestamp record of attn_fwd_timed.
+int attn_fwd(Engine* E, TowerState& st, int l, int q_rows, bool timed, hipStream_t s) {
+  const double T = (double)st.N * st.L, rows = q_rows > 0 ? (double)q_rows : (double)st.L;
+  const double fl = 4.0 * rows * st.L * 64.0 * st.N * st.H * (st.causal ? 0.5 : 1.0);
+  float* lse = st.saved ? st.lse[l] : nullptr;
+  if (st.xs) {
+    Attn32Args a{st.qkv[l], st.attn[l], lse, st.N, st.L, st.H, st.causal ? 1 : 0, q_rows};
+    a.out_lo8 = st.xs == 2 ? 1 : 0;
+    ProfScope ps(E, s, PC_ATTN_FWD, fl, T * st.d * 16.0);
+    HIPCHK(E, launch_attn32_fwd(E->dt, a, s));
+    return 0;
+  }
+  AttnArgs a{st.qkv[l], st.attn[l], lse, st.N, st.L, st.H, st.causal ? 1 : 0, q_rows};
+  const double by = T * st.d * 2.0 * (q_rows > 0 ? 2.0 : 4.0);
+  ProfScope ps(E, s, PC_ATTN_FWD, fl, by);
+  HIPCHK(E, timed ? attn_fwd_timed(E, a, fl, by, s) : launch_attn_fwd(E->dt, a, s));
   return 0;
 }
-int attn32_bwd(Engine* E, TowerState& st, int l, hipStream_t s) {
-  Attn32BwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.L, st.H, st.causal ? 1 : 0};
-  a.lo8 = st.xs == 2 ? 1 : 0;
-  ProfScope ps(E, s, PC_ATTN_BWD, 14.0 * st.L * st.L * 64.0 * st.N * st.H * (st.causal ? 0.5 : 1.0), (double)st.N * st.L * st.d * 32.0);
-  HIPCHK(E, launch_attn32_bwd(E->dt, a, s));
+// Attention backward of layer l: dO16 -> dqkv16 at full width, or (cls, single operands only) the backward of query 0 of every
+// sequence on the compact rows of the last image block
+int attn_bwd(Engine* E, TowerState& st, int l, const Compact* cls, hipStream_t s) {
+  const double T = (double)st.N * st.L, cz = st.causal ? 0.5 : 1.0;
+  if (cls) {
+    ProfScope ps(E, s, PC_ATTN_BWD, 10.0 * st.L * 64.0 * st.N * st.H * cz, T * st.d * 2.0 * 5.0);
+    HIPCHK(E, launch_attn_bwd_cls(E->dt, st.qkv[l], cls->a16, cls->dO16, st.lse[l], st.dqkv16, st.N, st.L, st.H, s));
+    return 0;
+  }
+  const double fl = 14.0 * st.L * st.L * 64.0 * st.N * st.H * cz;
+  if (st.xs) {
+    Attn32BwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.L, st.H, st.causal ? 1 : 0};
+    a.lo8 = st.xs == 2 ? 1 : 0;
+    ProfScope ps(E, s, PC_ATTN_BWD, fl, T * st.d * 32.0);
+    HIPCHK(E, launch_attn32_bwd(E->dt, a, s));
+    return 0;
+  }
+  AttnBwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.L, st.H, st.causal ? 1 : 0};
+  ProfScope ps(E, s, PC_ATTN_BWD, fl, T * st.d * 2.0 * 8.0);
+  HIPCHK(E, launch_attn_bwd(E->dt, a, s));
   return 0;
 }
 
@@ -431,77 +457,37 @@ Fold fold_consumer(const TowerState& st, int which, const Linear& L) {
   return f;
 }
 
-// Split-precision variant of block_fwd / block_bwd below: every GEMM A operand is a 16-bit hi|lo pair (~22 bits), the
-// attention core runs in fp32.  Used for towers that carry a gradient (and for every tower under MVLPT_PREC_SPLIT_ALL).
+// ResidualAttentionBlock.forward (clip/model.py:185-188) on token buffers.  Split towers (st.xs; towers that carry a gradient, and every
+// tower under MVLPT_PREC_SPLIT_ALL): every GEMM A operand is a 16-bit hi|lo pair (~22 bits), the attention core runs in fp32, and the
+// pair rows between the two MLP GEMMs have the pitch st.wide_pitch.
 // ln1_folded: h16 / part[0] already hold this block's ln_1 input in folded form (written by the previous block's FC2);
 // next_ln1: the LayerNorm the block's output goes into next, when that one may be folded; *produced: it was.
-int block_fwd_x(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s, bool ln1_folded, const LNp* next_ln1, bool* produced) {
-  const Block& B = W.blocks[l];
-  const int T = st.N * st.L, d = st.d;
-  float* xin = st.x[2 * l]; float* xmid = st.x[2 * l + 1]; float* xout = st.x[2 * l + 2];
-  Fold fq, fo, ff, fp;
-  if (ln1_folded) fq = fold_consumer(st, 0, B.qkv);
-  else HIPCHK(E, ln_fwd(E, E->dt, xin, nullptr, 1, B.ln1, st.h16, T, d, s, st.xs));
-  HIPCHK(E, gemm(E, EPI_STORE_SPLIT, st.h16, B.qkv.fw(), T, 3 * d, d, ln1_folded ? B.qkv.fold_b : B.qkv.b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, st.xs,
-                 ln1_folded ? &fq : nullptr));
-  if (int rc = attn32_fwd(E, st, l, 0, s)) return rc;
-  const bool p2 = fold_producer(E, st, 1, T, d, d, B.ln2, s, &fo);
-  HIPCHK(E, gemm(E, p2 ? EPI_RESID32_LN : EPI_RESID32, st.attn[l], B.o.fw(), T, d, d, B.o.b, nullptr, xin, xmid, nullptr, s, -1, st.xs, p2 ? &fo : nullptr));
-  if (p2) ff = fold_consumer(st, 1, B.fc);
-  else HIPCHK(E, ln_fwd(E, E->dt, xmid, nullptr, 1, B.ln2, st.h16, T, d, s, st.xs));
-  HIPCHK(E, gemm(E, EPI_GELU_SPLIT, st.h16, B.fc.fw(), T, 4 * d, d, p2 ? B.fc.fold_b : B.fc.b, nullptr, nullptr, st.a16, st.saved ? st.u[l] : nullptr, s, -1, st.xs,
-                 p2 ? &ff : nullptr, 0, st.wide_pitch));
-  const bool p1 = next_ln1 && fold_producer(E, st, 0, T, d, 4 * d, *next_ln1, s, &fp);
-  HIPCHK(E, gemm(E, p1 ? EPI_RESID32_LN : EPI_RESID32, st.a16, B.pr.fw(), T, d, 4 * d, B.pr.b, nullptr, xmid, xout, nullptr, s, -1, st.xs, p1 ? &fp : nullptr,
-                 st.wide_pitch, 0));
-  if (produced) *produced = p1;
-  return 0;
-}
-int block_bwd_x(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s) {
-  const Block& B = W.blocks[l];
-  const int T = st.N * st.L, d = st.d;
-  HIPCHK(E, gemm(E, EPI_GELUBWD_SPLIT, st.dx16, B.pr.bw(), T, 4 * d, d, nullptr, st.u[l], nullptr, st.du16, nullptr, s, -1, st.xs, nullptr, 0, st.wide_pitch));
-  HIPCHK(E, gemm(E, EPI_STORE32, st.du16, B.fc.bw(), T, d, 4 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, st.xs, nullptr, st.wide_pitch, 0));
-  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l + 1], nullptr, 1, B.ln2, st.dx32, st.dx32, st.dx16, T, d, s, -1, st.xs));
-  HIPCHK(E, gemm(E, EPI_STORE_SPLIT, st.dx16, B.o.bw(), T, d, d, nullptr, nullptr, nullptr, st.dO16, nullptr, s, -1, st.xs));
-  if (int rc = attn32_bwd(E, st, l, s)) return rc;
-  HIPCHK(E, gemm(E, EPI_STORE32, st.dqkv16, B.qkv.bw(), T, d, 3 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, st.xs));
-  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, B.ln1, st.dx32, st.dx32, st.dx16, T, d, s, -1, st.xs));
-  return 0;
-}
-
-// ResidualAttentionBlock.forward (clip/model.py:185-188) on token buffers (LayerNorm folding: see block_fwd_x)
 int block_fwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s, bool ln1_folded = false, const LNp* next_ln1 = nullptr,
               bool* produced = nullptr) {
   if (produced) *produced = false;
-  if (st.exact) return block_fwd_x(E, W, st, l, s, ln1_folded, next_ln1, produced);
   const Block& B = W.blocks[l];
-  const int T = st.N * st.L, d = st.d;
+  const int T = st.N * st.L, d = st.d, xs = st.xs, wp = st.wide_pitch;
   float* xin = st.x[2 * l]; float* xmid = st.x[2 * l + 1]; float* xout = st.x[2 * l + 2];
   Fold fq, fo, ff, fp;
   if (ln1_folded) fq = fold_consumer(st, 0, B.qkv);
-  else HIPCHK(E, ln_fwd(E, E->dt, xin, nullptr, 1, B.ln1, st.h16, T, d, s));
-  HIPCHK(E, gemm(E, EPI_STORE16, st.h16, B.qkv.fw(), T, 3 * d, d, ln1_folded ? B.qkv.fold_b : B.qkv.b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, 0,
+  else HIPCHK(E, ln_fwd(E, E->dt, xin, nullptr, 1, B.ln1, st.h16, T, d, s, xs));
+  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, st.h16, B.qkv.fw(), T, 3 * d, d, ln1_folded ? B.qkv.fold_b : B.qkv.b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, xs,
                  ln1_folded ? &fq : nullptr));
-  {
-    AttnArgs a{st.qkv[l], st.attn[l], st.saved ? st.lse[l] : nullptr, st.N, st.L, st.H, st.causal ? 1 : 0};
-    const double fl = 4.0 * st.L * st.L * 64.0 * st.N * st.H * (st.causal ? 0.5 : 1.0);
-    ProfScope ps(E, s, PC_ATTN_FWD, fl, (double)T * d * 2.0 * 4.0);
-    HIPCHK(E, attn_fwd_timed(E, a, fl, (double)T * d * 2.0 * 4.0, s));
-  }
+  if (int rc = attn_fwd(E, st, l, 0, true, s)) return rc;
   const bool p2 = fold_producer(E, st, 1, T, d, d, B.ln2, s, &fo);
-  HIPCHK(E, gemm(E, p2 ? EPI_RESID32_LN : EPI_RESID32, st.attn[l], B.o.fw(), T, d, d, B.o.b, nullptr, xin, xmid, nullptr, s, -1, 0, p2 ? &fo : nullptr));
+  HIPCHK(E, gemm(E, p2 ? EPI_RESID32_LN : EPI_RESID32, st.attn[l], B.o.fw(), T, d, d, B.o.b, nullptr, xin, xmid, nullptr, s, -1, xs, p2 ? &fo : nullptr));
   if (p2) ff = fold_consumer(st, 1, B.fc);
-  else HIPCHK(E, ln_fwd(E, E->dt, xmid, nullptr, 1, B.ln2, st.h16, T, d, s));
-  HIPCHK(E, gemm(E, EPI_GELU, st.h16, B.fc.fw(), T, 4 * d, d, p2 ? B.fc.fold_b : B.fc.b, nullptr, nullptr, st.a16, st.saved ? st.u[l] : nullptr, s, -1, 0,
-                 p2 ? &ff : nullptr));
+  else HIPCHK(E, ln_fwd(E, E->dt, xmid, nullptr, 1, B.ln2, st.h16, T, d, s, xs));
+  HIPCHK(E, gemm(E, xs ? EPI_GELU_SPLIT : EPI_GELU, st.h16, B.fc.fw(), T, 4 * d, d, p2 ? B.fc.fold_b : B.fc.b, nullptr, nullptr, st.a16, st.saved ? st.u[l] : nullptr, s, -1, xs,
+                 p2 ? &ff : nullptr, 0, wp));
   const bool p1 = next_ln1 && fold_producer(E, st, 0, T, d, 4 * d, *next_ln1, s, &fp);
-  HIPCHK(E, gemm(E, p1 ? EPI_RESID32_LN : EPI_RESID32, st.a16, B.pr.fw(), T, d, 4 * d, B.pr.b, nullptr, xmid, xout, nullptr, s, -1, 0, p1 ? &fp : nullptr));
+  HIPCHK(E, gemm(E, p1 ? EPI_RESID32_LN : EPI_RESID32, st.a16, B.pr.fw(), T, d, 4 * d, B.pr.b, nullptr, xmid, xout, nullptr, s, -1, xs, p1 ? &fp : nullptr,
+                 wp, 0));
   if (produced) *produced = p1;
   return 0;
 }
 
-// block_fwd on the PACKED residual stream (common.h respk_*, kernels.h EPI_RESIDP_LN): fp16 tower, single operands, nothing saved,
+// block_fwd on the PACKED residual stream (common.h respk_*, kernels.h EPI_RESIDP_LN): fp16 tower, single operands (st.xs == 0), nothing saved,
 // both LayerNorms folded.  The stream lives in st.x[0] as hi [T,d] fp16 | lo [T,d] bytes and is updated in place; the hi plane is
 // the A operand of the QKV / MLP-up GEMMs, whose weights carry the LayerNorm's gamma (Linear::wg).  part[0] holds the row
 // statistics of the stream on entry (the previous block's FC2, or the pack kernel in front of block 0).
@@ -514,12 +500,7 @@ int block_fwd_packed(Engine* E, const TowerW& W, TowerState& st, int l, hipStrea
   fq.fold_colsum = B.qkv.fold_sg;
   HIPCHK(E, gemm(E, EPI_STORE16, hi, B.qkv.fwg(), T, 3 * d, d, B.qkv.fold_b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, 0, &fq));
   dbg_ck(E, st.qkv[l], (size_t)T * 3 * d * 2, s);
-  {
-    AttnArgs a{st.qkv[l], st.attn[l], nullptr, st.N, st.L, st.H, st.causal ? 1 : 0};
-    const double fl = 4.0 * st.L * st.L * 64.0 * st.N * st.H * (st.causal ? 0.5 : 1.0);
-    ProfScope ps(E, s, PC_ATTN_FWD, fl, (double)T * d * 2.0 * 4.0);
-    HIPCHK(E, attn_fwd_timed(E, a, fl, (double)T * d * 2.0 * 4.0, s));
-  }
+  if (int rc = attn_fwd(E, st, l, 0, true, s)) return rc;
   dbg_ck(E, st.attn[l], (size_t)T * d * 2, s);
   if (!fold_producer(E, st, 1, T, d, d, B.ln2, s, &fo)) return fail(E, MVLPT_ERR_STATE, "packed residual stream: out-projection cannot produce the ln_2 statistics");
   fo.rp_hi_in = hi; fo.rp_lo_in = lo; fo.rp_lo_out = lo;
@@ -538,22 +519,94 @@ int block_fwd_packed(Engine* E, const TowerW& W, TowerState& st, int l, hipStrea
 
 // dX-only backward of one block: dx32/dx16 hold d(block output) on entry and d(block input) on exit
 int block_bwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s) {
-  if (st.exact) return block_bwd_x(E, W, st, l, s);
   const Block& B = W.blocks[l];
-  const int T = st.N * st.L, d = st.d;
-  HIPCHK(E, gemm(E, EPI_GELUBWD, st.dx16, B.pr.bw(), T, 4 * d, d, nullptr, st.u[l], nullptr, st.du16, nullptr, s));
+  const int T = st.N * st.L, d = st.d, xs = st.xs, wp = st.wide_pitch;
+  HIPCHK(E, gemm(E, xs ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, st.dx16, B.pr.bw(), T, 4 * d, d, nullptr, st.u[l], nullptr, st.du16, nullptr, s, -1, xs, nullptr, 0, wp));
   // the dX GEMMs that feed a LayerNorm backward store fp32 (one 16-bit rounding less per half layer)
-  HIPCHK(E, gemm(E, EPI_STORE32, st.du16, B.fc.bw(), T, d, 4 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s));
-  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l + 1], nullptr, 1, B.ln2, st.dx32, st.dx32, st.dx16, T, d, s));
-  HIPCHK(E, gemm(E, EPI_STORE16, st.dx16, B.o.bw(), T, d, d, nullptr, nullptr, nullptr, st.dO16, nullptr, s));
-  {
-    AttnBwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.L, st.H, st.causal ? 1 : 0};
-    const double fl = 14.0 * st.L * st.L * 64.0 * st.N * st.H * (st.causal ? 0.5 : 1.0);
-    ProfScope ps(E, s, PC_ATTN_BWD, fl, (double)T * d * 2.0 * 8.0);
-    HIPCHK(E, launch_attn_bwd(E->dt, a, s));
-  }
-  HIPCHK(E, gemm(E, EPI_STORE32, st.dqkv16, B.qkv.bw(), T, d, 3 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s));
-  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, B.ln1, st.dx32, st.dx32, st.dx16, T, d, s));
+  HIPCHK(E, gemm(E, EPI_STORE32, st.du16, B.fc.bw(), T, d, 4 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs, nullptr, wp, 0));
+  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l + 1], nullptr, 1, B.ln2, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs));
+  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, st.dx16, B.o.bw(), T, d, d, nullptr, nullptr, nullptr, st.dO16, nullptr, s, -1, xs));
+  if (int rc = attn_bwd(E, st, l, nullptr, s)) return rc;
+  HIPCHK(E, gemm(E, EPI_STORE32, st.dqkv16, B.qkv.bw(), T, d, 3 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs));
+  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, B.ln1, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs));
+  return 0;
+}
+
+// ---- The last block of a tower, evaluated on the rows that are read (Compact): ln_1, QKV and the attention still see every token
+// (keys / values), then out-proj, ln_2, the MLP and the closing LayerNorm run on the R = st.N compact rows instead of R * L: ~20/24
+// of the layer's GEMM FLOPs vanish, in the forward and, when the tower has a backward, in the backward as well.
+// Bytes of the compact buffers as the workspace formulas publish them (u16, never a pair, is counted at pair width)
+size_t compact_bytes(size_t R, size_t d, size_t X) {
+  return 7 * align256(R * d * 4) + 4 * align256(R * d * 2 * X) + 3 * align256(R * d * 8 * X);
+}
+void carve_compact(Bump& bp, Compact& c, size_t R, size_t d, size_t X) {
+  c = Compact();
+  for (float** p : {&c.out32, &c.dout32, &c.x32, &c.xm32, &c.xo32, &c.dx32, &c.dh32}) *p = bp.take<float>(R * d);
+  for (void** p : {&c.a16, &c.h16, &c.dx16, &c.dO16}) *p = bp.take_bytes(R * d * 2 * X);
+  c.g16 = bp.take_bytes(R * d * 8 * X); c.u16 = bp.take_bytes(R * d * 8); c.du16 = bp.take_bytes(R * d * 8 * X);
+}
+// compact row r <-> token row rows[r] or (rows == null) row 0 of sequence r; scatter: compact -> full width
+hipError_t move_rows(const void* src, void* dst, const int32_t* rows, int R, int L, size_t row_bytes, int scatter, hipStream_t s) {
+  if (rows) return launch_copy_rows(src, dst, rows, R, (int)row_bytes, scatter, s);
+  return launch_copy_rows_strided(src, dst, R, scatter ? row_bytes : L * row_bytes, scatter ? L * row_bytes : row_bytes, (int)row_bytes, s);
+}
+// Image: only x[:, 0, :] of the last block is consumed (trainers/mvlpt.py:88), rows == null, and only the CLS query runs (q_rows = 1).
+// Text: only x[c, eot_c] (trainers/mvlpt.py:126-128), rows = eot_rows, every query runs.  packed: the image tower's packed stream.
+// ln_close: ln_post / ln_final, into c.out32.  ck: mvlpt_debug_checksums fingerprints (image tower only).
+int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const int32_t* rows, int q_rows, bool packed, bool ln1_ready,
+                   const LNp& ln_close, bool ck, hipStream_t s) {
+  const int l = st.layers - 1, T = st.N * st.L, R = st.N, d = st.d;
+  const int xs = st.xs;                 // split-precision operands (hi|lo pairs, twice the columns) + pair-product attention
+  const size_t X = xs ? 2 : 1;
+  const Block& Bk = W.blocks[l];
+  float* xin = st.x[2 * l];
+  c.kept = st.saved;
+  Fold fq;
+  if (ln1_ready) fq = fold_consumer(st, 0, Bk.qkv);
+  else HIPCHK(E, ln_fwd(E, E->dt, xin, nullptr, 1, Bk.ln1, st.h16, T, d, s, xs));
+  if (packed) fq.fold_colsum = Bk.qkv.fold_sg;       // A = the stream's hi plane, gamma inside the weight
+  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, packed ? (void*)st.x[0] : st.h16, packed ? Bk.qkv.fwg() : Bk.qkv.fw(), T, 3 * d, d,
+                 ln1_ready ? Bk.qkv.fold_b : Bk.qkv.b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, xs, ln1_ready ? &fq : nullptr));
+  if (ck) dbg_ck(E, st.qkv[l], (size_t)T * 3 * d * 2 * X, s);
+  // split operands, some queries only: the other rows of the attention output are not produced, and the backward
+  // (delta = rowsum(dO * O) over EVERY row, with dO = 0 off the compact rows) must not meet uninitialised memory there
+  if (xs && q_rows > 0 && st.saved) HIPCHK(E, launch_zero(st.attn[l], (size_t)T * d * 2 * X, s));
+  if (int rc = attn_fwd(E, st, l, q_rows, false, s)) return rc;
+  { ProfScope ps(E, s, PC_GLUE, 0, (double)R * d * 12.0);
+    HIPCHK(E, move_rows(st.attn[l], c.a16, rows, R, st.L, (size_t)d * 2 * X, 0, s));
+    if (packed) HIPCHK(E, launch_respk_unpack_rows(st.x[0], (uint8_t*)st.x[0] + (size_t)T * d * 2, st.L, c.x32, R, d, s));
+    else HIPCHK(E, move_rows(xin, c.x32, rows, R, st.L, (size_t)d * 4, 0, s)); }
+  if (ck) { dbg_ck(E, c.a16, (size_t)R * d * 2 * X, s); dbg_ck(E, c.x32, (size_t)R * d * 4, s); }
+  HIPCHK(E, gemm(E, EPI_RESID32, c.a16, Bk.o.fw(), R, d, d, Bk.o.b, nullptr, c.x32, c.xm32, nullptr, s, -1, xs));
+  HIPCHK(E, ln_fwd(E, E->dt, c.xm32, nullptr, 1, Bk.ln2, c.h16, R, d, s, xs));
+  HIPCHK(E, gemm(E, xs ? EPI_GELU_SPLIT : EPI_GELU, c.h16, Bk.fc.fw(), R, 4 * d, d, Bk.fc.b, nullptr, nullptr, c.g16, st.saved ? c.u16 : nullptr, s, -1, xs));
+  HIPCHK(E, gemm(E, EPI_RESID32, c.g16, Bk.pr.fw(), R, d, 4 * d, Bk.pr.b, nullptr, c.xm32, c.xo32, nullptr, s, -1, xs));
+  HIPCHK(E, ln_fwd(E, DT_F32, c.xo32, nullptr, 1, ln_close, c.out32, R, d, s));
+  return 0;
+}
+// Backward of last_block_fwd from c.dout32: the closing LayerNorm, MLP, ln_2 and out-proj on the compact rows, the attention backward,
+// then the full-width QKV^T GEMM and ln_1 (keys / values of every token).  st.dx32 is zero on entry.  A single-operand tower whose
+// forward ran q_rows queries takes the single-query attention backward on the compact rows; every other one scatters the compact dO
+// into a zeroed dO16 and runs the attention backward at full width.
+int last_block_bwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const int32_t* rows, int q_rows, const LNp& ln_close, hipStream_t s) {
+  const int l = st.layers - 1, T = st.N * st.L, R = st.N, d = st.d, xs = st.xs;
+  const size_t X = xs ? 2 : 1;
+  const Block& Bk = W.blocks[l];
+  const bool cls = q_rows > 0 && !xs;
+  HIPCHK(E, ln_bwd(E, c.dout32, DT_F32, c.xo32, nullptr, 1, ln_close, nullptr, c.dx32, c.dx16, R, d, s, -1, xs));
+  HIPCHK(E, gemm(E, xs ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, c.dx16, Bk.pr.bw(), R, 4 * d, d, nullptr, c.u16, nullptr, c.du16, nullptr, s, -1, xs));
+  HIPCHK(E, gemm(E, EPI_STORE32, c.du16, Bk.fc.bw(), R, d, 4 * d, nullptr, nullptr, nullptr, c.dh32, nullptr, s, -1, xs));
+  HIPCHK(E, ln_bwd(E, c.dh32, DT_F32, c.xm32, nullptr, 1, Bk.ln2, c.dx32, c.dx32, c.dx16, R, d, s, -1, xs));
+  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, c.dx16, Bk.o.bw(), R, d, d, nullptr, nullptr, nullptr, c.dO16, nullptr, s, -1, xs));
+  { ProfScope ps(E, s, PC_GLUE, 0, (cls ? 0.0 : (double)T * d * 2.0 * X) + (double)R * d * 8.0);
+    if (!cls) {
+      HIPCHK(E, launch_zero(st.dO16, (size_t)T * d * 2 * X, s));      // (split: dO is a hi|lo pair)
+      HIPCHK(E, move_rows(c.dO16, st.dO16, rows, R, st.L, (size_t)d * 2 * X, 1, s));
+    }
+    HIPCHK(E, move_rows(c.dx32, st.dx32, rows, R, st.L, (size_t)d * 4, 1, s)); }     // residual path: d(block input) of the compact rows
+  if (int rc = attn_bwd(E, st, l, cls ? &c : nullptr, s)) return rc;
+  HIPCHK(E, gemm(E, EPI_STORE32, st.dqkv16, Bk.qkv.bw(), T, d, 3 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs));
+  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, Bk.ln1, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs));
   return 0;
 }
 
@@ -845,6 +898,7 @@ int resnet_fwd(Engine* E, const void* image, int image_dtype, int B, float* feat
   void* q16 = bp.take_bytes((size_t)B * Ech * 2);
   void* o16 = bp.take_bytes((size_t)B * Ech * 2);
   void *x = buf[0], *a = buf[1], *b = buf[2], *c = buf[3], *d = buf[4];
+  if (bp.off > bp.cap) return fail(E, MVLPT_ERR_STATE, "image_fwd (ResNet): the workspace carve exceeds its reservation");
 
   { ProfScope ps(E, s, PC_GLUE, 0, (double)B * res * res * (3.0 * 4.0 + 16.0));
     HIPCHK(E, launch_nchw_to_nhwc8(image, image_dtype, img8, B, res, s)); }
@@ -1248,24 +1302,16 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
   const size_t X = exact ? 2 : 1;
   const size_t npatch = (size_t)B * G2;
   size_t need = tower_bytes(E->vis, B, Lv, save, exact) + align256(npatch * E->Kp * 2) + align256(npatch * dv * 4) +
-                7 * align256((size_t)B * dv * 4) + 4 * align256((size_t)B * dv * 2 * X) + 3 * align256((size_t)B * dv * 8 * X) + 4096;
+                compact_bytes(B, dv, X) + 4096;
   E->vs.valid = false;
   HIPCHK(E, E->vis_ws.reserve(need));
   Bump bp; bp.base = (char*)E->vis_ws.p; bp.cap = E->vis_ws.cap;
   void* patches = bp.take_bytes(npatch * E->Kp * 2);
   float* pe = bp.take<float>(npatch * dv);
-  E->cls32 = bp.take<float>((size_t)B * dv);
-  E->dcls32 = bp.take<float>((size_t)B * dv);
-  E->xc32 = bp.take<float>((size_t)B * dv);
-  E->ac16 = bp.take_bytes((size_t)B * dv * 2 * X); E->hc16 = bp.take_bytes((size_t)B * dv * 2 * X);
-  E->gc16 = bp.take_bytes((size_t)B * dv * 4 * 2 * X);
-  E->xcm32 = bp.take<float>((size_t)B * dv); E->xco32 = bp.take<float>((size_t)B * dv);
-  E->dxc32 = bp.take<float>((size_t)B * dv); E->dhc32 = bp.take<float>((size_t)B * dv);
-  E->dxc16 = bp.take_bytes((size_t)B * dv * 2 * X); E->dOc16 = bp.take_bytes((size_t)B * dv * 2 * X);
-  E->uc16 = bp.take_bytes((size_t)B * dv * 4 * 2); E->duc16 = bp.take_bytes((size_t)B * dv * 4 * 2 * X);
-  E->v_cls_last = false;
+  carve_compact(bp, E->vc, B, dv, X);
   carve_tower(bp, E->vis, E->vs, B, Lv, save, false, exact, split_kind(E));
   TowerState& st = E->vs;
+  if (bp.off > bp.cap) { st.valid = false; return fail(E, MVLPT_ERR_STATE, "image_fwd_begin: the workspace carve exceeds its reservation"); }
   E->vB = B; E->v_nvpt = n_vpt; E->v_ndeep = n_deep;
   st.fold = E->fold_mode >= 1 && (size_t)B * Lv >= (size_t)E->fold_min_rows && dv >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
@@ -1326,59 +1372,17 @@ int mvlpt_image_fwd_resume(void* h, float* feat_out, mvlpt_stream_t stream) {
   TowerState& st = E->vs;
   const MvlptArch& A = E->arch;
   const int B = E->vB, dv = A.vision_width, e = A.embed_dim, Lv = st.L;
-  const bool save = E->ip.save, packed = E->ip.packed;
-  const size_t X = st.exact ? 2 : 1;
-  void* const xhi = st.x[0];
-  uint8_t* const xlo = (uint8_t*)st.x[0] + (size_t)B * Lv * dv * 2;
+  const bool packed = E->ip.packed;
   bool ln1_ready = E->ip.ln1_ready;
   const int rest = image_blocks(E, E->ip.next, E->vis.layers, packed, &ln1_ready, E->ip.vpt_deep, s);
   if (rest < 0) { st.valid = false; return rest; }
-  const bool cls_only_last = rest == 1;
-  if (cls_only_last) {
-    // Only x[:, 0, :] of the last block is consumed (trainers/mvlpt.py:88): keys/values are still needed for every
-    // token, but queries, out-proj, ln_2 and the MLP are evaluated for the CLS row only (B rows instead of B*Lv: ~20/24
-    // of the layer's GEMM FLOPs vanish) — in the forward and, when the tower has a backward, in the backward as well
-    // (mvlpt_image_bwd: only the CLS query carries a gradient into this block's attention).
-    const int l = E->vis.layers - 1;
-    const Block& Bk = E->vis.blocks[l];
-    const int T = B * Lv;
-    float* xin = st.x[2 * l];
-    float* xmid = save ? E->xcm32 : E->xc32;     // kept for the backward: LN2 input ...
-    float* xout = save ? E->xco32 : E->xc32;     // ... and ln_post input
-    E->v_cls_last = save;
-    const int xs = st.xs;                 // split-precision operands (hi|lo pairs, twice the columns) + pair-product attention
-    Fold fq;
-    if (ln1_ready) fq = fold_consumer(st, 0, Bk.qkv);
-    else HIPCHK(E, ln_fwd(E, E->dt, xin, nullptr, 1, Bk.ln1, st.h16, T, dv, s, xs));
-    if (packed) fq.fold_colsum = Bk.qkv.fold_sg;       // A = the stream's hi plane, gamma inside the weight
-    HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, packed ? xhi : st.h16, packed ? Bk.qkv.fwg() : Bk.qkv.fw(), T, 3 * dv, dv,
-                   ln1_ready ? Bk.qkv.fold_b : Bk.qkv.b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, xs, ln1_ready ? &fq : nullptr));
-    dbg_ck(E, st.qkv[l], (size_t)T * 3 * dv * 2 * X, s);
-    if (xs) {
-      // only the CLS rows of the attention output are produced: the backward (delta = rowsum(dO * O) over EVERY row, with
-      // dO = 0 off the CLS rows) must not meet uninitialised memory there
-      if (save) HIPCHK(E, launch_zero(st.attn[l], (size_t)T * dv * 4, s));
-      if (int rc = attn32_fwd(E, st, l, 1, s)) return rc;
-    } else {
-      AttnArgs a{st.qkv[l], st.attn[l], save ? st.lse[l] : nullptr, st.N, st.L, st.H, 0, 1};
-      ProfScope ps(E, s, PC_ATTN_FWD, 4.0 * st.L * 64.0 * st.N * st.H, (double)T * dv * 2.0 * 2.0);
-      HIPCHK(E, launch_attn_fwd(E->dt, a, s));
-    }
-    { ProfScope ps(E, s, PC_GLUE, 0, (double)B * dv * 12.0);
-      HIPCHK(E, launch_copy_rows_strided(st.attn[l], E->ac16, B, (size_t)Lv * dv * 2 * X, (size_t)dv * 2 * X, (int)(dv * 2 * X), s));
-      if (packed) HIPCHK(E, launch_respk_unpack_rows(xhi, xlo, Lv, E->xc32, B, dv, s));
-      else HIPCHK(E, launch_copy_rows_strided(xin, E->xc32, B, (size_t)Lv * dv * 4, (size_t)dv * 4, dv * 4, s)); }
-    dbg_ck(E, E->ac16, (size_t)B * dv * 2 * X, s); dbg_ck(E, E->xc32, (size_t)B * dv * 4, s);
-    HIPCHK(E, gemm(E, EPI_RESID32, E->ac16, Bk.o.fw(), B, dv, dv, Bk.o.b, nullptr, E->xc32, xmid, nullptr, s, -1, xs));
-    HIPCHK(E, ln_fwd(E, E->dt, xmid, nullptr, 1, Bk.ln2, E->hc16, B, dv, s, xs));
-    HIPCHK(E, gemm(E, xs ? EPI_GELU_SPLIT : EPI_GELU, E->hc16, Bk.fc.fw(), B, 4 * dv, dv, Bk.fc.b, nullptr, nullptr, E->gc16, save ? E->uc16 : nullptr, s, -1, xs));
-    HIPCHK(E, gemm(E, EPI_RESID32, E->gc16, Bk.pr.fw(), B, dv, 4 * dv, Bk.pr.b, nullptr, xmid, xout, nullptr, s, -1, xs));
-    HIPCHK(E, ln_fwd(E, DT_F32, xout, nullptr, 1, E->ln_post, E->cls32, B, dv, s));
+  if (rest == 1) {      // the last block, CLS rows only (mvlpt_image_bwd: only the CLS query carries a gradient into its attention)
+    if (int rc = last_block_fwd(E, E->vis, st, E->vc, nullptr, 1, packed, ln1_ready, E->ln_post, true, s)) return rc;
   } else
   // ln_post on the CLS row, then @ proj   (trainers/mvlpt.py:88-91)
-  HIPCHK(E, ln_fwd(E, DT_F32, st.x[2 * E->vis.layers], nullptr, Lv, E->ln_post, E->cls32, B, dv, s));
+  HIPCHK(E, ln_fwd(E, DT_F32, st.x[2 * E->vis.layers], nullptr, Lv, E->ln_post, E->vc.out32, B, dv, s));
   { ProfScope ps(E, s, PC_HEAD, 2.0 * B * e * dv, 4.0 * ((double)B * dv + (double)e * dv + (double)B * e));
-    HIPCHK(E, launch_sgemm_bt(E->cls32, E->vproj_t, feat_out, B, e, dv, nullptr, s)); }
+    HIPCHK(E, launch_sgemm_bt(E->vc.out32, E->vproj_t, feat_out, B, e, dv, nullptr, s)); }
   return 0;
 }
 
@@ -1410,43 +1414,25 @@ int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, 
   const size_t T = (size_t)B * Lv;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dv * 10.0);
     HIPCHK(E, launch_grad_scale(dfeat, (size_t)B * e, 64.0f, st.scale_dev, s));
-    HIPCHK(E, launch_sgemm_bt(dfeat, E->vproj, E->dcls32, B, dv, e, st.scale_dev, s)); }
+    HIPCHK(E, launch_sgemm_bt(dfeat, E->vproj, E->vc.dout32, B, dv, e, st.scale_dev, s)); }
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dv * 4.0);
     HIPCHK(E, launch_zero(st.dx32, T * dv * 4, s)); }
   int l_top = st.layers - 1;
   const int xs = st.xs;
-  if (E->v_cls_last) {
-    // last block, CLS rows only (see mvlpt_image_fwd): ln_post, MLP, ln_2, out-proj on B compact rows; the attention
-    // backward of a single query per head; then the full-width QKV^T GEMM and ln_1 (keys / values of every token)
-    const int l = st.layers - 1;
-    const Block& Bk = E->vis.blocks[l];
-    const int Ti = (int)T;
-    HIPCHK(E, ln_bwd(E, E->dcls32, DT_F32, E->xco32, nullptr, 1, E->ln_post, nullptr, E->dxc32, E->dxc16, B, dv, s, -1, xs));
-    HIPCHK(E, gemm(E, xs ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, E->dxc16, Bk.pr.bw(), B, 4 * dv, dv, nullptr, E->uc16, nullptr, E->duc16, nullptr, s, -1, xs));
-    HIPCHK(E, gemm(E, EPI_STORE32, E->duc16, Bk.fc.bw(), B, dv, 4 * dv, nullptr, nullptr, nullptr, E->dhc32, nullptr, s, -1, xs));
-    HIPCHK(E, ln_bwd(E, E->dhc32, DT_F32, E->xcm32, nullptr, 1, Bk.ln2, E->dxc32, E->dxc32, E->dxc16, B, dv, s, -1, xs));
-    HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, E->dxc16, Bk.o.bw(), B, dv, dv, nullptr, nullptr, nullptr, E->dOc16, nullptr, s, -1, xs));
-    if (xs) {
-      // split-precision attention backward at full width on a dO that is zero except for the CLS rows
-      { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dv * 4.0);
-        HIPCHK(E, launch_zero(st.dO16, T * dv * 4, s));
-        HIPCHK(E, launch_copy_rows_strided(E->dOc16, st.dO16, B, (size_t)dv * 4, (size_t)Lv * dv * 4, dv * 4, s)); }
-      if (int rc = attn32_bwd(E, st, l, s)) return rc;
-    } else {
-      ProfScope ps(E, s, PC_ATTN_BWD, 10.0 * st.L * 64.0 * st.N * st.H, (double)T * dv * 2.0 * 5.0);
-      HIPCHK(E, launch_attn_bwd_cls(E->dt, st.qkv[l], E->ac16, E->dOc16, st.lse[l], st.dqkv16, st.N, st.L, st.H, s)); }
-    { ProfScope ps(E, s, PC_GLUE, 0, (double)B * dv * 8.0);      // residual path: d(block input) of the CLS rows
-      HIPCHK(E, launch_copy_rows_strided(E->dxc32, st.dx32, B, (size_t)dv * 4, (size_t)Lv * dv * 4, dv * 4, s)); }
-    HIPCHK(E, gemm(E, EPI_STORE32, st.dqkv16, Bk.qkv.bw(), Ti, dv, 3 * dv, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs));
-    HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, Bk.ln1, st.dx32, st.dx32, st.dx16, Ti, dv, s, -1, xs));
-    if (l > 0 && E->v_ndeep > 0 && l <= E->v_ndeep) {
-      ProfScope ps(E, s, PC_GLUE, 0, (double)B * n * dv * 10.0);
-      HIPCHK(E, launch_reduce_prompt_rows(E->dt, st.dx32, st.dx16, B, Lv, dv, 1, n, dvpt_deep + (size_t)(l - 1) * n * dv,
-                                          st.scale_dev, 1, s, xs, E->v_mask ? E->v_mask + (size_t)l * B * n * dv : nullptr));
-    }
-    l_top = l - 1;
+  // gradient of the deep prompts of block l (its input rows 1..n), which then stop carrying one
+  auto reduce_deep = [&](int l) -> int {
+    if (!(l > 0 && E->v_ndeep > 0 && l <= E->v_ndeep)) return 0;
+    ProfScope ps(E, s, PC_GLUE, 0, (double)B * n * dv * 10.0);
+    HIPCHK(E, launch_reduce_prompt_rows(E->dt, st.dx32, st.dx16, B, Lv, dv, 1, n, dvpt_deep + (size_t)(l - 1) * n * dv,
+                                        st.scale_dev, 1, s, xs, E->v_mask ? E->v_mask + (size_t)l * B * n * dv : nullptr));
+    return 0;
+  };
+  if (E->vc.kept) {      // last block, CLS rows only (see mvlpt_image_fwd_resume)
+    if (int rc = last_block_bwd(E, E->vis, st, E->vc, nullptr, 1, E->ln_post, s)) return rc;
+    if (int rc = reduce_deep(l_top)) return rc;
+    --l_top;
   } else {
-    HIPCHK(E, ln_bwd(E, E->dcls32, DT_F32, st.x[2 * st.layers], nullptr, Lv, E->ln_post, nullptr, st.dx32, nullptr, B, dv, s));
+    HIPCHK(E, ln_bwd(E, E->vc.dout32, DT_F32, st.x[2 * st.layers], nullptr, Lv, E->ln_post, nullptr, st.dx32, nullptr, B, dv, s));
     { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dv * 6.0);
       if (xs) HIPCHK(E, launch_cast_f32_split(E->dt, st.dx32, st.dx16, T, dv, nullptr, s, xs == 2));
       else HIPCHK(E, launch_cast_f32_to16(E->dt, st.dx32, st.dx16, T * dv, nullptr, s)); }
@@ -1454,11 +1440,7 @@ int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, 
   for (int l = l_top; l >= 0; --l) {
     if (st.skip[l]) continue;
     if (int rc = block_bwd(E, E->vis, st, l, s)) return rc;
-    if (l > 0 && E->v_ndeep > 0 && l <= E->v_ndeep) {
-      ProfScope ps(E, s, PC_GLUE, 0, (double)B * n * dv * 10.0);
-      HIPCHK(E, launch_reduce_prompt_rows(E->dt, st.dx32, st.dx16, B, Lv, dv, 1, n, dvpt_deep + (size_t)(l - 1) * n * dv,
-                                          st.scale_dev, 1, s, xs, E->v_mask ? E->v_mask + (size_t)l * B * n * dv : nullptr));
-    }
+    if (int rc = reduce_deep(l)) return rc;
   }
   if (n > 0) {
     ProfScope ps(E, s, PC_GLUE, 0, (double)B * n * dv * 4.0);
@@ -1502,8 +1484,7 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 static size_t text_ws_bytes(Engine* E, int C, int L, bool save, bool exact, size_t ctx_rows) {
   const int dtw = E->arch.text_width;
   const size_t X = exact ? 2 : 1;
-  return tower_bytes(E->txt, C, L, save, exact) + 7 * align256((size_t)C * dtw * 4) + 4 * align256((size_t)C * dtw * 2 * X) +
-         3 * align256((size_t)C * dtw * 8 * X) + align256((size_t)C * 4) + align256(ctx_rows * 4) + 4096;
+  return tower_bytes(E->txt, C, L, save, exact) + compact_bytes(C, dtw, X) + align256((size_t)C * 4) + align256(ctx_rows * 4) + 4096;
 }
 static bool text_exact(const Engine* E) { return E->prec_mode == MVLPT_PREC_SPLIT_ALL || E->prec_mode == MVLPT_PREC_SPLIT_GRAD; }
 
@@ -1538,20 +1519,14 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
   E->ts.valid = false;
   HIPCHK(E, E->txt_ws.reserve(need));
   Bump bp; bp.base = (char*)E->txt_ws.p; bp.cap = E->txt_ws.cap;
-  E->eot32 = bp.take<float>((size_t)C * dtw);
-  E->deot32 = bp.take<float>((size_t)C * dtw);
+  carve_compact(bp, E->tc, C, dtw, X);
   E->eot_rows = bp.take<int32_t>(C);
   E->ctx_pos = bp.take<int32_t>(ctx_rows);
   int32_t* range_dev = ranged ? bp.take<int32_t>(range_ints) : nullptr;
   int32_t* ids_dev = ids ? bp.take<int32_t>(ids_ints) : nullptr;
-  E->txc32 = bp.take<float>((size_t)C * dtw); E->txm32 = bp.take<float>((size_t)C * dtw); E->txo32 = bp.take<float>((size_t)C * dtw);
-  E->tdxc32 = bp.take<float>((size_t)C * dtw); E->tdhc32 = bp.take<float>((size_t)C * dtw);
-  E->tac16 = bp.take_bytes((size_t)C * dtw * 2 * X); E->thc16 = bp.take_bytes((size_t)C * dtw * 2 * X);
-  E->tdxc16 = bp.take_bytes((size_t)C * dtw * 2 * X); E->tdOc16 = bp.take_bytes((size_t)C * dtw * 2 * X);
-  E->tgc16 = bp.take_bytes((size_t)C * dtw * 8 * X); E->tuc16 = bp.take_bytes((size_t)C * dtw * 8); E->tduc16 = bp.take_bytes((size_t)C * dtw * 8 * X);
-  E->t_eot_last = false;
   carve_tower(bp, E->txt, E->ts, C, L, save, true, exact, split_kind(E));
   TowerState& st = E->ts;
+  if (bp.off > bp.cap) { st.valid = false; return fail(E, MVLPT_ERR_STATE, "text_fwd: the workspace carve exceeds its reservation"); }
   E->tC = C; E->tL = L; E->t_nctx = n_ctx; E->t_per_class = ctx_per_class;
   E->t_kind = kind; E->t_groups = G; E->t_rlo = range_dev; E->t_rstart = ranged ? range_dev + G : nullptr;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
@@ -1580,39 +1555,10 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
     if (int rc = block_fwd(E, E->txt, st, l, s, ln1_ready, st.fold ? &E->txt.blocks[l + 1].ln1 : nullptr, &produced)) return rc;
     ln1_ready = produced;
   }
-  {
-    // Only x[c, eot_c] of the last block is consumed (trainers/mvlpt.py:126-128): LN1, QKV and the attention run for every
-    // position (keys / values), then out-proj, ln_2, the MLP and ln_final run on the C gathered EOT rows — forward and,
-    // in mvlpt_text_bwd, backward.
-    const int l = E->txt.layers - 1;
-    const Block& Bk = E->txt.blocks[l];
-    const int T = C * L;
-    float* xin = st.x[2 * l];
-    E->t_eot_last = save;
-    const int xs = st.xs;
-    Fold fq;
-    if (ln1_ready) fq = fold_consumer(st, 0, Bk.qkv);
-    else HIPCHK(E, ln_fwd(E, E->dt, xin, nullptr, 1, Bk.ln1, st.h16, T, dtw, s, xs));
-    HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, st.h16, Bk.qkv.fw(), T, 3 * dtw, dtw, ln1_ready ? Bk.qkv.fold_b : Bk.qkv.b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, xs,
-                   ln1_ready ? &fq : nullptr));
-    if (xs) {
-      if (int rc = attn32_fwd(E, st, l, 0, s)) return rc;
-    } else {
-      AttnArgs a{st.qkv[l], st.attn[l], save ? st.lse[l] : nullptr, st.N, st.L, st.H, 1};
-      ProfScope ps(E, s, PC_ATTN_FWD, 2.0 * st.L * st.L * 64.0 * st.N * st.H, (double)T * dtw * 2.0 * 4.0);
-      HIPCHK(E, launch_attn_fwd(E->dt, a, s));
-    }
-    { ProfScope ps(E, s, PC_GLUE, 0, (double)C * dtw * 12.0);
-      HIPCHK(E, launch_copy_rows(st.attn[l], E->tac16, E->eot_rows, C, (int)(dtw * 2 * X), 0, s));
-      HIPCHK(E, launch_copy_rows(xin, E->txc32, E->eot_rows, C, dtw * 4, 0, s)); }
-    HIPCHK(E, gemm(E, EPI_RESID32, E->tac16, Bk.o.fw(), C, dtw, dtw, Bk.o.b, nullptr, E->txc32, E->txm32, nullptr, s, -1, xs));
-    HIPCHK(E, ln_fwd(E, E->dt, E->txm32, nullptr, 1, Bk.ln2, E->thc16, C, dtw, s, xs));
-    HIPCHK(E, gemm(E, xs ? EPI_GELU_SPLIT : EPI_GELU, E->thc16, Bk.fc.fw(), C, 4 * dtw, dtw, Bk.fc.b, nullptr, nullptr, E->tgc16, save ? E->tuc16 : nullptr, s, -1, xs));
-    HIPCHK(E, gemm(E, EPI_RESID32, E->tgc16, Bk.pr.fw(), C, dtw, 4 * dtw, Bk.pr.b, nullptr, E->txm32, E->txo32, nullptr, s, -1, xs));
-    HIPCHK(E, ln_fwd(E, DT_F32, E->txo32, nullptr, 1, E->ln_final, E->eot32, C, dtw, s));
-  }
+  // the last block on the C gathered EOT rows
+  if (int rc = last_block_fwd(E, E->txt, st, E->tc, E->eot_rows, 0, false, ln1_ready, E->ln_final, false, s)) return rc;
   { ProfScope ps(E, s, PC_HEAD, 2.0 * C * e * dtw, 4.0 * ((double)C * dtw + (double)e * dtw + (double)C * e));
-    HIPCHK(E, launch_sgemm_bt(E->eot32, E->tproj_t, feat_out, C, e, dtw, nullptr, s)); }
+    HIPCHK(E, launch_sgemm_bt(E->tc.out32, E->tproj_t, feat_out, C, e, dtw, nullptr, s)); }
   return 0;
 }
 
@@ -1710,37 +1656,11 @@ int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stre
   const size_t T = (size_t)C * L;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dtw * 10.0);
     HIPCHK(E, launch_grad_scale(dfeat, (size_t)C * e, 64.0f, st.scale_dev, s));
-    HIPCHK(E, launch_sgemm_bt(dfeat, E->tproj, E->deot32, C, dtw, e, st.scale_dev, s)); }
+    HIPCHK(E, launch_sgemm_bt(dfeat, E->tproj, E->tc.dout32, C, dtw, e, st.scale_dev, s)); }
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dtw * 4.0);
     HIPCHK(E, launch_zero(st.dx32, T * dtw * 4, s)); }
-  if (!E->t_eot_last) return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward did not keep the last block's activations");
-  {
-    // last block on the C compact EOT rows (see mvlpt_text_fwd); the attention backward runs at full width on a dO that
-    // is zero except for the EOT rows, then the QKV^T GEMM and ln_1 as usual
-    const int l = st.layers - 1;
-    const Block& Bk = E->txt.blocks[l];
-    const int Ti = (int)T;
-    const int xs = st.xs;
-    const size_t X = xs ? 2 : 1;
-    HIPCHK(E, ln_bwd(E, E->deot32, DT_F32, E->txo32, nullptr, 1, E->ln_final, nullptr, E->tdxc32, E->tdxc16, C, dtw, s, -1, xs));
-    HIPCHK(E, gemm(E, xs ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, E->tdxc16, Bk.pr.bw(), C, 4 * dtw, dtw, nullptr, E->tuc16, nullptr, E->tduc16, nullptr, s, -1, xs));
-    HIPCHK(E, gemm(E, EPI_STORE32, E->tduc16, Bk.fc.bw(), C, dtw, 4 * dtw, nullptr, nullptr, nullptr, E->tdhc32, nullptr, s, -1, xs));
-    HIPCHK(E, ln_bwd(E, E->tdhc32, DT_F32, E->txm32, nullptr, 1, Bk.ln2, E->tdxc32, E->tdxc32, E->tdxc16, C, dtw, s, -1, xs));
-    HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, E->tdxc16, Bk.o.bw(), C, dtw, dtw, nullptr, nullptr, nullptr, E->tdOc16, nullptr, s, -1, xs));
-    { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dtw * 2.0);
-      HIPCHK(E, launch_zero(st.dO16, T * dtw * 2 * X, s));      // (exact: dO is a hi|lo pair)
-      HIPCHK(E, launch_copy_rows(E->tdOc16, st.dO16, E->eot_rows, C, (int)(dtw * 2 * X), 1, s));
-      HIPCHK(E, launch_copy_rows(E->tdxc32, st.dx32, E->eot_rows, C, dtw * 4, 1, s)); }     // residual path (dx32 was zeroed)
-    if (xs) {
-      if (int rc = attn32_bwd(E, st, l, s)) return rc;
-    } else {
-      AttnBwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.L, st.H, 1};
-      ProfScope ps(E, s, PC_ATTN_BWD, 7.0 * st.L * st.L * 64.0 * st.N * st.H, (double)T * dtw * 2.0 * 8.0);
-      HIPCHK(E, launch_attn_bwd(E->dt, a, s));
-    }
-    HIPCHK(E, gemm(E, EPI_STORE32, st.dqkv16, Bk.qkv.bw(), Ti, dtw, 3 * dtw, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs));
-    HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, Bk.ln1, st.dx32, st.dx32, st.dx16, Ti, dtw, s, -1, xs));
-  }
+  if (!E->tc.kept) return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward did not keep the last block's activations");
+  if (int rc = last_block_bwd(E, E->txt, st, E->tc, E->eot_rows, 0, E->ln_final, s)) return rc;      // the last block on the C compact EOT rows
   for (int l = st.layers - 2; l >= 0; --l)
     if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)C * E->t_nctx * dtw * 4.0);

@@ -221,13 +221,22 @@ def test_split_forward_equals_whole(vitb32, packed):
         eng.set_resid_packed(True)
 
 
-@pytest.mark.parametrize("n_deep", [11, 4])
-def test_split_forward_with_deep_prompts_and_backward(vitb32, n_deep):
+@pytest.mark.parametrize("n_deep,precision", [(11, "split_grad"), (4, "split_grad"), (11, "split_all")], ids=["11", "4", "11-split_all"])
+def test_split_forward_with_deep_prompts_and_backward(vitb32, n_deep, precision):
     """n_deep = 11: every later block has its prompt rows overwritten, the last one is CLS-only.  n_deep = 4: blocks 5 .. 11 are
     skipped (the reference's quirk), activations copied through for the backward; the cut falls in front of, at the edge of and
-    inside the skipped range."""
+    inside the skipped range.  split_all: 16-bit pair operands instead of the default's mixed pairs, through the full-width blocks
+    and the CLS-only last block, forward and backward."""
     eng, arch, image = vitb32
     assert arch.vision_layers == 12
+    eng.set_precision(precision)
+    try:
+        _split_deep_prompts_and_backward(eng, arch, image, n_deep)
+    finally:
+        eng.set_precision("split_grad")
+
+
+def _split_deep_prompts_and_backward(eng, arch, image, n_deep):
     g = torch.Generator().manual_seed(12)
     dv = arch.vision_width
     vpt = (torch.randn(3, dv, generator=g) * 0.1).to(DEV)

@@ -175,6 +175,23 @@ def test_tiny_case_fast_mode(name, tiny_clip_fast):
     run_case(case, model, t(case["image"]), TOL_FAST, GRAD_TOL_FAST)
 
 
+@pytest.fixture(scope="module")
+def tiny_clip_split_all():
+    from mvlpt_amd.model import FrozenCLIP
+    return FrozenCLIP(tiny_state_dict(), compute_dtype="fp16", precision="split_all")
+
+
+@pytest.mark.parametrize("name", ["tiny_upt"])
+def test_tiny_case_split_all_mode(name, tiny_clip_split_all):
+    """MVLPT_PREC_SPLIT_ALL: 16-bit hi|lo pairs in both towers (the default mode's towers carry mixed pairs), through the
+    full-width blocks and the compact last blocks, forward and backward.  No operand is narrower than in the default mode, so
+    the north_star bounds of the default mode hold."""
+    case = load_npz(name)
+    model = build_model(case, tiny_clip_split_all, 32, t(case["token_prefix"]), t(case["token_suffix"]))
+    err, worst = run_case(case, model, t(case["image"]), TOL_TINY_FP16, GRAD_TOL_FP16)
+    print(f"{name} split_all: logits {err:.2e} grads {max(worst.values()):.2e}")
+
+
 @pytest.mark.parametrize("name", ["tiny_coop_middle", "tiny_vpt_deep", "tiny_upt"])
 def test_tiny_case_bf16(name, tiny_clip_bf16):
     case = load_npz(name)

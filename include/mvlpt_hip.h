@@ -203,8 +203,27 @@ int mvlpt_text_bwd(void* handle, const float* dfeat, float* dctx, mvlpt_stream_t
 /* *out = bytes of text-tower workspace a text_fwd / text_fwd_grouped / text_fwd_ranged over C_total sequences of length L reserves (the
  * ctx-position table counted for the largest n_ctx, L - 2; a grouped or ranged tower adds its range tables, and a ranged one a per-class
  * position table, a few bytes per class and sequence, which the figure covers unless n_ctx is within a few tokens of L - 2); the
- * workspace only grows, so a caller that chunks G keeps its peak under a budget. */
+ * workspace only grows, so a caller that chunks G keeps its peak under a budget.  With save_for_bwd the figure is the one under the
+ * current mvlpt_set_text_act_ckpt setting (below): fewer saved layers, more sequences per chunk. */
 int mvlpt_text_workspace_bytes(void* handle, int C_total, int L, int save_for_bwd, int64_t* out);
+/* Activation checkpointing of the text tower, TRAINER.ACT_CKPT of the reference (trainers/mvlpt.py:119-121:
+ * checkpoint_sequential(resblocks, ACT_CKPT, x)).  An engine setting like mvlpt_set_precision; default 1 (everything saved).
+ * The plan is torch's: k = min(segments, text_layers) segments, the first k - 1 of text_layers / k blocks each, the last one takes
+ * the rest.  A saving forward (text_fwd / _grouped / _ranged with save_for_bwd = 1) keeps only the input of the first k - 1 segments
+ * and the activations of the last one; mvlpt_text_bwd runs every other segment again before that segment's backward, launch for launch
+ * as the forward did (no LayerNorm is folded across a segment boundary: k - 1 more LayerNorm launches), so features and dctx have
+ * the bits of an un-checkpointed tower whenever LayerNorm folding is off or the tower is below its row threshold, and stay within
+ * the tower's accuracy otherwise.  The largest segment is the last one, text_layers - (k - 1) * (text_layers / k) blocks, which is
+ * not monotonic in k (12 layers: k = 5 -> 4 blocks, k = 7 -> 6 blocks); k in {2, 3, 4, 6, 12} are the useful settings at 12 layers.
+ * segments < 1: MVLPT_ERR_ARG.  Takes effect at the next text forward and in mvlpt_text_workspace_bytes, which reports the reduced
+ * figure; a forward records its own plan, so a call between a forward and its backward does not change that backward.  With k > 1 a
+ * backward consumes the saved state: a second mvlpt_text_bwd on the same forward returns MVLPT_ERR_STATE without launching (with
+ * k = 1 it still repeats the backward).  mvlpt_text_encode_tokens and the image tower save nothing and are not affected. */
+int mvlpt_set_text_act_ckpt(void* handle, int segments);
+/* The plan the next saving text forward will use under the current setting (trainers/mvlpt.py:119-121, torch's
+ * checkpoint_sequential rule as above): *n_segments = k, first_layer[i] = first block of segment i for i < k (HOST array of `cap`
+ * entries; cap < k: MVLPT_ERR_ARG, *n_segments still set).  Segments 0 .. k-2 are checkpointed, segment k-1 is saved. */
+int mvlpt_text_act_ckpt_plan(void* handle, int32_t* first_layer, int cap, int* n_segments);
 
 /* CLIP.encode_text (clip/model.py:343-356: token_embedding(text) + positional_embedding -> transformer -> ln_final ->
  * x[arange, text.argmax(-1)] @ text_projection) for S sequences of token ids: what the zero-shot trainers feed (trainers/zsclip.py:45-49,

@@ -92,6 +92,8 @@ SIGNATURES = {
     "mvlpt_text_fwd_grouped": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_fwd_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_workspace_bytes": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int64)]),
+    "mvlpt_set_text_act_ckpt": (_i, [_vp, _i]),
+    "mvlpt_text_act_ckpt_plan": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(_i)]),
     "mvlpt_text_encode_tokens": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "mvlpt_text_ensemble": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mvlpt_logits_fwd": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp]),

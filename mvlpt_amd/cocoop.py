@@ -24,7 +24,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import distributed as dist_utils
-from .model import FrozenCLIP, PretokenizedPrompts, _text_inputs, build_prompt_layout
+from .model import FrozenCLIP, PretokenizedPrompts, _text_inputs, apply_text_act_ckpt, build_prompt_layout
 from .trainer import MVLPT, TrainerX, build_lr_scheduler, build_optimizer, load_pretrained_weights
 from .weights import get_arch, make_state_dict
 
@@ -143,6 +143,7 @@ class CustomCLIP(nn.Module):
         self.tokenized_prompts = self.prompt_learner.tokenized_prompts
         self.clip_model = clip_model
         self.engine = clip_model.engine
+        self.text_act_ckpt = apply_text_act_ckpt(cfg, self.engine)      # TRAINER.ACT_CKPT: images_per_chunk sees the smaller workspace
         self.logit_scale = clip_model.logit_scale
         self.logit_scale_exp = float(clip_model.logit_scale.exp())
         self.dtype = clip_model.dtype

@@ -60,6 +60,9 @@ def get_cfg_default() -> CfgNode:
                    FUSED=False)
     cfg.TRAIN = CN(PRINT_FREQ=5, CHECKPOINT_FREQ=0)
     cfg.TEST = CN(FINAL_MODEL="last_step", SPLIT="test", NO_TEST=False)   # Dassl's defaults; a run without evaluation data sets NO_TEST True
+    # ACT_CKPT (train.py:164, trainers/mvlpt.py:119-121): segments of the text tower's activation checkpointing; the three CustomCLIP
+    # classes set it on their engine (Engine.set_text_act_ckpt).  1: every block's activations are saved.  It applies with or without
+    # CUT_CONTEXTLEN (the reference: only with it) and changes memory and time, never a value.
     cfg.TRAINER = CN(NAME="MVLPT", CUT_CONTEXTLEN=False, ACT_CKPT=1)
     cfg.TRAINER.MVLPT = CN(
         PREC="fp16", PROJECT_METHOD="transformer", PROJECT_DIM=128,

@@ -160,6 +160,11 @@ struct TowerState {
   bool fold = false;
   float* part[2] = {nullptr, nullptr};   // [T][FOLD_NTP][2]
   int nt[2] = {0, 0}, ntp[2] = {0, 0};   // slots in use / slots per row, as the last producer wrote them
+  // Activation checkpointing (text tower, mvlpt_set_text_act_ckpt): the plan this forward ran under, seg[i] = first layer of segment
+  // i, seg[k] = layers.  Segments 0 .. k-2 kept only their input; the per-layer tensors above are then slots shared by the segments
+  // (indexed by the layer's position in its segment) and a backward recomputes each segment into them.  k = 1: nothing shared.
+  std::vector<int> seg;
+  bool consumed = false;                 // k > 1: a backward has overwritten the slots
 };
 constexpr int FOLD_NTP = 8;              // slots per row the buffers are sized for (gemm.hip: FOLD_MAX_NTP)
 
@@ -190,6 +195,7 @@ struct Engine {
   int dt = DT_F16;
   int prec_mode = MVLPT_PREC_SPLIT_GRAD;
   int fold_mode = 2;    // LayerNorm folding: 0 off, 1 image tower, 2 both towers (MVLPT_LN_FOLD, mvlpt_set_ln_fold)
+  int text_act_ckpt = 1;      // segments of the text tower's activation checkpointing (mvlpt_set_text_act_ckpt; 1: everything is saved)
   int fold_min_rows = 1024;   // towers with fewer token rows keep the stand-alone LayerNorm (a handful of tiles: nothing to win).  4096 until round 6: the small-tile
                               // consumer geometries were where the packed-fp32 hazard first showed (NOTES round 6); cfg1 (1 600 image rows): -1.5 %
   bool fold_ready = false;
@@ -336,11 +342,25 @@ hipError_t ln_bwd(Engine* E, const void* dy, int dy_dtype, const float* x, const
 }
 
 // ------------------------------------------------------------------------------------------------ tower workspace
+// The segments of torch.utils.checkpoint.checkpoint_sequential(blocks, segments, x), as the reference cuts its text tower
+// (trainers/mvlpt.py:119-121): k = min(max(segments, 1), layers) segments, the first k - 1 of layers / k blocks each (checkpointed),
+// the last one takes the rest (saved).  Returns the first layer of every segment and, behind them, `layers`.
+std::vector<int> ckpt_plan(int layers, int segments) {
+  const int k = std::min(std::max(segments, 1), std::max(layers, 1)), size = layers / k;
+  std::vector<int> seg((size_t)k + 1);
+  for (int i = 0; i < k; ++i) seg[i] = i * size;
+  seg[k] = layers;
+  return seg;
+}
 // `exact` (split-precision mode): every 16-bit operand buffer holds a hi|lo pair (twice the columns) and QKV / dO are fp32
-size_t tower_bytes(const TowerW& W, int N, int L, bool save, bool exact) {
-  const size_t T = (size_t)N * L, d = W.width, H = W.heads, nl = W.layers, X = exact ? 2 : 1;
+// segments > 1 (a saving text tower under activation checkpointing): the per-layer tensors shrink to the m slots of the largest
+// segment (the last one), the k segment inputs stay (x[0] and k - 1 boundary buffers)
+size_t tower_bytes(const TowerW& W, int N, int L, bool save, bool exact, int segments = 1) {
+  const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1;
+  const std::vector<int> seg = ckpt_plan(W.layers, save ? segments : 1);
+  const size_t k = seg.size() - 1, nl = k > 1 ? (size_t)(seg[k] - seg[k - 1]) : (size_t)W.layers;      // slots of the per-layer tensors
   size_t b = 0;
-  b += (save ? (2 * nl + 1) : 1) * align256(T * d * 4);             // x
+  b += (save ? (k > 1 ? k + 2 * nl - 1 : 2 * nl + 1) : 1) * align256(T * d * 4);             // x
   b += align256(T * d * 2 * X);                                      // h16
   b += (save ? nl : 1) * align256(T * 3 * d * 2 * X);                // qkv
   b += (save ? nl : 1) * align256(T * d * 2 * X);                    // attn
@@ -359,21 +379,49 @@ size_t tower_bytes(const TowerW& W, int N, int L, bool save, bool exact) {
 int wide_pitch(int cols) {
   return (4 * cols) % 4096 == 0 ? 2 * cols + 64 : 0;
 }
-void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool save, bool causal, bool exact, int xs) {
+void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool save, bool causal, bool exact, int xs, int segments = 1) {
   const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1; const int nl = W.layers;
   st = TowerState();
   st.N = N; st.L = L; st.d = (int)d; st.H = (int)H; st.layers = nl; st.saved = save; st.causal = causal; st.exact = exact;
   st.xs = exact ? xs : 0;
+  st.seg = ckpt_plan(nl, save ? segments : 1);
+  const int k = (int)st.seg.size() - 1;
   st.x.resize(2 * nl + 1); st.qkv.resize(nl); st.attn.resize(nl); st.u.resize(nl); st.lse.resize(nl); st.skip.assign(nl, 0);
   float* x0 = bp.take<float>(T * d);
-  for (int i = 0; i < 2 * nl + 1; ++i) st.x[i] = (save && i > 0) ? bp.take<float>(T * d) : x0;
-  st.h16 = bp.take_bytes(T * d * 2 * X);
-  for (int l = 0; l < nl; ++l) {
-    const bool fresh = save || l == 0;
-    st.qkv[l] = fresh ? bp.take_bytes(T * 3 * d * 2 * X) : st.qkv[0];
-    st.attn[l] = fresh ? bp.take_bytes(T * d * 2 * X) : st.attn[0];
-    st.lse[l] = fresh ? bp.take<float>((size_t)N * H * L) : st.lse[0];
-    st.u[l] = fresh ? bp.take_bytes(T * 4 * d * 2) : st.u[0];
+  if (k > 1) {
+    // layer l at position j of its segment: its input is the segment's input (x0, or the boundary buffer the block in front of
+    // it wrote) at j = 0 and slot j otherwise; x[2 l + 1] and the 16-bit tensors are slot j.  The largest segment is the last one.
+    const int m = st.seg[k] - st.seg[k - 1];
+    std::vector<float*> xin(m), xmid(m); std::vector<void*> qkv(m), attn(m), u(m); std::vector<float*> lse(m);
+    for (int j = 0; j < m; ++j) { xin[j] = j ? bp.take<float>(T * d) : nullptr; xmid[j] = bp.take<float>(T * d); }
+    st.x[2 * nl] = x0;      // the last block runs on compact rows: nothing is written here
+    for (int i = 0; i < k; ++i) {
+      float* in = i ? bp.take<float>(T * d) : x0;
+      for (int l = st.seg[i]; l < st.seg[i + 1]; ++l) {
+        const int j = l - st.seg[i];
+        st.x[2 * l] = j ? xin[j] : in; st.x[2 * l + 1] = xmid[j];
+      }
+    }
+    st.h16 = bp.take_bytes(T * d * 2 * X);
+    for (int j = 0; j < m; ++j) {
+      qkv[j] = bp.take_bytes(T * 3 * d * 2 * X); attn[j] = bp.take_bytes(T * d * 2 * X);
+      lse[j] = bp.take<float>((size_t)N * H * L); u[j] = bp.take_bytes(T * 4 * d * 2);
+    }
+    for (int i = 0; i < k; ++i)
+      for (int l = st.seg[i]; l < st.seg[i + 1]; ++l) {
+        const int j = l - st.seg[i];
+        st.qkv[l] = qkv[j]; st.attn[l] = attn[j]; st.lse[l] = lse[j]; st.u[l] = u[j];
+      }
+  } else {
+    for (int i = 0; i < 2 * nl + 1; ++i) st.x[i] = (save && i > 0) ? bp.take<float>(T * d) : x0;
+    st.h16 = bp.take_bytes(T * d * 2 * X);
+    for (int l = 0; l < nl; ++l) {
+      const bool fresh = save || l == 0;
+      st.qkv[l] = fresh ? bp.take_bytes(T * 3 * d * 2 * X) : st.qkv[0];
+      st.attn[l] = fresh ? bp.take_bytes(T * d * 2 * X) : st.attn[0];
+      st.lse[l] = fresh ? bp.take<float>((size_t)N * H * L) : st.lse[0];
+      st.u[l] = fresh ? bp.take_bytes(T * 4 * d * 2) : st.u[0];
+    }
   }
   st.a16 = bp.take_bytes(T * (4 * d * 2 * X + 128));
   st.wide_pitch = exact ? wide_pitch(4 * (int)d) : 0;
@@ -1473,7 +1521,8 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 // ------------------------------------------------------------------------------------------------ text tower
 // Bytes of txt_ws a text forward over C sequences of length L reserves, without the range table of a ranged / grouped forward and the
 // id table of mvlpt_text_encode_tokens (text_fwd_impl adds those).  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of
-// the ctx_pos table.
+// the ctx_pos table.  A saving tower is counted under the engine's activation-checkpointing setting (mvlpt_set_text_act_ckpt), the
+// same one the carve of the next forward uses.
 // mvlpt_text_workspace_bytes publishes this figure with ctx_rows = C * (L - 2), the largest n_ctx a forward accepts.  A ranged or
 // grouped forward over S sequences in G <= S groups of a class table no longer than S also reserves its range table, 2 G + 1 + 2 S
 // <= 4 S + 1 ints, and uses S * n_ctx of the ctx_pos rows, so the published figure still bounds the reservation whenever
@@ -1484,9 +1533,24 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 static size_t text_ws_bytes(Engine* E, int C, int L, bool save, bool exact, size_t ctx_rows) {
   const int dtw = E->arch.text_width;
   const size_t X = exact ? 2 : 1;
-  return tower_bytes(E->txt, C, L, save, exact) + compact_bytes(C, dtw, X) + align256((size_t)C * 4) + align256(ctx_rows * 4) + 4096;
+  return tower_bytes(E->txt, C, L, save, exact, E->text_act_ckpt) + compact_bytes(C, dtw, X) + align256((size_t)C * 4) + align256(ctx_rows * 4) + 4096;
 }
 static bool text_exact(const Engine* E) { return E->prec_mode == MVLPT_PREC_SPLIT_ALL || E->prec_mode == MVLPT_PREC_SPLIT_GRAD; }
+
+// Full-width text blocks first .. end-1 of one checkpoint segment (a tower without checkpointing is one `last` segment), starting
+// from the stand-alone ln_1.  Only the last segment hands a folded ln_1 on to the block behind it (the compact last block); a
+// checkpointed one closes with the plain residual epilogue, so that the segment behind it starts the same way in the first pass and
+// in the backward's recomputation.  *ln1_ready: what the block behind `end - 1` finds.
+static int text_segment_fwd(Engine* E, TowerState& st, int first, int end, bool last, bool* ln1_ready, hipStream_t s) {
+  *ln1_ready = false;
+  for (int l = first; l < end; ++l) {
+    bool produced = false;
+    const bool next = st.fold && (last || l + 1 < end);
+    if (int rc = block_fwd(E, E->txt, st, l, s, *ln1_ready, next ? &E->txt.blocks[l + 1].ln1 : nullptr, &produced)) return rc;
+    *ln1_ready = produced;
+  }
+  return 0;
+}
 
 // The text tower over C sequences.  Plain: mvlpt_text_fwd (prefix / suffix / layout / eot [C, ...], ctx [n_ctx, d] or CSC [C, n_ctx, d];
 // G = 0, Cg = C).  Ranged: mvlpt_text_fwd_ranged / _grouped, G groups over the [Cg, ...] class tables and ctx [G, n_ctx, d], C = S
@@ -1524,7 +1588,7 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
   E->ctx_pos = bp.take<int32_t>(ctx_rows);
   int32_t* range_dev = ranged ? bp.take<int32_t>(range_ints) : nullptr;
   int32_t* ids_dev = ids ? bp.take<int32_t>(ids_ints) : nullptr;
-  carve_tower(bp, E->txt, E->ts, C, L, save, true, exact, split_kind(E));
+  carve_tower(bp, E->txt, E->ts, C, L, save, true, exact, split_kind(E), E->text_act_ckpt);
   TowerState& st = E->ts;
   if (bp.off > bp.cap) { st.valid = false; return fail(E, MVLPT_ERR_STATE, "text_fwd: the workspace carve exceeds its reservation"); }
   E->tC = C; E->tL = L; E->t_nctx = n_ctx; E->t_per_class = ctx_per_class;
@@ -1549,11 +1613,15 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
       HIPCHK(E, launch_eot_rows(eot, E->eot_rows, C, L, s));
       if (save && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, C, L, n_ctx, s));
     } }
+  // Checkpointed segments (every one but the last, st.seg) run as a tower that saves nothing; their closing block writes the next
+  // segment's boundary buffer.  No ln_1 is folded across a segment boundary, so mvlpt_text_bwd can repeat a segment launch for launch.
   bool ln1_ready = false;
-  for (int l = 0; l + 1 < E->txt.layers; ++l) {
-    bool produced = false;
-    if (int rc = block_fwd(E, E->txt, st, l, s, ln1_ready, st.fold ? &E->txt.blocks[l + 1].ln1 : nullptr, &produced)) return rc;
-    ln1_ready = produced;
+  const int k = (int)st.seg.size() - 1;
+  for (int i = 0; i < k; ++i) {
+    st.saved = save && i == k - 1;
+    const int rc = text_segment_fwd(E, st, st.seg[i], std::min(st.seg[i + 1], E->txt.layers - 1), i == k - 1, &ln1_ready, s);
+    st.saved = save;
+    if (rc) { st.valid = false; return rc; }
   }
   // the last block on the C gathered EOT rows
   if (int rc = last_block_fwd(E, E->txt, st, E->tc, E->eot_rows, 0, false, ln1_ready, E->ln_final, false, s)) return rc;
@@ -1636,6 +1704,25 @@ int mvlpt_text_ensemble(const float* feats, int T, int C, int e, float* out, mvl
   return 0;
 }
 
+int mvlpt_set_text_act_ckpt(void* h, int segments) {
+  Engine* E = (Engine*)h;
+  if (!E) return fail(E, MVLPT_ERR_ARG, "set_text_act_ckpt: null handle");
+  if (segments < 1) return fail(E, MVLPT_ERR_ARG, "set_text_act_ckpt: segments must be at least 1");
+  E->text_act_ckpt = segments;      // clamped to the layer count where it is used (ckpt_plan)
+  return 0;
+}
+
+int mvlpt_text_act_ckpt_plan(void* h, int32_t* first_layer, int cap, int* n_segments) {
+  Engine* E = (Engine*)h;
+  if (!E || !first_layer || !n_segments || cap < 0) return fail(E, MVLPT_ERR_ARG, "text_act_ckpt_plan: null/invalid argument");
+  const std::vector<int> seg = ckpt_plan(E->txt.layers, E->text_act_ckpt);
+  const int k = (int)seg.size() - 1;
+  *n_segments = k;
+  if (cap < k) return fail(E, MVLPT_ERR_ARG, "text_act_ckpt_plan: first_layer holds fewer than n_segments entries");
+  for (int i = 0; i < k; ++i) first_layer[i] = seg[i];
+  return 0;
+}
+
 int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, int64_t* out) {
   Engine* E = (Engine*)h;
   if (!E || !out || C_total <= 0 || L <= 2) return fail(E, MVLPT_ERR_ARG, "text_workspace_bytes: null/invalid argument");
@@ -1648,6 +1735,8 @@ int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stre
   Engine* E = (Engine*)h;
   if (!E || !dfeat || !dctx) return fail(E, MVLPT_ERR_ARG, "text_bwd: null argument");
   TowerState& st = E->ts;
+  if (st.valid && st.consumed)
+    return fail(E, MVLPT_ERR_STATE, "text_bwd: a backward under activation checkpointing has consumed the saved state; run the forward again");
   if (!st.valid || !st.saved) return fail(E, MVLPT_ERR_STATE, "text_bwd: call text_fwd(save_for_bwd=1) first");
   if (E->t_nctx <= 0) return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward had no context tokens");
   hipStream_t s = (hipStream_t)stream;
@@ -1660,14 +1749,26 @@ int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stre
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dtw * 4.0);
     HIPCHK(E, launch_zero(st.dx32, T * dtw * 4, s)); }
   if (!E->tc.kept) return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward did not keep the last block's activations");
+  // the plan of the forward that saved this state (st.seg), not the engine's current setting
+  const int k = (int)st.seg.size() - 1;
+  if (k > 1) st.consumed = true;      // from here on the slots no longer hold what the forward left
   if (int rc = last_block_bwd(E, E->txt, st, E->tc, E->eot_rows, 0, E->ln_final, s)) return rc;      // the last block on the C compact EOT rows
-  for (int l = st.layers - 2; l >= 0; --l)
+  for (int l = st.layers - 2; l >= st.seg[k - 1]; --l)
     if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
+  // checkpointed segments, from the back: the forward's launches again from the segment's input, this time keeping lse / u, into
+  // the slots the segment behind it no longer needs; then its backward
+  for (int i = k - 2; i >= 0; --i) {
+    bool ln1_ready = false;
+    if (int rc = text_segment_fwd(E, st, st.seg[i], st.seg[i + 1], false, &ln1_ready, s)) return rc;
+    for (int l = st.seg[i + 1] - 1; l >= st.seg[i]; --l)
+      if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
+  }
   { ProfScope ps(E, s, PC_GLUE, 0, (double)C * E->t_nctx * dtw * 4.0);
     if (E->t_kind == TextKind::Ranged)
       HIPCHK(E, launch_gather_ctx_grad_ranged(st.dx32, E->ctx_pos, E->t_rlo, E->t_rstart, E->t_groups, L, dtw, E->t_nctx, dctx, st.scale_dev, s));
     else
       HIPCHK(E, launch_gather_ctx_grad(st.dx32, E->ctx_pos, C, L, dtw, E->t_nctx, E->t_per_class, dctx, st.scale_dev, s)); }
+  if (k > 1) st.saved = false;
   return 0;
 }
 

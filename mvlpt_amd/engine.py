@@ -152,6 +152,21 @@ class Engine:
         _lib.check(lib.mvlpt_set_precision(self.h, int(code)), self.h, "set_precision")
         self.precision = int(code)
 
+    def set_text_act_ckpt(self, segments: int) -> None:
+        """TRAINER.ACT_CKPT (include/mvlpt_hip.h: mvlpt_set_text_act_ckpt): the text tower keeps only the inputs of `segments`
+        segments (torch's checkpoint_sequential rule) and runs all but the last one again inside text_bwd.  1: everything is
+        saved.  Applies from the next text forward and to text_workspace_bytes."""
+        _lib.check(lib.mvlpt_set_text_act_ckpt(self.h, int(segments)), self.h, "set_text_act_ckpt")
+
+    def text_act_ckpt_plan(self) -> List[Tuple[int, int, bool]]:
+        """The plan the next saving text forward uses, as mvlpt_amd.model.checkpoint_segments gives it:
+        [(first, last_exclusive, checkpointed)]."""
+        layers = int(self.arch.transformer_layers)
+        first, n = (C.c_int32 * max(layers, 1))(), C.c_int(0)
+        _lib.check(lib.mvlpt_text_act_ckpt_plan(self.h, first, max(layers, 1), C.byref(n)), self.h, "text_act_ckpt_plan")
+        lo = [int(first[i]) for i in range(n.value)] + [layers]
+        return [(lo[i], lo[i + 1], i < n.value - 1) for i in range(n.value)]
+
     def set_vpt_dropout(self, masks: Optional[torch.Tensor]) -> None:
         """Per-image dropout masks of the visual prompt rows for the next image_fwd / image_bwd pair (include/mvlpt_hip.h:
         mvlpt_set_vpt_dropout): fp32 [n_layers, B, n_vpt, width], or None to clear.  One-shot: the next image_fwd consumes the setting

@@ -196,6 +196,31 @@ MAX_SEQUENCES_PER_TOWER = 32768
 MIN_SEQUENCES_PER_CHUNK = 512
 
 
+def checkpoint_segments(layers: int, segments: int) -> List[tuple]:
+    """TRAINER.ACT_CKPT's cut of the text blocks, [(first, last_exclusive, checkpointed)], by the rule of
+    torch.utils.checkpoint.checkpoint_sequential (the reference: trainers/mvlpt.py:119-121): k = min(max(segments, 1), layers)
+    segments, the first k - 1 of layers // k blocks each are checkpointed, the last one takes the rest and is saved.  The last
+    segment is the largest and its size is not monotonic in k (12 layers: k = 5 -> 4 blocks, k = 7 -> 6).  The engine computes
+    the same plan itself (Engine.text_act_ckpt_plan)."""
+    k = min(max(int(segments), 1), int(layers))
+    size = layers // k
+    return [(i * size, (i + 1) * size, True) for i in range(k - 1)] + [((k - 1) * size, layers, False)]
+
+
+def apply_text_act_ckpt(cfg, engine) -> int:
+    """Set cfg.TRAINER.ACT_CKPT (absent: 1) on the engine of a model that is being built; returns the value.  The reference
+    honours the key only together with CUT_CONTEXTLEN (its other branch calls self.transformer(x) directly); here it applies
+    either way, since checkpointing changes no value.  An engine without the setting saves everything, which is ACT_CKPT = 1;
+    asking such an engine for more is an error, not a silent no-op."""
+    n = int(cfg.TRAINER.get("ACT_CKPT", 1))
+    setter = getattr(engine, "set_text_act_ckpt", None)
+    if setter is not None:
+        setter(n)
+    elif n != 1:
+        raise ValueError(f"TRAINER.ACT_CKPT = {n}: this engine ({type(engine).__name__}) has no activation checkpointing")
+    return n
+
+
 def plan_text_chunks(eot: Sequence[int], workspace_bytes: Callable[[int, int], int], budget: int, min_len: int = TEXT_MIN_L,
                      max_seq: int = MAX_SEQUENCES_PER_TOWER, min_chunk: int = MIN_SEQUENCES_PER_CHUNK,
                      force_len: Optional[int] = None):
@@ -658,6 +683,7 @@ class CustomCLIP(nn.Module):
         self.tokenized_prompts = self.prompt_learner.tokenized_prompts
         self.clip_model = clip_model
         self.engine = clip_model.engine
+        self.text_act_ckpt = apply_text_act_ckpt(cfg, self.engine)      # TRAINER.ACT_CKPT
         self.logit_scale = clip_model.logit_scale
         self.logit_scale_exp = float(clip_model.logit_scale.exp())
         self.dtype = clip_model.dtype

@@ -40,7 +40,7 @@ import torch.nn as nn
 
 from . import _lib
 from .cocoop import DEFAULT_MAX_TEXT_WORKSPACE_BYTES, MAX_SEQUENCES_PER_TOWER
-from .model import FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, _text_inputs, build_prompt_layout
+from .model import FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, _text_inputs, apply_text_act_ckpt, build_prompt_layout
 from .model import MultitaskVLPromptLearner as _BasePromptLearner
 from .weights import is_resnet
 
@@ -260,6 +260,7 @@ class CustomCLIP(nn.Module):
         self.tokenized_prompts = self.prompt_learner.tokenized_prompts
         self.clip_model = clip_model
         self.engine = clip_model.engine
+        self.text_act_ckpt = apply_text_act_ckpt(cfg, self.engine)      # TRAINER.ACT_CKPT: the chunk planner sees the smaller workspace
         self.logit_scale = clip_model.logit_scale
         self.logit_scale_exp = float(clip_model.logit_scale.exp())
         self.dtype = clip_model.dtype

@@ -1,13 +1,34 @@
-"""Time the text tower fwd+bwd alone (C=100, L=77, ViT-B/16 text width 512) through the engine. GPU box only."""
-import sys, os, time
+"""Time the text tower fwd+bwd alone (C=100, L=77, ViT-B/16 text width 512) through the engine. GPU box only.
+
+  python tools/text_bench.py [C] [L] [--act-ckpt N] [--n-ctx 16] [--reps 7] [--iters 20]
+
+--act-ckpt N: TRAINER.ACT_CKPT (Engine.set_text_act_ckpt); prints the plan, the workspace bytes of the step and the median over
+`reps` timings of `iters` forward + backward pairs each."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from mvlpt_amd.model import FrozenCLIP, build_prompt_layout
 from mvlpt_amd.weights import ARCHS, make_state_dict
+
+ap = argparse.ArgumentParser()
+ap.add_argument("C", nargs="?", type=int, default=100)
+ap.add_argument("L", nargs="?", type=int, default=77)
+ap.add_argument("--act-ckpt", type=int, default=1)
+ap.add_argument("--n-ctx", type=int, default=16)
+ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--iters", type=int, default=20)
+args = ap.parse_args()
+
 arch = ARCHS["ViT-B/16"]
 clip = FrozenCLIP(make_state_dict(arch, 1), precision=os.environ.get("PREC", "split_grad"))
 eng = clip.engine
-C, L, n = int(sys.argv[1]) if len(sys.argv) > 1 else 100, int(sys.argv[2]) if len(sys.argv) > 2 else 77, 16
+eng.set_text_act_ckpt(args.act_ckpt)
+C, L, n = args.C, args.L, args.n_ctx
 nl = [1 + (i % 3) for i in range(C)]
 layout = build_prompt_layout(nl, n, L, "middle").cuda()
 eot = torch.tensor([n + x + 2 for x in nl], dtype=torch.int32).cuda()
@@ -15,18 +36,34 @@ pre = torch.randn(C, 1, 512, device="cuda") * 0.02
 suf = torch.randn(C, L - 1 - n, 512, device="cuda") * 0.02
 ctx = torch.randn(n, 512, device="cuda") * 0.02
 dfeat = torch.randn(C, 512, device="cuda") * 1e-3
+
+
 def run():
     eng.text_fwd(pre, suf, ctx, layout, eot, save_for_bwd=True)
     eng.text_bwd(dfeat)
-for _ in range(3): run()
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-for _ in range(20): run()
-torch.cuda.synchronize()
-print(f"text tower C={C} L={L}: fwd+bwd {(time.perf_counter()-t0)/20*1e3:.3f} ms")
+
+
 def runf():
     eng.text_fwd(pre, suf, ctx, layout, eot, save_for_bwd=True)
-t0 = time.perf_counter()
-for _ in range(20): runf()
-torch.cuda.synchronize()
-print(f"   fwd only {(time.perf_counter()-t0)/20*1e3:.3f} ms")
+
+
+def timed(fn):
+    ms = []
+    for _ in range(args.reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) / args.iters * 1e3)
+    return statistics.median(ms), min(ms), max(ms)
+
+
+for _ in range(3):
+    run()
+plan = eng.text_act_ckpt_plan()
+ws = eng.text_workspace_bytes(C, L, True)
+both, fwd = timed(run), timed(runf)
+print(f"text tower C={C} L={L} act_ckpt={args.act_ckpt} (segments {[b - a for a, b, _ in plan]}): "
+      f"fwd+bwd {both[0]:.3f} ms (min {both[1]:.3f}, max {both[2]:.3f}; median of {args.reps}), workspace {ws} bytes ({ws / 2**30:.3f} GiB)")
+print(f"   fwd only {fwd[0]:.3f} ms")

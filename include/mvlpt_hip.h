@@ -179,29 +179,26 @@ int mvlpt_image_bwd(void* handle, const float* dfeat, float* dvpt, float* dvpt_d
 int mvlpt_text_fwd(void* handle, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
                    const int32_t* layout, const int32_t* eot, int C, int L, float* feat_out, int save_for_bwd,
                    mvlpt_stream_t stream);
-/* CoCoOp: PromptLearner.forward + one TextEncoder call per image (trainers/cocoop.py:123-161, 48-59, 184-189) as ONE tower over
- * G * C sequences.  Sequence s = g * C + c is class c's prefix / suffix / layout row / eot with context block g of ctx [G,n_ctx,dt] fp32
- * (ctx + meta_net(image g), one block per image); prefix [C,1,dt], suffix [C,L-1-n_ctx,dt], layout int32 [C,L] and eot int32 [C] are
- * the class tables of mvlpt_text_fwd, read G times (never copied).  feat_out [G*C,embed] fp32, row s = (image g, class c).
- * Runs as mvlpt_text_fwd_ranged with every range full. */
-int mvlpt_text_fwd_grouped(void* handle, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
-                           const int32_t* eot, int G, int C, int L, float* feat_out, int save_for_bwd, mvlpt_stream_t stream);
-/* The MVLPT trainer's CoCoOp branch under MULTITASK_LABEL_PERTASK (trainers/mvlpt.py:556-581): image g keeps only the logits of its own
- * task's class range, so only those sequences run.  Group g owns classes [class_lo[g], class_hi[g]), 0 <= lo <= hi <= C (an empty range
- * is legal, not all of them); its sequences are those classes in order, the groups follow one another: S = sum_g (hi - lo) sequences,
- * feat_out [S,embed] fp32.  class_lo / class_hi are HOST int32 [G] arrays (the task of an image is known on the host before the step);
- * they are checked and uploaded with the call, which stays enqueue-only.  The class tables are those of mvlpt_text_fwd_grouped, read
- * through the ranges, never copied.  G <= 65535, S * L inside int32.  lo = 0, hi = C for every g is text_fwd_grouped. */
+/* Image-conditioned prompts: one context block per image, ctx [G,n_ctx,dt] fp32 (ctx + meta_net(image g)), against the class tables of
+ * mvlpt_text_fwd (prefix [C,1,dt], suffix [C,L-1-n_ctx,dt], layout int32 [C,L], eot int32 [C]), which are read through the ranges,
+ * never copied, as ONE tower.  The MVLPT trainer's CoCoOp branch under MULTITASK_LABEL_PERTASK (trainers/mvlpt.py:556-581): image g
+ * keeps only the logits of its own task's class range, so only those sequences run.  Group g owns classes [class_lo[g], class_hi[g]),
+ * 0 <= lo <= hi <= C (an empty range is legal, not all of them); its sequences are those classes in order, each class c's prefix /
+ * suffix / layout row / eot with context block g, the groups follow one another: S = sum_g (hi - lo) sequences, feat_out [S,embed] fp32.
+ * class_lo / class_hi are HOST int32 [G] arrays (the task of an image is known on the host before the step); they are checked and
+ * uploaded with the call, which stays enqueue-only.  G <= 65535, S * L inside int32.
+ * Every range [0, C) is CoCoOp's tower, PromptLearner.forward + one TextEncoder call per image (trainers/cocoop.py:123-161, 48-59):
+ * S = G * C, row g * C + c = (image g, class c). */
 int mvlpt_text_fwd_ranged(void* handle, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                           const int32_t* eot, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L, float* feat_out,
                           int save_for_bwd, mvlpt_stream_t stream);
-/* dfeat [C,embed] fp32 -> dctx (same shape as ctx).  Must follow text_fwd(save_for_bwd=1).  After text_fwd_grouped(save_for_bwd=1):
- * dfeat [G*C,embed] -> dctx [G,n_ctx,dt], dctx[g] = sum over the C classes of image g (fixed order: deterministic).  After
- * text_fwd_ranged(save_for_bwd=1): dfeat [S,embed] -> dctx [G,n_ctx,dt], dctx[g] = sum over the sequences of group g's own range in the
- * same fixed order (no atomics); all zeros for an empty range. */
+/* dfeat [C,embed] fp32 -> dctx (same shape as ctx).  Must follow text_fwd(save_for_bwd=1).  After
+ * text_fwd_ranged(save_for_bwd=1): dfeat [S,embed] -> dctx [G,n_ctx,dt], dctx[g] = sum over the sequences of group g's own range in a
+ * fixed order (no atomics: deterministic); all zeros for an empty range.  CoCoOp's full ranges: dfeat [G*C,embed], dctx[g] = sum over
+ * the C classes of image g. */
 int mvlpt_text_bwd(void* handle, const float* dfeat, float* dctx, mvlpt_stream_t stream);
-/* *out = bytes of text-tower workspace a text_fwd / text_fwd_grouped / text_fwd_ranged over C_total sequences of length L reserves (the
- * ctx-position table counted for the largest n_ctx, L - 2; a grouped or ranged tower adds its range tables, and a ranged one a per-class
+/* *out = bytes of text-tower workspace a text_fwd / text_fwd_ranged over C_total sequences of length L reserves (the
+ * ctx-position table counted for the largest n_ctx, L - 2; a ranged tower adds its range tables and a per-class
  * position table, a few bytes per class and sequence, which the figure covers unless n_ctx is within a few tokens of L - 2); the
  * workspace only grows, so a caller that chunks G keeps its peak under a budget.  With save_for_bwd the figure is the one under the
  * current mvlpt_set_text_act_ckpt setting (below): fewer saved layers, more sequences per chunk. */
@@ -209,7 +206,7 @@ int mvlpt_text_workspace_bytes(void* handle, int C_total, int L, int save_for_bw
 /* Activation checkpointing of the text tower, TRAINER.ACT_CKPT of the reference (trainers/mvlpt.py:119-121:
  * checkpoint_sequential(resblocks, ACT_CKPT, x)).  An engine setting like mvlpt_set_precision; default 1 (everything saved).
  * The plan is torch's: k = min(segments, text_layers) segments, the first k - 1 of text_layers / k blocks each, the last one takes
- * the rest.  A saving forward (text_fwd / _grouped / _ranged with save_for_bwd = 1) keeps only the input of the first k - 1 segments
+ * the rest.  A saving forward (text_fwd / text_fwd_ranged with save_for_bwd = 1) keeps only the input of the first k - 1 segments
  * and the activations of the last one; mvlpt_text_bwd runs every other segment again before that segment's backward, launch for launch
  * as the forward did (no LayerNorm is folded across a segment boundary: k - 1 more LayerNorm launches), so features and dctx have
  * the bits of an un-checkpointed tower whenever LayerNorm folding is off or the tower is below its row threshold, and stay within
@@ -257,18 +254,15 @@ int mvlpt_logits_fwd(void* handle, const float* img_feat, const float* txt_feat,
 /* dlogits [B,C] -> dimg [B,embed], dtxt [C,embed] (either may be NULL).  Uses the features of the last
  * mvlpt_logits_fwd call on this handle. */
 int mvlpt_logits_bwd(void* handle, const float* dlogits, float* dimg, float* dtxt, mvlpt_stream_t stream);
-/* CoCoOp's head (trainers/cocoop.py:184-189): logits[g,c] = logit_scale_exp * <img_g/|img_g|, txt_{gC+c}/|txt_{gC+c}|>,
- * img [G,embed], txt [G*C,embed] (rows of mvlpt_text_fwd_grouped), logits [G,C]; fp32 throughout.  The backward gives dtxt [G*C,embed]
- * only (the image tower is frozen and carries no prompts there).  Uses the features of the last logits_grouped_fwd on this handle.
- * Runs as the ranged head with every range full; each backward still follows only the forward of its own name (MVLPT_ERR_STATE). */
-int mvlpt_logits_grouped_fwd(void* handle, const float* img, const float* txt, float logit_scale_exp, int G, int C, float* logits,
-                             mvlpt_stream_t stream);
-int mvlpt_logits_grouped_bwd(void* handle, const float* dlogits, float* dtxt, mvlpt_stream_t stream);
 /* The ranged head: img [G,embed], txt [S,embed] (rows of mvlpt_text_fwd_ranged over the same HOST class_lo / class_hi), logits [G,C]:
  * inside image g's range the cosine logit against its own text row, outside it exactly 0.0f (logits * select_index, :581).
  * The backward reads dlogits [G,C] inside the ranges only and gives dtxt [S,embed] and / or dimg [G,embed] (either may be NULL): dimg is
  * the gradient with respect to the UN-normalised image features (the image tower may carry visual prompts on this route).  Uses the
- * features of the last logits_ranged_fwd on this handle. */
+ * features of the last logits_ranged_fwd on this handle; after mvlpt_logits_fwd it returns MVLPT_ERR_STATE, as mvlpt_logits_bwd does
+ * after logits_ranged_fwd.  fp32 throughout.
+ * Every range [0, C) is CoCoOp's head (trainers/cocoop.py:184-189): logits[g,c] = logit_scale_exp * <img_g/|img_g|,
+ * txt_{gC+c}/|txt_{gC+c}|> over txt [G*C,embed]; its backward asks for dtxt only (dimg NULL: the image tower is frozen and carries no
+ * prompts there). */
 int mvlpt_logits_ranged_fwd(void* handle, const float* img, const float* txt, float logit_scale_exp, const int32_t* class_lo,
                             const int32_t* class_hi, int G, int C, float* logits, mvlpt_stream_t stream);
 int mvlpt_logits_ranged_bwd(void* handle, const float* dlogits, float* dtxt, float* dimg, mvlpt_stream_t stream);
@@ -378,9 +372,9 @@ int mvlpt_op_attention_fwd(int dtype, const void* qkv, void* out, float* lse, in
 int mvlpt_op_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int N, int L, int H, int causal, mvlpt_stream_t stream);
 int mvlpt_op_cast(int dtype, const float* in, void* out, int64_t n, mvlpt_stream_t stream);
-/* the glue of mvlpt_text_fwd_ranged / _grouped / text_bwd: x [S, L, d] fp32 = assembled prompts + pos [L, d] (layout entries must address
+/* the glue of mvlpt_text_fwd_ranged / text_bwd: x [S, L, d] fp32 = assembled prompts + pos [L, d] (layout entries must address
  * rows inside prefix / suffix / ctx) and dx [S, L, d] over the sequences of HOST class_lo / class_hi int32 [G] (see mvlpt_text_fwd_ranged;
- * lo = 0, hi = C for every g is the grouped tower, S = G * C), dctx [G, n_ctx, d] = sum over group g's sequences of dx at ctx_pos
+ * lo = 0, hi = C for every g is CoCoOp's tower, S = G * C), dctx [G, n_ctx, d] = sum over group g's sequences of dx at ctx_pos
  * int32 [C, n_ctx].  These two calls wait for their kernel (test entry points). */
 int mvlpt_op_assemble_prompts_ranged(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                                      const float* pos, float* x, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L,

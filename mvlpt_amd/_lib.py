@@ -89,7 +89,6 @@ SIGNATURES = {
     "mvlpt_image_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mvlpt_text_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_bwd": (_i, [_vp, _vp, _vp, _vp]),
-    "mvlpt_text_fwd_grouped": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_fwd_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_workspace_bytes": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int64)]),
     "mvlpt_set_text_act_ckpt": (_i, [_vp, _i]),
@@ -98,8 +97,6 @@ SIGNATURES = {
     "mvlpt_text_ensemble": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "mvlpt_logits_fwd": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp]),
     "mvlpt_logits_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
-    "mvlpt_logits_grouped_fwd": (_i, [_vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
-    "mvlpt_logits_grouped_bwd": (_i, [_vp, _vp, _vp, _vp]),
     "mvlpt_logits_ranged_fwd": (_i, [_vp, _vp, _vp, _f, _vp, _vp, _i, _i, _vp, _vp]),
     "mvlpt_logits_ranged_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mvlpt_cross_entropy": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),

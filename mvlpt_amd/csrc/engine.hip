@@ -185,10 +185,10 @@ static const char* kProfNames[PC_COUNT] = {"gemm_bt", "attention_fwd", "attentio
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes, flops_exec; int M = 0, N = 0, K = 0, epi = -1, split = 0, fold = 0; };
 
 // How the sequences of a text forward are put together: prompts of C classes (mvlpt_text_fwd), prompts of per-group class ranges
-// (mvlpt_text_fwd_ranged; mvlpt_text_fwd_grouped is every range full), token ids (mvlpt_text_encode_tokens)
+// (mvlpt_text_fwd_ranged; CoCoOp is every range full), token ids (mvlpt_text_encode_tokens)
 enum class TextKind { Plain, Ranged, Ids };
-// The entry that ran the last head forward.  Grouped is computed as Ranged with every range full.
-enum class HeadKind { Plain, Grouped, Ranged };
+// The entry that ran the last head forward
+enum class HeadKind { Plain, Ranged };
 
 struct Engine {
   MvlptArch arch{};
@@ -231,7 +231,7 @@ struct Engine {
   // text fwd extras
   int tC = 0, tL = 0, t_nctx = 0, t_per_class = 0; int32_t* eot_rows = nullptr; int32_t* ctx_pos = nullptr;
   TextKind t_kind = TextKind::Plain;   // the last text forward
-  // TextKind::Ranged (mvlpt_text_fwd_ranged, mvlpt_text_fwd_grouped): t_groups groups, tC = sum of the range widths; device tables in txt_ws
+  // TextKind::Ranged (mvlpt_text_fwd_ranged): t_groups groups, tC = sum of the range widths; device tables in txt_ws
   int t_groups = 0; const int32_t *t_rlo = nullptr, *t_rstart = nullptr;
   std::vector<int32_t> t_range_host, h_range_host;   // host images of the range tables (source of the asynchronous upload)
   std::vector<int32_t> t_ids_host;   // mvlpt_text_encode_tokens: [ids (S * L, trimmed rows) | eot rows (S)], checked on the host
@@ -239,7 +239,7 @@ struct Engine {
   // head state
   int hB = 0, hC = 0; float h_scale = 0.f; const int32_t *h_lo = nullptr, *h_hi = nullptr;
   HeadKind h_kind = HeadKind::Plain;   // the last head forward; a backward runs only after the forward of its own name
-  // HeadKind::Grouped / Ranged: hB = G groups over hC classes, hS text rows; device tables in head_ws
+  // HeadKind::Ranged: hB = G groups over hC classes, hS text rows; device tables in head_ws
   int hS = 0; const int32_t *h_rlo = nullptr, *h_rstart = nullptr, *h_rgrp = nullptr;
   float *imn = nullptr, *txn = nullptr, *inorm = nullptr, *tnorm = nullptr;
   // profiling
@@ -1519,12 +1519,12 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 }
 
 // ------------------------------------------------------------------------------------------------ text tower
-// Bytes of txt_ws a text forward over C sequences of length L reserves, without the range table of a ranged / grouped forward and the
+// Bytes of txt_ws a text forward over C sequences of length L reserves, without the range table of a ranged forward and the
 // id table of mvlpt_text_encode_tokens (text_fwd_impl adds those).  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of
 // the ctx_pos table.  A saving tower is counted under the engine's activation-checkpointing setting (mvlpt_set_text_act_ckpt), the
 // same one the carve of the next forward uses.
-// mvlpt_text_workspace_bytes publishes this figure with ctx_rows = C * (L - 2), the largest n_ctx a forward accepts.  A ranged or
-// grouped forward over S sequences in G <= S groups of a class table no longer than S also reserves its range table, 2 G + 1 + 2 S
+// mvlpt_text_workspace_bytes publishes this figure with ctx_rows = C * (L - 2), the largest n_ctx a forward accepts.  A ranged
+// forward over S sequences in G <= S groups of a class table no longer than S also reserves its range table, 2 G + 1 + 2 S
 // <= 4 S + 1 ints, and uses S * n_ctx of the ctx_pos rows, so the published figure still bounds the reservation whenever
 // S * (L - 2 - n_ctx) >= 4 S + 1 + 128 ints (the 128 cover the two roundings to 256 bytes): n_ctx <= L - 7 from S = 129 sequences on,
 // n_ctx <= L - 8 from S = 65, the trainers' n_ctx = 4 or 16 at L = 77 from S = 3.  It does not when n_ctx is close to L - 2 (or for
@@ -1553,7 +1553,7 @@ static int text_segment_fwd(Engine* E, TowerState& st, int first, int end, bool 
 }
 
 // The text tower over C sequences.  Plain: mvlpt_text_fwd (prefix / suffix / layout / eot [C, ...], ctx [n_ctx, d] or CSC [C, n_ctx, d];
-// G = 0, Cg = C).  Ranged: mvlpt_text_fwd_ranged / _grouped, G groups over the [Cg, ...] class tables and ctx [G, n_ctx, d], C = S
+// G = 0, Cg = C).  Ranged: mvlpt_text_fwd_ranged, G groups over the [Cg, ...] class tables and ctx [G, n_ctx, d], C = S
 // sequences described by E->t_range_host.  Ids: mvlpt_text_encode_tokens, C sequences of token ids (E->t_ids_host); no prefix /
 // suffix / ctx / layout / eot tables.
 static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
@@ -1639,21 +1639,9 @@ int mvlpt_text_fwd(void* h, const float* prefix, const float* suffix, const floa
   return text_fwd_impl(E, TextKind::Plain, prefix, suffix, ctx, ctx_per_class, n_ctx, layout, eot, 0, C, C, L, feat_out, save_for_bwd, stream);
 }
 
-// PromptLearner.forward + the per-image TextEncoder calls of CoCoOp (trainers/cocoop.py:123-161, 48-59): one tower over G * C sequences,
-// the ranged tower with every range full
-int mvlpt_text_fwd_grouped(void* h, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
-                           const int32_t* eot, int G, int C, int L, float* feat_out, int save_for_bwd, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !prefix || !suffix || !ctx || !layout || !eot || !feat_out || G <= 0 || C <= 0 || L <= 0 || n_ctx <= 0)
-    return fail(E, MVLPT_ERR_ARG, "text_fwd_grouped: null/invalid argument");
-  if (G > 65535 || (int64_t)G * C > (int64_t)INT32_MAX / (L > 0 ? L : 1))
-    return fail(E, MVLPT_ERR_ARG, "text_fwd_grouped: too many sequences");
-  const std::vector<int32_t> lo((size_t)G, 0), hi((size_t)G, C);
-  const int64_t S = build_range_table(lo.data(), hi.data(), G, C, E->t_range_host);
-  return text_fwd_impl(E, TextKind::Ranged, prefix, suffix, ctx, 0, n_ctx, layout, eot, G, C, (int)S, L, feat_out, save_for_bwd, stream);
-}
-
-// The MVLPT trainer's CoCoOp branch under the per-task mask (trainers/mvlpt.py:556-581): image g runs only the classes of its own task
+// The MVLPT trainer's CoCoOp branch under the per-task mask (trainers/mvlpt.py:556-581): image g runs only the classes of its own task.
+// Every range [0, C) is PromptLearner.forward + the per-image TextEncoder calls of CoCoOp (trainers/cocoop.py:123-161, 48-59): one
+// tower over G * C sequences
 int mvlpt_text_fwd_ranged(void* h, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                           const int32_t* eot, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L, float* feat_out,
                           int save_for_bwd, mvlpt_stream_t stream) {
@@ -1813,7 +1801,7 @@ int mvlpt_logits_bwd(void* h, const float* dlogits, float* dimg, float* dtxt, mv
 }
 
 // The ranged head over the table in E->h_range_host (G groups, S text rows): image g against the text rows of its own class range
-static int head_ranged_fwd(Engine* E, HeadKind kind, const float* img, const float* txt, float scale, int G, int C, int S, float* logits,
+static int head_ranged_fwd(Engine* E, const float* img, const float* txt, float scale, int G, int C, int S, float* logits,
                            hipStream_t s) {
   const int e = E->arch.embed_dim;
   const size_t ints = E->h_range_host.size();
@@ -1829,7 +1817,7 @@ static int head_ranged_fwd(Engine* E, HeadKind kind, const float* img, const flo
   HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, G, e, s));
   HIPCHK(E, launch_normalize_rows(txt, E->txn, E->tnorm, S, e, s));
   HIPCHK(E, launch_logits_ranged(E->imn, E->txn, scale, tab, tab + G, logits, G, C, e, s));
-  E->hB = G; E->hC = C; E->hS = S; E->h_scale = scale; E->h_lo = E->h_hi = nullptr; E->h_kind = kind;
+  E->hB = G; E->hC = C; E->hS = S; E->h_scale = scale; E->h_lo = E->h_hi = nullptr; E->h_kind = HeadKind::Ranged;
   E->h_rlo = tab; E->h_rstart = tab + G; E->h_rgrp = tab + 2 * G + 1 + S;
   return 0;
 }
@@ -1842,26 +1830,8 @@ static int head_ranged_bwd(Engine* E, const float* dlogits, float* dtxt, float* 
   return 0;
 }
 
-// CoCoOp's head (trainers/cocoop.py:184-189): image g against its own C text features txt[g*C .. g*C + C), the ranged head with every
-// range full
-int mvlpt_logits_grouped_fwd(void* h, const float* img, const float* txt, float scale, int G, int C, float* logits, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !img || !txt || !logits || G <= 0 || C <= 0 || G > 65535 || (int64_t)G * C > INT32_MAX)
-    return fail(E, MVLPT_ERR_ARG, "logits_grouped_fwd: null/invalid argument");
-  E->hB = 0;
-  const std::vector<int32_t> lo((size_t)G, 0), hi((size_t)G, C);
-  const int64_t S = build_range_table(lo.data(), hi.data(), G, C, E->h_range_host);
-  return head_ranged_fwd(E, HeadKind::Grouped, img, txt, scale, G, C, (int)S, logits, (hipStream_t)stream);
-}
-
-int mvlpt_logits_grouped_bwd(void* h, const float* dlogits, float* dtxt, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !dlogits || !dtxt) return fail(E, MVLPT_ERR_ARG, "logits_grouped_bwd: null argument");
-  if (E->hB <= 0 || !E->imn || E->h_kind != HeadKind::Grouped) return fail(E, MVLPT_ERR_STATE, "logits_grouped_bwd: call logits_grouped_fwd first");
-  return head_ranged_bwd(E, dlogits, dtxt, nullptr, (hipStream_t)stream);      // the image side is frozen and carries no prompts there
-}
-
-// The ranged head (trainers/mvlpt.py:556-581): image g against the text rows of its own class range, 0 outside it
+// The ranged head (trainers/mvlpt.py:556-581): image g against the text rows of its own class range, 0 outside it.  Every range
+// [0, C) is CoCoOp's head (trainers/cocoop.py:184-189): image g against its own C text features txt[g*C .. g*C + C)
 int mvlpt_logits_ranged_fwd(void* h, const float* img, const float* txt, float scale, const int32_t* class_lo, const int32_t* class_hi,
                             int G, int C, float* logits, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
@@ -1870,7 +1840,7 @@ int mvlpt_logits_ranged_fwd(void* h, const float* img, const float* txt, float s
   E->hB = 0;
   const int64_t S = build_range_table(class_lo, class_hi, G, C, E->h_range_host);
   if (S <= 0) return fail(E, MVLPT_ERR_ARG, "logits_ranged_fwd: a class range is not inside [0, C], or every range is empty");
-  return head_ranged_fwd(E, HeadKind::Ranged, img, txt, scale, G, C, (int)S, logits, (hipStream_t)stream);
+  return head_ranged_fwd(E, img, txt, scale, G, C, (int)S, logits, (hipStream_t)stream);
 }
 
 int mvlpt_logits_ranged_bwd(void* h, const float* dlogits, float* dtxt, float* dimg, mvlpt_stream_t stream) {

@@ -343,31 +343,12 @@ class Engine:
         return feat
 
     @_on_device
-    def text_fwd_grouped(self, prefix: torch.Tensor, suffix: torch.Tensor, ctx: torch.Tensor, layout: torch.Tensor,
-                         eot: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
-        """CoCoOp's text side (mvlpt_text_fwd_grouped): ctx [G, n_ctx, dt], one context block per image, against the
-        [C, ...] class tables -> features [G*C, e], row g*C + c = (image g, class c).  A following text_bwd returns [G, n_ctx, dt]."""
-        prefix = _req(prefix, torch.float32, "token_prefix")
-        suffix = _req(suffix, torch.float32, "token_suffix")
-        layout = _req(layout, torch.int32, "layout")
-        eot = _req(eot, torch.int32, "eot")
-        ctx = _req(ctx, torch.float32, "ctx")
-        if ctx.dim() != 3:
-            raise ValueError("grouped ctx must be [G, n_ctx, ctx_dim]")
-        Cn, L = layout.shape
-        G, n_ctx = ctx.shape[0], ctx.shape[1]
-        feat = torch.empty(G * Cn, self.arch.embed_dim, device=prefix.device, dtype=torch.float32)
-        _lib.check(lib.mvlpt_text_fwd_grouped(self.h, _ptr(prefix), _ptr(suffix), _ptr(ctx), n_ctx, _ptr(layout), _ptr(eot),
-                                              G, Cn, L, _ptr(feat), int(save_for_bwd), _stream()), self.h, "text_fwd_grouped")
-        self._txt_state = (tuple(ctx.shape), layout, eot) if save_for_bwd else None
-        return feat
-
-    @_on_device
     def text_fwd_ranged(self, prefix: torch.Tensor, suffix: torch.Tensor, ctx: torch.Tensor, layout: torch.Tensor, eot: torch.Tensor,
                         class_lo, class_hi, save_for_bwd: bool = False) -> torch.Tensor:
         """The ranged text side (mvlpt_text_fwd_ranged): ctx [G, n_ctx, dt]; image g runs classes [class_lo[g], class_hi[g]) only.
         `class_lo` / `class_hi` are HOST integer sequences (lists, numpy or CPU tensors) of length G: nothing is read back from the
-        device.  Features [S, e], S = sum of the range widths, group after group.  A following text_bwd returns [G, n_ctx, dt]."""
+        device.  Features [S, e], S = sum of the range widths, group after group.  A following text_bwd returns [G, n_ctx, dt].
+        [0] * G, [C] * G is CoCoOp's text side: features [G*C, e], row g*C + c = (image g, class c)."""
         prefix = _req(prefix, torch.float32, "token_prefix")
         suffix = _req(suffix, torch.float32, "token_suffix")
         layout = _req(layout, torch.int32, "layout")
@@ -502,35 +483,10 @@ class Engine:
         return dimg, dtxt
 
     @_on_device
-    def logits_grouped_fwd(self, img_feat, txt_feat, logit_scale_exp: float) -> torch.Tensor:
-        """CoCoOp's head (mvlpt_logits_grouped_fwd): img [G, e] against its own rows of txt [G*C, e] -> logits [G, C]."""
-        img_feat = _req(img_feat, torch.float32, "img_feat")
-        txt_feat = _req(txt_feat, torch.float32, "txt_feat")
-        G = img_feat.shape[0]
-        if txt_feat.shape[0] % G:
-            raise ValueError(f"grouped head: {txt_feat.shape[0]} text rows are not a multiple of {G} images")
-        Cn = txt_feat.shape[0] // G
-        logits = torch.empty(G, Cn, device=img_feat.device, dtype=torch.float32)
-        _lib.check(lib.mvlpt_logits_grouped_fwd(self.h, _ptr(img_feat), _ptr(txt_feat), float(logit_scale_exp), G, Cn, _ptr(logits),
-                                                _stream()), self.h, "logits_grouped_fwd")
-        self._head_state = (None, None, G, Cn)
-        return logits
-
-    @_on_device
-    def logits_grouped_bwd(self, dlogits) -> torch.Tensor:
-        """d txt [G*C, e] of the last logits_grouped_fwd (the image side carries no gradient)."""
-        if self._head_state is None:
-            raise RuntimeError("logits_grouped_bwd without logits_grouped_fwd")
-        _, _, G, Cn = self._head_state
-        dlogits = _req(dlogits, torch.float32, "dlogits")
-        dtxt = torch.empty(G * Cn, self.arch.embed_dim, device=dlogits.device, dtype=torch.float32)
-        _lib.check(lib.mvlpt_logits_grouped_bwd(self.h, _ptr(dlogits), _ptr(dtxt), _stream()), self.h, "logits_grouped_bwd")
-        return dtxt
-
-    @_on_device
     def logits_ranged_fwd(self, img_feat, txt_feat, logit_scale_exp: float, class_lo, class_hi, n_cls: int) -> torch.Tensor:
         """The ranged head (mvlpt_logits_ranged_fwd): img [G, e] against txt [S, e] (rows of text_fwd_ranged over the same host ranges)
-        -> logits [G, n_cls], exactly 0 outside image g's range."""
+        -> logits [G, n_cls], exactly 0 outside image g's range.  [0] * G, [C] * G is CoCoOp's head: img [G, e] against its own
+        rows of txt [G*C, e]."""
         img_feat = _req(img_feat, torch.float32, "img_feat")
         txt_feat = _req(txt_feat, torch.float32, "txt_feat")
         G = img_feat.shape[0]
@@ -688,7 +644,7 @@ def join_mixed(p: torch.Tensor) -> torch.Tensor:
 def op_assemble_prompts_ranged(prefix, suffix, ctx, layout, pos, class_lo, class_hi) -> torch.Tensor:
     """x [S, L, d] of the ranged tower's entry (mvlpt_op_assemble_prompts_ranged): class rows of prefix [C,1,d] / suffix [C,L-1-n,d] /
     layout [C,L] with context block g of ctx [G,n,d], plus pos [L,d] (the first L rows are read).  class_lo / class_hi: host sequences
-    of length G; [0]*G, [C]*G is the grouped (CoCoOp) tower, S = G*C."""
+    of length G; [0]*G, [C]*G is CoCoOp's tower, S = G*C."""
     G, n, d = ctx.shape
     C_, L = layout.shape
     lo, hi, S = _host_ranges(class_lo, class_hi, G, C_)

@@ -187,7 +187,7 @@ class FrozenCLIP:
         return self.engine.image_fwd(image.to(self.device), None, None, save_for_bwd=False)
 
 
-# Workspace budget of one encode_text chunk (not a reference key), the figure CoCoOp's grouped tower uses
+# Workspace budget of one encode_text chunk (not a reference key), the figure CoCoOp's tower uses
 DEFAULT_MAX_TEXT_WORKSPACE_BYTES = 16 << 30
 # sequences per tower: the attention launches put the sequence index on grid.y
 MAX_SEQUENCES_PER_TOWER = 32768
@@ -305,6 +305,65 @@ class _ProjTransformer(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------ prompt learner
+def class_prompt_tables(clip_model: FrozenCLIP, classnames, pretokenized: Optional[PretokenizedPrompts], prompt_prefix: str, cut: bool):
+    """Tokenisation + frozen token embeddings of the class prompts (init time, CPU; trainers/mvlpt.py:292-307, trainers/cocoop.py:105-111):
+    (tokenized_prompts [n_cls, L], name_lens, embedding [n_cls, L, ctx_dim]).  `pretokenized` gives the first two instead of the
+    tokenizer; `cut` is TRAINER.CUT_CONTEXTLEN (L = the longest prompt), which the reference's CoCoOp trainer does not have."""
+    if pretokenized is not None:
+        tokenized_prompts, name_lens = pretokenized.tokenized_prompts, pretokenized.name_lens
+    else:
+        tok = clip_model.tokenizer
+        names = [n.replace("_", " ") for n in classnames]
+        name_lens = [len(tok.encode(n)) for n in names]
+        prompts = [prompt_prefix + " " + n + "." for n in names]
+        max_length = clip_model.context_length
+        if cut:
+            max_length = min(max_length, max(len(tok.encode(p)) + 2 for p in prompts))
+        tokenized_prompts = torch.cat([tok.tokenize(p, context_length=max_length) for p in prompts])
+    with torch.no_grad():
+        embedding = clip_model.token_embedding(tokenized_prompts).to(clip_model.dtype)
+    return tokenized_prompts, name_lens, embedding
+
+
+def register_class_tables(pl: nn.Module, n_cls: int, tables, n_ctx: int, position: str) -> None:
+    """Give the prompt learner `pl` what the HIP text tower reads, from `class_prompt_tables`: the `token_prefix` / `token_suffix`
+    buffers (saved by save_model, dropped by load_model; :312-316), the integer tables `layout` and `eot` (not persistent), and
+    `n_cls`, `tokenized_prompts`, `name_lens`, `max_eot`.  `n_ctx` context tokens stand at `position` ("end" | "middle" | "front")."""
+    tokenized_prompts, name_lens, embedding = tables
+    pl.register_buffer("token_prefix", embedding[:, :1, :].contiguous())                # SOS
+    pl.register_buffer("token_suffix", embedding[:, 1 + n_ctx:, :].contiguous())        # CLS, EOS
+    pl.n_cls = n_cls
+    pl.tokenized_prompts = tokenized_prompts
+    pl.name_lens = list(name_lens)
+    L = tokenized_prompts.shape[1]
+    pl.register_buffer("layout", build_prompt_layout(pl.name_lens, n_ctx, L, position), persistent=False)
+    pl.register_buffer("eot", tokenized_prompts.argmax(dim=-1).to(torch.int32), persistent=False)   # :128
+    pl.max_eot = int(pl.eot.max())
+
+
+def image_conditioned_ctx(clip_model: FrozenCLIP, n_ctx: int, ctx_init: str, ctx_dim: int, vis_dim: int, dtype):
+    """CoCoOp's trainable text side (trainers/cocoop.py:76-100, trainers/mvlpt.py:262-286): the context vectors [n_ctx, ctx_dim] (the
+    embedding of `ctx_init`, or N(0, 0.02)) and then `meta_net`, in the order the RNG is consumed.  Returns (ctx_vectors, meta_net,
+    prompt_prefix, n_ctx): `ctx_init` sets its own n_ctx."""
+    if ctx_init:
+        ctx_init = ctx_init.replace("_", " ")
+        n_ctx = len(ctx_init.split(" "))
+        ids = clip_model.tokenizer.tokenize(ctx_init)
+        with torch.no_grad():
+            ctx_vectors = clip_model.token_embedding(ids)[0, 1:1 + n_ctx, :].to(dtype)
+        prompt_prefix = ctx_init
+    else:
+        ctx_vectors = torch.empty(n_ctx, ctx_dim, dtype=dtype)
+        nn.init.normal_(ctx_vectors, std=0.02)
+        prompt_prefix = " ".join(["X"] * n_ctx)
+    meta_net = nn.Sequential(OrderedDict([
+        ("linear1", nn.Linear(vis_dim, vis_dim // 16)),
+        ("relu", nn.ReLU(inplace=True)),
+        ("linear2", nn.Linear(vis_dim // 16, ctx_dim)),
+    ]))
+    return ctx_vectors, meta_net, prompt_prefix, n_ctx
+
+
 class MultitaskVLPromptLearner(nn.Module):
     """trainers/mvlpt.py:138-515.  ``clip_model`` is a :class:`FrozenCLIP`; ``classnames`` a list of str, or a
     :class:`PretokenizedPrompts` (then ``classnames`` only gives n_cls)."""
@@ -319,37 +378,9 @@ class MultitaskVLPromptLearner(nn.Module):
                                       "mvlpt_amd.mvlpt_cocoop (MultitaskVLPromptLearner / CustomCLIP there; MVLPT.build_model picks them)")
         arch = clip_model.arch
         dtype = clip_model.dtype
-        if is_resnet(arch) and vpt_n_ctx != 0:
-            raise ValueError("visual prompts (VPT.N_CTX != 0, UPT) need a ViT backbone: a ResNet tower is frozen and forward-only here, and the "
-                             "reference cannot prompt it either (trainers/mvlpt.py:48 \"HACK: Assume all is vision transformer\")")
         coop_ctx_dim, vpt_ctx_dim = arch.transformer_width, arch.vision_width
-        clip_imsize, cfg_imsize = arch.image_resolution, cfg.INPUT.SIZE[0]
-        assert cfg_imsize == clip_imsize, f"cfg_imsize ({cfg_imsize}) must equal to clip_imsize ({clip_imsize})"
-
-        self.vpt_dropout = nn.Dropout(T.VPT.DROPOUT)                                    # :165 (applied per image: CustomCLIP.forward)
-        self.vpt_deep = T.VPT.DEEP
-        self.vpt_embeddings = None
-        self.vpt_embeddings_deep = None
-        prompt_prefix = ""
-        if vpt_n_ctx != 0:
-            if T.VPT.PROJECT > -1:                                                      # :170-175
-                vpt_dim = T.VPT.PROJECT
-                self.vpt_proj = nn.Linear(vpt_dim, vpt_ctx_dim, dtype=dtype)
-                nn.init.kaiming_normal_(self.vpt_proj.weight, a=0, mode="fan_out")
-            else:
-                vpt_dim = vpt_ctx_dim
-                self.vpt_proj = nn.Identity()
-            if T.VPT.CTX_INIT:
-                raise ValueError("CTX initiation scheme is not supported")            # :180-182
-            ps = arch.vision_patch_size
-            val = math.sqrt(6. / float(3 * reduce(mul, (ps, ps), 1) + vpt_dim))         # :186
-            self.vpt_embeddings = nn.Parameter(torch.zeros(1, vpt_n_ctx, vpt_dim, dtype=dtype))
-            nn.init.uniform_(self.vpt_embeddings.data, -val, val)
-            if self.vpt_deep:
-                self.vision_layers = arch.vision_layers
-                self.vpt_embeddings_deep = nn.Parameter(torch.zeros(arch.vision_layers - 1, vpt_n_ctx, vpt_dim, dtype=dtype))
-                nn.init.uniform_(self.vpt_embeddings_deep.data, -val, val)
-            prompt_prefix = "a photo of a "                                             # :201
+        self._init_visual_prompts(cfg, clip_model)
+        prompt_prefix = "a photo of a " if vpt_n_ctx != 0 else ""                       # :201
 
         self.ctx = None
         if coop_n_ctx != 0:
@@ -388,34 +419,47 @@ class MultitaskVLPromptLearner(nn.Module):
                     raise AttributeError("module 'torch.nn' has no attribute 'GeLU'")
         self.cocoop_ctx = None
 
-        # ---- tokenisation + frozen token embeddings (init time, CPU) : trainers/mvlpt.py:292-316 ----
-        if pretokenized is not None:
-            tokenized_prompts, name_lens = pretokenized.tokenized_prompts, pretokenized.name_lens
-        else:
-            tok = clip_model.tokenizer
-            names = [n.replace("_", " ") for n in classnames]
-            name_lens = [len(tok.encode(n)) for n in names]
-            prompts = [prompt_prefix + " " + n + "." for n in names]
-            if cfg.TRAINER.CUT_CONTEXTLEN:
-                max_length = min(clip_model.context_length, max(len(tok.encode(p)) + 2 for p in prompts))
-            else:
-                max_length = clip_model.context_length
-            tokenized_prompts = torch.cat([tok.tokenize(p, context_length=max_length) for p in prompts])
-        with torch.no_grad():
-            embedding = clip_model.token_embedding(tokenized_prompts).to(dtype)
-        self.register_buffer("token_prefix", embedding[:, :1, :].contiguous())                       # SOS
-        self.register_buffer("token_suffix", embedding[:, 1 + coop_n_ctx:, :].contiguous())         # CLS, EOS
-
-        self.n_cls, self.vpt_n_ctx, self.coop_n_ctx, self.cocoop_n_ctx = n_cls, vpt_n_ctx, coop_n_ctx, 0
-        self.tokenized_prompts = tokenized_prompts
-        self.name_lens = list(name_lens)
+        self.vpt_n_ctx, self.coop_n_ctx, self.cocoop_n_ctx = vpt_n_ctx, coop_n_ctx, 0
         self.class_token_position = T.COOP.CLASS_TOKEN_POSITION
-        L = tokenized_prompts.shape[1]
-        # integer tables consumed by the HIP text tower (bit-exact indexing)
-        self.register_buffer("layout", build_prompt_layout(self.name_lens, coop_n_ctx, L, self.class_token_position),
-                             persistent=False)
-        self.register_buffer("eot", tokenized_prompts.argmax(dim=-1).to(torch.int32), persistent=False)   # :128
-        self.max_eot = int(self.eot.max())
+        tables = class_prompt_tables(clip_model, classnames, pretokenized, prompt_prefix, cfg.TRAINER.CUT_CONTEXTLEN)
+        register_class_tables(self, n_cls, tables, coop_n_ctx, self.class_token_position)
+
+    def _init_visual_prompts(self, cfg, clip_model: FrozenCLIP) -> None:
+        """The image side of the constructor (trainers/mvlpt.py:165-201), for this class and the COCOOP.N_CTX != 0 route: the ResNet
+        refusal, the image-size check, `vpt_dropout` / `vpt_deep`, and with VPT.N_CTX != 0 `vpt_proj`, `vpt_embeddings` and
+        `vpt_embeddings_deep` (None otherwise).  The RNG is consumed in that order."""
+        V = cfg.TRAINER.MVLPT.VPT
+        arch, dtype = clip_model.arch, clip_model.dtype
+        vpt_n_ctx, vpt_ctx_dim = V.N_CTX, arch.vision_width
+        if is_resnet(arch) and vpt_n_ctx != 0:
+            raise ValueError("visual prompts (VPT.N_CTX != 0, UPT) need a ViT backbone: a ResNet tower is frozen and forward-only here, and the "
+                             "reference cannot prompt it either (trainers/mvlpt.py:48 \"HACK: Assume all is vision transformer\")")
+        clip_imsize, cfg_imsize = arch.image_resolution, cfg.INPUT.SIZE[0]
+        assert cfg_imsize == clip_imsize, f"cfg_imsize ({cfg_imsize}) must equal to clip_imsize ({clip_imsize})"
+
+        self.vpt_dropout = nn.Dropout(V.DROPOUT)                                        # :165 (applied per image: CustomCLIP.forward)
+        self.vpt_deep = V.DEEP
+        self.vpt_embeddings = None
+        self.vpt_embeddings_deep = None
+        if vpt_n_ctx == 0:
+            return
+        if V.PROJECT > -1:                                                              # :170-175
+            vpt_dim = V.PROJECT
+            self.vpt_proj = nn.Linear(vpt_dim, vpt_ctx_dim, dtype=dtype)
+            nn.init.kaiming_normal_(self.vpt_proj.weight, a=0, mode="fan_out")
+        else:
+            vpt_dim = vpt_ctx_dim
+            self.vpt_proj = nn.Identity()
+        if V.CTX_INIT:
+            raise ValueError("CTX initiation scheme is not supported")                # :180-182
+        ps = arch.vision_patch_size
+        val = math.sqrt(6. / float(3 * reduce(mul, (ps, ps), 1) + vpt_dim))             # :186
+        self.vpt_embeddings = nn.Parameter(torch.zeros(1, vpt_n_ctx, vpt_dim, dtype=dtype))
+        nn.init.uniform_(self.vpt_embeddings.data, -val, val)
+        if self.vpt_deep:
+            self.vision_layers = arch.vision_layers
+            self.vpt_embeddings_deep = nn.Parameter(torch.zeros(arch.vision_layers - 1, vpt_n_ctx, vpt_dim, dtype=dtype))
+            nn.init.uniform_(self.vpt_embeddings_deep.data, -val, val)
 
     # trainers/mvlpt.py:376-414
     def forward_mvlpt_proj(self, dtype=torch.float):

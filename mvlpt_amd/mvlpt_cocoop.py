@@ -29,20 +29,15 @@ sharding do not apply to per-image text features.
 """
 from __future__ import annotations
 
-import math
-from collections import OrderedDict
-from functools import reduce
-from operator import mul
 from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
-from . import _lib
-from .cocoop import DEFAULT_MAX_TEXT_WORKSPACE_BYTES, MAX_SEQUENCES_PER_TOWER
-from .model import FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, _text_inputs, apply_text_act_ckpt, build_prompt_layout
+from .cocoop import MAX_SEQUENCES_PER_TOWER, PerImageTextCLIP
+from .model import (FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, _text_inputs, class_prompt_tables, image_conditioned_ctx,
+                    register_class_tables)
 from .model import MultitaskVLPromptLearner as _BasePromptLearner
-from .weights import is_resnet
 
 
 class MultitaskVLPromptLearner(_BasePromptLearner):
@@ -60,84 +55,19 @@ class MultitaskVLPromptLearner(_BasePromptLearner):
             raise NotImplementedError("COOP.N_CTX != 0 together with COCOOP.N_CTX != 0: the reference builds a `ctx` its logits never "
                                       "depend on (trainers/mvlpt.py:556-571); set COOP.N_CTX 0")
         arch = clip_model.arch
-        dtype = clip_model.dtype                                                        # fp32 masters (module docstring)
-        if is_resnet(arch) and vpt_n_ctx != 0:
-            raise ValueError("visual prompts (VPT.N_CTX != 0, UPT) need a ViT backbone: a ResNet tower is frozen and forward-only here, and the "
-                             "reference cannot prompt it either (trainers/mvlpt.py:48 \"HACK: Assume all is vision transformer\")")
-        cocoop_ctx_dim, vpt_ctx_dim, vis_dim = arch.transformer_width, arch.vision_width, arch.embed_dim
-        clip_imsize, cfg_imsize = arch.image_resolution, cfg.INPUT.SIZE[0]
-        assert cfg_imsize == clip_imsize, f"cfg_imsize ({cfg_imsize}) must equal to clip_imsize ({clip_imsize})"
-
-        self.vpt_dropout = nn.Dropout(T.VPT.DROPOUT)                                    # :165
-        self.vpt_deep = T.VPT.DEEP
-        self.vpt_embeddings = None
-        self.vpt_embeddings_deep = None
-        if vpt_n_ctx != 0:                                                              # :167-201, as the base class
-            if T.VPT.PROJECT > -1:
-                vpt_dim = T.VPT.PROJECT
-                self.vpt_proj = nn.Linear(vpt_dim, vpt_ctx_dim, dtype=dtype)
-                nn.init.kaiming_normal_(self.vpt_proj.weight, a=0, mode="fan_out")
-            else:
-                vpt_dim = vpt_ctx_dim
-                self.vpt_proj = nn.Identity()
-            if T.VPT.CTX_INIT:
-                raise ValueError("CTX initiation scheme is not supported")            # :180-182
-            ps = arch.vision_patch_size
-            val = math.sqrt(6. / float(3 * reduce(mul, (ps, ps), 1) + vpt_dim))         # :186
-            self.vpt_embeddings = nn.Parameter(torch.zeros(1, vpt_n_ctx, vpt_dim, dtype=dtype))
-            nn.init.uniform_(self.vpt_embeddings.data, -val, val)
-            if self.vpt_deep:
-                self.vision_layers = arch.vision_layers
-                self.vpt_embeddings_deep = nn.Parameter(torch.zeros(arch.vision_layers - 1, vpt_n_ctx, vpt_dim, dtype=dtype))
-                nn.init.uniform_(self.vpt_embeddings_deep.data, -val, val)
+        self._init_visual_prompts(cfg, clip_model)                                      # :165-201, as the base class
         self.ctx = None
         self.mvlpt_proj = nn.Identity()                                                 # :235 (no COOP ctx: nothing to project)
 
-        ctx_init = T.COCOOP.CTX_INIT
-        if ctx_init:                                                                    # :262-270
-            ctx_init = ctx_init.replace("_", " ")
-            cocoop_n_ctx = len(ctx_init.split(" "))
-            ids = clip_model.tokenizer.tokenize(ctx_init)
-            with torch.no_grad():
-                ctx_vectors = clip_model.token_embedding(ids)[0, 1:1 + cocoop_n_ctx, :].to(dtype)
-            prompt_prefix = ctx_init
-        else:                                                                           # :271-275
-            ctx_vectors = torch.empty(cocoop_n_ctx, cocoop_ctx_dim, dtype=dtype)
-            nn.init.normal_(ctx_vectors, std=0.02)
-            prompt_prefix = " ".join(["X"] * cocoop_n_ctx)
+        ctx_vectors, self.meta_net, prompt_prefix, cocoop_n_ctx = image_conditioned_ctx(    # :262-286; fp32 masters (module docstring)
+            clip_model, cocoop_n_ctx, T.COCOOP.CTX_INIT, arch.transformer_width, arch.embed_dim, clip_model.dtype)
         self.cocoop_ctx = nn.Parameter(ctx_vectors)
-        self.meta_net = nn.Sequential(OrderedDict([                                     # :282-286
-            ("linear1", nn.Linear(vis_dim, vis_dim // 16)),
-            ("relu", nn.ReLU(inplace=True)),
-            ("linear2", nn.Linear(vis_dim // 16, cocoop_ctx_dim)),
-        ]))
 
-        if pretokenized is not None:
-            tokenized_prompts, name_lens = pretokenized.tokenized_prompts, pretokenized.name_lens
-        else:                                                                           # :292-305
-            tok = clip_model.tokenizer
-            names = [n.replace("_", " ") for n in classnames]
-            name_lens = [len(tok.encode(n)) for n in names]
-            prompts = [prompt_prefix + " " + n + "." for n in names]
-            if cfg.TRAINER.CUT_CONTEXTLEN:
-                max_length = min(clip_model.context_length, max(len(tok.encode(p)) + 2 for p in prompts))
-            else:
-                max_length = clip_model.context_length
-            tokenized_prompts = torch.cat([tok.tokenize(p, context_length=max_length) for p in prompts])
-        with torch.no_grad():
-            embedding = clip_model.token_embedding(tokenized_prompts).to(dtype)
-        self.register_buffer("token_prefix", embedding[:, :1, :].contiguous())                       # SOS
-        self.register_buffer("token_suffix", embedding[:, 1 + cocoop_n_ctx:, :].contiguous())       # CLS, EOS (:313-314)
-
-        self.n_cls, self.vpt_n_ctx, self.coop_n_ctx, self.cocoop_n_ctx = n_cls, vpt_n_ctx, 0, cocoop_n_ctx
-        self.tokenized_prompts = tokenized_prompts
-        self.name_lens = list(name_lens)
+        self.vpt_n_ctx, self.coop_n_ctx, self.cocoop_n_ctx = vpt_n_ctx, 0, cocoop_n_ctx
         self.class_token_position = T.COOP.CLASS_TOKEN_POSITION
-        L = tokenized_prompts.shape[1]
+        tables = class_prompt_tables(clip_model, classnames, pretokenized, prompt_prefix, cfg.TRAINER.CUT_CONTEXTLEN)   # :292-307
         # construct_prompts (:327-346) is cat([prefix, ctx, suffix]): the "end" layout of the HIP text tower
-        self.register_buffer("layout", build_prompt_layout(self.name_lens, cocoop_n_ctx, L, "end"), persistent=False)
-        self.register_buffer("eot", tokenized_prompts.argmax(dim=-1).to(torch.int32), persistent=False)
-        self.max_eot = int(self.eot.max())
+        register_class_tables(self, n_cls, tables, cocoop_n_ctx, "end")                 # token_suffix: CLS, EOS (:313-314)
 
     def forward(self, im_features):
         """forward_cocoop (:348-374) up to the shifted contexts [B, n_ctx, ctx_dim]; the prompts are assembled by the HIP tower."""
@@ -251,28 +181,15 @@ class _TextSideFn(torch.autograd.Function):
         return None, dimg, dctx, None, None, None, None
 
 
-class CustomCLIP(nn.Module):
+class CustomCLIP(PerImageTextCLIP):
     """trainers/mvlpt.py:517-583 for COCOOP.N_CTX != 0: `forward(image, task=None)` returns the logits [B, n_cls]."""
 
     def __init__(self, cfg, classnames, clip_model: FrozenCLIP, dm=None, pretokenized: Optional[PretokenizedPrompts] = None):
         super().__init__()
         self.prompt_learner = MultitaskVLPromptLearner(cfg, classnames, clip_model, pretokenized)
-        self.tokenized_prompts = self.prompt_learner.tokenized_prompts
-        self.clip_model = clip_model
-        self.engine = clip_model.engine
-        self.text_act_ckpt = apply_text_act_ckpt(cfg, self.engine)      # TRAINER.ACT_CKPT: the chunk planner sees the smaller workspace
-        self.logit_scale = clip_model.logit_scale
-        self.logit_scale_exp = float(clip_model.logit_scale.exp())
-        self.dtype = clip_model.dtype
-        self.trim_text_to_eot = False        # mvlpt_amd.model.CustomCLIP's switch, same default
+        self._init_engine_side(cfg, clip_model)      # precision raised to split_all, as in mvlpt_amd.cocoop.CustomCLIP
         self.ranged_text = True              # False: every range full (B x n_cls sequences) + multiplicative mask
-        self.max_text_workspace_bytes = DEFAULT_MAX_TEXT_WORKSPACE_BYTES
-        # Precision (DESIGN.md §2): the image features are meta_net's input and every text row carries a gradient; as
-        # mvlpt_amd.cocoop.CustomCLIP, raise the engine's default mode to split_all and leave an explicit "fast" alone
-        if self.engine.precision == _lib.PREC_SPLIT_GRAD:
-            self.engine.set_precision("split_all")
-        self.last_ncorrect = None
-        self.last_chunks = self.last_sequences = 0
+        self.last_sequences = 0
         self.last_recompute = False
         self._fwd_generation = 0
         self.multi_task_label_pertask = cfg.DATASET.MULTITASK_LABEL_PERTASK
@@ -343,12 +260,6 @@ class CustomCLIP(nn.Module):
             return self._image_side(image.to(self.clip_model.device))[1]
         finally:
             pl.train(was_training)
-
-    def interpret_images(self, images, topk: int = 5):
-        """Nearest vocabulary words of every image's own contexts: [B][n_ctx] lists of (word, distance), B * n_ctx rows in ONE
-        nearest-token call (mvlpt_amd.interpret)."""
-        from .interpret import nearest_words
-        return nearest_words(self.clip_model, self.image_contexts(images), topk)
 
     def forward(self, image, task=None):
         pl = self.prompt_learner

@@ -512,6 +512,12 @@ class MVLPT(TrainerX):
         clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec)
         self.model = model_cls(cfg, classnames, clip_model, dm=self.dm, pretokenized=pretok)
         self.model.prefetch_split = prefetch_split(cfg)
+        self.train_prompt_learner_only()
+
+    def train_prompt_learner_only(self):
+        """The tail of build_model, for every trainer whose `self.model` has a `prompt_learner`: freeze the rest, INIT_WEIGHTS, move
+        to the device, broadcast, optimizer."""
+        cfg = self.cfg
         for name, param in self.model.named_parameters():               # :855-858 (the towers hold no nn.Parameters)
             if "prompt_learner" not in name:
                 param.requires_grad_(False)
@@ -694,8 +700,12 @@ class MVLPT(TrainerX):
             path = osp.join(directory, name, model_file)
             if not osp.exists(path):
                 raise FileNotFoundError('Model not found at "{}"'.format(path))
-            ck = torch.load(path, map_location="cpu")
-            sd = {k.replace("upt_proj", "mvlpt_proj"): v for k, v in ck["state_dict"].items()}   # :1112
-            sd.pop("token_prefix", None)
-            sd.pop("token_suffix", None)
-            self._models[name].load_state_dict(sd, strict=False)
+            self.load_state_dict_from_checkpoint(name, torch.load(path, map_location="cpu"))
+
+    def load_state_dict_from_checkpoint(self, name, checkpoint):
+        """The part of load_model after the file read: `checkpoint` is a Dassl checkpoint dict (state_dict, epoch, ...).
+        token_prefix / token_suffix are dropped: they come from the current class names."""
+        sd = {k.replace("upt_proj", "mvlpt_proj"): v for k, v in checkpoint["state_dict"].items()}   # :1112
+        sd.pop("token_prefix", None)
+        sd.pop("token_suffix", None)
+        self._models[name].load_state_dict(sd, strict=False)

@@ -146,3 +146,71 @@ def test_mvlpt_embedded_cocoop_still_refused():
     with pytest.raises(NotImplementedError):
         MultitaskVLPromptLearner(cfg, ["a", "b"], OracleFrozenCLIP(tiny_sd_with_tokens(), ARCHS["tiny"]))
     assert get_cfg_default().TRAINER.COCOOP == {"N_CTX": 16, "CTX_INIT": "", "PREC": "fp16"}      # train.py:125-128
+
+
+# ------------------------------------------------------------------------------------------------ registration order
+def _registration_cases():
+    """(name, constructor) of one prompt learner per route, on the tiny arch with the hash tokenizer and three classes."""
+    from mvlpt_amd.cocoop import PromptLearner
+    from mvlpt_amd.config import get_cfg_default
+    from mvlpt_amd.model import MultitaskVLPromptLearner as Base
+    from mvlpt_amd.mvlpt_cocoop import MultitaskVLPromptLearner as Route
+    from mvlpt_amd.weights import ARCHS
+    from tests.fake_engine import OracleFrozenCLIP
+    arch = ARCHS["tiny"]
+    sd = tiny_sd_with_tokens()
+    names = ["cat", "red fox", "aeroplane"]
+
+    def make(cls, coop=0, cocoop=0, vpt=0, deep=False, project=-1):
+        def build():
+            cfg = get_cfg_default()
+            cfg.INPUT.SIZE = (arch.image_resolution, arch.image_resolution)
+            T = cfg.TRAINER.MVLPT
+            T.COOP.N_CTX, T.COCOOP.N_CTX, T.VPT.N_CTX, T.VPT.DEEP, T.VPT.PROJECT = coop, cocoop, vpt, deep, project
+            T.PROJECT_METHOD, T.PROJECT_DIM = "transformer", 64
+            cfg.TRAINER.COCOOP.N_CTX = 4
+            return cls(cfg, names, OracleFrozenCLIP(sd, arch))
+        return build
+    return [("coop", make(Base, coop=4)), ("upt_deep_project", make(Base, coop=4, vpt=3, deep=True, project=24)),
+            ("cocoop", make(PromptLearner)), ("mvlpt_cocoop_vpt", make(Route, cocoop=4, vpt=3, deep=True, project=24))]
+
+
+# name: state_dict() keys with shapes, in order.  The order is part of the format of what has been saved so far: the flat prompt
+# buffers, the fused optimizer's segments, the broadcast and optimizer checkpoints follow the parameter order, model checkpoints
+# the state_dict order.  The three learners share their setup helpers (mvlpt_amd.model), so a change there moves all of them.
+_TABLES = [("token_prefix", [3, 1, 128]), ("token_suffix", [3, 72, 128])]
+_BUFFERS = _TABLES + [("layout", [3, 77]), ("eot", [3])]
+_VPT = [("vpt_embeddings", [1, 3, 24]), ("vpt_embeddings_deep", [2, 3, 24])]
+_VPT_PROJ = [("vpt_proj.weight", [128, 24]), ("vpt_proj.bias", [128])]
+_META_NET = [("meta_net.linear1.weight", [8, 128]), ("meta_net.linear1.bias", [8]),
+             ("meta_net.linear2.weight", [128, 8]), ("meta_net.linear2.bias", [128])]
+_MVLPT_PROJ = [("mvlpt_proj.resblocks.0.attn.in_proj_weight", [192, 64]), ("mvlpt_proj.resblocks.0.attn.in_proj_bias", [192]),
+               ("mvlpt_proj.resblocks.0.attn.out_proj.weight", [64, 64]), ("mvlpt_proj.resblocks.0.attn.out_proj.bias", [64]),
+               ("mvlpt_proj.resblocks.0.ln_1.weight", [64]), ("mvlpt_proj.resblocks.0.ln_1.bias", [64]),
+               ("mvlpt_proj.resblocks.0.mlp.c_fc.weight", [256, 64]), ("mvlpt_proj.resblocks.0.mlp.c_fc.bias", [256]),
+               ("mvlpt_proj.resblocks.0.mlp.c_proj.weight", [64, 256]), ("mvlpt_proj.resblocks.0.mlp.c_proj.bias", [64]),
+               ("mvlpt_proj.resblocks.0.ln_2.weight", [64]), ("mvlpt_proj.resblocks.0.ln_2.bias", [64]),
+               ("mvlpt_proj_ctx_vpt_pre.weight", [64, 128]), ("mvlpt_proj_ctx_vpt_pre.bias", [64]),
+               ("mvlpt_proj_ctx_vpt_post.weight", [128, 64]), ("mvlpt_proj_ctx_vpt_post.bias", [128]),
+               ("mvlpt_proj_ctx_coop_pre.weight", [64, 128]), ("mvlpt_proj_ctx_coop_pre.bias", [64]),
+               ("mvlpt_proj_ctx_coop_post.weight", [128, 64]), ("mvlpt_proj_ctx_coop_post.bias", [128])]
+# A module's own parameters come first, then (state_dict only) its persistent buffers, then its submodules in registration order;
+# named_parameters() is the state_dict without the two buffers, named_buffers() adds the two non-persistent tables.
+REGISTRATION = {
+    "coop": [("ctx", [4, 128])] + _TABLES,
+    "upt_deep_project": _VPT + [("ctx", [4, 128])] + _TABLES + _VPT_PROJ + _MVLPT_PROJ,
+    "cocoop": [("ctx", [4, 128])] + _TABLES + _META_NET,
+    "mvlpt_cocoop_vpt": _VPT + [("cocoop_ctx", [4, 128])] + _TABLES + _VPT_PROJ + _META_NET,
+}
+
+
+def test_registration_order_of_the_three_prompt_learners():
+    cases = _registration_cases()
+    assert [n for n, _ in cases] == list(REGISTRATION)
+    for name, build in cases:
+        torch.manual_seed(11)
+        pl = build()
+        state = REGISTRATION[name]
+        assert [(k, list(v.shape)) for k, v in pl.state_dict().items()] == state, name
+        assert [(k, list(v.shape)) for k, v in pl.named_parameters()] == [kv for kv in state if kv not in _TABLES], name
+        assert [(k, list(v.shape)) for k, v in pl.named_buffers()] == _BUFFERS, name

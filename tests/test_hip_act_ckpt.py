@@ -112,7 +112,7 @@ def test_folded_tower_stays_within_the_oracle_bar_and_is_deterministic(folded):
     print(f"folded n=3 against n=1: features {_rel(out[3][0], out[1][0]):.2e}, dctx {_rel(out[3][1], out[1][1]):.2e}")
 
 
-# ------------------------------------------------------------------------------------------------ 3: ranged and grouped
+# ------------------------------------------------------------------------------------------------ 3: ranged, partial and full ranges
 def _group_inputs(small, G):
     from mvlpt_amd.model import build_prompt_layout
     g = torch.Generator().manual_seed(23)
@@ -127,6 +127,7 @@ def _group_inputs(small, G):
 
 
 def test_ranged_and_grouped_towers_keep_their_bits(small):
+    """The ranged tower over partial ranges and over every range full (CoCoOp's per-image tower)."""
     eng, e = small.eng, small.arch.embed_dim
     lo, hi = [0, 2, 1], [2, 2, 5]                       # the second group is empty
     C_, g, inputs = _group_inputs(small, len(lo))
@@ -138,14 +139,14 @@ def test_ranged_and_grouped_towers_keep_their_bits(small):
             eng.set_text_act_ckpt(n_seg)
             fr = eng.text_fwd_ranged(*inputs, lo, hi, save_for_bwd=True).clone()
             dr = eng.text_bwd(dfeat_r).clone()
-            fg = eng.text_fwd_grouped(*inputs, save_for_bwd=True).clone()
+            fg = eng.text_fwd_ranged(*inputs, [0] * len(lo), [C_] * len(lo), save_for_bwd=True).clone()
             dg = eng.text_bwd(dfeat_g).clone()
             torch.cuda.synchronize()
             res[n_seg] = (fr, dr, fg, dg)
     finally:
         eng.set_text_act_ckpt(1)
     assert bool(res[1][1].abs().max() > 0) and torch.equal(res[1][1][1], torch.zeros_like(res[1][1][1])), "empty range: zero gradient"
-    for a, b, what in zip(res[1], res[2], ("ranged features", "ranged dctx", "grouped features", "grouped dctx")):
+    for a, b, what in zip(res[1], res[2], ("ranged features", "ranged dctx", "full-range features", "full-range dctx")):
         assert torch.equal(a, b), f"{what}: ACT_CKPT = 2 differs from ACT_CKPT = 1"
 
 

@@ -1,4 +1,5 @@
-"""CoCoOp on the HIP engine (-m gpu): the grouped glue kernels, the grouped text tower against the existing CSC tower, the model
+"""CoCoOp on the HIP engine (-m gpu): the ranged glue kernels, text tower and head with every range full (one context block per image
+against every class), the tower against the existing CSC tower, the model
 against the REAL reference's fixtures (tools/make_cocoop_golden.py) at the project's criterion (max|d| <= 1e-3 max|ref|),
 chunking, and the trainer's step."""
 import numpy as np
@@ -83,8 +84,9 @@ def test_grouped_head_fwd_bwd_against_float64(tiny_clip):
     G, C, scale = 5, 9, 100.0
     img, txt = torch.randn(G, e, generator=g) * 3, torch.randn(G * C, e, generator=g) * 0.5
     dl = torch.randn(G, C, generator=g)
-    logits = eng.logits_grouped_fwd(img.to(DEV), txt.to(DEV), scale)
-    dtxt = eng.logits_grouped_bwd(dl.to(DEV))
+    logits = eng.logits_ranged_fwd(img.to(DEV), txt.to(DEV), scale, [0] * G, [C] * G, C)
+    dimg, dtxt = eng.logits_ranged_bwd(dl.to(DEV), need_img=False, need_txt=True)
+    assert dimg is None
     img64, txt64 = img.double(), txt.double().requires_grad_(True)
     imn = img64 / img64.norm(dim=-1, keepdim=True)
     txn = (txt64 / txt64.norm(dim=-1, keepdim=True)).view(G, C, e)
@@ -96,7 +98,7 @@ def test_grouped_head_fwd_bwd_against_float64(tiny_clip):
 
 # ------------------------------------------------------------------------------------------------ engine
 def test_grouped_text_tower_equals_csc_tower(tiny_clip):
-    """The grouped entry against the plain kernels.  (1, 17): a single group with more classes than the gather has waves; (2, 16):
+    """The ranged entry with every range full against the plain kernels.  (1, 17): a single group with more classes than the gather has waves; (2, 16):
     exactly one class per wave."""
     from mvlpt_amd.model import build_prompt_layout
     eng, arch = tiny_clip.engine, tiny_clip.arch
@@ -110,14 +112,14 @@ def test_grouped_text_tower_equals_csc_tower(tiny_clip):
         suffix = (torch.randn(C, L - 1 - n, dt, generator=g) * 0.02).to(DEV)
         ctx = (torch.randn(G, n, dt, generator=g) * 0.1).to(DEV)
         dfeat = torch.randn(G * C, arch.embed_dim, generator=g).to(DEV)
-        fg = eng.text_fwd_grouped(prefix, suffix, ctx, layout, eot, save_for_bwd=True)
+        fg = eng.text_fwd_ranged(prefix, suffix, ctx, layout, eot, [0] * G, [C] * G, save_for_bwd=True)
         dg = eng.text_bwd(dfeat)
-        assert dg.shape == (G, n, dt)
+        assert fg.shape == (G * C, arch.embed_dim) and dg.shape == (G, n, dt)
         fc = eng.text_fwd(prefix.repeat(G, 1, 1), suffix.repeat(G, 1, 1), ctx.repeat_interleave(C, 0), layout.repeat(G, 1),
                           eot.repeat(G), save_for_bwd=True)
         dc = eng.text_bwd(dfeat)
         torch.cuda.synchronize()
-        assert torch.equal(fg, fc), f"G={G} C={C}: grouped features must be bit-identical to the materialised CSC tower"
+        assert torch.equal(fg, fc), f"G={G} C={C}: full-range features must be bit-identical to the materialised CSC tower"
         want = dc.view(G, C, n, dt).double().sum(1)
         assert float((dg.double() - want).abs().max()) <= 1e-6 * float(want.abs().max()), f"G={G} C={C}"
         per_image = eng.text_workspace_bytes(C, L, True)
@@ -125,8 +127,7 @@ def test_grouped_text_tower_equals_csc_tower(tiny_clip):
 
 
 def test_head_backward_follows_only_its_own_forward(tiny_clip):
-    """logits_bwd, logits_grouped_bwd and logits_ranged_bwd each run after the forward of their own name and raise after either of
-    the other two, although the grouped head is computed by the ranged kernels."""
+    """logits_bwd and logits_ranged_bwd each run after the forward of their own name and raise after the other's."""
     eng = tiny_clip.engine
     e = tiny_clip.arch.embed_dim
     g = torch.Generator().manual_seed(11)
@@ -136,12 +137,10 @@ def test_head_backward_follows_only_its_own_forward(tiny_clip):
     dl = torch.randn(G, C, generator=g).to(DEV)
     forwards = {
         "plain": lambda: eng.logits_fwd(img, txt_c, 10.0),
-        "grouped": lambda: eng.logits_grouped_fwd(img, txt_gc, 10.0),
         "ranged": lambda: eng.logits_ranged_fwd(img, txt_gc, 10.0, [0] * G, [C] * G, C),
     }
     backwards = {
         "plain": lambda: eng.logits_bwd(dl),
-        "grouped": lambda: eng.logits_grouped_bwd(dl),
         "ranged": lambda: eng.logits_ranged_bwd(dl),
     }
     for f, fwd in forwards.items():

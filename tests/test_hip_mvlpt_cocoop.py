@@ -1,5 +1,5 @@
 """MVLPT's CoCoOp route on the HIP engine (-m gpu): the ranged glue kernels, the ranged head, the ranged text tower against the
-class-specific-context tower and the grouped tower, the model against the REAL reference's fixtures
+class-specific-context tower (partial ranges and every range full), the model against the REAL reference's fixtures
 (tools/make_mvlpt_cocoop_golden.py) at the project's criterion (max|d| <= 1e-3 max|ref|), ranged against dense,
 chunking with the recompute-in-backward path, and the trainer."""
 import numpy as np
@@ -80,7 +80,7 @@ def test_ranged_ctx_grad_gather_deterministic_and_exact():
         want[gi] += dx[s].double()[ctx_pos[c].long()]
     assert float((a.double() - want).abs().max()) <= 1e-6 * float(want.abs().max())
     assert torch.equal(a[3], torch.zeros(n, d)), "an empty range must give exact zeros"
-    # every range full (the grouped tower): group by group the bits of the generic-context gather over the group's C sequences
+    # every range full (CoCoOp's tower): group by group the bits of the generic-context gather over the group's C sequences
     G2 = 3
     dx2 = torch.randn(G2 * C, L, d, generator=g)
     full = op_gather_ctx_grad_ranged(dx2.to(DEV), ctx_pos.to(DEV), [0] * G2, [C] * G2).cpu()
@@ -165,25 +165,37 @@ def test_ranged_text_tower_equals_csc_tower(tiny_clip):
     assert torch.equal(eng.text_fwd_ranged(prefix, suffix, ctx, layout, eot, lo, hi, save_for_bwd=False), fr)
 
 
-def test_full_ranges_equal_grouped_tower(tiny_clip):
+def test_full_ranges_equal_csc_tower_and_float64_head(tiny_clip):
+    """Every range full (CoCoOp's case) at the shapes of this file: the tower against the materialised class-specific-context tower
+    (bit-equal features, context gradient within 1e-6 of the float64 sum over each image's classes), the head against float64 (1e-5);
+    the bounds of tests/test_hip_cocoop.py."""
     eng, arch = tiny_clip.engine, tiny_clip.arch
     g = torch.Generator().manual_seed(9)
     G = 3
     C, L, n, dt, layout, eot, prefix, suffix, ctx = _tower_inputs(arch, G, g)
-    dfeat = torch.randn(G * C, arch.embed_dim, generator=g).to(DEV)
-    img = torch.randn(G, arch.embed_dim, generator=g).to(DEV)
+    e = arch.embed_dim
+    dfeat = torch.randn(G * C, e, generator=g).to(DEV)
+    img = torch.randn(G, e, generator=g).to(DEV)
     dl = torch.randn(G, C, generator=g).to(DEV)
     fr = eng.text_fwd_ranged(prefix, suffix, ctx, layout, eot, [0] * G, [C] * G, save_for_bwd=True)
     dr = eng.text_bwd(dfeat)
     lr = eng.logits_ranged_fwd(img, fr, 50.0, [0] * G, [C] * G, C)
     _, tr = eng.logits_ranged_bwd(dl)
-    fg = eng.text_fwd_grouped(prefix, suffix, ctx, layout, eot, save_for_bwd=True)
-    dg = eng.text_bwd(dfeat)
-    lg = eng.logits_grouped_fwd(img, fg, 50.0)
-    tg = eng.logits_grouped_bwd(dl)
+    assert fr.shape == (G * C, e) and dr.shape == (G, n, dt) and lr.shape == (G, C) and tr.shape == (G * C, e)
+    fc = eng.text_fwd(prefix.repeat(G, 1, 1), suffix.repeat(G, 1, 1), ctx.repeat_interleave(C, 0), layout.repeat(G, 1),
+                      eot.repeat(G), save_for_bwd=True)
+    dc = eng.text_bwd(dfeat)
     torch.cuda.synchronize()
-    assert torch.equal(fr, fg) and torch.equal(dr, dg)
-    assert torch.equal(lr, lg) and torch.equal(tr, tg)
+    assert torch.equal(fr, fc), "full-range features must be bit-identical to the materialised CSC tower"
+    want = dc.view(G, C, n, dt).double().sum(1)
+    assert float((dr.double() - want).abs().max()) <= 1e-6 * float(want.abs().max())
+    img64, txt64 = img.double().cpu(), fr.double().cpu().requires_grad_(True)
+    imn = img64 / img64.norm(dim=-1, keepdim=True)
+    txn = (txt64 / txt64.norm(dim=-1, keepdim=True)).view(G, C, e)
+    want = 50.0 * torch.einsum("ge,gce->gc", imn, txn)
+    want.backward(dl.double().cpu())
+    assert _rel(lr, want.detach()) <= 1e-5
+    assert _rel(tr, txt64.grad) <= 1e-5
 
 
 def test_ranged_calls_refuse_bad_ranges(tiny_clip):

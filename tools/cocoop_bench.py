@@ -4,7 +4,7 @@ B = 8, and evaluation images/s at test batch 100.  Prints one JSON line.
     python tools/cocoop_bench.py [--steps 10] [--warmup 3] [--eval-iters 3]
 
 Frozen weights are the synthetic ViT-B/16 of mvlpt_amd.weights (the speed does not depend on their values).  A step is what
-CoCoOp.forward_backward does: image tower, meta_net, grouped text tower forward + backward chunk by chunk, optimizer step.
+CoCoOp.forward_backward does: image tower, meta_net, full-range text tower forward + backward chunk by chunk, optimizer step.
 """
 from __future__ import annotations
 

@@ -5,7 +5,7 @@ COCOOP.N_CTX 16, per-task mask.  Prints one JSON line.
 
 Tasks are drawn with a fixed seed (a) in proportion to their class counts (k-shot sampling) and (b) evenly.  Per draw: training ms per
 step (forward, cross-entropy, backward, optimizer step) and evaluation images/s, each for the ranged text tower and for the dense
-grouped tower, with sequences per step, chunks and text workspace bytes.  Dense at the config's batch 32 is 36 832 sequences per step
+tower (every range full), with sequences per step, chunks and text workspace bytes.  Dense at the config's batch 32 is 36 832 sequences per step
 (dozens of chunks under the default budget), so dense is timed at `--dense-batch` / `--dense-eval-batch` images and the line says so;
 `*_ms_per_kseq` (ms per 1000 text sequences) is the figure to compare: the step's text time should follow the sequence count.
 Ranged and dense alternate in one process; every figure is event-timed after warm-up.

@@ -510,6 +510,60 @@ int mvlpt_op_nearest_rows(const float* q, const float* table, int R, int V, int 
                           int64_t workspace_bytes, mvlpt_stream_t stream);
 int mvlpt_nearest_tokens(void* handle, const float* q, int R, int k, int32_t* idx, float* dist, mvlpt_stream_t stream);
 
+/* ---- evaluation on the device: class counters and column rank statistics (row f1b of the scope table; tests/test_hip_eval.py) ----
+ * Everything MVLPT.test reports is a function of integer counts; these two entries produce the counts exactly, and the few remaining
+ * double-precision divisions and means are finished on the host (mvlpt_amd/evaluator.py) with the calls mvlpt_amd/metrics.py makes.
+ * Both are handle-free (errors: mvlpt_last_error(NULL)) and enqueue-only on `stream`; a NULL required pointer, an extent outside its
+ * limits, a pitch below the width or a workspace that is too small return MVLPT_ERR_ARG (N > MVLPT_EVAL_MAX_ROWS:
+ * MVLPT_ERR_UNSUPPORTED) before anything is launched.  Device index arrays are the caller's responsibility: a row index, task id or
+ * int64 label outside its extent is clamped or skipped (nothing is read or written out of bounds; the counts are then meaningless).
+ *
+ * mvlpt_op_eval_count: streaming class counters, one launch per evaluation batch and no host sync.  Replaces the per-batch
+ *   `output.max(1)[1]`, the Python loop over `set(tasks_)` with its boolean masks and ranged arg-max (trainers/mvlpt.py:1023-1045) and
+ *   the arg-max of balanced_accuracy_score (trainers/vision_benchmark/datasets/metrics.py:1271-1274 behind filter_out_zero_tgt).
+ *   logits fp32 [B, C] with row pitch ld >= C.  labels: int64 [B] (MVLPT_LABEL_INT64) or fp32 [B, C] with pitch label_ld
+ *   (MVLPT_LABEL_PROB_F32: the row's arg-max is its label, as `label.argmax(dim=1)`).  rows: optional int32 [n_rows] list of the rows
+ *   that are counted (NULL: all B rows).  task int32 [B] with lo / hi int32 [T] (device; all three or none): the row's own class range.
+ *   col_mask: optional uint8 [C]; every arg-max, the label's included, then runs over the columns with a non-zero byte only.
+ *   col_seen: optional uint8 [C] output, set to 1 for every column that holds a non-zero target (the int64 label's column) in a counted
+ *   row and otherwise left alone: the column-occurrence pass whose result is the col_mask of mean-per-class (filter_out_zero_tgt).
+ *   Added into caller-owned int64 device buffers: n_true[C], n_pred[C], n_hit[C] for the arg-max over all columns; with ranges
+ *   n_pred_r[C], n_hit_r[C] for the arg-max over [lo_t, hi_t); cmat (optional) [C, C] indexed (true, pred).  Arg-max as numpy: the
+ *   lowest index among equal maxima, a NaN counts as maximal.  The adds are 64-bit integer atomics: the result does not depend on the
+ *   order of the rows or on a rerun.  No floating-point atomics.
+ *
+ * mvlpt_op_eval_rank_columns: per column c of scores fp32 [N, C] (pitch ld >= C: a column slice is read in place), over the rows of
+ *   the optional int32 list `rows` [n_rows] (NULL: all N rows; a non-NULL list may be empty, n_rows <= N), with a target that is
+ *   positive where int64 labels[row] == c (MVLPT_LABEL_INT64) or where the fp32 matrix [N, target_ld] holds exactly 1
+ *   (MVLPT_LABEL_PROB_F32), the sorted-order statistics that roc_auc_score and the 11-point walk of map_11_points read
+ *   (metrics.py:1265-1268, 1277-1280, 853-895).  Scores order by value, -0.0 and +0.0 are one value:
+ *     n_pos[c], n_neg[c]   int64
+ *     twice_u[c]           int64: sum over the runs [a, b) of equal scores in ascending order of (positives in the run) * (a + 1 + b),
+ *                          minus n_pos * (n_pos + 1): twice the tie-averaged Mann-Whitney U
+ *     interp[c * 11 + i]   double: the largest precision tp / cnt among the points (one per run start a: tp = positives at or behind a,
+ *                          cnt = n - a, recall = tp / n_pos, or 1 when n_pos == 0; plus the closing point precision 1, recall 0) with
+ *                          thresholds[i] <= recall, 0 when there is none.  thresholds: 11 HOST doubles.  IEEE double divisions.
+ *     flags[c]             int32: MVLPT_EVAL_FLAG_NONFINITE when a selected score of the column is NaN or +-inf (numpy's np.diff splits
+ *                          runs of equal infinities; the caller then finishes that metric on the host);
+ *                          MVLPT_EVAL_FLAG_SOFT_TARGET when a selected fp32 target of the column is neither 0 nor 1 (metrics.py keeps a
+ *                          column for any non-zero target but counts only 1 as positive: the host decides such inputs too).
+ *   One workgroup sorts one column: in LDS up to MVLPT_EVAL_SORT_TILE rows, beyond that with `workspace` for the long strides.
+ * mvlpt_eval_workspace_bytes: *out = bytes mvlpt_op_eval_rank_columns needs for at most N selected rows and C columns on `stream`
+ *   (0 when the columns fit in LDS: the workspace may then be NULL). */
+enum { MVLPT_EVAL_SORT_TILE = 4096 };
+enum { MVLPT_EVAL_MAX_ROWS = 1 << 20 };
+enum { MVLPT_EVAL_POINTS = 11 };
+enum { MVLPT_EVAL_FLAG_NONFINITE = 1, MVLPT_EVAL_FLAG_SOFT_TARGET = 2 };
+int mvlpt_op_eval_count(const float* logits, int64_t ld, int B, int C, const void* labels, int label_kind, int64_t label_ld,
+                        const int32_t* rows, int n_rows, const int32_t* task, const int32_t* lo, const int32_t* hi, int T,
+                        const uint8_t* col_mask, uint8_t* col_seen, int64_t* n_true, int64_t* n_pred, int64_t* n_hit, int64_t* n_pred_r,
+                        int64_t* n_hit_r, int64_t* cmat, mvlpt_stream_t stream);
+int mvlpt_op_eval_rank_columns(const float* scores, int64_t ld, int N, int C, const void* targets, int target_kind, int64_t target_ld,
+                               const int32_t* rows, int n_rows, const double* thresholds, int64_t* n_pos, int64_t* n_neg,
+                               int64_t* twice_u, double* interp, int32_t* flags, void* workspace, int64_t workspace_bytes,
+                               mvlpt_stream_t stream);
+int mvlpt_eval_workspace_bytes(int N, int C, mvlpt_stream_t stream, int64_t* out);
+
 /* ---- linear-probe CLIP baseline: L2-regularised multinomial logistic regression (row j of the scope table; tests/test_hip_softmax_reg.py) ----
  * Replaces sklearn's LogisticRegression(solver="lbfgs", penalty="l2", C=C) of lpclip/linear_probe.py with full-batch evaluations on
  * the device.  The objective is the one sklearn 1.7 minimises,

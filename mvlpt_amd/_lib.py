@@ -24,7 +24,8 @@ GEMM_BT_128x128_R2, GEMM_BT_128x128_R4, GEMM_BT_256x128_R3, GEMM_BT_256x256_R2, 
 PREC_FAST, PREC_SPLIT_GRAD, PREC_SPLIT_ALL = 0, 1, 2
 ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4      # MVLPT_ERR_*
 NEAREST_MAX_K, NEAREST_MAX_ROWS = 64, 65535 * 8      # MVLPT_NEAREST_MAX_K, MVLPT_NEAREST_MAX_ROWS
-TEXT_MIN_L = 3      # MVLPT_TEXT_MIN_L: the smallest sequence length mvlpt_text_encode_tokens accepts
+EVAL_SORT_TILE, EVAL_MAX_ROWS, EVAL_POINTS, EVAL_FLAG_NONFINITE, EVAL_FLAG_SOFT_TARGET = 4096, 1 << 20, 11, 1, 2      # MVLPT_EVAL_*
+TEXT_MIN_L = 3     # MVLPT_TEXT_MIN_L: the smallest sequence length mvlpt_text_encode_tokens accepts
 
 
 class MvlptArch(C.Structure):
@@ -152,6 +153,11 @@ SIGNATURES = {
     "mvlpt_nearest_workspace_bytes": (_i, [_i, _i, _i, _i, _vp, C.POINTER(C.c_int64)]),
     "mvlpt_op_nearest_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_int64, _vp]),
     "mvlpt_nearest_tokens": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "mvlpt_op_eval_count": (_i, [_vp, C.c_int64, _i, _i, _vp, _i, C.c_int64, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp]),
+    "mvlpt_op_eval_rank_columns": (_i, [_vp, C.c_int64, _i, _i, _vp, _i, C.c_int64, _vp, _i, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp,
+                                        _vp, C.c_int64, _vp]),
+    "mvlpt_eval_workspace_bytes": (_i, [_i, _i, _vp, C.POINTER(C.c_int64)]),
     "mvlpt_softmax_reg_workspace_bytes": (_i, [_i, _i, _i, C.POINTER(C.c_size_t)]),
     "mvlpt_op_softmax_reg_eval": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mvlpt_op_softmax_reg_predict": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),

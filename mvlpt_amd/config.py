@@ -59,7 +59,10 @@ def get_cfg_default() -> CfgNode:
                    # not in the reference: the one-launch HIP optimizer step over flat prompt buffers (mvlpt_amd.optim), opt-in
                    FUSED=False)
     cfg.TRAIN = CN(PRINT_FREQ=5, CHECKPOINT_FREQ=0)
-    cfg.TEST = CN(FINAL_MODEL="last_step", SPLIT="test", NO_TEST=False)   # Dassl's defaults; a run without evaluation data sets NO_TEST True
+    # Dassl's names and defaults (a run without evaluation data sets NO_TEST True).  PER_CLASS_RESULT / COMPUTE_CMAT: the per-class table
+    # and the confusion matrix (OUTPUT_DIR/cmat.pt) of Dassl's Classification evaluator (mvlpt_amd.evaluator).  DEVICE_METRICS (not in the
+    # reference): MVLPT.test finishes its figures from device counters whenever the logits are on a GPU; False keeps the host route.
+    cfg.TEST = CN(FINAL_MODEL="last_step", SPLIT="test", NO_TEST=False, PER_CLASS_RESULT=False, COMPUTE_CMAT=False, DEVICE_METRICS=True)
     # ACT_CKPT (train.py:164, trainers/mvlpt.py:119-121): segments of the text tower's activation checkpointing; the three CustomCLIP
     # classes set it on their engine (Engine.set_text_act_ckpt).  1: every block's activations are saved.  It applies with or without
     # CUT_CONTEXTLEN (the reference: only with it) and changes memory and time, never a value.

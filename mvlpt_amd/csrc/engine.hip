@@ -2351,6 +2351,71 @@ int mvlpt_nearest_tokens(void* h, const float* q, int R, int k, int32_t* idx, fl
                      &E->err);
 }
 
+// ------------------------------------------------------------------------------------------------ evaluation counts
+// Every limit of include/mvlpt_hip.h is checked here, before a launch (evaluate.hip).
+int mvlpt_op_eval_count(const float* logits, int64_t ld, int B, int C, const void* labels, int label_kind, int64_t label_ld,
+                        const int32_t* rows, int n_rows, const int32_t* task, const int32_t* lo, const int32_t* hi, int T,
+                        const uint8_t* col_mask, uint8_t* col_seen, int64_t* n_true, int64_t* n_pred, int64_t* n_hit, int64_t* n_pred_r,
+                        int64_t* n_hit_r, int64_t* cmat, mvlpt_stream_t stream) {
+  auto bad = [&](const char* what) { g_create_err = std::string("op_eval_count: ") + what; return MVLPT_ERR_ARG; };
+  if (!logits || !labels || !n_true || !n_pred || !n_hit) return bad("null argument");
+  if (B < 1 || C < 1 || ld < C) return bad("B and C must be at least 1 and the row pitch at least C");
+  if (label_kind != MVLPT_LABEL_INT64 && label_kind != MVLPT_LABEL_PROB_F32) return bad("unknown label kind");
+  if (label_kind == MVLPT_LABEL_PROB_F32 && label_ld < C) return bad("the label pitch must be at least C");
+  if (rows && n_rows < 0) return bad("n_rows must not be negative");
+  const bool ranged = task || lo || hi;
+  if (ranged && (!task || !lo || !hi || T < 1 || !n_pred_r || !n_hit_r))
+    return bad("task ranges need task, lo, hi, T >= 1, n_pred_r and n_hit_r together");
+  if (cmat && (int64_t)C * C > ((int64_t)1 << 31)) return bad("the confusion matrix needs C * C <= 2^31");
+  EvalCountArgs a;
+  a.logits = logits; a.ld = ld; a.B = B; a.C = C;
+  a.label_i = label_kind == MVLPT_LABEL_INT64 ? (const long long*)labels : nullptr;
+  a.label_f = label_kind == MVLPT_LABEL_PROB_F32 ? (const float*)labels : nullptr;
+  a.label_ld = label_ld;
+  a.rows = rows; a.n = rows ? n_rows : B;
+  a.task = ranged ? task : nullptr; a.lo = lo; a.hi = hi; a.T = T;
+  a.col_mask = col_mask; a.col_seen = col_seen;
+  a.n_true = n_true; a.n_pred = n_pred; a.n_hit = n_hit; a.n_pred_r = n_pred_r; a.n_hit_r = n_hit_r; a.cmat = cmat;
+  OPCHK(launch_eval_count(a, (hipStream_t)stream));
+  return 0;
+}
+static int eval_rank_check(const char* who, int N, int C) {
+  auto bad = [&](int code, const char* what) { g_create_err = std::string(who) + ": " + what; return code; };
+  if (N < 1 || C < 1) return bad(MVLPT_ERR_ARG, "N and C must be at least 1");
+  if (N > MVLPT_EVAL_MAX_ROWS) return bad(MVLPT_ERR_UNSUPPORTED, "N exceeds MVLPT_EVAL_MAX_ROWS");
+  return 0;
+}
+int mvlpt_eval_workspace_bytes(int N, int C, mvlpt_stream_t stream, int64_t* out) {
+  if (!out) { g_create_err = "eval_workspace_bytes: null argument"; return MVLPT_ERR_ARG; }
+  if (int rc = eval_rank_check("eval_workspace_bytes", N, C)) return rc;
+  *out = (int64_t)eval_rank_plan(N, C, stream_cus((hipStream_t)stream)).ws_bytes;
+  return 0;
+}
+int mvlpt_op_eval_rank_columns(const float* scores, int64_t ld, int N, int C, const void* targets, int target_kind, int64_t target_ld,
+                               const int32_t* rows, int n_rows, const double* thresholds, int64_t* n_pos, int64_t* n_neg,
+                               int64_t* twice_u, double* interp, int32_t* flags, void* workspace, int64_t workspace_bytes,
+                               mvlpt_stream_t stream) {
+  auto bad = [&](const char* what) { g_create_err = std::string("op_eval_rank_columns: ") + what; return MVLPT_ERR_ARG; };
+  if (!scores || !targets || !thresholds || !n_pos || !n_neg || !twice_u || !interp || !flags) return bad("null argument");
+  if (int rc = eval_rank_check("op_eval_rank_columns", N, C)) return rc;
+  if (ld < C) return bad("the row pitch must be at least C");
+  if (target_kind != MVLPT_LABEL_INT64 && target_kind != MVLPT_LABEL_PROB_F32) return bad("unknown target kind");
+  if (target_kind == MVLPT_LABEL_PROB_F32 && target_ld < C) return bad("the target pitch must be at least C");
+  if (rows && (n_rows < 0 || n_rows > N)) return bad("n_rows must lie in [0, N]");
+  const int n = rows ? n_rows : N;
+  const EvalRankPlan p = eval_rank_plan(n, C, stream_cus((hipStream_t)stream));
+  if (p.ws_bytes && (!workspace || workspace_bytes < 0 || (uint64_t)workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 7) != 0)) {
+    g_create_err = "op_eval_rank_columns: the workspace is smaller than mvlpt_eval_workspace_bytes (" + std::to_string(p.ws_bytes) +
+                   " bytes), or not 8-byte aligned";
+    return MVLPT_ERR_ARG;
+  }
+  OPCHK(launch_eval_rank_columns(scores, ld, N, C, target_kind == MVLPT_LABEL_INT64 ? (const long long*)targets : nullptr,
+                                 target_kind == MVLPT_LABEL_PROB_F32 ? (const float*)targets : nullptr, target_ld, rows, n, thresholds,
+                                 (long long*)n_pos, (long long*)n_neg, (long long*)twice_u, interp, flags, workspace, p,
+                                 (hipStream_t)stream));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ softmax regression (linear probe)
 // Every limit of include/mvlpt_hip.h is checked here, before a launch: the kernels (softmax_reg.hip) trust their arguments.
 static int softmax_reg_check(const char* who, int N, int D, int K) {

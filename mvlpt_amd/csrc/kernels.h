@@ -365,4 +365,26 @@ hipError_t launch_softmax_reg_eval(const float* X, const int32_t* y, const float
 hipError_t launch_softmax_reg_predict(const float* X, const float* theta, int N, int D, int K, int32_t* pred, float* margin, void* ws,
                                       const SoftmaxRegPlan& p, hipStream_t s);
 
+// ---------------------------------------------------------------- evaluation counts (evaluate.hip; semantics in include/mvlpt_hip.h)
+// The arguments are checked by the caller (engine.hip); row indices, task ids, ranges and labels that lie outside their extents are
+// clamped or skipped by the kernels, never dereferenced.
+struct EvalCountArgs {
+  const float* logits; long long ld; int B, C;     // B: rows of logits / labels / task; C: columns
+  const long long* label_i; const float* label_f; long long label_ld;    // exactly one of the two label forms
+  const int* rows; int n;                          // rows counted: the list (NULL: 0 .. n-1, n == B)
+  const int *task, *lo, *hi; int T;                // optional task ranges
+  const uint8_t* col_mask;                         // optional: the columns every arg-max runs over
+  uint8_t* col_seen;                               // optional: set to 1 for every column with a non-zero target in a counted row
+  int64_t *n_true, *n_pred, *n_hit, *n_pred_r, *n_hit_r, *cmat;
+};
+hipError_t launch_eval_count(const EvalCountArgs& a, hipStream_t s);
+// Geometry of one rank call for n selected rows: P = n padded to a power of two; columns of at most MVLPT_EVAL_SORT_TILE items stay in
+// LDS (no scratch), longer ones get P items of scratch per workgroup.  ws_bytes never decreases with n at a given (C, cus).
+struct EvalRankPlan { int P = 0, grid = 0; bool resident = true; size_t ws_bytes = 0; };
+EvalRankPlan eval_rank_plan(int n, int C, int cus);
+hipError_t launch_eval_rank_columns(const float* scores, long long ld, int N, int C, const long long* label, const float* target,
+                                    long long target_ld, const int* rows, int n, const double* thresholds, long long* n_pos,
+                                    long long* n_neg, long long* twice_u, double* interp, int* flags, void* ws, const EvalRankPlan& p,
+                                    hipStream_t s);
+
 }  // namespace mvlpt

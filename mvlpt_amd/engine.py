@@ -704,6 +704,117 @@ def op_nearest_rows(q, table, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     return idx, dist
 
 
+def _pitched(t: torch.Tensor, name: str) -> torch.Tensor:
+    """fp32 [R, C] on the device with unit column stride and a row stride >= C: a column slice of a wider matrix passes in place (its
+    row stride is the pitch the kernels take); anything else is copied once."""
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA/HIP tensor: mvlpt_amd has no CPU path")
+    if t.dim() != 2:
+        raise ValueError(f"{name} must be a matrix")
+    if t.dtype != torch.float32 or t.stride(1) != 1 or t.stride(0) < t.shape[1]:
+        t = t.float().contiguous()
+    return t
+
+
+def _eval_labels(labels: torch.Tensor, R: int, C_: int, name: str):
+    """(tensor, MVLPT_LABEL_*, pitch) of int64 [R] labels or an fp32 [R, C] target matrix."""
+    if labels.dim() == 1:
+        labels = _req(labels, torch.int64, name)
+        if labels.shape[0] != R:
+            raise ValueError(f"{name} has {labels.shape[0]} rows, the scores {R}")
+        return labels, _lib.LABEL_INT64, 0
+    labels = _pitched(labels, name)
+    if tuple(labels.shape) != (R, C_):
+        raise ValueError(f"{name} has shape {tuple(labels.shape)}, the scores {(R, C_)}")
+    return labels, _lib.LABEL_PROB_F32, labels.stride(0)
+
+
+def _eval_rows(rows: Optional[torch.Tensor]):
+    """(pointer, n_rows, the tensor that keeps the pointer alive) of an optional int32 row list; an empty list still passes a non-NULL
+    pointer (NULL means every row)."""
+    if rows is None:
+        return None, 0, None
+    rows = _req(rows, torch.int32, "rows")
+    keep = rows if rows.numel() else torch.zeros(1, device=rows.device, dtype=torch.int32)
+    return _ptr(keep), int(rows.numel()), keep
+
+
+def op_eval_count(logits, labels, n_true, n_pred, n_hit, task=None, lo=None, hi=None, n_pred_r=None, n_hit_r=None, cmat=None, rows=None,
+                  col_mask=None, col_seen=None) -> None:
+    """One launch of the streaming class counters (mvlpt_op_eval_count), no host sync: the arg-max of every row of logits [B, C] (over
+    all columns, and over the row's task range when task int32 [B] / lo / hi int32 [T] are given) is counted against its label (int64
+    [B], or the arg-max of a float [B, C] row) into the caller's int64 device counters, which accumulate over calls."""
+    logits = _pitched(logits, "logits")
+    B, C_ = logits.shape
+    labels, kind, lab_ld = _eval_labels(labels, B, C_, "labels")
+    for name, t, numel in (("n_true", n_true, C_), ("n_pred", n_pred, C_), ("n_hit", n_hit, C_), ("n_pred_r", n_pred_r, C_),
+                           ("n_hit_r", n_hit_r, C_), ("cmat", cmat, C_ * C_)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == numel):
+            raise ValueError(f"{name} must be a contiguous int64 device tensor of {numel} elements")
+    T = 0
+    if task is not None:
+        task, lo, hi = _req(task, torch.int32, "task"), _req(lo, torch.int32, "lo"), _req(hi, torch.int32, "hi")
+        T = lo.numel()
+        if task.numel() != B or hi.numel() != T:
+            raise ValueError("task must have one entry per row, lo and hi one per task")
+    if col_mask is not None:
+        col_mask = _req(col_mask, torch.uint8, "col_mask")
+        if col_mask.numel() != C_:
+            raise ValueError("col_mask must have one entry per column")
+    if col_seen is not None and not (col_seen.is_cuda and col_seen.dtype == torch.uint8 and col_seen.is_contiguous() and col_seen.numel() == C_):
+        raise ValueError("col_seen must be a contiguous uint8 device tensor with one entry per column")
+    rows_p, n_rows, _keep = _eval_rows(rows)
+    if rows is not None and n_rows == 0:
+        return
+    with torch.cuda.device(logits.device):
+        _lib.check(lib.mvlpt_op_eval_count(_ptr(logits), logits.stride(0), B, C_, _ptr(labels), kind, lab_ld, rows_p, n_rows, _ptr(task),
+                                           _ptr(lo), _ptr(hi), T, _ptr(col_mask), _ptr(col_seen), _ptr(n_true), _ptr(n_pred), _ptr(n_hit), _ptr(n_pred_r),
+                                           _ptr(n_hit_r), _ptr(cmat), _stream()), None, "op_eval_count")
+
+
+def eval_workspace_bytes(N: int, C_: int) -> int:
+    """Scratch bytes op_eval_rank_columns needs for at most N selected rows and C columns on the current stream."""
+    out = C.c_int64()
+    _lib.check(lib.mvlpt_eval_workspace_bytes(int(N), int(C_), _stream(), C.byref(out)), None, "eval_workspace_bytes")
+    return int(out.value)
+
+
+def op_eval_rank_columns(scores, targets, rows=None, thresholds=None) -> Dict[str, torch.Tensor]:
+    """Sorted-order statistics of every column of scores [N, C] over the rows of the optional int32 list `rows` (None: all; may be
+    empty) against int64 [N] labels or a float [N, C] target matrix (mvlpt_op_eval_rank_columns): device tensors n_pos / n_neg /
+    twice_u int64 [C], interp float64 [C, 11], flags int32 [C], all views of the one int64 buffer "packed" (one copy reads them back:
+    `unpack_eval_rank`).  A column slice is read in place."""
+    scores = _pitched(scores, "scores")
+    N, C_ = scores.shape
+    targets, kind, tgt_ld = _eval_labels(targets, N, C_, "targets")
+    if thresholds is None:
+        import numpy as np
+        thresholds = np.linspace(1, 0, _lib.EVAL_POINTS, endpoint=True).tolist()
+    if len(thresholds) != _lib.EVAL_POINTS:
+        raise ValueError(f"{_lib.EVAL_POINTS} thresholds are needed")
+    th = (C.c_double * _lib.EVAL_POINTS)(*thresholds)
+    rows_p, n_rows, _keep = _eval_rows(rows)
+    P = _lib.EVAL_POINTS
+    with torch.cuda.device(scores.device):
+        packed = torch.zeros(C_ * (3 + P) + (C_ + 1) // 2, device=scores.device, dtype=torch.int64)      # (the odd flag word is padding)
+        out = unpack_eval_rank(packed, C_)
+        nb = eval_workspace_bytes(N if rows is None else max(n_rows, 1), C_)
+        ws = torch.empty(nb // 8, device=scores.device, dtype=torch.int64) if nb else None
+        _lib.check(lib.mvlpt_op_eval_rank_columns(_ptr(scores), scores.stride(0), N, C_, _ptr(targets), kind, tgt_ld, rows_p, n_rows, th,
+                                                  _ptr(out["n_pos"]), _ptr(out["n_neg"]), _ptr(out["twice_u"]), _ptr(out["interp"]),
+                                                  _ptr(out["flags"]), _ptr(ws), nb, _stream()), None, "op_eval_rank_columns")
+    out["packed"] = packed
+    return out
+
+
+def unpack_eval_rank(packed, C_: int):
+    """The five arrays of op_eval_rank_columns as views of its packed int64 buffer (a torch tensor on any device)."""
+    P = _lib.EVAL_POINTS
+    return {"n_pos": packed[:C_], "n_neg": packed[C_:2 * C_], "twice_u": packed[2 * C_:3 * C_],
+            "interp": packed[3 * C_:(3 + P) * C_].view(torch.float64).view(C_, P),
+            "flags": packed[(3 + P) * C_:].view(torch.int32)[:C_]}
+
+
 def softmax_reg_workspace_bytes(N: int, D: int, K: int) -> int:
     """Scratch bytes op_softmax_reg_eval / op_softmax_reg_predict need for these sizes (mvlpt_softmax_reg_workspace_bytes)."""
     out = C.c_size_t()

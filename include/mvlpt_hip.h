@@ -372,6 +372,34 @@ int mvlpt_op_attention_fwd(int dtype, const void* qkv, void* out, float* lse, in
 int mvlpt_op_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int N, int L, int H, int causal, mvlpt_stream_t stream);
 int mvlpt_op_cast(int dtype, const float* in, void* out, int64_t n, mvlpt_stream_t stream);
+/* ---- LayerNorm, the operand-format kernels and the patch extraction with every argument the towers set (tests/test_hip_norm_matrix.py,
+ * tests/test_hip_formats.py).  Every entry checks its arguments before anything is launched: a NULL pointer, an unknown dtype / format /
+ * split returns MVLPT_ERR_ARG, a shape the kernels do not have (d % 4, d > 2048, Kp % 8, R % P) MVLPT_ERR_UNSUPPORTED, and the output is
+ * untouched; rows = 0 succeeds and writes nothing.
+ * layernorm_fwd_ex: y row r = LN(x row r * row_mul) (biased variance, eps 1e-5, fp32 statistics); out_dtype fp32 / fp16 / bf16; split
+ *   (16-bit only) 0: y [rows, d], 1: hi|lo pair [rows, 2d], 2: mixed pair at the same pitch.
+ * layernorm_bwd_ex: dy [rows, d] dense, of dy_dtype (fp32: what the towers pass; or `dtype`); row r of x, resid, out32 and out16 is row
+ *   r * row_mul of its buffer (the rows in between are not touched): out32 = (resid ? resid : 0) + dLN/dx, out16 = out32 in the format
+ *   `split`.  resid and out16 may be NULL, out32 may alias resid.
+ * layernorm_route: which kernel both of them run for rows x d on `stream`, without launching: returns 0 (one wave per row) or 1 (the
+ *   grid-stride kernel), *nv = float4 per lane of the instantiation (2, 3, 4 or 8; 8 for the direct kernel), *grid = workgroups.
+ * cast_ex: out = format(in * scale_dev[0]) (scale_dev: a DEVICE float or NULL for 1); format 0: [rows, d], 1: hi|lo pair [rows, 2d] with
+ *   hi = round16(v), lo = round16(v - hi), 2: mixed pair (above).  cast_to_f32: exact widening of n elements (fp32 input: a copy).
+ * pack_weight: w32 [rows, cols] -> out [rows, ld_out] = round(w32) with a zero tail (ld_out >= cols), or, transposed, out [cols, ld_out]
+ *   with out[c][r] = round(w32[r][c]) (ld_out >= rows; the tail is NOT written); ld_out = 0: dense; dtype fp32 / fp16 / bf16.
+ * patchify: image [B, 3, R, R] of image_dtype -> out [B (R/P)^2, Kp] of dtype, out[b G^2 + gy G + gx][c P^2 + ky P + kx] =
+ *   round16(image[b][c][gy P + ky][gx P + kx]), zero from column 3 P^2 on (Kp >= 3 P^2).  patchify_route: the kernel that call uses:
+ *   0 scalar, 1 vector (fp32 image, P % 8 == 0), 2 the 16-byte copy (image of the compute type, P % 8 == 0, 6 P R bytes <= 64 KB). */
+int mvlpt_op_layernorm_fwd_ex(int out_dtype, const float* x, int row_mul, const float* gamma, const float* beta, void* y, int rows, int d,
+                              int split, mvlpt_stream_t stream);
+int mvlpt_op_layernorm_bwd_ex(int dtype, const void* dy, int dy_dtype, const float* x, int row_mul, const float* gamma, const float* resid,
+                              float* out32, void* out16, int rows, int d, int split, mvlpt_stream_t stream);
+int mvlpt_op_layernorm_route(int rows, int d, mvlpt_stream_t stream, int* nv, int* grid);
+int mvlpt_op_cast_ex(int dtype, const float* in, void* out, int64_t rows, int d, int format, const float* scale_dev, mvlpt_stream_t stream);
+int mvlpt_op_cast_to_f32(int in_dtype, const void* in, float* out, int64_t n, mvlpt_stream_t stream);
+int mvlpt_op_pack_weight(int dtype, const float* w32, int rows, int cols, int transposed, int ld_out, void* out, mvlpt_stream_t stream);
+int mvlpt_op_patchify(int dtype, const void* image, int image_dtype, void* out, int B, int R, int P, int Kp, mvlpt_stream_t stream);
+int mvlpt_op_patchify_route(int dtype, int image_dtype, int R, int P);
 /* the glue of mvlpt_text_fwd_ranged / text_bwd: x [S, L, d] fp32 = assembled prompts + pos [L, d] (layout entries must address
  * rows inside prefix / suffix / ctx) and dx [S, L, d] over the sequences of HOST class_lo / class_hi int32 [G] (see mvlpt_text_fwd_ranged;
  * lo = 0, hi = C for every g is CoCoOp's tower, S = G * C), dctx [G, n_ctx, d] = sum over group g's sequences of dx at ctx_pos

@@ -129,6 +129,14 @@ SIGNATURES = {
     "mvlpt_op_attention_fwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_attention_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_cast": (_i, [_i, _vp, _vp, C.c_int64, _vp]),
+    "mvlpt_op_layernorm_fwd_ex": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mvlpt_op_layernorm_bwd_ex": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "mvlpt_op_layernorm_route": (_i, [_i, _i, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "mvlpt_op_cast_ex": (_i, [_i, _vp, _vp, C.c_int64, _i, _i, _vp, _vp]),
+    "mvlpt_op_cast_to_f32": (_i, [_i, _vp, _vp, C.c_int64, _vp]),
+    "mvlpt_op_pack_weight": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "mvlpt_op_patchify": (_i, [_i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_patchify_route": (_i, [_i, _i, _i, _i]),
     "mvlpt_op_pack_conv_weight": (_i, [_vp, _i, _i, _i, _i, _vp, C.POINTER(C.c_int), _vp]),
     "mvlpt_op_conv2d": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mvlpt_op_avgpool2x2": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

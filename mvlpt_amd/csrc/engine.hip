@@ -2165,6 +2165,85 @@ int mvlpt_op_cast(int dtype, const float* in, void* out, int64_t n, mvlpt_stream
   OPCHK(launch_cast_f32_to16(dtype, in, out, (size_t)n, nullptr, (hipStream_t)stream));
   return 0;
 }
+// ---- LayerNorm, the operand-format kernels and the patch extraction with every argument the towers set; everything is checked here,
+// before a launch, so that a refused call leaves its output untouched
+static bool is16(int dt) { return dt == DT_F16 || dt == DT_BF16; }
+static int ln_shape_check(const char* who, int rows, int d, int row_mul, int split) {
+  if (rows < 0 || d <= 0 || row_mul < 1 || split < 0 || split > 2) return fail(nullptr, MVLPT_ERR_ARG, std::string(who) + ": rows >= 0, d > 0, row_mul >= 1, split in {0, 1, 2}");
+  if (d % 4 || d > 2048) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, std::string(who) + ": d must be a multiple of 4 and at most 2048");
+  return 0;
+}
+int mvlpt_op_layernorm_fwd_ex(int out_dtype, const float* x, int row_mul, const float* gamma, const float* beta, void* y, int rows, int d,
+                              int split, mvlpt_stream_t stream) {
+  if (!x || !gamma || !beta || !y) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_fwd_ex: null pointer");
+  if (out_dtype != DT_F32 && !is16(out_dtype)) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_fwd_ex: unknown output dtype");
+  if (out_dtype == DT_F32 && split) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_fwd_ex: a pair output is 16-bit");
+  if (int rc = ln_shape_check("op_layernorm_fwd_ex", rows, d, row_mul, split)) return rc;
+  LnFwdArgs a{x, nullptr, row_mul, gamma, beta, y, rows, d};
+  a.split = split;
+  OPCHK(launch_ln_fwd(out_dtype, a, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_layernorm_bwd_ex(int dtype, const void* dy, int dy_dtype, const float* x, int row_mul, const float* gamma, const float* resid,
+                              float* out32, void* out16, int rows, int d, int split, mvlpt_stream_t stream) {
+  if (!dy || !x || !gamma || !out32) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_bwd_ex: null pointer");
+  if (!is16(dtype) || (dy_dtype != DT_F32 && dy_dtype != dtype)) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_bwd_ex: dtype is fp16 or bf16, dy_dtype fp32 or dtype");
+  if (int rc = ln_shape_check("op_layernorm_bwd_ex", rows, d, row_mul, split)) return rc;
+  LnBwdArgs a{dy, dy_dtype, x, nullptr, row_mul, gamma, resid, out32, out16, rows, d};
+  a.split = split;
+  OPCHK(launch_ln_bwd(dtype, a, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_layernorm_route(int rows, int d, mvlpt_stream_t stream, int* nv, int* grid) {
+  if (rows <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_route: rows > 0 (an empty call launches nothing)");
+  if (int rc = ln_shape_check("op_layernorm_route", rows, d, 1, 0)) return rc;
+  const LnRoute r = ln_route(rows, d, (hipStream_t)stream);
+  if (nv) *nv = r.nv;
+  if (grid) *grid = r.grid;
+  return r.stream;
+}
+int mvlpt_op_cast_ex(int dtype, const float* in, void* out, int64_t rows, int d, int format, const float* scale_dev, mvlpt_stream_t stream) {
+  if (!in || !out) return fail(nullptr, MVLPT_ERR_ARG, "op_cast_ex: null pointer");
+  if (!is16(dtype) || format < 0 || format > 2 || rows < 0 || d <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_cast_ex: dtype is fp16 or bf16, format in {0, 1, 2}, rows >= 0, d > 0");
+  if (d % 4) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "op_cast_ex: d must be a multiple of 4");
+  if (format == 0) OPCHK(launch_cast_f32_to16(dtype, in, out, (size_t)rows * d, scale_dev, (hipStream_t)stream));
+  else OPCHK(launch_cast_f32_split(dtype, in, out, (size_t)rows, d, scale_dev, (hipStream_t)stream, format == 2));
+  return 0;
+}
+int mvlpt_op_cast_to_f32(int in_dtype, const void* in, float* out, int64_t n, mvlpt_stream_t stream) {
+  if (!in || !out || n < 0) return fail(nullptr, MVLPT_ERR_ARG, "op_cast_to_f32: null pointer or n < 0");
+  if (in_dtype != DT_F32 && !is16(in_dtype)) return fail(nullptr, MVLPT_ERR_ARG, "op_cast_to_f32: unknown input dtype");
+  OPCHK(launch_cast_any_to_f32(in_dtype, in, out, (size_t)n, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_pack_weight(int dtype, const float* w32, int rows, int cols, int transposed, int ld_out, void* out, mvlpt_stream_t stream) {
+  if (!w32 || !out || rows <= 0 || cols <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_pack_weight: null pointer or empty weight");
+  if (dtype != DT_F32 && !is16(dtype)) return fail(nullptr, MVLPT_ERR_ARG, "op_pack_weight: unknown dtype");
+  const int width = transposed ? rows : cols;
+  if (ld_out <= 0) ld_out = width;
+  if (ld_out < width) return fail(nullptr, MVLPT_ERR_ARG, "op_pack_weight: ld_out is shorter than a row of the output");
+  if (transposed) OPCHK(launch_pack_weight_t(dtype, w32, out, rows, cols, (hipStream_t)stream, ld_out));
+  else OPCHK(launch_pack_weight(dtype, w32, out, rows, cols, ld_out, (hipStream_t)stream));
+  return 0;
+}
+static int patchify_check(const char* who, int dtype, int image_dtype, int R, int P) {
+  if (!is16(dtype) || (image_dtype != DT_F32 && !is16(image_dtype))) return fail(nullptr, MVLPT_ERR_ARG, std::string(who) + ": dtype is fp16 or bf16, image_dtype fp32, fp16 or bf16");
+  if (R <= 0 || P <= 0) return fail(nullptr, MVLPT_ERR_ARG, std::string(who) + ": R, P > 0");
+  if (R % P) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, std::string(who) + ": R must be a multiple of P");
+  return 0;
+}
+int mvlpt_op_patchify(int dtype, const void* image, int image_dtype, void* out, int B, int R, int P, int Kp, mvlpt_stream_t stream) {
+  if (!image || !out || B <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_patchify: null pointer or B <= 0");
+  if (int rc = patchify_check("op_patchify", dtype, image_dtype, R, P)) return rc;
+  if (Kp % 8) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "op_patchify: Kp must be a multiple of 8");
+  if (Kp < 3 * P * P) return fail(nullptr, MVLPT_ERR_ARG, "op_patchify: Kp is shorter than a patch (3 P^2)");
+  OPCHK(launch_patchify(dtype, image, image_dtype, out, B, R, P, Kp, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_patchify_route(int dtype, int image_dtype, int R, int P) {
+  if (int rc = patchify_check("op_patchify_route", dtype, image_dtype, R, P)) return rc;
+  return patchify_route(dtype, image_dtype, R, P);
+}
 // The ranged glue without a tower (tests).  The range table is built and checked on the host, uploaded into a temporary buffer, and the
 // call waits for its kernel before the buffer is freed.
 static int op_range_table(const int32_t* class_lo, const int32_t* class_hi, int G, int C, std::vector<int32_t>& t, int32_t** dev, int* S) {

@@ -245,13 +245,21 @@ __global__ __launch_bounds__(256) void patchify16_kernel(const u32x4* __restrict
     out[((size_t)(b * G + gy) * G + gx) * KC + cb] = v;
   }
 }
+// The one place that chooses the patch-extraction kernel (patchify_t and mvlpt_op_patchify_route ask it): 2 = the 16-byte copy (image of
+// the compute type, 8-pixel chunks, one patch row of the image within 64 KB of LDS), 1 = the vector kernel (fp32 image), 0 = scalar.
+int patchify_route(int dtype, int image_dtype, int R, int P) {
+  if (image_dtype == dtype && P % 8 == 0 && R % 8 == 0 && 3 * P * (R / 8) * 16 <= 65536) return 2;
+  if (image_dtype == DT_F32 && P % 8 == 0 && R % 4 == 0) return 1;
+  return 0;
+}
 template <typename T>
 static hipError_t patchify_t(const void* image, int image_dtype, T* out, int B, int R, int P, int Kp, hipStream_t s) {
-  if (image_dtype == (sizeof(T) == 2 && std::is_same<T, f16>::value ? DT_F16 : DT_BF16) && P % 8 == 0 && R % 8 == 0 && 3 * P * (R / 8) * 16 <= 65536) {
+  const int route = patchify_route(std::is_same<T, f16>::value ? DT_F16 : DT_BF16, image_dtype, R, P);
+  if (route == 2) {
     hipLaunchKernelGGL(patchify16_kernel, dim3(B * (R / P)), dim3(256), 3 * P * (R / 8) * 16, s, (const u32x4*)image, (u32x4*)out, R, P, Kp);
     return hipGetLastError();
   }
-  if (image_dtype == DT_F32 && P % 8 == 0 && R % 4 == 0) {
+  if (route == 1) {
     const size_t n8v = (size_t)B * (R / P) * (R / P) * (Kp / 8);
     const int gridv = (int)((n8v + 255) / 256 < 16384 ? (n8v + 255) / 256 : 16384);
     hipLaunchKernelGGL((patchify_vec_kernel<T>), dim3(gridv), dim3(256), 0, s, (const float*)image, out, B, R, P, Kp);

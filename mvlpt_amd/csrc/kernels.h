@@ -153,6 +153,10 @@ struct LnBwdArgs {
   int split = 0;         // out16 is [*, 2d] = [hi | lo]; 2: [hi | lo8 bytes | unused] (mixed pair)
 };
 hipError_t launch_ln_bwd(int dtype, const LnBwdArgs& a, hipStream_t s);
+// The kernel both launchers use for `rows` x `d` on stream `s`: stream = 0 one wave per row (ln_*_kernel), 1 grid-stride
+// (ln_*_stream_kernel<.., nv>); grid = its workgroups of 4 waves.  Part of the C ABI (mvlpt_op_layernorm_route).
+struct LnRoute { int stream, nv, grid; };
+LnRoute ln_route(int rows, int d, hipStream_t s);
 
 // ---------------------------------------------------------------- attention (head_dim 64, L <= 256)
 // qkv: [N*L, 3*d] 16-bit, token = n*L + i, columns [q | k | v], head h at h*64 inside each third.
@@ -235,6 +239,8 @@ hipError_t launch_pack_weight8(const float* w, uint8_t* out8, int rows, int cols
 hipError_t launch_pack_weight_t(int dtype, const float* w, void* out, int rows, int cols, hipStream_t s, int ld_out = 0);
 // image [B,3,R,R] (fp32 / f16 / bf16) -> patches16 [B*g*g, Kp], column order (c,ky,kx), zero padded to Kp
 hipError_t launch_patchify(int dtype, const void* image, int image_dtype, void* out, int B, int R, int P, int Kp, hipStream_t s);
+// the kernel launch_patchify uses: 0 patchify_kernel (scalar), 1 patchify_vec_kernel, 2 patchify16_kernel (mvlpt_op_patchify_route)
+int patchify_route(int dtype, int image_dtype, int R, int P);
 // tokens: row0 = LN(cls + pos0); rows 1..n = vpt; rest = LN(patch + pos)   (trainers/mvlpt.py:56-62)
 hipError_t launch_assemble_tokens(const float* patch_emb, const float* cls, const float* pos, const float* g, const float* b,
                                   const float* vpt, int n_vpt, float* x, int B, int G2, int d, hipStream_t s,

@@ -147,16 +147,24 @@ __global__ __launch_bounds__(256) void ln_fwd_stream_kernel(LnFwdArgs a) {
   }
 }
 
-template <typename TO>
-static void launch_ln_fwd_stream(const LnFwdArgs& a, hipStream_t s) {
-  const int cus = stream_cus(s);
+// The one place that chooses the kernel and its grid (launch_ln_fwd, launch_ln_bwd and mvlpt_op_layernorm_route all ask it): from 4096
+// rows on, the grid-stride kernels with 8 resident workgroups per compute unit of the stream and NV = 2 / 3 / 4 / 8 float4 per lane;
+// below, one wave per row.
+LnRoute ln_route(int rows, int d, hipStream_t s) {
+  const int want = (rows + 3) / 4;
+  if (rows < 4096) return LnRoute{0, LN_MAXV, want};
   constexpr int per_cu = 8;      // resident workgroups per CU
-  const int want = (a.rows + 3) / 4;
-  dim3 grid(want < cus * per_cu ? want : cus * per_cu), block(256);
-  const int nv = (a.d + 255) / 256;
-  if (nv <= 2) hipLaunchKernelGGL((ln_fwd_stream_kernel<TO, 2>), grid, block, 0, s, a);
-  else if (nv == 3) hipLaunchKernelGGL((ln_fwd_stream_kernel<TO, 3>), grid, block, 0, s, a);
-  else if (nv == 4) hipLaunchKernelGGL((ln_fwd_stream_kernel<TO, 4>), grid, block, 0, s, a);
+  const int cus = stream_cus(s);
+  const int nv = (d + 255) / 256;
+  return LnRoute{1, nv <= 2 ? 2 : nv == 3 ? 3 : nv == 4 ? 4 : LN_MAXV, want < cus * per_cu ? want : cus * per_cu};
+}
+
+template <typename TO>
+static void launch_ln_fwd_stream(const LnFwdArgs& a, const LnRoute& r, hipStream_t s) {
+  dim3 grid(r.grid), block(256);
+  if (r.nv == 2) hipLaunchKernelGGL((ln_fwd_stream_kernel<TO, 2>), grid, block, 0, s, a);
+  else if (r.nv == 3) hipLaunchKernelGGL((ln_fwd_stream_kernel<TO, 3>), grid, block, 0, s, a);
+  else if (r.nv == 4) hipLaunchKernelGGL((ln_fwd_stream_kernel<TO, 4>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((ln_fwd_stream_kernel<TO, LN_MAXV>), grid, block, 0, s, a);
 }
 
@@ -278,29 +286,26 @@ __global__ __launch_bounds__(256) void ln_bwd_stream_kernel(LnBwdArgs a) {
 }
 
 template <typename TDY, typename T>
-static void launch_ln_bwd_stream(const LnBwdArgs& a, hipStream_t s) {
-  const int cus = stream_cus(s);
-  constexpr int per_cu = 8;      // resident workgroups per CU
-  const int want = (a.rows + 3) / 4;
-  dim3 grid(want < cus * per_cu ? want : cus * per_cu), block(256);
-  const int nv = (a.d + 255) / 256;
-  if (nv <= 2) hipLaunchKernelGGL((ln_bwd_stream_kernel<TDY, T, 2>), grid, block, 0, s, a);
-  else if (nv == 3) hipLaunchKernelGGL((ln_bwd_stream_kernel<TDY, T, 3>), grid, block, 0, s, a);
-  else if (nv == 4) hipLaunchKernelGGL((ln_bwd_stream_kernel<TDY, T, 4>), grid, block, 0, s, a);
+static void launch_ln_bwd_stream(const LnBwdArgs& a, const LnRoute& r, hipStream_t s) {
+  dim3 grid(r.grid), block(256);
+  if (r.nv == 2) hipLaunchKernelGGL((ln_bwd_stream_kernel<TDY, T, 2>), grid, block, 0, s, a);
+  else if (r.nv == 3) hipLaunchKernelGGL((ln_bwd_stream_kernel<TDY, T, 3>), grid, block, 0, s, a);
+  else if (r.nv == 4) hipLaunchKernelGGL((ln_bwd_stream_kernel<TDY, T, 4>), grid, block, 0, s, a);
   else hipLaunchKernelGGL((ln_bwd_stream_kernel<TDY, T, LN_MAXV>), grid, block, 0, s, a);
 }
 
 hipError_t launch_ln_fwd(int out_dtype, const LnFwdArgs& a, hipStream_t s) {
   if (a.rows <= 0) return hipSuccess;
   if (a.d % 4 != 0 || a.d > LN_MAXV * 256) return hipErrorInvalidValue;
-  if (a.rows >= 4096) {
-    if (out_dtype == DT_F32) launch_ln_fwd_stream<float>(a, s);
-    else if (out_dtype == DT_F16) launch_ln_fwd_stream<f16>(a, s);
-    else if (out_dtype == DT_BF16) launch_ln_fwd_stream<bf16>(a, s);
+  const LnRoute r = ln_route(a.rows, a.d, s);
+  if (r.stream) {
+    if (out_dtype == DT_F32) launch_ln_fwd_stream<float>(a, r, s);
+    else if (out_dtype == DT_F16) launch_ln_fwd_stream<f16>(a, r, s);
+    else if (out_dtype == DT_BF16) launch_ln_fwd_stream<bf16>(a, r, s);
     else return hipErrorInvalidValue;
     return hipGetLastError();
   }
-  dim3 grid((a.rows + 3) / 4), block(256);
+  dim3 grid(r.grid), block(256);
   if (out_dtype == DT_F32) hipLaunchKernelGGL(ln_fwd_kernel<float>, grid, block, 0, s, a);
   else if (out_dtype == DT_F16) hipLaunchKernelGGL(ln_fwd_kernel<f16>, grid, block, 0, s, a);
   else if (out_dtype == DT_BF16) hipLaunchKernelGGL(ln_fwd_kernel<bf16>, grid, block, 0, s, a);
@@ -311,11 +316,12 @@ hipError_t launch_ln_fwd(int out_dtype, const LnFwdArgs& a, hipStream_t s) {
 hipError_t launch_ln_bwd(int dtype, const LnBwdArgs& a, hipStream_t s) {
   if (a.rows <= 0) return hipSuccess;
   if (a.d % 4 != 0 || a.d > LN_MAXV * 256) return hipErrorInvalidValue;
-  dim3 grid((a.rows + 3) / 4), block(256);
+  const LnRoute r = ln_route(a.rows, a.d, s);
+  dim3 grid(r.grid), block(256);
   const bool dy32 = a.dy_dtype == DT_F32;
-  if (a.rows >= 4096) {
-    if (dtype == DT_F16) { if (dy32) launch_ln_bwd_stream<float, f16>(a, s); else launch_ln_bwd_stream<f16, f16>(a, s); }
-    else if (dtype == DT_BF16) { if (dy32) launch_ln_bwd_stream<float, bf16>(a, s); else launch_ln_bwd_stream<bf16, bf16>(a, s); }
+  if (r.stream) {
+    if (dtype == DT_F16) { if (dy32) launch_ln_bwd_stream<float, f16>(a, r, s); else launch_ln_bwd_stream<f16, f16>(a, r, s); }
+    else if (dtype == DT_BF16) { if (dy32) launch_ln_bwd_stream<float, bf16>(a, r, s); else launch_ln_bwd_stream<bf16, bf16>(a, r, s); }
     else return hipErrorInvalidValue;
     return hipGetLastError();
   }

@@ -1128,6 +1128,69 @@ def op_layernorm_bwd(dy, x, gamma, resid=None, want16=True):
     return out32, out16
 
 
+def _dt(dtype) -> int:
+    """A torch dtype, or the raw MVLPT_DT_* integer (refusal tests pass unknown ones)."""
+    return dtype if isinstance(dtype, int) else _TORCH2DT[dtype]
+
+
+def op_layernorm_fwd_ex(x, gamma, beta, y, rows, d, row_mul=1, split=0, out_dtype=None):
+    """mvlpt_op_layernorm_fwd_ex on caller-owned tensors (nothing is copied, allocated or made contiguous)."""
+    _lib.check(lib.mvlpt_op_layernorm_fwd_ex(_dt(y.dtype if out_dtype is None else out_dtype), _ptr(x), row_mul, _ptr(gamma), _ptr(beta),
+                                             _ptr(y), rows, d, split, _stream()), None, "op_layernorm_fwd_ex")
+    return y
+
+
+def op_layernorm_bwd_ex(dy, x, gamma, out32, rows, d, dtype, resid=None, out16=None, row_mul=1, split=0, dy_dtype=None):
+    """mvlpt_op_layernorm_bwd_ex on caller-owned tensors; out32 may be `resid` itself."""
+    _lib.check(lib.mvlpt_op_layernorm_bwd_ex(_dt(dtype), _ptr(dy), _dt(dy.dtype if dy_dtype is None else dy_dtype), _ptr(x), row_mul,
+                                             _ptr(gamma), _ptr(resid), _ptr(out32), _ptr(out16), rows, d, split, _stream()),
+               None, "op_layernorm_bwd_ex")
+    return out32, out16
+
+
+def op_layernorm_route(rows, d):
+    """(0 direct / 1 grid-stride, float4 per lane of the instantiation, workgroups) of a LayerNorm launch on the current stream."""
+    nv, grid = C.c_int(0), C.c_int(0)
+    kind = lib.mvlpt_op_layernorm_route(rows, d, _stream(), C.byref(nv), C.byref(grid))
+    if kind < 0:
+        raise RuntimeError(f"libmvlpt_hip op_layernorm_route failed (code {kind}): {_lib.last_error(None)}")
+    return kind, nv.value, grid.value
+
+
+def op_cast_ex(x32, out, rows, d, fmt=0, scale_dev=None, dtype=None):
+    """mvlpt_op_cast_ex: fmt 0 plain, 1 hi|lo pair, 2 mixed pair; scale_dev a device float tensor or None."""
+    _lib.check(lib.mvlpt_op_cast_ex(_dt(out.dtype if dtype is None else dtype), _ptr(x32), _ptr(out), rows, d, fmt, _ptr(scale_dev),
+                                    _stream()), None, "op_cast_ex")
+    return out
+
+
+def op_cast_to_f32(x, out, n, in_dtype=None):
+    _lib.check(lib.mvlpt_op_cast_to_f32(_dt(x.dtype if in_dtype is None else in_dtype), _ptr(x), _ptr(out), n, _stream()), None,
+               "op_cast_to_f32")
+    return out
+
+
+def op_pack_weight(w32, out, rows, cols, transposed=False, ld_out=0, dtype=None):
+    _lib.check(lib.mvlpt_op_pack_weight(_dt(out.dtype if dtype is None else dtype), _ptr(w32), rows, cols, int(transposed), ld_out,
+                                        _ptr(out), _stream()), None, "op_pack_weight")
+    return out
+
+
+def op_patchify(image, out, B, R, P, Kp, dtype=None, image_dtype=None):
+    _lib.check(lib.mvlpt_op_patchify(_dt(out.dtype if dtype is None else dtype), _ptr(image),
+                                     _dt(image.dtype if image_dtype is None else image_dtype), _ptr(out), B, R, P, Kp, _stream()),
+               None, "op_patchify")
+    return out
+
+
+def op_patchify_route(dtype, image_dtype, R, P):
+    """0 scalar, 1 vector, 2 the 16-byte copy: the kernel op_patchify uses."""
+    route = lib.mvlpt_op_patchify_route(_dt(dtype), _dt(image_dtype), R, P)
+    if route < 0:
+        raise RuntimeError(f"libmvlpt_hip op_patchify_route failed (code {route}): {_lib.last_error(None)}")
+    return route
+
+
 def op_attention_fwd(qkv, N, L, H, causal, want_lse=True):
     out = torch.empty(N * L, H * 64, device=qkv.device, dtype=qkv.dtype)
     lse = torch.empty(N * H * L, device=qkv.device, dtype=torch.float32) if want_lse else None

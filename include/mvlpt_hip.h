@@ -639,6 +639,43 @@ typedef struct MvlptImageDesc {
 int mvlpt_preprocess(void* handle, const uint8_t* src, int64_t src_bytes, const MvlptImageDesc* descs, int B, int out_h, int out_w,
                      const float* mean, const float* std, void* out, int out_dtype, uint8_t* out_u8, mvlpt_stream_t stream);
 
+/* ---- augmented input pipeline (row f3b of the scope table) ---------------------------------------------------
+ * The augmentations of Dassl's `build_transform` beyond those three (the launcher's --transforms): colorjitter,
+ * randomgrayscale, random_crop with zero padding, cutout.  torchvision runs them on PIL images: ColorJitter is
+ * `ImageEnhance.Brightness / Contrast / Color` and an HSV round trip in a drawn order, RandomGrayscale is `convert("L")`,
+ * RandomCrop(padding) is `pad(fill=0)` in front of a crop, and Dassl's Cutout zeroes rectangles of the tensor before
+ * Normalize.  The caller draws the parameters; the pixels are bit-identical to Pillow's and torch's:
+ *   L                (R*19595 + G*38470 + B*7471 + 0x8000) >> 16
+ *   blend(d, x, a)   t = (float)d + a * (float)(x - d) in fp32; 0 <= a <= 1: (uint8)(int)t; else t <= 0 -> 0, t >= 255 -> 255, else (int)t
+ *   brightness       blend(0, x, factor[0]);  saturation: blend(L of the pixel, x, factor[2])
+ *   contrast         blend(m, x, factor[1]), m = (int)((double)(sum of L) / (double)(out_h*out_w) + 0.5) over the whole output
+ *                    window, padding included, of the image as it stands at that point of the chain
+ *   hue              Pillow's RGB -> HSV, H = (H + hue_shift) & 255, HSV -> RGB; it runs for a shift of 0 too and is not the identity
+ *   grayscale        every channel := L;  holes: the rectangle := 0 in all channels
+ * Order per image: resample -> window -> flip -> ops[0..n_ops) -> grayscale -> holes -> ToTensor -> Normalize. */
+#define MVLPT_AUG_MAX_HOLES 4
+#define MVLPT_AUG_BRIGHTNESS 0
+#define MVLPT_AUG_CONTRAST 1
+#define MVLPT_AUG_SATURATION 2
+#define MVLPT_AUG_HUE 3
+typedef struct MvlptAugmentDesc {
+  int32_t n_ops;            /* 0..4 colour operations, applied in the order of ops[] */
+  int32_t ops[4];           /* distinct MVLPT_AUG_* ids */
+  float   factor[3];        /* brightness, contrast, saturation factor (finite, >= 0), read only if the operation is listed */
+  int32_t hue_shift;        /* 0..255, added to H modulo 256; read only if hue is listed */
+  int32_t grayscale;        /* 1: replace the image by its L channel after the colour operations */
+  int32_t n_holes;          /* 0..MVLPT_AUG_MAX_HOLES */
+  int32_t hole[MVLPT_AUG_MAX_HOLES][4];   /* top, left, height >= 1, width >= 1, inside the output window (clipped by the caller) */
+} MvlptAugmentDesc;
+/* As mvlpt_preprocess, plus: aug: HOST array of B descriptors or NULL (no colour operation, grayscale or hole);
+ * fill_outside 1: the window [out_top, out_top+out_h) x [out_left, out_left+out_w) may lie partly or wholly outside the resized image
+ * (offsets within +-2^30), pixels outside are (0, 0, 0); 0: it must lie inside.  With aug == NULL and fill_outside == 0 the call IS
+ * mvlpt_preprocess.  out_u8 is the 8-bit image just before ToTensor (after flip, colour operations, grayscale and holes).  Everything
+ * the device indexes is checked on the host first: a bad descriptor returns MVLPT_ERR_ARG and nothing is launched.  B == 0 returns 0. */
+int mvlpt_preprocess_aug(void* handle, const uint8_t* src, int64_t src_bytes, const MvlptImageDesc* descs, const MvlptAugmentDesc* aug,
+                         int B, int out_h, int out_w, int fill_outside, const float* mean, const float* std, void* out, int out_dtype,
+                         uint8_t* out_u8, mvlpt_stream_t stream);
+
 /* ---- per-kernel timing with HIP events on the launch stream (bench.py's roofline leg) --------------------- */
 typedef struct MvlptKernelStat {
   char name[32];

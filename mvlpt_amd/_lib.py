@@ -49,6 +49,15 @@ class MvlptImageDesc(C.Structure):
         "out_top", "out_left", "flip", "reserved")]
 
 
+AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE = 0, 1, 2, 3      # MVLPT_AUG_*
+AUG_MAX_HOLES = 4                                                      # MVLPT_AUG_MAX_HOLES
+
+
+class MvlptAugmentDesc(C.Structure):
+    _fields_ = [("n_ops", C.c_int32), ("ops", C.c_int32 * 4), ("factor", C.c_float * 3), ("hue_shift", C.c_int32),
+                ("grayscale", C.c_int32), ("n_holes", C.c_int32), ("hole", (C.c_int32 * 4) * AUG_MAX_HOLES)]
+
+
 OPTIM_SGD, OPTIM_ADAM, OPTIM_ADAMW = 0, 1, 2
 OPTIM_MAX_SEGS = 1024   # MVLPT_OPTIM_MAX_SEGS
 
@@ -170,6 +179,8 @@ SIGNATURES = {
     "mvlpt_op_softmax_reg_eval": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mvlpt_op_softmax_reg_predict": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, C.c_size_t, _vp]),
     "mvlpt_preprocess": (_i, [_vp, _vp, C.c_int64, C.POINTER(MvlptImageDesc), _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _i, _vp, _vp]),
+    "mvlpt_preprocess_aug": (_i, [_vp, _vp, C.c_int64, C.POINTER(MvlptImageDesc), C.POINTER(MvlptAugmentDesc), _i, _i, _i, _i,
+                                  C.POINTER(_f), C.POINTER(_f), _vp, _i, _vp, _vp]),
     "mvlpt_profile_begin": (_i, [_vp, _i]),
     "mvlpt_profile_pause": (_i, [_vp, _i]),
     "mvlpt_profile_end": (_i, [_vp, C.POINTER(MvlptKernelStat), _i]),

@@ -50,7 +50,10 @@ def get_cfg_default() -> CfgNode:
     cfg.SEED = 1
     cfg.OUTPUT_DIR = "./output"
     cfg.MODEL = CN(BACKBONE=CN(NAME="ViT-B/16"), INIT_WEIGHTS="")
-    cfg.INPUT = CN(SIZE=(224, 224))
+    # TRANSFORMS and the parameters of its augmentations: Dassl's names and defaults (mvlpt_amd.transforms.build_device_transform; the
+    # launcher's --transforms).  On the command line the list comes as JSON: INPUT.TRANSFORMS '["random_crop", "random_flip", "cutout"]'
+    cfg.INPUT = CN(SIZE=(224, 224), TRANSFORMS=["random_resized_crop", "random_flip", "normalize"], COLORJITTER_B=0.4, COLORJITTER_C=0.4,
+                   COLORJITTER_S=0.4, COLORJITTER_H=0.1, RGS_P=0.2, CROP_PADDING=4, CUTOUT_N=1, CUTOUT_LEN=16)
     cfg.DATALOADER = CN(TRAIN_X=CN(BATCH_SIZE=32), TEST=CN(BATCH_SIZE=100), NUM_WORKERS=8)
     # configs/trainers/MVLPT/vit_b16.yaml:15-22 + Dassl optimizer defaults
     cfg.OPTIM = CN(NAME="sgd", LR=0.002, MAX_EPOCH=200, MOMENTUM=0.9, WEIGHT_DECAY=5e-4, SGD_DAMPNING=0.0,

@@ -2580,6 +2580,72 @@ int mvlpt_preprocess(void* h, const uint8_t* src, int64_t src_bytes, const Mvlpt
   return 0;
 }
 
+int mvlpt_preprocess_aug(void* h, const uint8_t* src, int64_t src_bytes, const MvlptImageDesc* descs, const MvlptAugmentDesc* aug, int B,
+                         int out_h, int out_w, int fill_outside, const float* mean, const float* stdv, void* out, int out_dtype,
+                         uint8_t* out_u8, mvlpt_stream_t stream) {
+  static_assert(sizeof(MvlptAugmentDesc) == sizeof(PpAug) && MVLPT_AUG_MAX_HOLES == PP_AUG_MAX_HOLES, "descriptor layouts must match");
+  Engine* E = (Engine*)h;
+  if (!E) return MVLPT_ERR_ARG;
+  if (B < 0 || (fill_outside != 0 && fill_outside != 1)) return fail(E, MVLPT_ERR_ARG, "preprocess_aug: negative batch, or fill_outside is not 0 or 1");
+  if (B == 0) return 0;
+  if (!aug && !fill_outside) return mvlpt_preprocess(h, src, src_bytes, descs, B, out_h, out_w, mean, stdv, out, out_dtype, out_u8, stream);
+  if (!src || !descs || out_h <= 0 || out_w <= 0 || (int64_t)out_h * out_w > (1 << 29) || !mean || !stdv || (!out && !out_u8))
+    return fail(E, MVLPT_ERR_ARG, "preprocess_aug: null pointer or empty / oversized output");
+  if (out && out_dtype != DT_F32 && out_dtype != DT_F16 && out_dtype != DT_BF16) return fail(E, MVLPT_ERR_ARG, "preprocess_aug: bad out_dtype");
+  int max_crop_h = 0, ks_max = 1;
+  const int64_t far = (int64_t)1 << 30;
+  for (int b = 0; b < B; ++b) {
+    const MvlptImageDesc& d = descs[b];
+    bool ok = d.height > 0 && d.width > 0 && d.offset >= 0 && d.offset + (int64_t)d.height * d.width * 3 <= src_bytes &&
+              d.crop_top >= 0 && d.crop_left >= 0 && d.crop_height > 0 && d.crop_width > 0 &&
+              d.crop_top + d.crop_height <= d.height && d.crop_left + d.crop_width <= d.width && d.resize_height > 0 &&
+              d.resize_width > 0 && (d.flip == 0 || d.flip == 1);
+    if (fill_outside) ok = ok && d.out_top >= -far && d.out_top <= far && d.out_left >= -far && d.out_left <= far;
+    else ok = ok && d.out_top >= 0 && d.out_left >= 0 && (int64_t)d.out_top + out_h <= d.resize_height && (int64_t)d.out_left + out_w <= d.resize_width;
+    if (!ok) return fail(E, MVLPT_ERR_ARG, "preprocess_aug: descriptor " + std::to_string(b) + " is inconsistent (box outside the image, image outside src, or window outside the resized image without fill_outside)");
+    max_crop_h = std::max(max_crop_h, (int)d.crop_height);
+    const double sh = std::max(1.0, (double)d.crop_height / d.resize_height), sw = std::max(1.0, (double)d.crop_width / d.resize_width);
+    ks_max = std::max(ks_max, std::max((int)std::ceil(2.0 * sh), (int)std::ceil(2.0 * sw)) * 2 + 1);
+    if (!aug) continue;
+    const MvlptAugmentDesc& a = aug[b];
+    ok = a.n_ops >= 0 && a.n_ops <= PP_AUG_MAX_OPS && (a.grayscale == 0 || a.grayscale == 1) && a.n_holes >= 0 && a.n_holes <= PP_AUG_MAX_HOLES;
+    unsigned seen = 0;
+    for (int k = 0; ok && k < a.n_ops; ++k) {
+      const int op = a.ops[k];
+      ok = op >= 0 && op <= PP_OP_HUE && !(seen >> op & 1u);
+      if (!ok) break;
+      seen |= 1u << op;
+      if (op == PP_OP_HUE) ok = a.hue_shift >= 0 && a.hue_shift <= 255;
+      else ok = std::isfinite(a.factor[op]) && a.factor[op] >= 0.0f;
+    }
+    for (int k = 0; ok && k < a.n_holes; ++k) {
+      const int32_t* r = a.hole[k];
+      ok = r[0] >= 0 && r[1] >= 0 && r[2] >= 1 && r[3] >= 1 && (int64_t)r[0] + r[2] <= out_h && (int64_t)r[1] + r[3] <= out_w;
+    }
+    if (!ok) return fail(E, MVLPT_ERR_ARG, "preprocess_aug: augmentation " + std::to_string(b) + " is malformed (operation count / id / repeat, factor not finite or negative, hue_shift, grayscale, or a hole outside the window)");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int n_max = std::max(out_h, out_w);
+  const size_t table_stride = (size_t)(2 + ks_max) * n_max;                          // int32 per (image, pass)
+  const size_t tmp_stride = align256((size_t)max_crop_h * out_w * 3);
+  const size_t desc_bytes = align256(sizeof(PpDesc) * (size_t)B), aug_bytes = align256(sizeof(PpAug) * (size_t)B);
+  const size_t table_bytes = align256(table_stride * 4 * 2 * (size_t)B), tmp_bytes = align256(tmp_stride * (size_t)B);
+  const size_t win_bytes = out_u8 ? 0 : (size_t)B * out_h * out_w * 3;                 // the colour stage works in out_u8 when it is asked for
+  HIPCHK(E, E->pp_ws.reserve(desc_bytes + aug_bytes + table_bytes + tmp_bytes + win_bytes));
+  char* base = (char*)E->pp_ws.p;
+  PpDesc* descs_dev = (PpDesc*)base;
+  PpAug* augs_dev = (PpAug*)(base + desc_bytes);
+  int32_t* tables = (int32_t*)(base + desc_bytes + aug_bytes);
+  uint8_t* tmp = (uint8_t*)(base + desc_bytes + aug_bytes + table_bytes);
+  uint8_t* win = out_u8 ? out_u8 : tmp + tmp_bytes;
+  HIPCHK(E, hipMemcpyAsync(descs_dev, descs, sizeof(PpDesc) * (size_t)B, hipMemcpyHostToDevice, s));
+  if (aug) HIPCHK(E, hipMemcpyAsync(augs_dev, aug, sizeof(PpAug) * (size_t)B, hipMemcpyHostToDevice, s));
+  else HIPCHK(E, hipMemsetAsync(augs_dev, 0, sizeof(PpAug) * (size_t)B, s));
+  HIPCHK(E, launch_preprocess_aug(src, descs_dev, augs_dev, B, max_crop_h, ks_max, out_h, out_w, tables, table_stride, tmp, tmp_stride, win,
+                                  mean, stdv, out, out_dtype, s));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ profiling
 int mvlpt_profile_begin(void* h, int all_kernels) {
   Engine* E = (Engine*)h;

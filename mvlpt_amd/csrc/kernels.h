@@ -222,6 +222,20 @@ struct PpDesc {
 hipError_t launch_preprocess(const uint8_t* src, const PpDesc* descs_dev, int B, int max_crop_h, int ks_max, int out_h, int out_w,
                              int32_t* tables, size_t table_stride, uint8_t* tmp, size_t tmp_stride, const float* mean,
                              const float* stdv, void* out, int out_dtype, uint8_t* out_u8, hipStream_t s);
+// same layout as MvlptAugmentDesc (include/mvlpt_hip.h)
+constexpr int PP_AUG_MAX_OPS = 4, PP_AUG_MAX_HOLES = 4;
+enum { PP_OP_BRIGHTNESS = 0, PP_OP_CONTRAST = 1, PP_OP_SATURATION = 2, PP_OP_HUE = 3 };
+struct PpAug {
+  int32_t n_ops, ops[PP_AUG_MAX_OPS];        // colour operations in the order they are applied
+  float factor[3];                           // brightness, contrast, saturation
+  int32_t hue_shift, grayscale, n_holes;
+  int32_t hole[PP_AUG_MAX_HOLES][4];         // top, left, height, width inside the output window
+};
+// the FILL form of the three kernels above (a window index outside the resized image produces 0), the vertical pass writing only the
+// flipped 8-bit window `win` [B,out_h,out_w,3], then the colour chain / grayscale / holes in place on it and ToTensor / Normalize
+hipError_t launch_preprocess_aug(const uint8_t* src, const PpDesc* descs_dev, const PpAug* augs_dev, int B, int max_crop_h, int ks_max,
+                                 int out_h, int out_w, int32_t* tables, size_t table_stride, uint8_t* tmp, size_t tmp_stride, uint8_t* win,
+                                 const float* mean, const float* stdv, void* out, int out_dtype, hipStream_t s);
 
 // ---------------------------------------------------------------- glue
 hipError_t launch_cast_f32_to16(int dtype, const float* in, void* out, size_t n, const float* scale_dev, hipStream_t s);

@@ -552,6 +552,27 @@ class Engine:
                                         _ptr(u8), _stream()), self.h, "preprocess")
         return (out, u8) if want_u8 else out
 
+    @_on_device
+    def preprocess_aug(self, src: torch.Tensor, descs, augs, out_size, mean, std, out_dtype=torch.float32, want_u8: bool = False,
+                       fill_outside: bool = False):
+        """`preprocess` with the augmentations of `mvlpt_preprocess_aug`: augs is a `_lib.MvlptAugmentDesc` ctypes array (one per image:
+        colour operations, grayscale, cutout holes) or None; fill_outside lets a window hang over the resized image, zero filled
+        (random_crop with padding).  The 8-bit images of `want_u8` are the ones just before ToTensor, after every augmentation."""
+        if not src.is_cuda or src.dtype != torch.uint8:
+            raise RuntimeError("src must be a uint8 CUDA/HIP tensor: mvlpt_amd has no CPU path")
+        if augs is not None and len(augs) != len(descs):
+            raise ValueError("one augmentation descriptor per image descriptor")
+        src = src.contiguous()
+        B = len(descs)
+        oh, ow = (out_size, out_size) if isinstance(out_size, int) else tuple(out_size)
+        out = torch.empty(B, 3, oh, ow, device=src.device, dtype=out_dtype)
+        u8 = torch.empty(B, oh, ow, 3, device=src.device, dtype=torch.uint8) if want_u8 else None
+        m = (C.c_float * 3)(*[float(v) for v in mean])
+        sd = (C.c_float * 3)(*[float(v) for v in std])
+        _lib.check(lib.mvlpt_preprocess_aug(self.h, _ptr(src), src.numel(), descs, augs, B, oh, ow, int(bool(fill_outside)), m, sd,
+                                            _ptr(out), _TORCH2DT[out_dtype], _ptr(u8), _stream()), self.h, "preprocess_aug")
+        return (out, u8) if want_u8 else out
+
     # ------------------------------------------------------------------ profiling
     @_on_device
     def profile_begin(self, all_kernels: bool = False):

@@ -5,9 +5,15 @@ Normalize: trainers/vision_benchmark/evaluation/feature.py:538-553), re-cut for 
 parameters and packs decoded uint8 images into one pinned buffer; crop, antialiased bicubic resample, flip, ToTensor
 and Normalize run in `mvlpt_preprocess` (csrc/preprocess.hip), bit-identical to Pillow + torch CPU.
 
+The launcher's `--transforms` reaches the same `build_transform`, so `DeviceTransform(transforms=...)` /
+`build_device_transform` also take Dassl's `random_crop` (zero padding), `center_crop`, `colorjitter`, `randomgrayscale` and
+`cutout`; their pixels run in `mvlpt_preprocess_aug`, bit-identical to Pillow's ImageEnhance / convert("L") / convert("HSV").
+
 The parameter sampling follows torchvision's documented algorithms (`RandomResizedCrop.get_params`, `Resize` with an
-int size, `CenterCrop`); torchvision is not installed in the build image, so those few integer formulas are restated
-from its documentation and are NOT pinned against it — the pixel arithmetic (Pillow) is, by tests/golden/preprocess.npz."""
+int size, `CenterCrop`, `RandomCrop.get_params`, `ColorJitter.get_params`, `RandomGrayscale`) and Dassl's `Cutout`; neither
+package is installed in the build image, so those few formulas and the order of the draws are restated from their
+documentation and are NOT pinned against them — the pixel arithmetic (Pillow) is, by tests/golden/preprocess.npz and
+tests/golden/augment.npz."""
 from __future__ import annotations
 
 import math
@@ -63,18 +69,80 @@ def center_crop_offsets(height: int, width: int, out_h: int, out_w: int) -> Tupl
     return int(round((height - out_h) / 2.0)), int(round((width - out_w) / 2.0))
 
 
+DEFAULT_TRANSFORMS = ("random_resized_crop", "random_flip", "normalize")
+# the names of Dassl's build_transform that run on the device.  Not offered: gaussian_blur, gaussian_noise,
+# random_translation, instance_norm and the randaugment / policy families.
+ACCEPTED_TRANSFORMS = ("random_resized_crop", "random_crop", "random_flip", "center_crop", "colorjitter", "randomgrayscale", "cutout",
+                       "normalize")
+
+
+def check_transforms(names: Sequence[str]) -> Tuple[str, ...]:
+    names = tuple(names)
+    bad = [n for n in names if n not in ACCEPTED_TRANSFORMS]
+    if bad:
+        raise ValueError(f"transforms {bad} do not run on the device; accepted: {', '.join(ACCEPTED_TRANSFORMS)}")
+    # one resample per image: a random_resized_crop OF a padded crop, or either of a centre crop, would need a second one
+    if sum(n in names for n in ("random_resized_crop", "random_crop", "center_crop")) > 1:
+        raise ValueError("random_resized_crop, random_crop and center_crop exclude one another on the device (one resample per image)")
+    return names
+
+
+def color_jitter_params(brightness: float, contrast: float, saturation: float, hue: float, generator: Optional[torch.Generator] = None):
+    """(ops, factors, hue_shift) as torchvision.transforms.ColorJitter.get_params draws them: a random order of the four operations,
+    then brightness / contrast / saturation factors uniform in [max(0, 1 - x), 1 + x] and the hue in [-h, h]; a parameter of 0 leaves its
+    operation out.  hue_shift is what adjust_hue adds to the 8-bit H channel: trunc(hue * 255) modulo 256."""
+    order = [int(k) for k in torch.randperm(4, generator=generator)]
+    factors = [1.0, 1.0, 1.0]
+    for k, x in enumerate((brightness, contrast, saturation)):
+        if x:
+            factors[k] = float(torch.empty(1).uniform_(max(0.0, 1.0 - x), 1.0 + x, generator=generator))
+    shift = int(float(torch.empty(1).uniform_(-hue, hue, generator=generator)) * 255) % 256 if hue else 0
+    on = (bool(brightness), bool(contrast), bool(saturation), bool(hue))
+    return [k for k in order if on[k]], factors, shift
+
+
+def cutout_holes(height: int, width: int, n_holes: int, length: int, generator: Optional[torch.Generator] = None):
+    """(top, left, h, w) of Dassl's Cutout: centres uniform over the image, [c - length // 2, c + length // 2) clipped to it; empty
+    rectangles are dropped."""
+    holes = []
+    for _ in range(n_holes):
+        cy = int(torch.randint(0, height, (1,), generator=generator))
+        cx = int(torch.randint(0, width, (1,), generator=generator))
+        y1, y2 = max(cy - length // 2, 0), min(cy + length // 2, height)
+        x1, x2 = max(cx - length // 2, 0), min(cx + length // 2, width)
+        if y2 > y1 and x2 > x1:
+            holes.append((y1, x1, y2 - y1, x2 - x1))
+    return holes
+
+
 class DeviceTransform:
-    """train=True : random_resized_crop + random_flip + normalize   (vit_b16.yaml:8-13)
+    """train=True : `transforms`, Dassl's names (default random_resized_crop + random_flip + normalize, vit_b16.yaml:8-13), composed in
+                 Dassl's fixed order whatever the order of the list: Resize((size, size)) unless random_resized_crop [Resize(size) +
+                 CenterCrop(size) with center_crop] -> random_crop (pad `crop_padding` zeros, crop at a uniform offset) ->
+                 random_resized_crop -> random_flip -> colorjitter -> randomgrayscale -> ToTensor -> cutout -> normalize.
     train=False: Resize(size) + CenterCrop(size) + normalize when `center_crop`, else Resize((size, size)) + normalize
                  (feature.py:538-553).
     Call with a list of decoded uint8 HWC numpy arrays (or uint8 tensors); returns the [B,3,size,size] device batch."""
 
     def __init__(self, engine, size: int = 224, train: bool = True, center_crop: bool = True, mean: Sequence[float] = CLIP_MEAN,
                  std: Sequence[float] = CLIP_STD, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip_p: float = 0.5,
-                 out_dtype=torch.float32, generator: Optional[torch.Generator] = None):
+                 out_dtype=torch.float32, generator: Optional[torch.Generator] = None, transforms: Optional[Sequence[str]] = None,
+                 colorjitter=(0.4, 0.4, 0.4, 0.1), rgs_p: float = 0.2, crop_padding: int = 4, cutout_n: int = 1, cutout_len: int = 16):
         self.engine, self.size, self.train, self.center_crop = engine, int(size), train, center_crop
         self.mean, self.std, self.scale, self.ratio, self.flip_p = tuple(mean), tuple(std), scale, ratio, flip_p
         self.out_dtype, self.generator = out_dtype, generator
+        self.transforms = check_transforms(DEFAULT_TRANSFORMS if transforms is None else transforms)
+        self.colorjitter, self.rgs_p, self.crop_padding = tuple(float(v) for v in colorjitter), float(rgs_p), int(crop_padding)
+        self.cutout_n, self.cutout_len = int(cutout_n), int(cutout_len)
+        if len(self.colorjitter) != 4 or min(self.colorjitter) < 0 or self.colorjitter[3] > 0.5:
+            raise ValueError("colorjitter is (brightness, contrast, saturation, hue), each >= 0 and hue <= 0.5")
+        if self.crop_padding < 0 or not 0 <= self.cutout_n <= _lib.AUG_MAX_HOLES or self.cutout_len < 0:
+            raise ValueError(f"crop_padding and cutout_len must be >= 0 and cutout_n in 0..{_lib.AUG_MAX_HOLES}")
+        if train and "normalize" not in self.transforms:               # Dassl then adds no Normalize: (x - 0) / 1 == x in fp32
+            self.mean, self.std = (0.0, 0.0, 0.0), (1.0, 1.0, 1.0)
+        # the window hangs over the resized image (zero filled) only under random_crop with padding
+        self.fill_outside = train and "random_crop" in self.transforms and self.crop_padding > 0
+        self.augments = train and any(n in self.transforms for n in ("colorjitter", "randomgrayscale", "cutout"))
         # ring of pinned staging buffers, each guarded by the event of its last H2D copy: the train step does not
         # synchronise per step, so the copy of batch i may still be queued when batch i+1 is packed
         self._ring: List[list] = [[None, None] for _ in range(3)]      # [pinned tensor, torch.cuda.Event]
@@ -82,17 +150,50 @@ class DeviceTransform:
 
     def describe(self, shapes: Sequence[Tuple[int, int]]):
         """Descriptors (ctypes array) for images of the given (height, width); draws the random parameters."""
-        R = self.size
+        descs, _, off = self.describe_aug(shapes)
+        return descs, off
+
+    def describe_aug(self, shapes: Sequence[Tuple[int, int]]):
+        """(image descriptors, augmentation descriptors or None when no transform needs them, total source bytes).  Per image the draws
+        come in the order of the composition: crop, flip, colorjitter, randomgrayscale, cutout."""
+        R, names, g = self.size, self.transforms, self.generator
         descs = (_lib.MvlptImageDesc * len(shapes))()
+        augs = (_lib.MvlptAugmentDesc * len(shapes))() if self.augments else None
         off = 0
-        for d, (h, w) in zip(descs, shapes):
+        for k, (d, (h, w)) in enumerate(zip(descs, shapes)):
             d.offset, d.height, d.width = off, h, w
             off += h * w * 3
             if self.train:
-                d.crop_top, d.crop_left, d.crop_height, d.crop_width = random_resized_crop_params(h, w, self.scale, self.ratio, self.generator)
                 d.resize_height = d.resize_width = R
                 d.out_top = d.out_left = 0
-                d.flip = int(float(torch.rand(1, generator=self.generator)) < self.flip_p)
+                if "random_resized_crop" in names:
+                    d.crop_top, d.crop_left, d.crop_height, d.crop_width = random_resized_crop_params(h, w, self.scale, self.ratio, g)
+                else:
+                    d.crop_top = d.crop_left = 0
+                    d.crop_height, d.crop_width = h, w
+                    if "center_crop" in names:
+                        d.resize_height, d.resize_width = resize_shorter_side(h, w, R)
+                        d.out_top, d.out_left = center_crop_offsets(d.resize_height, d.resize_width, R, R)
+                    elif "random_crop" in names:                       # RandomCrop.get_params on the padded image
+                        p = self.crop_padding
+                        d.out_top = int(torch.randint(0, 2 * p + 1, (1,), generator=g)) - p
+                        d.out_left = int(torch.randint(0, 2 * p + 1, (1,), generator=g)) - p
+                d.flip = int(float(torch.rand(1, generator=g)) < self.flip_p) if "random_flip" in names else 0
+                if augs is None:
+                    continue
+                a = augs[k]
+                if "colorjitter" in names:
+                    ops, factors, a.hue_shift = color_jitter_params(*self.colorjitter, generator=g)
+                    a.n_ops = len(ops)
+                    a.ops[:len(ops)] = ops
+                    a.factor[:] = factors
+                if "randomgrayscale" in names:
+                    a.grayscale = int(float(torch.rand(1, generator=g)) < self.rgs_p)
+                if "cutout" in names:
+                    holes = cutout_holes(R, R, self.cutout_n, self.cutout_len, g)
+                    a.n_holes = len(holes)
+                    for j, hole in enumerate(holes):
+                        a.hole[j][:] = hole
             else:
                 d.crop_top = d.crop_left = 0
                 d.crop_height, d.crop_width = h, w
@@ -103,7 +204,7 @@ class DeviceTransform:
                     d.resize_height = d.resize_width = R
                     d.out_top = d.out_left = 0
                 d.flip = 0
-        return descs, off
+        return descs, augs, off
 
     def pack(self, images: Sequence) -> Tuple[torch.Tensor, int]:
         """Copies the decoded images back to back into a (re-used) pinned host buffer."""
@@ -128,11 +229,22 @@ class DeviceTransform:
         return pinned, total
 
     def __call__(self, images: Sequence, want_u8: bool = False):
-        descs, total = self.describe([(int(im.shape[0]), int(im.shape[1])) for im in images])
+        descs, augs, total = self.describe_aug([(int(im.shape[0]), int(im.shape[1])) for im in images])
         host, n = self.pack(images)
         src = host[:n].to(self.engine.device if hasattr(self.engine, "device") else "cuda", non_blocking=True)
         if src.is_cuda:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(src.device))
             self._ring[self._slot][1] = ev
-        return self.engine.preprocess(src, descs, self.size, self.mean, self.std, self.out_dtype, want_u8)
+        if augs is None and not self.fill_outside:
+            return self.engine.preprocess(src, descs, self.size, self.mean, self.std, self.out_dtype, want_u8)
+        return self.engine.preprocess_aug(src, descs, augs, self.size, self.mean, self.std, self.out_dtype, want_u8, self.fill_outside)
+
+
+def build_device_transform(cfg, engine, train: bool = True, **kwargs) -> DeviceTransform:
+    """The transform Dassl's `build_transform(cfg, is_train=train)` would build from INPUT.TRANSFORMS and its parameters (same key names
+    and defaults), on the device.  Testing is Dassl's Resize(size) + CenterCrop(size) + normalize; the names are checked either way."""
+    inp = cfg.INPUT
+    return DeviceTransform(engine, size=int(inp.SIZE[0]), train=train, center_crop=True, transforms=check_transforms(inp.TRANSFORMS),
+                           colorjitter=(inp.COLORJITTER_B, inp.COLORJITTER_C, inp.COLORJITTER_S, inp.COLORJITTER_H), rgs_p=inp.RGS_P,
+                           crop_padding=inp.CROP_PADDING, cutout_n=inp.CUTOUT_N, cutout_len=inp.CUTOUT_LEN, **kwargs)

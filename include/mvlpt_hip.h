@@ -676,6 +676,68 @@ int mvlpt_preprocess_aug(void* handle, const uint8_t* src, int64_t src_bytes, co
                          int B, int out_h, int out_w, int fill_outside, const float* mean, const float* std, void* out, int out_dtype,
                          uint8_t* out_u8, mvlpt_stream_t stream);
 
+/* ---- baseline JPEG decode on the device (row f3c of the scope table) -----------------------------------------
+ * Compressed files -> the packed uint8 HWC RGB buffer mvlpt_preprocess(_aug) reads (MvlptImageDesc.offset), bit-identical to
+ * Pillow's `Image.open(f).convert("RGB")` (libjpeg-turbo: Huffman decode, jidctint "islow" IDCT, fancy chroma upsampling, 16-bit
+ * fixed-point YCbCr -> RGB; EXIF orientation is not applied, as Pillow does not on open).
+ * The device decodes one SOF0 frame (baseline, Huffman, 8-bit samples and tables) with one interleaved scan of one component
+ * (grayscale, replicated to R = G = B) or of three taken as YCbCr (JFIF APP0 present or component ids 1, 2, 3; no Adobe APP14), luma
+ * sampled 1x1, 2x1 or 2x2 with 1x1 chroma, with or without restart intervals.  Every other file is found by the host parser before
+ * anything is launched and left to the caller (MVLPT_JPEG_ROUTE_*): nothing is emulated. */
+enum {
+  MVLPT_JPEG_ROUTE_DEVICE = 0,
+  MVLPT_JPEG_ROUTE_MALFORMED = 1,   /* no SOI, a marker where none may stand, a marker length past the file, no frame / scan header */
+  MVLPT_JPEG_ROUTE_FRAME = 2,       /* not SOF0 / 8 bit: progressive, arithmetic, extended (SOF1), lossless, 12-bit */
+  MVLPT_JPEG_ROUTE_SCANS = 3,       /* several scans, a scan that does not interleave all components, DNL */
+  MVLPT_JPEG_ROUTE_COLOUR = 4,      /* CMYK / YCCK, Adobe APP14, RGB-tagged components */
+  MVLPT_JPEG_ROUTE_SAMPLING = 5,    /* other sampling factors (4:4:0, 4:1:1, ...) */
+  MVLPT_JPEG_ROUTE_TABLES = 6,      /* a table the scan names is missing, 16-bit, outside baseline's ids, or not a prefix code */
+  MVLPT_JPEG_ROUTE_RESTART = 7,     /* RSTn out of sequence, or not ceil(MCUs / DRI) - 1 of them */
+  MVLPT_JPEG_ROUTE_SIZE = 8         /* an empty image, one above 2^26 pixels, or a file of 2 GiB or more */
+};
+/* bits of a status word > 0 (corrupt entropy data; the segment it was met in stops, its remaining coefficients are 0) */
+#define MVLPT_JPEG_ST_BAD_CODE 1     /* the next 16 bits match no Huffman code */
+#define MVLPT_JPEG_ST_COEF_INDEX 2   /* a run carries the coefficient index past 63 */
+#define MVLPT_JPEG_ST_ENDED_EARLY 4  /* the segment's bytes ran out before its MCUs did (zeros were fed) */
+#define MVLPT_JPEG_ST_BAD_SIZE 8     /* a DC size above 15 */
+typedef struct MvlptJpegInfo {
+  int32_t height, width, components;   /* as the frame header gives them; 0 when it was not reached */
+  int32_t h_samp, v_samp;              /* sampling factors of the first component */
+  int32_t restart_interval;            /* DRI, in MCUs; 0: none */
+  int32_t n_segments;                  /* restart segments of the scan (1 without DRI); 0 unless route == MVLPT_JPEG_ROUTE_DEVICE */
+  int32_t route;                       /* MVLPT_JPEG_ROUTE_* */
+} MvlptJpegInfo;
+/* Host only, no handle, no device: reads the headers of the n bytes at `bytes`, never outside [0, n), and delimits the restart segments. */
+int mvlpt_jpeg_probe(const uint8_t* bytes, int64_t n, MvlptJpegInfo* info);
+/* Bytes of engine workspace a decode of these B files takes (coefficient blocks, component planes, descriptors and tables of the files
+ * whose route is DEVICE).  The engine reserves it itself (grow-only); the figure is for planning. */
+int mvlpt_jpeg_workspace_bytes(const MvlptJpegInfo* infos, int B, int64_t* bytes);
+/* Decodes B files.  src_host / src_dev: the same compressed bytes in host and device memory, file b at [src_offsets[b], + src_sizes[b])
+ * of both (host arrays).  The host parses, uploads table sets, segment and image descriptors and the initial status on `stream`, and
+ * launches entropy decode, IDCT and upsample / colour for the files whose route is DEVICE; file b's pixels go to dst_dev +
+ * dst_offsets[b] as uint8 [height, width, 3].  The others are skipped (the caller decodes them and writes their pixels there).
+ * status_dev: int32 [B] on the device: 0 decoded, > 0 corrupt entropy data (MVLPT_JPEG_ST_*; the pixels are what the damaged data
+ * gives, in bounds), -1 left to the host.  Enqueue-only: nothing is read back.  Everything the device indexes is checked on the host
+ * first: a descriptor that would reach outside [0, dst_bytes), a negative offset or size, or B > 16384 returns MVLPT_ERR_ARG with
+ * nothing launched.  B == 0 returns 0. */
+int mvlpt_jpeg_decode(void* handle, const uint8_t* src_host, const uint8_t* src_dev, const int64_t* src_offsets, const int64_t* src_sizes,
+                      int B, uint8_t* dst_dev, int64_t dst_bytes, const int64_t* dst_offsets, int32_t* status_dev, mvlpt_stream_t stream);
+/* The three stages on their own (kernel-level tests; handle-free, enqueue-only).
+ *   mvlpt_op_jpeg_entropy: one file whose route is DEVICE (MVLPT_ERR_UNSUPPORTED otherwise), n bytes at file_host and file_dev.  coefs:
+ *     device int16 [coef_blocks][64], natural order, component after component, each raster over its whole-MCU block grid; zeroed and
+ *     filled by the call; coef_blocks must be the file's block count.  ws / ws_bytes: device scratch for descriptor, tables and segment
+ *     table, at least 4096 + 8 * n_segments bytes.  status_dev: one int32.
+ *   mvlpt_op_jpeg_idct: coefs int16 [n_blocks][64] x quant uint8 [64] (natural order, device) -> plane uint8 [n_blocks / blocks_w * 8]
+ *     [blocks_w * 8]; n_blocks % blocks_w == 0; plane 8-byte aligned.
+ *   mvlpt_op_jpeg_colour: planes of `components` (1 or 3) components at planes + plane_off[c] with pitch plane_w[c] (host arrays; luma at
+ *     least height x width, chroma at least ceil(height / vs) x ceil(width / hs)), luma factors hs x vs in {1x1, 2x1, 2x2} -> dst uint8
+ *     [height, width, 3]. */
+int mvlpt_op_jpeg_entropy(const uint8_t* file_host, int64_t n, const uint8_t* file_dev, void* ws, int64_t ws_bytes, int16_t* coefs,
+                          int64_t coef_blocks, int32_t* status_dev, mvlpt_stream_t stream);
+int mvlpt_op_jpeg_idct(const int16_t* coefs, const uint8_t* quant, int n_blocks, int blocks_w, uint8_t* plane, mvlpt_stream_t stream);
+int mvlpt_op_jpeg_colour(const uint8_t* planes, const int64_t* plane_off, const int32_t* plane_w, int components, int hs, int vs, int height,
+                         int width, uint8_t* dst, mvlpt_stream_t stream);
+
 /* ---- per-kernel timing with HIP events on the launch stream (bench.py's roofline leg) --------------------- */
 typedef struct MvlptKernelStat {
   char name[32];

@@ -58,6 +58,17 @@ class MvlptAugmentDesc(C.Structure):
                 ("grayscale", C.c_int32), ("n_holes", C.c_int32), ("hole", (C.c_int32 * 4) * AUG_MAX_HOLES)]
 
 
+# MVLPT_JPEG_ROUTE_*: who decodes a file (0: the device), and the bits of a status word > 0 (MVLPT_JPEG_ST_*)
+(JPEG_ROUTE_DEVICE, JPEG_ROUTE_MALFORMED, JPEG_ROUTE_FRAME, JPEG_ROUTE_SCANS, JPEG_ROUTE_COLOUR, JPEG_ROUTE_SAMPLING, JPEG_ROUTE_TABLES,
+ JPEG_ROUTE_RESTART, JPEG_ROUTE_SIZE) = range(9)
+JPEG_ST_BAD_CODE, JPEG_ST_COEF_INDEX, JPEG_ST_ENDED_EARLY, JPEG_ST_BAD_SIZE = 1, 2, 4, 8
+JPEG_MAX_BATCH = 16384
+
+
+class MvlptJpegInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("height", "width", "components", "h_samp", "v_samp", "restart_interval", "n_segments", "route")]
+
+
 OPTIM_SGD, OPTIM_ADAM, OPTIM_ADAMW = 0, 1, 2
 OPTIM_MAX_SEGS = 1024   # MVLPT_OPTIM_MAX_SEGS
 
@@ -181,6 +192,12 @@ SIGNATURES = {
     "mvlpt_preprocess": (_i, [_vp, _vp, C.c_int64, C.POINTER(MvlptImageDesc), _i, _i, _i, C.POINTER(_f), C.POINTER(_f), _vp, _i, _vp, _vp]),
     "mvlpt_preprocess_aug": (_i, [_vp, _vp, C.c_int64, C.POINTER(MvlptImageDesc), C.POINTER(MvlptAugmentDesc), _i, _i, _i, _i,
                                   C.POINTER(_f), C.POINTER(_f), _vp, _i, _vp, _vp]),
+    "mvlpt_jpeg_probe": (_i, [_vp, C.c_int64, C.POINTER(MvlptJpegInfo)]),
+    "mvlpt_jpeg_workspace_bytes": (_i, [C.POINTER(MvlptJpegInfo), _i, C.POINTER(C.c_int64)]),
+    "mvlpt_jpeg_decode": (_i, [_vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _i, _vp, C.c_int64, C.POINTER(C.c_int64), _vp, _vp]),
+    "mvlpt_op_jpeg_entropy": (_i, [_vp, C.c_int64, _vp, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp]),
+    "mvlpt_op_jpeg_idct": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "mvlpt_op_jpeg_colour": (_i, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _vp, _vp]),
     "mvlpt_profile_begin": (_i, [_vp, _i]),
     "mvlpt_profile_pause": (_i, [_vp, _i]),
     "mvlpt_profile_end": (_i, [_vp, C.POINTER(MvlptKernelStat), _i]),

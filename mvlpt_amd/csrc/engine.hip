@@ -26,6 +26,7 @@
 
 #include "../../include/mvlpt_hip.h"
 #include "kernels.h"
+#include "jpeg_core.h"
 
 using namespace mvlpt;
 
@@ -221,7 +222,9 @@ struct Engine {
   // token embedding [vocab, text_width] fp32: kept only when the caller loads it (mvlpt_text_encode_tokens reads it)
   float* tok_emb = nullptr; int vocab = 0;
   std::vector<void*> owned;               // every weight allocation (freed in destroy)
-  DevBuf vis_ws, txt_ws, head_ws, ce_ws, tmp, pp_ws, near_ws;
+  DevBuf vis_ws, txt_ws, head_ws, ce_ws, tmp, pp_ws, near_ws, jpeg_ws;
+  std::vector<uint8_t> jpeg_meta_host;    // mvlpt_jpeg_decode: descriptors, table sets and segment table (source of the asynchronous upload)
+  std::vector<int32_t> jpeg_status_host;  // ... and the initial status words
   TowerState vs, ts;
   // vision fwd extras (carved from vis_ws)
   int vB = 0, v_nvpt = 0, v_ndeep = 0;
@@ -2643,6 +2646,184 @@ int mvlpt_preprocess_aug(void* h, const uint8_t* src, int64_t src_bytes, const M
   else HIPCHK(E, hipMemsetAsync(augs_dev, 0, sizeof(PpAug) * (size_t)B, s));
   HIPCHK(E, launch_preprocess_aug(src, descs_dev, augs_dev, B, max_crop_h, ks_max, out_h, out_w, tables, table_stride, tmp, tmp_stride, win,
                                   mean, stdv, out, out_dtype, s));
+  return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ JPEG decode
+namespace {
+static_assert(sizeof(MvlptJpegInfo) == sizeof(jpeg::Info), "info layouts must match");
+static_assert(MVLPT_JPEG_ROUTE_SIZE == jpeg::ROUTE_SIZE && MVLPT_JPEG_ST_BAD_SIZE == jpeg::ST_BAD_SIZE, "route / status codes must match");
+constexpr int JPEG_MAX_BATCH = 16384;            // images and 3 x planes ride on grid.y
+
+// where the parts of a decode's workspace lie: [image descs | plane descs | table sets | segment table] (uploaded as one block), then
+// the coefficient blocks and the component planes
+struct JpegLayout {
+  size_t descs = 0, planes = 0, tables = 0, segs = 0, meta = 0, coefs = 0, pix = 0, total = 0;
+  JpegLayout(size_t n_images, size_t n_segs, int64_t coef_blocks, int64_t plane_bytes) {
+    descs = 0;
+    planes = descs + align256(n_images * sizeof(jpeg::ImgDesc));
+    tables = planes + align256(3 * n_images * sizeof(jpeg::PlaneDesc));
+    segs = tables + align256(n_images * sizeof(jpeg::Tables));
+    meta = segs + align256(n_segs * sizeof(jpeg::Seg));
+    coefs = meta;
+    pix = coefs + align256((size_t)coef_blocks * 128);
+    total = pix + align256((size_t)plane_bytes);
+  }
+};
+}  // namespace
+
+extern "C" {
+
+int mvlpt_jpeg_probe(const uint8_t* bytes, int64_t n, MvlptJpegInfo* info) {
+  if (!bytes || !info || n < 0) { g_create_err = "jpeg_probe: null argument or negative size"; return MVLPT_ERR_ARG; }
+  jpeg::Parsed P;
+  jpeg::parse(bytes, (size_t)n, &P);
+  if (P.info.route != jpeg::ROUTE_DEVICE) P.info.n_segments = 0;
+  memcpy(info, &P.info, sizeof(*info));
+  return 0;
+}
+
+int mvlpt_jpeg_workspace_bytes(const MvlptJpegInfo* infos, int B, int64_t* bytes) {
+  if (!bytes || B < 0 || (B > 0 && !infos)) { g_create_err = "jpeg_workspace_bytes: null argument or negative batch"; return MVLPT_ERR_ARG; }
+  size_t n_images = 0, n_segs = 0;
+  int64_t blocks = 0, pix = 0;
+  for (int b = 0; b < B; ++b) {
+    if (infos[b].route != MVLPT_JPEG_ROUTE_DEVICE) continue;
+    jpeg::Info f;
+    memcpy(&f, &infos[b], sizeof(f));
+    const bool ok = f.height > 0 && f.width > 0 && (int64_t)f.height * f.width <= jpeg::MAX_PIXELS && (f.components == 1 || f.components == 3) &&
+                    f.h_samp >= 1 && f.h_samp <= 4 && f.v_samp >= 1 && f.v_samp <= 4 && f.n_segments >= 1;
+    if (!ok) { g_create_err = "jpeg_workspace_bytes: info " + std::to_string(b) + " is not one mvlpt_jpeg_probe returns"; return MVLPT_ERR_ARG; }
+    const jpeg::Geom g = jpeg::geometry(f);
+    ++n_images; n_segs += (size_t)f.n_segments; blocks += g.total_blocks; pix += g.total_plane_bytes;
+  }
+  *bytes = (int64_t)JpegLayout(n_images, n_segs, blocks, pix).total;
+  return 0;
+}
+
+int mvlpt_jpeg_decode(void* h, const uint8_t* src_host, const uint8_t* src_dev, const int64_t* src_offsets, const int64_t* src_sizes, int B,
+                      uint8_t* dst_dev, int64_t dst_bytes, const int64_t* dst_offsets, int32_t* status_dev, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E) return MVLPT_ERR_ARG;
+  if (B < 0 || B > JPEG_MAX_BATCH) return fail(E, MVLPT_ERR_ARG, "jpeg_decode: batch negative or above 16384");
+  if (B == 0) return 0;
+  if (!src_host || !src_dev || !src_offsets || !src_sizes || !dst_dev || !dst_offsets || !status_dev || dst_bytes < 0)
+    return fail(E, MVLPT_ERR_ARG, "jpeg_decode: null argument");
+  std::vector<jpeg::Parsed> parsed((size_t)B);
+  size_t n_images = 0, n_segs = 0;
+  int64_t blocks = 0, pix = 0;
+  for (int b = 0; b < B; ++b) {
+    if (src_offsets[b] < 0 || src_sizes[b] < 0) return fail(E, MVLPT_ERR_ARG, "jpeg_decode: negative source offset or size at " + std::to_string(b));
+    jpeg::parse(src_host + src_offsets[b], (size_t)src_sizes[b], &parsed[b]);
+    const jpeg::Info& f = parsed[b].info;
+    if (f.route != jpeg::ROUTE_DEVICE) continue;
+    if (dst_offsets[b] < 0 || dst_offsets[b] > dst_bytes || (int64_t)f.height * f.width * 3 > dst_bytes - dst_offsets[b])
+      return fail(E, MVLPT_ERR_ARG, "jpeg_decode: image " + std::to_string(b) + " (" + std::to_string(f.height) + " x " + std::to_string(f.width) +
+                                        ") does not fit dst_bytes at its offset");
+    const jpeg::Geom g = jpeg::geometry(f);
+    ++n_images; n_segs += parsed[b].segs.size(); blocks += g.total_blocks; pix += g.total_plane_bytes;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  E->jpeg_status_host.assign((size_t)B, -1);
+  for (int b = 0; b < B; ++b) if (parsed[b].info.route == jpeg::ROUTE_DEVICE) E->jpeg_status_host[b] = 0;
+  HIPCHK(E, hipMemcpyAsync(status_dev, E->jpeg_status_host.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+  if (n_images == 0) return 0;
+  const JpegLayout lay(n_images, n_segs, blocks, pix);
+  HIPCHK(E, E->jpeg_ws.reserve(lay.total));
+  E->jpeg_meta_host.assign(lay.meta, 0);
+  uint8_t* mh = E->jpeg_meta_host.data();
+  jpeg::ImgDesc* descs = (jpeg::ImgDesc*)(mh + lay.descs);
+  jpeg::PlaneDesc* planes = (jpeg::PlaneDesc*)(mh + lay.planes);
+  jpeg::Tables* tables = (jpeg::Tables*)(mh + lay.tables);
+  jpeg::Seg* segs = (jpeg::Seg*)(mh + lay.segs);
+  int n_tables = 0, n_planes = 0, max_blocks = 0;
+  size_t k = 0, seg_at = 0;
+  int64_t coef_at = 0, pix_at = 0;
+  long long max_groups = 0;
+  for (int b = 0; b < B; ++b) {
+    const jpeg::Parsed& P = parsed[b];
+    if (P.info.route != jpeg::ROUTE_DEVICE) continue;
+    if (n_tables == 0 || memcmp(&tables[n_tables - 1], &P.tables, sizeof(jpeg::Tables)) != 0) tables[n_tables++] = P.tables;   // shared with the previous image when equal
+    const jpeg::ImgDesc d = jpeg::describe(P, src_offsets[b], dst_offsets[b], coef_at, pix_at, (int)seg_at, n_tables - 1, b);
+    descs[k++] = d;
+    for (int c = 0; c < d.ncomp; ++c) {
+      jpeg::PlaneDesc& p = planes[n_planes++];
+      p.coef_off = d.coef_off[c]; p.plane_off = d.plane_off[c];
+      p.n_blocks = d.blocks_w[c] * (d.plane_h[c] / 8); p.blocks_w = d.blocks_w[c]; p.plane_w = d.plane_w[c];
+      p.tables = d.tables; p.tq = d.tq[c]; p.reserved = 0;
+      max_blocks = std::max(max_blocks, p.n_blocks);
+    }
+    for (const jpeg::Seg& sg : P.segs) segs[seg_at++] = sg;
+    const jpeg::Geom g = jpeg::geometry(P.info);
+    coef_at += g.total_blocks; pix_at += g.total_plane_bytes;
+    max_groups = std::max(max_groups, (long long)((d.width + 3) >> 2) * d.height);
+  }
+  char* base = (char*)E->jpeg_ws.p;
+  int16_t* coefs_dev = (int16_t*)(base + lay.coefs);
+  uint8_t* pix_dev = (uint8_t*)(base + lay.pix);
+  HIPCHK(E, hipMemcpyAsync(base, mh, lay.meta, hipMemcpyHostToDevice, s));
+  HIPCHK(E, hipMemsetAsync(coefs_dev, 0, (size_t)blocks * 128, s));
+  HIPCHK(E, launch_jpeg_entropy(src_dev, (const jpeg::ImgDesc*)(base + lay.descs), (const jpeg::Tables*)(base + lay.tables),
+                                (const jpeg::Seg*)(base + lay.segs), (int)n_images, coefs_dev, status_dev, s));
+  HIPCHK(E, launch_jpeg_idct((const jpeg::PlaneDesc*)(base + lay.planes), n_planes, max_blocks, (const jpeg::Tables*)(base + lay.tables), coefs_dev,
+                             pix_dev, s));
+  HIPCHK(E, launch_jpeg_colour((const jpeg::ImgDesc*)(base + lay.descs), (int)n_images, max_groups, pix_dev, dst_dev, s));
+  return 0;
+}
+
+int mvlpt_op_jpeg_entropy(const uint8_t* file_host, int64_t n, const uint8_t* file_dev, void* ws, int64_t ws_bytes, int16_t* coefs,
+                          int64_t coef_blocks, int32_t* status_dev, mvlpt_stream_t stream) {
+  if (!file_host || !file_dev || !ws || !coefs || !status_dev || n < 0) { g_create_err = "op_jpeg_entropy: null argument"; return MVLPT_ERR_ARG; }
+  static thread_local jpeg::Parsed P;
+  static thread_local std::vector<uint8_t> host;
+  jpeg::parse(file_host, (size_t)n, &P);
+  if (P.info.route != jpeg::ROUTE_DEVICE) { g_create_err = "op_jpeg_entropy: route " + std::to_string(P.info.route) + ", not a file the device decodes"; return MVLPT_ERR_UNSUPPORTED; }
+  const jpeg::Geom g = jpeg::geometry(P.info);
+  const size_t need = 4096 + 8 * P.segs.size();
+  if (coef_blocks != g.total_blocks || ws_bytes < (int64_t)need || ((uintptr_t)ws & 15)) {
+    g_create_err = "op_jpeg_entropy: coef_blocks must be " + std::to_string(g.total_blocks) + " and ws hold " + std::to_string(need) + " bytes, 16-byte aligned";
+    return MVLPT_ERR_ARG;
+  }
+  static_assert(sizeof(jpeg::ImgDesc) <= 512 && sizeof(jpeg::Tables) <= 3584, "the op's scratch layout");
+  host.assign(need, 0);
+  const jpeg::ImgDesc d = jpeg::describe(P, 0, 0, 0, 0, 0, 0, 0);
+  memcpy(host.data(), &d, sizeof(d));
+  memcpy(host.data() + 512, &P.tables, sizeof(P.tables));
+  memcpy(host.data() + 4096, P.segs.data(), 8 * P.segs.size());
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)ws;
+  OPCHK(hipMemcpyAsync(base, host.data(), need, hipMemcpyHostToDevice, s));
+  OPCHK(hipMemsetAsync(coefs, 0, (size_t)coef_blocks * 128, s));
+  OPCHK(launch_jpeg_entropy(file_dev, (const jpeg::ImgDesc*)base, (const jpeg::Tables*)(base + 512), (const jpeg::Seg*)(base + 4096), 1, coefs,
+                            status_dev, s));
+  return 0;
+}
+
+int mvlpt_op_jpeg_idct(const int16_t* coefs, const uint8_t* quant, int n_blocks, int blocks_w, uint8_t* plane, mvlpt_stream_t stream) {
+  if (!coefs || !quant || !plane || n_blocks <= 0 || blocks_w <= 0 || n_blocks % blocks_w || blocks_w > (1 << 20) || ((uintptr_t)plane & 7)) {
+    g_create_err = "op_jpeg_idct: null / misaligned pointer, or n_blocks is not a positive multiple of blocks_w"; return MVLPT_ERR_ARG; }
+  jpeg::PlaneDesc p = {};
+  p.n_blocks = n_blocks; p.blocks_w = blocks_w; p.plane_w = blocks_w * 8;
+  OPCHK(launch_jpeg_idct_one(p, quant, coefs, plane, (hipStream_t)stream));
+  return 0;
+}
+
+int mvlpt_op_jpeg_colour(const uint8_t* planes, const int64_t* plane_off, const int32_t* plane_w, int components, int hs, int vs, int height,
+                         int width, uint8_t* dst, mvlpt_stream_t stream) {
+  const bool samp_ok = (hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2);
+  if (!planes || !plane_off || !plane_w || !dst || (components != 1 && components != 3) || !samp_ok || height <= 0 || width <= 0 ||
+      (int64_t)height * width > jpeg::MAX_PIXELS) { g_create_err = "op_jpeg_colour: null / invalid argument"; return MVLPT_ERR_ARG; }
+  jpeg::ImgDesc d;
+  memset(&d, 0, sizeof(d));
+  d.width = width; d.height = height; d.ncomp = components; d.hs = components == 1 ? 1 : hs; d.vs = components == 1 ? 1 : vs;
+  for (int c = 0; c < components; ++c) {
+    const int need_w = c == 0 ? width : (width + d.hs - 1) / d.hs;
+    if (plane_off[c] < 0 || plane_w[c] < need_w) { g_create_err = "op_jpeg_colour: a plane is narrower than its component"; return MVLPT_ERR_ARG; }
+    d.plane_off[c] = plane_off[c]; d.plane_w[c] = plane_w[c];
+  }
+  OPCHK(launch_jpeg_colour_one(d, planes, dst, (hipStream_t)stream));
   return 0;
 }
 

@@ -237,6 +237,20 @@ hipError_t launch_preprocess_aug(const uint8_t* src, const PpDesc* descs_dev, co
                                  int out_h, int out_w, int32_t* tables, size_t table_stride, uint8_t* tmp, size_t tmp_stride, uint8_t* win,
                                  const float* mean, const float* stdv, void* out, int out_dtype, hipStream_t s);
 
+// ---------------------------------------------------------------- JPEG decode (jpeg.hip; the structures are in jpeg_core.h)
+namespace jpeg { struct ImgDesc; struct PlaneDesc; struct Tables; struct Seg; }
+// entropy stage of n_images images: coefficient blocks (int16 [64], natural order; `coefs` zeroed by the caller) and status[d.index]
+hipError_t launch_jpeg_entropy(const uint8_t* src, const jpeg::ImgDesc* descs_dev, const jpeg::Tables* tables_dev, const jpeg::Seg* segs_dev,
+                               int n_images, int16_t* coefs, int32_t* status, hipStream_t s);
+// dequantise + IDCT of every component plane (max_blocks: the largest n_blocks among them)
+hipError_t launch_jpeg_idct(const jpeg::PlaneDesc* planes_dev, int n_planes, int max_blocks, const jpeg::Tables* tables_dev,
+                            const int16_t* coefs, uint8_t* planes, hipStream_t s);
+hipError_t launch_jpeg_idct_one(const jpeg::PlaneDesc& p, const uint8_t* quant_dev, const int16_t* coefs, uint8_t* plane, hipStream_t s);
+// upsample + colour into dst + d.dst_off, packed HWC RGB (max_groups: the largest ceil(width / 4) * height)
+hipError_t launch_jpeg_colour(const jpeg::ImgDesc* descs_dev, int n_images, long long max_groups, const uint8_t* planes, uint8_t* dst,
+                              hipStream_t s);
+hipError_t launch_jpeg_colour_one(const jpeg::ImgDesc& d, const uint8_t* planes, uint8_t* dst, hipStream_t s);
+
 // ---------------------------------------------------------------- glue
 hipError_t launch_cast_f32_to16(int dtype, const float* in, void* out, size_t n, const float* scale_dev, hipStream_t s);
 // fp32 [rows,d] (* scale_dev[0]) -> 16-bit pair [rows, 2d] = [hi | lo]

@@ -240,6 +240,26 @@ class DeviceTransform:
             return self.engine.preprocess(src, descs, self.size, self.mean, self.std, self.out_dtype, want_u8)
         return self.engine.preprocess_aug(src, descs, augs, self.size, self.mean, self.std, self.out_dtype, want_u8, self.fill_outside)
 
+    def describe_encoded(self, blobs: Sequence):
+        """(probe results, (height, width) per file, image descriptors, augmentation descriptors or None) for JPEG files: the sizes come
+        from the frame headers, and the random parameters are drawn as `__call__` draws them for decoded images of those sizes."""
+        from . import jpeg
+        infos = [jpeg.probe(b) for b in blobs]
+        shapes, _ = jpeg.shapes_of(blobs, infos)
+        descs, augs, _ = self.describe_aug(shapes)
+        return infos, shapes, descs, augs
+
+    def from_encoded(self, blobs: Sequence, want_u8: bool = False, check: bool = True):
+        """`__call__` for a list of JPEG files (bytes): they are decoded on the device (mvlpt_amd.jpeg.decode_batch; Pillow for the files
+        the device does not take), and the same generator state gives the batch `__call__` gives for the Pillow-decoded arrays, bit for
+        bit.  check=False leaves the decode status unread (no synchronisation; corrupt files keep the device's pixels)."""
+        from . import jpeg
+        infos, _, descs, augs = self.describe_encoded(blobs)
+        src, _, _, _ = jpeg.decode_batch(self.engine, blobs, check=check, infos=infos)
+        if augs is None and not self.fill_outside:
+            return self.engine.preprocess(src, descs, self.size, self.mean, self.std, self.out_dtype, want_u8)
+        return self.engine.preprocess_aug(src, descs, augs, self.size, self.mean, self.std, self.out_dtype, want_u8, self.fill_outside)
+
 
 def build_device_transform(cfg, engine, train: bool = True, **kwargs) -> DeviceTransform:
     """The transform Dassl's `build_transform(cfg, is_train=train)` would build from INPUT.TRANSFORMS and its parameters (same key names

@@ -37,6 +37,9 @@ class CfgNode(dict):
                 elif isinstance(old, list) and old and isinstance(old[0], str):
                     import json
                     val = [str(x) for x in json.loads(val)]      # a list of strings (TRAINER.ZSCLIP.TEMPLATES) comes as JSON
+                elif key == "DATASET.SOURCES":
+                    import json
+                    val = [[str(x) for x in row] for row in json.loads(val)]      # JSON: [["task", "split.json or empty", "folder"], ...]
                 elif isinstance(old, (list, tuple)):
                     val = type(old)(int(x) for x in val.strip("()[]").split(","))
                 else:
@@ -54,7 +57,11 @@ def get_cfg_default() -> CfgNode:
     # launcher's --transforms).  On the command line the list comes as JSON: INPUT.TRANSFORMS '["random_crop", "random_flip", "cutout"]'
     cfg.INPUT = CN(SIZE=(224, 224), TRANSFORMS=["random_resized_crop", "random_flip", "normalize"], COLORJITTER_B=0.4, COLORJITTER_C=0.4,
                    COLORJITTER_S=0.4, COLORJITTER_H=0.1, RGS_P=0.2, CROP_PADDING=4, CUTOUT_N=1, CUTOUT_LEN=16)
-    cfg.DATALOADER = CN(TRAIN_X=CN(BATCH_SIZE=32), TEST=CN(BATCH_SIZE=100), NUM_WORKERS=8)
+    # NUM_WORKERS: host threads of mvlpt_amd.data (file reads, header probes, Pillow decodes), at most 16.  Not in the reference:
+    # RESIDENT_BYTES, the budget for splits kept decoded on the device (train, val, test in that order; 16 GiB covers ImageNet 16-shot,
+    # 16 000 images of about 0.5 MB; 0: every split streams), and DECODE, "device" (mvlpt_jpeg_decode, Pillow for the files it does not
+    # take) or "host" (Pillow for every file).
+    cfg.DATALOADER = CN(TRAIN_X=CN(BATCH_SIZE=32), TEST=CN(BATCH_SIZE=100), NUM_WORKERS=8, RESIDENT_BYTES=16 * 2 ** 30, DECODE="device")
     # configs/trainers/MVLPT/vit_b16.yaml:15-22 + Dassl optimizer defaults
     cfg.OPTIM = CN(NAME="sgd", LR=0.002, MAX_EPOCH=200, MOMENTUM=0.9, WEIGHT_DECAY=5e-4, SGD_DAMPNING=0.0,
                    SGD_NESTEROV=False, LR_SCHEDULER="cosine", WARMUP_EPOCH=1, WARMUP_TYPE="constant",
@@ -99,6 +106,9 @@ def get_cfg_default() -> CfgNode:
     # mvlpt_amd.zsclip (--trainer ZeroshotCLIP / ZeroshotCLIP2).  Not a reference key: the reference picks its templates from tables in
     # its own source by DATASET.NAME; here they are configuration.  ZeroshotCLIP takes exactly one, ZeroshotCLIP2 any number >= 1.
     cfg.TRAINER.ZSCLIP = CN(TEMPLATES=["a photo of a {}."])
+    # SOURCES (not in the reference, which has one reader module per dataset): [task name, CoOp split file or "", image folder] per dataset;
+    # non-empty, a trainer that is given no data manager builds mvlpt_amd.data.DeviceDataManager from it.  On the command line as JSON.
+    # SUBSAMPLE_CLASSES: all | base | new (train.py:117).
     cfg.DATASET = CN(NAME="synthetic", COOP=True, MULTITASK=False, MULTITASK_LABEL_PERTASK=False,
-                     MULTITASK_EVALKEY="average", NUM_SHOTS=16)
+                     MULTITASK_EVALKEY="average", NUM_SHOTS=16, SOURCES=[], SUBSAMPLE_CLASSES="all")
     return cfg

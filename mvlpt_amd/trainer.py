@@ -338,8 +338,12 @@ class TrainerX:
         return self.test()
 
     def end_of_epoch_loop(self):
-        """The loop left the loader (exhausted, hook break, exception): nothing of the look-ahead may survive it."""
+        """The loop left the loader (exhausted, hook break, exception): nothing of the look-ahead may survive it, and a loader with
+        reader threads (mvlpt_amd.data.DeviceLoader) joins them."""
         self.next_batch = None
+        close = getattr(getattr(self, "train_loader_x", None), "close", None)
+        if close is not None:
+            close()
 
     # hooks the concrete trainer provides
     def check_cfg(self, cfg):
@@ -480,6 +484,9 @@ class MVLPT(TrainerX):
         self.multi_task = self.cfg.DATASET.MULTITASK
         self.multi_task_label_pertask = self.cfg.DATASET.MULTITASK_LABEL_PERTASK
         dm = self._dm_arg
+        if dm is None and self.cfg.DATASET.SOURCES:
+            from .data import DeviceDataManager       # image files through the device input pipeline
+            dm = DeviceDataManager(self.cfg, rank=self.rank)
         if dm is None:
             raise ValueError("pass a data manager (e.g. SyntheticDataManager); dataset readers are out of scope")
         # the look-ahead lives in the loader (see LookAheadLoader): a plain `for batch in self.train_loader_x` pipelines
@@ -528,6 +535,14 @@ class MVLPT(TrainerX):
             dist_utils.broadcast_parameters(self.model.prompt_learner)   # identical prompts on every rank
         self.optim, self.sched = self.build_optim("prompt_learner", self.model.prompt_learner)   # NOTE: only the prompt learner (:869)
         self.scaler = None    # the HIP backward scales its 16-bit activation gradients internally
+        self.bind_data(self.model.engine)
+
+    def bind_data(self, engine):
+        """Dassl builds the loaders before the model, and the engine is born with the model: a data manager whose loaders run on the
+        engine (mvlpt_amd.data.DeviceDataManager) gets it here."""
+        bind = getattr(self.dm, "bind", None)
+        if bind is not None:
+            bind(engine)
 
     def forward_backward(self, batch):
         """trainers/mvlpt.py:910-951.  When the loop has read one batch ahead (`self.next_batch`, TrainerX.run_epoch) and

@@ -240,25 +240,40 @@ class DeviceTransform:
             return self.engine.preprocess(src, descs, self.size, self.mean, self.std, self.out_dtype, want_u8)
         return self.engine.preprocess_aug(src, descs, augs, self.size, self.mean, self.std, self.out_dtype, want_u8, self.fill_outside)
 
-    def describe_encoded(self, blobs: Sequence):
+    def describe_encoded(self, blobs: Sequence, infos=None, decoded=None):
         """(probe results, (height, width) per file, image descriptors, augmentation descriptors or None) for JPEG files: the sizes come
-        from the frame headers, and the random parameters are drawn as `__call__` draws them for decoded images of those sizes."""
+        from the frame headers, and the random parameters are drawn as `__call__` draws them for decoded images of those sizes.
+        infos / decoded: what `jpeg.probe` / `jpeg.shapes_of` gave for these files, when the caller has them already."""
         from . import jpeg
-        infos = [jpeg.probe(b) for b in blobs]
-        shapes, _ = jpeg.shapes_of(blobs, infos)
+        infos = [jpeg.probe(b) for b in blobs] if infos is None else infos
+        shapes, _ = jpeg.shapes_of(blobs, infos, decoded)
         descs, augs, _ = self.describe_aug(shapes)
         return infos, shapes, descs, augs
 
-    def from_encoded(self, blobs: Sequence, want_u8: bool = False, check: bool = True):
-        """`__call__` for a list of JPEG files (bytes): they are decoded on the device (mvlpt_amd.jpeg.decode_batch; Pillow for the files
-        the device does not take), and the same generator state gives the batch `__call__` gives for the Pillow-decoded arrays, bit for
-        bit.  check=False leaves the decode status unread (no synchronisation; corrupt files keep the device's pixels)."""
-        from . import jpeg
-        infos, _, descs, augs = self.describe_encoded(blobs)
-        src, _, _, _ = jpeg.decode_batch(self.engine, blobs, check=check, infos=infos)
+    def _run(self, src, descs, augs, want_u8):
         if augs is None and not self.fill_outside:
             return self.engine.preprocess(src, descs, self.size, self.mean, self.std, self.out_dtype, want_u8)
         return self.engine.preprocess_aug(src, descs, augs, self.size, self.mean, self.std, self.out_dtype, want_u8, self.fill_outside)
+
+    def from_encoded(self, blobs: Sequence, want_u8: bool = False, check: bool = True, infos=None, decoded=None):
+        """`__call__` for a list of JPEG files (bytes): they are decoded on the device (mvlpt_amd.jpeg.decode_batch; Pillow for the files
+        the device does not take), and the same generator state gives the batch `__call__` gives for the Pillow-decoded arrays, bit for
+        bit.  check=False leaves the decode status unread (no synchronisation; corrupt files keep the device's pixels).
+        infos / decoded ({index: pixels} of host-route files): host work a loader's threads have done already."""
+        from . import jpeg
+        infos, _, descs, augs = self.describe_encoded(blobs, infos, decoded)
+        src, _, _, _ = jpeg.decode_batch(self.engine, blobs, check=check, infos=infos, decoded=decoded)
+        return self._run(src, descs, augs, want_u8)
+
+    def from_resident(self, image_set, indices: Sequence[int], want_u8: bool = False):
+        """`__call__` for images that lie decoded in a resident device buffer (mvlpt_amd.data.ResidentImageSet: `buf`, `offsets`,
+        `shapes`): nothing is packed or uploaded but the descriptors, whose `offset` is the image's place in the set (64 bits), and the
+        whole set is the source of the one preprocess launch.  The same generator state draws what `__call__` draws for these images."""
+        indices = [int(i) for i in indices]
+        descs, augs, _ = self.describe_aug([image_set.shapes[i] for i in indices])
+        for d, i in zip(descs, indices):
+            d.offset = int(image_set.offsets[i])
+        return self._run(image_set.buf, descs, augs, want_u8)
 
 
 def build_device_transform(cfg, engine, train: bool = True, **kwargs) -> DeviceTransform:

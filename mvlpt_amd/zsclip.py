@@ -67,6 +67,7 @@ class ZeroshotCLIP(MVLPT):
         self.tokenized_prompts = tokenized
         self.clip_model = clip_model
         self.logit_scale_exp = float(clip_model.logit_scale.exp())
+        self.bind_data(clip_model.engine)
 
     @torch.no_grad()
     def model_inference(self, image, task=None):

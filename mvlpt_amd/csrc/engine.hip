@@ -197,13 +197,11 @@ struct Engine {
   int prec_mode = MVLPT_PREC_SPLIT_GRAD;
   int fold_mode = 2;    // LayerNorm folding: 0 off, 1 image tower, 2 both towers (MVLPT_LN_FOLD, mvlpt_set_ln_fold)
   int text_act_ckpt = 1;      // segments of the text tower's activation checkpointing (mvlpt_set_text_act_ckpt; 1: everything is saved)
-  int fold_min_rows = 1024;   // towers with fewer token rows keep the stand-alone LayerNorm (a handful of tiles: nothing to win).  4096 until round 6: the small-tile
-                              // consumer geometries were where the packed-fp32 hazard first showed (NOTES round 6); cfg1 (1 600 image rows): -1.5 %
+  int fold_min_rows = 1024;   // towers with fewer token rows keep the stand-alone LayerNorm (a handful of tiles: nothing to win)
   bool fold_ready = false;
   // packed residual stream: the fp16 image tower without prompts and without a backward carries x as hi (fp16, at the
   // same time the A operand behind every LayerNorm) + one byte instead of fp32 + a 16-bit copy.  MVLPT_RESID_PACKED / mvlpt_set_resid_packed
-  int resid_packed = 1;      // on (round 6): the rare 1e-3 glitch of round 5 was the packed-fp32 hazard in the tower entry, gone with the NOPK build
-                             // (0 / 20 000 towers under a concurrent text tower, profiles/r06_packed_stream_determinism.txt); MVLPT_RESID_PACKED=0: fp32 stream
+  int resid_packed = 1;      // MVLPT_RESID_PACKED=0: fp32 stream
   // mvlpt_set_vpt_dropout: [layers, B, n_vpt, d] masks of the visual prompt rows for the NEXT image_fwd (one-shot: the forward
   // validates the geometry, takes the setting over as v_mask — what ITS backward uses — and clears it, so a stale pointer never
   // reaches another forward or another user of the engine)
@@ -1006,18 +1004,22 @@ const char* mvlpt_version(void) { return "mvlpt_hip 0.1 (gfx950) src:" MVLPT_SRC
 
 const char* mvlpt_last_error(void* h) { return h ? ((Engine*)h)->err.c_str() : g_create_err.c_str(); }
 
-int mvlpt_create(const MvlptArch* a, void** handle) {
-  if (!a || !handle) return fail(nullptr, MVLPT_ERR_ARG, "null argument");
-  if (a->compute_dtype != MVLPT_DT_F16 && a->compute_dtype != MVLPT_DT_BF16)
-    return fail(nullptr, MVLPT_ERR_ARG, "compute_dtype must be MVLPT_DT_F16 or MVLPT_DT_BF16");
+// What mvlpt_create and mvlpt_create_resnet share.  arch_check: the transformer limits, in the order both entries report them.
+// vit = false (create_resnet): the ViT vision fields are 0, as that entry has checked, and put nothing in the way of the text tower's checks.
+static int arch_check(const MvlptArch* a, bool vit) {
   if (a->vision_width != a->vision_heads * 64 || a->text_width != a->text_heads * 64)
-    return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "head_dim must be 64 (CLIP ViT: heads = width // 64)");
+    return fail(nullptr, MVLPT_ERR_UNSUPPORTED, vit ? "head_dim must be 64 (CLIP ViT: heads = width // 64)" : "head_dim must be 64");
   if (a->vision_width % 128 || a->text_width % 128 || a->embed_dim % 64)
     return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "widths must be multiples of 128 and embed_dim of 64");
-  if (a->patch_size <= 0 || a->image_resolution % a->patch_size)
+  if (vit && (a->patch_size <= 0 || a->image_resolution % a->patch_size))
     return fail(nullptr, MVLPT_ERR_ARG, "image_resolution must be a multiple of patch_size");
-  if (a->vision_layers <= 0 || a->text_layers <= 0 || a->context_length <= 0)
+  if ((vit && a->vision_layers <= 0) || a->text_layers <= 0 || a->context_length <= 0)
     return fail(nullptr, MVLPT_ERR_ARG, "bad layer count / context length");
+  return 0;
+}
+// engine_new: the device probe, a handle with the environment's overrides and the text tower sized.  The ResNet tower has no packed
+// stream: its entry does not read MVLPT_RESID_PACKED.
+static int engine_new(const MvlptArch* a, bool read_resid_packed, Engine** out) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
     return fail(nullptr, MVLPT_ERR_HIP, "no HIP device visible: libmvlpt_hip needs an AMD GPU (there is no CPU fallback)");
@@ -1025,12 +1027,23 @@ int mvlpt_create(const MvlptArch* a, void** handle) {
   E->arch = *a; E->dt = a->compute_dtype;
   if (const char* v = getenv("MVLPT_SPLIT_LO8")) E->lo8 = atoi(v) != 0;
   if (const char* v = getenv("MVLPT_LN_FOLD")) E->fold_mode = atoi(v);
-  if (const char* v = getenv("MVLPT_RESID_PACKED")) E->resid_packed = atoi(v) ? 1 : 0;
+  if (const char* v = read_resid_packed ? getenv("MVLPT_RESID_PACKED") : nullptr) E->resid_packed = atoi(v) ? 1 : 0;
   if (const char* v = getenv("MVLPT_LN_FOLD_MIN_ROWS")) E->fold_min_rows = atoi(v) > 0 ? atoi(v) : 1;
-  E->vis.width = a->vision_width; E->vis.layers = a->vision_layers; E->vis.heads = a->vision_heads;
-  E->vis.blocks.resize(a->vision_layers);
   E->txt.width = a->text_width; E->txt.layers = a->text_layers; E->txt.heads = a->text_heads;
   E->txt.blocks.resize(a->text_layers);
+  *out = E;
+  return 0;
+}
+
+int mvlpt_create(const MvlptArch* a, void** handle) {
+  if (!a || !handle) return fail(nullptr, MVLPT_ERR_ARG, "null argument");
+  if (a->compute_dtype != MVLPT_DT_F16 && a->compute_dtype != MVLPT_DT_BF16)
+    return fail(nullptr, MVLPT_ERR_ARG, "compute_dtype must be MVLPT_DT_F16 or MVLPT_DT_BF16");
+  if (int rc = arch_check(a, true)) return rc;
+  Engine* E = nullptr;
+  if (int rc = engine_new(a, true, &E)) return rc;
+  E->vis.width = a->vision_width; E->vis.layers = a->vision_layers; E->vis.heads = a->vision_heads;
+  E->vis.blocks.resize(a->vision_layers);
   const int K = 3 * a->patch_size * a->patch_size;
   E->Kp = (K + 63) / 64 * 64;
   *handle = E;
@@ -1043,9 +1056,7 @@ int mvlpt_create_resnet(const MvlptArch* a, const MvlptResNetArch* rn, void** ha
     return fail(nullptr, MVLPT_ERR_ARG, "create_resnet: the ViT vision fields of MvlptArch must be 0");
   if (a->compute_dtype == MVLPT_DT_BF16) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "create_resnet: the ResNet tower computes in fp16 only");
   if (a->compute_dtype != MVLPT_DT_F16) return fail(nullptr, MVLPT_ERR_ARG, "compute_dtype must be MVLPT_DT_F16");
-  if (a->text_width != a->text_heads * 64) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "head_dim must be 64");
-  if (a->text_width % 128 || a->embed_dim % 64) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "widths must be multiples of 128 and embed_dim of 64");
-  if (a->text_layers <= 0 || a->context_length <= 0) return fail(nullptr, MVLPT_ERR_ARG, "bad layer count / context length");
+  if (int rc = arch_check(a, false)) return rc;
   if (rn->image_resolution <= 0 || rn->image_resolution % 32) return fail(nullptr, MVLPT_ERR_ARG, "create_resnet: image_resolution must be a positive multiple of 32");
   if (rn->width <= 0 || rn->width % 4) return fail(nullptr, MVLPT_ERR_ARG, "create_resnet: width must be a positive multiple of 4");
   for (int i = 0; i < 4; ++i) if (rn->layers[i] <= 0) return fail(nullptr, MVLPT_ERR_ARG, "create_resnet: every stage needs at least one block");
@@ -1055,16 +1066,8 @@ int mvlpt_create_resnet(const MvlptArch* a, const MvlptResNetArch* rn, void** ha
     return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "create_resnet: width must be a multiple of 16 and output_dim of 128");
   const int g = rn->image_resolution / 32;
   if (g * g + 1 > attnpool_max_tokens()) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "create_resnet: more than 145 attention-pool tokens");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail(nullptr, MVLPT_ERR_HIP, "no HIP device visible: libmvlpt_hip needs an AMD GPU (there is no CPU fallback)");
-  Engine* E = new Engine();
-  E->arch = *a; E->dt = a->compute_dtype;
-  if (const char* v = getenv("MVLPT_SPLIT_LO8")) E->lo8 = atoi(v) != 0;
-  if (const char* v = getenv("MVLPT_LN_FOLD")) E->fold_mode = atoi(v);
-  if (const char* v = getenv("MVLPT_LN_FOLD_MIN_ROWS")) E->fold_min_rows = atoi(v) > 0 ? atoi(v) : 1;
-  E->txt.width = a->text_width; E->txt.layers = a->text_layers; E->txt.heads = a->text_heads;
-  E->txt.blocks.resize(a->text_layers);
+  Engine* E = nullptr;
+  if (int rc = engine_new(a, false, &E)) return rc;
   ResNetW& R = E->rn;
   R.on = true; R.a = *rn;
   const int w = rn->width;
@@ -1689,9 +1692,9 @@ int mvlpt_text_encode_tokens(void* h, const int32_t* ids, int ld, int S, int L, 
 }
 
 int mvlpt_text_ensemble(const float* feats, int T, int C, int e, float* out, mvlpt_stream_t stream) {
-  if (!feats || !out || T <= 0 || C <= 0 || e <= 0) { g_create_err = "text_ensemble: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!feats || !out || T <= 0 || C <= 0 || e <= 0) return fail(nullptr, MVLPT_ERR_ARG, "text_ensemble: null/invalid argument");
   const hipError_t rc = launch_ensemble_features(feats, out, T, C, e, (hipStream_t)stream);
-  if (rc != hipSuccess) { g_create_err = std::string("text_ensemble: ") + hipGetErrorString(rc); return MVLPT_ERR_HIP; }
+  if (rc != hipSuccess) return fail(nullptr, MVLPT_ERR_HIP, std::string("text_ensemble: ") + hipGetErrorString(rc));
   return 0;
 }
 
@@ -1866,7 +1869,30 @@ int mvlpt_cross_entropy(void* h, const float* logits, const void* labels, int ki
 }
 
 // ------------------------------------------------------------------------------------------------ kernel-level ops
-#define OPCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { g_create_err = std::string(#call) + ": " + hipGetErrorString(_e); return MVLPT_ERR_HIP; } } while (0)
+#define OPCHK(call) HIPCHK(nullptr, call)
+
+#if defined(MVLPT_GEMM_TRACE) || defined(MVLPT_ATTN_TRACE)
+// debug builds: the timeline of one workgroup.  A zeroed device buffer of int64 records for the launch that follows, when the
+// environment variable names a file (ptr() is null otherwise); dump() waits for the stream and writes the records to that file.
+struct TraceCapture {
+  const char* path; hipStream_t s; size_t bytes; DevBuf buf; hipError_t err = hipSuccess;
+  TraceCapture(const char* env, size_t records, hipStream_t s_) : path(getenv(env)), s(s_), bytes(records * sizeof(long long)) {
+    if (!path) return;
+    err = buf.reserve(bytes);
+    if (err == hipSuccess) err = hipMemsetAsync(buf.p, 0, bytes, s);
+  }
+  long long* ptr() const { return (long long*)buf.p; }
+  hipError_t dump() {
+    if (!path) return hipSuccess;
+    std::vector<long long> h(bytes / sizeof(long long));
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(h.data(), buf.p, bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    if (FILE* f = fopen(path, "wb")) { fwrite(h.data(), 1, bytes, f); fclose(f); }
+    return hipSuccess;
+  }
+};
+#endif
 
 int mvlpt_op_gemm(int dtype, int epi, const void* A, const void* Bt, int M, int N, int K, const float* bias, const void* aux,
                   const float* resid, void* out, void* out2, mvlpt_stream_t stream) {
@@ -1875,25 +1901,19 @@ int mvlpt_op_gemm(int dtype, int epi, const void* A, const void* Bt, int M, int 
   // debug builds: row pitches of A / Bt from the environment (tools/pitch_probe.py allocates the operands that wide)
   if (getenv("MVLPT_DBG_LDA")) g.lda = atoi(getenv("MVLPT_DBG_LDA"));
   if (getenv("MVLPT_DBG_LDB")) g.ldb = atoi(getenv("MVLPT_DBG_LDB"));
-  // debug builds: timeline of workgroup 0 -> $MVLPT_GEMM_TRACE_FILE (8 waves x 2048 int64 records)
-  const char* path = getenv("MVLPT_GEMM_TRACE_FILE");
-  long long* tr = nullptr;
-  const size_t tr_bytes = 16 * 2048 * sizeof(long long);
-  if (path) { OPCHK(hipMalloc(&tr, tr_bytes)); OPCHK(hipMemsetAsync(tr, 0, tr_bytes, (hipStream_t)stream)); g.trace = tr; }
+  // timeline of workgroup 0 -> $MVLPT_GEMM_TRACE_FILE (8 waves x 2048 int64 records)
+  TraceCapture tc("MVLPT_GEMM_TRACE_FILE", 16 * 2048, (hipStream_t)stream);
+  OPCHK(tc.err);
+  g.trace = tc.ptr();
 #endif
   OPCHK(launch_gemm(dtype, epi, g, (hipStream_t)stream));
 #ifdef MVLPT_GEMM_TRACE
-  if (path) {
-    std::vector<long long> h(16 * 2048);
-    OPCHK(hipStreamSynchronize((hipStream_t)stream));
-    OPCHK(hipMemcpy(h.data(), tr, tr_bytes, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(path, "wb")) { fwrite(h.data(), 1, tr_bytes, f); fclose(f); }
-    (void)hipFree(tr);
-  }
+  OPCHK(tc.dump());
 #endif
   return 0;
 }
-// every GemmArgs field the towers set, straight into launch_gemm (which checks them)
+// every GemmArgs field the towers set, straight into launch_gemm (which checks them); the split and mixed entries below are this one
+// with their fields preset
 int mvlpt_op_gemm_ex(int dtype, int epi, const void* A, const void* Bt, int M, int N, int K, const float* bias, const void* aux,
                      const float* resid, void* out, void* out2, int a_split, int lda, int ldo, int ldb, int w8_exp, int out_lo8,
                      mvlpt_stream_t stream) {
@@ -1907,7 +1927,7 @@ int mvlpt_op_gemm_route(int dtype, int epi, int a_split, int M, int N, int K, in
   GemmArgs g{nullptr, nullptr, M, N, K, nullptr, nullptr, nullptr, nullptr, nullptr};
   g.a_split = a_split; g.fold_ntp = fold_ntp;
   GemmRoute r;
-  if (gemm_route(dtype, epi, g, fold_ntp > 0, (hipStream_t)stream, &r) != hipSuccess) { g_create_err = "gemm_route: no kernel for this problem"; return MVLPT_ERR_ARG; }
+  if (gemm_route(dtype, epi, g, fold_ntp > 0, (hipStream_t)stream, &r) != hipSuccess) return fail(nullptr, MVLPT_ERR_ARG, "gemm_route: no kernel for this problem");
   if (tile_m) *tile_m = r.tile_m;
   if (tile_n) *tile_n = r.tile_n;
   if (ring) *ring = r.ring;
@@ -1915,19 +1935,17 @@ int mvlpt_op_gemm_route(int dtype, int epi, int a_split, int M, int N, int K, in
 }
 int mvlpt_op_gemm_split(int dtype, int epi, const void* A, const void* Bt, int M, int N, int K, const float* bias, const void* aux,
                         const float* resid, void* out, void* out2, mvlpt_stream_t stream) {
-  GemmArgs g{A, Bt, M, N, K, bias, aux, resid, out, out2};
-  g.a_split = 1;
-  OPCHK(launch_gemm(dtype, epi, g, (hipStream_t)stream));
-  return 0;
+  return mvlpt_op_gemm_ex(dtype, epi, A, Bt, M, N, K, bias, aux, resid, out, out2, 1, 0, 0, 0, 0, 0, stream);
 }
 // ---- mixed pair (GemmArgs::a_split == 2): [hi (cols x 16 bit) | residual bytes (cols, e5m2) | unused], pitch 2*cols elements
 int mvlpt_op_pack_weight_mixed(int dtype, const float* w32, int rows, int cols, int transposed, void* out, int* w8_exp,
                                mvlpt_stream_t stream) {
-  if (!w32 || !out || !w8_exp || rows <= 0 || cols <= 0) { g_create_err = "pack_weight_mixed: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!w32 || !out || !w8_exp || rows <= 0 || cols <= 0) return fail(nullptr, MVLPT_ERR_ARG, "pack_weight_mixed: null/invalid argument");
   hipStream_t s = (hipStream_t)stream;
-  const int R = transposed ? cols : rows, K = transposed ? rows : cols, ld = K + K / 2;
-  float* sc = nullptr;
-  OPCHK(hipMalloc(&sc, 16));
+  const int K = transposed ? rows : cols, ld = K + K / 2;
+  DevBuf scale;
+  OPCHK(scale.reserve(16));
+  float* sc = (float*)scale.p;
   if (transposed) OPCHK(launch_pack_weight_t(dtype, w32, out, rows, cols, s, ld));
   else OPCHK(launch_pack_weight(dtype, w32, out, rows, cols, ld, s));
   OPCHK(launch_grad_scale(w32, (size_t)rows * cols, 128.0f, sc, s));
@@ -1935,23 +1953,27 @@ int mvlpt_op_pack_weight_mixed(int dtype, const float* w32, int rows, int cols, 
   float h = 1.0f;
   OPCHK(hipMemcpyAsync(&h, sc, 4, hipMemcpyDeviceToHost, s));
   OPCHK(hipStreamSynchronize(s));
-  (void)hipFree(sc);
   int e = 0; (void)frexpf(h, &e);
-  *w8_exp = e - 1; (void)R;
+  *w8_exp = e - 1;
   return 0;
 }
 int mvlpt_op_gemm_mixed(int dtype, int epi, const void* A, const void* Bt, int ldb, int w8_exp, int M, int N, int K, const float* bias,
                         const void* aux, const float* resid, void* out, void* out2, mvlpt_stream_t stream) {
-  GemmArgs g{A, Bt, M, N, K, bias, aux, resid, out, out2};
-  g.a_split = 2; g.ldb = ldb; g.w8_exp = w8_exp;
-  g.out_lo8 = (epi == EPI_GELU_SPLIT || epi == EPI_GELUBWD_SPLIT) ? 1 : 0;
-  OPCHK(launch_gemm(dtype, epi, g, (hipStream_t)stream));
-  return 0;
+  const int out_lo8 = (epi == EPI_GELU_SPLIT || epi == EPI_GELUBWD_SPLIT) ? 1 : 0;
+  return mvlpt_op_gemm_ex(dtype, epi, A, Bt, M, N, K, bias, aux, resid, out, out2, 2, 0, 0, ldb, w8_exp, out_lo8, stream);
 }
 // ---- LayerNorm folding, kernel level (the same launches block_fwd makes)
 int mvlpt_op_fold_vectors(int dtype, const void* W16, int ld, const float* gamma, const float* beta, const float* b, float* colsum,
                           float* bias2, int N, int K, mvlpt_stream_t stream) {
   OPCHK(launch_fold_vectors(dtype, W16, ld, gamma, beta, b, colsum, bias2, N, K, (hipStream_t)stream));
+  return 0;
+}
+// a LayerNorm-producing GEMM (g.ln_part / g.ln_ntp set): whole N tiles, and a slot per block of 128 columns; *nt: the slots it fills
+static int op_gemm_producer(const char* who, int dtype, int epi, const GemmArgs& g, int* nt, mvlpt_stream_t stream) {
+  const int bn = gemm_tile_n(dtype, epi, g, (hipStream_t)stream);
+  if (bn <= 0 || g.N % bn || g.N / 128 > g.ln_ntp) return fail(nullptr, MVLPT_ERR_ARG, std::string(who) + ": ntp smaller than N / 128");
+  if (nt) *nt = g.N / 128;
+  OPCHK(launch_gemm(dtype, epi, g, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_gemm_ln_producer(int dtype, const void* A, int a_split, const void* Bt, int ldb, int w8_exp, int M, int N, int K,
@@ -1960,11 +1982,7 @@ int mvlpt_op_gemm_ln_producer(int dtype, const void* A, int a_split, const void*
   GemmArgs g{A, Bt, M, N, K, bias, nullptr, resid, out32, nullptr};
   g.a_split = a_split; g.ldb = ldb; g.w8_exp = w8_exp;
   g.ln_gamma = gamma; g.ln_x16 = x16; g.ln_split = x16_split; g.ln_part = part; g.ln_ntp = ntp;
-  const int bn = gemm_tile_n(dtype, EPI_RESID32_LN, g, (hipStream_t)stream);
-  if (bn <= 0 || N % bn || N / 128 > ntp) { g_create_err = "gemm_ln_producer: ntp smaller than N / 128"; return MVLPT_ERR_ARG; }
-  if (nt) *nt = N / 128;
-  OPCHK(launch_gemm(dtype, EPI_RESID32_LN, g, (hipStream_t)stream));
-  return 0;
+  return op_gemm_producer("gemm_ln_producer", dtype, EPI_RESID32_LN, g, nt, stream);
 }
 int mvlpt_op_gemm_folded(int dtype, int epi, const void* A16, int a_split, const void* Bt, int ldb, int w8_exp, int M, int N, int K,
                          const float* colsum, const float* bias2, const float* part, int ntp, int nt, void* out, void* out2,
@@ -1999,114 +2017,101 @@ int mvlpt_op_gemm_residp(const void* A, const void* Bt, int ldb, int M, int N, i
   GemmArgs g{A, Bt, M, N, K, bias, nullptr, nullptr, hi_out, nullptr};
   g.ldb = ldb;
   g.rp_hi_in = hi_in; g.rp_lo_in = lo_in; g.rp_lo_out = lo_out; g.ln_part = part; g.ln_ntp = ntp;
-  const int bn = gemm_tile_n(DT_F16, EPI_RESIDP_LN, g, (hipStream_t)stream);
-  if (bn <= 0 || N % bn || N / 128 > ntp) { g_create_err = "gemm_residp: ntp smaller than N / 128"; return MVLPT_ERR_ARG; }
-  if (nt) *nt = N / 128;
-  OPCHK(launch_gemm(DT_F16, EPI_RESIDP_LN, g, (hipStream_t)stream));
-  return 0;
+  return op_gemm_producer("gemm_residp", DT_F16, EPI_RESIDP_LN, g, nt, stream);
 }
 int mvlpt_op_cast_mixed(int dtype, const float* in, void* out, int64_t rows, int d, mvlpt_stream_t stream) {
   OPCHK(launch_cast_f32_split(dtype, in, out, (size_t)rows, d, nullptr, (hipStream_t)stream, 1));
   return 0;
 }
-int mvlpt_op_layernorm_fwd_mixed(int out_dtype, const float* x, const float* gamma, const float* beta, void* y, int rows, int d,
-                                 mvlpt_stream_t stream) {
-  if (out_dtype == DT_F32) { g_create_err = "layernorm_fwd_mixed: 16-bit output only"; return MVLPT_ERR_ARG; }
-  LnFwdArgs a{x, nullptr, 1, gamma, beta, y, rows, d};
-  a.split = 2;
+// LayerNorm: every entry, old or _ex, fills the same arguments from (row_mul, split, dy_dtype); what a caller's arguments are
+// checked against is each entry's own business
+static int op_ln_fwd(int out_dtype, const float* x, int row_mul, const float* gamma, const float* beta, void* y, int rows, int d, int split,
+                     mvlpt_stream_t stream) {
+  LnFwdArgs a{x, nullptr, row_mul, gamma, beta, y, rows, d};
+  a.split = split;
   OPCHK(launch_ln_fwd(out_dtype, a, (hipStream_t)stream));
   return 0;
+}
+static int op_ln_bwd(int dtype, const void* dy, int dy_dtype, const float* x, int row_mul, const float* gamma, const float* resid,
+                     float* out32, void* out16, int rows, int d, int split, mvlpt_stream_t stream) {
+  LnBwdArgs a{dy, dy_dtype, x, nullptr, row_mul, gamma, resid, out32, out16, rows, d};
+  a.split = split;
+  OPCHK(launch_ln_bwd(dtype, a, (hipStream_t)stream));
+  return 0;
+}
+// pair-product attention; lo8: the pairs are mixed (hi + e5m2 residual byte).  Debug builds: timeline of one workgroup ->
+// $MVLPT_ATTN_TRACE_FILE (8 waves x 256 int64 records)
+static int op_attn32_fwd(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int causal, int q_rows, int lo8,
+                         mvlpt_stream_t stream) {
+  Attn32Args a{qkv, out, lse, N, L, H, causal, q_rows};
+  a.out_lo8 = lo8;
+#ifdef MVLPT_ATTN_TRACE
+  TraceCapture tc("MVLPT_ATTN_TRACE_FILE", 8 * 256, (hipStream_t)stream);
+  OPCHK(tc.err);
+  a.trace = tc.ptr();
+#endif
+  OPCHK(launch_attn32_fwd(dtype, a, (hipStream_t)stream));
+#ifdef MVLPT_ATTN_TRACE
+  OPCHK(tc.dump());
+#endif
+  return 0;
+}
+static int op_attn32_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int N,
+                         int L, int H, int causal, int lo8, mvlpt_stream_t stream) {
+  Attn32BwdArgs a{qkv, out, dout, lse, delta, dqkv, N, L, H, causal};
+  a.lo8 = lo8;
+#ifdef MVLPT_ATTN_TRACE
+  TraceCapture tc("MVLPT_ATTN_TRACE_FILE", 8 * 256, (hipStream_t)stream);
+  OPCHK(tc.err);
+  a.trace = tc.ptr();
+#endif
+  OPCHK(launch_attn32_bwd(dtype, a, (hipStream_t)stream));
+#ifdef MVLPT_ATTN_TRACE
+  OPCHK(tc.dump());
+#endif
+  return 0;
+}
+int mvlpt_op_layernorm_fwd_mixed(int out_dtype, const float* x, const float* gamma, const float* beta, void* y, int rows, int d,
+                                 mvlpt_stream_t stream) {
+  if (out_dtype == DT_F32) return fail(nullptr, MVLPT_ERR_ARG, "layernorm_fwd_mixed: 16-bit output only");
+  return op_ln_fwd(out_dtype, x, 1, gamma, beta, y, rows, d, 2, stream);
 }
 int mvlpt_op_layernorm_bwd_mixed(int dtype, const void* dy, const float* x, const float* gamma, const float* resid, float* out32,
                                  void* out16, int rows, int d, mvlpt_stream_t stream) {
-  LnBwdArgs a{dy, DT_F32, x, nullptr, 1, gamma, resid, out32, out16, rows, d};
-  a.split = 2;
-  OPCHK(launch_ln_bwd(dtype, a, (hipStream_t)stream));
-  return 0;
+  return op_ln_bwd(dtype, dy, DT_F32, x, 1, gamma, resid, out32, out16, rows, d, 2, stream);
 }
 int mvlpt_op_attention32_fwd_mixed(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int causal, int q_rows,
                                    mvlpt_stream_t stream) {
-  Attn32Args a{qkv, out, lse, N, L, H, causal, q_rows};
-  a.out_lo8 = 1;
-  OPCHK(launch_attn32_fwd(dtype, a, (hipStream_t)stream));
-  return 0;
+  return op_attn32_fwd(dtype, qkv, out, lse, N, L, H, causal, q_rows, 1, stream);
 }
 int mvlpt_op_attention32_bwd_mixed(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                                    void* dqkv, int N, int L, int H, int causal, mvlpt_stream_t stream) {
-  Attn32BwdArgs a{qkv, out, dout, lse, delta, dqkv, N, L, H, causal};
-  a.lo8 = 1;
-  OPCHK(launch_attn32_bwd(dtype, a, (hipStream_t)stream));
-  return 0;
+  return op_attn32_bwd(dtype, qkv, out, dout, lse, delta, dqkv, N, L, H, causal, 1, stream);
 }
 int mvlpt_op_layernorm_fwd_split(int out_dtype, const float* x, const float* gamma, const float* beta, void* y, int rows, int d,
                                  mvlpt_stream_t stream) {
-  if (out_dtype == DT_F32) { g_create_err = "layernorm_fwd_split: 16-bit output only"; return MVLPT_ERR_ARG; }
-  LnFwdArgs a{x, nullptr, 1, gamma, beta, y, rows, d};
-  a.split = 1;
-  OPCHK(launch_ln_fwd(out_dtype, a, (hipStream_t)stream));
-  return 0;
+  if (out_dtype == DT_F32) return fail(nullptr, MVLPT_ERR_ARG, "layernorm_fwd_split: 16-bit output only");
+  return op_ln_fwd(out_dtype, x, 1, gamma, beta, y, rows, d, 1, stream);
 }
 int mvlpt_op_layernorm_bwd_split(int dtype, const void* dy, const float* x, const float* gamma, const float* resid, float* out32,
                                  void* out16, int rows, int d, mvlpt_stream_t stream) {
-  LnBwdArgs a{dy, DT_F32, x, nullptr, 1, gamma, resid, out32, out16, rows, d};
-  a.split = 1;
-  OPCHK(launch_ln_bwd(dtype, a, (hipStream_t)stream));
-  return 0;
+  return op_ln_bwd(dtype, dy, DT_F32, x, 1, gamma, resid, out32, out16, rows, d, 1, stream);
 }
 int mvlpt_op_attention32_fwd(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int causal, int q_rows,
                              mvlpt_stream_t stream) {
-  Attn32Args a{qkv, out, lse, N, L, H, causal, q_rows};
-#ifdef MVLPT_ATTN_TRACE
-  // debug builds: timeline of one workgroup -> $MVLPT_ATTN_TRACE_FILE (8 waves x 256 int64 records)
-  const char* path = getenv("MVLPT_ATTN_TRACE_FILE");
-  long long* tr = nullptr;
-  const size_t tr_bytes = 8 * 256 * sizeof(long long);
-  if (path) { OPCHK(hipMalloc(&tr, tr_bytes)); OPCHK(hipMemsetAsync(tr, 0, tr_bytes, (hipStream_t)stream)); a.trace = tr; }
-#endif
-  OPCHK(launch_attn32_fwd(dtype, a, (hipStream_t)stream));
-#ifdef MVLPT_ATTN_TRACE
-  if (path) {
-    std::vector<long long> hbuf(8 * 256);
-    OPCHK(hipStreamSynchronize((hipStream_t)stream));
-    OPCHK(hipMemcpy(hbuf.data(), tr, tr_bytes, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(path, "wb")) { fwrite(hbuf.data(), 1, tr_bytes, f); fclose(f); }
-    (void)hipFree(tr);
-  }
-#endif
-  return 0;
+  return op_attn32_fwd(dtype, qkv, out, lse, N, L, H, causal, q_rows, 0, stream);
 }
 int mvlpt_op_attention32_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                              void* dqkv, int N, int L, int H, int causal, mvlpt_stream_t stream) {
-  Attn32BwdArgs a{qkv, out, dout, lse, delta, dqkv, N, L, H, causal};
-#ifdef MVLPT_ATTN_TRACE
-  const char* path = getenv("MVLPT_ATTN_TRACE_FILE");
-  long long* tr = nullptr;
-  const size_t tr_bytes = 8 * 256 * sizeof(long long);
-  if (path) { OPCHK(hipMalloc(&tr, tr_bytes)); OPCHK(hipMemsetAsync(tr, 0, tr_bytes, (hipStream_t)stream)); a.trace = tr; }
-#endif
-  OPCHK(launch_attn32_bwd(dtype, a, (hipStream_t)stream));
-#ifdef MVLPT_ATTN_TRACE
-  if (path) {
-    std::vector<long long> hbuf(8 * 256);
-    OPCHK(hipStreamSynchronize((hipStream_t)stream));
-    OPCHK(hipMemcpy(hbuf.data(), tr, tr_bytes, hipMemcpyDeviceToHost));
-    if (FILE* f = fopen(path, "wb")) { fwrite(hbuf.data(), 1, tr_bytes, f); fclose(f); }
-    (void)hipFree(tr);
-  }
-#endif
-  return 0;
+  return op_attn32_bwd(dtype, qkv, out, dout, lse, delta, dqkv, N, L, H, causal, 0, stream);
 }
 int mvlpt_op_layernorm_fwd(int out_dtype, const float* x, const float* gamma, const float* beta, void* y, int rows, int d,
                            mvlpt_stream_t stream) {
-  LnFwdArgs a{x, nullptr, 1, gamma, beta, y, rows, d};
-  OPCHK(launch_ln_fwd(out_dtype, a, (hipStream_t)stream));
-  return 0;
+  return op_ln_fwd(out_dtype, x, 1, gamma, beta, y, rows, d, 0, stream);
 }
 int mvlpt_op_layernorm_bwd(int dtype, const void* dy, const float* x, const float* gamma, const float* resid, float* out32,
                            void* out16, int rows, int d, mvlpt_stream_t stream) {
-  LnBwdArgs a{dy, dtype, x, nullptr, 1, gamma, resid, out32, out16, rows, d};
-  OPCHK(launch_ln_bwd(dtype, a, (hipStream_t)stream));
-  return 0;
+  return op_ln_bwd(dtype, dy, dtype, x, 1, gamma, resid, out32, out16, rows, d, 0, stream);
 }
 int mvlpt_op_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int causal,
                            mvlpt_stream_t stream) {
@@ -2182,20 +2187,14 @@ int mvlpt_op_layernorm_fwd_ex(int out_dtype, const float* x, int row_mul, const 
   if (out_dtype != DT_F32 && !is16(out_dtype)) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_fwd_ex: unknown output dtype");
   if (out_dtype == DT_F32 && split) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_fwd_ex: a pair output is 16-bit");
   if (int rc = ln_shape_check("op_layernorm_fwd_ex", rows, d, row_mul, split)) return rc;
-  LnFwdArgs a{x, nullptr, row_mul, gamma, beta, y, rows, d};
-  a.split = split;
-  OPCHK(launch_ln_fwd(out_dtype, a, (hipStream_t)stream));
-  return 0;
+  return op_ln_fwd(out_dtype, x, row_mul, gamma, beta, y, rows, d, split, stream);
 }
 int mvlpt_op_layernorm_bwd_ex(int dtype, const void* dy, int dy_dtype, const float* x, int row_mul, const float* gamma, const float* resid,
                               float* out32, void* out16, int rows, int d, int split, mvlpt_stream_t stream) {
   if (!dy || !x || !gamma || !out32) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_bwd_ex: null pointer");
   if (!is16(dtype) || (dy_dtype != DT_F32 && dy_dtype != dtype)) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_bwd_ex: dtype is fp16 or bf16, dy_dtype fp32 or dtype");
   if (int rc = ln_shape_check("op_layernorm_bwd_ex", rows, d, row_mul, split)) return rc;
-  LnBwdArgs a{dy, dy_dtype, x, nullptr, row_mul, gamma, resid, out32, out16, rows, d};
-  a.split = split;
-  OPCHK(launch_ln_bwd(dtype, a, (hipStream_t)stream));
-  return 0;
+  return op_ln_bwd(dtype, dy, dy_dtype, x, row_mul, gamma, resid, out32, out16, rows, d, split, stream);
 }
 int mvlpt_op_layernorm_route(int rows, int d, mvlpt_stream_t stream, int* nv, int* grid) {
   if (rows <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_route: rows > 0 (an empty call launches nothing)");
@@ -2249,105 +2248,103 @@ int mvlpt_op_patchify_route(int dtype, int image_dtype, int R, int P) {
 }
 // The ranged glue without a tower (tests).  The range table is built and checked on the host, uploaded into a temporary buffer, and the
 // call waits for its kernel before the buffer is freed.
-static int op_range_table(const int32_t* class_lo, const int32_t* class_hi, int G, int C, std::vector<int32_t>& t, int32_t** dev, int* S) {
+static int op_range_table(const int32_t* class_lo, const int32_t* class_hi, int G, int C, DevBuf& dev, int* S) {
+  std::vector<int32_t> t;
   const int64_t S64 = build_range_table(class_lo, class_hi, G, C, t);
-  if (S64 <= 0) { g_create_err = "ranged op: a class range is not inside [0, C], or every range is empty"; return MVLPT_ERR_ARG; }
+  if (S64 <= 0) return fail(nullptr, MVLPT_ERR_ARG, "ranged op: a class range is not inside [0, C], or every range is empty");
   *S = (int)S64;
-  OPCHK(hipMalloc((void**)dev, t.size() * 4));
-  hipError_t e = hipMemcpy(*dev, t.data(), t.size() * 4, hipMemcpyHostToDevice);
-  if (e != hipSuccess) { (void)hipFree(*dev); *dev = nullptr; OPCHK(e); }
+  OPCHK(dev.reserve(t.size() * 4));
+  OPCHK(hipMemcpy(dev.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
   return 0;
 }
 int mvlpt_op_assemble_prompts_ranged(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
                                      const float* pos, float* x, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L,
                                      int d, mvlpt_stream_t stream) {
   if (!prefix || !suffix || !ctx || !layout || !pos || !x || !class_lo || !class_hi || G <= 0 || C <= 0 || L <= n_ctx + 1 || n_ctx <= 0 ||
-      d <= 0) {
-    g_create_err = "op_assemble_prompts_ranged: null/invalid argument"; return MVLPT_ERR_ARG; }
-  std::vector<int32_t> t; int32_t* dev = nullptr; int S = 0;
-  if (int rc = op_range_table(class_lo, class_hi, G, C, t, &dev, &S)) return rc;
-  hipError_t e = launch_assemble_prompts_ranged(prefix, suffix, ctx, n_ctx, layout, pos, x, dev + 2 * G + 1, dev + 2 * G + 1 + S, S, L, d,
-                                                (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(dev);
-  OPCHK(e);
+      d <= 0)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_assemble_prompts_ranged: null/invalid argument");
+  DevBuf table; int S = 0;
+  if (int rc = op_range_table(class_lo, class_hi, G, C, table, &S)) return rc;
+  const int32_t* dev = (const int32_t*)table.p;
+  OPCHK(launch_assemble_prompts_ranged(prefix, suffix, ctx, n_ctx, layout, pos, x, dev + 2 * G + 1, dev + 2 * G + 1 + S, S, L, d,
+                                       (hipStream_t)stream));
+  OPCHK(hipStreamSynchronize((hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos, const int32_t* class_lo, const int32_t* class_hi, int G, int C,
                                     int L, int d, int n_ctx, float* dctx, mvlpt_stream_t stream) {
-  if (!dx || !ctx_pos || !dctx || !class_lo || !class_hi || G <= 0 || C <= 0 || L <= 0 || n_ctx <= 0 || d <= 0) {
-    g_create_err = "op_gather_ctx_grad_ranged: null/invalid argument"; return MVLPT_ERR_ARG; }
-  std::vector<int32_t> t; int32_t* dev = nullptr; int S = 0;
-  if (int rc = op_range_table(class_lo, class_hi, G, C, t, &dev, &S)) return rc;
-  hipError_t e = launch_gather_ctx_grad_ranged(dx, ctx_pos, dev, dev + G, G, L, d, n_ctx, dctx, nullptr, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(dev);
-  OPCHK(e);
+  if (!dx || !ctx_pos || !dctx || !class_lo || !class_hi || G <= 0 || C <= 0 || L <= 0 || n_ctx <= 0 || d <= 0)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_gather_ctx_grad_ranged: null/invalid argument");
+  DevBuf table; int S = 0;
+  if (int rc = op_range_table(class_lo, class_hi, G, C, table, &S)) return rc;
+  const int32_t* dev = (const int32_t*)table.p;
+  OPCHK(launch_gather_ctx_grad_ranged(dx, ctx_pos, dev, dev + G, G, L, d, n_ctx, dctx, nullptr, (hipStream_t)stream));
+  OPCHK(hipStreamSynchronize((hipStream_t)stream));
   return 0;
 }
 
 // The dense head's neighbours and the fp32 glue without a tower (tests): the launchers the towers call, unchanged.
 int mvlpt_op_sgemm_bt(const float* A, const float* Bt, float* Cm, int M, int N, int K, const float* alpha_dev, mvlpt_stream_t stream) {
-  if (!A || !Bt || !Cm) { g_create_err = "op_sgemm_bt: null argument"; return MVLPT_ERR_ARG; }
+  if (!A || !Bt || !Cm) return fail(nullptr, MVLPT_ERR_ARG, "op_sgemm_bt: null argument");
   OPCHK(launch_sgemm_bt(A, Bt, Cm, M, N, K, alpha_dev, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_grad_scale(const float* v, int64_t n, float target, float* scale_dev, mvlpt_stream_t stream) {
-  if (!v || !scale_dev || n <= 0 || !(target > 0.f)) { g_create_err = "op_grad_scale: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!v || !scale_dev || n <= 0 || !(target > 0.f)) return fail(nullptr, MVLPT_ERR_ARG, "op_grad_scale: null/invalid argument");
   OPCHK(launch_grad_scale(v, (size_t)n, target, scale_dev, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_optim_step(const MvlptOptimHyper* hyper, float* param, const float* grad, float* state1, float* state2, int64_t n,
                         const MvlptOptimSeg* segs_dev, int n_segs, const float* loss_dev, int32_t* skipped_dev, mvlpt_stream_t stream) {
-  if (!hyper || !param || !grad || !segs_dev || n <= 0 || n_segs <= 0) { g_create_err = "op_optim_step: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!hyper || !param || !grad || !segs_dev || n <= 0 || n_segs <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_optim_step: null/invalid argument");
   const MvlptOptimHyper& h = *hyper;
-  if (h.kind < MVLPT_OPTIM_SGD || h.kind > MVLPT_OPTIM_ADAMW || h.launch < 1) { g_create_err = "op_optim_step: unknown kind, or launch < 1"; return MVLPT_ERR_ARG; }
-  if (n_segs > MVLPT_OPTIM_MAX_SEGS) { g_create_err = "op_optim_step: more than MVLPT_OPTIM_MAX_SEGS segments"; return MVLPT_ERR_UNSUPPORTED; }
-  if ((h.kind == MVLPT_OPTIM_SGD && h.momentum != 0.0 && !state1) || (h.kind != MVLPT_OPTIM_SGD && (!state1 || !state2))) {
-    g_create_err = "op_optim_step: this optimizer kind needs its state buffer(s)"; return MVLPT_ERR_ARG; }
-  if (h.kind == MVLPT_OPTIM_SGD && h.nesterov && (h.momentum <= 0.0 || h.dampening != 0.0)) {
-    g_create_err = "op_optim_step: nesterov needs a momentum and zero dampening"; return MVLPT_ERR_ARG; }
-  if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)state1 | (uintptr_t)state2) & 15) != 0) {
-    g_create_err = "op_optim_step: the flat buffers must be 16-byte aligned"; return MVLPT_ERR_ARG; }
+  if (h.kind < MVLPT_OPTIM_SGD || h.kind > MVLPT_OPTIM_ADAMW || h.launch < 1) return fail(nullptr, MVLPT_ERR_ARG, "op_optim_step: unknown kind, or launch < 1");
+  if (n_segs > MVLPT_OPTIM_MAX_SEGS) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "op_optim_step: more than MVLPT_OPTIM_MAX_SEGS segments");
+  if ((h.kind == MVLPT_OPTIM_SGD && h.momentum != 0.0 && !state1) || (h.kind != MVLPT_OPTIM_SGD && (!state1 || !state2)))
+    return fail(nullptr, MVLPT_ERR_ARG, "op_optim_step: this optimizer kind needs its state buffer(s)");
+  if (h.kind == MVLPT_OPTIM_SGD && h.nesterov && (h.momentum <= 0.0 || h.dampening != 0.0))
+    return fail(nullptr, MVLPT_ERR_ARG, "op_optim_step: nesterov needs a momentum and zero dampening");
+  if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)state1 | (uintptr_t)state2) & 15) != 0)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_optim_step: the flat buffers must be 16-byte aligned");
   OPCHK(launch_optim_step(h, param, grad, state1, state2, n, segs_dev, n_segs, loss_dev, skipped_dev, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_reduce_prompt_rows(int dtype, float* dx32, void* dx16, int B, int L, int d, int row0, int n, float* out,
                                 const float* scale_dev, int zero_after, int split16, const float* vmask, mvlpt_stream_t stream) {
-  if (!dx32 || !out || B <= 0 || d <= 0 || n <= 0 || row0 < 0 || row0 + n > L || split16 < 0 || split16 > 2) {
-    g_create_err = "op_reduce_prompt_rows: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!dx32 || !out || B <= 0 || d <= 0 || n <= 0 || row0 < 0 || row0 + n > L || split16 < 0 || split16 > 2)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_reduce_prompt_rows: null/invalid argument");
   OPCHK(launch_reduce_prompt_rows(dtype, dx32, dx16, B, L, d, row0, n, out, scale_dev, zero_after, (hipStream_t)stream, split16, vmask));
   return 0;
 }
 int mvlpt_op_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C, int L, int d, int n_ctx, int per_class, float* dctx,
                              const float* scale_dev, mvlpt_stream_t stream) {
-  if (!dx || !ctx_pos || !dctx || C <= 0 || L <= 0 || n_ctx <= 0 || d <= 0) {
-    g_create_err = "op_gather_ctx_grad: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!dx || !ctx_pos || !dctx || C <= 0 || L <= 0 || n_ctx <= 0 || d <= 0)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_gather_ctx_grad: null/invalid argument");
   OPCHK(launch_gather_ctx_grad(dx, ctx_pos, C, L, d, n_ctx, per_class, dctx, scale_dev, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_attention_bwd_cls(int dtype, const void* qkv, const void* o_cls, const void* do_cls, const float* lse, void* dqkv, int N,
                                int L, int H, mvlpt_stream_t stream) {
-  if (!qkv || !o_cls || !do_cls || !lse || !dqkv) { g_create_err = "op_attention_bwd_cls: null argument"; return MVLPT_ERR_ARG; }
+  if (!qkv || !o_cls || !do_cls || !lse || !dqkv) return fail(nullptr, MVLPT_ERR_ARG, "op_attention_bwd_cls: null argument");
   OPCHK(launch_attn_bwd_cls(dtype, qkv, o_cls, do_cls, lse, dqkv, N, L, H, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, mvlpt_stream_t stream) {
-  if (!src || !dst || !idx || rows <= 0 || row_bytes <= 0) { g_create_err = "op_copy_rows: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!src || !dst || !idx || rows <= 0 || row_bytes <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_copy_rows: null/invalid argument");
   OPCHK(launch_copy_rows(src, dst, idx, rows, row_bytes, scatter, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_overwrite_rows(const float* rows, int n, float* x, int B, int L, int d, const float* vmask, mvlpt_stream_t stream) {
-  if (!rows || !x || n <= 0 || B <= 0 || 1 + n > L || d <= 0 || d % 4) {
-    g_create_err = "op_overwrite_rows: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!rows || !x || n <= 0 || B <= 0 || 1 + n > L || d <= 0 || d % 4)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_overwrite_rows: null/invalid argument");
   OPCHK(launch_overwrite_rows(rows, n, x, B, L, d, (hipStream_t)stream, vmask));
   return 0;
 }
 int mvlpt_op_assemble_tokens(const float* patch_emb, const float* cls, const float* pos, const float* ln_g, const float* ln_b,
                              const float* vpt, int n_vpt, const float* vmask, float* x, int B, int G2, int d, mvlpt_stream_t stream) {
   if (!patch_emb || !cls || !pos || !ln_g || !ln_b || !x || B <= 0 || G2 <= 0 || d <= 0 || n_vpt < 0 || (n_vpt > 0 && !vpt) ||
-      (vmask && n_vpt == 0)) {
-    g_create_err = "op_assemble_tokens: null/invalid argument"; return MVLPT_ERR_ARG; }
+      (vmask && n_vpt == 0))
+    return fail(nullptr, MVLPT_ERR_ARG, "op_assemble_tokens: null/invalid argument");
   OPCHK(launch_assemble_tokens(patch_emb, cls, pos, ln_g, ln_b, vpt, n_vpt, x, B, G2, d, (hipStream_t)stream, vmask));
   return 0;
 }
@@ -2355,8 +2352,8 @@ int mvlpt_op_assemble_prompts(const float* prefix, const float* suffix, const fl
                               const int32_t* layout, const float* pos, const int32_t* eot, float* x, int32_t* ctx_pos, int32_t* eot_rows,
                               int C, int L, int d, mvlpt_stream_t stream) {
   if (!prefix || !suffix || !layout || !pos || !eot || !x || !eot_rows || C <= 0 || n_ctx < 0 || L < n_ctx + 1 || d <= 0 ||
-      (n_ctx > 0 && (!ctx || !ctx_pos))) {
-    g_create_err = "op_assemble_prompts: null/invalid argument"; return MVLPT_ERR_ARG; }
+      (n_ctx > 0 && (!ctx || !ctx_pos)))
+    return fail(nullptr, MVLPT_ERR_ARG, "op_assemble_prompts: null/invalid argument");
   hipStream_t s = (hipStream_t)stream;
   OPCHK(launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, pos, x, C, L, d, s));
   OPCHK(launch_eot_rows(eot, eot_rows, C, L, s));
@@ -2368,57 +2365,55 @@ int mvlpt_op_assemble_prompts(const float* prefix, const float* suffix, const fl
 // [0, vocab) — the caller's responsibility at this level (mvlpt_text_encode_tokens checks its host table).
 int mvlpt_op_embed_tokens(const float* emb, const float* pos, const int32_t* ids, int ld, float* x, int S, int L, int d,
                           mvlpt_stream_t stream) {
-  if (!emb || !pos || !ids || !x || S <= 0 || L <= 0 || ld < L || d <= 0 || d % 4) {
-    g_create_err = "op_embed_tokens: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!emb || !pos || !ids || !x || S <= 0 || L <= 0 || ld < L || d <= 0 || d % 4)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_embed_tokens: null/invalid argument");
   OPCHK(launch_embed_tokens(emb, pos, ids, ld, x, S, L, d, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_ensemble_features(const float* feats, float* out, int T, int C, int e, mvlpt_stream_t stream) {
-  if (!feats || !out || T <= 0 || C <= 0 || e <= 0) { g_create_err = "op_ensemble_features: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!feats || !out || T <= 0 || C <= 0 || e <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_ensemble_features: null/invalid argument");
   OPCHK(launch_ensemble_features(feats, out, T, C, e, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_normalize_rows(const float* x, float* xn, float* norm, int rows, int d, mvlpt_stream_t stream) {
-  if (!x || !xn || !norm || rows <= 0 || d <= 0) { g_create_err = "op_normalize_rows: null/invalid argument"; return MVLPT_ERR_ARG; }
+  if (!x || !xn || !norm || rows <= 0 || d <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_normalize_rows: null/invalid argument");
   OPCHK(launch_normalize_rows(x, xn, norm, rows, d, (hipStream_t)stream));
   return 0;
 }
 
 // ------------------------------------------------------------------------------------------------ prompt interpretation
 // Every limit of include/mvlpt_hip.h is checked here, before a launch: the kernels (nearest.hip) trust their arguments.
-static int nearest_check(const char* who, int R, int V, int d, int k, std::string* msg) {
-  auto bad = [&](int code, const char* what) { *msg = std::string(who) + ": " + what; return code; };
-  if (R < 1 || V < 1) return bad(MVLPT_ERR_ARG, "R and V must be at least 1");
-  if (k > MVLPT_NEAREST_MAX_K) return bad(MVLPT_ERR_UNSUPPORTED, "k exceeds MVLPT_NEAREST_MAX_K");
-  if (k < 1 || k > V) return bad(MVLPT_ERR_ARG, "k must lie in [1, min(V, MVLPT_NEAREST_MAX_K)]");
-  if (d < 4 || d % 4 || d > 1024) return bad(MVLPT_ERR_ARG, "d must be a multiple of 4 in [4, 1024]");
-  if (R > MVLPT_NEAREST_MAX_ROWS) return bad(MVLPT_ERR_ARG, "R exceeds MVLPT_NEAREST_MAX_ROWS (chunk the rows)");
+static int nearest_check(Engine* E, const char* who, int R, int V, int d, int k) {
+  const std::string w = std::string(who) + ": ";
+  if (R < 1 || V < 1) return fail(E, MVLPT_ERR_ARG, w + "R and V must be at least 1");
+  if (k > MVLPT_NEAREST_MAX_K) return fail(E, MVLPT_ERR_UNSUPPORTED, w + "k exceeds MVLPT_NEAREST_MAX_K");
+  if (k < 1 || k > V) return fail(E, MVLPT_ERR_ARG, w + "k must lie in [1, min(V, MVLPT_NEAREST_MAX_K)]");
+  if (d < 4 || d % 4 || d > 1024) return fail(E, MVLPT_ERR_ARG, w + "d must be a multiple of 4 in [4, 1024]");
+  if (R > MVLPT_NEAREST_MAX_ROWS) return fail(E, MVLPT_ERR_ARG, w + "R exceeds MVLPT_NEAREST_MAX_ROWS (chunk the rows)");
   return 0;
 }
-static int nearest_run(const char* who, const float* q, const float* table, int R, int V, int d, int k, int32_t* idx, float* dist,
-                       void* ws, const NearestPlan& p, hipStream_t s, std::string* msg) {
-  if ((((uintptr_t)q | (uintptr_t)table) & 15) != 0) { *msg = std::string(who) + ": q and table must be 16-byte aligned"; return MVLPT_ERR_ARG; }
+static int nearest_run(Engine* E, const char* who, const float* q, const float* table, int R, int V, int d, int k, int32_t* idx,
+                       float* dist, void* ws, const NearestPlan& p, hipStream_t s) {
+  if ((((uintptr_t)q | (uintptr_t)table) & 15) != 0) return fail(E, MVLPT_ERR_ARG, std::string(who) + ": q and table must be 16-byte aligned");
   const hipError_t e = launch_nearest_rows(q, table, R, V, d, k, idx, dist, ws, p, s);
-  if (e != hipSuccess) { *msg = std::string(who) + ": " + hipGetErrorString(e); return MVLPT_ERR_HIP; }
+  if (e != hipSuccess) return hipfail(E, e, who);
   return 0;
 }
 int mvlpt_nearest_workspace_bytes(int R, int V, int d, int k, mvlpt_stream_t stream, int64_t* out) {
-  if (!out) { g_create_err = "nearest_workspace_bytes: null argument"; return MVLPT_ERR_ARG; }
-  if (int rc = nearest_check("nearest_workspace_bytes", R, V, d, k, &g_create_err)) return rc;
+  if (!out) return fail(nullptr, MVLPT_ERR_ARG, "nearest_workspace_bytes: null argument");
+  if (int rc = nearest_check(nullptr, "nearest_workspace_bytes", R, V, d, k)) return rc;
   *out = (int64_t)nearest_plan(R, V, k, stream_cus((hipStream_t)stream)).ws_bytes;
   return 0;
 }
 int mvlpt_op_nearest_rows(const float* q, const float* table, int R, int V, int d, int k, int32_t* idx, float* dist, void* workspace,
                           int64_t workspace_bytes, mvlpt_stream_t stream) {
-  if (!q || !table || !idx || !dist || !workspace) { g_create_err = "op_nearest_rows: null argument"; return MVLPT_ERR_ARG; }
-  if (int rc = nearest_check("op_nearest_rows", R, V, d, k, &g_create_err)) return rc;
+  if (!q || !table || !idx || !dist || !workspace) return fail(nullptr, MVLPT_ERR_ARG, "op_nearest_rows: null argument");
+  if (int rc = nearest_check(nullptr, "op_nearest_rows", R, V, d, k)) return rc;
   const NearestPlan p = nearest_plan(R, V, k, stream_cus((hipStream_t)stream));
-  if (workspace_bytes < 0 || (uint64_t)workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 7) != 0) {
-    g_create_err = "op_nearest_rows: the workspace is smaller than mvlpt_nearest_workspace_bytes (" + std::to_string(p.ws_bytes) +
-                   " bytes), or not 8-byte aligned";
-    return MVLPT_ERR_ARG;
-  }
-  return nearest_run("op_nearest_rows", q, table, R, V, d, k, idx, dist, workspace, p, (hipStream_t)stream, &g_create_err);
+  if (workspace_bytes < 0 || (uint64_t)workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 7) != 0)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_nearest_rows: the workspace is smaller than mvlpt_nearest_workspace_bytes (" +
+                                            std::to_string(p.ws_bytes) + " bytes), or not 8-byte aligned");
+  return nearest_run(nullptr, "op_nearest_rows", q, table, R, V, d, k, idx, dist, workspace, p, (hipStream_t)stream);
 }
 int mvlpt_nearest_tokens(void* h, const float* q, int R, int k, int32_t* idx, float* dist, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
@@ -2426,11 +2421,10 @@ int mvlpt_nearest_tokens(void* h, const float* q, int R, int k, int32_t* idx, fl
   if (!q || !idx || !dist) return fail(E, MVLPT_ERR_ARG, "nearest_tokens: null argument");
   if (!E->tok_emb || E->vocab <= 0)
     return fail(E, MVLPT_ERR_STATE, "nearest_tokens: token_embedding.weight is not loaded (mvlpt_load_frozen)");
-  if (int rc = nearest_check("nearest_tokens", R, E->vocab, E->arch.text_width, k, &E->err)) return rc;
+  if (int rc = nearest_check(E, "nearest_tokens", R, E->vocab, E->arch.text_width, k)) return rc;
   const NearestPlan p = nearest_plan(R, E->vocab, k, stream_cus((hipStream_t)stream));
   HIPCHK(E, E->near_ws.reserve(p.ws_bytes));
-  return nearest_run("nearest_tokens", q, E->tok_emb, R, E->vocab, E->arch.text_width, k, idx, dist, E->near_ws.p, p, (hipStream_t)stream,
-                     &E->err);
+  return nearest_run(E, "nearest_tokens", q, E->tok_emb, R, E->vocab, E->arch.text_width, k, idx, dist, E->near_ws.p, p, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------ evaluation counts
@@ -2439,16 +2433,15 @@ int mvlpt_op_eval_count(const float* logits, int64_t ld, int B, int C, const voi
                         const int32_t* rows, int n_rows, const int32_t* task, const int32_t* lo, const int32_t* hi, int T,
                         const uint8_t* col_mask, uint8_t* col_seen, int64_t* n_true, int64_t* n_pred, int64_t* n_hit, int64_t* n_pred_r,
                         int64_t* n_hit_r, int64_t* cmat, mvlpt_stream_t stream) {
-  auto bad = [&](const char* what) { g_create_err = std::string("op_eval_count: ") + what; return MVLPT_ERR_ARG; };
-  if (!logits || !labels || !n_true || !n_pred || !n_hit) return bad("null argument");
-  if (B < 1 || C < 1 || ld < C) return bad("B and C must be at least 1 and the row pitch at least C");
-  if (label_kind != MVLPT_LABEL_INT64 && label_kind != MVLPT_LABEL_PROB_F32) return bad("unknown label kind");
-  if (label_kind == MVLPT_LABEL_PROB_F32 && label_ld < C) return bad("the label pitch must be at least C");
-  if (rows && n_rows < 0) return bad("n_rows must not be negative");
+  if (!logits || !labels || !n_true || !n_pred || !n_hit) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_count: null argument");
+  if (B < 1 || C < 1 || ld < C) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_count: B and C must be at least 1 and the row pitch at least C");
+  if (label_kind != MVLPT_LABEL_INT64 && label_kind != MVLPT_LABEL_PROB_F32) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_count: unknown label kind");
+  if (label_kind == MVLPT_LABEL_PROB_F32 && label_ld < C) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_count: the label pitch must be at least C");
+  if (rows && n_rows < 0) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_count: n_rows must not be negative");
   const bool ranged = task || lo || hi;
   if (ranged && (!task || !lo || !hi || T < 1 || !n_pred_r || !n_hit_r))
-    return bad("task ranges need task, lo, hi, T >= 1, n_pred_r and n_hit_r together");
-  if (cmat && (int64_t)C * C > ((int64_t)1 << 31)) return bad("the confusion matrix needs C * C <= 2^31");
+    return fail(nullptr, MVLPT_ERR_ARG, "op_eval_count: task ranges need task, lo, hi, T >= 1, n_pred_r and n_hit_r together");
+  if (cmat && (int64_t)C * C > ((int64_t)1 << 31)) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_count: the confusion matrix needs C * C <= 2^31");
   EvalCountArgs a;
   a.logits = logits; a.ld = ld; a.B = B; a.C = C;
   a.label_i = label_kind == MVLPT_LABEL_INT64 ? (const long long*)labels : nullptr;
@@ -2462,13 +2455,12 @@ int mvlpt_op_eval_count(const float* logits, int64_t ld, int B, int C, const voi
   return 0;
 }
 static int eval_rank_check(const char* who, int N, int C) {
-  auto bad = [&](int code, const char* what) { g_create_err = std::string(who) + ": " + what; return code; };
-  if (N < 1 || C < 1) return bad(MVLPT_ERR_ARG, "N and C must be at least 1");
-  if (N > MVLPT_EVAL_MAX_ROWS) return bad(MVLPT_ERR_UNSUPPORTED, "N exceeds MVLPT_EVAL_MAX_ROWS");
+  if (N < 1 || C < 1) return fail(nullptr, MVLPT_ERR_ARG, std::string(who) + ": N and C must be at least 1");
+  if (N > MVLPT_EVAL_MAX_ROWS) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, std::string(who) + ": N exceeds MVLPT_EVAL_MAX_ROWS");
   return 0;
 }
 int mvlpt_eval_workspace_bytes(int N, int C, mvlpt_stream_t stream, int64_t* out) {
-  if (!out) { g_create_err = "eval_workspace_bytes: null argument"; return MVLPT_ERR_ARG; }
+  if (!out) return fail(nullptr, MVLPT_ERR_ARG, "eval_workspace_bytes: null argument");
   if (int rc = eval_rank_check("eval_workspace_bytes", N, C)) return rc;
   *out = (int64_t)eval_rank_plan(N, C, stream_cus((hipStream_t)stream)).ws_bytes;
   return 0;
@@ -2477,20 +2469,17 @@ int mvlpt_op_eval_rank_columns(const float* scores, int64_t ld, int N, int C, co
                                const int32_t* rows, int n_rows, const double* thresholds, int64_t* n_pos, int64_t* n_neg,
                                int64_t* twice_u, double* interp, int32_t* flags, void* workspace, int64_t workspace_bytes,
                                mvlpt_stream_t stream) {
-  auto bad = [&](const char* what) { g_create_err = std::string("op_eval_rank_columns: ") + what; return MVLPT_ERR_ARG; };
-  if (!scores || !targets || !thresholds || !n_pos || !n_neg || !twice_u || !interp || !flags) return bad("null argument");
+  if (!scores || !targets || !thresholds || !n_pos || !n_neg || !twice_u || !interp || !flags) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_rank_columns: null argument");
   if (int rc = eval_rank_check("op_eval_rank_columns", N, C)) return rc;
-  if (ld < C) return bad("the row pitch must be at least C");
-  if (target_kind != MVLPT_LABEL_INT64 && target_kind != MVLPT_LABEL_PROB_F32) return bad("unknown target kind");
-  if (target_kind == MVLPT_LABEL_PROB_F32 && target_ld < C) return bad("the target pitch must be at least C");
-  if (rows && (n_rows < 0 || n_rows > N)) return bad("n_rows must lie in [0, N]");
+  if (ld < C) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_rank_columns: the row pitch must be at least C");
+  if (target_kind != MVLPT_LABEL_INT64 && target_kind != MVLPT_LABEL_PROB_F32) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_rank_columns: unknown target kind");
+  if (target_kind == MVLPT_LABEL_PROB_F32 && target_ld < C) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_rank_columns: the target pitch must be at least C");
+  if (rows && (n_rows < 0 || n_rows > N)) return fail(nullptr, MVLPT_ERR_ARG, "op_eval_rank_columns: n_rows must lie in [0, N]");
   const int n = rows ? n_rows : N;
   const EvalRankPlan p = eval_rank_plan(n, C, stream_cus((hipStream_t)stream));
-  if (p.ws_bytes && (!workspace || workspace_bytes < 0 || (uint64_t)workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 7) != 0)) {
-    g_create_err = "op_eval_rank_columns: the workspace is smaller than mvlpt_eval_workspace_bytes (" + std::to_string(p.ws_bytes) +
-                   " bytes), or not 8-byte aligned";
-    return MVLPT_ERR_ARG;
-  }
+  if (p.ws_bytes && (!workspace || workspace_bytes < 0 || (uint64_t)workspace_bytes < p.ws_bytes || ((uintptr_t)workspace & 7) != 0))
+    return fail(nullptr, MVLPT_ERR_ARG, "op_eval_rank_columns: the workspace is smaller than mvlpt_eval_workspace_bytes (" +
+                                            std::to_string(p.ws_bytes) + " bytes), or not 8-byte aligned");
   OPCHK(launch_eval_rank_columns(scores, ld, N, C, target_kind == MVLPT_LABEL_INT64 ? (const long long*)targets : nullptr,
                                  target_kind == MVLPT_LABEL_PROB_F32 ? (const float*)targets : nullptr, target_ld, rows, n, thresholds,
                                  (long long*)n_pos, (long long*)n_neg, (long long*)twice_u, interp, flags, workspace, p,
@@ -2501,33 +2490,31 @@ int mvlpt_op_eval_rank_columns(const float* scores, int64_t ld, int N, int C, co
 // ------------------------------------------------------------------------------------------------ softmax regression (linear probe)
 // Every limit of include/mvlpt_hip.h is checked here, before a launch: the kernels (softmax_reg.hip) trust their arguments.
 static int softmax_reg_check(const char* who, int N, int D, int K) {
-  auto bad = [&](const char* what) { g_create_err = std::string(who) + ": " + what; return MVLPT_ERR_ARG; };
-  if (N < 1) return bad("N must be at least 1");
-  if (K < 2) return bad("K must be at least 2");
-  if (D < 4 || D % 4) return bad("D must be a multiple of 4, at least 4");
-  if ((int64_t)K * ((int64_t)D + 1) >= ((int64_t)1 << 31)) return bad("K * (D + 1) must stay below 2^31");
+  const std::string w = std::string(who) + ": ";
+  if (N < 1) return fail(nullptr, MVLPT_ERR_ARG, w + "N must be at least 1");
+  if (K < 2) return fail(nullptr, MVLPT_ERR_ARG, w + "K must be at least 2");
+  if (D < 4 || D % 4) return fail(nullptr, MVLPT_ERR_ARG, w + "D must be a multiple of 4, at least 4");
+  if ((int64_t)K * ((int64_t)D + 1) >= ((int64_t)1 << 31)) return fail(nullptr, MVLPT_ERR_ARG, w + "K * (D + 1) must stay below 2^31");
   return 0;
 }
 static int softmax_reg_ws_check(const char* who, const void* ws, size_t have, size_t need) {
-  if (have < need || ((uintptr_t)ws & 15) != 0) {
-    g_create_err = std::string(who) + ": the workspace is smaller than needed (" + std::to_string(need) + " bytes), or not 16-byte aligned";
-    return MVLPT_ERR_ARG;
-  }
+  if (have < need || ((uintptr_t)ws & 15) != 0)
+    return fail(nullptr, MVLPT_ERR_ARG, std::string(who) + ": the workspace is smaller than needed (" + std::to_string(need) + " bytes), or not 16-byte aligned");
   return 0;
 }
 int mvlpt_softmax_reg_workspace_bytes(int N, int D, int K, size_t* bytes) {
-  if (!bytes) { g_create_err = "softmax_reg_workspace_bytes: null argument"; return MVLPT_ERR_ARG; }
+  if (!bytes) return fail(nullptr, MVLPT_ERR_ARG, "softmax_reg_workspace_bytes: null argument");
   if (int rc = softmax_reg_check("softmax_reg_workspace_bytes", N, D, K)) return rc;
   *bytes = softmax_reg_plan(N, D, K).ws_bytes;
   return 0;
 }
 int mvlpt_op_softmax_reg_eval(const float* X, const int32_t* y, const float* theta, const float* dir, int N, int D, int K, double l2,
                               float* grad, double* stats, void* ws, size_t ws_bytes, mvlpt_stream_t stream) {
-  if (!X || !y || !theta || !grad || !stats || !ws) { g_create_err = "op_softmax_reg_eval: null argument"; return MVLPT_ERR_ARG; }
+  if (!X || !y || !theta || !grad || !stats || !ws) return fail(nullptr, MVLPT_ERR_ARG, "op_softmax_reg_eval: null argument");
   if (int rc = softmax_reg_check("op_softmax_reg_eval", N, D, K)) return rc;
-  if (!(l2 >= 0.0)) { g_create_err = "op_softmax_reg_eval: l2 must be a number >= 0"; return MVLPT_ERR_ARG; }
-  if ((((uintptr_t)X | (uintptr_t)theta) & 15) != 0 || ((uintptr_t)stats & 7) != 0) {
-    g_create_err = "op_softmax_reg_eval: X and theta must be 16-byte aligned, stats 8-byte aligned"; return MVLPT_ERR_ARG; }
+  if (!(l2 >= 0.0)) return fail(nullptr, MVLPT_ERR_ARG, "op_softmax_reg_eval: l2 must be a number >= 0");
+  if ((((uintptr_t)X | (uintptr_t)theta) & 15) != 0 || ((uintptr_t)stats & 7) != 0)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_softmax_reg_eval: X and theta must be 16-byte aligned, stats 8-byte aligned");
   const SoftmaxRegPlan p = softmax_reg_plan(N, D, K);
   if (int rc = softmax_reg_ws_check("op_softmax_reg_eval", ws, ws_bytes, p.ws_bytes)) return rc;
   OPCHK(launch_softmax_reg_eval(X, y, theta, dir, N, D, K, l2, grad, stats, ws, p, (hipStream_t)stream));
@@ -2535,10 +2522,10 @@ int mvlpt_op_softmax_reg_eval(const float* X, const int32_t* y, const float* the
 }
 int mvlpt_op_softmax_reg_predict(const float* X, const float* theta, int N, int D, int K, int32_t* pred, float* margin, void* ws,
                                  size_t ws_bytes, mvlpt_stream_t stream) {
-  if (!X || !theta || !pred || !ws) { g_create_err = "op_softmax_reg_predict: null argument"; return MVLPT_ERR_ARG; }
+  if (!X || !theta || !pred || !ws) return fail(nullptr, MVLPT_ERR_ARG, "op_softmax_reg_predict: null argument");
   if (int rc = softmax_reg_check("op_softmax_reg_predict", N, D, K)) return rc;
-  if ((((uintptr_t)X | (uintptr_t)theta) & 15) != 0) {
-    g_create_err = "op_softmax_reg_predict: X and theta must be 16-byte aligned"; return MVLPT_ERR_ARG; }
+  if ((((uintptr_t)X | (uintptr_t)theta) & 15) != 0)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_softmax_reg_predict: X and theta must be 16-byte aligned");
   const SoftmaxRegPlan p = softmax_reg_plan(N, D, K);
   if (int rc = softmax_reg_ws_check("op_softmax_reg_predict", ws, ws_bytes, p.predict_bytes)) return rc;
   OPCHK(launch_softmax_reg_predict(X, theta, N, D, K, pred, margin, ws, p, (hipStream_t)stream));
@@ -2546,56 +2533,12 @@ int mvlpt_op_softmax_reg_predict(const float* X, const float* theta, int N, int 
 }
 
 // ------------------------------------------------------------------------------------------------ input pipeline
-int mvlpt_preprocess(void* h, const uint8_t* src, int64_t src_bytes, const MvlptImageDesc* descs, int B, int out_h, int out_w,
-                     const float* mean, const float* stdv, void* out, int out_dtype, uint8_t* out_u8, mvlpt_stream_t stream) {
-  static_assert(sizeof(MvlptImageDesc) == sizeof(PpDesc), "descriptor layouts must match");
-  Engine* E = (Engine*)h;
-  if (!E) return MVLPT_ERR_ARG;
-  if (!src || !descs || B <= 0 || out_h <= 0 || out_w <= 0 || !mean || !stdv || (!out && !out_u8))
-    return fail(E, MVLPT_ERR_ARG, "preprocess: null pointer or empty batch / output");
-  if (out && out_dtype != DT_F32 && out_dtype != DT_F16 && out_dtype != DT_BF16) return fail(E, MVLPT_ERR_ARG, "preprocess: bad out_dtype");
-  int max_crop_h = 0, ks_max = 1;
-  for (int b = 0; b < B; ++b) {
-    const MvlptImageDesc& d = descs[b];
-    const bool ok = d.height > 0 && d.width > 0 && d.offset >= 0 && d.offset + (int64_t)d.height * d.width * 3 <= src_bytes &&
-                    d.crop_top >= 0 && d.crop_left >= 0 && d.crop_height > 0 && d.crop_width > 0 &&
-                    d.crop_top + d.crop_height <= d.height && d.crop_left + d.crop_width <= d.width && d.resize_height > 0 &&
-                    d.resize_width > 0 && d.out_top >= 0 && d.out_left >= 0 && d.out_top + out_h <= d.resize_height &&
-                    d.out_left + out_w <= d.resize_width && (d.flip == 0 || d.flip == 1);
-    if (!ok) return fail(E, MVLPT_ERR_ARG, "preprocess: descriptor " + std::to_string(b) + " is inconsistent (box / window outside the image, or image outside src)");
-    max_crop_h = std::max(max_crop_h, (int)d.crop_height);
-    const double sh = std::max(1.0, (double)d.crop_height / d.resize_height), sw = std::max(1.0, (double)d.crop_width / d.resize_width);
-    ks_max = std::max(ks_max, std::max((int)std::ceil(2.0 * sh), (int)std::ceil(2.0 * sw)) * 2 + 1);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  const int n_max = std::max(out_h, out_w);
-  const size_t table_stride = (size_t)(2 + ks_max) * n_max;                          // int32 per (image, pass)
-  const size_t tmp_stride = align256((size_t)max_crop_h * out_w * 3);
-  const size_t desc_bytes = align256(sizeof(PpDesc) * (size_t)B), table_bytes = align256(table_stride * 4 * 2 * (size_t)B);
-  HIPCHK(E, E->pp_ws.reserve(desc_bytes + table_bytes + tmp_stride * (size_t)B));
-  char* base = (char*)E->pp_ws.p;
-  PpDesc* descs_dev = (PpDesc*)base;
-  int32_t* tables = (int32_t*)(base + desc_bytes);
-  uint8_t* tmp = (uint8_t*)(base + desc_bytes + table_bytes);
-  HIPCHK(E, hipMemcpyAsync(descs_dev, descs, sizeof(PpDesc) * (size_t)B, hipMemcpyHostToDevice, s));
-  HIPCHK(E, launch_preprocess(src, descs_dev, B, max_crop_h, ks_max, out_h, out_w, tables, table_stride, tmp, tmp_stride, mean, stdv,
-                              out, out_dtype, out_u8, s));
-  return 0;
-}
-
-int mvlpt_preprocess_aug(void* h, const uint8_t* src, int64_t src_bytes, const MvlptImageDesc* descs, const MvlptAugmentDesc* aug, int B,
-                         int out_h, int out_w, int fill_outside, const float* mean, const float* stdv, void* out, int out_dtype,
-                         uint8_t* out_u8, mvlpt_stream_t stream) {
-  static_assert(sizeof(MvlptAugmentDesc) == sizeof(PpAug) && MVLPT_AUG_MAX_HOLES == PP_AUG_MAX_HOLES, "descriptor layouts must match");
-  Engine* E = (Engine*)h;
-  if (!E) return MVLPT_ERR_ARG;
-  if (B < 0 || (fill_outside != 0 && fill_outside != 1)) return fail(E, MVLPT_ERR_ARG, "preprocess_aug: negative batch, or fill_outside is not 0 or 1");
-  if (B == 0) return 0;
-  if (!aug && !fill_outside) return mvlpt_preprocess(h, src, src_bytes, descs, B, out_h, out_w, mean, stdv, out, out_dtype, out_u8, stream);
-  if (!src || !descs || out_h <= 0 || out_w <= 0 || (int64_t)out_h * out_w > (1 << 29) || !mean || !stdv || (!out && !out_u8))
-    return fail(E, MVLPT_ERR_ARG, "preprocess_aug: null pointer or empty / oversized output");
-  if (out && out_dtype != DT_F32 && out_dtype != DT_F16 && out_dtype != DT_BF16) return fail(E, MVLPT_ERR_ARG, "preprocess_aug: bad out_dtype");
-  int max_crop_h = 0, ks_max = 1;
+// One pass over a batch's descriptors for the entry `who`: every box inside its image, every image inside src, and the output window
+// inside the resized image, or, under fill_outside, merely near enough to it for 32-bit arithmetic; `why` is the entry's wording of
+// that.  aug (may be null): the augmentation of image b is checked right behind its descriptor.  Returns the tallest crop and the
+// widest filter footprint of the batch.
+static int pp_check(Engine* E, const char* who, const char* why, const MvlptImageDesc* descs, const MvlptAugmentDesc* aug, int B,
+                    int64_t src_bytes, int out_h, int out_w, int fill_outside, int* max_crop_h, int* ks_max) {
   const int64_t far = (int64_t)1 << 30;
   for (int b = 0; b < B; ++b) {
     const MvlptImageDesc& d = descs[b];
@@ -2605,10 +2548,10 @@ int mvlpt_preprocess_aug(void* h, const uint8_t* src, int64_t src_bytes, const M
               d.resize_width > 0 && (d.flip == 0 || d.flip == 1);
     if (fill_outside) ok = ok && d.out_top >= -far && d.out_top <= far && d.out_left >= -far && d.out_left <= far;
     else ok = ok && d.out_top >= 0 && d.out_left >= 0 && (int64_t)d.out_top + out_h <= d.resize_height && (int64_t)d.out_left + out_w <= d.resize_width;
-    if (!ok) return fail(E, MVLPT_ERR_ARG, "preprocess_aug: descriptor " + std::to_string(b) + " is inconsistent (box outside the image, image outside src, or window outside the resized image without fill_outside)");
-    max_crop_h = std::max(max_crop_h, (int)d.crop_height);
+    if (!ok) return fail(E, MVLPT_ERR_ARG, std::string(who) + ": descriptor " + std::to_string(b) + " is inconsistent (" + why + ")");
+    *max_crop_h = std::max(*max_crop_h, (int)d.crop_height);
     const double sh = std::max(1.0, (double)d.crop_height / d.resize_height), sw = std::max(1.0, (double)d.crop_width / d.resize_width);
-    ks_max = std::max(ks_max, std::max((int)std::ceil(2.0 * sh), (int)std::ceil(2.0 * sw)) * 2 + 1);
+    *ks_max = std::max(*ks_max, std::max((int)std::ceil(2.0 * sh), (int)std::ceil(2.0 * sw)) * 2 + 1);
     if (!aug) continue;
     const MvlptAugmentDesc& a = aug[b];
     ok = a.n_ops >= 0 && a.n_ops <= PP_AUG_MAX_OPS && (a.grayscale == 0 || a.grayscale == 1) && a.n_holes >= 0 && a.n_holes <= PP_AUG_MAX_HOLES;
@@ -2625,26 +2568,75 @@ int mvlpt_preprocess_aug(void* h, const uint8_t* src, int64_t src_bytes, const M
       const int32_t* r = a.hole[k];
       ok = r[0] >= 0 && r[1] >= 0 && r[2] >= 1 && r[3] >= 1 && (int64_t)r[0] + r[2] <= out_h && (int64_t)r[1] + r[3] <= out_w;
     }
-    if (!ok) return fail(E, MVLPT_ERR_ARG, "preprocess_aug: augmentation " + std::to_string(b) + " is malformed (operation count / id / repeat, factor not finite or negative, hue_shift, grayscale, or a hole outside the window)");
+    if (!ok) return fail(E, MVLPT_ERR_ARG, std::string(who) + ": augmentation " + std::to_string(b) + " is malformed (operation count / id / repeat, factor not finite or negative, hue_shift, grayscale, or a hole outside the window)");
   }
+  return 0;
+}
+// where the parts of pp_ws lie: [image descs | augmentations (with_aug) | resampling tables | row-pass output | windows (with_win)]
+struct PpLayout {
+  size_t table_stride = 0, tmp_stride = 0;      // int32 per (image, pass); bytes per image
+  size_t augs = 0, tables = 0, tmp = 0, win = 0, total = 0;
+  PpLayout(int B, int max_crop_h, int ks_max, int out_h, int out_w, bool with_aug, bool with_win) {
+    table_stride = (size_t)(2 + ks_max) * std::max(out_h, out_w);
+    tmp_stride = align256((size_t)max_crop_h * out_w * 3);
+    augs = align256(sizeof(PpDesc) * (size_t)B);
+    tables = augs + (with_aug ? align256(sizeof(PpAug) * (size_t)B) : 0);
+    tmp = tables + align256(table_stride * 4 * 2 * (size_t)B);
+    win = tmp + align256(tmp_stride * (size_t)B);
+    total = win + (with_win ? (size_t)B * out_h * out_w * 3 : 0);
+  }
+};
+
+int mvlpt_preprocess(void* h, const uint8_t* src, int64_t src_bytes, const MvlptImageDesc* descs, int B, int out_h, int out_w,
+                     const float* mean, const float* stdv, void* out, int out_dtype, uint8_t* out_u8, mvlpt_stream_t stream) {
+  static_assert(sizeof(MvlptImageDesc) == sizeof(PpDesc), "descriptor layouts must match");
+  Engine* E = (Engine*)h;
+  if (!E) return MVLPT_ERR_ARG;
+  if (!src || !descs || B <= 0 || out_h <= 0 || out_w <= 0 || !mean || !stdv || (!out && !out_u8))
+    return fail(E, MVLPT_ERR_ARG, "preprocess: null pointer or empty batch / output");
+  if (out && out_dtype != DT_F32 && out_dtype != DT_F16 && out_dtype != DT_BF16) return fail(E, MVLPT_ERR_ARG, "preprocess: bad out_dtype");
+  int max_crop_h = 0, ks_max = 1;
+  if (int rc = pp_check(E, "preprocess", "box / window outside the image, or image outside src", descs, nullptr, B, src_bytes, out_h, out_w, 0,
+                        &max_crop_h, &ks_max))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int n_max = std::max(out_h, out_w);
-  const size_t table_stride = (size_t)(2 + ks_max) * n_max;                          // int32 per (image, pass)
-  const size_t tmp_stride = align256((size_t)max_crop_h * out_w * 3);
-  const size_t desc_bytes = align256(sizeof(PpDesc) * (size_t)B), aug_bytes = align256(sizeof(PpAug) * (size_t)B);
-  const size_t table_bytes = align256(table_stride * 4 * 2 * (size_t)B), tmp_bytes = align256(tmp_stride * (size_t)B);
-  const size_t win_bytes = out_u8 ? 0 : (size_t)B * out_h * out_w * 3;                 // the colour stage works in out_u8 when it is asked for
-  HIPCHK(E, E->pp_ws.reserve(desc_bytes + aug_bytes + table_bytes + tmp_bytes + win_bytes));
+  const PpLayout lay(B, max_crop_h, ks_max, out_h, out_w, false, false);
+  HIPCHK(E, E->pp_ws.reserve(lay.total));
   char* base = (char*)E->pp_ws.p;
   PpDesc* descs_dev = (PpDesc*)base;
-  PpAug* augs_dev = (PpAug*)(base + desc_bytes);
-  int32_t* tables = (int32_t*)(base + desc_bytes + aug_bytes);
-  uint8_t* tmp = (uint8_t*)(base + desc_bytes + aug_bytes + table_bytes);
-  uint8_t* win = out_u8 ? out_u8 : tmp + tmp_bytes;
+  HIPCHK(E, hipMemcpyAsync(descs_dev, descs, sizeof(PpDesc) * (size_t)B, hipMemcpyHostToDevice, s));
+  HIPCHK(E, launch_preprocess(src, descs_dev, B, max_crop_h, ks_max, out_h, out_w, (int32_t*)(base + lay.tables), lay.table_stride,
+                              (uint8_t*)(base + lay.tmp), lay.tmp_stride, mean, stdv, out, out_dtype, out_u8, s));
+  return 0;
+}
+
+int mvlpt_preprocess_aug(void* h, const uint8_t* src, int64_t src_bytes, const MvlptImageDesc* descs, const MvlptAugmentDesc* aug, int B,
+                         int out_h, int out_w, int fill_outside, const float* mean, const float* stdv, void* out, int out_dtype,
+                         uint8_t* out_u8, mvlpt_stream_t stream) {
+  static_assert(sizeof(MvlptAugmentDesc) == sizeof(PpAug) && MVLPT_AUG_MAX_HOLES == PP_AUG_MAX_HOLES, "descriptor layouts must match");
+  Engine* E = (Engine*)h;
+  if (!E) return MVLPT_ERR_ARG;
+  if (B < 0 || (fill_outside != 0 && fill_outside != 1)) return fail(E, MVLPT_ERR_ARG, "preprocess_aug: negative batch, or fill_outside is not 0 or 1");
+  if (B == 0) return 0;
+  if (!aug && !fill_outside) return mvlpt_preprocess(h, src, src_bytes, descs, B, out_h, out_w, mean, stdv, out, out_dtype, out_u8, stream);
+  if (!src || !descs || out_h <= 0 || out_w <= 0 || (int64_t)out_h * out_w > (1 << 29) || !mean || !stdv || (!out && !out_u8))
+    return fail(E, MVLPT_ERR_ARG, "preprocess_aug: null pointer or empty / oversized output");
+  if (out && out_dtype != DT_F32 && out_dtype != DT_F16 && out_dtype != DT_BF16) return fail(E, MVLPT_ERR_ARG, "preprocess_aug: bad out_dtype");
+  int max_crop_h = 0, ks_max = 1;
+  if (int rc = pp_check(E, "preprocess_aug", "box outside the image, image outside src, or window outside the resized image without fill_outside",
+                        descs, aug, B, src_bytes, out_h, out_w, fill_outside, &max_crop_h, &ks_max))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  const PpLayout lay(B, max_crop_h, ks_max, out_h, out_w, true, !out_u8);            // the colour stage works in out_u8 when it is asked for
+  HIPCHK(E, E->pp_ws.reserve(lay.total));
+  char* base = (char*)E->pp_ws.p;
+  PpDesc* descs_dev = (PpDesc*)base;
+  PpAug* augs_dev = (PpAug*)(base + lay.augs);
   HIPCHK(E, hipMemcpyAsync(descs_dev, descs, sizeof(PpDesc) * (size_t)B, hipMemcpyHostToDevice, s));
   if (aug) HIPCHK(E, hipMemcpyAsync(augs_dev, aug, sizeof(PpAug) * (size_t)B, hipMemcpyHostToDevice, s));
   else HIPCHK(E, hipMemsetAsync(augs_dev, 0, sizeof(PpAug) * (size_t)B, s));
-  HIPCHK(E, launch_preprocess_aug(src, descs_dev, augs_dev, B, max_crop_h, ks_max, out_h, out_w, tables, table_stride, tmp, tmp_stride, win,
+  HIPCHK(E, launch_preprocess_aug(src, descs_dev, augs_dev, B, max_crop_h, ks_max, out_h, out_w, (int32_t*)(base + lay.tables),
+                                  lay.table_stride, (uint8_t*)(base + lay.tmp), lay.tmp_stride, out_u8 ? out_u8 : (uint8_t*)(base + lay.win),
                                   mean, stdv, out, out_dtype, s));
   return 0;
 }
@@ -2677,7 +2669,7 @@ struct JpegLayout {
 extern "C" {
 
 int mvlpt_jpeg_probe(const uint8_t* bytes, int64_t n, MvlptJpegInfo* info) {
-  if (!bytes || !info || n < 0) { g_create_err = "jpeg_probe: null argument or negative size"; return MVLPT_ERR_ARG; }
+  if (!bytes || !info || n < 0) return fail(nullptr, MVLPT_ERR_ARG, "jpeg_probe: null argument or negative size");
   jpeg::Parsed P;
   jpeg::parse(bytes, (size_t)n, &P);
   if (P.info.route != jpeg::ROUTE_DEVICE) P.info.n_segments = 0;
@@ -2686,7 +2678,7 @@ int mvlpt_jpeg_probe(const uint8_t* bytes, int64_t n, MvlptJpegInfo* info) {
 }
 
 int mvlpt_jpeg_workspace_bytes(const MvlptJpegInfo* infos, int B, int64_t* bytes) {
-  if (!bytes || B < 0 || (B > 0 && !infos)) { g_create_err = "jpeg_workspace_bytes: null argument or negative batch"; return MVLPT_ERR_ARG; }
+  if (!bytes || B < 0 || (B > 0 && !infos)) return fail(nullptr, MVLPT_ERR_ARG, "jpeg_workspace_bytes: null argument or negative batch");
   size_t n_images = 0, n_segs = 0;
   int64_t blocks = 0, pix = 0;
   for (int b = 0; b < B; ++b) {
@@ -2695,7 +2687,7 @@ int mvlpt_jpeg_workspace_bytes(const MvlptJpegInfo* infos, int B, int64_t* bytes
     memcpy(&f, &infos[b], sizeof(f));
     const bool ok = f.height > 0 && f.width > 0 && (int64_t)f.height * f.width <= jpeg::MAX_PIXELS && (f.components == 1 || f.components == 3) &&
                     f.h_samp >= 1 && f.h_samp <= 4 && f.v_samp >= 1 && f.v_samp <= 4 && f.n_segments >= 1;
-    if (!ok) { g_create_err = "jpeg_workspace_bytes: info " + std::to_string(b) + " is not one mvlpt_jpeg_probe returns"; return MVLPT_ERR_ARG; }
+    if (!ok) return fail(nullptr, MVLPT_ERR_ARG, "jpeg_workspace_bytes: info " + std::to_string(b) + " is not one mvlpt_jpeg_probe returns");
     const jpeg::Geom g = jpeg::geometry(f);
     ++n_images; n_segs += (size_t)f.n_segments; blocks += g.total_blocks; pix += g.total_plane_bytes;
   }
@@ -2775,17 +2767,15 @@ int mvlpt_jpeg_decode(void* h, const uint8_t* src_host, const uint8_t* src_dev, 
 
 int mvlpt_op_jpeg_entropy(const uint8_t* file_host, int64_t n, const uint8_t* file_dev, void* ws, int64_t ws_bytes, int16_t* coefs,
                           int64_t coef_blocks, int32_t* status_dev, mvlpt_stream_t stream) {
-  if (!file_host || !file_dev || !ws || !coefs || !status_dev || n < 0) { g_create_err = "op_jpeg_entropy: null argument"; return MVLPT_ERR_ARG; }
+  if (!file_host || !file_dev || !ws || !coefs || !status_dev || n < 0) return fail(nullptr, MVLPT_ERR_ARG, "op_jpeg_entropy: null argument");
   static thread_local jpeg::Parsed P;
   static thread_local std::vector<uint8_t> host;
   jpeg::parse(file_host, (size_t)n, &P);
-  if (P.info.route != jpeg::ROUTE_DEVICE) { g_create_err = "op_jpeg_entropy: route " + std::to_string(P.info.route) + ", not a file the device decodes"; return MVLPT_ERR_UNSUPPORTED; }
+  if (P.info.route != jpeg::ROUTE_DEVICE) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "op_jpeg_entropy: route " + std::to_string(P.info.route) + ", not a file the device decodes");
   const jpeg::Geom g = jpeg::geometry(P.info);
   const size_t need = 4096 + 8 * P.segs.size();
-  if (coef_blocks != g.total_blocks || ws_bytes < (int64_t)need || ((uintptr_t)ws & 15)) {
-    g_create_err = "op_jpeg_entropy: coef_blocks must be " + std::to_string(g.total_blocks) + " and ws hold " + std::to_string(need) + " bytes, 16-byte aligned";
-    return MVLPT_ERR_ARG;
-  }
+  if (coef_blocks != g.total_blocks || ws_bytes < (int64_t)need || ((uintptr_t)ws & 15))
+    return fail(nullptr, MVLPT_ERR_ARG, "op_jpeg_entropy: coef_blocks must be " + std::to_string(g.total_blocks) + " and ws hold " + std::to_string(need) + " bytes, 16-byte aligned");
   static_assert(sizeof(jpeg::ImgDesc) <= 512 && sizeof(jpeg::Tables) <= 3584, "the op's scratch layout");
   host.assign(need, 0);
   const jpeg::ImgDesc d = jpeg::describe(P, 0, 0, 0, 0, 0, 0, 0);
@@ -2802,8 +2792,8 @@ int mvlpt_op_jpeg_entropy(const uint8_t* file_host, int64_t n, const uint8_t* fi
 }
 
 int mvlpt_op_jpeg_idct(const int16_t* coefs, const uint8_t* quant, int n_blocks, int blocks_w, uint8_t* plane, mvlpt_stream_t stream) {
-  if (!coefs || !quant || !plane || n_blocks <= 0 || blocks_w <= 0 || n_blocks % blocks_w || blocks_w > (1 << 20) || ((uintptr_t)plane & 7)) {
-    g_create_err = "op_jpeg_idct: null / misaligned pointer, or n_blocks is not a positive multiple of blocks_w"; return MVLPT_ERR_ARG; }
+  if (!coefs || !quant || !plane || n_blocks <= 0 || blocks_w <= 0 || n_blocks % blocks_w || blocks_w > (1 << 20) || ((uintptr_t)plane & 7))
+    return fail(nullptr, MVLPT_ERR_ARG, "op_jpeg_idct: null / misaligned pointer, or n_blocks is not a positive multiple of blocks_w");
   jpeg::PlaneDesc p = {};
   p.n_blocks = n_blocks; p.blocks_w = blocks_w; p.plane_w = blocks_w * 8;
   OPCHK(launch_jpeg_idct_one(p, quant, coefs, plane, (hipStream_t)stream));
@@ -2814,13 +2804,13 @@ int mvlpt_op_jpeg_colour(const uint8_t* planes, const int64_t* plane_off, const 
                          int width, uint8_t* dst, mvlpt_stream_t stream) {
   const bool samp_ok = (hs == 1 && vs == 1) || (hs == 2 && vs == 1) || (hs == 2 && vs == 2);
   if (!planes || !plane_off || !plane_w || !dst || (components != 1 && components != 3) || !samp_ok || height <= 0 || width <= 0 ||
-      (int64_t)height * width > jpeg::MAX_PIXELS) { g_create_err = "op_jpeg_colour: null / invalid argument"; return MVLPT_ERR_ARG; }
+      (int64_t)height * width > jpeg::MAX_PIXELS) return fail(nullptr, MVLPT_ERR_ARG, "op_jpeg_colour: null / invalid argument");
   jpeg::ImgDesc d;
   memset(&d, 0, sizeof(d));
   d.width = width; d.height = height; d.ncomp = components; d.hs = components == 1 ? 1 : hs; d.vs = components == 1 ? 1 : vs;
   for (int c = 0; c < components; ++c) {
     const int need_w = c == 0 ? width : (width + d.hs - 1) / d.hs;
-    if (plane_off[c] < 0 || plane_w[c] < need_w) { g_create_err = "op_jpeg_colour: a plane is narrower than its component"; return MVLPT_ERR_ARG; }
+    if (plane_off[c] < 0 || plane_w[c] < need_w) return fail(nullptr, MVLPT_ERR_ARG, "op_jpeg_colour: a plane is narrower than its component");
     d.plane_off[c] = plane_off[c]; d.plane_w[c] = plane_w[c];
   }
   OPCHK(launch_jpeg_colour_one(d, planes, dst, (hipStream_t)stream));

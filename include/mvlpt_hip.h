@@ -79,6 +79,23 @@ typedef struct MvlptResNetArch {
 int mvlpt_create_resnet(const MvlptArch* arch, const MvlptResNetArch* rn, void** handle);
 /* switch the precision mode (takes effect at the next tower forward) */
 int mvlpt_set_precision(void* handle, int mode);
+/* The activation of the MLP in every transformer block of both towers (the text tower of a ResNet handle included).
+ *   MVLPT_ACT_QUICKGELU  (default) x * sigmoid(1.702 x), clip/model.py:162-164: the archives clip.load downloads.  Fused into the
+ *                        epilogues of the two MLP GEMMs.
+ *   MVLPT_ACT_GELU       nn.GELU, the erf form x * Phi(x): CLIP checkpoints of the same architecture and the same state-dict keys
+ *                        that were trained with it.  The MLP-up GEMM stores its fp32 pre-activation and a stand-alone pass applies
+ *                        GELU (backward: GELU' on the fp32 dA) and writes the next GEMM's operand: two more element-wise passes
+ *                        over [tokens, 4 width] per block and direction, and one fp32 scratch buffer of that size per tower
+ *                        (plus [rows, 4 width] for the compact last block), counted by mvlpt_text_workspace_bytes only under this
+ *                        setting.  The image tower's packed residual stream is not taken, and ln_2 is not folded into the
+ *                        MLP-up GEMM (ln_1 still is).  Nothing else changes; MvlptArch does not carry the setting.
+ * A setting like mvlpt_set_precision: legal before the first tower forward and after any completed step.  Between a forward with
+ * save_for_bwd = 1 and the backward of that tower (and between mvlpt_image_fwd_begin and _resume) it returns MVLPT_ERR_STATE with a
+ * message and changes nothing: the saved pre-activations belong to the activation of their forward.  Any other value:
+ * MVLPT_ERR_ARG, nothing is touched. */
+enum { MVLPT_ACT_QUICKGELU = 0, MVLPT_ACT_GELU = 1 };
+int mvlpt_set_activation(void* handle, int activation);
+int mvlpt_get_activation(void* handle, int* activation);
 /* LayerNorm folding (no counterpart in the reference, which calls nn.LayerNorm as its own op, clip/model.py:186-187): inside a
  * tower the GEMM in front of a LayerNorm (out-projection / MLP down-projection + fp32 residual) also writes round16(x * gamma)
  * and per-row partial sums, and the GEMM behind it (QKV / MLP up-projection) applies mean and rstd in its epilogue — the
@@ -286,6 +303,20 @@ int mvlpt_op_gemm(int dtype, int epi, const void* A, const void* Bt, int M, int 
 int mvlpt_op_gemm_ex(int dtype, int epi, const void* A, const void* Bt, int M, int N, int K, const float* bias, const void* aux,
                      const float* resid, void* out, void* out2, int a_split, int lda, int ldo, int ldb, int w8_exp, int out_lo8,
                      mvlpt_stream_t stream);
+/* The stand-alone activation pass of MVLPT_ACT_GELU, kernel level (both are also instantiated for MVLPT_ACT_QUICKGELU, which the
+ * engine never takes: it reproduces epilogues 1 / 5 bit for bit from the fp32 pre-activation epilogue 4 stores).
+ *   forward:  out = act(u32), u16_out (optional, 16-bit [M, N] dense) = u32 rounded once;
+ *   backward: out = da32 * act'(u16), u16 the saved pre-activation (16-bit [M, N] dense).
+ * u32 / da32: fp32 [M, N] at a pitch of ld_in floats (0 = dense).  `out` is the A operand of the next GEMM in out_format
+ * MVLPT_ACT_OUT_SINGLE (16-bit [M, N]), _PAIR (hi|lo pair [M, 2N]) or _MIXED (mixed pair, [hi | e5m2 residual bytes | unused], same
+ * pitch) at a pitch of ld_out 16-bit elements (0 = dense: N, or 2N for the pairs).  dtype: MVLPT_DT_F16 / _BF16, the 16-bit type.
+ * N and both pitches are multiples of 8, every pointer is 16-byte aligned, M is arbitrary.  An unknown activation or format, a pitch
+ * below the row width or not a multiple of 8, a null or misaligned pointer: MVLPT_ERR_ARG, nothing is launched or written. */
+enum { MVLPT_ACT_OUT_SINGLE = 0, MVLPT_ACT_OUT_PAIR = 1, MVLPT_ACT_OUT_MIXED = 2 };
+int mvlpt_op_activation_fwd(int dtype, int activation, const float* u32, int ld_in, int M, int N, int out_format, void* out, int ld_out,
+                            void* u16_out, mvlpt_stream_t stream);
+int mvlpt_op_activation_bwd(int dtype, int activation, const float* da32, int ld_in, const void* u16, int M, int N, int out_format,
+                            void* out, int ld_out, mvlpt_stream_t stream);
 /* Which kernel a GEMM launch on `stream` would use, without launching (the choice depends on the tile counts against the stream's
  * compute units; fold_ntp > 0: a folded consumer, mvlpt_op_gemm_folded, with that many slots per row).  Returns the kernel family
  * (MVLPT_GEMM_*) and its tile / LDS-ring depth through the optional pointers, or a negative error. */

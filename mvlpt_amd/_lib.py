@@ -22,6 +22,8 @@ EPI_STORE16, EPI_GELU, EPI_RESID32, EPI_GELUBWD, EPI_STORE32, EPI_GELU_SPLIT, EP
 # kernel families mvlpt_op_gemm_route reports (MVLPT_GEMM_* in the header)
 GEMM_BT_128x128_R2, GEMM_BT_128x128_R4, GEMM_BT_256x128_R3, GEMM_BT_256x256_R2, GEMM_PHASED, GEMM_PC, GEMM_PCP = 1, 2, 3, 4, 5, 6, 7
 PREC_FAST, PREC_SPLIT_GRAD, PREC_SPLIT_ALL = 0, 1, 2
+ACT_QUICKGELU, ACT_GELU = 0, 1                           # MVLPT_ACT_*
+ACT_OUT_SINGLE, ACT_OUT_PAIR, ACT_OUT_MIXED = 0, 1, 2    # MVLPT_ACT_OUT_*
 ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4      # MVLPT_ERR_*
 NEAREST_MAX_K, NEAREST_MAX_ROWS = 64, 65535 * 8      # MVLPT_NEAREST_MAX_K, MVLPT_NEAREST_MAX_ROWS
 EVAL_SORT_TILE, EVAL_MAX_ROWS, EVAL_POINTS, EVAL_FLAG_NONFINITE, EVAL_FLAG_SOFT_TARGET = 4096, 1 << 20, 11, 1, 2      # MVLPT_EVAL_*
@@ -90,6 +92,8 @@ SIGNATURES = {
     "mvlpt_create_resnet": (_i, [C.POINTER(MvlptArch), C.POINTER(MvlptResNetArch), C.POINTER(_vp)]),
     "mvlpt_destroy": (_i, [_vp]),
     "mvlpt_set_precision": (_i, [_vp, _i]),
+    "mvlpt_set_activation": (_i, [_vp, _i]),
+    "mvlpt_get_activation": (_i, [_vp, C.POINTER(_i)]),
     "mvlpt_trim": (_i, [_vp]),
     "mvlpt_debug_checksums": (_i, [_vp, _i, C.POINTER(C.c_uint64), _i]),
     "mvlpt_set_ln_fold": (_i, [_vp, _i, _i]),
@@ -123,6 +127,8 @@ SIGNATURES = {
     "mvlpt_cross_entropy": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "mvlpt_op_gemm": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvlpt_op_gemm_ex": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_activation_fwd": (_i, [_i, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "mvlpt_op_activation_bwd": (_i, [_i, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mvlpt_op_gemm_route": (_i, [_i, _i, _i, _i, _i, _i, _i, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "mvlpt_op_gemm_split": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mvlpt_op_layernorm_fwd_split": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _vp]),

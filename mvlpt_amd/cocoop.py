@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from .config import read_activation
 from .model import (FrozenCLIP, PretokenizedPrompts, _text_inputs, apply_text_act_ckpt, class_prompt_tables, image_conditioned_ctx,
                     register_class_tables)
 from .trainer import MVLPT, TrainerX
@@ -209,7 +210,8 @@ class CoCoOp(MVLPT):
             sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED)
         # fp16 / amp / fp32 all end in split_all (CustomCLIP raises the default mode); GRAD_PRECISION = "fast" keeps single operands
         prec = "split_all" if cfg.TRAINER.COCOOP.PREC == "fp32" else cfg.TRAINER.MVLPT.GRAD_PRECISION
-        clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec)
+        clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec,
+                                activation=read_activation(cfg))
         self.model = CustomCLIP(cfg, classnames, clip_model, pretokenized=pretok)
         self.train_prompt_learner_only()                                # :220-241
 

@@ -47,12 +47,26 @@ class CfgNode(dict):
             node[parts[-1]] = val
 
 
+ACTIVATIONS = ("quick_gelu", "gelu")
+
+
+def read_activation(cfg) -> str:
+    """MODEL.BACKBONE.ACTIVATION (absent: "quick_gelu"), checked: the MLP activation every trainer hands to its engine."""
+    act = cfg.MODEL.BACKBONE.get("ACTIVATION", "quick_gelu")
+    if act not in ACTIVATIONS:
+        raise ValueError(f"MODEL.BACKBONE.ACTIVATION = {act!r}: the accepted values are 'quick_gelu' and 'gelu'")
+    return act
+
+
 def get_cfg_default() -> CfgNode:
     CN = CfgNode
     cfg = CN()
     cfg.SEED = 1
     cfg.OUTPUT_DIR = "./output"
-    cfg.MODEL = CN(BACKBONE=CN(NAME="ViT-B/16"), INIT_WEIGHTS="")
+    # ACTIVATION (not in the reference, whose clip/model.py:162-164 has QuickGELU compiled in): the MLP activation of both towers.
+    # "quick_gelu": the archives clip.load downloads.  "gelu": a checkpoint with the same architecture and state-dict keys that was
+    # trained with nn.GELU (the erf form); with the default its logits and gradients would come out of the wrong function without an error.
+    cfg.MODEL = CN(BACKBONE=CN(NAME="ViT-B/16", ACTIVATION="quick_gelu"), INIT_WEIGHTS="")
     # TRANSFORMS and the parameters of its augmentations: Dassl's names and defaults (mvlpt_amd.transforms.build_device_transform; the
     # launcher's --transforms).  On the command line the list comes as JSON: INPUT.TRANSFORMS '["random_crop", "random_flip", "cutout"]'
     cfg.INPUT = CN(SIZE=(224, 224), TRANSFORMS=["random_resized_crop", "random_flip", "normalize"], COLORJITTER_B=0.4, COLORJITTER_C=0.4,

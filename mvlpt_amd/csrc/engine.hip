@@ -153,6 +153,8 @@ struct TowerState {
   std::vector<void*> qkv, attn, u;       // per layer (all equal when !saved)
   std::vector<float*> lse;
   void *h16 = nullptr, *a16 = nullptr;
+  float* act32 = nullptr;                // exact GELU only: fp32 [T, 4d] between an MLP GEMM and the stand-alone activation pass
+  bool bwd_done = false;                 // a backward has run on the saved state (mvlpt_set_activation)
   float* dx32 = nullptr; void *dx16 = nullptr, *du16 = nullptr, *dO16 = nullptr, *dqkv16 = nullptr; float* dh32 = nullptr;
   float* delta = nullptr; float* scale_dev = nullptr;
   std::vector<char> skip;                // layer skipped (reference deep-prompt quirk, Appendix A.3)
@@ -178,6 +180,7 @@ struct Compact {
   float *out32 = nullptr, *dout32 = nullptr;                   // closing LayerNorm output (the projection's input) and its gradient
   void *a16 = nullptr, *h16 = nullptr, *g16 = nullptr, *u16 = nullptr;      // attention output, ln_2 output, GELU output, pre-GELU
   float *dx32 = nullptr, *dh32 = nullptr; void *dx16 = nullptr, *dO16 = nullptr, *du16 = nullptr;
+  float* act32 = nullptr;                // exact GELU only: fp32 [R, 4d] (TowerState::act32 on the compact rows)
 };
 
 enum ProfClass { PC_GEMM = 0, PC_ATTN_FWD, PC_ATTN_BWD, PC_LN_FWD, PC_LN_BWD, PC_GLUE, PC_HEAD, PC_ATTN_FWD_IMG, PC_COUNT };
@@ -196,6 +199,7 @@ struct Engine {
   int dt = DT_F16;
   int prec_mode = MVLPT_PREC_SPLIT_GRAD;
   int fold_mode = 2;    // LayerNorm folding: 0 off, 1 image tower, 2 both towers (MVLPT_LN_FOLD, mvlpt_set_ln_fold)
+  int act = ACT_QUICKGELU;    // the MLP activation of both towers (mvlpt_set_activation; DESIGN.md "Exact GELU")
   int text_act_ckpt = 1;      // segments of the text tower's activation checkpointing (mvlpt_set_text_act_ckpt; 1: everything is saved)
   int fold_min_rows = 1024;   // towers with fewer token rows keep the stand-alone LayerNorm (a handful of tiles: nothing to win)
   bool fold_ready = false;
@@ -356,7 +360,8 @@ std::vector<int> ckpt_plan(int layers, int segments) {
 // `exact` (split-precision mode): every 16-bit operand buffer holds a hi|lo pair (twice the columns) and QKV / dO are fp32
 // segments > 1 (a saving text tower under activation checkpointing): the per-layer tensors shrink to the m slots of the largest
 // segment (the last one), the k segment inputs stay (x[0] and k - 1 boundary buffers)
-size_t tower_bytes(const TowerW& W, int N, int L, bool save, bool exact, int segments = 1) {
+// gelu (Engine::act == ACT_GELU): one more fp32 [T, 4d] buffer, the scratch of the stand-alone activation pass
+size_t tower_bytes(const TowerW& W, int N, int L, bool save, bool exact, bool gelu, int segments = 1) {
   const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1;
   const std::vector<int> seg = ckpt_plan(W.layers, save ? segments : 1);
   const size_t k = seg.size() - 1, nl = k > 1 ? (size_t)(seg[k] - seg[k - 1]) : (size_t)W.layers;      // slots of the per-layer tensors
@@ -373,6 +378,7 @@ size_t tower_bytes(const TowerW& W, int N, int L, bool save, bool exact, int seg
     b += 2 * align256(T * d * 4) + 2 * align256(T * d * 2 * X) + (align256(T * 4 * d * 2) + align256(T * 3 * d * 2)) * X + align256(T * 128);
     b += align256((size_t)N * H * L * 4) + 256;
   }
+  if (gelu) b += align256(T * 4 * d * 4);                            // act32
   return b + 4096;
 }
 // row pitch (16-bit elements) of the pair tensors between the two MLP GEMMs ([T, 2 * 4d]: a16, du16; GemmArgs::lda / ldo): rows
@@ -380,7 +386,8 @@ size_t tower_bytes(const TowerW& W, int N, int L, bool save, bool exact, int seg
 int wide_pitch(int cols) {
   return (4 * cols) % 4096 == 0 ? 2 * cols + 64 : 0;
 }
-void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool save, bool causal, bool exact, int xs, int segments = 1) {
+void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool save, bool causal, bool exact, int xs, bool gelu,
+                 int segments = 1) {
   const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1; const int nl = W.layers;
   st = TowerState();
   st.N = N; st.L = L; st.d = (int)d; st.H = (int)H; st.layers = nl; st.saved = save; st.causal = causal; st.exact = exact;
@@ -434,6 +441,7 @@ void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool s
     st.delta = bp.take<float>((size_t)N * H * L);
     st.scale_dev = bp.take<float>(4);   // {scale, 1/scale, amax scratch, pad}
   }
+  if (gelu) st.act32 = bp.take<float>(T * 4 * d);
   st.valid = true;
 }
 
@@ -506,6 +514,35 @@ Fold fold_consumer(const TowerState& st, int which, const Linear& L) {
   return f;
 }
 
+// ---- The MLP's activation (Engine::act).  QuickGELU lives in the GEMM epilogues (EPI_GELU* / EPI_GELUBWD*).  The exact GELU of a
+// checkpoint trained with nn.GELU is a pass of its own (activation.hip): the GEMM stores fp32 into `scratch` (EPI_STORE32: the activation
+// sees u = acc + bias unrounded) and the pass writes the A operand of the next GEMM in the tower's format xs at the pitch ldo.
+// mlp_up: a16 = act(h16 fc^T + bias), u16 (optional) = the saved pre-activation.  f: the consumer side of a folded ln_2 (QuickGELU only)
+int mlp_up(Engine* E, const void* h16, WRef fc, const float* bias, int M, int d, int xs, void* a16, int ldo, void* u16, float* scratch,
+           const Fold* f, hipStream_t s) {
+  if (E->act == ACT_QUICKGELU) {
+    HIPCHK(E, gemm(E, xs ? EPI_GELU_SPLIT : EPI_GELU, h16, fc, M, 4 * d, d, bias, nullptr, nullptr, a16, u16, s, -1, xs, f, 0, ldo));
+    return 0;
+  }
+  if (f || !scratch) return fail(E, MVLPT_ERR_STATE, "exact GELU: the MLP-up GEMM has no folded form and needs its scratch");
+  HIPCHK(E, gemm(E, EPI_STORE32, h16, fc, M, 4 * d, d, bias, nullptr, nullptr, scratch, nullptr, s, -1, xs));
+  ProfScope ps(E, s, PC_GLUE, 10.0 * M * 4 * d, (double)M * 4 * d * (4.0 + (xs == 1 ? 4.0 : xs ? 3.0 : 2.0) + (u16 ? 2.0 : 0.0)));
+  HIPCHK(E, launch_act_fwd(E->dt, E->act, ActArgs{scratch, 0, a16, xs, ldo, u16, M, 4 * d}, s));
+  return 0;
+}
+// mlp_up_bwd: du16 = (dx16 pr) * act'(u16), the gradient at the pre-activation in the format xs
+int mlp_up_bwd(Engine* E, const void* dx16, WRef prt, int M, int d, int xs, const void* u16, void* du16, int ldo, float* scratch, hipStream_t s) {
+  if (E->act == ACT_QUICKGELU) {
+    HIPCHK(E, gemm(E, xs ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, dx16, prt, M, 4 * d, d, nullptr, u16, nullptr, du16, nullptr, s, -1, xs, nullptr, 0, ldo));
+    return 0;
+  }
+  if (!scratch) return fail(E, MVLPT_ERR_STATE, "exact GELU: the saved state was carved without the activation scratch");
+  HIPCHK(E, gemm(E, EPI_STORE32, dx16, prt, M, 4 * d, d, nullptr, nullptr, nullptr, scratch, nullptr, s, -1, xs));
+  ProfScope ps(E, s, PC_GLUE, 14.0 * M * 4 * d, (double)M * 4 * d * (6.0 + (xs == 1 ? 4.0 : xs ? 3.0 : 2.0)));
+  HIPCHK(E, launch_act_bwd(E->dt, E->act, ActArgs{scratch, 0, du16, xs, ldo, const_cast<void*>(u16), M, 4 * d}, s));
+  return 0;
+}
+
 // ResidualAttentionBlock.forward (clip/model.py:185-188) on token buffers.  Split towers (st.xs; towers that carry a gradient, and every
 // tower under MVLPT_PREC_SPLIT_ALL): every GEMM A operand is a 16-bit hi|lo pair (~22 bits), the attention core runs in fp32, and the
 // pair rows between the two MLP GEMMs have the pitch st.wide_pitch.
@@ -523,12 +560,13 @@ int block_fwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s, 
   HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, st.h16, B.qkv.fw(), T, 3 * d, d, ln1_folded ? B.qkv.fold_b : B.qkv.b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, xs,
                  ln1_folded ? &fq : nullptr));
   if (int rc = attn_fwd(E, st, l, 0, true, s)) return rc;
-  const bool p2 = fold_producer(E, st, 1, T, d, d, B.ln2, s, &fo);
+  // (exact GELU: ln_2 stays a pass of its own: its consumer stores fp32, which has no folded epilogue; ln_1 is folded as ever)
+  const bool p2 = E->act == ACT_QUICKGELU && fold_producer(E, st, 1, T, d, d, B.ln2, s, &fo);
   HIPCHK(E, gemm(E, p2 ? EPI_RESID32_LN : EPI_RESID32, st.attn[l], B.o.fw(), T, d, d, B.o.b, nullptr, xin, xmid, nullptr, s, -1, xs, p2 ? &fo : nullptr));
   if (p2) ff = fold_consumer(st, 1, B.fc);
   else HIPCHK(E, ln_fwd(E, E->dt, xmid, nullptr, 1, B.ln2, st.h16, T, d, s, xs));
-  HIPCHK(E, gemm(E, xs ? EPI_GELU_SPLIT : EPI_GELU, st.h16, B.fc.fw(), T, 4 * d, d, p2 ? B.fc.fold_b : B.fc.b, nullptr, nullptr, st.a16, st.saved ? st.u[l] : nullptr, s, -1, xs,
-                 p2 ? &ff : nullptr, 0, wp));
+  if (int rc = mlp_up(E, st.h16, B.fc.fw(), p2 ? B.fc.fold_b : B.fc.b, T, d, xs, st.a16, wp, st.saved ? st.u[l] : nullptr, st.act32,
+                      p2 ? &ff : nullptr, s)) return rc;
   const bool p1 = next_ln1 && fold_producer(E, st, 0, T, d, 4 * d, *next_ln1, s, &fp);
   HIPCHK(E, gemm(E, p1 ? EPI_RESID32_LN : EPI_RESID32, st.a16, B.pr.fw(), T, d, 4 * d, B.pr.b, nullptr, xmid, xout, nullptr, s, -1, xs, p1 ? &fp : nullptr,
                  wp, 0));
@@ -543,6 +581,7 @@ int block_fwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s, 
 int block_fwd_packed(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s) {
   const Block& B = W.blocks[l];
   const int T = st.N * st.L, d = st.d;
+  if (E->act != ACT_QUICKGELU) return fail(E, MVLPT_ERR_STATE, "packed residual stream: QuickGELU only (the image forward does not take it under the exact GELU)");
   void* hi = st.x[0];
   uint8_t* lo = (uint8_t*)st.x[0] + (size_t)T * d * 2;
   Fold fq = fold_consumer(st, 0, B.qkv), fo, ff, fp;
@@ -570,7 +609,7 @@ int block_fwd_packed(Engine* E, const TowerW& W, TowerState& st, int l, hipStrea
 int block_bwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s) {
   const Block& B = W.blocks[l];
   const int T = st.N * st.L, d = st.d, xs = st.xs, wp = st.wide_pitch;
-  HIPCHK(E, gemm(E, xs ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, st.dx16, B.pr.bw(), T, 4 * d, d, nullptr, st.u[l], nullptr, st.du16, nullptr, s, -1, xs, nullptr, 0, wp));
+  if (int rc = mlp_up_bwd(E, st.dx16, B.pr.bw(), T, d, xs, st.u[l], st.du16, wp, st.act32, s)) return rc;
   // the dX GEMMs that feed a LayerNorm backward store fp32 (one 16-bit rounding less per half layer)
   HIPCHK(E, gemm(E, EPI_STORE32, st.du16, B.fc.bw(), T, d, 4 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs, nullptr, wp, 0));
   HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l + 1], nullptr, 1, B.ln2, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs));
@@ -585,14 +624,15 @@ int block_bwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s) 
 // (keys / values), then out-proj, ln_2, the MLP and the closing LayerNorm run on the R = st.N compact rows instead of R * L: ~20/24
 // of the layer's GEMM FLOPs vanish, in the forward and, when the tower has a backward, in the backward as well.
 // Bytes of the compact buffers as the workspace formulas publish them (u16, never a pair, is counted at pair width)
-size_t compact_bytes(size_t R, size_t d, size_t X) {
-  return 7 * align256(R * d * 4) + 4 * align256(R * d * 2 * X) + 3 * align256(R * d * 8 * X);
+size_t compact_bytes(size_t R, size_t d, size_t X, bool gelu) {
+  return 7 * align256(R * d * 4) + 4 * align256(R * d * 2 * X) + 3 * align256(R * d * 8 * X) + (gelu ? align256(R * d * 16) : 0);
 }
-void carve_compact(Bump& bp, Compact& c, size_t R, size_t d, size_t X) {
+void carve_compact(Bump& bp, Compact& c, size_t R, size_t d, size_t X, bool gelu) {
   c = Compact();
   for (float** p : {&c.out32, &c.dout32, &c.x32, &c.xm32, &c.xo32, &c.dx32, &c.dh32}) *p = bp.take<float>(R * d);
   for (void** p : {&c.a16, &c.h16, &c.dx16, &c.dO16}) *p = bp.take_bytes(R * d * 2 * X);
   c.g16 = bp.take_bytes(R * d * 8 * X); c.u16 = bp.take_bytes(R * d * 8); c.du16 = bp.take_bytes(R * d * 8 * X);
+  if (gelu) c.act32 = bp.take<float>(R * 4 * d);
 }
 // compact row r <-> token row rows[r] or (rows == null) row 0 of sequence r; scatter: compact -> full width
 hipError_t move_rows(const void* src, void* dst, const int32_t* rows, int R, int L, size_t row_bytes, int scatter, hipStream_t s) {
@@ -628,7 +668,7 @@ int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const
   if (ck) { dbg_ck(E, c.a16, (size_t)R * d * 2 * X, s); dbg_ck(E, c.x32, (size_t)R * d * 4, s); }
   HIPCHK(E, gemm(E, EPI_RESID32, c.a16, Bk.o.fw(), R, d, d, Bk.o.b, nullptr, c.x32, c.xm32, nullptr, s, -1, xs));
   HIPCHK(E, ln_fwd(E, E->dt, c.xm32, nullptr, 1, Bk.ln2, c.h16, R, d, s, xs));
-  HIPCHK(E, gemm(E, xs ? EPI_GELU_SPLIT : EPI_GELU, c.h16, Bk.fc.fw(), R, 4 * d, d, Bk.fc.b, nullptr, nullptr, c.g16, st.saved ? c.u16 : nullptr, s, -1, xs));
+  if (int rc = mlp_up(E, c.h16, Bk.fc.fw(), Bk.fc.b, R, d, xs, c.g16, 0, st.saved ? c.u16 : nullptr, c.act32, nullptr, s)) return rc;
   HIPCHK(E, gemm(E, EPI_RESID32, c.g16, Bk.pr.fw(), R, d, 4 * d, Bk.pr.b, nullptr, c.xm32, c.xo32, nullptr, s, -1, xs));
   HIPCHK(E, ln_fwd(E, DT_F32, c.xo32, nullptr, 1, ln_close, c.out32, R, d, s));
   return 0;
@@ -643,7 +683,7 @@ int last_block_bwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const
   const Block& Bk = W.blocks[l];
   const bool cls = q_rows > 0 && !xs;
   HIPCHK(E, ln_bwd(E, c.dout32, DT_F32, c.xo32, nullptr, 1, ln_close, nullptr, c.dx32, c.dx16, R, d, s, -1, xs));
-  HIPCHK(E, gemm(E, xs ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, c.dx16, Bk.pr.bw(), R, 4 * d, d, nullptr, c.u16, nullptr, c.du16, nullptr, s, -1, xs));
+  if (int rc = mlp_up_bwd(E, c.dx16, Bk.pr.bw(), R, d, xs, c.u16, c.du16, 0, c.act32, s)) return rc;
   HIPCHK(E, gemm(E, EPI_STORE32, c.du16, Bk.fc.bw(), R, d, 4 * d, nullptr, nullptr, nullptr, c.dh32, nullptr, s, -1, xs));
   HIPCHK(E, ln_bwd(E, c.dh32, DT_F32, c.xm32, nullptr, 1, Bk.ln2, c.dx32, c.dx32, c.dx16, R, d, s, -1, xs));
   HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, c.dx16, Bk.o.bw(), R, d, d, nullptr, nullptr, nullptr, c.dO16, nullptr, s, -1, xs));
@@ -1099,6 +1139,26 @@ int mvlpt_set_precision(void* h, int mode) {
   return 0;
 }
 
+int mvlpt_set_activation(void* h, int act) {
+  Engine* E = (Engine*)h;
+  if (!E) return MVLPT_ERR_ARG;
+  if (act != MVLPT_ACT_QUICKGELU && act != MVLPT_ACT_GELU)
+    return fail(E, MVLPT_ERR_ARG, "set_activation: the activation is MVLPT_ACT_QUICKGELU or MVLPT_ACT_GELU");
+  // a saved state was carved for, and its pre-activations belong to, the activation of its forward: the backward must see the same
+  auto pending = [](const TowerState& st) { return st.valid && st.saved && !st.bwd_done; };
+  if (E->ip.active || pending(E->vs) || pending(E->ts))
+    return fail(E, MVLPT_ERR_STATE, "set_activation: a forward has saved activations whose backward has not run (or an image forward is "
+                                    "pending); change the activation before a forward or after a completed step");
+  E->act = act;
+  return 0;
+}
+int mvlpt_get_activation(void* h, int* act) {
+  Engine* E = (Engine*)h;
+  if (!E || !act) return fail(E, MVLPT_ERR_ARG, "get_activation: null argument");
+  *act = E->act;
+  return 0;
+}
+
 int mvlpt_stream_create_cus(int cu_first, int cu_count, mvlpt_stream_t* stream) {
   if (!stream) return fail(nullptr, MVLPT_ERR_ARG, "stream_create_cus: null argument");
   const int total = device_cus();
@@ -1355,15 +1415,16 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
   const bool exact = E->prec_mode == MVLPT_PREC_SPLIT_ALL || (E->prec_mode == MVLPT_PREC_SPLIT_GRAD && save);
   const size_t X = exact ? 2 : 1;
   const size_t npatch = (size_t)B * G2;
-  size_t need = tower_bytes(E->vis, B, Lv, save, exact) + align256(npatch * E->Kp * 2) + align256(npatch * dv * 4) +
-                compact_bytes(B, dv, X) + 4096;
+  const bool gelu = E->act == ACT_GELU;
+  size_t need = tower_bytes(E->vis, B, Lv, save, exact, gelu) + align256(npatch * E->Kp * 2) + align256(npatch * dv * 4) +
+                compact_bytes(B, dv, X, gelu) + 4096;
   E->vs.valid = false;
   HIPCHK(E, E->vis_ws.reserve(need));
   Bump bp; bp.base = (char*)E->vis_ws.p; bp.cap = E->vis_ws.cap;
   void* patches = bp.take_bytes(npatch * E->Kp * 2);
   float* pe = bp.take<float>(npatch * dv);
-  carve_compact(bp, E->vc, B, dv, X);
-  carve_tower(bp, E->vis, E->vs, B, Lv, save, false, exact, split_kind(E));
+  carve_compact(bp, E->vc, B, dv, X, gelu);
+  carve_tower(bp, E->vis, E->vs, B, Lv, save, false, exact, split_kind(E), gelu);
   TowerState& st = E->vs;
   if (bp.off > bp.cap) { st.valid = false; return fail(E, MVLPT_ERR_STATE, "image_fwd_begin: the workspace carve exceeds its reservation"); }
   E->vB = B; E->v_nvpt = n_vpt; E->v_ndeep = n_deep;
@@ -1388,7 +1449,7 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
   // Packed residual stream (block_fwd_packed): fp16 tower, no prompts, nothing saved, every LayerNorm folded.  assemble_tokens
   // writes the rows in the packed format together with the row statistics of ln_1 of block 0.
   const int nt_d = dv / 128, ntp_d = (nt_d + 1) & ~1;
-  const bool packed = E->resid_packed && E->dt == DT_F16 && !save && !exact && st.fold && n_vpt == 0 && dv % 128 == 0 &&
+  const bool packed = E->resid_packed && E->dt == DT_F16 && !gelu && !save && !exact && st.fold && n_vpt == 0 && dv % 128 == 0 &&
                       ntp_d <= FOLD_NTP && E->vis.blocks[0].qkv.wg != nullptr;
   void* const xhi = st.x[0];
   uint8_t* const xlo = (uint8_t*)st.x[0] + (size_t)B * Lv * dv * 2;
@@ -1500,6 +1561,7 @@ int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, 
     ProfScope ps(E, s, PC_GLUE, 0, (double)B * n * dv * 4.0);
     HIPCHK(E, launch_reduce_prompt_rows(E->dt, st.dx32, st.dx16, B, Lv, dv, 1, n, dvpt, st.scale_dev, 0, s, 0, E->v_mask));
   }
+  st.bwd_done = true;
   return 0;
 }
 
@@ -1539,7 +1601,8 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 static size_t text_ws_bytes(Engine* E, int C, int L, bool save, bool exact, size_t ctx_rows) {
   const int dtw = E->arch.text_width;
   const size_t X = exact ? 2 : 1;
-  return tower_bytes(E->txt, C, L, save, exact, E->text_act_ckpt) + compact_bytes(C, dtw, X) + align256((size_t)C * 4) + align256(ctx_rows * 4) + 4096;
+  const bool gelu = E->act == ACT_GELU;
+  return tower_bytes(E->txt, C, L, save, exact, gelu, E->text_act_ckpt) + compact_bytes(C, dtw, X, gelu) + align256((size_t)C * 4) + align256(ctx_rows * 4) + 4096;
 }
 static bool text_exact(const Engine* E) { return E->prec_mode == MVLPT_PREC_SPLIT_ALL || E->prec_mode == MVLPT_PREC_SPLIT_GRAD; }
 
@@ -1589,12 +1652,12 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
   E->ts.valid = false;
   HIPCHK(E, E->txt_ws.reserve(need));
   Bump bp; bp.base = (char*)E->txt_ws.p; bp.cap = E->txt_ws.cap;
-  carve_compact(bp, E->tc, C, dtw, X);
+  carve_compact(bp, E->tc, C, dtw, X, E->act == ACT_GELU);
   E->eot_rows = bp.take<int32_t>(C);
   E->ctx_pos = bp.take<int32_t>(ctx_rows);
   int32_t* range_dev = ranged ? bp.take<int32_t>(range_ints) : nullptr;
   int32_t* ids_dev = ids ? bp.take<int32_t>(ids_ints) : nullptr;
-  carve_tower(bp, E->txt, E->ts, C, L, save, true, exact, split_kind(E), E->text_act_ckpt);
+  carve_tower(bp, E->txt, E->ts, C, L, save, true, exact, split_kind(E), E->act == ACT_GELU, E->text_act_ckpt);
   TowerState& st = E->ts;
   if (bp.off > bp.cap) { st.valid = false; return fail(E, MVLPT_ERR_STATE, "text_fwd: the workspace carve exceeds its reservation"); }
   E->tC = C; E->tL = L; E->t_nctx = n_ctx; E->t_per_class = ctx_per_class;
@@ -1763,6 +1826,7 @@ int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stre
     else
       HIPCHK(E, launch_gather_ctx_grad(st.dx32, E->ctx_pos, C, L, dtw, E->t_nctx, E->t_per_class, dctx, st.scale_dev, s)); }
   if (k > 1) st.saved = false;
+  st.bwd_done = true;
   return 0;
 }
 
@@ -1921,6 +1985,20 @@ int mvlpt_op_gemm_ex(int dtype, int epi, const void* A, const void* Bt, int M, i
   g.a_split = a_split; g.lda = lda; g.ldo = ldo; g.ldb = ldb; g.w8_exp = w8_exp; g.out_lo8 = out_lo8;
   OPCHK(launch_gemm(dtype, epi, g, (hipStream_t)stream));
   return 0;
+}
+// ---- stand-alone activation, kernel level (the launches mlp_up / mlp_up_bwd make under MVLPT_ACT_GELU)
+static int op_activation(const char* who, bool bwd, int dtype, int act, ActArgs a, mvlpt_stream_t stream) {
+  if (const char* why = act_check(dtype, act, bwd, a)) return fail(nullptr, MVLPT_ERR_ARG, std::string(who) + ": " + why);
+  OPCHK(bwd ? launch_act_bwd(dtype, act, a, (hipStream_t)stream) : launch_act_fwd(dtype, act, a, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_activation_fwd(int dtype, int act, const float* u32, int ld_in, int M, int N, int out_format, void* out, int ld_out,
+                            void* u16_out, mvlpt_stream_t stream) {
+  return op_activation("op_activation_fwd", false, dtype, act, ActArgs{u32, ld_in, out, out_format, ld_out, u16_out, M, N}, stream);
+}
+int mvlpt_op_activation_bwd(int dtype, int act, const float* da32, int ld_in, const void* u16, int M, int N, int out_format, void* out,
+                            int ld_out, mvlpt_stream_t stream) {
+  return op_activation("op_activation_bwd", true, dtype, act, ActArgs{da32, ld_in, out, out_format, ld_out, const_cast<void*>(u16), M, N}, stream);
 }
 int mvlpt_op_gemm_route(int dtype, int epi, int a_split, int M, int N, int K, int fold_ntp, mvlpt_stream_t stream, int* tile_m,
                         int* tile_n, int* ring) {

@@ -328,6 +328,25 @@ hipError_t launch_fold_weight(const void* W16, int ld, const float* gamma, void*
 hipError_t launch_respk_pack_rows(const float* x, void* hi, uint8_t* lo, float* part, int ntp, int rows, int d, hipStream_t s);
 hipError_t launch_respk_unpack_rows(const void* hi, const uint8_t* lo, int row_mul, float* out, int rows, int d, hipStream_t s);
 
+// ---------------------------------------------------------------- stand-alone MLP activation (activation.hip)
+// The towers' activation (values are part of the C ABI: MVLPT_ACT_*).  ACT_QUICKGELU is what the GEMM epilogues EPI_GELU* compute;
+// ACT_GELU (nn.GELU, the erf form) runs as its own element-wise pass between the two MLP GEMMs.
+enum ActKind { ACT_QUICKGELU = 0, ACT_GELU = 1 };
+// A-operand formats of the output (GemmArgs::a_split of the GEMM that reads it): [M, N], hi|lo pair [M, 2N], mixed pair (same pitch)
+enum ActFmt { ACT_FMT_SINGLE = 0, ACT_FMT_PAIR = 1, ACT_FMT_MIXED = 2 };
+struct ActArgs {
+  const float* in;     // forward: the pre-activation u; backward: dA; fp32 [M, N], as EPI_STORE32 writes them
+  int ldi;             // row pitch of `in` in floats (0: dense)
+  void* out;           // act(u) / dA * act'(u) in format fmt
+  int fmt;
+  int ldo;             // row pitch of `out` in 16-bit elements (0: dense, N or 2N)
+  void* u16;           // 16-bit [M, N], dense: forward, optional: the saved pre-activation is written; backward: it is read
+  int M, N;            // N % 8 == 0; pitches multiples of 8; every pointer 16-byte aligned
+};
+const char* act_check(int dtype, int act, bool bwd, ActArgs& a);      // null when the launch is legal (pitches resolved), else why not
+hipError_t launch_act_fwd(int dtype, int act, const ActArgs& a, hipStream_t s);
+hipError_t launch_act_bwd(int dtype, int act, const ActArgs& a, hipStream_t s);
+
 // ---------------------------------------------------------------- head: cosine logits + cross-entropy (fp32)
 hipError_t launch_normalize_rows(const float* x, float* xn, float* norm, int rows, int d, hipStream_t s);
 // prompt ensembling (trainers/zsclip.py:88-96): out [C, e] = normalize(mean_t normalize(feats[t, c])), feats [T, C, e]; fixed summation

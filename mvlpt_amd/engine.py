@@ -95,10 +95,16 @@ def _req(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+_ACTIVATIONS = {"quick_gelu": _lib.ACT_QUICKGELU, "gelu": _lib.ACT_GELU}      # MODEL.BACKBONE.ACTIVATION -> MVLPT_ACT_*
+
+
 class Engine:
     """One handle per process per GPU (include/mvlpt_hip.h)."""
 
-    def __init__(self, arch: ClipArch, compute_dtype: str = "fp16", device: Optional[torch.device] = None):
+    def __init__(self, arch: ClipArch, compute_dtype: str = "fp16", device: Optional[torch.device] = None,
+                 activation: str = "quick_gelu"):
+        if activation not in _ACTIVATIONS:
+            raise ValueError(f"activation = {activation!r}: the accepted values are 'quick_gelu' and 'gelu'")
         if not torch.cuda.is_available():
             raise RuntimeError("mvlpt_amd.Engine needs a HIP device (no CPU fallback)")
         self.device = torch.device(device if device is not None else f"cuda:{torch.cuda.current_device()}")
@@ -127,6 +133,9 @@ class Engine:
                 _lib.check(lib.mvlpt_create(C.byref(a), C.byref(h)), None, "mvlpt_create")
         self.h = h
         self.precision = _lib.PREC_SPLIT_GRAD
+        self.activation = "quick_gelu"
+        if activation != "quick_gelu":
+            self.set_activation(activation)
         self._keep: List[torch.Tensor] = []     # tensors the library reads asynchronously / later
         self._img_state = None
         self._img_pending = None      # image_fwd_begin .. image_fwd_resume: (image, vpt, vpt_deep, masks, state for image_bwd)
@@ -151,6 +160,19 @@ class Engine:
         code = {"fast": _lib.PREC_FAST, "split_grad": _lib.PREC_SPLIT_GRAD, "split_all": _lib.PREC_SPLIT_ALL}.get(mode, mode)
         _lib.check(lib.mvlpt_set_precision(self.h, int(code)), self.h, "set_precision")
         self.precision = int(code)
+
+    def set_activation(self, activation: str) -> None:
+        """"quick_gelu" (default) | "gelu": the MLP activation of both towers (include/mvlpt_hip.h: mvlpt_set_activation).  Legal before
+        a forward and after a completed step; between a saving forward and its backward the library refuses (RuntimeError)."""
+        if activation not in _ACTIVATIONS:
+            raise ValueError(f"activation = {activation!r}: the accepted values are 'quick_gelu' and 'gelu'")
+        _lib.check(lib.mvlpt_set_activation(self.h, _ACTIVATIONS[activation]), self.h, "set_activation")
+        self.activation = activation
+
+    def get_activation(self) -> str:
+        code = C.c_int(-1)
+        _lib.check(lib.mvlpt_get_activation(self.h, C.byref(code)), self.h, "get_activation")
+        return {v: k for k, v in _ACTIVATIONS.items()}[code.value]
 
     def set_text_act_ckpt(self, segments: int) -> None:
         """TRAINER.ACT_CKPT (include/mvlpt_hip.h: mvlpt_set_text_act_ckpt): the text tower keeps only the inputs of `segments`
@@ -212,8 +234,8 @@ class Engine:
 
     @classmethod
     def from_state_dict(cls, sd: Dict[str, torch.Tensor], compute_dtype: str = "fp16", device=None,
-                        arch: Optional[ClipArch] = None) -> "Engine":
-        eng = cls(arch or arch_from_state_dict(sd), compute_dtype, device)
+                        arch: Optional[ClipArch] = None, activation: str = "quick_gelu") -> "Engine":
+        eng = cls(arch or arch_from_state_dict(sd), compute_dtype, device, activation)
         eng.load_frozen(sd)
         return eng
 
@@ -611,6 +633,29 @@ def op_gemm_ex(A, Bt, epi, M, N, K, out, bias=None, aux=None, resid=None, out2=N
     _lib.check(lib.mvlpt_op_gemm_ex(_TORCH2DT[A.dtype], epi, _ptr(A), _ptr(Bt), M, N, K, _ptr(bias), _ptr(aux), _ptr(resid), _ptr(out),
                                     _ptr(out2), a_split, lda, ldo, ldb, w8_exp, out_lo8, _stream()), None, "op_gemm_ex")
     return out
+
+
+def _act_code(activation) -> int:
+    return _ACTIVATIONS.get(activation, activation)
+
+
+def op_activation_fwd(u32, M, N, out, activation="gelu", out_format=0, ld_in=0, ld_out=0, u16_out=None):
+    """mvlpt_op_activation_fwd on caller-owned tensors: out (16-bit, format _lib.ACT_OUT_*, pitch ld_out) = act(u32 fp32 [M, N] at
+    pitch ld_in); u16_out (optional, [M, N]): the saved pre-activation.  `activation`: "quick_gelu" | "gelu" (or a raw code)."""
+    _lib.check(lib.mvlpt_op_activation_fwd(_TORCH2DT[out.dtype], _act_code(activation), _ptr(u32), ld_in, M, N, out_format, _ptr(out),
+                                           ld_out, _ptr(u16_out), _stream()), None, "op_activation_fwd")
+    return out
+
+
+def op_activation_bwd(da32, u16, M, N, out, activation="gelu", out_format=0, ld_in=0, ld_out=0):
+    """mvlpt_op_activation_bwd: out = da32 (fp32 [M, N] at pitch ld_in) * act'(u16 [M, N]) in format out_format at pitch ld_out."""
+    _lib.check(lib.mvlpt_op_activation_bwd(_TORCH2DT[out.dtype], _act_code(activation), _ptr(da32), ld_in, _ptr(u16), M, N, out_format,
+                                           _ptr(out), ld_out, _stream()), None, "op_activation_bwd")
+    return out
+
+
+Engine.op_activation_fwd = staticmethod(op_activation_fwd)
+Engine.op_activation_bwd = staticmethod(op_activation_bwd)
 
 
 def op_gemm_route(dtype, epi, a_split, M, N, K, fold_ntp=0):

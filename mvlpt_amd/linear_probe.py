@@ -297,7 +297,8 @@ def extract_features(clip, batches: Iterable) -> Tuple[np.ndarray, np.ndarray]:
     """(features [n, embed] fp32, labels [n] int64) of an iterable of (images, labels): FrozenCLIP.encode_image per batch, un-normalised
     as the reference's clip_model.visual(data) is (lpclip/feat_extractor.py:155), rows in input order.  The tower is whatever the
     FrozenCLIP holds: the reference hard-codes RN50 (mvlpt_amd.weights.RESNET_ARCHS["RN50"], the convolutional tower of
-    mvlpt_create_resnet); any ViT of ARCHS works the same way."""
+    mvlpt_create_resnet); any ViT of ARCHS works the same way, under the activation the FrozenCLIP was built with
+    (FrozenCLIP(activation=read_activation(cfg)): MODEL.BACKBONE.ACTIVATION)."""
     feats, labels = [], []
     for images, lab in batches:
         feats.append(clip.encode_image(images).float().cpu().numpy())

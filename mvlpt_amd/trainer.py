@@ -24,7 +24,7 @@ from typing import Dict, Iterable, Optional
 import torch
 
 from . import distributed as dist_utils
-from .config import CfgNode
+from .config import CfgNode, read_activation
 from .model import CustomCLIP, FrozenCLIP
 from .weights import RESNET_ARCHS, get_arch, make_state_dict
 
@@ -516,7 +516,8 @@ class MVLPT(TrainerX):
             from .mvlpt_cocoop import CustomCLIP as model_cls
             if cfg.TRAINER.MVLPT.COCOOP.PREC == "fp32":
                 prec = "split_all"
-        clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec)
+        clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec,
+                                activation=read_activation(cfg))
         self.model = model_cls(cfg, classnames, clip_model, dm=self.dm, pretokenized=pretok)
         self.model.prefetch_split = prefetch_split(cfg)
         self.train_prompt_learner_only()

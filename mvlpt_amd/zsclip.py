@@ -19,6 +19,7 @@ from typing import List, Sequence
 
 import torch
 
+from .config import read_activation
 from .model import FrozenCLIP
 from .trainer import MVLPT, TrainerX
 from .weights import get_arch, make_state_dict
@@ -58,7 +59,8 @@ class ZeroshotCLIP(MVLPT):
         if sd is None:
             sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED, include_token_embedding=True)
         clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device,
-                                precision=cfg.TRAINER.MVLPT.GRAD_PRECISION)   # text tower: split operands unless "fast"
+                                precision=cfg.TRAINER.MVLPT.GRAD_PRECISION,   # text tower: split operands unless "fast"
+                                activation=read_activation(cfg))
         prompts = build_prompts(self.templates, classnames)
         tokenized = clip_model.tokenizer.tokenize(prompts, clip_model.context_length)
         T, C = len(self.templates), len(classnames)

@@ -54,6 +54,14 @@ typedef struct MvlptArch {
  *   MVLPT_PREC_SPLIT_ALL  split operands in every tower, 16-bit hi+lo pairs (~22 bits) everywhere (PREC = "fp32") */
 enum { MVLPT_PREC_FAST = 0, MVLPT_PREC_SPLIT_GRAD = 1, MVLPT_PREC_SPLIT_ALL = 2 };
 
+/* A handle for a ViT image tower and the text tower.  Widths are multiples of 128 and embed_dim of 64.  The text tower's heads are 64
+ * wide (text_width == text_heads * 64).  The image tower's head width vision_width / vision_heads is 64 (CLIP's own ViTs: heads =
+ * width // 64) or one of 80, 96, 112, 128 (the ViT-H/14 family: width 1280 = 16 heads of 80); any other head width returns
+ * MVLPT_ERR_UNSUPPORTED.  An image tower with heads wider than 64 is frozen, prompt-free and forward-only on single 16-bit operands
+ * (CoOp, CoCoOp, zero-shot, feature extraction): mvlpt_image_fwd with n_vpt == 0 and save_for_bwd == 0 and mvlpt_image_fwd_begin /
+ * _resume / _abandon run, at any token count; visual prompts, save_for_bwd != 0, mvlpt_image_bwd, mvlpt_set_vpt_dropout and an image
+ * forward under MVLPT_PREC_SPLIT_ALL (whose forward-only towers run on pairs) return MVLPT_ERR_UNSUPPORTED with a message naming the
+ * cause, without touching the device, and leave the handle usable. */
 int mvlpt_create(const MvlptArch* arch, void** handle);
 /* A handle whose image tower is CLIP's ModifiedResNet (clip/model.py:94-150: RN50, RN101; three-conv stem, four stages of Bottleneck
  * blocks of `layers[i]` blocks and width * {1,2,4,8} planes, AttentionPool2d with `heads` heads of 64 over 32 * width channels).
@@ -397,11 +405,19 @@ int mvlpt_op_layernorm_fwd(int out_dtype, const float* x, const float* gamma, co
                            mvlpt_stream_t stream);
 int mvlpt_op_layernorm_bwd(int dtype, const void* dy, const float* x, const float* gamma, const float* resid, float* out32,
                            void* out16, int rows, int d, mvlpt_stream_t stream);
-/* qkv [N*L,3*H*64] 16-bit -> out [N*L,H*64], lse [N*H*L] (may be NULL) */
+/* qkv [N*L,3*H*64] 16-bit -> out [N*L,H*64], lse [N*H*L] (may be NULL); heads of 64 (wider heads: mvlpt_op_attention_wide_fwd) */
 int mvlpt_op_attention_fwd(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int causal,
                            mvlpt_stream_t stream);
 int mvlpt_op_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                            void* dqkv, int N, int L, int H, int causal, mvlpt_stream_t stream);
+/* The forward for heads wider than 64 (attention_wide.hip), non-causal, any L >= 1: qkv [N*L,3*H*w] 16-bit with head h at h*w inside
+ * each third -> out [N*L,H*w], lse [N*H*L] (may be NULL), w = head_width in {80, 96, 112, 128} (any other: MVLPT_ERR_UNSUPPORTED; 64 is
+ * mvlpt_op_attention_fwd's).  q_rows > 0: only queries 0..q_rows-1 of every sequence are computed and only their rows of out / lse are
+ * written.  Scores are scaled by 1/sqrt(w) in fp32, the softmax runs online in fp32, P is rounded once to the 16-bit type, keys >= L
+ * weigh exactly 0.  Handle-free and enqueue-only; a NULL pointer, a non-positive size or an unknown dtype returns MVLPT_ERR_ARG with
+ * nothing launched.  There is no backward. */
+int mvlpt_op_attention_wide_fwd(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int head_width, int q_rows,
+                                mvlpt_stream_t stream);
 int mvlpt_op_cast(int dtype, const float* in, void* out, int64_t n, mvlpt_stream_t stream);
 /* ---- LayerNorm, the operand-format kernels and the patch extraction with every argument the towers set (tests/test_hip_norm_matrix.py,
  * tests/test_hip_formats.py).  Every entry checks its arguments before anything is launched: a NULL pointer, an unknown dtype / format /

@@ -154,6 +154,7 @@ SIGNATURES = {
     "mvlpt_op_layernorm_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
     "mvlpt_op_attention_fwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "mvlpt_op_attention_bwd": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_attention_wide_fwd": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvlpt_op_cast": (_i, [_i, _vp, _vp, C.c_int64, _vp]),
     "mvlpt_op_layernorm_fwd_ex": (_i, [_i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvlpt_op_layernorm_bwd_ex": (_i, [_i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),

@@ -22,10 +22,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .config import read_activation
+from .config import read_activation, read_vision_head_width
 from .model import (FrozenCLIP, PretokenizedPrompts, _text_inputs, apply_text_act_ckpt, class_prompt_tables, image_conditioned_ctx,
                     register_class_tables)
-from .trainer import MVLPT, TrainerX
+from .trainer import MVLPT, TrainerX, refuse_wide_heads
 from .weights import get_arch, make_state_dict
 
 # Workspace budget of the CoCoOp text tower (not a reference key).  A chunk is the largest number of images whose
@@ -121,7 +121,9 @@ class PerImageTextCLIP(nn.Module):
         # default mode (split operands only in towers kept for a backward) the ViT-B/16 fixture's ctx / meta_net gradients land at
         # 0.9-1.3e-3 of the reference; with split operands in every tower (MVLPT_PREC_SPLIT_ALL) at <= 8.3e-4.  CoCoOp therefore
         # raises the engine's default mode to split_all ("fast", an explicit request for single operands, is left alone).
-        if self.engine.precision == _lib.PREC_SPLIT_GRAD:
+        # (An image tower with heads wider than 64 has single operands only: its mode stays split_grad, under which the text tower,
+        # which carries the gradient, runs on pairs all the same.)
+        if self.engine.precision == _lib.PREC_SPLIT_GRAD and getattr(clip_model.arch, "vision_head_width", 64) == 64:
             self.engine.set_precision("split_all")
         self.last_chunks = 0
         self.last_ncorrect = None
@@ -203,6 +205,7 @@ class CoCoOp(MVLPT):
 
     def build_model(self):
         cfg = self.cfg
+        refuse_wide_heads(cfg, "CoCoOp")
         classnames = self.dm.dataset.classnames
         pretok = getattr(self.dm, "pretokenized", None)
         sd = self._sd_arg
@@ -211,7 +214,7 @@ class CoCoOp(MVLPT):
         # fp16 / amp / fp32 all end in split_all (CustomCLIP raises the default mode); GRAD_PRECISION = "fast" keeps single operands
         prec = "split_all" if cfg.TRAINER.COCOOP.PREC == "fp32" else cfg.TRAINER.MVLPT.GRAD_PRECISION
         clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec,
-                                activation=read_activation(cfg))
+                                activation=read_activation(cfg), vision_head_width=read_vision_head_width(cfg))
         self.model = CustomCLIP(cfg, classnames, clip_model, pretokenized=pretok)
         self.train_prompt_learner_only()                                # :220-241
 

@@ -58,6 +58,24 @@ def read_activation(cfg) -> str:
     return act
 
 
+VISION_HEAD_WIDTHS = (64, 80, 96, 112, 128)
+
+
+def read_vision_head_width(cfg) -> int:
+    """MODEL.BACKBONE.VISION_HEAD_WIDTH, checked: the width of one head of a ViT image tower.  0 (or absent): the named backbone's own,
+    64 for every CLIP ViT of the reference and 80 for "ViT-H/14".  A state dict does not say it (the reference computes heads =
+    width // 64), so every trainer hands this value to the arch it builds from INIT_WEIGHTS."""
+    w = cfg.MODEL.BACKBONE.get("VISION_HEAD_WIDTH", 0)
+    if isinstance(w, bool) or not isinstance(w, int) or (w != 0 and w not in VISION_HEAD_WIDTHS):
+        raise ValueError(f"MODEL.BACKBONE.VISION_HEAD_WIDTH = {w!r}: the accepted values are 0 (the backbone's own) and "
+                         f"{', '.join(str(v) for v in VISION_HEAD_WIDTHS)}")
+    if w == 0:
+        from .weights import WIDE_HEAD_ARCHS
+        arch = WIDE_HEAD_ARCHS.get(cfg.MODEL.BACKBONE.NAME)
+        w = arch.vision_head_width if arch is not None else 64
+    return w
+
+
 def get_cfg_default() -> CfgNode:
     CN = CfgNode
     cfg = CN()
@@ -66,7 +84,9 @@ def get_cfg_default() -> CfgNode:
     # ACTIVATION (not in the reference, whose clip/model.py:162-164 has QuickGELU compiled in): the MLP activation of both towers.
     # "quick_gelu": the archives clip.load downloads.  "gelu": a checkpoint with the same architecture and state-dict keys that was
     # trained with nn.GELU (the erf form); with the default its logits and gradients would come out of the wrong function without an error.
-    cfg.MODEL = CN(BACKBONE=CN(NAME="ViT-B/16", ACTIVATION="quick_gelu"), INIT_WEIGHTS="")
+    # VISION_HEAD_WIDTH (not in the reference, whose clip/model.py:268 has heads = width // 64 compiled in): the width of one head of a ViT
+    # image tower, 0 = the named backbone's own (64; "ViT-H/14": 80).  A wide-headed tower is frozen and forward-only (read_vision_head_width).
+    cfg.MODEL = CN(BACKBONE=CN(NAME="ViT-B/16", ACTIVATION="quick_gelu", VISION_HEAD_WIDTH=0), INIT_WEIGHTS="")
     # TRANSFORMS and the parameters of its augmentations: Dassl's names and defaults (mvlpt_amd.transforms.build_device_transform; the
     # launcher's --transforms).  On the command line the list comes as JSON: INPUT.TRANSFORMS '["random_crop", "random_flip", "cutout"]'
     cfg.INPUT = CN(SIZE=(224, 224), TRANSFORMS=["random_resized_crop", "random_flip", "normalize"], COLORJITTER_B=0.4, COLORJITTER_C=0.4,

@@ -149,6 +149,7 @@ struct TowerState {
   int wide_pitch = 0;                    // split towers: row pitch of a16 / du16 (0: dense)
   int xs = 0;                            // GEMM A operands: 0 single 16-bit, 1 16-bit pair, 2 mixed pair (hi + e5m2 residual byte)
   int N = 0, L = 0, d = 0, H = 0, layers = 0;
+  int hw = 64;                           // head width d / H: 64, or a wide-headed image tower's 80 / 96 / 112 / 128 (attention_wide.hip)
   std::vector<float*> x;                 // 2*layers+1 entries (all equal when !saved)
   std::vector<void*> qkv, attn, u;       // per layer (all equal when !saved)
   std::vector<float*> lse;
@@ -390,7 +391,7 @@ void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool s
                  int segments = 1) {
   const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1; const int nl = W.layers;
   st = TowerState();
-  st.N = N; st.L = L; st.d = (int)d; st.H = (int)H; st.layers = nl; st.saved = save; st.causal = causal; st.exact = exact;
+  st.N = N; st.L = L; st.d = (int)d; st.H = (int)H; st.hw = (int)(d / H); st.layers = nl; st.saved = save; st.causal = causal; st.exact = exact;
   st.xs = exact ? xs : 0;
   st.seg = ckpt_plan(nl, save ? segments : 1);
   const int k = (int)st.seg.size() - 1;
@@ -454,8 +455,15 @@ int split_kind(const Engine* E) { return (E->prec_mode == MVLPT_PREC_SPLIT_ALL |
 // adds the dispatch-timestamp record of attn_fwd_timed.
 int attn_fwd(Engine* E, TowerState& st, int l, int q_rows, bool timed, hipStream_t s) {
   const double T = (double)st.N * st.L, rows = q_rows > 0 ? (double)q_rows : (double)st.L;
-  const double fl = 4.0 * rows * st.L * 64.0 * st.N * st.H * (st.causal ? 0.5 : 1.0);
+  const double fl = 4.0 * rows * st.L * (double)st.hw * st.N * st.H * (st.causal ? 0.5 : 1.0);
   float* lse = st.saved ? st.lse[l] : nullptr;
+  if (st.hw != 64) {      // a wide-headed image tower: frozen, prompt-free, forward-only on single operands (kRefuseWide)
+    if (st.xs || st.causal || st.saved) return fail(E, MVLPT_ERR_STATE, "wide-headed attention: single operands, non-causal, nothing saved");
+    AttnArgs a{st.qkv[l], st.attn[l], nullptr, st.N, st.L, st.H, 0, q_rows};
+    ProfScope ps(E, s, PC_ATTN_FWD, fl, T * st.d * 2.0 * (q_rows > 0 ? 2.0 : 4.0));
+    HIPCHK(E, launch_attn_fwd_wide(E->dt, a, st.hw, s));
+    return 0;
+  }
   if (st.xs) {
     Attn32Args a{st.qkv[l], st.attn[l], lse, st.N, st.L, st.H, st.causal ? 1 : 0, q_rows};
     a.out_lo8 = st.xs == 2 ? 1 : 0;
@@ -847,6 +855,10 @@ int prepare_fold(Engine* E, hipStream_t s) {
   return 0;
 }
 
+// A ViT image tower whose heads are wider than 64 (ViT-H/14: 16 heads of 80) has the forward kernel of attention_wide.hip and nothing else
+const char* kRefuseWide = "an image tower with heads wider than 64 is frozen, prompt-free and forward-only on single 16-bit operands: ";
+static bool vision_wide(const Engine* E) { return !E->rn.on && E->vis.heads > 0 && E->vis.width != E->vis.heads * 64; }
+
 // ------------------------------------------------------------------------------------------------ ModifiedResNet image tower
 const char* kRefuseRN = "the ResNet image tower is frozen and forward-only in one piece (trainers/mvlpt.py:48 cannot prompt a ResNet): ";
 
@@ -1047,8 +1059,11 @@ const char* mvlpt_last_error(void* h) { return h ? ((Engine*)h)->err.c_str() : g
 // What mvlpt_create and mvlpt_create_resnet share.  arch_check: the transformer limits, in the order both entries report them.
 // vit = false (create_resnet): the ViT vision fields are 0, as that entry has checked, and put nothing in the way of the text tower's checks.
 static int arch_check(const MvlptArch* a, bool vit) {
-  if (a->vision_width != a->vision_heads * 64 || a->text_width != a->text_heads * 64)
-    return fail(nullptr, MVLPT_ERR_UNSUPPORTED, vit ? "head_dim must be 64 (CLIP ViT: heads = width // 64)" : "head_dim must be 64");
+  // the text tower's heads are 64 wide; a ViT image tower's may be 80 / 96 / 112 / 128 as well (vision_wide)
+  bool vis_ok = a->vision_width == a->vision_heads * 64;
+  if (vit && !vis_ok && a->vision_heads > 0 && a->vision_width % a->vision_heads == 0) vis_ok = attn_wide_supported(a->vision_width / a->vision_heads);
+  if (!vis_ok || a->text_width != a->text_heads * 64)
+    return fail(nullptr, MVLPT_ERR_UNSUPPORTED, vit ? "head_dim must be 64 (CLIP ViT: heads = width // 64), or 80 / 96 / 112 / 128 in the image tower" : "head_dim must be 64");
   if (a->vision_width % 128 || a->text_width % 128 || a->embed_dim % 64)
     return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "widths must be multiples of 128 and embed_dim of 64");
   if (vit && (a->patch_size <= 0 || a->image_resolution % a->patch_size))
@@ -1225,6 +1240,7 @@ int mvlpt_set_vpt_dropout(void* h, const float* masks, int n_layers, int batch, 
   Engine* E = (Engine*)h;
   if (!E) return MVLPT_ERR_ARG;
   if (E->rn.on) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "set_vpt_dropout");
+  if (vision_wide(E)) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseWide) + "set_vpt_dropout");
   if (masks && (n_layers <= 0 || batch <= 0 || n_vpt <= 0 || width != E->arch.vision_width))
     return fail(E, MVLPT_ERR_ARG, "set_vpt_dropout: masks are [n_layers, batch, n_vpt, vision_width], every extent positive");
   E->vpt_mask = masks;
@@ -1402,6 +1418,13 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
   Engine* E = (Engine*)h;
   if (!E || !image || B <= 0) return fail(E, MVLPT_ERR_ARG, "image_fwd: null/invalid argument");
   if (E->rn.on) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "image_fwd_begin");
+  const bool wide = vision_wide(E);
+  if (wide) {
+    if (vpt || vpt_deep || n_vpt || n_deep) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseWide) + "visual prompts");
+    if (save_for_bwd) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseWide) + "save_for_bwd");
+    if (E->prec_mode == MVLPT_PREC_SPLIT_ALL)
+      return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseWide) + "MVLPT_PREC_SPLIT_ALL (its forward-only towers run on pairs)");
+  }
   if (E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_fwd_begin: a forward is pending (call image_fwd_resume or image_fwd_abandon first)");
   if (int rc = mvlpt_frozen_ready(h)) return rc;
   if ((n_vpt > 0) != (vpt != nullptr)) return fail(E, MVLPT_ERR_ARG, "image_fwd: vpt pointer and n_vpt disagree");
@@ -1410,7 +1433,7 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
   const MvlptArch& A = E->arch;
   const int G = A.image_resolution / A.patch_size, G2 = G * G, dv = A.vision_width;
   const int Lv = 1 + n_vpt + G2;
-  if (Lv > attn_max_len()) return fail(E, MVLPT_ERR_UNSUPPORTED, "image_fwd: sequence length > 256 not supported yet");
+  if (!wide && Lv > attn_max_len()) return fail(E, MVLPT_ERR_UNSUPPORTED, "image_fwd: sequence length > 256 not supported yet");
   const bool save = save_for_bwd != 0;
   const bool exact = E->prec_mode == MVLPT_PREC_SPLIT_ALL || (E->prec_mode == MVLPT_PREC_SPLIT_GRAD && save);
   const size_t X = exact ? 2 : 1;
@@ -1519,6 +1542,7 @@ int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, 
   Engine* E = (Engine*)h;
   if (!E || !dfeat) return fail(E, MVLPT_ERR_ARG, "image_bwd: null argument");
   if (E->rn.on) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "image_bwd");
+  if (vision_wide(E)) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseWide) + "image_bwd");
   TowerState& st = E->vs;
   if (E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_bwd: a forward is pending between image_fwd_begin and image_fwd_resume");
   if (!st.valid || !st.saved) return fail(E, MVLPT_ERR_STATE, "image_bwd: call image_fwd(save_for_bwd=1) first");
@@ -2195,6 +2219,15 @@ int mvlpt_op_attention_fwd(int dtype, const void* qkv, void* out, float* lse, in
                            mvlpt_stream_t stream) {
   AttnArgs a{qkv, out, lse, N, L, H, causal};
   OPCHK(launch_attn_fwd(dtype, a, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_attention_wide_fwd(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int head_width, int q_rows,
+                                mvlpt_stream_t stream) {
+  if (!attn_wide_supported(head_width)) return fail(nullptr, MVLPT_ERR_UNSUPPORTED, "op_attention_wide_fwd: head_width must be 80, 96, 112 or 128");
+  if (!qkv || !out || N <= 0 || L <= 0 || H <= 0 || q_rows < 0 || (dtype != DT_F16 && dtype != DT_BF16))
+    return fail(nullptr, MVLPT_ERR_ARG, "op_attention_wide_fwd: null / invalid argument");
+  AttnArgs a{qkv, out, lse, N, L, H, 0, q_rows};
+  OPCHK(launch_attn_fwd_wide(dtype, a, head_width, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_attention_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,

@@ -181,6 +181,10 @@ hipError_t launch_attn_bwd_cls(int dtype, const void* qkv, const void* o_cls, co
 // streaming variants (attention_stream.hip): any L, 32 KiB LDS ring; launch_attn_* picks between the two families
 hipError_t launch_attn_fwd_stream(int dtype, const AttnArgs& a, hipStream_t s);
 hipError_t launch_attn_bwd_stream(int dtype, const AttnBwdArgs& a, hipStream_t s);
+// heads wider than 64 (attention_wide.hip): head h at h*head_width inside each third, head_width in {80, 96, 112, 128}, any L, non-causal
+// (causal != 0 -> hipErrorInvalidValue), forward only; only rows 0..q_rows-1 of every sequence are written when q_rows > 0
+bool attn_wide_supported(int head_width);
+hipError_t launch_attn_fwd_wide(int dtype, const AttnArgs& a, int head_width, hipStream_t s);
 
 // ---------------------------------------------------------------- split-precision attention (attention32.hip), any L
 // Split-precision mode of the towers that carry a gradient: every operand is a 16-bit hi|lo pair [rows, 2*cols]

@@ -1265,6 +1265,18 @@ def op_attention_fwd(qkv, N, L, H, causal, want_lse=True):
     return out, lse
 
 
+def op_attention_wide_fwd(qkv, N, L, H, head_width, q_rows=0, want_lse=True, out=None, lse=None):
+    """The forward for heads wider than 64 (mvlpt_op_attention_wide_fwd): qkv [N*L, 3*H*w] -> (out [N*L, H*w], lse [N*H*L] or None).
+    out / lse: caller-owned destinations (contiguous views; q_rows > 0 writes only rows 0..q_rows-1 of every sequence)."""
+    if out is None:
+        out = torch.empty(N * L, H * head_width, device=qkv.device, dtype=qkv.dtype)
+    if lse is None and want_lse:
+        lse = torch.empty(N * H * L, device=qkv.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_attention_wide_fwd(_TORCH2DT[qkv.dtype], _ptr(qkv), _ptr(out), _ptr(lse), N, L, H, int(head_width), int(q_rows),
+                                               _stream()), None, "op_attention_wide_fwd")
+    return out, lse
+
+
 def op_attention_bwd(qkv, out, dout, lse, N, L, H, causal):
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(N * H * L, device=qkv.device, dtype=torch.float32)

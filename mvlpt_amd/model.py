@@ -123,8 +123,9 @@ class FrozenCLIP:
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], compute_dtype: str = "fp16", device=None,
                  tokenizer=None, arch: Optional[ClipArch] = None, token_seed: int = 0, precision: str = "split_grad",
-                 activation: str = "quick_gelu"):
-        self.arch = arch or arch_from_state_dict(state_dict)
+                 activation: str = "quick_gelu", vision_head_width: int = 64):
+        # vision_head_width (MODEL.BACKBONE.VISION_HEAD_WIDTH): a state dict does not say it; ignored when `arch` is given
+        self.arch = arch or arch_from_state_dict(state_dict, vision_head_width=vision_head_width)
         # activation: "quick_gelu" | "gelu" (MODEL.BACKBONE.ACTIVATION): what the checkpoint's MLPs were trained with
         self.engine = Engine.from_state_dict(state_dict, compute_dtype, device, self.arch, activation)
         self.engine.set_precision(precision)       # "fast" | "split_grad" | "split_all" (include/mvlpt_hip.h MVLPT_PREC_*)

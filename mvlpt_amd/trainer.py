@@ -24,7 +24,7 @@ from typing import Dict, Iterable, Optional
 import torch
 
 from . import distributed as dist_utils
-from .config import CfgNode, read_activation
+from .config import CfgNode, read_activation, read_vision_head_width
 from .model import CustomCLIP, FrozenCLIP
 from .weights import RESNET_ARCHS, get_arch, make_state_dict
 
@@ -457,6 +457,26 @@ class SyntheticDataManager:
 
 
 # ------------------------------------------------------------------------------------------------ the trainer
+def refuse_wide_heads(cfg, trainer: str = "MVLPT") -> None:
+    """An image tower whose heads are wider than 64 (MODEL.BACKBONE.VISION_HEAD_WIDTH; "ViT-H/14": 80) is frozen, prompt-free and
+    forward-only on single 16-bit operands: it has an attention forward kernel and nothing else.  CoOp, CoCoOp, MVLPT-CoCoOp without
+    visual prompts, the zero-shot trainers and the linear probe run; what needs more is refused here, before any engine exists.
+    trainer: "MVLPT" (reads TRAINER.MVLPT.*) or "CoCoOp" (TRAINER.COCOOP.PREC)."""
+    w = read_vision_head_width(cfg)
+    if w == 64 or cfg.MODEL.BACKBONE.NAME in RESNET_ARCHS:
+        return
+    what = f"an image tower with heads of {w} (MODEL.BACKBONE.VISION_HEAD_WIDTH) is frozen, prompt-free and forward-only: "
+    if trainer == "CoCoOp":
+        if cfg.TRAINER.COCOOP.PREC == "fp32":
+            raise ValueError(what + "TRAINER.COCOOP.PREC = 'fp32' runs every tower on operand pairs; use fp16 or amp")
+        return
+    if cfg.TRAINER.MVLPT.VPT.N_CTX != 0:
+        raise ValueError(what + "visual prompts (TRAINER.MVLPT.VPT.N_CTX != 0: VPT, UPT, MVLPT-CoCoOp with visual prompts) need a "
+                         "backward through it; set VPT.N_CTX 0 (CoOp)")
+    if cfg.TRAINER.MVLPT.PREC == "fp32" or (cfg.TRAINER.MVLPT.COCOOP.N_CTX != 0 and cfg.TRAINER.MVLPT.COCOOP.PREC == "fp32"):
+        raise ValueError(what + "PREC = 'fp32' runs every tower on operand pairs; use fp16 or amp")
+
+
 class MVLPT(TrainerX):
     """trainers/mvlpt.py:827-1125 on the HIP engine."""
 
@@ -500,6 +520,7 @@ class MVLPT(TrainerX):
 
     def build_model(self):
         cfg = self.cfg
+        refuse_wide_heads(cfg)
         classnames = self.dm.dataset.classnames if cfg.DATASET.COOP else list(self.dm.lab2cname.values())
         # token ids produced elsewhere (mvlpt_amd.class_prompts: reference-tokenizer tables for the BASELINE class lists)
         pretok = getattr(self.dm, "pretokenized", None)
@@ -517,7 +538,7 @@ class MVLPT(TrainerX):
             if cfg.TRAINER.MVLPT.COCOOP.PREC == "fp32":
                 prec = "split_all"
         clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec,
-                                activation=read_activation(cfg))
+                                activation=read_activation(cfg), vision_head_width=read_vision_head_width(cfg))
         self.model = model_cls(cfg, classnames, clip_model, dm=self.dm, pretokenized=pretok)
         self.model.prefetch_split = prefetch_split(cfg)
         self.train_prompt_learner_only()

@@ -29,10 +29,13 @@ class ClipArch:
     transformer_width: int
     transformer_heads: int
     transformer_layers: int
+    # width of one image-tower head: 64 in every ViT of the reference (clip/model.py:268 computes heads = width // 64, so its
+    # build_model cannot describe anything else); 80 in the ViT-H/14 family (width 1280 = 16 heads of 80)
+    vision_head_width: int = 64
 
     @property
-    def vision_heads(self) -> int:  # clip/model.py:268
-        return self.vision_width // 64
+    def vision_heads(self) -> int:
+        return self.vision_width // self.vision_head_width
 
     @property
     def grid(self) -> int:
@@ -52,6 +55,15 @@ ARCHS: Dict[str, ClipArch] = {
     "ViT-L/14@336px": ClipArch("ViT-L/14@336px", 768, 336, 24, 1024, 14, 77, 49408, 768, 12, 12),
     # test-size architecture: head_dim stays 64 as in every CLIP ViT (heads = width // 64)
     "tiny": ClipArch("tiny", 128, 32, 3, 128, 16, 77, 49408, 128, 2, 2),
+}
+
+# ViT backbones whose image tower has heads wider than 64: frozen, prompt-free and forward-only here (csrc/attention_wide.hip).  Kept
+# apart from ARCHS as RESNET_ARCHS is: ARCHS stays the list of the backbones every trainer configuration runs on (and the reference builds).
+WIDE_HEAD_ARCHS: Dict[str, ClipArch] = {
+    # the ViT-H/14 family (LAION-2B, DFN, MetaCLIP, CLIPA): image tower 1280 = 16 heads of 80, text tower 1024 = 16 heads of 64, 24 layers
+    "ViT-H/14": ClipArch("ViT-H/14", 1024, 224, 32, 1280, 14, 77, 49408, 1024, 16, 24, vision_head_width=80),
+    # test-size architecture: 640 = 8 heads of 80 (the smallest multiple of 128 that 80 divides), 10 tokens
+    "tiny-h": ClipArch("tiny-h", 128, 48, 3, 640, 16, 77, 49408, 128, 2, 2, vision_head_width=80),
 }
 
 
@@ -108,13 +120,17 @@ def get_arch(name: str) -> AnyArch:
     """The architecture of a backbone name (cfg.MODEL.BACKBONE.NAME), ViT or ResNet."""
     if name in ARCHS:
         return ARCHS[name]
+    if name in WIDE_HEAD_ARCHS:
+        return WIDE_HEAD_ARCHS[name]
     if name in RESNET_ARCHS:
         return RESNET_ARCHS[name]
-    raise KeyError(f"unknown backbone {name!r}: known are {sorted(ARCHS) + sorted(RESNET_ARCHS)}")
+    raise KeyError(f"unknown backbone {name!r}: known are {sorted(ARCHS) + sorted(WIDE_HEAD_ARCHS) + sorted(RESNET_ARCHS)}")
 
 
-def arch_from_state_dict(sd: Dict[str, torch.Tensor], name: str = "custom") -> AnyArch:
-    """Same shape inference as clip.model.build_model (clip/model.py:395-418)."""
+
+def arch_from_state_dict(sd: Dict[str, torch.Tensor], name: str = "custom", vision_head_width: int = 64) -> AnyArch:
+    """Same shape inference as clip.model.build_model (clip/model.py:395-418).  The head width of a ViT image tower is not in a state
+    dict (the reference assumes 64): `vision_head_width` says it (MODEL.BACKBONE.VISION_HEAD_WIDTH; 80 for a ViT-H/14 checkpoint)."""
     tw = sd["ln_final.weight"].shape[0]
     tl = len({k.split(".")[2] for k in sd if k.startswith("transformer.resblocks")})
     vocab = sd["token_embedding.weight"].shape[0] if "token_embedding.weight" in sd else 49408
@@ -128,8 +144,11 @@ def arch_from_state_dict(sd: Dict[str, torch.Tensor], name: str = "custom") -> A
     vl = len([k for k in sd if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
     ps = sd["visual.conv1.weight"].shape[-1]
     grid = round((sd["visual.positional_embedding"].shape[0] - 1) ** 0.5)
+    if vision_head_width <= 0 or vw % vision_head_width:
+        raise ValueError(f"the image tower's width {vw} is not a multiple of the head width {vision_head_width} "
+                         "(MODEL.BACKBONE.VISION_HEAD_WIDTH)")
     return ClipArch(name, sd["text_projection"].shape[1], ps * grid, vl, vw, ps,
-                    sd["positional_embedding"].shape[0], vocab, tw, tw // 64, tl)
+                    sd["positional_embedding"].shape[0], vocab, tw, tw // 64, tl, vision_head_width=vision_head_width)
 
 
 def _randn(name: str, seed: int, shape, std: float, fp16_exact: bool = False) -> torch.Tensor:

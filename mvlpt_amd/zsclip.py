@@ -19,7 +19,7 @@ from typing import List, Sequence
 
 import torch
 
-from .config import read_activation
+from .config import read_activation, read_vision_head_width
 from .model import FrozenCLIP
 from .trainer import MVLPT, TrainerX
 from .weights import get_arch, make_state_dict
@@ -60,7 +60,7 @@ class ZeroshotCLIP(MVLPT):
             sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED, include_token_embedding=True)
         clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device,
                                 precision=cfg.TRAINER.MVLPT.GRAD_PRECISION,   # text tower: split operands unless "fast"
-                                activation=read_activation(cfg))
+                                activation=read_activation(cfg), vision_head_width=read_vision_head_width(cfg))
         prompts = build_prompts(self.templates, classnames)
         tokenized = clip_model.tokenizer.tokenize(prompts, clip_model.context_length)
         T, C = len(self.templates), len(classnames)

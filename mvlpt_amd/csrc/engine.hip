@@ -101,15 +101,15 @@ struct DevBuf {
     return hipSuccess;
   }
 };
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// base == null: a counting pass.  `off` advances as in a carve and every take returns null (carve_ws below).
 struct Bump {
   char* base = nullptr; size_t off = 0, cap = 0;
   template <typename T> T* take(size_t count) {
-    size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-    T* r = (T*)(base + off); off += bytes; return r;
+    T* r = base ? (T*)(base + off) : nullptr; off += align256(count * sizeof(T)); return r;
   }
   void* take_bytes(size_t bytes) { return take<char>(bytes); }
 };
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // Packed frozen weight of one nn.Linear: rows of [W16 (K x 16 bit) | W8 (K bytes, e4m3(W * 2^e8))] with a pitch of 3K/2
 // elements, in both orientations (GemmArgs::a_split == 2 reads the fp8 plane, every other GEMM only the 16-bit one).
@@ -262,6 +262,18 @@ int hipfail(Engine* E, hipError_t e, const char* what) {
 }
 #define HIPCHK(E, call) do { hipError_t _e = (call); if (_e != hipSuccess) return hipfail((E), _e, #call); } while (0)
 
+// A workspace is sized by the function that carves it.  `layout` does the takes and stores the pointers; it runs once on a counting
+// Bump (the pointers it stores are null then), `ws` reserves that count plus `slack`, and it runs again on the real block.
+constexpr size_t kCarveSlack = 4096;
+template <typename F> size_t carve_count(F&& layout) { Bump bp; layout(bp); return bp.off; }
+template <typename F> int carve_ws(Engine* E, DevBuf& ws, const char* who, size_t slack, F&& layout) {
+  HIPCHK(E, ws.reserve(carve_count(layout) + slack));
+  Bump bp; bp.base = (char*)ws.p; bp.cap = ws.cap;
+  layout(bp);
+  if (bp.off > bp.cap) return fail(E, MVLPT_ERR_STATE, std::string(who) + ": the workspace carve exceeds its reservation");
+  return 0;
+}
+
 // Two events of the profiling pool, which grows by 512 up to 65 536 events; false: none left (the launch then goes unrecorded)
 bool take_events(Engine* E, hipEvent_t* a, hipEvent_t* b) {
   if (E->ev_used + 2 > E->ev_pool.size() && E->ev_pool.size() < 65536)
@@ -358,35 +370,16 @@ std::vector<int> ckpt_plan(int layers, int segments) {
   seg[k] = layers;
   return seg;
 }
-// `exact` (split-precision mode): every 16-bit operand buffer holds a hi|lo pair (twice the columns) and QKV / dO are fp32
-// segments > 1 (a saving text tower under activation checkpointing): the per-layer tensors shrink to the m slots of the largest
-// segment (the last one), the k segment inputs stay (x[0] and k - 1 boundary buffers)
-// gelu (Engine::act == ACT_GELU): one more fp32 [T, 4d] buffer, the scratch of the stand-alone activation pass
-size_t tower_bytes(const TowerW& W, int N, int L, bool save, bool exact, bool gelu, int segments = 1) {
-  const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1;
-  const std::vector<int> seg = ckpt_plan(W.layers, save ? segments : 1);
-  const size_t k = seg.size() - 1, nl = k > 1 ? (size_t)(seg[k] - seg[k - 1]) : (size_t)W.layers;      // slots of the per-layer tensors
-  size_t b = 0;
-  b += (save ? (k > 1 ? k + 2 * nl - 1 : 2 * nl + 1) : 1) * align256(T * d * 4);             // x
-  b += align256(T * d * 2 * X);                                      // h16
-  b += (save ? nl : 1) * align256(T * 3 * d * 2 * X);                // qkv
-  b += (save ? nl : 1) * align256(T * d * 2 * X);                    // attn
-  b += (save ? nl : 1) * align256((size_t)N * H * L * 4);            // lse
-  b += (save ? nl : 1) * align256(T * 4 * d * 2);                    // u
-  b += align256(T * (4 * d * 2 * X + 128));                          // a16 (pair rows padded: wide_pitch)
-  b += 2 * align256(T * FOLD_NTP * 8);                               // LayerNorm-folding partials
-  if (save) {
-    b += 2 * align256(T * d * 4) + 2 * align256(T * d * 2 * X) + (align256(T * 4 * d * 2) + align256(T * 3 * d * 2)) * X + align256(T * 128);
-    b += align256((size_t)N * H * L * 4) + 256;
-  }
-  if (gelu) b += align256(T * 4 * d * 4);                            // act32
-  return b + 4096;
-}
 // row pitch (16-bit elements) of the pair tensors between the two MLP GEMMs ([T, 2 * 4d]: a16, du16; GemmArgs::lda / ldo): rows
 // whose dense pitch is a multiple of 4 KiB get 128 bytes more (every CLIP width: 16 d bytes)
 int wide_pitch(int cols) {
   return (4 * cols) % 4096 == 0 ? 2 * cols + 64 : 0;
 }
+// The tower's buffers; on a counting Bump (carve_ws) the tower's size.
+// `exact` (split-precision mode): every 16-bit operand buffer holds a hi|lo pair (twice the columns) and QKV / dO are fp32
+// segments > 1 (a saving text tower under activation checkpointing): the per-layer tensors shrink to the m slots of the largest
+// segment (the last one), the k segment inputs stay (x[0] and k - 1 boundary buffers)
+// gelu (Engine::act == ACT_GELU): one more fp32 [T, 4d] buffer, the scratch of the stand-alone activation pass
 void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool save, bool causal, bool exact, int xs, bool gelu,
                  int segments = 1) {
   const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1; const int nl = W.layers;
@@ -631,15 +624,12 @@ int block_bwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s) 
 // ---- The last block of a tower, evaluated on the rows that are read (Compact): ln_1, QKV and the attention still see every token
 // (keys / values), then out-proj, ln_2, the MLP and the closing LayerNorm run on the R = st.N compact rows instead of R * L: ~20/24
 // of the layer's GEMM FLOPs vanish, in the forward and, when the tower has a backward, in the backward as well.
-// Bytes of the compact buffers as the workspace formulas publish them (u16, never a pair, is counted at pair width)
-size_t compact_bytes(size_t R, size_t d, size_t X, bool gelu) {
-  return 7 * align256(R * d * 4) + 4 * align256(R * d * 2 * X) + 3 * align256(R * d * 8 * X) + (gelu ? align256(R * d * 16) : 0);
-}
+// u16 is never a pair and still taken at pair width: mvlpt_text_workspace_bytes publishes it at that width (see kTextSlack)
 void carve_compact(Bump& bp, Compact& c, size_t R, size_t d, size_t X, bool gelu) {
   c = Compact();
   for (float** p : {&c.out32, &c.dout32, &c.x32, &c.xm32, &c.xo32, &c.dx32, &c.dh32}) *p = bp.take<float>(R * d);
   for (void** p : {&c.a16, &c.h16, &c.dx16, &c.dO16}) *p = bp.take_bytes(R * d * 2 * X);
-  c.g16 = bp.take_bytes(R * d * 8 * X); c.u16 = bp.take_bytes(R * d * 8); c.du16 = bp.take_bytes(R * d * 8 * X);
+  c.g16 = bp.take_bytes(R * d * 8 * X); c.u16 = bp.take_bytes(R * d * 8 * X); c.du16 = bp.take_bytes(R * d * 8 * X);
   if (gelu) c.act32 = bp.take<float>(R * 4 * d);
 }
 // compact row r <-> token row rows[r] or (rows == null) row 0 of sequence r; scatter: compact -> full width
@@ -746,29 +736,93 @@ int pack_linear(Engine* E, const float* w32, int out, int in, Linear* L, hipStre
   L->w = w; L->wt = wt; L->out = out; L->in = in; L->ldw = ldw; L->ldwt = ldwt; L->e8 = e8 - 1; return 0;
 }
 
+// ---- The frozen tensors of a ViT / text handle, each described once: mvlpt_load_frozen, load_block_tensor and first_missing walk
+// these lists, the last in list order (the ResNet tower has its own loader, rn_load).  Shape [r], or [r, c] when c != 0.
+enum FrozenKind {
+  FZ_F32,         // upload_f32 into the float* at `slot`
+  FZ_LINEAR,      // pack_linear [r, c] into the Linear at `slot`
+  FZ_CONV1,       // visual.conv1.weight [r, 3, c, c]: packed [r, Kp] into the void* at `slot`
+  FZ_PROJ,        // visual.proj / text_projection: fp32 in both orientations, into the float* at `slot` and at `slot_t`
+  FZ_TOKENS,      // token_embedding.weight [vocab > 0, c]: optional, read by mvlpt_text_encode_tokens only
+};
+struct FrozenTensor { const char* name; FrozenKind kind; int r, c; void* slot; float** slot_t = nullptr; };
+std::vector<FrozenTensor> top_tensors(Engine* E) {
+  const MvlptArch& A = E->arch;
+  const int dv = A.vision_width, dtw = A.text_width, e = A.embed_dim;
+  std::vector<FrozenTensor> v;
+  if (!E->rn.on) {
+    const int G = A.image_resolution / A.patch_size;
+    v = {{"visual.conv1.weight", FZ_CONV1, dv, A.patch_size, &E->conv_w}, {"visual.class_embedding", FZ_F32, dv, 0, &E->cls_emb},
+         {"visual.positional_embedding", FZ_F32, G * G + 1, dv, &E->vpos},
+         {"visual.ln_pre.weight", FZ_F32, dv, 0, &E->ln_pre.g}, {"visual.ln_pre.bias", FZ_F32, dv, 0, &E->ln_pre.b},
+         {"visual.ln_post.weight", FZ_F32, dv, 0, &E->ln_post.g}, {"visual.ln_post.bias", FZ_F32, dv, 0, &E->ln_post.b},
+         {"visual.proj", FZ_PROJ, dv, e, &E->vproj, &E->vproj_t}};
+  }
+  v.insert(v.end(), {{"positional_embedding", FZ_F32, A.context_length, dtw, &E->tpos},
+                     {"ln_final.weight", FZ_F32, dtw, 0, &E->ln_final.g}, {"ln_final.bias", FZ_F32, dtw, 0, &E->ln_final.b},
+                     {"text_projection", FZ_PROJ, dtw, e, &E->tproj, &E->tproj_t},
+                     {"token_embedding.weight", FZ_TOKENS, 0, dtw, &E->tok_emb}});
+  return v;
+}
+// the names behind "resblocks.<l>."
+std::array<FrozenTensor, 12> block_tensors(Block& B, int d) {
+  return {{{"attn.in_proj_weight", FZ_LINEAR, 3 * d, d, &B.qkv}, {"attn.in_proj_bias", FZ_F32, 3 * d, 0, &B.qkv.b},
+           {"attn.out_proj.weight", FZ_LINEAR, d, d, &B.o}, {"attn.out_proj.bias", FZ_F32, d, 0, &B.o.b},
+           {"mlp.c_fc.weight", FZ_LINEAR, 4 * d, d, &B.fc}, {"mlp.c_fc.bias", FZ_F32, 4 * d, 0, &B.fc.b},
+           {"mlp.c_proj.weight", FZ_LINEAR, d, 4 * d, &B.pr}, {"mlp.c_proj.bias", FZ_F32, d, 0, &B.pr.b},
+           {"ln_1.weight", FZ_F32, d, 0, &B.ln1.g}, {"ln_1.bias", FZ_F32, d, 0, &B.ln1.b},
+           {"ln_2.weight", FZ_F32, d, 0, &B.ln2.g}, {"ln_2.bias", FZ_F32, d, 0, &B.ln2.b}}};
+}
+bool frozen_shape_ok(const FrozenTensor& t, const int64_t* shape, int ndim) {
+  if (t.kind == FZ_CONV1) return ndim == 4 && shape[0] == t.r && shape[1] == 3 && shape[2] == t.c && shape[3] == t.c;
+  if (t.kind == FZ_TOKENS) return ndim == 2 && shape[0] > 0 && shape[0] <= INT32_MAX && shape[1] == t.c;
+  return t.c ? (ndim == 2 && shape[0] == t.r && shape[1] == t.c) : (ndim == 1 && shape[0] == t.r);
+}
+const void* frozen_loaded(const FrozenTensor& t) {
+  return t.kind == FZ_LINEAR ? ((const Linear*)t.slot)->w : t.kind == FZ_CONV1 ? *(void**)t.slot : *(float**)t.slot;
+}
+// `p`: the tensor as fp32 on the device, of a shape frozen_shape_ok has accepted
+int frozen_load(Engine* E, const FrozenTensor& t, const float* p, const int64_t* shape, hipStream_t s) {
+  const size_t n = (size_t)t.r * (t.c ? t.c : 1);
+  switch (t.kind) {
+    case FZ_F32: return upload_f32(E, p, n, (float**)t.slot, s);
+    case FZ_LINEAR: return pack_linear(E, p, t.r, t.c, (Linear*)t.slot, s);
+    case FZ_CONV1: {
+      void* w = nullptr;
+      HIPCHK(E, hipMalloc(&w, (size_t)t.r * E->Kp * 2)); E->owned.push_back(w);
+      HIPCHK(E, launch_pack_weight(E->dt, p, w, t.r, 3 * t.c * t.c, E->Kp, s));
+      *(void**)t.slot = w;
+      return 0;
+    }
+    case FZ_PROJ: {
+      // proj is [r, c]: forward Bt = proj^T [c, r]; dX Bt = proj [r, c]; both kept in fp32 (the projections next to the logits)
+      void *w = nullptr, *wt = nullptr;
+      HIPCHK(E, hipMalloc(&w, n * 4)); E->owned.push_back(w);
+      HIPCHK(E, hipMalloc(&wt, n * 4)); E->owned.push_back(wt);
+      HIPCHK(E, launch_pack_weight(DT_F32, p, w, t.r, t.c, t.c, s));
+      HIPCHK(E, launch_pack_weight_t(DT_F32, p, wt, t.r, t.c, s));
+      *(float**)t.slot = (float*)w; *t.slot_t = (float*)wt;
+      return 0;
+    }
+    case FZ_TOKENS: {
+      E->vocab = 0;
+      const int rc = upload_f32(E, p, (size_t)shape[0] * t.c, (float**)t.slot, s);
+      if (!rc) E->vocab = (int)shape[0];
+      return rc;
+    }
+  }
+  return 0;
+}
+
 int load_block_tensor(Engine* E, TowerW& W, int layer, const char* tail, const float* p, const int64_t* shape, int ndim,
                       hipStream_t s) {
   if (layer < 0 || layer >= W.layers) return fail(E, MVLPT_ERR_ARG, "layer index out of range");
-  Block& B = W.blocks[layer];
-  const int d = W.width;
-  auto is2 = [&](int r, int c) { return ndim == 2 && shape[0] == r && shape[1] == c; };
-  auto is1 = [&](int r) { return ndim == 1 && shape[0] == r; };
-  std::string t(tail);
-  if (t == "attn.in_proj_weight") { if (!is2(3 * d, d)) goto bad; return pack_linear(E, p, 3 * d, d, &B.qkv, s); }
-  if (t == "attn.in_proj_bias") { if (!is1(3 * d)) goto bad; return upload_f32(E, p, 3 * d, &B.qkv.b, s); }
-  if (t == "attn.out_proj.weight") { if (!is2(d, d)) goto bad; return pack_linear(E, p, d, d, &B.o, s); }
-  if (t == "attn.out_proj.bias") { if (!is1(d)) goto bad; return upload_f32(E, p, d, &B.o.b, s); }
-  if (t == "mlp.c_fc.weight") { if (!is2(4 * d, d)) goto bad; return pack_linear(E, p, 4 * d, d, &B.fc, s); }
-  if (t == "mlp.c_fc.bias") { if (!is1(4 * d)) goto bad; return upload_f32(E, p, 4 * d, &B.fc.b, s); }
-  if (t == "mlp.c_proj.weight") { if (!is2(d, 4 * d)) goto bad; return pack_linear(E, p, d, 4 * d, &B.pr, s); }
-  if (t == "mlp.c_proj.bias") { if (!is1(d)) goto bad; return upload_f32(E, p, d, &B.pr.b, s); }
-  if (t == "ln_1.weight") { if (!is1(d)) goto bad; return upload_f32(E, p, d, &B.ln1.g, s); }
-  if (t == "ln_1.bias") { if (!is1(d)) goto bad; return upload_f32(E, p, d, &B.ln1.b, s); }
-  if (t == "ln_2.weight") { if (!is1(d)) goto bad; return upload_f32(E, p, d, &B.ln2.g, s); }
-  if (t == "ln_2.bias") { if (!is1(d)) goto bad; return upload_f32(E, p, d, &B.ln2.b, s); }
+  for (const FrozenTensor& t : block_tensors(W.blocks[layer], W.width)) {
+    if (strcmp(tail, t.name)) continue;
+    if (!frozen_shape_ok(t, shape, ndim)) return fail(E, MVLPT_ERR_ARG, std::string("shape mismatch for block tensor ") + tail);
+    return frozen_load(E, t, p, shape, s);
+  }
   return fail(E, MVLPT_ERR_ARG, std::string("unknown block tensor: ") + tail);
-bad:
-  return fail(E, MVLPT_ERR_ARG, std::string("shape mismatch for block tensor ") + tail);
 }
 
 const char* first_missing(Engine* E) {
@@ -794,24 +848,14 @@ const char* first_missing(Engine* E) {
       if (!E->rn.have[i] && m.empty()) m = std::string("visual.attnpool.") + pn[i] + "_proj.weight";
       if (!E->rn.have[4 + i] && m.empty()) m = std::string("visual.attnpool.") + pn[i] + "_proj.bias";
     }
-  } else {
-  chk(E->conv_w, "visual.conv1.weight"); chk(E->cls_emb, "visual.class_embedding"); chk(E->vpos, "visual.positional_embedding");
-  chk(E->ln_pre.g, "visual.ln_pre.weight"); chk(E->ln_pre.b, "visual.ln_pre.bias");
-  chk(E->ln_post.g, "visual.ln_post.weight"); chk(E->ln_post.b, "visual.ln_post.bias"); chk(E->vproj, "visual.proj");
   }
-  chk(E->tpos, "positional_embedding"); chk(E->ln_final.g, "ln_final.weight"); chk(E->ln_final.b, "ln_final.bias");
-  chk(E->tproj, "text_projection");
+  // (every forward asks: a name is put together only for a tensor that is missing)
+  for (const FrozenTensor& t : top_tensors(E)) if (t.kind != FZ_TOKENS && !frozen_loaded(t) && m.empty()) m = t.name;
   for (int t = 0; t < 2; ++t) {
     TowerW& W = t ? E->txt : E->vis;
-    const std::string pre = t ? "transformer.resblocks." : "visual.transformer.resblocks.";
-    for (int l = 0; l < W.layers; ++l) {
-      const Block& B = W.blocks[l]; const std::string q = pre + std::to_string(l) + ".";
-      chk(B.qkv.w, q + "attn.in_proj_weight"); chk(B.qkv.b, q + "attn.in_proj_bias");
-      chk(B.o.w, q + "attn.out_proj.weight"); chk(B.o.b, q + "attn.out_proj.bias");
-      chk(B.fc.w, q + "mlp.c_fc.weight"); chk(B.fc.b, q + "mlp.c_fc.bias");
-      chk(B.pr.w, q + "mlp.c_proj.weight"); chk(B.pr.b, q + "mlp.c_proj.bias");
-      chk(B.ln1.g, q + "ln_1.weight"); chk(B.ln1.b, q + "ln_1.bias"); chk(B.ln2.g, q + "ln_2.weight"); chk(B.ln2.b, q + "ln_2.bias");
-    }
+    for (int l = 0; l < W.layers; ++l)
+      for (const FrozenTensor& b : block_tensors(W.blocks[l], W.width))
+        if (!frozen_loaded(b) && m.empty()) m = (t ? "transformer.resblocks." : "visual.transformer.resblocks.") + std::to_string(l) + "." + b.name;
   }
   return m.empty() ? nullptr : m.c_str();
 }
@@ -986,20 +1030,17 @@ int resnet_fwd(Engine* E, const void* image, int image_dtype, int B, float* feat
   if ((size_t)B * res * res / 4 * w > (size_t)1 << 40 || B > 65535) return fail(E, MVLPT_ERR_ARG, "image_fwd: batch too large");
   // the largest map: the stem's last conv and the first stage's output, B * (res/2)^2 * w elements; five maps live at once
   const size_t mapn = (size_t)B * (res / 2) * (res / 2) * w;
-  const size_t need = align256((size_t)B * res * res * 8 * 2) + 5 * align256(mapn * 2) + align256((size_t)B * T * Ech * 2) +
-                      align256((size_t)B * T * 2 * Ech * 2) + 2 * align256((size_t)B * Ech * 2) + 4096;
   E->vs.valid = false;
-  HIPCHK(E, E->vis_ws.reserve(need));
-  Bump bp; bp.base = (char*)E->vis_ws.p; bp.cap = E->vis_ws.cap;
-  void* img8 = bp.take_bytes((size_t)B * res * res * 8 * 2);
-  void* buf[5];
-  for (void*& b : buf) b = bp.take_bytes(mapn * 2);
-  void* tok = bp.take_bytes((size_t)B * T * Ech * 2);
-  void* kv = bp.take_bytes((size_t)B * T * 2 * Ech * 2);
-  void* q16 = bp.take_bytes((size_t)B * Ech * 2);
-  void* o16 = bp.take_bytes((size_t)B * Ech * 2);
+  void *img8, *buf[5], *tok, *kv, *q16, *o16;
+  if (int rc = carve_ws(E, E->vis_ws, "image_fwd (ResNet)", kCarveSlack, [&](Bump& bp) {
+        img8 = bp.take_bytes((size_t)B * res * res * 8 * 2);
+        for (void*& b : buf) b = bp.take_bytes(mapn * 2);
+        tok = bp.take_bytes((size_t)B * T * Ech * 2);
+        kv = bp.take_bytes((size_t)B * T * 2 * Ech * 2);
+        q16 = bp.take_bytes((size_t)B * Ech * 2);
+        o16 = bp.take_bytes((size_t)B * Ech * 2);
+      })) return rc;
   void *x = buf[0], *a = buf[1], *b = buf[2], *c = buf[3], *d = buf[4];
-  if (bp.off > bp.cap) return fail(E, MVLPT_ERR_STATE, "image_fwd (ResNet): the workspace carve exceeds its reservation");
 
   { ProfScope ps(E, s, PC_GLUE, 0, (double)B * res * res * (3.0 * 4.0 + 16.0));
     HIPCHK(E, launch_nchw_to_nhwc8(image, image_dtype, img8, B, res, s)); }
@@ -1295,8 +1336,12 @@ int mvlpt_load_frozen(void* h, const char* name, const void* dev_ptr, int dtype,
   for (int i = 0; i < ndim; ++i) n *= (size_t)shape[i];
   std::string nm(name);
   if (nm == "logit_scale") return 0;  // not used by the towers
-  const bool is_tok = nm == "token_embedding.weight";   // read by mvlpt_text_encode_tokens only: the towers' packed state is untouched
-  if (!is_tok) E->fold_ready = false;      // W gamma / b + W beta of the LayerNorm folding are rebuilt from the new tensors (prepare_fold)
+  const std::vector<FrozenTensor> tops = top_tensors(E);
+  const FrozenTensor* top = nullptr;
+  for (const FrozenTensor& t : tops) if (nm == t.name) top = &t;
+  // the token table is read by mvlpt_text_encode_tokens only: the towers' packed state is untouched.  Every other call, a refused one
+  // too: W gamma / b + W beta of the LayerNorm folding are rebuilt from the new tensors (prepare_fold)
+  if (!(top && top->kind == FZ_TOKENS)) E->fold_ready = false;
   // stage as fp32
   const float* p32 = (const float*)dev_ptr;
   if (dtype != MVLPT_DT_F32) {
@@ -1304,11 +1349,6 @@ int mvlpt_load_frozen(void* h, const char* name, const void* dev_ptr, int dtype,
     HIPCHK(E, launch_cast_any_to_f32(dtype, dev_ptr, (float*)E->tmp.p, n, s));
     p32 = (const float*)E->tmp.p;
   }
-  const MvlptArch& A = E->arch;
-  const int dv = A.vision_width, dtw = A.text_width, e = A.embed_dim;
-  const int G = A.patch_size > 0 ? A.image_resolution / A.patch_size : 0, G2 = G * G;      // (a ResNet handle has no patches)
-  auto is1 = [&](int r) { return ndim == 1 && shape[0] == r; };
-  auto is2 = [&](int r, int c) { return ndim == 2 && shape[0] == r && shape[1] == c; };
   int rc = 0;
   const char* vb = "visual.transformer.resblocks.";
   const char* tb = "transformer.resblocks.";
@@ -1319,44 +1359,9 @@ int mvlpt_load_frozen(void* h, const char* name, const void* dev_ptr, int dtype,
     int layer; const char* tail;
     if (!parse_block_name(name + strlen(isv ? vb : tb), &layer, &tail)) return fail(E, MVLPT_ERR_ARG, "malformed block name: " + nm);
     rc = load_block_tensor(E, isv ? E->vis : E->txt, layer, tail, p32, shape, ndim, s);
-  } else if (nm == "visual.conv1.weight") {
-    if (!(ndim == 4 && shape[0] == dv && shape[1] == 3 && shape[2] == A.patch_size && shape[3] == A.patch_size))
-      return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
-    void* w = nullptr;
-    HIPCHK(E, hipMalloc(&w, (size_t)dv * E->Kp * 2)); E->owned.push_back(w);
-    HIPCHK(E, launch_pack_weight(E->dt, p32, w, dv, 3 * A.patch_size * A.patch_size, E->Kp, s));
-    E->conv_w = w;
-  } else if (nm == "visual.class_embedding") { if (!is1(dv)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->cls_emb, s);
-  } else if (nm == "visual.positional_embedding") { if (!is2(G2 + 1, dv)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->vpos, s);
-  } else if (nm == "visual.ln_pre.weight") { if (!is1(dv)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->ln_pre.g, s);
-  } else if (nm == "visual.ln_pre.bias") { if (!is1(dv)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->ln_pre.b, s);
-  } else if (nm == "visual.ln_post.weight") { if (!is1(dv)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->ln_post.g, s);
-  } else if (nm == "visual.ln_post.bias") { if (!is1(dv)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->ln_post.b, s);
-  } else if (nm == "visual.proj") {
-    if (!is2(dv, e)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
-    // proj is [dv,e]: forward Bt = proj^T [e,dv]; dX Bt = proj [dv,e]; both kept in fp32
-    void *w = nullptr, *wt = nullptr;
-    HIPCHK(E, hipMalloc(&w, n * 4)); E->owned.push_back(w);
-    HIPCHK(E, hipMalloc(&wt, n * 4)); E->owned.push_back(wt);
-    HIPCHK(E, launch_pack_weight(DT_F32, p32, w, dv, e, e, s));
-    HIPCHK(E, launch_pack_weight_t(DT_F32, p32, wt, dv, e, s));
-    E->vproj = (float*)w; E->vproj_t = (float*)wt;
-  } else if (nm == "positional_embedding") { if (!is2(A.context_length, dtw)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->tpos, s);
-  } else if (nm == "ln_final.weight") { if (!is1(dtw)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->ln_final.g, s);
-  } else if (nm == "ln_final.bias") { if (!is1(dtw)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm); rc = upload_f32(E, p32, n, &E->ln_final.b, s);
-  } else if (is_tok) {
-    if (!(ndim == 2 && shape[0] > 0 && shape[0] <= INT32_MAX && shape[1] == dtw)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
-    E->vocab = 0;
-    rc = upload_f32(E, p32, n, &E->tok_emb, s);
-    if (!rc) E->vocab = (int)shape[0];
-  } else if (nm == "text_projection") {
-    if (!is2(dtw, e)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
-    void *w = nullptr, *wt = nullptr;
-    HIPCHK(E, hipMalloc(&w, n * 4)); E->owned.push_back(w);
-    HIPCHK(E, hipMalloc(&wt, n * 4)); E->owned.push_back(wt);
-    HIPCHK(E, launch_pack_weight(DT_F32, p32, w, dtw, e, e, s));
-    HIPCHK(E, launch_pack_weight_t(DT_F32, p32, wt, dtw, e, s));
-    E->tproj = (float*)w; E->tproj_t = (float*)wt;
+  } else if (top) {
+    if (!frozen_shape_ok(*top, shape, ndim)) return fail(E, MVLPT_ERR_ARG, "shape mismatch: " + nm);
+    rc = frozen_load(E, *top, p32, shape, s);
   } else {
     return fail(E, MVLPT_ERR_ARG, "unknown frozen tensor name: " + nm);
   }
@@ -1439,17 +1444,15 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
   const size_t X = exact ? 2 : 1;
   const size_t npatch = (size_t)B * G2;
   const bool gelu = E->act == ACT_GELU;
-  size_t need = tower_bytes(E->vis, B, Lv, save, exact, gelu) + align256(npatch * E->Kp * 2) + align256(npatch * dv * 4) +
-                compact_bytes(B, dv, X, gelu) + 4096;
-  E->vs.valid = false;
-  HIPCHK(E, E->vis_ws.reserve(need));
-  Bump bp; bp.base = (char*)E->vis_ws.p; bp.cap = E->vis_ws.cap;
-  void* patches = bp.take_bytes(npatch * E->Kp * 2);
-  float* pe = bp.take<float>(npatch * dv);
-  carve_compact(bp, E->vc, B, dv, X, gelu);
-  carve_tower(bp, E->vis, E->vs, B, Lv, save, false, exact, split_kind(E), gelu);
   TowerState& st = E->vs;
-  if (bp.off > bp.cap) { st.valid = false; return fail(E, MVLPT_ERR_STATE, "image_fwd_begin: the workspace carve exceeds its reservation"); }
+  void* patches; float* pe;
+  const int carved = carve_ws(E, E->vis_ws, "image_fwd_begin", kCarveSlack, [&](Bump& bp) {
+    patches = bp.take_bytes(npatch * E->Kp * 2);
+    pe = bp.take<float>(npatch * dv);
+    carve_compact(bp, E->vc, B, dv, X, gelu);
+    carve_tower(bp, E->vis, st, B, Lv, save, false, exact, split_kind(E), gelu);
+  });
+  if (carved) { st.valid = false; return carved; }
   E->vB = B; E->v_nvpt = n_vpt; E->v_ndeep = n_deep;
   st.fold = E->fold_mode >= 1 && (size_t)B * Lv >= (size_t)E->fold_min_rows && dv >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
@@ -1611,23 +1614,30 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 }
 
 // ------------------------------------------------------------------------------------------------ text tower
-// Bytes of txt_ws a text forward over C sequences of length L reserves, without the range table of a ranged forward and the
-// id table of mvlpt_text_encode_tokens (text_fwd_impl adds those).  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of
-// the ctx_pos table.  A saving tower is counted under the engine's activation-checkpointing setting (mvlpt_set_text_act_ckpt), the
-// same one the carve of the next forward uses.
-// mvlpt_text_workspace_bytes publishes this figure with ctx_rows = C * (L - 2), the largest n_ctx a forward accepts.  A ranged
+// What a text forward over C sequences of length L carves from txt_ws: text_fwd_impl carves with it and mvlpt_text_workspace_bytes
+// counts with it.  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of the ctx_pos table; range_ints / ids_ints: the range
+// table of a ranged forward and the id table of mvlpt_text_encode_tokens (0: none, a null pointer).  A saving tower is carved under the
+// engine's activation-checkpointing setting (mvlpt_set_text_act_ckpt).
+struct TextTables { int32_t *eot_rows = nullptr, *ctx_pos = nullptr, *range = nullptr, *ids = nullptr; };
+static void text_layout(Bump& bp, const Engine* E, TowerState& st, Compact& c, TextTables& t, int C, int L, bool save, bool exact,
+                        size_t ctx_rows, size_t range_ints, size_t ids_ints) {
+  const bool gelu = E->act == ACT_GELU;
+  carve_compact(bp, c, C, E->arch.text_width, exact ? 2 : 1, gelu);
+  t.eot_rows = bp.take<int32_t>(C);
+  t.ctx_pos = bp.take<int32_t>(ctx_rows);
+  t.range = range_ints ? bp.take<int32_t>(range_ints) : nullptr;
+  t.ids = ids_ints ? bp.take<int32_t>(ids_ints) : nullptr;
+  carve_tower(bp, E->txt, st, C, L, save, true, exact, split_kind(E), gelu, E->text_act_ckpt);
+}
+// The published figure is the count plus 8192 bytes: the Python chunk planners compare it with budgets, so it stays where it is, to the byte.
+constexpr size_t kTextSlack = 2 * kCarveSlack;
+// mvlpt_text_workspace_bytes publishes the count with ctx_rows = C * (L - 2), the largest n_ctx a forward accepts, and no tables.  A ranged
 // forward over S sequences in G <= S groups of a class table no longer than S also reserves its range table, 2 G + 1 + 2 S
 // <= 4 S + 1 ints, and uses S * n_ctx of the ctx_pos rows, so the published figure still bounds the reservation whenever
 // S * (L - 2 - n_ctx) >= 4 S + 1 + 128 ints (the 128 cover the two roundings to 256 bytes): n_ctx <= L - 7 from S = 129 sequences on,
 // n_ctx <= L - 8 from S = 65, the trainers' n_ctx = 4 or 16 at L = 77 from S = 3.  It does not when n_ctx is close to L - 2 (or for
 // a ranged forward over fewer sequences than classes); the reservation then exceeds it by at most 16 S + 514 bytes, and txt_ws
 // grows on demand.
-static size_t text_ws_bytes(Engine* E, int C, int L, bool save, bool exact, size_t ctx_rows) {
-  const int dtw = E->arch.text_width;
-  const size_t X = exact ? 2 : 1;
-  const bool gelu = E->act == ACT_GELU;
-  return tower_bytes(E->txt, C, L, save, exact, gelu, E->text_act_ckpt) + compact_bytes(C, dtw, X, gelu) + align256((size_t)C * 4) + align256(ctx_rows * 4) + 4096;
-}
 static bool text_exact(const Engine* E) { return E->prec_mode == MVLPT_PREC_SPLIT_ALL || E->prec_mode == MVLPT_PREC_SPLIT_GRAD; }
 
 // Full-width text blocks first .. end-1 of one checkpoint segment (a tower without checkpointing is one `last` segment), starting
@@ -1667,23 +1677,18 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
   // per parameter version, not per batch, so the extra matrix time does not recur — and single operands leave 5-9e-4 on the text
   // features, which put the inference logits of 5 of the 18 reference fixtures outside 1e-3 (profiles/r04_inference_parity.txt)
   const bool exact = text_exact(E);
-  const size_t X = exact ? 2 : 1;
   // ctx_pos is per class for the ranged tower, which may run fewer sequences than there are classes
   const size_t ctx_rows = (size_t)(ranged && Cg > C ? Cg : C) * (n_ctx > 0 ? n_ctx : 1);
   const size_t range_ints = ranged ? E->t_range_host.size() : 0;
   const size_t ids_ints = ids ? E->t_ids_host.size() : 0;
-  size_t need = text_ws_bytes(E, C, L, save, exact, ctx_rows) + align256(range_ints * 4) + align256(ids_ints * 4);
-  E->ts.valid = false;
-  HIPCHK(E, E->txt_ws.reserve(need));
-  Bump bp; bp.base = (char*)E->txt_ws.p; bp.cap = E->txt_ws.cap;
-  carve_compact(bp, E->tc, C, dtw, X, E->act == ACT_GELU);
-  E->eot_rows = bp.take<int32_t>(C);
-  E->ctx_pos = bp.take<int32_t>(ctx_rows);
-  int32_t* range_dev = ranged ? bp.take<int32_t>(range_ints) : nullptr;
-  int32_t* ids_dev = ids ? bp.take<int32_t>(ids_ints) : nullptr;
-  carve_tower(bp, E->txt, E->ts, C, L, save, true, exact, split_kind(E), E->act == ACT_GELU, E->text_act_ckpt);
   TowerState& st = E->ts;
-  if (bp.off > bp.cap) { st.valid = false; return fail(E, MVLPT_ERR_STATE, "text_fwd: the workspace carve exceeds its reservation"); }
+  TextTables tab;
+  const int carved = carve_ws(E, E->txt_ws, "text_fwd", kTextSlack, [&](Bump& bp) {
+    text_layout(bp, E, st, E->tc, tab, C, L, save, exact, ctx_rows, range_ints, ids_ints);
+  });
+  if (carved) { st.valid = false; return carved; }
+  E->eot_rows = tab.eot_rows; E->ctx_pos = tab.ctx_pos;
+  int32_t *const range_dev = tab.range, *const ids_dev = tab.ids;
   E->tC = C; E->tL = L; E->t_nctx = n_ctx; E->t_per_class = ctx_per_class;
   E->t_kind = kind; E->t_groups = G; E->t_rlo = range_dev; E->t_rstart = ranged ? range_dev + G : nullptr;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
@@ -1808,7 +1813,11 @@ int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, in
   Engine* E = (Engine*)h;
   if (!E || !out || C_total <= 0 || L <= 2) return fail(E, MVLPT_ERR_ARG, "text_workspace_bytes: null/invalid argument");
   // the ctx_pos table is sized for the largest n_ctx a forward accepts (L - 2): at most C_total * L * 4 bytes over the exact figure
-  *out = (int64_t)text_ws_bytes(E, C_total, L, save_for_bwd != 0, text_exact(E), (size_t)C_total * (L - 2));
+  // a counting pass into scratch state: a saved forward whose backward has not run keeps its own
+  TowerState st; Compact c; TextTables tab;
+  *out = (int64_t)(carve_count([&](Bump& bp) {
+    text_layout(bp, E, st, c, tab, C_total, L, save_for_bwd != 0, text_exact(E), (size_t)C_total * (L - 2), 0, 0);
+  }) + kTextSlack);
   return 0;
 }
 
@@ -1855,15 +1864,14 @@ int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stre
 }
 
 // ------------------------------------------------------------------------------------------------ head
-static int head_reserve(Engine* E, int B, int C) {
+// The normalised rows and norms of B image and C text features; the ranged head's table of `ints` ints behind them (*tab)
+static int head_carve(Engine* E, const char* who, int B, int C, size_t ints = 0, int32_t** tab = nullptr) {
   const int e = E->arch.embed_dim;
-  const size_t need = align256((size_t)B * e * 4) + align256((size_t)C * e * 4) + align256((size_t)B * 4) +
-                      align256((size_t)C * 4) + 4096;
-  HIPCHK(E, E->head_ws.reserve(need));
-  Bump bp; bp.base = (char*)E->head_ws.p;
-  E->imn = bp.take<float>((size_t)B * e); E->txn = bp.take<float>((size_t)C * e);
-  E->inorm = bp.take<float>(B); E->tnorm = bp.take<float>(C);
-  return 0;
+  return carve_ws(E, E->head_ws, who, kCarveSlack, [&](Bump& bp) {
+    E->imn = bp.take<float>((size_t)B * e); E->txn = bp.take<float>((size_t)C * e);
+    E->inorm = bp.take<float>(B); E->tnorm = bp.take<float>(C);
+    if (tab) *tab = bp.take<int32_t>(ints);
+  });
 }
 
 int mvlpt_logits_fwd(void* h, const float* img, const float* txt, float scale, const int32_t* lo, const int32_t* hi, int B, int C,
@@ -1874,7 +1882,7 @@ int mvlpt_logits_fwd(void* h, const float* img, const float* txt, float scale, c
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
   E->hB = 0;
-  if (int rc = head_reserve(E, B, C)) return rc;
+  if (int rc = head_carve(E, "logits_fwd", B, C)) return rc;
   ProfScope ps(E, s, PC_HEAD, 2.0 * B * C * e, 4.0 * ((double)B * e + (double)C * e + (double)B * C));
   HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, B, e, s));
   HIPCHK(E, launch_normalize_rows(txt, E->txn, E->tnorm, C, e, s));
@@ -1899,13 +1907,8 @@ static int head_ranged_fwd(Engine* E, const float* img, const float* txt, float 
                            hipStream_t s) {
   const int e = E->arch.embed_dim;
   const size_t ints = E->h_range_host.size();
-  const size_t need = align256((size_t)G * e * 4) + align256((size_t)S * e * 4) + align256((size_t)G * 4) + align256((size_t)S * 4) +
-                      align256(ints * 4) + 4096;
-  HIPCHK(E, E->head_ws.reserve(need));
-  Bump bp; bp.base = (char*)E->head_ws.p;
-  E->imn = bp.take<float>((size_t)G * e); E->txn = bp.take<float>((size_t)S * e);
-  E->inorm = bp.take<float>(G); E->tnorm = bp.take<float>(S);
-  int32_t* tab = bp.take<int32_t>(ints);
+  int32_t* tab = nullptr;
+  if (int rc = head_carve(E, "logits_ranged_fwd", G, S, ints, &tab)) return rc;
   ProfScope ps(E, s, PC_HEAD, 2.0 * S * e, 4.0 * ((double)G * e + (double)S * e + (double)G * C));
   HIPCHK(E, hipMemcpyAsync(tab, E->h_range_host.data(), ints * 4, hipMemcpyHostToDevice, s));
   HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, G, e, s));

@@ -237,7 +237,7 @@ def _align256(n):
 
 
 def _per_layer_and_boundary(arch, C_, L, X):
-    """The six per-layer terms of the engine's tower_bytes (x twice, qkv, attn, lse, u) and one fp32 boundary buffer."""
+    """The six per-layer terms of the engine's carve_tower (x twice, qkv, attn, lse, u) and one fp32 boundary buffer."""
     T, d, H = C_ * L, arch.transformer_width, arch.transformer_heads
     x = _align256(T * d * 4)
     return 2 * x + _align256(T * 3 * d * 2 * X) + _align256(T * d * 2 * X) + _align256(C_ * H * L * 4) + _align256(T * 4 * d * 2), x

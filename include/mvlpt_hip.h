@@ -222,6 +222,25 @@ int mvlpt_text_fwd_ranged(void* handle, const float* prefix, const float* suffix
  * fixed order (no atomics: deterministic); all zeros for an empty range.  CoCoOp's full ranges: dfeat [G*C,embed], dctx[g] = sum over
  * the C classes of image g. */
 int mvlpt_text_bwd(void* handle, const float* dfeat, float* dctx, mvlpt_stream_t stream);
+/* Deep language prompting (per-layer text contexts; the language half of MaPLe, "independent V-L prompting" next to deep visual prompts).
+ * The tower of mvlpt_text_fwd with a generic context ctx [n_ctx,dt] and, in front of block l = 1 .. n_deep, the hidden states at the
+ * context positions replaced: x_l[c, ctx_pos[c,j], :] = ctx_deep[l-1, j, :], ctx_deep [n_deep,n_ctx,dt] fp32, for every class c and
+ * every CLASS_TOKEN_POSITION (the positions come from `layout`).  No positional embedding is added to the replaced rows.  Blocks behind
+ * n_deep run on whatever the block in front of them left; no block is skipped.  1 <= n_deep <= text_layers - 1.  ln_1 of a block behind
+ * an overwrite is not folded into the FC2 in front of it (n_deep more LayerNorm launches when LayerNorm folding is on).
+ * n_deep == 0 (ctx_deep is then ignored) launches what mvlpt_text_fwd launches: the same bits.
+ * MVLPT_ERR_ARG before any device work: n_deep > text_layers - 1, n_deep < 0, n_deep > 0 with n_ctx == 0 or with ctx_deep == NULL.
+ * Per-class (CSC) deep prompts, the ranged tower and token-id sequences are not offered on this entry.
+ * With save_for_bwd, ctx_deep must stay valid and unchanged until the backward has been enqueued on the same stream: under
+ * mvlpt_set_text_act_ckpt the backward's recomputation of a segment reads it again.  mvlpt_text_workspace_bytes is unchanged.
+ * Backward: dctx as mvlpt_text_bwd; dctx_deep [n_deep,n_ctx,dt], dctx_deep[l-1, j] = sum over the classes (fixed order, no atomics) of
+ * the gradient at the input of block l at ctx_pos[c,j]; those rows then carry no gradient into block l-1.  After a deep forward
+ * mvlpt_text_bwd returns MVLPT_ERR_STATE (call mvlpt_text_bwd_deep); mvlpt_text_bwd_deep after a forward without deep prompts is
+ * mvlpt_text_bwd and accepts dctx_deep == NULL. */
+int mvlpt_text_fwd_deep(void* handle, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const float* ctx_deep,
+                        int n_deep, const int32_t* layout, const int32_t* eot, int C, int L, float* feat_out, int save_for_bwd,
+                        mvlpt_stream_t stream);
+int mvlpt_text_bwd_deep(void* handle, const float* dfeat, float* dctx, float* dctx_deep, mvlpt_stream_t stream);
 /* *out = bytes of text-tower workspace a text_fwd / text_fwd_ranged over C_total sequences of length L reserves (the
  * ctx-position table counted for the largest n_ctx, L - 2; a ranged tower adds its range tables and a per-class
  * position table, a few bytes per class and sequence, which the figure covers unless n_ctx is within a few tokens of L - 2); the
@@ -494,6 +513,15 @@ int mvlpt_op_attention_bwd_cls(int dtype, const void* qkv, const void* o_cls, co
                                int L, int H, mvlpt_stream_t stream);
 int mvlpt_op_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, mvlpt_stream_t stream);
 int mvlpt_op_overwrite_rows(const float* rows, int n, float* x, int B, int L, int d, const float* vmask, mvlpt_stream_t stream);
+/* the glue of mvlpt_text_fwd_deep / text_bwd_deep (tests/test_hip_deep_text_ops.py); ctx_pos int32 [C,n_ctx] with entries in [0, L)
+ * (an entry outside is skipped), d % 4 == 0:
+ * overwrite_ctx_rows: x[c, ctx_pos[c,j], :] = rows[j, :], x [C,L,d] fp32, rows [n_ctx,d]; no other row is written.
+ * gather_zero_ctx_grad: out [n_ctx,d] = scale_dev[1] (or 1 when NULL) * sum_c dx32[c, ctx_pos[c,j], :] with the bits of
+ *   gather_ctx_grad (per_class = 0), then those rows of dx32 [C,L,d] and of its 16-bit copy dx16 (may be NULL; split16 as in
+ *   reduce_prompt_rows; of a mixed row the hi plane and the d residual bytes) are zero; nothing else is written. */
+int mvlpt_op_overwrite_ctx_rows(const float* rows, const int32_t* ctx_pos, float* x, int C, int L, int d, int n_ctx, mvlpt_stream_t stream);
+int mvlpt_op_gather_zero_ctx_grad(int dtype, float* dx32, void* dx16, int split16, const int32_t* ctx_pos, int C, int L, int d, int n_ctx,
+                                  float* out, const float* scale_dev, mvlpt_stream_t stream);
 int mvlpt_op_assemble_tokens(const float* patch_emb, const float* cls, const float* pos, const float* ln_g, const float* ln_b,
                              const float* vpt, int n_vpt, const float* vmask, float* x, int B, int G2, int d, mvlpt_stream_t stream);
 int mvlpt_op_assemble_prompts(const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,

@@ -114,6 +114,8 @@ SIGNATURES = {
     "mvlpt_image_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mvlpt_text_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_bwd": (_i, [_vp, _vp, _vp, _vp]),
+    "mvlpt_text_fwd_deep": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
+    "mvlpt_text_bwd_deep": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mvlpt_text_fwd_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
     "mvlpt_text_workspace_bytes": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int64)]),
     "mvlpt_set_text_act_ckpt": (_i, [_vp, _i]),
@@ -183,6 +185,8 @@ SIGNATURES = {
     "mvlpt_op_attention_bwd_cls": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvlpt_op_copy_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvlpt_op_overwrite_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "mvlpt_op_overwrite_ctx_rows": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_gather_zero_ctx_grad": (_i, [_i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mvlpt_op_assemble_tokens": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
     "mvlpt_op_assemble_prompts": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "mvlpt_nearest_workspace_bytes": (_i, [_i, _i, _i, _i, _vp, C.POINTER(C.c_int64)]),

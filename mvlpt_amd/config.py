@@ -114,7 +114,11 @@ def get_cfg_default() -> CfgNode:
     cfg.TRAINER.MVLPT = CN(
         PREC="fp16", PROJECT_METHOD="transformer", PROJECT_DIM=128,
         VPT=CN(N_CTX=0, CSC=False, CTX_INIT="", DROPOUT=0.0, PROJECT=-1, DEEP=True),
-        COOP=CN(N_CTX=0, CSC=False, CTX_INIT="", CLASS_TOKEN_POSITION="middle"),
+        # N_DEEP (not in the reference): deep language prompting, the text-side twin of VPT.DEEP.  The hidden states at the context
+        # positions in front of text blocks 1 .. N_DEEP are replaced by learned rows (prompt_learner.ctx_deep [N_DEEP, n_ctx, width]);
+        # with VPT.DEEP and PROJECT_METHOD "identity" beside it this is MaPLe's "independent V-L prompting".  0: off.  Needs
+        # N_CTX > 0 and a generic context (no CSC), at most text_layers - 1; refused with the UPT projection and COCOOP.N_CTX != 0.
+        COOP=CN(N_CTX=0, CSC=False, CTX_INIT="", CLASS_TOKEN_POSITION="middle", N_DEEP=0),
         COCOOP=CN(N_CTX=0, CTX_INIT="", PREC="fp16"),
         # not in the reference: MFMA input type of the MI355X towers
         COMPUTE_DTYPE="fp16",

@@ -237,6 +237,8 @@ struct Engine {
   // text fwd extras
   int tC = 0, tL = 0, t_nctx = 0, t_per_class = 0; int32_t* eot_rows = nullptr; int32_t* ctx_pos = nullptr;
   TextKind t_kind = TextKind::Plain;   // the last text forward
+  // deep text prompts (mvlpt_text_fwd_deep): ctx_deep [t_ndeep, t_nctx, dt], the caller's buffer, read again by the backward's recomputation
+  int t_ndeep = 0; const float* t_ctx_deep = nullptr;
   // TextKind::Ranged (mvlpt_text_fwd_ranged): t_groups groups, tC = sum of the range widths; device tables in txt_ws
   int t_groups = 0; const int32_t *t_rlo = nullptr, *t_rstart = nullptr;
   std::vector<int32_t> t_range_host, h_range_host;   // host images of the range tables (source of the asynchronous upload)
@@ -1644,11 +1646,22 @@ static bool text_exact(const Engine* E) { return E->prec_mode == MVLPT_PREC_SPLI
 // from the stand-alone ln_1.  Only the last segment hands a folded ln_1 on to the block behind it (the compact last block); a
 // checkpointed one closes with the plain residual epilogue, so that the segment behind it starts the same way in the first pass and
 // in the backward's recomputation.  *ln1_ready: what the block behind `end - 1` finds.
+// Deep text prompts: the context rows of block l's input (1 <= l <= t_ndeep) are replaced by ctx_deep[l - 1] in front of the block, in
+// the first pass and in the recomputation alike (writing a segment's boundary buffer twice writes the same values).
+static int text_deep_overwrite(Engine* E, TowerState& st, int l, hipStream_t s) {
+  if (l < 1 || l > E->t_ndeep) return 0;
+  const int dtw = st.d, n = E->t_nctx;
+  ProfScope ps(E, s, PC_GLUE, 0, (double)st.N * n * dtw * 4.0);
+  HIPCHK(E, launch_overwrite_ctx_rows(E->t_ctx_deep + (size_t)(l - 1) * n * dtw, E->ctx_pos, st.x[2 * l], st.N, st.L, dtw, n, s));
+  return 0;
+}
 static int text_segment_fwd(Engine* E, TowerState& st, int first, int end, bool last, bool* ln1_ready, hipStream_t s) {
   *ln1_ready = false;
   for (int l = first; l < end; ++l) {
+    if (int rc = text_deep_overwrite(E, st, l, s)) return rc;
     bool produced = false;
-    const bool next = st.fold && (last || l + 1 < end);
+    // (ln_1 of a block behind an overwrite is not folded: its input rows change after the FC2 in front of it wrote them)
+    const bool next = st.fold && (last || l + 1 < end) && l + 1 > E->t_ndeep;
     if (int rc = block_fwd(E, E->txt, st, l, s, *ln1_ready, next ? &E->txt.blocks[l + 1].ln1 : nullptr, &produced)) return rc;
     *ln1_ready = produced;
   }
@@ -1659,9 +1672,10 @@ static int text_segment_fwd(Engine* E, TowerState& st, int first, int end, bool 
 // G = 0, Cg = C).  Ranged: mvlpt_text_fwd_ranged, G groups over the [Cg, ...] class tables and ctx [G, n_ctx, d], C = S
 // sequences described by E->t_range_host.  Ids: mvlpt_text_encode_tokens, C sequences of token ids (E->t_ids_host); no prefix /
 // suffix / ctx / layout / eot tables.
+// Deep (mvlpt_text_fwd_deep): a plain tower whose context rows are replaced by ctx_deep [n_deep, n_ctx, d] in front of blocks 1 .. n_deep.
 static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
                          const int32_t* layout, const int32_t* eot, int G, int Cg, int C, int L, float* feat_out, int save_for_bwd,
-                         mvlpt_stream_t stream) {
+                         mvlpt_stream_t stream, const float* ctx_deep = nullptr, int n_deep = 0) {
   const bool ranged = kind == TextKind::Ranged, ids = kind == TextKind::Ids;
   if (int rc = mvlpt_frozen_ready(E)) return rc;
   if ((n_ctx > 0) != (ctx != nullptr) || n_ctx < 0 || n_ctx > L - 2) return fail(E, MVLPT_ERR_ARG, "text_fwd: ctx pointer and n_ctx disagree");
@@ -1691,6 +1705,7 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
   int32_t *const range_dev = tab.range, *const ids_dev = tab.ids;
   E->tC = C; E->tL = L; E->t_nctx = n_ctx; E->t_per_class = ctx_per_class;
   E->t_kind = kind; E->t_groups = G; E->t_rlo = range_dev; E->t_rstart = ranged ? range_dev + G : nullptr;
+  E->t_ndeep = n_deep; E->t_ctx_deep = n_deep > 0 ? ctx_deep : nullptr;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
   if (ids) {
@@ -1709,7 +1724,7 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
     } else {
       HIPCHK(E, launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, E->tpos, st.x[0], C, L, dtw, s));
       HIPCHK(E, launch_eot_rows(eot, E->eot_rows, C, L, s));
-      if (save && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, C, L, n_ctx, s));
+      if ((save || n_deep > 0) && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, C, L, n_ctx, s));
     } }
   // Checkpointed segments (every one but the last, st.seg) run as a tower that saves nothing; their closing block writes the next
   // segment's boundary buffer.  No ln_1 is folded across a segment boundary, so mvlpt_text_bwd can repeat a segment launch for launch.
@@ -1722,6 +1737,7 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
     if (rc) { st.valid = false; return rc; }
   }
   // the last block on the C gathered EOT rows
+  if (int rc = text_deep_overwrite(E, st, E->txt.layers - 1, s)) { st.valid = false; return rc; }
   if (int rc = last_block_fwd(E, E->txt, st, E->tc, E->eot_rows, 0, false, ln1_ready, E->ln_final, false, s)) return rc;
   { ProfScope ps(E, s, PC_HEAD, 2.0 * C * e * dtw, 4.0 * ((double)C * dtw + (double)e * dtw + (double)C * e));
     HIPCHK(E, launch_sgemm_bt(E->tc.out32, E->tproj_t, feat_out, C, e, dtw, nullptr, s)); }
@@ -1735,6 +1751,23 @@ int mvlpt_text_fwd(void* h, const float* prefix, const float* suffix, const floa
   if (!E || !prefix || !suffix || !layout || !eot || !feat_out || C <= 0 || L <= 0)
     return fail(E, MVLPT_ERR_ARG, "text_fwd: null/invalid argument");
   return text_fwd_impl(E, TextKind::Plain, prefix, suffix, ctx, ctx_per_class, n_ctx, layout, eot, 0, C, C, L, feat_out, save_for_bwd, stream);
+}
+
+// Deep language prompting: mvlpt_text_fwd with a generic context whose rows are replaced in front of blocks 1 .. n_deep
+int mvlpt_text_fwd_deep(void* h, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const float* ctx_deep, int n_deep,
+                        const int32_t* layout, const int32_t* eot, int C, int L, float* feat_out, int save_for_bwd, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !prefix || !suffix || !layout || !eot || !feat_out || C <= 0 || L <= 0)
+    return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: null/invalid argument");
+  if (n_deep < 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: n_deep is negative");
+  if (n_deep > 0) {
+    if (!ctx_deep) return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: ctx_deep is null with n_deep > 0");
+    if (n_ctx <= 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: deep prompts need context tokens (n_ctx == 0)");
+    if (n_deep > E->txt.layers - 1)
+      return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: n_deep exceeds text_layers - 1 (block 0 reads the embedding-level context)");
+  }
+  return text_fwd_impl(E, TextKind::Plain, prefix, suffix, ctx, 0, n_ctx, layout, eot, 0, C, C, L, feat_out, save_for_bwd, stream,
+                       ctx_deep, n_deep);
 }
 
 // The MVLPT trainer's CoCoOp branch under the per-task mask (trainers/mvlpt.py:556-581): image g runs only the classes of its own task.
@@ -1821,14 +1854,17 @@ int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, in
   return 0;
 }
 
-int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !dfeat || !dctx) return fail(E, MVLPT_ERR_ARG, "text_bwd: null argument");
+// The backward of every text forward.  dctx_deep: the gradient of the deep prompts (mvlpt_text_bwd_deep); `plain` (mvlpt_text_bwd) has
+// no place for it and refuses a deep forward.
+static int text_bwd_impl(Engine* E, const float* dfeat, float* dctx, float* dctx_deep, bool plain, mvlpt_stream_t stream) {
   TowerState& st = E->ts;
   if (st.valid && st.consumed)
     return fail(E, MVLPT_ERR_STATE, "text_bwd: a backward under activation checkpointing has consumed the saved state; run the forward again");
   if (!st.valid || !st.saved) return fail(E, MVLPT_ERR_STATE, "text_bwd: call text_fwd(save_for_bwd=1) first");
   if (E->t_nctx <= 0) return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward had no context tokens");
+  if (E->t_ndeep > 0 && plain)
+    return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward ran deep prompts (mvlpt_text_fwd_deep); call mvlpt_text_bwd_deep");
+  if (E->t_ndeep > 0 && !dctx_deep) return fail(E, MVLPT_ERR_ARG, "text_bwd_deep: dctx_deep is null after a forward with deep prompts");
   hipStream_t s = (hipStream_t)stream;
   const MvlptArch& A = E->arch;
   const int C = E->tC, L = E->tL, dtw = A.text_width, e = A.embed_dim;
@@ -1842,16 +1878,30 @@ int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stre
   // the plan of the forward that saved this state (st.seg), not the engine's current setting
   const int k = (int)st.seg.size() - 1;
   if (k > 1) st.consumed = true;      // from here on the slots no longer hold what the forward left
+  // gradient of the deep prompts of block l (its input's context rows), which then stop carrying one into block l - 1
+  auto gather_deep = [&](int l) -> int {
+    if (l < 1 || l > E->t_ndeep) return 0;
+    const int n = E->t_nctx;
+    ProfScope ps(E, s, PC_GLUE, 0, (double)C * n * dtw * 10.0);
+    HIPCHK(E, launch_gather_zero_ctx_grad(E->dt, st.dx32, st.dx16, st.xs, E->ctx_pos, C, L, dtw, n, dctx_deep + (size_t)(l - 1) * n * dtw,
+                                          st.scale_dev, s));
+    return 0;
+  };
   if (int rc = last_block_bwd(E, E->txt, st, E->tc, E->eot_rows, 0, E->ln_final, s)) return rc;      // the last block on the C compact EOT rows
-  for (int l = st.layers - 2; l >= st.seg[k - 1]; --l)
+  if (int rc = gather_deep(st.layers - 1)) return rc;
+  for (int l = st.layers - 2; l >= st.seg[k - 1]; --l) {
     if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
+    if (int rc = gather_deep(l)) return rc;
+  }
   // checkpointed segments, from the back: the forward's launches again from the segment's input, this time keeping lse / u, into
   // the slots the segment behind it no longer needs; then its backward
   for (int i = k - 2; i >= 0; --i) {
     bool ln1_ready = false;
     if (int rc = text_segment_fwd(E, st, st.seg[i], st.seg[i + 1], false, &ln1_ready, s)) return rc;
-    for (int l = st.seg[i + 1] - 1; l >= st.seg[i]; --l)
+    for (int l = st.seg[i + 1] - 1; l >= st.seg[i]; --l) {
       if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
+      if (int rc = gather_deep(l)) return rc;
+    }
   }
   { ProfScope ps(E, s, PC_GLUE, 0, (double)C * E->t_nctx * dtw * 4.0);
     if (E->t_kind == TextKind::Ranged)
@@ -1861,6 +1911,18 @@ int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stre
   if (k > 1) st.saved = false;
   st.bwd_done = true;
   return 0;
+}
+
+int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !dfeat || !dctx) return fail(E, MVLPT_ERR_ARG, "text_bwd: null argument");
+  return text_bwd_impl(E, dfeat, dctx, nullptr, true, stream);
+}
+
+int mvlpt_text_bwd_deep(void* h, const float* dfeat, float* dctx, float* dctx_deep, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !dfeat || !dctx) return fail(E, MVLPT_ERR_ARG, "text_bwd_deep: null argument");
+  return text_bwd_impl(E, dfeat, dctx, dctx_deep, false, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ head
@@ -2435,6 +2497,20 @@ int mvlpt_op_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C, int
   if (!dx || !ctx_pos || !dctx || C <= 0 || L <= 0 || n_ctx <= 0 || d <= 0)
     return fail(nullptr, MVLPT_ERR_ARG, "op_gather_ctx_grad: null/invalid argument");
   OPCHK(launch_gather_ctx_grad(dx, ctx_pos, C, L, d, n_ctx, per_class, dctx, scale_dev, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_overwrite_ctx_rows(const float* rows, const int32_t* ctx_pos, float* x, int C, int L, int d, int n_ctx, mvlpt_stream_t stream) {
+  if (!rows || !ctx_pos || !x || C <= 0 || L <= 0 || n_ctx <= 0 || n_ctx > L || d <= 0 || d % 4)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_overwrite_ctx_rows: null/invalid argument");
+  OPCHK(launch_overwrite_ctx_rows(rows, ctx_pos, x, C, L, d, n_ctx, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_gather_zero_ctx_grad(int dtype, float* dx32, void* dx16, int split16, const int32_t* ctx_pos, int C, int L, int d, int n_ctx,
+                                  float* out, const float* scale_dev, mvlpt_stream_t stream) {
+  if (!dx32 || !ctx_pos || !out || C <= 0 || L <= 0 || n_ctx <= 0 || n_ctx > L || d <= 0 || d % 4 || split16 < 0 || split16 > 2 ||
+      (dtype != DT_F16 && dtype != DT_BF16))
+    return fail(nullptr, MVLPT_ERR_ARG, "op_gather_zero_ctx_grad: null/invalid argument");
+  OPCHK(launch_gather_zero_ctx_grad(dtype, dx32, dx16, split16, ctx_pos, C, L, d, n_ctx, out, scale_dev, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_attention_bwd_cls(int dtype, const void* qkv, const void* o_cls, const void* do_cls, const float* lse, void* dqkv, int N,

@@ -1,4 +1,4 @@
-// Launcher declarations for the hand-written gfx950 kernels (gemm.hip, norm.hip, attention.hip, glue.hip).
+// Launcher declarations for the hand-written gfx950 kernels (gemm.hip, norm.hip, attention.hip, glue.hip, ...).
 // Every launcher only enqueues on the given stream; no hidden synchronisation.
 #pragma once
 #include "common.h"
@@ -313,6 +313,12 @@ hipError_t launch_eot_rows_ranged(const int32_t* eot, int32_t* rows, const int32
 // dctx (ranged) [G,n,d] = inv_scale * sum_k dx[start[g] + k, ctx_pos[lo[g] + k, j], :]  (ctx_pos per class, [C, n]); zeros for an empty range
 hipError_t launch_gather_ctx_grad_ranged(const float* dx, const int32_t* ctx_pos, const int32_t* lo, const int32_t* start, int G, int L,
                                          int d, int n_ctx, float* dctx, const float* scale_dev, hipStream_t s);
+// deep text prompts (deep_text.hip): x[c, ctx_pos[c,j], :] = rows[j, :] over x [C,L,d] fp32, rows [n_ctx,d], ctx_pos int32 [C,n_ctx]; d % 4 == 0
+hipError_t launch_overwrite_ctx_rows(const float* rows, const int32_t* ctx_pos, float* x, int C, int L, int d, int n_ctx, hipStream_t s);
+// out [n_ctx,d] = inv_scale * sum_c dx32[c, ctx_pos[c,j], :] in gather_ctx_grad's fixed order (the same bits), then those rows of dx32 and
+// of its 16-bit copy dx16 (may be null; split16 0: [C*L, d], 1: hi|lo pair [C*L, 2d], 2: mixed pair at the same pitch) are zeroed
+hipError_t launch_gather_zero_ctx_grad(int dtype, float* dx32, void* dx16, int split16, const int32_t* ctx_pos, int C, int L, int d,
+                                       int n_ctx, float* out, const float* scale_dev, hipStream_t s);
 // scale_dev[0] = 2^k with amax(|v|)*2^k ~ target ; scale_dev[1] = 1/scale_dev[0]
 hipError_t launch_grad_scale(const float* v, size_t n, float target, float* scale_dev, hipStream_t s);
 // fused optimizer step over the flat prompt buffers (optim.hip; semantics in include/mvlpt_hip.h, mvlpt_op_optim_step); the

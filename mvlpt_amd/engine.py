@@ -365,6 +365,47 @@ class Engine:
         return feat
 
     @_on_device
+    def text_fwd_deep(self, prefix: torch.Tensor, suffix: torch.Tensor, ctx: Optional[torch.Tensor], ctx_deep: Optional[torch.Tensor],
+                      layout: torch.Tensor, eot: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
+        """Deep language prompting (mvlpt_text_fwd_deep): text_fwd with a generic ctx [n_ctx, dt] whose rows are replaced by
+        ctx_deep[l - 1] ([n_deep, n_ctx, dt], 1 <= n_deep <= text_layers - 1) in front of block l.  ctx_deep None runs the plain tower
+        (the bits of text_fwd).  A following text_bwd_deep returns (dctx, dctx_deep).  The engine reads ctx_deep again in a
+        checkpointed backward; the tensor handed over here is kept until then."""
+        prefix = _req(prefix, torch.float32, "token_prefix")
+        suffix = _req(suffix, torch.float32, "token_suffix")
+        layout = _req(layout, torch.int32, "layout")
+        eot = _req(eot, torch.int32, "eot")
+        Cn, L = layout.shape
+        n_ctx = n_deep = 0
+        if ctx is not None:
+            ctx = _req(ctx, torch.float32, "ctx")
+            if ctx.dim() != 2:
+                raise ValueError("deep text prompts take a generic ctx [n_ctx, ctx_dim] (no per-class contexts)")
+            n_ctx = ctx.shape[0]
+        if ctx_deep is not None:
+            ctx_deep = _req(ctx_deep, torch.float32, "ctx_deep")
+            if ctx_deep.dim() != 3 or ctx_deep.shape[1] != n_ctx or ctx_deep.shape[2] != self.arch.transformer_width:
+                raise ValueError(f"ctx_deep must be [n_deep, {n_ctx}, {self.arch.transformer_width}], got {tuple(ctx_deep.shape)}")
+            n_deep = ctx_deep.shape[0]
+        feat = torch.empty(Cn, self.arch.embed_dim, device=prefix.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_text_fwd_deep(self.h, _ptr(prefix), _ptr(suffix), _ptr(ctx), n_ctx, _ptr(ctx_deep), n_deep, _ptr(layout),
+                                           _ptr(eot), Cn, L, _ptr(feat), int(save_for_bwd), _stream()), self.h, "text_fwd_deep")
+        self._txt_state = ((tuple(ctx.shape) if ctx is not None else None, layout, eot, ctx_deep) if save_for_bwd else None)
+        return feat
+
+    @_on_device
+    def text_bwd_deep(self, dfeat: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """(dctx, dctx_deep) of the last text_fwd_deep(save_for_bwd=True); dctx_deep is None when that forward had no deep prompts."""
+        st = self._txt_state
+        if st is None or st[0] is None or len(st) < 4:
+            raise RuntimeError("text_bwd_deep without text_fwd_deep(save_for_bwd=True) with context tokens")
+        dfeat = _req(dfeat, torch.float32, "dfeat")
+        dctx = torch.empty(st[0], device=dfeat.device, dtype=torch.float32)
+        ddeep = torch.empty(tuple(st[3].shape), device=dfeat.device, dtype=torch.float32) if st[3] is not None else None
+        _lib.check(lib.mvlpt_text_bwd_deep(self.h, _ptr(dfeat), _ptr(dctx), _ptr(ddeep), _stream()), self.h, "text_bwd_deep")
+        return dctx, ddeep
+
+    @_on_device
     def text_fwd_ranged(self, prefix: torch.Tensor, suffix: torch.Tensor, ctx: torch.Tensor, layout: torch.Tensor, eot: torch.Tensor,
                         class_lo, class_hi, save_for_bwd: bool = False) -> torch.Tensor:
         """The ranged text side (mvlpt_text_fwd_ranged): ctx [G, n_ctx, dt]; image g runs classes [class_lo[g], class_hi[g]) only.
@@ -1028,6 +1069,30 @@ def op_overwrite_rows(rows, x, vmask=None) -> torch.Tensor:
     _lib.check(lib.mvlpt_op_overwrite_rows(_ptr(rows.contiguous()), rows.shape[0], _ptr(x), B, L, d, _ptr(vmask), _stream()), None,
                "op_overwrite_rows")
     return x
+
+
+def op_overwrite_ctx_rows(rows, ctx_pos, x) -> torch.Tensor:
+    """x[c, ctx_pos[c, j]] = rows[j] IN PLACE on the contiguous fp32 x [C, L, d], which is returned; ctx_pos int32 [C, n_ctx]."""
+    C_, L, d = x.shape
+    if not x.is_contiguous() or x.dtype != torch.float32:
+        raise ValueError("op_overwrite_ctx_rows works in place: contiguous fp32 x only")
+    _lib.check(lib.mvlpt_op_overwrite_ctx_rows(_ptr(rows.contiguous()), _ptr(ctx_pos.to(torch.int32).contiguous()), _ptr(x), C_, L, d,
+                                               ctx_pos.shape[1], _stream()), None, "op_overwrite_ctx_rows")
+    return x
+
+
+def op_gather_zero_ctx_grad(dx32, dx16, ctx_pos, split16=0, scale_dev=None, dtype=None) -> torch.Tensor:
+    """out [n_ctx, d] = scale_dev[1] * sum_c dx32[c, ctx_pos[c, j]]; those rows of dx32 [C, L, d] and of its 16-bit copy dx16
+    ([C * L, d or 2d], or None) are zeroed IN PLACE."""
+    C_, L, d = dx32.shape
+    if not dx32.is_contiguous() or dx32.dtype != torch.float32 or (dx16 is not None and not dx16.is_contiguous()):
+        raise ValueError("op_gather_zero_ctx_grad works in place: contiguous tensors only")
+    dt = _TORCH2DT[dx16.dtype] if dx16 is not None else (_TORCH2DT[dtype] if dtype is not None else DT_F16)
+    n = ctx_pos.shape[1]
+    out = torch.empty(n, d, device=dx32.device, dtype=torch.float32)
+    _lib.check(lib.mvlpt_op_gather_zero_ctx_grad(dt, _ptr(dx32), _ptr(dx16), int(split16), _ptr(ctx_pos.to(torch.int32).contiguous()), C_, L,
+                                                 d, n, _ptr(out), _ptr(scale_dev), _stream()), None, "op_gather_zero_ctx_grad")
+    return out
 
 
 def op_assemble_tokens(pe, cls, pos, g, b, batch: int, vpt=None, vmask=None, fill=float("nan")) -> torch.Tensor:

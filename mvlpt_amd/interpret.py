@@ -62,7 +62,8 @@ def interpret_state_dict(state_dict: Dict[str, torch.Tensor], clip, topk: int,
       "ctx" [n_ctx, dt]          generic context       -> [words of vector 0, words of vector 1, ...]
       "ctx" [n_cls, n_ctx, dt]   class-specific (CSC)  -> {class label: [words of vector 0, ...]} (labels: `classnames`, or "class <c>")
       "cocoop_ctx" [n_ctx, dt]   the MVLPT CoCoOp route's static context, as the generic one.
-    Every other key is ignored (`token_prefix` / `token_suffix` come from the class names, as the reference's load_model notes)."""
+    Every other key is ignored (`token_prefix` / `token_suffix` come from the class names, as the reference's load_model notes;
+    `ctx_deep`, the deep text prompts, are hidden states of later blocks, not token embeddings, and have no nearest words)."""
     topk = _check_topk(topk)
     if isinstance(state_dict.get("state_dict"), dict):
         state_dict = state_dict["state_dict"]

@@ -367,6 +367,34 @@ def image_conditioned_ctx(clip_model: FrozenCLIP, n_ctx: int, ctx_init: str, ctx
     return ctx_vectors, meta_net, prompt_prefix, n_ctx
 
 
+def deep_text_prompts(cfg, arch: ClipArch) -> int:
+    """TRAINER.MVLPT.COOP.N_DEEP (absent: 0) of a model that is being built, checked against everything the deep text route does not
+    offer; every refusal names its cause and comes before anything is allocated.  Deep language prompting replaces the hidden states
+    at the context positions in front of text blocks 1 .. N_DEEP by the rows of `ctx_deep` [N_DEEP, n_ctx, width]."""
+    T = cfg.TRAINER.MVLPT
+    n_deep = int(T.COOP.get("N_DEEP", 0))
+    if n_deep == 0:
+        return 0
+    if n_deep < 0:
+        raise ValueError(f"COOP.N_DEEP = {n_deep}: the number of deep text prompt layers cannot be negative")
+    if T.COCOOP.N_CTX != 0:
+        raise NotImplementedError("COOP.N_DEEP > 0 together with COCOOP.N_CTX != 0: the image-conditioned (ranged) text tower has no "
+                                  "deep prompts; set COCOOP.N_CTX 0")
+    if T.COOP.N_CTX == 0:
+        raise ValueError("COOP.N_DEEP > 0 needs context tokens: the deep prompts replace the hidden states at the context positions, "
+                         "and COOP.N_CTX is 0")
+    if T.COOP.CSC:
+        raise NotImplementedError("COOP.N_DEEP > 0 together with COOP.CSC: per-class deep prompts are not offered (the deep rows are "
+                                  "shared by all classes); set COOP.CSC False")
+    if n_deep > arch.transformer_layers - 1:
+        raise ValueError(f"COOP.N_DEEP = {n_deep} exceeds transformer_layers - 1 = {arch.transformer_layers - 1}: block 0 reads the "
+                         "embedding-level context `ctx`, only the later blocks take deep prompts")
+    if T.VPT.N_CTX != 0 and T.PROJECT_METHOD != "identity":
+        raise NotImplementedError(f"COOP.N_DEEP > 0 with visual prompts under PROJECT_METHOD = {T.PROJECT_METHOD!r}: the UPT projection "
+                                  "has no place for the deep text prompts; set PROJECT_METHOD \"identity\" (independent V-L prompting)")
+    return n_deep
+
+
 class MultitaskVLPromptLearner(nn.Module):
     """trainers/mvlpt.py:138-515.  ``clip_model`` is a :class:`FrozenCLIP`; ``classnames`` a list of str, or a
     :class:`PretokenizedPrompts` (then ``classnames`` only gives n_cls)."""
@@ -376,6 +404,7 @@ class MultitaskVLPromptLearner(nn.Module):
         n_cls = len(classnames)
         T = cfg.TRAINER.MVLPT
         coop_n_ctx, cocoop_n_ctx, vpt_n_ctx = T.COOP.N_CTX, T.COCOOP.N_CTX, T.VPT.N_CTX
+        n_deep = deep_text_prompts(cfg, clip_model.arch)
         if cocoop_n_ctx != 0:
             raise NotImplementedError("COCOOP.N_CTX != 0 is not this class's route: image-conditioned prompts live in "
                                       "mvlpt_amd.mvlpt_cocoop (MultitaskVLPromptLearner / CustomCLIP there; MVLPT.build_model picks them)")
@@ -421,6 +450,13 @@ class MultitaskVLPromptLearner(nn.Module):
                     # 'mlp' crashes in the reference too (nn.GeLU, trainers/mvlpt.py:253)
                     raise AttributeError("module 'torch.nn' has no attribute 'GeLU'")
         self.cocoop_ctx = None
+        # deep text prompts (COOP.N_DEEP; not in the reference): drawn after every other draw, so a seed gives the same ctx / vpt_*
+        # with and without them; the attribute exists only with N_DEEP > 0, so the state_dict keys are unchanged at 0
+        self.coop_n_deep = n_deep
+        if n_deep > 0:
+            ctx_deep = torch.empty(n_deep, coop_n_ctx, coop_ctx_dim, dtype=dtype)
+            nn.init.normal_(ctx_deep, std=0.02)
+            self.ctx_deep = nn.Parameter(ctx_deep)
 
         self.vpt_n_ctx, self.coop_n_ctx, self.cocoop_n_ctx = vpt_n_ctx, coop_n_ctx, 0
         self.class_token_position = T.COOP.CLASS_TOKEN_POSITION
@@ -568,12 +604,18 @@ class _PromptedClipFn(torch.autograd.Function):
     """CustomCLIP.forward as ONE autograd node: forward and backward are libmvlpt_hip.so calls."""
 
     @staticmethod
-    def forward(fctx, model: "CustomCLIP", image, task_lo, task_hi, coop_emb, vpt_emb, vpt_deep_emb, grad_on=True):
+    def forward(fctx, model: "CustomCLIP", image, task_lo, task_hi, coop_emb, vpt_emb, vpt_deep_emb, grad_on=True, ctx_deep=None):
         eng = model.engine
         pl = model.prompt_learner
+        if ctx_deep is not None:
+            # deep text prompts (COOP.N_DEEP): the same tower through the deep entries; class sharding is refused at set-up
+            def text_fwd(prefix, suffix, ctx, layout, eot, save_for_bwd=False):
+                return eng.text_fwd_deep(prefix, suffix, ctx, ctx_deep, layout, eot, save_for_bwd=save_for_bwd)
+        else:
+            text_fwd = eng.text_fwd
         # (grad mode is off inside Function.forward: ask autograd which inputs need a gradient)
         # `grad_on` = torch.is_grad_enabled() at the call site (needs_input_grad ignores torch.no_grad())
-        need_txt = grad_on and bool(fctx.needs_input_grad[4])
+        need_txt = grad_on and bool(fctx.needs_input_grad[4] or fctx.needs_input_grad[8])
         need_img = grad_on and bool(fctx.needs_input_grad[5] or fctx.needs_input_grad[6])
         # inference: the text features depend only on the prompt parameters -> computed once per parameter version
         # instead of once per batch as the reference does (trainers/mvlpt.py:546-548 under test(), :989-1088)
@@ -637,14 +679,14 @@ class _PromptedClipFn(torch.autograd.Function):
             main = torch.cuda.current_stream()
             side.wait_stream(main)
             with torch.cuda.stream(side):
-                txt = eng.text_fwd(pl.token_prefix, suffix, coop_emb, layout, pl.eot, save_for_bwd=need_txt)
+                txt = text_fwd(pl.token_prefix, suffix, coop_emb, layout, pl.eot, save_for_bwd=need_txt)
             img = image_fwd(image, vpt_emb, vpt_deep_emb, save_for_bwd=need_img)
             main.wait_stream(side)
             txt.record_stream(main)
         else:
             img = image_fwd(image, vpt_emb, vpt_deep_emb, save_for_bwd=need_img)
             if run_text:
-                txt = eng.text_fwd(pl.token_prefix, suffix, coop_emb, layout, pl.eot, save_for_bwd=need_txt)
+                txt = text_fwd(pl.token_prefix, suffix, coop_emb, layout, pl.eot, save_for_bwd=need_txt)
         if not run_text:
             txt = model._const_text_features
         elif coop_emb is None:
@@ -662,6 +704,7 @@ class _PromptedClipFn(torch.autograd.Function):
         fctx.model, fctx.need_img, fctx.need_txt = model, need_img, need_txt
         fctx.shard, fctx.ctx_shape = shard, (None if coop_emb is None else coop_emb.shape)
         fctx.has_deep = vpt_deep_emb is not None
+        fctx.text_deep = ctx_deep is not None
         fctx.vpt_shape = None if vpt_emb is None else vpt_emb.shape
         return logits
 
@@ -672,7 +715,13 @@ class _PromptedClipFn(torch.autograd.Function):
             raise RuntimeError("backward of a stale forward: the engine holds the saved activations of the most recent "
                                "CustomCLIP.forward only (call backward before the next forward)")
         dimg, dtxt = eng.logits_bwd(dlogits.contiguous(), fctx.need_img, fctx.need_txt)
-        dctx = dvpt = ddeep = None
+        dctx = dvpt = ddeep = dctx_deep = None
+        if fctx.text_deep:
+            def text_bwd(d):
+                return eng.text_bwd_deep(d)
+        else:
+            def text_bwd(d):
+                return eng.text_bwd(d), None
         if fctx.need_txt and fctx.shard is not None:
             lo, hi = fctx.shard.lo, fctx.shard.hi
             # sum over ranks of d(local loss)/d(txt) for the classes this rank owns; the trainer's gradient
@@ -692,16 +741,18 @@ class _PromptedClipFn(torch.autograd.Function):
                 main = torch.cuda.current_stream()
                 part.wait_stream(main)
                 with torch.cuda.stream(part):
-                    dctx = eng.text_bwd(dtxt)
+                    dctx, dctx_deep = text_bwd(dtxt)
                 dtxt.record_stream(part)
                 main.wait_stream(part)
                 dctx.record_stream(main)
+                if dctx_deep is not None:
+                    dctx_deep.record_stream(main)
             else:
-                dctx = eng.text_bwd(dtxt)
+                dctx, dctx_deep = text_bwd(dtxt)
         if fctx.need_img:
             dvpt, ddeep = eng.image_bwd(dimg)
             dvpt = dvpt.view(fctx.vpt_shape)
-        return None, None, None, None, dctx, dvpt, ddeep, None
+        return None, None, None, None, dctx, dvpt, ddeep, None, dctx_deep
 
 
 class _CrossEntropyFn(torch.autograd.Function):
@@ -771,6 +822,9 @@ class CustomCLIP(nn.Module):
         if world <= 1:
             self._class_shard = None
             return
+        if getattr(self.prompt_learner, "coop_n_deep", 0) > 0:
+            raise NotImplementedError("class sharding with deep text prompts (COOP.N_DEEP > 0) is not offered: the sharded text tower "
+                                      "runs the plain entries; set COOP.N_DEEP 0 or run the text tower replicated")
         C = self.prompt_learner.n_cls
         if world > C:
             raise ValueError(f"class sharding needs at least one class per rank ({C} classes, {world} ranks)")
@@ -930,7 +984,8 @@ class CustomCLIP(nn.Module):
             t = task.cpu().long() if torch.is_tensor(task) else torch.as_tensor(task).long()
             lo = self.class_index_pertask_start[t].to(torch.int32).to(image.device)
             hi = self.class_index_pertask_end[t].to(torch.int32).to(image.device)
-        return _PromptedClipFn.apply(self, image, lo, hi, coop_emb, vpt_emb, vpt_emb_deep, torch.is_grad_enabled())
+        return _PromptedClipFn.apply(self, image, lo, hi, coop_emb, vpt_emb, vpt_emb_deep, torch.is_grad_enabled(),
+                                     getattr(self.prompt_learner, "ctx_deep", None))
 
     def cross_entropy(self, logits, label):
         """HIP replacement for ``F.cross_entropy(output, label)`` (trainers/mvlpt.py:931)."""

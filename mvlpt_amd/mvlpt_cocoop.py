@@ -35,8 +35,8 @@ import torch
 import torch.nn as nn
 
 from .cocoop import MAX_SEQUENCES_PER_TOWER, PerImageTextCLIP
-from .model import (FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, _text_inputs, class_prompt_tables, image_conditioned_ctx,
-                    register_class_tables)
+from .model import (FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, _text_inputs, class_prompt_tables, deep_text_prompts,
+                    image_conditioned_ctx, register_class_tables)
 from .model import MultitaskVLPromptLearner as _BasePromptLearner
 
 
@@ -51,6 +51,7 @@ class MultitaskVLPromptLearner(_BasePromptLearner):
         cocoop_n_ctx, vpt_n_ctx = T.COCOOP.N_CTX, T.VPT.N_CTX
         if cocoop_n_ctx == 0:
             raise ValueError("mvlpt_amd.mvlpt_cocoop is the COCOOP.N_CTX != 0 route; use mvlpt_amd.model otherwise")
+        deep_text_prompts(cfg, clip_model.arch)      # COOP.N_DEEP > 0 is refused on this route
         if T.COOP.N_CTX != 0:
             raise NotImplementedError("COOP.N_CTX != 0 together with COCOOP.N_CTX != 0: the reference builds a `ctx` its logits never "
                                       "depend on (trainers/mvlpt.py:556-571); set COOP.N_CTX 0")

@@ -740,7 +740,8 @@ class MVLPT(TrainerX):
 
     def interpret_prompt(self, topk: int = 5):
         """Nearest vocabulary words of the live model's context vectors (mvlpt_amd.interpret.interpret_model): "ctx" (per class under
-        CSC), "cocoop_ctx", and under UPT "ctx (projected)", the contexts that enter the text tower.  Never called by the loop."""
+        CSC), "cocoop_ctx", and under UPT "ctx (projected)", the contexts that enter the text tower.  The deep text prompts "ctx_deep" (COOP.N_DEEP) are ignored: they replace hidden
+        states in front of later blocks, which do not live in the space of the token embeddings.  Never called by the loop."""
         from .interpret import interpret_model
         cfg = self.cfg
         classnames = self.dm.dataset.classnames if cfg.DATASET.COOP else list(self.dm.lab2cname.values())

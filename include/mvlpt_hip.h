@@ -175,6 +175,19 @@ int mvlpt_load_frozen(void* handle, const char* name, const void* dev_ptr, int d
  * 0 when every tensor the towers need has been loaded; otherwise <0 and last_error names the first missing. */
 int mvlpt_frozen_ready(void* handle);
 
+/* What the engine remembers of a forward.  It keeps one record per job (image tower, text tower, head): the last forward of that
+ * job.  A backward, mvlpt_image_fwd_resume and mvlpt_set_activation decide by it alone, and a forward that returns an error after it
+ * has touched the job's workspace leaves nothing a backward would run on: the backward then returns MVLPT_ERR_STATE.  A forward
+ * refused for its arguments before that point leaves the record of the forward in front of it usable.
+ * Every input of a forward is read by the launches it enqueues.  These caller buffers are read AGAIN by later calls, so they stay
+ * valid and unchanged for longer:
+ *   - the masks of mvlpt_set_vpt_dropout: from the mvlpt_image_fwd (or _begin) that takes them over until its last mvlpt_image_bwd
+ *     has been enqueued;
+ *   - vpt_deep (and vpt, and the masks) of mvlpt_image_fwd_begin: until mvlpt_image_fwd_resume has been enqueued;
+ *   - ctx_deep of mvlpt_text_fwd_deep with save_for_bwd: until its last mvlpt_text_bwd_deep has been enqueued;
+ *   - task_lo / task_hi of mvlpt_logits_fwd: until the last mvlpt_logits_bwd of that forward has been enqueued.
+ * The class ranges of the ranged entries are host arrays, copied by the call. */
+
 /* ImageEncoder.forward (trainers/mvlpt.py:52-93).  image [B,3,R,R] of `image_dtype`; vpt [n_vpt,dv] fp32 or
  * NULL (shallow prompts, forward_vpt :416-437); vpt_deep [n_deep,n_vpt,dv] fp32 or NULL (deep prompts for
  * layers 1..n_deep, :73-83).  feat_out [B,embed] fp32.  save_for_bwd != 0 keeps activations for image_bwd. */

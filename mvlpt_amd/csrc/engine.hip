@@ -22,6 +22,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mvlpt_hip.h"
@@ -144,7 +145,8 @@ struct ResNetW {
 };
 
 struct TowerState {
-  bool valid = false, saved = false, causal = false;
+  bool causal = false;
+  bool keep = false;                     // the pass now running writes what a backward reads (lse, u, the skip copies); set by whoever runs the pass
   bool exact = false;                    // split-precision operands + pair-product attention (see DESIGN.md "Precision modes")
   int wide_pitch = 0;                    // split towers: row pitch of a16 / du16 (0: dense)
   int xs = 0;                            // GEMM A operands: 0 single 16-bit, 1 16-bit pair, 2 mixed pair (hi + e5m2 residual byte)
@@ -155,7 +157,6 @@ struct TowerState {
   std::vector<float*> lse;
   void *h16 = nullptr, *a16 = nullptr;
   float* act32 = nullptr;                // exact GELU only: fp32 [T, 4d] between an MLP GEMM and the stand-alone activation pass
-  bool bwd_done = false;                 // a backward has run on the saved state (mvlpt_set_activation)
   float* dx32 = nullptr; void *dx16 = nullptr, *du16 = nullptr, *dO16 = nullptr, *dqkv16 = nullptr; float* dh32 = nullptr;
   float* delta = nullptr; float* scale_dev = nullptr;
   std::vector<char> skip;                // layer skipped (reference deep-prompt quirk, Appendix A.3)
@@ -168,7 +169,6 @@ struct TowerState {
   // i, seg[k] = layers.  Segments 0 .. k-2 kept only their input; the per-layer tensors above are then slots shared by the segments
   // (indexed by the layer's position in its segment) and a backward recomputes each segment into them.  k = 1: nothing shared.
   std::vector<int> seg;
-  bool consumed = false;                 // k > 1: a backward has overwritten the slots
 };
 constexpr int FOLD_NTP = 8;              // slots per row the buffers are sized for (gemm.hip: FOLD_MAX_NTP)
 
@@ -176,7 +176,6 @@ constexpr int FOLD_NTP = 8;              // slots per row the buffers are sized 
 // gathered into compact [R, ·] buffers: out-projection, ln_2, the MLP and the closing LayerNorm run on these rows only
 // (last_block_fwd / last_block_bwd).  The 16-bit buffers hold hi|lo pairs in a split tower.
 struct Compact {
-  bool kept = false;                     // the forward kept what last_block_bwd reads
   float *x32 = nullptr, *xm32 = nullptr, *xo32 = nullptr;      // block input, ln_2 input, closing LayerNorm input
   float *out32 = nullptr, *dout32 = nullptr;                   // closing LayerNorm output (the projection's input) and its gradient
   void *a16 = nullptr, *h16 = nullptr, *g16 = nullptr, *u16 = nullptr;      // attention output, ln_2 output, GELU output, pre-GELU
@@ -195,6 +194,61 @@ enum class TextKind { Plain, Ranged, Ids };
 // The entry that ran the last head forward
 enum class HeadKind { Plain, Ranged };
 
+// ---- What the engine remembers of a forward: one record per job (image tower, text tower, head), one phase per record.
+// A forward OPENS its record (a fresh one, Phase::None) where it first touches the job's workspace and raises the phase in its last
+// statement, so a forward that fails anywhere in between leaves "nothing usable" without a line of its own.  A refusal in front of
+// the opening leaves the earlier record as it was.  Readers decide by the phase alone.
+//   None      nothing usable (never run, a forward failed or was abandoned)
+//   Pending   image only: between mvlpt_image_fwd_begin and mvlpt_image_fwd_resume
+//   Done      the forward finished, nothing was saved
+//   Saved     saved, no backward yet (the head: every forward; its backward may run any number of times)
+//   BwdDone   saved and a backward has run; another one is legal (nothing was checkpointed), and so is mvlpt_set_activation
+//   Consumed  text only: a backward under activation checkpointing has overwritten the saved slots
+//   entry                          record   from               to
+//   image_fwd_begin                image    any but Pending    Pending            (None on failure)
+//   image_fwd_resume               image    Pending            Done / Saved       (None on failure)
+//   image_fwd_abandon              image    Pending            None
+//   image_fwd (ResNet)             image    any                Done               (None on failure)
+//   image_bwd                      image    Saved / BwdDone    BwdDone
+//   text_fwd* / encode_tokens      text     any                Done / Saved       (None on failure)
+//   text_bwd / text_bwd_deep       text     Saved / BwdDone    BwdDone, or Consumed once a checkpointed backward touches the slots
+//   logits_fwd / logits_ranged_fwd head     any                Saved              (None on failure)
+//   logits_bwd / logits_ranged_bwd head     Saved              Saved              (the forward of its own kind only)
+enum class Phase { None, Pending, Done, Saved, BwdDone, Consumed };
+static bool bwd_ready(Phase p) { return p == Phase::Saved || p == Phase::BwdDone; }
+
+struct ImageRun {
+  Phase phase = Phase::None;
+  TowerState st; Compact c;              // carved from vis_ws; c: the CLS-only last block (compact [B,·] rows)
+  int B = 0, n_vpt = 0, n_deep = 0;
+  bool last_compact = false;             // the last block ran on the compact rows (false: skipped by the deep-prompt quirk)
+  bool packed = false, ln1_ready = false, save = false; int next = 0;      // what crosses the begin / resume cut
+  // Caller-owned.  mask: the dropout masks this forward took over from mvlpt_set_vpt_dropout (null: none), alive until the last
+  // mvlpt_image_bwd of this forward is enqueued.  vpt_deep: alive from mvlpt_image_fwd_begin until mvlpt_image_fwd_resume is enqueued.
+  const float *mask = nullptr, *vpt_deep = nullptr;
+};
+struct TextRun {
+  Phase phase = Phase::None;
+  TowerState st; Compact c;              // carved from txt_ws; c: the EOT-only last block (compact [C,·] rows)
+  TextKind kind = TextKind::Plain;
+  int C = 0, L = 0, n_ctx = 0, per_class = 0, n_deep = 0;
+  int groups = 0;                        // TextKind::Ranged: the groups, C = sum of the range widths
+  // device tables in txt_ws.  range: [lo (groups) | start (groups + 1) | ...] (build_range_table), ids: mvlpt_text_encode_tokens
+  int32_t *eot_rows = nullptr, *ctx_pos = nullptr, *range = nullptr, *ids = nullptr;
+  // Caller-owned: ctx_deep [n_deep, n_ctx, dt] (mvlpt_text_fwd_deep), read again by the recomputation of a checkpointed backward:
+  // alive until the last mvlpt_text_bwd_deep of this forward is enqueued
+  const float* ctx_deep = nullptr;
+};
+struct HeadRun {
+  Phase phase = Phase::None;
+  HeadKind kind = HeadKind::Plain;       // a backward runs only after the forward of its own name
+  int B = 0, C = 0, S = 0; float scale = 0.f;      // HeadKind::Ranged: B = G groups over C classes, S text rows
+  float *imn = nullptr, *txn = nullptr, *inorm = nullptr, *tnorm = nullptr;      // carved from head_ws, like the ranged head's tables
+  const int32_t *rlo = nullptr, *rstart = nullptr, *rgrp = nullptr;
+  // Caller-owned: the class window of mvlpt_logits_fwd (null: none), alive until the last mvlpt_logits_bwd of this forward is enqueued
+  const int32_t *lo = nullptr, *hi = nullptr;
+};
+
 struct Engine {
   MvlptArch arch{};
   int dt = DT_F16;
@@ -208,11 +262,9 @@ struct Engine {
   // same time the A operand behind every LayerNorm) + one byte instead of fp32 + a 16-bit copy.  MVLPT_RESID_PACKED / mvlpt_set_resid_packed
   int resid_packed = 1;      // MVLPT_RESID_PACKED=0: fp32 stream
   // mvlpt_set_vpt_dropout: [layers, B, n_vpt, d] masks of the visual prompt rows for the NEXT image_fwd (one-shot: the forward
-  // validates the geometry, takes the setting over as v_mask — what ITS backward uses — and clears it, so a stale pointer never
-  // reaches another forward or another user of the engine)
-  const float* vpt_mask = nullptr;
-  int vpt_mask_layers = 0, vpt_mask_B = 0, vpt_mask_n = 0, vpt_mask_d = 0;
-  const float* v_mask = nullptr;     // the masks of the forward whose activations are saved (null: none)
+  // validates the geometry, takes the setting over as ImageRun::mask — what ITS backward uses — and clears it, so a stale pointer
+  // never reaches another forward or another user of the engine)
+  struct VptMask { const float* p = nullptr; int layers = 0, B = 0, n = 0; } vpt_mask;
   bool lo8 = true;      // split towers of MVLPT_PREC_SPLIT_GRAD use the mixed pair (hi + e5m2 residual byte; MVLPT_SPLIT_LO8=0: 16-bit pairs)
   std::string err;
   TowerW vis, txt;
@@ -228,28 +280,9 @@ struct Engine {
   DevBuf vis_ws, txt_ws, head_ws, ce_ws, tmp, pp_ws, near_ws, jpeg_ws;
   std::vector<uint8_t> jpeg_meta_host;    // mvlpt_jpeg_decode: descriptors, table sets and segment table (source of the asynchronous upload)
   std::vector<int32_t> jpeg_status_host;  // ... and the initial status words
-  TowerState vs, ts;
-  // vision fwd extras (carved from vis_ws)
-  int vB = 0, v_nvpt = 0, v_ndeep = 0;
-  Compact vc;                            // CLS-only last image block (compact [B,·] rows)
-  // mvlpt_image_fwd_begin .. mvlpt_image_fwd_resume: what crosses the cut (the rest is in vs / the v_* fields above)
-  struct ImgPending { bool active = false, packed = false, ln1_ready = false, save = false; int next = 0; const float* vpt_deep = nullptr; } ip;
-  // text fwd extras
-  int tC = 0, tL = 0, t_nctx = 0, t_per_class = 0; int32_t* eot_rows = nullptr; int32_t* ctx_pos = nullptr;
-  TextKind t_kind = TextKind::Plain;   // the last text forward
-  // deep text prompts (mvlpt_text_fwd_deep): ctx_deep [t_ndeep, t_nctx, dt], the caller's buffer, read again by the backward's recomputation
-  int t_ndeep = 0; const float* t_ctx_deep = nullptr;
-  // TextKind::Ranged (mvlpt_text_fwd_ranged): t_groups groups, tC = sum of the range widths; device tables in txt_ws
-  int t_groups = 0; const int32_t *t_rlo = nullptr, *t_rstart = nullptr;
+  ImageRun vrun; TextRun trun; HeadRun hrun;      // the last forward of each job (see Phase)
   std::vector<int32_t> t_range_host, h_range_host;   // host images of the range tables (source of the asynchronous upload)
   std::vector<int32_t> t_ids_host;   // mvlpt_text_encode_tokens: [ids (S * L, trimmed rows) | eot rows (S)], checked on the host
-  Compact tc;                            // EOT-only last text block (compact [C,·] rows)
-  // head state
-  int hB = 0, hC = 0; float h_scale = 0.f; const int32_t *h_lo = nullptr, *h_hi = nullptr;
-  HeadKind h_kind = HeadKind::Plain;   // the last head forward; a backward runs only after the forward of its own name
-  // HeadKind::Ranged: hB = G groups over hC classes, hS text rows; device tables in head_ws
-  int hS = 0; const int32_t *h_rlo = nullptr, *h_rstart = nullptr, *h_rgrp = nullptr;
-  float *imn = nullptr, *txn = nullptr, *inorm = nullptr, *tnorm = nullptr;
   // profiling
   // mvlpt_debug_checksums: one 64-bit fingerprint per intermediate of the image tower (debug; off by default)
   unsigned long long* dbg_ck = nullptr; int dbg_ck_n = 0; bool dbg_ck_on = false;
@@ -386,7 +419,7 @@ void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool s
                  int segments = 1) {
   const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1; const int nl = W.layers;
   st = TowerState();
-  st.N = N; st.L = L; st.d = (int)d; st.H = (int)H; st.hw = (int)(d / H); st.layers = nl; st.saved = save; st.causal = causal; st.exact = exact;
+  st.N = N; st.L = L; st.d = (int)d; st.H = (int)H; st.hw = (int)(d / H); st.layers = nl; st.causal = causal; st.exact = exact;
   st.xs = exact ? xs : 0;
   st.seg = ckpt_plan(nl, save ? segments : 1);
   const int k = (int)st.seg.size() - 1;
@@ -438,22 +471,21 @@ void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool s
     st.scale_dev = bp.take<float>(4);   // {scale, 1/scale, amax scratch, pad}
   }
   if (gelu) st.act32 = bp.take<float>(T * 4 * d);
-  st.valid = true;
 }
 
 // which pair format a split tower uses: the default mode carries the residual as one e5m2 byte (GemmArgs::a_split == 2);
 // MVLPT_PREC_SPLIT_ALL (PREC = "fp32": as exact as this engine gets) keeps 16-bit pairs everywhere
 int split_kind(const Engine* E) { return (E->prec_mode == MVLPT_PREC_SPLIT_ALL || !E->lo8) ? 1 : 2; }
 
-// Attention core of layer l, all rows or (q_rows > 0) only queries 0..q_rows-1 of every sequence; lse is kept when the tower saves its
-// activations.  Split towers (st.xs): qkv pair [T,6d] -> O as a hi|lo pair [T,2d].  Single operands: `timed` (the full-width blocks)
+// Attention core of layer l, all rows or (q_rows > 0) only queries 0..q_rows-1 of every sequence; lse is kept when the pass keeps its
+// activations (st.keep).  Split towers (st.xs): qkv pair [T,6d] -> O as a hi|lo pair [T,2d].  Single operands: `timed` (the full-width blocks)
 // adds the dispatch-timestamp record of attn_fwd_timed.
 int attn_fwd(Engine* E, TowerState& st, int l, int q_rows, bool timed, hipStream_t s) {
   const double T = (double)st.N * st.L, rows = q_rows > 0 ? (double)q_rows : (double)st.L;
   const double fl = 4.0 * rows * st.L * (double)st.hw * st.N * st.H * (st.causal ? 0.5 : 1.0);
-  float* lse = st.saved ? st.lse[l] : nullptr;
+  float* lse = st.keep ? st.lse[l] : nullptr;
   if (st.hw != 64) {      // a wide-headed image tower: frozen, prompt-free, forward-only on single operands (kRefuseWide)
-    if (st.xs || st.causal || st.saved) return fail(E, MVLPT_ERR_STATE, "wide-headed attention: single operands, non-causal, nothing saved");
+    if (st.xs || st.causal || st.keep) return fail(E, MVLPT_ERR_STATE, "wide-headed attention: single operands, non-causal, nothing saved");
     AttnArgs a{st.qkv[l], st.attn[l], nullptr, st.N, st.L, st.H, 0, q_rows};
     ProfScope ps(E, s, PC_ATTN_FWD, fl, T * st.d * 2.0 * (q_rows > 0 ? 2.0 : 4.0));
     HIPCHK(E, launch_attn_fwd_wide(E->dt, a, st.hw, s));
@@ -568,7 +600,7 @@ int block_fwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s, 
   HIPCHK(E, gemm(E, p2 ? EPI_RESID32_LN : EPI_RESID32, st.attn[l], B.o.fw(), T, d, d, B.o.b, nullptr, xin, xmid, nullptr, s, -1, xs, p2 ? &fo : nullptr));
   if (p2) ff = fold_consumer(st, 1, B.fc);
   else HIPCHK(E, ln_fwd(E, E->dt, xmid, nullptr, 1, B.ln2, st.h16, T, d, s, xs));
-  if (int rc = mlp_up(E, st.h16, B.fc.fw(), p2 ? B.fc.fold_b : B.fc.b, T, d, xs, st.a16, wp, st.saved ? st.u[l] : nullptr, st.act32,
+  if (int rc = mlp_up(E, st.h16, B.fc.fw(), p2 ? B.fc.fold_b : B.fc.b, T, d, xs, st.a16, wp, st.keep ? st.u[l] : nullptr, st.act32,
                       p2 ? &ff : nullptr, s)) return rc;
   const bool p1 = next_ln1 && fold_producer(E, st, 0, T, d, 4 * d, *next_ln1, s, &fp);
   HIPCHK(E, gemm(E, p1 ? EPI_RESID32_LN : EPI_RESID32, st.a16, B.pr.fw(), T, d, 4 * d, B.pr.b, nullptr, xmid, xout, nullptr, s, -1, xs, p1 ? &fp : nullptr,
@@ -639,7 +671,7 @@ hipError_t move_rows(const void* src, void* dst, const int32_t* rows, int R, int
   if (rows) return launch_copy_rows(src, dst, rows, R, (int)row_bytes, scatter, s);
   return launch_copy_rows_strided(src, dst, R, scatter ? row_bytes : L * row_bytes, scatter ? L * row_bytes : row_bytes, (int)row_bytes, s);
 }
-// Image: only x[:, 0, :] of the last block is consumed (trainers/mvlpt.py:88), rows == null, and only the CLS query runs (q_rows = 1).
+// Image: only x[:, 0, :] of the last block is read (trainers/mvlpt.py:88), rows == null, and only the CLS query runs (q_rows = 1).
 // Text: only x[c, eot_c] (trainers/mvlpt.py:126-128), rows = eot_rows, every query runs.  packed: the image tower's packed stream.
 // ln_close: ln_post / ln_final, into c.out32.  ck: mvlpt_debug_checksums fingerprints (image tower only).
 int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const int32_t* rows, int q_rows, bool packed, bool ln1_ready,
@@ -649,7 +681,6 @@ int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const
   const size_t X = xs ? 2 : 1;
   const Block& Bk = W.blocks[l];
   float* xin = st.x[2 * l];
-  c.kept = st.saved;
   Fold fq;
   if (ln1_ready) fq = fold_consumer(st, 0, Bk.qkv);
   else HIPCHK(E, ln_fwd(E, E->dt, xin, nullptr, 1, Bk.ln1, st.h16, T, d, s, xs));
@@ -659,7 +690,7 @@ int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const
   if (ck) dbg_ck(E, st.qkv[l], (size_t)T * 3 * d * 2 * X, s);
   // split operands, some queries only: the other rows of the attention output are not produced, and the backward
   // (delta = rowsum(dO * O) over EVERY row, with dO = 0 off the compact rows) must not meet uninitialised memory there
-  if (xs && q_rows > 0 && st.saved) HIPCHK(E, launch_zero(st.attn[l], (size_t)T * d * 2 * X, s));
+  if (xs && q_rows > 0 && st.keep) HIPCHK(E, launch_zero(st.attn[l], (size_t)T * d * 2 * X, s));
   if (int rc = attn_fwd(E, st, l, q_rows, false, s)) return rc;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)R * d * 12.0);
     HIPCHK(E, move_rows(st.attn[l], c.a16, rows, R, st.L, (size_t)d * 2 * X, 0, s));
@@ -668,7 +699,7 @@ int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const
   if (ck) { dbg_ck(E, c.a16, (size_t)R * d * 2 * X, s); dbg_ck(E, c.x32, (size_t)R * d * 4, s); }
   HIPCHK(E, gemm(E, EPI_RESID32, c.a16, Bk.o.fw(), R, d, d, Bk.o.b, nullptr, c.x32, c.xm32, nullptr, s, -1, xs));
   HIPCHK(E, ln_fwd(E, E->dt, c.xm32, nullptr, 1, Bk.ln2, c.h16, R, d, s, xs));
-  if (int rc = mlp_up(E, c.h16, Bk.fc.fw(), Bk.fc.b, R, d, xs, c.g16, 0, st.saved ? c.u16 : nullptr, c.act32, nullptr, s)) return rc;
+  if (int rc = mlp_up(E, c.h16, Bk.fc.fw(), Bk.fc.b, R, d, xs, c.g16, 0, st.keep ? c.u16 : nullptr, c.act32, nullptr, s)) return rc;
   HIPCHK(E, gemm(E, EPI_RESID32, c.g16, Bk.pr.fw(), R, d, 4 * d, Bk.pr.b, nullptr, c.xm32, c.xo32, nullptr, s, -1, xs));
   HIPCHK(E, ln_fwd(E, DT_F32, c.xo32, nullptr, 1, ln_close, c.out32, R, d, s));
   return 0;
@@ -1032,7 +1063,7 @@ int resnet_fwd(Engine* E, const void* image, int image_dtype, int B, float* feat
   if ((size_t)B * res * res / 4 * w > (size_t)1 << 40 || B > 65535) return fail(E, MVLPT_ERR_ARG, "image_fwd: batch too large");
   // the largest map: the stem's last conv and the first stage's output, B * (res/2)^2 * w elements; five maps live at once
   const size_t mapn = (size_t)B * (res / 2) * (res / 2) * w;
-  E->vs.valid = false;
+  E->vrun = ImageRun();      // opened: the workspace below no longer holds the last transformer forward
   void *img8, *buf[5], *tok, *kv, *q16, *o16;
   if (int rc = carve_ws(E, E->vis_ws, "image_fwd (ResNet)", kCarveSlack, [&](Bump& bp) {
         img8 = bp.take_bytes((size_t)B * res * res * 8 * 2);
@@ -1080,6 +1111,7 @@ int resnet_fwd(Engine* E, const void* image, int image_dtype, int B, float* feat
   { ProfScope ps(E, s, PC_ATTN_FWD, 4.0 * T * 64.0 * B * (Ech / 64), (double)B * T * 2 * Ech * 2.0);
     HIPCHK(E, launch_attnpool_query(q16, kv, o16, B, T, Ech, s)); }
   HIPCHK(E, gemm(E, EPI_STORE32, o16, WRef{R.cw, Ech, 0}, B, e, Ech, R.cb, nullptr, nullptr, feat_out, nullptr, s, DT_F16));
+  E->vrun.phase = Phase::Done;
   return 0;
 }
 
@@ -1203,8 +1235,7 @@ int mvlpt_set_activation(void* h, int act) {
   if (act != MVLPT_ACT_QUICKGELU && act != MVLPT_ACT_GELU)
     return fail(E, MVLPT_ERR_ARG, "set_activation: the activation is MVLPT_ACT_QUICKGELU or MVLPT_ACT_GELU");
   // a saved state was carved for, and its pre-activations belong to, the activation of its forward: the backward must see the same
-  auto pending = [](const TowerState& st) { return st.valid && st.saved && !st.bwd_done; };
-  if (E->ip.active || pending(E->vs) || pending(E->ts))
+  if (E->vrun.phase == Phase::Pending || E->vrun.phase == Phase::Saved || E->trun.phase == Phase::Saved)
     return fail(E, MVLPT_ERR_STATE, "set_activation: a forward has saved activations whose backward has not run (or an image forward is "
                                     "pending); change the activation before a forward or after a completed step");
   E->act = act;
@@ -1286,9 +1317,7 @@ int mvlpt_set_vpt_dropout(void* h, const float* masks, int n_layers, int batch, 
   if (vision_wide(E)) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseWide) + "set_vpt_dropout");
   if (masks && (n_layers <= 0 || batch <= 0 || n_vpt <= 0 || width != E->arch.vision_width))
     return fail(E, MVLPT_ERR_ARG, "set_vpt_dropout: masks are [n_layers, batch, n_vpt, vision_width], every extent positive");
-  E->vpt_mask = masks;
-  E->vpt_mask_layers = masks ? n_layers : 0;
-  E->vpt_mask_B = masks ? batch : 0; E->vpt_mask_n = masks ? n_vpt : 0; E->vpt_mask_d = masks ? width : 0;
+  E->vpt_mask = masks ? Engine::VptMask{masks, n_layers, batch, n_vpt} : Engine::VptMask{};
   return 0;
 }
 
@@ -1382,12 +1411,12 @@ int mvlpt_frozen_ready(void* h) {
 
 // ------------------------------------------------------------------------------------------------ image tower
 // Blocks [from, to) of the image tower at full width, each behind its deep-prompt overwrite (or skipped, see below).  Returns 1 when
-// it reaches the last block, which is CLS-only and run by mvlpt_image_fwd_resume.  `ln1_ready` is carried from block to block, and
+// it reaches the last block, which is CLS-only and run by mvlpt_image_fwd_resume.  R.ln1_ready is carried from block to block, and
 // across the begin / resume cut.
-static int image_blocks(Engine* E, int from, int to, bool packed, bool* ln1_ready, const float* vpt_deep, hipStream_t s) {
-  TowerState& st = E->vs;
-  const int B = E->vB, n_vpt = E->v_nvpt, n_deep = E->v_ndeep, dv = E->arch.vision_width, Lv = st.L;
-  const float* const masks = E->v_mask;
+static int image_blocks(Engine* E, int from, int to, hipStream_t s) {
+  ImageRun& R = E->vrun; TowerState& st = R.st;
+  const int B = R.B, n_vpt = R.n_vpt, n_deep = R.n_deep, dv = E->arch.vision_width, Lv = st.L;
+  const float* const masks = R.mask;
   auto vmask = [&](int l) -> const float* { return masks ? masks + (size_t)l * B * n_vpt * dv : nullptr; };
   // ln_1 of block l can be folded when nothing touches the residual stream between FC2 of block l-1 and it: not behind a
   // deep-prompt overwrite, not behind a skipped block
@@ -1401,21 +1430,21 @@ static int image_blocks(Engine* E, int from, int to, bool packed, bool* ln1_read
     if (l > 0 && n_deep > 0) {
       if (l <= n_deep) {
         ProfScope ps(E, s, PC_GLUE, 0, (double)B * n_vpt * dv * 4.0);
-        HIPCHK(E, launch_overwrite_rows(vpt_deep + (size_t)(l - 1) * n_vpt * dv, n_vpt, st.x[2 * l], B, Lv, dv, s, vmask(l)));
+        HIPCHK(E, launch_overwrite_rows(R.vpt_deep + (size_t)(l - 1) * n_vpt * dv, n_vpt, st.x[2 * l], B, Lv, dv, s, vmask(l)));
       } else {
         // reference quirk (trainers/mvlpt.py:71-83 has no `else`): the layer is skipped entirely
         st.skip[l] = 1;
-        if (st.saved) {
+        if (st.keep) {
           HIPCHK(E, hipMemcpyAsync(st.x[2 * l + 2], st.x[2 * l], (size_t)B * Lv * dv * 4, hipMemcpyDeviceToDevice, s));
         }
         continue;
       }
     }
     if (l == E->vis.layers - 1) return 1;      // the caller runs it on the CLS rows only
-    if (packed) { if (int rc = block_fwd_packed(E, E->vis, st, l, s)) return rc; continue; }
+    if (R.packed) { if (int rc = block_fwd_packed(E, E->vis, st, l, s)) return rc; continue; }
     bool produced = false;
-    if (int rc = block_fwd(E, E->vis, st, l, s, *ln1_ready, next_foldable(l), &produced)) return rc;
-    *ln1_ready = produced;
+    if (int rc = block_fwd(E, E->vis, st, l, s, R.ln1_ready, next_foldable(l), &produced)) return rc;
+    R.ln1_ready = produced;
   }
   return 0;
 }
@@ -1432,7 +1461,8 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
     if (E->prec_mode == MVLPT_PREC_SPLIT_ALL)
       return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseWide) + "MVLPT_PREC_SPLIT_ALL (its forward-only towers run on pairs)");
   }
-  if (E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_fwd_begin: a forward is pending (call image_fwd_resume or image_fwd_abandon first)");
+  ImageRun& R = E->vrun;
+  if (R.phase == Phase::Pending) return fail(E, MVLPT_ERR_STATE, "image_fwd_begin: a forward is pending (call image_fwd_resume or image_fwd_abandon first)");
   if (int rc = mvlpt_frozen_ready(h)) return rc;
   if ((n_vpt > 0) != (vpt != nullptr)) return fail(E, MVLPT_ERR_ARG, "image_fwd: vpt pointer and n_vpt disagree");
   if ((n_deep > 0) != (vpt_deep != nullptr) || (n_deep > 0 && n_vpt <= 0)) return fail(E, MVLPT_ERR_ARG, "image_fwd: deep prompts need vpt");
@@ -1446,28 +1476,24 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
   const size_t X = exact ? 2 : 1;
   const size_t npatch = (size_t)B * G2;
   const bool gelu = E->act == ACT_GELU;
-  TowerState& st = E->vs;
+  R = ImageRun();      // opened: from here on the workspace no longer holds the last forward
+  TowerState& st = R.st;
   void* patches; float* pe;
-  const int carved = carve_ws(E, E->vis_ws, "image_fwd_begin", kCarveSlack, [&](Bump& bp) {
-    patches = bp.take_bytes(npatch * E->Kp * 2);
-    pe = bp.take<float>(npatch * dv);
-    carve_compact(bp, E->vc, B, dv, X, gelu);
-    carve_tower(bp, E->vis, st, B, Lv, save, false, exact, split_kind(E), gelu);
-  });
-  if (carved) { st.valid = false; return carved; }
-  E->vB = B; E->v_nvpt = n_vpt; E->v_ndeep = n_deep;
+  if (int rc = carve_ws(E, E->vis_ws, "image_fwd_begin", kCarveSlack, [&](Bump& bp) {
+        patches = bp.take_bytes(npatch * E->Kp * 2);
+        pe = bp.take<float>(npatch * dv);
+        carve_compact(bp, R.c, B, dv, X, gelu);
+        carve_tower(bp, E->vis, st, B, Lv, save, false, exact, split_kind(E), gelu);
+      })) return rc;
+  R.B = B; R.n_vpt = n_vpt; R.n_deep = n_deep; R.save = st.keep = save; R.vpt_deep = vpt_deep;
   st.fold = E->fold_mode >= 1 && (size_t)B * Lv >= (size_t)E->fold_min_rows && dv >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
 
-  // vpt_dropout masks of layer l's prompt rows (mvlpt_set_vpt_dropout), or null
-  // the setting belongs to THIS forward (and its backward) only
-  const float* const masks = E->vpt_mask;
-  const int mask_layers = E->vpt_mask_layers, mask_B = E->vpt_mask_B, mask_n = E->vpt_mask_n;
-  E->vpt_mask = nullptr; E->vpt_mask_layers = 0; E->v_mask = nullptr;
-  if (masks && (n_vpt <= 0 || mask_layers < 1 + n_deep || mask_B != B || mask_n != n_vpt))
+  // the prompt dropout masks (mvlpt_set_vpt_dropout) belong to THIS forward and its backward only: taken over and cleared, then checked
+  const Engine::VptMask m = std::exchange(E->vpt_mask, {});
+  if (m.p && (n_vpt <= 0 || m.layers < 1 + n_deep || m.B != B || m.n != n_vpt))
     return fail(E, MVLPT_ERR_ARG, "image_fwd: the prompt dropout masks do not match this forward (layers >= 1 + n_deep, batch, n_vpt)");
-  E->v_mask = masks;
-  const float* const vmask0 = masks;      // layer 0: the shallow prompts
+  R.mask = m.p;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)npatch * E->Kp * 6.0);
     HIPCHK(E, launch_patchify(E->dt, image, image_dtype, patches, B, A.image_resolution, A.patch_size, E->Kp, s)); }
   if (E->dbg_ck_on) { E->dbg_ck_n = 0; if (E->dbg_ck) (void)hipMemsetAsync(E->dbg_ck, 0, DBG_CK_MAX * sizeof(unsigned long long), s); }
@@ -1488,20 +1514,21 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
     dbg_ck(E, xhi, (size_t)B * Lv * dv * 3, s); dbg_ck(E, st.part[0], (size_t)B * Lv * ntp_d * 8, s);
   } else {
     ProfScope ps(E, s, PC_GLUE, 0, (double)B * Lv * dv * 8.0);
-    HIPCHK(E, launch_assemble_tokens(pe, E->cls_emb, E->vpos, E->ln_pre.g, E->ln_pre.b, vpt, n_vpt, st.x[0], B, G2, dv, s, vmask0));
+    HIPCHK(E, launch_assemble_tokens(pe, E->cls_emb, E->vpos, E->ln_pre.g, E->ln_pre.b, vpt, n_vpt, st.x[0], B, G2, dv, s, R.mask));      // (layer 0's masks: the shallow prompts)
   }
   // blocks [0, stop_block); the last block (CLS rows only) always belongs to resume
   const int stop = std::min(std::max(stop_block, 0), E->vis.layers - 1);
-  bool ln1_ready = packed;      // LayerNorm folding: the previous block's FC2 left this block's ln_1 input in folded form
-  if (int rc = image_blocks(E, 0, stop, packed, &ln1_ready, vpt_deep, s)) return rc;
-  E->ip.active = true; E->ip.packed = packed; E->ip.ln1_ready = ln1_ready; E->ip.save = save; E->ip.next = stop; E->ip.vpt_deep = vpt_deep;
+  R.next = stop;
+  R.packed = R.ln1_ready = packed;      // LayerNorm folding: the previous block's FC2 left this block's ln_1 input in folded form
+  if (int rc = image_blocks(E, 0, stop, s)) return rc;
+  R.phase = Phase::Pending;
   return 0;
 }
 
 int mvlpt_image_fwd_abandon(void* h) {
   Engine* E = (Engine*)h;
   if (!E) return MVLPT_ERR_ARG;
-  if (E->ip.active) { E->ip.active = false; E->vs.valid = false; }
+  if (E->vrun.phase == Phase::Pending) E->vrun.phase = Phase::None;
   return 0;
 }
 
@@ -1509,23 +1536,24 @@ int mvlpt_image_fwd_resume(void* h, float* feat_out, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !feat_out) return fail(E, MVLPT_ERR_ARG, "image_fwd_resume: null argument");
   if (E->rn.on) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "image_fwd_resume");
-  if (!E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_fwd_resume: call image_fwd_begin first");
-  E->ip.active = false;
+  ImageRun& R = E->vrun;
+  if (R.phase != Phase::Pending) return fail(E, MVLPT_ERR_STATE, "image_fwd_resume: call image_fwd_begin first");
+  R.phase = Phase::None;      // opened again: pending no longer, and nothing usable until the last statement
   hipStream_t s = (hipStream_t)stream;
-  TowerState& st = E->vs;
+  TowerState& st = R.st;
   const MvlptArch& A = E->arch;
-  const int B = E->vB, dv = A.vision_width, e = A.embed_dim, Lv = st.L;
-  const bool packed = E->ip.packed;
-  bool ln1_ready = E->ip.ln1_ready;
-  const int rest = image_blocks(E, E->ip.next, E->vis.layers, packed, &ln1_ready, E->ip.vpt_deep, s);
-  if (rest < 0) { st.valid = false; return rest; }
+  const int B = R.B, dv = A.vision_width, e = A.embed_dim, Lv = st.L;
+  const int rest = image_blocks(E, R.next, E->vis.layers, s);
+  if (rest < 0) return rest;
+  R.last_compact = rest == 1;
   if (rest == 1) {      // the last block, CLS rows only (mvlpt_image_bwd: only the CLS query carries a gradient into its attention)
-    if (int rc = last_block_fwd(E, E->vis, st, E->vc, nullptr, 1, packed, ln1_ready, E->ln_post, true, s)) return rc;
+    if (int rc = last_block_fwd(E, E->vis, st, R.c, nullptr, 1, R.packed, R.ln1_ready, E->ln_post, true, s)) return rc;
   } else
   // ln_post on the CLS row, then @ proj   (trainers/mvlpt.py:88-91)
-  HIPCHK(E, ln_fwd(E, DT_F32, st.x[2 * E->vis.layers], nullptr, Lv, E->ln_post, E->vc.out32, B, dv, s));
+  HIPCHK(E, ln_fwd(E, DT_F32, st.x[2 * E->vis.layers], nullptr, Lv, E->ln_post, R.c.out32, B, dv, s));
   { ProfScope ps(E, s, PC_HEAD, 2.0 * B * e * dv, 4.0 * ((double)B * dv + (double)e * dv + (double)B * e));
-    HIPCHK(E, launch_sgemm_bt(E->vc.out32, E->vproj_t, feat_out, B, e, dv, nullptr, s)); }
+    HIPCHK(E, launch_sgemm_bt(R.c.out32, E->vproj_t, feat_out, B, e, dv, nullptr, s)); }
+  R.phase = R.save ? Phase::Saved : Phase::Done;
   return 0;
 }
 
@@ -1548,35 +1576,35 @@ int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, 
   if (!E || !dfeat) return fail(E, MVLPT_ERR_ARG, "image_bwd: null argument");
   if (E->rn.on) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseRN) + "image_bwd");
   if (vision_wide(E)) return fail(E, MVLPT_ERR_UNSUPPORTED, std::string(kRefuseWide) + "image_bwd");
-  TowerState& st = E->vs;
-  if (E->ip.active) return fail(E, MVLPT_ERR_STATE, "image_bwd: a forward is pending between image_fwd_begin and image_fwd_resume");
-  if (!st.valid || !st.saved) return fail(E, MVLPT_ERR_STATE, "image_bwd: call image_fwd(save_for_bwd=1) first");
-  if ((E->v_nvpt > 0 && !dvpt) || (E->v_ndeep > 0 && !dvpt_deep)) return fail(E, MVLPT_ERR_ARG, "image_bwd: missing gradient output");
+  ImageRun& R = E->vrun; TowerState& st = R.st;
+  if (R.phase == Phase::Pending) return fail(E, MVLPT_ERR_STATE, "image_bwd: a forward is pending between image_fwd_begin and image_fwd_resume");
+  if (!bwd_ready(R.phase)) return fail(E, MVLPT_ERR_STATE, "image_bwd: call image_fwd(save_for_bwd=1) first");
+  if ((R.n_vpt > 0 && !dvpt) || (R.n_deep > 0 && !dvpt_deep)) return fail(E, MVLPT_ERR_ARG, "image_bwd: missing gradient output");
   hipStream_t s = (hipStream_t)stream;
   const MvlptArch& A = E->arch;
-  const int B = E->vB, dv = A.vision_width, e = A.embed_dim, Lv = st.L, n = E->v_nvpt;
+  const int B = R.B, dv = A.vision_width, e = A.embed_dim, Lv = st.L, n = R.n_vpt;
   const size_t T = (size_t)B * Lv;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dv * 10.0);
     HIPCHK(E, launch_grad_scale(dfeat, (size_t)B * e, 64.0f, st.scale_dev, s));
-    HIPCHK(E, launch_sgemm_bt(dfeat, E->vproj, E->vc.dout32, B, dv, e, st.scale_dev, s)); }
+    HIPCHK(E, launch_sgemm_bt(dfeat, E->vproj, R.c.dout32, B, dv, e, st.scale_dev, s)); }
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dv * 4.0);
     HIPCHK(E, launch_zero(st.dx32, T * dv * 4, s)); }
   int l_top = st.layers - 1;
   const int xs = st.xs;
   // gradient of the deep prompts of block l (its input rows 1..n), which then stop carrying one
   auto reduce_deep = [&](int l) -> int {
-    if (!(l > 0 && E->v_ndeep > 0 && l <= E->v_ndeep)) return 0;
+    if (!(l > 0 && R.n_deep > 0 && l <= R.n_deep)) return 0;
     ProfScope ps(E, s, PC_GLUE, 0, (double)B * n * dv * 10.0);
     HIPCHK(E, launch_reduce_prompt_rows(E->dt, st.dx32, st.dx16, B, Lv, dv, 1, n, dvpt_deep + (size_t)(l - 1) * n * dv,
-                                        st.scale_dev, 1, s, xs, E->v_mask ? E->v_mask + (size_t)l * B * n * dv : nullptr));
+                                        st.scale_dev, 1, s, xs, R.mask ? R.mask + (size_t)l * B * n * dv : nullptr));
     return 0;
   };
-  if (E->vc.kept) {      // last block, CLS rows only (see mvlpt_image_fwd_resume)
-    if (int rc = last_block_bwd(E, E->vis, st, E->vc, nullptr, 1, E->ln_post, s)) return rc;
+  if (R.last_compact) {      // last block, CLS rows only (see mvlpt_image_fwd_resume)
+    if (int rc = last_block_bwd(E, E->vis, st, R.c, nullptr, 1, E->ln_post, s)) return rc;
     if (int rc = reduce_deep(l_top)) return rc;
     --l_top;
   } else {
-    HIPCHK(E, ln_bwd(E, E->vc.dout32, DT_F32, st.x[2 * st.layers], nullptr, Lv, E->ln_post, nullptr, st.dx32, nullptr, B, dv, s));
+    HIPCHK(E, ln_bwd(E, R.c.dout32, DT_F32, st.x[2 * st.layers], nullptr, Lv, E->ln_post, nullptr, st.dx32, nullptr, B, dv, s));
     { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dv * 6.0);
       if (xs) HIPCHK(E, launch_cast_f32_split(E->dt, st.dx32, st.dx16, T, dv, nullptr, s, xs == 2));
       else HIPCHK(E, launch_cast_f32_to16(E->dt, st.dx32, st.dx16, T * dv, nullptr, s)); }
@@ -1588,9 +1616,9 @@ int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, 
   }
   if (n > 0) {
     ProfScope ps(E, s, PC_GLUE, 0, (double)B * n * dv * 4.0);
-    HIPCHK(E, launch_reduce_prompt_rows(E->dt, st.dx32, st.dx16, B, Lv, dv, 1, n, dvpt, st.scale_dev, 0, s, 0, E->v_mask));
+    HIPCHK(E, launch_reduce_prompt_rows(E->dt, st.dx32, st.dx16, B, Lv, dv, 1, n, dvpt, st.scale_dev, 0, s, 0, R.mask));
   }
-  st.bwd_done = true;
+  R.phase = Phase::BwdDone;
   return 0;
 }
 
@@ -1620,16 +1648,15 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 // counts with it.  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of the ctx_pos table; range_ints / ids_ints: the range
 // table of a ranged forward and the id table of mvlpt_text_encode_tokens (0: none, a null pointer).  A saving tower is carved under the
 // engine's activation-checkpointing setting (mvlpt_set_text_act_ckpt).
-struct TextTables { int32_t *eot_rows = nullptr, *ctx_pos = nullptr, *range = nullptr, *ids = nullptr; };
-static void text_layout(Bump& bp, const Engine* E, TowerState& st, Compact& c, TextTables& t, int C, int L, bool save, bool exact,
-                        size_t ctx_rows, size_t range_ints, size_t ids_ints) {
+static void text_layout(Bump& bp, const Engine* E, TextRun& R, int C, int L, bool save, bool exact, size_t ctx_rows, size_t range_ints,
+                        size_t ids_ints) {
   const bool gelu = E->act == ACT_GELU;
-  carve_compact(bp, c, C, E->arch.text_width, exact ? 2 : 1, gelu);
-  t.eot_rows = bp.take<int32_t>(C);
-  t.ctx_pos = bp.take<int32_t>(ctx_rows);
-  t.range = range_ints ? bp.take<int32_t>(range_ints) : nullptr;
-  t.ids = ids_ints ? bp.take<int32_t>(ids_ints) : nullptr;
-  carve_tower(bp, E->txt, st, C, L, save, true, exact, split_kind(E), gelu, E->text_act_ckpt);
+  carve_compact(bp, R.c, C, E->arch.text_width, exact ? 2 : 1, gelu);
+  R.eot_rows = bp.take<int32_t>(C);
+  R.ctx_pos = bp.take<int32_t>(ctx_rows);
+  R.range = range_ints ? bp.take<int32_t>(range_ints) : nullptr;
+  R.ids = ids_ints ? bp.take<int32_t>(ids_ints) : nullptr;
+  carve_tower(bp, E->txt, R.st, C, L, save, true, exact, split_kind(E), gelu, E->text_act_ckpt);
 }
 // The published figure is the count plus 8192 bytes: the Python chunk planners compare it with budgets, so it stays where it is, to the byte.
 constexpr size_t kTextSlack = 2 * kCarveSlack;
@@ -1646,22 +1673,25 @@ static bool text_exact(const Engine* E) { return E->prec_mode == MVLPT_PREC_SPLI
 // from the stand-alone ln_1.  Only the last segment hands a folded ln_1 on to the block behind it (the compact last block); a
 // checkpointed one closes with the plain residual epilogue, so that the segment behind it starts the same way in the first pass and
 // in the backward's recomputation.  *ln1_ready: what the block behind `end - 1` finds.
-// Deep text prompts: the context rows of block l's input (1 <= l <= t_ndeep) are replaced by ctx_deep[l - 1] in front of the block, in
+// Deep text prompts: the context rows of block l's input (1 <= l <= n_deep) are replaced by ctx_deep[l - 1] in front of the block, in
 // the first pass and in the recomputation alike (writing a segment's boundary buffer twice writes the same values).
-static int text_deep_overwrite(Engine* E, TowerState& st, int l, hipStream_t s) {
-  if (l < 1 || l > E->t_ndeep) return 0;
-  const int dtw = st.d, n = E->t_nctx;
+static int text_deep_overwrite(Engine* E, int l, hipStream_t s) {
+  const TextRun& R = E->trun; const TowerState& st = R.st;
+  if (l < 1 || l > R.n_deep) return 0;
+  const int dtw = st.d, n = R.n_ctx;
   ProfScope ps(E, s, PC_GLUE, 0, (double)st.N * n * dtw * 4.0);
-  HIPCHK(E, launch_overwrite_ctx_rows(E->t_ctx_deep + (size_t)(l - 1) * n * dtw, E->ctx_pos, st.x[2 * l], st.N, st.L, dtw, n, s));
+  HIPCHK(E, launch_overwrite_ctx_rows(R.ctx_deep + (size_t)(l - 1) * n * dtw, R.ctx_pos, st.x[2 * l], st.N, st.L, dtw, n, s));
   return 0;
 }
-static int text_segment_fwd(Engine* E, TowerState& st, int first, int end, bool last, bool* ln1_ready, hipStream_t s) {
-  *ln1_ready = false;
+// keep: this pass writes what a backward reads (false: the first pass of a checkpointed segment)
+static int text_segment_fwd(Engine* E, int first, int end, bool last, bool keep, bool* ln1_ready, hipStream_t s) {
+  TowerState& st = E->trun.st;
+  st.keep = keep; *ln1_ready = false;
   for (int l = first; l < end; ++l) {
-    if (int rc = text_deep_overwrite(E, st, l, s)) return rc;
+    if (int rc = text_deep_overwrite(E, l, s)) return rc;
     bool produced = false;
     // (ln_1 of a block behind an overwrite is not folded: its input rows change after the FC2 in front of it wrote them)
-    const bool next = st.fold && (last || l + 1 < end) && l + 1 > E->t_ndeep;
+    const bool next = st.fold && (last || l + 1 < end) && l + 1 > E->trun.n_deep;
     if (int rc = block_fwd(E, E->txt, st, l, s, *ln1_ready, next ? &E->txt.blocks[l + 1].ln1 : nullptr, &produced)) return rc;
     *ln1_ready = produced;
   }
@@ -1695,52 +1725,47 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
   const size_t ctx_rows = (size_t)(ranged && Cg > C ? Cg : C) * (n_ctx > 0 ? n_ctx : 1);
   const size_t range_ints = ranged ? E->t_range_host.size() : 0;
   const size_t ids_ints = ids ? E->t_ids_host.size() : 0;
-  TowerState& st = E->ts;
-  TextTables tab;
-  const int carved = carve_ws(E, E->txt_ws, "text_fwd", kTextSlack, [&](Bump& bp) {
-    text_layout(bp, E, st, E->tc, tab, C, L, save, exact, ctx_rows, range_ints, ids_ints);
-  });
-  if (carved) { st.valid = false; return carved; }
-  E->eot_rows = tab.eot_rows; E->ctx_pos = tab.ctx_pos;
-  int32_t *const range_dev = tab.range, *const ids_dev = tab.ids;
-  E->tC = C; E->tL = L; E->t_nctx = n_ctx; E->t_per_class = ctx_per_class;
-  E->t_kind = kind; E->t_groups = G; E->t_rlo = range_dev; E->t_rstart = ranged ? range_dev + G : nullptr;
-  E->t_ndeep = n_deep; E->t_ctx_deep = n_deep > 0 ? ctx_deep : nullptr;
+  TextRun& R = E->trun = TextRun();      // opened: from here on the workspace no longer holds the last forward
+  TowerState& st = R.st;
+  if (int rc = carve_ws(E, E->txt_ws, "text_fwd", kTextSlack, [&](Bump& bp) {
+        text_layout(bp, E, R, C, L, save, exact, ctx_rows, range_ints, ids_ints);
+      })) return rc;
+  R.C = C; R.L = L; R.n_ctx = n_ctx; R.per_class = ctx_per_class; R.kind = kind; R.groups = G;
+  R.n_deep = n_deep; R.ctx_deep = n_deep > 0 ? ctx_deep : nullptr;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
   if (ids) {
     ProfScope ps(E, s, PC_GLUE, 0, (double)C * L * dtw * 12.0);
-    HIPCHK(E, hipMemcpyAsync(ids_dev, E->t_ids_host.data(), ids_ints * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(E, hipMemcpyAsync(E->eot_rows, ids_dev + (size_t)C * L, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(E, launch_embed_tokens(E->tok_emb, E->tpos, ids_dev, L, st.x[0], C, L, dtw, s));
+    HIPCHK(E, hipMemcpyAsync(R.ids, E->t_ids_host.data(), ids_ints * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(E, hipMemcpyAsync(R.eot_rows, R.ids + (size_t)C * L, (size_t)C * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(E, launch_embed_tokens(E->tok_emb, E->tpos, R.ids, L, st.x[0], C, L, dtw, s));
   } else
   { ProfScope ps(E, s, PC_GLUE, 0, (double)C * L * dtw * 12.0);
     if (ranged) {
-      const int32_t *seq_cls = range_dev + 2 * G + 1, *seq_grp = seq_cls + C;
-      HIPCHK(E, hipMemcpyAsync(range_dev, E->t_range_host.data(), range_ints * 4, hipMemcpyHostToDevice, s));
+      const int32_t *seq_cls = R.range + 2 * G + 1, *seq_grp = seq_cls + C;
+      HIPCHK(E, hipMemcpyAsync(R.range, E->t_range_host.data(), range_ints * 4, hipMemcpyHostToDevice, s));
       HIPCHK(E, launch_assemble_prompts_ranged(prefix, suffix, ctx, n_ctx, layout, E->tpos, st.x[0], seq_cls, seq_grp, C, L, dtw, s));
-      HIPCHK(E, launch_eot_rows_ranged(eot, E->eot_rows, seq_cls, C, L, s));
-      if (save) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
+      HIPCHK(E, launch_eot_rows_ranged(eot, R.eot_rows, seq_cls, C, L, s));
+      if (save) HIPCHK(E, launch_build_ctx_pos(layout, R.ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
     } else {
       HIPCHK(E, launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, E->tpos, st.x[0], C, L, dtw, s));
-      HIPCHK(E, launch_eot_rows(eot, E->eot_rows, C, L, s));
-      if ((save || n_deep > 0) && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(layout, E->ctx_pos, C, L, n_ctx, s));
+      HIPCHK(E, launch_eot_rows(eot, R.eot_rows, C, L, s));
+      if ((save || n_deep > 0) && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(layout, R.ctx_pos, C, L, n_ctx, s));
     } }
   // Checkpointed segments (every one but the last, st.seg) run as a tower that saves nothing; their closing block writes the next
   // segment's boundary buffer.  No ln_1 is folded across a segment boundary, so mvlpt_text_bwd can repeat a segment launch for launch.
   bool ln1_ready = false;
   const int k = (int)st.seg.size() - 1;
-  for (int i = 0; i < k; ++i) {
-    st.saved = save && i == k - 1;
-    const int rc = text_segment_fwd(E, st, st.seg[i], std::min(st.seg[i + 1], E->txt.layers - 1), i == k - 1, &ln1_ready, s);
-    st.saved = save;
-    if (rc) { st.valid = false; return rc; }
-  }
+  for (int i = 0; i < k; ++i)
+    if (int rc = text_segment_fwd(E, st.seg[i], std::min(st.seg[i + 1], E->txt.layers - 1), i == k - 1, save && i == k - 1, &ln1_ready, s))
+      return rc;
   // the last block on the C gathered EOT rows
-  if (int rc = text_deep_overwrite(E, st, E->txt.layers - 1, s)) { st.valid = false; return rc; }
-  if (int rc = last_block_fwd(E, E->txt, st, E->tc, E->eot_rows, 0, false, ln1_ready, E->ln_final, false, s)) return rc;
+  st.keep = save;
+  if (int rc = text_deep_overwrite(E, E->txt.layers - 1, s)) return rc;
+  if (int rc = last_block_fwd(E, E->txt, st, R.c, R.eot_rows, 0, false, ln1_ready, E->ln_final, false, s)) return rc;
   { ProfScope ps(E, s, PC_HEAD, 2.0 * C * e * dtw, 4.0 * ((double)C * dtw + (double)e * dtw + (double)C * e));
-    HIPCHK(E, launch_sgemm_bt(E->tc.out32, E->tproj_t, feat_out, C, e, dtw, nullptr, s)); }
+    HIPCHK(E, launch_sgemm_bt(R.c.out32, E->tproj_t, feat_out, C, e, dtw, nullptr, s)); }
+  R.phase = save ? Phase::Saved : Phase::Done;
   return 0;
 }
 
@@ -1847,9 +1872,9 @@ int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, in
   if (!E || !out || C_total <= 0 || L <= 2) return fail(E, MVLPT_ERR_ARG, "text_workspace_bytes: null/invalid argument");
   // the ctx_pos table is sized for the largest n_ctx a forward accepts (L - 2): at most C_total * L * 4 bytes over the exact figure
   // a counting pass into scratch state: a saved forward whose backward has not run keeps its own
-  TowerState st; Compact c; TextTables tab;
+  TextRun scratch;
   *out = (int64_t)(carve_count([&](Bump& bp) {
-    text_layout(bp, E, st, c, tab, C_total, L, save_for_bwd != 0, text_exact(E), (size_t)C_total * (L - 2), 0, 0);
+    text_layout(bp, E, scratch, C_total, L, save_for_bwd != 0, text_exact(E), (size_t)C_total * (L - 2), 0, 0);
   }) + kTextSlack);
   return 0;
 }
@@ -1857,37 +1882,36 @@ int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, in
 // The backward of every text forward.  dctx_deep: the gradient of the deep prompts (mvlpt_text_bwd_deep); `plain` (mvlpt_text_bwd) has
 // no place for it and refuses a deep forward.
 static int text_bwd_impl(Engine* E, const float* dfeat, float* dctx, float* dctx_deep, bool plain, mvlpt_stream_t stream) {
-  TowerState& st = E->ts;
-  if (st.valid && st.consumed)
+  TextRun& R = E->trun; TowerState& st = R.st;
+  if (R.phase == Phase::Consumed)
     return fail(E, MVLPT_ERR_STATE, "text_bwd: a backward under activation checkpointing has consumed the saved state; run the forward again");
-  if (!st.valid || !st.saved) return fail(E, MVLPT_ERR_STATE, "text_bwd: call text_fwd(save_for_bwd=1) first");
-  if (E->t_nctx <= 0) return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward had no context tokens");
-  if (E->t_ndeep > 0 && plain)
+  if (!bwd_ready(R.phase)) return fail(E, MVLPT_ERR_STATE, "text_bwd: call text_fwd(save_for_bwd=1) first");
+  if (R.n_ctx <= 0) return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward had no context tokens");
+  if (R.n_deep > 0 && plain)
     return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward ran deep prompts (mvlpt_text_fwd_deep); call mvlpt_text_bwd_deep");
-  if (E->t_ndeep > 0 && !dctx_deep) return fail(E, MVLPT_ERR_ARG, "text_bwd_deep: dctx_deep is null after a forward with deep prompts");
+  if (R.n_deep > 0 && !dctx_deep) return fail(E, MVLPT_ERR_ARG, "text_bwd_deep: dctx_deep is null after a forward with deep prompts");
   hipStream_t s = (hipStream_t)stream;
   const MvlptArch& A = E->arch;
-  const int C = E->tC, L = E->tL, dtw = A.text_width, e = A.embed_dim;
+  const int C = R.C, L = R.L, dtw = A.text_width, e = A.embed_dim;
   const size_t T = (size_t)C * L;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dtw * 10.0);
     HIPCHK(E, launch_grad_scale(dfeat, (size_t)C * e, 64.0f, st.scale_dev, s));
-    HIPCHK(E, launch_sgemm_bt(dfeat, E->tproj, E->tc.dout32, C, dtw, e, st.scale_dev, s)); }
+    HIPCHK(E, launch_sgemm_bt(dfeat, E->tproj, R.c.dout32, C, dtw, e, st.scale_dev, s)); }
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dtw * 4.0);
     HIPCHK(E, launch_zero(st.dx32, T * dtw * 4, s)); }
-  if (!E->tc.kept) return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward did not keep the last block's activations");
   // the plan of the forward that saved this state (st.seg), not the engine's current setting
   const int k = (int)st.seg.size() - 1;
-  if (k > 1) st.consumed = true;      // from here on the slots no longer hold what the forward left
+  if (k > 1) R.phase = Phase::Consumed;      // from here on the slots no longer hold what the forward left
   // gradient of the deep prompts of block l (its input's context rows), which then stop carrying one into block l - 1
   auto gather_deep = [&](int l) -> int {
-    if (l < 1 || l > E->t_ndeep) return 0;
-    const int n = E->t_nctx;
+    if (l < 1 || l > R.n_deep) return 0;
+    const int n = R.n_ctx;
     ProfScope ps(E, s, PC_GLUE, 0, (double)C * n * dtw * 10.0);
-    HIPCHK(E, launch_gather_zero_ctx_grad(E->dt, st.dx32, st.dx16, st.xs, E->ctx_pos, C, L, dtw, n, dctx_deep + (size_t)(l - 1) * n * dtw,
+    HIPCHK(E, launch_gather_zero_ctx_grad(E->dt, st.dx32, st.dx16, st.xs, R.ctx_pos, C, L, dtw, n, dctx_deep + (size_t)(l - 1) * n * dtw,
                                           st.scale_dev, s));
     return 0;
   };
-  if (int rc = last_block_bwd(E, E->txt, st, E->tc, E->eot_rows, 0, E->ln_final, s)) return rc;      // the last block on the C compact EOT rows
+  if (int rc = last_block_bwd(E, E->txt, st, R.c, R.eot_rows, 0, E->ln_final, s)) return rc;      // the last block on the C compact EOT rows
   if (int rc = gather_deep(st.layers - 1)) return rc;
   for (int l = st.layers - 2; l >= st.seg[k - 1]; --l) {
     if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
@@ -1897,19 +1921,18 @@ static int text_bwd_impl(Engine* E, const float* dfeat, float* dctx, float* dctx
   // the slots the segment behind it no longer needs; then its backward
   for (int i = k - 2; i >= 0; --i) {
     bool ln1_ready = false;
-    if (int rc = text_segment_fwd(E, st, st.seg[i], st.seg[i + 1], false, &ln1_ready, s)) return rc;
+    if (int rc = text_segment_fwd(E, st.seg[i], st.seg[i + 1], false, true, &ln1_ready, s)) return rc;
     for (int l = st.seg[i + 1] - 1; l >= st.seg[i]; --l) {
       if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
       if (int rc = gather_deep(l)) return rc;
     }
   }
-  { ProfScope ps(E, s, PC_GLUE, 0, (double)C * E->t_nctx * dtw * 4.0);
-    if (E->t_kind == TextKind::Ranged)
-      HIPCHK(E, launch_gather_ctx_grad_ranged(st.dx32, E->ctx_pos, E->t_rlo, E->t_rstart, E->t_groups, L, dtw, E->t_nctx, dctx, st.scale_dev, s));
+  { ProfScope ps(E, s, PC_GLUE, 0, (double)C * R.n_ctx * dtw * 4.0);
+    if (R.kind == TextKind::Ranged)
+      HIPCHK(E, launch_gather_ctx_grad_ranged(st.dx32, R.ctx_pos, R.range, R.range + R.groups, R.groups, L, dtw, R.n_ctx, dctx, st.scale_dev, s));
     else
-      HIPCHK(E, launch_gather_ctx_grad(st.dx32, E->ctx_pos, C, L, dtw, E->t_nctx, E->t_per_class, dctx, st.scale_dev, s)); }
-  if (k > 1) st.saved = false;
-  st.bwd_done = true;
+      HIPCHK(E, launch_gather_ctx_grad(st.dx32, R.ctx_pos, C, L, dtw, R.n_ctx, R.per_class, dctx, st.scale_dev, s)); }
+  if (k == 1) R.phase = Phase::BwdDone;
   return 0;
 }
 
@@ -1929,9 +1952,10 @@ int mvlpt_text_bwd_deep(void* h, const float* dfeat, float* dctx, float* dctx_de
 // The normalised rows and norms of B image and C text features; the ranged head's table of `ints` ints behind them (*tab)
 static int head_carve(Engine* E, const char* who, int B, int C, size_t ints = 0, int32_t** tab = nullptr) {
   const int e = E->arch.embed_dim;
+  HeadRun& R = E->hrun;
   return carve_ws(E, E->head_ws, who, kCarveSlack, [&](Bump& bp) {
-    E->imn = bp.take<float>((size_t)B * e); E->txn = bp.take<float>((size_t)C * e);
-    E->inorm = bp.take<float>(B); E->tnorm = bp.take<float>(C);
+    R.imn = bp.take<float>((size_t)B * e); R.txn = bp.take<float>((size_t)C * e);
+    R.inorm = bp.take<float>(B); R.tnorm = bp.take<float>(C);
     if (tab) *tab = bp.take<int32_t>(ints);
   });
 }
@@ -1943,49 +1967,26 @@ int mvlpt_logits_fwd(void* h, const float* img, const float* txt, float scale, c
     return fail(E, MVLPT_ERR_ARG, "logits_fwd: null/invalid argument");
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
-  E->hB = 0;
+  HeadRun& R = E->hrun = HeadRun();      // opened
   if (int rc = head_carve(E, "logits_fwd", B, C)) return rc;
   ProfScope ps(E, s, PC_HEAD, 2.0 * B * C * e, 4.0 * ((double)B * e + (double)C * e + (double)B * C));
-  HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, B, e, s));
-  HIPCHK(E, launch_normalize_rows(txt, E->txn, E->tnorm, C, e, s));
-  HIPCHK(E, launch_logits(E->imn, E->txn, scale, lo, hi, logits, B, C, e, s));
-  E->hB = B; E->hC = C; E->h_scale = scale; E->h_lo = lo; E->h_hi = hi; E->h_kind = HeadKind::Plain;
+  HIPCHK(E, launch_normalize_rows(img, R.imn, R.inorm, B, e, s));
+  HIPCHK(E, launch_normalize_rows(txt, R.txn, R.tnorm, C, e, s));
+  HIPCHK(E, launch_logits(R.imn, R.txn, scale, lo, hi, logits, B, C, e, s));
+  R.B = B; R.C = C; R.scale = scale; R.lo = lo; R.hi = hi; R.kind = HeadKind::Plain;
+  R.phase = Phase::Saved;
   return 0;
 }
 
 int mvlpt_logits_bwd(void* h, const float* dlogits, float* dimg, float* dtxt, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !dlogits) return fail(E, MVLPT_ERR_ARG, "logits_bwd: null argument");
-  if (E->hB <= 0 || !E->imn || E->h_kind != HeadKind::Plain) return fail(E, MVLPT_ERR_STATE, "logits_bwd: call logits_fwd first");
+  const HeadRun& R = E->hrun;
+  if (R.phase != Phase::Saved || R.kind != HeadKind::Plain) return fail(E, MVLPT_ERR_STATE, "logits_bwd: call logits_fwd first");
   hipStream_t s = (hipStream_t)stream;
   const int e = E->arch.embed_dim;
-  ProfScope ps(E, s, PC_HEAD, 4.0 * E->hB * E->hC * e, 4.0 * ((double)E->hB * e + (double)E->hC * e + (double)E->hB * E->hC) * 2);
-  HIPCHK(E, launch_logits_bwd(dlogits, E->imn, E->txn, E->inorm, E->tnorm, E->h_scale, E->h_lo, E->h_hi, dimg, dtxt, E->hB, E->hC, e, s));
-  return 0;
-}
-
-// The ranged head over the table in E->h_range_host (G groups, S text rows): image g against the text rows of its own class range
-static int head_ranged_fwd(Engine* E, const float* img, const float* txt, float scale, int G, int C, int S, float* logits,
-                           hipStream_t s) {
-  const int e = E->arch.embed_dim;
-  const size_t ints = E->h_range_host.size();
-  int32_t* tab = nullptr;
-  if (int rc = head_carve(E, "logits_ranged_fwd", G, S, ints, &tab)) return rc;
-  ProfScope ps(E, s, PC_HEAD, 2.0 * S * e, 4.0 * ((double)G * e + (double)S * e + (double)G * C));
-  HIPCHK(E, hipMemcpyAsync(tab, E->h_range_host.data(), ints * 4, hipMemcpyHostToDevice, s));
-  HIPCHK(E, launch_normalize_rows(img, E->imn, E->inorm, G, e, s));
-  HIPCHK(E, launch_normalize_rows(txt, E->txn, E->tnorm, S, e, s));
-  HIPCHK(E, launch_logits_ranged(E->imn, E->txn, scale, tab, tab + G, logits, G, C, e, s));
-  E->hB = G; E->hC = C; E->hS = S; E->h_scale = scale; E->h_lo = E->h_hi = nullptr; E->h_kind = HeadKind::Ranged;
-  E->h_rlo = tab; E->h_rstart = tab + G; E->h_rgrp = tab + 2 * G + 1 + S;
-  return 0;
-}
-// dtxt [S, e] and / or dimg [G, e] of the last head_ranged_fwd (a null output's kernel is not launched)
-static int head_ranged_bwd(Engine* E, const float* dlogits, float* dtxt, float* dimg, hipStream_t s) {
-  const int e = E->arch.embed_dim;
-  ProfScope ps(E, s, PC_HEAD, 6.0 * E->hS * e, 4.0 * ((double)E->hB * e * 2 + 3.0 * E->hS * e + (double)E->hS));
-  HIPCHK(E, launch_logits_ranged_bwd(dlogits, E->imn, E->txn, E->inorm, E->tnorm, E->h_scale, E->h_rlo, E->h_rstart, E->h_rgrp, dimg, dtxt,
-                                     E->hB, E->hS, E->hC, e, s));
+  ProfScope ps(E, s, PC_HEAD, 4.0 * R.B * R.C * e, 4.0 * ((double)R.B * e + (double)R.C * e + (double)R.B * R.C) * 2);
+  HIPCHK(E, launch_logits_bwd(dlogits, R.imn, R.txn, R.inorm, R.tnorm, R.scale, R.lo, R.hi, dimg, dtxt, R.B, R.C, e, s));
   return 0;
 }
 
@@ -1996,17 +1997,36 @@ int mvlpt_logits_ranged_fwd(void* h, const float* img, const float* txt, float s
   Engine* E = (Engine*)h;
   if (!E || !img || !txt || !class_lo || !class_hi || !logits || G <= 0 || C <= 0 || G > 65535 || (int64_t)G * C > INT32_MAX)
     return fail(E, MVLPT_ERR_ARG, "logits_ranged_fwd: null/invalid argument");
-  E->hB = 0;
-  const int64_t S = build_range_table(class_lo, class_hi, G, C, E->h_range_host);
+  HeadRun& R = E->hrun = HeadRun();      // opened
+  const int S = (int)build_range_table(class_lo, class_hi, G, C, E->h_range_host);      // (at most G * C)
   if (S <= 0) return fail(E, MVLPT_ERR_ARG, "logits_ranged_fwd: a class range is not inside [0, C], or every range is empty");
-  return head_ranged_fwd(E, img, txt, scale, G, C, (int)S, logits, (hipStream_t)stream);
+  hipStream_t s = (hipStream_t)stream;
+  const int e = E->arch.embed_dim;
+  const size_t ints = E->h_range_host.size();
+  int32_t* tab = nullptr;
+  if (int rc = head_carve(E, "logits_ranged_fwd", G, S, ints, &tab)) return rc;
+  ProfScope ps(E, s, PC_HEAD, 2.0 * S * e, 4.0 * ((double)G * e + (double)S * e + (double)G * C));
+  HIPCHK(E, hipMemcpyAsync(tab, E->h_range_host.data(), ints * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(E, launch_normalize_rows(img, R.imn, R.inorm, G, e, s));
+  HIPCHK(E, launch_normalize_rows(txt, R.txn, R.tnorm, S, e, s));
+  HIPCHK(E, launch_logits_ranged(R.imn, R.txn, scale, tab, tab + G, logits, G, C, e, s));
+  R.B = G; R.C = C; R.S = S; R.scale = scale; R.kind = HeadKind::Ranged;
+  R.rlo = tab; R.rstart = tab + G; R.rgrp = tab + 2 * G + 1 + S;
+  R.phase = Phase::Saved;
+  return 0;
 }
 
+// dtxt [S, e] and / or dimg [G, e] of the last mvlpt_logits_ranged_fwd (a null output's kernel is not launched)
 int mvlpt_logits_ranged_bwd(void* h, const float* dlogits, float* dtxt, float* dimg, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
   if (!E || !dlogits || (!dtxt && !dimg)) return fail(E, MVLPT_ERR_ARG, "logits_ranged_bwd: null argument");
-  if (E->hB <= 0 || !E->imn || E->h_kind != HeadKind::Ranged) return fail(E, MVLPT_ERR_STATE, "logits_ranged_bwd: call logits_ranged_fwd first");
-  return head_ranged_bwd(E, dlogits, dtxt, dimg, (hipStream_t)stream);
+  const HeadRun& R = E->hrun;
+  if (R.phase != Phase::Saved || R.kind != HeadKind::Ranged) return fail(E, MVLPT_ERR_STATE, "logits_ranged_bwd: call logits_ranged_fwd first");
+  hipStream_t s = (hipStream_t)stream;
+  const int e = E->arch.embed_dim;
+  ProfScope ps(E, s, PC_HEAD, 6.0 * R.S * e, 4.0 * ((double)R.B * e * 2 + 3.0 * R.S * e + (double)R.S));
+  HIPCHK(E, launch_logits_ranged_bwd(dlogits, R.imn, R.txn, R.inorm, R.tnorm, R.scale, R.rlo, R.rstart, R.rgrp, dimg, dtxt, R.B, R.S, R.C, e, s));
+  return 0;
 }
 
 int mvlpt_cross_entropy(void* h, const float* logits, const void* labels, int kind, int B, int C, float* loss, float* dlogits,

@@ -23,16 +23,12 @@ import torch.nn as nn
 
 from . import _lib
 from .config import read_activation, read_vision_head_width
-from .model import (FrozenCLIP, PretokenizedPrompts, _text_inputs, apply_text_act_ckpt, class_prompt_tables, image_conditioned_ctx,
-                    register_class_tables)
+# DEFAULT_MAX_TEXT_WORKSPACE_BYTES: workspace budget of the CoCoOp text tower (not a reference key).  A chunk is the largest number of
+# images whose text tower fits it (mvlpt_text_workspace_bytes); ViT-B/16 with 100 classes needs 1.67 GiB per image for a training step.
+from .model import (DEFAULT_MAX_TEXT_WORKSPACE_BYTES, MAX_SEQUENCES_PER_TOWER, FrozenCLIP, PretokenizedPrompts, _text_inputs,
+                    apply_text_act_ckpt, class_prompt_tables, image_conditioned_ctx, register_class_tables)
 from .trainer import MVLPT, TrainerX, refuse_wide_heads
 from .weights import get_arch, make_state_dict
-
-# Workspace budget of the CoCoOp text tower (not a reference key).  A chunk is the largest number of images whose
-# text tower fits it (mvlpt_text_workspace_bytes).  ViT-B/16 with 100 classes needs 1.67 GiB per image for a training step.
-DEFAULT_MAX_TEXT_WORKSPACE_BYTES = 16 << 30
-# sequences per tower: the attention launches put the sequence index on grid.y
-MAX_SEQUENCES_PER_TOWER = 32768
 
 
 class PromptLearner(nn.Module):

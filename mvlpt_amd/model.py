@@ -9,8 +9,8 @@ as in the reference.  The towers do NOT run on PyTorch ops: `CustomCLIP.forward`
 tiny UPT projection (forward_mvlpt_proj, ≤52 tokens × width 128, trainable weights) stays on torch autograd.
 
 Deviations (documented in DESIGN.md): prompt parameters are kept in fp32 even when PREC == "fp16" (fp32 master
-copies; the reference keeps fp16 parameters and has no loss scaling); CoCoOp inside MVLPT (MVLPT.COCOOP.N_CTX != 0) is out of
-scope — trainers/cocoop.py's own CoCoOp lives in mvlpt_amd/cocoop.py.
+copies; the reference keeps fp16 parameters and has no loss scaling).  CoCoOp inside MVLPT (MVLPT.COCOOP.N_CTX != 0) is not this
+module's route: it lives in mvlpt_amd/mvlpt_cocoop.py, and trainers/cocoop.py's own CoCoOp in mvlpt_amd/cocoop.py.
 """
 from __future__ import annotations
 
@@ -27,6 +27,7 @@ import torch.nn as nn
 
 from ._lib import TEXT_MIN_L
 from .engine import Engine
+from .schedule import ImagePrefetch, TextFeatureCache, check_forward_is_current, fork
 from .weights import ClipArch, _randn, arch_from_state_dict, is_resnet
 
 # compute units of the text tower's partition in the two-tower pipeline (CustomCLIP.set_cu_partition); 0 = no partition.
@@ -607,148 +608,93 @@ class _PromptedClipFn(torch.autograd.Function):
     def forward(fctx, model: "CustomCLIP", image, task_lo, task_hi, coop_emb, vpt_emb, vpt_deep_emb, grad_on=True, ctx_deep=None):
         eng = model.engine
         pl = model.prompt_learner
-        if ctx_deep is not None:
-            # deep text prompts (COOP.N_DEEP): the same tower through the deep entries; class sharding is refused at set-up
-            def text_fwd(prefix, suffix, ctx, layout, eot, save_for_bwd=False):
-                return eng.text_fwd_deep(prefix, suffix, ctx, ctx_deep, layout, eot, save_for_bwd=save_for_bwd)
-        else:
-            text_fwd = eng.text_fwd
         # (grad mode is off inside Function.forward: ask autograd which inputs need a gradient)
         # `grad_on` = torch.is_grad_enabled() at the call site (needs_input_grad ignores torch.no_grad())
         need_txt = grad_on and bool(fctx.needs_input_grad[4] or fctx.needs_input_grad[8])
         need_img = grad_on and bool(fctx.needs_input_grad[5] or fctx.needs_input_grad[6])
-        # inference: the text features depend only on the prompt parameters -> computed once per parameter version
-        # instead of once per batch as the reference does (trainers/mvlpt.py:546-548 under test(), :989-1088)
-        ver = None
-        if not pl.training and not need_txt and coop_emb is not None:   # Dassl sets the mode on the registered prompt_learner
-            ver = tuple((id(p), p._version) for p in model.prompt_learner.parameters())
-            if model._eval_text_cache is not None and model._eval_text_cache[0] == ver:
-                model._const_text_features, cached_eval = model._eval_text_cache[1], True
-            else:
-                cached_eval = False
-        else:
-            cached_eval = False
-        run_text = not ((coop_emb is None or cached_eval) and model._const_text_features is not None)
-        suffix, layout = _text_inputs(model, pl, pl.coop_n_ctx)
-        # features computed ahead of time (prefetch_image_features), keyed by the tensor they belong to
-        key = (image.data_ptr(), tuple(image.shape), image._version)
-        if model._pending is not None and (vpt_emb is not None or key not in model._prefetched):
-            # a tower begun under the prefetch split that nobody resumed (the loop left the loader early), or begun for THIS tensor:
-            # it is finished before this forward uses the engine's one image-tower state
-            model._resume_pending()
-        pre = model._prefetched.pop(key, None) if vpt_emb is None else None
-        if pre is not None:
-            def image_fwd(*_a, **_k):
-                torch.cuda.current_stream().wait_event(pre[1])
-                pre[0].record_stream(torch.cuda.current_stream())
-                return pre[0]
-        else:
-            # prefetches for OTHER tensors are (or were) writing the image-tower workspace on their own stream: this forward
-            # runs the tower itself, behind them (and they stay available to the forwards they were made for)
-            for other in model._prefetched.values():
-                torch.cuda.current_stream().wait_event(other[1])
-            image_fwd = eng.image_fwd
-        shard = model._class_shard if (run_text and coop_emb is not None) else None
-        side = model._side_stream if (run_text and model.overlap_towers and shard is None) else None
-        if shard is not None:
-            # Class-sharded text tower (ClassShard): this rank encodes classes [lo, hi) only and the features are
-            # all-gathered; the backward reduce-scatters d(txt) back to the owners.  Tower and collective run on the second
-            # stream underneath the image tower, exactly like the replicated text tower below.
-            lo, hi = shard.lo, shard.hi
-            ctx_loc = coop_emb if coop_emb.dim() == 2 else coop_emb[lo:hi]
 
-            def text_side():
-                loc = eng.text_fwd(pl.token_prefix[lo:hi], suffix[lo:hi], ctx_loc, layout[lo:hi], pl.eot[lo:hi],
-                                   save_for_bwd=need_txt)
-                return shard.gather(loc)
-            side_s = model._side_stream if model.overlap_towers else None
-            if side_s is not None:
-                main = torch.cuda.current_stream()
-                side_s.wait_stream(main)
-                with torch.cuda.stream(side_s):
-                    txt = text_side()
-                img = image_fwd(image, vpt_emb, vpt_deep_emb, save_for_bwd=need_img)
-                main.wait_stream(side_s)
-                txt.record_stream(main)
+        # 1. text features from the cache, or a text job to run
+        txt, slot = model.text_cache.lookup(pl, coop_emb is not None, need_txt)
+        shard = text_job = None
+        if txt is None:
+            suffix, layout = _text_inputs(model, pl, pl.coop_n_ctx)
+            shard = model._class_shard if coop_emb is not None else None
+            if shard is not None:
+                # Class-sharded text tower (ClassShard): this rank encodes classes [lo, hi) only and the features are
+                # all-gathered; the backward reduce-scatters d(txt) back to the owners.  Tower and collective are one job.
+                lo, hi = shard.lo, shard.hi
+                ctx_loc = coop_emb if coop_emb.dim() == 2 else coop_emb[lo:hi]
+
+                def text_job():
+                    loc = eng.text_fwd(pl.token_prefix[lo:hi], suffix[lo:hi], ctx_loc, layout[lo:hi], pl.eot[lo:hi],
+                                       save_for_bwd=need_txt)
+                    return shard.gather(loc)
+            elif ctx_deep is not None:
+                # deep text prompts (COOP.N_DEEP): the same tower through the deep entries; class sharding is refused at set-up
+                def text_job():
+                    return eng.text_fwd_deep(pl.token_prefix, suffix, coop_emb, ctx_deep, layout, pl.eot, save_for_bwd=need_txt)
             else:
-                img = image_fwd(image, vpt_emb, vpt_deep_emb, save_for_bwd=need_img)
-                txt = text_side()
-        elif side is not None:
-            # The two towers are independent until the logits: the text tower (few, small launches that cannot
-            # fill 256 CUs) runs on a second HIP stream underneath the image tower's large GEMMs.
-            main = torch.cuda.current_stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                txt = text_fwd(pl.token_prefix, suffix, coop_emb, layout, pl.eot, save_for_bwd=need_txt)
-            img = image_fwd(image, vpt_emb, vpt_deep_emb, save_for_bwd=need_img)
-            main.wait_stream(side)
-            txt.record_stream(main)
-        else:
-            img = image_fwd(image, vpt_emb, vpt_deep_emb, save_for_bwd=need_img)
-            if run_text:
-                txt = text_fwd(pl.token_prefix, suffix, coop_emb, layout, pl.eot, save_for_bwd=need_txt)
-        if not run_text:
-            txt = model._const_text_features
-        elif coop_emb is None:
-            model._const_text_features = txt     # no text context: features are constants
-        if ver is not None:
-            model._eval_text_cache = (ver, txt.clone() if shard is not None else txt)   # (a gathered txt lives in a reused buffer)
-        if coop_emb is not None:
-            model._const_text_features = None    # only the no-context case may persist across training steps
+                def text_job():
+                    return eng.text_fwd(pl.token_prefix, suffix, coop_emb, layout, pl.eot, save_for_bwd=need_txt)
+
+        # 2. image features from the prefetch (prefetch_image_features), or an image job to run
+        entry = model.prefetch.claim(image, prompted=vpt_emb is not None)
+
+        def image_job():
+            if entry is not None:
+                return model.prefetch.pick_up(entry)
+            return eng.image_fwd(image, vpt_emb, vpt_deep_emb, save_for_bwd=need_img)
+
+        # 3. The two towers are independent until the logits: the text tower (few, small launches that cannot fill 256 CUs) is
+        # forked onto the text stream underneath the image tower's large GEMMs and joined behind it.  With no such stream the
+        # "join" is the text job itself: inline, image tower first, then text
+        side = model.text_stream if (text_job is not None and model.overlap_towers) else None
+        join = text_job if side is None else fork(side, text_job)
+        img = image_job()
+        if text_job is not None:
+            txt = join()
+            model.text_cache.store(slot, txt, gathered=shard is not None)
+
+        # 4. the head
         logits = eng.logits_fwd(img, txt, model.logit_scale_exp, task_lo, task_hi)
-        # the engine keeps ONE set of saved activations per tower: stamp this forward so that a backward that arrives
-        # after another forward has overwritten them (gradient accumulation, test() between forward and backward) is
-        # refused instead of silently using the wrong activations
-        model._fwd_generation += 1
+        model._fwd_generation += 1               # (check_forward_is_current)
         fctx.generation = model._fwd_generation
         fctx.model, fctx.need_img, fctx.need_txt = model, need_img, need_txt
         fctx.shard, fctx.ctx_shape = shard, (None if coop_emb is None else coop_emb.shape)
-        fctx.has_deep = vpt_deep_emb is not None
         fctx.text_deep = ctx_deep is not None
         fctx.vpt_shape = None if vpt_emb is None else vpt_emb.shape
         return logits
 
     @staticmethod
     def backward(fctx, dlogits):
-        eng = fctx.model.engine
-        if fctx.generation != fctx.model._fwd_generation:
-            raise RuntimeError("backward of a stale forward: the engine holds the saved activations of the most recent "
-                               "CustomCLIP.forward only (call backward before the next forward)")
+        model, shard = fctx.model, fctx.shard
+        eng = model.engine
+        check_forward_is_current(model, fctx.generation)
         dimg, dtxt = eng.logits_bwd(dlogits.contiguous(), fctx.need_img, fctx.need_txt)
         dctx = dvpt = ddeep = dctx_deep = None
-        if fctx.text_deep:
-            def text_bwd(d):
-                return eng.text_bwd_deep(d)
-        else:
-            def text_bwd(d):
-                return eng.text_bwd(d), None
-        if fctx.need_txt and fctx.shard is not None:
-            lo, hi = fctx.shard.lo, fctx.shard.hi
-            # sum over ranks of d(local loss)/d(txt) for the classes this rank owns; the trainer's gradient
-            # all-reduce (mean over ranks) then yields d(global mean loss)/d(ctx) summed over all class shards
-            own = fctx.shard.scatter_grads(dtxt)
-            dloc = eng.text_bwd(own)
-            if len(fctx.ctx_shape) == 3:                      # class-specific contexts: only the owned rows are non-zero
-                dctx = torch.zeros(fctx.ctx_shape, device=dloc.device, dtype=dloc.dtype)
-                dctx[lo:hi] = dloc
+        if fctx.need_txt:
+            if shard is not None:
+                def text_job():
+                    # sum over ranks of d(local loss)/d(txt) for the classes this rank owns; the trainer's gradient
+                    # all-reduce (mean over ranks) then yields d(global mean loss)/d(ctx) summed over all class shards
+                    own = shard.scatter_grads(dtxt)
+                    dloc = eng.text_bwd(own)
+                    if len(fctx.ctx_shape) == 3:                      # class-specific contexts: only the owned rows are non-zero
+                        full = torch.zeros(fctx.ctx_shape, device=dloc.device, dtype=dloc.dtype)
+                        full[shard.lo:shard.hi] = dloc
+                        return full, None
+                    return dloc, None
+            elif fctx.text_deep:
+                def text_job():
+                    return eng.text_bwd_deep(dtxt)
             else:
-                dctx = dloc
-        elif fctx.need_txt:
-            part = fctx.model._text_partition
-            if part is not None and not fctx.need_img:
-                # CU partition (set_cu_partition): the backward of the text tower stays on the text stream's compute units,
-                # next to the image tower of the following batch on the prefetch stream's
-                main = torch.cuda.current_stream()
-                part.wait_stream(main)
-                with torch.cuda.stream(part):
-                    dctx, dctx_deep = text_bwd(dtxt)
-                dtxt.record_stream(part)
-                main.wait_stream(part)
-                dctx.record_stream(main)
-                if dctx_deep is not None:
-                    dctx_deep.record_stream(main)
-            else:
-                dctx, dctx_deep = text_bwd(dtxt)
+                def text_job():
+                    return eng.text_bwd(dtxt), None
+            # CU partition (set_cu_partition): the backward of the text tower stays on the text stream's compute units,
+            # next to the image tower of the following batch on the prefetch stream's; otherwise it runs where it is
+            partitioned = model.text_cus and shard is None and not fctx.need_img
+            join = fork(model.text_stream, text_job, uses=(dtxt,)) if partitioned else text_job
+            dctx, dctx_deep = join()
         if fctx.need_img:
             dvpt, ddeep = eng.image_bwd(dimg)
             dvpt = dvpt.view(fctx.vpt_shape)
@@ -772,8 +718,57 @@ class _CrossEntropyFn(torch.autograd.Function):
         return None, dl * g, None
 
 
-class CustomCLIP(nn.Module):
-    """trainers/mvlpt.py:517-583."""
+def class_range_tables(dm):
+    """(start, end): the class range of every task, indexed by task id; sized num_classes as in the reference
+    (trainers/mvlpt.py:529-537).  Host tensors."""
+    start = torch.arange(dm._num_classes)
+    end = torch.arange(dm._num_classes)
+    s = 0
+    for i, task in enumerate(dm._task_names):
+        start[i] = s
+        s += len(dm._labelmap[task])
+        end[i] = s
+    return start, end
+
+
+class VisualPromptSide:
+    """The visual-prompt side of a model with a `prompt_learner` of MultitaskVLPromptLearner's kind, `engine`, `clip_model` and
+    `dtype`: mvlpt_amd.model.CustomCLIP and mvlpt_amd.mvlpt_cocoop.CustomCLIP."""
+
+    def projected_prompts(self, batch: Optional[int] = None):
+        """(coop_emb, vpt, vpt_deep) as the towers take them: forward_mvlpt_proj, then vpt_proj (VPT.PROJECT > -1: a trainable
+        Linear, else Identity) in front of the shallow and of every deep prompt (:424, :77) — a few hundred FLOPs on [n, vpt_dim]
+        rows, left to torch autograd.  `batch`: the forward over that many images follows, and the engine gets its dropout masks."""
+        pl = self.prompt_learner
+        coop_emb, vpt_emb, vpt_emb_deep = pl.forward_mvlpt_proj(self.dtype)
+        if vpt_emb is not None:
+            vpt_emb = pl.vpt_proj(vpt_emb)
+            if vpt_emb_deep is not None:
+                vpt_emb_deep = pl.vpt_proj(vpt_emb_deep)
+            if batch is not None:
+                self.engine.set_vpt_dropout(self.vpt_dropout_masks(batch))
+        return coop_emb, vpt_emb, vpt_emb_deep
+
+    def vpt_dropout_masks(self, B):
+        """Outcome of `vpt_dropout` on the prompt rows of every prompted layer, drawn in the reference's order (the shallow prompts
+        in forward_vpt, trainers/mvlpt.py:424, then layer 1, 2, ... in ImageEncoder.forward, :77), each on the rows already expanded
+        over the batch: [n_layers, B, n_vpt, width] of 0 or 1 / (1 - p), or None when nothing is dropped (p = 0, eval mode)."""
+        pl = self.prompt_learner
+        p = float(pl.vpt_dropout.p)
+        if pl.vpt_embeddings is None or p == 0.0 or not pl.training:
+            return None
+        if getattr(self, "_vpt_masks_override", None) is not None:      # tests: the masks the reference drew
+            return self._vpt_masks_override
+        n_layers = 1 + (pl.vpt_embeddings_deep.shape[0] if (pl.vpt_deep and pl.vpt_embeddings_deep is not None) else 0)
+        dev = pl.vpt_embeddings.device
+        ones = torch.ones(B, pl.vpt_n_ctx, self.clip_model.arch.vision_width, device=dev)
+        return torch.stack([pl.vpt_dropout(ones) for _ in range(n_layers)])
+
+
+class CustomCLIP(VisualPromptSide, nn.Module):
+    """trainers/mvlpt.py:517-583.  The step schedule (mvlpt_amd.schedule, DESIGN.md "Step schedule"): `text_stream` carries the text
+    tower beside the image tower when `overlap_towers`, `prefetch` the image towers computed ahead, `text_cache` the text features
+    that outlive a forward."""
 
     def __init__(self, cfg, classnames, clip_model: FrozenCLIP, dm=None, pretokenized: Optional[PretokenizedPrompts] = None):
         super().__init__()
@@ -785,36 +780,21 @@ class CustomCLIP(nn.Module):
         self.logit_scale = clip_model.logit_scale
         self.logit_scale_exp = float(clip_model.logit_scale.exp())
         self.dtype = clip_model.dtype
-        self._const_text_features = None
         self.last_ncorrect = None
         self.overlap_towers = True
         self._class_shard = None
-        self._eval_text_cache = None
         self.trim_text_to_eot = False
-        self._prefetch_stream = None
-        self._prefetched = {}                     # (data_ptr, shape, version) of an image tensor -> (features, event, the tensor:
-                                                  # holding it pins its storage, so the pointer cannot be handed to another batch)
-        self._pending = None                      # prefetch split: (key, image, event behind the first part) of the tower begun
-        self.prefetch_split = (0, 0)              # (stop_block, cu_cap) of TRAINER.MVLPT.PREFETCH_SPLIT; (0, 0): one piece
+        self.text_cache = TextFeatureCache()
+        self.prefetch = ImagePrefetch(self.engine, clip_model.device)
         self._fwd_generation = 0
-        # MVLPT_TEXT_PRIORITY=1 (experiment): the text tower's stream above, the image prefetch stream below the default priority
-        self._prio = os.environ.get("MVLPT_TEXT_PRIORITY", "0") != "0"
-        self._side_stream = torch.cuda.Stream(device=clip_model.device, priority=-1 if self._prio else 0) if torch.cuda.is_available() else None
-        self._text_partition = None
+        # None without a GPU: both towers inline.  Under a CU partition (text_cus > 0) it owns compute units [0, text_cus)
+        self.text_stream = torch.cuda.Stream(device=clip_model.device) if torch.cuda.is_available() else None
         self.text_cus = 0
-        if self._side_stream is not None:
+        if self.text_stream is not None:
             self.set_cu_partition(int(os.environ.get("MVLPT_TEXT_CUS", DEFAULT_TEXT_CUS)))
         self.multi_task_label_pertask = cfg.DATASET.MULTITASK_LABEL_PERTASK
         if self.multi_task_label_pertask:
-            # indexed by task id; sized num_classes as in the reference (:529-537)
-            start = torch.arange(dm._num_classes)
-            end = torch.arange(dm._num_classes)
-            s = 0
-            for i, task in enumerate(dm._task_names):
-                start[i] = s
-                s += len(dm._labelmap[task])
-                end[i] = s
-            self.class_index_pertask_start, self.class_index_pertask_end = start, end
+            self.class_index_pertask_start, self.class_index_pertask_end = class_range_tables(dm)
 
     def enable_class_sharding(self, rank: int, world: int) -> None:
         """Shard the text tower over classes across `world` data-parallel ranks (many-class configs: the text tower
@@ -840,17 +820,26 @@ class CustomCLIP(nn.Module):
         dev = self.clip_model.device
         pl = self.prompt_learner
         if text_cus <= 0 or pl.vpt_embeddings is not None or pl.coop_n_ctx == 0:
-            if self._text_partition is not None:
-                self._side_stream = torch.cuda.Stream(device=dev)
-                self._prefetch_stream = None
-            self._text_partition, self.text_cus = None, 0
+            if self.text_cus:
+                self.text_stream = torch.cuda.Stream(device=dev)
+                self.prefetch.stream = None
+            self.text_cus = 0
             return
         total = device_cus(dev)
         text_cus = min(max(8, text_cus // 8 * 8), total - 8)       # whole CUs of every XCD on both sides
         torch.cuda.synchronize(dev)
-        self._side_stream = self._text_partition = partition_stream(dev, 0, text_cus)
-        self._prefetch_stream = partition_stream(dev, text_cus, total - text_cus)
+        self.text_stream = partition_stream(dev, 0, text_cus)
+        self.prefetch.stream = partition_stream(dev, text_cus, total - text_cus)
         self.text_cus = text_cus
+
+    @property
+    def prefetch_split(self) -> tuple:
+        """(stop_block, cu_cap) of TRAINER.MVLPT.PREFETCH_SPLIT; (0, 0): the image tower in one piece."""
+        return self.prefetch.split
+
+    @prefetch_split.setter
+    def prefetch_split(self, split) -> None:
+        self.prefetch.split = split
 
     def split_active(self) -> bool:
         """The prefetch split applies: a split is set and nothing makes today's schedule the only one (the towers on one stream,
@@ -860,125 +849,37 @@ class CustomCLIP(nn.Module):
         layers = getattr(getattr(self.engine, "arch", None), "vision_layers", 0)
         # (a split point past the last full-width block is not a split of THIS tower: a default found on twelve blocks leaves a
         # two-block test tower in one piece; stop_block = layers - 1 is the old early-prefetch schedule, kept as the control)
-        return (0 < self.prefetch_split[0] <= layers - 1 and self.overlap_towers and self._side_stream is not None
+        return (0 < self.prefetch_split[0] <= layers - 1 and self.overlap_towers and self.text_stream is not None
                 and self._class_shard is None and self.text_cus == 0 and self.prompt_learner.vpt_embeddings is None)
 
     def has_prefetched(self, image) -> bool:
-        return (image.data_ptr(), tuple(image.shape), image._version) in self._prefetched
-
-    def _resume_pending(self) -> None:
-        """Second part of the tower begun by prefetch_image_features(stop_block=...): uncapped, on the prefetch stream."""
-        key, image, _ = self._pending
-        self._pending = None
-        st = self._prefetch_stream
-        with torch.cuda.stream(st):
-            feat = self.engine.image_fwd_resume()
-            ev = torch.cuda.Event()
-            ev.record(st)
-        if len(self._prefetched) >= 4:
-            self._prefetched.pop(next(iter(self._prefetched)))
-        self._prefetched[key] = (feat, ev, image)
+        return self.prefetch.get(image) is not None
 
     def prefetch_image_features(self, image, stop_block=None, cu_cap=None) -> bool:
         """Software pipelining across steps: with no visual prompts the image tower is a pure function of the image
         (frozen weights, trainers/mvlpt.py:855-858), so the features of the NEXT batch are computed on a third HIP stream
         beside the current step's text tower (forward, backward: small launches that cannot fill the chip), head and
         optimizer.  `forward(image)` picks the result up when it is called with the same tensor.  Successive prefetches
-        queue up on that one stream (they share the tower workspace), so the trainer can issue the one for batch i+1 BEFORE
-        step i's own forward: the image stream then never waits for a step's logits.
+        queue up on that one stream (they share the tower workspace).
 
-        Prefetch split: with `stop_block` > 0 only the tower entry and blocks [0, stop_block) are enqueued, with their grids capped
-        at `cu_cap` compute units (0 / None: uncapped) so that they leave the rest of the chip to the text forward they run beside;
-        a second call for the same tensor enqueues the rest, uncapped, behind whatever the main stream holds at that point."""
-        pl = self.prompt_learner
-        if pl.vpt_embeddings is not None or self._side_stream is None:
+        Prefetch split: with `stop_block` > 0 (and `split_active`) only the first blocks are enqueued, capped at `cu_cap` compute
+        units; a second call for the same tensor enqueues the rest (ImagePrefetch.start).  False: this model prefetches nothing."""
+        if self.prompt_learner.vpt_embeddings is not None or self.text_stream is None:
             return False
-        key = (image.data_ptr(), tuple(image.shape), image._version)
-        if key in self._prefetched:
-            return True
-        main = torch.cuda.current_stream()
-        if self._prefetch_stream is None:
-            self._prefetch_stream = torch.cuda.Stream(device=self.clip_model.device, priority=1 if self._prio else 0)
-        st = self._prefetch_stream
-        # the image tensor was produced (uploaded) on the main stream; an image forward that ran on the main stream itself
-        # (no prefetch: the first step, an evaluation) must be done with the tower workspace
-        ready = torch.cuda.Event()
-        ready.record(main)
-        st.wait_event(ready)
-        if self._pending is not None:
-            # the second call for the tensor whose tower was begun — or a tower begun for a tensor nobody came back for
-            mine = self._pending[0] == key
-            self._resume_pending()
-            if mine:
-                return True
-        if stop_block and self.split_active():
-            from .engine import set_stream_cu_cap
-            with torch.cuda.stream(st):
-                set_stream_cu_cap(st, int(cu_cap or 0))
-                try:
-                    self.engine.image_fwd_begin(image, None, None, save_for_bwd=False, stop_block=int(stop_block))
-                finally:
-                    set_stream_cu_cap(st, 0)
-                ev = torch.cuda.Event()
-                ev.record(st)
-            image.record_stream(st)
-            self._pending = (key, image, ev)
-            return True
-        with torch.cuda.stream(st):
-            feat = self.engine.image_fwd(image, None, None, save_for_bwd=False)
-            ev = torch.cuda.Event()
-            ev.record(st)
-        image.record_stream(st)
-        if len(self._prefetched) >= 4:            # never picked up (a loop that reads ahead without consuming): keep the newest
-            self._prefetched.pop(next(iter(self._prefetched)))
-        self._prefetched[key] = (feat, ev, image)
+        split = bool(stop_block) and self.split_active()
+        self.prefetch.start(image, int(stop_block) if split else 0, int(cu_cap or 0))
         return True
 
     def drop_prefetch(self) -> None:
-        """Forget prefetched image forwards that nobody will pick up (the loop left the loader early): the main stream
-        waits for the side stream so that the image-tower workspace is quiescent for whatever runs next.  A tower that was
-        begun and not resumed is given up: the next forward carves the workspace anew, behind the first part."""
-        if self._pending is not None:
-            self.engine.image_fwd_abandon()
-            torch.cuda.current_stream().wait_event(self._pending[2])
-            self._pending = None
-        pre, self._prefetched = self._prefetched, {}
-        for entry in pre.values():
-            torch.cuda.current_stream().wait_event(entry[1])
+        """Forget prefetched image forwards that nobody will pick up (the loop left the loader early)."""
+        self.prefetch.drop()
 
     def prompt_learner_visual_prompts(self):
         """(vpt, vpt_deep) as the image tower takes them: forward_mvlpt_proj, then vpt_proj (no dropout)."""
-        _, vpt_emb, vpt_emb_deep = self.prompt_learner.forward_mvlpt_proj(self.dtype)
-        if vpt_emb is not None:
-            vpt_emb = self.prompt_learner.vpt_proj(vpt_emb)
-            vpt_emb_deep = None if vpt_emb_deep is None else self.prompt_learner.vpt_proj(vpt_emb_deep)
-        return vpt_emb, vpt_emb_deep
-
-    def vpt_dropout_masks(self, B):
-        """Outcome of `vpt_dropout` on the prompt rows of every prompted layer, drawn in the reference's order (the shallow prompts
-        in forward_vpt, trainers/mvlpt.py:424, then layer 1, 2, ... in ImageEncoder.forward, :77), each on the rows already expanded
-        over the batch: [n_layers, B, n_vpt, width] of 0 or 1 / (1 - p), or None when nothing is dropped (p = 0, eval mode)."""
-        pl = self.prompt_learner
-        p = float(pl.vpt_dropout.p)
-        if pl.vpt_embeddings is None or p == 0.0 or not pl.training:
-            return None
-        if getattr(self, "_vpt_masks_override", None) is not None:      # tests: the masks the reference drew
-            return self._vpt_masks_override
-        n_layers = 1 + (pl.vpt_embeddings_deep.shape[0] if (pl.vpt_deep and pl.vpt_embeddings_deep is not None) else 0)
-        dev = pl.vpt_embeddings.device
-        ones = torch.ones(B, pl.vpt_n_ctx, self.clip_model.arch.vision_width, device=dev)
-        return torch.stack([pl.vpt_dropout(ones) for _ in range(n_layers)])
+        return self.projected_prompts()[1:]
 
     def forward(self, image, task=None):
-        coop_emb, vpt_emb, vpt_emb_deep = self.prompt_learner.forward_mvlpt_proj(self.dtype)
-        if vpt_emb is not None:
-            # vpt_proj (VPT.PROJECT > -1: a trainable Linear, else Identity) in front of the shallow and of every deep prompt
-            # (:424, :77): a few hundred FLOPs on [n, vpt_dim] rows, left to torch autograd like forward_mvlpt_proj
-            proj = self.prompt_learner.vpt_proj
-            vpt_emb = proj(vpt_emb)
-            if vpt_emb_deep is not None:
-                vpt_emb_deep = proj(vpt_emb_deep)
-            self.engine.set_vpt_dropout(self.vpt_dropout_masks(image.shape[0]))
+        coop_emb, vpt_emb, vpt_emb_deep = self.projected_prompts(batch=image.shape[0])
         lo = hi = None
         if self.multi_task_label_pertask:
             t = task.cpu().long() if torch.is_tensor(task) else torch.as_tensor(task).long()

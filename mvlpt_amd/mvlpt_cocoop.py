@@ -35,9 +35,10 @@ import torch
 import torch.nn as nn
 
 from .cocoop import MAX_SEQUENCES_PER_TOWER, PerImageTextCLIP
-from .model import (FrozenCLIP, PretokenizedPrompts, _CrossEntropyFn, _text_inputs, class_prompt_tables, deep_text_prompts,
-                    image_conditioned_ctx, register_class_tables)
+from .model import (FrozenCLIP, PretokenizedPrompts, VisualPromptSide, _CrossEntropyFn, _text_inputs, class_prompt_tables,
+                    class_range_tables, deep_text_prompts, image_conditioned_ctx, register_class_tables)
 from .model import MultitaskVLPromptLearner as _BasePromptLearner
+from .schedule import check_forward_is_current
 
 
 class MultitaskVLPromptLearner(_BasePromptLearner):
@@ -112,9 +113,7 @@ class _ImageTowerFn(torch.autograd.Function):
 
     @staticmethod
     def backward(fctx, dimg):
-        if fctx.generation != fctx.model._fwd_generation:
-            raise RuntimeError("backward of a stale forward: the engine holds the saved activations of the most recent "
-                               "CustomCLIP.forward only (call backward before the next forward)")
+        check_forward_is_current(fctx.model, fctx.generation)
         dvpt, ddeep = fctx.model.engine.image_bwd(dimg.contiguous())
         return None, None, dvpt.view(fctx.vpt_shape), ddeep, None
 
@@ -162,9 +161,8 @@ class _TextSideFn(torch.autograd.Function):
     def backward(fctx, dlogits):
         model = fctx.model
         eng = model.engine
-        if fctx.saved_in_engine and fctx.generation != model._fwd_generation:
-            raise RuntimeError("backward of a stale forward: the engine holds the saved activations of the most recent "
-                               "CustomCLIP.forward only (call backward before the next forward)")
+        if fctx.saved_in_engine:
+            check_forward_is_current(model, fctx.generation)
         img, ctx_shifted = fctx.saved_tensors
         dl = dlogits.contiguous() if fctx.mask is None else (dlogits * fctx.mask).contiguous()
         dimg = torch.zeros_like(img) if fctx.need_img else None
@@ -182,7 +180,7 @@ class _TextSideFn(torch.autograd.Function):
         return None, dimg, dctx, None, None, None, None
 
 
-class CustomCLIP(PerImageTextCLIP):
+class CustomCLIP(VisualPromptSide, PerImageTextCLIP):
     """trainers/mvlpt.py:517-583 for COCOOP.N_CTX != 0: `forward(image, task=None)` returns the logits [B, n_cls]."""
 
     def __init__(self, cfg, classnames, clip_model: FrozenCLIP, dm=None, pretokenized: Optional[PretokenizedPrompts] = None):
@@ -196,14 +194,7 @@ class CustomCLIP(PerImageTextCLIP):
         self.multi_task_label_pertask = cfg.DATASET.MULTITASK_LABEL_PERTASK
         self.class_index_pertask_start = self.class_index_pertask_end = None
         if self.multi_task_label_pertask:
-            # indexed by task id; sized num_classes as in the reference (:529-537); kept on the CPU
-            start, end = torch.arange(dm._num_classes), torch.arange(dm._num_classes)
-            s = 0
-            for i, task in enumerate(dm._task_names):
-                start[i] = s
-                s += len(dm._labelmap[task])
-                end[i] = s
-            self.class_index_pertask_start, self.class_index_pertask_end = start, end
+            self.class_index_pertask_start, self.class_index_pertask_end = class_range_tables(dm)      # kept on the CPU
 
     # ---- what does not apply to per-image text features
     def enable_class_sharding(self, rank: int, world: int) -> None:
@@ -228,25 +219,15 @@ class CustomCLIP(PerImageTextCLIP):
         return chunk_bounds([b - a for a, b in zip(lo, hi)],
                             lambda S: S <= MAX_SEQUENCES_PER_TOWER and eng.text_workspace_bytes(S, L, save_for_bwd) <= budget)
 
-    def vpt_dropout_masks(self, B):
-        from .model import CustomCLIP as _Base
-        return _Base.vpt_dropout_masks(self, B)
-
     def _image_side(self, image):
         """(image features [B, e], shifted contexts [B, n_ctx, ctx_dim]): the image tower with its visual prompts, then :561-563."""
-        pl = self.prompt_learner
-        _, vpt_emb, vpt_emb_deep = pl.forward_mvlpt_proj(self.dtype)             # :541 (no COOP ctx: the parameters themselves)
+        _, vpt_emb, vpt_emb_deep = self.projected_prompts(batch=image.shape[0])  # :541 (no COOP ctx: the parameters themselves)
         if vpt_emb is not None:
-            proj = pl.vpt_proj                                                   # :424, :77, as mvlpt_amd.model.CustomCLIP.forward
-            vpt_emb = proj(vpt_emb)
-            if vpt_emb_deep is not None:
-                vpt_emb_deep = proj(vpt_emb_deep)
-            self.engine.set_vpt_dropout(self.vpt_dropout_masks(image.shape[0]))
             img = _ImageTowerFn.apply(self, image, vpt_emb, vpt_emb_deep, torch.is_grad_enabled())
         else:
             img = self.engine.image_fwd(image, None, None, save_for_bwd=False)   # frozen, prompt-free image tower
         imf = img / img.norm(dim=-1, keepdim=True)                               # :561 (meta_net's input)
-        return img, pl(imf)                                                      # :563, :361-364
+        return img, self.prompt_learner(imf)                                     # :563, :361-364
 
     @torch.no_grad()
     def image_contexts(self, image) -> torch.Tensor:

@@ -128,12 +128,6 @@ def build_lr_scheduler(optim, optim_cfg):
     return _ConstantWarmupCosine(optim, optim_cfg)
 
 
-# Enqueue order of MVLPT.forward_backward: the next batch's image tower BEFORE (1) or behind (0, default) this step's own forward.
-# Measured (NOTES_experiments.md, round 4): enqueued early the image stream never waits for a step's logits, but the step gets no
-# shorter — 14.18-14.21 vs 14.11-14.12 ms in the same run: what bounds the step is the work of the two towers, not that bubble.
-_PREFETCH_EARLY = os.environ.get("MVLPT_PREFETCH_EARLY", "0") != "0"
-
-
 def prefetch_split(cfg) -> tuple:
     """(stop_block, cu_cap) of the prefetch split: MVLPT_PREFETCH_SPLIT=k:c when set (any backbone), else TRAINER.MVLPT.PREFETCH_SPLIT
     on the backbones of TRAINER.MVLPT.PREFETCH_SPLIT_TOWERS and (0, 0) on every other."""
@@ -484,6 +478,10 @@ class MVLPT(TrainerX):
         self._dm_arg, self._sd_arg = dm, clip_state_dict
         super().__init__(cfg)
 
+    # the look-ahead state: (batch, its parse_batch_train result) of batch i+1, parsed and uploaded during step i.  (Declared on the
+    # class, not in __init__: tests/test_train_step_fixture.py assembles a trainer without running it.)
+    _parsed_ahead = None
+
     def check_cfg(self, cfg):
         """:835-836 accepts fp16 | fp32 | amp.  Mapping onto the MI355X engine ("Precision modes"):
           fp16 : fp16 MFMA operands, fp32 accumulation / LayerNorm / softmax / residual stream; towers that carry a
@@ -569,40 +567,32 @@ class MVLPT(TrainerX):
     def forward_backward(self, batch):
         """trainers/mvlpt.py:910-951.  When the loop has read one batch ahead (`self.next_batch`, TrainerX.run_epoch) and
         the method has no visual prompts, the image features of the following step are computed underneath this step's
-        text-tower backward (model.prefetch_image_features)."""
+        text-tower backward (model.prefetch_image_features).  Two schedules: the whole tower of batch i+1 behind this step's loss,
+        or (prefetch split, TRAINER.MVLPT.PREFETCH_SPLIT) its first blocks ahead of this step's forward and the rest behind the loss."""
         next_batch = self.next_batch if self.cfg.TRAINER.MVLPT.STEP_PIPELINING else None
-        ahead = getattr(self, "_parsed_ahead", None)
+        ahead = self._parsed_ahead
+        self._parsed_ahead = None
         if ahead is not None and ahead[0] is batch:
             image, label, tasks_ = ahead[1]          # parsed (and uploaded) during the previous step
         else:
             image, label, tasks_ = self.parse_batch_train(batch)
-        self._parsed_ahead = None
         if len(label.shape) > 1 and label.shape[-1] > 1:                # :914-916
             label = label.float()
             label = label / label.sum(dim=-1, keepdim=True)
-        early = next_batch is not None and _PREFETCH_EARLY
-        # prefetch split (TRAINER.MVLPT.PREFETCH_SPLIT): only the first blocks of batch i+1's tower go in front of this step's forward,
-        # on capped grids beside the text forward; the rest follows behind the cross-entropy.  Only when this step's own features
-        # are there already (from the second step on): a forward that has to run its tower first gains nothing from it.
-        stop_block, cu_cap = getattr(self.model, "prefetch_split", (0, 0))
-        split = (next_batch is not None and not early and stop_block > 0 and self.model.split_active()
+        # prefetch split: the first blocks of batch i+1's tower go in front of this step's forward, on capped grids beside the text
+        # forward.  Only when this step's own features are there already (from the second step on): a forward that has to run its
+        # tower first gains nothing from it.
+        stop_block, cu_cap = self.model.prefetch_split
+        split = (next_batch is not None and stop_block > 0 and self.model.split_active()
                  and self.model.has_prefetched(image))
-        if early or split:
-            # batch i+1: its H2D copy and its image tower are enqueued BEFORE step i's own forward, so the image stream
-            # goes from one batch straight into the next while this step's text tower, head and optimizer run beside it
-            parsed = self.parse_batch_train(next_batch)
-            self._parsed_ahead = (next_batch, parsed)
-            if split:
-                self.model.prefetch_image_features(parsed[0], stop_block=stop_block, cu_cap=cu_cap)
-            else:
-                self.model.prefetch_image_features(parsed[0])
+        if split:
+            next_image = self.parse_ahead(next_batch)
+            self.model.prefetch_image_features(next_image, stop_block=stop_block, cu_cap=cu_cap)
         output = self.model(image, task=tasks_)
         loss = self.model.cross_entropy(output, label)                  # F.cross_entropy (:931) as a HIP kernel
-        if next_batch is not None and not early:                        # the H2D copy of batch i+1 and its image tower overlap this step's backward
-            if not split:
-                parsed = self.parse_batch_train(next_batch)
-                self._parsed_ahead = (next_batch, parsed)
-            self.model.prefetch_image_features(parsed[0])               # (prefetch split: the rest of the tower begun above)
+        if next_batch is not None:
+            # the H2D copy of batch i+1 (unless the split made it above) and its image tower, or the rest of it, overlap this step's backward
+            self.model.prefetch_image_features(next_image if split else self.parse_ahead(next_batch))
         self.model_backward_and_update(loss)
         # device tensors: no .item() sync inside the step (the reference syncs twice per step, :941-942)
         loss_summary = {"loss": loss.detach(), "acc": self.model.last_ncorrect[0] * (100.0 / output.shape[0])}
@@ -611,6 +601,11 @@ class MVLPT(TrainerX):
         if (self.batch_idx + 1) == self.num_batches:
             self.update_lr()
         return loss_summary
+
+    def parse_ahead(self, next_batch):
+        """Parse (upload) the batch of the following step now and keep it for that step; returns its image tensor."""
+        self._parsed_ahead = (next_batch, self.parse_batch_train(next_batch))
+        return self._parsed_ahead[1][0]
 
     def end_of_epoch_loop(self):
         super().end_of_epoch_loop()

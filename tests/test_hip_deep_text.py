@@ -310,12 +310,12 @@ def test_eval_text_cache_follows_ctx_deep(ref, clips):
     image, _ = _batch(ref.arch)
     with torch.no_grad():
         a = model(image.to(DEV)).clone()
-        ver = model._eval_text_cache[0]
+        ver = model.text_cache.eval_key
         b = model(image.to(DEV)).clone()
-        assert model._eval_text_cache[0] == ver and torch.equal(a, b)
+        assert model.text_cache.eval_key == ver and torch.equal(a, b)
         model.prompt_learner.ctx_deep.mul_(0.5)
         c = model(image.to(DEV))
-    assert model._eval_text_cache[0] != ver and not torch.equal(a, c)
+    assert model.text_cache.eval_key != ver and not torch.equal(a, c)
 
 
 def test_class_sharding_is_refused(clips):

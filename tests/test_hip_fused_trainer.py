@@ -205,16 +205,16 @@ def test_eval_text_cache_is_refreshed_after_a_fused_step(tmp_path):
     acc = tr.test()
     assert 0.0 <= acc <= 100.0
     model = tr.model
-    assert model._eval_text_cache is not None
-    ver0, txt0 = model._eval_text_cache[0], model._eval_text_cache[1].clone()
+    assert model.text_cache.eval_key is not None
+    ver0, txt0 = model.text_cache.eval_key, model.text_cache.eval_features.clone()
     tr.test()
-    assert model._eval_text_cache[0] == ver0
+    assert model.text_cache.eval_key == ver0
     tr.set_model_mode("train")
     tr.num_batches, tr.batch_idx = 10, 0
     tr.forward_backward(tr.train_loader_x[0])
     tr.test()
-    assert model._eval_text_cache[0] != ver0
-    assert not torch.equal(model._eval_text_cache[1], txt0)       # ... and the text features are those of the NEW prompts
+    assert model.text_cache.eval_key != ver0
+    assert not torch.equal(model.text_cache.eval_features, txt0)       # ... and the text features are those of the NEW prompts
 
 
 def test_a_prompt_tensor_without_a_gradient_is_not_touched(tmp_path):

@@ -308,7 +308,7 @@ def test_trainer_prefetch_split_is_transparent_and_inert(tmp_path):
     tr, calls1, out1, p1 = _run_three_steps(tmp_path, (1, 8))
     # step 0 runs its own tower and prefetches batch 1 in one piece; step 1 begins batch 2 ahead of its forward and resumes it
     assert calls1 == {"begin": 1, "resume": 1, "whole": 2}, calls1
-    assert tr.model._pending is None and not tr.model._prefetched
+    assert not tr.model.prefetch.begun and not tr.model.prefetch.finished
     assert torch.equal(out0[0], out1[0]) and torch.equal(out0[1], out1[1])
     assert set(p0) == set(p1)
     for k in p0:
@@ -348,9 +348,9 @@ def test_begin_without_resume_leaves_no_stale_workspace(tmp_path):
         logits_b = model(img_b).clone()
     torch.cuda.synchronize()
     # the loop leaves the loader after the first part of batch a's tower: the trainer's epilogue gives it up
-    assert model.prefetch_image_features(img_a, stop_block=1, cu_cap=8) and model._pending is not None
+    assert model.prefetch_image_features(img_a, stop_block=1, cu_cap=8) and model.prefetch.begun
     tr.end_of_epoch_loop()
-    assert model._pending is None and not eng.image_fwd_pending()
+    assert not model.prefetch.begun and not eng.image_fwd_pending()
     assert torch.equal(eng.image_fwd(img_b), want_b)
     # ... and a forward that meets a tower begun for another tensor finishes that one first, then runs its own
     assert model.prefetch_image_features(img_a, stop_block=1, cu_cap=8)
@@ -358,8 +358,8 @@ def test_begin_without_resume_leaves_no_stale_workspace(tmp_path):
         got = model(img_b)
     torch.cuda.synchronize()
     assert torch.equal(got, logits_b)
-    assert model._pending is None and model.has_prefetched(img_a)
-    feat_a, ev, _ = model._prefetched[(img_a.data_ptr(), tuple(img_a.shape), img_a._version)]
+    assert not model.prefetch.begun and model.has_prefetched(img_a)
+    feat_a, ev = model.prefetch.get(img_a).features, model.prefetch.get(img_a).ready
     ev.synchronize()
     assert torch.equal(feat_a, want_a)
     model.drop_prefetch()

@@ -236,10 +236,10 @@ def test_cfg3_vpt_deep_1000_classes_batch_256():
         return logits.detach().clone(), float(loss.detach()), _grads(model)
 
     l0, s0, g0 = run()
-    txt = model._const_text_features
+    txt = model.text_cache.constants
     assert txt is not None and txt.shape == (1000, 512), "no text context: the 1000 text features are constants and must be cached"
     l1, s1, g1 = run()
-    assert model._const_text_features is txt, "cached text features must be reused, not recomputed every step"
+    assert model.text_cache.constants is txt, "cached text features must be reused, not recomputed every step"
     assert torch.equal(l0, l1) and s0 == s1 and all(torch.equal(g0[k], g1[k]) for k in g0), "bitwise deterministic"
     assert set(g0) == {"vpt_embeddings", "vpt_embeddings_deep"} and g0["vpt_embeddings_deep"].shape == (11, 8, 768)
     _, s4, g4 = run(4.0)

@@ -67,15 +67,15 @@ def test_eval_accuracy_and_text_cache(tmp_path):
     acc = tr.test()
     assert 0.0 <= acc <= 100.0 and set(tr.last_task_results) <= {"task0", "task1", "task2"}
     model = tr.model
-    assert model._eval_text_cache is not None
-    ver0 = model._eval_text_cache[0]
+    assert model.text_cache.eval_key is not None
+    ver0 = model.text_cache.eval_key
     tr.test()
-    assert model._eval_text_cache[0] == ver0                    # prompts unchanged -> text tower not re-run
+    assert model.text_cache.eval_key == ver0                    # prompts unchanged -> text tower not re-run
     tr.set_model_mode("train")
     tr.num_batches, tr.batch_idx = 10, 0
     tr.forward_backward(tr.train_loader_x[0])                    # SGD step bumps the parameter versions
     tr.test()
-    assert model._eval_text_cache[0] != ver0
+    assert model.text_cache.eval_key != ver0
 
 
 def test_elevater_eval_branch_uses_the_task_metrics(tmp_path):
@@ -168,10 +168,10 @@ def test_lookahead_reaches_a_plain_dassl_loop(tmp_path):
     # leaving the loop early drops the pending prefetch instead of leaving it for an unrelated forward
     it = iter(tr.train_loader_x)
     tr.forward_backward(next(it))
-    assert len(tr.model._prefetched) == 1
+    assert len(tr.model.prefetch.finished) == 1
     it.close()
     tr.end_of_epoch_loop()
-    assert not tr.model._prefetched and tr._parsed_ahead is None and tr.next_batch is None
+    assert not tr.model.prefetch.finished and tr._parsed_ahead is None and tr.next_batch is None
 
 
 @pytest.mark.parametrize("prec", ["fp16", "amp", "fp32"])

@@ -124,6 +124,81 @@ def test_stale_backward_is_refused():
     assert model.prompt_learner.ctx.grad is not None
 
 
+def _count_engine_calls(model, names=("image_fwd", "text_fwd")):
+    """Wrap the OracleEngine's entries of `model`: returns the list every call's name is appended to."""
+    calls = []
+    for name in names:
+        orig = getattr(model.engine, name)
+        setattr(model.engine, name, lambda *a, _o=orig, _n=name, **k: (calls.append(_n), _o(*a, **k))[1])
+    return calls
+
+
+def test_text_feature_cache_states(monkeypatch):
+    """mvlpt_amd.schedule.TextFeatureCache: constants without a text context, one tower per parameter version in evaluation, a tower
+    per training forward."""
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)      # the oracle engine runs on the host: no second stream
+    img, label = torch.randn(2, 3, 32, 32), torch.tensor([0, 1])
+    # constants: no text context (VPT only) -> the text tower runs once over two training steps
+    from mvlpt_amd.config import get_cfg_default
+    from mvlpt_amd.model import CustomCLIP
+    from mvlpt_amd.weights import ARCHS, make_state_dict
+    from tests.fake_engine import OracleFrozenCLIP
+    cfg = get_cfg_default()
+    cfg.INPUT.SIZE = (32, 32)
+    cfg.TRAINER.MVLPT.COOP.N_CTX, cfg.TRAINER.MVLPT.VPT.N_CTX = 0, 2
+    torch.manual_seed(3)
+    vpt = CustomCLIP(cfg, ["dog", "grand piano", "sea horse"], OracleFrozenCLIP(make_state_dict(ARCHS["tiny"], seed=5), ARCHS["tiny"]))
+    calls = _count_engine_calls(vpt)
+    opt = torch.optim.SGD(vpt.prompt_learner.parameters(), lr=0.1)
+    for _ in range(2):
+        opt.zero_grad()
+        vpt.cross_entropy(vpt(img), label).backward()
+        opt.step()
+    assert calls.count("text_fwd") == 1 and calls.count("image_fwd") == 2, calls
+    assert vpt.text_cache.constants is not None and vpt.text_cache.eval_key is None
+    # evaluation: unchanged prompts -> one tower; again after an optimizer step.  Training: always.
+    model, _ = _tiny_oracle_model()
+    calls = _count_engine_calls(model)
+    opt = torch.optim.SGD(model.prompt_learner.parameters(), lr=0.1)
+    model.prompt_learner.eval()
+    with torch.no_grad():
+        a, b = model(img), model(img)
+    assert calls.count("text_fwd") == 1 and torch.equal(a, b)
+    model.prompt_learner.train()
+    for k in (2, 3):
+        opt.zero_grad()
+        model.cross_entropy(model(img), label).backward()
+        assert calls.count("text_fwd") == k
+    opt.step()
+    model.prompt_learner.eval()
+    with torch.no_grad():
+        c, d = model(img), model(img)
+    assert calls.count("text_fwd") == 4 and torch.equal(c, d) and not torch.equal(a, c)
+    assert model.text_cache.constants is None
+
+
+def test_inline_order_is_image_then_text(monkeypatch):
+    """With no second stream (no GPU) a forward runs the image tower, then the text tower: replicated and class-sharded alike."""
+    from mvlpt_amd.model import ClassShard, class_shard_bounds
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    img = torch.randn(2, 3, 32, 32)
+    model, _ = _tiny_oracle_model()
+    assert model.text_stream is None
+    calls = _count_engine_calls(model)
+    model(img)
+    assert calls == ["image_fwd", "text_fwd"]
+
+    class OneRankOfTwo(ClassShard):      # the gather of a rank that owns classes [0, 2) of 3, with no process group
+        def gather(self, loc):
+            calls.append("gather")
+            return torch.cat([loc, torch.zeros(1, loc.shape[1])])
+
+    model._class_shard = OneRankOfTwo(0, class_shard_bounds(3, 2), torch.device("cpu"))
+    del calls[:]
+    model(img)
+    assert calls == ["image_fwd", "text_fwd", "gather"]
+
+
 def test_init_weights_drop_class_buffers_and_mismatched_shapes(tmp_path):
     """MODEL.INIT_WEIGHTS from a checkpoint with ANOTHER class count (trainers/mvlpt.py:864-865 + Dassl
     load_pretrained_weights): ctx is taken, token_prefix / token_suffix are not."""

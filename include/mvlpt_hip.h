@@ -278,6 +278,18 @@ int mvlpt_set_text_act_ckpt(void* handle, int segments);
  * checkpoint_sequential rule as above): *n_segments = k, first_layer[i] = first block of segment i for i < k (HOST array of `cap`
  * entries; cap < k: MVLPT_ERR_ARG, *n_segments still set).  Segments 0 .. k-2 are checkpointed, segment k-1 is saved. */
 int mvlpt_text_act_ckpt_plan(void* handle, int32_t* first_layer, int cap, int* n_segments);
+/* Gradient length of the text tower: the backward processes only the leading grad_len positions of every sequence.  The only
+ * gradient entering the tower sits on each sequence's EOT row, the attention is causal and LayerNorm, MLP and activation act row by
+ * row, so in every block the gradient of a position behind its sequence's EOT is exactly 0.0: with max(eot) < grad_len the backward
+ * skips rows of zeros and dctx / dctx_deep keep their bits.  The forward is untouched (every position is evaluated and saved, at the
+ * pitch L); the gradient buffers are compact [C, grad_len, .].  An engine setting like mvlpt_set_text_act_ckpt; the default is every
+ * position.  grad_len outside [MVLPT_TEXT_MIN_L, context_length] or max_eot < 0: MVLPT_ERR_ARG.  Takes effect at the next saving
+ * text forward (plain, deep or ranged), which runs under min(grad_len, L) and records it, so a call between a forward and its
+ * backward does not change that backward.  max_eot is the CALLER'S largest entry of the `eot` tables it will pass (a device array
+ * the engine does not read back): a saving forward whose gradient length is below L and not above max_eot returns MVLPT_ERR_ARG before
+ * anything is launched, and a caller whose tables change calls this again.  An understated max_eot gives a wrong gradient, never an
+ * out-of-bounds access.  mvlpt_text_workspace_bytes keeps reporting the figure of the full length, an upper bound. */
+int mvlpt_set_text_grad_len(void* handle, int grad_len, int max_eot);
 
 /* CLIP.encode_text (clip/model.py:343-356: token_embedding(text) + positional_embedding -> transformer -> ln_final ->
  * x[arange, text.argmax(-1)] @ text_projection) for S sequences of token ids: what the zero-shot trainers feed (trainers/zsclip.py:45-49,
@@ -474,6 +486,21 @@ int mvlpt_op_layernorm_fwd_ex(int out_dtype, const float* x, int row_mul, const 
 int mvlpt_op_layernorm_bwd_ex(int dtype, const void* dy, int dy_dtype, const float* x, int row_mul, const float* gamma, const float* resid,
                               float* out32, void* out16, int rows, int d, int split, mvlpt_stream_t stream);
 int mvlpt_op_layernorm_route(int rows, int d, mvlpt_stream_t stream, int* nv, int* grid);
+/* The launches of the text backward under a gradient length (mvlpt_set_text_grad_len), kernel level.  A saved forward tensor holds
+ * sequences of seq_pitch rows; the gradient side holds the leading grad_len rows of each, compact, and row r of it belongs to saved
+ * row (r / grad_len) * seq_pitch + r % grad_len.  grad_len == seq_pitch is the plain launch.
+ * gemm_gelubwd_rows: mvlpt_op_gemm_ex with epi 3 / 6 (no bias, resid, out2), `aux` [., N] read through the map; M % grad_len == 0,
+ *   grad_len >= 3.  layernorm_bwd_rows: mvlpt_op_layernorm_bwd_ex with row_mul 1 and `x` alone read through the map (dy, resid, out32,
+ *   out16 at row r); rows % grad_len == 0.  attention_bwd_rows: the causal attention backward over positions 0 .. grad_len-1 of N
+ *   sequences: qkv / out / lse are saved tensors ([N seq_pitch, .], lse [N H seq_pitch]), dout / dqkv / delta compact
+ *   ([N grad_len, .], [N H grad_len]); pair != 0: the pair kernels (mvlpt_op_attention32_bwd, lo8 != 0: _mixed; grad_len <= 80), else
+ *   mvlpt_op_attention_bwd's (grad_len <= 256). */
+int mvlpt_op_gemm_gelubwd_rows(int dtype, int epi, const void* A, const void* Bt, int M, int N, int K, const void* aux, void* out, int a_split,
+                               int lda, int ldo, int ldb, int w8_exp, int out_lo8, int grad_len, int seq_pitch, mvlpt_stream_t stream);
+int mvlpt_op_layernorm_bwd_rows(int dtype, const void* dy, int dy_dtype, const float* x, const float* gamma, const float* resid,
+                                float* out32, void* out16, int rows, int d, int split, int grad_len, int seq_pitch, mvlpt_stream_t stream);
+int mvlpt_op_attention_bwd_rows(int dtype, int pair, int lo8, const void* qkv, const void* out, const void* dout, const float* lse,
+                                float* delta, void* dqkv, int N, int grad_len, int seq_pitch, int H, mvlpt_stream_t stream);
 int mvlpt_op_cast_ex(int dtype, const float* in, void* out, int64_t rows, int d, int format, const float* scale_dev, mvlpt_stream_t stream);
 int mvlpt_op_cast_to_f32(int in_dtype, const void* in, float* out, int64_t n, mvlpt_stream_t stream);
 int mvlpt_op_pack_weight(int dtype, const float* w32, int rows, int cols, int transposed, int ld_out, void* out, mvlpt_stream_t stream);

@@ -26,7 +26,7 @@ from .config import read_activation, read_vision_head_width
 # DEFAULT_MAX_TEXT_WORKSPACE_BYTES: workspace budget of the CoCoOp text tower (not a reference key).  A chunk is the largest number of
 # images whose text tower fits it (mvlpt_text_workspace_bytes); ViT-B/16 with 100 classes needs 1.67 GiB per image for a training step.
 from .model import (DEFAULT_MAX_TEXT_WORKSPACE_BYTES, MAX_SEQUENCES_PER_TOWER, FrozenCLIP, PretokenizedPrompts, _text_inputs,
-                    apply_text_act_ckpt, class_prompt_tables, image_conditioned_ctx, register_class_tables)
+                    apply_text_act_ckpt, apply_text_grad_len, class_prompt_tables, image_conditioned_ctx, register_class_tables)
 from .trainer import MVLPT, TrainerX, refuse_wide_heads
 from .weights import get_arch, make_state_dict
 
@@ -72,6 +72,7 @@ class _CoCoOpLossFn(torch.autograd.Function):
         suffix, layout = _text_inputs(model, pl, pl.n_ctx)
         B = ctx_shifted.shape[0]
         step = model.images_per_chunk(B, layout.shape[1], save_for_bwd=True)
+        apply_text_grad_len(model, pl)      # the backwards below stop behind the class table's largest EOT position
         dctx = torch.empty_like(ctx_shifted)
         loss = torch.zeros(1, device=ctx_shifted.device, dtype=torch.float32)
         ncorrect = torch.zeros(1, device=ctx_shifted.device, dtype=torch.float32)
@@ -112,6 +113,7 @@ class PerImageTextCLIP(nn.Module):
         self.logit_scale_exp = float(clip_model.logit_scale.exp())
         self.dtype = clip_model.dtype
         self.trim_text_to_eot = False        # mvlpt_amd.model.CustomCLIP's switch, same default
+        self.text_grad_to_eot = bool(cfg.TRAINER.MVLPT.get("TEXT_GRAD_TO_EOT", True))      # likewise
         self.max_text_workspace_bytes = DEFAULT_MAX_TEXT_WORKSPACE_BYTES
         # Precision: the image features are meta_net's input and every text row carries a gradient, so under the
         # default mode (split operands only in towers kept for a backward) the ViT-B/16 fixture's ctx / meta_net gradients land at

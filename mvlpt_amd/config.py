@@ -138,6 +138,10 @@ def get_cfg_default() -> CfgNode:
         # the backbones (MODEL.BACKBONE.NAME) PREFETCH_SPLIT applies to; every other tower runs in one piece.  Measured: ViT-B/16 -2.1 % at
         # B = 256 and at B = 128, but ViT-B/32 (B = 256) +2.1 % and ViT-L/14 (B = 128) +1.0 % with the same setting.  (): every backbone.
         PREFETCH_SPLIT_TOWERS=("ViT-B/16",),
+        # not in the reference: the text backward processes only the positions up to the largest EOT of the class table (the rows
+        # behind a sequence's EOT carry an exactly zero gradient: Engine.set_text_grad_len).  The forward still evaluates every
+        # position and every result keeps its bits; False runs the backward over all positions (A/B runs).
+        TEXT_GRAD_TO_EOT=True,
     )
     # trainers/cocoop.py's own keys (train.py:125-128), read by mvlpt_amd.cocoop (--trainer CoCoOp)
     cfg.TRAINER.COCOOP = CN(N_CTX=16, CTX_INIT="", PREC="fp16")

@@ -330,10 +330,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
   constexpr int DSB = NKT > 16 ? 4 : (NKT / 2 < 8 ? NKT / 2 : 8);   // 32-key blocks of dS^T held at a time (register budget)
   char* sK = smem;
   char* sV = smem + LP * 128;
-  const int L = a.L, H = a.H, d = H * 64;
+  // L: the positions that carry a gradient (dout, delta, dqkv rows per sequence); Ls: the pitch of the saved tensors (AttnBwdArgs::Ls)
+  const int L = a.L, Ls = a.Ls > 0 ? a.Ls : a.L, H = a.H, d = H * 64;
   const int n = blockIdx.x / H, h = blockIdx.x % H;
   const size_t ld = (size_t)3 * d;
-  const T* base = (const T*)a.qkv + (size_t)n * L * ld + h * 64;
+  const T* base = (const T*)a.qkv + (size_t)n * Ls * ld + h * 64;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fg = lane >> 4;
   const int nqt = (L + 15) >> 4;
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
     const size_t tok = (size_t)n * L + qr;
     const T* qp = base + (size_t)qr * ld + fg * 8;
     const T* dop = (const T*)a.dout + tok * d + h * 64 + fg * 8;
-    const T* op = (const T*)a.out + tok * d + h * 64 + fg * 8;
+    const T* op = (const T*)a.out + ((size_t)n * Ls + qr) * d + h * 64 + fg * 8;
     r.q0 = *(const v8*)qp; r.q1 = *(const v8*)(qp + 32);
     r.do0 = *(const v8*)dop; r.do1 = *(const v8*)(dop + 32);
     const v8 o0 = *(const v8*)op, o1 = *(const v8*)(op + 32);
@@ -355,7 +356,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) t += to_f32<T>(r.do0[e]) * to_f32<T>(o0[e]) + to_f32<T>(r.do1[e]) * to_f32<T>(o1[e]);
     r.dl = quad_sum(t);                                        // delta = rowsum(dO * O)
-    r.lse = a.lse[((size_t)n * H + h) * L + qr];
+    r.lse = a.lse[((size_t)n * H + h) * Ls + qr];
     return r;
   };
   constexpr bool PRELOAD = NKT <= 16;
@@ -451,10 +452,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs a) {
   char* sdO = smem + LP * 128;
   float* sLse = (float*)(smem + 2 * LP * 128);
   float* sDel = sLse + LP;
-  const int L = a.L, H = a.H, d = H * 64;
+  const int L = a.L, Ls = a.Ls > 0 ? a.Ls : a.L, H = a.H, d = H * 64;      // (as in attn_bwd_dq_kernel)
   const int n = blockIdx.x / H, h = blockIdx.x % H;
   const size_t ld = (size_t)3 * d;
-  const T* base = (const T*)a.qkv + (size_t)n * L * ld + h * 64;
+  const T* base = (const T*)a.qkv + (size_t)n * Ls * ld + h * 64;
   const T* dob = (const T*)a.dout + (size_t)n * L * d + h * 64;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fg = lane >> 4;
@@ -477,7 +478,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs a) {
     for (int i = 0; i < MAXK; ++i) pre[i] = load_kv(wave + 4 * i);
   }
   for (int i = threadIdx.x; i < LP; i += 256) {
-    sLse[i] = i < L ? a.lse[((size_t)n * H + h) * L + i] : 0.f;
+    sLse[i] = i < L ? a.lse[((size_t)n * H + h) * Ls + i] : 0.f;
     sDel[i] = i < L ? a.delta[((size_t)n * H + h) * L + i] : 0.f;
   }
   stage_rows_dma<T>(sQ, base, ld, L, LP, wave, lane);
@@ -731,8 +732,10 @@ hipError_t launch_attn_fwd(int dtype, const AttnArgs& a_, hipStream_t s, hipEven
 }
 hipError_t launch_attn_bwd(int dtype, const AttnBwdArgs& a, hipStream_t s) {
   if (a.L <= 0 || a.L > attn_max_len() || a.N <= 0) return hipErrorInvalidValue;
+  // a gradient shorter than the saved sequences (AttnBwdArgs::Ls): causal, resident kernels only
+  if (a.Ls > 0 && a.Ls != a.L && (a.Ls < a.L || !a.causal || use_stream(a.L))) return hipErrorInvalidValue;
   if (use_stream(a.L)) return launch_attn_bwd_stream(dtype, a, s);
-  const int nkt = nkt_for(a.L);
+  const int nkt = nkt_for(a.L);      // (key tiles of the positions that carry a gradient)
   if (dtype == DT_F16) return a.causal ? bwd_n<f16, true>(nkt, a, s) : bwd_n<f16, false>(nkt, a, s);
   if (dtype == DT_BF16) return a.causal ? bwd_n<bf16, true>(nkt, a, s) : bwd_n<bf16, false>(nkt, a, s);
   return hipErrorInvalidValue;

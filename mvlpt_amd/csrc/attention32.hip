@@ -667,9 +667,10 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
   char *I0h = sm, *I0l = sm + TIMG, *I1h = sm + 2 * TIMG, *I1l = sm + 3 * TIMG;
   using v8 = typename Vec<T>::v8;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, fg = lane >> 4;
-  const int n = blockIdx.y, h = blockIdx.x, L = a.L, d = a.H * 64;
+  // L: the positions that carry a gradient (dO, dQKV rows per sequence); Ls: the pitch of the saved tensors (Attn32BwdArgs::Ls)
+  const int n = blockIdx.y, h = blockIdx.x, L = a.L, Ls = a.Ls > 0 ? a.Ls : a.L, d = a.H * 64;
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d, gld = 2 * (size_t)d;
-  const T* base = (const T*)a.qkv_split + (size_t)n * L * ld + h * 64;
+  const T* base = (const T*)a.qkv_split + (size_t)n * Ls * ld + h * 64;
   const T* gbase = (const T*)a.dout_split + (size_t)n * L * gld + h * 64;
 #ifdef MVLPT_ATTN_TRACE
   int atr_n = 0;
@@ -677,7 +678,7 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
   MVLPT_ATRB(40);
   stage_short<T>(I0h, I0l, base + d, lo, ld, L, wave, lane);          // K
   stage_short<T>(I1h, I1l, base + 2 * d, lo, ld, L, wave, lane);      // V
-  const size_t stat0 = ((size_t)n * a.H + h) * L;
+  const size_t stat0 = ((size_t)n * a.H + h) * Ls;
   const int nt = (L + 15) >> 4;
   const int row = wave * 16 + fr, rc = row < L ? row : L - 1;     // own row: query in phase A, key in phase B
   v8 Qh[2], Ql[2], Gh[2], Gl[2], Kh[2], Kl[2], Vh[2], Vl[2];
@@ -686,7 +687,7 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
   float dl = 0.f;       // delta = rowsum(dO * O) of the own query row
   {
     // dO of the own row is in registers already (Gh, Gl): O in the same fragment layout, no second read of dO
-    const T* orow = (const T*)a.out_split + ((size_t)n * L + rc) * gld + h * 64;
+    const T* orow = (const T*)a.out_split + ((size_t)n * Ls + rc) * gld + h * 64;
     dl = delta_part<T>(orow, d, h * 64, fg, a.lo8, Gh, Gl);
     dl = quad_sum(dl);
   }
@@ -1297,6 +1298,8 @@ static hipError_t fwd_t(const Attn32Args& a, hipStream_t s) {
 }
 template <typename T>
 static hipError_t bwd_t(const Attn32BwdArgs& a, hipStream_t s) {
+  // a gradient shorter than the saved sequences: the short causal kernel only (the others take every position)
+  if (a.Ls > 0 && a.Ls != a.L && (a.Ls < a.L || a.L > SROWS || !a.causal)) return hipErrorInvalidValue;
   if (a.L <= SROWS) {
     dim3 grid(a.H, a.N), block(SNT * 64);
     if (a.causal) hipLaunchKernelGGL((attn32t_bwd_kernel<T, true>), grid, block, 0, s, a);

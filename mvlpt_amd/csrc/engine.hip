@@ -151,6 +151,10 @@ struct TowerState {
   int wide_pitch = 0;                    // split towers: row pitch of a16 / du16 (0: dense)
   int xs = 0;                            // GEMM A operands: 0 single 16-bit, 1 16-bit pair, 2 mixed pair (hi + e5m2 residual byte)
   int N = 0, L = 0, d = 0, H = 0, layers = 0;
+  // Gradient length (mvlpt_set_text_grad_len): the leading positions of every sequence a backward processes.  Every gradient buffer
+  // (dx32 .. delta) is compact [N, Lg, .]; the saved forward tensors keep the pitch L and are read through the row map
+  // r -> (r / Lg) * L + r % Lg.  Lg == L: every position (the image tower, and the text tower's default).
+  int Lg = 0;
   int hw = 64;                           // head width d / H: 64, or a wide-headed image tower's 80 / 96 / 112 / 128 (attention_wide.hip)
   std::vector<float*> x;                 // 2*layers+1 entries (all equal when !saved)
   std::vector<void*> qkv, attn, u;       // per layer (all equal when !saved)
@@ -256,6 +260,8 @@ struct Engine {
   int fold_mode = 2;    // LayerNorm folding: 0 off, 1 image tower, 2 both towers (MVLPT_LN_FOLD, mvlpt_set_ln_fold)
   int act = ACT_QUICKGELU;    // the MLP activation of both towers (mvlpt_set_activation; DESIGN.md "Exact GELU")
   int text_act_ckpt = 1;      // segments of the text tower's activation checkpointing (mvlpt_set_text_act_ckpt; 1: everything is saved)
+  // mvlpt_set_text_grad_len: gradient length of the next saving text forwards (0: every position) and the caller's largest EOT position
+  int text_grad_len = 0, text_max_eot = 0;
   int fold_min_rows = 1024;   // towers with fewer token rows keep the stand-alone LayerNorm (a handful of tiles: nothing to win)
   bool fold_ready = false;
   // packed residual stream: the fp16 image tower without prompts and without a backward carries x as hi (fp16, at the
@@ -355,9 +361,9 @@ struct Fold {
 };
 hipError_t gemm(Engine* E, int epi, const void* A, WRef Bt, int M, int N, int K, const float* bias, const void* aux,
                 const float* resid, void* out, void* out2, hipStream_t s, int dtype = -1, int a_split = 0, const Fold* f = nullptr,
-                int lda = 0, int ldo = 0) {
+                int lda = 0, int ldo = 0, int aux_seq = 0, int aux_pitch = 0) {
   GemmArgs g{A, Bt.p, M, N, K, bias, aux, resid, out, out2};
-  g.a_split = a_split; g.ldb = Bt.ld; g.w8_exp = Bt.e8; g.lda = lda; g.ldo = ldo;
+  g.a_split = a_split; g.ldb = Bt.ld; g.w8_exp = Bt.e8; g.lda = lda; g.ldo = ldo; g.aux_seq = aux_seq; g.aux_pitch = aux_pitch;
   if (f) {
     g.ln_gamma = f->ln_gamma; g.ln_x16 = f->ln_x16; g.ln_split = f->ln_split; g.ln_part = f->ln_part; g.ln_ntp = f->ln_ntp;
     g.fold_part = f->fold_part; g.fold_colsum = f->fold_colsum; g.fold_ntp = f->fold_ntp; g.fold_nt = f->fold_nt;
@@ -387,9 +393,10 @@ hipError_t ln_fwd(Engine* E, int out_dt, const float* x, const int32_t* idx, int
   return launch_ln_fwd(out_dt, a, s);
 }
 hipError_t ln_bwd(Engine* E, const void* dy, int dy_dtype, const float* x, const int32_t* idx, int row_mul, const LNp& p,
-                  const float* resid, float* out32, void* out16, int rows, int d, hipStream_t s, int dtype = -1, int split = 0) {
+                  const float* resid, float* out32, void* out16, int rows, int d, hipStream_t s, int dtype = -1, int split = 0,
+                  int x_seq = 0, int x_pitch = 0) {
   LnBwdArgs a{dy, dy_dtype, x, idx, row_mul, p.g, resid, out32, out16, rows, d};
-  a.split = split;
+  a.split = split; a.x_seq = x_seq; a.x_pitch = x_pitch;
   ProfScope ps(E, s, PC_LN_BWD, 14.0 * rows * d, (double)rows * d * ((dy_dtype == DT_F32 ? 4.0 : 2.0) + 4.0 + (resid ? 4.0 : 0.0) + 4.0 + (out16 ? 2.0 : 0.0)));
   return launch_ln_bwd(dtype >= 0 ? dtype : E->dt, a, s);
 }
@@ -415,11 +422,12 @@ int wide_pitch(int cols) {
 // segments > 1 (a saving text tower under activation checkpointing): the per-layer tensors shrink to the m slots of the largest
 // segment (the last one), the k segment inputs stay (x[0] and k - 1 boundary buffers)
 // gelu (Engine::act == ACT_GELU): one more fp32 [T, 4d] buffer, the scratch of the stand-alone activation pass
+// Lg (TowerState::Lg; 0: L): the gradient buffers hold N * Lg rows
 void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool save, bool causal, bool exact, int xs, bool gelu,
-                 int segments = 1) {
+                 int segments = 1, int Lg = 0) {
   const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1; const int nl = W.layers;
   st = TowerState();
-  st.N = N; st.L = L; st.d = (int)d; st.H = (int)H; st.hw = (int)(d / H); st.layers = nl; st.causal = causal; st.exact = exact;
+  st.N = N; st.L = L; st.Lg = Lg > 0 ? Lg : L; st.d = (int)d; st.H = (int)H; st.hw = (int)(d / H); st.layers = nl; st.causal = causal; st.exact = exact;
   st.xs = exact ? xs : 0;
   st.seg = ckpt_plan(nl, save ? segments : 1);
   const int k = (int)st.seg.size() - 1;
@@ -464,10 +472,11 @@ void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool s
   st.wide_pitch = exact ? wide_pitch(4 * (int)d) : 0;
   st.part[0] = bp.take<float>(T * FOLD_NTP * 2); st.part[1] = bp.take<float>(T * FOLD_NTP * 2);
   if (save) {
-    st.dx32 = bp.take<float>(T * d);
-    st.dx16 = bp.take_bytes(T * d * 2 * X); st.dh32 = bp.take<float>(T * d); st.dO16 = bp.take_bytes(T * d * 2 * X);
-    st.du16 = bp.take_bytes(T * (4 * d * 2 * X + 128)); st.dqkv16 = bp.take_bytes(T * 3 * d * 2 * X);
-    st.delta = bp.take<float>((size_t)N * H * L);
+    const size_t Tg = (size_t)N * st.Lg;
+    st.dx32 = bp.take<float>(Tg * d);
+    st.dx16 = bp.take_bytes(Tg * d * 2 * X); st.dh32 = bp.take<float>(Tg * d); st.dO16 = bp.take_bytes(Tg * d * 2 * X);
+    st.du16 = bp.take_bytes(Tg * (4 * d * 2 * X + 128)); st.dqkv16 = bp.take_bytes(Tg * 3 * d * 2 * X);
+    st.delta = bp.take<float>((size_t)N * H * st.Lg);
     st.scale_dev = bp.take<float>(4);   // {scale, 1/scale, amax scratch, pad}
   }
   if (gelu) st.act32 = bp.take<float>(T * 4 * d);
@@ -513,16 +522,18 @@ int attn_bwd(Engine* E, TowerState& st, int l, const Compact* cls, hipStream_t s
     HIPCHK(E, launch_attn_bwd_cls(E->dt, st.qkv[l], cls->a16, cls->dO16, st.lse[l], st.dqkv16, st.N, st.L, st.H, s));
     return 0;
   }
-  const double fl = 14.0 * st.L * st.L * 64.0 * st.N * st.H * cz;
+  // (the positions that carry a gradient: st.Lg of the st.L saved ones)
+  const double fl = 14.0 * st.Lg * st.Lg * 64.0 * st.N * st.H * cz, Tg = (double)st.N * st.Lg;
   if (st.xs) {
-    Attn32BwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.L, st.H, st.causal ? 1 : 0};
-    a.lo8 = st.xs == 2 ? 1 : 0;
-    ProfScope ps(E, s, PC_ATTN_BWD, fl, T * st.d * 32.0);
+    Attn32BwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.Lg, st.H, st.causal ? 1 : 0};
+    a.lo8 = st.xs == 2 ? 1 : 0; a.Ls = st.L;
+    ProfScope ps(E, s, PC_ATTN_BWD, fl, Tg * st.d * 32.0);
     HIPCHK(E, launch_attn32_bwd(E->dt, a, s));
     return 0;
   }
-  AttnBwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.L, st.H, st.causal ? 1 : 0};
-  ProfScope ps(E, s, PC_ATTN_BWD, fl, T * st.d * 2.0 * 8.0);
+  AttnBwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.Lg, st.H, st.causal ? 1 : 0};
+  a.Ls = st.L;
+  ProfScope ps(E, s, PC_ATTN_BWD, fl, Tg * st.d * 2.0 * 8.0);
   HIPCHK(E, launch_attn_bwd(E->dt, a, s));
   return 0;
 }
@@ -566,15 +577,18 @@ int mlp_up(Engine* E, const void* h16, WRef fc, const float* bias, int M, int d,
   return 0;
 }
 // mlp_up_bwd: du16 = (dx16 pr) * act'(u16), the gradient at the pre-activation in the format xs
-int mlp_up_bwd(Engine* E, const void* dx16, WRef prt, int M, int d, int xs, const void* u16, void* du16, int ldo, float* scratch, hipStream_t s) {
+// u_seq > 0: u16 holds sequences of u_pitch rows and row m of the gradient belongs to row (m / u_seq) * u_pitch + m % u_seq of it
+int mlp_up_bwd(Engine* E, const void* dx16, WRef prt, int M, int d, int xs, const void* u16, void* du16, int ldo, float* scratch, hipStream_t s,
+               int u_seq = 0, int u_pitch = 0) {
   if (E->act == ACT_QUICKGELU) {
-    HIPCHK(E, gemm(E, xs ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, dx16, prt, M, 4 * d, d, nullptr, u16, nullptr, du16, nullptr, s, -1, xs, nullptr, 0, ldo));
+    HIPCHK(E, gemm(E, xs ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, dx16, prt, M, 4 * d, d, nullptr, u16, nullptr, du16, nullptr, s, -1, xs, nullptr, 0, ldo,
+                   u_seq, u_pitch));
     return 0;
   }
   if (!scratch) return fail(E, MVLPT_ERR_STATE, "exact GELU: the saved state was carved without the activation scratch");
   HIPCHK(E, gemm(E, EPI_STORE32, dx16, prt, M, 4 * d, d, nullptr, nullptr, nullptr, scratch, nullptr, s, -1, xs));
   ProfScope ps(E, s, PC_GLUE, 14.0 * M * 4 * d, (double)M * 4 * d * (6.0 + (xs == 1 ? 4.0 : xs ? 3.0 : 2.0)));
-  HIPCHK(E, launch_act_bwd(E->dt, E->act, ActArgs{scratch, 0, du16, xs, ldo, const_cast<void*>(u16), M, 4 * d}, s));
+  HIPCHK(E, launch_act_bwd(E->dt, E->act, ActArgs{scratch, 0, du16, xs, ldo, const_cast<void*>(u16), M, 4 * d, u_seq, u_pitch}, s));
   return 0;
 }
 
@@ -641,17 +655,19 @@ int block_fwd_packed(Engine* E, const TowerW& W, TowerState& st, int l, hipStrea
 }
 
 // dX-only backward of one block: dx32/dx16 hold d(block output) on entry and d(block input) on exit
+// The gradient buffers hold the T = N * Lg rows that carry a gradient (TowerState::Lg); the saved u and x are read through the row map.
 int block_bwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s) {
   const Block& B = W.blocks[l];
-  const int T = st.N * st.L, d = st.d, xs = st.xs, wp = st.wide_pitch;
-  if (int rc = mlp_up_bwd(E, st.dx16, B.pr.bw(), T, d, xs, st.u[l], st.du16, wp, st.act32, s)) return rc;
+  const int T = st.N * st.Lg, d = st.d, xs = st.xs, wp = st.wide_pitch;
+  const int ms = st.Lg != st.L ? st.Lg : 0, mp = ms ? st.L : 0;      // the row map of the saved tensors (0: none)
+  if (int rc = mlp_up_bwd(E, st.dx16, B.pr.bw(), T, d, xs, st.u[l], st.du16, wp, st.act32, s, ms, mp)) return rc;
   // the dX GEMMs that feed a LayerNorm backward store fp32 (one 16-bit rounding less per half layer)
   HIPCHK(E, gemm(E, EPI_STORE32, st.du16, B.fc.bw(), T, d, 4 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs, nullptr, wp, 0));
-  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l + 1], nullptr, 1, B.ln2, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs));
+  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l + 1], nullptr, 1, B.ln2, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs, ms, mp));
   HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, st.dx16, B.o.bw(), T, d, d, nullptr, nullptr, nullptr, st.dO16, nullptr, s, -1, xs));
   if (int rc = attn_bwd(E, st, l, nullptr, s)) return rc;
   HIPCHK(E, gemm(E, EPI_STORE32, st.dqkv16, B.qkv.bw(), T, d, 3 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs));
-  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, B.ln1, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs));
+  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, B.ln1, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs, ms, mp));
   return 0;
 }
 
@@ -667,8 +683,10 @@ void carve_compact(Bump& bp, Compact& c, size_t R, size_t d, size_t X, bool gelu
   if (gelu) c.act32 = bp.take<float>(R * 4 * d);
 }
 // compact row r <-> token row rows[r] or (rows == null) row 0 of sequence r; scatter: compact -> full width
-hipError_t move_rows(const void* src, void* dst, const int32_t* rows, int R, int L, size_t row_bytes, int scatter, hipStream_t s) {
-  if (rows) return launch_copy_rows(src, dst, rows, R, (int)row_bytes, scatter, s);
+// Lfar (0: L): `rows` addresses sequences of L rows and the full-width side holds Lfar rows of each (TowerState::Lg)
+hipError_t move_rows(const void* src, void* dst, const int32_t* rows, int R, int L, size_t row_bytes, int scatter, hipStream_t s, int Lfar = 0) {
+  if (rows) return launch_copy_rows(src, dst, rows, R, (int)row_bytes, scatter, s, Lfar && Lfar != L ? L : 0, Lfar && Lfar != L ? Lfar : 0);
+  if (Lfar && Lfar != L) return hipErrorInvalidValue;
   return launch_copy_rows_strided(src, dst, R, scatter ? row_bytes : L * row_bytes, scatter ? L * row_bytes : row_bytes, (int)row_bytes, s);
 }
 // Image: only x[:, 0, :] of the last block is read (trainers/mvlpt.py:88), rows == null, and only the CLS query runs (q_rows = 1).
@@ -709,10 +727,13 @@ int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const
 // forward ran q_rows queries takes the single-query attention backward on the compact rows; every other one scatters the compact dO
 // into a zeroed dO16 and runs the attention backward at full width.
 int last_block_bwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const int32_t* rows, int q_rows, const LNp& ln_close, hipStream_t s) {
-  const int l = st.layers - 1, T = st.N * st.L, R = st.N, d = st.d, xs = st.xs;
+  // (T: the full-width rows that carry a gradient, TowerState::Lg, compact in the gradient buffers)
+  const int l = st.layers - 1, T = st.N * st.Lg, R = st.N, d = st.d, xs = st.xs;
+  const int ms = st.Lg != st.L ? st.Lg : 0, mp = ms ? st.L : 0;
   const size_t X = xs ? 2 : 1;
   const Block& Bk = W.blocks[l];
   const bool cls = q_rows > 0 && !xs;
+  if (ms && (cls || !rows)) return fail(E, MVLPT_ERR_STATE, "last_block_bwd: a gradient length needs the row table of a text tower");
   HIPCHK(E, ln_bwd(E, c.dout32, DT_F32, c.xo32, nullptr, 1, ln_close, nullptr, c.dx32, c.dx16, R, d, s, -1, xs));
   if (int rc = mlp_up_bwd(E, c.dx16, Bk.pr.bw(), R, d, xs, c.u16, c.du16, 0, c.act32, s)) return rc;
   HIPCHK(E, gemm(E, EPI_STORE32, c.du16, Bk.fc.bw(), R, d, 4 * d, nullptr, nullptr, nullptr, c.dh32, nullptr, s, -1, xs));
@@ -721,12 +742,12 @@ int last_block_bwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const
   { ProfScope ps(E, s, PC_GLUE, 0, (cls ? 0.0 : (double)T * d * 2.0 * X) + (double)R * d * 8.0);
     if (!cls) {
       HIPCHK(E, launch_zero(st.dO16, (size_t)T * d * 2 * X, s));      // (split: dO is a hi|lo pair)
-      HIPCHK(E, move_rows(c.dO16, st.dO16, rows, R, st.L, (size_t)d * 2 * X, 1, s));
+      HIPCHK(E, move_rows(c.dO16, st.dO16, rows, R, st.L, (size_t)d * 2 * X, 1, s, st.Lg));
     }
-    HIPCHK(E, move_rows(c.dx32, st.dx32, rows, R, st.L, (size_t)d * 4, 1, s)); }     // residual path: d(block input) of the compact rows
+    HIPCHK(E, move_rows(c.dx32, st.dx32, rows, R, st.L, (size_t)d * 4, 1, s, st.Lg)); }     // residual path: d(block input) of the compact rows
   if (int rc = attn_bwd(E, st, l, cls ? &c : nullptr, s)) return rc;
   HIPCHK(E, gemm(E, EPI_STORE32, st.dqkv16, Bk.qkv.bw(), T, d, 3 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs));
-  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, Bk.ln1, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs));
+  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, Bk.ln1, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs, ms, mp));
   return 0;
 }
 
@@ -1648,16 +1669,19 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 // counts with it.  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of the ctx_pos table; range_ints / ids_ints: the range
 // table of a ranged forward and the id table of mvlpt_text_encode_tokens (0: none, a null pointer).  A saving tower is carved under the
 // engine's activation-checkpointing setting (mvlpt_set_text_act_ckpt).
+// Lg: the gradient length of a saving tower (text_grad_len below; L: every position).
 static void text_layout(Bump& bp, const Engine* E, TextRun& R, int C, int L, bool save, bool exact, size_t ctx_rows, size_t range_ints,
-                        size_t ids_ints) {
+                        size_t ids_ints, int Lg) {
   const bool gelu = E->act == ACT_GELU;
   carve_compact(bp, R.c, C, E->arch.text_width, exact ? 2 : 1, gelu);
   R.eot_rows = bp.take<int32_t>(C);
   R.ctx_pos = bp.take<int32_t>(ctx_rows);
   R.range = range_ints ? bp.take<int32_t>(range_ints) : nullptr;
   R.ids = ids_ints ? bp.take<int32_t>(ids_ints) : nullptr;
-  carve_tower(bp, E->txt, R.st, C, L, save, true, exact, split_kind(E), gelu, E->text_act_ckpt);
+  carve_tower(bp, E->txt, R.st, C, L, save, true, exact, split_kind(E), gelu, E->text_act_ckpt, Lg);
 }
+// The gradient length a saving forward over sequences of L positions runs under (mvlpt_set_text_grad_len): the setting, at most L
+static int text_grad_len(const Engine* E, int L) { return E->text_grad_len > 0 && E->text_grad_len < L ? E->text_grad_len : L; }
 // The published figure is the count plus 8192 bytes: the Python chunk planners compare it with budgets, so it stays where it is, to the byte.
 constexpr size_t kTextSlack = 2 * kCarveSlack;
 // mvlpt_text_workspace_bytes publishes the count with ctx_rows = C * (L - 2), the largest n_ctx a forward accepts, and no tables.  A ranged
@@ -1725,10 +1749,14 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
   const size_t ctx_rows = (size_t)(ranged && Cg > C ? Cg : C) * (n_ctx > 0 ? n_ctx : 1);
   const size_t range_ints = ranged ? E->t_range_host.size() : 0;
   const size_t ids_ints = ids ? E->t_ids_host.size() : 0;
+  // a gradient that stops in front of an EOT row would be wrong (never out of bounds): refused before anything is launched
+  const int Lg = save ? text_grad_len(E, L) : L;
+  if (Lg < L && Lg <= E->text_max_eot)
+    return fail(E, MVLPT_ERR_ARG, "text_fwd: the gradient length (mvlpt_set_text_grad_len) does not reach the largest EOT position");
   TextRun& R = E->trun = TextRun();      // opened: from here on the workspace no longer holds the last forward
   TowerState& st = R.st;
   if (int rc = carve_ws(E, E->txt_ws, "text_fwd", kTextSlack, [&](Bump& bp) {
-        text_layout(bp, E, R, C, L, save, exact, ctx_rows, range_ints, ids_ints);
+        text_layout(bp, E, R, C, L, save, exact, ctx_rows, range_ints, ids_ints, Lg);
       })) return rc;
   R.C = C; R.L = L; R.n_ctx = n_ctx; R.per_class = ctx_per_class; R.kind = kind; R.groups = G;
   R.n_deep = n_deep; R.ctx_deep = n_deep > 0 ? ctx_deep : nullptr;
@@ -1856,6 +1884,16 @@ int mvlpt_set_text_act_ckpt(void* h, int segments) {
   return 0;
 }
 
+int mvlpt_set_text_grad_len(void* h, int grad_len, int max_eot) {
+  Engine* E = (Engine*)h;
+  if (!E) return fail(E, MVLPT_ERR_ARG, "set_text_grad_len: null handle");
+  if (grad_len < MVLPT_TEXT_MIN_L || grad_len > E->arch.context_length)
+    return fail(E, MVLPT_ERR_ARG, "set_text_grad_len: the gradient length must lie in [MVLPT_TEXT_MIN_L, context_length]");
+  if (max_eot < 0) return fail(E, MVLPT_ERR_ARG, "set_text_grad_len: max_eot is negative");
+  E->text_grad_len = grad_len; E->text_max_eot = max_eot;      // read by the next saving text forward, which records what it ran under
+  return 0;
+}
+
 int mvlpt_text_act_ckpt_plan(void* h, int32_t* first_layer, int cap, int* n_segments) {
   Engine* E = (Engine*)h;
   if (!E || !first_layer || !n_segments || cap < 0) return fail(E, MVLPT_ERR_ARG, "text_act_ckpt_plan: null/invalid argument");
@@ -1874,7 +1912,7 @@ int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, in
   // a counting pass into scratch state: a saved forward whose backward has not run keeps its own
   TextRun scratch;
   *out = (int64_t)(carve_count([&](Bump& bp) {
-    text_layout(bp, E, scratch, C_total, L, save_for_bwd != 0, text_exact(E), (size_t)C_total * (L - 2), 0, 0);
+    text_layout(bp, E, scratch, C_total, L, save_for_bwd != 0, text_exact(E), (size_t)C_total * (L - 2), 0, 0, L);
   }) + kTextSlack);
   return 0;
 }
@@ -1892,7 +1930,8 @@ static int text_bwd_impl(Engine* E, const float* dfeat, float* dctx, float* dctx
   if (R.n_deep > 0 && !dctx_deep) return fail(E, MVLPT_ERR_ARG, "text_bwd_deep: dctx_deep is null after a forward with deep prompts");
   hipStream_t s = (hipStream_t)stream;
   const MvlptArch& A = E->arch;
-  const int C = R.C, L = R.L, dtw = A.text_width, e = A.embed_dim;
+  // L: the gradient length this forward was saved under (TowerState::Lg), the sequence pitch of every gradient buffer
+  const int C = R.C, L = st.Lg, dtw = A.text_width, e = A.embed_dim;
   const size_t T = (size_t)C * L;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dtw * 10.0);
     HIPCHK(E, launch_grad_scale(dfeat, (size_t)C * e, 64.0f, st.scale_dev, s));
@@ -2291,6 +2330,41 @@ int mvlpt_op_attention32_fwd(int dtype, const void* qkv, void* out, float* lse, 
 int mvlpt_op_attention32_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                              void* dqkv, int N, int L, int H, int causal, mvlpt_stream_t stream) {
   return op_attn32_bwd(dtype, qkv, out, dout, lse, delta, dqkv, N, L, H, causal, 0, stream);
+}
+// ---- the text backward's launches under a gradient length (mvlpt_set_text_grad_len): saved operands at the pitch seq_pitch, read
+// through the row map r -> (r / grad_len) * seq_pitch + r % grad_len; everything else compact.  The launchers check the maps.
+int mvlpt_op_gemm_gelubwd_rows(int dtype, int epi, const void* A, const void* Bt, int M, int N, int K, const void* aux, void* out, int a_split,
+                               int lda, int ldo, int ldb, int w8_exp, int out_lo8, int grad_len, int seq_pitch, mvlpt_stream_t stream) {
+  if (epi != EPI_GELUBWD && epi != EPI_GELUBWD_SPLIT) return fail(nullptr, MVLPT_ERR_ARG, "op_gemm_gelubwd_rows: a GELU-backward epilogue");
+  GemmArgs g{A, Bt, M, N, K, nullptr, aux, nullptr, out, nullptr};
+  g.a_split = a_split; g.lda = lda; g.ldo = ldo; g.ldb = ldb; g.w8_exp = w8_exp; g.out_lo8 = out_lo8;
+  g.aux_seq = grad_len; g.aux_pitch = seq_pitch;
+  OPCHK(launch_gemm(dtype, epi, g, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_layernorm_bwd_rows(int dtype, const void* dy, int dy_dtype, const float* x, const float* gamma, const float* resid,
+                                float* out32, void* out16, int rows, int d, int split, int grad_len, int seq_pitch, mvlpt_stream_t stream) {
+  if (!dy || !x || !gamma || !out32 || rows <= 0 || grad_len <= 0 || rows % grad_len)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_bwd_rows: null/invalid argument");
+  LnBwdArgs a{dy, dy_dtype, x, nullptr, 1, gamma, resid, out32, out16, rows, d};
+  a.split = split; a.x_seq = grad_len; a.x_pitch = seq_pitch;
+  OPCHK(launch_ln_bwd(dtype, a, (hipStream_t)stream));
+  return 0;
+}
+// causal; pair: attention32.hip (lo8: mixed pairs), else the single-operand kernels of attention.hip
+int mvlpt_op_attention_bwd_rows(int dtype, int pair, int lo8, const void* qkv, const void* out, const void* dout, const float* lse,
+                                float* delta, void* dqkv, int N, int grad_len, int seq_pitch, int H, mvlpt_stream_t stream) {
+  if (!qkv || !out || !dout || !lse || !delta || !dqkv) return fail(nullptr, MVLPT_ERR_ARG, "op_attention_bwd_rows: null argument");
+  if (pair) {
+    Attn32BwdArgs a{qkv, out, dout, lse, delta, dqkv, N, grad_len, H, 1};
+    a.lo8 = lo8; a.Ls = seq_pitch;
+    OPCHK(launch_attn32_bwd(dtype, a, (hipStream_t)stream));
+  } else {
+    AttnBwdArgs a{qkv, out, dout, lse, delta, dqkv, N, grad_len, H, 1};
+    a.Ls = seq_pitch;
+    OPCHK(launch_attn_bwd(dtype, a, (hipStream_t)stream));
+  }
+  return 0;
 }
 int mvlpt_op_layernorm_fwd(int out_dtype, const float* x, const float* gamma, const float* beta, void* y, int rows, int d,
                            mvlpt_stream_t stream) {

@@ -75,6 +75,9 @@ struct GemmArgs {
   // pads such rows by 128 bytes.
   int lda = 0, ldo = 0;
   int xcd_order = 0;   // set by the one-tile-per-workgroup launcher (gemm_pc_kernel): XCD-aware tile order
+  // EPI_GELUBWD / EPI_GELUBWD_SPLIT: output row m reads aux row (m / aux_seq) * aux_pitch + m % aux_seq (the leading aux_seq positions of
+  // sequences saved at a pitch of aux_pitch rows; M % aux_seq == 0).  aux_seq == 0: row m.
+  int aux_seq = 0, aux_pitch = 0;
   // ---- LayerNorm folding: LN(x) W^T = rstd_r * ((x * gamma) W^T)[r,n] - rstd_r * mean_r * (W gamma)[n] + (W beta)[n], so the
   // GEMM in front of a LayerNorm hands the un-normalised row to the GEMM behind it and the LayerNorm pass (one read of the fp32
   // residual stream + one 16-bit write per LayerNorm) disappears.  No atomics, no extra launch: every output tile owns its slots.
@@ -151,6 +154,9 @@ struct LnBwdArgs {
   void* out16;           // optional 16-bit copy, same row mapping
   int rows, d;
   int split = 0;         // out16 is [*, 2d] = [hi | lo]; 2: [hi | lo8 bytes | unused] (mixed pair)
+  // x_seq > 0 (row_idx null, row_mul 1): x alone is read at row (r / x_seq) * x_pitch + r % x_seq, the leading x_seq positions of
+  // sequences saved at a pitch of x_pitch rows; dy, resid and the outputs stay at row r
+  int x_seq = 0, x_pitch = 0;
 };
 hipError_t launch_ln_bwd(int dtype, const LnBwdArgs& a, hipStream_t s);
 // The kernel both launchers use for `rows` x `d` on stream `s`: stream = 0 one wave per row (ln_*_kernel), 1 grid-stride
@@ -172,6 +178,9 @@ struct AttnBwdArgs {
   const void* qkv; const void* out; const void* dout; const float* lse;
   float* delta /*[N*H*L] scratch*/; void* dqkv /*[N*L,3d]*/;
   int N, L, H; int causal;
+  // Ls > L: the saved tensors (qkv, out, lse) hold sequences of Ls positions and only the leading L carry a gradient: dout, delta and
+  // dqkv are [N*L, .] and positions >= L are neither staged nor computed (causal only: no row < L reads a key or query >= L).  0: L
+  int Ls = 0;
 };
 hipError_t launch_attn_bwd(int dtype, const AttnBwdArgs& a, hipStream_t s);
 int attn_max_len();
@@ -207,6 +216,7 @@ struct Attn32BwdArgs {
   float* delta /*[N*H*L] scratch*/; void* dqkv_split /*[N*L, 6d] 16-bit: [hi(3d) | lo(3d)]*/;
   int N, L, H; int causal;
   int lo8 = 0;           // out_split rows are [hi | lo8] (read for delta) and dqkv_split rows are written as [hi(3d) | lo8 (3d bytes) | unused]
+  int Ls = 0;            // as AttnBwdArgs::Ls (the short causal kernel, L <= 80, only)
 #ifdef MVLPT_ATTN_TRACE
   long long* trace = nullptr;   // debug builds only (tools/attn_trace.py bwd): records of one workgroup of attn32r_bwd_kernel
 #endif
@@ -292,7 +302,10 @@ hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipS
 // of them inside the table (checked on the host by the callers); d % 4 == 0
 hipError_t launch_embed_tokens(const float* emb, const float* pos, const int32_t* ids, int ld, float* x, int S, int L, int d, hipStream_t s);
 // dst[r] = src[idx[r]] (scatter = 0) or dst[idx[r]] = src[r] (scatter = 1); row_bytes % 16 == 0
-hipError_t launch_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, hipStream_t s);
+// idx_seq > 0: idx addresses sequences of idx_seq rows and the far side holds them at a pitch of far_seq rows: idx[r] stands for
+// (idx[r] / idx_seq) * far_seq + idx[r] % idx_seq
+hipError_t launch_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, hipStream_t s,
+                            int idx_seq = 0, int far_seq = 0);
 // rows of row_bytes (multiple of 16) from src + r*src_pitch to dst + r*dst_pitch
 hipError_t launch_copy_rows_strided(const void* src, void* dst, int rows, size_t src_pitch, size_t dst_pitch, int row_bytes, hipStream_t s);
 // out[j,:] = inv_scale * sum_b dx[b, row0+j, :]; optionally zero those rows of dx32/dx16 afterwards
@@ -352,6 +365,8 @@ struct ActArgs {
   int ldo;             // row pitch of `out` in 16-bit elements (0: dense, N or 2N)
   void* u16;           // 16-bit [M, N], dense: forward, optional: the saved pre-activation is written; backward: it is read
   int M, N;            // N % 8 == 0; pitches multiples of 8; every pointer 16-byte aligned
+  // backward only: row m reads u16 row (m / u_seq) * u_pitch + m % u_seq (GemmArgs::aux_seq for the stand-alone pass).  0: row m
+  int u_seq = 0, u_pitch = 0;
 };
 const char* act_check(int dtype, int act, bool bwd, ActArgs& a);      // null when the launch is legal (pitches resolved), else why not
 hipError_t launch_act_fwd(int dtype, int act, const ActArgs& a, hipStream_t s);

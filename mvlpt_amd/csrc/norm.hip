@@ -174,7 +174,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.rows) return;
   const size_t in_row = a.row_idx ? (size_t)a.row_idx[row] : (size_t)row * a.row_mul;
-  const float* x = a.x + in_row * a.d;
+  const size_t x_row = a.x_seq > 0 ? (size_t)(row / a.x_seq) * a.x_pitch + row % a.x_seq : in_row;      // (LnBwdArgs::x_seq)
+  const float* x = a.x + x_row * a.d;
   const TDY* dy = (const TDY*)a.dy + (size_t)row * a.d;
   f32x4 v[LN_MAXV], gg[LN_MAXV]; bool ok[LN_MAXV];
 #pragma unroll
@@ -231,10 +232,11 @@ __global__ __launch_bounds__(256) void ln_bwd_stream_kernel(LnBwdArgs a) {
   auto in_row_of = [&](int r) { return a.row_idx ? (size_t)a.row_idx[r] : (size_t)r * a.row_mul; };
   auto load_row = [&](int r, f32x4* x, f32x4* d, f32x4* rs) {
     const size_t in_row = in_row_of(r);
+    const size_t x_row = a.x_seq > 0 ? (size_t)(r / a.x_seq) * a.x_pitch + r % a.x_seq : in_row;      // (LnBwdArgs::x_seq)
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * 4;
-      x[i] = ok[i] ? __builtin_nontemporal_load((const f32x4*)(a.x + in_row * a.d + c)) : zero;
+      x[i] = ok[i] ? __builtin_nontemporal_load((const f32x4*)(a.x + x_row * a.d + c)) : zero;
       if (ok[i]) {
         if constexpr (sizeof(TDY) == 4) d[i] = __builtin_nontemporal_load((const f32x4*)((const float*)a.dy + (size_t)r * a.d + c));
         else d[i] = load4<TDY>((const TDY*)a.dy + (size_t)r * a.d + c);
@@ -316,7 +318,12 @@ hipError_t launch_ln_fwd(int out_dtype, const LnFwdArgs& a, hipStream_t s) {
 hipError_t launch_ln_bwd(int dtype, const LnBwdArgs& a, hipStream_t s) {
   if (a.rows <= 0) return hipSuccess;
   if (a.d % 4 != 0 || a.d > LN_MAXV * 256) return hipErrorInvalidValue;
-  const LnRoute r = ln_route(a.rows, a.d, s);
+  if (a.x_seq < 0 || (a.x_seq > 0 && (a.row_idx || a.row_mul != 1 || a.x_pitch < a.x_seq))) return hipErrorInvalidValue;
+  // The two kernels sum a row in different orders.  Under the row map the kernel is the one the saved rows would take, so that a
+  // backward over the leading positions keeps the bits of one over all of them; the grid follows the rows there are.
+  LnRoute r = ln_route(a.x_seq > 0 ? a.rows / a.x_seq * a.x_pitch : a.rows, a.d, s);
+  const int want = (a.rows + 3) / 4;
+  if (!r.stream || r.grid > want) r.grid = want;
   dim3 grid(r.grid), block(256);
   const bool dy32 = a.dy_dtype == DT_F32;
   if (r.stream) {

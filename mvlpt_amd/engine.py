@@ -180,6 +180,13 @@ class Engine:
         saved.  Applies from the next text forward and to text_workspace_bytes."""
         _lib.check(lib.mvlpt_set_text_act_ckpt(self.h, int(segments)), self.h, "set_text_act_ckpt")
 
+    def set_text_grad_len(self, grad_len: int, max_eot: int) -> None:
+        """Gradient length of the text tower (include/mvlpt_hip.h: mvlpt_set_text_grad_len): text_bwd processes only the leading
+        `grad_len` positions of every sequence; the rows behind a sequence's EOT carry an exactly zero gradient, so with
+        grad_len > max_eot (the largest entry of the eot tables the caller is going to pass) the gradients keep their bits.
+        grad_len = context_length: every position.  Applies from the next saving text forward."""
+        _lib.check(lib.mvlpt_set_text_grad_len(self.h, int(grad_len), int(max_eot)), self.h, "set_text_grad_len")
+
     def text_act_ckpt_plan(self) -> List[Tuple[int, int, bool]]:
         """The plan the next saving text forward uses, as mvlpt_amd.model.checkpoint_segments gives it:
         [(first, last_exclusive, checkpointed)]."""

@@ -225,6 +225,26 @@ def apply_text_act_ckpt(cfg, engine) -> int:
     return n
 
 
+def apply_text_grad_len(model, pl, classes: Optional[tuple] = None) -> None:
+    """Tell the engine of `model` how far the next saving text forward's backward has to reach (Engine.set_text_grad_len): the largest
+    EOT position of the class table of `pl` plus one, or every position when `model.text_grad_to_eot` is off
+    (TRAINER.MVLPT.TEXT_GRAD_TO_EOT).  `classes` = (lo, hi): the class shard the tower runs, whose own maximum counts.  Called in
+    front of every saving forward: several models may share one engine, and a class table may have been rebuilt since the last
+    step.  A host call, nothing is enqueued; an engine without the setting runs every position."""
+    setter = getattr(model.engine, "set_text_grad_len", None)
+    if setter is None:
+        return
+    if classes is None:
+        max_eot = int(pl.max_eot)
+    else:      # (the shard's maximum is read back once per table: pl.eot lives on the device)
+        key = (id(pl.eot), tuple(classes))
+        if getattr(model, "_shard_max_eot", (None, 0))[0] != key:
+            model._shard_max_eot = (key, int(pl.eot[classes[0]:classes[1]].max()))
+        max_eot = model._shard_max_eot[1]
+    full = int(model.clip_model.context_length)
+    setter(min(max(max_eot + 1, TEXT_MIN_L), full) if getattr(model, "text_grad_to_eot", True) else full, max_eot)
+
+
 def plan_text_chunks(eot: Sequence[int], workspace_bytes: Callable[[int, int], int], budget: int, min_len: int = TEXT_MIN_L,
                      max_seq: int = MAX_SEQUENCES_PER_TOWER, min_chunk: int = MIN_SEQUENCES_PER_CHUNK,
                      force_len: Optional[int] = None):
@@ -619,6 +639,8 @@ class _PromptedClipFn(torch.autograd.Function):
         if txt is None:
             suffix, layout = _text_inputs(model, pl, pl.coop_n_ctx)
             shard = model._class_shard if coop_emb is not None else None
+            if need_txt:
+                apply_text_grad_len(model, pl, (shard.lo, shard.hi) if shard is not None else None)
             if shard is not None:
                 # Class-sharded text tower (ClassShard): this rank encodes classes [lo, hi) only and the features are
                 # all-gathered; the backward reduce-scatters d(txt) back to the owners.  Tower and collective are one job.
@@ -784,6 +806,7 @@ class CustomCLIP(VisualPromptSide, nn.Module):
         self.overlap_towers = True
         self._class_shard = None
         self.trim_text_to_eot = False
+        self.text_grad_to_eot = bool(cfg.TRAINER.MVLPT.get("TEXT_GRAD_TO_EOT", True))
         self.text_cache = TextFeatureCache()
         self.prefetch = ImagePrefetch(self.engine, clip_model.device)
         self._fwd_generation = 0

@@ -35,8 +35,8 @@ import torch
 import torch.nn as nn
 
 from .cocoop import MAX_SEQUENCES_PER_TOWER, PerImageTextCLIP
-from .model import (FrozenCLIP, PretokenizedPrompts, VisualPromptSide, _CrossEntropyFn, _text_inputs, class_prompt_tables,
-                    class_range_tables, deep_text_prompts, image_conditioned_ctx, register_class_tables)
+from .model import (FrozenCLIP, PretokenizedPrompts, VisualPromptSide, _CrossEntropyFn, _text_inputs, apply_text_grad_len,
+                    class_prompt_tables, class_range_tables, deep_text_prompts, image_conditioned_ctx, register_class_tables)
 from .model import MultitaskVLPromptLearner as _BasePromptLearner
 from .schedule import check_forward_is_current
 
@@ -127,6 +127,8 @@ class _TextSideFn(torch.autograd.Function):
         eng, pl = model.engine, model.prompt_learner
         suffix, layout = _text_inputs(model, pl, pl.cocoop_n_ctx)
         clo, chi = lo[g0:g1], hi[g0:g1]
+        if save:
+            apply_text_grad_len(model, pl)
         txt = eng.text_fwd_ranged(pl.token_prefix, suffix, ctx_shifted[g0:g1], layout, pl.eot, clo, chi, save_for_bwd=save)
         return eng.logits_ranged_fwd(img[g0:g1], txt, model.logit_scale_exp, clo, chi, pl.n_cls)
 

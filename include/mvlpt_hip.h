@@ -290,6 +290,24 @@ int mvlpt_text_act_ckpt_plan(void* handle, int32_t* first_layer, int cap, int* n
  * anything is launched, and a caller whose tables change calls this again.  An understated max_eot gives a wrong gradient, never an
  * out-of-bounds access.  mvlpt_text_workspace_bytes keeps reporting the figure of the full length, an upper bound. */
 int mvlpt_set_text_grad_len(void* handle, int grad_len, int max_eot);
+/* Shared prefix of the class prompts: the CALLER vouches that positions 0 .. prefix-1 of `layout` hold the same entries in every class
+ * row, none of them a suffix entry, that every row of `prefix` (the SOS embedding) is bitwise the same, that the context is generic and
+ * that every EOT lies at or behind position `prefix`.  The attention is causal and everything else acts row by row, so those positions
+ * have the same hidden state in every sequence: the tower evaluates them once, in C + 1 "slots" of L - P rows (slot 0: the prefix,
+ * slot c + 1: positions P .. L-1 of class c), and its backward carries the SUM over the classes of their gradient, which is all dctx
+ * needs; the one class-dependent path into them, dK / dV of the prefix keys from later queries, is summed from fp32 partials in a fixed
+ * order (no atomics).  For more than 512 classes that sum is carried scaled down by a power of two and rescaled exactly at the end.
+ * The features keep their bits; dctx rows of prefix positions change at rounding level (another summation order).
+ * Unlike mvlpt_set_text_grad_len the engine cannot check this setting against its tables, so it is ONE-SHOT: the next text forward
+ * through any entry (mvlpt_text_fwd, saving or not; _deep; _ranged; mvlpt_text_encode_tokens) consumes it, and a forward without a new
+ * call runs without a prefix.  The forward records what it ran under: a call between a forward and its backward does not change that
+ * backward.  0 (the default): off, today's launches.  prefix < 0 or >= context_length: MVLPT_ERR_ARG.  The engine uses
+ * P = min(prefix, L - 1) lowered until P <= grad_len - P and grad_len - P >= MVLPT_TEXT_MIN_L (any shorter prefix is as correct), and
+ * P = 0 on every route that has no slot layout: ctx_per_class, deep prompts, the ranged and token-id entries, activation checkpointing
+ * (mvlpt_set_text_act_ckpt > 1), L > 80.  Split and single operands (MVLPT_PREC_FAST) share alike.  mvlpt_text_workspace_bytes keeps reporting the
+ * figure without a prefix: an upper bound once the prefix saves rows ((C + 1) (L - P) + the partials <= C L); the workspace grows on
+ * demand otherwise. */
+int mvlpt_set_text_shared_prefix(void* handle, int prefix);
 
 /* CLIP.encode_text (clip/model.py:343-356: token_embedding(text) + positional_embedding -> transformer -> ln_final ->
  * x[arange, text.argmax(-1)] @ text_projection) for S sequences of token ids: what the zero-shot trainers feed (trainers/zsclip.py:45-49,
@@ -501,6 +519,22 @@ int mvlpt_op_layernorm_bwd_rows(int dtype, const void* dy, int dy_dtype, const f
                                 float* out32, void* out16, int rows, int d, int split, int grad_len, int seq_pitch, mvlpt_stream_t stream);
 int mvlpt_op_attention_bwd_rows(int dtype, int pair, int lo8, const void* qkv, const void* out, const void* dout, const float* lse,
                                 float* delta, void* dqkv, int N, int grad_len, int seq_pitch, int H, mvlpt_stream_t stream);
+/* The pair attention under a shared prefix (mvlpt_set_text_shared_prefix), kernel level; causal, seq_len <= 80, lo8 != 0: mixed pairs.
+ * Every tensor holds N + 1 slots: slot 0 = the prefix in its first P rows (the others are never read; the forward writes zeros into
+ * them in out / lse, the backward's reduction into dqkv), slot n + 1 = positions P .. of sequence n; 2 P <= L.  fwd: qkv / out in slots of L - P rows, lse [N + 1, H, L - P].  bwd: qkv / out / lse as the forward left
+ * them with L = seq_len; dout / dqkv in slots of grad_len - P rows (2 P <= grad_len); slot 0 of dout is the prefix's own dO (a class
+ * sequence takes dO of its positions < P as zero).  kv_part: fp32 scratch [N + 1, P, 2 H 64].  Two launches: the backward, then the
+ * reduction that writes dK / dV of slot 0 = own + part_mul * sum over the sequences, and zeros into rows P .. of slot 0. */
+int mvlpt_op_attention32_fwd_prefix(int dtype, int lo8, const void* qkv, void* out, float* lse, int N, int L, int H, int prefix,
+                                    mvlpt_stream_t stream);
+int mvlpt_op_attention32_bwd_prefix(int dtype, int lo8, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                                    void* dqkv, float* kv_part, float part_mul, int N, int grad_len, int seq_len, int H, int prefix,
+                                    mvlpt_stream_t stream);
+/* The same for single operands (the kernels of MVLPT_PREC_FAST): qkv [., 3 H 64], out / dout [., H 64], dqkv [., 3 H 64] 16-bit, slots as
+ * above; delta: scratch [N + 1, H, grad_len - P]; three launches in the backward (dQ, dK / dV, the reduction). */
+int mvlpt_op_attention_fwd_prefix(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int prefix, mvlpt_stream_t stream);
+int mvlpt_op_attention_bwd_prefix(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                  float* kv_part, float part_mul, int N, int grad_len, int seq_len, int H, int prefix, mvlpt_stream_t stream);
 int mvlpt_op_cast_ex(int dtype, const float* in, void* out, int64_t rows, int d, int format, const float* scale_dev, mvlpt_stream_t stream);
 int mvlpt_op_cast_to_f32(int in_dtype, const void* in, float* out, int64_t n, mvlpt_stream_t stream);
 int mvlpt_op_pack_weight(int dtype, const float* w32, int rows, int cols, int transposed, int ld_out, void* out, mvlpt_stream_t stream);

@@ -120,6 +120,7 @@ SIGNATURES = {
     "mvlpt_text_workspace_bytes": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int64)]),
     "mvlpt_set_text_act_ckpt": (_i, [_vp, _i]),
     "mvlpt_set_text_grad_len": (_i, [_vp, _i, _i]),
+    "mvlpt_set_text_shared_prefix": (_i, [_vp, _i]),
     "mvlpt_text_act_ckpt_plan": (_i, [_vp, C.POINTER(C.c_int32), _i, C.POINTER(_i)]),
     "mvlpt_text_encode_tokens": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
     "mvlpt_text_ensemble": (_i, [_vp, _i, _i, _i, _vp, _vp]),
@@ -165,6 +166,10 @@ SIGNATURES = {
     "mvlpt_op_gemm_gelubwd_rows": (_i, [_i, _i, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mvlpt_op_layernorm_bwd_rows": (_i, [_i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "mvlpt_op_attention_bwd_rows": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_attention32_fwd_prefix": (_i, [_i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_attention32_bwd_prefix": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _i, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_attention_fwd_prefix": (_i, [_i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "mvlpt_op_attention_bwd_prefix": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _i, _i, _i, _i, _i, _vp]),
     "mvlpt_op_cast_ex": (_i, [_i, _vp, _vp, C.c_int64, _i, _i, _vp, _vp]),
     "mvlpt_op_cast_to_f32": (_i, [_i, _vp, _vp, C.c_int64, _vp]),
     "mvlpt_op_pack_weight": (_i, [_i, _vp, _i, _i, _i, _i, _vp, _vp]),

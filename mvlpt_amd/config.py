@@ -142,6 +142,11 @@ def get_cfg_default() -> CfgNode:
         # behind a sequence's EOT carry an exactly zero gradient: Engine.set_text_grad_len).  The forward still evaluates every
         # position and every result keeps its bits; False runs the backward over all positions (A/B runs).
         TEXT_GRAD_TO_EOT=True,
+        # not in the reference: with a generic context the leading positions of every class prompt (SOS and the context rows in
+        # front of the class name: 1 + n_ctx/2 for "middle", 1 + n_ctx for "end") are the same rows in every class; the text tower
+        # evaluates them once and its backward carries their gradient summed over the classes (Engine.set_text_shared_prefix).
+        # The features keep their bits, dctx of those positions changes at rounding level; False evaluates them per class (A/B runs).
+        TEXT_SHARED_PREFIX=True,
     )
     # trainers/cocoop.py's own keys (train.py:125-128), read by mvlpt_amd.cocoop (--trainer CoCoOp)
     cfg.TRAINER.COCOOP = CN(N_CTX=16, CTX_INIT="", PREC="fp16")

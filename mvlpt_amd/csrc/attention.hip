@@ -24,7 +24,10 @@ constexpr int ATT_MAX_NKT = 38;  // 38 tiles * 16 keys = 608: ViT-L/14@336 (577 
 int attn_max_len() { return ATT_MAX_NKT * 16; }
 
 // ======================================================================================= forward
-template <typename T, int NKT, bool CAUSAL>
+// PFX: the shared-prefix layout (AttnArgs::prefix > 0; causal, q_rows == 0).  `split` is the first position a class sequence owns (0 in
+// the prefix's own workgroups, whose length is P); position p sits at row p of slot 0 (p < split) or at row row0 + p.  The arithmetic
+// per (query, key) is that of the plain kernel at the same NKT.
+template <typename T, int NKT, bool CAUSAL, bool PFX = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using v8 = typename Vec<T>::v8;
@@ -34,13 +37,19 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   constexpr bool PRELOAD = NKT <= 16;
   char* sK = smem;                            // [LP][64] row-major, 16-B chunks swizzled by (row & 7)
   char* sV = smem + LP * 128;                 // same image for V; transposed on the fly by ds_read_b64_tr_b16
-  const int L = a.L, H = a.H, d = H * 64;
+  const int H = a.H, d = H * 64;
   const int n = blockIdx.x / H, h = blockIdx.x % H;
+  const bool own_pre = PFX && n == a.N;                       // the workgroups of the prefix itself
+  const int L = own_pre ? a.prefix : a.L;
+  const int split = PFX && !own_pre ? a.prefix : 0;
+  const int Lf = PFX ? a.L - a.prefix : a.L;                  // rows per slot
   const size_t ld = (size_t)3 * d;
-  const T* base = (const T*)a.qkv + (size_t)n * L * ld + h * 64;
+  const size_t row0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * Lf - a.prefix) : (size_t)n * L;
+  const T* base = (const T*)a.qkv + row0 * ld + h * 64;
+  const T* base_pre = (const T*)a.qkv + h * 64;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fg = lane >> 4;
-  const int nqt = a.q_rows > 0 ? ((a.q_rows < L ? a.q_rows : L) + 15) >> 4 : (L + 15) >> 4;
+  const int nqt = !PFX && a.q_rows > 0 ? ((a.q_rows < L ? a.q_rows : L) + 15) >> 4 : (L + 15) >> 4;
   // short sequences: every Q fragment this wave will need is requested before the K/V DMA is waited for
   constexpr int MAXQ = PRELOAD ? (NKT + 3) / 4 : 1;
   v8 qf[MAXQ][2];
@@ -49,15 +58,34 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
     for (int i = 0; i < MAXQ; ++i) {
       int qr = (wave + 4 * i) * 16 + fr;
       qr = qr < L ? qr : L - 1;
-      const T* qp = base + (size_t)qr * ld + fg * 8;
+      const T* qp = (qr < split ? base_pre : base) + (size_t)qr * ld + fg * 8;
       qf[i][0] = *(const v8*)qp;
       qf[i][1] = *(const v8*)(qp + 32);
     }
   }
-  stage_rows_dma<T>(sK, base + d, ld, L, LP, wave, lane, a.flags & 1);
-  stage_rows_dma<T>(sV, base + 2 * d, ld, L, LP, wave, lane, a.flags & 1);
+  if constexpr (PFX) {
+    stage_rows_dma_pfx<T>(sK, base_pre + d, base + d, split, ld, L, LP, wave, lane, a.flags & 1);
+    stage_rows_dma_pfx<T>(sV, base_pre + 2 * d, base + 2 * d, split, ld, L, LP, wave, lane, a.flags & 1);
+  } else {
+    stage_rows_dma<T>(sK, base + d, ld, L, LP, wave, lane, a.flags & 1);
+    stage_rows_dma<T>(sV, base + 2 * d, ld, L, LP, wave, lane, a.flags & 1);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
+  if constexpr (PFX) {
+    // the unused rows P .. Lf-1 of slot 0 (this head's columns, and their lse): zeros, finite and deterministic for the row-wise kernels
+    if (own_pre) {
+      for (int i = threadIdx.x; i < (Lf - L) * 16; i += 256) {
+        const int r = L + (i >> 4), c = (i & 15) * 4;
+        v4 z;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) z[e] = from_f32<T>(0.f);
+        *(v4*)((T*)a.out + (size_t)r * d + h * 64 + c) = z;
+      }
+      if (a.lse)
+        for (int j = L + threadIdx.x; j < Lf; j += 256) a.lse[(size_t)h * Lf + j] = 0.f;
+    }
+  }
 
   constexpr float SC = 0.125f * 1.4426950408889634f;   // 1/sqrt(64) * log2(e): softmax in base 2
   auto process = [&](const int qt, const v8 q0, const v8 q1) {
@@ -119,8 +147,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
     }
     sum = quad_sum(sum);
     const float inv = 1.0f / sum;
-    if (qrow < L) {
-      T* op = (T*)a.out + ((size_t)n * L + qrow) * d + h * 64 + fg * 4;
+    if (qrow < L && qrow >= split) {
+      T* op = (T*)a.out + (row0 + qrow) * d + h * 64 + fg * 4;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         v4 w;
@@ -130,13 +158,17 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
         else *(v4*)(op + dt * 16) = w;
       }
       // natural-log LSE of the scaled scores (the backward recomputes P = exp(s/8 - lse))
-      if (a.lse && fg == 0) a.lse[((size_t)n * H + h) * L + qrow] = (mrun + log2f(sum)) * 0.6931471805599453f;
+      if (a.lse && fg == 0) {
+        const size_t li = PFX ? ((size_t)(own_pre ? 0 : n + 1) * H + h) * Lf + (qrow - split) : ((size_t)n * H + h) * L + qrow;
+        a.lse[li] = (mrun + log2f(sum)) * 0.6931471805599453f;
+      }
     }
   };
   if constexpr (PRELOAD) {
 #pragma unroll
     for (int qi = 0; qi < MAXQ; ++qi) {
       if (wave + 4 * qi >= nqt) break;
+      if (PFX && (wave + 4 * qi) * 16 + 15 < split) continue;      // a tile of prefix queries only: the prefix's own workgroups have them
       process(wave + 4 * qi, qf[qi][0], qf[qi][1]);
     }
   } else {
@@ -320,7 +352,9 @@ __global__ __launch_bounds__(PNW * 64) void attn_fwdp_kernel(AttnArgs a, int tot
 // ======================================================================================= backward A: dQ (+ delta)
 // per query tile:  S^T, P^T = exp(S^T*scale - lse), dP^T = V dO^T, dS^T = P^T (dP^T - delta) * scale,
 //                  dQ^T = K^T dS^T.   LDS: K rows, V rows (DMA-staged); K^T fragments by transpose-read.
-template <typename T, int NKT, bool CAUSAL>
+// PFX: the shared-prefix layout (AttnBwdArgs::prefix > 0), addressed as in the forward.  A class sequence's queries below `split` carry no
+// gradient: their tiles are skipped where whole, their dQ and delta are not stored.
+template <typename T, int NKT, bool CAUSAL, bool PFX = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using v8 = typename Vec<T>::v8;
@@ -331,10 +365,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
   char* sK = smem;
   char* sV = smem + LP * 128;
   // L: the positions that carry a gradient (dout, delta, dqkv rows per sequence); Ls: the pitch of the saved tensors (AttnBwdArgs::Ls)
-  const int L = a.L, Ls = a.Ls > 0 ? a.Ls : a.L, H = a.H, d = H * 64;
+  const int H = a.H, d = H * 64;
   const int n = blockIdx.x / H, h = blockIdx.x % H;
+  const bool own_pre = PFX && n == a.N;                       // the workgroups of the prefix itself
+  const int L = own_pre ? a.prefix : a.L, Ls = a.Ls > 0 ? a.Ls : a.L;
+  const int split = PFX && !own_pre ? a.prefix : 0;
+  const int Lf = PFX ? Ls - a.prefix : Ls, Lt = PFX ? a.L - a.prefix : a.L;      // rows per slot: saved / gradient tensors
   const size_t ld = (size_t)3 * d;
-  const T* base = (const T*)a.qkv + (size_t)n * Ls * ld + h * 64;
+  // rows of position p >= split in the saved and in the gradient tensors; p < split: row p of slot 0
+  const size_t srow0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * Lf - a.prefix) : (size_t)n * Ls;
+  const size_t grow0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * Lt - a.prefix) : (size_t)n * L;
+  const size_t stat0 = ((size_t)(PFX ? (own_pre ? 0 : n + 1) : n) * H + h);      // (slot, head) of lse / delta for p >= split
+  const T* base = (const T*)a.qkv + srow0 * ld + h * 64;
+  const T* base_pre = (const T*)a.qkv + h * 64;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fg = lane >> 4;
   const int nqt = (L + 15) >> 4;
@@ -345,10 +388,10 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
     QOps r;
     int qr = qt * 16 + fr;
     qr = qr < L ? qr : L - 1;
-    const size_t tok = (size_t)n * L + qr;
-    const T* qp = base + (size_t)qr * ld + fg * 8;
-    const T* dop = (const T*)a.dout + tok * d + h * 64 + fg * 8;
-    const T* op = (const T*)a.out + ((size_t)n * Ls + qr) * d + h * 64 + fg * 8;
+    const bool in_pre = qr < split;      // (PFX) a prefix position of a class sequence: slot 0, nothing of it is stored
+    const T* qp = (in_pre ? base_pre : base) + (size_t)qr * ld + fg * 8;
+    const T* dop = (const T*)a.dout + ((in_pre ? 0 : grow0) + qr) * d + h * 64 + fg * 8;
+    const T* op = (const T*)a.out + ((in_pre ? 0 : srow0) + qr) * d + h * 64 + fg * 8;
     r.q0 = *(const v8*)qp; r.q1 = *(const v8*)(qp + 32);
     r.do0 = *(const v8*)dop; r.do1 = *(const v8*)(dop + 32);
     const v8 o0 = *(const v8*)op, o1 = *(const v8*)(op + 32);
@@ -356,7 +399,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) t += to_f32<T>(r.do0[e]) * to_f32<T>(o0[e]) + to_f32<T>(r.do1[e]) * to_f32<T>(o1[e]);
     r.dl = quad_sum(t);                                        // delta = rowsum(dO * O)
-    r.lse = a.lse[((size_t)n * H + h) * Ls + qr];
+    r.lse = PFX ? a.lse[in_pre ? (size_t)h * Lf + qr : stat0 * Lf + (qr - split)] : a.lse[((size_t)n * H + h) * Ls + qr];
     return r;
   };
   constexpr bool PRELOAD = NKT <= 16;
@@ -365,14 +408,19 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
 #pragma unroll
     for (int i = 0; i < MAXQ; ++i) pre[i] = load_ops(wave + 4 * i);
   }
-  stage_rows_dma<T>(sK, base + d, ld, L, LP, wave, lane);
-  stage_rows_dma<T>(sV, base + 2 * d, ld, L, LP, wave, lane);
+  if constexpr (PFX) {
+    stage_rows_dma_pfx<T>(sK, base_pre + d, base + d, split, ld, L, LP, wave, lane);
+    stage_rows_dma_pfx<T>(sV, base_pre + 2 * d, base + 2 * d, split, ld, L, LP, wave, lane);
+  } else {
+    stage_rows_dma<T>(sK, base + d, ld, L, LP, wave, lane);
+    stage_rows_dma<T>(sV, base + 2 * d, ld, L, LP, wave, lane);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   auto process = [&](const int qt, const QOps& O_) {
     const int qrow = qt * 16 + fr;
-    if (qrow < L && fg == 0) a.delta[((size_t)n * H + h) * L + qrow] = O_.dl;
+    if (qrow < L && qrow >= split && fg == 0) a.delta[PFX ? stat0 * Lt + (qrow - split) : ((size_t)n * H + h) * L + qrow] = O_.dl;
     const int nkt = CAUSAL ? (qt + 1 < NKT ? qt + 1 : NKT) : NKT;
     f32x4 dq[4];
 #pragma unroll
@@ -415,8 +463,8 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
         }
       }
     }
-    if (qrow < L) {
-      T* gp = (T*)a.dqkv + ((size_t)n * L + qrow) * ld + h * 64 + fg * 4;
+    if (qrow < L && qrow >= split) {
+      T* gp = (T*)a.dqkv + (grow0 + qrow) * ld + h * 64 + fg * 4;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         v4 w;
@@ -430,6 +478,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
 #pragma unroll
     for (int qi = 0; qi < MAXQ; ++qi) {
       if (wave + 4 * qi >= nqt) break;
+      if (PFX && (wave + 4 * qi) * 16 + 15 < split) continue;
       process(wave + 4 * qi, pre[qi]);
     }
   } else {
@@ -441,7 +490,9 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnBwdArgs a) {
 // per key tile (col = key = lane&15), looping over 32-query blocks:
 //   S = Q K^T (rows = queries), P, dP = dO V^T, dS ;  dV^T += dO^T P ;  dK^T += Q^T dS.
 // LDS: Q rows, dO rows (DMA-staged; Q^T / dO^T fragments by transpose-read), lse[LP], delta[LP].
-template <typename T, int NKT, bool CAUSAL>
+// PFX: as above.  A class sequence's queries below `split` enter with lse = +inf (P = 0 exactly) and delta = 0, so the dO rows staged for
+// them (slot 0, finite) drop out of dK / dV; dK / dV of prefix keys go as fp32 to kv_part [sequence (N: the prefix's own), P, dK | dV].
+template <typename T, int NKT, bool CAUSAL, bool PFX = false>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   using v8 = typename Vec<T>::v8;
@@ -452,11 +503,21 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs a) {
   char* sdO = smem + LP * 128;
   float* sLse = (float*)(smem + 2 * LP * 128);
   float* sDel = sLse + LP;
-  const int L = a.L, Ls = a.Ls > 0 ? a.Ls : a.L, H = a.H, d = H * 64;      // (as in attn_bwd_dq_kernel)
+  const int H = a.H, d = H * 64;
   const int n = blockIdx.x / H, h = blockIdx.x % H;
+  const bool own_pre = PFX && n == a.N;                       // the workgroups of the prefix itself
+  const int L = own_pre ? a.prefix : a.L, Ls = a.Ls > 0 ? a.Ls : a.L;
+  const int split = PFX && !own_pre ? a.prefix : 0;
+  const int Lf = PFX ? Ls - a.prefix : Ls, Lt = PFX ? a.L - a.prefix : a.L;      // rows per slot: saved / gradient tensors
   const size_t ld = (size_t)3 * d;
-  const T* base = (const T*)a.qkv + (size_t)n * Ls * ld + h * 64;
-  const T* dob = (const T*)a.dout + (size_t)n * L * d + h * 64;
+  // rows of position p >= split in the saved and in the gradient tensors; p < split: row p of slot 0
+  const size_t srow0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * Lf - a.prefix) : (size_t)n * Ls;
+  const size_t grow0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * Lt - a.prefix) : (size_t)n * L;
+  const size_t stat0 = ((size_t)(PFX ? (own_pre ? 0 : n + 1) : n) * H + h);      // (slot, head) of lse / delta for p >= split
+  const T* base = (const T*)a.qkv + srow0 * ld + h * 64;
+  const T* base_pre = (const T*)a.qkv + h * 64;
+  const T* dob = (const T*)a.dout + grow0 * d + h * 64;
+  const T* dob_pre = (const T*)a.dout + h * 64;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fg = lane >> 4;
   const int nkt_all = (L + 15) >> 4;
@@ -466,7 +527,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs a) {
     KOps r;
     int kr = kt * 16 + fr;
     kr = kr < L ? kr : L - 1;
-    const T* kp = base + (size_t)kr * ld + d + fg * 8;
+    const T* kp = (kr < split ? base_pre : base) + (size_t)kr * ld + d + fg * 8;
     r.k0 = *(const v8*)kp; r.k1 = *(const v8*)(kp + 32);
     r.v0 = *(const v8*)(kp + d); r.v1 = *(const v8*)(kp + d + 32);
     return r;
@@ -478,11 +539,21 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs a) {
     for (int i = 0; i < MAXK; ++i) pre[i] = load_kv(wave + 4 * i);
   }
   for (int i = threadIdx.x; i < LP; i += 256) {
-    sLse[i] = i < L ? a.lse[((size_t)n * H + h) * Ls + i] : 0.f;
-    sDel[i] = i < L ? a.delta[((size_t)n * H + h) * L + i] : 0.f;
+    if constexpr (PFX) {
+      sLse[i] = i < L ? (i < split ? INFINITY : a.lse[stat0 * Lf + (i - split)]) : 0.f;
+      sDel[i] = i < L && i >= split ? a.delta[stat0 * Lt + (i - split)] : 0.f;
+    } else {
+      sLse[i] = i < L ? a.lse[((size_t)n * H + h) * Ls + i] : 0.f;
+      sDel[i] = i < L ? a.delta[((size_t)n * H + h) * L + i] : 0.f;
+    }
   }
-  stage_rows_dma<T>(sQ, base, ld, L, LP, wave, lane);
-  stage_rows_dma<T>(sdO, dob, (size_t)d, L, LP, wave, lane);
+  if constexpr (PFX) {
+    stage_rows_dma_pfx<T>(sQ, base_pre, base, split, ld, L, LP, wave, lane);
+    stage_rows_dma_pfx<T>(sdO, dob_pre, dob, split, (size_t)d, L, LP, wave, lane);
+  } else {
+    stage_rows_dma<T>(sQ, base, ld, L, LP, wave, lane);
+    stage_rows_dma<T>(sdO, dob, (size_t)d, L, LP, wave, lane);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -524,8 +595,15 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnBwdArgs a) {
         }
       }
     }
-    if (key < L) {
-      T* gp = (T*)a.dqkv + ((size_t)n * L + key) * ld + d + h * 64 + fg * 4;
+    if (PFX && key < L && (own_pre || key < split)) {
+      float* pp = a.kv_part + ((size_t)n * a.prefix + key) * (2 * (size_t)d) + h * 64 + fg * 4;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        *(f32x4*)(pp + dt * 16) = dk[dt];
+        *(f32x4*)(pp + d + dt * 16) = dv[dt];
+      }
+    } else if (key < L) {
+      T* gp = (T*)a.dqkv + (grow0 + key) * ld + d + h * 64 + fg * 4;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         v4 wk, wv;
@@ -639,33 +717,93 @@ hipError_t launch_attn_bwd_cls(int dtype, const void* qkv, const void* o_cls, co
   return hipGetLastError();
 }
 
+// ======================================================================================= shared prefix: dK / dV of slot 0
+// attn32t_prefix_reduce_kernel (attention32.hip) for single 16-bit outputs: slot 0 row p of dqkv [., 3d] gets dK | dV =
+// kv_part[N][p] + part_mul * sum_n kv_part[n][p], the unused rows P .. Lt-1 of slot 0 get zeros in all 3d columns.  The same fixed order:
+// wave w adds sequences w, w + 16, ..., wave 0 adds the sixteen sums in order on top of the prefix's own term.
+template <typename T>
+__global__ __launch_bounds__(1024) void attn_prefix_reduce_kernel(AttnBwdArgs a) {
+  __shared__ f32x4 part[16][64];
+  using v4 = typename Vec<T>::v4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int d = a.H * 64, P = a.prefix, Lt = a.L - P, p = blockIdx.y;
+  const size_t ld = 3 * (size_t)d, gld = 2 * (size_t)d;
+  const int c = (blockIdx.x * 64 + lane) * 4;      // column inside dK (d) | dV (d)
+  T* orow = (T*)a.dqkv + (size_t)p * ld;
+  if (p >= P) {
+    const int col = blockIdx.x * 384 + (int)threadIdx.x * 4;      // this workgroup's share of the 3d columns (256 of 2d -> 384 of 3d)
+    if (p < Lt && threadIdx.x < 96 && col < 3 * d) {
+      v4 z;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) z[e] = from_f32<T>(0.f);
+      *(v4*)(orow + col) = z;
+    }
+    return;
+  }
+  const bool ok = c < 2 * d;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (ok)
+    for (int k = wave; k < a.N; k += 16) acc += *(const f32x4*)(a.kv_part + ((size_t)k * P + p) * gld + c);
+  part[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && ok) {
+    f32x4 t = part[0][lane];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) t += part[w][lane];
+    t = *(const f32x4*)(a.kv_part + ((size_t)a.N * P + p) * gld + c) + t * a.part_mul;
+    v4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = from_f32<T>(t[e]);
+    *(v4*)(orow + d + c) = o;
+  }
+}
+
 // ======================================================================================= launchers
 static thread_local hipEvent_t t_ev_a = nullptr, t_ev_b = nullptr;      // launch_attn_fwd's optional dispatch events
-template <typename T, int NKT, bool CAUSAL>
+template <typename T, int NKT, bool CAUSAL, bool PFX = false>
 static hipError_t fwd_t(const AttnArgs& a, hipStream_t s) {
   constexpr int LP = NKT * 16;
   constexpr int lds = 2 * LP * 128;
   static bool set = false;
-  if (!set) { hipFuncSetAttribute((const void*)attn_fwd_kernel<T, NKT, CAUSAL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); set = true; }
-  hipExtLaunchKernelGGL((attn_fwd_kernel<T, NKT, CAUSAL>), dim3(a.N * a.H), dim3(256), lds, s, t_ev_a, t_ev_b, 0, a);
+  if (!set) { hipFuncSetAttribute((const void*)attn_fwd_kernel<T, NKT, CAUSAL, PFX>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); set = true; }
+  hipExtLaunchKernelGGL((attn_fwd_kernel<T, NKT, CAUSAL, PFX>), dim3((a.N + (PFX ? 1 : 0)) * a.H), dim3(256), lds, s, t_ev_a, t_ev_b, 0, a);
   return hipGetLastError();
 }
-template <typename T, int NKT, bool CAUSAL>
+template <typename T, int NKT, bool CAUSAL, bool PFX = false>
 static hipError_t bwd_t(const AttnBwdArgs& a, hipStream_t s) {
   constexpr int LP = NKT * 16;
   constexpr int lds_a = 2 * LP * 128;
   constexpr int lds_b = 2 * LP * 128 + 2 * LP * 4;
   static bool set = false;
   if (!set) {
-    hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<T, NKT, CAUSAL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_a);
-    hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<T, NKT, CAUSAL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);
+    hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<T, NKT, CAUSAL, PFX>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_a);
+    hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<T, NKT, CAUSAL, PFX>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_b);
     set = true;
   }
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, NKT, CAUSAL>), dim3(a.N * a.H), dim3(256), lds_a, s, a);
+  const dim3 grid((a.N + (PFX ? 1 : 0)) * a.H);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, NKT, CAUSAL, PFX>), grid, dim3(256), lds_a, s, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, NKT, CAUSAL>), dim3(a.N * a.H), dim3(256), lds_b, s, a);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, NKT, CAUSAL, PFX>), grid, dim3(256), lds_b, s, a);
+  if constexpr (PFX) {
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((attn_prefix_reduce_kernel<T>), dim3((2 * a.H * 64 + 255) / 256, a.L - a.prefix), dim3(1024), 0, s, a);
+  }
   return hipGetLastError();
+}
+// shared prefix: causal, at most 80 positions (nkt 2, 4, 6)
+template <typename T> static hipError_t fwd_pfx(int nkt, const AttnArgs& a, hipStream_t s) {
+  if (nkt == 2) return fwd_t<T, 2, true, true>(a, s);
+  if (nkt == 4) return fwd_t<T, 4, true, true>(a, s);
+  if (nkt == 6) return fwd_t<T, 6, true, true>(a, s);
+  return hipErrorInvalidValue;
+}
+template <typename T> static hipError_t bwd_pfx(int nkt, const AttnBwdArgs& a, hipStream_t s) {
+  if (nkt == 2) return bwd_t<T, 2, true, true>(a, s);
+  if (nkt == 4) return bwd_t<T, 4, true, true>(a, s);
+  if (nkt == 6) return bwd_t<T, 6, true, true>(a, s);
+  return hipErrorInvalidValue;
 }
 
 #define MVLPT_NKT_SWITCH(FN, ARGS)                                  \
@@ -707,6 +845,12 @@ hipError_t launch_attn_fwd(int dtype, const AttnArgs& a_, hipStream_t s, hipEven
   AttnArgs a = a_;
   a.flags = 3;
   if (a.L <= 0 || a.L > attn_max_len() || a.N <= 0) return hipErrorInvalidValue;
+  if (a.prefix != 0) {      // shared prefix (AttnArgs::prefix)
+    if (a.prefix < 0 || 2 * a.prefix > a.L || a.L > 80 || !a.causal || a.q_rows > 0) return hipErrorInvalidValue;
+    if (dtype == DT_F16) return fwd_pfx<f16>(nkt_for(a.L), a, s);
+    if (dtype == DT_BF16) return fwd_pfx<bf16>(nkt_for(a.L), a, s);
+    return hipErrorInvalidValue;
+  }
   if (use_stream(a.L)) return launch_attn_fwd_stream(dtype, a, s);
   // persistent variant for the headline's shape: 13 key tiles, full sequences, at least two heads per compute unit of the stream
   if (!a.causal && a.q_rows <= 0 && (a.L + 15) / 16 == PNT && (dtype == DT_F16 || dtype == DT_BF16)) {
@@ -734,6 +878,12 @@ hipError_t launch_attn_bwd(int dtype, const AttnBwdArgs& a, hipStream_t s) {
   if (a.L <= 0 || a.L > attn_max_len() || a.N <= 0) return hipErrorInvalidValue;
   // a gradient shorter than the saved sequences (AttnBwdArgs::Ls): causal, resident kernels only
   if (a.Ls > 0 && a.Ls != a.L && (a.Ls < a.L || !a.causal || use_stream(a.L))) return hipErrorInvalidValue;
+  if (a.prefix != 0) {      // shared prefix (AttnBwdArgs::prefix)
+    if (a.prefix < 0 || 2 * a.prefix > a.L || a.L > 80 || !a.causal || !a.kv_part) return hipErrorInvalidValue;
+    if (dtype == DT_F16) return bwd_pfx<f16>(nkt_for(a.L), a, s);
+    if (dtype == DT_BF16) return bwd_pfx<bf16>(nkt_for(a.L), a, s);
+    return hipErrorInvalidValue;
+  }
   if (use_stream(a.L)) return launch_attn_bwd_stream(dtype, a, s);
   const int nkt = nkt_for(a.L);      // (key tiles of the positions that carry a gradient)
   if (dtype == DT_F16) return a.causal ? bwd_n<f16, true>(nkt, a, s) : bwd_n<f16, false>(nkt, a, s);

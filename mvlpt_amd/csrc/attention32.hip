@@ -547,6 +547,22 @@ __device__ __forceinline__ void stage_short(char* hi, char* lo, const T* src, si
     dma_raw<16>(g + lo_off, lo + sl * 1024);
   }
 }
+// stage_short under a shared prefix (Attn32Args::prefix): positions below `split` come from src_pre, the others from src
+// (position p at src + p * ld either way: the callers fold the slot offsets into the two pointers)
+template <typename T>
+__device__ __forceinline__ void stage_short_pfx(char* hi, char* lo, const T* src_pre, const T* src, int split, size_t lo_off, size_t ld, int L,
+                                                int wave, int lane) {
+  const int srow = lane >> 3, chunk = (lane & 7) ^ srow;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int sl = wave + SNT * i;
+    int row = sl * 8 + srow;
+    row = row < L ? row : L - 1;
+    const T* g = (row < split ? src_pre : src) + (ptrdiff_t)row * (ptrdiff_t)ld + chunk * 8;
+    dma_raw<16>(g, hi + sl * 1024);
+    dma_raw<16>(g + lo_off, lo + sl * 1024);
+  }
+}
 // one streamed 16-row tile against the own rows: lane holds [own = fr][streamed = 16*kt + 4fg + r]
 template <typename T>
 __device__ __forceinline__ f32x4 tile_rows3(const char* hi, const char* lo, int kt, const typename Vec<T>::v8 (&oh)[2],
@@ -594,27 +610,54 @@ __device__ __forceinline__ void accum_all3(f32x4 (&out)[4], const char* hi, cons
 }
 }  // namespace
 
-template <typename T, bool CAUSAL>
+// PFX: the shared-prefix layout (Attn32Args::prefix > 0, q_rows == 0).  `split` is the first position a class sequence owns (0 in
+// the prefix's own workgroup row, whose length is P); position p sits at row p of slot 0 (p < split) or at row row0 + p.
+template <typename T, bool CAUSAL, bool PFX = false>
 __global__ __launch_bounds__(SNT * 64) void attn32t_fwd_kernel(Attn32Args a) {
   __shared__ __attribute__((aligned(16))) char sm[4 * TIMG];
   char *Kh = sm, *Kl = sm + TIMG, *Vh = sm + 2 * TIMG, *Vl = sm + 3 * TIMG;
   using v8 = typename Vec<T>::v8;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, fg = lane >> 4;
-  const int n = blockIdx.y, h = blockIdx.x, L = a.L, d = a.H * 64;
+  const int n = blockIdx.y, h = blockIdx.x, d = a.H * 64;
+  const bool own_pre = PFX && n == a.N;                       // the workgroup row of the prefix itself
+  const int L = own_pre ? a.prefix : a.L;
+  const int split = PFX && !own_pre ? a.prefix : 0;
+  const int Lf = PFX ? a.L - a.prefix : a.L;                  // rows per slot
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d;
-  const T* base = (const T*)a.qkv_split + (size_t)n * L * ld + h * 64;
-  stage_short<T>(Kh, Kl, base + d, lo, ld, L, wave, lane);
-  stage_short<T>(Vh, Vl, base + 2 * d, lo, ld, L, wave, lane);
+  const size_t row0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * Lf - a.prefix) : (size_t)n * L;
+  const T* base = (const T*)a.qkv_split + row0 * ld + h * 64;
+  const T* base_pre = (const T*)a.qkv_split + h * 64;
+  if constexpr (PFX) {
+    stage_short_pfx<T>(Kh, Kl, base_pre + d, base + d, split, lo, ld, L, wave, lane);
+    stage_short_pfx<T>(Vh, Vl, base_pre + 2 * d, base + 2 * d, split, lo, ld, L, wave, lane);
+  } else {
+    stage_short<T>(Kh, Kl, base + d, lo, ld, L, wave, lane);
+    stage_short<T>(Vh, Vl, base + 2 * d, lo, ld, L, wave, lane);
+  }
   const int nt = (L + 15) >> 4;
-  const int qlim = a.q_rows > 0 ? (a.q_rows < L ? a.q_rows : L) : L;
+  const int qlim = !PFX && a.q_rows > 0 ? (a.q_rows < L ? a.q_rows : L) : L;
   const int q = wave * 16 + fr, qc = q < L ? q : L - 1;
   v8 Qh[2], Ql[2];
-  load_own_pair<T>(Qh, Ql, base + (size_t)qc * ld, lo, fg);
+  load_own_pair<T>(Qh, Ql, (qc < split ? base_pre : base) + (size_t)qc * ld, lo, fg);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (a.lse && qlim < L)          // rows that are not computed: lse = +huge (P = 0 in a backward over the full sequence)
+  if (!PFX && a.lse && qlim < L)          // rows that are not computed: lse = +huge (P = 0 in a backward over the full sequence)
     for (int j = qlim + tid; j < L; j += SNT * 64) a.lse[((size_t)n * a.H + h) * L + j] = 3.0e38f;
+  if constexpr (PFX) {
+    // the unused rows P .. Lf-1 of slot 0 (this head's columns, and their lse): zeros, so that the row-wise kernels behind the
+    // attention meet finite, deterministic values there; no result reads them
+    if (own_pre) {
+      for (int i = tid; i < (Lf - L) * 16; i += SNT * 64) {
+        const int r = L + (i >> 4), c = (i & 15) * 4;
+        T* zrow = (T*)a.out_split + (size_t)r * (2 * (size_t)d) + h * 64 + c;
+        store_pair4_m<T>(zrow, d, h * 64 + c, f32x4{0.f, 0.f, 0.f, 0.f}, a.out_lo8);
+      }
+      if (a.lse)
+        for (int j = L + tid; j < Lf; j += SNT * 64) a.lse[(size_t)h * Lf + j] = 0.f;
+    }
+  }
   if (wave * 16 >= qlim || wave >= nt) return;
+  if (PFX && wave * 16 + 15 < split) return;      // a tile of prefix queries only: the prefix's own workgroup row computes them
   const int kt_end = CAUSAL ? wave + 1 : nt;
   f32x4 S[SNT];
   float mx = -INFINITY;
@@ -646,18 +689,25 @@ __global__ __launch_bounds__(SNT * 64) void attn32t_fwd_kernel(Attn32Args a) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) O[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   accum_all3<T>(O, Vh, Vl, S, 0, kt_end, fr, fg);
-  if (q < qlim) {
+  if (q < qlim && q >= split) {
     const float inv = 1.f / sum;
-    T* orow = (T*)a.out_split + ((size_t)n * L + q) * (2 * (size_t)d) + h * 64;
+    T* orow = (T*)a.out_split + (row0 + q) * (2 * (size_t)d) + h * 64;
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, d, h * 64 + 16 * dt + 4 * fg, O[dt] * inv, a.out_lo8);
-    if (a.lse && fg == 0) a.lse[((size_t)n * a.H + h) * L + q] = mx * SCALE + logf(sum);
+    if (a.lse && fg == 0) {
+      if constexpr (PFX) a.lse[((size_t)(own_pre ? 0 : n + 1) * a.H + h) * Lf + (q - split)] = mx * SCALE + logf(sum);
+      else a.lse[((size_t)n * a.H + h) * L + q] = mx * SCALE + logf(sum);
+    }
   }
 }
 
 // (4 waves per SIMD = 128 VGPRs, three workgroups per CU instead of the two that the unconstrained 136 allowed: 100 sequences
 // 55.9 -> 51.2 us, 2191 sequences 1 192 -> 1 010 us per layer; the forward at 5 waves per SIMD (96 VGPRs, 3 spilled) got slower)
-template <typename T, bool CAUSAL>
+// PFX: the shared-prefix layout (Attn32BwdArgs::prefix > 0).  As in the forward, `split` is the first position a class sequence owns;
+// srow0 + p / grow0 + p are the rows of position p >= split in the saved and in the gradient tensors, row p of slot 0 holds p < split.
+// A class sequence's queries below split carry no gradient: their lse is taken as +inf (P = 0 exactly) and their delta as 0, so the
+// dO rows staged for them (slot 0, finite) drop out of dK / dV without a mask in the product loops.
+template <typename T, bool CAUSAL, bool PFX = false>
 __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs a) {
   // one set of four images (40 KiB, three workgroups per CU): K, V while the waves own query tiles (phase A: dQ), then Q, dO
   // while they own key tiles (phase B: dK, dV); the own rows live in registers in both phases.  (Eight images in flight
@@ -668,30 +718,50 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
   using v8 = typename Vec<T>::v8;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, fg = lane >> 4;
   // L: the positions that carry a gradient (dO, dQKV rows per sequence); Ls: the pitch of the saved tensors (Attn32BwdArgs::Ls)
-  const int n = blockIdx.y, h = blockIdx.x, L = a.L, Ls = a.Ls > 0 ? a.Ls : a.L, d = a.H * 64;
+  const int n = blockIdx.y, h = blockIdx.x, d = a.H * 64;
+  const bool own_pre = PFX && n == a.N;                       // the workgroup row of the prefix itself
+  const int L = own_pre ? a.prefix : a.L, Ls = a.Ls > 0 ? a.Ls : a.L;
+  const int split = PFX && !own_pre ? a.prefix : 0;
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d, gld = 2 * (size_t)d;
-  const T* base = (const T*)a.qkv_split + (size_t)n * Ls * ld + h * 64;
-  const T* gbase = (const T*)a.dout_split + (size_t)n * L * gld + h * 64;
+  // rows of position p >= split: saved tensors / gradient tensors (PFX: slots of Ls - P and of a.L - P rows)
+  const size_t srow0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * (Ls - a.prefix) - a.prefix) : (size_t)n * Ls;
+  const size_t grow0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * (a.L - a.prefix) - a.prefix) : (size_t)n * L;
+  const T* base = (const T*)a.qkv_split + srow0 * ld + h * 64;
+  const T* gbase = (const T*)a.dout_split + grow0 * gld + h * 64;
+  const T* base_pre = (const T*)a.qkv_split + h * 64;
+  const T* gbase_pre = (const T*)a.dout_split + h * 64;
 #ifdef MVLPT_ATTN_TRACE
   int atr_n = 0;
 #endif
   MVLPT_ATRB(40);
-  stage_short<T>(I0h, I0l, base + d, lo, ld, L, wave, lane);          // K
-  stage_short<T>(I1h, I1l, base + 2 * d, lo, ld, L, wave, lane);      // V
-  const size_t stat0 = ((size_t)n * a.H + h) * Ls;
+  if constexpr (PFX) {
+    stage_short_pfx<T>(I0h, I0l, base_pre + d, base + d, split, lo, ld, L, wave, lane);              // K
+    stage_short_pfx<T>(I1h, I1l, base_pre + 2 * d, base + 2 * d, split, lo, ld, L, wave, lane);      // V
+  } else {
+    stage_short<T>(I0h, I0l, base + d, lo, ld, L, wave, lane);          // K
+    stage_short<T>(I1h, I1l, base + 2 * d, lo, ld, L, wave, lane);      // V
+  }
   const int nt = (L + 15) >> 4;
   const int row = wave * 16 + fr, rc = row < L ? row : L - 1;     // own row: query in phase A, key in phase B
+  const bool in_pre = rc < split;                                 // (PFX) the own row is a prefix position of a class sequence
   v8 Qh[2], Ql[2], Gh[2], Gl[2], Kh[2], Kl[2], Vh[2], Vl[2];
-  load_own_pair<T>(Qh, Ql, base + (size_t)rc * ld, lo, fg);
-  load_own_pair<T>(Gh, Gl, gbase + (size_t)rc * gld, d, fg);
+  load_own_pair<T>(Qh, Ql, (in_pre ? base_pre : base) + (size_t)rc * ld, lo, fg);
+  load_own_pair<T>(Gh, Gl, (in_pre ? gbase_pre : gbase) + (size_t)rc * gld, d, fg);
   float dl = 0.f;       // delta = rowsum(dO * O) of the own query row
   {
     // dO of the own row is in registers already (Gh, Gl): O in the same fragment layout, no second read of dO
-    const T* orow = (const T*)a.out_split + ((size_t)n * Ls + rc) * gld + h * 64;
+    const T* orow = (const T*)a.out_split + ((in_pre ? 0 : srow0) + rc) * gld + h * 64;
     dl = delta_part<T>(orow, d, h * 64, fg, a.lo8, Gh, Gl);
     dl = quad_sum(dl);
   }
-  const float nlse = -a.lse[stat0 + rc] * LOG2E;
+  float nlse;
+  if constexpr (PFX) {
+    const int Lf = Ls - a.prefix;
+    nlse = -a.lse[in_pre ? (size_t)h * Lf + rc : ((size_t)(own_pre ? 0 : n + 1) * a.H + h) * Lf + (rc - split)] * LOG2E;
+    if (in_pre) { nlse = -INFINITY; dl = 0.f; }
+  } else {
+    nlse = -a.lse[((size_t)n * a.H + h) * Ls + rc] * LOG2E;
+  }
   if (fg == 0) { nlse_s[row] = nlse; del_s[row] = dl; }
   MVLPT_ATRB(41);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -706,9 +776,9 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
   }
   asm volatile("" ::: "memory");
   const bool active = wave < nt;
-  T* orow = (T*)a.dqkv_split + ((size_t)n * L + rc) * ld + h * 64;
-  // ---- phase A: own query tile -> dQ
-  if (active) {
+  T* orow = (T*)a.dqkv_split + ((in_pre ? 0 : grow0) + rc) * ld + h * 64;
+  // ---- phase A: own query tile -> dQ (PFX: not for a tile of prefix queries only; the prefix's own workgroup row has them)
+  if (active && wave * 16 + 15 >= split) {
     const int kt_end = CAUSAL ? wave + 1 : nt;
     f32x4 dS[SNT];
 #pragma unroll
@@ -732,7 +802,7 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
     for (int i = 0; i < 4; ++i) dQ[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     accum_all3<T>(dQ, I0h, I0l, dS, 0, kt_end, fr, fg);
     MVLPT_ATRB(44);
-    if (row < L) {
+    if (row < L && row >= split) {
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, lo, h * 64 + 16 * dt + 4 * fg, dQ[dt] * SCALE, a.lo8);
     }
@@ -740,8 +810,13 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
   MVLPT_ATRB(45);
   __syncthreads();
   MVLPT_ATRB(46);
-  stage_short<T>(I0h, I0l, base, lo, ld, L, wave, lane);              // Q
-  stage_short<T>(I1h, I1l, gbase, d, gld, L, wave, lane);             // dO
+  if constexpr (PFX) {
+    stage_short_pfx<T>(I0h, I0l, base_pre, base, split, lo, ld, L, wave, lane);             // Q
+    stage_short_pfx<T>(I1h, I1l, gbase_pre, gbase, split, d, gld, L, wave, lane);           // dO (below split: see above)
+  } else {
+    stage_short<T>(I0h, I0l, base, lo, ld, L, wave, lane);              // Q
+    stage_short<T>(I1h, I1l, gbase, d, gld, L, wave, lane);             // dO
+  }
   MVLPT_ATRB(47);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -774,7 +849,15 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
     accum_all3<T>(dV, I1h, I1l, P, qt_lo, nt, fr, fg);
     accum_all3<T>(dK, I0h, I0l, dS, qt_lo, nt, fr, fg);
     MVLPT_ATRB(50);
-    if (row < L) {
+    if (PFX && row < L && (own_pre || in_pre)) {
+      // a prefix key: fp32 partial [sequence (N: the prefix's own), P, dK (d) | dV (d)], summed by attn32t_prefix_reduce_kernel
+      float* prow = a.kv_part + ((size_t)n * a.prefix + row) * gld + h * 64;
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt) {
+        *(f32x4*)(prow + 16 * dt + 4 * fg) = dK[dt] * SCALE;
+        *(f32x4*)(prow + d + 16 * dt + 4 * fg) = dV[dt];
+      }
+    } else if (row < L) {
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
         store_pair4_m<T>(orow + d + 16 * dt + 4 * fg, lo, d + h * 64 + 16 * dt + 4 * fg, dK[dt] * SCALE, a.lo8);
@@ -783,6 +866,41 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
     }
   }
   MVLPT_ATRB(51);
+}
+
+// dK / dV of the shared prefix (Attn32BwdArgs::kv_part): slot 0 row p of dqkv = kv_part[N][p] + mul * sum_n kv_part[n][p] in the pair
+// format, and zeros in the unused rows P .. Lt-1 of slot 0 (all of dQ | dK | dV), so that the row-wise kernels behind it meet finite
+// values there.  One workgroup per (row, 256 columns of dK | dV): 16 waves, wave w adds sequences w, w + 16, ... and wave 0 adds the
+// sixteen partial sums in order on top of the prefix's own term: a fixed order, so two runs give the same bits.  (Not class order:
+// a serial pass over the classes per element would put C dependent adds behind C loads in one thread; that the interleaved form
+// is the faster one is reasoned from the context gather's shape, not measured.)
+template <typename T>
+__global__ __launch_bounds__(1024) void attn32t_prefix_reduce_kernel(Attn32BwdArgs a) {
+  __shared__ f32x4 part[16][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int d = a.H * 64, P = a.prefix, Lt = a.L - P, p = blockIdx.y;
+  const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d, gld = 2 * (size_t)d;
+  const int c = (blockIdx.x * 64 + lane) * 4;      // column inside dK (d) | dV (d)
+  T* orow = (T*)a.dqkv_split + (size_t)p * ld;
+  if (p >= P) {
+    // an unused row: this workgroup's share of its 3d columns is 384 of them (256 of 2d -> 384 of 3d)
+    const int col = blockIdx.x * 384 + (int)threadIdx.x * 4;
+    if (p < Lt && threadIdx.x < 96 && col < 3 * d) store_pair4_m<T>(orow + col, lo, col, f32x4{0.f, 0.f, 0.f, 0.f}, a.lo8);
+    return;
+  }
+  const bool ok = c < 2 * d;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  if (ok)
+    for (int k = wave; k < a.N; k += 16) acc += *(const f32x4*)(a.kv_part + ((size_t)k * P + p) * gld + c);
+  part[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && ok) {
+    f32x4 t = part[0][lane];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) t += part[w][lane];
+    t = *(const f32x4*)(a.kv_part + ((size_t)a.N * P + p) * gld + c) + t * a.part_mul;
+    store_pair4_m<T>(orow + d + c, lo, d + c, t, a.lo8);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------ resident, medium sequences
@@ -1272,6 +1390,12 @@ static hipError_t bwd_x(const Attn32BwdArgs& a, hipStream_t s) {
 
 template <typename T>
 static hipError_t fwd_t(const Attn32Args& a, hipStream_t s) {
+  if (a.prefix != 0) {      // shared prefix: the short causal kernel, every query, N + 1 workgroup rows
+    // (2 P <= L: the prefix fits slot 0 and no slot offset goes negative, as in the backward)
+    if (a.prefix < 0 || 2 * a.prefix > a.L || a.L > SROWS || !a.causal || a.q_rows > 0 || a.N >= 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((attn32t_fwd_kernel<T, true, true>), dim3(a.H, a.N + 1), dim3(SNT * 64), 0, s, a);
+    return hipGetLastError();
+  }
   if (a.L <= SROWS) {
     dim3 grid(a.H, a.N), block(SNT * 64);
     if (a.causal) hipLaunchKernelGGL((attn32t_fwd_kernel<T, true>), grid, block, 0, s, a);
@@ -1300,6 +1424,12 @@ template <typename T>
 static hipError_t bwd_t(const Attn32BwdArgs& a, hipStream_t s) {
   // a gradient shorter than the saved sequences: the short causal kernel only (the others take every position)
   if (a.Ls > 0 && a.Ls != a.L && (a.Ls < a.L || a.L > SROWS || !a.causal)) return hipErrorInvalidValue;
+  if (a.prefix != 0) {      // shared prefix: slots of L - P gradient rows must hold the P prefix rows
+    if (a.prefix < 0 || 2 * a.prefix > a.L || a.L > SROWS || !a.causal || !a.kv_part || a.N >= 65535) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((attn32t_bwd_kernel<T, true, true>), dim3(a.H, a.N + 1), dim3(SNT * 64), 0, s, a);
+    hipLaunchKernelGGL((attn32t_prefix_reduce_kernel<T>), dim3((2 * a.H * 64 + 255) / 256, a.L - a.prefix), dim3(1024), 0, s, a);
+    return hipGetLastError();
+  }
   if (a.L <= SROWS) {
     dim3 grid(a.H, a.N), block(SNT * 64);
     if (a.causal) hipLaunchKernelGGL((attn32t_bwd_kernel<T, true>), grid, block, 0, s, a);

@@ -21,6 +21,20 @@ __device__ __forceinline__ void stage_rows_dma(char* dst, const T* src, size_t l
     else glds16(src + (size_t)row * ld + chunk * 8, dst + sl * 1024);
   }
 }
+// stage_rows_dma under a shared prefix (kernels.h AttnArgs::prefix): positions below `split` come from src_pre, the others from src
+// (position p at p * ld of either pointer: the callers fold the slot offsets into the two pointers)
+template <typename T>
+__device__ __forceinline__ void stage_rows_dma_pfx(char* dst, const T* src_pre, const T* src, int split, size_t ld, int L, int LP, int wave,
+                                                   int lane, bool nt = false) {
+  const int srow = lane >> 3, chunk = (lane & 7) ^ srow;
+  for (int sl = wave; sl < LP / 8; sl += 4) {
+    int row = sl * 8 + srow;
+    row = row < L ? row : L - 1;
+    const T* g = (row < split ? src_pre : src) + (size_t)row * ld + chunk * 8;
+    if (nt) glds16_nt(g, dst + sl * 1024);
+    else glds16(g, dst + sl * 1024);
+  }
+}
 // LDS-DMA issued from inline assembly.  With the builtin, the compiler's wait-count pass knows an LDS write is in
 // flight and puts `s_waitcnt vmcnt(0)` in front of every ds_read_b64_tr_b16 — which would serialise the DMA of chunk
 // c+1 behind the arithmetic on chunk c.  Through asm the only waits are the counted ones written in the kernels

@@ -155,6 +155,15 @@ struct TowerState {
   // (dx32 .. delta) is compact [N, Lg, .]; the saved forward tensors keep the pitch L and are read through the row map
   // r -> (r / Lg) * L + r % Lg.  Lg == L: every position (the image tower, and the text tower's default).
   int Lg = 0;
+  // Shared prefix of a text tower (mvlpt_set_text_shared_prefix; 0: none).  P > 0: the first P positions are the same rows in every
+  // class sequence and are evaluated once.  The tower then runs over N = C + 1 "slots" of L rows: slot 0 holds the prefix in its first
+  // P rows, slot c + 1 positions P .. of class c, so L and Lg above are the sequence and gradient lengths MINUS P and every row-wise
+  // kernel and row map works on the slots unchanged.  Only the attention core (Attn32Args::prefix), the prompt tables (glue.hip) and
+  // the last block's compact rows (C of them) know.  kv_part: the attention backward's fp32 dK / dV partials of the prefix keys
+  // [N, P, 2d]; part_mul = 2^-s: what they are scaled by when they enter slot 0 (the sum over many classes must stay inside the
+  // 16-bit hi plane), undone by the context gather.
+  int P = 0; float* kv_part = nullptr; float part_mul = 1.f;
+  int seqs() const { return P > 0 ? N - 1 : N; }      // sequences that end in a compact row
   int hw = 64;                           // head width d / H: 64, or a wide-headed image tower's 80 / 96 / 112 / 128 (attention_wide.hip)
   std::vector<float*> x;                 // 2*layers+1 entries (all equal when !saved)
   std::vector<void*> qkv, attn, u;       // per layer (all equal when !saved)
@@ -262,6 +271,7 @@ struct Engine {
   int text_act_ckpt = 1;      // segments of the text tower's activation checkpointing (mvlpt_set_text_act_ckpt; 1: everything is saved)
   // mvlpt_set_text_grad_len: gradient length of the next saving text forwards (0: every position) and the caller's largest EOT position
   int text_grad_len = 0, text_max_eot = 0;
+  int text_shared_prefix = 0;      // mvlpt_set_text_shared_prefix: leading positions every class shares (0: off); the next text forward consumes it
   int fold_min_rows = 1024;   // towers with fewer token rows keep the stand-alone LayerNorm (a handful of tiles: nothing to win)
   bool fold_ready = false;
   // packed residual stream: the fp16 image tower without prompts and without a backward carries x as hi (fp16, at the
@@ -424,9 +434,10 @@ int wide_pitch(int cols) {
 // gelu (Engine::act == ACT_GELU): one more fp32 [T, 4d] buffer, the scratch of the stand-alone activation pass
 // Lg (TowerState::Lg; 0: L): the gradient buffers hold N * Lg rows
 void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool save, bool causal, bool exact, int xs, bool gelu,
-                 int segments = 1, int Lg = 0) {
+                 int segments = 1, int Lg = 0, int P = 0) {
   const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1; const int nl = W.layers;
   st = TowerState();
+  st.P = P;      // (N, L, Lg are the slot figures then: TowerState::P)
   st.N = N; st.L = L; st.Lg = Lg > 0 ? Lg : L; st.d = (int)d; st.H = (int)H; st.hw = (int)(d / H); st.layers = nl; st.causal = causal; st.exact = exact;
   st.xs = exact ? xs : 0;
   st.seg = ckpt_plan(nl, save ? segments : 1);
@@ -477,6 +488,7 @@ void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool s
     st.dx16 = bp.take_bytes(Tg * d * 2 * X); st.dh32 = bp.take<float>(Tg * d); st.dO16 = bp.take_bytes(Tg * d * 2 * X);
     st.du16 = bp.take_bytes(Tg * (4 * d * 2 * X + 128)); st.dqkv16 = bp.take_bytes(Tg * 3 * d * 2 * X);
     st.delta = bp.take<float>((size_t)N * H * st.Lg);
+    if (P > 0) st.kv_part = bp.take<float>((size_t)N * P * 2 * d);
     st.scale_dev = bp.take<float>(4);   // {scale, 1/scale, amax scratch, pad}
   }
   if (gelu) st.act32 = bp.take<float>(T * 4 * d);
@@ -501,13 +513,14 @@ int attn_fwd(Engine* E, TowerState& st, int l, int q_rows, bool timed, hipStream
     return 0;
   }
   if (st.xs) {
-    Attn32Args a{st.qkv[l], st.attn[l], lse, st.N, st.L, st.H, st.causal ? 1 : 0, q_rows};
-    a.out_lo8 = st.xs == 2 ? 1 : 0;
+    Attn32Args a{st.qkv[l], st.attn[l], lse, st.seqs(), st.L + st.P, st.H, st.causal ? 1 : 0, q_rows};
+    a.out_lo8 = st.xs == 2 ? 1 : 0; a.prefix = st.P;
     ProfScope ps(E, s, PC_ATTN_FWD, fl, T * st.d * 16.0);
     HIPCHK(E, launch_attn32_fwd(E->dt, a, s));
     return 0;
   }
-  AttnArgs a{st.qkv[l], st.attn[l], lse, st.N, st.L, st.H, st.causal ? 1 : 0, q_rows};
+  AttnArgs a{st.qkv[l], st.attn[l], lse, st.seqs(), st.L + st.P, st.H, st.causal ? 1 : 0, q_rows};
+  a.prefix = st.P;      // (shared prefix: slots, TowerState::P)
   const double by = T * st.d * 2.0 * (q_rows > 0 ? 2.0 : 4.0);
   ProfScope ps(E, s, PC_ATTN_FWD, fl, by);
   HIPCHK(E, timed ? attn_fwd_timed(E, a, fl, by, s) : launch_attn_fwd(E->dt, a, s));
@@ -525,14 +538,16 @@ int attn_bwd(Engine* E, TowerState& st, int l, const Compact* cls, hipStream_t s
   // (the positions that carry a gradient: st.Lg of the st.L saved ones)
   const double fl = 14.0 * st.Lg * st.Lg * 64.0 * st.N * st.H * cz, Tg = (double)st.N * st.Lg;
   if (st.xs) {
-    Attn32BwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.Lg, st.H, st.causal ? 1 : 0};
-    a.lo8 = st.xs == 2 ? 1 : 0; a.Ls = st.L;
+    Attn32BwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.seqs(), st.Lg + st.P, st.H, st.causal ? 1 : 0};
+    a.lo8 = st.xs == 2 ? 1 : 0; a.Ls = st.L + st.P;
+    a.prefix = st.P; a.kv_part = st.kv_part; a.part_mul = st.part_mul;      // (shared prefix: one more launch, the reduction of kv_part)
     ProfScope ps(E, s, PC_ATTN_BWD, fl, Tg * st.d * 32.0);
     HIPCHK(E, launch_attn32_bwd(E->dt, a, s));
     return 0;
   }
-  AttnBwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.N, st.Lg, st.H, st.causal ? 1 : 0};
-  a.Ls = st.L;
+  AttnBwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.seqs(), st.Lg + st.P, st.H, st.causal ? 1 : 0};
+  a.Ls = st.L + st.P;
+  a.prefix = st.P; a.kv_part = st.kv_part; a.part_mul = st.part_mul;
   ProfScope ps(E, s, PC_ATTN_BWD, fl, Tg * st.d * 2.0 * 8.0);
   HIPCHK(E, launch_attn_bwd(E->dt, a, s));
   return 0;
@@ -694,7 +709,7 @@ hipError_t move_rows(const void* src, void* dst, const int32_t* rows, int R, int
 // ln_close: ln_post / ln_final, into c.out32.  ck: mvlpt_debug_checksums fingerprints (image tower only).
 int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const int32_t* rows, int q_rows, bool packed, bool ln1_ready,
                    const LNp& ln_close, bool ck, hipStream_t s) {
-  const int l = st.layers - 1, T = st.N * st.L, R = st.N, d = st.d;
+  const int l = st.layers - 1, T = st.N * st.L, R = st.seqs(), d = st.d;
   const int xs = st.xs;                 // split-precision operands (hi|lo pairs, twice the columns) + pair-product attention
   const size_t X = xs ? 2 : 1;
   const Block& Bk = W.blocks[l];
@@ -728,7 +743,7 @@ int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const
 // into a zeroed dO16 and runs the attention backward at full width.
 int last_block_bwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const int32_t* rows, int q_rows, const LNp& ln_close, hipStream_t s) {
   // (T: the full-width rows that carry a gradient, TowerState::Lg, compact in the gradient buffers)
-  const int l = st.layers - 1, T = st.N * st.Lg, R = st.N, d = st.d, xs = st.xs;
+  const int l = st.layers - 1, T = st.N * st.Lg, R = st.seqs(), d = st.d, xs = st.xs;
   const int ms = st.Lg != st.L ? st.Lg : 0, mp = ms ? st.L : 0;
   const size_t X = xs ? 2 : 1;
   const Block& Bk = W.blocks[l];
@@ -1671,14 +1686,27 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 // engine's activation-checkpointing setting (mvlpt_set_text_act_ckpt).
 // Lg: the gradient length of a saving tower (text_grad_len below; L: every position).
 static void text_layout(Bump& bp, const Engine* E, TextRun& R, int C, int L, bool save, bool exact, size_t ctx_rows, size_t range_ints,
-                        size_t ids_ints, int Lg) {
+                        size_t ids_ints, int Lg, int P = 0) {
   const bool gelu = E->act == ACT_GELU;
   carve_compact(bp, R.c, C, E->arch.text_width, exact ? 2 : 1, gelu);
   R.eot_rows = bp.take<int32_t>(C);
   R.ctx_pos = bp.take<int32_t>(ctx_rows);
   R.range = range_ints ? bp.take<int32_t>(range_ints) : nullptr;
   R.ids = ids_ints ? bp.take<int32_t>(ids_ints) : nullptr;
-  carve_tower(bp, E->txt, R.st, C, L, save, true, exact, split_kind(E), gelu, E->text_act_ckpt, Lg);
+  // (a shared prefix: C + 1 slots of L - P rows, TowerState::P)
+  if (P > 0) carve_tower(bp, E->txt, R.st, C + 1, L - P, save, true, exact, split_kind(E), gelu, E->text_act_ckpt, Lg - P, P);
+  else carve_tower(bp, E->txt, R.st, C, L, save, true, exact, split_kind(E), gelu, E->text_act_ckpt, Lg);
+}
+// The shared prefix a plain forward runs under (mvlpt_set_text_shared_prefix): the setting, lowered until the prefix fits a gradient
+// slot (P <= Lg - P) and a slot keeps MVLPT_TEXT_MIN_L rows (Lg - P >= 3); 0 on every route that does not take one: class-specific or
+// deep contexts, the ranged and token-id towers, activation checkpointing, sequences the short kernels do not take.  Split and single
+// operands alike (attention32.hip / attention.hip).  `setting`: what the forward took out of Engine::text_shared_prefix.
+static int text_prefix_len(const Engine* E, int setting, TextKind kind, int ctx_per_class, int n_ctx, int n_deep, int L, int Lg) {
+  if (setting <= 0 || kind != TextKind::Plain || ctx_per_class || n_ctx <= 0 || n_deep > 0 || L > 80 || E->text_act_ckpt != 1)
+    return 0;
+  int P = std::min(setting, L - 1);
+  P = std::min(P, std::min(Lg / 2, Lg - 3));
+  return P > 0 ? P : 0;
 }
 // The gradient length a saving forward over sequences of L positions runs under (mvlpt_set_text_grad_len): the setting, at most L
 static int text_grad_len(const Engine* E, int L) { return E->text_grad_len > 0 && E->text_grad_len < L ? E->text_grad_len : L; }
@@ -1731,6 +1759,10 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
                          const int32_t* layout, const int32_t* eot, int G, int Cg, int C, int L, float* feat_out, int save_for_bwd,
                          mvlpt_stream_t stream, const float* ctx_deep = nullptr, int n_deep = 0) {
   const bool ranged = kind == TextKind::Ranged, ids = kind == TextKind::Ids;
+  // one-shot, taken before any check can refuse the call: the caller's proof holds for the tables of THIS forward only, whichever
+  // entry it came through and whether or not it runs
+  const int prefix_setting = E->text_shared_prefix;
+  E->text_shared_prefix = 0;
   if (int rc = mvlpt_frozen_ready(E)) return rc;
   if ((n_ctx > 0) != (ctx != nullptr) || n_ctx < 0 || n_ctx > L - 2) return fail(E, MVLPT_ERR_ARG, "text_fwd: ctx pointer and n_ctx disagree");
   const MvlptArch& A = E->arch;
@@ -1753,11 +1785,17 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
   const int Lg = save ? text_grad_len(E, L) : L;
   if (Lg < L && Lg <= E->text_max_eot)
     return fail(E, MVLPT_ERR_ARG, "text_fwd: the gradient length (mvlpt_set_text_grad_len) does not reach the largest EOT position");
+  const int P = text_prefix_len(E, prefix_setting, kind, ctx_per_class, n_ctx, n_deep, L, Lg);
   TextRun& R = E->trun = TextRun();      // opened: from here on the workspace no longer holds the last forward
   TowerState& st = R.st;
   if (int rc = carve_ws(E, E->txt_ws, "text_fwd", kTextSlack, [&](Bump& bp) {
-        text_layout(bp, E, R, C, L, save, exact, ctx_rows, range_ints, ids_ints, Lg);
+        text_layout(bp, E, R, C, L, save, exact, ctx_rows, range_ints, ids_ints, Lg, P);
       })) return rc;
+  if (P > 0) {      // the sum over more than 512 classes enters slot 0 scaled down by a power of two (TowerState::part_mul)
+    int sh = 0;
+    while (((int64_t)512 << sh) < C) ++sh;
+    st.part_mul = std::ldexp(1.0f, -sh);
+  }
   R.C = C; R.L = L; R.n_ctx = n_ctx; R.per_class = ctx_per_class; R.kind = kind; R.groups = G;
   R.n_deep = n_deep; R.ctx_deep = n_deep > 0 ? ctx_deep : nullptr;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
@@ -1776,9 +1814,9 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
       HIPCHK(E, launch_eot_rows_ranged(eot, R.eot_rows, seq_cls, C, L, s));
       if (save) HIPCHK(E, launch_build_ctx_pos(layout, R.ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
     } else {
-      HIPCHK(E, launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, E->tpos, st.x[0], C, L, dtw, s));
-      HIPCHK(E, launch_eot_rows(eot, R.eot_rows, C, L, s));
-      if ((save || n_deep > 0) && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(layout, R.ctx_pos, C, L, n_ctx, s));
+      HIPCHK(E, launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, E->tpos, st.x[0], C, L, dtw, s, P));
+      HIPCHK(E, launch_eot_rows(eot, R.eot_rows, C, L, s, P));
+      if ((save || n_deep > 0) && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(layout, R.ctx_pos, C, L, n_ctx, s, P, st.Lg));
     } }
   // Checkpointed segments (every one but the last, st.seg) run as a tower that saves nothing; their closing block writes the next
   // segment's boundary buffer.  No ln_1 is folded across a segment boundary, so mvlpt_text_bwd can repeat a segment launch for launch.
@@ -1894,6 +1932,15 @@ int mvlpt_set_text_grad_len(void* h, int grad_len, int max_eot) {
   return 0;
 }
 
+int mvlpt_set_text_shared_prefix(void* h, int prefix) {
+  Engine* E = (Engine*)h;
+  if (!E) return fail(E, MVLPT_ERR_ARG, "set_text_shared_prefix: null handle");
+  if (prefix < 0 || prefix >= E->arch.context_length)
+    return fail(E, MVLPT_ERR_ARG, "set_text_shared_prefix: the prefix must lie in [0, context_length)");
+  E->text_shared_prefix = prefix;      // consumed by the next text forward, which records what it ran under (TowerState::P)
+  return 0;
+}
+
 int mvlpt_text_act_ckpt_plan(void* h, int32_t* first_layer, int cap, int* n_segments) {
   Engine* E = (Engine*)h;
   if (!E || !first_layer || !n_segments || cap < 0) return fail(E, MVLPT_ERR_ARG, "text_act_ckpt_plan: null/invalid argument");
@@ -1931,8 +1978,9 @@ static int text_bwd_impl(Engine* E, const float* dfeat, float* dctx, float* dctx
   hipStream_t s = (hipStream_t)stream;
   const MvlptArch& A = E->arch;
   // L: the gradient length this forward was saved under (TowerState::Lg), the sequence pitch of every gradient buffer
+  // (under a shared prefix the buffers hold C + 1 slots of L rows: TowerState::P)
   const int C = R.C, L = st.Lg, dtw = A.text_width, e = A.embed_dim;
-  const size_t T = (size_t)C * L;
+  const size_t T = (size_t)st.N * L;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dtw * 10.0);
     HIPCHK(E, launch_grad_scale(dfeat, (size_t)C * e, 64.0f, st.scale_dev, s));
     HIPCHK(E, launch_sgemm_bt(dfeat, E->tproj, R.c.dout32, C, dtw, e, st.scale_dev, s)); }
@@ -1970,7 +2018,7 @@ static int text_bwd_impl(Engine* E, const float* dfeat, float* dctx, float* dctx
     if (R.kind == TextKind::Ranged)
       HIPCHK(E, launch_gather_ctx_grad_ranged(st.dx32, R.ctx_pos, R.range, R.range + R.groups, R.groups, L, dtw, R.n_ctx, dctx, st.scale_dev, s));
     else
-      HIPCHK(E, launch_gather_ctx_grad(st.dx32, R.ctx_pos, C, L, dtw, R.n_ctx, R.per_class, dctx, st.scale_dev, s)); }
+      HIPCHK(E, launch_gather_ctx_grad(st.dx32, R.ctx_pos, C, L, dtw, R.n_ctx, R.per_class, dctx, st.scale_dev, s, st.P, 1.f / st.part_mul)); }
   if (k == 1) R.phase = Phase::BwdDone;
   return 0;
 }
@@ -2364,6 +2412,42 @@ int mvlpt_op_attention_bwd_rows(int dtype, int pair, int lo8, const void* qkv, c
     a.Ls = seq_pitch;
     OPCHK(launch_attn_bwd(dtype, a, (hipStream_t)stream));
   }
+  return 0;
+}
+// ---- the pair attention under a shared prefix (mvlpt_set_text_shared_prefix; kernels.h Attn32Args::prefix): causal, slots
+int mvlpt_op_attention32_fwd_prefix(int dtype, int lo8, const void* qkv, void* out, float* lse, int N, int L, int H, int prefix,
+                                    mvlpt_stream_t stream) {
+  if (!qkv || !out || prefix <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_attention32_fwd_prefix: null/invalid argument");
+  Attn32Args a{qkv, out, lse, N, L, H, 1, 0};
+  a.out_lo8 = lo8; a.prefix = prefix;
+  OPCHK(launch_attn32_fwd(dtype, a, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_attention32_bwd_prefix(int dtype, int lo8, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+                                    void* dqkv, float* kv_part, float part_mul, int N, int grad_len, int seq_len, int H, int prefix,
+                                    mvlpt_stream_t stream) {
+  if (!qkv || !out || !dout || !lse || !delta || !dqkv || !kv_part || prefix <= 0 || seq_len < grad_len)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_attention32_bwd_prefix: null/invalid argument");
+  Attn32BwdArgs a{qkv, out, dout, lse, delta, dqkv, N, grad_len, H, 1};
+  a.lo8 = lo8; a.Ls = seq_len; a.prefix = prefix; a.kv_part = kv_part; a.part_mul = part_mul;
+  OPCHK(launch_attn32_bwd(dtype, a, (hipStream_t)stream));
+  return 0;
+}
+// ... and the single-operand attention (attention.hip) under a shared prefix: the fast mode's kernels, same slots, 16-bit tensors
+int mvlpt_op_attention_fwd_prefix(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int prefix, mvlpt_stream_t stream) {
+  if (!qkv || !out || prefix <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_attention_fwd_prefix: null/invalid argument");
+  AttnArgs a{qkv, out, lse, N, L, H, 1};
+  a.prefix = prefix;
+  OPCHK(launch_attn_fwd(dtype, a, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_attention_bwd_prefix(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
+                                  float* kv_part, float part_mul, int N, int grad_len, int seq_len, int H, int prefix, mvlpt_stream_t stream) {
+  if (!qkv || !out || !dout || !lse || !delta || !dqkv || !kv_part || prefix <= 0 || seq_len < grad_len)
+    return fail(nullptr, MVLPT_ERR_ARG, "op_attention_bwd_prefix: null/invalid argument");
+  AttnBwdArgs a{qkv, out, dout, lse, delta, dqkv, N, grad_len, H, 1};
+  a.Ls = seq_len; a.prefix = prefix; a.kv_part = kv_part; a.part_mul = part_mul;
+  OPCHK(launch_attn_bwd(dtype, a, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_layernorm_fwd(int out_dtype, const float* x, const float* gamma, const float* beta, void* y, int rows, int d,

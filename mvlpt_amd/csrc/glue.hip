@@ -527,9 +527,38 @@ __global__ void assemble_prompts_kernel(const float* __restrict__ prefix, const 
     return prompt_row(prefix, suffix, ctx + (size_t)(ctx_per_class ? cls * n_ctx : 0) * d, suf_len, layout[seq * L + pos_i], cls, d);
   });
 }
+// The same tokens in the shared-prefix layout (kernels.h Attn32Args::prefix): x holds C + 1 slots of L - P rows; slot 0 = positions
+// 0 .. P-1 as class 0 has them (the caller vouches that every class has the same) and zeros in its unused rows, slot c + 1 =
+// positions P .. L-1 of class c.  A generic context only.
+__global__ void assemble_prompts_prefix_kernel(const float* __restrict__ prefix, const float* __restrict__ suffix,
+                                               const float* __restrict__ ctx, int n_ctx, const int32_t* __restrict__ layout,
+                                               const float* __restrict__ pos, float* __restrict__ x, int C, int L, int d, int P) {
+  const int suf_len = L - 1 - n_ctx, Lf = L - P, d4 = d / 4;
+  const size_t total = (size_t)(C + 1) * Lf * d4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int c4 = (int)(i % d4);
+    const size_t tok = i / d4;
+    const int r = (int)(tok % Lf), slot = (int)(tok / Lf);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (slot > 0 || r < P) {
+      const int cls = slot > 0 ? slot - 1 : 0, pos_i = slot > 0 ? r + P : r;
+      const float* src = prompt_row(prefix, suffix, ctx, suf_len, layout[(size_t)cls * L + pos_i], cls, d);
+      v = *(const f32x4*)(src + c4 * 4) + *(const f32x4*)(pos + (size_t)pos_i * d + c4 * 4);
+    }
+    *(f32x4*)(x + tok * d + c4 * 4) = v;
+  }
+}
 hipError_t launch_assemble_prompts(const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
-                                   const int32_t* layout, const float* pos, float* x, int C, int L, int d, hipStream_t s) {
+                                   const int32_t* layout, const float* pos, float* x, int C, int L, int d, hipStream_t s, int shared_prefix) {
   if (d % 4) return hipErrorInvalidValue;
+  if (shared_prefix) {
+    if (shared_prefix < 0 || shared_prefix >= L || ctx_per_class) return hipErrorInvalidValue;
+    const size_t tot = (size_t)(C + 1) * (L - shared_prefix) * (d / 4);
+    const int g = (int)((tot + 255) / 256 < 8192 ? (tot + 255) / 256 : 8192);
+    hipLaunchKernelGGL(assemble_prompts_prefix_kernel, dim3(g), dim3(256), 0, s, prefix, suffix, ctx, n_ctx, layout, pos, x, C, L, d,
+                       shared_prefix);
+    return hipGetLastError();
+  }
   const size_t total = (size_t)C * L * (d / 4);
   const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
   hipLaunchKernelGGL(assemble_prompts_kernel, dim3(grid), dim3(256), 0, s, prefix, suffix, ctx, ctx_per_class, n_ctx, layout,
@@ -537,20 +566,28 @@ hipError_t launch_assemble_prompts(const float* prefix, const float* suffix, con
   return hipGetLastError();
 }
 
-__global__ void build_ctx_pos_kernel(const int32_t* __restrict__ layout, int32_t* __restrict__ ctx_pos, int C, int L, int n_ctx) {
+// P > 0 (shared-prefix layout, gradient slots of Lt rows): a position p >= P is stored as p - P + Lt, so that class c's row is
+// c * Lt + entry as ever ((c + 1) * Lt + p - P); a position p < P is stored as p, row p of slot 0 (entry < Lt: gather_ctx_grad_prefix_kernel)
+__global__ void build_ctx_pos_kernel(const int32_t* __restrict__ layout, int32_t* __restrict__ ctx_pos, int C, int L, int n_ctx, int P, int Lt) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= C * L) return;
-  const int e = layout[i];
-  if (e < 0) ctx_pos[(i / L) * n_ctx + (-e - 1)] = i % L;
+  const int e = layout[i], p = i % L;
+  if (e < 0) ctx_pos[(i / L) * n_ctx + (-e - 1)] = p < P ? p : p - P + Lt;
 }
-hipError_t launch_build_ctx_pos(const int32_t* layout, int32_t* ctx_pos, int C, int L, int n_ctx, hipStream_t s) {
+hipError_t launch_build_ctx_pos(const int32_t* layout, int32_t* ctx_pos, int C, int L, int n_ctx, hipStream_t s, int shared_prefix, int Lt) {
   if (n_ctx <= 0) return hipSuccess;
-  hipLaunchKernelGGL(build_ctx_pos_kernel, dim3((C * L + 255) / 256), dim3(256), 0, s, layout, ctx_pos, C, L, n_ctx);
+  if (shared_prefix < 0 || (shared_prefix > 0 && Lt < shared_prefix)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(build_ctx_pos_kernel, dim3((C * L + 255) / 256), dim3(256), 0, s, layout, ctx_pos, C, L, n_ctx, shared_prefix,
+                     shared_prefix > 0 ? Lt : 0);
   return hipGetLastError();
 }
-__global__ void eot_rows_kernel(const int32_t* __restrict__ eot, int32_t* __restrict__ rows, int C, int L) {
+// P > 0 (shared-prefix layout, slots of L - P rows): the row of position eot[c] >= P in slot c + 1; an EOT inside the prefix would be
+// a caller's error and is clamped to the slot's first row (a wrong result, never an access outside the slot)
+__global__ void eot_rows_kernel(const int32_t* __restrict__ eot, int32_t* __restrict__ rows, int C, int L, int P) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < C) rows[c] = c * L + eot[c];
+  if (c >= C) return;
+  if (P > 0) { const int e = eot[c] - P; rows[c] = (c + 1) * (L - P) + (e > 0 ? e : 0); }
+  else rows[c] = c * L + eot[c];
 }
 // dst[r] = src[idx[r]] (gather) or dst[idx[r]] = src[r] (scatter); rows of row_bytes (a multiple of 16) bytes
 __global__ void copy_rows_kernel(const char* __restrict__ src, char* __restrict__ dst, const int32_t* __restrict__ idx, int rows,
@@ -581,8 +618,9 @@ hipError_t launch_copy_rows(const void* src, void* dst, const int32_t* idx, int 
   return hipGetLastError();
 }
 
-hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipStream_t s) {
-  hipLaunchKernelGGL(eot_rows_kernel, dim3((C + 255) / 256), dim3(256), 0, s, eot, rows, C, L);
+hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipStream_t s, int shared_prefix) {
+  if (shared_prefix < 0 || shared_prefix >= L) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(eot_rows_kernel, dim3((C + 255) / 256), dim3(256), 0, s, eot, rows, C, L, shared_prefix);
   return hipGetLastError();
 }
 
@@ -644,10 +682,34 @@ __global__ __launch_bounds__(1024) void gather_ctx_grad_kernel(const float* __re
   const int j = blockIdx.y;
   gather_ctx_row(part, dx, ctx_pos, j, C, L, d, n_ctx, dctx, (size_t)j, scale_dev);
 }
+// shared-prefix layout (build_ctx_pos_kernel with P > 0; dx: C + 1 slots of L rows): a context row inside the prefix is row
+// ctx_pos[j] < L of slot 0, which already holds the sum over the classes divided by pre_mul; every other one is summed as above,
+// from slot c + 1
+__global__ __launch_bounds__(1024) void gather_ctx_grad_prefix_kernel(const float* __restrict__ dx, const int32_t* __restrict__ ctx_pos,
+                                                                      int C, int L, int d, int n_ctx, float* __restrict__ dctx,
+                                                                      const float* scale_dev, float pre_mul) {
+  __shared__ f32x4 part[16][64];
+  const int j = blockIdx.y, p0 = ctx_pos[j];
+  if (p0 < L) {      // (the same for every thread of the workgroup)
+    const int c = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+    if (threadIdx.x < 64 && c < d) {
+      const float inv = scale_dev ? scale_dev[1] : 1.0f;
+      *(f32x4*)(dctx + (size_t)j * d + c) = (*(const f32x4*)(dx + (size_t)p0 * d + c) * pre_mul) * inv;
+    }
+    return;
+  }
+  gather_ctx_row(part, dx, ctx_pos, j, C, L, d, n_ctx, dctx, (size_t)j, scale_dev);
+}
 hipError_t launch_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C, int L, int d, int n_ctx, int per_class,
-                                  float* dctx, const float* scale_dev, hipStream_t s) {
+                                  float* dctx, const float* scale_dev, hipStream_t s, int shared_prefix, float pre_mul) {
   if (n_ctx <= 0) return hipSuccess;
   if (d % 4) return hipErrorInvalidValue;
+  if (shared_prefix) {
+    if (shared_prefix < 0 || shared_prefix > L || per_class) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gather_ctx_grad_prefix_kernel, dim3((d + 255) / 256, n_ctx), dim3(1024), 0, s, dx, ctx_pos, C, L, d, n_ctx, dctx, scale_dev,
+                       pre_mul);
+    return hipGetLastError();
+  }
   if (per_class)
     hipLaunchKernelGGL(gather_ctx_grad_csc_kernel, dim3((d + 255) / 256, n_ctx, C), dim3(256), 0, s, dx, ctx_pos, L, d, n_ctx, dctx, scale_dev);
   else

@@ -171,6 +171,9 @@ struct AttnArgs {
   int N, L, H; int causal;
   int q_rows = 0;   // > 0: only queries 0..q_rows-1 of every sequence are computed (last layer: only CLS is consumed)
   int flags = 0;    // experiment bits: 1 = non-temporal K/V staging, 2 = non-temporal output stores
+  // Shared prefix, as Attn32Args::prefix, on single operands: causal, L <= 80, q_rows == 0, 2 P <= L; N + 1 slots of L - P rows in qkv /
+  // out, lse [N + 1, H, L - P]; workgroups (N, h) are the prefix itself and also write zeros into the unused rows of slot 0
+  int prefix = 0;
 };
 // ea / eb (optional): start / stop events of the kernel's own dispatch (hipExtLaunchKernelGGL), for mvlpt_profile_* — resident kernels only
 hipError_t launch_attn_fwd(int dtype, const AttnArgs& a, hipStream_t s, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr);
@@ -181,6 +184,10 @@ struct AttnBwdArgs {
   // Ls > L: the saved tensors (qkv, out, lse) hold sequences of Ls positions and only the leading L carry a gradient: dout, delta and
   // dqkv are [N*L, .] and positions >= L are neither staged nor computed (causal only: no row < L reads a key or query >= L).  0: L
   int Ls = 0;
+  // Shared prefix, as Attn32BwdArgs::prefix, on single operands (causal, L <= 80, 2 P <= L): saved tensors in slots of Ls - P rows,
+  // dout / dqkv in slots of L - P rows, delta [N + 1, H, L - P]; kv_part fp32 [N + 1, P, 2d]; a third launch writes dK / dV of slot 0 =
+  // kv_part[N] + part_mul * sum_n kv_part[n] (the fixed order of attn32t_prefix_reduce_kernel) and zeroes the unused rows of slot 0
+  int prefix = 0; float* kv_part = nullptr; float part_mul = 1.f;
 };
 hipError_t launch_attn_bwd(int dtype, const AttnBwdArgs& a, hipStream_t s);
 int attn_max_len();
@@ -206,6 +213,12 @@ struct Attn32Args {
   int N, L, H; int causal;
   int q_rows = 0;        // > 0: only queries 0..q_rows-1 of every sequence are computed
   int out_lo8 = 0;       // out_split rows are [hi(d) | lo8 (d bytes) | unused] (mixed pair: the out-projection's A operand)
+  // Shared prefix (the short causal kernel, L <= 80, q_rows == 0, only).  prefix = P > 0: positions 0 .. P-1 are the same rows in all N
+  // sequences and every tensor holds N + 1 "slots" of L - P rows: slot 0 = the prefix in its first P rows, slot n + 1 = positions
+  // P .. L-1 of sequence n (lse: [slot, H, L - P]).  Sequence n reads position p < P from slot 0 and writes only its queries >= P;
+  // one more workgroup row (blockIdx.y == N) is the prefix itself, length P; it also writes zeros into the other rows of slot 0 of out /
+  // lse (never read by the attention: the row-wise kernels behind it then meet finite, deterministic values).  2 P <= L.
+  int prefix = 0;
 #ifdef MVLPT_ATTN_TRACE
   long long* trace = nullptr;   // debug builds only (tools/attn_trace.py): (point id << 56 | s_memtime) records of one workgroup
 #endif
@@ -217,6 +230,12 @@ struct Attn32BwdArgs {
   int N, L, H; int causal;
   int lo8 = 0;           // out_split rows are [hi | lo8] (read for delta) and dqkv_split rows are written as [hi(3d) | lo8 (3d bytes) | unused]
   int Ls = 0;            // as AttnBwdArgs::Ls (the short causal kernel, L <= 80, only)
+  // Shared prefix (Attn32Args::prefix; the short causal kernel only).  The saved tensors hold N + 1 slots of Ls - P rows, dout / dqkv
+  // N + 1 slots of L - P rows.  Sequence n takes dO of its positions < P as zero, stores dQ / dK / dV of its positions >= P and writes
+  // dK / dV of the prefix keys as fp32 into kv_part [N + 1, P, 2d] (row: dK (d) | dV (d)); workgroup row N is the prefix's own
+  // backward from slot 0 of dout (dQ into slot 0 of dqkv, dK / dV into kv_part[N]).  A second launch then writes dK / dV of slot 0:
+  // kv_part[N] + part_mul * sum_n kv_part[n] (a fixed order, no atomics), and zeroes the unused rows P .. L-P-1 of slot 0.
+  int prefix = 0; float* kv_part = nullptr; float part_mul = 1.f;
 #ifdef MVLPT_ATTN_TRACE
   long long* trace = nullptr;   // debug builds only (tools/attn_trace.py bwd): records of one workgroup of attn32r_bwd_kernel
 #endif
@@ -295,9 +314,12 @@ hipError_t launch_assemble_tokens_packed(const float* patch_emb, const float* cl
 hipError_t launch_overwrite_rows(const float* rows, int n, float* x, int B, int L, int d, hipStream_t s, const float* vmask = nullptr);
 // prompts (forward_coop + positional embedding, trainers/mvlpt.py:439-515, 107/112)
 hipError_t launch_assemble_prompts(const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
-                                   const int32_t* layout, const float* pos, float* x, int C, int L, int d, hipStream_t s);
-hipError_t launch_build_ctx_pos(const int32_t* layout, int32_t* ctx_pos, int C, int L, int n_ctx, hipStream_t s);
-hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipStream_t s);
+                                   const int32_t* layout, const float* pos, float* x, int C, int L, int d, hipStream_t s,
+                                   int shared_prefix = 0);
+// shared_prefix = P > 0: the three tables / tokens in the shared-prefix layout (Attn32Args::prefix; glue.hip): x as C + 1 slots of
+// L - P rows, eot rows in slot c + 1, ctx_pos against gradient slots of Lt rows
+hipError_t launch_build_ctx_pos(const int32_t* layout, int32_t* ctx_pos, int C, int L, int n_ctx, hipStream_t s, int shared_prefix = 0, int Lt = 0);
+hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipStream_t s, int shared_prefix = 0);
 // token ids (clip/model.py encode_text): x [S, L, d] = emb[ids[s, t]] + pos[t]; ids int32 [S, ld], ld >= L, columns 0 .. L-1 read, every one
 // of them inside the table (checked on the host by the callers); d % 4 == 0
 hipError_t launch_embed_tokens(const float* emb, const float* pos, const int32_t* ids, int ld, float* x, int S, int L, int d, hipStream_t s);
@@ -312,8 +334,10 @@ hipError_t launch_copy_rows_strided(const void* src, void* dst, int rows, size_t
 hipError_t launch_reduce_prompt_rows(int dtype, float* dx32, void* dx16, int B, int L, int d, int row0, int n, float* out,
                                      const float* scale_dev, int zero_after, hipStream_t s, int split16 = 0, const float* vmask = nullptr);
 // dctx (generic) [n,d] = inv_scale * sum_c dx[c, ctx_pos[c,j], :]  or (per class) [C,n,d]
+// shared_prefix > 0: dx holds C + 1 slots of L rows and ctx_pos is launch_build_ctx_pos's table for it; the rows of slot 0 are
+// multiplied by pre_mul (the power of two the prefix gradient was scaled down by)
 hipError_t launch_gather_ctx_grad(const float* dx, const int32_t* ctx_pos, int C, int L, int d, int n_ctx, int per_class,
-                                  float* dctx, const float* scale_dev, hipStream_t s);
+                                  float* dctx, const float* scale_dev, hipStream_t s, int shared_prefix = 0, float pre_mul = 1.f);
 // ranged prompts (one context block of ctx [G, n_ctx, d] per image, trainers/cocoop.py:123-161; under the per-task mask of
 // trainers/mvlpt.py:556-581 only the image's own classes): group g owns classes [lo[g], lo[g] + start[g+1] - start[g]); its
 // sequences start[g] .. start[g+1] - 1 are those classes in order.  seq_cls / seq_grp int32 [S]: class and group of every sequence;

@@ -187,6 +187,14 @@ class Engine:
         grad_len = context_length: every position.  Applies from the next saving text forward."""
         _lib.check(lib.mvlpt_set_text_grad_len(self.h, int(grad_len), int(max_eot)), self.h, "set_text_grad_len")
 
+    def set_text_shared_prefix(self, prefix: int) -> None:
+        """Shared prefix of the class prompts (include/mvlpt_hip.h: mvlpt_set_text_shared_prefix): the caller vouches that the first
+        `prefix` positions hold the same rows in every class (same layout columns, no suffix entry, one SOS embedding, a generic
+        context, every EOT at or behind them); the next text forward evaluates them once and CONSUMES the setting (one-shot: the
+        engine cannot check the claim against another call's tables).  0: off.  The engine lowers the value where its layout needs it
+        and ignores it on the routes that have no shared layout."""
+        _lib.check(lib.mvlpt_set_text_shared_prefix(self.h, int(prefix)), self.h, "set_text_shared_prefix")
+
     def text_act_ckpt_plan(self) -> List[Tuple[int, int, bool]]:
         """The plan the next saving text forward uses, as mvlpt_amd.model.checkpoint_segments gives it:
         [(first, last_exclusive, checkpointed)]."""

@@ -245,6 +245,63 @@ def apply_text_grad_len(model, pl, classes: Optional[tuple] = None) -> None:
     setter(min(max(max_eot + 1, TEXT_MIN_L), full) if getattr(model, "text_grad_to_eot", True) else full, max_eot)
 
 
+def shared_prefix_len(layout: torch.Tensor, token_prefix: torch.Tensor, generic: bool, enabled: bool = True) -> int:
+    """The leading positions every class prompt shares (Engine.set_text_shared_prefix): the leading columns of `layout` [C, L] that
+    are identical in every class row and hold the prefix entry (0) or a context entry (< 0), never a suffix entry; 0 unless the
+    context is generic, every row of `token_prefix` has the same bits and `enabled`.  Reads the tables back: cache the result."""
+    if not enabled or not generic or layout.dim() != 2 or layout.shape[0] == 0:
+        return 0
+    rows = token_prefix.detach().reshape(token_prefix.shape[0], -1).contiguous().view(torch.uint8)      # bits, not values
+    if rows.shape[0] != layout.shape[0] or not bool((rows == rows[:1]).all()):
+        return 0
+    ok = ((layout == layout[:1]).all(dim=0) & (layout[0] <= 0)).to("cpu")
+    bad = (~ok).nonzero()
+    return int(bad[0]) if bad.numel() else int(layout.shape[1])
+
+
+def clamp_shared_prefix(prefix: int, seq_len: int, grad_len: int, min_len: int = TEXT_MIN_L) -> int:
+    """The prefix the engine runs a tower of `seq_len` positions under, given the setting `prefix` and the gradient length: it fits
+    a gradient slot (P <= grad_len - P) and leaves a slot `min_len` rows (the engine's rule, restated for planning and tests)."""
+    p = min(int(prefix), seq_len - 1, grad_len // 2, grad_len - min_len)
+    return max(p, 0)
+
+
+# The shared prefix pays by the rows it removes, C * P - (L - P) of the forward's C * L (one slot of L - P rows is added), and costs
+# one more launch per block in the backward (the reduction of the prefix keys' dK / dV), a serial link of the text chain: about
+# 12 x 5 us at ViT-B's depth, the time of some 460 backward rows at the 0.13 us per row the gradient length measured
+# (NOTES_experiments.md round 8).  An ESTIMATE, not a measured break-even (the kernel trace of round 9 has the reduce at 4.6 us
+# alone and 36.6 us beside the image tower; no class table near the threshold was timed).  A class table that removes fewer rows than
+# this runs every class in full, as it always did.
+MIN_SHARED_PREFIX_ROWS = 512
+
+
+def apply_text_shared_prefix(model, pl, layout: torch.Tensor, generic: bool, classes: Optional[tuple] = None) -> int:
+    """Tell the engine of `model` how many leading positions the class prompts of the next text forward share
+    (shared_prefix_len over the rows `classes` = (lo, hi) of `layout` / pl.token_prefix; TRAINER.MVLPT.TEXT_SHARED_PREFIX), or 0
+    where that removes fewer than `model.shared_prefix_min_rows` (MIN_SHARED_PREFIX_ROWS) rows.  Called in front of every CoOp text
+    forward, saving or not, next to apply_text_grad_len; the tables are read back once per class table.
+    A host call; an engine without the setting evaluates every position of every class."""
+    setter = getattr(model.engine, "set_text_shared_prefix", None)
+    if setter is None:
+        return 0
+    enabled = bool(getattr(model, "text_shared_prefix", True))
+    p = 0
+    if enabled and generic:
+        # (`layout` may be a trimmed view made for this call: the table it comes from identifies it, as in apply_text_grad_len)
+        # (the tensors' version counters catch an in-place edit of a table)
+        key = (id(pl.layout), id(pl.token_prefix), pl.layout._version, pl.token_prefix._version, tuple(layout.shape),
+               tuple(classes) if classes is not None else None)
+        if getattr(model, "_shared_prefix", (None, 0))[0] != key:
+            lo, hi = classes if classes is not None else (0, layout.shape[0])
+            model._shared_prefix = (key, shared_prefix_len(layout[lo:hi], pl.token_prefix[lo:hi], True))
+        p = model._shared_prefix[1]
+        n_cls = (classes[1] - classes[0]) if classes is not None else int(layout.shape[0])
+        if n_cls * p - (int(layout.shape[1]) - p) < int(getattr(model, "shared_prefix_min_rows", MIN_SHARED_PREFIX_ROWS)):
+            p = 0
+    setter(min(p, int(model.clip_model.context_length) - 1))
+    return p
+
+
 def plan_text_chunks(eot: Sequence[int], workspace_bytes: Callable[[int, int], int], budget: int, min_len: int = TEXT_MIN_L,
                      max_seq: int = MAX_SEQUENCES_PER_TOWER, min_chunk: int = MIN_SEQUENCES_PER_CHUNK,
                      force_len: Optional[int] = None):
@@ -641,6 +698,9 @@ class _PromptedClipFn(torch.autograd.Function):
             shard = model._class_shard if coop_emb is not None else None
             if need_txt:
                 apply_text_grad_len(model, pl, (shard.lo, shard.hi) if shard is not None else None)
+            # the leading positions every class shares are evaluated once (generic context, no deep prompts; saving or not)
+            apply_text_shared_prefix(model, pl, layout, coop_emb is not None and coop_emb.dim() == 2 and ctx_deep is None,
+                                     (shard.lo, shard.hi) if shard is not None else None)
             if shard is not None:
                 # Class-sharded text tower (ClassShard): this rank encodes classes [lo, hi) only and the features are
                 # all-gathered; the backward reduce-scatters d(txt) back to the owners.  Tower and collective are one job.
@@ -807,6 +867,8 @@ class CustomCLIP(VisualPromptSide, nn.Module):
         self._class_shard = None
         self.trim_text_to_eot = False
         self.text_grad_to_eot = bool(cfg.TRAINER.MVLPT.get("TEXT_GRAD_TO_EOT", True))
+        self.text_shared_prefix = bool(cfg.TRAINER.MVLPT.get("TEXT_SHARED_PREFIX", True))
+        self.shared_prefix_min_rows = MIN_SHARED_PREFIX_ROWS
         self.text_cache = TextFeatureCache()
         self.prefetch = ImagePrefetch(self.engine, clip_model.device)
         self._fwd_generation = 0

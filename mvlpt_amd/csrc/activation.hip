@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(ActArgs a) {
     const int c = (int)(i - m * n8) * 8;
     const float* row = (const float*)a.in + m * (size_t)a.ldi + c;
     const f32x4 d0 = __builtin_nontemporal_load((const f32x4*)row), d1 = __builtin_nontemporal_load((const f32x4*)(row + 4));
-    const size_t um = a.u_seq > 0 ? (m / a.u_seq) * a.u_pitch + m % a.u_seq : m;      // (ActArgs::u_seq)
+    const size_t um = a.u_rows.row((int)m);      // (ActArgs::u_rows; m < M)
     const v8 u = __builtin_nontemporal_load((const v8*)((const T*)a.u16 + um * (size_t)a.N + c));
     f32x4 r0, r1;
 #pragma unroll
@@ -103,7 +103,7 @@ const char* act_check(int dtype, int act, bool bwd, ActArgs& a) {
   if (a.fmt != ACT_FMT_SINGLE && a.fmt != ACT_FMT_PAIR && a.fmt != ACT_FMT_MIXED) return "unknown output format";
   if (!a.in || !a.out || (bwd && !a.u16)) return "null pointer";
   if (a.M <= 0 || a.N <= 0 || (a.N % 8) != 0) return "M, N positive and N a multiple of 8";
-  if (a.u_seq < 0 || (a.u_seq > 0 && (!bwd || a.u_pitch < a.u_seq || a.M % a.u_seq))) return "u16 row map: backward only, whole sequences";
+  if (!row_map_ok(a.u_rows, a.M) || (a.u_rows.seq && !bwd)) return "u16 row map: backward only, whole sequences";
   const int wi = a.N, wo = a.fmt == ACT_FMT_SINGLE ? a.N : 2 * a.N;
   if (a.ldi == 0) a.ldi = wi;
   if (a.ldo == 0) a.ldo = wo;

@@ -840,6 +840,8 @@ static int nkt_for(int L) {
 static bool use_stream(int L) { return L > 256; }
 
 hipError_t launch_attn_fwd(int dtype, const AttnArgs& a_, hipStream_t s, hipEvent_t ea, hipEvent_t eb) {
+  if (a_.fmt == 1 || a_.fmt == 2) return attn32_fwd(dtype, a_, s);      // pairs (no dispatch events there)
+  if (a_.fmt != 0) return hipErrorInvalidValue;
   t_ev_a = ea; t_ev_b = eb;
   // bit 0: non-temporal K/V staging (one workgroup reads them once), bit 1: non-temporal output stores  (+0.5 % on the step)
   AttnArgs a = a_;
@@ -875,6 +877,8 @@ hipError_t launch_attn_fwd(int dtype, const AttnArgs& a_, hipStream_t s, hipEven
   return hipErrorInvalidValue;
 }
 hipError_t launch_attn_bwd(int dtype, const AttnBwdArgs& a, hipStream_t s) {
+  if (a.fmt == 1 || a.fmt == 2) return attn32_bwd(dtype, a, s);      // pairs
+  if (a.fmt != 0) return hipErrorInvalidValue;
   if (a.L <= 0 || a.L > attn_max_len() || a.N <= 0) return hipErrorInvalidValue;
   // a gradient shorter than the saved sequences (AttnBwdArgs::Ls): causal, resident kernels only
   if (a.Ls > 0 && a.Ls != a.L && (a.Ls < a.L || !a.causal || use_stream(a.L))) return hipErrorInvalidValue;

@@ -209,7 +209,7 @@ constexpr float SC2 = SCALE * LOG2E;      // exp(s/8 - m/8) = exp2(s*SC2 - m*SC2
 // ------------------------------------------------------------------------------------------------ streamed kernels
 // NW waves x 32 own rows; ring of two slots x four 8 KiB images (64 KiB): chunk c+1 is in flight while chunk c is multiplied
 template <typename T, bool CAUSAL, int NW>
-__global__ __launch_bounds__(NW * 64) void attn32x_fwd_kernel(Attn32Args a, int nqc) {
+__global__ __launch_bounds__(NW * 64) void attn32x_fwd_kernel(AttnArgs a, int nqc) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
   using v8 = typename Vec<T>::v8;
   constexpr int WR = NW * 32;
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(NW * 64) void attn32x_fwd_kernel(Attn32Args a, int 
   MVLPT_ATR(10);
   const int n = nh / a.H, h = nh % a.H, L = a.L, d = a.H * 64;
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d;
-  const T* base = (const T*)a.qkv_split + (size_t)n * L * ld + h * 64;
+  const T* base = (const T*)a.qkv + (size_t)n * L * ld + h * 64;
   const int qb = qcx * WR;
   const int kend = CAUSAL ? (qb + WR < L ? qb + WR : L) : L;
   const int nch = (kend + CH - 1) / CH;
@@ -314,9 +314,9 @@ __global__ __launch_bounds__(NW * 64) void attn32x_fwd_kernel(Attn32Args a, int 
     const float lt = quad_sum(l[t]);
     if (q[t] < qlim) {
       const float inv = 1.f / lt;
-      T* orow = (T*)a.out_split + ((size_t)n * L + q[t]) * (2 * (size_t)d) + h * 64;
+      T* orow = (T*)a.out + ((size_t)n * L + q[t]) * (2 * (size_t)d) + h * 64;
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, d, h * 64 + 16 * dt + 4 * fg, O[t][dt] * inv, a.out_lo8);
+      for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, d, h * 64 + 16 * dt + 4 * fg, O[t][dt] * inv, a.fmt == 2);
       if (a.lse && fg == 0) a.lse[((size_t)n * a.H + h) * L + q[t]] = m[t] * SCALE + logf(lt);
     }
   }
@@ -327,13 +327,13 @@ __global__ __launch_bounds__(NW * 64) void attn32x_fwd_kernel(Attn32Args a, int 
 // own rows are published in LDS ([0] .. [lpad) and [lpad] .. [2*lpad)) for a dK/dV phase in the same workgroup instead of
 // delta going through global memory.
 template <typename T, bool CAUSAL, int NW>
-__device__ __forceinline__ void attn32x_dq_phase(const Attn32BwdArgs& a, int nh, int qcx, char* sm, float* stat_lds, int lpad) {
+__device__ __forceinline__ void attn32x_dq_phase(const AttnBwdArgs& a, int nh, int qcx, char* sm, float* stat_lds, int lpad) {
   using v8 = typename Vec<T>::v8;
   constexpr int WR = NW * 32;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, fg = lane >> 4;
   const int n = nh / a.H, h = nh % a.H, L = a.L, d = a.H * 64;
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d;
-  const T* base = (const T*)a.qkv_split + (size_t)n * L * ld + h * 64;
+  const T* base = (const T*)a.qkv + (size_t)n * L * ld + h * 64;
   const int qb = qcx * WR;
   const int kend = CAUSAL ? (qb + WR < L ? qb + WR : L) : L;
   const int nch = (kend + CH - 1) / CH;
@@ -350,8 +350,8 @@ __device__ __forceinline__ void attn32x_dq_phase(const Attn32BwdArgs& a, int nh,
   for (int t = 0; t < 2; ++t) {
     q[t] = qb + wave * 32 + t * 16 + fr;
     const int qc = q[t] < L ? q[t] : L - 1;
-    const T* grow = (const T*)a.dout_split + ((size_t)n * L + qc) * (2 * (size_t)d) + h * 64;
-    const T* orow = (const T*)a.out_split + ((size_t)n * L + qc) * (2 * (size_t)d) + h * 64;
+    const T* grow = (const T*)a.dout + ((size_t)n * L + qc) * (2 * (size_t)d) + h * 64;
+    const T* orow = (const T*)a.out + ((size_t)n * L + qc) * (2 * (size_t)d) + h * 64;
     load_own_pair<T>(Qh[t], Ql[t], base + (size_t)qc * ld, lo, fg);
     load_own_pair<T>(Gh[t], Gl[t], grow, d, fg);
     const size_t stat = ((size_t)n * a.H + h) * L + qc;
@@ -359,7 +359,7 @@ __device__ __forceinline__ void attn32x_dq_phase(const Attn32BwdArgs& a, int nh,
     float acc = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const f32x4 o = load_pair4_m<T>(orow + 16 * k + 4 * fg, d, h * 64 + 16 * k + 4 * fg, a.lo8);
+      const f32x4 o = load_pair4_m<T>(orow + 16 * k + 4 * fg, d, h * 64 + 16 * k + 4 * fg, a.fmt == 2);
       const f32x4 g = load_pair4<T>(grow + 16 * k + 4 * fg, d);
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc += o[e] * g[e];
@@ -404,16 +404,16 @@ __device__ __forceinline__ void attn32x_dq_phase(const Attn32BwdArgs& a, int nh,
 #pragma unroll
   for (int t = 0; t < 2; ++t)
     if (q[t] < L) {
-      T* row = (T*)a.dqkv_split + ((size_t)n * L + q[t]) * ld + h * 64;
+      T* row = (T*)a.dqkv + ((size_t)n * L + q[t]) * ld + h * 64;
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(row + 16 * dt + 4 * fg, lo, h * 64 + 16 * dt + 4 * fg, dQ[t][dt] * SCALE, a.lo8);
+      for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(row + 16 * dt + 4 * fg, lo, h * 64 + 16 * dt + 4 * fg, dQ[t][dt] * SCALE, a.fmt == 2);
     }
 }
 
 // dK, dV of the NW*32 keys starting at kcx*NW*32 of head nh.  `preload`: -lse*log2(e) and delta of the whole sequence are
 // read from global into the LDS arrays behind the ring; otherwise a dQ phase of this workgroup has left them there.
 template <typename T, bool CAUSAL, int NW>
-__device__ __forceinline__ void attn32x_dkv_phase(const Attn32BwdArgs& a, int nh, int kcx, char* sm, int lpad, bool preload) {
+__device__ __forceinline__ void attn32x_dkv_phase(const AttnBwdArgs& a, int nh, int kcx, char* sm, int lpad, bool preload) {
   using v8 = typename Vec<T>::v8;
   constexpr int WR = NW * 32;
   float* nlse_s = (float*)(sm + 8 * XIMG);      // [lpad] -lse * log2(e)
@@ -421,8 +421,8 @@ __device__ __forceinline__ void attn32x_dkv_phase(const Attn32BwdArgs& a, int nh
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, fg = lane >> 4;
   const int n = nh / a.H, h = nh % a.H, L = a.L, d = a.H * 64;
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d, gld = 2 * (size_t)d;
-  const T* base = (const T*)a.qkv_split + (size_t)n * L * ld + h * 64;
-  const T* gbase = (const T*)a.dout_split + (size_t)n * L * gld + h * 64;
+  const T* base = (const T*)a.qkv + (size_t)n * L * ld + h * 64;
+  const T* gbase = (const T*)a.dout + (size_t)n * L * gld + h * 64;
   const int kb = kcx * WR;
   const int c0 = CAUSAL ? kb / CH : 0, nch = (L + CH - 1) / CH;     // causal: queries before the first own key see none of them
   auto issue = [&](int c) {
@@ -487,24 +487,24 @@ __device__ __forceinline__ void attn32x_dkv_phase(const Attn32BwdArgs& a, int nh
 #pragma unroll
   for (int t = 0; t < 2; ++t)
     if (kk[t] < L) {
-      T* row = (T*)a.dqkv_split + ((size_t)n * L + kk[t]) * ld + h * 64;
+      T* row = (T*)a.dqkv + ((size_t)n * L + kk[t]) * ld + h * 64;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        store_pair4_m<T>(row + d + 16 * dt + 4 * fg, lo, d + h * 64 + 16 * dt + 4 * fg, dK[t][dt] * SCALE, a.lo8);
-        store_pair4_m<T>(row + 2 * d + 16 * dt + 4 * fg, lo, 2 * d + h * 64 + 16 * dt + 4 * fg, dV[t][dt], a.lo8);
+        store_pair4_m<T>(row + d + 16 * dt + 4 * fg, lo, d + h * 64 + 16 * dt + 4 * fg, dK[t][dt] * SCALE, a.fmt == 2);
+        store_pair4_m<T>(row + 2 * d + 16 * dt + 4 * fg, lo, 2 * d + h * 64 + 16 * dt + 4 * fg, dV[t][dt], a.fmt == 2);
       }
     }
 }
 
 template <typename T, bool CAUSAL, int NW>
-__global__ __launch_bounds__(NW * 64) void attn32x_dq_kernel(Attn32BwdArgs a, int nqc) {
+__global__ __launch_bounds__(NW * 64) void attn32x_dq_kernel(AttnBwdArgs a, int nqc) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
   int nh, qcx;
   if (!map_block(a.N * a.H, nqc, nh, qcx)) return;
   attn32x_dq_phase<T, CAUSAL, NW>(a, nh, qcx, sm, nullptr, 0);
 }
 template <typename T, bool CAUSAL, int NW>
-__global__ __launch_bounds__(NW * 64) void attn32x_dkv_kernel(Attn32BwdArgs a, int nkc, int lpad) {
+__global__ __launch_bounds__(NW * 64) void attn32x_dkv_kernel(AttnBwdArgs a, int nkc, int lpad) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
   int nh, kcx;
   if (!map_block(a.N * a.H, nkc, nh, kcx)) return;
@@ -514,7 +514,7 @@ __global__ __launch_bounds__(NW * 64) void attn32x_dkv_kernel(Attn32BwdArgs a, i
 // the first phase) and K / V (streamed by it) while they are still in this XCD's L2, lse comes from the first phase's
 // registers and delta never goes through global memory: 1.29 GB instead of 1.93 GB of HBM traffic per ViT-B/16 layer.
 template <typename T, bool CAUSAL, int NW>
-__global__ __launch_bounds__(NW * 64) void attn32x_bwd_fused_kernel(Attn32BwdArgs a, int lpad) {
+__global__ __launch_bounds__(NW * 64) void attn32x_bwd_fused_kernel(AttnBwdArgs a, int lpad) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
   int nh, c;
   if (!map_block(a.N * a.H, 1, nh, c)) return;
@@ -547,7 +547,7 @@ __device__ __forceinline__ void stage_short(char* hi, char* lo, const T* src, si
     dma_raw<16>(g + lo_off, lo + sl * 1024);
   }
 }
-// stage_short under a shared prefix (Attn32Args::prefix): positions below `split` come from src_pre, the others from src
+// stage_short under a shared prefix (AttnArgs::prefix): positions below `split` come from src_pre, the others from src
 // (position p at src + p * ld either way: the callers fold the slot offsets into the two pointers)
 template <typename T>
 __device__ __forceinline__ void stage_short_pfx(char* hi, char* lo, const T* src_pre, const T* src, int split, size_t lo_off, size_t ld, int L,
@@ -610,10 +610,10 @@ __device__ __forceinline__ void accum_all3(f32x4 (&out)[4], const char* hi, cons
 }
 }  // namespace
 
-// PFX: the shared-prefix layout (Attn32Args::prefix > 0, q_rows == 0).  `split` is the first position a class sequence owns (0 in
+// PFX: the shared-prefix layout (AttnArgs::prefix > 0, q_rows == 0).  `split` is the first position a class sequence owns (0 in
 // the prefix's own workgroup row, whose length is P); position p sits at row p of slot 0 (p < split) or at row row0 + p.
 template <typename T, bool CAUSAL, bool PFX = false>
-__global__ __launch_bounds__(SNT * 64) void attn32t_fwd_kernel(Attn32Args a) {
+__global__ __launch_bounds__(SNT * 64) void attn32t_fwd_kernel(AttnArgs a) {
   __shared__ __attribute__((aligned(16))) char sm[4 * TIMG];
   char *Kh = sm, *Kl = sm + TIMG, *Vh = sm + 2 * TIMG, *Vl = sm + 3 * TIMG;
   using v8 = typename Vec<T>::v8;
@@ -625,8 +625,8 @@ __global__ __launch_bounds__(SNT * 64) void attn32t_fwd_kernel(Attn32Args a) {
   const int Lf = PFX ? a.L - a.prefix : a.L;                  // rows per slot
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d;
   const size_t row0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * Lf - a.prefix) : (size_t)n * L;
-  const T* base = (const T*)a.qkv_split + row0 * ld + h * 64;
-  const T* base_pre = (const T*)a.qkv_split + h * 64;
+  const T* base = (const T*)a.qkv + row0 * ld + h * 64;
+  const T* base_pre = (const T*)a.qkv + h * 64;
   if constexpr (PFX) {
     stage_short_pfx<T>(Kh, Kl, base_pre + d, base + d, split, lo, ld, L, wave, lane);
     stage_short_pfx<T>(Vh, Vl, base_pre + 2 * d, base + 2 * d, split, lo, ld, L, wave, lane);
@@ -649,8 +649,8 @@ __global__ __launch_bounds__(SNT * 64) void attn32t_fwd_kernel(Attn32Args a) {
     if (own_pre) {
       for (int i = tid; i < (Lf - L) * 16; i += SNT * 64) {
         const int r = L + (i >> 4), c = (i & 15) * 4;
-        T* zrow = (T*)a.out_split + (size_t)r * (2 * (size_t)d) + h * 64 + c;
-        store_pair4_m<T>(zrow, d, h * 64 + c, f32x4{0.f, 0.f, 0.f, 0.f}, a.out_lo8);
+        T* zrow = (T*)a.out + (size_t)r * (2 * (size_t)d) + h * 64 + c;
+        store_pair4_m<T>(zrow, d, h * 64 + c, f32x4{0.f, 0.f, 0.f, 0.f}, a.fmt == 2);
       }
       if (a.lse)
         for (int j = L + tid; j < Lf; j += SNT * 64) a.lse[(size_t)h * Lf + j] = 0.f;
@@ -691,9 +691,9 @@ __global__ __launch_bounds__(SNT * 64) void attn32t_fwd_kernel(Attn32Args a) {
   accum_all3<T>(O, Vh, Vl, S, 0, kt_end, fr, fg);
   if (q < qlim && q >= split) {
     const float inv = 1.f / sum;
-    T* orow = (T*)a.out_split + (row0 + q) * (2 * (size_t)d) + h * 64;
+    T* orow = (T*)a.out + (row0 + q) * (2 * (size_t)d) + h * 64;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, d, h * 64 + 16 * dt + 4 * fg, O[dt] * inv, a.out_lo8);
+    for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, d, h * 64 + 16 * dt + 4 * fg, O[dt] * inv, a.fmt == 2);
     if (a.lse && fg == 0) {
       if constexpr (PFX) a.lse[((size_t)(own_pre ? 0 : n + 1) * a.H + h) * Lf + (q - split)] = mx * SCALE + logf(sum);
       else a.lse[((size_t)n * a.H + h) * L + q] = mx * SCALE + logf(sum);
@@ -703,12 +703,12 @@ __global__ __launch_bounds__(SNT * 64) void attn32t_fwd_kernel(Attn32Args a) {
 
 // (4 waves per SIMD = 128 VGPRs, three workgroups per CU instead of the two that the unconstrained 136 allowed: 100 sequences
 // 55.9 -> 51.2 us, 2191 sequences 1 192 -> 1 010 us per layer; the forward at 5 waves per SIMD (96 VGPRs, 3 spilled) got slower)
-// PFX: the shared-prefix layout (Attn32BwdArgs::prefix > 0).  As in the forward, `split` is the first position a class sequence owns;
+// PFX: the shared-prefix layout (AttnBwdArgs::prefix > 0).  As in the forward, `split` is the first position a class sequence owns;
 // srow0 + p / grow0 + p are the rows of position p >= split in the saved and in the gradient tensors, row p of slot 0 holds p < split.
 // A class sequence's queries below split carry no gradient: their lse is taken as +inf (P = 0 exactly) and their delta as 0, so the
 // dO rows staged for them (slot 0, finite) drop out of dK / dV without a mask in the product loops.
 template <typename T, bool CAUSAL, bool PFX = false>
-__global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs a) {
+__global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(AttnBwdArgs a) {
   // one set of four images (40 KiB, three workgroups per CU): K, V while the waves own query tiles (phase A: dQ), then Q, dO
   // while they own key tiles (phase B: dK, dV); the own rows live in registers in both phases.  (Eight images in flight
   // at once, 80 KiB, no restaging barrier: measured 20 % slower at 100 sequences, 4 % at 2191.)
@@ -717,7 +717,7 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
   char *I0h = sm, *I0l = sm + TIMG, *I1h = sm + 2 * TIMG, *I1l = sm + 3 * TIMG;
   using v8 = typename Vec<T>::v8;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, fg = lane >> 4;
-  // L: the positions that carry a gradient (dO, dQKV rows per sequence); Ls: the pitch of the saved tensors (Attn32BwdArgs::Ls)
+  // L: the positions that carry a gradient (dO, dQKV rows per sequence); Ls: the pitch of the saved tensors (AttnBwdArgs::Ls)
   const int n = blockIdx.y, h = blockIdx.x, d = a.H * 64;
   const bool own_pre = PFX && n == a.N;                       // the workgroup row of the prefix itself
   const int L = own_pre ? a.prefix : a.L, Ls = a.Ls > 0 ? a.Ls : a.L;
@@ -726,10 +726,10 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
   // rows of position p >= split: saved tensors / gradient tensors (PFX: slots of Ls - P and of a.L - P rows)
   const size_t srow0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * (Ls - a.prefix) - a.prefix) : (size_t)n * Ls;
   const size_t grow0 = PFX ? (own_pre ? 0 : (size_t)(n + 1) * (a.L - a.prefix) - a.prefix) : (size_t)n * L;
-  const T* base = (const T*)a.qkv_split + srow0 * ld + h * 64;
-  const T* gbase = (const T*)a.dout_split + grow0 * gld + h * 64;
-  const T* base_pre = (const T*)a.qkv_split + h * 64;
-  const T* gbase_pre = (const T*)a.dout_split + h * 64;
+  const T* base = (const T*)a.qkv + srow0 * ld + h * 64;
+  const T* gbase = (const T*)a.dout + grow0 * gld + h * 64;
+  const T* base_pre = (const T*)a.qkv + h * 64;
+  const T* gbase_pre = (const T*)a.dout + h * 64;
 #ifdef MVLPT_ATTN_TRACE
   int atr_n = 0;
 #endif
@@ -750,8 +750,8 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
   float dl = 0.f;       // delta = rowsum(dO * O) of the own query row
   {
     // dO of the own row is in registers already (Gh, Gl): O in the same fragment layout, no second read of dO
-    const T* orow = (const T*)a.out_split + ((in_pre ? 0 : srow0) + rc) * gld + h * 64;
-    dl = delta_part<T>(orow, d, h * 64, fg, a.lo8, Gh, Gl);
+    const T* orow = (const T*)a.out + ((in_pre ? 0 : srow0) + rc) * gld + h * 64;
+    dl = delta_part<T>(orow, d, h * 64, fg, a.fmt == 2, Gh, Gl);
     dl = quad_sum(dl);
   }
   float nlse;
@@ -776,7 +776,7 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
   }
   asm volatile("" ::: "memory");
   const bool active = wave < nt;
-  T* orow = (T*)a.dqkv_split + ((in_pre ? 0 : grow0) + rc) * ld + h * 64;
+  T* orow = (T*)a.dqkv + ((in_pre ? 0 : grow0) + rc) * ld + h * 64;
   // ---- phase A: own query tile -> dQ (PFX: not for a tile of prefix queries only; the prefix's own workgroup row has them)
   if (active && wave * 16 + 15 >= split) {
     const int kt_end = CAUSAL ? wave + 1 : nt;
@@ -804,7 +804,7 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
     MVLPT_ATRB(44);
     if (row < L && row >= split) {
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, lo, h * 64 + 16 * dt + 4 * fg, dQ[dt] * SCALE, a.lo8);
+      for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, lo, h * 64 + 16 * dt + 4 * fg, dQ[dt] * SCALE, a.fmt == 2);
     }
   }
   MVLPT_ATRB(45);
@@ -860,32 +860,32 @@ __global__ __launch_bounds__(SNT * 64, 4) void attn32t_bwd_kernel(Attn32BwdArgs 
     } else if (row < L) {
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        store_pair4_m<T>(orow + d + 16 * dt + 4 * fg, lo, d + h * 64 + 16 * dt + 4 * fg, dK[dt] * SCALE, a.lo8);
-        store_pair4_m<T>(orow + 2 * d + 16 * dt + 4 * fg, lo, 2 * d + h * 64 + 16 * dt + 4 * fg, dV[dt], a.lo8);
+        store_pair4_m<T>(orow + d + 16 * dt + 4 * fg, lo, d + h * 64 + 16 * dt + 4 * fg, dK[dt] * SCALE, a.fmt == 2);
+        store_pair4_m<T>(orow + 2 * d + 16 * dt + 4 * fg, lo, 2 * d + h * 64 + 16 * dt + 4 * fg, dV[dt], a.fmt == 2);
       }
     }
   }
   MVLPT_ATRB(51);
 }
 
-// dK / dV of the shared prefix (Attn32BwdArgs::kv_part): slot 0 row p of dqkv = kv_part[N][p] + mul * sum_n kv_part[n][p] in the pair
+// dK / dV of the shared prefix (AttnBwdArgs::kv_part): slot 0 row p of dqkv = kv_part[N][p] + mul * sum_n kv_part[n][p] in the pair
 // format, and zeros in the unused rows P .. Lt-1 of slot 0 (all of dQ | dK | dV), so that the row-wise kernels behind it meet finite
 // values there.  One workgroup per (row, 256 columns of dK | dV): 16 waves, wave w adds sequences w, w + 16, ... and wave 0 adds the
 // sixteen partial sums in order on top of the prefix's own term: a fixed order, so two runs give the same bits.  (Not class order:
 // a serial pass over the classes per element would put C dependent adds behind C loads in one thread; that the interleaved form
 // is the faster one is reasoned from the context gather's shape, not measured.)
 template <typename T>
-__global__ __launch_bounds__(1024) void attn32t_prefix_reduce_kernel(Attn32BwdArgs a) {
+__global__ __launch_bounds__(1024) void attn32t_prefix_reduce_kernel(AttnBwdArgs a) {
   __shared__ f32x4 part[16][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int d = a.H * 64, P = a.prefix, Lt = a.L - P, p = blockIdx.y;
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d, gld = 2 * (size_t)d;
   const int c = (blockIdx.x * 64 + lane) * 4;      // column inside dK (d) | dV (d)
-  T* orow = (T*)a.dqkv_split + (size_t)p * ld;
+  T* orow = (T*)a.dqkv + (size_t)p * ld;
   if (p >= P) {
     // an unused row: this workgroup's share of its 3d columns is 384 of them (256 of 2d -> 384 of 3d)
     const int col = blockIdx.x * 384 + (int)threadIdx.x * 4;
-    if (p < Lt && threadIdx.x < 96 && col < 3 * d) store_pair4_m<T>(orow + col, lo, col, f32x4{0.f, 0.f, 0.f, 0.f}, a.lo8);
+    if (p < Lt && threadIdx.x < 96 && col < 3 * d) store_pair4_m<T>(orow + col, lo, col, f32x4{0.f, 0.f, 0.f, 0.f}, a.fmt == 2);
     return;
   }
   const bool ok = c < 2 * d;
@@ -899,7 +899,7 @@ __global__ __launch_bounds__(1024) void attn32t_prefix_reduce_kernel(Attn32BwdAr
 #pragma unroll
     for (int w = 1; w < 16; ++w) t += part[w][lane];
     t = *(const f32x4*)(a.kv_part + ((size_t)a.N * P + p) * gld + c) + t * a.part_mul;
-    store_pair4_m<T>(orow + d + c, lo, d + c, t, a.lo8);
+    store_pair4_m<T>(orow + d + c, lo, d + c, t, a.fmt == 2);
   }
 }
 
@@ -938,14 +938,14 @@ __device__ __forceinline__ void accum_res3(f32x4 (&out)[4], const char* hi, cons
 }  // namespace
 
 template <typename T>
-__global__ __launch_bounds__(RNW * 64) void attn32r_fwd_kernel(Attn32Args a) {
+__global__ __launch_bounds__(RNW * 64) void attn32r_fwd_kernel(AttnArgs a) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
   char *Kh = sm, *Kl = sm + RIMG, *Vh = sm + 2 * RIMG, *Vl = sm + 3 * RIMG;
   using v8 = typename Vec<T>::v8;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, fg = lane >> 4;
   const int n = blockIdx.y, h = blockIdx.x, L = a.L, d = a.H * 64;
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d;
-  const T* base = (const T*)a.qkv_split + (size_t)n * L * ld + h * 64;
+  const T* base = (const T*)a.qkv + (size_t)n * L * ld + h * 64;
   stage_res<T>(Kh, Kl, base + d, lo, ld, L, wave, lane);
   stage_res<T>(Vh, Vl, base + 2 * d, lo, ld, L, wave, lane);
   const int nt = (L + 15) >> 4;
@@ -996,16 +996,16 @@ __global__ __launch_bounds__(RNW * 64) void attn32r_fwd_kernel(Attn32Args a) {
     accum_res3<T>(O, Vh, Vl, S, 0, nt, fr, fg);
     if (q < qlim) {
       const float inv = 1.f / sum;
-      T* orow = (T*)a.out_split + ((size_t)n * L + q) * (2 * (size_t)d) + h * 64;
+      T* orow = (T*)a.out + ((size_t)n * L + q) * (2 * (size_t)d) + h * 64;
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, d, h * 64 + 16 * dt + 4 * fg, O[dt] * inv, a.out_lo8);
+      for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, d, h * 64 + 16 * dt + 4 * fg, O[dt] * inv, a.fmt == 2);
       if (a.lse && fg == 0) a.lse[((size_t)n * a.H + h) * L + q] = mx * SCALE + logf(sum);
     }
   }
 }
 
 template <typename T>
-__global__ __launch_bounds__(RNW * 64) void attn32r_bwd_kernel(Attn32BwdArgs a) {
+__global__ __launch_bounds__(RNW * 64) void attn32r_bwd_kernel(AttnBwdArgs a) {
   // phase A: K, V resident, the waves own query tiles -> dQ; phase B: Q, dO resident, the waves own key tiles -> dK, dV
   extern __shared__ __attribute__((aligned(16))) char sm[];
   char *I0h = sm, *I0l = sm + RIMG, *I1h = sm + 2 * RIMG, *I1l = sm + 3 * RIMG;
@@ -1015,8 +1015,8 @@ __global__ __launch_bounds__(RNW * 64) void attn32r_bwd_kernel(Attn32BwdArgs a) 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, fg = lane >> 4;
   const int n = blockIdx.y, h = blockIdx.x, L = a.L, d = a.H * 64;
   const size_t ld = 6 * (size_t)d, lo = 3 * (size_t)d, gld = 2 * (size_t)d;
-  const T* base = (const T*)a.qkv_split + (size_t)n * L * ld + h * 64;
-  const T* gbase = (const T*)a.dout_split + (size_t)n * L * gld + h * 64;
+  const T* base = (const T*)a.qkv + (size_t)n * L * ld + h * 64;
+  const T* gbase = (const T*)a.dout + (size_t)n * L * gld + h * 64;
 #ifdef MVLPT_ATTN_TRACE
   int atr_n = 0;
 #endif
@@ -1029,10 +1029,10 @@ __global__ __launch_bounds__(RNW * 64) void attn32r_bwd_kernel(Attn32BwdArgs a) 
 #pragma unroll
   for (int o = 0; o < 2; ++o) {
     const int row = (wave + o * RNW) * 16 + fr, rc = row < L ? row : L - 1;
-    const T* orow = (const T*)a.out_split + ((size_t)n * L + rc) * gld + h * 64;
+    const T* orow = (const T*)a.out + ((size_t)n * L + rc) * gld + h * 64;
     v8 gh[2], gl[2];
     load_own_pair<T>(gh, gl, gbase + (size_t)rc * gld, d, fg);
-    dl[o] = quad_sum(delta_part<T>(orow, d, h * 64, fg, a.lo8, gh, gl));
+    dl[o] = quad_sum(delta_part<T>(orow, d, h * 64, fg, a.fmt == 2, gh, gl));
     nlse[o] = -a.lse[stat0 + rc] * LOG2E;
     if (fg == 0 && row < RROWS) { nlse_s[row] = nlse[o]; del_s[row] = dl[o]; }
   }
@@ -1072,9 +1072,9 @@ __global__ __launch_bounds__(RNW * 64) void attn32r_bwd_kernel(Attn32BwdArgs a) 
     accum_res3<T>(dQ, I0h, I0l, dS, 0, nt, fr, fg);
     MVLPT_ATRB(25);
     if (row < L) {
-      T* orow = (T*)a.dqkv_split + ((size_t)n * L + row) * ld + h * 64;
+      T* orow = (T*)a.dqkv + ((size_t)n * L + row) * ld + h * 64;
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, lo, h * 64 + 16 * dt + 4 * fg, dQ[dt] * SCALE, a.lo8);
+      for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, lo, h * 64 + 16 * dt + 4 * fg, dQ[dt] * SCALE, a.fmt == 2);
     }
     MVLPT_ATRB(26);
   }
@@ -1122,11 +1122,11 @@ __global__ __launch_bounds__(RNW * 64) void attn32r_bwd_kernel(Attn32BwdArgs a) 
     accum_res3<T>(dK, I0h, I0l, dS, 0, nt, fr, fg);
     MVLPT_ATRB(33);
     if (row < L) {
-      T* orow = (T*)a.dqkv_split + ((size_t)n * L + row) * ld + h * 64;
+      T* orow = (T*)a.dqkv + ((size_t)n * L + row) * ld + h * 64;
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
-        store_pair4_m<T>(orow + d + 16 * dt + 4 * fg, lo, d + h * 64 + 16 * dt + 4 * fg, dK[dt] * SCALE, a.lo8);
-        store_pair4_m<T>(orow + 2 * d + 16 * dt + 4 * fg, lo, 2 * d + h * 64 + 16 * dt + 4 * fg, dV[dt], a.lo8);
+        store_pair4_m<T>(orow + d + 16 * dt + 4 * fg, lo, d + h * 64 + 16 * dt + 4 * fg, dK[dt] * SCALE, a.fmt == 2);
+        store_pair4_m<T>(orow + 2 * d + 16 * dt + 4 * fg, lo, 2 * d + h * 64 + 16 * dt + 4 * fg, dV[dt], a.fmt == 2);
       }
     }
     MVLPT_ATRB(34);
@@ -1168,7 +1168,7 @@ __device__ __forceinline__ void stage_res8(char* buf, const T* src, size_t lo_of
 // (A compile-time tile count makes the phases straight-line code, which hipcc schedules into 60-80 spilled registers — spill traffic
 // counts in vmcnt, its waits drain the prefetch DMA; leaving the tile loop with `break` turns S[][] into a dynamically indexed stack array.)
 template <typename T>
-__global__ __launch_bounds__(RNW * 64) void attn32p_fwd_kernel(Attn32Args a, int total) {
+__global__ __launch_bounds__(RNW * 64) void attn32p_fwd_kernel(AttnArgs a, int total) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
   using v8 = typename Vec<T>::v8;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), fr = lane & 15, fg = lane >> 4;
@@ -1178,7 +1178,7 @@ __global__ __launch_bounds__(RNW * 64) void attn32p_fwd_kernel(Attn32Args a, int
   const bool two = wave + RNW < nt;          // the wave's second tile exists
   auto head_base = [&](int item) -> const T* {
     const int n = item / a.H, h = item - n * a.H;
-    return (const T*)a.qkv_split + (size_t)n * L * ld + h * 64;
+    return (const T*)a.qkv + (size_t)n * L * ld + h * 64;
   };
   auto load_q = [&](const T* base, v8 (&Qh)[2][2], v8 (&Ql)[2][2]) {
 #pragma unroll
@@ -1337,10 +1337,10 @@ __global__ __launch_bounds__(RNW * 64) void attn32p_fwd_kernel(Attn32Args a, int
       const bool ok = q < qlim;
       const int qc = ok ? q : 0;
       const float inv = 1.f / sum[o];
-      T* orow = (T*)a.out_split + ((size_t)n * L + qc) * (2 * (size_t)d) + h * 64;
+      T* orow = (T*)a.out + ((size_t)n * L + qc) * (2 * (size_t)d) + h * 64;
       if (ok) {
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, d, h * 64 + 16 * dt + 4 * fg, O[o][dt] * inv, a.out_lo8);
+        for (int dt = 0; dt < 4; ++dt) store_pair4_m<T>(orow + 16 * dt + 4 * fg, d, h * 64 + 16 * dt + 4 * fg, O[o][dt] * inv, a.fmt == 2);
         if (a.lse && fg == 0) a.lse[((size_t)n * a.H + h) * L + q] = mx[o] * SCALE + logf(sum[o]);
       }
     }
@@ -1359,7 +1359,7 @@ template <typename K>
 static void set_lds(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
 
 template <typename T, bool CAUSAL, int NW>
-static hipError_t fwd_x(const Attn32Args& a, hipStream_t s) {
+static hipError_t fwd_x(const AttnArgs& a, hipStream_t s) {
   const int lq = a.q_rows > 0 ? (a.q_rows < a.L ? a.q_rows : a.L) : a.L;
   const int nqc = (lq + NW * 32 - 1) / (NW * 32);
   constexpr int lds = 8 * XIMG;
@@ -1369,7 +1369,7 @@ static hipError_t fwd_x(const Attn32Args& a, hipStream_t s) {
   return hipGetLastError();
 }
 template <typename T, bool CAUSAL, int NW>
-static hipError_t bwd_x(const Attn32BwdArgs& a, hipStream_t s) {
+static hipError_t bwd_x(const AttnBwdArgs& a, hipStream_t s) {
   const int nc = (a.L + NW * 32 - 1) / (NW * 32), lpad = (a.L + CH - 1) / CH * CH;
   constexpr int lds = 8 * XIMG;
   const int lds_kv = lds + 8 * lpad;
@@ -1389,7 +1389,7 @@ static hipError_t bwd_x(const Attn32BwdArgs& a, hipStream_t s) {
 }
 
 template <typename T>
-static hipError_t fwd_t(const Attn32Args& a, hipStream_t s) {
+static hipError_t fwd_t(const AttnArgs& a, hipStream_t s) {
   if (a.prefix != 0) {      // shared prefix: the short causal kernel, every query, N + 1 workgroup rows
     // (2 P <= L: the prefix fits slot 0 and no slot offset goes negative, as in the backward)
     if (a.prefix < 0 || 2 * a.prefix > a.L || a.L > SROWS || !a.causal || a.q_rows > 0 || a.N >= 65535) return hipErrorInvalidValue;
@@ -1421,7 +1421,7 @@ static hipError_t fwd_t(const Attn32Args& a, hipStream_t s) {
   return a.causal ? fwd_x<T, true, 4>(a, s) : fwd_x<T, false, 4>(a, s);
 }
 template <typename T>
-static hipError_t bwd_t(const Attn32BwdArgs& a, hipStream_t s) {
+static hipError_t bwd_t(const AttnBwdArgs& a, hipStream_t s) {
   // a gradient shorter than the saved sequences: the short causal kernel only (the others take every position)
   if (a.Ls > 0 && a.Ls != a.L && (a.Ls < a.L || a.L > SROWS || !a.causal)) return hipErrorInvalidValue;
   if (a.prefix != 0) {      // shared prefix: slots of L - P gradient rows must hold the P prefix rows
@@ -1447,14 +1447,14 @@ static hipError_t bwd_t(const Attn32BwdArgs& a, hipStream_t s) {
   return a.causal ? bwd_x<T, true, 4>(a, s) : bwd_x<T, false, 4>(a, s);
 }
 
-hipError_t launch_attn32_fwd(int dtype, const Attn32Args& a, hipStream_t s) {
-  if (a.L <= 0 || a.N <= 0 || a.H <= 0 || !a.qkv_split || !a.out_split) return hipErrorInvalidValue;
+hipError_t attn32_fwd(int dtype, const AttnArgs& a, hipStream_t s) {
+  if (a.L <= 0 || a.N <= 0 || a.H <= 0 || !a.qkv || !a.out) return hipErrorInvalidValue;
   if (dtype == DT_F16) return fwd_t<f16>(a, s);
   if (dtype == DT_BF16) return fwd_t<bf16>(a, s);
   return hipErrorInvalidValue;
 }
-hipError_t launch_attn32_bwd(int dtype, const Attn32BwdArgs& a, hipStream_t s) {
-  if (a.L <= 0 || a.N <= 0 || a.H <= 0 || !a.qkv_split || !a.out_split || !a.dout_split || !a.lse || !a.delta || !a.dqkv_split)
+hipError_t attn32_bwd(int dtype, const AttnBwdArgs& a, hipStream_t s) {
+  if (a.L <= 0 || a.N <= 0 || a.H <= 0 || !a.qkv || !a.out || !a.dout || !a.lse || !a.delta || !a.dqkv)
     return hipErrorInvalidValue;
   if (dtype == DT_F16) return bwd_t<f16>(a, s);
   if (dtype == DT_BF16) return bwd_t<bf16>(a, s);

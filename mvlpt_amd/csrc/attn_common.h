@@ -5,6 +5,10 @@
 
 namespace mvlpt {
 
+// The pair formats (AttnArgs::fmt 1 / 2) of launch_attn_fwd / launch_attn_bwd: attention32.hip, any L, its own shape checks
+hipError_t attn32_fwd(int dtype, const AttnArgs& a, hipStream_t s);
+hipError_t attn32_bwd(int dtype, const AttnBwdArgs& a, hipStream_t s);
+
 // ---- staging helpers -------------------------------------------------------------------------------------
 // Row-major [LP][64] 16-bit LDS image with 128-B rows whose 16-B chunks are XOR-swizzled by (row & 7), filled by
 // LDS-DMA (global_load_lds, 16 B per lane, no VGPR round trip, all slabs in flight at once):

@@ -153,12 +153,13 @@ struct TowerState {
   int N = 0, L = 0, d = 0, H = 0, layers = 0;
   // Gradient length (mvlpt_set_text_grad_len): the leading positions of every sequence a backward processes.  Every gradient buffer
   // (dx32 .. delta) is compact [N, Lg, .]; the saved forward tensors keep the pitch L and are read through the row map
-  // r -> (r / Lg) * L + r % Lg.  Lg == L: every position (the image tower, and the text tower's default).
+  // saved_rows().  Lg == L: every position (the image tower, and the text tower's default).
   int Lg = 0;
+  RowMap saved_rows() const { return Lg != L ? RowMap{Lg, L} : RowMap(); }      // compact gradient row -> row of a saved tensor
   // Shared prefix of a text tower (mvlpt_set_text_shared_prefix; 0: none).  P > 0: the first P positions are the same rows in every
   // class sequence and are evaluated once.  The tower then runs over N = C + 1 "slots" of L rows: slot 0 holds the prefix in its first
   // P rows, slot c + 1 positions P .. of class c, so L and Lg above are the sequence and gradient lengths MINUS P and every row-wise
-  // kernel and row map works on the slots unchanged.  Only the attention core (Attn32Args::prefix), the prompt tables (glue.hip) and
+  // kernel and row map works on the slots unchanged.  Only the attention core (AttnArgs::prefix), the prompt tables (glue.hip) and
   // the last block's compact rows (C of them) know.  kv_part: the attention backward's fp32 dK / dV partials of the prefix keys
   // [N, P, 2d]; part_mul = 2^-s: what they are scaled by when they enter slot 0 (the sum over many classes must stay inside the
   // 16-bit hi plane), undone by the context gather.
@@ -363,24 +364,19 @@ static hipError_t attn_fwd_timed(Engine* E, const AttnArgs& a, double flops, dou
 }
 
 // ------------------------------------------------------------------------------------------------ kernel wrappers
-// LayerNorm folding of one GEMM call (GemmArgs::ln_* / fold_*)
-struct Fold {
-  const float* ln_gamma = nullptr; void* ln_x16 = nullptr; int ln_split = 0; float* ln_part = nullptr; int ln_ntp = 0;   // producer
-  const float* fold_part = nullptr; const float* fold_colsum = nullptr; int fold_ntp = 0, fold_nt = 0;                   // consumer
-  const void* rp_hi_in = nullptr; const uint8_t* rp_lo_in = nullptr; uint8_t* rp_lo_out = nullptr;                       // packed stream (EPI_RESIDP_LN)
-};
-hipError_t gemm(Engine* E, int epi, const void* A, WRef Bt, int M, int N, int K, const float* bias, const void* aux,
-                const float* resid, void* out, void* out2, hipStream_t s, int dtype = -1, int a_split = 0, const Fold* f = nullptr,
-                int lda = 0, int ldo = 0, int aux_seq = 0, int aux_pitch = 0) {
-  GemmArgs g{A, Bt.p, M, N, K, bias, aux, resid, out, out2};
-  g.a_split = a_split; g.ldb = Bt.ld; g.w8_exp = Bt.e8; g.lda = lda; g.ldo = ldo; g.aux_seq = aux_seq; g.aux_pitch = aux_pitch;
-  if (f) {
-    g.ln_gamma = f->ln_gamma; g.ln_x16 = f->ln_x16; g.ln_split = f->ln_split; g.ln_part = f->ln_part; g.ln_ntp = f->ln_ntp;
-    g.fold_part = f->fold_part; g.fold_colsum = f->fold_colsum; g.fold_ntp = f->fold_ntp; g.fold_nt = f->fold_nt;
-    g.rp_hi_in = f->rp_hi_in; g.rp_lo_in = f->rp_lo_in; g.rp_lo_out = f->rp_lo_out;
-  }
-  g.out_lo8 = (a_split == 2 && (epi == EPI_GELU_SPLIT || epi == EPI_GELUBWD_SPLIT)) ? 1 : 0;
+// What a launch's arguments are is decided in kernels.h: the call sites below fill the launcher's struct by field name, and the wrappers
+// add only what the engine knows, the compute dtype, the packed weight (WRef -> Bt / ldb / w8_exp), the mixed-pair output rule and
+// the profile record.  gemm_args / ln_args / ln_bwd_args: the fields every such launch has.
+GemmArgs gemm_args(const void* A, int M, int N, int K, void* out) {
+  GemmArgs g;
+  g.A = A; g.M = M; g.N = N; g.K = K; g.out = out;
+  return g;
+}
+hipError_t gemm(Engine* E, int epi, GemmArgs g, WRef Bt, hipStream_t s, int dtype = -1) {
+  g.Bt = Bt.p; g.ldb = Bt.ld; g.w8_exp = Bt.e8;
+  g.out_lo8 = (g.a_split == 2 && (epi == EPI_GELU_SPLIT || epi == EPI_GELUBWD_SPLIT)) ? 1 : 0;
   const int dt = dtype >= 0 ? dtype : E->dt;
+  const int M = g.M, N = g.N, K = g.K, a_split = g.a_split;
   const double ob = (epi == EPI_RESIDP_LN) ? 6.0 : (epi == EPI_RESID32) ? 8.0 : (epi == EPI_RESID32_LN) ? 8.0 + 2.0 * (a_split ? 1.5 : 1.0) : ((epi == EPI_STORE32 || epi == EPI_STORE_SPLIT) ? 4.0 : ((epi == EPI_GELUBWD || epi == EPI_GELU_SPLIT) ? 4.0 :
                     (epi == EPI_GELUBWD_SPLIT ? 6.0 : 2.0)));
   // the dominant kernel is timed by its own dispatch (start/stop timestamps of the AQL packet): no marker packets
@@ -390,25 +386,31 @@ hipError_t gemm(Engine* E, int epi, const void* A, WRef Bt, int M, int N, int K,
     // (16-bit pair) or 1.5x in 16-bit-MFMA time (mixed pair: the residual term runs on the fp8 MFMA at twice the rate)
     const double xa = a_split == 2 ? 1.5 : (a_split ? 2.0 : 1.0);
     E->prof.push_back(ProfRec{PC_GEMM, ea, eb, 2.0 * M * N * K,
-                              2.0 * ((double)M * K * xa + (double)N * K * (a_split == 2 ? 1.5 : 1.0)) + ob * M * N + (out2 ? 2.0 * M * N : 0),
-                              2.0 * M * N * K * xa, M, N, K, epi, a_split, (f && f->fold_part) ? 1 : 0});
+                              2.0 * ((double)M * K * xa + (double)N * K * (a_split == 2 ? 1.5 : 1.0)) + ob * M * N + (g.out2 ? 2.0 * M * N : 0),
+                              2.0 * M * N * K * xa, M, N, K, epi, a_split, g.fold_part ? 1 : 0});
   }
   return launch_gemm(dt, epi, g, s, ea, eb);
 }
-hipError_t ln_fwd(Engine* E, int out_dt, const float* x, const int32_t* idx, int row_mul, const LNp& p, void* y, int rows, int d,
-                  hipStream_t s, int split = 0) {
-  LnFwdArgs a{x, idx, row_mul, p.g, p.b, y, rows, d};
-  a.split = (split && out_dt != DT_F32) ? split : 0;
-  ProfScope ps(E, s, PC_LN_FWD, 8.0 * rows * d, (double)rows * d * (4.0 + (out_dt == DT_F32 ? 4.0 : 2.0)));
+// (every row of x in order: row_idx null, row_mul 1)
+LnFwdArgs ln_args(const float* x, const LNp& p, void* y, int rows, int d) {
+  LnFwdArgs a;
+  a.x = x; a.gamma = p.g; a.beta = p.b; a.y = y; a.rows = rows; a.d = d;
+  return a;
+}
+hipError_t ln_fwd(Engine* E, int out_dt, const LnFwdArgs& a, hipStream_t s) {
+  ProfScope ps(E, s, PC_LN_FWD, 8.0 * a.rows * a.d, (double)a.rows * a.d * (4.0 + (out_dt == DT_F32 ? 4.0 : 2.0)));
   return launch_ln_fwd(out_dt, a, s);
 }
-hipError_t ln_bwd(Engine* E, const void* dy, int dy_dtype, const float* x, const int32_t* idx, int row_mul, const LNp& p,
-                  const float* resid, float* out32, void* out16, int rows, int d, hipStream_t s, int dtype = -1, int split = 0,
-                  int x_seq = 0, int x_pitch = 0) {
-  LnBwdArgs a{dy, dy_dtype, x, idx, row_mul, p.g, resid, out32, out16, rows, d};
-  a.split = split; a.x_seq = x_seq; a.x_pitch = x_pitch;
-  ProfScope ps(E, s, PC_LN_BWD, 14.0 * rows * d, (double)rows * d * ((dy_dtype == DT_F32 ? 4.0 : 2.0) + 4.0 + (resid ? 4.0 : 0.0) + 4.0 + (out16 ? 2.0 : 0.0)));
-  return launch_ln_bwd(dtype >= 0 ? dtype : E->dt, a, s);
+// (dy fp32: the dX GEMMs that feed a LayerNorm backward store fp32)
+LnBwdArgs ln_bwd_args(const float* dy, const float* x, const LNp& p, float* out32, int rows, int d) {
+  LnBwdArgs a;
+  a.dy = dy; a.dy_dtype = DT_F32; a.x = x; a.gamma = p.g; a.out32 = out32; a.rows = rows; a.d = d;
+  return a;
+}
+hipError_t ln_bwd(Engine* E, const LnBwdArgs& a, hipStream_t s) {
+  ProfScope ps(E, s, PC_LN_BWD, 14.0 * a.rows * a.d,
+               (double)a.rows * a.d * ((a.dy_dtype == DT_F32 ? 4.0 : 2.0) + 4.0 + (a.resid ? 4.0 : 0.0) + 4.0 + (a.out16 ? 2.0 : 0.0)));
+  return launch_ln_bwd(E->dt, a, s);
 }
 
 // ------------------------------------------------------------------------------------------------ tower workspace
@@ -433,8 +435,16 @@ int wide_pitch(int cols) {
 // segment (the last one), the k segment inputs stay (x[0] and k - 1 boundary buffers)
 // gelu (Engine::act == ACT_GELU): one more fp32 [T, 4d] buffer, the scratch of the stand-alone activation pass
 // Lg (TowerState::Lg; 0: L): the gradient buffers hold N * Lg rows
-void carve_tower(Bump& bp, const TowerW& W, TowerState& st, int N, int L, bool save, bool causal, bool exact, int xs, bool gelu,
-                 int segments = 1, int Lg = 0, int P = 0) {
+struct TowerShape {
+  int N = 0, L = 0;
+  bool save = false, causal = false, exact = false;
+  int xs = 0;            // the pair format of an `exact` tower (split_kind)
+  bool gelu = false;
+  int segments = 1, Lg = 0, P = 0;
+};
+void carve_tower(Bump& bp, const TowerW& W, TowerState& st, const TowerShape& t) {
+  const int N = t.N, L = t.L, Lg = t.Lg, P = t.P, xs = t.xs, segments = t.segments;
+  const bool save = t.save, causal = t.causal, exact = t.exact, gelu = t.gelu;
   const size_t T = (size_t)N * L, d = W.width, H = W.heads, X = exact ? 2 : 1; const int nl = W.layers;
   st = TowerState();
   st.P = P;      // (N, L, Lg are the slot figures then: TowerState::P)
@@ -504,26 +514,19 @@ int split_kind(const Engine* E) { return (E->prec_mode == MVLPT_PREC_SPLIT_ALL |
 int attn_fwd(Engine* E, TowerState& st, int l, int q_rows, bool timed, hipStream_t s) {
   const double T = (double)st.N * st.L, rows = q_rows > 0 ? (double)q_rows : (double)st.L;
   const double fl = 4.0 * rows * st.L * (double)st.hw * st.N * st.H * (st.causal ? 0.5 : 1.0);
-  float* lse = st.keep ? st.lse[l] : nullptr;
+  AttnArgs a;
+  a.qkv = st.qkv[l]; a.out = st.attn[l]; a.lse = st.keep ? st.lse[l] : nullptr;
+  a.N = st.seqs(); a.L = st.L + st.P; a.H = st.H; a.causal = st.causal ? 1 : 0;      // (shared prefix: slots, TowerState::P)
+  a.q_rows = q_rows; a.prefix = st.P; a.fmt = st.xs;
   if (st.hw != 64) {      // a wide-headed image tower: frozen, prompt-free, forward-only on single operands (kRefuseWide)
     if (st.xs || st.causal || st.keep) return fail(E, MVLPT_ERR_STATE, "wide-headed attention: single operands, non-causal, nothing saved");
-    AttnArgs a{st.qkv[l], st.attn[l], nullptr, st.N, st.L, st.H, 0, q_rows};
     ProfScope ps(E, s, PC_ATTN_FWD, fl, T * st.d * 2.0 * (q_rows > 0 ? 2.0 : 4.0));
     HIPCHK(E, launch_attn_fwd_wide(E->dt, a, st.hw, s));
     return 0;
   }
-  if (st.xs) {
-    Attn32Args a{st.qkv[l], st.attn[l], lse, st.seqs(), st.L + st.P, st.H, st.causal ? 1 : 0, q_rows};
-    a.out_lo8 = st.xs == 2 ? 1 : 0; a.prefix = st.P;
-    ProfScope ps(E, s, PC_ATTN_FWD, fl, T * st.d * 16.0);
-    HIPCHK(E, launch_attn32_fwd(E->dt, a, s));
-    return 0;
-  }
-  AttnArgs a{st.qkv[l], st.attn[l], lse, st.seqs(), st.L + st.P, st.H, st.causal ? 1 : 0, q_rows};
-  a.prefix = st.P;      // (shared prefix: slots, TowerState::P)
-  const double by = T * st.d * 2.0 * (q_rows > 0 ? 2.0 : 4.0);
+  const double by = st.xs ? T * st.d * 16.0 : T * st.d * 2.0 * (q_rows > 0 ? 2.0 : 4.0);
   ProfScope ps(E, s, PC_ATTN_FWD, fl, by);
-  HIPCHK(E, timed ? attn_fwd_timed(E, a, fl, by, s) : launch_attn_fwd(E->dt, a, s));
+  HIPCHK(E, timed && !st.xs ? attn_fwd_timed(E, a, fl, by, s) : launch_attn_fwd(E->dt, a, s));
   return 0;
 }
 // Attention backward of layer l: dO16 -> dqkv16 at full width, or (cls, single operands only) the backward of query 0 of every
@@ -537,18 +540,11 @@ int attn_bwd(Engine* E, TowerState& st, int l, const Compact* cls, hipStream_t s
   }
   // (the positions that carry a gradient: st.Lg of the st.L saved ones)
   const double fl = 14.0 * st.Lg * st.Lg * 64.0 * st.N * st.H * cz, Tg = (double)st.N * st.Lg;
-  if (st.xs) {
-    Attn32BwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.seqs(), st.Lg + st.P, st.H, st.causal ? 1 : 0};
-    a.lo8 = st.xs == 2 ? 1 : 0; a.Ls = st.L + st.P;
-    a.prefix = st.P; a.kv_part = st.kv_part; a.part_mul = st.part_mul;      // (shared prefix: one more launch, the reduction of kv_part)
-    ProfScope ps(E, s, PC_ATTN_BWD, fl, Tg * st.d * 32.0);
-    HIPCHK(E, launch_attn32_bwd(E->dt, a, s));
-    return 0;
-  }
-  AttnBwdArgs a{st.qkv[l], st.attn[l], st.dO16, st.lse[l], st.delta, st.dqkv16, st.seqs(), st.Lg + st.P, st.H, st.causal ? 1 : 0};
-  a.Ls = st.L + st.P;
-  a.prefix = st.P; a.kv_part = st.kv_part; a.part_mul = st.part_mul;
-  ProfScope ps(E, s, PC_ATTN_BWD, fl, Tg * st.d * 2.0 * 8.0);
+  AttnBwdArgs a;
+  a.qkv = st.qkv[l]; a.out = st.attn[l]; a.dout = st.dO16; a.lse = st.lse[l]; a.delta = st.delta; a.dqkv = st.dqkv16;
+  a.N = st.seqs(); a.L = st.Lg + st.P; a.Ls = st.L + st.P; a.H = st.H; a.causal = st.causal ? 1 : 0; a.fmt = st.xs;
+  a.prefix = st.P; a.kv_part = st.kv_part; a.part_mul = st.part_mul;      // (shared prefix: one more launch, the reduction of kv_part)
+  ProfScope ps(E, s, PC_ATTN_BWD, fl, st.xs ? Tg * st.d * 32.0 : Tg * st.d * 2.0 * 8.0);
   HIPCHK(E, launch_attn_bwd(E->dt, a, s));
   return 0;
 }
@@ -556,54 +552,60 @@ int attn_bwd(Engine* E, TowerState& st, int l, const Compact* cls, hipStream_t s
 // ---- LayerNorm folding (kernels.h GemmArgs::ln_* / fold_*): the residual GEMM in front of a LayerNorm writes
 // round16(x * gamma) into h16 and per-row partial sums; the GEMM behind it applies mean / rstd in its epilogue.
 // which = 0: the LayerNorm is ln_1 (producer: FC2 of the previous block), 1: ln_2 (producer: this block's out-projection).
-bool fold_producer(Engine* E, TowerState& st, int which, int M, int N, int K, const LNp& ln, hipStream_t s, Fold* f) {
+// fold_producer: `g` (M, N, K set) becomes the producer when its launch can be one, and the tower remembers the slots it fills;
+// fold_consumer: `g` reads them, colsum = W gamma of its weight (Linear::fold_s, or fold_sg on the packed stream).
+bool fold_producer(Engine* E, TowerState& st, int which, const LNp& ln, hipStream_t s, GemmArgs& g) {
   if (!st.fold) return false;
-  GemmArgs q{};
-  q.M = M; q.N = N; q.K = K; q.a_split = st.xs;
+  GemmArgs q;      // (the shape and the operand format: all the launcher's routing reads)
+  q.M = g.M; q.N = g.N; q.K = g.K; q.a_split = st.xs;
   const int bn = gemm_tile_n(E->dt, EPI_RESID32_LN, q, s);      // the launcher's N-tile for this problem on this stream
-  if (bn <= 0 || N % bn) return false;
-  const int nt = N / 128, ntp = (nt + 1) & ~1;          // one slot per 128 output columns, whatever the tile geometry
+  if (bn <= 0 || g.N % bn) return false;
+  const int nt = g.N / 128, ntp = (nt + 1) & ~1;          // one slot per 128 output columns, whatever the tile geometry
   if (ntp > FOLD_NTP) return false;
-  *f = Fold();
-  f->ln_gamma = ln.g; f->ln_x16 = st.h16; f->ln_split = st.xs; f->ln_part = st.part[which]; f->ln_ntp = ntp;
+  g.ln_gamma = ln.g; g.ln_x16 = st.h16; g.ln_split = st.xs; g.ln_part = st.part[which]; g.ln_ntp = ntp;
   st.nt[which] = nt; st.ntp[which] = ntp;
   return true;
 }
-Fold fold_consumer(const TowerState& st, int which, const Linear& L) {
-  Fold f;
-  f.fold_part = st.part[which]; f.fold_colsum = L.fold_s; f.fold_ntp = st.ntp[which]; f.fold_nt = st.nt[which];
-  return f;
+void fold_consumer(const TowerState& st, int which, const float* colsum, GemmArgs& g) {
+  g.fold_part = st.part[which]; g.fold_colsum = colsum; g.fold_ntp = st.ntp[which]; g.fold_nt = st.nt[which];
 }
 
 // ---- The MLP's activation (Engine::act).  QuickGELU lives in the GEMM epilogues (EPI_GELU* / EPI_GELUBWD*).  The exact GELU of a
 // checkpoint trained with nn.GELU is a pass of its own (activation.hip): the GEMM stores fp32 into `scratch` (EPI_STORE32: the activation
-// sees u = acc + bias unrounded) and the pass writes the A operand of the next GEMM in the tower's format xs at the pitch ldo.
-// mlp_up: a16 = act(h16 fc^T + bias), u16 (optional) = the saved pre-activation.  f: the consumer side of a folded ln_2 (QuickGELU only)
-int mlp_up(Engine* E, const void* h16, WRef fc, const float* bias, int M, int d, int xs, void* a16, int ldo, void* u16, float* scratch,
-           const Fold* f, hipStream_t s) {
+// sees u = acc + bias unrounded) and the pass writes the A operand of the next GEMM in the tower's format at the pitch g.ldo.
+// mlp_up: g.out = act(g.A fc^T + g.bias) in the format g.a_split, u16 (optional) = the saved pre-activation.  g may be the consumer
+// side of a folded ln_2 (QuickGELU only)
+int mlp_up(Engine* E, GemmArgs g, WRef fc, void* u16, float* scratch, hipStream_t s) {
   if (E->act == ACT_QUICKGELU) {
-    HIPCHK(E, gemm(E, xs ? EPI_GELU_SPLIT : EPI_GELU, h16, fc, M, 4 * d, d, bias, nullptr, nullptr, a16, u16, s, -1, xs, f, 0, ldo));
+    g.out2 = u16;
+    HIPCHK(E, gemm(E, g.a_split ? EPI_GELU_SPLIT : EPI_GELU, g, fc, s));
     return 0;
   }
-  if (f || !scratch) return fail(E, MVLPT_ERR_STATE, "exact GELU: the MLP-up GEMM has no folded form and needs its scratch");
-  HIPCHK(E, gemm(E, EPI_STORE32, h16, fc, M, 4 * d, d, bias, nullptr, nullptr, scratch, nullptr, s, -1, xs));
-  ProfScope ps(E, s, PC_GLUE, 10.0 * M * 4 * d, (double)M * 4 * d * (4.0 + (xs == 1 ? 4.0 : xs ? 3.0 : 2.0) + (u16 ? 2.0 : 0.0)));
-  HIPCHK(E, launch_act_fwd(E->dt, E->act, ActArgs{scratch, 0, a16, xs, ldo, u16, M, 4 * d}, s));
+  if (g.fold_part || !scratch) return fail(E, MVLPT_ERR_STATE, "exact GELU: the MLP-up GEMM has no folded form and needs its scratch");
+  const int M = g.M, N = g.N, xs = g.a_split;
+  ActArgs a;
+  a.in = scratch; a.out = g.out; a.fmt = xs; a.ldo = g.ldo; a.u16 = u16; a.M = M; a.N = N;
+  g.out = scratch; g.ldo = 0;
+  HIPCHK(E, gemm(E, EPI_STORE32, g, fc, s));
+  ProfScope ps(E, s, PC_GLUE, 10.0 * M * N, (double)M * N * (4.0 + (xs == 1 ? 4.0 : xs ? 3.0 : 2.0) + (u16 ? 2.0 : 0.0)));
+  HIPCHK(E, launch_act_fwd(E->dt, E->act, a, s));
   return 0;
 }
-// mlp_up_bwd: du16 = (dx16 pr) * act'(u16), the gradient at the pre-activation in the format xs
-// u_seq > 0: u16 holds sequences of u_pitch rows and row m of the gradient belongs to row (m / u_seq) * u_pitch + m % u_seq of it
-int mlp_up_bwd(Engine* E, const void* dx16, WRef prt, int M, int d, int xs, const void* u16, void* du16, int ldo, float* scratch, hipStream_t s,
-               int u_seq = 0, int u_pitch = 0) {
+// mlp_up_bwd: g.out = (g.A prt^T) * act'(g.aux), the gradient at the pre-activation in the format g.a_split; g.aux is the saved u16,
+// read through g.aux_rows
+int mlp_up_bwd(Engine* E, GemmArgs g, WRef prt, float* scratch, hipStream_t s) {
   if (E->act == ACT_QUICKGELU) {
-    HIPCHK(E, gemm(E, xs ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, dx16, prt, M, 4 * d, d, nullptr, u16, nullptr, du16, nullptr, s, -1, xs, nullptr, 0, ldo,
-                   u_seq, u_pitch));
+    HIPCHK(E, gemm(E, g.a_split ? EPI_GELUBWD_SPLIT : EPI_GELUBWD, g, prt, s));
     return 0;
   }
   if (!scratch) return fail(E, MVLPT_ERR_STATE, "exact GELU: the saved state was carved without the activation scratch");
-  HIPCHK(E, gemm(E, EPI_STORE32, dx16, prt, M, 4 * d, d, nullptr, nullptr, nullptr, scratch, nullptr, s, -1, xs));
-  ProfScope ps(E, s, PC_GLUE, 14.0 * M * 4 * d, (double)M * 4 * d * (6.0 + (xs == 1 ? 4.0 : xs ? 3.0 : 2.0)));
-  HIPCHK(E, launch_act_bwd(E->dt, E->act, ActArgs{scratch, 0, du16, xs, ldo, const_cast<void*>(u16), M, 4 * d, u_seq, u_pitch}, s));
+  const int M = g.M, N = g.N, xs = g.a_split;
+  ActArgs a;
+  a.in = scratch; a.out = g.out; a.fmt = xs; a.ldo = g.ldo; a.u16 = const_cast<void*>(g.aux); a.M = M; a.N = N; a.u_rows = g.aux_rows;
+  g.out = scratch; g.ldo = 0; g.aux = nullptr; g.aux_rows = RowMap();
+  HIPCHK(E, gemm(E, EPI_STORE32, g, prt, s));
+  ProfScope ps(E, s, PC_GLUE, 14.0 * M * N, (double)M * N * (6.0 + (xs == 1 ? 4.0 : xs ? 3.0 : 2.0)));
+  HIPCHK(E, launch_act_bwd(E->dt, E->act, a, s));
   return 0;
 }
 
@@ -618,22 +620,29 @@ int block_fwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s, 
   const Block& B = W.blocks[l];
   const int T = st.N * st.L, d = st.d, xs = st.xs, wp = st.wide_pitch;
   float* xin = st.x[2 * l]; float* xmid = st.x[2 * l + 1]; float* xout = st.x[2 * l + 2];
-  Fold fq, fo, ff, fp;
-  if (ln1_folded) fq = fold_consumer(st, 0, B.qkv);
-  else HIPCHK(E, ln_fwd(E, E->dt, xin, nullptr, 1, B.ln1, st.h16, T, d, s, xs));
-  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, st.h16, B.qkv.fw(), T, 3 * d, d, ln1_folded ? B.qkv.fold_b : B.qkv.b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, xs,
-                 ln1_folded ? &fq : nullptr));
+  LnFwdArgs ln = ln_args(xin, B.ln1, st.h16, T, d);
+  ln.split = xs;
+  GemmArgs q = gemm_args(st.h16, T, 3 * d, d, st.qkv[l]);
+  q.a_split = xs; q.bias = ln1_folded ? B.qkv.fold_b : B.qkv.b;
+  if (ln1_folded) fold_consumer(st, 0, B.qkv.fold_s, q);
+  else HIPCHK(E, ln_fwd(E, E->dt, ln, s));
+  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, q, B.qkv.fw(), s));
   if (int rc = attn_fwd(E, st, l, 0, true, s)) return rc;
+  GemmArgs o = gemm_args(st.attn[l], T, d, d, xmid);
+  o.a_split = xs; o.bias = B.o.b; o.resid = xin;
   // (exact GELU: ln_2 stays a pass of its own: its consumer stores fp32, which has no folded epilogue; ln_1 is folded as ever)
-  const bool p2 = E->act == ACT_QUICKGELU && fold_producer(E, st, 1, T, d, d, B.ln2, s, &fo);
-  HIPCHK(E, gemm(E, p2 ? EPI_RESID32_LN : EPI_RESID32, st.attn[l], B.o.fw(), T, d, d, B.o.b, nullptr, xin, xmid, nullptr, s, -1, xs, p2 ? &fo : nullptr));
-  if (p2) ff = fold_consumer(st, 1, B.fc);
-  else HIPCHK(E, ln_fwd(E, E->dt, xmid, nullptr, 1, B.ln2, st.h16, T, d, s, xs));
-  if (int rc = mlp_up(E, st.h16, B.fc.fw(), p2 ? B.fc.fold_b : B.fc.b, T, d, xs, st.a16, wp, st.keep ? st.u[l] : nullptr, st.act32,
-                      p2 ? &ff : nullptr, s)) return rc;
-  const bool p1 = next_ln1 && fold_producer(E, st, 0, T, d, 4 * d, *next_ln1, s, &fp);
-  HIPCHK(E, gemm(E, p1 ? EPI_RESID32_LN : EPI_RESID32, st.a16, B.pr.fw(), T, d, 4 * d, B.pr.b, nullptr, xmid, xout, nullptr, s, -1, xs, p1 ? &fp : nullptr,
-                 wp, 0));
+  const bool p2 = E->act == ACT_QUICKGELU && fold_producer(E, st, 1, B.ln2, s, o);
+  HIPCHK(E, gemm(E, p2 ? EPI_RESID32_LN : EPI_RESID32, o, B.o.fw(), s));
+  GemmArgs fc = gemm_args(st.h16, T, 4 * d, d, st.a16);
+  fc.a_split = xs; fc.bias = p2 ? B.fc.fold_b : B.fc.b; fc.ldo = wp;
+  ln.x = xmid; ln.gamma = B.ln2.g; ln.beta = B.ln2.b;
+  if (p2) fold_consumer(st, 1, B.fc.fold_s, fc);
+  else HIPCHK(E, ln_fwd(E, E->dt, ln, s));
+  if (int rc = mlp_up(E, fc, B.fc.fw(), st.keep ? st.u[l] : nullptr, st.act32, s)) return rc;
+  GemmArgs pr = gemm_args(st.a16, T, d, 4 * d, xout);
+  pr.a_split = xs; pr.bias = B.pr.b; pr.resid = xmid; pr.lda = wp;
+  const bool p1 = next_ln1 && fold_producer(E, st, 0, *next_ln1, s, pr);
+  HIPCHK(E, gemm(E, p1 ? EPI_RESID32_LN : EPI_RESID32, pr, B.pr.fw(), s));
   if (produced) *produced = p1;
   return 0;
 }
@@ -648,41 +657,56 @@ int block_fwd_packed(Engine* E, const TowerW& W, TowerState& st, int l, hipStrea
   if (E->act != ACT_QUICKGELU) return fail(E, MVLPT_ERR_STATE, "packed residual stream: QuickGELU only (the image forward does not take it under the exact GELU)");
   void* hi = st.x[0];
   uint8_t* lo = (uint8_t*)st.x[0] + (size_t)T * d * 2;
-  Fold fq = fold_consumer(st, 0, B.qkv), fo, ff, fp;
-  fq.fold_colsum = B.qkv.fold_sg;
-  HIPCHK(E, gemm(E, EPI_STORE16, hi, B.qkv.fwg(), T, 3 * d, d, B.qkv.fold_b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, 0, &fq));
+  GemmArgs q = gemm_args(hi, T, 3 * d, d, st.qkv[l]);
+  q.bias = B.qkv.fold_b;
+  fold_consumer(st, 0, B.qkv.fold_sg, q);
+  HIPCHK(E, gemm(E, EPI_STORE16, q, B.qkv.fwg(), s));
   dbg_ck(E, st.qkv[l], (size_t)T * 3 * d * 2, s);
   if (int rc = attn_fwd(E, st, l, 0, true, s)) return rc;
   dbg_ck(E, st.attn[l], (size_t)T * d * 2, s);
-  if (!fold_producer(E, st, 1, T, d, d, B.ln2, s, &fo)) return fail(E, MVLPT_ERR_STATE, "packed residual stream: out-projection cannot produce the ln_2 statistics");
-  fo.rp_hi_in = hi; fo.rp_lo_in = lo; fo.rp_lo_out = lo;
-  HIPCHK(E, gemm(E, EPI_RESIDP_LN, st.attn[l], B.o.fw(), T, d, d, B.o.b, nullptr, nullptr, hi, nullptr, s, -1, 0, &fo));
-  dbg_ck(E, hi, (size_t)T * d * 3, s); dbg_ck(E, fo.ln_part, (size_t)T * fo.ln_ntp * 8, s);
-  ff = fold_consumer(st, 1, B.fc);
-  ff.fold_colsum = B.fc.fold_sg;
-  HIPCHK(E, gemm(E, EPI_GELU, hi, B.fc.fwg(), T, 4 * d, d, B.fc.fold_b, nullptr, nullptr, st.a16, nullptr, s, -1, 0, &ff));
+  GemmArgs o = gemm_args(st.attn[l], T, d, d, hi);
+  o.bias = B.o.b; o.rp_hi_in = hi; o.rp_lo_in = lo; o.rp_lo_out = lo;
+  if (!fold_producer(E, st, 1, B.ln2, s, o)) return fail(E, MVLPT_ERR_STATE, "packed residual stream: out-projection cannot produce the ln_2 statistics");
+  HIPCHK(E, gemm(E, EPI_RESIDP_LN, o, B.o.fw(), s));
+  dbg_ck(E, hi, (size_t)T * d * 3, s); dbg_ck(E, o.ln_part, (size_t)T * o.ln_ntp * 8, s);
+  GemmArgs fc = gemm_args(hi, T, 4 * d, d, st.a16);
+  fc.bias = B.fc.fold_b;
+  fold_consumer(st, 1, B.fc.fold_sg, fc);
+  HIPCHK(E, gemm(E, EPI_GELU, fc, B.fc.fwg(), s));
   dbg_ck(E, st.a16, (size_t)T * 4 * d * 2, s);
-  if (!fold_producer(E, st, 0, T, d, 4 * d, B.ln1, s, &fp)) return fail(E, MVLPT_ERR_STATE, "packed residual stream: MLP down-projection cannot produce the ln_1 statistics");
-  fp.rp_hi_in = hi; fp.rp_lo_in = lo; fp.rp_lo_out = lo;
-  HIPCHK(E, gemm(E, EPI_RESIDP_LN, st.a16, B.pr.fw(), T, d, 4 * d, B.pr.b, nullptr, nullptr, hi, nullptr, s, -1, 0, &fp));
-  dbg_ck(E, hi, (size_t)T * d * 3, s); dbg_ck(E, fp.ln_part, (size_t)T * fp.ln_ntp * 8, s);
+  GemmArgs pr = gemm_args(st.a16, T, d, 4 * d, hi);
+  pr.bias = B.pr.b; pr.rp_hi_in = hi; pr.rp_lo_in = lo; pr.rp_lo_out = lo;
+  if (!fold_producer(E, st, 0, B.ln1, s, pr)) return fail(E, MVLPT_ERR_STATE, "packed residual stream: MLP down-projection cannot produce the ln_1 statistics");
+  HIPCHK(E, gemm(E, EPI_RESIDP_LN, pr, B.pr.fw(), s));
+  dbg_ck(E, hi, (size_t)T * d * 3, s); dbg_ck(E, pr.ln_part, (size_t)T * pr.ln_ntp * 8, s);
   return 0;
 }
 
 // dX-only backward of one block: dx32/dx16 hold d(block output) on entry and d(block input) on exit
-// The gradient buffers hold the T = N * Lg rows that carry a gradient (TowerState::Lg); the saved u and x are read through the row map.
+// The gradient buffers hold the T = N * Lg rows that carry a gradient (TowerState::Lg); the saved u and x are read through the row
+// map st.saved_rows().
 int block_bwd(Engine* E, const TowerW& W, TowerState& st, int l, hipStream_t s) {
   const Block& B = W.blocks[l];
   const int T = st.N * st.Lg, d = st.d, xs = st.xs, wp = st.wide_pitch;
-  const int ms = st.Lg != st.L ? st.Lg : 0, mp = ms ? st.L : 0;      // the row map of the saved tensors (0: none)
-  if (int rc = mlp_up_bwd(E, st.dx16, B.pr.bw(), T, d, xs, st.u[l], st.du16, wp, st.act32, s, ms, mp)) return rc;
+  GemmArgs up = gemm_args(st.dx16, T, 4 * d, d, st.du16);
+  up.a_split = xs; up.aux = st.u[l]; up.aux_rows = st.saved_rows(); up.ldo = wp;
+  if (int rc = mlp_up_bwd(E, up, B.pr.bw(), st.act32, s)) return rc;
   // the dX GEMMs that feed a LayerNorm backward store fp32 (one 16-bit rounding less per half layer)
-  HIPCHK(E, gemm(E, EPI_STORE32, st.du16, B.fc.bw(), T, d, 4 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs, nullptr, wp, 0));
-  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l + 1], nullptr, 1, B.ln2, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs, ms, mp));
-  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, st.dx16, B.o.bw(), T, d, d, nullptr, nullptr, nullptr, st.dO16, nullptr, s, -1, xs));
+  GemmArgs fc = gemm_args(st.du16, T, d, 4 * d, st.dh32);
+  fc.a_split = xs; fc.lda = wp;
+  HIPCHK(E, gemm(E, EPI_STORE32, fc, B.fc.bw(), s));
+  LnBwdArgs ln = ln_bwd_args(st.dh32, st.x[2 * l + 1], B.ln2, st.dx32, T, d);
+  ln.resid = st.dx32; ln.out16 = st.dx16; ln.split = xs; ln.x_rows = st.saved_rows();
+  HIPCHK(E, ln_bwd(E, ln, s));
+  GemmArgs o = gemm_args(st.dx16, T, d, d, st.dO16);
+  o.a_split = xs;
+  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, o, B.o.bw(), s));
   if (int rc = attn_bwd(E, st, l, nullptr, s)) return rc;
-  HIPCHK(E, gemm(E, EPI_STORE32, st.dqkv16, B.qkv.bw(), T, d, 3 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs));
-  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, B.ln1, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs, ms, mp));
+  GemmArgs q = gemm_args(st.dqkv16, T, d, 3 * d, st.dh32);
+  q.a_split = xs;
+  HIPCHK(E, gemm(E, EPI_STORE32, q, B.qkv.bw(), s));
+  ln.x = st.x[2 * l]; ln.gamma = B.ln1.g;
+  HIPCHK(E, ln_bwd(E, ln, s));
   return 0;
 }
 
@@ -698,71 +722,99 @@ void carve_compact(Bump& bp, Compact& c, size_t R, size_t d, size_t X, bool gelu
   if (gelu) c.act32 = bp.take<float>(R * 4 * d);
 }
 // compact row r <-> token row rows[r] or (rows == null) row 0 of sequence r; scatter: compact -> full width
-// Lfar (0: L): `rows` addresses sequences of L rows and the full-width side holds Lfar rows of each (TowerState::Lg)
-hipError_t move_rows(const void* src, void* dst, const int32_t* rows, int R, int L, size_t row_bytes, int scatter, hipStream_t s, int Lfar = 0) {
-  if (rows) return launch_copy_rows(src, dst, rows, R, (int)row_bytes, scatter, s, Lfar && Lfar != L ? L : 0, Lfar && Lfar != L ? Lfar : 0);
-  if (Lfar && Lfar != L) return hipErrorInvalidValue;
-  return launch_copy_rows_strided(src, dst, R, scatter ? row_bytes : L * row_bytes, scatter ? L * row_bytes : row_bytes, (int)row_bytes, s);
+// A gather reads the saved tensors (pitch st.L).  A scatter writes the gradient buffers, which hold st.Lg rows of every sequence while
+// `rows` goes on naming saved rows: st.saved_rows()
+hipError_t move_rows(const TowerState& st, const void* src, void* dst, const int32_t* rows, int R, size_t row_bytes, int scatter, hipStream_t s) {
+  const RowMap far = scatter ? st.saved_rows() : RowMap();
+  if (rows) return launch_copy_rows(src, dst, rows, R, (int)row_bytes, scatter, s, far);
+  if (far.seq) return hipErrorInvalidValue;
+  return launch_copy_rows_strided(src, dst, R, scatter ? row_bytes : st.L * row_bytes, scatter ? st.L * row_bytes : row_bytes, (int)row_bytes, s);
 }
+// Which rows a tower's last block is evaluated on and what closes it.
 // Image: only x[:, 0, :] of the last block is read (trainers/mvlpt.py:88), rows == null, and only the CLS query runs (q_rows = 1).
-// Text: only x[c, eot_c] (trainers/mvlpt.py:126-128), rows = eot_rows, every query runs.  packed: the image tower's packed stream.
-// ln_close: ln_post / ln_final, into c.out32.  ck: mvlpt_debug_checksums fingerprints (image tower only).
-int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const int32_t* rows, int q_rows, bool packed, bool ln1_ready,
-                   const LNp& ln_close, bool ck, hipStream_t s) {
+// Text: only x[c, eot_c] (trainers/mvlpt.py:126-128), rows = eot_rows, every query runs (q_rows = 0).
+// ln_close: ln_post / ln_final, into c.out32.
+struct LastRows { const int32_t* rows; int q_rows; const LNp& ln_close; };
+// packed: the image tower's packed stream.  The image tower (rows == null) also leaves mvlpt_debug_checksums fingerprints.
+int last_block_fwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const LastRows& lr, bool packed, bool ln1_ready, hipStream_t s) {
   const int l = st.layers - 1, T = st.N * st.L, R = st.seqs(), d = st.d;
   const int xs = st.xs;                 // split-precision operands (hi|lo pairs, twice the columns) + pair-product attention
   const size_t X = xs ? 2 : 1;
+  const bool ck = !lr.rows;
   const Block& Bk = W.blocks[l];
   float* xin = st.x[2 * l];
-  Fold fq;
-  if (ln1_ready) fq = fold_consumer(st, 0, Bk.qkv);
-  else HIPCHK(E, ln_fwd(E, E->dt, xin, nullptr, 1, Bk.ln1, st.h16, T, d, s, xs));
-  if (packed) fq.fold_colsum = Bk.qkv.fold_sg;       // A = the stream's hi plane, gamma inside the weight
-  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, packed ? (void*)st.x[0] : st.h16, packed ? Bk.qkv.fwg() : Bk.qkv.fw(), T, 3 * d, d,
-                 ln1_ready ? Bk.qkv.fold_b : Bk.qkv.b, nullptr, nullptr, st.qkv[l], nullptr, s, -1, xs, ln1_ready ? &fq : nullptr));
+  LnFwdArgs ln = ln_args(xin, Bk.ln1, st.h16, T, d);
+  ln.split = xs;
+  GemmArgs q = gemm_args(packed ? (void*)st.x[0] : st.h16, T, 3 * d, d, st.qkv[l]);
+  q.a_split = xs; q.bias = ln1_ready ? Bk.qkv.fold_b : Bk.qkv.b;
+  // (packed: A = the stream's hi plane, gamma inside the weight)
+  if (ln1_ready) fold_consumer(st, 0, packed ? Bk.qkv.fold_sg : Bk.qkv.fold_s, q);
+  else HIPCHK(E, ln_fwd(E, E->dt, ln, s));
+  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, q, packed ? Bk.qkv.fwg() : Bk.qkv.fw(), s));
   if (ck) dbg_ck(E, st.qkv[l], (size_t)T * 3 * d * 2 * X, s);
   // split operands, some queries only: the other rows of the attention output are not produced, and the backward
   // (delta = rowsum(dO * O) over EVERY row, with dO = 0 off the compact rows) must not meet uninitialised memory there
-  if (xs && q_rows > 0 && st.keep) HIPCHK(E, launch_zero(st.attn[l], (size_t)T * d * 2 * X, s));
-  if (int rc = attn_fwd(E, st, l, q_rows, false, s)) return rc;
+  if (xs && lr.q_rows > 0 && st.keep) HIPCHK(E, launch_zero(st.attn[l], (size_t)T * d * 2 * X, s));
+  if (int rc = attn_fwd(E, st, l, lr.q_rows, false, s)) return rc;
   { ProfScope ps(E, s, PC_GLUE, 0, (double)R * d * 12.0);
-    HIPCHK(E, move_rows(st.attn[l], c.a16, rows, R, st.L, (size_t)d * 2 * X, 0, s));
+    HIPCHK(E, move_rows(st, st.attn[l], c.a16, lr.rows, R, (size_t)d * 2 * X, 0, s));
     if (packed) HIPCHK(E, launch_respk_unpack_rows(st.x[0], (uint8_t*)st.x[0] + (size_t)T * d * 2, st.L, c.x32, R, d, s));
-    else HIPCHK(E, move_rows(xin, c.x32, rows, R, st.L, (size_t)d * 4, 0, s)); }
+    else HIPCHK(E, move_rows(st, xin, c.x32, lr.rows, R, (size_t)d * 4, 0, s)); }
   if (ck) { dbg_ck(E, c.a16, (size_t)R * d * 2 * X, s); dbg_ck(E, c.x32, (size_t)R * d * 4, s); }
-  HIPCHK(E, gemm(E, EPI_RESID32, c.a16, Bk.o.fw(), R, d, d, Bk.o.b, nullptr, c.x32, c.xm32, nullptr, s, -1, xs));
-  HIPCHK(E, ln_fwd(E, E->dt, c.xm32, nullptr, 1, Bk.ln2, c.h16, R, d, s, xs));
-  if (int rc = mlp_up(E, c.h16, Bk.fc.fw(), Bk.fc.b, R, d, xs, c.g16, 0, st.keep ? c.u16 : nullptr, c.act32, nullptr, s)) return rc;
-  HIPCHK(E, gemm(E, EPI_RESID32, c.g16, Bk.pr.fw(), R, d, 4 * d, Bk.pr.b, nullptr, c.xm32, c.xo32, nullptr, s, -1, xs));
-  HIPCHK(E, ln_fwd(E, DT_F32, c.xo32, nullptr, 1, ln_close, c.out32, R, d, s));
+  GemmArgs o = gemm_args(c.a16, R, d, d, c.xm32);
+  o.a_split = xs; o.bias = Bk.o.b; o.resid = c.x32;
+  HIPCHK(E, gemm(E, EPI_RESID32, o, Bk.o.fw(), s));
+  ln = ln_args(c.xm32, Bk.ln2, c.h16, R, d);
+  ln.split = xs;
+  HIPCHK(E, ln_fwd(E, E->dt, ln, s));
+  GemmArgs fc = gemm_args(c.h16, R, 4 * d, d, c.g16);
+  fc.a_split = xs; fc.bias = Bk.fc.b;
+  if (int rc = mlp_up(E, fc, Bk.fc.fw(), st.keep ? c.u16 : nullptr, c.act32, s)) return rc;
+  GemmArgs pr = gemm_args(c.g16, R, d, 4 * d, c.xo32);
+  pr.a_split = xs; pr.bias = Bk.pr.b; pr.resid = c.xm32;
+  HIPCHK(E, gemm(E, EPI_RESID32, pr, Bk.pr.fw(), s));
+  HIPCHK(E, ln_fwd(E, DT_F32, ln_args(c.xo32, lr.ln_close, c.out32, R, d), s));
   return 0;
 }
 // Backward of last_block_fwd from c.dout32: the closing LayerNorm, MLP, ln_2 and out-proj on the compact rows, the attention backward,
 // then the full-width QKV^T GEMM and ln_1 (keys / values of every token).  st.dx32 is zero on entry.  A single-operand tower whose
 // forward ran q_rows queries takes the single-query attention backward on the compact rows; every other one scatters the compact dO
 // into a zeroed dO16 and runs the attention backward at full width.
-int last_block_bwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const int32_t* rows, int q_rows, const LNp& ln_close, hipStream_t s) {
+int last_block_bwd(Engine* E, const TowerW& W, TowerState& st, Compact& c, const LastRows& lr, hipStream_t s) {
   // (T: the full-width rows that carry a gradient, TowerState::Lg, compact in the gradient buffers)
   const int l = st.layers - 1, T = st.N * st.Lg, R = st.seqs(), d = st.d, xs = st.xs;
-  const int ms = st.Lg != st.L ? st.Lg : 0, mp = ms ? st.L : 0;
   const size_t X = xs ? 2 : 1;
   const Block& Bk = W.blocks[l];
-  const bool cls = q_rows > 0 && !xs;
-  if (ms && (cls || !rows)) return fail(E, MVLPT_ERR_STATE, "last_block_bwd: a gradient length needs the row table of a text tower");
-  HIPCHK(E, ln_bwd(E, c.dout32, DT_F32, c.xo32, nullptr, 1, ln_close, nullptr, c.dx32, c.dx16, R, d, s, -1, xs));
-  if (int rc = mlp_up_bwd(E, c.dx16, Bk.pr.bw(), R, d, xs, c.u16, c.du16, 0, c.act32, s)) return rc;
-  HIPCHK(E, gemm(E, EPI_STORE32, c.du16, Bk.fc.bw(), R, d, 4 * d, nullptr, nullptr, nullptr, c.dh32, nullptr, s, -1, xs));
-  HIPCHK(E, ln_bwd(E, c.dh32, DT_F32, c.xm32, nullptr, 1, Bk.ln2, c.dx32, c.dx32, c.dx16, R, d, s, -1, xs));
-  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, c.dx16, Bk.o.bw(), R, d, d, nullptr, nullptr, nullptr, c.dO16, nullptr, s, -1, xs));
+  const bool cls = lr.q_rows > 0 && !xs;
+  if (st.saved_rows().seq && (cls || !lr.rows)) return fail(E, MVLPT_ERR_STATE, "last_block_bwd: a gradient length needs the row table of a text tower");
+  LnBwdArgs ln = ln_bwd_args(c.dout32, c.xo32, lr.ln_close, c.dx32, R, d);
+  ln.out16 = c.dx16; ln.split = xs;
+  HIPCHK(E, ln_bwd(E, ln, s));
+  GemmArgs up = gemm_args(c.dx16, R, 4 * d, d, c.du16);
+  up.a_split = xs; up.aux = c.u16;
+  if (int rc = mlp_up_bwd(E, up, Bk.pr.bw(), c.act32, s)) return rc;
+  GemmArgs fc = gemm_args(c.du16, R, d, 4 * d, c.dh32);
+  fc.a_split = xs;
+  HIPCHK(E, gemm(E, EPI_STORE32, fc, Bk.fc.bw(), s));
+  ln = ln_bwd_args(c.dh32, c.xm32, Bk.ln2, c.dx32, R, d);
+  ln.resid = c.dx32; ln.out16 = c.dx16; ln.split = xs;
+  HIPCHK(E, ln_bwd(E, ln, s));
+  GemmArgs o = gemm_args(c.dx16, R, d, d, c.dO16);
+  o.a_split = xs;
+  HIPCHK(E, gemm(E, xs ? EPI_STORE_SPLIT : EPI_STORE16, o, Bk.o.bw(), s));
   { ProfScope ps(E, s, PC_GLUE, 0, (cls ? 0.0 : (double)T * d * 2.0 * X) + (double)R * d * 8.0);
     if (!cls) {
       HIPCHK(E, launch_zero(st.dO16, (size_t)T * d * 2 * X, s));      // (split: dO is a hi|lo pair)
-      HIPCHK(E, move_rows(c.dO16, st.dO16, rows, R, st.L, (size_t)d * 2 * X, 1, s, st.Lg));
+      HIPCHK(E, move_rows(st, c.dO16, st.dO16, lr.rows, R, (size_t)d * 2 * X, 1, s));
     }
-    HIPCHK(E, move_rows(c.dx32, st.dx32, rows, R, st.L, (size_t)d * 4, 1, s, st.Lg)); }     // residual path: d(block input) of the compact rows
+    HIPCHK(E, move_rows(st, c.dx32, st.dx32, lr.rows, R, (size_t)d * 4, 1, s)); }     // residual path: d(block input) of the compact rows
   if (int rc = attn_bwd(E, st, l, cls ? &c : nullptr, s)) return rc;
-  HIPCHK(E, gemm(E, EPI_STORE32, st.dqkv16, Bk.qkv.bw(), T, d, 3 * d, nullptr, nullptr, nullptr, st.dh32, nullptr, s, -1, xs));
-  HIPCHK(E, ln_bwd(E, st.dh32, DT_F32, st.x[2 * l], nullptr, 1, Bk.ln1, st.dx32, st.dx32, st.dx16, T, d, s, -1, xs, ms, mp));
+  GemmArgs q = gemm_args(st.dqkv16, T, d, 3 * d, st.dh32);
+  q.a_split = xs;
+  HIPCHK(E, gemm(E, EPI_STORE32, q, Bk.qkv.bw(), s));
+  ln = ln_bwd_args(st.dh32, st.x[2 * l], Bk.ln1, st.dx32, T, d);
+  ln.resid = st.dx32; ln.out16 = st.dx16; ln.split = xs; ln.x_rows = st.saved_rows();
+  HIPCHK(E, ln_bwd(E, ln, s));
   return 0;
 }
 
@@ -1087,9 +1139,9 @@ int prepare_resnet(Engine* E, hipStream_t s) {
   return 0;
 }
 
-hipError_t rn_conv(const ConvW& c, const void* x, const void* resid, void* y, int B, int H, int W, int stride, int relu, hipStream_t s) {
-  ConvArgs a{x, c.w, c.bn.scale, c.bn.shift, resid, y, B, H, W, c.cin_pad, c.cout, c.k, stride, relu};
-  return launch_conv2d(a, s);
+// conv + BatchNorm + ReLU of one ConvW at stride 1, no residual: what most of the tower's convolutions are
+ConvArgs conv_args(const ConvW& c, const void* x, void* y, int B, int H, int W) {
+  return ConvArgs{x, c.w, c.bn.scale, c.bn.shift, nullptr, y, B, H, W, c.cin_pad, c.cout, c.k, 1, 1};
 }
 
 int resnet_fwd(Engine* E, const void* image, int image_dtype, int B, float* feat_out, hipStream_t s) {
@@ -1114,39 +1166,51 @@ int resnet_fwd(Engine* E, const void* image, int image_dtype, int B, float* feat
   { ProfScope ps(E, s, PC_GLUE, 0, (double)B * res * res * (3.0 * 4.0 + 16.0));
     HIPCHK(E, launch_nchw_to_nhwc8(image, image_dtype, img8, B, res, s)); }
   int H = res / 2;      // the stem: conv3x3 stride 2, conv3x3, conv3x3 (each + BN + ReLU), AvgPool2d(2)
-  HIPCHK(E, rn_conv(R.stem[0], img8, nullptr, a, B, res, res, 2, 1, s));
-  HIPCHK(E, rn_conv(R.stem[1], a, nullptr, b, B, H, H, 1, 1, s));
-  HIPCHK(E, rn_conv(R.stem[2], b, nullptr, a, B, H, H, 1, 1, s));
+  ConvArgs stem0 = conv_args(R.stem[0], img8, a, B, res, res);
+  stem0.stride = 2;
+  HIPCHK(E, launch_conv2d(stem0, s));
+  HIPCHK(E, launch_conv2d(conv_args(R.stem[1], a, b, B, H, H), s));
+  HIPCHK(E, launch_conv2d(conv_args(R.stem[2], b, a, B, H, H), s));
   HIPCHK(E, launch_avgpool2x2(a, x, B, H, H, w, s));
   H /= 2;
   for (int st = 0; st < 4; ++st)
     for (const RNBlock& K : R.stage[st]) {
       // Bottleneck (clip/model.py:10-55): every strided convolution is an average pool in front of a stride-1 convolution
       const int Ho = H / K.stride;
-      HIPCHK(E, rn_conv(K.c1, x, nullptr, a, B, H, H, 1, 1, s));
-      HIPCHK(E, rn_conv(K.c2, a, nullptr, b, B, H, H, 1, 1, s));
+      HIPCHK(E, launch_conv2d(conv_args(K.c1, x, a, B, H, H), s));
+      HIPCHK(E, launch_conv2d(conv_args(K.c2, a, b, B, H, H), s));
       const void* main_in = b;
       if (K.stride > 1) { HIPCHK(E, launch_avgpool2x2(b, a, B, H, H, K.c2.cout, s)); main_in = a; }
       const void* identity = x;
       if (K.has_ds) {
         const void* ds_in = x;
         if (K.stride > 1) { HIPCHK(E, launch_avgpool2x2(x, c, B, H, H, K.ds.cin, s)); ds_in = c; }
-        HIPCHK(E, rn_conv(K.ds, ds_in, nullptr, d, B, Ho, Ho, 1, 0, s));
+        ConvArgs ds = conv_args(K.ds, ds_in, d, B, Ho, Ho);
+        ds.relu = 0;
+        HIPCHK(E, launch_conv2d(ds, s));
         identity = d;
       }
-      HIPCHK(E, rn_conv(K.c3, main_in, identity, b == main_in ? a : b, B, Ho, Ho, 1, 1, s));
       void* out = b == main_in ? a : b;
+      ConvArgs c3 = conv_args(K.c3, main_in, out, B, Ho, Ho);
+      c3.resid = identity;
+      HIPCHK(E, launch_conv2d(c3, s));
       if (out == a) { a = x; x = out; } else { b = x; x = out; }
       H = Ho;
     }
   // AttentionPool2d (clip/model.py:58-91): only token 0's output is returned, so only its query is projected
   { ProfScope ps(E, s, PC_GLUE, 0, (double)B * T * Ech * 4.0);
     HIPCHK(E, launch_attnpool_tokens(x, R.pos, tok, B, HW, Ech, s)); }
-  HIPCHK(E, gemm(E, EPI_STORE16, tok, WRef{R.qw, Ech, 0}, B, Ech, Ech, R.qb, nullptr, nullptr, q16, nullptr, s, DT_F16, 0, nullptr, T * Ech));
-  HIPCHK(E, gemm(E, EPI_STORE16, tok, WRef{R.kvw, Ech, 0}, B * T, 2 * Ech, Ech, R.kvb, nullptr, nullptr, kv, nullptr, s, DT_F16));
+  GemmArgs gq = gemm_args(tok, B, Ech, Ech, q16);      // (row b: token 0 of image b)
+  gq.bias = R.qb; gq.lda = T * Ech;
+  HIPCHK(E, gemm(E, EPI_STORE16, gq, WRef{R.qw, Ech, 0}, s, DT_F16));
+  GemmArgs gkv = gemm_args(tok, B * T, 2 * Ech, Ech, kv);
+  gkv.bias = R.kvb;
+  HIPCHK(E, gemm(E, EPI_STORE16, gkv, WRef{R.kvw, Ech, 0}, s, DT_F16));
   { ProfScope ps(E, s, PC_ATTN_FWD, 4.0 * T * 64.0 * B * (Ech / 64), (double)B * T * 2 * Ech * 2.0);
     HIPCHK(E, launch_attnpool_query(q16, kv, o16, B, T, Ech, s)); }
-  HIPCHK(E, gemm(E, EPI_STORE32, o16, WRef{R.cw, Ech, 0}, B, e, Ech, R.cb, nullptr, nullptr, feat_out, nullptr, s, DT_F16));
+  GemmArgs gc = gemm_args(o16, B, e, Ech, feat_out);
+  gc.bias = R.cb;
+  HIPCHK(E, gemm(E, EPI_STORE32, gc, WRef{R.cw, Ech, 0}, s, DT_F16));
   E->vrun.phase = Phase::Done;
   return 0;
 }
@@ -1519,7 +1583,9 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
         patches = bp.take_bytes(npatch * E->Kp * 2);
         pe = bp.take<float>(npatch * dv);
         carve_compact(bp, R.c, B, dv, X, gelu);
-        carve_tower(bp, E->vis, st, B, Lv, save, false, exact, split_kind(E), gelu);
+        TowerShape t;
+        t.N = B; t.L = Lv; t.save = save; t.exact = exact; t.xs = split_kind(E); t.gelu = gelu;
+        carve_tower(bp, E->vis, st, t);
       })) return rc;
   R.B = B; R.n_vpt = n_vpt; R.n_deep = n_deep; R.save = st.keep = save; R.vpt_deep = vpt_deep;
   st.fold = E->fold_mode >= 1 && (size_t)B * Lv >= (size_t)E->fold_min_rows && dv >= 256;
@@ -1534,7 +1600,7 @@ int mvlpt_image_fwd_begin(void* h, const void* image, int image_dtype, const flo
     HIPCHK(E, launch_patchify(E->dt, image, image_dtype, patches, B, A.image_resolution, A.patch_size, E->Kp, s)); }
   if (E->dbg_ck_on) { E->dbg_ck_n = 0; if (E->dbg_ck) (void)hipMemsetAsync(E->dbg_ck, 0, DBG_CK_MAX * sizeof(unsigned long long), s); }
   dbg_ck(E, patches, (size_t)npatch * E->Kp * 2, s);
-  HIPCHK(E, gemm(E, EPI_STORE32, patches, WRef{E->conv_w, 0, 0}, (int)npatch, dv, E->Kp, nullptr, nullptr, nullptr, pe, nullptr, s));
+  HIPCHK(E, gemm(E, EPI_STORE32, gemm_args(patches, (int)npatch, dv, E->Kp, pe), WRef{E->conv_w, 0, 0}, s));
   dbg_ck(E, pe, (size_t)npatch * dv * 4, s);
   // Packed residual stream (block_fwd_packed): fp16 tower, no prompts, nothing saved, every LayerNorm folded.  assemble_tokens
   // writes the rows in the packed format together with the row statistics of ln_1 of block 0.
@@ -1583,10 +1649,13 @@ int mvlpt_image_fwd_resume(void* h, float* feat_out, mvlpt_stream_t stream) {
   if (rest < 0) return rest;
   R.last_compact = rest == 1;
   if (rest == 1) {      // the last block, CLS rows only (mvlpt_image_bwd: only the CLS query carries a gradient into its attention)
-    if (int rc = last_block_fwd(E, E->vis, st, R.c, nullptr, 1, R.packed, R.ln1_ready, E->ln_post, true, s)) return rc;
-  } else
-  // ln_post on the CLS row, then @ proj   (trainers/mvlpt.py:88-91)
-  HIPCHK(E, ln_fwd(E, DT_F32, st.x[2 * E->vis.layers], nullptr, Lv, E->ln_post, R.c.out32, B, dv, s));
+    if (int rc = last_block_fwd(E, E->vis, st, R.c, LastRows{nullptr, 1, E->ln_post}, R.packed, R.ln1_ready, s)) return rc;
+  } else {
+    // ln_post on the CLS row, then @ proj   (trainers/mvlpt.py:88-91)
+    LnFwdArgs ln = ln_args(st.x[2 * E->vis.layers], E->ln_post, R.c.out32, B, dv);
+    ln.row_mul = Lv;
+    HIPCHK(E, ln_fwd(E, DT_F32, ln, s));
+  }
   { ProfScope ps(E, s, PC_HEAD, 2.0 * B * e * dv, 4.0 * ((double)B * dv + (double)e * dv + (double)B * e));
     HIPCHK(E, launch_sgemm_bt(R.c.out32, E->vproj_t, feat_out, B, e, dv, nullptr, s)); }
   R.phase = R.save ? Phase::Saved : Phase::Done;
@@ -1636,11 +1705,13 @@ int mvlpt_image_bwd(void* h, const float* dfeat, float* dvpt, float* dvpt_deep, 
     return 0;
   };
   if (R.last_compact) {      // last block, CLS rows only (see mvlpt_image_fwd_resume)
-    if (int rc = last_block_bwd(E, E->vis, st, R.c, nullptr, 1, E->ln_post, s)) return rc;
+    if (int rc = last_block_bwd(E, E->vis, st, R.c, LastRows{nullptr, 1, E->ln_post}, s)) return rc;
     if (int rc = reduce_deep(l_top)) return rc;
     --l_top;
   } else {
-    HIPCHK(E, ln_bwd(E, R.c.dout32, DT_F32, st.x[2 * st.layers], nullptr, Lv, E->ln_post, nullptr, st.dx32, nullptr, B, dv, s));
+    LnBwdArgs ln = ln_bwd_args(R.c.dout32, st.x[2 * st.layers], E->ln_post, st.dx32, B, dv);
+    ln.row_mul = Lv;
+    HIPCHK(E, ln_bwd(E, ln, s));
     { ProfScope ps(E, s, PC_GLUE, 0, (double)T * dv * 6.0);
       if (xs) HIPCHK(E, launch_cast_f32_split(E->dt, st.dx32, st.dx16, T, dv, nullptr, s, xs == 2));
       else HIPCHK(E, launch_cast_f32_to16(E->dt, st.dx32, st.dx16, T * dv, nullptr, s)); }
@@ -1680,31 +1751,52 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 }
 
 // ------------------------------------------------------------------------------------------------ text tower
+// One text forward, as its entry describes it once its own checks have passed (text_fwd_impl).
+// Plain: mvlpt_text_fwd (prefix / suffix / layout / eot [C, ...], ctx [n_ctx, d] or CSC [C, n_ctx, d]; G = 0, Cg = C).
+// Ranged: mvlpt_text_fwd_ranged, G groups over the [Cg, ...] class tables and ctx [G, n_ctx, d], C = S sequences described by
+// E->t_range_host.  Ids: mvlpt_text_encode_tokens, C sequences of token ids (E->t_ids_host); no class tables and no ctx.
+// Deep (mvlpt_text_fwd_deep): a plain tower whose context rows are replaced by ctx_deep [n_deep, n_ctx, d] in front of blocks 1 .. n_deep.
+struct TextJob {
+  TextKind kind = TextKind::Plain;
+  const float *prefix = nullptr, *suffix = nullptr; const int32_t *layout = nullptr, *eot = nullptr;      // the four class tables
+  const float* ctx = nullptr; int per_class = 0, n_ctx = 0;
+  const float* ctx_deep = nullptr; int n_deep = 0;
+  int G = 0, Cg = 0, C = 0, L = 0;
+  int save = 0;
+  float* feat_out = nullptr;
+};
 // What a text forward over C sequences of length L carves from txt_ws: text_fwd_impl carves with it and mvlpt_text_workspace_bytes
 // counts with it.  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of the ctx_pos table; range_ints / ids_ints: the range
 // table of a ranged forward and the id table of mvlpt_text_encode_tokens (0: none, a null pointer).  A saving tower is carved under the
 // engine's activation-checkpointing setting (mvlpt_set_text_act_ckpt).
-// Lg: the gradient length of a saving tower (text_grad_len below; L: every position).
-static void text_layout(Bump& bp, const Engine* E, TextRun& R, int C, int L, bool save, bool exact, size_t ctx_rows, size_t range_ints,
-                        size_t ids_ints, int Lg, int P = 0) {
+// Lg: the gradient length of a saving tower (text_grad_len below; L: every position).  P: the shared prefix (text_prefix_len).
+struct TextShape {
+  int C = 0, L = 0;
+  bool save = false, exact = false;
+  size_t ctx_rows = 0, range_ints = 0, ids_ints = 0;
+  int Lg = 0, P = 0;
+};
+static void text_layout(Bump& bp, const Engine* E, TextRun& R, const TextShape& t) {
   const bool gelu = E->act == ACT_GELU;
-  carve_compact(bp, R.c, C, E->arch.text_width, exact ? 2 : 1, gelu);
-  R.eot_rows = bp.take<int32_t>(C);
-  R.ctx_pos = bp.take<int32_t>(ctx_rows);
-  R.range = range_ints ? bp.take<int32_t>(range_ints) : nullptr;
-  R.ids = ids_ints ? bp.take<int32_t>(ids_ints) : nullptr;
-  // (a shared prefix: C + 1 slots of L - P rows, TowerState::P)
-  if (P > 0) carve_tower(bp, E->txt, R.st, C + 1, L - P, save, true, exact, split_kind(E), gelu, E->text_act_ckpt, Lg - P, P);
-  else carve_tower(bp, E->txt, R.st, C, L, save, true, exact, split_kind(E), gelu, E->text_act_ckpt, Lg);
+  carve_compact(bp, R.c, t.C, E->arch.text_width, t.exact ? 2 : 1, gelu);
+  R.eot_rows = bp.take<int32_t>(t.C);
+  R.ctx_pos = bp.take<int32_t>(t.ctx_rows);
+  R.range = t.range_ints ? bp.take<int32_t>(t.range_ints) : nullptr;
+  R.ids = t.ids_ints ? bp.take<int32_t>(t.ids_ints) : nullptr;
+  TowerShape w;
+  w.N = t.C; w.L = t.L; w.Lg = t.Lg; w.P = t.P;
+  w.save = t.save; w.causal = true; w.exact = t.exact; w.xs = split_kind(E); w.gelu = gelu; w.segments = E->text_act_ckpt;
+  if (t.P > 0) { w.N = t.C + 1; w.L = t.L - t.P; w.Lg = t.Lg - t.P; }      // (a shared prefix: C + 1 slots of L - P rows, TowerState::P)
+  carve_tower(bp, E->txt, R.st, w);
 }
 // The shared prefix a plain forward runs under (mvlpt_set_text_shared_prefix): the setting, lowered until the prefix fits a gradient
 // slot (P <= Lg - P) and a slot keeps MVLPT_TEXT_MIN_L rows (Lg - P >= 3); 0 on every route that does not take one: class-specific or
 // deep contexts, the ranged and token-id towers, activation checkpointing, sequences the short kernels do not take.  Split and single
 // operands alike (attention32.hip / attention.hip).  `setting`: what the forward took out of Engine::text_shared_prefix.
-static int text_prefix_len(const Engine* E, int setting, TextKind kind, int ctx_per_class, int n_ctx, int n_deep, int L, int Lg) {
-  if (setting <= 0 || kind != TextKind::Plain || ctx_per_class || n_ctx <= 0 || n_deep > 0 || L > 80 || E->text_act_ckpt != 1)
+static int text_prefix_len(const Engine* E, int setting, const TextJob& j, int Lg) {
+  if (setting <= 0 || j.kind != TextKind::Plain || j.per_class || j.n_ctx <= 0 || j.n_deep > 0 || j.L > 80 || E->text_act_ckpt != 1)
     return 0;
-  int P = std::min(setting, L - 1);
+  int P = std::min(setting, j.L - 1);
   P = std::min(P, std::min(Lg / 2, Lg - 3));
   return P > 0 ? P : 0;
 }
@@ -1750,27 +1842,22 @@ static int text_segment_fwd(Engine* E, int first, int end, bool last, bool keep,
   return 0;
 }
 
-// The text tower over C sequences.  Plain: mvlpt_text_fwd (prefix / suffix / layout / eot [C, ...], ctx [n_ctx, d] or CSC [C, n_ctx, d];
-// G = 0, Cg = C).  Ranged: mvlpt_text_fwd_ranged, G groups over the [Cg, ...] class tables and ctx [G, n_ctx, d], C = S
-// sequences described by E->t_range_host.  Ids: mvlpt_text_encode_tokens, C sequences of token ids (E->t_ids_host); no prefix /
-// suffix / ctx / layout / eot tables.
-// Deep (mvlpt_text_fwd_deep): a plain tower whose context rows are replaced by ctx_deep [n_deep, n_ctx, d] in front of blocks 1 .. n_deep.
-static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
-                         const int32_t* layout, const int32_t* eot, int G, int Cg, int C, int L, float* feat_out, int save_for_bwd,
-                         mvlpt_stream_t stream, const float* ctx_deep = nullptr, int n_deep = 0) {
-  const bool ranged = kind == TextKind::Ranged, ids = kind == TextKind::Ids;
+// The text tower over the j.C sequences of one TextJob
+static int text_fwd_impl(Engine* E, const TextJob& j, mvlpt_stream_t stream) {
+  const bool ranged = j.kind == TextKind::Ranged, ids = j.kind == TextKind::Ids;
+  const int C = j.C, L = j.L, n_ctx = j.n_ctx, n_deep = j.n_deep, G = j.G, Cg = j.Cg;
   // one-shot, taken before any check can refuse the call: the caller's proof holds for the tables of THIS forward only, whichever
   // entry it came through and whether or not it runs
   const int prefix_setting = E->text_shared_prefix;
   E->text_shared_prefix = 0;
   if (int rc = mvlpt_frozen_ready(E)) return rc;
-  if ((n_ctx > 0) != (ctx != nullptr) || n_ctx < 0 || n_ctx > L - 2) return fail(E, MVLPT_ERR_ARG, "text_fwd: ctx pointer and n_ctx disagree");
+  if ((n_ctx > 0) != (j.ctx != nullptr) || n_ctx < 0 || n_ctx > L - 2) return fail(E, MVLPT_ERR_ARG, "text_fwd: ctx pointer and n_ctx disagree");
   const MvlptArch& A = E->arch;
   if (L > A.context_length) return fail(E, MVLPT_ERR_ARG, "text_fwd: L exceeds context_length");
   if (L > attn_max_len()) return fail(E, MVLPT_ERR_UNSUPPORTED, "text_fwd: L > 256");
   hipStream_t s = (hipStream_t)stream;
   const int dtw = A.text_width, e = A.embed_dim;
-  const bool save = save_for_bwd != 0;
+  const bool save = j.save != 0;
   // The text tower runs with split operands in every mode but MVLPT_PREC_FAST, also when nothing is saved for a backward:
   // n_ctx == 0: the features are constants of the run (computed once and cached by the caller) that enter every
   // image-side gradient through the logits; inference (model_inference, trainers/mvlpt.py:986-987): they are computed once
@@ -1778,26 +1865,26 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
   // features, which put the inference logits of 5 of the 18 reference fixtures outside 1e-3 (profiles/r04_inference_parity.txt)
   const bool exact = text_exact(E);
   // ctx_pos is per class for the ranged tower, which may run fewer sequences than there are classes
-  const size_t ctx_rows = (size_t)(ranged && Cg > C ? Cg : C) * (n_ctx > 0 ? n_ctx : 1);
-  const size_t range_ints = ranged ? E->t_range_host.size() : 0;
-  const size_t ids_ints = ids ? E->t_ids_host.size() : 0;
+  TextShape shape;
+  shape.C = C; shape.L = L; shape.save = save; shape.exact = exact;
+  shape.ctx_rows = (size_t)(ranged && Cg > C ? Cg : C) * (n_ctx > 0 ? n_ctx : 1);
+  const size_t range_ints = shape.range_ints = ranged ? E->t_range_host.size() : 0;
+  const size_t ids_ints = shape.ids_ints = ids ? E->t_ids_host.size() : 0;
   // a gradient that stops in front of an EOT row would be wrong (never out of bounds): refused before anything is launched
-  const int Lg = save ? text_grad_len(E, L) : L;
+  const int Lg = shape.Lg = save ? text_grad_len(E, L) : L;
   if (Lg < L && Lg <= E->text_max_eot)
     return fail(E, MVLPT_ERR_ARG, "text_fwd: the gradient length (mvlpt_set_text_grad_len) does not reach the largest EOT position");
-  const int P = text_prefix_len(E, prefix_setting, kind, ctx_per_class, n_ctx, n_deep, L, Lg);
+  const int P = shape.P = text_prefix_len(E, prefix_setting, j, Lg);
   TextRun& R = E->trun = TextRun();      // opened: from here on the workspace no longer holds the last forward
   TowerState& st = R.st;
-  if (int rc = carve_ws(E, E->txt_ws, "text_fwd", kTextSlack, [&](Bump& bp) {
-        text_layout(bp, E, R, C, L, save, exact, ctx_rows, range_ints, ids_ints, Lg, P);
-      })) return rc;
+  if (int rc = carve_ws(E, E->txt_ws, "text_fwd", kTextSlack, [&](Bump& bp) { text_layout(bp, E, R, shape); })) return rc;
   if (P > 0) {      // the sum over more than 512 classes enters slot 0 scaled down by a power of two (TowerState::part_mul)
     int sh = 0;
     while (((int64_t)512 << sh) < C) ++sh;
     st.part_mul = std::ldexp(1.0f, -sh);
   }
-  R.C = C; R.L = L; R.n_ctx = n_ctx; R.per_class = ctx_per_class; R.kind = kind; R.groups = G;
-  R.n_deep = n_deep; R.ctx_deep = n_deep > 0 ? ctx_deep : nullptr;
+  R.C = C; R.L = L; R.n_ctx = n_ctx; R.per_class = j.per_class; R.kind = j.kind; R.groups = G;
+  R.n_deep = n_deep; R.ctx_deep = n_deep > 0 ? j.ctx_deep : nullptr;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
   if (ids) {
@@ -1810,13 +1897,13 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
     if (ranged) {
       const int32_t *seq_cls = R.range + 2 * G + 1, *seq_grp = seq_cls + C;
       HIPCHK(E, hipMemcpyAsync(R.range, E->t_range_host.data(), range_ints * 4, hipMemcpyHostToDevice, s));
-      HIPCHK(E, launch_assemble_prompts_ranged(prefix, suffix, ctx, n_ctx, layout, E->tpos, st.x[0], seq_cls, seq_grp, C, L, dtw, s));
-      HIPCHK(E, launch_eot_rows_ranged(eot, R.eot_rows, seq_cls, C, L, s));
-      if (save) HIPCHK(E, launch_build_ctx_pos(layout, R.ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
+      HIPCHK(E, launch_assemble_prompts_ranged(j.prefix, j.suffix, j.ctx, n_ctx, j.layout, E->tpos, st.x[0], seq_cls, seq_grp, C, L, dtw, s));
+      HIPCHK(E, launch_eot_rows_ranged(j.eot, R.eot_rows, seq_cls, C, L, s));
+      if (save) HIPCHK(E, launch_build_ctx_pos(j.layout, R.ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
     } else {
-      HIPCHK(E, launch_assemble_prompts(prefix, suffix, ctx, ctx_per_class, n_ctx, layout, E->tpos, st.x[0], C, L, dtw, s, P));
-      HIPCHK(E, launch_eot_rows(eot, R.eot_rows, C, L, s, P));
-      if ((save || n_deep > 0) && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(layout, R.ctx_pos, C, L, n_ctx, s, P, st.Lg));
+      HIPCHK(E, launch_assemble_prompts(j.prefix, j.suffix, j.ctx, j.per_class, n_ctx, j.layout, E->tpos, st.x[0], C, L, dtw, s, P));
+      HIPCHK(E, launch_eot_rows(j.eot, R.eot_rows, C, L, s, P));
+      if ((save || n_deep > 0) && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(j.layout, R.ctx_pos, C, L, n_ctx, s, P, st.Lg));
     } }
   // Checkpointed segments (every one but the last, st.seg) run as a tower that saves nothing; their closing block writes the next
   // segment's boundary buffer.  No ln_1 is folded across a segment boundary, so mvlpt_text_bwd can repeat a segment launch for launch.
@@ -1828,9 +1915,9 @@ static int text_fwd_impl(Engine* E, TextKind kind, const float* prefix, const fl
   // the last block on the C gathered EOT rows
   st.keep = save;
   if (int rc = text_deep_overwrite(E, E->txt.layers - 1, s)) return rc;
-  if (int rc = last_block_fwd(E, E->txt, st, R.c, R.eot_rows, 0, false, ln1_ready, E->ln_final, false, s)) return rc;
+  if (int rc = last_block_fwd(E, E->txt, st, R.c, LastRows{R.eot_rows, 0, E->ln_final}, false, ln1_ready, s)) return rc;
   { ProfScope ps(E, s, PC_HEAD, 2.0 * C * e * dtw, 4.0 * ((double)C * dtw + (double)e * dtw + (double)C * e));
-    HIPCHK(E, launch_sgemm_bt(R.c.out32, E->tproj_t, feat_out, C, e, dtw, nullptr, s)); }
+    HIPCHK(E, launch_sgemm_bt(R.c.out32, E->tproj_t, j.feat_out, C, e, dtw, nullptr, s)); }
   R.phase = save ? Phase::Saved : Phase::Done;
   return 0;
 }
@@ -1841,7 +1928,11 @@ int mvlpt_text_fwd(void* h, const float* prefix, const float* suffix, const floa
   Engine* E = (Engine*)h;
   if (!E || !prefix || !suffix || !layout || !eot || !feat_out || C <= 0 || L <= 0)
     return fail(E, MVLPT_ERR_ARG, "text_fwd: null/invalid argument");
-  return text_fwd_impl(E, TextKind::Plain, prefix, suffix, ctx, ctx_per_class, n_ctx, layout, eot, 0, C, C, L, feat_out, save_for_bwd, stream);
+  TextJob j;
+  j.prefix = prefix; j.suffix = suffix; j.layout = layout; j.eot = eot;
+  j.ctx = ctx; j.per_class = ctx_per_class; j.n_ctx = n_ctx;
+  j.Cg = j.C = C; j.L = L; j.save = save_for_bwd; j.feat_out = feat_out;
+  return text_fwd_impl(E, j, stream);
 }
 
 // Deep language prompting: mvlpt_text_fwd with a generic context whose rows are replaced in front of blocks 1 .. n_deep
@@ -1857,8 +1948,11 @@ int mvlpt_text_fwd_deep(void* h, const float* prefix, const float* suffix, const
     if (n_deep > E->txt.layers - 1)
       return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: n_deep exceeds text_layers - 1 (block 0 reads the embedding-level context)");
   }
-  return text_fwd_impl(E, TextKind::Plain, prefix, suffix, ctx, 0, n_ctx, layout, eot, 0, C, C, L, feat_out, save_for_bwd, stream,
-                       ctx_deep, n_deep);
+  TextJob j;
+  j.prefix = prefix; j.suffix = suffix; j.layout = layout; j.eot = eot;
+  j.ctx = ctx; j.n_ctx = n_ctx; j.ctx_deep = ctx_deep; j.n_deep = n_deep;
+  j.Cg = j.C = C; j.L = L; j.save = save_for_bwd; j.feat_out = feat_out;
+  return text_fwd_impl(E, j, stream);
 }
 
 // The MVLPT trainer's CoCoOp branch under the per-task mask (trainers/mvlpt.py:556-581): image g runs only the classes of its own task.
@@ -1875,7 +1969,12 @@ int mvlpt_text_fwd_ranged(void* h, const float* prefix, const float* suffix, con
   if (S < 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: a class range is not inside [0, C] or the ranges hold too many sequences");
   if (S == 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: every range is empty");
   if (S > (int64_t)INT32_MAX / L) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: too many sequences");
-  return text_fwd_impl(E, TextKind::Ranged, prefix, suffix, ctx, 0, n_ctx, layout, eot, G, C, (int)S, L, feat_out, save_for_bwd, stream);
+  TextJob j;
+  j.kind = TextKind::Ranged;
+  j.prefix = prefix; j.suffix = suffix; j.layout = layout; j.eot = eot;
+  j.ctx = ctx; j.n_ctx = n_ctx;
+  j.G = G; j.Cg = C; j.C = (int)S; j.L = L; j.save = save_for_bwd; j.feat_out = feat_out;
+  return text_fwd_impl(E, j, stream);
 }
 
 // CLIP.encode_text (clip/model.py:343-356) over S sequences of token ids, trimmed to their first L positions
@@ -1904,7 +2003,10 @@ int mvlpt_text_encode_tokens(void* h, const int32_t* ids, int ld, int S, int L, 
     }
     rows[q] = q * L + arg;
   }
-  return text_fwd_impl(E, TextKind::Ids, nullptr, nullptr, nullptr, 0, 0, nullptr, nullptr, 0, S, S, L, feat_out, 0, stream);
+  TextJob j;
+  j.kind = TextKind::Ids;
+  j.Cg = j.C = S; j.L = L; j.feat_out = feat_out;
+  return text_fwd_impl(E, j, stream);
 }
 
 int mvlpt_text_ensemble(const float* feats, int T, int C, int e, float* out, mvlpt_stream_t stream) {
@@ -1958,9 +2060,10 @@ int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, in
   // the ctx_pos table is sized for the largest n_ctx a forward accepts (L - 2): at most C_total * L * 4 bytes over the exact figure
   // a counting pass into scratch state: a saved forward whose backward has not run keeps its own
   TextRun scratch;
-  *out = (int64_t)(carve_count([&](Bump& bp) {
-    text_layout(bp, E, scratch, C_total, L, save_for_bwd != 0, text_exact(E), (size_t)C_total * (L - 2), 0, 0, L);
-  }) + kTextSlack);
+  TextShape shape;
+  shape.C = C_total; shape.L = shape.Lg = L; shape.save = save_for_bwd != 0; shape.exact = text_exact(E);
+  shape.ctx_rows = (size_t)C_total * (L - 2);
+  *out = (int64_t)(carve_count([&](Bump& bp) { text_layout(bp, E, scratch, shape); }) + kTextSlack);
   return 0;
 }
 
@@ -1998,7 +2101,7 @@ static int text_bwd_impl(Engine* E, const float* dfeat, float* dctx, float* dctx
                                           st.scale_dev, s));
     return 0;
   };
-  if (int rc = last_block_bwd(E, E->txt, st, R.c, R.eot_rows, 0, E->ln_final, s)) return rc;      // the last block on the C compact EOT rows
+  if (int rc = last_block_bwd(E, E->txt, st, R.c, LastRows{R.eot_rows, 0, E->ln_final}, s)) return rc;      // the last block on the C compact EOT rows
   if (int rc = gather_deep(st.layers - 1)) return rc;
   for (int l = st.layers - 2; l >= st.seg[k - 1]; --l) {
     if (int rc = block_bwd(E, E->txt, st, l, s)) return rc;
@@ -2313,33 +2416,27 @@ static int op_ln_bwd(int dtype, const void* dy, int dy_dtype, const float* x, in
   OPCHK(launch_ln_bwd(dtype, a, (hipStream_t)stream));
   return 0;
 }
-// pair-product attention; lo8: the pairs are mixed (hi + e5m2 residual byte).  Debug builds: timeline of one workgroup ->
+// pair-product attention (a.fmt 1: 16-bit pairs, 2: mixed pairs, hi + e5m2 residual byte).  Debug builds: timeline of one workgroup ->
 // $MVLPT_ATTN_TRACE_FILE (8 waves x 256 int64 records)
-static int op_attn32_fwd(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int causal, int q_rows, int lo8,
-                         mvlpt_stream_t stream) {
-  Attn32Args a{qkv, out, lse, N, L, H, causal, q_rows};
-  a.out_lo8 = lo8;
+static int op_attn32_fwd(int dtype, AttnArgs a, mvlpt_stream_t stream) {
 #ifdef MVLPT_ATTN_TRACE
   TraceCapture tc("MVLPT_ATTN_TRACE_FILE", 8 * 256, (hipStream_t)stream);
   OPCHK(tc.err);
   a.trace = tc.ptr();
 #endif
-  OPCHK(launch_attn32_fwd(dtype, a, (hipStream_t)stream));
+  OPCHK(launch_attn_fwd(dtype, a, (hipStream_t)stream));
 #ifdef MVLPT_ATTN_TRACE
   OPCHK(tc.dump());
 #endif
   return 0;
 }
-static int op_attn32_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int N,
-                         int L, int H, int causal, int lo8, mvlpt_stream_t stream) {
-  Attn32BwdArgs a{qkv, out, dout, lse, delta, dqkv, N, L, H, causal};
-  a.lo8 = lo8;
+static int op_attn32_bwd(int dtype, AttnBwdArgs a, mvlpt_stream_t stream) {
 #ifdef MVLPT_ATTN_TRACE
   TraceCapture tc("MVLPT_ATTN_TRACE_FILE", 8 * 256, (hipStream_t)stream);
   OPCHK(tc.err);
   a.trace = tc.ptr();
 #endif
-  OPCHK(launch_attn32_bwd(dtype, a, (hipStream_t)stream));
+  OPCHK(launch_attn_bwd(dtype, a, (hipStream_t)stream));
 #ifdef MVLPT_ATTN_TRACE
   OPCHK(tc.dump());
 #endif
@@ -2356,11 +2453,15 @@ int mvlpt_op_layernorm_bwd_mixed(int dtype, const void* dy, const float* x, cons
 }
 int mvlpt_op_attention32_fwd_mixed(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int causal, int q_rows,
                                    mvlpt_stream_t stream) {
-  return op_attn32_fwd(dtype, qkv, out, lse, N, L, H, causal, q_rows, 1, stream);
+  AttnArgs a{qkv, out, lse, N, L, H, causal, q_rows};
+  a.fmt = 2;
+  return op_attn32_fwd(dtype, a, stream);
 }
 int mvlpt_op_attention32_bwd_mixed(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                                    void* dqkv, int N, int L, int H, int causal, mvlpt_stream_t stream) {
-  return op_attn32_bwd(dtype, qkv, out, dout, lse, delta, dqkv, N, L, H, causal, 1, stream);
+  AttnBwdArgs a{qkv, out, dout, lse, delta, dqkv, N, L, H, causal};
+  a.fmt = 2;
+  return op_attn32_bwd(dtype, a, stream);
 }
 int mvlpt_op_layernorm_fwd_split(int out_dtype, const float* x, const float* gamma, const float* beta, void* y, int rows, int d,
                                  mvlpt_stream_t stream) {
@@ -2373,11 +2474,15 @@ int mvlpt_op_layernorm_bwd_split(int dtype, const void* dy, const float* x, cons
 }
 int mvlpt_op_attention32_fwd(int dtype, const void* qkv, void* out, float* lse, int N, int L, int H, int causal, int q_rows,
                              mvlpt_stream_t stream) {
-  return op_attn32_fwd(dtype, qkv, out, lse, N, L, H, causal, q_rows, 0, stream);
+  AttnArgs a{qkv, out, lse, N, L, H, causal, q_rows};
+  a.fmt = 1;
+  return op_attn32_fwd(dtype, a, stream);
 }
 int mvlpt_op_attention32_bwd(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                              void* dqkv, int N, int L, int H, int causal, mvlpt_stream_t stream) {
-  return op_attn32_bwd(dtype, qkv, out, dout, lse, delta, dqkv, N, L, H, causal, 0, stream);
+  AttnBwdArgs a{qkv, out, dout, lse, delta, dqkv, N, L, H, causal};
+  a.fmt = 1;
+  return op_attn32_bwd(dtype, a, stream);
 }
 // ---- the text backward's launches under a gradient length (mvlpt_set_text_grad_len): saved operands at the pitch seq_pitch, read
 // through the row map r -> (r / grad_len) * seq_pitch + r % grad_len; everything else compact.  The launchers check the maps.
@@ -2386,7 +2491,7 @@ int mvlpt_op_gemm_gelubwd_rows(int dtype, int epi, const void* A, const void* Bt
   if (epi != EPI_GELUBWD && epi != EPI_GELUBWD_SPLIT) return fail(nullptr, MVLPT_ERR_ARG, "op_gemm_gelubwd_rows: a GELU-backward epilogue");
   GemmArgs g{A, Bt, M, N, K, nullptr, aux, nullptr, out, nullptr};
   g.a_split = a_split; g.lda = lda; g.ldo = ldo; g.ldb = ldb; g.w8_exp = w8_exp; g.out_lo8 = out_lo8;
-  g.aux_seq = grad_len; g.aux_pitch = seq_pitch;
+  g.aux_rows = RowMap{grad_len, seq_pitch};
   OPCHK(launch_gemm(dtype, epi, g, (hipStream_t)stream));
   return 0;
 }
@@ -2395,7 +2500,7 @@ int mvlpt_op_layernorm_bwd_rows(int dtype, const void* dy, int dy_dtype, const f
   if (!dy || !x || !gamma || !out32 || rows <= 0 || grad_len <= 0 || rows % grad_len)
     return fail(nullptr, MVLPT_ERR_ARG, "op_layernorm_bwd_rows: null/invalid argument");
   LnBwdArgs a{dy, dy_dtype, x, nullptr, 1, gamma, resid, out32, out16, rows, d};
-  a.split = split; a.x_seq = grad_len; a.x_pitch = seq_pitch;
+  a.split = split; a.x_rows = RowMap{grad_len, seq_pitch};
   OPCHK(launch_ln_bwd(dtype, a, (hipStream_t)stream));
   return 0;
 }
@@ -2403,24 +2508,18 @@ int mvlpt_op_layernorm_bwd_rows(int dtype, const void* dy, int dy_dtype, const f
 int mvlpt_op_attention_bwd_rows(int dtype, int pair, int lo8, const void* qkv, const void* out, const void* dout, const float* lse,
                                 float* delta, void* dqkv, int N, int grad_len, int seq_pitch, int H, mvlpt_stream_t stream) {
   if (!qkv || !out || !dout || !lse || !delta || !dqkv) return fail(nullptr, MVLPT_ERR_ARG, "op_attention_bwd_rows: null argument");
-  if (pair) {
-    Attn32BwdArgs a{qkv, out, dout, lse, delta, dqkv, N, grad_len, H, 1};
-    a.lo8 = lo8; a.Ls = seq_pitch;
-    OPCHK(launch_attn32_bwd(dtype, a, (hipStream_t)stream));
-  } else {
-    AttnBwdArgs a{qkv, out, dout, lse, delta, dqkv, N, grad_len, H, 1};
-    a.Ls = seq_pitch;
-    OPCHK(launch_attn_bwd(dtype, a, (hipStream_t)stream));
-  }
+  AttnBwdArgs a{qkv, out, dout, lse, delta, dqkv, N, grad_len, H, 1};
+  a.Ls = seq_pitch; a.fmt = pair ? (lo8 ? 2 : 1) : 0;
+  OPCHK(launch_attn_bwd(dtype, a, (hipStream_t)stream));
   return 0;
 }
-// ---- the pair attention under a shared prefix (mvlpt_set_text_shared_prefix; kernels.h Attn32Args::prefix): causal, slots
+// ---- the pair attention under a shared prefix (mvlpt_set_text_shared_prefix; kernels.h AttnArgs::prefix): causal, slots
 int mvlpt_op_attention32_fwd_prefix(int dtype, int lo8, const void* qkv, void* out, float* lse, int N, int L, int H, int prefix,
                                     mvlpt_stream_t stream) {
   if (!qkv || !out || prefix <= 0) return fail(nullptr, MVLPT_ERR_ARG, "op_attention32_fwd_prefix: null/invalid argument");
-  Attn32Args a{qkv, out, lse, N, L, H, 1, 0};
-  a.out_lo8 = lo8; a.prefix = prefix;
-  OPCHK(launch_attn32_fwd(dtype, a, (hipStream_t)stream));
+  AttnArgs a{qkv, out, lse, N, L, H, 1, 0};
+  a.fmt = lo8 ? 2 : 1; a.prefix = prefix;
+  OPCHK(launch_attn_fwd(dtype, a, (hipStream_t)stream));
   return 0;
 }
 int mvlpt_op_attention32_bwd_prefix(int dtype, int lo8, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
@@ -2428,9 +2527,9 @@ int mvlpt_op_attention32_bwd_prefix(int dtype, int lo8, const void* qkv, const v
                                     mvlpt_stream_t stream) {
   if (!qkv || !out || !dout || !lse || !delta || !dqkv || !kv_part || prefix <= 0 || seq_len < grad_len)
     return fail(nullptr, MVLPT_ERR_ARG, "op_attention32_bwd_prefix: null/invalid argument");
-  Attn32BwdArgs a{qkv, out, dout, lse, delta, dqkv, N, grad_len, H, 1};
-  a.lo8 = lo8; a.Ls = seq_len; a.prefix = prefix; a.kv_part = kv_part; a.part_mul = part_mul;
-  OPCHK(launch_attn32_bwd(dtype, a, (hipStream_t)stream));
+  AttnBwdArgs a{qkv, out, dout, lse, delta, dqkv, N, grad_len, H, 1};
+  a.fmt = lo8 ? 2 : 1; a.Ls = seq_len; a.prefix = prefix; a.kv_part = kv_part; a.part_mul = part_mul;
+  OPCHK(launch_attn_bwd(dtype, a, (hipStream_t)stream));
   return 0;
 }
 // ... and the single-operand attention (attention.hip) under a shared prefix: the fast mode's kernels, same slots, 16-bit tensors

@@ -1149,9 +1149,8 @@ static bool gemm_args_ok(int dtype, int epi, const GemmArgs& g, bool folded, boo
   if (epi == EPI_RESIDP_LN && (!g.rp_hi_in || !g.rp_lo_in || !g.rp_lo_out || !g.ln_part || g.ln_ntp <= 0 || (g.ln_ntp & 1))) return false;
   if (folded && (!g.fold_colsum || !g.bias || g.fold_nt <= 0 || g.fold_nt > g.fold_ntp)) return false;
   if ((epi == EPI_GELUBWD || epi == EPI_GELUBWD_SPLIT) && !g.aux) return false;
-  // the aux row map: whole sequences of at least 3 rows (the epilogue steps 4 rows at most two sequences on), aux rows below 2^31
-  if (g.aux_seq && (!(epi == EPI_GELUBWD || epi == EPI_GELUBWD_SPLIT) || g.aux_seq < 3 || g.aux_pitch < g.aux_seq || g.M % g.aux_seq ||
-                    (int64_t)(g.M / g.aux_seq) * g.aux_pitch > INT32_MAX)) return false;
+  // the aux row map: GELU-backward epilogues only, sequences of at least 3 rows (the epilogue steps 4 rows at most two sequences on)
+  if (g.aux_rows.seq && (!(epi == EPI_GELUBWD || epi == EPI_GELUBWD_SPLIT) || g.aux_rows.seq < 3 || !row_map_ok(g.aux_rows, g.M))) return false;
   return true;
 }
 

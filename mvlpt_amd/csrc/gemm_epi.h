@@ -304,11 +304,11 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&
     f32x4 rv[4][4];
     v4 uv[4][4];
     if constexpr (RESID || EPI == EPI_GELUBWD || EPI == EPI_GELUBWD_SPLIT) {
-      // GemmArgs::aux_seq: aux row of output row m = m + (m / aux_seq) * (aux_pitch - aux_seq).  The lane's 16 rows are 4 apart, so
-      // one division places the first and every further one is at most two sequences on (aux_seq >= 3)
+      // GemmArgs::aux_rows: the aux row of output row m is aux_rows.row(m), the same map in incremental form.  The lane's 16 rows
+      // are 4 apart, so one division places the first and every further one is at most two sequences on (seq >= 3)
       [[maybe_unused]] int aseq = 0, apos = 0;
       if constexpr (!RESID) {
-        if (g.aux_seq) { const int m0 = mbase + rq; aseq = m0 / g.aux_seq; apos = m0 - aseq * g.aux_seq; }
+        if (g.aux_rows.seq) { const int m0 = mbase + rq; aseq = m0 / g.aux_rows.seq; apos = m0 - aseq * g.aux_rows.seq; }
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -318,12 +318,12 @@ __device__ __forceinline__ void epilogue_store(const GemmArgs& g, const f32x4 (&
           m = m < M ? m : M - 1;
           if constexpr (RESID) rv[i][it] = __builtin_nontemporal_load((const f32x4*)(g.resid + (size_t)m * N + nbase + c * 4));
           else {
-            if (g.aux_seq) {
+            if (g.aux_rows.seq) {
               // (rows past M read the last aux row of the last sequence, like the clamp above)
-              m = mbase + i * 16 + it * 4 + rq < M ? aseq * g.aux_pitch + apos : (M / g.aux_seq - 1) * g.aux_pitch + g.aux_seq - 1;
+              m = mbase + i * 16 + it * 4 + rq < M ? aseq * g.aux_rows.pitch + apos : (M / g.aux_rows.seq - 1) * g.aux_rows.pitch + g.aux_rows.seq - 1;
               apos += 4;
-              if (apos >= g.aux_seq) { apos -= g.aux_seq; ++aseq; }
-              if (apos >= g.aux_seq) { apos -= g.aux_seq; ++aseq; }
+              if (apos >= g.aux_rows.seq) { apos -= g.aux_rows.seq; ++aseq; }
+              if (apos >= g.aux_rows.seq) { apos -= g.aux_rows.seq; ++aseq; }
             }
             uv[i][it] = __builtin_nontemporal_load((const v4*)((const T*)g.aux + (size_t)m * N + nbase + c * 4));
           }

@@ -527,7 +527,7 @@ __global__ void assemble_prompts_kernel(const float* __restrict__ prefix, const 
     return prompt_row(prefix, suffix, ctx + (size_t)(ctx_per_class ? cls * n_ctx : 0) * d, suf_len, layout[seq * L + pos_i], cls, d);
   });
 }
-// The same tokens in the shared-prefix layout (kernels.h Attn32Args::prefix): x holds C + 1 slots of L - P rows; slot 0 = positions
+// The same tokens in the shared-prefix layout (kernels.h AttnArgs::prefix): x holds C + 1 slots of L - P rows; slot 0 = positions
 // 0 .. P-1 as class 0 has them (the caller vouches that every class has the same) and zeros in its unused rows, slot c + 1 =
 // positions P .. L-1 of class c.  A generic context only.
 __global__ void assemble_prompts_prefix_kernel(const float* __restrict__ prefix, const float* __restrict__ suffix,
@@ -591,16 +591,15 @@ __global__ void eot_rows_kernel(const int32_t* __restrict__ eot, int32_t* __rest
 }
 // dst[r] = src[idx[r]] (gather) or dst[idx[r]] = src[r] (scatter); rows of row_bytes (a multiple of 16) bytes
 __global__ void copy_rows_kernel(const char* __restrict__ src, char* __restrict__ dst, const int32_t* __restrict__ idx, int rows,
-                                 int row_bytes, int scatter, int idx_seq, int far_seq) {
+                                 int row_bytes, int scatter, RowMap far_rows) {
   const int chunks = row_bytes / 16;
   const size_t total = (size_t)rows * chunks;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int r = (int)(i / chunks), c = (int)(i % chunks);
     int fr = idx[r];
-    if (idx_seq > 0) {
-      const int pos = fr % idx_seq;
-      if (pos >= far_seq) continue;      // a position the far side does not hold: skipped, never dereferenced
-      fr = (fr / idx_seq) * far_seq + pos;
+    if (far_rows.seq > 0) {      // idx names saved rows, the far side is compact: the map read backwards
+      if (fr % far_rows.pitch >= far_rows.seq) continue;      // a position the far side does not hold: skipped, never dereferenced
+      fr = (int)RowMap{far_rows.pitch, far_rows.seq}.row(fr);
     }
     const size_t far = (size_t)fr * row_bytes + (size_t)c * 16, near = (size_t)r * row_bytes + (size_t)c * 16;
     if (scatter) *(f32x4*)(dst + far) = *(const f32x4*)(src + near);
@@ -608,13 +607,14 @@ __global__ void copy_rows_kernel(const char* __restrict__ src, char* __restrict_
   }
 }
 hipError_t launch_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, hipStream_t s,
-                            int idx_seq, int far_seq) {
+                            RowMap far) {
   if (rows <= 0) return hipSuccess;
-  if (row_bytes % 16 || idx_seq < 0 || (idx_seq > 0 && far_seq <= 0)) return hipErrorInvalidValue;
+  // (how many rows the far side holds is the caller's knowledge, like the range of idx: the map alone is checked)
+  if (row_bytes % 16 || !row_map_ok(far, 0)) return hipErrorInvalidValue;
   const size_t total = (size_t)rows * (row_bytes / 16);
   const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
   hipLaunchKernelGGL(copy_rows_kernel, dim3(grid), dim3(256), 0, s, (const char*)src, (char*)dst, idx, rows, row_bytes, scatter,
-                     idx_seq, far_seq);
+                     far);
   return hipGetLastError();
 }
 

@@ -17,6 +17,21 @@ int stream_cus(hipStream_t s);
 // a cap then changes how many workgroups run, never which arithmetic.
 int stream_cus_nocap(hipStream_t s);
 
+// ---------------------------------------------------------------- row map
+// The leading `seq` positions of sequences that are saved at a pitch of `pitch` rows: compact row r belongs to saved row
+// (r / seq) * pitch + r % seq.  seq == 0: the identity.  The one statement of the map: every launcher that reads a saved tensor from
+// compact rows (GemmArgs::aux_rows, LnBwdArgs::x_rows, ActArgs::u_rows, launch_copy_rows) carries this struct and calls row().
+struct RowMap {
+  int seq = 0, pitch = 0;
+  __host__ __device__ size_t row(int r) const { return seq > 0 ? (size_t)(r / seq) * pitch + r % seq : (size_t)r; }
+};
+// When a map is legal for `rows` compact rows: whole sequences, pitch >= seq, and the saved rows below 2^31.  Each launcher adds
+// its own conditions to this one.
+inline bool row_map_ok(RowMap m, int rows) {
+  if (m.seq == 0) return true;
+  return m.seq > 0 && m.pitch >= m.seq && rows % m.seq == 0 && (int64_t)(rows / m.seq) * m.pitch <= INT32_MAX;
+}
+
 // ---------------------------------------------------------------- GEMM  C = A * Bt^T (+ epilogue)
 enum GemmEpi {
   EPI_STORE16 = 0,  // out16 = acc (+bias)
@@ -46,14 +61,14 @@ constexpr int epi_base(int epi) {
 constexpr bool epi_folds(int epi) { return epi >= EPI_STORE16_FOLD && epi <= EPI_GELU_SPLIT_FOLD; }
 constexpr bool epi_ln_producer(int epi) { return epi == EPI_RESID32_LN || epi == EPI_RESIDP_LN; }
 struct GemmArgs {
-  const void* A;       // [M,K] 16-bit
-  const void* Bt;      // [N,K] 16-bit
-  int M, N, K;
-  const float* bias;   // [N] or null
-  const void* aux;     // [M,N] 16-bit (EPI_GELUBWD)
-  const float* resid;  // [M,N] fp32   (EPI_RESID32)
-  void* out;           // [M,N]
-  void* out2;          // [M,N] 16-bit, optional (EPI_GELU)
+  const void* A = nullptr;       // [M,K] 16-bit
+  const void* Bt = nullptr;      // [N,K] 16-bit
+  int M = 0, N = 0, K = 0;
+  const float* bias = nullptr;   // [N] or null
+  const void* aux = nullptr;     // [M,N] 16-bit (EPI_GELUBWD)
+  const float* resid = nullptr;  // [M,N] fp32   (EPI_RESID32)
+  void* out = nullptr;           // [M,N]
+  void* out2 = nullptr;          // [M,N] 16-bit, optional (EPI_GELU)
   // Split-precision A operand: A is [M, 2K] = [A_hi | A_lo] (16-bit pair, A ~ A_hi + A_lo to ~22 bits) and the
   // product is A_hi*Bt^T + A_lo*Bt^T in the same fp32 accumulators: the K loop runs over 2K with the Bt K-index wrapping.
   // The frozen weights are exactly representable in 16 bits (they are stored so, clip/model.py:371-392), so the product
@@ -75,9 +90,8 @@ struct GemmArgs {
   // pads such rows by 128 bytes.
   int lda = 0, ldo = 0;
   int xcd_order = 0;   // set by the one-tile-per-workgroup launcher (gemm_pc_kernel): XCD-aware tile order
-  // EPI_GELUBWD / EPI_GELUBWD_SPLIT: output row m reads aux row (m / aux_seq) * aux_pitch + m % aux_seq (the leading aux_seq positions of
-  // sequences saved at a pitch of aux_pitch rows; M % aux_seq == 0).  aux_seq == 0: row m.
-  int aux_seq = 0, aux_pitch = 0;
+  // EPI_GELUBWD / EPI_GELUBWD_SPLIT: output row m reads aux row aux_rows.row(m) (sequences of at least 3 rows)
+  RowMap aux_rows;
   // ---- LayerNorm folding: LN(x) W^T = rstd_r * ((x * gamma) W^T)[r,n] - rstd_r * mean_r * (W gamma)[n] + (W beta)[n], so the
   // GEMM in front of a LayerNorm hands the un-normalised row to the GEMM behind it and the LayerNorm pass (one read of the fp32
   // residual stream + one 16-bit write per LayerNorm) disappears.  No atomics, no extra launch: every output tile owns its slots.
@@ -135,28 +149,27 @@ hipError_t launch_sgemm_bt(const float* A, const float* Bt, float* C, int M, int
 // ---------------------------------------------------------------- LayerNorm (fp32 statistics)
 // Input row r is read at  x + in_row(r) * d  with in_row(r) = row_idx ? row_idx[r] : r * row_mul.
 struct LnFwdArgs {
-  const float* x; const int32_t* row_idx; int row_mul;
-  const float* gamma; const float* beta;
-  void* y;          // [rows,d] contiguous, 16-bit (out_dtype = compute dtype) or fp32 (out_dtype = DT_F32)
-  int rows, d;
+  const float* x = nullptr; const int32_t* row_idx = nullptr; int row_mul = 1;
+  const float* gamma = nullptr; const float* beta = nullptr;
+  void* y = nullptr;   // [rows,d] contiguous, 16-bit (out_dtype = compute dtype) or fp32 (out_dtype = DT_F32)
+  int rows = 0, d = 0;
   int split = 0;    // 16-bit outputs only: y is [rows, 2d] = [hi | lo] (split-precision A operand, see GemmArgs::a_split);
                     // 2: same pitch, [hi | lo8 bytes | unused] (mixed pair)
 };
 hipError_t launch_ln_fwd(int out_dtype, const LnFwdArgs& a, hipStream_t s);
 
 struct LnBwdArgs {
-  const void* dy;        // [rows,d] contiguous, 16-bit (dy_dtype = compute dtype) or fp32 (dy_dtype = DT_F32)
-  int dy_dtype;
-  const float* x; const int32_t* row_idx; int row_mul;   // LN input rows (same mapping as forward)
-  const float* gamma;
-  const float* resid;    // fp32, same row mapping as x, or null:  out32 = resid + dx
-  float* out32;          // fp32, same row mapping as x (may alias resid)
-  void* out16;           // optional 16-bit copy, same row mapping
-  int rows, d;
+  const void* dy = nullptr;        // [rows,d] contiguous, 16-bit (dy_dtype = compute dtype) or fp32 (dy_dtype = DT_F32)
+  int dy_dtype = DT_F32;
+  const float* x = nullptr; const int32_t* row_idx = nullptr; int row_mul = 1;   // LN input rows (same mapping as forward)
+  const float* gamma = nullptr;
+  const float* resid = nullptr;    // fp32, same row mapping as x, or null:  out32 = resid + dx
+  float* out32 = nullptr;          // fp32, same row mapping as x (may alias resid)
+  void* out16 = nullptr;           // optional 16-bit copy, same row mapping
+  int rows = 0, d = 0;
   int split = 0;         // out16 is [*, 2d] = [hi | lo]; 2: [hi | lo8 bytes | unused] (mixed pair)
-  // x_seq > 0 (row_idx null, row_mul 1): x alone is read at row (r / x_seq) * x_pitch + r % x_seq, the leading x_seq positions of
-  // sequences saved at a pitch of x_pitch rows; dy, resid and the outputs stay at row r
-  int x_seq = 0, x_pitch = 0;
+  // a map (row_idx null, row_mul 1): x alone is read at row x_rows.row(r); dy, resid and the outputs stay at row r
+  RowMap x_rows;
 };
 hipError_t launch_ln_bwd(int dtype, const LnBwdArgs& a, hipStream_t s);
 // The kernel both launchers use for `rows` x `d` on stream `s`: stream = 0 one wave per row (ln_*_kernel), 1 grid-stride
@@ -164,32 +177,59 @@ hipError_t launch_ln_bwd(int dtype, const LnBwdArgs& a, hipStream_t s);
 struct LnRoute { int stream, nv, grid; };
 LnRoute ln_route(int rows, int d, hipStream_t s);
 
-// ---------------------------------------------------------------- attention (head_dim 64, L <= 256)
-// qkv: [N*L, 3*d] 16-bit, token = n*L + i, columns [q | k | v], head h at h*64 inside each third.
+// ---------------------------------------------------------------- attention (head_dim 64)
+// fmt 0 (single 16-bit operands, attention.hip; L <= 256 resident, longer sequences streamed):
+//   qkv: [N*L, 3*d] 16-bit, token = n*L + i, columns [q | k | v], head h at h*64 inside each third; out [N*L, d].
+// fmt 1 / 2 (split-precision attention, attention32.hip, any L) — the mode of the towers that carry a gradient: every operand is a
+//   16-bit hi|lo pair [rows, 2*cols] (hi = round16(x), lo = round16(x - hi)), products keep hi*hi + hi*lo + lo*hi on the 16-bit MFMA
+//   (fp32 accumulation); the outputs are pairs again: directly the `a_split` A operand of the next GEMM.
+//   qkv: [N*L, 6d] 16-bit: [hi(q|k|v) | lo(q|k|v)], head h at h*64 inside each d-wide block; out [N*L, 2d]: [hi(d) | lo(d)].
+//   fmt 2 (mixed pair): `out` rows are [hi(d) | lo8 (d bytes) | unused], the out-projection's A operand.
 struct AttnArgs {
-  const void* qkv; void* out /*[N*L,d]*/; float* lse /*[N*H*L] or null*/;
-  int N, L, H; int causal;
+  const void* qkv = nullptr; void* out = nullptr; float* lse = nullptr /*[N*H*L] or null*/;
+  int N = 0, L = 0, H = 0; int causal = 0;
   int q_rows = 0;   // > 0: only queries 0..q_rows-1 of every sequence are computed (last layer: only CLS is consumed)
-  int flags = 0;    // experiment bits: 1 = non-temporal K/V staging, 2 = non-temporal output stores
-  // Shared prefix, as Attn32Args::prefix, on single operands: causal, L <= 80, q_rows == 0, 2 P <= L; N + 1 slots of L - P rows in qkv /
-  // out, lse [N + 1, H, L - P]; workgroups (N, h) are the prefix itself and also write zeros into the unused rows of slot 0
+  int flags = 0;    // experiment bits: 1 = non-temporal K/V staging, 2 = non-temporal output stores (fmt 0; set by launch_attn_fwd)
+  // Shared prefix (the short causal kernels: causal, L <= 80, q_rows == 0, 2 P <= L).  prefix = P > 0: positions 0 .. P-1 are the same
+  // rows in all N sequences and every tensor holds N + 1 "slots" of L - P rows: slot 0 = the prefix in its first P rows, slot n + 1 =
+  // positions P .. L-1 of sequence n (lse: [slot, H, L - P]).  Sequence n reads position p < P from slot 0 and writes only its
+  // queries >= P; one more workgroup row (pairs: blockIdx.y == N; single operands: workgroups (N, h)) is the prefix itself, length P;
+  // it also writes zeros into the other rows of slot 0 of out / lse (never read by the attention: the row-wise kernels behind it
+  // then meet finite, deterministic values).
   int prefix = 0;
+  // Operand format: 0 single 16-bit, 1 hi|lo pair, 2 mixed pair — the encoding of TowerState::xs, GemmArgs::a_split, LnFwdArgs::split
+  int fmt = 0;
+#ifdef MVLPT_ATTN_TRACE
+  long long* trace = nullptr;   // debug builds only (tools/attn_trace.py): (point id << 56 | s_memtime) records of one workgroup
+#endif
 };
-// ea / eb (optional): start / stop events of the kernel's own dispatch (hipExtLaunchKernelGGL), for mvlpt_profile_* — resident kernels only
+// Routes on a.fmt.  ea / eb (optional): start / stop events of the kernel's own dispatch (hipExtLaunchKernelGGL), for
+// mvlpt_profile_* — the resident single-operand kernels only
 hipError_t launch_attn_fwd(int dtype, const AttnArgs& a, hipStream_t s, hipEvent_t ea = nullptr, hipEvent_t eb = nullptr);
 struct AttnBwdArgs {
-  const void* qkv; const void* out; const void* dout; const float* lse;
-  float* delta /*[N*H*L] scratch*/; void* dqkv /*[N*L,3d]*/;
-  int N, L, H; int causal;
+  const void* qkv = nullptr; const void* out = nullptr; const void* dout = nullptr /*[N*L, d]; pairs: [N*L, 2d]*/;
+  const float* lse = nullptr;
+  float* delta = nullptr /*[N*H*L] scratch*/; void* dqkv = nullptr /*[N*L, 3d]; pairs: [N*L, 6d] = [hi(3d) | lo(3d)]*/;
+  int N = 0, L = 0, H = 0; int causal = 0;
   // Ls > L: the saved tensors (qkv, out, lse) hold sequences of Ls positions and only the leading L carry a gradient: dout, delta and
-  // dqkv are [N*L, .] and positions >= L are neither staged nor computed (causal only: no row < L reads a key or query >= L).  0: L
+  // dqkv are [N*L, .] and positions >= L are neither staged nor computed (causal only: no row < L reads a key or query >= L; pairs:
+  // the short causal kernel, L <= 80, only).  0: L
   int Ls = 0;
-  // Shared prefix, as Attn32BwdArgs::prefix, on single operands (causal, L <= 80, 2 P <= L): saved tensors in slots of Ls - P rows,
-  // dout / dqkv in slots of L - P rows, delta [N + 1, H, L - P]; kv_part fp32 [N + 1, P, 2d]; a third launch writes dK / dV of slot 0 =
-  // kv_part[N] + part_mul * sum_n kv_part[n] (the fixed order of attn32t_prefix_reduce_kernel) and zeroes the unused rows of slot 0
+  // Shared prefix (AttnArgs::prefix; the short causal kernels only, 2 P <= L).  The saved tensors hold N + 1 slots of Ls - P rows,
+  // dout / dqkv N + 1 slots of L - P rows, delta [N + 1, H, L - P].  Sequence n takes dO of its positions < P as zero, stores dQ / dK /
+  // dV of its positions >= P and writes dK / dV of the prefix keys as fp32 into kv_part [N + 1, P, 2d] (row: dK (d) | dV (d));
+  // workgroup row N is the prefix's own backward from slot 0 of dout (dQ into slot 0 of dqkv, dK / dV into kv_part[N]).  One more
+  // launch then writes dK / dV of slot 0: kv_part[N] + part_mul * sum_n kv_part[n] (a fixed order, no atomics; single operands in
+  // the order of attn32t_prefix_reduce_kernel), and zeroes the unused rows P .. L-P-1 of slot 0.
   int prefix = 0; float* kv_part = nullptr; float part_mul = 1.f;
+  // Operand format, as AttnArgs::fmt.  2: `out` rows are [hi | lo8] (read for delta) and dqkv rows are written as
+  // [hi(3d) | lo8 (3d bytes) | unused]
+  int fmt = 0;
+#ifdef MVLPT_ATTN_TRACE
+  long long* trace = nullptr;   // debug builds only (tools/attn_trace.py bwd): records of one workgroup of attn32r_bwd_kernel
+#endif
 };
-hipError_t launch_attn_bwd(int dtype, const AttnBwdArgs& a, hipStream_t s);
+hipError_t launch_attn_bwd(int dtype, const AttnBwdArgs& a, hipStream_t s);      // routes on a.fmt
 int attn_max_len();
 // backward when only query 0 of every sequence carries a gradient: o_cls / do_cls are compact [N, H*64] rows
 hipError_t launch_attn_bwd_cls(int dtype, const void* qkv, const void* o_cls, const void* do_cls, const float* lse, void* dqkv,
@@ -201,46 +241,6 @@ hipError_t launch_attn_bwd_stream(int dtype, const AttnBwdArgs& a, hipStream_t s
 // (causal != 0 -> hipErrorInvalidValue), forward only; only rows 0..q_rows-1 of every sequence are written when q_rows > 0
 bool attn_wide_supported(int head_width);
 hipError_t launch_attn_fwd_wide(int dtype, const AttnArgs& a, int head_width, hipStream_t s);
-
-// ---------------------------------------------------------------- split-precision attention (attention32.hip), any L
-// Split-precision mode of the towers that carry a gradient: every operand is a 16-bit hi|lo pair [rows, 2*cols]
-// (hi = round16(x), lo = round16(x - hi)), products keep hi*hi + hi*lo + lo*hi on the 16-bit MFMA (fp32 accumulation);
-// the outputs are pairs again: directly the `a_split` A operand of the next GEMM.
-struct Attn32Args {
-  const void* qkv_split; // [N*L, 6d] 16-bit: [hi(q|k|v) | lo(q|k|v)], head h at h*64 inside each d-wide block
-  void* out_split;       // [N*L, 2d] 16-bit: [hi(d) | lo(d)]
-  float* lse;            // [N*H*L] or null
-  int N, L, H; int causal;
-  int q_rows = 0;        // > 0: only queries 0..q_rows-1 of every sequence are computed
-  int out_lo8 = 0;       // out_split rows are [hi(d) | lo8 (d bytes) | unused] (mixed pair: the out-projection's A operand)
-  // Shared prefix (the short causal kernel, L <= 80, q_rows == 0, only).  prefix = P > 0: positions 0 .. P-1 are the same rows in all N
-  // sequences and every tensor holds N + 1 "slots" of L - P rows: slot 0 = the prefix in its first P rows, slot n + 1 = positions
-  // P .. L-1 of sequence n (lse: [slot, H, L - P]).  Sequence n reads position p < P from slot 0 and writes only its queries >= P;
-  // one more workgroup row (blockIdx.y == N) is the prefix itself, length P; it also writes zeros into the other rows of slot 0 of out /
-  // lse (never read by the attention: the row-wise kernels behind it then meet finite, deterministic values).  2 P <= L.
-  int prefix = 0;
-#ifdef MVLPT_ATTN_TRACE
-  long long* trace = nullptr;   // debug builds only (tools/attn_trace.py): (point id << 56 | s_memtime) records of one workgroup
-#endif
-};
-hipError_t launch_attn32_fwd(int dtype, const Attn32Args& a, hipStream_t s);
-struct Attn32BwdArgs {
-  const void* qkv_split; const void* out_split; const void* dout_split /*[N*L, 2d]*/; const float* lse;
-  float* delta /*[N*H*L] scratch*/; void* dqkv_split /*[N*L, 6d] 16-bit: [hi(3d) | lo(3d)]*/;
-  int N, L, H; int causal;
-  int lo8 = 0;           // out_split rows are [hi | lo8] (read for delta) and dqkv_split rows are written as [hi(3d) | lo8 (3d bytes) | unused]
-  int Ls = 0;            // as AttnBwdArgs::Ls (the short causal kernel, L <= 80, only)
-  // Shared prefix (Attn32Args::prefix; the short causal kernel only).  The saved tensors hold N + 1 slots of Ls - P rows, dout / dqkv
-  // N + 1 slots of L - P rows.  Sequence n takes dO of its positions < P as zero, stores dQ / dK / dV of its positions >= P and writes
-  // dK / dV of the prefix keys as fp32 into kv_part [N + 1, P, 2d] (row: dK (d) | dV (d)); workgroup row N is the prefix's own
-  // backward from slot 0 of dout (dQ into slot 0 of dqkv, dK / dV into kv_part[N]).  A second launch then writes dK / dV of slot 0:
-  // kv_part[N] + part_mul * sum_n kv_part[n] (a fixed order, no atomics), and zeroes the unused rows P .. L-P-1 of slot 0.
-  int prefix = 0; float* kv_part = nullptr; float part_mul = 1.f;
-#ifdef MVLPT_ATTN_TRACE
-  long long* trace = nullptr;   // debug builds only (tools/attn_trace.py bwd): records of one workgroup of attn32r_bwd_kernel
-#endif
-};
-hipError_t launch_attn32_bwd(int dtype, const Attn32BwdArgs& a, hipStream_t s);
 
 // ---------------------------------------------------------------- input pipeline (preprocess.hip)
 // same layout as MvlptImageDesc (include/mvlpt_hip.h)
@@ -316,7 +316,7 @@ hipError_t launch_overwrite_rows(const float* rows, int n, float* x, int B, int 
 hipError_t launch_assemble_prompts(const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
                                    const int32_t* layout, const float* pos, float* x, int C, int L, int d, hipStream_t s,
                                    int shared_prefix = 0);
-// shared_prefix = P > 0: the three tables / tokens in the shared-prefix layout (Attn32Args::prefix; glue.hip): x as C + 1 slots of
+// shared_prefix = P > 0: the three tables / tokens in the shared-prefix layout (AttnArgs::prefix; glue.hip): x as C + 1 slots of
 // L - P rows, eot rows in slot c + 1, ctx_pos against gradient slots of Lt rows
 hipError_t launch_build_ctx_pos(const int32_t* layout, int32_t* ctx_pos, int C, int L, int n_ctx, hipStream_t s, int shared_prefix = 0, int Lt = 0);
 hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipStream_t s, int shared_prefix = 0);
@@ -324,10 +324,10 @@ hipError_t launch_eot_rows(const int32_t* eot, int32_t* rows, int C, int L, hipS
 // of them inside the table (checked on the host by the callers); d % 4 == 0
 hipError_t launch_embed_tokens(const float* emb, const float* pos, const int32_t* ids, int ld, float* x, int S, int L, int d, hipStream_t s);
 // dst[r] = src[idx[r]] (scatter = 0) or dst[idx[r]] = src[r] (scatter = 1); row_bytes % 16 == 0
-// idx_seq > 0: idx addresses sequences of idx_seq rows and the far side holds them at a pitch of far_seq rows: idx[r] stands for
-// (idx[r] / idx_seq) * far_seq + idx[r] % idx_seq
+// far (a map): idx names rows of the saved tensors and the far side is compact, holding the leading far.seq positions of every
+// sequence of far.pitch: the map read backwards.  An idx[r] whose position the far side does not hold is skipped.
 hipError_t launch_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, hipStream_t s,
-                            int idx_seq = 0, int far_seq = 0);
+                            RowMap far = RowMap());
 // rows of row_bytes (multiple of 16) from src + r*src_pitch to dst + r*dst_pitch
 hipError_t launch_copy_rows_strided(const void* src, void* dst, int rows, size_t src_pitch, size_t dst_pitch, int row_bytes, hipStream_t s);
 // out[j,:] = inv_scale * sum_b dx[b, row0+j, :]; optionally zero those rows of dx32/dx16 afterwards
@@ -382,15 +382,15 @@ enum ActKind { ACT_QUICKGELU = 0, ACT_GELU = 1 };
 // A-operand formats of the output (GemmArgs::a_split of the GEMM that reads it): [M, N], hi|lo pair [M, 2N], mixed pair (same pitch)
 enum ActFmt { ACT_FMT_SINGLE = 0, ACT_FMT_PAIR = 1, ACT_FMT_MIXED = 2 };
 struct ActArgs {
-  const float* in;     // forward: the pre-activation u; backward: dA; fp32 [M, N], as EPI_STORE32 writes them
-  int ldi;             // row pitch of `in` in floats (0: dense)
-  void* out;           // act(u) / dA * act'(u) in format fmt
-  int fmt;
-  int ldo;             // row pitch of `out` in 16-bit elements (0: dense, N or 2N)
-  void* u16;           // 16-bit [M, N], dense: forward, optional: the saved pre-activation is written; backward: it is read
-  int M, N;            // N % 8 == 0; pitches multiples of 8; every pointer 16-byte aligned
-  // backward only: row m reads u16 row (m / u_seq) * u_pitch + m % u_seq (GemmArgs::aux_seq for the stand-alone pass).  0: row m
-  int u_seq = 0, u_pitch = 0;
+  const float* in = nullptr;      // forward: the pre-activation u; backward: dA; fp32 [M, N], as EPI_STORE32 writes them
+  int ldi = 0;                    // row pitch of `in` in floats (0: dense)
+  void* out = nullptr;            // act(u) / dA * act'(u) in format fmt
+  int fmt = ACT_FMT_SINGLE;
+  int ldo = 0;                    // row pitch of `out` in 16-bit elements (0: dense, N or 2N)
+  void* u16 = nullptr;            // 16-bit [M, N], dense: forward, optional: the saved pre-activation is written; backward: it is read
+  int M = 0, N = 0;               // N % 8 == 0; pitches multiples of 8; every pointer 16-byte aligned
+  // backward only: row m reads u16 row u_rows.row(m) (GemmArgs::aux_rows for the stand-alone pass)
+  RowMap u_rows;
 };
 const char* act_check(int dtype, int act, bool bwd, ActArgs& a);      // null when the launch is legal (pitches resolved), else why not
 hipError_t launch_act_fwd(int dtype, int act, const ActArgs& a, hipStream_t s);

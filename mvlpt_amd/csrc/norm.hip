@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(LnBwdArgs a) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.rows) return;
   const size_t in_row = a.row_idx ? (size_t)a.row_idx[row] : (size_t)row * a.row_mul;
-  const size_t x_row = a.x_seq > 0 ? (size_t)(row / a.x_seq) * a.x_pitch + row % a.x_seq : in_row;      // (LnBwdArgs::x_seq)
+  const size_t x_row = a.x_rows.seq > 0 ? a.x_rows.row(row) : in_row;      // (LnBwdArgs::x_rows)
   const float* x = a.x + x_row * a.d;
   const TDY* dy = (const TDY*)a.dy + (size_t)row * a.d;
   f32x4 v[LN_MAXV], gg[LN_MAXV]; bool ok[LN_MAXV];
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void ln_bwd_stream_kernel(LnBwdArgs a) {
   auto in_row_of = [&](int r) { return a.row_idx ? (size_t)a.row_idx[r] : (size_t)r * a.row_mul; };
   auto load_row = [&](int r, f32x4* x, f32x4* d, f32x4* rs) {
     const size_t in_row = in_row_of(r);
-    const size_t x_row = a.x_seq > 0 ? (size_t)(r / a.x_seq) * a.x_pitch + r % a.x_seq : in_row;      // (LnBwdArgs::x_seq)
+    const size_t x_row = a.x_rows.seq > 0 ? a.x_rows.row(r) : in_row;      // (LnBwdArgs::x_rows)
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * 4;
@@ -318,10 +318,10 @@ hipError_t launch_ln_fwd(int out_dtype, const LnFwdArgs& a, hipStream_t s) {
 hipError_t launch_ln_bwd(int dtype, const LnBwdArgs& a, hipStream_t s) {
   if (a.rows <= 0) return hipSuccess;
   if (a.d % 4 != 0 || a.d > LN_MAXV * 256) return hipErrorInvalidValue;
-  if (a.x_seq < 0 || (a.x_seq > 0 && (a.row_idx || a.row_mul != 1 || a.x_pitch < a.x_seq))) return hipErrorInvalidValue;
+  if (!row_map_ok(a.x_rows, a.rows) || (a.x_rows.seq && (a.row_idx || a.row_mul != 1))) return hipErrorInvalidValue;
   // The two kernels sum a row in different orders.  Under the row map the kernel is the one the saved rows would take, so that a
   // backward over the leading positions keeps the bits of one over all of them; the grid follows the rows there are.
-  LnRoute r = ln_route(a.x_seq > 0 ? a.rows / a.x_seq * a.x_pitch : a.rows, a.d, s);
+  LnRoute r = ln_route(a.x_rows.seq > 0 ? a.rows / a.x_rows.seq * a.x_rows.pitch : a.rows, a.d, s);
   const int want = (a.rows + 3) / 4;
   if (!r.stream || r.grid > want) r.grid = want;
   dim3 grid(r.grid), block(256);

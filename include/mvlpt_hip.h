@@ -687,6 +687,39 @@ int mvlpt_op_nearest_rows(const float* q, const float* table, int R, int V, int 
                           int64_t workspace_bytes, mvlpt_stream_t stream);
 int mvlpt_nearest_tokens(void* handle, const float* q, int R, int k, int32_t* idx, float* dist, mvlpt_stream_t stream);
 
+/* ---- test-time prompt tuning: the entropy head over V views per image (row o of the scope table; tests/test_hip_tpt_head.py) ----
+ * Replaces, per optimisation step of TPT (Shu et al., NeurIPS 2022), the logits product, log_softmax, per-view entropy, the
+ * argsort-based confidence selection, the marginal entropy of the selected views and autograd back to the text features.
+ * All fp32, row-major: img [G, V, e] un-normalised features of the V views of each of G test images; txt [G*C, e] un-normalised text
+ * features, row g*C + c = (image g, class c) (mvlpt_text_fwd_ranged over full ranges); scale = exp(logit_scale); 1 <= k <= V.
+ *   Forward:  z[g,v,c] = scale <img/|img|, txt/|txt|>;  logp = z - logsumexp_c z;  H[g,v] = -sum_c exp(logp) logp;
+ *     sel[g] = the k views with the smallest H under the total order (H, then view index), NaN behind every number, written as
+ *     int32 [G, k] in that order;  a[g,c] = logsumexp_{v in sel[g]} logp[g,v,c] - log k;  loss[g] = -sum_c exp(a) a.
+ *     Outputs loss [G], H [G, V], sel [G, k]; z [G, V, C] only when the pointer is not NULL (tests): no [G, V, C] array is written
+ *     otherwise.  C = 1 gives H = 0 and loss = 0 exactly.
+ *   Backward: d (sum_g w_g loss[g]) / d txt with the selection held constant (w [G] on the device, NULL: all 1):
+ *     p = exp(logp), u_c = -(a_c + 1), dz[g,v,j] = (w_g / k) p_vj (u_j - sum_c p_vc u_c) for v in sel[g], 0 otherwise;
+ *     dtn[g,c] = scale sum_{v in sel} dz[g,v,c] img_v/|img_v|;  dtxt[g*C+c] = (dtn - <dtn, tn> tn) / |txt|.  Output dtxt [G*C, e];
+ *     there is no dimg (the image tower is frozen on this route).
+ *     The backward READS the workspace its forward filled (normalised rows, |txt|, the selection, logp and a of the selected views)
+ *     and recomputes nothing: it must follow mvlpt_op_tpt_head_fwd with the same sizes on the same stream and workspace, with nothing
+ *     else written to the workspace in between; it may be repeated (other weights).  It does not read img / txt / sel again.
+ *   Arithmetic: fp32 vector ALU; one lane adds the e terms of a (view, class) pair in the order i = 0 .. e-1, so the bits of z and of
+ *     H depend on the view's and the group's rows alone: not on the view's position v, the group's index, G or a rerun.  Two
+ *     bit-identical views have bit-identical H and resolve by index.  No floating-point atomics; every sum has one order.
+ *   Limits: 1 <= G <= MVLPT_TPT_MAX_GROUPS, 1 <= V <= MVLPT_TPT_MAX_VIEWS, 1 <= C <= MVLPT_TPT_MAX_CLASSES, G * C < 2^31,
+ *     4 <= e <= 1024 with e % 4 == 0, 1 <= k <= V; img, txt, dtxt and the workspace 16-byte aligned.  Every violation, a NULL required
+ *     pointer and a workspace below mvlpt_tpt_workspace_bytes return MVLPT_ERR_ARG (message: mvlpt_last_error(NULL)) before anything
+ *     is launched; nothing is written.  Handle-free, enqueue-only on `stream`, offsets are 64-bit. */
+enum { MVLPT_TPT_MAX_VIEWS = 128 };
+enum { MVLPT_TPT_MAX_GROUPS = 65535 };
+enum { MVLPT_TPT_MAX_CLASSES = 1 << 20 };
+int mvlpt_tpt_workspace_bytes(int G, int V, int C, int e, int k, int64_t* bytes);
+int mvlpt_op_tpt_head_fwd(const float* img, const float* txt, float scale, int G, int V, int C, int e, int k, float* loss, float* H,
+                          int32_t* sel, float* z, void* workspace, int64_t workspace_bytes, mvlpt_stream_t stream);
+int mvlpt_op_tpt_head_bwd(const float* w, float scale, int G, int V, int C, int e, int k, float* dtxt, void* workspace,
+                          int64_t workspace_bytes, mvlpt_stream_t stream);
+
 /* ---- evaluation on the device: class counters and column rank statistics (row f1b of the scope table; tests/test_hip_eval.py) ----
  * Everything MVLPT.test reports is a function of integer counts; these two entries produce the counts exactly, and the few remaining
  * double-precision divisions and means are finished on the host (mvlpt_amd/evaluator.py) with the calls mvlpt_amd/metrics.py makes.

@@ -26,6 +26,7 @@ ACT_QUICKGELU, ACT_GELU = 0, 1                           # MVLPT_ACT_*
 ACT_OUT_SINGLE, ACT_OUT_PAIR, ACT_OUT_MIXED = 0, 1, 2    # MVLPT_ACT_OUT_*
 ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4      # MVLPT_ERR_*
 NEAREST_MAX_K, NEAREST_MAX_ROWS = 64, 65535 * 8      # MVLPT_NEAREST_MAX_K, MVLPT_NEAREST_MAX_ROWS
+TPT_MAX_VIEWS, TPT_MAX_GROUPS, TPT_MAX_CLASSES = 128, 65535, 1 << 20      # MVLPT_TPT_MAX_*
 EVAL_SORT_TILE, EVAL_MAX_ROWS, EVAL_POINTS, EVAL_FLAG_NONFINITE, EVAL_FLAG_SOFT_TARGET = 4096, 1 << 20, 11, 1, 2      # MVLPT_EVAL_*
 TEXT_MIN_L = 3     # MVLPT_TEXT_MIN_L: the smallest sequence length mvlpt_text_encode_tokens accepts
 
@@ -201,6 +202,9 @@ SIGNATURES = {
     "mvlpt_nearest_workspace_bytes": (_i, [_i, _i, _i, _i, _vp, C.POINTER(C.c_int64)]),
     "mvlpt_op_nearest_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, C.c_int64, _vp]),
     "mvlpt_nearest_tokens": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "mvlpt_tpt_workspace_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int64)]),
+    "mvlpt_op_tpt_head_fwd": (_i, [_vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    "mvlpt_op_tpt_head_bwd": (_i, [_vp, _f, _i, _i, _i, _i, _i, _vp, _vp, C.c_int64, _vp]),
     "mvlpt_op_eval_count": (_i, [_vp, C.c_int64, _i, _i, _vp, _i, C.c_int64, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp]),
     "mvlpt_op_eval_rank_columns": (_i, [_vp, C.c_int64, _i, _i, _vp, _i, C.c_int64, _vp, _i, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp,

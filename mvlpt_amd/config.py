@@ -153,6 +153,11 @@ def get_cfg_default() -> CfgNode:
     # mvlpt_amd.zsclip (--trainer ZeroshotCLIP / ZeroshotCLIP2).  Not a reference key: the reference picks its templates from tables in
     # its own source by DATASET.NAME; here they are configuration.  ZeroshotCLIP takes exactly one, ZeroshotCLIP2 any number >= 1.
     cfg.TRAINER.ZSCLIP = CN(TEMPLATES=["a photo of a {}."])
+    # mvlpt_amd.tpt (--trainer TPT): test-time prompt tuning (Shu et al., NeurIPS 2022), evaluation only.  Per test image N_VIEWS views
+    # (view 0 the test view), the k = max(1, int(N_VIEWS * SELECTION_P)) most confident are kept, STEPS AdamW steps at LR on the image's
+    # own copy of the context minimise the entropy of their averaged prediction.  The context starts from TRAINER.MVLPT.COOP (N_CTX /
+    # CTX_INIT / CLASS_TOKEN_POSITION, e.g. with a CoOp checkpoint) when COOP.N_CTX != 0, else from N_CTX / CTX_INIT here, class at the end.
+    cfg.TRAINER.TPT = CN(N_VIEWS=64, SELECTION_P=0.1, STEPS=1, LR=5e-3, N_CTX=4, CTX_INIT="a photo of a", PREC="fp16")
     # SOURCES (not in the reference, which has one reader module per dataset): [task name, CoOp split file or "", image folder] per dataset;
     # non-empty, a trainer that is given no data manager builds mvlpt_amd.data.DeviceDataManager from it.  On the command line as JSON.
     # SUBSAMPLE_CLASSES: all | base | new (train.py:117).

@@ -2894,6 +2894,51 @@ int mvlpt_nearest_tokens(void* h, const float* q, int R, int k, int32_t* idx, fl
   return nearest_run(E, "nearest_tokens", q, E->tok_emb, R, E->vocab, E->arch.text_width, k, idx, dist, E->near_ws.p, p, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------------------------------------ test-time prompt tuning head
+// Every limit of include/mvlpt_hip.h is checked here, before a launch: the kernels (tpt.hip) trust their arguments.
+static int tpt_check(const char* who, int G, int V, int C, int e, int k) {
+  const std::string w = std::string(who) + ": ";
+  if (G < 1 || G > MVLPT_TPT_MAX_GROUPS) return fail(nullptr, MVLPT_ERR_ARG, w + "G must lie in [1, MVLPT_TPT_MAX_GROUPS]");
+  if (V < 1 || V > MVLPT_TPT_MAX_VIEWS) return fail(nullptr, MVLPT_ERR_ARG, w + "V must lie in [1, MVLPT_TPT_MAX_VIEWS]");
+  if (C < 1 || C > MVLPT_TPT_MAX_CLASSES) return fail(nullptr, MVLPT_ERR_ARG, w + "C must lie in [1, MVLPT_TPT_MAX_CLASSES]");
+  if (e < 4 || e % 4 || e > 1024) return fail(nullptr, MVLPT_ERR_ARG, w + "e must be a multiple of 4 in [4, 1024]");
+  if (k < 1 || k > V) return fail(nullptr, MVLPT_ERR_ARG, w + "k must lie in [1, V]");
+  if ((int64_t)G * C >= ((int64_t)1 << 31)) return fail(nullptr, MVLPT_ERR_ARG, w + "G * C must stay below 2^31 (chunk the images)");
+  return 0;
+}
+static int tpt_ws_check(const char* who, const void* ws, int64_t have, size_t need) {
+  if (!ws || have < 0 || (uint64_t)have < need || ((uintptr_t)ws & 15) != 0)
+    return fail(nullptr, MVLPT_ERR_ARG, std::string(who) + ": the workspace is smaller than mvlpt_tpt_workspace_bytes (" +
+                                            std::to_string(need) + " bytes), or not 16-byte aligned");
+  return 0;
+}
+int mvlpt_tpt_workspace_bytes(int G, int V, int C, int e, int k, int64_t* bytes) {
+  if (!bytes) return fail(nullptr, MVLPT_ERR_ARG, "tpt_workspace_bytes: null argument");
+  if (int rc = tpt_check("tpt_workspace_bytes", G, V, C, e, k)) return rc;
+  *bytes = (int64_t)tpt_plan(G, V, C, e, k).ws_bytes;
+  return 0;
+}
+int mvlpt_op_tpt_head_fwd(const float* img, const float* txt, float scale, int G, int V, int C, int e, int k, float* loss, float* H,
+                          int32_t* sel, float* z, void* workspace, int64_t workspace_bytes, mvlpt_stream_t stream) {
+  if (!img || !txt || !loss || !H || !sel) return fail(nullptr, MVLPT_ERR_ARG, "op_tpt_head_fwd: null argument");
+  if (int rc = tpt_check("op_tpt_head_fwd", G, V, C, e, k)) return rc;
+  if ((((uintptr_t)img | (uintptr_t)txt) & 15) != 0) return fail(nullptr, MVLPT_ERR_ARG, "op_tpt_head_fwd: img and txt must be 16-byte aligned");
+  const TptPlan p = tpt_plan(G, V, C, e, k);
+  if (int rc = tpt_ws_check("op_tpt_head_fwd", workspace, workspace_bytes, p.ws_bytes)) return rc;
+  OPCHK(launch_tpt_head_fwd(img, txt, scale, G, V, C, e, k, loss, H, sel, z, workspace, p, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_tpt_head_bwd(const float* w, float scale, int G, int V, int C, int e, int k, float* dtxt, void* workspace,
+                          int64_t workspace_bytes, mvlpt_stream_t stream) {
+  if (!dtxt) return fail(nullptr, MVLPT_ERR_ARG, "op_tpt_head_bwd: null argument");
+  if (int rc = tpt_check("op_tpt_head_bwd", G, V, C, e, k)) return rc;
+  if (((uintptr_t)dtxt & 15) != 0) return fail(nullptr, MVLPT_ERR_ARG, "op_tpt_head_bwd: dtxt must be 16-byte aligned");
+  const TptPlan p = tpt_plan(G, V, C, e, k);
+  if (int rc = tpt_ws_check("op_tpt_head_bwd", workspace, workspace_bytes, p.ws_bytes)) return rc;
+  OPCHK(launch_tpt_head_bwd(w, scale, G, V, C, e, k, dtxt, workspace, p, (hipStream_t)stream));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ evaluation counts
 // Every limit of include/mvlpt_hip.h is checked here, before a launch (evaluate.hip).
 int mvlpt_op_eval_count(const float* logits, int64_t ld, int B, int C, const void* labels, int label_kind, int64_t label_ld,

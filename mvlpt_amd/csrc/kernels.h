@@ -452,6 +452,17 @@ NearestPlan nearest_plan(int R, int V, int k, int cus);
 hipError_t launch_nearest_rows(const float* q, const float* table, int R, int V, int d, int k, int32_t* idx, float* dist, void* ws,
                                const NearestPlan& p, hipStream_t s);
 
+// ---------------------------------------------------------------- test-time prompt tuning head (tpt.hip; semantics in include/mvlpt_hip.h)
+// Workspace layout of one call, a function of (G, V, C, e, k) alone; offsets in floats, every section on a 256-byte boundary: the
+// normalised image and text rows, |txt|, the views' softmax statistics (max, log sum), the selection, then logp, a and dz of the
+// selected views.  The arguments are checked by the caller (engine.hip).
+struct TptPlan { size_t off_imn = 0, off_tn = 0, off_nt = 0, off_m = 0, off_ls = 0, off_sel = 0, off_lp = 0, off_a = 0, off_dz = 0, ws_bytes = 0; };
+TptPlan tpt_plan(int G, int V, int C, int e, int k);
+hipError_t launch_tpt_head_fwd(const float* img, const float* txt, float scale, int G, int V, int C, int e, int k, float* loss, float* H,
+                               int32_t* sel, float* z, void* ws, const TptPlan& p, hipStream_t s);
+hipError_t launch_tpt_head_bwd(const float* w, float scale, int G, int V, int C, int e, int k, float* dtxt, void* ws, const TptPlan& p,
+                               hipStream_t s);
+
 // ---------------------------------------------------------------- softmax regression (softmax_reg.hip; semantics in include/mvlpt_hip.h)
 // Geometry and workspace layout of one call, a function of (N, D, K) alone: the logits / residuals Z [N, ldz] first (all that predict
 // needs: predict_bytes), then `slices` partial [K, D] gradients, their column sums, the loss partials of the row blocks and the

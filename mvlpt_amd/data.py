@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib, jpeg
-from .transforms import build_device_transform
+from .transforms import build_device_transform, build_view_transform
 
 SUPER_BATCH = 1024                   # files per mvlpt_jpeg_decode call while a resident set is filled
 MAX_WORKERS = 16
@@ -219,6 +219,7 @@ class DeviceLoader:
         self.workers = max(0, min(int(cfg.DATALOADER.NUM_WORKERS), MAX_WORKERS))
         self.epoch = 0
         self.engine = self.transform = self.image_set = None
+        self.n_views = 0          # > 0 (request_views): "img" is [B, n_views, 3, R, R], view 0 the test view (test-time prompt tuning)
         self._labels = torch.tensor([it.label for it in self.dataset], dtype=torch.int64)
         self._domains = torch.tensor([it.domain for it in self.dataset], dtype=torch.int64)
         self._pools: List[ThreadPoolExecutor] = []
@@ -229,8 +230,21 @@ class DeviceLoader:
 
     def bind(self, engine, image_set: Optional[ResidentImageSet] = None):
         self.engine, self.image_set = engine, image_set
+        if self.n_views > 0:
+            gen = torch.Generator().manual_seed(rank_seed(self.cfg.SEED, self.rank))
+            self.transform = build_view_transform(self.cfg, engine, self.n_views, generator=gen)
+            return
         gen = torch.Generator().manual_seed(rank_seed(self.cfg.SEED, self.rank)) if self.train else None
         self.transform = build_device_transform(self.cfg, engine, train=self.train, generator=gen)
+
+    def request_views(self, n_views: int) -> None:
+        """Serve `n_views` views per image from now on (mvlpt_amd.transforms.ViewTransform; 0: the plain batches again).  Evaluation
+        loaders only; a bound loader rebuilds its transform, with a freshly seeded generator."""
+        if self.train:
+            raise ValueError("views are served by the evaluation loaders (test-time prompt tuning), not by the train loader")
+        self.n_views = int(n_views)
+        if self.engine is not None:
+            self.bind(self.engine, self.image_set)
 
     def order(self, epoch: int) -> List[int]:
         """the item indices of `epoch`, in the order they are served"""
@@ -380,6 +394,12 @@ class DeviceDataManager:
                     budget -= need
             self.image_sets[name] = image_set
             loader.bind(engine, image_set)
+
+    def request_views(self, n_views: int) -> None:
+        """The val and test loaders serve `n_views` views per image (DeviceLoader.request_views); the train loader is untouched."""
+        for loader in (self.val_loader, self.test_loader):
+            if loader is not None:
+                loader.request_views(n_views)
 
     @property
     def resident_bytes(self) -> int:

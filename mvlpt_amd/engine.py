@@ -591,6 +591,50 @@ class Engine:
         return dimg, dtxt
 
     @_on_device
+    def tpt_head_fwd(self, img, txt, logit_scale_exp: float, k: int, want_logits: bool = False):
+        """The test-time prompt tuning head (mvlpt_op_tpt_head_fwd): img [G, V, e] views against txt [G*C, e] (rows of text_fwd_ranged
+        over full ranges) -> (loss [G], H [G, V], sel int32 [G, k]), and z [G, V, C] as a fourth value under `want_logits` (tests).
+        Device tensors, no host sync.  The workspace is the engine's own, grow-only; tpt_head_bwd reads it."""
+        self._tpt_state = None
+        img = _req(img, torch.float32, "img")
+        txt = _req(txt, torch.float32, "txt")
+        if img.dim() != 3 or txt.dim() != 2 or img.shape[2] != txt.shape[1]:
+            raise ValueError("tpt head: img must be [G, V, e] and txt [G*C, e]")
+        G, V, e = img.shape
+        if G == 0 or txt.shape[0] == 0 or txt.shape[0] % G:
+            raise ValueError(f"tpt head: {txt.shape[0]} text rows are not a whole number of classes for each of {G} images")
+        Cn, k = txt.shape[0] // G, int(k)
+        nb = C.c_int64()
+        _lib.check(lib.mvlpt_tpt_workspace_bytes(G, V, Cn, e, k, C.byref(nb)), None, "tpt_workspace_bytes")
+        ws = getattr(self, "_tpt_ws", None)
+        if ws is None or ws.numel() * 8 < nb.value or ws.device != img.device:
+            ws = self._tpt_ws = torch.empty((nb.value + 7) // 8, device=img.device, dtype=torch.int64)
+        loss = torch.empty(G, device=img.device, dtype=torch.float32)
+        H = torch.empty(G, V, device=img.device, dtype=torch.float32)
+        sel = torch.empty(G, k, device=img.device, dtype=torch.int32)
+        z = torch.empty(G, V, Cn, device=img.device, dtype=torch.float32) if want_logits else None
+        _lib.check(lib.mvlpt_op_tpt_head_fwd(_ptr(img), _ptr(txt), float(logit_scale_exp), G, V, Cn, e, k, _ptr(loss), _ptr(H), _ptr(sel),
+                                             _ptr(z), _ptr(ws), ws.numel() * 8, _stream()), None, "op_tpt_head_fwd")
+        self._tpt_state = (float(logit_scale_exp), G, V, Cn, e, k)
+        return (loss, H, sel, z) if want_logits else (loss, H, sel)
+
+    @_on_device
+    def tpt_head_bwd(self, weights=None) -> torch.Tensor:
+        """d (sum_g weights[g] * loss[g]) / d txt [G*C, e] of the last tpt_head_fwd (selection constant; weights None: all 1)."""
+        if getattr(self, "_tpt_state", None) is None:
+            raise RuntimeError("tpt_head_bwd without tpt_head_fwd")
+        scale, G, V, Cn, e, k = self._tpt_state
+        ws = self._tpt_ws
+        if weights is not None:
+            weights = _req(weights, torch.float32, "weights")
+            if weights.shape != (G,):
+                raise ValueError(f"tpt head: weights must be [{G}]")
+        dtxt = torch.empty(G * Cn, e, device=ws.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_op_tpt_head_bwd(_ptr(weights), scale, G, V, Cn, e, k, _ptr(dtxt), _ptr(ws), ws.numel() * 8, _stream()),
+                   None, "op_tpt_head_bwd")
+        return dtxt
+
+    @_on_device
     def cross_entropy(self, logits, label, need_grad: bool = True):
         """Returns (loss[1], dlogits or None, ncorrect[1]) — device tensors, no host sync."""
         logits = _req(logits, torch.float32, "logits")
@@ -824,6 +868,13 @@ def op_nearest_rows(q, table, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
         _lib.check(lib.mvlpt_op_nearest_rows(_ptr(q), _ptr(table), R, V, d, int(k), _ptr(idx), _ptr(dist), _ptr(ws), nb, _stream()), None,
                    "op_nearest_rows")
     return idx, dist
+
+
+def tpt_workspace_bytes(G: int, V: int, C_: int, e: int, k: int) -> int:
+    """Scratch bytes mvlpt_op_tpt_head_fwd / _bwd need for these sizes (mvlpt_tpt_workspace_bytes)."""
+    out = C.c_int64()
+    _lib.check(lib.mvlpt_tpt_workspace_bytes(int(G), int(V), int(C_), int(e), int(k), C.byref(out)), None, "tpt_workspace_bytes")
+    return int(out.value)
 
 
 def _pitched(t: torch.Tensor, name: str) -> torch.Tensor:

@@ -276,6 +276,89 @@ class DeviceTransform:
         return self._run(image_set.buf, descs, augs, want_u8)
 
 
+class ViewTransform:
+    """V views of every image in ONE preprocess launch (test-time prompt tuning, mvlpt_amd.tpt): [G, V, 3, size, size].
+    View 0 of an image carries the descriptor of `test` (a train=False DeviceTransform: Resize + CenterCrop), views 1 .. V-1 those of
+    `train` (a train=True one: random_resized_crop, random_flip and whatever INPUT.TRANSFORMS adds), drawn image after image from
+    `train`'s generator: the same state draws, for image i, what `train.describe_aug([shape_i] * (V - 1))` draws.  All V descriptors
+    of an image share one `offset`: the image lies in the source once (a resident set's buffer, one packed upload, or one device
+    decode), never V times.  With augmentations in `train` the launch is the augmenting one and view 0 gets an empty augmentation
+    descriptor (no colour operation, no grayscale, no hole)."""
+
+    def __init__(self, test: DeviceTransform, train: DeviceTransform, n_views: int):
+        if test.train or not train.train:
+            raise ValueError("ViewTransform(test, train): `test` must be a train=False transform and `train` a train=True one")
+        if (test.size, test.mean, test.std, test.out_dtype) != (train.size, train.mean, train.std, train.out_dtype):
+            raise ValueError("the test and train transforms of a ViewTransform must share size, mean / std (keep 'normalize' in "
+                             "INPUT.TRANSFORMS) and output type: the views are one launch")
+        if int(n_views) < 1:
+            raise ValueError(f"n_views must be at least 1, got {n_views}")
+        self.test, self.train, self.n_views = test, train, int(n_views)
+        self.engine, self.size = train.engine, train.size
+
+    def describe_views(self, shapes: Sequence[Tuple[int, int]], offsets: Sequence[int]):
+        """(image descriptors [G * V], augmentation descriptors [G * V] or None), image-major; `offsets` [G]: each image's place in
+        the source."""
+        V, G = self.n_views, len(shapes)
+        descs = (_lib.MvlptImageDesc * (G * V))()
+        augs = (_lib.MvlptAugmentDesc * (G * V))() if self.train.augments else None
+        for g, (shape, off) in enumerate(zip(shapes, offsets)):
+            d0, _, _ = self.test.describe_aug([shape])
+            descs[g * V] = d0[0]
+            if V > 1:
+                dt, at, _ = self.train.describe_aug([shape] * (V - 1))
+                for j in range(V - 1):
+                    descs[g * V + 1 + j] = dt[j]
+                    if augs is not None:
+                        augs[g * V + 1 + j] = at[j]
+            for j in range(V):
+                descs[g * V + j].offset = int(off)
+        return descs, augs
+
+    def _run(self, src, descs, augs):
+        tr = self.train
+        if augs is None and not tr.fill_outside:
+            out = self.engine.preprocess(src, descs, self.size, tr.mean, tr.std, tr.out_dtype, False)
+        else:
+            out = self.engine.preprocess_aug(src, descs, augs, self.size, tr.mean, tr.std, tr.out_dtype, False, tr.fill_outside)
+        return out.view(len(descs) // self.n_views, self.n_views, *out.shape[1:])
+
+    def from_resident(self, image_set, indices: Sequence[int]):
+        indices = [int(i) for i in indices]
+        descs, augs = self.describe_views([image_set.shapes[i] for i in indices], [image_set.offsets[i] for i in indices])
+        return self._run(image_set.buf, descs, augs)
+
+    def __call__(self, images: Sequence):
+        """Decoded uint8 HWC arrays: packed and uploaded once."""
+        shapes, offsets, off = [], [], 0
+        for im in images:
+            shapes.append((int(im.shape[0]), int(im.shape[1])))
+            offsets.append(off)
+            off += shapes[-1][0] * shapes[-1][1] * 3
+        descs, augs = self.describe_views(shapes, offsets)
+        tr = self.train
+        host, n = tr.pack(images)
+        src = host[:n].to(self.engine.device if hasattr(self.engine, "device") else "cuda", non_blocking=True)
+        if src.is_cuda:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(src.device))
+            tr._ring[tr._slot][1] = ev
+        return self._run(src, descs, augs)
+
+    def from_encoded(self, blobs: Sequence, check: bool = True, infos=None, decoded=None):
+        """JPEG files (bytes): ONE device decode of the batch (mvlpt_amd.jpeg.decode_batch), V descriptors pointing at each image."""
+        from . import jpeg
+        src, offsets, shapes, _ = jpeg.decode_batch(self.engine, blobs, check=check, infos=infos, decoded=decoded)
+        descs, augs = self.describe_views([tuple(s) for s in shapes], [int(o) for o in offsets])
+        return self._run(src, descs, augs)
+
+
+def build_view_transform(cfg, engine, n_views: int, generator: Optional[torch.Generator] = None) -> ViewTransform:
+    """The ViewTransform of INPUT.*: view 0 as Dassl's test transform, the others as its train transform."""
+    return ViewTransform(build_device_transform(cfg, engine, train=False), build_device_transform(cfg, engine, train=True, generator=generator),
+                         n_views)
+
+
 def build_device_transform(cfg, engine, train: bool = True, **kwargs) -> DeviceTransform:
     """The transform Dassl's `build_transform(cfg, is_train=train)` would build from INPUT.TRANSFORMS and its parameters (same key names
     and defaults), on the device.  Testing is Dassl's Resize(size) + CenterCrop(size) + normalize; the names are checked either way."""

@@ -13,10 +13,22 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+TRAINERS = ("MVLPT", "CoCoOp", "ZeroshotCLIP", "ZeroshotCLIP2", "TPT")
+EVAL_ONLY_TRAINERS = ("ZeroshotCLIP", "ZeroshotCLIP2", "TPT")         # nothing is trained: test() straight away
+
+
+def trainer_class(name: str):
+    """The trainer class of `--trainer name`."""
+    from mvlpt_amd.cocoop import CoCoOp
+    from mvlpt_amd.tpt import TPT
+    from mvlpt_amd.trainer import MVLPT
+    from mvlpt_amd.zsclip import ZeroshotCLIP, ZeroshotCLIP2
+    return {"MVLPT": MVLPT, "CoCoOp": CoCoOp, "ZeroshotCLIP": ZeroshotCLIP, "ZeroshotCLIP2": ZeroshotCLIP2, "TPT": TPT}[name]
+
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--trainer", default="MVLPT", choices=["MVLPT", "CoCoOp", "ZeroshotCLIP", "ZeroshotCLIP2"], help="name of trainer")
+    ap.add_argument("--trainer", default="MVLPT", choices=list(TRAINERS), help="name of trainer")
     ap.add_argument("--output-dir", default="", help="output directory")
     ap.add_argument("--seed", type=int, default=-1, help="only positive value enables a fixed seed")
     ap.add_argument("--eval-only", action="store_true", help="evaluation only")
@@ -29,10 +41,7 @@ def main():
 
     import torch
 
-    from mvlpt_amd.cocoop import CoCoOp
     from mvlpt_amd.config import get_cfg_default
-    from mvlpt_amd.trainer import MVLPT
-    from mvlpt_amd.zsclip import ZeroshotCLIP, ZeroshotCLIP2
 
     cfg = get_cfg_default()
     cfg.TRAINER.NAME = args.trainer
@@ -54,12 +63,11 @@ def main():
         except RuntimeError:
             sd = torch.load(args.clip_weights, map_location="cpu")
             sd = sd.get("state_dict", sd) if isinstance(sd, dict) else sd.state_dict()
-    cls = {"MVLPT": MVLPT, "CoCoOp": CoCoOp, "ZeroshotCLIP": ZeroshotCLIP, "ZeroshotCLIP2": ZeroshotCLIP2}[args.trainer]
-    trainer = cls(cfg, clip_state_dict=sd)
+    trainer = trainer_class(args.trainer)(cfg, clip_state_dict=sd)
     sets = getattr(trainer.dm, "image_sets", {})
     print("resident on the device: " + ", ".join(f"{k} {s.resident_bytes / 2 ** 20:.1f} MiB ({s.n_device} device, {s.n_host} host, "
                                                    f"{s.n_corrupt} corrupt)" if s is not None else f"{k} streams" for k, s in sets.items()))
-    if args.eval_only or args.trainer.startswith("Zeroshot"):
+    if args.eval_only or args.trainer in EVAL_ONLY_TRAINERS:
         trainer.load_model(args.model_dir, epoch=args.load_epoch)
         print(f"{cfg.TEST.SPLIT}: {trainer.test():.4f}  {trainer.last_task_results or ''}")
         return

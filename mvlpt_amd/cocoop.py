@@ -21,14 +21,9 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import _lib
-from .config import read_activation, read_vision_head_width
-# DEFAULT_MAX_TEXT_WORKSPACE_BYTES: workspace budget of the CoCoOp text tower (not a reference key).  A chunk is the largest number of
-# images whose text tower fits it (mvlpt_text_workspace_bytes); ViT-B/16 with 100 classes needs 1.67 GiB per image for a training step.
-from .model import (DEFAULT_MAX_TEXT_WORKSPACE_BYTES, MAX_SEQUENCES_PER_TOWER, FrozenCLIP, PretokenizedPrompts, _text_inputs,
-                    apply_text_act_ckpt, apply_text_grad_len, class_prompt_tables, image_conditioned_ctx, register_class_tables)
+from .model import FrozenCLIP, PretokenizedPrompts, class_prompt_tables, image_conditioned_ctx, register_class_tables
+from .per_image_text import PerImageTextCLIP
 from .trainer import MVLPT, TrainerX, refuse_wide_heads
-from .weights import get_arch, make_state_dict
 
 
 class PromptLearner(nn.Module):
@@ -68,28 +63,24 @@ class _CoCoOpLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(fctx, model: "CustomCLIP", img, ctx_shifted, label):
-        eng, pl = model.engine, model.prompt_learner
-        suffix, layout = _text_inputs(model, pl, pl.n_ctx)
+        eng = model.engine
         B = ctx_shifted.shape[0]
-        step = model.images_per_chunk(B, layout.shape[1], save_for_bwd=True)
-        apply_text_grad_len(model, pl)      # the backwards below stop behind the class table's largest EOT position
+        lo, hi = model.full_ranges(B)
+        chunks = model.chunks(lo, hi, model.text_len(ctx_shifted), save_for_bwd=True)
         dctx = torch.empty_like(ctx_shifted)
         loss = torch.zeros(1, device=ctx_shifted.device, dtype=torch.float32)
         ncorrect = torch.zeros(1, device=ctx_shifted.device, dtype=torch.float32)
-        for g0 in range(0, B, step):
-            g1 = min(B, g0 + step)
-            w = (g1 - g0) / B                                # the chunk's cross-entropy is a mean over its own images
-            lo, hi = [0] * (g1 - g0), [pl.n_cls] * (g1 - g0)  # every image against every class
-            txt = eng.text_fwd_ranged(pl.token_prefix, suffix, ctx_shifted[g0:g1], layout, pl.eot, lo, hi, save_for_bwd=True)
-            logits = eng.logits_ranged_fwd(img[g0:g1], txt, model.logit_scale_exp, lo, hi, pl.n_cls)
+        for g0, g1, _ in chunks:
+            logits = model.chunk_logits(img, ctx_shifted, lo, hi, g0, g1, save=True)
             lc, dl, nc = eng.cross_entropy(logits, label[g0:g1], need_grad=True)
             if g1 - g0 != B:
+                w = (g1 - g0) / B                            # the chunk's cross-entropy is a mean over its own images
                 dl.mul_(w)
                 lc = lc * w
             dctx[g0:g1] = eng.text_bwd(eng.logits_ranged_bwd(dl, need_img=False, need_txt=True)[1])
             loss += lc
             ncorrect += nc
-        model.last_chunks = -(-B // step)
+        model.last_chunks = len(chunks)
         model.last_ncorrect = ncorrect
         fctx.save_for_backward(dctx)
         return loss.squeeze(0)
@@ -100,39 +91,6 @@ class _CoCoOpLossFn(torch.autograd.Function):
         return None, None, dctx * g, None
 
 
-class PerImageTextCLIP(nn.Module):
-    """What the two models with per-image text features share (CustomCLIP below and mvlpt_amd.mvlpt_cocoop.CustomCLIP): the engine
-    side of the constructor and `interpret_images`.  A subclass sets `prompt_learner` first and provides `image_contexts`."""
-
-    def _init_engine_side(self, cfg, clip_model: FrozenCLIP) -> None:
-        self.tokenized_prompts = self.prompt_learner.tokenized_prompts
-        self.clip_model = clip_model
-        self.engine = clip_model.engine
-        self.text_act_ckpt = apply_text_act_ckpt(cfg, self.engine)      # TRAINER.ACT_CKPT: the chunk planner sees the smaller workspace
-        self.logit_scale = clip_model.logit_scale
-        self.logit_scale_exp = float(clip_model.logit_scale.exp())
-        self.dtype = clip_model.dtype
-        self.trim_text_to_eot = False        # mvlpt_amd.model.CustomCLIP's switch, same default
-        self.text_grad_to_eot = bool(cfg.TRAINER.MVLPT.get("TEXT_GRAD_TO_EOT", True))      # likewise
-        self.max_text_workspace_bytes = DEFAULT_MAX_TEXT_WORKSPACE_BYTES
-        # Precision (DESIGN.md §2): the image features are meta_net's input and every text row carries a gradient, so under the
-        # default mode (split operands only in towers kept for a backward) the ViT-B/16 fixture's ctx / meta_net gradients land at
-        # 0.9-1.3e-3 of the reference; with split operands in every tower (MVLPT_PREC_SPLIT_ALL) at <= 8.3e-4.  CoCoOp therefore
-        # raises the engine's default mode to split_all ("fast", an explicit request for single operands, is left alone).
-        # (An image tower with heads wider than 64 has single operands only: its mode stays split_grad, under which the text tower,
-        # which carries the gradient, runs on pairs all the same.)
-        if self.engine.precision == _lib.PREC_SPLIT_GRAD and getattr(clip_model.arch, "vision_head_width", 64) == 64:
-            self.engine.set_precision("split_all")
-        self.last_chunks = 0
-        self.last_ncorrect = None
-
-    def interpret_images(self, images, topk: int = 5):
-        """Nearest vocabulary words of every image's own contexts: [B][n_ctx] lists of (word, distance), B * n_ctx rows in ONE
-        nearest-token call (mvlpt_amd.interpret)."""
-        from .interpret import nearest_words
-        return nearest_words(self.clip_model, self.image_contexts(images), topk)
-
-
 class CustomCLIP(PerImageTextCLIP):
     """trainers/cocoop.py:164-194."""
 
@@ -140,33 +98,6 @@ class CustomCLIP(PerImageTextCLIP):
         super().__init__()
         self.prompt_learner = PromptLearner(cfg, classnames, clip_model, pretokenized)
         self._init_engine_side(cfg, clip_model)
-
-    def images_per_chunk(self, B: int, L: int, save_for_bwd: bool) -> int:
-        """Largest number of images (<= B) whose full-range text tower fits `max_text_workspace_bytes`; at least 1."""
-        C = self.prompt_learner.n_cls
-        lo, hi = 1, max(1, min(B, MAX_SEQUENCES_PER_TOWER // C))
-        while lo < hi:
-            mid = (lo + hi + 1) // 2
-            if self.engine.text_workspace_bytes(mid * C, L, save_for_bwd) <= self.max_text_workspace_bytes:
-                lo = mid
-            else:
-                hi = mid - 1
-        return lo
-
-    @torch.no_grad()
-    def _eval_logits(self, img, ctx_shifted):
-        eng, pl = self.engine, self.prompt_learner
-        suffix, layout = _text_inputs(self, pl, pl.n_ctx)
-        B = ctx_shifted.shape[0]
-        step = self.images_per_chunk(B, layout.shape[1], save_for_bwd=False)
-        out = torch.empty(B, pl.n_cls, device=img.device, dtype=torch.float32)
-        for g0 in range(0, B, step):
-            g1 = min(B, g0 + step)
-            lo, hi = [0] * (g1 - g0), [pl.n_cls] * (g1 - g0)
-            txt = eng.text_fwd_ranged(pl.token_prefix, suffix, ctx_shifted[g0:g1], layout, pl.eot, lo, hi, save_for_bwd=False)
-            out[g0:g1] = eng.logits_ranged_fwd(img[g0:g1], txt, self.logit_scale_exp, lo, hi, pl.n_cls)
-        self.last_chunks = -(-B // step)
-        return out
 
     @torch.no_grad()
     def image_contexts(self, image) -> torch.Tensor:
@@ -186,7 +117,7 @@ class CustomCLIP(PerImageTextCLIP):
             return _CoCoOpLossFn.apply(self, img, ctx_shifted, label)
         with torch.no_grad():
             ctx_shifted = self.prompt_learner(imf)
-        return self._eval_logits(img, ctx_shifted)
+        return self.ranged_logits(img, ctx_shifted, *self.full_ranges(image.shape[0]))
 
 
 class CoCoOp(MVLPT):
@@ -206,14 +137,9 @@ class CoCoOp(MVLPT):
         refuse_wide_heads(cfg, "CoCoOp")
         classnames = self.dm.dataset.classnames
         pretok = getattr(self.dm, "pretokenized", None)
-        sd = self._sd_arg
-        if sd is None:
-            sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED)
         # fp16 / amp / fp32 all end in split_all (CustomCLIP raises the default mode); GRAD_PRECISION = "fast" keeps single operands
         prec = "split_all" if cfg.TRAINER.COCOOP.PREC == "fp32" else cfg.TRAINER.MVLPT.GRAD_PRECISION
-        clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec,
-                                activation=read_activation(cfg), vision_head_width=read_vision_head_width(cfg))
-        self.model = CustomCLIP(cfg, classnames, clip_model, pretokenized=pretok)
+        self.model = CustomCLIP(cfg, classnames, MVLPT.frozen_clip(self, prec), pretokenized=pretok)
         self.train_prompt_learner_only()                                # :220-241
 
     def forward_backward(self, batch):

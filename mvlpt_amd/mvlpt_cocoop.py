@@ -29,15 +29,15 @@ sharding do not apply to per-image text features.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import Optional
 
 import torch
 import torch.nn as nn
 
-from .cocoop import MAX_SEQUENCES_PER_TOWER, PerImageTextCLIP
-from .model import (FrozenCLIP, PretokenizedPrompts, VisualPromptSide, _CrossEntropyFn, _text_inputs, apply_text_grad_len,
-                    class_prompt_tables, class_range_tables, deep_text_prompts, image_conditioned_ctx, register_class_tables)
+from .model import (FrozenCLIP, PretokenizedPrompts, VisualPromptSide, _CrossEntropyFn, class_prompt_tables, class_range_tables,
+                    deep_text_prompts, image_conditioned_ctx, register_class_tables)
 from .model import MultitaskVLPromptLearner as _BasePromptLearner
+from .per_image_text import PerImageTextCLIP, class_ranges
 from .schedule import check_forward_is_current
 
 
@@ -77,30 +77,6 @@ class MultitaskVLPromptLearner(_BasePromptLearner):
         return self.cocoop_ctx.unsqueeze(0) + bias           # (batch, n_ctx, ctx_dim)
 
 
-def class_ranges(task, start, end, B: int, n_cls: int) -> Tuple[List[int], List[int]]:
-    """Host class range [lo_b, hi_b) of every image: its task's range (`start` / `end` indexed by task id, trainers/mvlpt.py:575-576)
-    or [0, n_cls) without the per-task mask (`start is None`).  `task` stays on the CPU: nothing is read back from the device."""
-    if start is None:
-        return [0] * B, [n_cls] * B
-    t = task.cpu().long() if torch.is_tensor(task) else torch.as_tensor(task).long()
-    if t.shape != (B,):
-        raise ValueError(f"task must hold one task id per image ({B}), got shape {tuple(t.shape)}")
-    return start[t].tolist(), end[t].tolist()
-
-
-def chunk_bounds(widths: List[int], fits) -> List[Tuple[int, int, int]]:
-    """Cut the images into chunks of consecutive images (g0, g1, S): greedily the longest run whose sequence count S = sum of the
-    range widths satisfies `fits(S)`; a single image that does not fit still makes a chunk of its own.  S may be 0 (empty ranges only)."""
-    out, g0, S = [], 0, 0
-    for g, w in enumerate(widths):
-        if g > g0 and S + w > 0 and not fits(S + w):
-            out.append((g0, g, S))
-            g0, S = g, 0
-        S += w
-    out.append((g0, len(widths), S))
-    return out
-
-
 class _ImageTowerFn(torch.autograd.Function):
     """The image tower with visual prompts as an autograd node: mvlpt_image_fwd(save_for_bwd) / mvlpt_image_bwd."""
 
@@ -123,41 +99,28 @@ class _TextSideFn(torch.autograd.Function):
     full on the dense route) and the ranged head.  See the module docstring for the one-chunk / recompute arrangement of the backward."""
 
     @staticmethod
-    def _chunk_forward(model, img, ctx_shifted, lo, hi, g0, g1, save):
-        eng, pl = model.engine, model.prompt_learner
-        suffix, layout = _text_inputs(model, pl, pl.cocoop_n_ctx)
-        clo, chi = lo[g0:g1], hi[g0:g1]
-        if save:
-            apply_text_grad_len(model, pl)
-        txt = eng.text_fwd_ranged(pl.token_prefix, suffix, ctx_shifted[g0:g1], layout, pl.eot, clo, chi, save_for_bwd=save)
-        return eng.logits_ranged_fwd(img[g0:g1], txt, model.logit_scale_exp, clo, chi, pl.n_cls)
-
-    @staticmethod
     def forward(fctx, model: "CustomCLIP", img, ctx_shifted, lo, hi, mask, grad_on=True):
-        pl = model.prompt_learner
         need_img = grad_on and bool(fctx.needs_input_grad[1])
         need_ctx = grad_on and bool(fctx.needs_input_grad[2])
-        need = need_img or need_ctx
-        L = _text_inputs(model, pl, pl.cocoop_n_ctx)[1].shape[1]
-        chunks = model.chunks(lo, hi, L, save_for_bwd=need)
-        save = need and len(chunks) == 1
-        B = ctx_shifted.shape[0]
-        logits = torch.empty(B, pl.n_cls, device=img.device, dtype=torch.float32)
-        for g0, g1, S in chunks:
-            if S == 0:
-                logits[g0:g1] = 0.0
-            else:
-                logits[g0:g1] = _TextSideFn._chunk_forward(model, img, ctx_shifted, lo, hi, g0, g1, save)
-        if mask is not None:
-            logits = logits * mask                           # the dense route's select_index (trainers/mvlpt.py:581)
-        model.last_chunks, model.last_sequences = len(chunks), sum(c[2] for c in chunks)
-        model.last_recompute = need and len(chunks) > 1
-        fctx.model, fctx.lo, fctx.hi, fctx.chunks, fctx.mask = model, lo, hi, chunks, mask
-        fctx.need_img, fctx.need_ctx, fctx.saved_in_engine = need_img, need_ctx, save
-        fctx.generation = model._fwd_generation
-        if need:
+        model.last_sequences = sum(hi) - sum(lo)
+        if not (need_img or need_ctx):
+            logits = model.ranged_logits(img, ctx_shifted, lo, hi)
+            model.last_recompute = False
+        else:
+            chunks = model.chunks(lo, hi, model.text_len(ctx_shifted), save_for_bwd=True)
+            save = len(chunks) == 1                          # more than one chunk: the backward runs each chunk's forward again
+            logits = torch.empty(len(lo), model.prompt_learner.n_cls, device=img.device, dtype=torch.float32)
+            for g0, g1, S in chunks:
+                if S == 0:
+                    logits[g0:g1] = 0.0
+                else:
+                    logits[g0:g1] = model.chunk_logits(img, ctx_shifted, lo, hi, g0, g1, save)
+            model.last_chunks, model.last_recompute = len(chunks), not save
+            fctx.model, fctx.lo, fctx.hi, fctx.chunks, fctx.mask = model, lo, hi, chunks, mask
+            fctx.need_img, fctx.need_ctx, fctx.saved_in_engine = need_img, need_ctx, save
+            fctx.generation = model._fwd_generation
             fctx.save_for_backward(img, ctx_shifted)
-        return logits
+        return logits if mask is None else logits * mask     # the dense route's select_index (trainers/mvlpt.py:581)
 
     @staticmethod
     def backward(fctx, dlogits):
@@ -173,7 +136,7 @@ class _TextSideFn(torch.autograd.Function):
             if S == 0:
                 continue                                     # empty ranges only: no logit depends on anything
             if not fctx.saved_in_engine:                     # more than one chunk: this chunk's forward again, saved this time
-                _TextSideFn._chunk_forward(model, img, ctx_shifted, fctx.lo, fctx.hi, g0, g1, fctx.need_ctx)
+                model.chunk_logits(img, ctx_shifted, fctx.lo, fctx.hi, g0, g1, fctx.need_ctx)
             di, dtxt = eng.logits_ranged_bwd(dl[g0:g1], need_img=fctx.need_img, need_txt=fctx.need_ctx)
             if fctx.need_img:
                 dimg[g0:g1] = di
@@ -214,13 +177,6 @@ class CustomCLIP(VisualPromptSide, PerImageTextCLIP):
     def drop_prefetch(self) -> None:
         pass
 
-    # ---- chunking
-    def chunks(self, lo: List[int], hi: List[int], L: int, save_for_bwd: bool) -> List[Tuple[int, int, int]]:
-        """[(g0, g1, S)]: consecutive images whose text tower over S = sum(hi - lo) sequences fits `max_text_workspace_bytes`."""
-        eng, budget = self.engine, self.max_text_workspace_bytes
-        return chunk_bounds([b - a for a, b in zip(lo, hi)],
-                            lambda S: S <= MAX_SEQUENCES_PER_TOWER and eng.text_workspace_bytes(S, L, save_for_bwd) <= budget)
-
     def _image_side(self, image):
         """(image features [B, e], shifted contexts [B, n_ctx, ctx_dim]): the image tower with its visual prompts, then :561-563."""
         _, vpt_emb, vpt_emb_deep = self.projected_prompts(batch=image.shape[0])  # :541 (no COOP ctx: the parameters themselves)
@@ -255,7 +211,7 @@ class CustomCLIP(VisualPromptSide, PerImageTextCLIP):
         if not self.ranged_text and self.multi_task_label_pertask:
             idx = torch.arange(pl.n_cls).unsqueeze(0)
             mask = ((idx >= torch.tensor(lo).unsqueeze(1)) & (idx < torch.tensor(hi).unsqueeze(1))).float().to(image.device)
-            lo, hi = [0] * B, [pl.n_cls] * B
+            lo, hi = self.full_ranges(B)
         return _TextSideFn.apply(self, img, ctx_shifted, lo, hi, mask, torch.is_grad_enabled())
 
     def cross_entropy(self, logits, label):

@@ -21,11 +21,10 @@ from typing import Optional, Tuple
 import torch
 import torch.nn as nn
 
-from .cocoop import CustomCLIP as _CoCoOpCLIP, PerImageTextCLIP
-from .config import CfgNode, read_activation, read_vision_head_width
-from .model import FrozenCLIP, MultitaskVLPromptLearner, PretokenizedPrompts, _text_inputs, apply_text_grad_len
+from .config import CfgNode
+from .model import FrozenCLIP, MultitaskVLPromptLearner, PretokenizedPrompts
+from .per_image_text import PerImageTextCLIP
 from .trainer import MVLPT, TrainerX, build_optimizer
-from .weights import get_arch, make_state_dict
 
 MAX_VIEWS = 128              # MVLPT_TPT_MAX_VIEWS
 ADAMW_WEIGHT_DECAY = 0.01    # torch.optim.AdamW's default: the published code passes the learning rate alone
@@ -84,8 +83,6 @@ class _Contexts(nn.Module):
 class CustomCLIP(PerImageTextCLIP):
     """The model of the TPT trainer: `tune(views)` -> logits [G, n_cls]."""
 
-    images_per_chunk = _CoCoOpCLIP.images_per_chunk          # the text-workspace planner, shared with CoCoOp
-
     def __init__(self, cfg, classnames, clip_model: FrozenCLIP, pretokenized: Optional[PretokenizedPrompts] = None):
         super().__init__()
         self.n_views, self.k, self.steps, self.lr = tpt_settings(cfg)
@@ -116,22 +113,19 @@ class CustomCLIP(PerImageTextCLIP):
     def tune_step(self, feats: torch.Tensor, ctx: torch.Tensor):
         """One forward + backward over every image, chunk by chunk: (loss [G], H [G, V], sel [G, k], dctx [G, n_ctx, dt]) for the
         contexts `ctx` against the (fixed) view features `feats` [G, V, e].  Per-image losses are independent: chunking is exact."""
-        eng, pl = self.engine, self.prompt_learner
-        suffix, layout = _text_inputs(self, pl, pl.coop_n_ctx)
+        eng = self.engine
         G, V = feats.shape[0], feats.shape[1]
-        step = self.images_per_chunk(G, layout.shape[1], save_for_bwd=True)
-        apply_text_grad_len(self, pl)
+        lo, hi = self.full_ranges(G)
+        chunks = self.chunks(lo, hi, self.text_len(ctx), save_for_bwd=True)
         loss = torch.empty(G, device=feats.device, dtype=torch.float32)
         H = torch.empty(G, V, device=feats.device, dtype=torch.float32)
         sel = torch.empty(G, self.k, device=feats.device, dtype=torch.int32)
         dctx = torch.empty_like(ctx)
-        for g0 in range(0, G, step):
-            g1 = min(G, g0 + step)
-            lo, hi = [0] * (g1 - g0), [pl.n_cls] * (g1 - g0)
-            txt = eng.text_fwd_ranged(pl.token_prefix, suffix, ctx[g0:g1], layout, pl.eot, lo, hi, save_for_bwd=True)
+        for g0, g1, _ in chunks:
+            txt = self.text_chunk(ctx, lo, hi, g0, g1, save=True)
             loss[g0:g1], H[g0:g1], sel[g0:g1] = eng.tpt_head_fwd(feats[g0:g1], txt, self.logit_scale_exp, self.k)
             dctx[g0:g1] = eng.text_bwd(eng.tpt_head_bwd())
-        self.last_chunks = -(-G // step)
+        self.last_chunks = len(chunks)
         return loss, H, sel, dctx
 
     @torch.no_grad()
@@ -162,18 +156,11 @@ class CustomCLIP(PerImageTextCLIP):
                 holder.ctx.grad.copy_(dctx)
             optim.step()
             ctx = holder.ctx.data
-        # 4. classify view 0 with the tuned contexts
-        suffix, layout = _text_inputs(self, pl, pl.coop_n_ctx)
-        step = self.images_per_chunk(G, layout.shape[1], save_for_bwd=False)
-        out = torch.empty(G, pl.n_cls, device=views.device, dtype=torch.float32)
-        img0 = feats[:, 0].contiguous()
-        for g0 in range(0, G, step):
-            g1 = min(G, g0 + step)
-            lo, hi = [0] * (g1 - g0), [pl.n_cls] * (g1 - g0)
-            txt = eng.text_fwd_ranged(pl.token_prefix, suffix, ctx[g0:g1], layout, pl.eot, lo, hi, save_for_bwd=False)
-            out[g0:g1] = eng.logits_ranged_fwd(img0[g0:g1], txt, self.logit_scale_exp, lo, hi, pl.n_cls)
-        if self.steps == 0:
-            self.last_chunks = -(-G // step)
+        # 4. classify view 0 with the tuned contexts; the chunk count reported is the tuning steps' when there were any
+        tuning_chunks = self.last_chunks
+        out = self.ranged_logits(feats[:, 0].contiguous(), ctx, *self.full_ranges(G))
+        if self.steps != 0:
+            self.last_chunks = tuning_chunks
         self.last_ctx = ctx
         return out
 
@@ -199,13 +186,8 @@ class TPT(MVLPT):
         cfg = self.cfg
         classnames = self.dm.dataset.classnames if cfg.DATASET.COOP else list(self.dm.lab2cname.values())
         pretok = getattr(self.dm, "pretokenized", None)
-        sd = self._sd_arg
-        if sd is None:
-            sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED, include_token_embedding=True)
         prec = "split_all" if cfg.TRAINER.TPT.PREC == "fp32" else cfg.TRAINER.MVLPT.GRAD_PRECISION
-        clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec,
-                                activation=read_activation(cfg), vision_head_width=read_vision_head_width(cfg))
-        self.model = CustomCLIP(cfg, classnames, clip_model, pretokenized=pretok)
+        self.model = CustomCLIP(cfg, classnames, MVLPT.frozen_clip(self, prec, include_token_embedding=True), pretokenized=pretok)
         self.train_prompt_learner_only()        # freezes the rest, INIT_WEIGHTS, device; the optimizer it builds is never stepped
 
     def forward_backward(self, batch):

@@ -516,16 +516,24 @@ class MVLPT(TrainerX):
         self.num_classes, self.num_source_domains, self.lab2cname = dm.num_classes, dm.num_source_domains, dm.lab2cname
         self.dm = dm
 
+    def frozen_clip(self, precision: str, include_token_embedding: bool = False) -> FrozenCLIP:
+        """The frozen CLIP every trainer's model is built on: the state dict handed to the trainer, else synthetic weights.  The
+        build_models call it through the class, MVLPT.frozen_clip(self, ...): it reads `cfg`, `_sd_arg` and `device` alone, and the
+        host tests run build_model on a stand-in that has just those."""
+        cfg = self.cfg
+        sd = self._sd_arg
+        if sd is None:
+            # no network: synthetic frozen weights of the named architecture (clip/clip.py:57 would download)
+            sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED, include_token_embedding=include_token_embedding)
+        return FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=precision,
+                          activation=read_activation(cfg), vision_head_width=read_vision_head_width(cfg))
+
     def build_model(self):
         cfg = self.cfg
         refuse_wide_heads(cfg)
         classnames = self.dm.dataset.classnames if cfg.DATASET.COOP else list(self.dm.lab2cname.values())
         # token ids produced elsewhere (mvlpt_amd.class_prompts: reference-tokenizer tables for the BASELINE class lists)
         pretok = getattr(self.dm, "pretokenized", None)
-        sd = self._sd_arg
-        if sd is None:
-            # no network: synthetic frozen weights of the named architecture (clip/clip.py:57 would download)
-            sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED)
         # PREC (see check_cfg): fp16 / amp -> split operands only where gradients flow; fp32 -> in every tower;
         # GRAD_PRECISION = "fast" (not in the reference) drops the split operands altogether (gradients within ~4e-3)
         prec = "split_all" if cfg.TRAINER.MVLPT.PREC == "fp32" else cfg.TRAINER.MVLPT.GRAD_PRECISION
@@ -535,9 +543,7 @@ class MVLPT(TrainerX):
             from .mvlpt_cocoop import CustomCLIP as model_cls
             if cfg.TRAINER.MVLPT.COCOOP.PREC == "fp32":
                 prec = "split_all"
-        clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device, precision=prec,
-                                activation=read_activation(cfg), vision_head_width=read_vision_head_width(cfg))
-        self.model = model_cls(cfg, classnames, clip_model, dm=self.dm, pretokenized=pretok)
+        self.model = model_cls(cfg, classnames, MVLPT.frozen_clip(self, prec), dm=self.dm, pretokenized=pretok)
         self.model.prefetch_split = prefetch_split(cfg)
         self.train_prompt_learner_only()
 

@@ -19,10 +19,8 @@ from typing import List, Sequence
 
 import torch
 
-from .config import read_activation, read_vision_head_width
 from .model import FrozenCLIP
 from .trainer import MVLPT, TrainerX
-from .weights import get_arch, make_state_dict
 
 
 def build_prompts(templates: Sequence[str], classnames: Sequence[str]) -> List[str]:
@@ -55,12 +53,8 @@ class ZeroshotCLIP(MVLPT):
         cfg = self.cfg
         classnames = self.dm.dataset.classnames
         self.templates = read_templates(cfg, self.single_template)      # an instance attribute, rebuilt from the config every time
-        sd = self._sd_arg
-        if sd is None:
-            sd = make_state_dict(get_arch(cfg.MODEL.BACKBONE.NAME), seed=cfg.SEED, include_token_embedding=True)
-        clip_model = FrozenCLIP(sd, compute_dtype=cfg.TRAINER.MVLPT.COMPUTE_DTYPE, device=self.device,
-                                precision=cfg.TRAINER.MVLPT.GRAD_PRECISION,   # text tower: split operands unless "fast"
-                                activation=read_activation(cfg), vision_head_width=read_vision_head_width(cfg))
+        # text tower: split operands unless "fast"
+        clip_model: FrozenCLIP = MVLPT.frozen_clip(self, cfg.TRAINER.MVLPT.GRAD_PRECISION, include_token_embedding=True)
         prompts = build_prompts(self.templates, classnames)
         tokenized = clip_model.tokenizer.tokenize(prompts, clip_model.context_length)
         T, C = len(self.templates), len(classnames)

@@ -104,7 +104,7 @@ def test_full_fixture_tables():
 
 
 def test_class_ranges_and_chunks():
-    from mvlpt_amd.mvlpt_cocoop import chunk_bounds, class_ranges
+    from mvlpt_amd.per_image_text import chunk_bounds, class_ranges
     start, end = torch.arange(6), torch.arange(6)
     start[:3], end[:3] = torch.tensor([0, 2, 3]), torch.tensor([2, 3, 6])          # task_counts [2, 1, 3], sized num_classes
     for task, lo, hi in [([0, 1, 2], [0, 2, 3], [2, 3, 6]),                         # ordered

@@ -194,7 +194,8 @@ def test_two_builds_in_a_row_keep_the_template_count(monkeypatch):
             seen.append(tokenized.shape[0])
             return torch.zeros(tokenized.shape[0], 8)
 
-    monkeypatch.setattr(zsclip, "FrozenCLIP", _Clip)
+    from mvlpt_amd import trainer
+    monkeypatch.setattr(trainer, "FrozenCLIP", _Clip)      # MVLPT.frozen_clip: every trainer builds its frozen CLIP there
     templates = ["a photo of a {}.", "a drawing of a {}.", "{} texture."]
     cfg = _cfg(templates)
     tr = object.__new__(zsclip.ZeroshotCLIP2)

@@ -113,7 +113,7 @@ def main():
 
 
 def _ranges(model, task, B, ranged):
-    from mvlpt_amd.mvlpt_cocoop import class_ranges
+    from mvlpt_amd.per_image_text import class_ranges
     n = model.prompt_learner.n_cls
     if not ranged:
         return [0] * B, [n] * B

@@ -57,7 +57,7 @@ def main():
 
     from mvlpt_amd import _lib
     from mvlpt_amd.config import get_cfg_default
-    from mvlpt_amd.model import FrozenCLIP, _text_inputs, apply_text_grad_len
+    from mvlpt_amd.model import FrozenCLIP
     from mvlpt_amd.tpt import CustomCLIP
     from mvlpt_amd.weights import ARCHS, make_state_dict
 
@@ -100,26 +100,19 @@ def main():
                 if fused:
                     _, _, _, dctx = model.tune_step(feats, holder.ctx.data)
                 else:
-                    suffix, layout = _text_inputs(model, pl, pl.coop_n_ctx)
-                    step = model.images_per_chunk(G, layout.shape[1], save_for_bwd=True)
-                    apply_text_grad_len(model, pl)
+                    lo, hi = model.full_ranges(G)
+                    chunks = model.chunks(lo, hi, model.text_len(ctx), save_for_bwd=True)
                     dctx = torch.empty_like(ctx)
-                    for g0 in range(0, G, step):
-                        g1 = min(G, g0 + step)
-                        lo, hi = [0] * (g1 - g0), [C] * (g1 - g0)
-                        txt = eng.text_fwd_ranged(pl.token_prefix, suffix, holder.ctx.data[g0:g1], layout, pl.eot, lo, hi, save_for_bwd=True)
+                    for g0, g1, _ in chunks:
+                        txt = model.text_chunk(holder.ctx.data, lo, hi, g0, g1, save=True)
                         _, dtxt = stock_head(feats[g0:g1], txt, model.logit_scale_exp, K)
                         dctx[g0:g1] = eng.text_bwd(dtxt)
-                    model.last_chunks = -(-G // step)
+                    model.last_chunks = len(chunks)
                 holder.ctx.grad = dctx
                 optim.step()
-                suffix, layout = _text_inputs(model, pl, pl.coop_n_ctx)
-                step = model.images_per_chunk(G, layout.shape[1], save_for_bwd=False)
-                for g0 in range(0, G, step):
-                    g1 = min(G, g0 + step)
-                    lo, hi = [0] * (g1 - g0), [C] * (g1 - g0)
-                    txt = eng.text_fwd_ranged(pl.token_prefix, suffix, holder.ctx.data[g0:g1], layout, pl.eot, lo, hi, save_for_bwd=False)
-                    eng.logits_ranged_fwd(feats[g0:g1, 0].contiguous(), txt, model.logit_scale_exp, lo, hi, C)
+                tuning_chunks = model.last_chunks
+                model.ranged_logits(feats[:, 0].contiguous(), holder.ctx.data, *model.full_ranges(G))
+                model.last_chunks = tuning_chunks            # the row reports the tuning step's chunk count
 
             with torch.no_grad():
                 for fused in (True, False):              # warm-up: workspaces, allocator

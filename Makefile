@@ -3,7 +3,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := mvlpt_amd/csrc
 OBJDIR := build/obj
-SRCS  := $(CSRC)/gemm.hip $(CSRC)/norm.hip $(CSRC)/attention.hip $(CSRC)/attention_stream.hip $(CSRC)/attention_wide.hip $(CSRC)/attention32.hip $(CSRC)/glue.hip $(CSRC)/deep_text.hip $(CSRC)/activation.hip $(CSRC)/conv.hip $(CSRC)/optim.hip $(CSRC)/nearest.hip $(CSRC)/tpt.hip $(CSRC)/softmax_reg.hip $(CSRC)/evaluate.hip $(CSRC)/preprocess.hip $(CSRC)/jpeg.hip $(CSRC)/engine.hip
+SRCS  := $(CSRC)/gemm.hip $(CSRC)/norm.hip $(CSRC)/attention.hip $(CSRC)/attention_stream.hip $(CSRC)/attention_wide.hip $(CSRC)/attention32.hip $(CSRC)/glue.hip $(CSRC)/deep_text.hip $(CSRC)/activation.hip $(CSRC)/conv.hip $(CSRC)/optim.hip $(CSRC)/nearest.hip $(CSRC)/tpt.hip $(CSRC)/tip.hip $(CSRC)/softmax_reg.hip $(CSRC)/evaluate.hip $(CSRC)/preprocess.hip $(CSRC)/jpeg.hip $(CSRC)/engine.hip
 OBJS  := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS))
 # -target-feature -packed-fp32-ops: NO packed fp32 VALU instructions (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 / v_pk_mov_b32) in
 # the device code.  On gfx950 a packed fp32 op whose LOW lane selects the HIGH register of a source pair (op_sel) can read 0 in lanes

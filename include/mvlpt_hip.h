@@ -797,6 +797,51 @@ int mvlpt_op_softmax_reg_eval(const float* X, const int32_t* y, const float* the
 int mvlpt_op_softmax_reg_predict(const float* X, const float* theta, int N, int D, int K, int32_t* pred, float* margin, void* ws,
                                  size_t ws_bytes, mvlpt_stream_t stream);
 
+/* ---- Tip-Adapter / Tip-Adapter-F: the fused key-value cache head (row p of the scope table; tests/test_hip_tip.py) ----
+ * Replaces, per call of Tip-Adapter (Zhang et al., ECCV 2022), `exp(-beta (1 - F K^T)) @ one_hot`, its [N, NK] array and the sum with
+ * the zero-shot logits; for Tip-Adapter-F the cross-entropy and autograd back to the keys; for the hyper-parameter search the loop over
+ * the (beta, alpha) grid.  All fp32, row-major: F [N, D] unit image features, K [NK, D] the cache keys SORTED BY CLASS, key_ptr int32
+ * [C + 1] on the device (non-decreasing, key_ptr[0] = 0, key_ptr[C] = NK: class c owns the keys [key_ptr[c], key_ptr[c + 1])), W [C, D]
+ * unit text features, s = exp(logit_scale).  A class may own no key: its cache term is exactly alpha * 0.
+ *     z[n, c] = s <f_n, w_c> + alpha * sum_{j in c} A[n, j],   A[n, j] = exp(beta * (<f_n, k_j> - 1)).
+ *   mvlpt_op_tip_logits: logits [N, C] = z.  No [N, NK] array exists.
+ *   mvlpt_op_tip_train_fwd: with labels y int32 [N] on the device, each in [0, C): loss [1] = the mean cross-entropy of z, correct [1]
+ *     (int32) = the rows whose arg-max is y; logits [N, C] only when the pointer is not NULL.  The workspace keeps A [N, NK] and
+ *     r = (softmax(z) - onehot) / N for the backward.  The row statistics are formed in double from the fp32 logits, the loss partials
+ *     added in double in a fixed order.  C = 1 gives loss = 0 and r = 0 exactly.
+ *   mvlpt_op_tip_train_bwd: dK [NK, D] = alpha beta sum_n A[n, j] r[n, cls(j)] f_n; the factor A r is formed while the operand is staged,
+ *     no [N, NK] gradient array is written.  Only the keys carry a gradient.  It READS the workspace of its forward: same sizes, stream
+ *     and workspace, nothing else written to the workspace in between; it may be repeated.  alpha = 0 or beta = 0 gives dK = 0.
+ *   mvlpt_op_tip_search: betas [nb], alphas [na] on the device; counts int32 [nb, na] = the rows whose arg-max of z at (betas[b],
+ *     alphas[a]) is y.  The affinity product is formed once, not per grid point; one exponential per (affinity, beta); alpha enters in
+ *     the arg-max alone.  The workspace holds one row chunk of [C, nb + 1] floats per row (about 512 MiB at most, or one block of 128
+ *     rows); the chunks follow each other on the stream.  The logits of a grid point have the bits mvlpt_op_tip_logits gives there.
+ *   mvlpt_tip_workspace_bytes: the bytes an entry needs; mode MVLPT_TIP_LOGITS (0: nb and na ignored), MVLPT_TIP_TRAIN (nb and na
+ *     ignored) or MVLPT_TIP_SEARCH.
+ *   Arithmetic: products on the fp32-input matrix instruction.  The keys of a class are added one by one in ascending order; every sum
+ *     has an order fixed by the sizes and key_ptr alone, so two calls are bit-equal and a row's logits do not depend on the rows
+ *     around it.  Arg-max ties go to the lowest class.  No
+ *     floating-point atomics; the search counts are integer atomic adds.
+ *   Limits: 1 <= N, NK <= MVLPT_TIP_MAX_ROWS, 1 <= C <= MVLPT_TIP_MAX_CLASSES, D >= 4 with D % 4 == 0, N * C < 2^31, 1 <= nb <= MVLPT_TIP_MAX_NB,
+ *     1 <= na <= MVLPT_TIP_MAX_NA; F, K, W, dK and the workspace 16-byte aligned.  Every violation, a NULL required pointer and a
+ *     workspace below mvlpt_tip_workspace_bytes return MVLPT_ERR_ARG (message: mvlpt_last_error(NULL)) before anything is launched;
+ *     nothing is written.  key_ptr and y are trusted: the caller validates them on the host.  Handle-free, enqueue-only on `stream`. */
+enum { MVLPT_TIP_LOGITS = 0, MVLPT_TIP_TRAIN = 1, MVLPT_TIP_SEARCH = 2 };
+enum { MVLPT_TIP_MAX_NB = 256, MVLPT_TIP_MAX_NA = 32 };
+enum { MVLPT_TIP_MAX_CLASSES = 1 << 20 };
+enum { MVLPT_TIP_MAX_ROWS = 2147483392 };      /* 2^31 - 256: row and key counts are rounded up to whole tiles in 32 bits */
+int mvlpt_tip_workspace_bytes(int N, int NK, int C, int D, int nb, int na, int mode, int64_t* bytes);
+int mvlpt_op_tip_logits(const float* F, const float* K, const int32_t* key_ptr, const float* W, float s, float alpha, float beta, int N,
+                        int NK, int C, int D, float* logits, mvlpt_stream_t stream);
+int mvlpt_op_tip_train_fwd(const float* F, const int32_t* y, const float* K, const int32_t* key_ptr, const float* W, float s, float alpha,
+                           float beta, int N, int NK, int C, int D, float* loss, int32_t* correct, float* logits, void* workspace,
+                           int64_t workspace_bytes, mvlpt_stream_t stream);
+int mvlpt_op_tip_train_bwd(const float* F, float alpha, float beta, int N, int NK, int C, int D, float* dK, void* workspace,
+                           int64_t workspace_bytes, mvlpt_stream_t stream);
+int mvlpt_op_tip_search(const float* F, const int32_t* y, const float* K, const int32_t* key_ptr, const float* W, float s,
+                        const float* betas, const float* alphas, int N, int NK, int C, int D, int nb, int na, int32_t* counts,
+                        void* workspace, int64_t workspace_bytes, mvlpt_stream_t stream);
+
 /* ---- input pipeline ("next" row f3 of the scope table) -------------------------------------------------------
  * Replaces the per-image CPU transform the reference runs in DataLoader workers: Dassl `build_transform` with
  * INPUT.TRANSFORMS = random_resized_crop / random_flip / normalize, INTERPOLATION bicubic, CLIP PIXEL_MEAN/STD

@@ -27,6 +27,8 @@ ACT_OUT_SINGLE, ACT_OUT_PAIR, ACT_OUT_MIXED = 0, 1, 2    # MVLPT_ACT_OUT_*
 ERR_ARG, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED = -1, -2, -3, -4      # MVLPT_ERR_*
 NEAREST_MAX_K, NEAREST_MAX_ROWS = 64, 65535 * 8      # MVLPT_NEAREST_MAX_K, MVLPT_NEAREST_MAX_ROWS
 TPT_MAX_VIEWS, TPT_MAX_GROUPS, TPT_MAX_CLASSES = 128, 65535, 1 << 20      # MVLPT_TPT_MAX_*
+TIP_LOGITS, TIP_TRAIN, TIP_SEARCH = 0, 1, 2               # MVLPT_TIP_* modes of mvlpt_tip_workspace_bytes
+TIP_MAX_NB, TIP_MAX_NA, TIP_MAX_CLASSES, TIP_MAX_ROWS = 256, 32, 1 << 20, (1 << 31) - 256      # MVLPT_TIP_MAX_*
 EVAL_SORT_TILE, EVAL_MAX_ROWS, EVAL_POINTS, EVAL_FLAG_NONFINITE, EVAL_FLAG_SOFT_TARGET = 4096, 1 << 20, 11, 1, 2      # MVLPT_EVAL_*
 TEXT_MIN_L = 3     # MVLPT_TEXT_MIN_L: the smallest sequence length mvlpt_text_encode_tokens accepts
 
@@ -205,6 +207,11 @@ SIGNATURES = {
     "mvlpt_tpt_workspace_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(C.c_int64)]),
     "mvlpt_op_tpt_head_fwd": (_i, [_vp, _vp, _f, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
     "mvlpt_op_tpt_head_bwd": (_i, [_vp, _f, _i, _i, _i, _i, _i, _vp, _vp, C.c_int64, _vp]),
+    "mvlpt_tip_workspace_bytes": (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int64)]),
+    "mvlpt_op_tip_logits": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _i, _i, _vp, _vp]),
+    "mvlpt_op_tip_train_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _f, _f, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_int64, _vp]),
+    "mvlpt_op_tip_train_bwd": (_i, [_vp, _f, _f, _i, _i, _i, _i, _vp, _vp, C.c_int64, _vp]),
+    "mvlpt_op_tip_search": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_int64, _vp]),
     "mvlpt_op_eval_count": (_i, [_vp, C.c_int64, _i, _i, _vp, _i, C.c_int64, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                  _vp, _vp]),
     "mvlpt_op_eval_rank_columns": (_i, [_vp, C.c_int64, _i, _i, _vp, _i, C.c_int64, _vp, _i, C.POINTER(C.c_double), _vp, _vp, _vp, _vp, _vp,

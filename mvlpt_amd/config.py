@@ -158,6 +158,12 @@ def get_cfg_default() -> CfgNode:
     # own copy of the context minimise the entropy of their averaged prediction.  The context starts from TRAINER.MVLPT.COOP (N_CTX /
     # CTX_INIT / CLASS_TOKEN_POSITION, e.g. with a CoOp checkpoint) when COOP.N_CTX != 0, else from N_CTX / CTX_INIT here, class at the end.
     cfg.TRAINER.TPT = CN(N_VIEWS=64, SELECTION_P=0.1, STEPS=1, LR=5e-3, N_CTX=4, CTX_INIT="a photo of a", PREC="fp16")
+    # mvlpt_amd.tip_adapter (--trainer TipAdapter): Tip-Adapter (Zhang et al., ECCV 2022), zero-shot CLIP plus a key-value cache of the
+    # few-shot features, with the published names in upper case.  AUGMENT_EPOCH passes over the few-shot set build the cache; INIT_ALPHA /
+    # INIT_BETA hold until SEARCH_HP replaces them by the best point of the SEARCH_STEP grid over (0.1, SEARCH_SCALE) (beta first);
+    # FINETUNE: Tip-Adapter-F, TRAIN_EPOCH epochs of AdamW(LR, EPS) on the cache keys.  The text classifier is TRAINER.ZSCLIP's.
+    cfg.TRAINER.TIP = CN(AUGMENT_EPOCH=10, INIT_ALPHA=1.0, INIT_BETA=5.5, SEARCH_HP=True, SEARCH_SCALE=[7.0, 3.0], SEARCH_STEP=[200, 20],
+                         FINETUNE=False, TRAIN_EPOCH=20, LR=1e-3, EPS=1e-4)
     # SOURCES (not in the reference, which has one reader module per dataset): [task name, CoOp split file or "", image folder] per dataset;
     # non-empty, a trainer that is given no data manager builds mvlpt_amd.data.DeviceDataManager from it.  On the command line as JSON.
     # SUBSAMPLE_CLASSES: all | base | new (train.py:117).

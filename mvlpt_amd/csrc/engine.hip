@@ -3044,6 +3044,75 @@ int mvlpt_op_softmax_reg_predict(const float* X, const float* theta, int N, int 
   return 0;
 }
 
+// ------------------------------------------------------------------------------------------------ Tip-Adapter head
+// Every limit of include/mvlpt_hip.h is checked here, before a launch: the kernels (tip.hip) trust their arguments.
+static int tip_check(const char* who, int N, int NK, int C, int D, int nb, int na, int mode) {
+  const std::string w = std::string(who) + ": ";
+  if (mode != MVLPT_TIP_LOGITS && mode != MVLPT_TIP_TRAIN && mode != MVLPT_TIP_SEARCH) return fail(nullptr, MVLPT_ERR_ARG, w + "unknown mode");
+  if (N < 1 || NK < 1 || N > MVLPT_TIP_MAX_ROWS || NK > MVLPT_TIP_MAX_ROWS)
+    return fail(nullptr, MVLPT_ERR_ARG, w + "N and NK must lie in [1, MVLPT_TIP_MAX_ROWS]");
+  if (C < 1 || C > MVLPT_TIP_MAX_CLASSES) return fail(nullptr, MVLPT_ERR_ARG, w + "C must lie in [1, MVLPT_TIP_MAX_CLASSES]");
+  if (D < 4 || D % 4) return fail(nullptr, MVLPT_ERR_ARG, w + "D must be a multiple of 4, at least 4");
+  if ((int64_t)N * C >= ((int64_t)1 << 31)) return fail(nullptr, MVLPT_ERR_ARG, w + "N * C must stay below 2^31 (chunk the rows)");
+  if (mode == MVLPT_TIP_SEARCH) {
+    if (nb < 1 || nb > MVLPT_TIP_MAX_NB) return fail(nullptr, MVLPT_ERR_ARG, w + "nb must lie in [1, MVLPT_TIP_MAX_NB]");
+    if (na < 1 || na > MVLPT_TIP_MAX_NA) return fail(nullptr, MVLPT_ERR_ARG, w + "na must lie in [1, MVLPT_TIP_MAX_NA]");
+  }
+  return 0;
+}
+static int tip_ws_check(const char* who, const void* ws, int64_t have, size_t need) {
+  if (!ws || have < 0 || (uint64_t)have < need || ((uintptr_t)ws & 15) != 0)
+    return fail(nullptr, MVLPT_ERR_ARG, std::string(who) + ": the workspace is smaller than mvlpt_tip_workspace_bytes (" +
+                                            std::to_string(need) + " bytes), or not 16-byte aligned");
+  return 0;
+}
+int mvlpt_tip_workspace_bytes(int N, int NK, int C, int D, int nb, int na, int mode, int64_t* bytes) {
+  if (!bytes) return fail(nullptr, MVLPT_ERR_ARG, "tip_workspace_bytes: null argument");
+  if (int rc = tip_check("tip_workspace_bytes", N, NK, C, D, nb, na, mode)) return rc;
+  *bytes = (int64_t)tip_plan(N, NK, C, D, nb, na, mode).ws_bytes;
+  return 0;
+}
+int mvlpt_op_tip_logits(const float* F, const float* K, const int32_t* key_ptr, const float* W, float s, float alpha, float beta, int N,
+                        int NK, int C, int D, float* logits, mvlpt_stream_t stream) {
+  if (!F || !K || !key_ptr || !W || !logits) return fail(nullptr, MVLPT_ERR_ARG, "op_tip_logits: null argument");
+  if (int rc = tip_check("op_tip_logits", N, NK, C, D, 0, 0, MVLPT_TIP_LOGITS)) return rc;
+  if ((((uintptr_t)F | (uintptr_t)K | (uintptr_t)W) & 15) != 0) return fail(nullptr, MVLPT_ERR_ARG, "op_tip_logits: F, K and W must be 16-byte aligned");
+  OPCHK(launch_tip_logits(F, K, key_ptr, W, s, alpha, beta, N, NK, C, D, logits, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_tip_train_fwd(const float* F, const int32_t* y, const float* K, const int32_t* key_ptr, const float* W, float s, float alpha,
+                           float beta, int N, int NK, int C, int D, float* loss, int32_t* correct, float* logits, void* workspace,
+                           int64_t workspace_bytes, mvlpt_stream_t stream) {
+  if (!F || !y || !K || !key_ptr || !W || !loss || !correct) return fail(nullptr, MVLPT_ERR_ARG, "op_tip_train_fwd: null argument");
+  if (int rc = tip_check("op_tip_train_fwd", N, NK, C, D, 0, 0, MVLPT_TIP_TRAIN)) return rc;
+  if ((((uintptr_t)F | (uintptr_t)K | (uintptr_t)W) & 15) != 0) return fail(nullptr, MVLPT_ERR_ARG, "op_tip_train_fwd: F, K and W must be 16-byte aligned");
+  const TipPlan p = tip_plan(N, NK, C, D, 0, 0, MVLPT_TIP_TRAIN);
+  if (int rc = tip_ws_check("op_tip_train_fwd", workspace, workspace_bytes, p.ws_bytes)) return rc;
+  OPCHK(launch_tip_train_fwd(F, y, K, key_ptr, W, s, alpha, beta, N, NK, C, D, loss, correct, logits, workspace, p, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_tip_train_bwd(const float* F, float alpha, float beta, int N, int NK, int C, int D, float* dK, void* workspace,
+                           int64_t workspace_bytes, mvlpt_stream_t stream) {
+  if (!F || !dK) return fail(nullptr, MVLPT_ERR_ARG, "op_tip_train_bwd: null argument");
+  if (int rc = tip_check("op_tip_train_bwd", N, NK, C, D, 0, 0, MVLPT_TIP_TRAIN)) return rc;
+  if ((((uintptr_t)F | (uintptr_t)dK) & 15) != 0) return fail(nullptr, MVLPT_ERR_ARG, "op_tip_train_bwd: F and dK must be 16-byte aligned");
+  const TipPlan p = tip_plan(N, NK, C, D, 0, 0, MVLPT_TIP_TRAIN);
+  if (int rc = tip_ws_check("op_tip_train_bwd", workspace, workspace_bytes, p.ws_bytes)) return rc;
+  OPCHK(launch_tip_train_bwd(F, alpha, beta, N, NK, C, D, dK, workspace, p, (hipStream_t)stream));
+  return 0;
+}
+int mvlpt_op_tip_search(const float* F, const int32_t* y, const float* K, const int32_t* key_ptr, const float* W, float s,
+                        const float* betas, const float* alphas, int N, int NK, int C, int D, int nb, int na, int32_t* counts,
+                        void* workspace, int64_t workspace_bytes, mvlpt_stream_t stream) {
+  if (!F || !y || !K || !key_ptr || !W || !betas || !alphas || !counts) return fail(nullptr, MVLPT_ERR_ARG, "op_tip_search: null argument");
+  if (int rc = tip_check("op_tip_search", N, NK, C, D, nb, na, MVLPT_TIP_SEARCH)) return rc;
+  if ((((uintptr_t)F | (uintptr_t)K | (uintptr_t)W) & 15) != 0) return fail(nullptr, MVLPT_ERR_ARG, "op_tip_search: F, K and W must be 16-byte aligned");
+  const TipPlan p = tip_plan(N, NK, C, D, nb, na, MVLPT_TIP_SEARCH);
+  if (int rc = tip_ws_check("op_tip_search", workspace, workspace_bytes, p.ws_bytes)) return rc;
+  OPCHK(launch_tip_search(F, y, K, key_ptr, W, s, betas, alphas, N, NK, C, D, nb, na, counts, workspace, p, (hipStream_t)stream));
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------------ input pipeline
 // One pass over a batch's descriptors for the entry `who`: every box inside its image, every image inside src, and the output window
 // inside the resized image, or, under fill_outside, merely near enough to it for 32-bit arithmetic; `why` is the entry's wording of

@@ -478,6 +478,28 @@ hipError_t launch_softmax_reg_eval(const float* X, const int32_t* y, const float
 hipError_t launch_softmax_reg_predict(const float* X, const float* theta, int N, int D, int K, int32_t* pred, float* margin, void* ws,
                                       const SoftmaxRegPlan& p, hipStream_t s);
 
+// ---------------------------------------------------------------- Tip-Adapter head (tip.hip; semantics in include/mvlpt_hip.h)
+// Workspace layout of one call, a function of the sizes and the mode alone (byte offsets, sections on 256-byte boundaries).
+// MVLPT_TIP_TRAIN: the keys' classes, A^T [NK, ldn], R^T [C, ldn], the logits [N, C] (unused when the caller takes them), the loss and
+// hit partials of the row blocks.  MVLPT_TIP_SEARCH: clip [C, chunk_rows] and cache [C, nb, chunk_rows] of one row chunk; the chunk is
+// a whole number of row blocks of TIP_ROWS.  MVLPT_TIP_LOGITS needs none.  The arguments are checked by the caller (engine.hip).
+constexpr int TIP_ROWS = 128;
+struct TipPlan {
+  int ldn = 0, row_blocks = 0, chunk_rows = 0;
+  size_t off_cls = 0, off_at = 0, off_rt = 0, off_z = 0, off_lossp = 0, off_corrp = 0, off_clip = 0, off_cache = 0, ws_bytes = 0;
+};
+TipPlan tip_plan(int N, int NK, int C, int D, int nb, int na, int mode);
+hipError_t launch_tip_logits(const float* F, const float* K, const int32_t* key_ptr, const float* W, float s, float alpha, float beta,
+                             int N, int NK, int C, int D, float* logits, hipStream_t st);
+hipError_t launch_tip_train_fwd(const float* F, const int32_t* y, const float* K, const int32_t* key_ptr, const float* W, float s,
+                                float alpha, float beta, int N, int NK, int C, int D, float* loss, int32_t* correct, float* logits,
+                                void* ws, const TipPlan& p, hipStream_t st);
+hipError_t launch_tip_train_bwd(const float* F, float alpha, float beta, int N, int NK, int C, int D, float* dK, void* ws,
+                                const TipPlan& p, hipStream_t st);
+hipError_t launch_tip_search(const float* F, const int32_t* y, const float* K, const int32_t* key_ptr, const float* W, float s,
+                             const float* betas, const float* alphas, int N, int NK, int C, int D, int nb, int na, int32_t* counts,
+                             void* ws, const TipPlan& p, hipStream_t st);
+
 // ---------------------------------------------------------------- evaluation counts (evaluate.hip; semantics in include/mvlpt_hip.h)
 // The arguments are checked by the caller (engine.hip); row indices, task ids, ranges and labels that lie outside their extents are
 // clamped or skipped by the kernels, never dereferenced.

@@ -272,6 +272,20 @@ class DeviceLoader:
         batches = self._index_batches(epoch)
         return self._resident(batches) if self.image_set is not None else self._stream(batches)
 
+    def ordered(self):
+        """Every item once, in dataset order, the last batch partial, through THIS loader's transform: a train loader's augmentation
+        parameters go on from its generator, so every pass draws them afresh.  The pass a feature cache is built from (Tip-Adapter's
+        build_cache_model reads its few-shot set with shuffle=False under the train transform).  It is not an epoch: `epoch` and the
+        permutations of `__iter__` stay where they are.  len(self.ordered_batches()) batches."""
+        if self.transform is None:
+            raise RuntimeError("this loader is not bound to an engine yet: call dm.bind(engine) before iterating it")
+        batches = self.ordered_batches()
+        return self._resident(batches) if self.image_set is not None else self._stream(batches)
+
+    def ordered_batches(self) -> List[List[int]]:
+        n, B = len(self.dataset), self.batch_size
+        return [list(range(k, min(k + B, n))) for k in range(0, n, B)]
+
     def _resident(self, batches):
         for idx in batches:
             yield self._batch(idx, self.transform.from_resident(self.image_set, idx))

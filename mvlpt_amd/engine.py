@@ -634,6 +634,82 @@ class Engine:
                    None, "op_tpt_head_bwd")
         return dtxt
 
+    # ---- Tip-Adapter head (mvlpt_op_tip_*): F [N, D] unit features, K [NK, D] keys sorted by class, key_ptr int32 [C + 1], W [C, D]
+    def _tip_args(self, F, K, key_ptr, W):
+        F, K, W = _req(F, torch.float32, "F"), _req(K, torch.float32, "K"), _req(W, torch.float32, "W")
+        key_ptr = _req(key_ptr, torch.int32, "key_ptr")
+        if F.dim() != 2 or K.dim() != 2 or W.dim() != 2 or K.shape[1] != F.shape[1] or W.shape[1] != F.shape[1]:
+            raise ValueError("tip head: F must be [N, D], K [NK, D] and W [C, D]")
+        if key_ptr.shape != (W.shape[0] + 1,):
+            raise ValueError(f"tip head: key_ptr must be [{W.shape[0] + 1}]")
+        return F, K, key_ptr, W, (F.shape[0], K.shape[0], W.shape[0], F.shape[1])
+
+    def _tip_workspace(self, N, NK, Cn, D, nb, na, mode, device):
+        need = C.c_int64()
+        _lib.check(lib.mvlpt_tip_workspace_bytes(N, NK, Cn, D, nb, na, mode, C.byref(need)), None, "tip_workspace_bytes")
+        ws = getattr(self, "_tip_ws", None)
+        if ws is None or ws.numel() * 8 < need.value or ws.device != device:
+            ws = self._tip_ws = torch.empty((need.value + 7) // 8, device=device, dtype=torch.int64)
+        return ws
+
+    @_on_device
+    def tip_logits(self, F, K, key_ptr, W, logit_scale_exp: float, alpha: float, beta: float) -> torch.Tensor:
+        """logits [N, C] = s F W^T + alpha * (per-class sums of exp(-beta (1 - F K^T))) (mvlpt_op_tip_logits).  No host sync."""
+        F, K, key_ptr, W, (N, NK, Cn, D) = self._tip_args(F, K, key_ptr, W)
+        logits = torch.empty(N, Cn, device=F.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_op_tip_logits(_ptr(F), _ptr(K), _ptr(key_ptr), _ptr(W), float(logit_scale_exp), float(alpha), float(beta),
+                                           N, NK, Cn, D, _ptr(logits), _stream()), None, "op_tip_logits")
+        return logits
+
+    @_on_device
+    def tip_train_fwd(self, F, y, K, key_ptr, W, logit_scale_exp: float, alpha: float, beta: float, want_logits: bool = False):
+        """(loss [1], correct int32 [1]) of the Tip-Adapter-F step, and the logits [N, C] as a third value under `want_logits`
+        (mvlpt_op_tip_train_fwd).  The workspace is the engine's own, grow-only; tip_train_bwd reads it."""
+        self._tip_state = None
+        F, K, key_ptr, W, (N, NK, Cn, D) = self._tip_args(F, K, key_ptr, W)
+        y = _req(y, torch.int32, "y")
+        if y.shape != (N,):
+            raise ValueError(f"tip head: y must be [{N}]")
+        ws = self._tip_workspace(N, NK, Cn, D, 0, 0, _lib.TIP_TRAIN, F.device)
+        loss = torch.empty(1, device=F.device, dtype=torch.float32)
+        correct = torch.empty(1, device=F.device, dtype=torch.int32)
+        logits = torch.empty(N, Cn, device=F.device, dtype=torch.float32) if want_logits else None
+        _lib.check(lib.mvlpt_op_tip_train_fwd(_ptr(F), _ptr(y), _ptr(K), _ptr(key_ptr), _ptr(W), float(logit_scale_exp), float(alpha),
+                                              float(beta), N, NK, Cn, D, _ptr(loss), _ptr(correct), _ptr(logits), _ptr(ws),
+                                              ws.numel() * 8, _stream()), None, "op_tip_train_fwd")
+        self._tip_state = (F, float(alpha), float(beta), N, NK, Cn, D)
+        return (loss, correct, logits) if want_logits else (loss, correct)
+
+    @_on_device
+    def tip_train_bwd(self) -> torch.Tensor:
+        """d loss / d K [NK, D] of the last tip_train_fwd."""
+        if getattr(self, "_tip_state", None) is None:
+            raise RuntimeError("tip_train_bwd without tip_train_fwd")
+        F, alpha, beta, N, NK, Cn, D = self._tip_state
+        ws = self._tip_ws
+        dK = torch.empty(NK, D, device=F.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_op_tip_train_bwd(_ptr(F), alpha, beta, N, NK, Cn, D, _ptr(dK), _ptr(ws), ws.numel() * 8, _stream()),
+                   None, "op_tip_train_bwd")
+        return dK
+
+    @_on_device
+    def tip_search(self, F, y, K, key_ptr, W, logit_scale_exp: float, betas, alphas) -> torch.Tensor:
+        """counts int32 [nb, na]: the rows whose arg-max at (betas[b], alphas[a]) is y (mvlpt_op_tip_search).  It uses the workspace
+        of the train entries: a tip_train_fwd before it can no longer be followed by tip_train_bwd."""
+        self._tip_state = None
+        F, K, key_ptr, W, (N, NK, Cn, D) = self._tip_args(F, K, key_ptr, W)
+        y = _req(y, torch.int32, "y")
+        betas, alphas = _req(betas, torch.float32, "betas"), _req(alphas, torch.float32, "alphas")
+        if y.shape != (N,) or betas.dim() != 1 or alphas.dim() != 1:
+            raise ValueError(f"tip head: y must be [{N}], betas and alphas vectors")
+        nb, na = betas.shape[0], alphas.shape[0]
+        ws = self._tip_workspace(N, NK, Cn, D, nb, na, _lib.TIP_SEARCH, F.device)
+        counts = torch.empty(nb, na, device=F.device, dtype=torch.int32)
+        _lib.check(lib.mvlpt_op_tip_search(_ptr(F), _ptr(y), _ptr(K), _ptr(key_ptr), _ptr(W), float(logit_scale_exp), _ptr(betas),
+                                           _ptr(alphas), N, NK, Cn, D, nb, na, _ptr(counts), _ptr(ws), ws.numel() * 8, _stream()),
+                   None, "op_tip_search")
+        return counts
+
     @_on_device
     def cross_entropy(self, logits, label, need_grad: bool = True):
         """Returns (loss[1], dlogits or None, ncorrect[1]) — device tensors, no host sync."""

@@ -13,17 +13,19 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-TRAINERS = ("MVLPT", "CoCoOp", "ZeroshotCLIP", "ZeroshotCLIP2", "TPT")
+TRAINERS = ("MVLPT", "CoCoOp", "ZeroshotCLIP", "ZeroshotCLIP2", "TPT", "TipAdapter")
 EVAL_ONLY_TRAINERS = ("ZeroshotCLIP", "ZeroshotCLIP2", "TPT")         # nothing is trained: test() straight away
 
 
 def trainer_class(name: str):
     """The trainer class of `--trainer name`."""
     from mvlpt_amd.cocoop import CoCoOp
+    from mvlpt_amd.tip_adapter import TipAdapter
     from mvlpt_amd.tpt import TPT
     from mvlpt_amd.trainer import MVLPT
     from mvlpt_amd.zsclip import ZeroshotCLIP, ZeroshotCLIP2
-    return {"MVLPT": MVLPT, "CoCoOp": CoCoOp, "ZeroshotCLIP": ZeroshotCLIP, "ZeroshotCLIP2": ZeroshotCLIP2, "TPT": TPT}[name]
+    return {"MVLPT": MVLPT, "CoCoOp": CoCoOp, "ZeroshotCLIP": ZeroshotCLIP, "ZeroshotCLIP2": ZeroshotCLIP2, "TPT": TPT,
+            "TipAdapter": TipAdapter}[name]
 
 
 def main():

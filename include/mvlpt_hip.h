@@ -184,7 +184,7 @@ int mvlpt_frozen_ready(void* handle);
  *   - the masks of mvlpt_set_vpt_dropout: from the mvlpt_image_fwd (or _begin) that takes them over until its last mvlpt_image_bwd
  *     has been enqueued;
  *   - vpt_deep (and vpt, and the masks) of mvlpt_image_fwd_begin: until mvlpt_image_fwd_resume has been enqueued;
- *   - ctx_deep of mvlpt_text_fwd_deep with save_for_bwd: until its last mvlpt_text_bwd_deep has been enqueued;
+ *   - ctx_deep of a saving mvlpt_text_fwd: until its last mvlpt_text_bwd has been enqueued;
  *   - task_lo / task_hi of mvlpt_logits_fwd: until the last mvlpt_logits_bwd of that forward has been enqueued.
  * The class ranges of the ranged entries are host arrays, copied by the call. */
 
@@ -208,53 +208,60 @@ int mvlpt_image_fwd_abandon(void* handle);
  * (sum over the batch: prompts are `expand`ed, :75,:424).  Must follow image_fwd(save_for_bwd=1), same B. */
 int mvlpt_image_bwd(void* handle, const float* dfeat, float* dvpt, float* dvpt_deep, mvlpt_stream_t stream);
 
-/* forward_coop + TextEncoder.forward (trainers/mvlpt.py:439-515, 105-130).
- * prefix [C,1,dt], suffix [C,L-1-n_ctx,dt] fp32 (the `token_prefix` / `token_suffix` buffers, :312-316);
- * ctx [n_ctx,dt] (ctx_per_class=0) or [C,n_ctx,dt] (CSC, ctx_per_class=1) fp32, NULL when n_ctx == 0;
- * layout int32 [C,L]: source row per position — 0 = prefix, e>0 = suffix row e-1, e<0 = ctx row -e-1
- * (encodes the end/middle/front layouts); eot int32 [C] = argmax of tokenized_prompts (:128).
- * L <= context_length (CUT_CONTEXTLEN gives L < 77, :111-117).  feat_out [C,embed] fp32. */
-int mvlpt_text_fwd(void* handle, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
-                   const int32_t* layout, const int32_t* eot, int C, int L, float* feat_out, int save_for_bwd,
-                   mvlpt_stream_t stream);
-/* Image-conditioned prompts: one context block per image, ctx [G,n_ctx,dt] fp32 (ctx + meta_net(image g)), against the class tables of
- * mvlpt_text_fwd (prefix [C,1,dt], suffix [C,L-1-n_ctx,dt], layout int32 [C,L], eot int32 [C]), which are read through the ranges,
- * never copied, as ONE tower.  The MVLPT trainer's CoCoOp branch under MULTITASK_LABEL_PERTASK (trainers/mvlpt.py:556-581): image g
- * keeps only the logits of its own task's class range, so only those sequences run.  Group g owns classes [class_lo[g], class_hi[g]),
- * 0 <= lo <= hi <= C (an empty range is legal, not all of them); its sequences are those classes in order, each class c's prefix /
- * suffix / layout row / eot with context block g, the groups follow one another: S = sum_g (hi - lo) sequences, feat_out [S,embed] fp32.
- * class_lo / class_hi are HOST int32 [G] arrays (the task of an image is known on the host before the step); they are checked and
- * uploaded with the call, which stays enqueue-only.  G <= 65535, S * L inside int32.
- * Every range [0, C) is CoCoOp's tower, PromptLearner.forward + one TextEncoder call per image (trainers/cocoop.py:123-161, 48-59):
- * S = G * C, row g * C + c = (image g, class c). */
-int mvlpt_text_fwd_ranged(void* handle, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
-                          const int32_t* eot, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L, float* feat_out,
-                          int save_for_bwd, mvlpt_stream_t stream);
-/* dfeat [C,embed] fp32 -> dctx (same shape as ctx).  Must follow text_fwd(save_for_bwd=1).  After
- * text_fwd_ranged(save_for_bwd=1): dfeat [S,embed] -> dctx [G,n_ctx,dt], dctx[g] = sum over the sequences of group g's own range in a
- * fixed order (no atomics: deterministic); all zeros for an empty range.  CoCoOp's full ranges: dfeat [G*C,embed], dctx[g] = sum over
- * the C classes of image g. */
-int mvlpt_text_bwd(void* handle, const float* dfeat, float* dctx, mvlpt_stream_t stream);
-/* Deep language prompting (per-layer text contexts; the language half of MaPLe, "independent V-L prompting" next to deep visual prompts).
- * The tower of mvlpt_text_fwd with a generic context ctx [n_ctx,dt] and, in front of block l = 1 .. n_deep, the hidden states at the
- * context positions replaced: x_l[c, ctx_pos[c,j], :] = ctx_deep[l-1, j, :], ctx_deep [n_deep,n_ctx,dt] fp32, for every class c and
- * every CLASS_TOKEN_POSITION (the positions come from `layout`).  No positional embedding is added to the replaced rows.  Blocks behind
- * n_deep run on whatever the block in front of them left; no block is skipped.  1 <= n_deep <= text_layers - 1.  ln_1 of a block behind
- * an overwrite is not folded into the FC2 in front of it (n_deep more LayerNorm launches when LayerNorm folding is on).
- * n_deep == 0 (ctx_deep is then ignored) launches what mvlpt_text_fwd launches: the same bits.
- * MVLPT_ERR_ARG before any device work: n_deep > text_layers - 1, n_deep < 0, n_deep > 0 with n_ctx == 0 or with ctx_deep == NULL.
- * Per-class (CSC) deep prompts, the ranged tower and token-id sequences are not offered on this entry.
- * With save_for_bwd, ctx_deep must stay valid and unchanged until the backward has been enqueued on the same stream: under
- * mvlpt_set_text_act_ckpt the backward's recomputation of a segment reads it again.  mvlpt_text_workspace_bytes is unchanged.
- * Backward: dctx as mvlpt_text_bwd; dctx_deep [n_deep,n_ctx,dt], dctx_deep[l-1, j] = sum over the classes (fixed order, no atomics) of
- * the gradient at the input of block l at ctx_pos[c,j]; those rows then carry no gradient into block l-1.  After a deep forward
- * mvlpt_text_bwd returns MVLPT_ERR_STATE (call mvlpt_text_bwd_deep); mvlpt_text_bwd_deep after a forward without deep prompts is
- * mvlpt_text_bwd and accepts dctx_deep == NULL. */
-int mvlpt_text_fwd_deep(void* handle, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const float* ctx_deep,
-                        int n_deep, const int32_t* layout, const int32_t* eot, int C, int L, float* feat_out, int save_for_bwd,
-                        mvlpt_stream_t stream);
-int mvlpt_text_bwd_deep(void* handle, const float* dfeat, float* dctx, float* dctx_deep, mvlpt_stream_t stream);
-/* *out = bytes of text-tower workspace a text_fwd / text_fwd_ranged over C_total sequences of length L reserves (the
+/* One text forward over prompts: forward_coop + TextEncoder.forward (trainers/mvlpt.py:439-515, 105-130).  The kind follows from the
+ * fields: class_lo / class_hi set = ranged, n_deep > 0 = deep, otherwise plain.  Pointers first, fixed-width fields, no implicit padding;
+ * a zeroed struct with the fields of one kind filled in by name is a valid job.  Device pointers unless marked HOST. */
+typedef struct MvlptTextJob {
+  /* the class tables: prefix [n_cls,1,dt], suffix [n_cls,L-1-n_ctx,dt] fp32 (the `token_prefix` / `token_suffix` buffers, :312-316) */
+  const float* prefix;
+  const float* suffix;
+  /* plain: [n_ctx,dt] (ctx_per_class = 0) or [n_cls,n_ctx,dt] (CSC, ctx_per_class = 1) fp32, NULL when n_ctx == 0; deep: [n_ctx,dt];
+   * ranged: [groups,n_ctx,dt], one context block per image (ctx + meta_net(image g)), n_ctx > 0 */
+  const float* ctx;
+  /* Deep language prompting (per-layer text contexts; the language half of MaPLe, "independent V-L prompting" next to deep visual
+   * prompts): [n_deep,n_ctx,dt] fp32.  In front of block l = 1 .. n_deep the hidden states at the context positions are replaced,
+   * x_l[c, ctx_pos[c,j], :] = ctx_deep[l-1, j, :], for every class c and every CLASS_TOKEN_POSITION (the positions come from `layout`).
+   * No positional embedding is added to the replaced rows.  Blocks behind n_deep run on whatever the block in front of them left; no
+   * block is skipped.  ln_1 of a block behind an overwrite is not folded into the FC2 in front of it (n_deep more LayerNorm launches
+   * when LayerNorm folding is on).  Ignored when n_deep == 0: the launches and the bits of the plain tower.  With save_for_bwd it stays
+   * valid and unchanged until the backward has been enqueued on the same stream: under mvlpt_set_text_act_ckpt the backward's
+   * recomputation of a segment reads it again. */
+  const float* ctx_deep;
+  /* int32 [n_cls,L]: source row per position — 0 = prefix, e>0 = suffix row e-1, e<0 = ctx row -e-1 (encodes the end/middle/front layouts) */
+  const int32_t* layout;
+  /* int32 [n_cls] = argmax of tokenized_prompts (:128) */
+  const int32_t* eot;
+  /* HOST int32 [groups], both NULL unless ranged (the task of an image is known on the host before the step); checked and uploaded with
+   * the call, which stays enqueue-only.  Group g owns classes [class_lo[g], class_hi[g]), 0 <= lo <= hi <= n_cls (an empty range is
+   * legal, not all of them); its sequences are those classes in order, each class c's prefix / suffix / layout row / eot with context
+   * block g, the groups follow one another as ONE tower: S = sum_g (hi - lo) sequences, S * L inside int32.  The class tables are read
+   * through the ranges, never copied.  The MVLPT trainer's CoCoOp branch under MULTITASK_LABEL_PERTASK (trainers/mvlpt.py:556-581): image
+   * g keeps only the logits of its own task's class range, so only those sequences run.  Every range [0, n_cls) is CoCoOp's tower,
+   * PromptLearner.forward + one TextEncoder call per image (trainers/cocoop.py:123-161, 48-59): row g * n_cls + c = (image g, class c). */
+  const int32_t* class_lo;
+  const int32_t* class_hi;
+  int32_t n_ctx;         /* context tokens, 0 <= n_ctx <= L - 2 */
+  int32_t ctx_per_class; /* plain only */
+  int32_t n_deep;        /* 0 <= n_deep <= text_layers - 1 (block 0 reads the embedding-level context); > 0 needs n_ctx > 0 and ctx_deep */
+  int32_t groups;        /* ranged: 1 .. 65535; 0 otherwise */
+  int32_t n_cls;         /* rows of the class tables */
+  int32_t L;             /* L <= context_length (CUT_CONTEXTLEN gives L < 77, :111-117) */
+  int32_t save_for_bwd;  /* != 0 keeps activations for mvlpt_text_bwd */
+  int32_t reserved;      /* 0 */
+} MvlptTextJob;
+#define MVLPT_TEXT_JOB_BYTES 96
+/* feat_out [n_cls,embed] fp32 ([S,embed] ranged).  MVLPT_ERR_ARG before any device work or engine state is touched: a null table, a
+ * field outside the limits above, class_lo / class_hi / groups not all set or all clear, and the combinations that are not offered:
+ * deep prompts with ctx_per_class or on the ranged tower, ctx_per_class on the ranged tower.  mvlpt_text_workspace_bytes does not depend
+ * on the kind. */
+int mvlpt_text_fwd(void* handle, const MvlptTextJob* job, float* feat_out, mvlpt_stream_t stream);
+/* dfeat [n_cls,embed] fp32 -> dctx (same shape as ctx).  Must follow mvlpt_text_fwd with save_for_bwd and n_ctx > 0.  Ranged: dfeat
+ * [S,embed] -> dctx [groups,n_ctx,dt], dctx[g] = sum over the sequences of group g's own range in a fixed order (no atomics:
+ * deterministic); all zeros for an empty range.  dctx_deep [n_deep,n_ctx,dt] exactly when the forward had n_deep > 0, NULL otherwise
+ * (MVLPT_ERR_ARG either way round; the saved forward stays usable): dctx_deep[l-1, j] = sum over the classes (fixed order, no atomics)
+ * of the gradient at the input of block l at ctx_pos[c,j]; those rows then carry no gradient into block l-1. */
+int mvlpt_text_bwd(void* handle, const float* dfeat, float* dctx, float* dctx_deep, mvlpt_stream_t stream);
+/* *out = bytes of text-tower workspace a mvlpt_text_fwd (S sequences when ranged) over C_total sequences of length L reserves (the
  * ctx-position table counted for the largest n_ctx, L - 2; a ranged tower adds its range tables and a per-class
  * position table, a few bytes per class and sequence, which the figure covers unless n_ctx is within a few tokens of L - 2); the
  * workspace only grows, so a caller that chunks G keeps its peak under a budget.  With save_for_bwd the figure is the one under the
@@ -263,7 +270,7 @@ int mvlpt_text_workspace_bytes(void* handle, int C_total, int L, int save_for_bw
 /* Activation checkpointing of the text tower, TRAINER.ACT_CKPT of the reference (trainers/mvlpt.py:119-121:
  * checkpoint_sequential(resblocks, ACT_CKPT, x)).  An engine setting like mvlpt_set_precision; default 1 (everything saved).
  * The plan is torch's: k = min(segments, text_layers) segments, the first k - 1 of text_layers / k blocks each, the last one takes
- * the rest.  A saving forward (text_fwd / text_fwd_ranged with save_for_bwd = 1) keeps only the input of the first k - 1 segments
+ * the rest.  A saving forward (mvlpt_text_fwd of any kind with save_for_bwd = 1) keeps only the input of the first k - 1 segments
  * and the activations of the last one; mvlpt_text_bwd runs every other segment again before that segment's backward, launch for launch
  * as the forward did (no LayerNorm is folded across a segment boundary: k - 1 more LayerNorm launches), so features and dctx have
  * the bits of an un-checkpointed tower whenever LayerNorm folding is off or the tower is below its row threshold, and stay within
@@ -299,7 +306,7 @@ int mvlpt_set_text_grad_len(void* handle, int grad_len, int max_eot);
  * order (no atomics).  For more than 512 classes that sum is carried scaled down by a power of two and rescaled exactly at the end.
  * The features keep their bits; dctx rows of prefix positions change at rounding level (another summation order).
  * Unlike mvlpt_set_text_grad_len the engine cannot check this setting against its tables, so it is ONE-SHOT: the next text forward
- * through any entry (mvlpt_text_fwd, saving or not; _deep; _ranged; mvlpt_text_encode_tokens) consumes it, and a forward without a new
+ * through either entry (mvlpt_text_fwd of any kind, saving or not; mvlpt_text_encode_tokens) consumes it, and a forward without a new
  * call runs without a prefix.  The forward records what it ran under: a call between a forward and its backward does not change that
  * backward.  0 (the default): off, today's launches.  prefix < 0 or >= context_length: MVLPT_ERR_ARG.  The engine uses
  * P = min(prefix, L - 1) lowered until P <= grad_len - P and grad_len - P >= MVLPT_TEXT_MIN_L (any shorter prefix is as correct), and
@@ -341,7 +348,7 @@ int mvlpt_logits_fwd(void* handle, const float* img_feat, const float* txt_feat,
 /* dlogits [B,C] -> dimg [B,embed], dtxt [C,embed] (either may be NULL).  Uses the features of the last
  * mvlpt_logits_fwd call on this handle. */
 int mvlpt_logits_bwd(void* handle, const float* dlogits, float* dimg, float* dtxt, mvlpt_stream_t stream);
-/* The ranged head: img [G,embed], txt [S,embed] (rows of mvlpt_text_fwd_ranged over the same HOST class_lo / class_hi), logits [G,C]:
+/* The ranged head: img [G,embed], txt [S,embed] (rows of a ranged mvlpt_text_fwd over the same HOST class_lo / class_hi), logits [G,C]:
  * inside image g's range the cosine logit against its own text row, outside it exactly 0.0f (logits * select_index, :581).
  * The backward reads dlogits [G,C] inside the ranges only and gives dtxt [S,embed] and / or dimg [G,embed] (either may be NULL): dimg is
  * the gradient with respect to the UN-normalised image features (the image tower may carry visual prompts on this route).  Uses the
@@ -540,8 +547,8 @@ int mvlpt_op_cast_to_f32(int in_dtype, const void* in, float* out, int64_t n, mv
 int mvlpt_op_pack_weight(int dtype, const float* w32, int rows, int cols, int transposed, int ld_out, void* out, mvlpt_stream_t stream);
 int mvlpt_op_patchify(int dtype, const void* image, int image_dtype, void* out, int B, int R, int P, int Kp, mvlpt_stream_t stream);
 int mvlpt_op_patchify_route(int dtype, int image_dtype, int R, int P);
-/* the glue of mvlpt_text_fwd_ranged / text_bwd: x [S, L, d] fp32 = assembled prompts + pos [L, d] (layout entries must address
- * rows inside prefix / suffix / ctx) and dx [S, L, d] over the sequences of HOST class_lo / class_hi int32 [G] (see mvlpt_text_fwd_ranged;
+/* the glue of the ranged mvlpt_text_fwd / text_bwd: x [S, L, d] fp32 = assembled prompts + pos [L, d] (layout entries must address
+ * rows inside prefix / suffix / ctx) and dx [S, L, d] over the sequences of HOST class_lo / class_hi int32 [G] (see MvlptTextJob;
  * lo = 0, hi = C for every g is CoCoOp's tower, S = G * C), dctx [G, n_ctx, d] = sum over group g's sequences of dx at ctx_pos
  * int32 [C, n_ctx].  These two calls wait for their kernel (test entry points). */
 int mvlpt_op_assemble_prompts_ranged(const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
@@ -587,7 +594,7 @@ int mvlpt_op_attention_bwd_cls(int dtype, const void* qkv, const void* o_cls, co
                                int L, int H, mvlpt_stream_t stream);
 int mvlpt_op_copy_rows(const void* src, void* dst, const int32_t* idx, int rows, int row_bytes, int scatter, mvlpt_stream_t stream);
 int mvlpt_op_overwrite_rows(const float* rows, int n, float* x, int B, int L, int d, const float* vmask, mvlpt_stream_t stream);
-/* the glue of mvlpt_text_fwd_deep / text_bwd_deep (tests/test_hip_deep_text_ops.py); ctx_pos int32 [C,n_ctx] with entries in [0, L)
+/* the glue of the deep mvlpt_text_fwd / text_bwd (tests/test_hip_deep_text_ops.py); ctx_pos int32 [C,n_ctx] with entries in [0, L)
  * (an entry outside is skipped), d % 4 == 0:
  * overwrite_ctx_rows: x[c, ctx_pos[c,j], :] = rows[j, :], x [C,L,d] fp32, rows [n_ctx,d]; no other row is written.
  * gather_zero_ctx_grad: out [n_ctx,d] = scale_dev[1] (or 1 when NULL) * sum_c dx32[c, ctx_pos[c,j], :] with the bits of
@@ -691,7 +698,7 @@ int mvlpt_nearest_tokens(void* handle, const float* q, int R, int k, int32_t* id
  * Replaces, per optimisation step of TPT (Shu et al., NeurIPS 2022), the logits product, log_softmax, per-view entropy, the
  * argsort-based confidence selection, the marginal entropy of the selected views and autograd back to the text features.
  * All fp32, row-major: img [G, V, e] un-normalised features of the V views of each of G test images; txt [G*C, e] un-normalised text
- * features, row g*C + c = (image g, class c) (mvlpt_text_fwd_ranged over full ranges); scale = exp(logit_scale); 1 <= k <= V.
+ * features, row g*C + c = (image g, class c) (a ranged mvlpt_text_fwd over full ranges); scale = exp(logit_scale); 1 <= k <= V.
  *   Forward:  z[g,v,c] = scale <img/|img|, txt/|txt|>;  logp = z - logsumexp_c z;  H[g,v] = -sum_c exp(logp) logp;
  *     sel[g] = the k views with the smallest H under the total order (H, then view index), NaN behind every number, written as
  *     int32 [G, k] in that order;  a[g,c] = logsumexp_{v in sel[g]} logp[g,v,c] - log k;  loss[g] = -sum_c exp(a) a.

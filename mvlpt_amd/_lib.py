@@ -43,6 +43,19 @@ class MvlptResNetArch(C.Structure):
     _fields_ = [("image_resolution", C.c_int), ("width", C.c_int), ("layers", C.c_int * 4), ("heads", C.c_int), ("output_dim", C.c_int)]
 
 
+TEXT_JOB_BYTES = 96     # MVLPT_TEXT_JOB_BYTES
+
+
+class MvlptTextJob(C.Structure):
+    """One text forward (include/mvlpt_hip.h documents the fields); class_lo / class_hi are host arrays, the other pointers device."""
+    _fields_ = ([(n, C.c_void_p) for n in ("prefix", "suffix", "ctx", "ctx_deep", "layout", "eot")]
+                + [(n, C.POINTER(C.c_int32)) for n in ("class_lo", "class_hi")]
+                + [(n, C.c_int32) for n in ("n_ctx", "ctx_per_class", "n_deep", "groups", "n_cls", "L", "save_for_bwd", "reserved")])
+
+
+assert C.sizeof(MvlptTextJob) == TEXT_JOB_BYTES
+
+
 class MvlptKernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_int64), ("ms", C.c_double),
                 ("flops", C.c_double), ("bytes", C.c_double), ("busy_ms", C.c_double), ("flops_executed", C.c_double)]
@@ -115,11 +128,8 @@ SIGNATURES = {
     "mvlpt_image_fwd_resume": (_i, [_vp, _vp, _vp]),
     "mvlpt_image_fwd_abandon": (_i, [_vp]),
     "mvlpt_image_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
-    "mvlpt_text_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
-    "mvlpt_text_bwd": (_i, [_vp, _vp, _vp, _vp]),
-    "mvlpt_text_fwd_deep": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _vp]),
-    "mvlpt_text_bwd_deep": (_i, [_vp, _vp, _vp, _vp, _vp]),
-    "mvlpt_text_fwd_ranged": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp]),
+    "mvlpt_text_fwd": (_i, [_vp, C.POINTER(MvlptTextJob), _vp, _vp]),
+    "mvlpt_text_bwd": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "mvlpt_text_workspace_bytes": (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int64)]),
     "mvlpt_set_text_act_ckpt": (_i, [_vp, _i]),
     "mvlpt_set_text_grad_len": (_i, [_vp, _i, _i]),

@@ -6,7 +6,7 @@ Same class names, constructor arguments and ``prompt_learner.state_dict()`` keys
 Every image g gets its own context ``ctx + meta_net(img_g / |img_g|)``, so the text tower runs over B x n_cls sequences per
 step.  The reference loops over the images in Python (trainers/cocoop.py:184-189) and trains at batch size 1; here the
 whole batch (or the largest chunk of it whose workspace fits ``CustomCLIP.max_text_workspace_bytes``) is ONE ranged tower with
-every image's class range full, [0, n_cls) (mvlpt_text_fwd_ranged: the [n_cls, ...] prefix / suffix / layout tables are read per
+every image's class range full, [0, n_cls) (the ranged mvlpt_text_fwd: the [n_cls, ...] prefix / suffix / layout tables are read per
 image, never copied), followed by the ranged cosine head over the same ranges (mvlpt_logits_ranged_fwd / _bwd) and the existing
 cross-entropy kernel: the entries the MVLPT trainer's COCOOP.N_CTX != 0 route (mvlpt_amd.mvlpt_cocoop) calls with per-task ranges.
 ``meta_net`` and ``ctx + bias`` (a few thousand FLOPs per image, trainable) stay on torch autograd, as the UPT projection does.

@@ -202,8 +202,8 @@ static const char* kProfNames[PC_COUNT] = {"gemm_bt", "attention_fwd", "attentio
                                            "glue", "head_logits_ce", "attention_fwd_image"};
 struct ProfRec { int cls; hipEvent_t a, b; double flops, bytes, flops_exec; int M = 0, N = 0, K = 0, epi = -1, split = 0, fold = 0; };
 
-// How the sequences of a text forward are put together: prompts of C classes (mvlpt_text_fwd), prompts of per-group class ranges
-// (mvlpt_text_fwd_ranged; CoCoOp is every range full), token ids (mvlpt_text_encode_tokens)
+// How the sequences of a text forward are put together: prompts of C classes, prompts of per-group class ranges (CoCoOp is every range
+// full; both mvlpt_text_fwd), token ids (mvlpt_text_encode_tokens)
 enum class TextKind { Plain, Ranged, Ids };
 // The entry that ran the last head forward
 enum class HeadKind { Plain, Ranged };
@@ -224,8 +224,8 @@ enum class HeadKind { Plain, Ranged };
 //   image_fwd_abandon              image    Pending            None
 //   image_fwd (ResNet)             image    any                Done               (None on failure)
 //   image_bwd                      image    Saved / BwdDone    BwdDone
-//   text_fwd* / encode_tokens      text     any                Done / Saved       (None on failure)
-//   text_bwd / text_bwd_deep       text     Saved / BwdDone    BwdDone, or Consumed once a checkpointed backward touches the slots
+//   text_fwd / encode_tokens       text     any                Done / Saved       (None on failure)
+//   text_bwd                       text     Saved / BwdDone    BwdDone, or Consumed once a checkpointed backward touches the slots
 //   logits_fwd / logits_ranged_fwd head     any                Saved              (None on failure)
 //   logits_bwd / logits_ranged_bwd head     Saved              Saved              (the forward of its own kind only)
 enum class Phase { None, Pending, Done, Saved, BwdDone, Consumed };
@@ -249,8 +249,8 @@ struct TextRun {
   int groups = 0;                        // TextKind::Ranged: the groups, C = sum of the range widths
   // device tables in txt_ws.  range: [lo (groups) | start (groups + 1) | ...] (build_range_table), ids: mvlpt_text_encode_tokens
   int32_t *eot_rows = nullptr, *ctx_pos = nullptr, *range = nullptr, *ids = nullptr;
-  // Caller-owned: ctx_deep [n_deep, n_ctx, dt] (mvlpt_text_fwd_deep), read again by the recomputation of a checkpointed backward:
-  // alive until the last mvlpt_text_bwd_deep of this forward is enqueued
+  // Caller-owned: ctx_deep [n_deep, n_ctx, dt] (MvlptTextJob), read again by the recomputation of a checkpointed backward:
+  // alive until the last mvlpt_text_bwd of this forward is enqueued
   const float* ctx_deep = nullptr;
 };
 struct HeadRun {
@@ -1751,19 +1751,15 @@ static int64_t build_range_table(const int32_t* class_lo, const int32_t* class_h
 }
 
 // ------------------------------------------------------------------------------------------------ text tower
-// One text forward, as its entry describes it once its own checks have passed (text_fwd_impl).
-// Plain: mvlpt_text_fwd (prefix / suffix / layout / eot [C, ...], ctx [n_ctx, d] or CSC [C, n_ctx, d]; G = 0, Cg = C).
-// Ranged: mvlpt_text_fwd_ranged, G groups over the [Cg, ...] class tables and ctx [G, n_ctx, d], C = S sequences described by
-// E->t_range_host.  Ids: mvlpt_text_encode_tokens, C sequences of token ids (E->t_ids_host); no class tables and no ctx.
-// Deep (mvlpt_text_fwd_deep): a plain tower whose context rows are replaced by ctx_deep [n_deep, n_ctx, d] in front of blocks 1 .. n_deep.
-struct TextJob {
+static_assert(sizeof(MvlptTextJob) == MVLPT_TEXT_JOB_BYTES, "MvlptTextJob has no implicit padding");
+// One text forward: the caller's job (its fields: include/mvlpt_hip.h) and what text_job_check derives from it.
+// Plain (and deep, n_deep > 0): C = Cg = n_cls sequences, G = 0.  Ranged: G = groups over the [Cg = n_cls, ...] class tables, C = S
+// sequences described by E->t_range_host.  Ids: mvlpt_text_encode_tokens, C sequences of token ids (E->t_ids_host); no class tables
+// and no ctx.
+struct TextJob : MvlptTextJob {
   TextKind kind = TextKind::Plain;
-  const float *prefix = nullptr, *suffix = nullptr; const int32_t *layout = nullptr, *eot = nullptr;      // the four class tables
-  const float* ctx = nullptr; int per_class = 0, n_ctx = 0;
-  const float* ctx_deep = nullptr; int n_deep = 0;
-  int G = 0, Cg = 0, C = 0, L = 0;
-  int save = 0;
-  float* feat_out = nullptr;
+  int C = 0, Cg = 0, G = 0;
+  explicit TextJob(const MvlptTextJob& job = MvlptTextJob{}) : MvlptTextJob(job) {}
 };
 // What a text forward over C sequences of length L carves from txt_ws: text_fwd_impl carves with it and mvlpt_text_workspace_bytes
 // counts with it.  `exact`: split operands (see mvlpt_text_fwd); ctx_rows: rows of the ctx_pos table; range_ints / ids_ints: the range
@@ -1794,7 +1790,7 @@ static void text_layout(Bump& bp, const Engine* E, TextRun& R, const TextShape& 
 // deep contexts, the ranged and token-id towers, activation checkpointing, sequences the short kernels do not take.  Split and single
 // operands alike (attention32.hip / attention.hip).  `setting`: what the forward took out of Engine::text_shared_prefix.
 static int text_prefix_len(const Engine* E, int setting, const TextJob& j, int Lg) {
-  if (setting <= 0 || j.kind != TextKind::Plain || j.per_class || j.n_ctx <= 0 || j.n_deep > 0 || j.L > 80 || E->text_act_ckpt != 1)
+  if (setting <= 0 || j.kind != TextKind::Plain || j.ctx_per_class || j.n_ctx <= 0 || j.n_deep > 0 || j.L > 80 || E->text_act_ckpt != 1)
     return 0;
   int P = std::min(setting, j.L - 1);
   P = std::min(P, std::min(Lg / 2, Lg - 3));
@@ -1843,7 +1839,7 @@ static int text_segment_fwd(Engine* E, int first, int end, bool last, bool keep,
 }
 
 // The text tower over the j.C sequences of one TextJob
-static int text_fwd_impl(Engine* E, const TextJob& j, mvlpt_stream_t stream) {
+static int text_fwd_impl(Engine* E, const TextJob& j, float* feat_out, mvlpt_stream_t stream) {
   const bool ranged = j.kind == TextKind::Ranged, ids = j.kind == TextKind::Ids;
   const int C = j.C, L = j.L, n_ctx = j.n_ctx, n_deep = j.n_deep, G = j.G, Cg = j.Cg;
   // one-shot, taken before any check can refuse the call: the caller's proof holds for the tables of THIS forward only, whichever
@@ -1857,7 +1853,7 @@ static int text_fwd_impl(Engine* E, const TextJob& j, mvlpt_stream_t stream) {
   if (L > attn_max_len()) return fail(E, MVLPT_ERR_UNSUPPORTED, "text_fwd: L > 256");
   hipStream_t s = (hipStream_t)stream;
   const int dtw = A.text_width, e = A.embed_dim;
-  const bool save = j.save != 0;
+  const bool save = j.save_for_bwd != 0;
   // The text tower runs with split operands in every mode but MVLPT_PREC_FAST, also when nothing is saved for a backward:
   // n_ctx == 0: the features are constants of the run (computed once and cached by the caller) that enter every
   // image-side gradient through the logits; inference (model_inference, trainers/mvlpt.py:986-987): they are computed once
@@ -1883,7 +1879,7 @@ static int text_fwd_impl(Engine* E, const TextJob& j, mvlpt_stream_t stream) {
     while (((int64_t)512 << sh) < C) ++sh;
     st.part_mul = std::ldexp(1.0f, -sh);
   }
-  R.C = C; R.L = L; R.n_ctx = n_ctx; R.per_class = j.per_class; R.kind = j.kind; R.groups = G;
+  R.C = C; R.L = L; R.n_ctx = n_ctx; R.per_class = j.ctx_per_class; R.kind = j.kind; R.groups = G;
   R.n_deep = n_deep; R.ctx_deep = n_deep > 0 ? j.ctx_deep : nullptr;
   st.fold = E->fold_mode >= 2 && (size_t)C * L >= (size_t)E->fold_min_rows && dtw >= 256;
   if (st.fold) if (int rc = prepare_fold(E, s)) return rc;
@@ -1901,7 +1897,7 @@ static int text_fwd_impl(Engine* E, const TextJob& j, mvlpt_stream_t stream) {
       HIPCHK(E, launch_eot_rows_ranged(j.eot, R.eot_rows, seq_cls, C, L, s));
       if (save) HIPCHK(E, launch_build_ctx_pos(j.layout, R.ctx_pos, Cg, L, n_ctx, s));     // per class: [Cg, n_ctx]
     } else {
-      HIPCHK(E, launch_assemble_prompts(j.prefix, j.suffix, j.ctx, j.per_class, n_ctx, j.layout, E->tpos, st.x[0], C, L, dtw, s, P));
+      HIPCHK(E, launch_assemble_prompts(j.prefix, j.suffix, j.ctx, j.ctx_per_class, n_ctx, j.layout, E->tpos, st.x[0], C, L, dtw, s, P));
       HIPCHK(E, launch_eot_rows(j.eot, R.eot_rows, C, L, s, P));
       if ((save || n_deep > 0) && n_ctx > 0) HIPCHK(E, launch_build_ctx_pos(j.layout, R.ctx_pos, C, L, n_ctx, s, P, st.Lg));
     } }
@@ -1917,64 +1913,46 @@ static int text_fwd_impl(Engine* E, const TextJob& j, mvlpt_stream_t stream) {
   if (int rc = text_deep_overwrite(E, E->txt.layers - 1, s)) return rc;
   if (int rc = last_block_fwd(E, E->txt, st, R.c, LastRows{R.eot_rows, 0, E->ln_final}, false, ln1_ready, s)) return rc;
   { ProfScope ps(E, s, PC_HEAD, 2.0 * C * e * dtw, 4.0 * ((double)C * dtw + (double)e * dtw + (double)C * e));
-    HIPCHK(E, launch_sgemm_bt(R.c.out32, E->tproj_t, j.feat_out, C, e, dtw, nullptr, s)); }
+    HIPCHK(E, launch_sgemm_bt(R.c.out32, E->tproj_t, feat_out, C, e, dtw, nullptr, s)); }
   R.phase = save ? Phase::Saved : Phase::Done;
   return 0;
 }
 
-int mvlpt_text_fwd(void* h, const float* prefix, const float* suffix, const float* ctx, int ctx_per_class, int n_ctx,
-                   const int32_t* layout, const int32_t* eot, int C, int L, float* feat_out, int save_for_bwd,
-                   mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !prefix || !suffix || !layout || !eot || !feat_out || C <= 0 || L <= 0)
+// Every refusal of a job for what it says (text_fwd_impl adds those that depend on the engine's settings), and the derived fields.
+// Nothing is launched and, up to the range table (host scratch no saved forward reads), no engine state is touched.
+static int text_job_check(Engine* E, TextJob& j, const float* feat_out) {
+  if (!j.prefix || !j.suffix || !j.layout || !j.eot || !feat_out || j.n_cls <= 0 || j.L <= 0 || j.reserved != 0)
     return fail(E, MVLPT_ERR_ARG, "text_fwd: null/invalid argument");
-  TextJob j;
-  j.prefix = prefix; j.suffix = suffix; j.layout = layout; j.eot = eot;
-  j.ctx = ctx; j.per_class = ctx_per_class; j.n_ctx = n_ctx;
-  j.Cg = j.C = C; j.L = L; j.save = save_for_bwd; j.feat_out = feat_out;
-  return text_fwd_impl(E, j, stream);
-}
-
-// Deep language prompting: mvlpt_text_fwd with a generic context whose rows are replaced in front of blocks 1 .. n_deep
-int mvlpt_text_fwd_deep(void* h, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const float* ctx_deep, int n_deep,
-                        const int32_t* layout, const int32_t* eot, int C, int L, float* feat_out, int save_for_bwd, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !prefix || !suffix || !layout || !eot || !feat_out || C <= 0 || L <= 0)
-    return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: null/invalid argument");
-  if (n_deep < 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: n_deep is negative");
-  if (n_deep > 0) {
-    if (!ctx_deep) return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: ctx_deep is null with n_deep > 0");
-    if (n_ctx <= 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: deep prompts need context tokens (n_ctx == 0)");
-    if (n_deep > E->txt.layers - 1)
-      return fail(E, MVLPT_ERR_ARG, "text_fwd_deep: n_deep exceeds text_layers - 1 (block 0 reads the embedding-level context)");
+  const bool ranged = j.class_lo || j.class_hi;
+  if (!j.class_lo != !j.class_hi || ranged != (j.groups != 0))
+    return fail(E, MVLPT_ERR_ARG, "text_fwd: class_lo, class_hi and groups come together");
+  if (j.n_deep < 0) return fail(E, MVLPT_ERR_ARG, "text_fwd: n_deep is negative");
+  if (j.n_deep > 0) {
+    if (ranged) return fail(E, MVLPT_ERR_ARG, "text_fwd: deep prompts are not offered on the ranged tower");
+    if (j.ctx_per_class) return fail(E, MVLPT_ERR_ARG, "text_fwd: deep prompts take a generic context (ctx_per_class = 0)");
+    if (!j.ctx_deep) return fail(E, MVLPT_ERR_ARG, "text_fwd: ctx_deep is null with n_deep > 0");
+    if (j.n_ctx <= 0) return fail(E, MVLPT_ERR_ARG, "text_fwd: deep prompts need context tokens (n_ctx == 0)");
+    if (j.n_deep > E->txt.layers - 1)
+      return fail(E, MVLPT_ERR_ARG, "text_fwd: n_deep exceeds text_layers - 1 (block 0 reads the embedding-level context)");
   }
-  TextJob j;
-  j.prefix = prefix; j.suffix = suffix; j.layout = layout; j.eot = eot;
-  j.ctx = ctx; j.n_ctx = n_ctx; j.ctx_deep = ctx_deep; j.n_deep = n_deep;
-  j.Cg = j.C = C; j.L = L; j.save = save_for_bwd; j.feat_out = feat_out;
-  return text_fwd_impl(E, j, stream);
+  j.C = j.Cg = j.n_cls;
+  if (!ranged) return 0;
+  if (!j.ctx || j.ctx_per_class || j.groups < 0 || j.n_ctx <= 0) return fail(E, MVLPT_ERR_ARG, "text_fwd: null/invalid argument");
+  if (j.groups > 65535) return fail(E, MVLPT_ERR_ARG, "text_fwd: too many groups");
+  const int64_t S = build_range_table(j.class_lo, j.class_hi, j.groups, j.n_cls, E->t_range_host);
+  if (S < 0) return fail(E, MVLPT_ERR_ARG, "text_fwd: a class range is not inside [0, C] or the ranges hold too many sequences");
+  if (S == 0) return fail(E, MVLPT_ERR_ARG, "text_fwd: every range is empty");
+  if (S > (int64_t)INT32_MAX / j.L) return fail(E, MVLPT_ERR_ARG, "text_fwd: too many sequences");
+  j.kind = TextKind::Ranged; j.G = j.groups; j.C = (int)S;
+  return 0;
 }
 
-// The MVLPT trainer's CoCoOp branch under the per-task mask (trainers/mvlpt.py:556-581): image g runs only the classes of its own task.
-// Every range [0, C) is PromptLearner.forward + the per-image TextEncoder calls of CoCoOp (trainers/cocoop.py:123-161, 48-59): one
-// tower over G * C sequences
-int mvlpt_text_fwd_ranged(void* h, const float* prefix, const float* suffix, const float* ctx, int n_ctx, const int32_t* layout,
-                          const int32_t* eot, const int32_t* class_lo, const int32_t* class_hi, int G, int C, int L, float* feat_out,
-                          int save_for_bwd, mvlpt_stream_t stream) {
+int mvlpt_text_fwd(void* h, const MvlptTextJob* job, float* feat_out, mvlpt_stream_t stream) {
   Engine* E = (Engine*)h;
-  if (!E || !prefix || !suffix || !ctx || !layout || !eot || !class_lo || !class_hi || !feat_out || G <= 0 || C <= 0 || L <= 0 || n_ctx <= 0)
-    return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: null/invalid argument");
-  if (G > 65535) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: too many groups");
-  const int64_t S = build_range_table(class_lo, class_hi, G, C, E->t_range_host);
-  if (S < 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: a class range is not inside [0, C] or the ranges hold too many sequences");
-  if (S == 0) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: every range is empty");
-  if (S > (int64_t)INT32_MAX / L) return fail(E, MVLPT_ERR_ARG, "text_fwd_ranged: too many sequences");
-  TextJob j;
-  j.kind = TextKind::Ranged;
-  j.prefix = prefix; j.suffix = suffix; j.layout = layout; j.eot = eot;
-  j.ctx = ctx; j.n_ctx = n_ctx;
-  j.G = G; j.Cg = C; j.C = (int)S; j.L = L; j.save = save_for_bwd; j.feat_out = feat_out;
-  return text_fwd_impl(E, j, stream);
+  if (!E || !job) return fail(E, MVLPT_ERR_ARG, "text_fwd: null/invalid argument");
+  TextJob j(*job);
+  if (int rc = text_job_check(E, j, feat_out)) return rc;
+  return text_fwd_impl(E, j, feat_out, stream);
 }
 
 // CLIP.encode_text (clip/model.py:343-356) over S sequences of token ids, trimmed to their first L positions
@@ -2005,8 +1983,8 @@ int mvlpt_text_encode_tokens(void* h, const int32_t* ids, int ld, int S, int L, 
   }
   TextJob j;
   j.kind = TextKind::Ids;
-  j.Cg = j.C = S; j.L = L; j.feat_out = feat_out;
-  return text_fwd_impl(E, j, stream);
+  j.Cg = j.C = S; j.L = L;
+  return text_fwd_impl(E, j, feat_out, stream);
 }
 
 int mvlpt_text_ensemble(const float* feats, int T, int C, int e, float* out, mvlpt_stream_t stream) {
@@ -2067,17 +2045,17 @@ int mvlpt_text_workspace_bytes(void* h, int C_total, int L, int save_for_bwd, in
   return 0;
 }
 
-// The backward of every text forward.  dctx_deep: the gradient of the deep prompts (mvlpt_text_bwd_deep); `plain` (mvlpt_text_bwd) has
-// no place for it and refuses a deep forward.
-static int text_bwd_impl(Engine* E, const float* dfeat, float* dctx, float* dctx_deep, bool plain, mvlpt_stream_t stream) {
+// The backward of every text forward.  dctx_deep: the gradient of the deep prompts, there exactly when the forward ran some.
+int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, float* dctx_deep, mvlpt_stream_t stream) {
+  Engine* E = (Engine*)h;
+  if (!E || !dfeat || !dctx) return fail(E, MVLPT_ERR_ARG, "text_bwd: null argument");
   TextRun& R = E->trun; TowerState& st = R.st;
   if (R.phase == Phase::Consumed)
     return fail(E, MVLPT_ERR_STATE, "text_bwd: a backward under activation checkpointing has consumed the saved state; run the forward again");
   if (!bwd_ready(R.phase)) return fail(E, MVLPT_ERR_STATE, "text_bwd: call text_fwd(save_for_bwd=1) first");
   if (R.n_ctx <= 0) return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward had no context tokens");
-  if (R.n_deep > 0 && plain)
-    return fail(E, MVLPT_ERR_STATE, "text_bwd: the forward ran deep prompts (mvlpt_text_fwd_deep); call mvlpt_text_bwd_deep");
-  if (R.n_deep > 0 && !dctx_deep) return fail(E, MVLPT_ERR_ARG, "text_bwd_deep: dctx_deep is null after a forward with deep prompts");
+  if (R.n_deep > 0 && !dctx_deep) return fail(E, MVLPT_ERR_ARG, "text_bwd: dctx_deep is null after a forward with deep prompts");
+  if (R.n_deep == 0 && dctx_deep) return fail(E, MVLPT_ERR_ARG, "text_bwd: dctx_deep is set after a forward without deep prompts");
   hipStream_t s = (hipStream_t)stream;
   const MvlptArch& A = E->arch;
   // L: the gradient length this forward was saved under (TowerState::Lg), the sequence pitch of every gradient buffer
@@ -2124,18 +2102,6 @@ static int text_bwd_impl(Engine* E, const float* dfeat, float* dctx, float* dctx
       HIPCHK(E, launch_gather_ctx_grad(st.dx32, R.ctx_pos, C, L, dtw, R.n_ctx, R.per_class, dctx, st.scale_dev, s, st.P, 1.f / st.part_mul)); }
   if (k == 1) R.phase = Phase::BwdDone;
   return 0;
-}
-
-int mvlpt_text_bwd(void* h, const float* dfeat, float* dctx, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !dfeat || !dctx) return fail(E, MVLPT_ERR_ARG, "text_bwd: null argument");
-  return text_bwd_impl(E, dfeat, dctx, nullptr, true, stream);
-}
-
-int mvlpt_text_bwd_deep(void* h, const float* dfeat, float* dctx, float* dctx_deep, mvlpt_stream_t stream) {
-  Engine* E = (Engine*)h;
-  if (!E || !dfeat || !dctx) return fail(E, MVLPT_ERR_ARG, "text_bwd_deep: null argument");
-  return text_bwd_impl(E, dfeat, dctx, dctx_deep, false, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ head

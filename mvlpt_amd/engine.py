@@ -5,7 +5,7 @@ PyTorch is plumbing here (device memory, streams); all compute is in libmvlpt_hi
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -93,6 +93,16 @@ def _req(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     if t.dtype != dtype:
         t = t.to(dtype)
     return t.contiguous()
+
+
+class _TxtState(NamedTuple):
+    """What text_bwd / text_bwd_deep need of the last saving text forward; the tensors stay alive for the library's backward.
+    deep: text_fwd_deep made the record, with or without deep prompts."""
+    ctx_shape: Optional[Tuple[int, ...]]
+    layout: torch.Tensor
+    eot: torch.Tensor
+    ctx_deep: Optional[torch.Tensor]
+    deep: bool
 
 
 _ACTIVATIONS = {"quick_gelu": _lib.ACT_QUICKGELU, "gelu": _lib.ACT_GELU}      # MODEL.BACKBONE.ACTIVATION -> MVLPT_ACT_*
@@ -360,88 +370,62 @@ class Engine:
         _lib.check(lib.mvlpt_image_bwd(self.h, _ptr(dfeat), _ptr(dvpt), _ptr(ddeep), _stream()), self.h, "image_bwd")
         return dvpt, ddeep
 
-    @_on_device
-    def text_fwd(self, prefix: torch.Tensor, suffix: torch.Tensor, ctx: Optional[torch.Tensor], layout: torch.Tensor,
-                 eot: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
+    def _text_fwd(self, who, prefix, suffix, ctx, layout, eot, save_for_bwd, ctx_deep=None, ranges=None):
+        """Every prompt forward (mvlpt_text_fwd): one MvlptTextJob, filled by field name.  ranges: _host_ranges' (lo, hi, S)."""
         prefix = _req(prefix, torch.float32, "token_prefix")
         suffix = _req(suffix, torch.float32, "token_suffix")
         layout = _req(layout, torch.int32, "layout")
         eot = _req(eot, torch.int32, "eot")
-        Cn, L = layout.shape
-        per_class, n_ctx = 0, 0
+        rows, L = layout.shape
+        job = _lib.MvlptTextJob(prefix=prefix.data_ptr(), suffix=suffix.data_ptr(), layout=layout.data_ptr(), eot=eot.data_ptr(),
+                                n_cls=rows, L=L, save_for_bwd=int(save_for_bwd))
         if ctx is not None:
             ctx = _req(ctx, torch.float32, "ctx")
-            per_class = int(ctx.dim() == 3)
-            n_ctx = ctx.shape[-2]
-        feat = torch.empty(Cn, self.arch.embed_dim, device=prefix.device, dtype=torch.float32)
-        _lib.check(lib.mvlpt_text_fwd(self.h, _ptr(prefix), _ptr(suffix), _ptr(ctx), per_class, n_ctx, _ptr(layout), _ptr(eot),
-                                      Cn, L, _ptr(feat), int(save_for_bwd), _stream()), self.h, "text_fwd")
-        self._txt_state = (tuple(ctx.shape) if ctx is not None else None, layout, eot) if save_for_bwd else None
+            job.ctx, job.n_ctx = ctx.data_ptr(), ctx.shape[-2]
+        if ranges is not None:
+            job.class_lo, job.class_hi, rows = ranges
+            job.groups = ctx.shape[0]
+        elif ctx is not None:
+            job.ctx_per_class = int(ctx.dim() == 3)
+        if ctx_deep is not None:
+            ctx_deep = _req(ctx_deep, torch.float32, "ctx_deep")
+            job.ctx_deep, job.n_deep = ctx_deep.data_ptr(), ctx_deep.shape[0]
+        feat = torch.empty(rows, self.arch.embed_dim, device=prefix.device, dtype=torch.float32)
+        _lib.check(lib.mvlpt_text_fwd(self.h, C.byref(job), _ptr(feat), _stream()), self.h, who)
+        self._txt_state = _TxtState(tuple(ctx.shape) if ctx is not None else None, layout, eot, ctx_deep,
+                                    who == "text_fwd_deep") if save_for_bwd else None
         return feat
+
+    @_on_device
+    def text_fwd(self, prefix: torch.Tensor, suffix: torch.Tensor, ctx: Optional[torch.Tensor], layout: torch.Tensor,
+                 eot: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
+        return self._text_fwd("text_fwd", prefix, suffix, ctx, layout, eot, save_for_bwd)
 
     @_on_device
     def text_fwd_deep(self, prefix: torch.Tensor, suffix: torch.Tensor, ctx: Optional[torch.Tensor], ctx_deep: Optional[torch.Tensor],
                       layout: torch.Tensor, eot: torch.Tensor, save_for_bwd: bool = False) -> torch.Tensor:
-        """Deep language prompting (mvlpt_text_fwd_deep): text_fwd with a generic ctx [n_ctx, dt] whose rows are replaced by
+        """Deep language prompting (mvlpt_text_fwd with n_deep > 0): text_fwd with a generic ctx [n_ctx, dt] whose rows are replaced by
         ctx_deep[l - 1] ([n_deep, n_ctx, dt], 1 <= n_deep <= text_layers - 1) in front of block l.  ctx_deep None runs the plain tower
         (the bits of text_fwd).  A following text_bwd_deep returns (dctx, dctx_deep).  The engine reads ctx_deep again in a
         checkpointed backward; the tensor handed over here is kept until then."""
-        prefix = _req(prefix, torch.float32, "token_prefix")
-        suffix = _req(suffix, torch.float32, "token_suffix")
-        layout = _req(layout, torch.int32, "layout")
-        eot = _req(eot, torch.int32, "eot")
-        Cn, L = layout.shape
-        n_ctx = n_deep = 0
-        if ctx is not None:
-            ctx = _req(ctx, torch.float32, "ctx")
-            if ctx.dim() != 2:
-                raise ValueError("deep text prompts take a generic ctx [n_ctx, ctx_dim] (no per-class contexts)")
-            n_ctx = ctx.shape[0]
-        if ctx_deep is not None:
-            ctx_deep = _req(ctx_deep, torch.float32, "ctx_deep")
-            if ctx_deep.dim() != 3 or ctx_deep.shape[1] != n_ctx or ctx_deep.shape[2] != self.arch.transformer_width:
-                raise ValueError(f"ctx_deep must be [n_deep, {n_ctx}, {self.arch.transformer_width}], got {tuple(ctx_deep.shape)}")
-            n_deep = ctx_deep.shape[0]
-        feat = torch.empty(Cn, self.arch.embed_dim, device=prefix.device, dtype=torch.float32)
-        _lib.check(lib.mvlpt_text_fwd_deep(self.h, _ptr(prefix), _ptr(suffix), _ptr(ctx), n_ctx, _ptr(ctx_deep), n_deep, _ptr(layout),
-                                           _ptr(eot), Cn, L, _ptr(feat), int(save_for_bwd), _stream()), self.h, "text_fwd_deep")
-        self._txt_state = ((tuple(ctx.shape) if ctx is not None else None, layout, eot, ctx_deep) if save_for_bwd else None)
-        return feat
-
-    @_on_device
-    def text_bwd_deep(self, dfeat: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-        """(dctx, dctx_deep) of the last text_fwd_deep(save_for_bwd=True); dctx_deep is None when that forward had no deep prompts."""
-        st = self._txt_state
-        if st is None or st[0] is None or len(st) < 4:
-            raise RuntimeError("text_bwd_deep without text_fwd_deep(save_for_bwd=True) with context tokens")
-        dfeat = _req(dfeat, torch.float32, "dfeat")
-        dctx = torch.empty(st[0], device=dfeat.device, dtype=torch.float32)
-        ddeep = torch.empty(tuple(st[3].shape), device=dfeat.device, dtype=torch.float32) if st[3] is not None else None
-        _lib.check(lib.mvlpt_text_bwd_deep(self.h, _ptr(dfeat), _ptr(dctx), _ptr(ddeep), _stream()), self.h, "text_bwd_deep")
-        return dctx, ddeep
+        if ctx is not None and ctx.dim() != 2:
+            raise ValueError("deep text prompts take a generic ctx [n_ctx, ctx_dim] (no per-class contexts)")
+        n_ctx = ctx.shape[0] if ctx is not None else 0
+        if ctx_deep is not None and (ctx_deep.dim() != 3 or ctx_deep.shape[1] != n_ctx or ctx_deep.shape[2] != self.arch.transformer_width):
+            raise ValueError(f"ctx_deep must be [n_deep, {n_ctx}, {self.arch.transformer_width}], got {tuple(ctx_deep.shape)}")
+        return self._text_fwd("text_fwd_deep", prefix, suffix, ctx, layout, eot, save_for_bwd, ctx_deep=ctx_deep)
 
     @_on_device
     def text_fwd_ranged(self, prefix: torch.Tensor, suffix: torch.Tensor, ctx: torch.Tensor, layout: torch.Tensor, eot: torch.Tensor,
                         class_lo, class_hi, save_for_bwd: bool = False) -> torch.Tensor:
-        """The ranged text side (mvlpt_text_fwd_ranged): ctx [G, n_ctx, dt]; image g runs classes [class_lo[g], class_hi[g]) only.
+        """The ranged text side (mvlpt_text_fwd with class ranges): ctx [G, n_ctx, dt]; image g runs classes [class_lo[g], class_hi[g]) only.
         `class_lo` / `class_hi` are HOST integer sequences (lists, numpy or CPU tensors) of length G: nothing is read back from the
         device.  Features [S, e], S = sum of the range widths, group after group.  A following text_bwd returns [G, n_ctx, dt].
         [0] * G, [C] * G is CoCoOp's text side: features [G*C, e], row g*C + c = (image g, class c)."""
-        prefix = _req(prefix, torch.float32, "token_prefix")
-        suffix = _req(suffix, torch.float32, "token_suffix")
-        layout = _req(layout, torch.int32, "layout")
-        eot = _req(eot, torch.int32, "eot")
-        ctx = _req(ctx, torch.float32, "ctx")
         if ctx.dim() != 3:
             raise ValueError("ranged ctx must be [G, n_ctx, ctx_dim]")
-        Cn, L = layout.shape
-        G, n_ctx = ctx.shape[0], ctx.shape[1]
-        lo, hi, S = _host_ranges(class_lo, class_hi, G, Cn)
-        feat = torch.empty(S, self.arch.embed_dim, device=prefix.device, dtype=torch.float32)
-        _lib.check(lib.mvlpt_text_fwd_ranged(self.h, _ptr(prefix), _ptr(suffix), _ptr(ctx), n_ctx, _ptr(layout), _ptr(eot), lo, hi,
-                                             G, Cn, L, _ptr(feat), int(save_for_bwd), _stream()), self.h, "text_fwd_ranged")
-        self._txt_state = (tuple(ctx.shape), layout, eot) if save_for_bwd else None
-        return feat
+        ranges = _host_ranges(class_lo, class_hi, ctx.shape[0], layout.shape[0])
+        return self._text_fwd("text_fwd_ranged", prefix, suffix, ctx, layout, eot, save_for_bwd, ranges=ranges)
 
     def load_token_embedding(self, weight: torch.Tensor) -> None:
         """Opt-in: keep an fp32 copy of `token_embedding.weight` [vocab, text_width] on the device for text_encode_tokens
@@ -524,14 +508,24 @@ class Engine:
                    "text_workspace_bytes")
         return int(out.value)
 
+    def _text_bwd(self, who: str, dfeat: torch.Tensor, deep: bool) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        st = self._txt_state
+        if st is None or st.ctx_shape is None or (deep and not st.deep):
+            raise RuntimeError(f"{who} without {'text_fwd_deep' if deep else 'text_fwd'}(save_for_bwd=True) with context tokens")
+        dfeat = _req(dfeat, torch.float32, "dfeat")
+        dctx = torch.empty(st.ctx_shape, device=dfeat.device, dtype=torch.float32)
+        ddeep = torch.empty_like(st.ctx_deep) if deep and st.ctx_deep is not None else None
+        _lib.check(lib.mvlpt_text_bwd(self.h, _ptr(dfeat), _ptr(dctx), _ptr(ddeep), _stream()), self.h, who)
+        return dctx, ddeep
+
     @_on_device
     def text_bwd(self, dfeat: torch.Tensor) -> torch.Tensor:
-        if self._txt_state is None or self._txt_state[0] is None:
-            raise RuntimeError("text_bwd without text_fwd(save_for_bwd=True) with context tokens")
-        dfeat = _req(dfeat, torch.float32, "dfeat")
-        dctx = torch.empty(self._txt_state[0], device=dfeat.device, dtype=torch.float32)
-        _lib.check(lib.mvlpt_text_bwd(self.h, _ptr(dfeat), _ptr(dctx), _stream()), self.h, "text_bwd")
-        return dctx
+        return self._text_bwd("text_bwd", dfeat, False)[0]
+
+    @_on_device
+    def text_bwd_deep(self, dfeat: torch.Tensor) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """(dctx, dctx_deep) of the last text_fwd_deep(save_for_bwd=True); dctx_deep is None when that forward had no deep prompts."""
+        return self._text_bwd("text_bwd_deep", dfeat, True)
 
     # ------------------------------------------------------------------ head
     @_on_device

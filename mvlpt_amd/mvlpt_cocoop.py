@@ -10,7 +10,7 @@ What the route does (trainers/mvlpt.py:541-581): image tower (with visual prompt
 The reference runs one text tower per image in a Python loop and multiplies every logit outside the image's task by 0.  Here
 
 * under ``DATASET.MULTITASK_LABEL_PERTASK`` image b runs ONLY the sequences of its own task's class range [lo_b, hi_b)
-  (mvlpt_text_fwd_ranged / mvlpt_logits_ranged_fwd): a masked logit is exactly 0 and carries no gradient, so its sequence is never
+  (the ranged mvlpt_text_fwd / mvlpt_logits_ranged_fwd): a masked logit is exactly 0 and carries no gradient, so its sequence is never
   computed.  ``CustomCLIP.ranged_text = False`` runs every range full (B x n_cls sequences, CoCoOp's tower) and a multiplicative mask
   instead — the same logits, for comparison and as an escape hatch.  Without the per-task mask every range is [0, n_cls).
 * the batch is cut into chunks of consecutive images whose text tower fits ``max_text_workspace_bytes`` (sized over the chunk's OWN

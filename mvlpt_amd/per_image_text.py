@@ -1,6 +1,6 @@
 """What the models with one text context per image share: mvlpt_amd.cocoop.CustomCLIP, mvlpt_amd.mvlpt_cocoop.CustomCLIP and
 mvlpt_amd.tpt.CustomCLIP.  Image g brings its own context `ctx[g]` and a class range [lo_g, hi_g), so a batch is ONE ranged text tower
-over sum(hi - lo) sequences (mvlpt_text_fwd_ranged), cut into chunks of consecutive images whose workspace fits
+over sum(hi - lo) sequences (the ranged mvlpt_text_fwd), cut into chunks of consecutive images whose workspace fits
 `max_text_workspace_bytes`.  Here live the chunk planner, one chunk's tower (the only caller of Engine.text_fwd_ranged) and the loop
 of a forward that keeps nothing for a backward.  A forward that saves differs in what follows the tower (CoCoOp: loss and backward
 per chunk; the MVLPT route: logits now, backward later; TPT: the entropy head), so those three loops stay with their models, each

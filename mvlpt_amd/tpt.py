@@ -3,7 +3,7 @@
 Label-free and evaluation-only.  For every test image: V augmented views (view 0 the clean test view), the k most confident views
 are kept, STEPS AdamW steps on the image's OWN copy of the text context minimise the entropy of their averaged prediction, the image
 is classified with the tuned context, and the context is reset.  The published implementation tunes one image at a time; here a batch
-of G test images is ONE ranged text tower with `ctx [G, n_ctx, dt]` and every class range full (mvlpt_text_fwd_ranged, CoCoOp's
+of G test images is ONE ranged text tower with `ctx [G, n_ctx, dt]` and every class range full (the ranged mvlpt_text_fwd, CoCoOp's
 situation), followed by the fused entropy head (mvlpt_op_tpt_head_fwd / _bwd, csrc/tpt.hip).  AdamW on the flat [G, n_ctx, dt] tensor
 is element-wise, so G images tuned side by side are G independent TPT problems, and chunks of images (sized by the text-workspace
 planner CoCoOp uses) are exact.

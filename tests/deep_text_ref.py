@@ -1,4 +1,4 @@
-"""TEST-ONLY restatement of deep language prompting (TRAINER.MVLPT.COOP.N_DEEP, mvlpt_text_fwd_deep / mvlpt_text_bwd_deep) on the CPU.
+"""TEST-ONLY restatement of deep language prompting (TRAINER.MVLPT.COOP.N_DEEP, mvlpt_text_fwd / mvlpt_text_bwd with n_deep > 0) on the CPU.
 
 It composes oracle.clip_oracle's own functions (assemble_prompts, block_fwd / block_bwd, layernorm_*, logits_*, cross_entropy_fwd_bwd,
 the image encoder) with the two steps of the contract:

@@ -322,7 +322,7 @@ def test_settings_plan_and_consumed_state(small):
         # the saved state: still there after an un-checkpointed backward, consumed by a checkpointed one
         dctx = torch.full_like(d1, 7.0)
         with torch.cuda.device(eng.device):
-            rc = _lib.lib.mvlpt_text_bwd(eng.h, small.dfeat.data_ptr(), dctx.data_ptr(), None)
+            rc = _lib.lib.mvlpt_text_bwd(eng.h, small.dfeat.data_ptr(), dctx.data_ptr(), None, None)
         torch.cuda.synchronize()
         if at_fwd == 1:
             assert rc == 0 and torch.equal(dctx, d1)

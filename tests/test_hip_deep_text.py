@@ -1,4 +1,4 @@
-"""Deep language prompting on the HIP engine (-m gpu): mvlpt_text_fwd_deep / mvlpt_text_bwd_deep, Engine.text_fwd_deep / text_bwd_deep,
+"""Deep language prompting on the HIP engine (-m gpu): mvlpt_text_fwd / mvlpt_text_bwd with n_deep > 0, Engine.text_fwd_deep / text_bwd_deep,
 TRAINER.MVLPT.COOP.N_DEEP through CustomCLIP and the MVLPT trainer.
 
 Expected values are computed at test time on the CPU by tests/deep_text_ref.py, which composes oracle.clip_oracle's own functions with
@@ -215,10 +215,11 @@ def test_no_deep_prompts_has_the_bits_of_the_plain_entries(ref, clips, segments)
         f2, d2 = torch.empty_like(f0), torch.empty_like(d0)
         st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
         P = lambda t: C.c_void_p(t.data_ptr())
-        rc = _lib.lib.mvlpt_text_fwd_deep(eng.h, P(prefix), P(suffix), P(ctx), R.N_CTX, P(junk), 0, P(layout), P(eot), len(R.NAME_LENS), 77,
-                                          P(f2), 1, st)
+        job = _lib.MvlptTextJob(prefix=prefix.data_ptr(), suffix=suffix.data_ptr(), ctx=ctx.data_ptr(), n_ctx=R.N_CTX, ctx_deep=junk.data_ptr(),
+                                n_deep=0, layout=layout.data_ptr(), eot=eot.data_ptr(), n_cls=len(R.NAME_LENS), L=77, save_for_bwd=1)
+        rc = _lib.lib.mvlpt_text_fwd(eng.h, C.byref(job), P(f2), st)
         assert rc == 0, _lib.last_error(eng.h)
-        assert _lib.lib.mvlpt_text_bwd(eng.h, P(dfeat), P(d2), st) == 0, _lib.last_error(eng.h)
+        assert _lib.lib.mvlpt_text_bwd(eng.h, P(dfeat), P(d2), None, st) == 0, _lib.last_error(eng.h)
         torch.cuda.synchronize()
         assert torch.equal(f0, f2) and torch.equal(d0, d2)
     finally:
@@ -393,8 +394,10 @@ def test_c_level_refusals_leave_the_outputs_alone(ref, clips):
     lib = _lib.lib
 
     def fwd(ctx_, n_ctx, deep_, n_deep, suffix_=suffix, layout_=layout, save=1):
-        return lib.mvlpt_text_fwd_deep(eng.h, P(prefix), P(suffix_), P(ctx_), n_ctx, P(deep_), n_deep, P(layout_), P(eot), Cn, 77, P(feat),
-                                       save, st)
+        D = lambda t: None if t is None else t.data_ptr()
+        job = _lib.MvlptTextJob(prefix=D(prefix), suffix=D(suffix_), ctx=D(ctx_), n_ctx=n_ctx, ctx_deep=D(deep_), n_deep=n_deep,
+                                layout=D(layout_), eot=D(eot), n_cls=Cn, L=77, save_for_bwd=save)
+        return lib.mvlpt_text_fwd(eng.h, C.byref(job), P(feat), st)
 
     too_deep = torch.zeros(R.TEXT_LAYERS, R.N_CTX, R.TEXT_WIDTH, device=DEV)
     assert fwd(ctx, R.N_CTX, too_deep, R.TEXT_LAYERS) == _lib.ERR_ARG and "text_layers - 1" in _lib.last_error(eng.h)
@@ -405,21 +408,20 @@ def test_c_level_refusals_leave_the_outputs_alone(ref, clips):
     torch.cuda.synchronize()
     assert bool((feat == SENT).all()), "a refused forward wrote its output"
 
-    # the plain backward after a deep forward: a state error that names the entry to call; nothing is written
+    # the backward without dctx_deep after a deep forward (the plain and the deep backward are one entry): refused; nothing is written
     assert fwd(ctx, R.N_CTX, deep, 2) == 0, _lib.last_error(eng.h)
-    assert lib.mvlpt_text_bwd(eng.h, P(dfeat), P(dctx), st) == _lib.ERR_STATE and "mvlpt_text_bwd_deep" in _lib.last_error(eng.h)
-    assert lib.mvlpt_text_bwd_deep(eng.h, P(dfeat), P(dctx), None, st) == _lib.ERR_ARG and "dctx_deep is null" in _lib.last_error(eng.h)
+    assert lib.mvlpt_text_bwd(eng.h, P(dfeat), P(dctx), None, st) == _lib.ERR_ARG and "dctx_deep is null" in _lib.last_error(eng.h)
     torch.cuda.synchronize()
     assert bool((dctx == SENT).all()) and bool((ddeep == SENT).all()), "a refused backward wrote its outputs"
     # ... and the state is still good for the right call
-    assert lib.mvlpt_text_bwd_deep(eng.h, P(dfeat), P(dctx), P(ddeep), st) == 0, _lib.last_error(eng.h)
+    assert lib.mvlpt_text_bwd(eng.h, P(dfeat), P(dctx), P(ddeep), st) == 0, _lib.last_error(eng.h)
     torch.cuda.synchronize()
     want = ref.get(77, "end", 2)
     assert rel(dctx, want[2]) <= BAR and rel(ddeep, want[3]) <= BAR
 
-    # the deep backward after a plain forward accepts a null dctx_deep
+    # the backward after a plain forward takes a null dctx_deep
     plain = eng.text_fwd(prefix, suffix, ctx, layout, eot, save_for_bwd=True)
-    assert lib.mvlpt_text_bwd_deep(eng.h, P(dfeat), P(dctx), None, st) == 0, _lib.last_error(eng.h)
+    assert lib.mvlpt_text_bwd(eng.h, P(dfeat), P(dctx), None, st) == 0, _lib.last_error(eng.h)
     torch.cuda.synchronize()
     assert torch.equal(dctx, eng.text_bwd(dfeat))
     del plain

@@ -6,8 +6,10 @@ The calls go straight to `_lib.lib`: the Python `Engine` mirrors some of this st
 sees them.
 
 RECORDED sequences are expected to answer what the library answered before the records existed: tools/make_engine_state_golden.py ran
-them on that build and wrote tests/golden/engine_call_sequences.json (codes and error texts only).  BY_DESIGN sequences are those where
-that build was unsound (it ran a backward over buffers no forward had written), so their expectation is written down here, with the reason.
+them on that build and wrote tests/golden/engine_call_sequences.json (codes and error texts only; one answer was rewritten when the
+plain and the deep text backward became one entry, see text_deep_forward_needs_the_deep_backward).  BY_DESIGN sequences are those where
+that build was unsound (it ran a backward over buffers no forward had written) or whose calls its entries could not express (text jobs
+since MvlptTextJob), so their expectation is written down here, with the reason.
 
 Steps that are tuples check buffers between calls: ("keep", buffer, tag) remembers a copy, ("same", buffer, tag) compares with it bit
 for bit, ("fill_nan", buffer) / ("all_nan", buffer) bracket a call that must not launch, ("fresh", buffer) compares with the same
@@ -58,6 +60,7 @@ class Rig:
         eot = torch.tensor([N_CTX + 2 + k for k in name_lens], dtype=torch.int32, device=DEV)
         prefix, suffix = rnd(NC, 1, dt, scale=0.02), rnd(NC, L - 1 - N_CTX, dt, scale=0.02)
         ctx, ctx_long, ctx_deep = rnd(N_CTX, dt, scale=0.1), rnd(L - 1, dt, scale=0.1), rnd(N_DEEP, N_CTX, dt, scale=0.1)
+        ctx_csc, ctx_grp = rnd(NC, N_CTX, dt, scale=0.1), rnd(B, N_CTX, dt, scale=0.1)
         feat_t, dfeat_t = torch.zeros(NC, e, device=DEV), rnd(NC, e)
         dctx, dctx_deep = torch.zeros(N_CTX, dt, device=DEV), torch.zeros(N_DEEP, N_CTX, dt, device=DEV)
         ids = torch.randint(1, VOCAB - 1, (NC, L), generator=g, dtype=torch.int32)
@@ -69,7 +72,7 @@ class Rig:
         dimg, dtxt, dtxt_r = torch.zeros(B, e, device=DEV), torch.zeros(NC, e, device=DEV), torch.zeros(4, e, device=DEV)
         lo, hi, hi_bad = (C.c_int32 * B)(0, 1), (C.c_int32 * B)(2, 3), (C.c_int32 * B)(2, NC + 1)      # 2 + 2 = 4 text rows
         self.buffers = {"feat_i": feat_i, "dvpt": dvpt, "feat_t": feat_t, "dctx": dctx, "dctx_deep": dctx_deep}
-        self._alive = (image, vpt, bad_masks, dfeat_i, layout, eot, prefix, suffix, ctx, ctx_long, ctx_deep, dfeat_t, ids, img_f, txt_f,
+        self._alive = (image, vpt, bad_masks, dfeat_i, layout, eot, prefix, suffix, ctx, ctx_long, ctx_deep, ctx_csc, ctx_grp, dfeat_t, ids, img_f, txt_f,
                        txt_r, logits, dlogits, dimg, dtxt, dtxt_r, lo, hi, hi_bad)
         half = _lib.DT_F16
 
@@ -77,9 +80,12 @@ class Rig:
             return lambda: lib.mvlpt_image_fwd(h, _ptr(image), half, _ptr(vpt) if prompts else None, None, N_VPT if prompts else 0, 0, B,
                                                _ptr(feat_i), save, _stream())
 
-        def text_fwd(save, c=ctx, n=N_CTX):
-            return lambda: lib.mvlpt_text_fwd(h, _ptr(prefix), _ptr(suffix), _ptr(c), 0, n, _ptr(layout), _ptr(eot), NC, L, _ptr(feat_t), save,
-                                              _stream())
+        def text_fwd(save, c=ctx, n=N_CTX, **fields):
+            job = _lib.MvlptTextJob(prefix=prefix.data_ptr(), suffix=suffix.data_ptr(), ctx=c.data_ptr(), n_ctx=n, layout=layout.data_ptr(),
+                                    eot=eot.data_ptr(), n_cls=NC, L=L, save_for_bwd=save, **fields)
+            return lambda: lib.mvlpt_text_fwd(h, C.byref(job), _ptr(feat_t), _stream())
+
+        deep = dict(ctx_deep=ctx_deep.data_ptr(), n_deep=N_DEEP)
 
         self.calls = {
             "set_activation": lambda: lib.mvlpt_set_activation(h, _lib.ACT_QUICKGELU),
@@ -97,11 +103,14 @@ class Rig:
             "text_fwd": text_fwd(0),
             "text_fwd_save": text_fwd(1),
             "text_fwd_save_n_ctx_too_long": text_fwd(1, ctx_long, L - 1),
-            "text_fwd_deep_save": lambda: lib.mvlpt_text_fwd_deep(h, _ptr(prefix), _ptr(suffix), _ptr(ctx), N_CTX, _ptr(ctx_deep), N_DEEP,
-                                                                  _ptr(layout), _ptr(eot), NC, L, _ptr(feat_t), 1, _stream()),
+            "text_fwd_deep_save": text_fwd(1, **deep),
+            # jobs no earlier entry could express
+            "text_fwd_deep_ranged": text_fwd(1, ctx_grp, class_lo=lo, class_hi=hi, groups=B, **deep),
+            "text_fwd_deep_per_class": text_fwd(1, ctx_csc, ctx_per_class=1, **deep),
+            "text_fwd_lo_without_hi": text_fwd(1, ctx_grp, class_lo=lo, groups=B),
             "text_encode_tokens": lambda: lib.mvlpt_text_encode_tokens(h, C.c_void_p(ids.data_ptr()), L, NC, L, _ptr(feat_t), _stream()),
-            "text_bwd": lambda: lib.mvlpt_text_bwd(h, _ptr(dfeat_t), _ptr(dctx), _stream()),
-            "text_bwd_deep": lambda: lib.mvlpt_text_bwd_deep(h, _ptr(dfeat_t), _ptr(dctx), _ptr(dctx_deep), _stream()),
+            "text_bwd": lambda: lib.mvlpt_text_bwd(h, _ptr(dfeat_t), _ptr(dctx), None, _stream()),
+            "text_bwd_deep": lambda: lib.mvlpt_text_bwd(h, _ptr(dfeat_t), _ptr(dctx), _ptr(dctx_deep), _stream()),
             # head
             "logits_fwd": lambda: lib.mvlpt_logits_fwd(h, _ptr(img_f), _ptr(txt_f), 10.0, None, None, B, NC, _ptr(logits), _stream()),
             "logits_bwd": lambda: lib.mvlpt_logits_bwd(h, _ptr(dlogits), _ptr(dimg), _ptr(dtxt), _stream()),
@@ -169,6 +178,26 @@ BY_DESIGN = {
         "engine is as good as new afterwards",
         ["image_fwd_save"] + _REFUSED_FWD + ["image_fwd_save", ("fresh", "feat_i"), "image_bwd", ("fresh", "dvpt")],
         [0] + _REFUSED_FWD_ANSWERS + [0, 0]),
+    "C_text_jobs_no_earlier_entry_could_express": (
+        "refused for their fields before any engine state is touched: the saved forward in front of them keeps its backward, bit for bit",
+        ["text_fwd_save", "text_bwd", ("keep", "dctx", "saved"),
+         "text_fwd_deep_ranged", "text_bwd", ("same", "dctx", "saved"),
+         "text_fwd_deep_per_class", "text_bwd", ("same", "dctx", "saved"),
+         "text_fwd_lo_without_hi", "text_bwd", ("same", "dctx", "saved")],
+        [0, 0, (ERR_ARG, "not offered on the ranged tower"), 0, (ERR_ARG, "generic context"), 0, (ERR_ARG, "come together"), 0]),
+    "D_text_bwd_without_dctx_deep_after_a_deep_forward": (
+        "dctx_deep is required exactly when the saved forward ran deep prompts; the refusal launches nothing and the right call that "
+        "follows gives the gradients of a run without the refused call",
+        ["text_fwd_deep_save", "text_bwd_deep", ("keep", "dctx", "clean"), ("keep", "dctx_deep", "clean_deep"),
+         "text_fwd_deep_save", ("fill_nan", "dctx"), "text_bwd", ("all_nan", "dctx"),
+         "text_bwd_deep", ("same", "dctx", "clean"), ("same", "dctx_deep", "clean_deep")],
+        [0, 0, 0, (ERR_ARG, "dctx_deep is null after a forward with deep prompts"), 0]),
+    "E_text_bwd_with_dctx_deep_after_a_forward_without_deep_prompts": (
+        "dctx_deep must be null when the saved forward ran no deep prompts; as above",
+        ["text_fwd_save", "text_bwd", ("keep", "dctx", "clean"),
+         "text_fwd_save", ("fill_nan", "dctx"), ("fill_nan", "dctx_deep"), "text_bwd_deep", ("all_nan", "dctx"), ("all_nan", "dctx_deep"),
+         "text_bwd", ("same", "dctx", "clean")],
+        [0, 0, 0, (ERR_ARG, "dctx_deep is set after a forward without deep prompts"), 0]),
 }
 
 

@@ -356,12 +356,13 @@ def test_setter_and_forward_refuse_bad_lengths(tower):
         eng.set_text_grad_len(L + 1, 5)
     eot = tower.eot(7)                                    # max(eot) = 6
     feat = torch.full((CS, tower.arch.embed_dim), 7.0, device=DEV)
+    job = lib.MvlptTextJob(prefix=tower.prefix.data_ptr(), suffix=tower.suffix.data_ptr(), ctx=tower.ctx.data_ptr(), n_ctx=tower.n,
+                           layout=tower.layout.data_ptr(), eot=eot.data_ptr(), n_cls=CS, L=L, save_for_bwd=1)
     try:
         for grad_len in (6, 5, 3):                        # does not reach the largest EOT position
             eng.set_text_grad_len(grad_len, 6)
             with torch.cuda.device(eng.device):
-                rc = lib.lib.mvlpt_text_fwd(eng.h, _ptr(tower.prefix), _ptr(tower.suffix), _ptr(tower.ctx), 0, tower.n, _ptr(tower.layout),
-                                            _ptr(eot), CS, L, _ptr(feat), 1, None)
+                rc = lib.lib.mvlpt_text_fwd(eng.h, C.byref(job), _ptr(feat), None)
             torch.cuda.synchronize()
             assert rc == lib.ERR_ARG and "gradient length" in lib.last_error(eng.h), grad_len
             assert bool((feat == 7.0).all()), "a refused forward must not launch"

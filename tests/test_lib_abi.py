@@ -38,6 +38,20 @@ def test_python_binding_covers_header(lib_path):
     assert _lib.lib.mvlpt_version().decode().startswith("mvlpt_hip")
 
 
+def test_text_job_struct_matches_the_header(lib_path):
+    """MvlptTextJob crosses the boundary by layout: the binding has the header's size and the header's fields in the header's order."""
+    from mvlpt_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "mvlpt_hip.h")).read(), flags=re.S)
+    size = int(re.search(r"#define\s+MVLPT_TEXT_JOB_BYTES\s+(\d+)", src).group(1))
+    assert ctypes.sizeof(_lib.MvlptTextJob) == size == _lib.TEXT_JOB_BYTES
+    body = re.search(r"typedef struct MvlptTextJob \{(.*?)\} MvlptTextJob;", src, flags=re.S).group(1)
+    fields = re.findall(r"(\w+)\s*;", body)
+    assert fields == [n for n, _ in _lib.MvlptTextJob._fields_]
+    # pointers first, then 32-bit integers: no implicit padding
+    pointers = [n for n in fields if re.search(r"\*\s*" + n + r"\s*;", body)]
+    assert fields[:len(pointers)] == pointers and size == 8 * len(pointers) + 4 * (len(fields) - len(pointers))
+
+
 def test_create_fails_loudly_without_gpu(lib_path):
     """No CPU fallback: on a box without a HIP device the handle cannot even be created."""
     import torch
